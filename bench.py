@@ -12,9 +12,18 @@ A "step" is one frame = one primary sample per pixel through the whole hot path 
 replay per pass; each frame keeps its own frame number and RNG streams and the result is bit-identical to rendering them
 one by one); exactly K frames are timed.  plan_schedule() chooses the pass size from measurements: a budget that fits the
 queues (up to 128 full frames' worth of paths) is ONE pass, a longer one is a sequence of --frames-per-pass (64) frame
-passes, four in flight.  The K-frame region is timed --reps times, each bracketed by a barrier + device synchronisation,
-and the MEDIAN is reported (`steps` stays K, `ms_per_step` = median / K; every repetition is listed in `config.rep_ms`):
-at the driver's K = 20 a region is one 24 ms graph replay, and single replays vary by several per cent.  Phase stamps go
+passes, four in flight.  The K-frame region is timed --reps times (default 1; --full: 5), each bracketed by a barrier +
+device synchronisation, and the MEDIAN is reported (`steps` stays K, `ms_per_step` = median / K; every repetition is listed
+in `config.rep_ms`): at the driver's K = 20 a region is one 24 ms graph replay, and single replays vary by several per cent.
+
+A plain run sets up, warms up, times the region and prints the line.  --full adds everything else the benchmark measures
+or checks, as separate work after the headline: the .obj round trip of config 2, the reference-mode measurement, the
+roofline, the CPU baseline and, on N > 1 GPUs, the strong-scaling region and the 1-GPU figure inside the job (each can still
+be switched off with its --no-... option).  --dump-outputs DIR writes what the timed region's last step left for a caller,
+in image order (pixel y * width + x, row 0 at the bottom of the view): DIR/accumulation.npy (float32 [height][width][3],
+the running mean of radiance) and DIR/rgba8.npy (float32 [height][width][4], the tonemapped 8-bit image); beyond 64 MB in
+all, the same fixed, seeded sample of pixels of both (DIR/pixel_index.npy, float64).  The scene is seeded and the RNG
+pixel-keyed: the same arguments give the same outputs.  Phase stamps go
 to stderr, and a watchdog dumps the Python stacks if a phase takes longer than NX_BENCH_WATCHDOG (150) seconds.  Msamples/s is the reference viewer's
 "Megarays/sec": width * height * frames / seconds / 1e6 (/root/reference/Nexus/src/Renderer/Panels/MetricsPanel.cpp:28,35,56).
 Scene and BVH live in HBM before the timed region starts.  N > 1: the frame is cut into interleaved 5-row tiles, every
@@ -24,7 +33,7 @@ bit-identical to the 1-GPU one.  A step on N GPUs is one frame PER GPU (--scalin
 work, K steps = K x N frames, all counted in `value`) or one frame in total (--scaling strong); a weak run on N > 1 GPUs reports the
 strong region too (config.strong_scaling).
 
-Rank 0 prints ONE JSON line.  It also carries
+Rank 0 prints ONE JSON line.  With --full it also carries
   roofline     : the closest-hit trace kernel against the three ceilings that could bind it, all from live launch durations
                  (hipEvents recorded by event nodes around every kernel node of the production hipGraph; every repetition of the
                  timed region is replayed on its own frame numbers and the block is computed from the MEDIAN repetition's
@@ -49,7 +58,7 @@ Rank 0 prints ONE JSON line.  It also carries
                  item: HBM-side bytes and VALU instructions from the same committed counter passes, against 8 TB/s and the issue rate.
   cpu_baseline : the CPU oracle (port of the reference algorithm) on full frames of the same scene, timed on the
                  host cores of this box (trace, logic and shade threaded).  A reported baseline, not a target.
-  emulated_rank (--emulate-rank-of N): rank 0's share of an N-way tile split rendered in this process, against full / N.
+  emulated_rank (--emulate-rank-of N, with or without --full): rank 0's share of an N-way tile split rendered in this process, against full / N.
 Counter constants carry the hash of the kernel sources they were measured on; a mismatch reports `traffic: null` and why.
 """
 import argparse
@@ -222,6 +231,31 @@ def cpu_baseline(sc, width, height, threads, frames, single_core=True):
     return out
 
 
+DUMP_BUDGET_BYTES = 64 * 10**6  # --dump-outputs: at most this much in all
+DUMP_SAMPLE_SEED = 20260916     # the fixed pixel sample of an image whose outputs exceed the budget
+
+
+def dump_outputs(directory, arrays, width, height):
+    """--dump-outputs: `arrays` maps a name to a float32 [width * height][channels] array in image order; each is written as
+    DIR/<name>.npy, [height][width][channels].  If together they exceed DUMP_BUDGET_BYTES, the same fixed, seeded sample of
+    pixels is written of each ([pixels][channels]), and its sorted pixel indices as DIR/pixel_index.npy (float64)."""
+    os.makedirs(directory, exist_ok=True)
+    n = width * height
+    per_pixel = sum(a.dtype.itemsize * a.shape[1] for a in arrays.values())
+    index_file = os.path.join(directory, "pixel_index.npy")
+    if n * per_pixel <= DUMP_BUDGET_BYTES:
+        if os.path.exists(index_file):
+            os.remove(index_file)  # (left by an earlier, larger dump into the same directory)
+        for name, a in arrays.items():
+            np.save(os.path.join(directory, name + ".npy"), a.reshape(height, width, a.shape[1]))
+        return
+    k = DUMP_BUDGET_BYTES // (per_pixel + 8)
+    idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, size=k, replace=False))
+    np.save(index_file, idx.astype(np.float64))
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a[idx])
+
+
 _T0 = time.time()
 _WATCHDOG_S = float(os.environ.get("NX_BENCH_WATCHDOG", "150"))
 
@@ -264,7 +298,15 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=None, help="frames timed per repetition (default 512; --config 5: 64)")
     ap.add_argument("--warmup", type=int, default=None, help="untimed frames first (default 64; --config 5: 16)")
-    ap.add_argument("--reps", type=int, default=5, help="repetitions of the K-frame timed region; the median is reported")
+    ap.add_argument("--reps", type=int, default=None, help="repetitions of the K-frame timed region; the median is reported (default 1; --full: 5)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, everything else the benchmark measures or checks: the .obj round trip (config 2), the reference-mode measurement, "
+                         "the roofline, the CPU baseline, on N > 1 GPUs the strong-scaling region and the 1-GPU figure inside the job (each still subject to its "
+                         "--no-... option).  Without it a run sets up, warms up, times the K steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed region, write what its last step left for a caller (rank 0, image order): DIR/accumulation.npy (float32 "
+                         "[height][width][3]) and DIR/rgba8.npy (float32 [height][width][4]); beyond 64 MB in all, a fixed seeded sample of pixels "
+                         "of both (DIR/pixel_index.npy)")
     ap.add_argument("--config", type=int, default=2, help="1 = configs[0] (the reference's Cornell box, 512x512, pathLength 4, diffuse only; the CPU baseline adds the BVH2 path); 2 = BASELINE.json configs[1] (the metric's workload); 4 = configs[3] (instanced TLAS, dielectric, environment NEE / MIS); 5 = configs[4] on one GPU (HBM-resident scene)")
     ap.add_argument("--width", type=int, default=None)
     ap.add_argument("--height", type=int, default=None)
@@ -314,6 +356,7 @@ def main():
     args.path_length = args.path_length or (16 if big else 4 if cornell else 8)
     args.steps = args.steps if args.steps is not None else (64 if big else 512)
     args.warmup = args.warmup if args.warmup is not None else (16 if big else 64)
+    args.reps = args.reps if args.reps is not None else (5 if args.full else 1)
 
     # stdout carries exactly one line, the JSON: libraries that print banners to stdout (RCCL does at init) are sent to stderr
     json_fd = os.dup(1)
@@ -372,7 +415,7 @@ def main():
     sc, workload_name, t_build = build_workload(args)
     stamp("scene built on the host (%.1f s)" % t_build)
     obj_check = None
-    if args.config == 2 and not args.no_obj_check and rank == 0:
+    if args.config == 2 and args.full and not args.no_obj_check and rank == 0:
         # (rank 0 only: eight ranks writing and reading a 120 MB file at once is 8 x 3 s of host work and file I/O in front of the
         #  first barrier for a check whose answer does not depend on the rank)
         obj_check = workloads.check_obj_round_trip(sc)
@@ -534,6 +577,21 @@ def main():
     # one step = one frame; a pass renders up to S frames
     rep_s = measure(n_frames, n_warm, args.reps, S, "timed region")
     elapsed = statistics.median(rep_s)
+    if args.dump_outputs and rank == 0:
+        # what the timed region's last step left for a caller: the accumulated image (running mean of radiance) and its RGBA8
+        # tonemap, in image order (a single context returns them in its path order; rank 0 of N > 1 holds the composed image)
+        if dist_mode:
+            acc = full_acc[:, :3].cpu().numpy()
+            rgba = full_rgba.cpu().numpy().view(np.uint32)
+        else:
+            acc, rgba = ctx.read_accumulation(), ctx.read_rgba8()
+            if args.pixel_order == "tiles":
+                order = multigpu.tiled_order(np.arange(W * H, dtype=np.uint32), W)
+                acc_img, rgba_img = np.zeros_like(acc), np.zeros_like(rgba)
+                acc_img[order], rgba_img[order] = acc, rgba
+                acc, rgba = acc_img, rgba_img
+        dump_outputs(args.dump_outputs, {"accumulation": acc.astype(np.float32), "rgba8": rgba.view(np.uint8).reshape(-1, 4).astype(np.float32)}, W, H)
+        stamp("outputs of the last step written to %s" % args.dump_outputs)
     if os.environ.get("NX_WAVE_TIMELINE_OUT"):
         # measurement builds only (tools/build_variant.sh ... -DNX_WAVE_TIMELINE): every trace wave's start / queue-dry / end times of
         # the last pass, [any-hit][bounce][wave][5] uint64, for tools/wave_timeline.py
@@ -551,7 +609,7 @@ def main():
 
     # a weak-scaling run on N > 1 GPUs also times the strong-scaling region — K frames in total, tile-split — as a second figure
     strong = None
-    if dist_mode and world > 1 and F > 1:
+    if args.full and dist_mode and world > 1 and F > 1:
         S_strong, _, _ = plan_schedule(args.steps, cap, 1, explicit_fpp, 1.0 / world, W * H)
         ss = measure(args.steps, args.warmup, 3, S_strong, "strong-scaling region")
         med = statistics.median(ss)
@@ -599,7 +657,7 @@ def main():
     # configuration renders at (`reference`: conductor hits end unshaded, as the reference's commented-out kernel leaves them)
     reference_mode = None
     headline_rgba8 = ctx.read_rgba8() if (args.png and not dist_mode) else None  # (--png shows the headline's image, not the second measurement's)
-    if not args.no_reference_mode and not dist_mode:
+    if args.full and not args.no_reference_mode and not dist_mode:
         reference_mode = {"what": "the timed region again (median of 3 repetitions) with random numbers keyed by queue slot and slots in the reference's serial order "
                                   "(NX_RNG_REFERENCE_SLOT, NX_COMPACT_ORDERED: tiles by ticket + decoupled look-back on all CUs); `reference` also drops the conductor kernel "
                                   "(NX_CONDUCTOR_REFERENCE), i.e. less work per frame than the headline; `ordered` keeps it (same work)"}
@@ -665,7 +723,7 @@ def main():
         # ... and the same K steps on ONE GPU inside this job (rank 0 alone, full frame, the others wait at a barrier), so that
         # the line carries its own denominator: efficiency = value_N / (N x value_1)
         single = None
-        if rank == 0:
+        if rank == 0 and args.full:
             ctx.sync()
             full_map = multigpu.tiled_order(np.arange(W * H, dtype=np.uint32), W) if args.pixel_order == "tiles" else None
             S1, _, _ = plan_schedule(args.steps, max(1, min(args.frames_per_pass or (16 if big else 64), 512)), 1, explicit_fpp, 1.0, W * H)
@@ -714,7 +772,7 @@ def main():
 
     # ---- roofline of the dominant kernel (closest-hit trace), on rank 0: at N > 1 these are rank 0's launches on ITS tiles (rays per
     # launch, durations, fractions per GPU); the section runs no collective, the other ranks wait at the closing barrier
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         stamp("roofline: in-graph kernel timing over the frames of the timed repetitions + counting variant on the median one")
         if ctx.frames_per_pass != S:
             ctx.set_frames_per_pass(S)
@@ -892,7 +950,7 @@ def main():
             classes[klass] = e
         rf["classes"] = classes
 
-    if rank == 0 and not dist_mode and not args.no_cpu_baseline:
+    if rank == 0 and not dist_mode and args.full and not args.no_cpu_baseline:
         # a 1-GPU box's CPU share is 16 hardware threads
         stamp("cpu baseline (oracle on the host cores)")
         threads = max(1, min(16, len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)))

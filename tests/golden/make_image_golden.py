@@ -1,13 +1,18 @@
 """Writes tests/golden/images/: small JPEG files of every kind the product's decoder supports (Pillow / libjpeg is only the
 ENCODER here; it is not needed to run the tests) and, beside them, what the reference's own decoder makes of each —
 stb_image through stbi_load_from_memory(..., 4), built from the reference's vendored header by `make -C oracle ref`
-(oracle/stb_ref.c) — as images_golden.npz.  Run in the build container (needs /root/reference for the reference build):
+(oracle/stb_ref.c) — as images_golden.npz; then stb_image's result on every file tests/test_image_decoders.py decodes (the
+fixtures, generated PNG / HDR files and damaged copies) as stb_results.npz: per input the first 16 bytes of the SHA-256 of its
+bytes, the height / width / channel count (height -1: refused) and the first 16 bytes of the SHA-256 of its RGBA8 pixels.
+Where the reference build can be made (`make -C oracle ref`):
 
-    make -C oracle ref && python tests/golden/make_image_golden.py
+    make -C oracle ref && python tests/golden/make_image_golden.py        # both files
+    make -C oracle ref && python tests/golden/make_image_golden.py stb    # stb_results.npz only (no Pillow needed)
 """
 import ctypes as C
 import io
 import os
+import sys
 
 import numpy as np
 
@@ -95,7 +100,27 @@ def main():
         golden[name + "__channels"] = np.int32(r[1])
         print("%-36s %6d bytes  %dx%d  channels %d" % (name, len(data), r[0].shape[1], r[0].shape[0], r[1]))
     np.savez_compressed(os.path.join(HERE, "images_golden.npz"), **golden)
+    write_stb_results()
+
+
+def write_stb_results():
+    sys.path.insert(0, os.path.join(HERE, "..", ".."))
+    from tests.test_image_decoders import _digest, result_of, stb_inputs
+
+    rows = {}
+    for data in stb_inputs():
+        r = result_of(stb_decode(data))
+        rows[_digest(data)] = ((-1, -1, -1), bytes(16)) if r is None else ((r[0][0], r[0][1], r[1]), r[2])
+    keys = sorted(rows)
+    np.savez_compressed(os.path.join(HERE, "stb_results.npz"),
+                        inputs=np.frombuffer(b"".join(keys), np.uint8).reshape(-1, 16),
+                        shapes=np.array([rows[k][0] for k in keys], np.int32),
+                        pixels=np.frombuffer(b"".join(rows[k][1] for k in keys), np.uint8).reshape(-1, 16))
+    print("stb_results.npz: %d inputs, %d refused" % (len(keys), sum(rows[k][0][0] < 0 for k in keys)))
 
 
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["stb"]:
+        write_stb_results()
+    else:
+        main()

@@ -63,7 +63,7 @@ def test_bench_two_ranks_on_one_gpu_render_the_single_rank_image(tmp_path):
     import json
 
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", OMP_NUM_THREADS="1", NX_BENCH_BACKEND="gloo", NX_BENCH_SHARE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    size = ["--reps", "1", "--frames-per-pass", "2", "--width", "256", "--height", "160", "--no-cpu-baseline"]
+    size = ["--reps", "1", "--frames-per-pass", "2", "--width", "256", "--height", "160", "--no-cpu-baseline", "--full"]
     k5, k10 = ["--steps", "5", "--warmup", "2"], ["--steps", "10", "--warmup", "4"]
 
     def run(cmd_prefix, extra, png):
@@ -160,7 +160,7 @@ def test_bench_four_ranks_on_one_gpu_render_the_single_rank_image(tmp_path):
     import json
 
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", OMP_NUM_THREADS="1", NX_BENCH_BACKEND="gloo", NX_BENCH_SHARE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    size = ["--reps", "1", "--frames-per-pass", "2", "--width", "320", "--height", "200", "--no-cpu-baseline", "--no-roofline", "--no-obj-check"]
+    size = ["--reps", "1", "--frames-per-pass", "2", "--width", "320", "--height", "200", "--no-cpu-baseline", "--no-roofline", "--no-obj-check", "--full"]
     k3, k12 = ["--steps", "3", "--warmup", "1"], ["--steps", "12", "--warmup", "4"]
 
     def run(cmd_prefix, extra, png):

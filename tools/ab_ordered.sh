@@ -8,7 +8,7 @@ mkdir -p $OUT
 lib_of() { if [ "$1" = main ]; then echo nexus_amd/lib/libnexus_amd.so; else echo nexus_amd/lib/variants/lib_$1.so; fi; }
 for r in $(seq 1 $ROUNDS); do
   for tag in "$@"; do
-    NEXUS_AMD_LIB=$(lib_of $tag) timeout -k 10 300 python bench.py $ARGS --no-cpu-baseline --no-obj-check --no-roofline > $OUT/${tag}_$r.json 2> $OUT/${tag}_$r.err || { echo "bench failed: $tag"; tail -3 $OUT/${tag}_$r.err; exit 1; }
+    NEXUS_AMD_LIB=$(lib_of $tag) timeout -k 10 300 python bench.py --full $ARGS --no-cpu-baseline --no-obj-check --no-roofline > $OUT/${tag}_$r.json 2> $OUT/${tag}_$r.err || { echo "bench failed: $tag"; tail -3 $OUT/${tag}_$r.err; exit 1; }
   done
 done
 python - "$OUT" "$ROUNDS" "$@" <<'PY'

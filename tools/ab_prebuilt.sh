@@ -12,7 +12,7 @@ lib_of() { local t=${1%%+*}; if [ "$t" = main ]; then echo nexus_amd/lib/libnexu
 env_of() { case "$1" in *+*) echo "NX_TUNING_KNOBS=1 ${1#*+}" | tr '+' ' ';; esac; }
 for r in $(seq 1 $ROUNDS); do
   for tag in "$@"; do
-    env $(env_of $tag) NEXUS_AMD_LIB=$(lib_of $tag) timeout -k 10 200 python bench.py $ARGS --no-cpu-baseline --no-obj-check > $OUT/${tag}_$r.json 2> $OUT/${tag}_$r.err || { echo "bench failed: $tag"; tail -3 $OUT/${tag}_$r.err; exit 1; }
+    env $(env_of $tag) NEXUS_AMD_LIB=$(lib_of $tag) timeout -k 10 200 python bench.py --full $ARGS --no-cpu-baseline --no-obj-check > $OUT/${tag}_$r.json 2> $OUT/${tag}_$r.err || { echo "bench failed: $tag"; tail -3 $OUT/${tag}_$r.err; exit 1; }
   done
 done
 python - "$OUT" "$ROUNDS" "$@" <<'PY'

@@ -48,7 +48,7 @@ def main():
             lines[mode] = json.loads(r.stdout.strip().splitlines()[-1])
             open(os.path.join(args.out, "facade_%s.json" % mode), "w").write(json.dumps(lines[mode]) + "\n")
             print("[facade %6.1f s] %s: %.1f Msamples/s" % (time.time() - t0, mode, lines[mode]["value"]), file=sys.stderr)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(args.steps), "--warmup", str(args.warmup), "--no-cpu-baseline", "--no-obj-check"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(args.steps), "--warmup", str(args.warmup), "--full", "--no-cpu-baseline", "--no-obj-check"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT)
     if r.returncode != 0:
         print(r.stderr[-2000:], file=sys.stderr)

@@ -8,7 +8,7 @@ i=0
 while read -r line; do
   [ -z "$line" ] && continue
   i=$((i+1))
-  timeout -k 10 200 rocprofv3 --kernel-trace --pmc $line --output-format csv -d $out/pass$i -- python bench.py "$@" --no-cpu-baseline --no-roofline --no-reference-mode > $out/pass$i.json 2> $out/pass$i.err
+  timeout -k 10 200 rocprofv3 --kernel-trace --pmc $line --output-format csv -d $out/pass$i -- python bench.py --full "$@" --no-cpu-baseline --no-roofline --no-reference-mode > $out/pass$i.json 2> $out/pass$i.err
   rc=$?
   echo "pass$i ($line) exit=$rc"
   [ $rc -ne 0 ] && exit $rc

@@ -13,8 +13,8 @@ cd /tmp && export TMPDIR=/tmp && cd "$root"
 # (otherwise profiled runs with passes in flight get the runtime's 4 queues and do not show the schedule the plain bench measures)
 export GPU_MAX_HW_QUEUES=${GPU_MAX_HW_QUEUES:-24}
 O=gpurun_out/prof_$tag; mkdir -p $O
-timeout -k 10 600 python bench.py --config $cfg "$@" > $O/bench_line.json 2> $O/bench_line.err || { tail -5 $O/bench_line.err; exit 1; }
-timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python bench.py --config $cfg "$@" --reps 1 --no-cpu-baseline --no-obj-check --no-reference-mode > $O/bench_under_rocprof.json 2> $O/stats.err || { tail -5 $O/stats.err; exit 1; }
+timeout -k 10 600 python bench.py --full --config $cfg "$@" > $O/bench_line.json 2> $O/bench_line.err || { tail -5 $O/bench_line.err; exit 1; }
+timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python bench.py --full --config $cfg "$@" --reps 1 --no-cpu-baseline --no-obj-check --no-reference-mode > $O/bench_under_rocprof.json 2> $O/stats.err || { tail -5 $O/stats.err; exit 1; }
 cp $(find $O/stats -name "*kernel_stats.csv" | head -1) $O/kernel_stats.csv
 python tools/level_timeline.py $O/stats 2 > $O/pass_timeline.txt 2>/dev/null
 i=0
