@@ -108,13 +108,12 @@ struct PassSlot {
     uint32_t* hostError = nullptr;
     bool errorFresh = false;
     size_t pathCapacity = 0;  // paths this slot's queue buffers hold right now; 0: released (nxhip_ctx::queueCapacity is the nominal size)
-    // Instances of the pass graph, one per SHAPE it has been asked for (see serial_shade, trace_blocks, tail_bounce in
+    // Instances of the pass graph, one per SHAPE it has been asked for (see trace_blocks, tail_bounce, pass_flavor in
     // nxhip_api.hip: a small pass, a large pass and a pass among several in flight are different graphs).  A pass of another
     // size class replays the instance built for that class instead of re-instantiating one inside the frame loop.
     struct GraphInstance {
         hipGraph_t graph = nullptr;
         hipGraphExec_t exec = nullptr;
-        bool serialShade = false;
         int traceBlocks = 0, tailBounce = 0;
         int flavor = 0;  // pass_flavor(): pipeline, miss kernel, logic kernel variant
     };
@@ -208,19 +207,11 @@ struct nxhip_ctx : nxd::PassSlot {
     int tailBounce = -1;  // first bounce of the tail kernel, 0 = off, -1 = automatic (see tail_bounce in nxhip_api.hip)
     bool traceGridForced = false;                            // NX_TRACE_BLOCKS_*: use them as they are
     int shadeBlocksPerCU = 10, logicBlocksPerCU = 2;  // grid-stride kernels: workgroups per CU
-    bool serialShade = false;  // the four material kernels of a bounce as one graph branch instead of four
-    int parallelShade = -1;    // NX_SHADE_PARALLEL (tuning experiments only): 1 = parallel branches whatever the pass size
     // material types the scene's materials use (bit NX_MAT_*): a type no material has can never receive a queue item, so its
     // kernel is left out of the pass graph (a launch on the critical path of every bounce, however empty)
     uint32_t materialTypeMask = 0xfu;
-    // NX_TUNING_KNOBS=1 NX_PIPELINE_CLASSIC=1 (measurement only): the logic kernel + material queues also under fast compaction
-    bool classicPipeline = false;
-    bool thinInFlight = false;  // NX_THIN_IN_FLIGHT (NX_TUNING_KNOBS): the thin level also when several passes are in flight
     bool thinInHooks = false;  // nxhip_debug_set_thin: the ray-batch hooks hand over and launch the thin kernel too
-    bool thinJoint = false;  // NX_THIN_JOINT=1 (measurement only): one thin launch per level instead of one per trace launch
-    bool thinWaves = true;  // the trace launches of a pass finish the last long rays of a dry wave cooperatively (NX_NO_THIN=1 with NX_TUNING_KNOBS=1: off)
     bool dead = false;          // nxhip_sync_timeout gave up: no further device work is issued or waited for
     int pixelOrder = 0;         // nxhip_set_pixel_order: NXHIP_ORDER_* of the full frame, re-applied by nxhip_resize (a caller's own map is not)
     bool entryPoints = false;   // nxhip_set_entry_points (the tables: PassSlot::entryTable, one per slot)
-    bool scanSeparate = false;  // NX_SCAN_SEPARATE=1 (measurement only): one material launch per type instead of one for all
 };

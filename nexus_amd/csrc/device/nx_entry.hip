@@ -135,9 +135,6 @@ NXD bool bundle_child_trace(const Bundle& b, const NX_G uint4* node, const uint3
                                   p[2] + scale[2] * (double)((qhiz >> (8 * j)) & 0xffu)};
             if (hi[0] < lo[0] || hi[1] < lo[1] || hi[2] < lo[2]) return false;  // (an inverted slot: leave it to the kernel's own arithmetic)
             const int c = classify(b, lo, hi);
-#ifdef NX_ENTRY_DEBUG
-            if (blockIdx.x * blockDim.x + threadIdx.x == NX_ENTRY_DEBUG) printf("child %d.%d bits %u class %d box [%g %g %g] [%g %g %g]\n", i, j, childBits, c, lo[0], lo[1], lo[2], hi[0], hi[1], hi[2]);
-#endif
             if (c == kUndecided) return false;
             if (c == kHitAll) hitMask |= childBits << bitIndex;
         }

@@ -172,7 +172,7 @@ struct Bvh2 {
     int* count;    // [n-1] primitives under the internal node
     Box3* box;     // [2n-1]
     int* arrived;  // [n-1]
-    struct Eval* eval;  // [7 (n-1)] cost table of the collapse (internal nodes; a leaf's entries follow from its box), or nullptr
+    struct Eval* eval;  // [7 (n-1)] cost table of the collapse (internal nodes; a leaf's entries follow from its box)
     float primCost;     // the collapse's cost of testing one primitive of a leaf slot, relative to one node test
 };
 
@@ -868,8 +868,7 @@ __device__ __forceinline__ bool is_inner(const Bvh2& t, const int n, const int c
 {
     if (c >= n - 1) return false;
     if (t.count[c] > kLeafMax) return true;  // (whatever the table says: a leaf slot cannot hold more)
-    if (t.eval) return eval_of(t, n, c, 0, false).decision == kDecInternal;
-    return false;
+    return eval_of(t, n, c, 0, false).decision == kDecInternal;
 }
 
 // meshCounters: per mesh {nodes used, prims used}; workCounter: work items of the next level.  meshes == nullptr: one mesh, whose
@@ -886,43 +885,23 @@ __global__ void __launch_bounds__(kBlock) collapse_level_kernel(const Bvh2 t, co
         uint32_t* const counters = meshCounters + 2 * (size_t)mesh;
         int child[8];
         int count = 0;
-        if (t.eval) {
-            // the children the cost table chose (Collapse.cpp GatherChildren): follow the "distribute" decisions down from
-            // entry 0 of this node; whatever is reached with another decision is a child
-            int todoNode[8], todoIdx[8], top = 0;
-            todoNode[top] = item.bvh2Node;
-            todoIdx[top++] = 0;
-            while (top > 0) {
-                const int x = todoNode[--top];
-                const Eval e = eval_of(t, n, x, todoIdx[top], false);
-                const int side[2] = {t.left[x], t.right[x]}, sideIdx[2] = {e.leftCount, e.rightCount};
-                for (int h = 0; h < 2; h++) {
-                    if (eval_of(t, n, side[h], sideIdx[h], false).decision == kDecDistribute && top < 8) {
-                        todoNode[top] = side[h];
-                        todoIdx[top++] = sideIdx[h];
-                    } else if (count < 8) {
-                        child[count++] = side[h];
-                    }
+        // the children the cost table chose (Collapse.cpp GatherChildren): follow the "distribute" decisions down from
+        // entry 0 of this node; whatever is reached with another decision is a child
+        int todoNode[8], todoIdx[8], top = 0;
+        todoNode[top] = item.bvh2Node;
+        todoIdx[top++] = 0;
+        while (top > 0) {
+            const int x = todoNode[--top];
+            const Eval e = eval_of(t, n, x, todoIdx[top], false);
+            const int side[2] = {t.left[x], t.right[x]}, sideIdx[2] = {e.leftCount, e.rightCount};
+            for (int h = 0; h < 2; h++) {
+                if (eval_of(t, n, side[h], sideIdx[h], false).decision == kDecDistribute && top < 8) {
+                    todoNode[top] = side[h];
+                    todoIdx[top++] = sideIdx[h];
+                } else if (count < 8) {
+                    child[count++] = side[h];
                 }
             }
-        } else {
-            count = 2;
-            child[0] = t.left[item.bvh2Node];
-            child[1] = t.right[item.bvh2Node];
-        }
-        // without a cost table: open children by largest area until eight (a BVH2 leaf, one triangle, cannot be opened)
-        while (!t.eval && count < 8) {
-            int best = -1;
-            float bestArea = -1.0f;
-            for (int k = 0; k < count; k++) {
-                if (child[k] >= n - 1) continue;
-                const float a = half_area(t.box[child[k]]);
-                if (a > bestArea) { bestArea = a; best = k; }
-            }
-            if (best < 0) break;
-            const int open = child[best];
-            child[best] = t.left[open];
-            child[count++] = t.right[open];
         }
         const Box3 nb = t.box[item.bvh2Node];
         // octant slots: the reference's greedy assignment (BVH8Builder.cpp:170-252) — repeatedly the (child, slot) pair with the
@@ -1423,18 +1402,11 @@ static int lbvh_from_boxes(nxhip_ctx* c, const DevBuf& triBox, const DevBuf& bou
     }
 
     // which subtrees become wide nodes, which leaf slots: the cost table of the SAH collapse, bottom-up over the finished tree
-    // (NX_DEVICE_COLLAPSE=greedy with NX_TUNING_KNOBS=1: the round-2 rule instead — open the largest child until there are eight,
-    // subtrees of at most three primitives become leaf slots — kept for the quality comparison of tools/builder_quality.py)
     DevBuf evals;
-    bool greedy = false;
-    if (const char* on = std::getenv("NX_TUNING_KNOBS"); on && std::atoi(on) == 1)
-        if (const char* e = std::getenv("NX_DEVICE_COLLAPSE")) greedy = std::strcmp(e, "greedy") == 0;
-    if (!greedy) {
-        if (!evals.alloc(inner * 7 * sizeof(Eval))) return NXHIP_ERR_HIP;
-        t.eval = evals.as<Eval>();
-        NX_HIP(hipMemsetAsync(arrived.p, 0, inner * 4, st));
-        cost_kernel<<<grid_for(n, cus), kBlock, 0, st>>>((int)n, t);
-    }
+    if (!evals.alloc(inner * 7 * sizeof(Eval))) return NXHIP_ERR_HIP;
+    t.eval = evals.as<Eval>();
+    NX_HIP(hipMemsetAsync(arrived.p, 0, inner * 4, st));
+    cost_kernel<<<grid_for(n, cus), kBlock, 0, st>>>((int)n, t);
 
     // collapse.  Every BVH8 node but the root stands for a distinct internal BVH2 node, so n - 1 nodes cannot be exceeded
     // (typical use: 0.1 - 0.2 n); the caller shrinks the array to the used size.

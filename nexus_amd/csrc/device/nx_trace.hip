@@ -38,13 +38,10 @@ namespace nxd {
 #define NX_RESERVE 512
 #endif
 // most rays one fetch atomic reserves.  Rounds 1-4: a block per WAVE, 256 (measured on large queues: 128 -3 %, 512 -1 %, 1024 -8 %).
-// Round 5: a block per WORKGROUP (NX_WG_RANGE, below), whose four waves share it: 512 (128: -2.7 %, 256: -1 %, 1024: =)
+// Round 5: a block per WORKGROUP (sRange, below), whose four waves share it: 512 (128: -2.7 %, 256: -1 %, 1024: =)
 constexpr int kReserve = NX_RESERVE;
 #ifndef NX_REFILL_BELOW
 #define NX_REFILL_BELOW 40
-#endif
-#ifndef NX_WG_RANGE
-#define NX_WG_RANGE 1
 #endif
 static_assert((kRaySurvives << 30) == 0x80000000u, "the roulette bit of rayO.w moves to bit 31 of the lane's ray index");
 constexpr int kRefillBelow = NX_REFILL_BELOW;  // refill idle lanes when fewer than this many of the 64 are still traversing
@@ -84,14 +81,6 @@ constexpr int kRefillBelow = NX_REFILL_BELOW;  // refill idle lanes when fewer t
 #define NX_THIN_FACTOR 4
 #endif
 constexpr int kThinFactor = NX_THIN_FACTOR;  // (the other two numbers of the rule travel in the device state: DeviceState::thinLanes / thinIters)
-#ifdef NX_NO_THIN_CODE
-constexpr bool kThinCode = false;  // (measurement: the kernel without the search's text)
-#else
-constexpr bool kThinCode = true;
-#endif
-#ifndef NX_THIN_FRAME_CACHE
-#define NX_THIN_FRAME_CACHE 1
-#endif
 #ifndef NX_POOL_SLOTS
 #define NX_POOL_SLOTS 1024
 #endif
@@ -220,7 +209,7 @@ NXD ThinResult thin_wave_search(const DeviceState* __restrict__ S, lds_u64* cons
         GF4 isect = nullptr;
         uint32_t instIdx = 0u;
         const bool inFrame = have && frame != 0u;
-        const bool known = NX_THIN_FRAME_CACHE && inFrame && frame == cFrame;  // (NX_THIN_FRAME_CACHE=0: measurement, every item derives its frame)
+        const bool known = inFrame && frame == cFrame;
         if (known) { nodes = cNodes; isect = cIsect; instIdx = cInst; ro = cO; rd = cD; ri = cI; }
         const bool derive = inFrame && !known;
         if (derive) {
@@ -408,11 +397,6 @@ NXD ThinResult thin_wave_search(const DeviceState* __restrict__ S, lds_u64* cons
     return r;
 }
 
-#ifdef NX_WAVE_TIMELINE
-constexpr int kTimelineBounces = 12, kTimelineWaves = 8192;
-__device__ unsigned long long g_waveTimeline[2][kTimelineBounces][kTimelineWaves][5];
-#endif
-
 template <bool ANY_HIT, bool STATS>
 // 5 waves per SIMD for both variants (96 VGPRs, no spills in the loop).  Before an instance entry also carried its BLAS
 // root (17 more live registers in the fetch), 6 waves at 80 VGPRs was the best point (5: -3 %, 7: -0.3 %, 8: -1.5 %); with it,
@@ -430,7 +414,7 @@ __global__ void __launch_bounds__(kTraceBlock) trace_kernel(const DeviceState* _
     // ... | kTraceEntryFlag: the rays name the entry state of their run (rayO.w): installed at refill instead of the root's
     const bool entryLaunch = !ANY_HIT && (bounceArg & kTraceEntryFlag) != 0 && S->entry != nullptr;
     // ... | kTraceThinFlag: the last long rays of a dry wave may be handed to the thin kernel (below)
-    bool thinAllowed = !STATS && kThinCode && (bounceArg & kTraceThinFlag) != 0;
+    bool thinAllowed = !STATS && (bounceArg & kTraceThinFlag) != 0;
     const int thinLanes = (int)(S->thinLanes & 0xffu);
     // (test hook, nxhip_debug_set_thin inHooks bit 1: hand over after thinIters iterations of EVERY stretch between two refill points, dry
     //  queue or not — rays then arrive at the thin kernel with the state of exactly that many steps)
@@ -446,7 +430,6 @@ __global__ void __launch_bounds__(kTraceBlock) trace_kernel(const DeviceState* _
     // and three IEEE divisions into every iteration in which any lane left an instance — most of them on instanced scenes.)
     __shared__ float ldsWorld[9 * kTraceBlock];
 
-#if NX_WG_RANGE
     // The workgroup's block of rays (see the refill): {next ray, end} packed in one 64-bit word the four waves draw from with
     // LDS atomics; sLock: a wave is fetching the next block; sDry: no shard holds rays any more; sShard: the shard the blocks come from
     // (sBegin / sEnd: the eight shards' first ray and end, sReserve: the block size — kept here, not in every wave's registers: they
@@ -454,7 +437,6 @@ __global__ void __launch_bounds__(kTraceBlock) trace_kernel(const DeviceState* _
     __shared__ unsigned long long sRange;
     __shared__ int sLock, sDry, sShard, sReserve;
     __shared__ int sBegin[kXcds], sEnd[kXcds];
-#endif
     NX_G Counters* C = S->counters;
     // the queue's eight regions (nx_device.h): region k = slots [k * cap, k * cap + regionRays[k]), fetch head k counts the
     // rays handed out of it
@@ -477,11 +459,7 @@ __global__ void __launch_bounds__(kTraceBlock) trace_kernel(const DeviceState* _
     GF4 rayD = ANY_HIT ? S->shadow.rayD : S->trace.rays[raySet].rayD;
     GU4 tlasNodes = S->tlasNodes;
     const NX_G InstTrav* instTrav = S->instTrav;
-#ifdef NX_NO_SCENE_FLAG
-    const bool sceneIdentity = false;
-#else
     const bool sceneIdentity = (S->sceneFlags & kSceneAllIdentity) != 0u;  // wave-uniform: no instance of the scene transforms a ray
-#endif
 
     const int lane = threadIdx.x & (kWave - 1);
     const unsigned long long laneLt = (1ull << lane) - 1ull;
@@ -489,13 +467,6 @@ __global__ void __launch_bounds__(kTraceBlock) trace_kernel(const DeviceState* _
     const int homeRays = shard_rays(homeShard);
     // this wave's rank among the waves that call this shard home
     const int rankInShard = (int)(blockIdx.x >> 3) * (kTraceBlock / kWave) + (int)(threadIdx.x / kWave);
-#ifdef NX_WAVE_TIMELINE
-    // measurement variant: every wave's life in the launch (wall_clock64: 100 MHz, one clock for the chip), kept in a device array
-    // and read with nxhip_debug_read_wave_timeline (bench.py NX_WAVE_TIMELINE_OUT)
-    const unsigned long long wpStart = wall_clock64();
-    unsigned long long wpDry = 0ull;
-    int wpHanded = 0;
-#endif
     // A wave the queue does not need leaves without touching a fetch head.  The grid is sized for the largest queue; on a
     // small one most waves would otherwise each walk all 8 heads with returning atomics to find out that nothing is left,
     // which made every launch cost about 0.5 ms however few rays it carried.
@@ -508,16 +479,12 @@ __global__ void __launch_bounds__(kTraceBlock) trace_kernel(const DeviceState* _
 #define NX_RPW_SHIFT 10
 #endif
     const int raysPerWave = min(256, max(kWave, (size >> NX_RPW_SHIFT) & ~(kWave - 1)));
-#if !NX_WG_RANGE
-    if (rankInShard * raysPerWave >= homeRays) return;
-#endif
     // Reservation size: kReserve rays, but no more than half a wave's even share of the queue, so that on a small queue
     // every wave draws a few times and the launch does not end with a handful of waves still holding full blocks
     // (one frame per pass: +14 %; 64 frames per pass: within noise).
     const int gridWaves = (int)(gridDim.x * (kTraceBlock / kWave));
     const int wavesAtWork = min(gridWaves, size / raysPerWave + kXcds);
     const int reserve = min(kReserve, max(kWave, (size / (wavesAtWork * 2)) & ~(kWave - 1)));
-#if NX_WG_RANGE
     if (threadIdx.x < kXcds) {
         sBegin[threadIdx.x] = shard_begin((int)threadIdx.x);
         sEnd[threadIdx.x] = shard_begin((int)threadIdx.x) + shard_rays((int)threadIdx.x);
@@ -525,7 +492,6 @@ __global__ void __launch_bounds__(kTraceBlock) trace_kernel(const DeviceState* _
     if (threadIdx.x == 0) { sRange = 0ull; sLock = 0; sDry = 0; sShard = homeShard; sReserve = reserve; }
     __syncthreads();  // (before any wave leaves: the exit below is per wave)
     if (rankInShard * raysPerWave >= homeRays) return;
-#endif
     int shard = homeShard;
     bool exhausted = false;
     int rngCur = 0, rngEnd = 0;  // rays reserved by this wave and not handed to a lane yet
@@ -534,9 +500,6 @@ __global__ void __launch_bounds__(kTraceBlock) trace_kernel(const DeviceState* _
     uint2 stackSpill[kSpillDepth];
     int sp = 0;
 
-#ifdef NX_EXTRA_VALU
-    float dummy0 = (float)lane, dummy1 = dummy0 + 1.0f, dummy2 = dummy0 + 2.0f, dummy3 = dummy0 + 3.0f;
-#endif
     bool active = false;
     bool resultPending = false;  // this lane's ray has finished and its result has not been written yet
     f3 org = mk3(0.0f), dir = mk3(0.0f), idir = mk3(0.0f);
@@ -593,12 +556,11 @@ __global__ void __launch_bounds__(kTraceBlock) trace_kernel(const DeviceState* _
                 if (rngCur >= rngEnd) {
                     if (exhausted) break;
                     const int leader = __ffsll((long long)needMask) - 1;
-#if NX_WG_RANGE
                     // The rays a wave hands its idle lanes come out of the WORKGROUP's block: one LDS atomic takes as many as the wave
-                    // needs now.  A block is what one returning atomic on the shard's head reserves (below) — as before, but for the
-                    // four waves together, so that the last block of a launch is finished by four waves side by side instead of by
-                    // the one that happened to draw it while the others leave (wave by wave, a launch's last 200-450 us ran on 2 % of
-                    // the chip: tools/wave_timeline.py).  (readfirstlane: what comes out of LDS is the same in every lane, and the
+                    // needs now.  A block is what one returning atomic on the shard's head reserves (below) — as it was for one wave in
+                    // rounds 1-4, but for the four waves together, so that the last block of a launch is finished by four waves side by
+                    // side instead of by the one that happened to draw it while the others leave (wave by wave, a launch's last
+                    // 200-450 us ran on 2 % of the chip: round 5's wave timeline).  (readfirstlane: what comes out of LDS is the same in every lane, and the
                     // compiler must know it — the range, `exhausted` and the loop's conditions stay scalar.)
                     {
                         const int want = (int)__popcll(needMask);
@@ -611,16 +573,10 @@ __global__ void __launch_bounds__(kTraceBlock) trace_kernel(const DeviceState* _
                             rngEnd = min(end, cur + want);
                         }
                     }
-                    if (rngCur >= rngEnd)
-#endif
-                    {
-#if NX_WG_RANGE
+                    if (rngCur >= rngEnd) {
                         // the workgroup's block is used up
                         if (__builtin_amdgcn_readfirstlane(__hip_atomic_load(&sDry, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) != 0) {
                             exhausted = true;
-#ifdef NX_WAVE_TIMELINE
-                            wpDry = wall_clock64();
-#endif
                             thinAfter = thinIters ? max(thinIters, (uint32_t)((float)kThinFactor * 40.0f * (float)itersTotal / (float)max(taken, 1u))) : 0u;
                             break;
                         }
@@ -643,18 +599,12 @@ __global__ void __launch_bounds__(kTraceBlock) trace_kernel(const DeviceState* _
                         shard = __builtin_amdgcn_readfirstlane(__hip_atomic_load(&sShard, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
                         const int shardBegin = __builtin_amdgcn_readfirstlane(sBegin[shard]), shardEnd = __builtin_amdgcn_readfirstlane(sEnd[shard]);
                         const int blockRays = __builtin_amdgcn_readfirstlane(sReserve);
-#else
-                        const int shardBegin = shard_begin(shard);
-                        const int shardEnd = shardBegin + shard_rays(shard);
-                        const int blockRays = reserve;
-#endif
                         // one returning atomic reserves a block of rays of `shard` (the head counts rays handed out)
                         int base = 0;
                         if (lane == leader) base = atomicAdd(&heads[shard * kRegionStride], blockRays);
                         base = __builtin_amdgcn_readlane(base, leader);
                         rngCur = shardBegin + base;
                         rngEnd = min(shardEnd, rngCur + blockRays);
-#if NX_WG_RANGE
                         if (rngCur < shardEnd) {  // the workgroup's new block
                             if (lane == leader) {
                                 __hip_atomic_store(&sRange, ((unsigned long long)(uint32_t)rngEnd << 32) | (unsigned long long)(uint32_t)rngCur, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -663,7 +613,6 @@ __global__ void __launch_bounds__(kTraceBlock) trace_kernel(const DeviceState* _
                             rngCur = rngEnd = 0;
                             continue;
                         }
-#endif
                         if (rngCur >= shardEnd) {
                             // this shard is dry: one load of all 8 heads tells which shards still hold rays (a load is served
                             // in parallel with other waves', returning atomics on a head are serialised); go to the fullest
@@ -671,11 +620,7 @@ __global__ void __launch_bounds__(kTraceBlock) trace_kernel(const DeviceState* _
                             int left = 0;
                             if (lane < kXcds) {
                                 const int taken = __hip_atomic_load(&heads[lane * kRegionStride], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#if NX_WG_RANGE
                                 left = max(0, sEnd[lane] - sBegin[lane] - taken);
-#else
-                                left = max(0, shard_rays(lane) - taken);
-#endif
                             }
                             int best = 0, bestLeft = 0;
 #pragma unroll
@@ -687,16 +632,12 @@ __global__ void __launch_bounds__(kTraceBlock) trace_kernel(const DeviceState* _
                             bestLeft = __builtin_amdgcn_readfirstlane(bestLeft);
                             if (bestLeft <= 0) {
                                 exhausted = true;
-#ifdef NX_WAVE_TIMELINE
-                                wpDry = wall_clock64();
-#endif
                                 // how long "long" is for this launch: kThinFactor times what a ray of this wave took on average (a wave
                                 // iteration advances its busy lanes — about 40 of 64 — by one record each), at least thinIters
                                 // (thinIters 0 — a test hook — hands a wave's rays over after their first iteration, dry queue or not)
                                 thinAfter = thinIters ? max(thinIters, (uint32_t)((float)kThinFactor * 40.0f * (float)itersTotal / (float)max(taken, 1u))) : 0u;
                             }
                             else shard = best;
-#if NX_WG_RANGE
                             // (the workgroup's state: no rays anywhere, or the shard its next block comes from; the other waves find out at
                             //  their next look)
                             if (lane == leader) {
@@ -704,7 +645,6 @@ __global__ void __launch_bounds__(kTraceBlock) trace_kernel(const DeviceState* _
                                 else __hip_atomic_store(&sShard, best, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                                 __hip_atomic_store(&sLock, 0, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
                             }
-#endif
                             continue;
                         }
                     }
@@ -763,7 +703,6 @@ __global__ void __launch_bounds__(kTraceBlock) trace_kernel(const DeviceState* _
                 // (the test hook — a wave-uniform scalar — leaves the range where it is: the same rays go out again at the next refill)
                 rngCur += requeue ? 0 : min(__popcll(needMask), avail);
                 taken += (uint32_t)min(__popcll(needMask), avail);
-#ifndef NX_NO_STALL_GUARD
                 // Progress per LAUNCH: a wave cannot be handed more rays than the queue holds.  One that is holds rays that come back into
                 // the queue — every one of them retires, so the iteration guard below, which counts between two refill points, never
                 // fires.  Same ending: the rays in hand are abandoned, the wave takes no more, the host gets NXHIP_ERR_TRAVERSAL.
@@ -776,7 +715,6 @@ __global__ void __launch_bounds__(kTraceBlock) trace_kernel(const DeviceState* _
                     rngCur = rngEnd = 0;
                     break;
                 }
-#endif
             }
         }
         unsigned long long activeMask = __ballot(active);
@@ -905,25 +843,13 @@ __global__ void __launch_bounds__(kTraceBlock) trace_kernel(const DeviceState* _
                 }
             }
             NX_STAMP(5);
-#ifndef NX_NO_EARLY_RETIRE
             // a ray that has nothing left (no pending child, no pending leaf, empty stack) retires now instead of spending the
             // next iteration's acquire step on finding that out: its lane counts as free one iteration earlier
             if (active && tg.y == 0u && (ng.y & 0xff000000u) == 0u && sp == 0) {
                 active = false;
                 resultPending = true;
             }
-#endif
-#ifdef NX_EXTRA_VALU
-            // experiment: how does the kernel's rate respond to its VALU instruction count?  NX_EXTRA_VALU
-            // independent FMAs per iteration that change no result: +64 on the ~330 of an iteration costs 15 % of the kernel's time
-#pragma unroll
-            for (int k = 0; k < NX_EXTRA_VALU; k += 4) {
-                dummy0 = fmaf(dummy0, 1.0001f, 0.5f); dummy1 = fmaf(dummy1, 1.0001f, 0.5f);
-                dummy2 = fmaf(dummy2, 1.0001f, 0.5f); dummy3 = fmaf(dummy3, 1.0001f, 0.5f);
-            }
-#endif
             activeMask = __ballot(active);
-#ifndef NX_NO_STALL_GUARD
             // A wave leaves this loop when enough of its rays have finished, or — once the queue is dry — when all have.  One that
             // is still here after kStallLimit iterations holds rays that go round in circles: not a tree.  It abandons them
             // (closest hit: they end with what they found so far; any hit: as occluded), takes no more, and tells the host.
@@ -934,24 +860,9 @@ __global__ void __launch_bounds__(kTraceBlock) trace_kernel(const DeviceState* _
                 exhausted = true;
                 rngCur = rngEnd = 0;
             }
-#endif
-            if (!STATS && kThinCode && thinAllowed && ((exhausted && rngCur >= rngEnd) || thinIters == 0u || thinAnyTime) && activeMask != 0ull && __popcll(activeMask) <= thinLanes && spins >= thinAfter) {
+            if (!STATS && thinAllowed && ((exhausted && rngCur >= rngEnd) || thinIters == 0u || thinAnyTime) && activeMask != 0ull && __popcll(activeMask) <= thinLanes && spins >= thinAfter) {
                 // the wave is dry and down to its last few long rays: they go to the thin kernel (below), which puts all 64 lanes of
                 // a wave on each of them; this wave is done
-#if defined(NX_THIN_DROP) && defined(NX_THIN_DROP_KIND)
-                if (ANY_HIT != (NX_THIN_DROP_KIND == 1)) { thinAllowed = false; }  // (bound per ray kind: the other kind's waves finish their rays themselves)
-                else
-#endif
-#ifdef NX_THIN_DROP
-                // BOUND EXPERIMENT (wrong results): the rays a hand-over rule would give away simply end here — closest hit with what they
-                // have found so far, any hit as occluded — so that the launch's time is what ANY hand-over, however fast, could reach
-                // at most (tools/ab_prebuilt.sh drop+NX_THIN_LANES=..+NX_THIN_ITERS=..)
-                {
-                    if (active) { active = false; resultPending = !ANY_HIT; }
-                    activeMask = 0ull;
-                    thinAllowed = false;
-                }
-#else
                 NX_G int* const count = &C->thinCount[ANY_HIT ? 1 : 0][bounce];
                 int base = 0;
                 const int leader = __ffsll((long long)activeMask) - 1, n = (int)__popcll(activeMask);
@@ -982,28 +893,11 @@ __global__ void __launch_bounds__(kTraceBlock) trace_kernel(const DeviceState* _
                 //  hands over after EVERY refill as long as the list has room, so that nearly all rays of a batch go through the search
                 //  however the waves share the queue)
                 if ((thinIters != 0u && !thinAnyTime) || base + n > (int)S->thinCapacity) thinAllowed = false;
-#ifdef NX_WAVE_TIMELINE
-                wpHanded = n;
-#endif
-#endif  // NX_THIN_DROP
             }
         } while (activeMask != 0ull && ((exhausted && rngCur >= rngEnd) || __popcll(activeMask) >= kRefillBelow));
         itersTotal += spins;
     }
 
-#ifdef NX_EXTRA_VALU
-    if (dummy0 + dummy1 + dummy2 + dummy3 == 123.456f) S->traceStats[0].rays = 1;  // keeps the filler alive
-#endif
-#ifdef NX_WAVE_TIMELINE
-    if (!STATS && lane == 0 && bounce < kTimelineBounces) {
-        const int w = (int)blockIdx.x * (kTraceBlock / kWave) + (int)(threadIdx.x / kWave);
-        if (w < kTimelineWaves) {
-            unsigned long long* rec = g_waveTimeline[ANY_HIT ? 1 : 0][bounce][w];
-            rec[0] = wpStart; rec[1] = wpDry; rec[2] = wall_clock64(); rec[3] = ((unsigned long long)taken << 32) | (unsigned long long)itersTotal;
-            rec[4] = (unsigned long long)wpHanded;
-        }
-    }
-#endif
     if (STATS) {
         // wave-level reduction, one atomic per wave and counter
         for (int o = 32; o > 0; o >>= 1) {
@@ -1034,9 +928,6 @@ template __global__ void trace_kernel<true, true>(const DeviceState*, int);
 
 // The listed rays of one level (closest-hit first, then any-hit; kThinClosestOnly / kThinAnyOnly: one list), one wave per ray,
 // grid-stride.  `bounceArg` as the trace launches got it: the ray set and the meaning of the closest-hit record follow kTraceScanFlag.
-#ifdef NX_THIN_WAVES_PER_EU
-__attribute__((amdgpu_waves_per_eu(NX_THIN_WAVES_PER_EU, NX_THIN_WAVES_PER_EU)))  // (measurement knob: DESIGN.md section 7)
-#endif
 __global__ void __launch_bounds__(kTraceBlock) thin_kernel(const DeviceState* __restrict__ S, const int bounceArg)
 {
     __shared__ unsigned long long sPool[(kTraceBlock / kWave) * kPoolSlots];
@@ -1091,9 +982,6 @@ __global__ void __launch_bounds__(kTraceBlock) thin_kernel(const DeviceState* __
             // (thin_wave_search), so a gate above t with the carried hit at or below the gate sends the ray to the replay.  The seeds'
             // own gate is 0: the loop visits a popped group without testing its box again.
             const bool ambiguous = r.count != 0 && r.replaced && (r.second == r.t || (gate > r.t && r.second <= gate));
-#ifdef NX_THIN_PRINTF
-            if (lane == 0 && (e == 0 || r.rounds >= 24u || !r.complete || ambiguous)) printf("thin closest bounce %d list %d ray %d rounds %u pool %d complete %d ambiguous %d t %g gate %g second %g\n", bounce, nClosest, e, r.rounds, r.poolMax, (int)r.complete, (int)ambiguous, r.t, r.gate, r.second);
-#endif
             float hitT = r.count ? r.t : 1e30f, hitU = r.u, hitV = r.v;
             uint32_t hitTri = r.count ? r.tri : 0xffffffffu, hitInst = r.inst;
             if (!r.complete || ambiguous) {
@@ -1120,9 +1008,6 @@ __global__ void __launch_bounds__(kTraceBlock) thin_kernel(const DeviceState* __
             const f3 org = mk3(o.x, o.y, o.z), dir = mk3(d.x, d.y, d.z);
             const ThinResult r = thin_wave_search<true>(S, pool, poolGate, org, dir, o.w, sceneIdentity, S->thinStates + (size_t)cap + (size_t)(e - nClosest));
             bool occluded = r.count != 0;
-#ifdef NX_THIN_PRINTF
-            if (lane == 0 && (e == nClosest || r.rounds >= 24u || !r.complete)) printf("thin any bounce %d list %d ray %d rounds %u pool %d complete %d occluded %d\n", bounce, nAny, e - nClosest, r.rounds, r.poolMax, (int)r.complete, (int)occluded);
-#endif
             if (!occluded && !r.complete) {
                 float t = o.w, u, v;
                 uint32_t tri, inst;
@@ -1141,19 +1026,6 @@ __global__ void __launch_bounds__(kTraceBlock) thin_kernel(const DeviceState* __
 }
 
 const void* thin_kernel_ptr() { return (const void*)thin_kernel; }
-
-#ifdef NX_WAVE_TIMELINE
-}  // namespace nxd
-// (measurement variant only) the timeline of the LAST launches of every level; clears it
-extern "C" int nxhip_debug_read_wave_timeline(void* out, unsigned long long bytes)
-{
-    if (bytes != sizeof(nxd::g_waveTimeline)) return (int)sizeof(nxd::g_waveTimeline) > 0 ? -1 : -2;
-    if (hipDeviceSynchronize() != hipSuccess) return -3;
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(nxd::g_waveTimeline), bytes) != hipSuccess) return -4;
-    return 0;
-}
-namespace nxd {
-#endif
 
 const void* trace_kernel_ptr(bool anyHit, bool stats)
 {

@@ -104,9 +104,7 @@ NXD bool enter_instance(const InstFetch& f, bool sceneIdentity, f3 org, f3 dir, 
 {
     float4 r0 = make_float4(1.0f, 0.0f, 0.0f, 0.0f), r1 = make_float4(0.0f, 1.0f, 0.0f, 0.0f), r2 = make_float4(0.0f, 0.0f, 1.0f, 0.0f);
     if (sceneIdentity) {
-#ifndef NX_NO_IDENTITY_FLAG
         if (ray_is_ordinary(org, dir)) return false;
-#endif
     } else {
         r0 = make_float4(__uint_as_float(f.rows[0].x), __uint_as_float(f.rows[0].y), __uint_as_float(f.rows[0].z), __uint_as_float(f.rows[0].w));
         r1 = make_float4(__uint_as_float(f.rows[1].x), __uint_as_float(f.rows[1].y), __uint_as_float(f.rows[1].z), __uint_as_float(f.rows[1].w));

@@ -194,12 +194,6 @@ struct SlotAllocator {
             for (int w = 0; w < nWaves; w++) total += sWave[threadIdx.x * kMaxWavesPerBlock + w];
             int* const word = counter_of((int)threadIdx.x) + region * kRegionStride;
             sBase[threadIdx.x] = total ? atomicAdd(word, total) : 0;
-#ifdef NX_EXTRA_ATOMICS
-            // experiment: are the logic / material kernels bound by the returning atomics on their queue
-            // counters?  NX_EXTRA_ATOMICS more of them per tile and counter, adding zero
-            for (int x = 0; x < NX_EXTRA_ATOMICS; x++)
-                if (total && atomicAdd(word, 0) == -123456789) sBase[threadIdx.x] = 0;  // (returning, result unused)
-#endif
         }
         __syncthreads();
 #pragma unroll
@@ -317,12 +311,6 @@ struct TileAllocator {
             }
             int* const word = counter_of((int)threadIdx.x) + region * kRegionStride;
             int run = total ? atomicAdd(word, total) : 0;
-#ifdef NX_EXTRA_ATOMICS
-            // experiment: are the logic / material kernels bound by the returning atomics on their queue
-            // counters?  NX_EXTRA_ATOMICS more of them per tile and counter, adding zero
-            for (int x = 0; x < NX_EXTRA_ATOMICS; x++)
-                if (total && atomicAdd(word, 0) == -123456789) run = 0;  // (returning, result unused)
-#endif
 #pragma unroll
             for (int u = 0; u < U; u++) {
                 sBase[u * K + (int)threadIdx.x] = run;
@@ -787,13 +775,7 @@ NXD void shade_path(const DeviceState* S, const int bounce, const uint32_t frame
     uint32_t rng = seed_for(S, seedSlot, pixelIdx, (uint32_t)bounce, 1u, frame);
 
     const NX_G ShadeInst* inst = &S->shadeInst[instanceIdx];
-#ifdef NX_SHADE_SEQ_TRI
-    // BOUND EXPERIMENT (wrong results): every item reads the shading triangle of its QUEUE SLOT instead of its hit's —
-    // consecutive items, consecutive 96-byte records — so that what is left of the material launch is everything but the random gather
-    const NX_G nx_triangle* tri = shade_tri(inst->tris, seedSlot % max(inst->triCount, 1u));
-#else
     const NX_G nx_triangle* tri = shade_tri(inst->tris, triIdx);
-#endif
     const nx_material material = inst->material;
     MatParams mp = load_params(material);
     const NX_G float* T = inst->transform;
@@ -1199,34 +1181,6 @@ __global__ void __launch_bounds__(kWideBlock) count_scan_kernel(const DeviceStat
     if ((threadIdx.x & (kWave - 1)) == 0 && n) atomicAdd(&C->region[0].materialSize[type][bounce], n);
 }
 
-// What is left of the logic kernel in the SCAN pipeline when a miss can contribute: the environment (flat colour or map, MIS-
-// weighted against the environment sampler) added to the radiance of the paths that missed — PathTracer.cu:152-164.  In the
-// graph only when the scene has an environment map or a background that is not black.
-__global__ void __launch_bounds__(kWideBlock) miss_scan_kernel(const DeviceState* __restrict__ S, const int bounce)
-{
-    Counters* C = S->counters;
-    const QueueView in = queue_view(&C->region[0].traceSize[bounce - 1], S->queueShardCap);
-    const uint32_t frame = S->frame->frameNumber;
-    const TraceRays rays = S->trace.rays[(bounce - 1) & 1];
-    for (int index = (int)(blockIdx.x * blockDim.x + threadIdx.x); index < in.total; index += (int)(gridDim.x * blockDim.x)) {
-        const int at = in.slot(index);
-        if ((S->trace.hitInst[at] >> kHitCodeShift) != kHitCodeMiss) continue;
-        const float4 dirPix = rays.rayD[at];
-        const uint32_t pixelIdx = __float_as_uint(dirPix.w);
-        const float4 tp = bounce == 1 ? make_float4(1.0f, 1.0f, 1.0f, 1.0e10f) : rays.tp[at];
-        bool miss, survived, needsPrevVertex;
-        f3 bg = mk3(0.0f), t = mk3(0.0f);
-        uint32_t inst = 0;
-        logic_path(S, bounce, frame, (uint32_t)at, pixelIdx, 1e30f, mk3(dirPix.x, dirPix.y, dirPix.z), tp, [&]() { return 0u; }, miss, bg, survived, t, inst, needsPrevVertex);
-        if ((__float_as_uint(bg.x) | __float_as_uint(bg.y) | __float_as_uint(bg.z)) != 0u) {  // (as the logic kernel: +0 changes nothing)
-            float4 r = bounce == 1 ? make_float4(0, 0, 0, 0) : S->radiance[pixelIdx];
-            r.x += bg.x; r.y += bg.y; r.z += bg.z;
-            if (bounce == 1) r = make_float4(bg.x, bg.y, bg.z, 0.0f);
-            S->radiance[pixelIdx] = r;
-        }
-    }
-}
-
 // ------------------------------------------------------------------------------------------------------
 // Tail kernel: the late bounces of a pass without the graph.  From bounce `firstBounce` on a pass carries a few per cent of
 // its rays, yet every bounce still costs a trace level as long as its slowest ray plus a logic and four material launches.
@@ -1484,23 +1438,23 @@ __global__ void __launch_bounds__(kWideBlock) tex2d_hook_kernel(const TextureDev
 // `items` per thread: kLogicItems (2) unless the caller asks for 1 — what a scene with an environment map gets, whose misses run the
 // map lookups (binary64 arc functions) in this kernel: with a second item's state live beside them the 64-register budget spills
 // into that path (configs[3]: logic kernel +8 % with two items, -6 % on configs[1])
-const void* logic_kernel_ptr(bool ordered, int items)
+const void* logic_kernel_ptr(int items)
 {
-    if (items == 1 || kLogicItems == 1) return ordered ? (const void*)logic_kernel<true, 1> : (const void*)logic_kernel<false, 1>;
-    return ordered ? (const void*)logic_kernel<true, kLogicItems> : (const void*)logic_kernel<false, kLogicItems>;
+    if (items == 1 || kLogicItems == 1) return (const void*)logic_kernel<true, 1>;
+    return (const void*)logic_kernel<true, kLogicItems>;
 }
 
-const void* shade_kernel_ptr(int type, bool ordered)
+// (the classic pipeline — logic kernel and per-type material kernels — runs under the ordered compaction only: see frame_levels)
+const void* shade_kernel_ptr(int type)
 {
     switch (type) {
-    case NX_MAT_DIFFUSE: return ordered ? (const void*)shade_kernel<NX_MAT_DIFFUSE, true> : (const void*)shade_kernel<NX_MAT_DIFFUSE, false>;
-    case NX_MAT_DIELECTRIC: return ordered ? (const void*)shade_kernel<NX_MAT_DIELECTRIC, true> : (const void*)shade_kernel<NX_MAT_DIELECTRIC, false>;
-    case NX_MAT_PLASTIC: return ordered ? (const void*)shade_kernel<NX_MAT_PLASTIC, true> : (const void*)shade_kernel<NX_MAT_PLASTIC, false>;
-    default: return ordered ? (const void*)shade_kernel<NX_MAT_CONDUCTOR, true> : (const void*)shade_kernel<NX_MAT_CONDUCTOR, false>;
+    case NX_MAT_DIFFUSE: return (const void*)shade_kernel<NX_MAT_DIFFUSE, true>;
+    case NX_MAT_DIELECTRIC: return (const void*)shade_kernel<NX_MAT_DIELECTRIC, true>;
+    case NX_MAT_PLASTIC: return (const void*)shade_kernel<NX_MAT_PLASTIC, true>;
+    default: return (const void*)shade_kernel<NX_MAT_CONDUCTOR, true>;
     }
 }
 const void* shade_scan_kernel_ptr() { return (const void*)shade_scan_kernel; }
-const void* miss_scan_kernel_ptr() { return (const void*)miss_scan_kernel; }
 const void* count_scan_kernel_ptr() { return (const void*)count_scan_kernel; }
 const void* tail_kernel_ptr() { return (const void*)tail_kernel; }
 const void* begin_frame_kernel_ptr() { return (const void*)begin_frame_kernel; }

@@ -18,10 +18,9 @@ namespace nxd {
 
 const void* trace_kernel_ptr(bool anyHit, bool stats);
 const void* tail_kernel_ptr();
-const void* logic_kernel_ptr(bool ordered, int items);
-const void* shade_kernel_ptr(int type, bool ordered);
+const void* logic_kernel_ptr(int items);
+const void* shade_kernel_ptr(int type);
 const void* shade_scan_kernel_ptr();
-const void* miss_scan_kernel_ptr();
 const void* count_scan_kernel_ptr();
 const void* inst_code_kernel_ptr();
 const void* entry_state_kernel_ptr();
@@ -215,7 +214,7 @@ static size_t scan_status_tiles(size_t n) { return n / (size_t)std::min(kLogicBl
 // Which pipeline a pass runs (nx_wavefront.hip): SCAN — the logic step's decision rides in the hit records and the material kernels
 // pick their items out of the trace queue — whenever slots are handed out by racing atomics; the CLASSIC logic kernel + material
 // queues for the ordered compaction, whose serial slot order IS the reference's copy order (PathTracer.cu:183-206).
-static bool scan_pipeline(const nxhip_ctx* c) { return c->h.compactMode == NX_COMPACT_FAST && !c->classicPipeline; }
+static bool scan_pipeline(const nxhip_ctx* c) { return c->h.compactMode == NX_COMPACT_FAST; }
 
 static TraceQueue trace_queue_of(const PassSlot* s)
 {
@@ -546,15 +545,8 @@ int nxhip_create(int device, uint32_t width, uint32_t height, void* stream, nxhi
                 const int n = std::atoi(e);
                 if (n >= 1 && n <= 64) c->logicBlocksPerCU = n;
             }
-            if (const char* e = std::getenv("NX_THIN_JOINT")) c->thinJoint = std::atoi(e) != 0;  // measurement only
             if (const char* e = std::getenv("NX_THIN_LANES")) { const int n = std::atoi(e); if (n >= 1 && n <= 64) c->h.thinLanes = (uint32_t)n; }   // sweeps of the hand-over rule
             if (const char* e = std::getenv("NX_THIN_ITERS")) { const int n = std::atoi(e); if (n >= 1 && n <= 4096) c->h.thinIters = (uint32_t)n; }
-            if (const char* e = std::getenv("NX_THIN_IN_FLIGHT")) c->thinInFlight = std::atoi(e) != 0;  // measurement only: the thin level with passes in flight too
-            if (const char* e = std::getenv("NX_NO_THIN")) c->thinWaves = std::atoi(e) == 0;  // measurement only: no cooperative finish of a dry wave's last rays
-            if (const char* e = std::getenv("NX_SCAN_SEPARATE")) c->scanSeparate = std::atoi(e) != 0;  // measurement only: one material launch per type in the SCAN pipeline
-            if (const char* e = std::getenv("NX_PIPELINE_CLASSIC")) c->classicPipeline = std::atoi(e) != 0;  // measurement only: logic kernel + material queues under fast compaction too
-            if (const char* e = std::getenv("NX_SHADE_SERIAL")) c->serialShade = std::atoi(e) != 0;  // tuning experiments only
-            if (const char* e = std::getenv("NX_SHADE_PARALLEL")) c->parallelShade = std::atoi(e);    // tuning experiments only
             if (const char* e = std::getenv("NX_TRACE_BLOCKS_TOTAL")) {  // tuning experiments only
                 const int n = std::atoi(e);
                 if (n >= 1 && n <= 65536) { c->traceBlocks = c->shadowBlocks = n; c->traceGridForced = true; }
@@ -1742,11 +1734,6 @@ int launch_begin_frame(nxhip_ctx* c, PassSlot* q, uint32_t frames, uint32_t fram
 // fraction of the image, so its 20-frame pass is a small one (8 ranks: 2.5 frames' worth of paths).
 double pass_size_in_frames(const nxhip_ctx* c) { return (double)c->localCount * (double)c->framesPerPass / (1920.0 * 1080.0); }
 
-// (round 3: with only the material kernels of types in use in the graph and the slot counters spread over the queue regions, one
-//  branch is also the faster form for large passes — 64 frames per pass, 4 in flight: 1 988 against 1 974 Msamples/s — so it is
-//  what every pass uses; NX_SHADE_PARALLEL=1 brings the parallel branches back for experiments)
-bool serial_shade(const nxhip_ctx* c) { return c->parallelShade != 1; }
-
 // Passes in flight right now: kernel timing and the counting variant measure one pass at a time, and a caller-bound
 // radiance buffer exists once.
 uint32_t effective_slots(const nxhip_ctx* c)
@@ -1797,8 +1784,7 @@ int tail_bounce(const nxhip_ctx* c)
         // (one pass at a time, round 5: the thin level takes the drains out of the trace launches, and the tail kernel — whose waves keep
         //  64 lanes for as long as their longest path, outlier rays included — only still pays for the smallest passes: one frame 595 ->
         //  620 Msamples/s with it, four frames 1 335 -> 1 315, a rank of 8 the same median with a 6.3 ms pass in seven instead of none)
-        else if (c->thinWaves) bounce = frames <= 1.5 ? 3 : 0;
-        else bounce = frames <= 1.5 ? 3 : frames <= 4.0 ? 4 : frames <= 10.0 ? 5 : 0;
+        else bounce = frames <= 1.5 ? 3 : 0;
         if (bounce > (int)c->h.settings.pathLength) bounce = 0;
     }
     if (bounce < 2 || bounce > (int)c->h.settings.pathLength) return 0;
@@ -1833,7 +1819,7 @@ int pass_flavor(const nxhip_ctx* c)
     // Small passes one at a time keep it as well: the median of single passes does not show it (a rank of 8's 2.5 frames' worth: 4.57 ->
     // 4.6-4.7 ms, an extra launch per level), but one pass in seven holds an outlier ray (6.2 ms instead of 4.6) and sequences of small
     // passes are what a viewer or a rank of a tile split renders: four frames per pass 1 223 -> 1 335 Msamples/s, one frame 602 -> 620.
-    if (c->thinWaves && !c->statsEnabled && (c->passesInFlight <= 1u || c->thinInFlight)) f |= kFlavorThin;  // (the caller's setting, not effective_slots(): a timing replay of a run with passes in flight keeps that run's kernels)
+    if (!c->statsEnabled && c->passesInFlight <= 1u) f |= kFlavorThin;  // (the caller's setting, not effective_slots(): a timing replay of a run with passes in flight keeps that run's kernels)
     return f;
 }
 
@@ -1842,7 +1828,6 @@ int pass_flavor(const nxhip_ctx* c)
 std::vector<std::vector<Launch>> frame_levels(nxhip_ctx* c, PassSlot* q)
 {
     const DeviceState* S = q->dState.as<DeviceState>();
-    const bool ordered = c->h.compactMode == NX_COMPACT_ORDERED;
     const bool stats = c->statsEnabled;
     const int wide = c->wideBlocks;
     const int wideThreads = kWideBlockThreads;
@@ -1865,10 +1850,6 @@ std::vector<std::vector<Launch>> frame_levels(nxhip_ctx* c, PassSlot* q)
         if (const char* e = std::getenv("NX_THIN_BLOCKS_PER_CU")) { const int n = std::atoi(e); if (n >= 1 && n <= 16) thinBlocks = n * c->numCUs; }  // sweeps only
     auto thin_level = [&](int bounceArg) {
         if (!thinFlag) return;
-        if (c->thinJoint) {  // (NX_THIN_JOINT, measurement only: one launch for both lists behind the whole level)
-            levels.push_back({make_launch(thin_kernel_ptr(), thinBlocks, kTraceBlockThreads, NXHIP_K_THIN, S, bounceArg)});
-            return;
-        }
         std::vector<Launch>& level = levels.back();
         const int n = (int)level.size();  // 1: the primary level (closest-hit only); 2: closest-hit, any-hit
         for (int k = 0; k < n; k++) {
@@ -1882,72 +1863,59 @@ std::vector<std::vector<Launch>> frame_levels(nxhip_ctx* c, PassSlot* q)
     //  would need)
     auto whole_regions = [](int g) { return (g + kQueueShards - 1) / kQueueShards * kQueueShards; };
     // (ordered compaction: the same grids — tiles are handed out by ticket and their slots found by look-back, nx_wavefront.hip)
-    const int og = whole_regions(c->shadeBlocksPerCU * c->numCUs), ob = ordered ? kShadeBlockOrderedThreads : kShadeBlockThreads;
+    const int og = whole_regions(c->shadeBlocksPerCU * c->numCUs);
     const int lg = whole_regions(c->logicBlocksPerCU * c->numCUs), lb = kLogicBlockThreads;
-    const int tailFrom = tail_bounce(c);
     auto in_use = [&](int type) { return (c->materialTypeMask >> type) & 1u; };
     if (scan_pipeline(c)) {
         // SCAN pipeline (nx_wavefront.hip): the closest-hit launch leaves the logic step's decision in its hit records, the material
-        // kernels find their items there.  Per bounce: [miss kernel, only when a miss can contribute] -> the material kernels of the
-        // types in use, one after the other -> trace || shadow trace.  One launch less per bounce than the reference's DAG.
+        // kernels find their items there.  Per bounce: ONE material launch for the types in use (shade_scan_kernel; the misses as a
+        // fifth type, only when a miss can contribute) -> [count_scan_kernel] -> trace || shadow trace.  One launch less per bounce than
+        // the reference's DAG.
         levels[1][0].bounce |= kTraceScanFlag;
         thin_level(0 | kTraceScanFlag);
         const bool misses = pass_flavor(c) & kFlavorMissKernel;
+        const int tailFrom = tail_bounce(c);
         for (int bounce = 1; bounce <= pathLength; bounce++) {
             if (bounce == tailFrom) {  // the rest of the pass in one launch
                 levels.push_back({make_launch(tail_kernel_ptr(), c->tailBlocks, kTraceBlockThreads, NXHIP_K_SHADE, S, bounce | kTraceScanFlag)});
                 break;
             }
-            if (misses && c->scanSeparate) levels.push_back({make_launch(miss_scan_kernel_ptr(), lg, kWideBlockThreads, NXHIP_K_LOGIC, S, bounce)});
-            std::vector<Launch> shade;
-            // the material kernels of the types in use: ONE launch for all of them (shade_scan_kernel), or — NX_SCAN_SEPARATE, measurement
-            // only — one per type in the reference's graph order
             int mask = (int)(c->materialTypeMask & 0xfu);
             if (c->h.conductorMode != NX_CONDUCTOR_EXTENDED) mask &= ~(1 << NX_MAT_CONDUCTOR);
             if (mask == 0) mask = 1 << NX_MAT_DIFFUSE;  // (a level cannot be empty)
-            if (misses && !c->scanSeparate) mask |= 1 << kScanMiss;  // the misses: a fifth type of the one launch
-            auto scan_launch = [&](int m) {
-                Launch l = make_launch(shade_scan_kernel_ptr(), og, kShadeBlockThreads, NXHIP_K_SHADE, S, bounce);
-                l.type = m;
-                l.nargs = 3;
-                return l;
-            };
-            if (c->scanSeparate) {
-                for (int type : {NX_MAT_DIFFUSE, NX_MAT_PLASTIC, NX_MAT_DIELECTRIC, NX_MAT_CONDUCTOR})
-                    if ((mask >> type) & 1) shade.push_back(scan_launch(1 << type));
-            } else shade.push_back(scan_launch(mask));
+            if (misses) mask |= 1 << kScanMiss;
+            Launch shade = make_launch(shade_scan_kernel_ptr(), og, kShadeBlockThreads, NXHIP_K_SHADE, S, bounce);
+            shade.type = mask;
+            shade.nargs = 3;
+            levels.push_back({shade});
             if (in_use(NX_MAT_CONDUCTOR) && c->h.conductorMode != NX_CONDUCTOR_EXTENDED) {  // (counted, not shaded: count_scan_kernel)
-                Launch l = make_launch(count_scan_kernel_ptr(), lg, kWideBlockThreads, NXHIP_K_LOGIC, S, bounce);
-                l.type = NX_MAT_CONDUCTOR;
-                l.nargs = 3;
-                shade.push_back(l);
+                Launch count = make_launch(count_scan_kernel_ptr(), lg, kWideBlockThreads, NXHIP_K_LOGIC, S, bounce);
+                count.type = NX_MAT_CONDUCTOR;
+                count.nargs = 3;
+                levels.push_back({count});
             }
-            for (auto& l : shade) levels.push_back({l});
             levels.push_back({make_launch(trace_kernel_ptr(false, stats), traceBlocks, kTraceBlockThreads, NXHIP_K_TRACE, S, bounce | kTraceScanFlag | thinFlag),
                               make_launch(trace_kernel_ptr(true, stats), shadowBlocks, kTraceBlockThreads, NXHIP_K_SHADOW, S, bounce | thinFlag)});
             thin_level(bounce | kTraceScanFlag);
         }
         return levels;
     }
+    // CLASSIC pipeline (ordered compaction; no tail kernel: tail_bounce): per bounce logic kernel -> the material kernels of the
+    // types in use -> trace || shadow trace
     thin_level(0);
+    const int ob = kShadeBlockOrderedThreads;
     for (int bounce = 1; bounce <= pathLength; bounce++) {
-        if (bounce == tailFrom) {  // the rest of the pass in one launch
-            levels.push_back({make_launch(tail_kernel_ptr(), c->tailBlocks, kTraceBlockThreads, NXHIP_K_SHADE, S, bounce)});
-            break;
-        }
-        levels.push_back({make_launch(logic_kernel_ptr(ordered, c->hdrMap.texels.p ? 1 : 2), lg, lb, NXHIP_K_LOGIC, S, bounce)});
+        levels.push_back({make_launch(logic_kernel_ptr(c->hdrMap.texels.p ? 1 : 2), lg, lb, NXHIP_K_LOGIC, S, bounce)});
         // graph insertion order of the reference: Diffuse, Plastic, Dielectric, Conductor (PathTracer.cpp:116-120)
         // (only the types some material of the scene has: a queue no material feeds stays empty)
         std::vector<Launch> shade;
-        if (in_use(NX_MAT_DIFFUSE)) shade.push_back(make_launch(shade_kernel_ptr(NX_MAT_DIFFUSE, ordered), og, ob, NXHIP_K_SHADE, S, bounce));
-        if (in_use(NX_MAT_PLASTIC)) shade.push_back(make_launch(shade_kernel_ptr(NX_MAT_PLASTIC, ordered), og, ob, NXHIP_K_SHADE, S, bounce));
-        if (in_use(NX_MAT_DIELECTRIC)) shade.push_back(make_launch(shade_kernel_ptr(NX_MAT_DIELECTRIC, ordered), og, ob, NXHIP_K_SHADE, S, bounce));
-        if (in_use(NX_MAT_CONDUCTOR) && c->h.conductorMode == NX_CONDUCTOR_EXTENDED) shade.push_back(make_launch(shade_kernel_ptr(NX_MAT_CONDUCTOR, ordered), og, ob, NXHIP_K_SHADE, S, bounce));
-        if (shade.empty()) shade.push_back(make_launch(shade_kernel_ptr(NX_MAT_DIFFUSE, ordered), og, ob, NXHIP_K_SHADE, S, bounce));  // (a level cannot be empty)
-        // serial slot order needs the kernels one after the other; so do several passes in flight, which would otherwise ask
-        // for four hardware queues per slot (the material kernels of one bounce serialise on the CUs anyway: each grid fills them)
-        if (ordered || serial_shade(c)) for (auto& l : shade) levels.push_back({l});
-        else levels.push_back(shade);
+        if (in_use(NX_MAT_DIFFUSE)) shade.push_back(make_launch(shade_kernel_ptr(NX_MAT_DIFFUSE), og, ob, NXHIP_K_SHADE, S, bounce));
+        if (in_use(NX_MAT_PLASTIC)) shade.push_back(make_launch(shade_kernel_ptr(NX_MAT_PLASTIC), og, ob, NXHIP_K_SHADE, S, bounce));
+        if (in_use(NX_MAT_DIELECTRIC)) shade.push_back(make_launch(shade_kernel_ptr(NX_MAT_DIELECTRIC), og, ob, NXHIP_K_SHADE, S, bounce));
+        if (in_use(NX_MAT_CONDUCTOR) && c->h.conductorMode == NX_CONDUCTOR_EXTENDED) shade.push_back(make_launch(shade_kernel_ptr(NX_MAT_CONDUCTOR), og, ob, NXHIP_K_SHADE, S, bounce));
+        if (shade.empty()) shade.push_back(make_launch(shade_kernel_ptr(NX_MAT_DIFFUSE), og, ob, NXHIP_K_SHADE, S, bounce));  // (a level cannot be empty)
+        // serial slot order needs the kernels one after the other
+        for (auto& l : shade) levels.push_back({l});
         levels.push_back({make_launch(trace_kernel_ptr(false, stats), traceBlocks, kTraceBlockThreads, NXHIP_K_TRACE, S, bounce | thinFlag),
                           make_launch(trace_kernel_ptr(true, stats), shadowBlocks, kTraceBlockThreads, NXHIP_K_SHADOW, S, bounce | thinFlag)});
         thin_level(bounce);
@@ -2001,10 +1969,9 @@ constexpr size_t kMaxGraphInstances = 8;
 
 static int pass_graph(nxhip_ctx* c, PassSlot* q, hipGraphExec_t* execOut)
 {
-    const bool serial = serial_shade(c);
     const int blocks = trace_blocks(c, c->traceBlocks), tail = tail_bounce(c), flavor = pass_flavor(c);
     for (auto& g : q->graphs)
-        if (g.serialShade == serial && g.traceBlocks == blocks && g.tailBounce == tail && g.flavor == flavor) {
+        if (g.traceBlocks == blocks && g.tailBounce == tail && g.flavor == flavor) {
             *execOut = g.exec;
             return NXHIP_OK;
         }
@@ -2019,7 +1986,6 @@ static int pass_graph(nxhip_ctx* c, PassSlot* q, hipGraphExec_t* execOut)
         q->graphs.erase(q->graphs.begin());
     }
     PassSlot::GraphInstance inst;
-    inst.serialShade = serial;
     inst.traceBlocks = blocks;
     inst.tailBounce = tail;
     inst.flavor = flavor;

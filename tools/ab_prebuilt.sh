@@ -1,12 +1,12 @@
 #!/bin/bash
 # Round-robin A/B of library variants built beforehand (nexus_amd/lib/variants/lib_<tag>.so, or "main" = the product library):
-#   ROUNDS=3 ARGS="--steps 256 --warmup 64" OUT=gpurun_out/ab1 tools/ab_prebuilt.sh main r2 nostall ...
+#   ROUNDS=3 ARGS="--steps 256 --warmup 64" OUT=bench_out/ab1 tools/ab_prebuilt.sh main parent ...
 # Prints per-variant medians of Msamples/s and of the closest-hit / any-hit trace time per frame.
 ROUNDS=${ROUNDS:-3}
 ARGS=${ARGS:---steps 256 --warmup 64}
 OUT=${OUT:-gpurun_out/ab}
 mkdir -p $OUT
-# A tag may carry environment settings for the run: "main+NX_ANY_FIRST=1" = the product library with that variable (and
+# A tag may carry environment settings for the run: "main+NX_THIN_LANES=8" = the product library with that variable (and
 # NX_TUNING_KNOBS=1) set; files are named after the whole tag.
 lib_of() { local t=${1%%+*}; if [ "$t" = main ]; then echo nexus_amd/lib/libnexus_amd.so; else echo nexus_amd/lib/variants/lib_$t.so; fi; }
 env_of() { case "$1" in *+*) echo "NX_TUNING_KNOBS=1 ${1#*+}" | tr '+' ' ';; esac; }

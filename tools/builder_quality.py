@@ -15,9 +15,9 @@ sys.path.insert(0, ROOT)
 from nexus_amd import capi, loaders, pod, scenegen  # noqa: E402
 
 IDENT = np.eye(4, dtype=np.float32).reshape(16)
-# device builders: (clustering radius, 0 = radix tree; collapse: the SAH cost table, or round 2's greedy rule)
-DEVICE = {"SAH device": (-1, "sah"), "PLOC r16": (16, "sah"), "PLOC r8": (8, "sah"), "LBVH": (0, "sah"), "PLOC r16 greedy": (16, "greedy"), "LBVH greedy": (0, "greedy")}
-BUILDERS = tuple(os.environ["BQ_BUILDERS"].split(",")) if os.environ.get("BQ_BUILDERS") else ("host SAH", "SAH device", "PLOC r16", "PLOC r8", "LBVH", "PLOC r16 greedy", "LBVH greedy")
+# device builders: clustering radius (0 = radix tree, -1 = SAH); every one collapses with the SAH cost table
+DEVICE = {"SAH device": -1, "PLOC r16": 16, "PLOC r8": 8, "LBVH": 0}
+BUILDERS = tuple(os.environ["BQ_BUILDERS"].split(",")) if os.environ.get("BQ_BUILDERS") else ("host SAH", "SAH device", "PLOC r16", "PLOC r8", "LBVH")
 
 
 def meshes():
@@ -66,10 +66,7 @@ def main():
                 t_build = time.time() - t0
                 bid = ctx.upload_blas(nodes, tris, idx)
             else:
-                radius, collapse = DEVICE[builder]
-                os.environ["NX_TUNING_KNOBS"] = "1"
-                os.environ["NX_DEVICE_COLLAPSE"] = collapse  # read by every build
-                ctx.set_device_builder(radius)
+                ctx.set_device_builder(DEVICE[builder])
                 ctx.build_blas(tris[:64])  # first use: code objects
                 ctx.clear_blas()
                 ctx.sync()

@@ -19,8 +19,9 @@ ap.add_argument("passes", nargs="+")
 a = ap.parse_args()
 
 # kernel classes: name pattern -> the unit its counters are divided by (rays traced; queue items processed)
-# (shade: the one material launch of the SCAN pipeline, or the classic per-type kernels; logic: the classic logic kernel, or what the SCAN pipeline keeps of it
-#  under NX_SCAN_SEPARATE; thin: the launch behind a level's trace launches that finishes the rays their dry waves handed over)
+# (shade: the one material launch of the SCAN pipeline, or the classic per-type kernels; logic: the classic logic kernel, or — in profiles of
+#  earlier rounds — the SCAN pipeline's separate miss kernel; thin: the launch behind a level's trace launches that finishes the rays their dry
+#  waves handed over)
 KERNELS = {"trace_closest": ("trace_kernel<false, false",), "trace_shadow": ("trace_kernel<true, false",), "logic": ("logic_kernel<", "miss_scan_kernel"),
            "shade": ("shade_kernel<", "shade_scan_kernel"), "thin": ("thin_kernel",)}
 bench = json.load(open(a.bench))
