@@ -719,11 +719,13 @@ class Context:
         return int(out[0]), int(out[1])
 
     def read_entry_states(self):
-        """(runs, 20) int32: the entry states of the last pass; column 19 = node steps saved, 16 = stack entries, 18 = instance record"""
+        """(runs, 40) int32: the entry states of the last pass; column 19 = node steps saved, 16 = stack entries, 18 = instance record,
+        31 = instance record of the triangle the walk consumed (-1: none), 35 = triangles it skipped, 38 / 39 = the run's hit-distance
+        bounds after the consumed triangle (float32 bits)"""
         self.L.nxhip_read_entry_states.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
         n = C.c_uint32(0)
         check(self.L.nxhip_read_entry_states(self.h, None, 0, C.byref(n)), "nxhip_read_entry_states")
-        out = np.zeros((n.value, 20), np.int32)
+        out = np.zeros((n.value, 40), np.int32)
         if n.value:
             check(self.L.nxhip_read_entry_states(self.h, _ptr(out), n.value, C.byref(n)), "nxhip_read_entry_states")
         return out

@@ -197,8 +197,24 @@ struct __attribute__((aligned(16))) EntryState {
     int32_t instSp;    // -1: in the TLAS
     int32_t leafSlot;  // instance record (TLAS leaf order) the state is inside of, -1: none
     int32_t steps;     // node steps taken (0: the state is the root's; the kernel then starts as usual)
+    // Everything else the install needs, so that it is 16-byte loads from this one address and none depends on another:
+    const NX_G uint4* nodes;   // leafSlot >= 0: that instance's BLAS arrays (InstTrav::nodes / isect)
+    const NX_G float4* isect;
+    // The triangle the walk CONSUMED because every ray of the run hits it (at most one): its record in the intersection stream's own
+    // 48-byte form — p0 | triangle word, edge0, edge1 — so that the install runs the loop's Moeller-Trumbore test on the same operands.
+    // The w words of the edges, which the test does not read, carry the walk's bookkeeping (test hooks).
+    float triP0[3];
+    uint32_t triWord;  // the record's triangle word (p0.w)
+    float triE0[3];
+    int32_t triLeaf;   // instance record (TLAS leaf order) the triangle is in, -1: none consumed
+    float triE1[3];
+    uint32_t skipped;  // triangles the walk skipped because every ray of the run misses them
+    uint32_t triInst;  // instance word of the consumed triangle (InstTrav::instIdx), 0xffffffff: none consumed
+    uint32_t instIdx;  // leafSlot >= 0: that instance's word (InstTrav::instIdx)
+    float hitLo, hitHi;  // every ray's hit distance after the consumed triangle lies in [hitLo, hitHi] (1e30: none consumed)
 };
-static_assert(sizeof(EntryState) == 80, "EntryState layout");
+static_assert(sizeof(EntryState) == 160 && offsetof(EntryState, nodes) == 80 && offsetof(EntryState, triP0) == 96 && offsetof(EntryState, triInst) == 144,
+              "EntryState layout: ten 16-byte words");
 struct ShadowQueue {
     NX_G float4* rayO;
     NX_G float4* rayD;
@@ -372,7 +388,7 @@ constexpr uint64_t layout_stamp()
     const uint64_t w[] = {
         sizeof(DeviceState), offsetof(DeviceState, camera), offsetof(DeviceState, envSampling), offsetof(DeviceState, localCount), offsetof(DeviceState, pixelMap),
         offsetof(DeviceState, radiance), offsetof(DeviceState, trace), offsetof(DeviceState, shadow), offsetof(DeviceState, material), offsetof(DeviceState, counters),
-        offsetof(DeviceState, frame), offsetof(DeviceState, traceStats), offsetof(DeviceState, scanStatus), offsetof(DeviceState, entry), offsetof(DeviceState, entryRuns), offsetof(DeviceState, debugRequeue), offsetof(DeviceState, thinStates), offsetof(DeviceState, leafOfInstance), sizeof(ThinState), offsetof(ThinState, stack), offsetof(DeviceState, thinClosest), offsetof(DeviceState, thinCapacity), offsetof(DeviceState, thinIters), offsetof(DeviceState, thinPoolLimit), offsetof(Counters, thinCount), sizeof(EntryState), offsetof(EntryState, sp), offsetof(Counters, scanTicket), offsetof(FrameState, scanEpoch),
+        offsetof(DeviceState, frame), offsetof(DeviceState, traceStats), offsetof(DeviceState, scanStatus), offsetof(DeviceState, entry), offsetof(DeviceState, entryRuns), offsetof(DeviceState, debugRequeue), offsetof(DeviceState, thinStates), offsetof(DeviceState, leafOfInstance), sizeof(ThinState), offsetof(ThinState, stack), offsetof(DeviceState, thinClosest), offsetof(DeviceState, thinCapacity), offsetof(DeviceState, thinIters), offsetof(DeviceState, thinPoolLimit), offsetof(Counters, thinCount), sizeof(EntryState), offsetof(EntryState, sp), offsetof(EntryState, triP0), offsetof(EntryState, triInst), offsetof(Counters, scanTicket), offsetof(FrameState, scanEpoch),
         (uint64_t)kScanKinds, (uint64_t)kScanWords, (uint64_t)kScanEpochLimit, (uint64_t)kShadeBlockOrderedThreads,
         sizeof(Counters), sizeof(RegionCounters), offsetof(RegionCounters, traceShadowSize), offsetof(RegionCounters, materialSize), offsetof(RegionCounters, traceHead),
         offsetof(RegionCounters, shadowHead), offsetof(RegionCounters, scanTile), offsetof(Counters, orderedBase), offsetof(Counters, tailHead),

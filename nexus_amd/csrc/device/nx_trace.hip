@@ -397,7 +397,10 @@ NXD ThinResult thin_wave_search(const DeviceState* __restrict__ S, lds_u64* cons
     return r;
 }
 
-template <bool ANY_HIT, bool STATS>
+// ENTRY: the primary launch of a pass with entry points (nx_entry.hip) — the only launch that installs entry states at refill; the
+// other launches are compiled without that code (its loads and the consumed triangle's test would cost every closest-hit launch's
+// refill registers).  The counting variant keeps it either way.
+template <bool ANY_HIT, bool STATS, bool ENTRY = false>
 // 5 waves per SIMD for both variants (96 VGPRs, no spills in the loop).  Before an instance entry also carried its BLAS
 // root (17 more live registers in the fetch), 6 waves at 80 VGPRs was the best point (5: -3 %, 7: -0.3 %, 8: -1.5 %); with it,
 // 6 waves spill 23 VGPRs inside the loop (-10 %), 5 and 4 measure +4.5 % and +1 % over the old kernel at 6.
@@ -412,7 +415,7 @@ __global__ void __launch_bounds__(kTraceBlock) trace_kernel(const DeviceState* _
     const int bounce = bounceArg & 0xff;
     const bool scan = !ANY_HIT && (bounceArg & kTraceScanFlag) != 0;
     // ... | kTraceEntryFlag: the rays name the entry state of their run (rayO.w): installed at refill instead of the root's
-    const bool entryLaunch = !ANY_HIT && (bounceArg & kTraceEntryFlag) != 0 && S->entry != nullptr;
+    const bool entryLaunch = !ANY_HIT && (ENTRY || STATS) && (bounceArg & kTraceEntryFlag) != 0 && S->entry != nullptr;
     // ... | kTraceThinFlag: the last long rays of a dry wave may be handed to the thin kernel (below)
     bool thinAllowed = !STATS && (bounceArg & kTraceThinFlag) != 0;
     const int thinLanes = (int)(S->thinLanes & 0xffu);
@@ -673,14 +676,35 @@ __global__ void __launch_bounds__(kTraceBlock) trace_kernel(const DeviceState* _
                     xformed = false;
                     nodes = tlasNodes;
                     if (STATS) nRays++;
-                    if (!ANY_HIT && entryLaunch) {
-                        // the state the first node steps of this ray's run provably lead to (nx_entry.hip), instead of the root's
+                    if (!ANY_HIT && (ENTRY || STATS) && entryLaunch) {
+                        // the state the first node steps of this ray's run provably lead to (nx_entry.hip), instead of the root's: 16-byte
+                        // loads from the one address the run's rays share, none of them behind another
                         const uint32_t en = __float_as_uint(o.w) >> kRayEntryShift;
                         if (en != 0u) {
                             const NX_G EntryState* es = entryTable + (en - 1u);
                             const int4 hdr = *(const NX_G int4*)&es->sp;  // sp, instSp, leafSlot, steps
                             if (hdr.w > 0) {
                                 const uint4 g = *(const NX_G uint4*)&es->ng;
+                                const uint4 tail = *(const NX_G uint4*)&es->triInst;  // triInst, instIdx, hitLo, hitHi
+                                if (tail.x != 0xffffffffu) {
+                                    // the triangle the walk consumed because every ray of the run hits it: this ray's own record for it, with
+                                    // the triangle step's arithmetic below on the same operands (identity instances: the ray is the world ray)
+                                    const float4 t0 = *(const NX_G float4*)&es->triP0[0], t1 = *(const NX_G float4*)&es->triE0[0], t2 = *(const NX_G float4*)&es->triE1[0];
+                                    const f3 p0 = mk3(t0.x, t0.y, t0.z), edge0 = mk3(t1.x, t1.y, t1.z), edge1 = mk3(t2.x, t2.y, t2.z);
+                                    const f3 rayCrossEdge1 = cross3(dir, edge1);
+                                    const float det = dot3(edge0, rayCrossEdge1);
+                                    const float invDet = 1.0f / det;
+                                    const f3 sv = org - p0;
+                                    const float u = invDet * dot3(sv, rayCrossEdge1);
+                                    const f3 sCrossEdge0 = cross3(sv, edge0);
+                                    const float v = invDet * dot3(dir, sCrossEdge0);
+                                    const float t = invDet * dot3(edge1, sCrossEdge0);
+                                    if (!(u < 0.0f || u > 1.0f) && !(v < 0.0f || u + v > 1.0f) && (t > 0.0f && t < hitT)) {
+                                        hitT = t; hitU = u; hitV = v;
+                                        hitTri = __float_as_uint(t0.w);
+                                        hitInst = tail.x;
+                                    }
+                                }
                                 ng = make_uint2(g.x, g.y);
                                 tg = make_uint2(g.z, g.w);
 #pragma unroll
@@ -691,10 +715,9 @@ __global__ void __launch_bounds__(kTraceBlock) trace_kernel(const DeviceState* _
                                 }
                                 instSp = hdr.y;
                                 if (hdr.z >= 0) {  // inside an (identity) instance: its BLAS arrays and index
-                                    const NX_G InstTrav* rec = instTrav + hdr.z;
-                                    nodes = rec->nodes;
-                                    isect = rec->isect;
-                                    instIdx = rec->instIdx;
+                                    nodes = es->nodes;
+                                    isect = es->isect;
+                                    instIdx = tail.y;
                                 }
                             }
                         }
@@ -922,6 +945,7 @@ __global__ void __launch_bounds__(kTraceBlock) trace_kernel(const DeviceState* _
 }
 
 template __global__ void trace_kernel<false, false>(const DeviceState*, int);
+template __global__ void trace_kernel<false, false, true>(const DeviceState*, int);
 template __global__ void trace_kernel<false, true>(const DeviceState*, int);
 template __global__ void trace_kernel<true, false>(const DeviceState*, int);
 template __global__ void trace_kernel<true, true>(const DeviceState*, int);
@@ -1026,6 +1050,7 @@ __global__ void __launch_bounds__(kTraceBlock) thin_kernel(const DeviceState* __
 }
 
 const void* thin_kernel_ptr() { return (const void*)thin_kernel; }
+const void* trace_entry_kernel_ptr() { return (const void*)trace_kernel<false, false, true>; }  // the primary launch with entry points
 
 const void* trace_kernel_ptr(bool anyHit, bool stats)
 {

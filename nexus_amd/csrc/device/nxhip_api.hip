@@ -25,6 +25,7 @@ const void* count_scan_kernel_ptr();
 const void* inst_code_kernel_ptr();
 const void* entry_state_kernel_ptr();
 const void* thin_kernel_ptr();
+const void* trace_entry_kernel_ptr();
 const void* begin_frame_kernel_ptr();
 const void* hook_sizes_kernel_ptr();
 const void* generate_kernel_ptr();
@@ -1836,12 +1837,15 @@ std::vector<std::vector<Launch>> frame_levels(nxhip_ctx* c, PassSlot* q)
     const bool entry = (pass_flavor(c) & kFlavorEntry) != 0;
     if (entry) {  // beside the generate kernel: the entry states of the primary rays' runs (nx_entry.hip), read by the launch below
         // (table and count come from the slot's DeviceState: a graph node holds no pointer that a re-allocation could leave dangling)
-        levels.back().push_back(make_launch(entry_state_kernel_ptr(), (int)((q->entryRuns + 63u) / 64u), 64, NXHIP_K_GENERATE, S));
+        // (eight lanes per run: a workgroup of 64 walks eight runs)
+        levels.back().push_back(make_launch(entry_state_kernel_ptr(), (int)((q->entryRuns + 7u) / 8u), 64, NXHIP_K_GENERATE, S));
     }
     const int traceBlocks = trace_blocks(c, c->traceBlocks), shadowBlocks = trace_blocks(c, c->shadowBlocks);
     // (the dry waves of a pass's trace launches may hand their last long rays to the thin kernel: nx_trace.hip)
     const int thinFlag = (pass_flavor(c) & kFlavorThin) ? kTraceThinFlag : 0;
-    levels.push_back({make_launch(trace_kernel_ptr(false, stats), traceBlocks, kTraceBlockThreads, NXHIP_K_TRACE, S, (entry ? kTraceEntryFlag : 0) | thinFlag)});
+    // (with entry points the primary launch is its own kernel instance: the only one that carries the install code)
+    levels.push_back({make_launch((entry && !stats) ? trace_entry_kernel_ptr() : trace_kernel_ptr(false, stats), traceBlocks, kTraceBlockThreads, NXHIP_K_TRACE, S,
+                                  (entry ? kTraceEntryFlag : 0) | thinFlag)});
     // behind the trace launch(es) of a level: the rays their dry waves handed over, a wave each (thin_kernel)
     // — each trace launch of the level gets its own, chained to it alone, so that the closest-hit rays' searches run beside whatever
     // the any-hit launch still has to do (it is the longer one of the early levels) and the other way round in the late ones
