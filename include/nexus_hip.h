@@ -213,6 +213,11 @@ int nxhip_debug_set_thin_pool(nxhip_ctx *ctx, uint32_t slots);
 int nxhip_debug_thin_counts(nxhip_ctx *ctx, int32_t counts[2]);
 /* ... and of level `bounce` (0 = the primary rays) of the pass rendered last: what its trace launches handed over (closest-hit, any-hit). */
 int nxhip_debug_thin_counts_of_pass(nxhip_ctx *ctx, uint32_t bounce, int32_t counts[2]);
+/* Test hook: the continuation rays the material launch of `bounce` of the pass rendered last did not queue because their Russian-
+ * roulette draw was lost when they were made (SCAN pipeline, pixel-keyed random numbers, no environment map and a black
+ * background: nothing could read what they hit).  nxhip_read_queue_sizes counts them in traceSize[bounce] as the reference does;
+ * this is the part of that size no trace launch saw.  0 for every other kind of pass. */
+int nxhip_debug_ended_rays_of_pass(nxhip_ctx *ctx, uint32_t bounce, int32_t *count);
 
 /* ---- rendering ----------------------------------------------------------------------------------- */
 

@@ -27,7 +27,7 @@ HIP_SYMBOLS = [
     "nxhip_read_kernel_times", "nxhip_read_graph_timeline", "nxhip_has_gfx950_code", "nxhip_build_info", "nxhip_set_pixel_order", "nxhip_sync_timeout", "nxhip_debug_set_requeue", "nxhip_debug_thin_counts_of_pass", "nxhip_debug_write_blas_node", "nxhip_rebuild_tlas", "nxhip_read_tlas_index", "nxhip_release_queues", "nxhip_set_device_builder",
     "nxhip_set_instance_transforms", "nxhip_read_tlas", "nxhip_set_passes_in_flight", "nxhip_set_tail_bounce", "nxhip_set_entry_points", "nxhip_read_entry_states", "nxhip_debug_set_thin", "nxhip_debug_set_thin_pool", "nxhip_debug_thin_counts", "nxhip_build_blas", "nxhip_read_blas", "nxhip_set_env_sampling",
     "nxhip_tile_pixel_map", "nxhip_mgpu_unique_id", "nxhip_mgpu_init", "nxhip_mgpu_attach", "nxhip_mgpu_gather", "nxhip_mgpu_read_rgba8",
-    "nxhip_mgpu_read_accumulation", "nxhip_mgpu_shutdown", "nxhip_fmath_batch", "nxhip_abi_stamp", "nxhip_check_library", "nxhip_build_blas_batch", "nxhip_read_blas_batch", "nxhip_debug_set_scan_epoch",
+    "nxhip_mgpu_read_accumulation", "nxhip_mgpu_shutdown", "nxhip_fmath_batch", "nxhip_abi_stamp", "nxhip_check_library", "nxhip_build_blas_batch", "nxhip_read_blas_batch", "nxhip_debug_set_scan_epoch", "nxhip_debug_ended_rays_of_pass",
 ]
 HOST_SYMBOLS = [
     "nxh_bvh8_build", "nxh_tlas_build", "nxh_tlas_refit", "nxh_bvh8_node_count", "nxh_bvh8_prim_count", "nxh_bvh8_nodes",
@@ -689,6 +689,13 @@ class Context:
         self.L.nxhip_debug_thin_counts_of_pass.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
         check(self.L.nxhip_debug_thin_counts_of_pass(self.h, bounce, c), "nxhip_debug_thin_counts_of_pass")
         return int(c[0]), int(c[1])
+
+    def debug_ended_rays_of_pass(self, bounce):
+        """continuation rays the material launch of `bounce` of the last pass did not queue: their roulette draw was lost already (include/nexus_hip.h)"""
+        n = C.c_int32(0)
+        self.L.nxhip_debug_ended_rays_of_pass.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_int32)]
+        check(self.L.nxhip_debug_ended_rays_of_pass(self.h, bounce, C.byref(n)), "nxhip_debug_ended_rays_of_pass")
+        return int(n.value)
 
     def debug_set_requeue(self, on=True):
         """test hook: the trace kernels hand the same rays out again and again (include/nexus_hip.h)"""

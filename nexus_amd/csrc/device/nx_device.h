@@ -166,6 +166,10 @@ constexpr int kTraceThinFlag = 0x400;
 // thin_kernel's argument: ... | kThinClosestOnly / kThinAnyOnly = one of the two lists only (the pass graph gives each trace launch of a
 // level its own thin launch, so that the closest-hit rays' searches run beside whatever the any-hit launch still has to do)
 constexpr int kThinClosestOnly = 0x800, kThinAnyOnly = 0x1000;
+// shade_scan_kernel's `bounce` argument: bounce | kShadeDropEnded = the pass has no miss type and its random numbers are keyed by
+// the pixel, so a continuation ray whose kRaySurvives draw is lost can reach nothing anybody reads — a hit gets code 0, a miss
+// adds a black background that no kernel looks at — and is not queued at all: counted (RegionCounters::endedSize), not traced
+constexpr int kShadeDropEnded = 0x2000;
 
 // The traversal state of a ray a dry trace wave hands to thin_kernel (nx_trace.hip, round 6): everything the loop keeps per lane at its
 // loop top, so that the wave-wide search CONTINUES the ray instead of starting it again at the TLAS root — the stack's groups and the
@@ -254,7 +258,10 @@ struct RegionCounters {
     // SCAN pipeline (nx_wavefront.hip shade_scan_kernel): tiles of this region's trace queue handed out so far to the material
     // kernel of a type, beyond the one every workgroup takes by its rank
     int32_t scanTile[5][kMaxBounceSlots];  // [NX_MAT_*], [kScanMiss]: the misses (a fifth "type" of the one material launch)
-    int32_t pad_[2048 - 13 * kMaxBounceSlots];
+    // continuation rays of this region the material launch of a bounce did NOT queue because their roulette draw was lost already
+    // (kShadeDropEnded); the reference queues them, so the trace-queue size the library reports is traceSize + endedSize
+    int32_t endedSize[kMaxBounceSlots];
+    int32_t pad_[2048 - 14 * kMaxBounceSlots];
 };
 static_assert(sizeof(RegionCounters) == 8192, "one region's counters per 8 KiB");
 constexpr int kRegionStride = (int)(sizeof(RegionCounters) / sizeof(int32_t));  // distance between the same word of two regions
@@ -391,7 +398,7 @@ constexpr uint64_t layout_stamp()
         offsetof(DeviceState, frame), offsetof(DeviceState, traceStats), offsetof(DeviceState, scanStatus), offsetof(DeviceState, entry), offsetof(DeviceState, entryRuns), offsetof(DeviceState, debugRequeue), offsetof(DeviceState, thinStates), offsetof(DeviceState, leafOfInstance), sizeof(ThinState), offsetof(ThinState, stack), offsetof(DeviceState, thinClosest), offsetof(DeviceState, thinCapacity), offsetof(DeviceState, thinIters), offsetof(DeviceState, thinPoolLimit), offsetof(Counters, thinCount), sizeof(EntryState), offsetof(EntryState, sp), offsetof(EntryState, triP0), offsetof(EntryState, triInst), offsetof(Counters, scanTicket), offsetof(FrameState, scanEpoch),
         (uint64_t)kScanKinds, (uint64_t)kScanWords, (uint64_t)kScanEpochLimit, (uint64_t)kShadeBlockOrderedThreads,
         sizeof(Counters), sizeof(RegionCounters), offsetof(RegionCounters, traceShadowSize), offsetof(RegionCounters, materialSize), offsetof(RegionCounters, traceHead),
-        offsetof(RegionCounters, shadowHead), offsetof(RegionCounters, scanTile), offsetof(Counters, orderedBase), offsetof(Counters, tailHead),
+        offsetof(RegionCounters, shadowHead), offsetof(RegionCounters, scanTile), offsetof(RegionCounters, endedSize), offsetof(Counters, orderedBase), offsetof(Counters, tailHead),
         sizeof(ShadeInst), offsetof(ShadeInst, tris), offsetof(ShadeInst, material), offsetof(DeviceState, shadeInst), sizeof(InstTrav), offsetof(InstTrav, nodes), offsetof(InstTrav, instIdx), offsetof(InstTrav, root), sizeof(BlasDev), offsetof(BlasDev, nodeCount),
         sizeof(TextureDev), sizeof(TraceQueue), sizeof(ShadowQueue), sizeof(MaterialQueue), sizeof(FrameState), sizeof(TraceStatsDev),
         (uint64_t)kNodeStride, (uint64_t)kTriStride, (uint64_t)kShadeTriStride, (uint64_t)kQueueShards, (uint64_t)kQueueShardSlack, (uint64_t)kRegionStride, (uint64_t)kMaxBounceSlots,

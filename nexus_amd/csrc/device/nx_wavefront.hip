@@ -952,8 +952,8 @@ static_assert(kScanRing >= kShadeBlock + 4 * kShadeBlock && (kScanRing & (kScanR
 // that is this type's to shade varies from none to all with what the camera sees there, so a static split leaves most workgroups
 // waiting for the few whose tiles were full (measured: +40 % on the kernels).
 template <int TYPE>
-NXD void shade_scan_type(const DeviceState* __restrict__ S, const int bounce, const int region, const int inRegion, const int per, const int firstTile, const int staticTiles,
-                         int* const sRing, int* const sHead, int* const sTicket)
+NXD void shade_scan_type(const DeviceState* __restrict__ S, const int bounce, const bool dropEnded, const int region, const int inRegion, const int per, const int firstTile,
+                         const int staticTiles, int* const sRing, int* const sHead, int* const sTicket)
 {
     // TYPE == kScanMiss: the rays that missed (code kHitCodeMiss) — what is left of the logic step when a miss can contribute: the
     // environment (flat colour or map, MIS-weighted against the environment sampler) added to the path's radiance, PathTracer.cu:152-164
@@ -985,6 +985,7 @@ NXD void shade_scan_type(const DeviceState* __restrict__ S, const int bounce, co
     const int lane = threadIdx.x & (kWave - 1);
     const unsigned long long laneLt = (1ull << lane) - 1ull;
     int tail = 0, head = 0;  // ring positions [tail, head) hold found slots not shaded yet (uniform)
+    int ended = 0;           // continuation rays of this wave that were not queued (dropEnded; uniform over the wave)
 
     // shades `take` <= 256 slots from the ring's tail
     const auto shade_batch = [&](const int take) {
@@ -1045,6 +1046,21 @@ NXD void shade_scan_type(const DeviceState* __restrict__ S, const int bounce, co
                              },
                              wantShadow, sh, wantTrace, updatePath, nextOrigin, nextDir, nextThroughput, nextPdf);
         }
+        // the path state that goes with the ray: the new one, or — a pass-through — the one the path arrived with
+        const float4 tpNext = updatePath ? make_float4(nextThroughput.x, nextThroughput.y, nextThroughput.z, nextPdf) : tpdf;
+        // the next logic step's Russian roulette, drawn here (kRaySurvives): its random number is keyed by the pixel — or, with
+        // slot-keyed numbers, by the slot the ray goes to — the next bounce and the frame, its probability is the throughput
+        // just computed.  dropEnded (pixel-keyed numbers, no miss type in the pass): the draw comes before the slot, and a ray that
+        // lost it gets none — whatever it hit, nobody would read the record (see kShadeDropEnded).  The shadow request stays.
+        bool survives = true;
+        if (dropEnded) {
+            if (wantTrace) {
+                uint32_t rng = seed_for(S, 0u, pixelIdx, (uint32_t)bounce + 1u, 0u, frame);
+                survives = rng_next(rng) < maxcomp3(mk3(tpNext.x, tpNext.y, tpNext.z));
+            }
+            ended += __popcll(__ballot(wantTrace && !survives));
+            wantTrace = wantTrace && survives;
+        }
         const bool want[2] = {wantShadow, wantTrace};
         int slot[2];
         slots.alloc(want, slot, 0, region);
@@ -1055,13 +1071,10 @@ NXD void shade_scan_type(const DeviceState* __restrict__ S, const int bounce, co
             S->shadow.radiance[shadowSlot] = make_float4(sh.radiance.x, sh.radiance.y, sh.radiance.z, 0.0f);
         }
         if (wantTrace) {
-            // the path state that goes with the ray: the new one, or — a pass-through — the one the path arrived with
-            const float4 tpNext = updatePath ? make_float4(nextThroughput.x, nextThroughput.y, nextThroughput.z, nextPdf) : tpdf;
-            // the next logic step's Russian roulette, drawn here (kRaySurvives): its random number is keyed by the pixel — or, with
-            // slot-keyed numbers, by the slot the ray goes to — the next bounce and the frame, its probability is the throughput
-            // just computed
-            uint32_t rng = seed_for(S, (uint32_t)traceSlot, pixelIdx, (uint32_t)bounce + 1u, 0u, frame);
-            const bool survives = rng_next(rng) < maxcomp3(mk3(tpNext.x, tpNext.y, tpNext.z));
+            if (!dropEnded) {
+                uint32_t rng = seed_for(S, (uint32_t)traceSlot, pixelIdx, (uint32_t)bounce + 1u, 0u, frame);
+                survives = rng_next(rng) < maxcomp3(mk3(tpNext.x, tpNext.y, tpNext.z));
+            }
             out.rayO[traceSlot] = make_float4(nextOrigin.x, nextOrigin.y, nextOrigin.z, __uint_as_float((updatePath ? 0u : kRayPassThrough) | (survives ? kRaySurvives : 0u)));
             out.rayD[traceSlot] = make_float4(nextDir.x, nextDir.y, nextDir.z, __uint_as_float(pixelIdx));
             out.tp[traceSlot] = tpNext;
@@ -1118,6 +1131,15 @@ NXD void shade_scan_type(const DeviceState* __restrict__ S, const int bounce, co
     if (head - tail > 0) shade_batch(head - tail);
     // the items this workgroup shaded, for nxhip_read_queue_sizes (the reference's per-type queue sizes, D_QueueSize)
     if (!kMiss && threadIdx.x == 0 && head) atomicAdd(&C->region[region].materialSize[kMiss ? 0 : TYPE][bounce], head);
+    // ... and the continuation rays it did not queue: the waves' counts meet in the ring's head word, one add per workgroup
+    if (!kMiss && dropEnded) {
+        __syncthreads();  // everybody has read the head
+        if (threadIdx.x == 0) *sHead = 0;
+        __syncthreads();
+        if (lane == 0 && ended) atomicAdd(sHead, ended);
+        __syncthreads();
+        if (threadIdx.x == 0 && *sHead) atomicAdd(&C->region[region].endedSize[bounce], *sHead);
+    }
 }
 
 // All material types of a bounce in ONE launch (`typeMask`: bit NX_MAT_* = that type has a kernel in this pass; bit kScanMiss = the
@@ -1125,8 +1147,10 @@ NXD void shade_scan_type(const DeviceState* __restrict__ S, const int bounce, co
 // workgroups start on different types (rank modulo the number of types) and move on to the next type when theirs has no tile
 // left, so the types run side by side, the launch ends when the last tile of the last type does, and a bounce costs one material
 // launch instead of one per type (the reference: four, PathTracer.cpp:116-120).  A single-bit mask is a per-type launch.
-__global__ void __launch_bounds__(kShadeBlock, NX_SHADE_WAVES) shade_scan_kernel(const DeviceState* __restrict__ S, const int bounce, const int typeMask)
+__global__ void __launch_bounds__(kShadeBlock, NX_SHADE_WAVES) shade_scan_kernel(const DeviceState* __restrict__ S, const int bounceArg, const int typeMask)
 {
+    const int bounce = bounceArg & 0xff;
+    const bool dropEnded = (bounceArg & kShadeDropEnded) != 0;  // (a property of the pass's shape: nxhip_api.hip pass_flavor)
     __shared__ int sRing[kScanRing];
     __shared__ int sHead, sTicket;
     const int region = (int)(blockIdx.x & (kQueueShards - 1));
@@ -1157,11 +1181,11 @@ __global__ void __launch_bounds__(kShadeBlock, NX_SHADE_WAVES) shade_scan_kernel
         const int starters = (ranks - want + nTypes - 1) / nTypes;  // workgroups whose first type this is: each takes the tile of its index
         const int first = step == 0 ? myIndex : -1;
         switch (type) {
-        case NX_MAT_DIFFUSE: shade_scan_type<NX_MAT_DIFFUSE>(S, bounce, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket); break;
-        case NX_MAT_PLASTIC: shade_scan_type<NX_MAT_PLASTIC>(S, bounce, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket); break;
-        case NX_MAT_DIELECTRIC: shade_scan_type<NX_MAT_DIELECTRIC>(S, bounce, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket); break;
-        case NX_MAT_CONDUCTOR: shade_scan_type<NX_MAT_CONDUCTOR>(S, bounce, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket); break;
-        case kScanMiss: shade_scan_type<kScanMiss>(S, bounce, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket); break;
+        case NX_MAT_DIFFUSE: shade_scan_type<NX_MAT_DIFFUSE>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket); break;
+        case NX_MAT_PLASTIC: shade_scan_type<NX_MAT_PLASTIC>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket); break;
+        case NX_MAT_DIELECTRIC: shade_scan_type<NX_MAT_DIELECTRIC>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket); break;
+        case NX_MAT_CONDUCTOR: shade_scan_type<NX_MAT_CONDUCTOR>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket); break;
+        case kScanMiss: shade_scan_type<kScanMiss>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket); break;
         default: break;
         }
     }

@@ -1797,7 +1797,7 @@ int tail_bounce(const nxhip_ctx* c)
 // kernel is in the graph only for a scene with an environment map or a background that is not exactly black — PathTracer.cu:
 // 152-164 adds throughput x background, and +0 changes nothing), and the logic kernel's variant (one item per thread under an
 // environment map).  Part of a graph instance's key, so a change of any of them picks or builds the matching instance.
-constexpr int kFlavorScan = 1, kFlavorMissKernel = 2, kFlavorEnvMap = 4, kFlavorEntry = 8, kFlavorThin = 16;
+constexpr int kFlavorScan = 1, kFlavorMissKernel = 2, kFlavorEnvMap = 4, kFlavorEntry = 8, kFlavorThin = 16, kFlavorDropEnded = 32;
 int pass_flavor(const nxhip_ctx* c)
 {
     int f = 0;
@@ -1812,6 +1812,10 @@ int pass_flavor(const nxhip_ctx* c)
         black = black && bits == 0u;
     }
     if (c->hdrMap.texels.p || !black) f |= kFlavorMissKernel;
+    // SCAN pipeline without a miss type: a continuation ray whose roulette draw is lost when it is made has no reader — its hit is
+    // dropped by code 0, its miss adds a black background no kernel is launched for — so the material launch does not queue it
+    // (kShadeDropEnded).  Pixel-keyed random numbers only: a slot-keyed draw needs the slot the ray goes to.
+    if (scan_pipeline(c) && !(f & kFlavorMissKernel) && c->h.rngMode == NX_RNG_PIXEL_KEYED) f |= kFlavorDropEnded;
     if (c->entryPoints) f |= kFlavorEntry;  // (the slot's table exists before its graph is asked for: ensure_entry_table)
     // The thin kernel (nx_trace.hip) pays when ONE pass runs at a time: the lanes a dry wave leaves idle are then idle SIMD time, and
     // a level ends with its slowest ray (driver command: mean of five repetitions 19.9 -> 19.0 ms, 512 frames in 64-frame passes one at a
@@ -1878,6 +1882,7 @@ std::vector<std::vector<Launch>> frame_levels(nxhip_ctx* c, PassSlot* q)
         levels[1][0].bounce |= kTraceScanFlag;
         thin_level(0 | kTraceScanFlag);
         const bool misses = pass_flavor(c) & kFlavorMissKernel;
+        const int dropFlag = (pass_flavor(c) & kFlavorDropEnded) ? kShadeDropEnded : 0;
         const int tailFrom = tail_bounce(c);
         for (int bounce = 1; bounce <= pathLength; bounce++) {
             if (bounce == tailFrom) {  // the rest of the pass in one launch
@@ -1888,7 +1893,7 @@ std::vector<std::vector<Launch>> frame_levels(nxhip_ctx* c, PassSlot* q)
             if (c->h.conductorMode != NX_CONDUCTOR_EXTENDED) mask &= ~(1 << NX_MAT_CONDUCTOR);
             if (mask == 0) mask = 1 << NX_MAT_DIFFUSE;  // (a level cannot be empty)
             if (misses) mask |= 1 << kScanMiss;
-            Launch shade = make_launch(shade_scan_kernel_ptr(), og, kShadeBlockThreads, NXHIP_K_SHADE, S, bounce);
+            Launch shade = make_launch(shade_scan_kernel_ptr(), og, kShadeBlockThreads, NXHIP_K_SHADE, S, bounce | dropFlag);
             shade.type = mask;
             shade.nargs = 3;
             levels.push_back({shade});
@@ -2307,6 +2312,23 @@ int nxhip_debug_thin_counts_of_pass(nxhip_ctx* c, uint32_t bounce, int32_t count
     return NXHIP_OK;
 }
 
+int nxhip_debug_ended_rays_of_pass(nxhip_ctx* c, uint32_t bounce, int32_t* count)
+{
+    NX_DEBUG_HOOK("nxhip_debug_ended_rays_of_pass");  // (first: a release library refuses whatever it is handed)
+    NX_CHECK_CTX(c);
+    if (!count || bounce >= (uint32_t)kMaxBounceSlots) return fail_invalid("nxhip_debug_ended_rays_of_pass: null destination or bounce out of range");
+    NX_HIP(hipSetDevice(c->device));
+    NX_SYNC_ALL(c);
+    const PassSlot* q = c->lastRendered ? c->lastRendered : static_cast<const PassSlot*>(c);
+    *count = 0;
+    for (int k = 0; k < kQueueShards; k++) {
+        int32_t n = 0;
+        NX_HIP(hipMemcpy(&n, &q->counters.as<Counters>()->region[k].endedSize[bounce], 4, hipMemcpyDeviceToHost));
+        *count += n;
+    }
+    return NXHIP_OK;
+}
+
 int nxhip_read_entry_states(nxhip_ctx* c, void* out, uint32_t capacityRuns, uint32_t* count)
 {
     NX_CHECK_CTX(c);
@@ -2557,7 +2579,8 @@ int nxhip_read_queue_sizes(nxhip_ctx* c, nxhip_queue_sizes* out)
     for (int k = 0; k < kQueueShards; k++)  // a queue's size = the sum over its regions
         for (int b = 0; b < kMaxBounceSlots; b++) {
             const RegionCounters& r = h.region[k];
-            out->traceSize[b] += r.traceSize[b];
+            // (the reference queues the continuation rays whose roulette draw is lost as well: D_QueueSize counts them)
+            out->traceSize[b] += r.traceSize[b] + r.endedSize[b];
             out->traceShadowSize[b] += r.traceShadowSize[b];
             out->diffuseSize[b] += r.materialSize[NX_MAT_DIFFUSE][b];
             out->plasticSize[b] += r.materialSize[NX_MAT_PLASTIC][b];
