@@ -50,6 +50,13 @@ public:
     // The order of the frame's paths: NXHIP_ORDER_ROWS (the reference's, default) or NXHIP_ORDER_TILES (8 x 8 pixel tiles: the rays a
     // wave fetches together are a compact block of the image; kept across OnResize).  nxhip_set_pixel_order.
     void SetPixelOrder(int order);
+    // Feature buffers of the camera ray's hit (nxhip_set_aov: albedo + coverage, shading normal + depth, accumulated like the colour;
+    // what Renderer::SetDenoise and any external denoiser or compositor need).  Off by default; switching them on starts the
+    // accumulation over (colour and features must cover the same frames).
+    void SetFeatureBuffers(bool on);
+    // The accumulated feature buffers as full-frame, row-major images (4 floats per pixel each), whatever the pixel order.  Not on a
+    // tile split (each rank holds its own tiles only).
+    void ReadFeatureBuffers(std::vector<float>& albedo4, std::vector<float>& normalDepth4);
     // Multi-GPU extension (no counterpart in the reference): one PathTracer per GPU, each renders and
     // accumulates the interleaved row tiles of its rank; Render() then ends with ONE RCCL gather of the accumulated tiles to
     // rank 0, whose GetPixelBuffer() returns the full frame.  `id128`: the 128 bytes rank 0 obtained from
@@ -71,6 +78,7 @@ private:
     std::vector<uint32_t> m_Pixels;
     bool m_PixelQueryPending = false;
     bool m_TileSplit = false;
+    int m_PixelOrder = 0;  // NXHIP_ORDER_* (SetPixelOrder)
     int m_Rank = 0;
 };
 

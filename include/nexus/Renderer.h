@@ -28,6 +28,19 @@ public:
     bool SaveScreenshot(const std::string& filepath);
     // Extension: the float accumulation as OpenEXR (scanline, uncompressed, 32-bit float R G B), top row first.
     bool SaveAccumulationEXR(const std::string& filepath);
+    // Extension (no counterpart in the reference, which shows the raw running mean): the edge-avoiding a-trous filter of the device
+    // layer (nxhip_denoise, default parameters) over the accumulated image.  SetDenoise(true) switches the feature buffers on and
+    // starts the accumulation over; from then on SaveScreenshot writes the DENOISED image.  The accumulation itself is never
+    // modified: rendering goes on, and SetDenoise(false) gives the raw image back.  Full-frame renderers only (no tile split).
+    void SetDenoise(bool on);
+    bool GetDenoise() const { return m_Denoise; }
+    // The denoised float image as OpenEXR (as SaveAccumulationEXR); needs SetDenoise(true).
+    bool SaveDenoisedEXR(const std::string& filepath);
+    // The accumulated feature buffers as THREE OpenEXR files beside each other (the writer knows R G B only): for "out.exr"
+    // out.albedo.exr (albedo), out.normal.exr (world-space shading normal, components as they are: -1 .. 1) and out.depth.exr (hit
+    // distance of the camera ray in all three channels, 0 where it missed).  Needs the feature buffers (SetDenoise(true) or
+    // PathTracer::SetFeatureBuffers(true)).
+    bool SaveFeatureEXR(const std::string& filepath);
 
     // Extension: PathTracer::SetDeviceBlasBuild for the renderer's scene (meshes loaded from now on are built on the GPU)
     void SetDeviceBlasBuild(bool enable) { m_PathTracer.SetDeviceBlasBuild(*m_Scene, enable); }
@@ -43,6 +56,7 @@ private:
     PathTracer m_PathTracer;
     double m_AccumulatedTime = 0.0;
     uint64_t m_Frames = 0;
+    bool m_Denoise = false;
 };
 
 // Image files (no stb): PNG (RGBA8, zlib deflate) and OpenEXR (scanline, uncompressed, float32 B G R channels).

@@ -35,7 +35,7 @@ enum {
 };
 
 /* Bumped whenever an entry point changes its signature or meaning, or a struct of this header / nexus_pod.h its layout. */
-#define NXHIP_API_VERSION 7
+#define NXHIP_API_VERSION 8
 
 /* Thread-local message of the last failing call (replaces CheckCudaErrors -> exit(99), Utils/Utils.cpp:3-12). */
 const char *nxhip_last_error(void);
@@ -298,6 +298,47 @@ int nxhip_mgpu_read_rgba8(nxhip_ctx *ctx, uint32_t *dst);        /* rank 0: widt
 int nxhip_mgpu_read_accumulation(nxhip_ctx *ctx, float *dst);    /* rank 0: width*height x 3 floats */
 int nxhip_mgpu_shutdown(nxhip_ctx *ctx);
 
+/* ---- feature buffers and the denoiser ------------------------------------------------------------------
+ * No counterpart in the reference, whose only image is the running mean (AccumulateKernel, PathTracer.cu:480-496): a viewer built
+ * on it shows noise for hundreds of frames.  Two steps, the second needs the first.
+ *
+ * Feature buffers (AOVs), off by default.  on != 0: every pass also records, per path, two float4 of the CAMERA ray's closest
+ * hit, whatever the material does next (opacity / alpha pass-through included):
+ *   albedo       xyz: the diffuse map's colour at the hit if the material has a map (it replaces the albedo, as in the shading
+ *                     code), else the albedo of a diffuse / plastic / dielectric material, else (conductor) (1, 1, 1); w: coverage,
+ *                     1 on a hit.  A miss: all 0.
+ *   normalDepth  xyz: the world-space shading normal, turned towards the camera; w: the hit distance.  A miss: all 0.
+ * nxhip_accumulate folds them into two context-wide running means with the update and frame order of the colour, so the
+ * accumulated values do not depend on frames per pass, passes in flight, pipeline, pixel order, tail bounce or entry points.
+ * With the switch off nothing is allocated or launched for them.  Turning it on after frames were accumulated is
+ * NXHIP_ERR_INVALID (colour and features must cover the same frames): nxhip_reset_frame_number first. */
+int nxhip_set_aov(nxhip_ctx *ctx, int on);
+/* The accumulated feature buffers, localCount x 4 floats each, in the order of nxhip_read_accumulation (either may be NULL). */
+int nxhip_read_aov(nxhip_ctx *ctx, float *albedo4, float *normalDepth4);
+/* The per-path values of the pass rendered last: localCount * framesPerPass x 4 floats each, frame slices one after the other
+ * (for consumers that accumulate themselves). */
+int nxhip_read_aov_frame(nxhip_ctx *ctx, float *albedo4, float *normalDepth4);
+/* The twin of nxhip_write_accumulation: load accumulated feature buffers (a checkpoint resumes colour AND features; the frame
+ * number comes with nxhip_write_accumulation).  Either may be NULL (left as it is). */
+int nxhip_write_aov(nxhip_ctx *ctx, const float *albedo4, const float *normalDepth4);
+/* Edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) over the accumulated colour C_0, guided by the accumulated feature
+ * buffers A (albedo + coverage, 4 components), N (normal) and Z (depth).  p = centre pixel, q = tap:
+ *   iteration i = 0 .. iterations - 1, step s = 2^i, taps q = p + s (dx, dy), dx, dy in {-2 .. 2}, taps outside the image skipped
+ *   h = (1/16, 1/4, 3/8, 1/4, 1/16)
+ *   w(p, q) = h[dx] h[dy] exp(-(|C_i(p) - C_i(q)|^2 / (sigmaColor 2^-i)^2 + |N(p) - N(q)|^2 / sigmaNormal^2
+ *                               + |A(p) - A(q)|^2 / sigmaAlbedo^2 + (Z(p) - Z(q))^2 / (sigmaDepth max(Z(p), 1e-6))^2))
+ *   C_{i+1}(p) = sum_q w(p, q) C_i(q) / sum_q w(p, q)        sums in the order dy-major, dx-minor; exp = nxf_expf
+ * The result is a SEPARATE full-frame image (row-major) and its RGBA8 (the tonemap of nxhip_read_rgba8): the accumulation and
+ * its RGBA8 are not touched, rendering goes on afterwards.  params == NULL: nxhip_denoise_defaults.  iterations == 0 copies.
+ * iterations > 6 or a sigma that is not a positive finite number: NXHIP_ERR_INVALID.  Needs the feature buffers, and a context
+ * that renders the full frame (identity map, NXHIP_ORDER_ROWS / NXHIP_ORDER_TILES): on a tile split (nxhip_set_pixel_map with a
+ * partial set, nxhip_mgpu_*) NXHIP_ERR_INVALID.  Asynchronous, on the context's stream behind the accumulates. */
+int nxhip_denoise(nxhip_ctx *ctx, const nx_denoise_params *params);
+int nxhip_denoise_defaults(nx_denoise_params *params);
+/* Read-back of the last nxhip_denoise (synchronises): width * height x 3 floats / width * height uint32, row-major. */
+int nxhip_read_denoised(nxhip_ctx *ctx, float *rgb);
+int nxhip_read_denoised_rgba8(nxhip_ctx *ctx, uint32_t *dst);
+
 /* D_QueueSize after the last rendered frame — Cuda/PathTracer/PathTracer.cuh:61-73.  Each array NX_PATH_MAX_LENGTH ints. */
 typedef struct nxhip_queue_sizes {
     int32_t traceSize[NX_PATH_MAX_LENGTH];
@@ -424,6 +465,7 @@ static inline uint64_t nxhip_header_abi_stamp(void)
         sizeof(nx_camera), offsetof(nx_camera, resolution), sizeof(nx_render_settings), offsetof(nx_render_settings, backgroundColor),
         sizeof(nx_ray), sizeof(nx_hit), sizeof(nx_bsdf_query), sizeof(nx_bsdf_result), offsetof(nx_bsdf_result, rngOut),
         sizeof(nxhip_queue_sizes), sizeof(nxhip_trace_stats), offsetof(nxhip_trace_stats, cycles), sizeof(nxhip_kernel_times), NXHIP_K_COUNT,
+        sizeof(nx_denoise_params), offsetof(nx_denoise_params, sigmaColor), offsetof(nx_denoise_params, sigmaDepth),
     };
     uint64_t h = 0xcbf29ce484222325ull;
     size_t i;

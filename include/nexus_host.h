@@ -124,6 +124,8 @@ int nxs_pathtracer_set_passes_in_flight(nxs_pathtracer *p, uint32_t passes);
 /* PathTracer::SetPixelOrder / SetEntryPoints (extensions): NXHIP_ORDER_* of the frame's paths; primary rays from their run's entry state */
 int nxs_pathtracer_set_pixel_order(nxs_pathtracer *p, int order);
 int nxs_pathtracer_set_entry_points(nxs_pathtracer *p, int on);
+/* PathTracer::SetFeatureBuffers (extension): albedo / normal / depth of the camera ray's hit, accumulated like the colour (nxhip_set_aov) */
+int nxs_pathtracer_set_feature_buffers(nxs_pathtracer *p, int on);
 /* PathTracer::SetDeviceBlasBuild (extension, off by default): meshes added to `s` from now on get their BVH8 from the device
  * builder (nxhip_build_blas) instead of the host's; switch it off, or destroy the scene, before `p` goes away. */
 int nxs_pathtracer_set_device_blas_build(nxs_pathtracer *p, nxs_scene *s, int enable);
@@ -152,6 +154,11 @@ uint32_t nxs_renderer_frame_number(const nxs_renderer *r);
 double nxs_renderer_megasamples_per_second(const nxs_renderer *r); /* MetricsPanel.cpp:28-56 */
 struct nxhip_ctx *nxs_renderer_device_context(nxs_renderer *r);
 int nxs_renderer_set_modes(nxs_renderer *r, int rngMode, int compactMode, int conductorMode);
+/* Renderer::SetDenoise / SaveDenoisedEXR / SaveFeatureEXR (extensions, include/nexus/Renderer.h): with denoise on the screenshot is the
+ * a-trous filtered image (nxhip_denoise); the feature buffers go to <stem>.albedo.exr, <stem>.normal.exr and <stem>.depth.exr */
+int nxs_renderer_set_denoise(nxs_renderer *r, int on);
+int nxs_renderer_save_denoised_exr(nxs_renderer *r, const char *path);
+int nxs_renderer_save_feature_exr(nxs_renderer *r, const char *path);
 /* Image writers without stb: PNG (RGBA8; the reference's stbi_write_png) and OpenEXR (scanline, uncompressed, float32 B G R).
  * flipVertically != 0 writes the last row first (the render buffer's row 0 is the bottom of the viewport). */
 int nxh_write_png(const char *path, const uint32_t *rgba8, uint32_t width, uint32_t height, int flipVertically);

@@ -150,6 +150,14 @@ NX_STATIC_ASSERT(sizeof(nx_bsdf_query) == 32, "nx_bsdf_query must be 32 bytes");
 NX_STATIC_ASSERT(sizeof(nx_bsdf_result) == 48, "nx_bsdf_result must be 48 bytes");
 
 
+/* Parameters of nxhip_denoise (include/nexus_hip.h): iterations of the a-trous filter (0 .. 6, step 2^i) and the widths of its four
+ * edge-stopping terms — colour (halved every iteration), shading normal, albedo + coverage, depth relative to the centre's. */
+typedef struct nx_denoise_params {
+    uint32_t iterations;
+    float sigmaColor, sigmaNormal, sigmaAlbedo, sigmaDepth;
+} nx_denoise_params;
+NX_STATIC_ASSERT(sizeof(nx_denoise_params) == 20, "nx_denoise_params must be 20 bytes");
+
 /* How Logic/Shade seed their RNG.  REFERENCE_SLOT mirrors Cuda/Random.cuh:79-82 + PathTracer.cu:143,326
  * (seed by queue slot, no bounce term).  PIXEL_KEYED seeds by (global pixel, bounce, frame): the image
  * then does not depend on queue slot order, so it is reproducible under racing compaction and under a

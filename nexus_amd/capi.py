@@ -28,6 +28,7 @@ HIP_SYMBOLS = [
     "nxhip_set_instance_transforms", "nxhip_read_tlas", "nxhip_set_passes_in_flight", "nxhip_set_tail_bounce", "nxhip_set_entry_points", "nxhip_read_entry_states", "nxhip_debug_set_thin", "nxhip_debug_set_thin_pool", "nxhip_debug_thin_counts", "nxhip_build_blas", "nxhip_read_blas", "nxhip_set_env_sampling",
     "nxhip_tile_pixel_map", "nxhip_mgpu_unique_id", "nxhip_mgpu_init", "nxhip_mgpu_attach", "nxhip_mgpu_gather", "nxhip_mgpu_read_rgba8",
     "nxhip_mgpu_read_accumulation", "nxhip_mgpu_shutdown", "nxhip_fmath_batch", "nxhip_abi_stamp", "nxhip_check_library", "nxhip_build_blas_batch", "nxhip_read_blas_batch", "nxhip_debug_set_scan_epoch", "nxhip_debug_ended_rays_of_pass",
+    "nxhip_set_aov", "nxhip_read_aov", "nxhip_read_aov_frame", "nxhip_write_aov", "nxhip_denoise", "nxhip_denoise_defaults", "nxhip_read_denoised", "nxhip_read_denoised_rgba8",
 ]
 HOST_SYMBOLS = [
     "nxh_bvh8_build", "nxh_tlas_build", "nxh_tlas_refit", "nxh_bvh8_node_count", "nxh_bvh8_prim_count", "nxh_bvh8_nodes",
@@ -36,7 +37,7 @@ HOST_SYMBOLS = [
     "nxh_loaded_material_textures", "nxh_loaded_warning_count", "nxh_loaded_warning", "nxh_decode_png", "nxh_write_png", "nxh_write_exr",
     "nxs_scene_add_hdr_map_file", "nxs_renderer_create", "nxs_renderer_destroy", "nxs_renderer_render", "nxs_renderer_reset", "nxs_renderer_on_resize",
     "nxs_renderer_save_screenshot", "nxs_renderer_save_exr", "nxs_renderer_frame_number", "nxs_renderer_megasamples_per_second", "nxs_renderer_device_context",
-    "nxs_renderer_set_modes",
+    "nxs_renderer_set_modes", "nxs_renderer_set_denoise", "nxs_renderer_save_denoised_exr", "nxs_renderer_save_feature_exr", "nxs_pathtracer_set_feature_buffers",
     "nxh_load_scene_file", "nxh_loaded_scene_free", "nxh_loaded_mesh_count", "nxh_loaded_mesh_triangle_count", "nxh_loaded_mesh_triangles",
     "nxh_loaded_material_count", "nxh_loaded_materials", "nxh_loaded_instance_count", "nxh_loaded_instances", "nxs_scene_load_file", "nxs_scene_set_instance_transform", "nxs_scene_assign_material", "nxs_scene_set_tlas_refit", "nxs_scene_set_device_tlas", "nxs_pathtracer_set_device_blas_build",
     "nxs_last_error", "nxs_scene_create", "nxs_scene_destroy", "nxs_scene_add_material", "nxs_scene_add_texture", "nxs_scene_set_hdr_map",
@@ -72,7 +73,7 @@ class KernelTimes(C.Structure):
 
 KERNEL_CLASSES = ("generate", "trace", "shadow", "logic", "shade", "accumulate", "thin")
 
-API_VERSION = 7  # NXHIP_API_VERSION of the include/nexus_hip.h these bindings were written against
+API_VERSION = 8  # NXHIP_API_VERSION of the include/nexus_hip.h these bindings were written against
 
 
 def abi_words():
@@ -87,6 +88,7 @@ def abi_words():
         pod.CAM_DT.itemsize, off(pod.CAM_DT, "resolution"), pod.SETTINGS_DT.itemsize, off(pod.SETTINGS_DT, "backgroundColor"),
         pod.RAY_DT.itemsize, pod.HIT_DT.itemsize, pod.BSDF_QUERY_DT.itemsize, pod.BSDF_RESULT_DT.itemsize, off(pod.BSDF_RESULT_DT, "rngOut"),
         C.sizeof(QueueSizes), C.sizeof(TraceStats), TraceStats.cycles.offset, C.sizeof(KernelTimes), len(KERNEL_CLASSES),
+        pod.DENOISE_DT.itemsize, off(pod.DENOISE_DT, "sigmaColor"), off(pod.DENOISE_DT, "sigmaDepth"),
     ]
 
 
@@ -187,6 +189,13 @@ def lib():
     L.nxhip_mgpu_read_rgba8.argtypes = [vp, vp]
     L.nxhip_mgpu_read_accumulation.argtypes = [vp, vp]
     L.nxhip_mgpu_shutdown.argtypes = [vp]
+    L.nxhip_set_aov.argtypes = [vp, C.c_int]
+    for f in ("nxhip_read_aov", "nxhip_read_aov_frame", "nxhip_write_aov"):
+        getattr(L, f).argtypes = [vp, vp, vp]
+    L.nxhip_denoise.argtypes = [vp, vp]
+    L.nxhip_denoise_defaults.argtypes = [vp]
+    L.nxhip_read_denoised.argtypes = [vp, vp]
+    L.nxhip_read_denoised_rgba8.argtypes = [vp, vp]
     # host builders
     L.nxh_bvh8_build.argtypes = [vp, u32, u32, C.POINTER(vp)]
     L.nxh_tlas_build.argtypes = [vp, u32, C.POINTER(vp)]
@@ -757,6 +766,54 @@ class Context:
         assert len(a) == self.local_count
         check(self.L.nxhip_write_accumulation(self.h, _ptr(a), int(frame_number)), "nxhip_write_accumulation")
 
+    # ---- feature buffers and the denoiser (include/nexus_hip.h) ----
+    def set_aov(self, on=True):
+        """Feature buffers of the camera ray's hit (albedo + coverage, shading normal + depth), accumulated like the colour"""
+        check(self.L.nxhip_set_aov(self.h, 1 if on else 0), "nxhip_set_aov")
+
+    def read_aov(self):
+        """(albedo, normalDepth): the accumulated feature buffers, (local_count, 4) float32 each, in the order of read_accumulation"""
+        a = np.zeros((self.local_count, 4), np.float32)
+        n = np.zeros((self.local_count, 4), np.float32)
+        check(self.L.nxhip_read_aov(self.h, _ptr(a), _ptr(n)), "nxhip_read_aov")
+        return a, n
+
+    def read_aov_frame(self):
+        """(albedo, normalDepth) of the pass rendered last: (local_count * frames_per_pass, 4) float32 each, frame slices in turn"""
+        a = np.zeros((self.local_count * self.frames_per_pass, 4), np.float32)
+        n = np.zeros((self.local_count * self.frames_per_pass, 4), np.float32)
+        check(self.L.nxhip_read_aov_frame(self.h, _ptr(a), _ptr(n)), "nxhip_read_aov_frame")
+        return a, n
+
+    def write_aov(self, albedo=None, normal_depth=None):
+        """Load accumulated feature buffers (the twin of write_accumulation); None leaves a buffer as it is"""
+        bufs = []
+        for b in (albedo, normal_depth):
+            if b is not None:
+                b = np.ascontiguousarray(b, dtype=np.float32).reshape(-1, 4)
+                assert len(b) == self.local_count
+            bufs.append(b)
+        check(self.L.nxhip_write_aov(self.h, _ptr(bufs[0]) if bufs[0] is not None else None, _ptr(bufs[1]) if bufs[1] is not None else None), "nxhip_write_aov")
+
+    def denoise(self, iterations=None, sigma_color=None, sigma_normal=None, sigma_albedo=None, sigma_depth=None):
+        """Edge-avoiding a-trous filter over the accumulated colour, guided by the accumulated feature buffers; None = the
+        library's default for that parameter.  The result is a separate image: read_denoised / read_denoised_rgba8."""
+        p = denoise_defaults()
+        for name, v in (("iterations", iterations), ("sigmaColor", sigma_color), ("sigmaNormal", sigma_normal), ("sigmaAlbedo", sigma_albedo), ("sigmaDepth", sigma_depth)):
+            if v is not None:
+                p[name] = v
+        check(self.L.nxhip_denoise(self.h, _ptr(p)), "nxhip_denoise")
+
+    def read_denoised(self):
+        out = np.zeros((self.width * self.height, 3), np.float32)
+        check(self.L.nxhip_read_denoised(self.h, _ptr(out)), "nxhip_read_denoised")
+        return out
+
+    def read_denoised_rgba8(self):
+        out = np.zeros(self.width * self.height, np.uint32)
+        check(self.L.nxhip_read_denoised_rgba8(self.h, _ptr(out)), "nxhip_read_denoised_rgba8")
+        return out
+
     def bind_radiance(self, dev_ptr, capacity):
         check(self.L.nxhip_bind_radiance(self.h, C.c_void_p(dev_ptr) if dev_ptr else None, capacity), "nxhip_bind_radiance")
 
@@ -882,6 +939,13 @@ class Context:
         t = KernelTimes()
         check(self.L.nxhip_read_kernel_times(self.h, C.byref(t), 1 if reset else 0), "nxhip_read_kernel_times")
         return {k: {"ms": t.ms[i], "launches": int(t.launches[i])} for i, k in enumerate(KERNEL_CLASSES)}
+
+
+def denoise_defaults():
+    """nxhip_denoise_defaults as a pod.DENOISE_DT record"""
+    p = np.zeros(1, pod.DENOISE_DT)
+    check(lib().nxhip_denoise_defaults(_ptr(p)), "nxhip_denoise_defaults")
+    return p
 
 
 def tile_pixel_map(width, height, world, rank, tile_rows, tiled=True):
@@ -1032,6 +1096,9 @@ class Renderer:
         L.nxs_renderer_device_context.argtypes = [C.c_void_p]
         L.nxs_renderer_device_context.restype = C.c_void_p
         L.nxs_renderer_set_modes.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
+        L.nxs_renderer_set_denoise.argtypes = [C.c_void_p, C.c_int]
+        L.nxs_renderer_save_denoised_exr.argtypes = [C.c_void_p, C.c_char_p]
+        L.nxs_renderer_save_feature_exr.argtypes = [C.c_void_p, C.c_char_p]
         h = C.c_void_p()
         _scheck(L.nxs_renderer_create(width, height, scene.h, device, C.byref(h)), "nxs_renderer_create")
         self.h = h
@@ -1062,6 +1129,28 @@ class Renderer:
 
     def save_exr(self, path):
         _scheck(self.L.nxs_renderer_save_exr(self.h, str(path).encode()), "nxs_renderer_save_exr")
+
+    def set_denoise(self, on=True):
+        """Renderer::SetDenoise: feature buffers on, accumulation restarted; save_screenshot then writes the filtered image"""
+        _scheck(self.L.nxs_renderer_set_denoise(self.h, 1 if on else 0), "nxs_renderer_set_denoise")
+
+    def save_denoised_exr(self, path):
+        _scheck(self.L.nxs_renderer_save_denoised_exr(self.h, str(path).encode()), "nxs_renderer_save_denoised_exr")
+
+    def save_feature_exr(self, path):
+        """<stem>.albedo.exr, <stem>.normal.exr, <stem>.depth.exr beside each other"""
+        _scheck(self.L.nxs_renderer_save_feature_exr(self.h, str(path).encode()), "nxs_renderer_save_feature_exr")
+
+    def device_context(self):
+        """the renderer's nxhip_ctx wrapped as a Context that does not own it (read-backs; do not close)"""
+        ctx = Context.__new__(Context)
+        ctx.L = lib()
+        ctx.h = C.c_void_p(self.L.nxs_renderer_device_context(self.h))
+        ctx.width, ctx.height = self.width, self.height
+        ctx.local_count = self.width * self.height
+        ctx.frames_per_pass = 1
+        ctx.close = lambda: None  # (the renderer owns it)
+        return ctx
 
     def frame_number(self):
         return int(self.L.nxs_renderer_frame_number(self.h))
@@ -1118,6 +1207,11 @@ class PathTracer:
     def set_entry_points(self, on=True):
         self.L.nxs_pathtracer_set_entry_points.argtypes = [C.c_void_p, C.c_int]
         _scheck(self.L.nxs_pathtracer_set_entry_points(self.h, 1 if on else 0), "nxs_pathtracer_set_entry_points")
+
+    def set_feature_buffers(self, on=True):
+        """PathTracer::SetFeatureBuffers: albedo / normal / depth of the camera ray's hit, accumulated like the colour"""
+        self.L.nxs_pathtracer_set_feature_buffers.argtypes = [C.c_void_p, C.c_int]
+        _scheck(self.L.nxs_pathtracer_set_feature_buffers(self.h, 1 if on else 0), "nxs_pathtracer_set_feature_buffers")
 
     def set_device_blas_build(self, scene, enable=True):
         """PathTracer::SetDeviceBlasBuild: meshes added to `scene` from now on are built into BVH8s on the GPU"""

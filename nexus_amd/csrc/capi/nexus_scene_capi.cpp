@@ -272,6 +272,7 @@ int nxs_pathtracer_set_frames_per_pass(nxs_pathtracer* p, uint32_t frames) { ret
 int nxs_pathtracer_set_passes_in_flight(nxs_pathtracer* p, uint32_t passes) { return guarded([&] { p->pt.SetPassesInFlight(passes); }); }
 int nxs_pathtracer_set_pixel_order(nxs_pathtracer* p, int order) { return guarded([&] { p->pt.SetPixelOrder(order); }); }
 int nxs_pathtracer_set_entry_points(nxs_pathtracer* p, int on) { return guarded([&] { p->pt.SetEntryPoints(on != 0); }); }
+int nxs_pathtracer_set_feature_buffers(nxs_pathtracer* p, int on) { return guarded([&] { p->pt.SetFeatureBuffers(on != 0); }); }
 int nxs_pathtracer_set_device_blas_build(nxs_pathtracer* p, nxs_scene* s, int enable)
 {
     return guarded([&] { p->pt.SetDeviceBlasBuild(s->scene, enable != 0); });
@@ -338,6 +339,19 @@ struct nxhip_ctx* nxs_renderer_device_context(nxs_renderer* r) { return r->r.Get
 int nxs_renderer_set_modes(nxs_renderer* r, int rngMode, int compactMode, int conductorMode)
 {
     return guarded([&] { r->r.GetPathTracer().SetModes(rngMode, compactMode, conductorMode); });
+}
+int nxs_renderer_set_denoise(nxs_renderer* r, int on) { return guarded([&] { r->r.SetDenoise(on != 0); }); }
+int nxs_renderer_save_denoised_exr(nxs_renderer* r, const char* path)
+{
+    return guarded([&] {
+        if (!path || !r->r.SaveDenoisedEXR(path)) throw std::runtime_error(std::string("cannot write the denoised image to ") + (path ? path : "(null)") + " (is denoise on?)");
+    });
+}
+int nxs_renderer_save_feature_exr(nxs_renderer* r, const char* path)
+{
+    return guarded([&] {
+        if (!path || !r->r.SaveFeatureEXR(path)) throw std::runtime_error(std::string("cannot write the feature buffers to ") + (path ? path : "(null)") + " (are they on?)");
+    });
 }
 
 int nxh_write_png(const char* path, const uint32_t* rgba8, uint32_t width, uint32_t height, int flipVertically)

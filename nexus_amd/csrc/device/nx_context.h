@@ -103,6 +103,8 @@ struct PassSlot {
     // entryRuns), never through a pointer fixed into a graph node.
     DevBuf entryTable;
     uint32_t entryRuns = 0;
+    // Feature buffers of the pass (nx_aov.hip aov_kernel), float4[pathCapacity] each, allocated only while nxhip_set_aov is on
+    DevBuf aovAlbedo, aovNormalDepth;
     // the slot's error word as the pass left it, copied into pinned host memory behind every pass on the slot's own stream: what
     // nxhip_sync reads instead of a blocking 4-byte device read per slot (errorFresh: no launch since that could have set it)
     uint32_t* hostError = nullptr;
@@ -214,4 +216,12 @@ struct nxhip_ctx : nxd::PassSlot {
     bool dead = false;          // nxhip_sync_timeout gave up: no further device work is issued or waited for
     int pixelOrder = 0;         // nxhip_set_pixel_order: NXHIP_ORDER_* of the full frame, re-applied by nxhip_resize (a caller's own map is not)
     bool entryPoints = false;   // nxhip_set_entry_points (the tables: PassSlot::entryTable, one per slot)
+    // feature buffers + denoiser (nx_aov.hip)
+    bool aov = false;            // nxhip_set_aov
+    bool coversFrame = true;     // the context's pixels are every pixel of the frame exactly once (identity, or a map that is a permutation)
+    nxd::DevBuf aovAccumAlbedo, aovAccumNormalDepth;  // running means over the frames, in the order of `accumulation`; exist while `aov`
+    // row-major planes of the filter, allocated by the first nxhip_denoise and dropped with the pixel set: gathered colour / albedo /
+    // normal + depth, the two colour planes the iterations alternate between, the tonemapped result
+    nxd::DevBuf dnColour, dnAlbedo, dnNormalDepth, dnPing, dnPong, dnRgba8;
+    const void* denoised = nullptr;  // the plane that holds the last nxhip_denoise's result (nullptr: none since the pixel set changed)
 };

@@ -377,7 +377,24 @@ struct DeviceState {
     uint32_t thinLanes, thinIters;   // hand-over rule: at most thinLanes busy lanes for at least thinIters iterations (16 / 16; a test hook sets 64 / 0: every ray of a dry wave)
     uint32_t thinPoolLimit;          // items a thin wave's pool may hold before a round puts items back (0: all of it; a test hook lowers it: nxhip_debug_set_thin_pool)
     uint32_t entryRuns;              // states in `entry`
-    uint32_t debugRequeue;           // test hook (nxhip_debug_set_requeue): the trace kernels hand the same rays out again and again — a ray that re-queues itself (see kErrRaysRetaken)
+    uint32_t debugRequeue;           // test hook (nxhip_debug_set_requeue): the trace kernels hand the same rays out again and again — a ray that re-queues itself (see kErrRaysRetaken)    // Feature buffers of the camera ray's hit (nxhip_set_aov; nx_aov.hip), nullptr while they are off.  Per path of the slot's pass, in path
+    // order like `radiance`: albedo (rgb, coverage) and shading normal (xyz, hit distance); and the context-wide running means over the
+    // frames, in the order of `accumulation`.  Last in the block: nothing in front of them moves.
+    NX_G float4* aovAlbedo;
+    NX_G float4* aovNormalDepth;
+    NX_G float4* aovAccumAlbedo;
+    NX_G float4* aovAccumNormalDepth;
+};
+
+// Argument block of one iteration of the edge-avoiding a-trous filter (nx_aov.hip denoise_iteration_kernel; filled by nxhip_denoise).
+struct DenoiseLaunch {
+    const float4* colour;  // C_i
+    const float4* albedo;
+    const float4* normalDepth;
+    float4* out;           // C_{i+1}
+    uint32_t* rgba8;       // the last iteration: the tonemapped image too (nullptr otherwise)
+    int32_t width, height, step;
+    float invColour, invNormal, invAlbedo, sigmaDepth;  // 1 / sigma^2 (colour: of this iteration), clamped to the largest finite float
 };
 
 // What a translation unit of the library believes about the device-resident structures and the compile-time knobs that shape
@@ -395,12 +412,12 @@ constexpr uint64_t layout_stamp()
     const uint64_t w[] = {
         sizeof(DeviceState), offsetof(DeviceState, camera), offsetof(DeviceState, envSampling), offsetof(DeviceState, localCount), offsetof(DeviceState, pixelMap),
         offsetof(DeviceState, radiance), offsetof(DeviceState, trace), offsetof(DeviceState, shadow), offsetof(DeviceState, material), offsetof(DeviceState, counters),
-        offsetof(DeviceState, frame), offsetof(DeviceState, traceStats), offsetof(DeviceState, scanStatus), offsetof(DeviceState, entry), offsetof(DeviceState, entryRuns), offsetof(DeviceState, debugRequeue), offsetof(DeviceState, thinStates), offsetof(DeviceState, leafOfInstance), sizeof(ThinState), offsetof(ThinState, stack), offsetof(DeviceState, thinClosest), offsetof(DeviceState, thinCapacity), offsetof(DeviceState, thinIters), offsetof(DeviceState, thinPoolLimit), offsetof(Counters, thinCount), sizeof(EntryState), offsetof(EntryState, sp), offsetof(EntryState, triP0), offsetof(EntryState, triInst), offsetof(Counters, scanTicket), offsetof(FrameState, scanEpoch),
+        offsetof(DeviceState, frame), offsetof(DeviceState, traceStats), offsetof(DeviceState, scanStatus), offsetof(DeviceState, entry), offsetof(DeviceState, entryRuns), offsetof(DeviceState, debugRequeue), offsetof(DeviceState, aovAlbedo), offsetof(DeviceState, aovAccumNormalDepth), offsetof(DeviceState, thinStates), offsetof(DeviceState, leafOfInstance), sizeof(ThinState), offsetof(ThinState, stack), offsetof(DeviceState, thinClosest), offsetof(DeviceState, thinCapacity), offsetof(DeviceState, thinIters), offsetof(DeviceState, thinPoolLimit), offsetof(Counters, thinCount), sizeof(EntryState), offsetof(EntryState, sp), offsetof(EntryState, triP0), offsetof(EntryState, triInst), offsetof(Counters, scanTicket), offsetof(FrameState, scanEpoch),
         (uint64_t)kScanKinds, (uint64_t)kScanWords, (uint64_t)kScanEpochLimit, (uint64_t)kShadeBlockOrderedThreads,
         sizeof(Counters), sizeof(RegionCounters), offsetof(RegionCounters, traceShadowSize), offsetof(RegionCounters, materialSize), offsetof(RegionCounters, traceHead),
         offsetof(RegionCounters, shadowHead), offsetof(RegionCounters, scanTile), offsetof(RegionCounters, endedSize), offsetof(Counters, orderedBase), offsetof(Counters, tailHead),
         sizeof(ShadeInst), offsetof(ShadeInst, tris), offsetof(ShadeInst, material), offsetof(DeviceState, shadeInst), sizeof(InstTrav), offsetof(InstTrav, nodes), offsetof(InstTrav, instIdx), offsetof(InstTrav, root), sizeof(BlasDev), offsetof(BlasDev, nodeCount),
-        sizeof(TextureDev), sizeof(TraceQueue), sizeof(ShadowQueue), sizeof(MaterialQueue), sizeof(FrameState), sizeof(TraceStatsDev),
+        sizeof(DenoiseLaunch), offsetof(DenoiseLaunch, width), sizeof(TextureDev), sizeof(TraceQueue), sizeof(ShadowQueue), sizeof(MaterialQueue), sizeof(FrameState), sizeof(TraceStatsDev),
         (uint64_t)kNodeStride, (uint64_t)kTriStride, (uint64_t)kShadeTriStride, (uint64_t)kQueueShards, (uint64_t)kQueueShardSlack, (uint64_t)kRegionStride, (uint64_t)kMaxBounceSlots,
         (uint64_t)kEnvGuide, (uint64_t)kHitCodeShift, sizeof(TraceRays), offsetof(TraceQueue, hit), (uint64_t)kMaterialTypeOffset, sizeof(nx_material), sizeof(nx_bvh_instance), sizeof(nx_triangle), sizeof(nx_light), sizeof(nx_camera),
     };

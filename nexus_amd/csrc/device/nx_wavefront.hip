@@ -20,6 +20,7 @@
 #include "nx_math.h"
 #include "nx_queue.h"
 #include "nx_texture.h"
+#include "nx_tonemap.h"
 #include "nx_traverse.h"
 
 namespace nxd {
@@ -1348,20 +1349,7 @@ __global__ void __launch_bounds__(kTraceBlock) tail_kernel(const DeviceState* __
 // ------------------------------------------------------------------------------------------------------
 // AccumulateKernel, Tonemap, LinearToGamma, ToColorUInt — PathTracer.cu:37-62, 480-496; Utils/Utils.h:51-54
 
-NXD uint32_t tonemap_rgba8(f3 c)
-{
-    const float v[3] = {c.x, c.y, c.z};
-    uint32_t out = 0;
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        float x = v[k] * 0.6f;
-        x = clampf((x * (2.51f * x + 0.03f)) / (x * (2.43f * x + 0.59f) + 0.14f), 0.0f, 1.0f);
-        x = (float)nxf_pow((double)x, 0.45454545454);
-        x = clampf(x, 0.0f, 1.0f);
-        out |= (uint32_t)(uint8_t)(x * 255.0f) << (8 * k);
-    }
-    return out | (255u << 24);
-}
+// (tonemap_rgba8: nx_tonemap.h — the denoiser's kernels write their RGBA8 image through the same text)
 
 // Running mean over `slices` consecutive frames per pixel, then tonemap.  src == nullptr: this context's own radiance
 // (slices = framesPerPass, the pass's frame numbers); otherwise externally gathered radiance laid out

@@ -31,12 +31,17 @@ const void* hook_sizes_kernel_ptr();
 const void* generate_kernel_ptr();
 const void* accumulate_kernel_ptr();
 const void* compose_kernel_ptr();
+const void* aov_kernel_ptr();
+const void* aov_fold_kernel_ptr();
+const void* denoise_gather_kernel_ptr();
+const void* denoise_iteration_kernel_ptr(int step, bool forceDirect);
 uint64_t layout_stamp_trace();
 uint64_t layout_stamp_wavefront();
 uint64_t layout_stamp_refit();
 uint64_t layout_stamp_lbvh();
 uint64_t layout_stamp_multigpu();
 uint64_t layout_stamp_entry();
+uint64_t layout_stamp_aov();
 const void* bsdf_hook_kernel_ptr();
 const void* fmath_hook_kernel_ptr();
 const void* tex2d_hook_kernel_ptr();
@@ -125,7 +130,7 @@ static int check_layouts()
 {
     const struct { const char* unit; uint64_t stamp; } units[] = {
         {"nx_trace.hip", layout_stamp_trace()}, {"nx_wavefront.hip", layout_stamp_wavefront()}, {"nx_refit.hip", layout_stamp_refit()},
-        {"nx_lbvh.hip", layout_stamp_lbvh()}, {"nxhip_multigpu.hip", layout_stamp_multigpu()}, {"nx_entry.hip", layout_stamp_entry()},
+        {"nx_lbvh.hip", layout_stamp_lbvh()}, {"nxhip_multigpu.hip", layout_stamp_multigpu()}, {"nx_entry.hip", layout_stamp_entry()}, {"nx_aov.hip", layout_stamp_aov()},
     };
     for (const auto& u : units) {
         if (u.stamp != layout_stamp()) {
@@ -248,6 +253,8 @@ static void compose_view(nxhip_ctx* c, PassSlot* s)
     v.thinStates = s->thinStates.as<ThinState>();
     v.entry = (c->entryPoints && s->entryTable.p) ? s->entryTable.as<EntryState>() : nullptr;
     v.entryRuns = v.entry ? s->entryRuns : 0u;
+    v.aovAlbedo = c->aov ? s->aovAlbedo.as<float4>() : nullptr;  // (per slot, like the entry table; the running means are the context's: c->h)
+    v.aovNormalDepth = c->aov ? s->aovNormalDepth.as<float4>() : nullptr;
     // queue regions: eight, or one spanning the buffer when slots are handed out in the reference's serial order
     const bool ordered = c->h.compactMode == NX_COMPACT_ORDERED;
     v.queueShards = ordered ? 1u : (uint32_t)kQueueShards;
@@ -305,6 +312,8 @@ static int alloc_slot_queues(nxhip_ctx* c, PassSlot* q, size_t n)
     q->scanStatus = std::move(freshStatus);
     q->thinLists = std::move(freshThin);
     q->thinStates = std::move(freshThinStates);
+    q->aovAlbedo.release();  // (sized by the capacity: the slot's next pass with feature buffers allocates them again, ensure_slot_aov)
+    q->aovNormalDepth.release();
     q->scanEpoch = 0;
     q->pathCapacity = n;
     q->queuesScan = scan;
@@ -331,6 +340,8 @@ static void release_slot_queues(nxhip_ctx* c, PassSlot* q)
     q->scanStatus.release();
     q->thinLists.release();
     q->thinStates.release();
+    q->aovAlbedo.release();
+    q->aovNormalDepth.release();
     q->pathCapacity = 0;
     if (q == static_cast<PassSlot*>(c)) {
         DeviceState& h = c->h;
@@ -372,6 +383,12 @@ static int ensure_slot_queues(nxhip_ctx* c, PassSlot* q)
     return rc;
 }
 
+static void release_denoise_planes(nxhip_ctx* c)
+{
+    for (DevBuf* b : {&c->dnColour, &c->dnAlbedo, &c->dnNormalDepth, &c->dnPing, &c->dnPong, &c->dnRgba8}) b->release();
+    c->denoised = nullptr;
+}
+
 // Everything sized by the pixel set of this context: queues for localCount * framesPerPass paths and a zeroed image.
 static int alloc_paths(nxhip_ctx* c, uint32_t localCount)
 {
@@ -380,8 +397,19 @@ static int alloc_paths(nxhip_ctx* c, uint32_t localCount)
     if (n > 0x7fffffffull) return fail_invalid("more than 2^31 paths (pixels x frames per pass): lower nxhip_set_frames_per_pass first");
     DevBuf freshAccum, freshRgba;  // all or nothing, as alloc_queues
     if (!freshAccum.alloc(full * 16) || !freshRgba.alloc(full * 4)) return NXHIP_ERR_HIP;
+    DevBuf freshAovA, freshAovN;  // the accumulated feature buffers follow the image (nxhip_set_aov)
+    if (c->aov && (!freshAovA.alloc(full * 16) || !freshAovN.alloc(full * 16))) return NXHIP_ERR_HIP;
     const int rc = alloc_queues(c, n);
     if (rc != NXHIP_OK) return rc;
+    if (c->aov) {
+        c->aovAccumAlbedo = std::move(freshAovA);
+        c->aovAccumNormalDepth = std::move(freshAovN);
+        NX_HIP(hipMemsetAsync(c->aovAccumAlbedo.p, 0, full * 16, c->stream));
+        NX_HIP(hipMemsetAsync(c->aovAccumNormalDepth.p, 0, full * 16, c->stream));
+        c->h.aovAccumAlbedo = c->aovAccumAlbedo.as<float4>();
+        c->h.aovAccumNormalDepth = c->aovAccumNormalDepth.as<float4>();
+    }
+    release_denoise_planes(c);  // (sized by the frame, and their content belongs to the previous pixel set)
     c->accumulation = std::move(freshAccum);
     c->rgba8 = std::move(freshRgba);
     NX_HIP(hipMemsetAsync(c->accumulation.p, 0, full * 16, c->stream));
@@ -689,6 +717,7 @@ int nxhip_resize(nxhip_ctx* c, uint32_t width, uint32_t height)
     c->h.camera.resolution[1] = height;
     c->pixelMap.release();
     c->h.pixelMap = nullptr;
+    c->coversFrame = true;
     c->stateDirty = true;
     const int rcFrame = set_frame_number_device(c, 0);
     if (rcFrame != NXHIP_OK) return rcFrame;
@@ -1601,6 +1630,7 @@ int nxhip_set_pixel_map(nxhip_ctx* c, const uint32_t* pixelMap, uint32_t localCo
         if (rc != NXHIP_OK) return rc;
         c->pixelMap.release();
         c->h.pixelMap = nullptr;
+        c->coversFrame = true;
         c->stateDirty = true;
         return set_frame_number_device(c, 0);
     }
@@ -1614,6 +1644,15 @@ int nxhip_set_pixel_map(nxhip_ctx* c, const uint32_t* pixelMap, uint32_t localCo
     if (rc != NXHIP_OK) return rc;
     c->pixelMap = std::move(freshMap);
     c->h.pixelMap = c->pixelMap.as<uint32_t>();
+    // every pixel of the frame exactly once?  (what nxhip_denoise needs: it filters in image space)
+    c->coversFrame = localCount == full;
+    if (c->coversFrame) {
+        std::vector<bool> seen(full, false);
+        for (uint32_t i = 0; i < localCount && c->coversFrame; i++) {
+            if (seen[pixelMap[i]]) c->coversFrame = false;
+            seen[pixelMap[i]] = true;
+        }
+    }
     c->stateDirty = true;
     return set_frame_number_device(c, 0);
 }
@@ -1691,6 +1730,8 @@ struct Launch {
     const float4* src;
     uint32_t count, slices, sliceStride, firstFrame;
     const uint32_t* dstMap;
+    void* plane[4];    // nargs 5: (S, plane[0..3]) — denoise_gather_kernel
+    DenoiseLaunch dn;  // nargs 40: (dn) — denoise_iteration_kernel
     int nargs;  // 1: (S), 2: (S, bounce), 3: (S, bounce, type), 7: accumulate
 };
 
@@ -1797,7 +1838,7 @@ int tail_bounce(const nxhip_ctx* c)
 // kernel is in the graph only for a scene with an environment map or a background that is not exactly black — PathTracer.cu:
 // 152-164 adds throughput x background, and +0 changes nothing), and the logic kernel's variant (one item per thread under an
 // environment map).  Part of a graph instance's key, so a change of any of them picks or builds the matching instance.
-constexpr int kFlavorScan = 1, kFlavorMissKernel = 2, kFlavorEnvMap = 4, kFlavorEntry = 8, kFlavorThin = 16, kFlavorDropEnded = 32;
+constexpr int kFlavorScan = 1, kFlavorMissKernel = 2, kFlavorEnvMap = 4, kFlavorEntry = 8, kFlavorThin = 16, kFlavorDropEnded = 32, kFlavorAov = 64;
 int pass_flavor(const nxhip_ctx* c)
 {
     int f = 0;
@@ -1816,6 +1857,7 @@ int pass_flavor(const nxhip_ctx* c)
     // dropped by code 0, its miss adds a black background no kernel is launched for — so the material launch does not queue it
     // (kShadeDropEnded).  Pixel-keyed random numbers only: a slot-keyed draw needs the slot the ray goes to.
     if (scan_pipeline(c) && !(f & kFlavorMissKernel) && c->h.rngMode == NX_RNG_PIXEL_KEYED) f |= kFlavorDropEnded;
+    if (c->aov) f |= kFlavorAov;  // (one more branch beside the bounce-1 material step: frame_levels)
     if (c->entryPoints) f |= kFlavorEntry;  // (the slot's table exists before its graph is asked for: ensure_entry_table)
     // The thin kernel (nx_trace.hip) pays when ONE pass runs at a time: the lanes a dry wave leaves idle are then idle SIMD time, and
     // a level ends with its slowest ray (driver command: mean of five repetitions 19.9 -> 19.0 ms, 512 frames in 64-frame passes one at a
@@ -1874,6 +1916,12 @@ std::vector<std::vector<Launch>> frame_levels(nxhip_ctx* c, PassSlot* q)
     const int og = whole_regions(c->shadeBlocksPerCU * c->numCUs);
     const int lg = whole_regions(c->logicBlocksPerCU * c->numCUs), lb = kLogicBlockThreads;
     auto in_use = [&](int type) { return (c->materialTypeMask >> type) & 1u; };
+    // Feature buffers: aov_kernel reads what the primary closest-hit launch left at the rays' slots (hit, hitInst, rays[0]) — records
+    // the bounce-1 material step only reads too, and that nothing writes before the trace launches of bounce 1 — so it runs BESIDE that
+    // step, as one more launch of its level
+    auto aov_beside = [&](std::vector<Launch>& level) {
+        if (pass_flavor(c) & kFlavorAov) level.push_back(make_launch(aov_kernel_ptr(), wide, wideThreads, NXHIP_K_SHADE, S));
+    };
     if (scan_pipeline(c)) {
         // SCAN pipeline (nx_wavefront.hip): the closest-hit launch leaves the logic step's decision in its hit records, the material
         // kernels find their items there.  Per bounce: ONE material launch for the types in use (shade_scan_kernel; the misses as a
@@ -1897,6 +1945,7 @@ std::vector<std::vector<Launch>> frame_levels(nxhip_ctx* c, PassSlot* q)
             shade.type = mask;
             shade.nargs = 3;
             levels.push_back({shade});
+            if (bounce == 1) aov_beside(levels.back());
             if (in_use(NX_MAT_CONDUCTOR) && c->h.conductorMode != NX_CONDUCTOR_EXTENDED) {  // (counted, not shaded: count_scan_kernel)
                 Launch count = make_launch(count_scan_kernel_ptr(), lg, kWideBlockThreads, NXHIP_K_LOGIC, S, bounce);
                 count.type = NX_MAT_CONDUCTOR;
@@ -1915,6 +1964,7 @@ std::vector<std::vector<Launch>> frame_levels(nxhip_ctx* c, PassSlot* q)
     const int ob = kShadeBlockOrderedThreads;
     for (int bounce = 1; bounce <= pathLength; bounce++) {
         levels.push_back({make_launch(logic_kernel_ptr(c->hdrMap.texels.p ? 1 : 2), lg, lb, NXHIP_K_LOGIC, S, bounce)});
+        if (bounce == 1) aov_beside(levels.back());
         // graph insertion order of the reference: Diffuse, Plastic, Dielectric, Conductor (PathTracer.cpp:116-120)
         // (only the types some material of the scene has: a queue no material feeds stays empty)
         std::vector<Launch> shade;
@@ -1934,7 +1984,9 @@ std::vector<std::vector<Launch>> frame_levels(nxhip_ctx* c, PassSlot* q)
 
 void fill_args(Launch& l, void** args)
 {
+    if (l.nargs == 40) { args[0] = (void*)&l.dn; return; }
     args[0] = (void*)&l.s;
+    if (l.nargs == 5) for (int k = 0; k < 4; k++) args[1 + k] = (void*)&l.plane[k];
     if (l.nargs == 2 || l.nargs == 3) args[1] = (void*)&l.bounce;
     if (l.nargs == 3) args[2] = (void*)&l.type;
     if (l.nargs == 30) { args[1] = (void*)&l.ptr; args[2] = (void*)&l.count; }
@@ -2071,6 +2123,18 @@ static int ensure_entry_table(nxhip_ctx* c, PassSlot* q)
     return NXHIP_OK;
 }
 
+// Feature buffers on: slot q holds two float4 per path of its queue capacity.
+static int ensure_slot_aov(nxhip_ctx* c, PassSlot* q)
+{
+    const size_t bytes = std::max<size_t>(q->pathCapacity, 1) * sizeof(float4);
+    if (q->aovAlbedo.p && q->aovNormalDepth.p && q->aovAlbedo.bytes >= bytes && q->aovNormalDepth.bytes >= bytes) return NXHIP_OK;
+    NX_SYNC_ALL(c);
+    NX_ALLOC(q->aovAlbedo, bytes);
+    NX_ALLOC(q->aovNormalDepth, bytes);
+    c->stateDirty = true;
+    return NXHIP_OK;
+}
+
 static int ensure_slot_events(PassSlot* q)
 {
     if (!q->done) NX_HIP(hipEventCreateWithFlags(&q->done, hipEventDisableTiming));
@@ -2104,6 +2168,12 @@ try {
     if (rc != NXHIP_OK) return rc;
     if (!slot_queues_ready(c, q)) {
         rc = ensure_slot_queues(c, q);
+        if (rc != NXHIP_OK) return rc;
+        rc = upload_state(c);
+        if (rc != NXHIP_OK) return rc;
+    }
+    if (c->aov) {  // the slot's feature buffers, as large as its queues
+        rc = ensure_slot_aov(c, q);
         if (rc != NXHIP_OK) return rc;
         rc = upload_state(c);
         if (rc != NXHIP_OK) return rc;
@@ -2191,8 +2261,15 @@ static int launch_accumulate(nxhip_ctx* c, PassSlot* stateSlot, const float4* sr
     l.firstFrame = firstFrame;
     l.dstMap = dstMap;
     const size_t before = c->timerPool.size();
-    const int rc = launch_now(c, l);
+    int rc = launch_now(c, l);
     if (rc == NXHIP_OK && c->timerPool.size() > before) c->timerClass.push_back(l.klass);
+    // the slot's own pass with feature buffers: the same running mean, in the same frame order, over them (nx_aov.hip)
+    if (rc == NXHIP_OK && !src && c->aov && stateSlot->aovAlbedo.p && stateSlot->aovNormalDepth.p) {
+        Launch f = make_launch(aov_fold_kernel_ptr(), c->wideBlocks, kWideBlockThreads, NXHIP_K_ACCUMULATE, stateSlot->dState.as<DeviceState>());
+        const size_t beforeFold = c->timerPool.size();
+        rc = launch_now(c, f);
+        if (rc == NXHIP_OK && c->timerPool.size() > beforeFold) c->timerClass.push_back(f.klass);
+    }
     return rc;
 }
 
@@ -2550,6 +2627,197 @@ try {
 } catch (const std::exception& e) {
     set_error(std::string("nxhip_write_accumulation: ") + e.what());
     return NXHIP_ERR_INVALID;
+}
+
+// ---- feature buffers and the denoiser (nx_aov.hip) ---------------------------------------------------
+
+int nxhip_set_aov(nxhip_ctx* c, int on)
+{
+    NX_CHECK_CTX(c);
+    if ((on != 0) == c->aov) return NXHIP_OK;
+    if (on && c->frameNumber != 0u) return fail_invalid("nxhip_set_aov: frames have been accumulated without feature buffers - reset the frame number first (colour and features must cover the same frames)");
+    NX_HIP(hipSetDevice(c->device));
+    NX_SYNC_ALL(c);
+    if (on) {
+        const size_t full = std::max<size_t>((size_t)c->width * c->height, c->localCount);
+        DevBuf a, n;  // all or nothing
+        if (!a.alloc(full * 16) || !n.alloc(full * 16)) return NXHIP_ERR_HIP;
+        NX_HIP(hipMemset(a.p, 0, full * 16));
+        NX_HIP(hipMemset(n.p, 0, full * 16));
+        c->aovAccumAlbedo = std::move(a);
+        c->aovAccumNormalDepth = std::move(n);
+    } else {
+        c->aovAccumAlbedo.release();
+        c->aovAccumNormalDepth.release();
+        for (uint32_t k = 0; k < slot_count(c); k++) {
+            slot_at(c, k)->aovAlbedo.release();
+            slot_at(c, k)->aovNormalDepth.release();
+        }
+        release_denoise_planes(c);
+    }
+    c->aov = on != 0;
+    c->h.aovAccumAlbedo = c->aovAccumAlbedo.as<float4>();
+    c->h.aovAccumNormalDepth = c->aovAccumNormalDepth.as<float4>();
+    c->stateDirty = true;  // (the pass graphs follow by their flavor: kFlavorAov)
+    return NXHIP_OK;
+}
+
+static int aov_required(nxhip_ctx* c, const char* who)
+{
+    if (!c->aov) return fail_invalid(std::string(who) + ": the feature buffers are off (nxhip_set_aov)");
+    return NXHIP_OK;
+}
+
+int nxhip_read_aov(nxhip_ctx* c, float* albedo4, float* normalDepth4)
+{
+    NX_CHECK_CTX(c);
+    int rc = aov_required(c, "nxhip_read_aov");
+    if (rc != NXHIP_OK) return rc;
+    NX_HIP(hipSetDevice(c->device));
+    NX_SYNC_ALL(c);
+    if (albedo4) NX_HIP(hipMemcpy(albedo4, c->aovAccumAlbedo.p, (size_t)c->localCount * 16, hipMemcpyDeviceToHost));
+    if (normalDepth4) NX_HIP(hipMemcpy(normalDepth4, c->aovAccumNormalDepth.p, (size_t)c->localCount * 16, hipMemcpyDeviceToHost));
+    return NXHIP_OK;
+}
+
+int nxhip_read_aov_frame(nxhip_ctx* c, float* albedo4, float* normalDepth4)
+{
+    NX_CHECK_CTX(c);
+    int rc = aov_required(c, "nxhip_read_aov_frame");
+    if (rc != NXHIP_OK) return rc;
+    const PassSlot* q = c->lastRendered ? c->lastRendered : static_cast<PassSlot*>(c);
+    const size_t bytes = (size_t)c->pathCount * 16;
+    if (!q->aovAlbedo.p || !q->aovNormalDepth.p || q->aovAlbedo.bytes < bytes || q->aovNormalDepth.bytes < bytes)
+        return fail_invalid("nxhip_read_aov_frame: no pass has been rendered with the feature buffers on (or its queues were released)");
+    NX_HIP(hipSetDevice(c->device));
+    NX_SYNC_ALL(c);
+    if (albedo4) NX_HIP(hipMemcpy(albedo4, q->aovAlbedo.p, bytes, hipMemcpyDeviceToHost));
+    if (normalDepth4) NX_HIP(hipMemcpy(normalDepth4, q->aovNormalDepth.p, bytes, hipMemcpyDeviceToHost));
+    return NXHIP_OK;
+}
+
+int nxhip_write_aov(nxhip_ctx* c, const float* albedo4, const float* normalDepth4)
+{
+    NX_CHECK_CTX(c);
+    int rc = aov_required(c, "nxhip_write_aov");
+    if (rc != NXHIP_OK) return rc;
+    NX_HIP(hipSetDevice(c->device));
+    NX_SYNC_ALL(c);
+    if (albedo4) NX_HIP(hipMemcpy(c->aovAccumAlbedo.p, albedo4, (size_t)c->localCount * 16, hipMemcpyHostToDevice));
+    if (normalDepth4) NX_HIP(hipMemcpy(c->aovAccumNormalDepth.p, normalDepth4, (size_t)c->localCount * 16, hipMemcpyHostToDevice));
+    return NXHIP_OK;
+}
+
+int nxhip_denoise_defaults(nx_denoise_params* p)
+{
+    if (!p) return fail_invalid("nxhip_denoise_defaults: null destination");
+    // (chosen from the sweep of profiles/r09_denoise.txt: Cornell box 256 x 256, 16 frames, error against 4 096 frames)
+    p->iterations = 5u;
+    p->sigmaColor = 2.5f;
+    p->sigmaNormal = 0.3f;
+    p->sigmaAlbedo = 0.2f;
+    p->sigmaDepth = 0.025f;
+    return NXHIP_OK;
+}
+
+static float inverse_square(float sigma)
+{
+    const float s2 = sigma * sigma;
+    return std::min(1.0f / s2, 3.402823466e38f);  // (a sigma whose square underflows: 0 x "infinity" must not become a NaN)
+}
+
+int nxhip_denoise(nxhip_ctx* c, const nx_denoise_params* params)
+{
+    NX_CHECK_CTX(c);
+    int rc = aov_required(c, "nxhip_denoise");
+    if (rc != NXHIP_OK) return rc;
+    nx_denoise_params p;
+    (void)nxhip_denoise_defaults(&p);
+    if (params) p = *params;
+    if (p.iterations > 6u) return fail_invalid("nxhip_denoise: iterations must be in [0, 6]");
+    for (const float sigma : {p.sigmaColor, p.sigmaNormal, p.sigmaAlbedo, p.sigmaDepth})
+        if (!(sigma > 0.0f) || !std::isfinite(sigma)) return fail_invalid("nxhip_denoise: every sigma must be a positive finite number");
+    const uint32_t full = c->width * c->height;
+    if (!c->coversFrame || c->localCount != full)
+        return fail_invalid("nxhip_denoise: the filter works in image space and needs a context that renders the full frame (NXHIP_ORDER_ROWS / NXHIP_ORDER_TILES); "
+                            "this one renders a tile split (nxhip_set_pixel_map with a partial set, nxhip_mgpu_*)");
+    NX_HIP(hipSetDevice(c->device));
+    rc = upload_state(c);
+    if (rc != NXHIP_OK) return rc;
+    if (!c->dnRgba8.p) {
+        DevBuf planes[5], rgba;  // all or nothing
+        for (DevBuf& b : planes)
+            if (!b.alloc((size_t)full * 16)) return NXHIP_ERR_HIP;
+        if (!rgba.alloc((size_t)full * 4)) return NXHIP_ERR_HIP;
+        c->dnColour = std::move(planes[0]);
+        c->dnAlbedo = std::move(planes[1]);
+        c->dnNormalDepth = std::move(planes[2]);
+        c->dnPing = std::move(planes[3]);
+        c->dnPong = std::move(planes[4]);
+        c->dnRgba8 = std::move(rgba);
+    }
+    // on the context's stream: behind the accumulates already issued
+    auto issue = [&](Launch& l) {
+        const size_t before = c->timerPool.size();
+        const int r = launch_now(c, l);
+        if (r == NXHIP_OK && c->timerPool.size() > before) c->timerClass.push_back(l.klass);
+        return r;
+    };
+    Launch g = make_launch(denoise_gather_kernel_ptr(), c->wideBlocks, kWideBlockThreads, NXHIP_K_ACCUMULATE, c->dState.as<DeviceState>());
+    g.nargs = 5;
+    g.plane[0] = c->dnColour.p;
+    g.plane[1] = c->dnAlbedo.p;
+    g.plane[2] = c->dnNormalDepth.p;
+    g.plane[3] = p.iterations == 0u ? c->dnRgba8.p : nullptr;
+    rc = issue(g);
+    if (rc != NXHIP_OK) return rc;
+    bool forceDirect = false;  // (sweeps only: the plane variant for steps 1 and 2 too)
+    if (const char* on = std::getenv("NX_TUNING_KNOBS"); on && std::atoi(on) == 1)
+        if (const char* e = std::getenv("NX_DENOISE_DIRECT")) forceDirect = std::atoi(e) != 0;
+    const void* in = c->dnColour.p;
+    for (uint32_t i = 0; i < p.iterations; i++) {
+        void* out = (i & 1u) ? c->dnPong.p : c->dnPing.p;
+        const int step = 1 << i;
+        Launch l = make_launch(denoise_iteration_kernel_ptr(step, forceDirect), 1, 1, NXHIP_K_ACCUMULATE, nullptr);
+        l.grid = dim3((c->width + 31u) / 32u, (c->height + 7u) / 8u);
+        l.block = dim3(32, 8);
+        l.nargs = 40;
+        l.dn.colour = static_cast<const float4*>(in);
+        l.dn.albedo = c->dnAlbedo.as<float4>();
+        l.dn.normalDepth = c->dnNormalDepth.as<float4>();
+        l.dn.out = static_cast<float4*>(out);
+        l.dn.rgba8 = i + 1u == p.iterations ? c->dnRgba8.as<uint32_t>() : nullptr;
+        l.dn.width = (int32_t)c->width;
+        l.dn.height = (int32_t)c->height;
+        l.dn.step = step;
+        l.dn.invColour = inverse_square(p.sigmaColor * std::ldexp(1.0f, -(int)i));
+        l.dn.invNormal = inverse_square(p.sigmaNormal);
+        l.dn.invAlbedo = inverse_square(p.sigmaAlbedo);
+        l.dn.sigmaDepth = p.sigmaDepth;
+        rc = issue(l);
+        if (rc != NXHIP_OK) return rc;
+        in = out;
+    }
+    c->denoised = in;
+    return NXHIP_OK;
+}
+
+int nxhip_read_denoised(nxhip_ctx* c, float* rgb)
+{
+    NX_CHECK_CTX(c);
+    if (!c->denoised) return fail_invalid("nxhip_read_denoised: nxhip_denoise has not run since the pixel set last changed");
+    return read_float4_as_float3(c, c->denoised, c->width * c->height, rgb);
+}
+
+int nxhip_read_denoised_rgba8(nxhip_ctx* c, uint32_t* dst)
+{
+    NX_CHECK_CTX(c);
+    if (!dst) return fail_invalid("null destination");
+    if (!c->denoised) return fail_invalid("nxhip_read_denoised_rgba8: nxhip_denoise has not run since the pixel set last changed");
+    NX_HIP(hipSetDevice(c->device));
+    NX_SYNC_ALL(c);
+    NX_HIP(hipMemcpy(dst, c->dnRgba8.p, (size_t)c->width * c->height * 4, hipMemcpyDeviceToHost));
+    return NXHIP_OK;
 }
 
 int nxhip_read_rgba8(nxhip_ctx* c, uint32_t* dst)

@@ -212,7 +212,38 @@ void PathTracer::SetEntryPoints(bool on) { Check(nxhip_set_entry_points(m_Ctx, o
 void PathTracer::SetPixelOrder(int order)
 {
     Check(nxhip_set_pixel_order(m_Ctx, order), "nxhip_set_pixel_order");
+    m_PixelOrder = order;
     m_FrameNumber = 0;  // (a new pixel set starts the accumulation over, as OnResize does)
+}
+
+void PathTracer::SetFeatureBuffers(bool on)
+{
+    if (on) ResetFrameNumber();  // (the library refuses features that would cover fewer frames than the colour)
+    Check(nxhip_set_aov(m_Ctx, on ? 1 : 0), "nxhip_set_aov");
+}
+
+void PathTracer::ReadFeatureBuffers(std::vector<float>& albedo4, std::vector<float>& normalDepth4)
+{
+    if (m_TileSplit) throw std::runtime_error("PathTracer::ReadFeatureBuffers: a tile-split rank holds its own tiles only");
+    const size_t n = static_cast<size_t>(m_ViewportWidth) * m_ViewportHeight;
+    std::vector<float> a(n * 4), d(n * 4);
+    Check(nxhip_read_aov(m_Ctx, a.data(), d.data()), "nxhip_read_aov");
+    if (m_PixelOrder == NXHIP_ORDER_ROWS) {
+        albedo4.swap(a);
+        normalDepth4.swap(d);
+        return;
+    }
+    // path order -> rows: the library's own map of the order (what nxhip_set_pixel_order installed)
+    std::vector<uint32_t> map(n);
+    uint32_t count = 0;
+    Check(nxhip_tile_pixel_map(m_ViewportWidth, m_ViewportHeight, 1, 0, 1, 1, map.data(), &count), "nxhip_tile_pixel_map");
+    albedo4.assign(n * 4, 0.0f);
+    normalDepth4.assign(n * 4, 0.0f);
+    for (size_t k = 0; k < count; k++)
+        for (int c = 0; c < 4; c++) {
+            albedo4[static_cast<size_t>(map[k]) * 4 + c] = a[k * 4 + c];
+            normalDepth4[static_cast<size_t>(map[k]) * 4 + c] = d[k * 4 + c];
+        }
 }
 
 void PathTracer::Render(const Scene&)

@@ -5,6 +5,7 @@
 
 #include <cstdio>
 #include <cstring>
+#include <exception>
 
 namespace nexus {
 
@@ -52,8 +53,57 @@ bool Renderer::SaveScreenshot(const std::string& filepath)
     std::string path = filepath;
     const std::string extension = ".png";
     if (path.length() < extension.length() || path.compare(path.size() - extension.size(), extension.size(), extension) != 0) path += extension;
+    if (m_Denoise) {  // the filtered image (its own buffer: the accumulation and its RGBA8 stay as they are)
+        std::vector<uint32_t> pixels(static_cast<size_t>(m_ViewportWidth) * m_ViewportHeight);
+        nxhip_ctx* ctx = m_PathTracer.GetDeviceContext();
+        if (nxhip_denoise(ctx, nullptr) != NXHIP_OK || nxhip_read_denoised_rgba8(ctx, pixels.data()) != NXHIP_OK) return false;
+        return WritePNG(path, pixels.data(), m_ViewportWidth, m_ViewportHeight, true);
+    }
     const std::vector<uint32_t>& pixels = m_PathTracer.GetPixelBuffer();
     return WritePNG(path, pixels.data(), m_ViewportWidth, m_ViewportHeight, true);
+}
+
+void Renderer::SetDenoise(bool on)
+{
+    if (on == m_Denoise) return;
+    if (on) {
+        m_PathTracer.SetFeatureBuffers(true);
+        Reset();
+    }
+    m_Denoise = on;
+}
+
+bool Renderer::SaveDenoisedEXR(const std::string& filepath)
+{
+    if (!m_Denoise) return false;
+    std::vector<float> rgb(static_cast<size_t>(m_ViewportWidth) * m_ViewportHeight * 3);
+    nxhip_ctx* ctx = m_PathTracer.GetDeviceContext();
+    if (nxhip_denoise(ctx, nullptr) != NXHIP_OK || nxhip_read_denoised(ctx, rgb.data()) != NXHIP_OK) return false;
+    return WriteEXR(filepath, rgb.data(), m_ViewportWidth, m_ViewportHeight, true);
+}
+
+bool Renderer::SaveFeatureEXR(const std::string& filepath)
+{
+    std::string stem = filepath;
+    const std::string extension = ".exr";
+    if (stem.length() >= extension.length() && stem.compare(stem.size() - extension.size(), extension.size(), extension) == 0) stem.resize(stem.size() - extension.size());
+    std::vector<float> albedo4, normalDepth4;
+    try {
+        m_PathTracer.ReadFeatureBuffers(albedo4, normalDepth4);
+    } catch (const std::exception&) {
+        return false;
+    }
+    const size_t n = static_cast<size_t>(m_ViewportWidth) * m_ViewportHeight;
+    std::vector<float> albedo(n * 3), normal(n * 3), depth(n * 3);
+    for (size_t i = 0; i < n; i++)
+        for (int c = 0; c < 3; c++) {
+            albedo[3 * i + c] = albedo4[4 * i + c];
+            normal[3 * i + c] = normalDepth4[4 * i + c];
+            depth[3 * i + c] = normalDepth4[4 * i + 3];
+        }
+    return WriteEXR(stem + ".albedo.exr", albedo.data(), m_ViewportWidth, m_ViewportHeight, true) &&
+           WriteEXR(stem + ".normal.exr", normal.data(), m_ViewportWidth, m_ViewportHeight, true) &&
+           WriteEXR(stem + ".depth.exr", depth.data(), m_ViewportWidth, m_ViewportHeight, true);
 }
 
 bool Renderer::SaveAccumulationEXR(const std::string& filepath)

@@ -95,6 +95,10 @@ BSDF_QUERY_DT = np.dtype([("wi", "<f4", 3), ("rng", "<u4"), ("wo", "<f4", 3), ("
 BSDF_RESULT_DT = np.dtype([("wo", "<f4", 3), ("pdf", "<f4"), ("throughput", "<f4", 3), ("ok", "<u4"), ("rngOut", "<u4"), ("pad_", "<u4", 3)])
 assert BSDF_QUERY_DT.itemsize == 32 and BSDF_RESULT_DT.itemsize == 48
 
+# nx_denoise_params (nxhip_denoise): iterations of the a-trous filter and the widths of its edge-stopping terms
+DENOISE_DT = np.dtype([("iterations", "<u4"), ("sigmaColor", "<f4"), ("sigmaNormal", "<f4"), ("sigmaAlbedo", "<f4"), ("sigmaDepth", "<f4")])
+assert DENOISE_DT.itemsize == 20
+
 MAT_DIFFUSE, MAT_DIELECTRIC, MAT_PLASTIC, MAT_CONDUCTOR = 0, 1, 2, 3
 LIGHT_POINT, LIGHT_AREA, LIGHT_MESH = 0, 1, 2
 RNG_REFERENCE_SLOT, RNG_PIXEL_KEYED = 0, 1
