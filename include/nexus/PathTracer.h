@@ -57,6 +57,15 @@ public:
     // The accumulated feature buffers as full-frame, row-major images (4 floats per pixel each), whatever the pixel order.  Not on a
     // tile split (each rank holds its own tiles only).
     void ReadFeatureBuffers(std::vector<float>& albedo4, std::vector<float>& normalDepth4);
+    // Adaptive sampling (nxhip_set_adaptive: per-pixel noise statistics, a per-block stop rule and — params->cull — passes that render the
+    // unsettled blocks only).  nullptr: off.  Switching it on starts the accumulation over.  Not on a tile split.  The image of an adaptive
+    // run is not an unbiased estimate (include/nexus_hip.h).
+    void SetAdaptive(const nx_adaptive_params* params);
+    // {render `interval` frames, accumulate, decide} until no block is active or maxFrames frames were issued (nxhip_render_adaptive);
+    // returns the frames issued.  activePixels: pixels still active afterwards.
+    uint32_t RenderAdaptive(const Scene& scene, uint32_t maxFrames, uint32_t interval, uint32_t* activePixels = nullptr);
+    // Samples folded into every pixel, as a full-frame, row-major image, whatever the pixel order.  Needs SetAdaptive.
+    void ReadSampleCounts(std::vector<uint32_t>& counts);
     // Multi-GPU extension (no counterpart in the reference): one PathTracer per GPU, each renders and
     // accumulates the interleaved row tiles of its rank; Render() then ends with ONE RCCL gather of the accumulated tiles to
     // rank 0, whose GetPixelBuffer() returns the full frame.  `id128`: the 128 bytes rank 0 obtained from

@@ -42,6 +42,15 @@ public:
     // PathTracer::SetFeatureBuffers(true)).
     bool SaveFeatureEXR(const std::string& filepath);
 
+    // Extension: adaptive sampling (PathTracer::SetAdaptive; nullptr: off).  Switching it on starts the accumulation over.
+    void SetAdaptive(const nx_adaptive_params* params);
+    // Render()'s scene handling, then PathTracer::RenderAdaptive: renders until every block of 64 paths has settled or maxFrames frames
+    // were issued, deciding every `interval` frames.  Returns the frames issued (0 for an empty scene).  GetMegaSamplesPerSecond does
+    // not count these frames: a culled pixel takes no sample.  Combines with SetDenoise.
+    uint32_t RenderAdaptive(Scene& scene, uint32_t maxFrames, uint32_t interval);
+    // The per-pixel sample count as OpenEXR, the count in all three channels (like the depth file of SaveFeatureEXR); needs SetAdaptive.
+    bool SaveSampleCountEXR(const std::string& filepath);
+
     // Extension: PathTracer::SetDeviceBlasBuild for the renderer's scene (meshes loaded from now on are built on the GPU)
     void SetDeviceBlasBuild(bool enable) { m_PathTracer.SetDeviceBlasBuild(*m_Scene, enable); }
 

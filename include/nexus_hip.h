@@ -34,7 +34,9 @@ enum {
     NXHIP_ERR_TIMEOUT = 6    /* nxhip_sync_timeout gave up waiting: the context is DEAD from then on (every later call returns this) */
 };
 
-/* Bumped whenever an entry point changes its signature or meaning, or a struct of this header / nexus_pod.h its layout. */
+/* Bumped whenever an entry point changes its signature or meaning, or a struct of this header / nexus_pod.h its layout.  (Entry points
+ * and structs that are only ADDED — adaptive sampling, nx_adaptive_params — leave it alone: the struct's words join the ABI stamp below,
+ * so a library without them is still refused.) */
 #define NXHIP_API_VERSION 8
 
 /* Thread-local message of the last failing call (replaces CheckCudaErrors -> exit(99), Utils/Utils.cpp:3-12). */
@@ -339,6 +341,64 @@ int nxhip_denoise_defaults(nx_denoise_params *params);
 int nxhip_read_denoised(nxhip_ctx *ctx, float *rgb);
 int nxhip_read_denoised_rgba8(nxhip_ctx *ctx, uint32_t *dst);
 
+/* ---- adaptive sampling ------------------------------------------------------------------------------------
+ * No counterpart in the reference, which sends a path through every pixel for as many frames as the caller guesses.  Off by
+ * default; with it off nothing is allocated and nothing extra is launched.
+ *
+ * The context's BASE set is what nxhip_set_pixel_map / nxhip_set_pixel_order / the identity define.  It keeps sizing the
+ * accumulation, the RGBA8 image, the accumulated feature buffers and every read-back.  Per pixel of it there are three more words:
+ * count (uint32), meanY and M2 (float).  While the mode is on, nxhip_accumulate folds a pass with ONE kernel; for a pixel that the
+ * pass rendered, per frame slice in frame order (binary32, no fused operation):
+ *   n = ++count
+ *   colour  a += (r - a) / n                                   (n == 1: a = r)  — the running mean with the PIXEL's count
+ *   Y = (0.2126 r.x + 0.7152 r.y) + 0.0722 r.z
+ *   d = Y - meanY;  meanY += d / n;  M2 += d * (Y - meanY)     (n == 1: meanY = Y, M2 = 0)   — Welford
+ * and the accumulated feature buffers (nxhip_set_aov) the same way, so features and colour cover the same samples.  While no
+ * pixel has been culled count == frame number, and accumulation, RGBA8 and radiance are what the plain path gives, bit for bit.
+ *
+ * A BLOCK is 64 consecutive paths of the base order (NXHIP_ORDER_TILES: an 8 x 8 pixel tile); the base set's last block may be
+ * partial.  nxhip_adaptive_update decides per pixel with count >= 2
+ *   e = sqrt(M2 / (n (n - 1))) / max(meanY, lumFloor)          relative standard error of the mean luminance
+ * unsettled = count < minSamples or not (e <= threshold) — a non-finite e keeps its block alive — and a pixel with count < 2 is
+ * unsettled.  A block stays active iff any of its pixels is unsettled; a block that has been deactivated stays so.  The
+ * block's largest e (NaN counts as +inf, pixels with count < 2 as 0) is kept for diagnostics.  With cull != 0 the passes that
+ * follow render the pixels of the active blocks only, in base order; with cull == 0 (estimate only) they keep rendering the whole
+ * base set and the block flags are the stop rule alone.
+ *
+ * BIAS.  A stop rule that reads the same samples it stops on biases the estimate (Kirk & Arvo 1991): pixels whose first samples
+ * happen to agree stop early and keep their too-dark (or too-bright) mean.  Deciding per block and the minSamples floor reduce
+ * that; they do not remove it.  The image of an adaptive run is NOT an unbiased estimate.
+ *
+ * Rules:
+ *   - needs NX_RNG_PIXEL_KEYED (a path's radiance must depend on (pixel, frame) only): nxhip_set_adaptive with slot-keyed numbers
+ *     is NXHIP_ERR_INVALID, and so is nxhip_set_modes back to slot-keyed while it is on;
+ *   - turning it on after frames were accumulated is NXHIP_ERR_INVALID (nxhip_reset_frame_number first), as nxhip_set_aov;
+ *   - on a context with nxhip_mgpu_* it is NXHIP_ERR_INVALID, and so is nxhip_mgpu_init / nxhip_mgpu_attach while it is on;
+ *   - nxhip_write_accumulation / nxhip_write_aov while it is on are NXHIP_ERR_INVALID (the counts have no checkpoint form);
+ *   - nxhip_resize, nxhip_set_pixel_map, nxhip_set_pixel_order and nxhip_reset_frame_number start the statistics over: all counts
+ *     0, every block active;
+ *   - cull != 0 and no active block: nxhip_render_frame / nxhip_render return NXHIP_OK, launch nothing and leave the frame number;
+ *   - nxhip_accumulate with nothing pending does nothing (folding the same radiance again would count samples twice);
+ *   - nxhip_read_radiance / nxhip_read_aov_frame return the paths of the last pass: its active count x its frames, active order;
+ *   - every other read-back stays in base order and base size.
+ * params: threshold >= 0, lumFloor > 0 (both finite), else NXHIP_ERR_INVALID.  NULL: off, buffers released, base set restored. */
+int nxhip_adaptive_defaults(nx_adaptive_params *p);   /* threshold 0.05, lumFloor 0.01, minSamples 16, cull 1: starting values, not tuned */
+int nxhip_set_adaptive(nxhip_ctx *ctx, const nx_adaptive_params *p);
+/* Folds the pending passes, decides, rebuilds the active set and synchronises.  activePixels / activeBlocks (either may be NULL):
+ * the pixels / blocks still active. */
+int nxhip_adaptive_update(nxhip_ctx *ctx, uint32_t *activePixels, uint32_t *activeBlocks);
+/* Repeats { render `interval` frames, accumulate, update } until no block is active or maxFrames frames have been issued by this
+ * call.  As the active set shrinks, more frames go into one pass: min(interval, paths the queues already hold / active pixels),
+ * at least 1; nothing is allocated.  Decisions happen at interval boundaries only, so the packing changes no result.
+ * framesRendered: frames issued by this call; activePixels: as of the last update (either may be NULL). */
+int nxhip_render_adaptive(nxhip_ctx *ctx, uint32_t maxFrames, uint32_t interval, uint32_t *framesRendered, uint32_t *activePixels);
+int nxhip_read_sample_counts(nxhip_ctx *ctx, uint32_t *counts);   /* base localCount */
+int nxhip_read_noise_stats(nxhip_ctx *ctx, float *meanM2);        /* base localCount x 2: (meanY, M2) */
+/* As of the last update (before the first: every block active, maxima 0).  blockMax / active may be NULL; capacity in blocks. */
+int nxhip_read_block_noise(nxhip_ctx *ctx, float *blockMax, uint8_t *active, uint32_t capacity, uint32_t *blocks);
+/* The set the next pass renders: base-local index of every path of a frame slice, in order. */
+int nxhip_read_active_map(nxhip_ctx *ctx, uint32_t *baseLocalIndex, uint32_t capacity, uint32_t *count);
+
 /* D_QueueSize after the last rendered frame — Cuda/PathTracer/PathTracer.cuh:61-73.  Each array NX_PATH_MAX_LENGTH ints. */
 typedef struct nxhip_queue_sizes {
     int32_t traceSize[NX_PATH_MAX_LENGTH];
@@ -465,6 +525,7 @@ static inline uint64_t nxhip_header_abi_stamp(void)
         sizeof(nx_camera), offsetof(nx_camera, resolution), sizeof(nx_render_settings), offsetof(nx_render_settings, backgroundColor),
         sizeof(nx_ray), sizeof(nx_hit), sizeof(nx_bsdf_query), sizeof(nx_bsdf_result), offsetof(nx_bsdf_result, rngOut),
         sizeof(nxhip_queue_sizes), sizeof(nxhip_trace_stats), offsetof(nxhip_trace_stats, cycles), sizeof(nxhip_kernel_times), NXHIP_K_COUNT,
+        sizeof(nx_adaptive_params), offsetof(nx_adaptive_params, minSamples), offsetof(nx_adaptive_params, cull),
         sizeof(nx_denoise_params), offsetof(nx_denoise_params, sigmaColor), offsetof(nx_denoise_params, sigmaDepth),
     };
     uint64_t h = 0xcbf29ce484222325ull;

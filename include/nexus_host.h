@@ -159,6 +159,13 @@ int nxs_renderer_set_modes(nxs_renderer *r, int rngMode, int compactMode, int co
 int nxs_renderer_set_denoise(nxs_renderer *r, int on);
 int nxs_renderer_save_denoised_exr(nxs_renderer *r, const char *path);
 int nxs_renderer_save_feature_exr(nxs_renderer *r, const char *path);
+/* Renderer::SetAdaptive / RenderAdaptive / SaveSampleCountEXR and PathTracer::SetAdaptive (extensions; adaptive sampling of the device
+ * layer, include/nexus_hip.h: per-pixel noise statistics, a per-block stop rule, passes over the unsettled blocks).  params == NULL: off.
+ * framesRendered (may be NULL): frames the call issued. */
+int nxs_renderer_set_adaptive(nxs_renderer *r, const nx_adaptive_params *params);
+int nxs_renderer_render_adaptive(nxs_renderer *r, nxs_scene *scene, uint32_t maxFrames, uint32_t interval, uint32_t *framesRendered);
+int nxs_renderer_save_sample_count_exr(nxs_renderer *r, const char *path);
+int nxs_pathtracer_set_adaptive(nxs_pathtracer *p, const nx_adaptive_params *params);
 /* Image writers without stb: PNG (RGBA8; the reference's stbi_write_png) and OpenEXR (scanline, uncompressed, float32 B G R).
  * flipVertically != 0 writes the last row first (the render buffer's row 0 is the bottom of the viewport). */
 int nxh_write_png(const char *path, const uint32_t *rgba8, uint32_t width, uint32_t height, int flipVertically);

@@ -158,6 +158,17 @@ typedef struct nx_denoise_params {
 } nx_denoise_params;
 NX_STATIC_ASSERT(sizeof(nx_denoise_params) == 20, "nx_denoise_params must be 20 bytes");
 
+/* Parameters of nxhip_set_adaptive (include/nexus_hip.h): a pixel is settled when it has at least minSamples samples and the relative
+ * standard error of its mean luminance, sqrt(M2 / (n (n - 1))) / max(meanY, lumFloor), is at most threshold.  cull != 0: blocks of 64
+ * paths whose pixels are all settled are no longer rendered; cull == 0: estimate only. */
+typedef struct nx_adaptive_params {
+    float threshold;
+    float lumFloor;
+    uint32_t minSamples;
+    uint32_t cull;
+} nx_adaptive_params;
+NX_STATIC_ASSERT(sizeof(nx_adaptive_params) == 16, "nx_adaptive_params must be 16 bytes");
+
 /* How Logic/Shade seed their RNG.  REFERENCE_SLOT mirrors Cuda/Random.cuh:79-82 + PathTracer.cu:143,326
  * (seed by queue slot, no bounce term).  PIXEL_KEYED seeds by (global pixel, bounce, frame): the image
  * then does not depend on queue slot order, so it is reproducible under racing compaction and under a

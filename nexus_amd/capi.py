@@ -29,6 +29,8 @@ HIP_SYMBOLS = [
     "nxhip_tile_pixel_map", "nxhip_mgpu_unique_id", "nxhip_mgpu_init", "nxhip_mgpu_attach", "nxhip_mgpu_gather", "nxhip_mgpu_read_rgba8",
     "nxhip_mgpu_read_accumulation", "nxhip_mgpu_shutdown", "nxhip_fmath_batch", "nxhip_abi_stamp", "nxhip_check_library", "nxhip_build_blas_batch", "nxhip_read_blas_batch", "nxhip_debug_set_scan_epoch", "nxhip_debug_ended_rays_of_pass",
     "nxhip_set_aov", "nxhip_read_aov", "nxhip_read_aov_frame", "nxhip_write_aov", "nxhip_denoise", "nxhip_denoise_defaults", "nxhip_read_denoised", "nxhip_read_denoised_rgba8",
+    "nxhip_adaptive_defaults", "nxhip_set_adaptive", "nxhip_adaptive_update", "nxhip_render_adaptive", "nxhip_read_sample_counts", "nxhip_read_noise_stats",
+    "nxhip_read_block_noise", "nxhip_read_active_map",
 ]
 HOST_SYMBOLS = [
     "nxh_bvh8_build", "nxh_tlas_build", "nxh_tlas_refit", "nxh_bvh8_node_count", "nxh_bvh8_prim_count", "nxh_bvh8_nodes",
@@ -38,6 +40,7 @@ HOST_SYMBOLS = [
     "nxs_scene_add_hdr_map_file", "nxs_renderer_create", "nxs_renderer_destroy", "nxs_renderer_render", "nxs_renderer_reset", "nxs_renderer_on_resize",
     "nxs_renderer_save_screenshot", "nxs_renderer_save_exr", "nxs_renderer_frame_number", "nxs_renderer_megasamples_per_second", "nxs_renderer_device_context",
     "nxs_renderer_set_modes", "nxs_renderer_set_denoise", "nxs_renderer_save_denoised_exr", "nxs_renderer_save_feature_exr", "nxs_pathtracer_set_feature_buffers",
+    "nxs_renderer_set_adaptive", "nxs_renderer_render_adaptive", "nxs_renderer_save_sample_count_exr", "nxs_pathtracer_set_adaptive",
     "nxh_load_scene_file", "nxh_loaded_scene_free", "nxh_loaded_mesh_count", "nxh_loaded_mesh_triangle_count", "nxh_loaded_mesh_triangles",
     "nxh_loaded_material_count", "nxh_loaded_materials", "nxh_loaded_instance_count", "nxh_loaded_instances", "nxs_scene_load_file", "nxs_scene_set_instance_transform", "nxs_scene_assign_material", "nxs_scene_set_tlas_refit", "nxs_scene_set_device_tlas", "nxs_pathtracer_set_device_blas_build",
     "nxs_last_error", "nxs_scene_create", "nxs_scene_destroy", "nxs_scene_add_material", "nxs_scene_add_texture", "nxs_scene_set_hdr_map",
@@ -88,6 +91,7 @@ def abi_words():
         pod.CAM_DT.itemsize, off(pod.CAM_DT, "resolution"), pod.SETTINGS_DT.itemsize, off(pod.SETTINGS_DT, "backgroundColor"),
         pod.RAY_DT.itemsize, pod.HIT_DT.itemsize, pod.BSDF_QUERY_DT.itemsize, pod.BSDF_RESULT_DT.itemsize, off(pod.BSDF_RESULT_DT, "rngOut"),
         C.sizeof(QueueSizes), C.sizeof(TraceStats), TraceStats.cycles.offset, C.sizeof(KernelTimes), len(KERNEL_CLASSES),
+        pod.ADAPTIVE_DT.itemsize, off(pod.ADAPTIVE_DT, "minSamples"), off(pod.ADAPTIVE_DT, "cull"),
         pod.DENOISE_DT.itemsize, off(pod.DENOISE_DT, "sigmaColor"), off(pod.DENOISE_DT, "sigmaDepth"),
     ]
 
@@ -196,6 +200,14 @@ def lib():
     L.nxhip_denoise_defaults.argtypes = [vp]
     L.nxhip_read_denoised.argtypes = [vp, vp]
     L.nxhip_read_denoised_rgba8.argtypes = [vp, vp]
+    L.nxhip_adaptive_defaults.argtypes = [vp]
+    L.nxhip_set_adaptive.argtypes = [vp, vp]
+    L.nxhip_adaptive_update.argtypes = [vp, C.POINTER(u32), C.POINTER(u32)]
+    L.nxhip_render_adaptive.argtypes = [vp, u32, u32, C.POINTER(u32), C.POINTER(u32)]
+    L.nxhip_read_sample_counts.argtypes = [vp, vp]
+    L.nxhip_read_noise_stats.argtypes = [vp, vp]
+    L.nxhip_read_block_noise.argtypes = [vp, vp, vp, u32, C.POINTER(u32)]
+    L.nxhip_read_active_map.argtypes = [vp, vp, u32, C.POINTER(u32)]
     # host builders
     L.nxh_bvh8_build.argtypes = [vp, u32, u32, C.POINTER(vp)]
     L.nxh_tlas_build.argtypes = [vp, u32, C.POINTER(vp)]
@@ -453,6 +465,9 @@ def decode_image(data):
 class Context:
     """One ``nxhip_ctx`` (one GPU).  Thin 1:1 wrapper of the C-ABI; raises NexusError on any failure."""
 
+    adaptive = False     # set_adaptive
+    _pass_paths = None   # adaptive: paths of the pass render_frame issued last (what read_radiance returns)
+
     def __init__(self, width, height, device=0, stream=None):
         self.L = lib()
         self.width, self.height = int(width), int(height)
@@ -670,6 +685,10 @@ class Context:
         return int(self.L.nxhip_frame_number(self.h))
 
     def render_frame(self):
+        if self.adaptive:  # the pass renders the active set as it is now
+            active = self.active_count()
+            if active:  # (no active pixel: nothing is rendered and the last pass stays the last pass)
+                self._pass_paths = active * self.frames_per_pass
         check(self.L.nxhip_render_frame(self.h), "nxhip_render_frame")
 
     def accumulate(self):
@@ -780,8 +799,8 @@ class Context:
 
     def read_aov_frame(self):
         """(albedo, normalDepth) of the pass rendered last: (local_count * frames_per_pass, 4) float32 each, frame slices in turn"""
-        a = np.zeros((self.local_count * self.frames_per_pass, 4), np.float32)
-        n = np.zeros((self.local_count * self.frames_per_pass, 4), np.float32)
+        a = np.zeros((self._last_pass_paths(), 4), np.float32)
+        n = np.zeros((self._last_pass_paths(), 4), np.float32)
         check(self.L.nxhip_read_aov_frame(self.h, _ptr(a), _ptr(n)), "nxhip_read_aov_frame")
         return a, n
 
@@ -814,6 +833,66 @@ class Context:
         check(self.L.nxhip_read_denoised_rgba8(self.h, _ptr(out)), "nxhip_read_denoised_rgba8")
         return out
 
+    # ---- adaptive sampling (include/nexus_hip.h) ----
+    def set_adaptive(self, threshold=None, lum_floor=None, min_samples=None, cull=None, on=True):
+        """Per-pixel noise statistics, the per-block stop rule and (cull) the device-built active set; None = the library's
+        default for that parameter.  on=False: off, buffers released, base set restored."""
+        if not on:
+            check(self.L.nxhip_set_adaptive(self.h, None), "nxhip_set_adaptive")
+            self.adaptive = False
+            return
+        p = adaptive_defaults()
+        for name, v in (("threshold", threshold), ("lumFloor", lum_floor), ("minSamples", min_samples), ("cull", cull)):
+            if v is not None:
+                p[name] = v
+        check(self.L.nxhip_set_adaptive(self.h, _ptr(p)), "nxhip_set_adaptive")
+        self.adaptive = True
+        self._pass_paths = None
+
+    def adaptive_update(self):
+        """Folds pending passes, decides, rebuilds the active set, synchronises: (active pixels, active blocks)"""
+        px, bl = C.c_uint32(0), C.c_uint32(0)
+        check(self.L.nxhip_adaptive_update(self.h, C.byref(px), C.byref(bl)), "nxhip_adaptive_update")
+        return px.value, bl.value
+
+    def render_adaptive(self, max_frames, interval):
+        """{render interval frames, accumulate, update} until no block is active or max_frames: (frames issued, active pixels)"""
+        fr, px = C.c_uint32(0), C.c_uint32(0)
+        self._pass_paths = None
+        check(self.L.nxhip_render_adaptive(self.h, int(max_frames), int(interval), C.byref(fr), C.byref(px)), "nxhip_render_adaptive")
+        return fr.value, px.value
+
+    def read_sample_counts(self):
+        out = np.zeros(self.local_count, np.uint32)
+        check(self.L.nxhip_read_sample_counts(self.h, _ptr(out)), "nxhip_read_sample_counts")
+        return out
+
+    def read_noise_stats(self):
+        """(local_count, 2) float32: Welford's (meanY, M2) of the luminance, base order"""
+        out = np.zeros((self.local_count, 2), np.float32)
+        check(self.L.nxhip_read_noise_stats(self.h, _ptr(out)), "nxhip_read_noise_stats")
+        return out
+
+    def read_block_noise(self):
+        """(largest relative standard error per block, active flag per block) as of the last adaptive_update"""
+        n = C.c_uint32(0)
+        check(self.L.nxhip_read_block_noise(self.h, None, None, 0, C.byref(n)), "nxhip_read_block_noise")
+        bmax, active = np.zeros(n.value, np.float32), np.zeros(n.value, np.uint8)
+        check(self.L.nxhip_read_block_noise(self.h, _ptr(bmax), _ptr(active), n.value, C.byref(n)), "nxhip_read_block_noise")
+        return bmax, active
+
+    def active_count(self):
+        n = C.c_uint32(0)
+        check(self.L.nxhip_read_active_map(self.h, None, 0, C.byref(n)), "nxhip_read_active_map")
+        return n.value
+
+    def read_active_map(self):
+        """base-local index of every path of a frame slice of the next pass, in order"""
+        out = np.zeros(max(self.active_count(), 1), np.uint32)
+        n = C.c_uint32(0)
+        check(self.L.nxhip_read_active_map(self.h, _ptr(out), len(out), C.byref(n)), "nxhip_read_active_map")
+        return out[:n.value]
+
     def bind_radiance(self, dev_ptr, capacity):
         check(self.L.nxhip_bind_radiance(self.h, C.c_void_p(dev_ptr) if dev_ptr else None, capacity), "nxhip_bind_radiance")
 
@@ -834,9 +913,17 @@ class Context:
         check(self.L.nxhip_sync(self.h), "nxhip_sync")
 
     def read_radiance(self):
-        out = np.zeros((self.local_count * self.frames_per_pass, 3), np.float32)
+        out = np.zeros((self._last_pass_paths(), 3), np.float32)
         check(self.L.nxhip_read_radiance(self.h, _ptr(out)), "nxhip_read_radiance")
         return out
+
+    def _last_pass_paths(self):
+        if not self.adaptive:
+            return self.local_count * self.frames_per_pass
+        if self._pass_paths is None:
+            raise NexusError("adaptive sampling: the per-path values are those of the last render_frame pass; none has been issued since "
+                             "set_adaptive / render_adaptive (whose passes pack a number of frames this wrapper does not know)")
+        return self._pass_paths
 
     def read_accumulation(self):
         out = np.zeros((self.local_count, 3), np.float32)
@@ -945,6 +1032,13 @@ def denoise_defaults():
     """nxhip_denoise_defaults as a pod.DENOISE_DT record"""
     p = np.zeros(1, pod.DENOISE_DT)
     check(lib().nxhip_denoise_defaults(_ptr(p)), "nxhip_denoise_defaults")
+    return p
+
+
+def adaptive_defaults():
+    """nxhip_adaptive_defaults as a pod.ADAPTIVE_DT record"""
+    p = np.zeros(1, pod.ADAPTIVE_DT)
+    check(lib().nxhip_adaptive_defaults(_ptr(p)), "nxhip_adaptive_defaults")
     return p
 
 
@@ -1099,6 +1193,9 @@ class Renderer:
         L.nxs_renderer_set_denoise.argtypes = [C.c_void_p, C.c_int]
         L.nxs_renderer_save_denoised_exr.argtypes = [C.c_void_p, C.c_char_p]
         L.nxs_renderer_save_feature_exr.argtypes = [C.c_void_p, C.c_char_p]
+        L.nxs_renderer_set_adaptive.argtypes = [C.c_void_p, C.c_void_p]
+        L.nxs_renderer_render_adaptive.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]
+        L.nxs_renderer_save_sample_count_exr.argtypes = [C.c_void_p, C.c_char_p]
         h = C.c_void_p()
         _scheck(L.nxs_renderer_create(width, height, scene.h, device, C.byref(h)), "nxs_renderer_create")
         self.h = h
@@ -1140,6 +1237,20 @@ class Renderer:
     def save_feature_exr(self, path):
         """<stem>.albedo.exr, <stem>.normal.exr, <stem>.depth.exr beside each other"""
         _scheck(self.L.nxs_renderer_save_feature_exr(self.h, str(path).encode()), "nxs_renderer_save_feature_exr")
+
+    def set_adaptive(self, params=None):
+        """Renderer::SetAdaptive: a pod.ADAPTIVE_DT record (adaptive_defaults()), None = off; starts the accumulation over"""
+        p = None if params is None else np.ascontiguousarray(params, dtype=pod.ADAPTIVE_DT).reshape(1)
+        _scheck(self.L.nxs_renderer_set_adaptive(self.h, _ptr(p) if p is not None else None), "nxs_renderer_set_adaptive")
+
+    def render_adaptive(self, scene, max_frames, interval):
+        """Renderer::RenderAdaptive: the frames issued"""
+        frames = C.c_uint32(0)
+        _scheck(self.L.nxs_renderer_render_adaptive(self.h, scene.h, int(max_frames), int(interval), C.byref(frames)), "nxs_renderer_render_adaptive")
+        return frames.value
+
+    def save_sample_count_exr(self, path):
+        _scheck(self.L.nxs_renderer_save_sample_count_exr(self.h, str(path).encode()), "nxs_renderer_save_sample_count_exr")
 
     def device_context(self):
         """the renderer's nxhip_ctx wrapped as a Context that does not own it (read-backs; do not close)"""
@@ -1212,6 +1323,12 @@ class PathTracer:
         """PathTracer::SetFeatureBuffers: albedo / normal / depth of the camera ray's hit, accumulated like the colour"""
         self.L.nxs_pathtracer_set_feature_buffers.argtypes = [C.c_void_p, C.c_int]
         _scheck(self.L.nxs_pathtracer_set_feature_buffers(self.h, 1 if on else 0), "nxs_pathtracer_set_feature_buffers")
+
+    def set_adaptive(self, params=None):
+        """PathTracer::SetAdaptive: a pod.ADAPTIVE_DT record (adaptive_defaults()), None = off"""
+        self.L.nxs_pathtracer_set_adaptive.argtypes = [C.c_void_p, C.c_void_p]
+        p = None if params is None else np.ascontiguousarray(params, dtype=pod.ADAPTIVE_DT).reshape(1)
+        _scheck(self.L.nxs_pathtracer_set_adaptive(self.h, _ptr(p) if p is not None else None), "nxs_pathtracer_set_adaptive")
 
     def set_device_blas_build(self, scene, enable=True):
         """PathTracer::SetDeviceBlasBuild: meshes added to `scene` from now on are built into BVH8s on the GPU"""

@@ -353,6 +353,21 @@ int nxs_renderer_save_feature_exr(nxs_renderer* r, const char* path)
         if (!path || !r->r.SaveFeatureEXR(path)) throw std::runtime_error(std::string("cannot write the feature buffers to ") + (path ? path : "(null)") + " (are they on?)");
     });
 }
+int nxs_renderer_set_adaptive(nxs_renderer* r, const nx_adaptive_params* params) { return guarded([&] { r->r.SetAdaptive(params); }); }
+int nxs_renderer_render_adaptive(nxs_renderer* r, nxs_scene* scene, uint32_t maxFrames, uint32_t interval, uint32_t* framesRendered)
+{
+    return guarded([&] {
+        const uint32_t frames = r->r.RenderAdaptive(scene->scene, maxFrames, interval);
+        if (framesRendered) *framesRendered = frames;
+    });
+}
+int nxs_renderer_save_sample_count_exr(nxs_renderer* r, const char* path)
+{
+    return guarded([&] {
+        if (!path || !r->r.SaveSampleCountEXR(path)) throw std::runtime_error(std::string("cannot write the sample counts to ") + (path ? path : "(null)") + " (is adaptive sampling on?)");
+    });
+}
+int nxs_pathtracer_set_adaptive(nxs_pathtracer* p, const nx_adaptive_params* params) { return guarded([&] { p->pt.SetAdaptive(params); }); }
 
 int nxh_write_png(const char* path, const uint32_t* rgba8, uint32_t width, uint32_t height, int flipVertically)
 {

@@ -175,9 +175,9 @@ __global__ void __launch_bounds__(kDnTileW * kDnTileH) denoise_iteration_kernel(
 __global__ void __launch_bounds__(kAovBlock) denoise_gather_kernel(const DeviceState* __restrict__ S, float4* __restrict__ colour, float4* __restrict__ albedo,
                                                                     float4* __restrict__ normalDepth, uint32_t* __restrict__ rgba8)
 {
-    const uint32_t count = S->localCount;
+    const uint32_t count = S->baseCount;  // (the base set: what `accumulation` is sized by, whatever set the passes render — nx_adaptive.hip)
     for (uint32_t k = blockIdx.x * blockDim.x + threadIdx.x; k < count; k += gridDim.x * blockDim.x) {
-        const uint32_t g = S->pixelMap ? S->pixelMap[k] : k;
+        const uint32_t g = S->basePixelMap ? S->basePixelMap[k] : k;
         const float4 c = S->accumulation[k];
         colour[g] = make_float4(c.x, c.y, c.z, 0.0f);
         albedo[g] = S->aovAccumAlbedo[k];

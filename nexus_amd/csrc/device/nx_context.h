@@ -125,6 +125,7 @@ struct PassSlot {
     bool awaitingAccumulate = false;   // holds a rendered pass that nxhip_accumulate has not consumed yet
     bool accumulateRecorded = false;   // `accumulated` was recorded after the last use: the next use must wait for it
     uint32_t frames = 0, frameLast = 0;  // of the pass it holds
+    uint32_t passPixels = 0;             // pixels per frame slice of the pass it holds (adaptive sampling: the active set it was rendered with)
     DeviceState view{};  // host mirror of this slot's device-state block
 };
 
@@ -224,4 +225,16 @@ struct nxhip_ctx : nxd::PassSlot {
     // normal + depth, the two colour planes the iterations alternate between, the tonemapped result
     nxd::DevBuf dnColour, dnAlbedo, dnNormalDepth, dnPing, dnPong, dnRgba8;
     const void* denoised = nullptr;  // the plane that holds the last nxhip_denoise's result (nullptr: none since the pixel set changed)
+    // adaptive sampling (nx_adaptive.hip; nxhip_set_adaptive).  localCount / pixelMap above stay the BASE set (image and read-back size);
+    // the set the passes render is activeCount paths of adPixelMap while `adaptive` is on.
+    bool adaptive = false;
+    nx_adaptive_params adParams{};
+    nxd::DevBuf adCount, adStats;                    // [localCount] uint32 / float2 (meanY, M2)
+    nxd::DevBuf adActiveIndex, adPixelMap;           // [localCount] the active set: base-local index, global pixel
+    nxd::DevBuf adBlockFlag, adBlockMax, adBlockOffset, adTotals;  // [blocks] x 3, [2]
+    uint32_t* adHostTotals = nullptr;                // pinned: {pixels, blocks} of the flagged blocks as of the last update
+    uint32_t adBlocks = 0;                           // ceil(localCount / 64)
+    uint32_t activeCount = 0;                        // paths per frame slice of the next pass (cull == 0: always localCount)
+    uint32_t unsettledPixels = 0, unsettledBlocks = 0;  // of the flagged blocks
+    uint32_t passFrames = 0;                         // frames of the pass being issued (nxhip_render_adaptive packs frames; 0: framesPerPass)
 };

@@ -384,6 +384,31 @@ struct DeviceState {
     NX_G float4* aovNormalDepth;
     NX_G float4* aovAccumAlbedo;
     NX_G float4* aovAccumNormalDepth;
+    // Adaptive sampling (nxhip_set_adaptive; nx_adaptive.hip).  The context's BASE set — what sizes `accumulation`, `rgba8` and the accumulated
+    // feature buffers — is always here; while adaptive sampling is off it is the set the passes render (localCount, pixelMap) and the three
+    // pointers behind it are nullptr.  While it is on, localCount / pixelMap above are the ACTIVE set: path k of a slice belongs to element
+    // activeIndex[k] of the base order.
+    const NX_G uint32_t* basePixelMap;  // base-local -> global pixel, nullptr = identity
+    const NX_G uint32_t* activeIndex;   // [localCount]
+    NX_G uint32_t* adCount;             // [baseCount] samples folded into the pixel
+    NX_G float2* adStats;               // [baseCount] Welford (meanY, M2) of the luminance
+    uint32_t baseCount;
+    uint32_t padAdaptive_;
+};
+
+// Argument block of the adaptive update's kernels (nx_adaptive.hip; filled by nxhip_adaptive_update)
+struct AdaptiveLaunch {
+    const uint32_t* count;
+    const float2* stats;
+    uint32_t* blockFlag;     // [blocks] 1: some pixel of the block is unsettled; only ever cleared
+    float* blockMax;         // [blocks] the block's largest relative standard error as of the last decision
+    uint32_t* blockOffset;   // [blocks] flagged blocks in front of this one
+    uint32_t* totals;        // [2] pixels of the flagged blocks, flagged blocks
+    const uint32_t* basePixelMap;
+    uint32_t* activeIndex;   // [baseCount]
+    uint32_t* pixelMap;      // [baseCount]
+    uint32_t baseCount, blocks, minSamples;
+    float threshold, lumFloor;
 };
 
 // Argument block of one iteration of the edge-avoiding a-trous filter (nx_aov.hip denoise_iteration_kernel; filled by nxhip_denoise).
@@ -412,7 +437,7 @@ constexpr uint64_t layout_stamp()
     const uint64_t w[] = {
         sizeof(DeviceState), offsetof(DeviceState, camera), offsetof(DeviceState, envSampling), offsetof(DeviceState, localCount), offsetof(DeviceState, pixelMap),
         offsetof(DeviceState, radiance), offsetof(DeviceState, trace), offsetof(DeviceState, shadow), offsetof(DeviceState, material), offsetof(DeviceState, counters),
-        offsetof(DeviceState, frame), offsetof(DeviceState, traceStats), offsetof(DeviceState, scanStatus), offsetof(DeviceState, entry), offsetof(DeviceState, entryRuns), offsetof(DeviceState, debugRequeue), offsetof(DeviceState, aovAlbedo), offsetof(DeviceState, aovAccumNormalDepth), offsetof(DeviceState, thinStates), offsetof(DeviceState, leafOfInstance), sizeof(ThinState), offsetof(ThinState, stack), offsetof(DeviceState, thinClosest), offsetof(DeviceState, thinCapacity), offsetof(DeviceState, thinIters), offsetof(DeviceState, thinPoolLimit), offsetof(Counters, thinCount), sizeof(EntryState), offsetof(EntryState, sp), offsetof(EntryState, triP0), offsetof(EntryState, triInst), offsetof(Counters, scanTicket), offsetof(FrameState, scanEpoch),
+        offsetof(DeviceState, frame), offsetof(DeviceState, traceStats), offsetof(DeviceState, scanStatus), offsetof(DeviceState, entry), offsetof(DeviceState, entryRuns), offsetof(DeviceState, debugRequeue), offsetof(DeviceState, aovAlbedo), offsetof(DeviceState, aovAccumNormalDepth), offsetof(DeviceState, basePixelMap), offsetof(DeviceState, adStats), offsetof(DeviceState, baseCount), sizeof(AdaptiveLaunch), offsetof(AdaptiveLaunch, baseCount), offsetof(DeviceState, thinStates), offsetof(DeviceState, leafOfInstance), sizeof(ThinState), offsetof(ThinState, stack), offsetof(DeviceState, thinClosest), offsetof(DeviceState, thinCapacity), offsetof(DeviceState, thinIters), offsetof(DeviceState, thinPoolLimit), offsetof(Counters, thinCount), sizeof(EntryState), offsetof(EntryState, sp), offsetof(EntryState, triP0), offsetof(EntryState, triInst), offsetof(Counters, scanTicket), offsetof(FrameState, scanEpoch),
         (uint64_t)kScanKinds, (uint64_t)kScanWords, (uint64_t)kScanEpochLimit, (uint64_t)kShadeBlockOrderedThreads,
         sizeof(Counters), sizeof(RegionCounters), offsetof(RegionCounters, traceShadowSize), offsetof(RegionCounters, materialSize), offsetof(RegionCounters, traceHead),
         offsetof(RegionCounters, shadowHead), offsetof(RegionCounters, scanTile), offsetof(RegionCounters, endedSize), offsetof(Counters, orderedBase), offsetof(Counters, tailHead),

@@ -42,6 +42,12 @@ uint64_t layout_stamp_lbvh();
 uint64_t layout_stamp_multigpu();
 uint64_t layout_stamp_entry();
 uint64_t layout_stamp_aov();
+const void* adaptive_accumulate_kernel_ptr();
+const void* adaptive_aov_fold_kernel_ptr();
+const void* adaptive_decide_kernel_ptr();
+const void* adaptive_scan_kernel_ptr();
+const void* adaptive_fill_kernel_ptr();
+uint64_t layout_stamp_adaptive();
 const void* bsdf_hook_kernel_ptr();
 const void* fmath_hook_kernel_ptr();
 const void* tex2d_hook_kernel_ptr();
@@ -131,6 +137,7 @@ static int check_layouts()
     const struct { const char* unit; uint64_t stamp; } units[] = {
         {"nx_trace.hip", layout_stamp_trace()}, {"nx_wavefront.hip", layout_stamp_wavefront()}, {"nx_refit.hip", layout_stamp_refit()},
         {"nx_lbvh.hip", layout_stamp_lbvh()}, {"nxhip_multigpu.hip", layout_stamp_multigpu()}, {"nx_entry.hip", layout_stamp_entry()}, {"nx_aov.hip", layout_stamp_aov()},
+        {"nx_adaptive.hip", layout_stamp_adaptive()},
     };
     for (const auto& u : units) {
         if (u.stamp != layout_stamp()) {
@@ -252,7 +259,8 @@ static void compose_view(nxhip_ctx* c, PassSlot* s)
     v.thinCapacity = (s->thinLists.p && s->thinStates.p) ? kThinListEntries : 0u;
     v.thinStates = s->thinStates.as<ThinState>();
     v.entry = (c->entryPoints && s->entryTable.p) ? s->entryTable.as<EntryState>() : nullptr;
-    v.entryRuns = v.entry ? s->entryRuns : 0u;
+    // (adaptive sampling: the table keeps the base set's size, the pass walks the runs of the active set — whole blocks in base order)
+    v.entryRuns = v.entry ? (c->adaptive ? (c->activeCount + 63u) / 64u : s->entryRuns) : 0u;
     v.aovAlbedo = c->aov ? s->aovAlbedo.as<float4>() : nullptr;  // (per slot, like the entry table; the running means are the context's: c->h)
     v.aovNormalDepth = c->aov ? s->aovNormalDepth.as<float4>() : nullptr;
     // queue regions: eight, or one spanning the buffer when slots are handed out in the reference's serial order
@@ -389,6 +397,27 @@ static void release_denoise_planes(nxhip_ctx* c)
     c->denoised = nullptr;
 }
 
+// Pixels per frame slice of the next pass: the context's pixel set, or the active part of it (adaptive sampling).  c->localCount stays
+// the size of the image and of every read-back.
+static uint32_t pass_pixels(const nxhip_ctx* c) { return c->adaptive ? c->activeCount : c->localCount; }
+
+// The pixel set as the kernels see it (DeviceState): the base set always, and the set the passes render — the same while adaptive
+// sampling is off, the active part of it while it is on.  Uploaded to every slot before the next pass.
+static void publish_pixel_set(nxhip_ctx* c)
+{
+    DeviceState& h = c->h;
+    h.baseCount = c->localCount;
+    h.basePixelMap = c->pixelMap.as<uint32_t>();
+    h.localCount = pass_pixels(c);
+    h.pixelMap = c->adaptive ? c->adPixelMap.as<uint32_t>() : c->pixelMap.as<uint32_t>();
+    h.activeIndex = c->adaptive ? c->adActiveIndex.as<uint32_t>() : nullptr;
+    h.adCount = c->adaptive ? c->adCount.as<uint32_t>() : nullptr;
+    h.adStats = c->adaptive ? c->adStats.as<float2>() : nullptr;
+    h.framesPerPass = c->framesPerPass;
+    h.pathCount = h.localCount * c->framesPerPass;
+    c->stateDirty = true;
+}
+
 // Everything sized by the pixel set of this context: queues for localCount * framesPerPass paths and a zeroed image.
 static int alloc_paths(nxhip_ctx* c, uint32_t localCount)
 {
@@ -417,10 +446,9 @@ static int alloc_paths(nxhip_ctx* c, uint32_t localCount)
     c->localCount = localCount;
     c->pixelSetGeneration++;
     c->pathCount = localCount * c->framesPerPass;
+    c->activeCount = localCount;  // (adaptive sampling: the caller starts the statistics over once the set's map is in place, pixel_set_changed)
     DeviceState& h = c->h;
-    h.localCount = localCount;
-    h.framesPerPass = c->framesPerPass;
-    h.pathCount = c->pathCount;
+    publish_pixel_set(c);
     h.accumulation = c->accumulation.as<float4>();
     h.rgba8 = c->rgba8.as<uint32_t>();
     c->stateDirty = true;
@@ -434,6 +462,94 @@ static int set_frame_number_device(nxhip_ctx* c, uint32_t f)
 {
     NX_SYNC_ALL(c);
     c->frameNumber = f;
+    return NXHIP_OK;
+}
+
+// ---- adaptive sampling (nx_adaptive.hip): the host side of the statistics and of the active set ------------------------------
+
+static AdaptiveLaunch adaptive_launch(const nxhip_ctx* c)
+{
+    AdaptiveLaunch L{};
+    L.count = c->adCount.as<uint32_t>();
+    L.stats = c->adStats.as<float2>();
+    L.blockFlag = c->adBlockFlag.as<uint32_t>();
+    L.blockMax = c->adBlockMax.as<float>();
+    L.blockOffset = c->adBlockOffset.as<uint32_t>();
+    L.totals = c->adTotals.as<uint32_t>();
+    L.basePixelMap = c->pixelMap.as<uint32_t>();
+    L.activeIndex = c->adActiveIndex.as<uint32_t>();
+    L.pixelMap = c->adPixelMap.as<uint32_t>();
+    L.baseCount = c->localCount;
+    L.blocks = c->adBlocks;
+    L.minSamples = c->adParams.minSamples;
+    L.threshold = c->adParams.threshold;
+    L.lumFloor = c->adParams.lumFloor;
+    return L;
+}
+
+// Flags -> prefix -> (with `fill`) the active set's two arrays, on the context's stream; the totals travel to pinned memory behind them.
+static int adaptive_compact(nxhip_ctx* c, bool decide, bool fill)
+{
+    AdaptiveLaunch L = adaptive_launch(c);
+    void* args[1] = {(void*)&L};
+    const dim3 perBlock((unsigned)((size_t)c->adBlocks * 64u + 255u) / 256u), one(1);
+    if (c->adBlocks != 0u) {
+        if (decide) NX_HIP(hipLaunchKernel(adaptive_decide_kernel_ptr(), perBlock, dim3(256), args, 0, c->stream));
+        NX_HIP(hipLaunchKernel(adaptive_scan_kernel_ptr(), one, dim3(1024), args, 0, c->stream));
+        if (fill) NX_HIP(hipLaunchKernel(adaptive_fill_kernel_ptr(), perBlock, dim3(256), args, 0, c->stream));
+    }
+    NX_HIP(hipMemcpyAsync(c->adHostTotals, c->adTotals.p, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    NX_HIP(hipStreamSynchronize(c->stream));
+    return NXHIP_OK;
+}
+
+static void adaptive_release(nxhip_ctx* c)
+{
+    for (DevBuf* b : {&c->adCount, &c->adStats, &c->adActiveIndex, &c->adPixelMap, &c->adBlockFlag, &c->adBlockMax, &c->adBlockOffset, &c->adTotals}) b->release();
+    c->adBlocks = 0;
+}
+
+// The statistics start over for the context's current base set: all counts 0, every block active, the active set = the base set.
+// (Re)allocates the buffers when the base set's size has changed.  Nothing may be in flight that uses them: synchronises first.
+static int adaptive_restart(nxhip_ctx* c)
+{
+    NX_SYNC_ALL(c);
+    const uint32_t n = c->localCount, blocks = (n + 63u) / 64u;
+    if (!c->adHostTotals) NX_HIP(hipHostMalloc((void**)&c->adHostTotals, 2 * sizeof(uint32_t), hipHostMallocDefault));
+    if (!c->adCount.p || c->adCount.bytes != std::max<size_t>((size_t)n * 4, 16) || c->adBlocks != blocks) {
+        DevBuf count, stats, index, map, flag, bmax, offset, totals;  // all or nothing
+        if (!count.alloc((size_t)n * 4) || !stats.alloc((size_t)n * 8) || !index.alloc((size_t)n * 4) || !map.alloc((size_t)n * 4) ||
+            !flag.alloc((size_t)blocks * 4) || !bmax.alloc((size_t)blocks * 4) || !offset.alloc((size_t)blocks * 4) || !totals.alloc(16)) return NXHIP_ERR_HIP;
+        c->adCount = std::move(count);
+        c->adStats = std::move(stats);
+        c->adActiveIndex = std::move(index);
+        c->adPixelMap = std::move(map);
+        c->adBlockFlag = std::move(flag);
+        c->adBlockMax = std::move(bmax);
+        c->adBlockOffset = std::move(offset);
+        c->adTotals = std::move(totals);
+        c->adBlocks = blocks;
+    }
+    NX_HIP(hipMemsetAsync(c->adCount.p, 0, (size_t)n * 4, c->stream));
+    NX_HIP(hipMemsetAsync(c->adStats.p, 0, (size_t)n * 8, c->stream));
+    NX_HIP(hipMemsetAsync(c->adBlockMax.p, 0, (size_t)blocks * 4, c->stream));
+    NX_HIP(hipMemsetAsync(c->adTotals.p, 0, 16, c->stream));
+    if (blocks) NX_HIP(hipMemsetD32Async((hipDeviceptr_t)c->adBlockFlag.p, 1, blocks, c->stream));
+    const int rc = adaptive_compact(c, false, true);
+    if (rc != NXHIP_OK) return rc;
+    c->unsettledPixels = c->adHostTotals[0];
+    c->unsettledBlocks = c->adHostTotals[1];
+    c->activeCount = n;
+    publish_pixel_set(c);
+    return NXHIP_OK;
+}
+
+// The context's base pixel set (count or map) has just changed.
+static int pixel_set_changed(nxhip_ctx* c)
+{
+    c->activeCount = c->localCount;
+    if (c->adaptive) return adaptive_restart(c);
+    publish_pixel_set(c);
     return NXHIP_OK;
 }
 
@@ -622,6 +738,7 @@ void nxhip_destroy(nxhip_ctx* c)
     if (c->stream2) (void)hipStreamDestroy(c->stream2);
     if (c->ownsStream && c->stream) (void)hipStreamDestroy(c->stream);
     if (c->hostStaging) (void)hipHostFree(c->hostStaging);
+    if (c->adHostTotals) (void)hipHostFree(c->adHostTotals);
     for (hipEvent_t e : c->stagingDone)
         if (e) (void)hipEventDestroy(e);
     delete c;
@@ -716,9 +833,9 @@ int nxhip_resize(nxhip_ctx* c, uint32_t width, uint32_t height)
     c->h.camera.resolution[0] = width;
     c->h.camera.resolution[1] = height;
     c->pixelMap.release();
-    c->h.pixelMap = nullptr;
     c->coversFrame = true;
-    c->stateDirty = true;
+    const int rcSet = pixel_set_changed(c);
+    if (rcSet != NXHIP_OK) return rcSet;
     const int rcFrame = set_frame_number_device(c, 0);
     if (rcFrame != NXHIP_OK) return rcFrame;
     // (the ORDER of the full frame survives a resize; a caller's own pixel map does not: it was made for the old size)
@@ -1608,6 +1725,8 @@ int nxhip_set_modes(nxhip_ctx* c, int rngMode, int compactMode, int conductorMod
     NX_CHECK_CTX(c);
     if (rngMode < 0 || rngMode > 1 || compactMode < 0 || compactMode > 1 || conductorMode < 0 || conductorMode > 1)
         return fail_invalid("nxhip_set_modes: unknown mode");
+    if (c->adaptive && rngMode != NX_RNG_PIXEL_KEYED)
+        return fail_invalid("nxhip_set_modes: adaptive sampling is on and needs NX_RNG_PIXEL_KEYED (nxhip_set_adaptive(ctx, NULL) first)");
     if (rngMode == c->h.rngMode && compactMode == c->h.compactMode && conductorMode == c->h.conductorMode) return NXHIP_OK;
     if (compactMode != c->h.compactMode || conductorMode != c->h.conductorMode) invalidate_graph(c);
     c->h.rngMode = rngMode;
@@ -1629,9 +1748,9 @@ int nxhip_set_pixel_map(nxhip_ctx* c, const uint32_t* pixelMap, uint32_t localCo
         const int rc = alloc_paths(c, full);
         if (rc != NXHIP_OK) return rc;
         c->pixelMap.release();
-        c->h.pixelMap = nullptr;
         c->coversFrame = true;
-        c->stateDirty = true;
+        const int rcSet = pixel_set_changed(c);
+        if (rcSet != NXHIP_OK) return rcSet;
         return set_frame_number_device(c, 0);
     }
     if (localCount == 0 || localCount > full) return fail_invalid("nxhip_set_pixel_map: localCount out of range");
@@ -1643,7 +1762,6 @@ int nxhip_set_pixel_map(nxhip_ctx* c, const uint32_t* pixelMap, uint32_t localCo
     const int rc = alloc_paths(c, localCount);
     if (rc != NXHIP_OK) return rc;
     c->pixelMap = std::move(freshMap);
-    c->h.pixelMap = c->pixelMap.as<uint32_t>();
     // every pixel of the frame exactly once?  (what nxhip_denoise needs: it filters in image space)
     c->coversFrame = localCount == full;
     if (c->coversFrame) {
@@ -1653,7 +1771,8 @@ int nxhip_set_pixel_map(nxhip_ctx* c, const uint32_t* pixelMap, uint32_t localCo
             seen[pixelMap[i]] = true;
         }
     }
-    c->stateDirty = true;
+    const int rcSet = pixel_set_changed(c);
+    if (rcSet != NXHIP_OK) return rcSet;
     return set_frame_number_device(c, 0);
 }
 
@@ -1684,7 +1803,9 @@ int nxhip_reset_frame_number(nxhip_ctx* c)
 {
     NX_CHECK_CTX(c);
     NX_HIP(hipSetDevice(c->device));
-    return set_frame_number_device(c, 0);
+    const int rc = set_frame_number_device(c, 0);
+    if (rc != NXHIP_OK || !c->adaptive) return rc;
+    return adaptive_restart(c);  // (a new image: all counts 0, every block active)
 }
 
 int nxhip_set_frame_number(nxhip_ctx* c, uint32_t f)
@@ -1774,7 +1895,9 @@ int launch_begin_frame(nxhip_ctx* c, PassSlot* q, uint32_t frames, uint32_t fram
 // "Small" = up to 4 frames' worth of paths at 1080p.
 // The size of a pass in 1080p frames: what the small-pass rules below were measured in.  A rank of a tile split renders a
 // fraction of the image, so its 20-frame pass is a small one (8 ranks: 2.5 frames' worth of paths).
-double pass_size_in_frames(const nxhip_ctx* c) { return (double)c->localCount * (double)c->framesPerPass / (1920.0 * 1080.0); }
+// (adaptive sampling: the pixels of the active set, and the frames nxhip_render_adaptive packs into the pass being issued)
+uint32_t pass_frames(const nxhip_ctx* c) { return c->passFrames ? c->passFrames : c->framesPerPass; }
+double pass_size_in_frames(const nxhip_ctx* c) { return (double)pass_pixels(c) * (double)pass_frames(c) / (1920.0 * 1080.0); }
 
 // Passes in flight right now: kernel timing and the counting variant measure one pass at a time, and a caller-bound
 // radiance buffer exists once.
@@ -2144,12 +2267,19 @@ static int ensure_slot_events(PassSlot* q)
 
 extern "C" {
 
-int nxhip_render_frame(nxhip_ctx* c)
+// One pass of `frames` frames (0: the context's frames per pass) through the pixels of the pass set.
+static int render_pass(nxhip_ctx* c, uint32_t framesArg)
 try {
     NX_CHECK_CTX(c);
     NX_HIP(hipSetDevice(c->device));
     int rc = check_scene_ready(c);
     if (rc != NXHIP_OK) return rc;
+    if (c->adaptive && pass_pixels(c) == 0u) return NXHIP_OK;  // no active block: nothing is launched, the frame number stays
+    struct PassFrames {  // what pass_size_in_frames (grids, tail rule, graph shape) sees while this pass is issued
+        nxhip_ctx* c;
+        ~PassFrames() { c->passFrames = 0; }
+    } passFramesGuard{c};
+    c->passFrames = framesArg;
     if (c->shadeInstDirty) {
         rc = refresh_shade_inst(c);
         if (rc != NXHIP_OK) return rc;
@@ -2185,7 +2315,7 @@ try {
         rc = upload_state(c);
         if (rc != NXHIP_OK) return rc;
     }
-    const uint32_t frames = c->framesPerPass, frameLast = c->frameNumber + frames;
+    const uint32_t frames = pass_frames(c), frameLast = c->frameNumber + frames;
     if (R > 1) {
         rc = ensure_slot_events(q);
         if (rc != NXHIP_OK) return rc;
@@ -2238,6 +2368,7 @@ try {
     if (R > 1) NX_HIP(hipEventRecord(q->done, q->stream));
     q->frames = frames;
     q->frameLast = frameLast;
+    q->passPixels = pass_pixels(c);
     q->awaitingAccumulate = true;
     c->pending.push_back(q);
     c->lastRendered = q;
@@ -2248,10 +2379,27 @@ try {
     return NXHIP_ERR_INVALID;
 }
 
+int nxhip_render_frame(nxhip_ctx* c) { return render_pass(c, 0u); }
+
 // AccumulateKernel on the context's (main) stream, reading `stateSlot`'s device state (its radiance, pass size, frame number).
 static int launch_accumulate(nxhip_ctx* c, PassSlot* stateSlot, const float4* src, uint32_t count, uint32_t slices, uint32_t sliceStride, uint32_t firstFrame,
                              const uint32_t* dstMap)
 {
+    if (c->adaptive && !src) {
+        // adaptive sampling: ONE kernel reads the pass's radiance once — running mean by the pixel's count, luminance statistics, tonemap —
+        // through the active set of the slot's device state; the feature buffers follow the same way (nx_adaptive.hip)
+        Launch a = make_launch(adaptive_accumulate_kernel_ptr(), c->wideBlocks, kWideBlockThreads, NXHIP_K_ACCUMULATE, stateSlot->dState.as<DeviceState>());
+        const size_t beforeA = c->timerPool.size();
+        int rcA = launch_now(c, a);
+        if (rcA == NXHIP_OK && c->timerPool.size() > beforeA) c->timerClass.push_back(a.klass);
+        if (rcA == NXHIP_OK && c->aov && stateSlot->aovAlbedo.p && stateSlot->aovNormalDepth.p) {
+            Launch f = make_launch(adaptive_aov_fold_kernel_ptr(), c->wideBlocks, kWideBlockThreads, NXHIP_K_ACCUMULATE, stateSlot->dState.as<DeviceState>());
+            const size_t beforeF = c->timerPool.size();
+            rcA = launch_now(c, f);
+            if (rcA == NXHIP_OK && c->timerPool.size() > beforeF) c->timerClass.push_back(f.klass);
+        }
+        return rcA;
+    }
     Launch l = make_launch(accumulate_kernel_ptr(), c->wideBlocks, kWideBlockThreads, NXHIP_K_ACCUMULATE, stateSlot->dState.as<DeviceState>());
     l.nargs = 7;
     l.src = src;
@@ -2279,6 +2427,7 @@ int nxhip_accumulate(nxhip_ctx* c)
     NX_HIP(hipSetDevice(c->device));
     int rc = upload_state(c);
     if (rc != NXHIP_OK) return rc;
+    if (c->pending.empty() && c->adaptive) return NXHIP_OK;  // (folding the same radiance again would count its samples twice)
     if (c->pending.empty()) {
         // nothing rendered since the last accumulate: the reference's AccumulateKernel would fold the same radiance in again
         PassSlot* q = c->lastRendered ? c->lastRendered : static_cast<PassSlot*>(c);
@@ -2542,6 +2691,7 @@ int nxhip_accumulate_external(nxhip_ctx* c, const void* src, uint32_t count, uin
     NX_CHECK_CTX(c);
     if (!src || count == 0 || count > c->width * c->height || firstFrame == 0 || slices == 0 || sliceStride < count)
         return fail_invalid("nxhip_accumulate_external: bad arguments");
+    if (c->adaptive) return fail_invalid("nxhip_accumulate_external: adaptive sampling is on (external radiance carries no sample counts)");
     NX_HIP(hipSetDevice(c->device));
     const int rc = upload_state(c);
     if (rc != NXHIP_OK) return rc;
@@ -2605,7 +2755,8 @@ int nxhip_read_radiance(nxhip_ctx* c, float* dst)
     // the pass rendered last (with several passes in flight: the newest one's slot)
     const PassSlot* q = c->lastRendered ? c->lastRendered : static_cast<PassSlot*>(c);
     const void* src = q == static_cast<PassSlot*>(c) ? (const void*)c->h.radiance : (const void*)q->radiance.p;
-    return read_float4_as_float3(c, src, c->pathCount, dst);
+    // (adaptive sampling: the active paths of that pass, its active count x its frames)
+    return read_float4_as_float3(c, src, c->adaptive && c->lastRendered ? q->passPixels * q->frames : c->pathCount, dst);
 }
 
 int nxhip_read_accumulation(nxhip_ctx* c, float* dst)
@@ -2618,6 +2769,7 @@ int nxhip_write_accumulation(nxhip_ctx* c, const float* src, uint32_t frameNumbe
 try {
     NX_CHECK_CTX(c);
     if (!src) return fail_invalid("nxhip_write_accumulation: null source");
+    if (c->adaptive) return fail_invalid("nxhip_write_accumulation: adaptive sampling is on (the sample counts have no checkpoint form)");
     NX_HIP(hipSetDevice(c->device));
     NX_SYNC_ALL(c);
     std::vector<float4> tmp(c->localCount);
@@ -2686,7 +2838,7 @@ int nxhip_read_aov_frame(nxhip_ctx* c, float* albedo4, float* normalDepth4)
     int rc = aov_required(c, "nxhip_read_aov_frame");
     if (rc != NXHIP_OK) return rc;
     const PassSlot* q = c->lastRendered ? c->lastRendered : static_cast<PassSlot*>(c);
-    const size_t bytes = (size_t)c->pathCount * 16;
+    const size_t bytes = (size_t)(c->adaptive && c->lastRendered ? q->passPixels * q->frames : c->pathCount) * 16;
     if (!q->aovAlbedo.p || !q->aovNormalDepth.p || q->aovAlbedo.bytes < bytes || q->aovNormalDepth.bytes < bytes)
         return fail_invalid("nxhip_read_aov_frame: no pass has been rendered with the feature buffers on (or its queues were released)");
     NX_HIP(hipSetDevice(c->device));
@@ -2701,10 +2853,179 @@ int nxhip_write_aov(nxhip_ctx* c, const float* albedo4, const float* normalDepth
     NX_CHECK_CTX(c);
     int rc = aov_required(c, "nxhip_write_aov");
     if (rc != NXHIP_OK) return rc;
+    if (c->adaptive) return fail_invalid("nxhip_write_aov: adaptive sampling is on (the sample counts have no checkpoint form)");
     NX_HIP(hipSetDevice(c->device));
     NX_SYNC_ALL(c);
     if (albedo4) NX_HIP(hipMemcpy(c->aovAccumAlbedo.p, albedo4, (size_t)c->localCount * 16, hipMemcpyHostToDevice));
     if (normalDepth4) NX_HIP(hipMemcpy(c->aovAccumNormalDepth.p, normalDepth4, (size_t)c->localCount * 16, hipMemcpyHostToDevice));
+    return NXHIP_OK;
+}
+
+// ---- adaptive sampling (nx_adaptive.hip) ------------------------------------------------------------
+
+int nxhip_adaptive_defaults(nx_adaptive_params* p)
+{
+    if (!p) return fail_invalid("nxhip_adaptive_defaults: null destination");
+    // (starting values, not tuned)
+    p->threshold = 0.05f;
+    p->lumFloor = 0.01f;
+    p->minSamples = 16u;
+    p->cull = 1u;
+    return NXHIP_OK;
+}
+
+static int adaptive_required(nxhip_ctx* c, const char* who)
+{
+    if (!c->adaptive) return fail_invalid(std::string(who) + ": adaptive sampling is off (nxhip_set_adaptive)");
+    return NXHIP_OK;
+}
+
+int nxhip_set_adaptive(nxhip_ctx* c, const nx_adaptive_params* p)
+{
+    NX_CHECK_CTX(c);
+    if (!p) {
+        if (!c->adaptive) return NXHIP_OK;
+        NX_HIP(hipSetDevice(c->device));
+        const int rcFold = nxhip_accumulate(c);  // (a pending pass was rendered through the active set: it is folded the way it was rendered)
+        if (rcFold != NXHIP_OK) return rcFold;
+        NX_SYNC_ALL(c);
+        c->adaptive = false;
+        adaptive_release(c);
+        c->activeCount = c->localCount;
+        publish_pixel_set(c);  // the base set again
+        return NXHIP_OK;
+    }
+    if (!(p->threshold >= 0.0f) || !std::isfinite(p->threshold) || !(p->lumFloor > 0.0f) || !std::isfinite(p->lumFloor))
+        return fail_invalid("nxhip_set_adaptive: threshold must be a finite number >= 0 and lumFloor a finite number > 0");
+    if (c->h.rngMode != NX_RNG_PIXEL_KEYED)
+        return fail_invalid("nxhip_set_adaptive: needs NX_RNG_PIXEL_KEYED (a path's radiance must depend on its pixel and frame only, not on a queue slot)");
+    if (c->mgpuComm) return fail_invalid("nxhip_set_adaptive: the context is part of a multi-GPU tile split (nxhip_mgpu_*)");
+    if (c->adaptive) {  // new parameters for the statistics gathered so far
+        c->adParams = *p;
+        return NXHIP_OK;
+    }
+    if (c->frameNumber != 0u) return fail_invalid("nxhip_set_adaptive: frames have been accumulated without sample counts - reset the frame number first");
+    NX_HIP(hipSetDevice(c->device));
+    c->adaptive = true;
+    c->adParams = *p;
+    const int rc = adaptive_restart(c);
+    if (rc != NXHIP_OK) {
+        c->adaptive = false;
+        adaptive_release(c);
+        publish_pixel_set(c);
+    }
+    return rc;
+}
+
+int nxhip_adaptive_update(nxhip_ctx* c, uint32_t* activePixels, uint32_t* activeBlocks)
+{
+    NX_CHECK_CTX(c);
+    int rc = adaptive_required(c, "nxhip_adaptive_update");
+    if (rc != NXHIP_OK) return rc;
+    NX_HIP(hipSetDevice(c->device));
+    rc = nxhip_accumulate(c);  // (nothing pending: nothing)
+    if (rc != NXHIP_OK) return rc;
+    // behind the accumulates, on the context's stream: decide, compact, and — when blocks are culled — the new active set in place
+    // (entry k of the new set comes from a base index at or behind the one entry k held, and the kernels read the base arrays only)
+    const bool cull = c->adParams.cull != 0u;
+    rc = adaptive_compact(c, true, cull);
+    if (rc != NXHIP_OK) return rc;
+    NX_SYNC_ALL(c);
+    c->unsettledPixels = c->adHostTotals[0];
+    c->unsettledBlocks = c->adHostTotals[1];
+    if (cull) {
+        c->activeCount = c->unsettledPixels;
+        publish_pixel_set(c);  // to every slot's device state before the next pass (upload_state)
+    }
+    if (activePixels) *activePixels = c->unsettledPixels;
+    if (activeBlocks) *activeBlocks = c->unsettledBlocks;
+    return NXHIP_OK;
+}
+
+int nxhip_render_adaptive(nxhip_ctx* c, uint32_t maxFrames, uint32_t interval, uint32_t* framesRendered, uint32_t* activePixels)
+{
+    NX_CHECK_CTX(c);
+    if (framesRendered) *framesRendered = 0u;
+    int rc = adaptive_required(c, "nxhip_render_adaptive");
+    if (rc != NXHIP_OK) return rc;
+    if (interval == 0u) return fail_invalid("nxhip_render_adaptive: interval must be at least 1");
+    uint32_t issued = 0u;
+    while (rc == NXHIP_OK && c->unsettledBlocks != 0u && issued < maxFrames) {
+        const uint32_t n = std::min(interval, maxFrames - issued), pixels = std::max(1u, pass_pixels(c));
+        // frames per pass of this interval: what the queues already hold (and a caller's radiance buffer, if one is bound)
+        size_t room = c->queueCapacity;
+        if (c->radianceBoundCapacity != 0) room = std::min(room, c->radianceBoundCapacity);
+        const uint32_t per = (uint32_t)std::max<size_t>(1, std::min<size_t>(std::min<size_t>(n, 1024), room / pixels));
+        for (uint32_t done = 0; done < n && rc == NXHIP_OK; done += per) {
+            rc = render_pass(c, std::min(per, n - done));
+            if (rc == NXHIP_OK) rc = nxhip_accumulate(c);
+        }
+        if (rc == NXHIP_OK) rc = nxhip_adaptive_update(c, nullptr, nullptr);
+        if (rc == NXHIP_OK) issued += n;
+    }
+    if (framesRendered) *framesRendered = issued;
+    if (activePixels) *activePixels = c->unsettledPixels;
+    return rc;
+}
+
+int nxhip_read_sample_counts(nxhip_ctx* c, uint32_t* counts)
+{
+    NX_CHECK_CTX(c);
+    const int rc = adaptive_required(c, "nxhip_read_sample_counts");
+    if (rc != NXHIP_OK) return rc;
+    if (!counts) return fail_invalid("null destination");
+    NX_HIP(hipSetDevice(c->device));
+    NX_SYNC_ALL(c);
+    NX_HIP(hipMemcpy(counts, c->adCount.p, (size_t)c->localCount * 4, hipMemcpyDeviceToHost));
+    return NXHIP_OK;
+}
+
+int nxhip_read_noise_stats(nxhip_ctx* c, float* meanM2)
+{
+    NX_CHECK_CTX(c);
+    const int rc = adaptive_required(c, "nxhip_read_noise_stats");
+    if (rc != NXHIP_OK) return rc;
+    if (!meanM2) return fail_invalid("null destination");
+    NX_HIP(hipSetDevice(c->device));
+    NX_SYNC_ALL(c);
+    NX_HIP(hipMemcpy(meanM2, c->adStats.p, (size_t)c->localCount * 8, hipMemcpyDeviceToHost));
+    return NXHIP_OK;
+}
+
+int nxhip_read_block_noise(nxhip_ctx* c, float* blockMax, uint8_t* active, uint32_t capacity, uint32_t* blocks)
+try {
+    NX_CHECK_CTX(c);
+    const int rc = adaptive_required(c, "nxhip_read_block_noise");
+    if (rc != NXHIP_OK) return rc;
+    if (blocks) *blocks = c->adBlocks;
+    if (!blockMax && !active) return NXHIP_OK;
+    if (capacity < c->adBlocks) return fail_invalid("nxhip_read_block_noise: capacity below the number of blocks");
+    NX_HIP(hipSetDevice(c->device));
+    NX_SYNC_ALL(c);
+    if (blockMax) NX_HIP(hipMemcpy(blockMax, c->adBlockMax.p, (size_t)c->adBlocks * 4, hipMemcpyDeviceToHost));
+    if (active) {
+        std::vector<uint32_t> flags(c->adBlocks);
+        NX_HIP(hipMemcpy(flags.data(), c->adBlockFlag.p, (size_t)c->adBlocks * 4, hipMemcpyDeviceToHost));
+        for (uint32_t b = 0; b < c->adBlocks; b++) active[b] = flags[b] != 0u ? 1 : 0;
+    }
+    return NXHIP_OK;
+} catch (const std::exception& e) {
+    set_error(std::string("nxhip_read_block_noise: ") + e.what());
+    return NXHIP_ERR_INVALID;
+}
+
+int nxhip_read_active_map(nxhip_ctx* c, uint32_t* baseLocalIndex, uint32_t capacity, uint32_t* count)
+{
+    NX_CHECK_CTX(c);
+    const int rc = adaptive_required(c, "nxhip_read_active_map");
+    if (rc != NXHIP_OK) return rc;
+    const uint32_t n = pass_pixels(c);
+    if (count) *count = n;
+    if (!baseLocalIndex) return NXHIP_OK;
+    if (capacity < n) return fail_invalid("nxhip_read_active_map: capacity below the number of active paths");
+    NX_HIP(hipSetDevice(c->device));
+    NX_SYNC_ALL(c);
+    if (n) NX_HIP(hipMemcpy(baseLocalIndex, c->adActiveIndex.p, (size_t)n * 4, hipMemcpyDeviceToHost));
     return NXHIP_OK;
 }
 

@@ -189,6 +189,7 @@ try {
 int nxhip_mgpu_init(nxhip_ctx* c, int worldSize, int rank, const void* id128, uint32_t tileRows)
 {
     if (!c) return fail(NXHIP_ERR_INVALID, "null context");
+    if (c->adaptive) return fail(NXHIP_ERR_INVALID, "nxhip_mgpu_init: adaptive sampling is on (nxhip_set_adaptive(ctx, NULL) first)");
     if (!id128) return fail(NXHIP_ERR_INVALID, "nxhip_mgpu_init: null unique id");
     if (c->mgpuComm) return fail(NXHIP_ERR_INVALID, "nxhip_mgpu_init: already initialised (nxhip_mgpu_shutdown first)");
     Rccl& r = rccl();
@@ -210,6 +211,7 @@ int nxhip_mgpu_init(nxhip_ctx* c, int worldSize, int rank, const void* id128, ui
 int nxhip_mgpu_attach(nxhip_ctx* c, void* ncclComm, int worldSize, int rank, uint32_t tileRows)
 {
     if (!c) return fail(NXHIP_ERR_INVALID, "null context");
+    if (c->adaptive) return fail(NXHIP_ERR_INVALID, "nxhip_mgpu_attach: adaptive sampling is on (nxhip_set_adaptive(ctx, NULL) first)");
     if (!ncclComm) return fail(NXHIP_ERR_INVALID, "nxhip_mgpu_attach: null communicator");
     if (c->mgpuComm) return fail(NXHIP_ERR_INVALID, "nxhip_mgpu_attach: already initialised (nxhip_mgpu_shutdown first)");
     Rccl& r = rccl();

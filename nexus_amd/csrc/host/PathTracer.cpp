@@ -246,6 +246,37 @@ void PathTracer::ReadFeatureBuffers(std::vector<float>& albedo4, std::vector<flo
         }
 }
 
+void PathTracer::SetAdaptive(const nx_adaptive_params* params)
+{
+    if (params && m_TileSplit) throw std::runtime_error("PathTracer::SetAdaptive: not on a tile split");
+    if (params) ResetFrameNumber();  // (the library refuses sample counts that would cover fewer frames than the colour)
+    Check(nxhip_set_adaptive(m_Ctx, params), "nxhip_set_adaptive");
+}
+
+uint32_t PathTracer::RenderAdaptive(const Scene&, uint32_t maxFrames, uint32_t interval, uint32_t* activePixels)
+{
+    uint32_t frames = 0;
+    Check(nxhip_render_adaptive(m_Ctx, maxFrames, interval, &frames, activePixels), "nxhip_render_adaptive");
+    m_FrameNumber += frames;
+    return frames;
+}
+
+void PathTracer::ReadSampleCounts(std::vector<uint32_t>& counts)
+{
+    const size_t n = static_cast<size_t>(m_ViewportWidth) * m_ViewportHeight;
+    std::vector<uint32_t> c(n);
+    Check(nxhip_read_sample_counts(m_Ctx, c.data()), "nxhip_read_sample_counts");
+    if (m_PixelOrder == NXHIP_ORDER_ROWS) {
+        counts.swap(c);
+        return;
+    }
+    std::vector<uint32_t> map(n);  // path order -> rows, as ReadFeatureBuffers
+    uint32_t count = 0;
+    Check(nxhip_tile_pixel_map(m_ViewportWidth, m_ViewportHeight, 1, 0, 1, 1, map.data(), &count), "nxhip_tile_pixel_map");
+    counts.assign(n, 0u);
+    for (size_t k = 0; k < count; k++) counts[map[k]] = c[k];
+}
+
 void PathTracer::Render(const Scene&)
 {
     m_FrameNumber += m_FramesPerPass;

@@ -106,6 +106,39 @@ bool Renderer::SaveFeatureEXR(const std::string& filepath)
            WriteEXR(stem + ".depth.exr", depth.data(), m_ViewportWidth, m_ViewportHeight, true);
 }
 
+void Renderer::SetAdaptive(const nx_adaptive_params* params)
+{
+    m_PathTracer.SetAdaptive(params);
+    if (params) Reset();
+}
+
+uint32_t Renderer::RenderAdaptive(Scene& scene, uint32_t maxFrames, uint32_t interval)
+{
+    if (scene.IsInvalid()) {
+        scene.Update();
+        m_PathTracer.ResetFrameNumber();
+    }
+    if (scene.IsEmpty()) {
+        m_PathTracer.ResetFrameNumber();
+        return 0;
+    }
+    m_PathTracer.UpdateDeviceScene(*m_Scene);
+    return m_PathTracer.RenderAdaptive(scene, maxFrames, interval);
+}
+
+bool Renderer::SaveSampleCountEXR(const std::string& filepath)
+{
+    std::vector<uint32_t> counts;
+    try {
+        m_PathTracer.ReadSampleCounts(counts);
+    } catch (const std::exception&) {
+        return false;
+    }
+    std::vector<float> rgb(counts.size() * 3);
+    for (size_t i = 0; i < counts.size(); i++) rgb[3 * i] = rgb[3 * i + 1] = rgb[3 * i + 2] = static_cast<float>(counts[i]);
+    return WriteEXR(filepath, rgb.data(), m_ViewportWidth, m_ViewportHeight, true);
+}
+
 bool Renderer::SaveAccumulationEXR(const std::string& filepath)
 {
     std::vector<float> rgb(static_cast<size_t>(m_ViewportWidth) * m_ViewportHeight * 3);

@@ -98,6 +98,8 @@ assert BSDF_QUERY_DT.itemsize == 32 and BSDF_RESULT_DT.itemsize == 48
 # nx_denoise_params (nxhip_denoise): iterations of the a-trous filter and the widths of its edge-stopping terms
 DENOISE_DT = np.dtype([("iterations", "<u4"), ("sigmaColor", "<f4"), ("sigmaNormal", "<f4"), ("sigmaAlbedo", "<f4"), ("sigmaDepth", "<f4")])
 assert DENOISE_DT.itemsize == 20
+ADAPTIVE_DT = np.dtype([("threshold", "<f4"), ("lumFloor", "<f4"), ("minSamples", "<u4"), ("cull", "<u4")])
+assert ADAPTIVE_DT.itemsize == 16
 
 MAT_DIFFUSE, MAT_DIELECTRIC, MAT_PLASTIC, MAT_CONDUCTOR = 0, 1, 2, 3
 LIGHT_POINT, LIGHT_AREA, LIGHT_MESH = 0, 1, 2
