@@ -114,6 +114,9 @@ typedef struct orc_scene {
  * x width x height / (2 pi^2). */
 void orc_env_distribution(const nx_texture_desc *hdr, float *marginalCdf, float *rowCdf, float *density);
 
+/* SampleBackground (PathTracer.cu:65-83) for n directions (3 floats each) -> n RGB triples */
+void orc_sample_background(const orc_scene *s, const float *directions, uint32_t n, float *rgb);
+
 /* Visit counters for the roofline's algorithmic bytes. */
 typedef struct orc_trace_stats {
     uint64_t rays, nodes, tris, instances, maxStack;

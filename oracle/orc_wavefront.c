@@ -122,6 +122,15 @@ static f3 sample_background(const orc_scene *s, f3 d)
     return scale3(ld3(s->settings.backgroundColor), s->settings.backgroundIntensity);
 }
 
+/* sample_background over an array of directions (tests/test_geometry_pins.py: the seam and the poles of the map) */
+void orc_sample_background(const orc_scene *s, const float *directions, uint32_t n, float *rgb)
+{
+    for (uint32_t i = 0; i < n; i++) {
+        const f3 c = sample_background(s, ld3(directions + 3 * (size_t)i));
+        rgb[3 * (size_t)i] = c.x; rgb[3 * (size_t)i + 1] = c.y; rgb[3 * (size_t)i + 2] = c.z;
+    }
+}
+
 /* ---- environment importance sampling (extension; see nexus_oracle.h) -------------------------------------------- */
 
 void orc_env_distribution(const nx_texture_desc *hdr, float *marginalCdf, float *rowCdf, float *density)

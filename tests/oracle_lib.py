@@ -311,6 +311,14 @@ class OracleScene:
         lib().orc_brute_closest(C.byref(self.c), _ptr(rays), len(rays), _ptr(hits))
         return hits
 
+    def sample_background(self, directions):
+        """SampleBackground for an array of directions (n, 3) -> RGB (n, 3)"""
+        d = np.ascontiguousarray(directions, dtype=np.float32).reshape(-1, 3)
+        out = np.zeros((len(d), 3), dtype=np.float32)
+        lib().orc_sample_background.argtypes = [C.POINTER(_Scene), C.c_void_p, C.c_uint32, C.c_void_p]
+        lib().orc_sample_background(C.byref(self.c), _ptr(d), len(d), _ptr(out))
+        return out
+
     def brute_any(self, rays, tmax):
         rays = np.ascontiguousarray(rays, dtype=pod.RAY_DT)
         tmax = np.ascontiguousarray(tmax, dtype=np.float32)
