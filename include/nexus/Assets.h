@@ -89,6 +89,13 @@ public:
     void SetBlasBatchBuilder(BlasBatchBuilder builder) { m_BlasBatchBuilder = std::move(builder); }
     int32_t CreateBVHs(const std::vector<std::vector<Triangle>>& meshes);
     int32_t AddMesh(Mesh&& mesh);
+    // Extension (deforming meshes; the reference builds a new BVH for a changed mesh, Assets/AssetManager.cpp:23-37): the same
+    // triangles of BVH `bvhId`, in the same order, at new positions.  The host tree is refitted (BVH8::Refit); Scene::Update then
+    // re-derives the world bounds of the mesh's instances and brings the TLAS up to date, and PathTracer::UpdateDeviceScene
+    // sends the mesh through nxhip_update_blas — no new BLAS id, no new instances.  Throws on another triangle count.
+    void UpdateMeshTriangles(int32_t bvhId, const std::vector<Triangle>& triangles);
+    // BVH ids changed by UpdateMeshTriangles since Scene::Update last asked (it re-places their instances)
+    std::set<int32_t> TakeDeformedBvhs();
     void AddMaterial();
     int AddMaterial(const Material& material);
     std::vector<Material>& GetMaterials() { return m_Materials; }
@@ -102,15 +109,17 @@ public:
     const std::vector<Texture>& GetDiffuseMaps() const { return m_DiffuseMaps; }
     const std::vector<Texture>& GetEmissiveMaps() const { return m_EmissiveMaps; }
     bool SendDataToDevice();  // clears the invalid-material set; returns whether anything changed
-    bool IsInvalid() const { return !m_InvalidMaterials.empty(); }
+    bool IsInvalid() const { return !m_InvalidMaterials.empty() || !m_DeformedBvhs.empty(); }
 
     // what the device still has to receive (consumed by PathTracer::UpdateDeviceScene)
     bool materialsDirty = true, texturesDirty = true;
     size_t uploadedBvhs = 0;
+    std::set<int32_t> deformedBvhs;  // changed by UpdateMeshTriangles and not yet sent through nxhip_update_blas
 
 private:
     std::vector<Material> m_Materials;
     std::set<uint32_t> m_InvalidMaterials;
+    std::set<int32_t> m_DeformedBvhs;
     std::vector<Texture> m_DiffuseMaps, m_EmissiveMaps;
     std::vector<BVH8> m_Bvhs;
     std::vector<Mesh> m_Meshes;

@@ -21,6 +21,9 @@ using BVH8Node = nx_bvh8_node;
 struct BVH8 {
     BVH8() = default;
     explicit BVH8(const std::vector<Triangle>& tri);
+    // Extension (deforming meshes): the same triangles, in the same order, at new positions — as many as the tree was built
+    // over.  Topology, indices and node count stay; the bounds are recomputed bottom-up with the builder's formulas.
+    void Refit(const std::vector<Triangle>& tri);
 
     std::vector<Triangle> triangles;
     std::vector<uint32_t> triangleIdx;  // triangle (BLAS) or instance (TLAS) ids in leaf order

@@ -131,6 +131,20 @@ int nxhip_read_tlas_index(nxhip_ctx *ctx, uint32_t *instanceIdx, uint32_t capaci
  * bottom-up refit of the TLAS BVH8 with unchanged topology (bit-identical to nexus::collapse::Refit / nxh_tlas_refit).
  * Runs on the context's stream after the frames already issued. */
 int nxhip_set_instance_transforms(nxhip_ctx *ctx, const uint32_t *instanceIds, const float *transforms16, uint32_t count);
+/* Deforming meshes: new vertices for an existing BLAS, refitted on the device.  The reference has
+ * nothing of the kind — a changed mesh there is a new BVH8Builder run (Assets/AssetManager.cpp:23-37), as nxhip_build_blas is
+ * here, with a new id, new instances and a new TLAS.  triCount must equal the BLAS's; triangle i replaces triangle i (the index
+ * hit records report).  Topology, node count, ids and every device pointer stay, so pass graphs and entry-state tables need no
+ * rebuild.  Works on any BLAS id: uploaded, device-built or one of a batch.  On the context's stream, with no read-back of the tree
+ * and no allocation after the first update of that BLAS: the triangles are copied, the intersection stream is rewritten, and the
+ * nodes are refitted bottom-up level by level (bit-identical to nexus::collapse::Refit over the triangles' vertex boxes,
+ * nxh_bvh8_refit).  Ordered behind every pass already issued on any pass slot and before every later one; frame number and
+ * accumulation are left alone.  What embeds the BLAS's root — its instances' world bounds, their traversal records, the TLAS — is
+ * brought up to date once, for all BLASes updated since, by the next render, ray-batch hook or nxhip_read_tlas.
+ * The _device form takes the 96-byte records from device memory (a caller's own skinning kernel), copied device to device in
+ * stream order; it does not wait for the device.  A bad id, NULL or another count: NXHIP_ERR_INVALID, nothing changed. */
+int nxhip_update_blas(nxhip_ctx *ctx, int32_t blasId, const nx_triangle *tris, uint32_t triCount);
+int nxhip_update_blas_device(nxhip_ctx *ctx, int32_t blasId, const void *trisDevice, uint32_t triCount);
 /* Read the device's TLAS nodes / instance table back (tests; either destination may be NULL). */
 int nxhip_read_tlas(nxhip_ctx *ctx, nx_bvh8_node *nodes, uint32_t nodeCapacity, nx_bvh_instance *instances, uint32_t instanceCapacity);
 /* AssetManager device materials — Assets/AssetManager.cpp:57-62,106-116 */

@@ -31,6 +31,12 @@ int nxh_tlas_build(const nx_bvh_instance *instances, uint32_t instanceCount, nxh
  * instances).  The refitted tree bounds the same instances, so closest hits are those of a rebuilt tree; only the order
  * of visits (and which of two equidistant hits wins) may differ.  Returns 0, or 1 on malformed input. */
 int nxh_tlas_refit(nx_bvh8_node *nodes, uint32_t nodeCount, const uint32_t *instanceIdx, const nx_bvh_instance *instances, uint32_t instanceCount);
+/* BLAS refit after a mesh's vertices moved (same triangles in the same order, same topology; BVH8::Refit): recomputes, in
+ * place, every node's frame and its children's quantised boxes bottom-up from the triangles' vertex boxes — pos0, pos1, pos2
+ * grown from the empty box — with the builder's formulas; imask, meta and indices stay.  With unchanged triangles it gives the
+ * builder's bytes.  The byte reference of nxhip_update_blas.  The reference rebuilds instead (Assets/AssetManager.cpp:23-37).
+ * Children need not follow their parent in the array (the device builders' trees).  Returns 0, or 1 on malformed input. */
+int nxh_bvh8_refit(nx_bvh8_node *nodes, uint32_t nodeCount, const uint32_t *triIdx, const nx_triangle *tris, uint32_t triCount);
 uint32_t nxh_bvh8_node_count(const nxh_bvh8 *b);
 uint32_t nxh_bvh8_prim_count(const nxh_bvh8 *b);
 const nx_bvh8_node *nxh_bvh8_nodes(const nxh_bvh8 *b);
@@ -95,6 +101,12 @@ int nxs_scene_set_hdr_map(nxs_scene *s, const uint8_t *rgba8, uint32_t w, uint32
 int nxs_scene_add_mesh(nxs_scene *s, const nx_triangle *tris, uint32_t triCount, int32_t materialId, int32_t *meshId);
 int nxs_scene_create_instance(nxs_scene *s, uint32_t meshId, int32_t materialId, const float pos[3], const float rotDeg[3],
                               const float scale[3], int32_t *instanceId);
+/* Extension (deforming meshes; the reference builds a new BVH instead, Assets/AssetManager.cpp:23-37):
+ * AssetManager::UpdateMeshTriangles — the same triangles of mesh `meshId`, in the same order, at new positions; as many as the mesh
+ * has.  The host tree is refitted; the next nxs_scene_update re-derives the bounds of the mesh's instances and brings the TLAS up
+ * to date by the mode in force, the next nxs_pathtracer_update_device_scene sends the mesh through nxhip_update_blas.  The scene
+ * counts as changed (nxs_renderer_render restarts the accumulation). */
+int nxs_scene_update_mesh(nxs_scene *s, uint32_t meshId, const nx_triangle *tris, uint32_t triCount);
 /* MeshInstance::AssignMaterial + Scene::InvalidateMeshInstance (the viewer's material picker): applied by the next nxs_scene_update. */
 int nxs_scene_assign_material(nxs_scene *s, uint32_t instanceId, int32_t materialId);
 /* MeshInstance::SetTransform + Scene::InvalidateMeshInstance: move an existing instance; applied by the next nxs_scene_update. */

@@ -30,10 +30,10 @@ HIP_SYMBOLS = [
     "nxhip_mgpu_read_accumulation", "nxhip_mgpu_shutdown", "nxhip_fmath_batch", "nxhip_abi_stamp", "nxhip_check_library", "nxhip_build_blas_batch", "nxhip_read_blas_batch", "nxhip_debug_set_scan_epoch", "nxhip_debug_ended_rays_of_pass",
     "nxhip_set_aov", "nxhip_read_aov", "nxhip_read_aov_frame", "nxhip_write_aov", "nxhip_denoise", "nxhip_denoise_defaults", "nxhip_read_denoised", "nxhip_read_denoised_rgba8",
     "nxhip_adaptive_defaults", "nxhip_set_adaptive", "nxhip_adaptive_update", "nxhip_render_adaptive", "nxhip_read_sample_counts", "nxhip_read_noise_stats",
-    "nxhip_read_block_noise", "nxhip_read_active_map",
+    "nxhip_read_block_noise", "nxhip_read_active_map", "nxhip_update_blas", "nxhip_update_blas_device",
 ]
 HOST_SYMBOLS = [
-    "nxh_bvh8_build", "nxh_tlas_build", "nxh_tlas_refit", "nxh_bvh8_node_count", "nxh_bvh8_prim_count", "nxh_bvh8_nodes",
+    "nxh_bvh8_build", "nxh_tlas_build", "nxh_tlas_refit", "nxh_bvh8_refit", "nxh_bvh8_node_count", "nxh_bvh8_prim_count", "nxh_bvh8_nodes",
     "nxh_bvh8_prim_indices", "nxh_bvh8_free", "nxh_bvh2_build", "nxh_mat4_from_trs", "nxh_mat4_invert",
     "nxh_instance_init", "nxh_camera_init", "nxh_loaded_texture_count", "nxh_loaded_texture_info", "nxh_loaded_texture_pixels",
     "nxh_loaded_material_textures", "nxh_loaded_warning_count", "nxh_loaded_warning", "nxh_decode_png", "nxh_write_png", "nxh_write_exr",
@@ -42,7 +42,7 @@ HOST_SYMBOLS = [
     "nxs_renderer_set_modes", "nxs_renderer_set_denoise", "nxs_renderer_save_denoised_exr", "nxs_renderer_save_feature_exr", "nxs_pathtracer_set_feature_buffers",
     "nxs_renderer_set_adaptive", "nxs_renderer_render_adaptive", "nxs_renderer_save_sample_count_exr", "nxs_pathtracer_set_adaptive",
     "nxh_load_scene_file", "nxh_loaded_scene_free", "nxh_loaded_mesh_count", "nxh_loaded_mesh_triangle_count", "nxh_loaded_mesh_triangles",
-    "nxh_loaded_material_count", "nxh_loaded_materials", "nxh_loaded_instance_count", "nxh_loaded_instances", "nxs_scene_load_file", "nxs_scene_set_instance_transform", "nxs_scene_assign_material", "nxs_scene_set_tlas_refit", "nxs_scene_set_device_tlas", "nxs_pathtracer_set_device_blas_build",
+    "nxh_loaded_material_count", "nxh_loaded_materials", "nxh_loaded_instance_count", "nxh_loaded_instances", "nxs_scene_load_file", "nxs_scene_set_instance_transform", "nxs_scene_assign_material", "nxs_scene_set_tlas_refit", "nxs_scene_set_device_tlas", "nxs_scene_update_mesh", "nxs_pathtracer_set_device_blas_build",
     "nxs_last_error", "nxs_scene_create", "nxs_scene_destroy", "nxs_scene_add_material", "nxs_scene_add_texture", "nxs_scene_set_hdr_map",
     "nxs_scene_add_mesh", "nxs_scene_create_instance", "nxs_scene_set_camera", "nxs_scene_set_render_settings", "nxs_scene_update",
     "nxs_scene_light_count", "nxs_scene_instance_count", "nxs_pathtracer_create", "nxs_pathtracer_destroy", "nxs_pathtracer_set_modes", "nxs_pathtracer_set_frames_per_pass", "nxs_pathtracer_set_passes_in_flight", "nxs_pathtracer_set_pixel_order", "nxs_pathtracer_set_entry_points",
@@ -185,6 +185,8 @@ def lib():
     L.nxhip_read_graph_timeline.argtypes = [vp, vp, vp, vp, u32, C.POINTER(u32)]
     L.nxhip_set_instance_transforms.argtypes = [vp, vp, vp, u32]
     L.nxhip_read_tlas.argtypes = [vp, vp, u32, vp, u32]
+    L.nxhip_update_blas.argtypes = [vp, i32, vp, u32]
+    L.nxhip_update_blas_device.argtypes = [vp, i32, vp, u32]
     L.nxhip_tile_pixel_map.argtypes = [u32, u32, C.c_int, C.c_int, u32, C.c_int, vp, C.POINTER(u32)]
     L.nxhip_mgpu_unique_id.argtypes = [vp]
     L.nxhip_mgpu_init.argtypes = [vp, C.c_int, C.c_int, vp, u32]
@@ -212,6 +214,7 @@ def lib():
     L.nxh_bvh8_build.argtypes = [vp, u32, u32, C.POINTER(vp)]
     L.nxh_tlas_build.argtypes = [vp, u32, C.POINTER(vp)]
     L.nxh_tlas_refit.argtypes = [vp, u32, vp, vp, u32]
+    L.nxh_bvh8_refit.argtypes = [vp, u32, vp, vp, u32]
     L.nxh_bvh8_node_count.argtypes = [vp]
     L.nxh_bvh8_node_count.restype = u32
     L.nxh_bvh8_prim_count.argtypes = [vp]
@@ -243,6 +246,7 @@ def lib():
     L.nxs_scene_load_file.argtypes = [vp, C.c_char_p, C.c_char_p]
     L.nxs_scene_set_instance_transform.argtypes = [vp, u32, vp, vp, vp]
     L.nxs_scene_set_tlas_refit.argtypes = [vp, C.c_int]
+    L.nxs_scene_update_mesh.argtypes = [vp, u32, vp, u32]
     # Scene / PathTracer facade
     L.nxs_last_error.restype = C.c_char_p
     L.nxs_scene_create.argtypes = [u32, u32, C.POINTER(vp)]
@@ -382,6 +386,17 @@ def tlas_refit(nodes, inst_idx, instances):
     instances = np.ascontiguousarray(instances, dtype=pod.INST_DT)
     if lib().nxh_tlas_refit(_ptr(nodes), len(nodes), _ptr(inst_idx), _ptr(instances), len(instances)) != 0:
         raise NexusError("nxh_tlas_refit: malformed TLAS")
+    return nodes
+
+
+def bvh8_refit(nodes, tri_idx, tris):
+    """Refit of a BLAS to moved vertices (returns the new node array): same topology, bounds from the triangles' vertex boxes.
+    The byte reference of Context.update_blas."""
+    nodes = np.ascontiguousarray(nodes, dtype=pod.NODE_DT).copy()
+    tri_idx = np.ascontiguousarray(tri_idx, dtype=np.uint32)
+    tris = np.ascontiguousarray(tris, dtype=pod.TRI_DT)
+    if lib().nxh_bvh8_refit(_ptr(nodes), len(nodes), _ptr(tri_idx), _ptr(tris), len(tris)) != 0:
+        raise NexusError("nxh_bvh8_refit: malformed BLAS")
     return nodes
 
 
@@ -637,6 +652,16 @@ class Context:
         ids = np.ascontiguousarray(instance_ids, dtype=np.uint32)
         m = np.ascontiguousarray(transforms16, dtype=np.float32).reshape(len(ids), 16)
         check(self.L.nxhip_set_instance_transforms(self.h, _ptr(ids), _ptr(m), len(ids)), "nxhip_set_instance_transforms")
+
+    def update_blas(self, blas_id, tris):
+        """new vertices for an existing BLAS (same triangles, same order): triangles, intersection stream and nodes are redone
+        on the device; instances and the TLAS follow before the next render / ray batch / read_tlas"""
+        t = np.ascontiguousarray(tris, dtype=pod.TRI_DT)
+        check(self.L.nxhip_update_blas(self.h, int(blas_id), _ptr(t), len(t)), "nxhip_update_blas")
+
+    def update_blas_device(self, blas_id, ptr, count):
+        """update_blas from `count` 96-byte triangle records in device memory (e.g. a torch tensor's data_ptr()); asynchronous"""
+        check(self.L.nxhip_update_blas_device(self.h, int(blas_id), C.c_void_p(int(ptr)) if ptr else None, int(count)), "nxhip_update_blas_device")
 
     def read_tlas(self, node_count, instance_count):
         nodes = np.zeros(node_count, dtype=pod.NODE_DT)
@@ -1111,6 +1136,11 @@ class Scene:
         i = C.c_int32(-1)
         _scheck(self.L.nxs_scene_add_mesh(self.h, _ptr(t), len(t), material_id, C.byref(i)), "nxs_scene_add_mesh")
         return i.value
+
+    def update_mesh(self, mesh_id, tris):
+        """AssetManager::UpdateMeshTriangles: the mesh's triangles, in the same order, at new positions (a deforming mesh)"""
+        t = np.ascontiguousarray(tris, dtype=pod.TRI_DT)
+        _scheck(self.L.nxs_scene_update_mesh(self.h, mesh_id, _ptr(t), len(t)), "nxs_scene_update_mesh")
 
     def set_instance_transform(self, instance_id, position, rotation_deg, scale):
         p, r, sc = (np.asarray(x, np.float32) for x in (position, rotation_deg, scale))

@@ -99,6 +99,37 @@ int nxh_tlas_refit(nx_bvh8_node* nodes, uint32_t nodeCount, const uint32_t* inst
     }
 }
 
+int nxh_bvh8_refit(nx_bvh8_node* nodes, uint32_t nodeCount, const uint32_t* triIdx, const nx_triangle* tris, uint32_t triCount)
+{
+    if (!nodes || nodeCount == 0 || !triIdx || !tris || triCount == 0) return 1;
+    try {
+        // a refit must not read outside the arrays it was given, and must end: indices in range, every node under one parent
+        for (uint32_t i = 0; i < triCount; i++)
+            if (triIdx[i] >= triCount) return 1;
+        std::vector<uint8_t> parents(nodeCount, 0);
+        for (uint32_t i = 0; i < nodeCount; i++) {
+            const nx_bvh8_node& n = nodes[i];
+            int inner = 0, prims = 0;
+            for (int s = 0; s < 8; s++) {
+                if (n.imask & (1u << s)) inner++;
+                else if (n.meta[s]) prims = std::max(prims, (n.meta[s] & 0x1f) + __builtin_popcount(n.meta[s] >> 5));
+            }
+            if (inner && static_cast<uint64_t>(n.childBaseIdx) + inner > nodeCount) return 1;
+            if (prims && static_cast<uint64_t>(n.triangleBaseIdx) + prims > triCount) return 1;
+            for (int k = 0; k < inner; k++)
+                if (n.childBaseIdx + k == 0 || parents[n.childBaseIdx + k]++) return 1;
+        }
+        BVH8 bvh;
+        bvh.nodes.assign(nodes, nodes + nodeCount);
+        bvh.triangleIdx.assign(triIdx, triIdx + triCount);
+        bvh.Refit(to_triangles(tris, triCount));
+        std::memcpy(nodes, bvh.nodes.data(), sizeof(nx_bvh8_node) * nodeCount);
+        return 0;
+    } catch (const std::bad_alloc&) {
+        return 2;
+    }
+}
+
 uint32_t nxh_bvh8_node_count(const nxh_bvh8* b) { return b ? static_cast<uint32_t>(b->bvh.nodes.size()) : 0; }
 uint32_t nxh_bvh8_prim_count(const nxh_bvh8* b) { return b ? static_cast<uint32_t>(b->bvh.triangleIdx.size()) : 0; }
 const nx_bvh8_node* nxh_bvh8_nodes(const nxh_bvh8* b) { return b ? b->bvh.nodes.data() : nullptr; }

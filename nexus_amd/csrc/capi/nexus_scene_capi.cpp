@@ -103,6 +103,18 @@ int nxs_scene_create_instance(nxs_scene* s, uint32_t meshId, int32_t materialId,
     });
 }
 
+int nxs_scene_update_mesh(nxs_scene* s, uint32_t meshId, const nx_triangle* tris, uint32_t triCount)
+{
+    return guarded([&] {
+        AssetManager& am = s->scene.GetAssetManager();
+        if (!tris || meshId >= am.GetMeshes().size()) throw std::runtime_error("nxs_scene_update_mesh: no such mesh, or null triangles");
+        std::vector<Triangle> v;
+        v.reserve(triCount);
+        for (uint32_t i = 0; i < triCount; i++) v.emplace_back(tris[i]);
+        am.UpdateMeshTriangles(am.GetMeshes()[meshId].bvhId, v);
+    });
+}
+
 int nxs_scene_assign_material(nxs_scene* s, uint32_t instanceId, int32_t materialId)
 {
     return guarded([&] {

@@ -64,6 +64,12 @@ struct BlasHost {
     uint32_t nodeCount = 0, triCount = 0;
     uint4 root[5] = {};      // host copy of node 0 (embedded in every InstTrav record of this BLAS), read back on first use
     bool rootKnown = false;
+    // refit plan of nxhip_update_blas (nx_refit.hip blas_refit_kernel), made by the first update of this BLAS: the node indices
+    // grouped by depth, deepest level first (`refitOrder`; level l is refitLevelStart[l] .. refitLevelStart[l + 1], kept on
+    // the host too: it shapes the launches) and the 32-byte box of every node
+    DevBuf refitOrder, refitLevelStart, refitBoxes;
+    std::vector<uint32_t> refitLevels;  // host copy of refitLevelStart; empty: no plan yet
+    bool refreshPending = false;        // updated since the last refresh_updated_blas: its instances and the TLAS still hold the old root
 };
 
 struct TextureHost {
@@ -170,6 +176,9 @@ struct nxhip_ctx : nxd::PassSlot {
     // per-node box scratch, staging for the ids / matrices of one call
     nxd::DevBuf refitOrder, refitLevelStart, leafOfInstance, refitBoxes, refitIds, refitMatrices;
     uint32_t refitLevels = 0, tlasNodeCount = 0;
+    bool blasRefreshPending = false;          // some BlasHost::refreshPending is set (nxhip_update_blas)
+    std::vector<uint32_t> blasRefreshIds;     // the instances of the BLASes the last refresh served, and the list on the device
+    nxd::DevBuf blasRefreshIdsDev;
     std::vector<nxd::TextureHost> diffuseMaps, emissiveMaps;
     nxd::TextureHost hdrMap;
     nxd::DevBuf diffuseTable, emissiveTable, srgbLut;

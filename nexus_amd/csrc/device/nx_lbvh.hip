@@ -1453,6 +1453,15 @@ int lbvh_build(nxhip_ctx* c, const nx_triangle* dTris, uint32_t n, int plocRadiu
     return NXHIP_OK;
 }
 
+// The intersection stream of a BLAS again, from new triangles in the same order (nxhip_update_blas): isect_kernel as the build
+// runs it, on the context's stream, without waiting for it.
+int lbvh_write_isect(nxhip_ctx* c, const nx_triangle* dTris, const uint32_t* dPrimIdx, uint32_t n, float4* dIsect)
+{
+    isect_kernel<<<grid_for(n, std::max(1, c->numCUs)), kBlock, 0, c->stream>>>(dTris, dPrimIdx, n, dIsect, nullptr, nullptr);
+    NX_HIP(hipGetLastError());
+    return NXHIP_OK;
+}
+
 // The same builder over instance boxes: a TLAS for `n` instances (device array, world bounds filled in).  nodes / primIdx
 // (the TLAS's instance index list, leaf order) stay on the device; *nodeCount = nodes used.
 int lbvh_build_tlas(nxhip_ctx* c, const nx_bvh_instance* dInstances, uint32_t n, int plocRadius, DevBuf& nodes, DevBuf& primIdx, DevBuf& box, bool* boxesAreTight, uint32_t* nodeCount)

@@ -53,9 +53,11 @@ const void* fmath_hook_kernel_ptr();
 const void* tex2d_hook_kernel_ptr();
 const void* instance_transform_kernel_ptr();
 const void* tlas_refit_kernel_ptr();
+const void* blas_refit_kernel_ptr();
 int lbvh_build(nxhip_ctx* c, const nx_triangle* dTris, uint32_t n, int plocRadius, DevBuf& nodes, DevBuf& primIdx, DevBuf& isect, uint32_t* nodeCount);
 int lbvh_build_batch(nxhip_ctx* c, const nx_triangle* dTris, const std::vector<uint32_t>& counts, DevBuf& nodes, DevBuf& primIdx, DevBuf& isect, std::vector<uint32_t>& nodeFirst,
                      std::vector<uint32_t>& nodeCounts);
+int lbvh_write_isect(nxhip_ctx* c, const nx_triangle* dTris, const uint32_t* dPrimIdx, uint32_t n, float4* dIsect);
 int lbvh_build_tlas(nxhip_ctx* c, const nx_bvh_instance* dInstances, uint32_t n, int plocRadius, DevBuf& nodes, DevBuf& primIdx, DevBuf& box, bool* boxesAreTight, uint32_t* nodeCount);
 
 static thread_local std::string g_lastError;
@@ -1280,7 +1282,8 @@ try {
     NX_CHECK_CTX(c);
     NX_HIP(hipSetDevice(c->device));
     NX_SYNC_ALL(c);
-    c->blas.clear();
+    c->blas.clear();  // (with their refit plans)
+    c->blasRefreshPending = false;
     c->tlasTightBoxes.release();
     c->hostInstances.clear();
     c->hostInstIdx.clear();
@@ -1401,6 +1404,75 @@ int nxhip_read_tlas_index(nxhip_ctx* c, uint32_t* instanceIdx, uint32_t capacity
     return NXHIP_OK;
 }
 
+// The two launches of the device-side refit, on the context's stream: BVHInstance::SetTransform for the `count` instances listed
+// in `ids` (device; matrices in c->refitMatrices; blasRefresh: each keeps its own and only what follows its BLAS's root is redone),
+// then the bottom-up sweep of the TLAS (nx_refit.hip).
+static int launch_instance_transform(nxhip_ctx* c, const uint32_t* ids, uint32_t count, bool blasRefresh)
+{
+    const DeviceState* S = c->dState.as<DeviceState>();
+    nx_bvh_instance* inst = c->instances.as<nx_bvh_instance>();
+    InstTrav* trav = c->instTrav.as<InstTrav>();
+    const uint32_t* leafOf = c->leafOfInstance.as<uint32_t>();
+    const float* mats = c->refitMatrices.as<float>();
+    void* tight = c->tlasTightBoxes.p;
+    // (the shading records follow the matrices when they are current; a stale set is rebuilt from the device's instance table)
+    ShadeInst* shadeInst = c->shadeInstDirty ? nullptr : c->shadeInst.as<ShadeInst>();
+    const uint32_t refresh = blasRefresh ? 1u : 0u;
+    void* args[10] = {(void*)&S, (void*)&inst, (void*)&trav, (void*)&leafOf, (void*)&ids, (void*)&mats, (void*)&count, (void*)&tight, (void*)&shadeInst, (void*)&refresh};
+    const unsigned grid = std::min<unsigned>((count + 255u) / 256u, (unsigned)c->wideBlocks);
+    NX_HIP(hipLaunchKernel(instance_transform_kernel_ptr(), dim3(grid), dim3(256), args, 0, c->stream));
+    return NXHIP_OK;
+}
+
+static int launch_tlas_refit(nxhip_ctx* c)
+{
+    nx_bvh8_node* nodes = c->tlasNodes.as<nx_bvh8_node>();
+    const uint32_t* primIdx = c->tlasInstIdx.as<uint32_t>();
+    const nx_bvh_instance* inst = c->instances.as<nx_bvh_instance>();
+    const uint32_t* order = c->refitOrder.as<uint32_t>();
+    const uint32_t* levelStart = c->refitLevelStart.as<uint32_t>();
+    const uint32_t levels = c->refitLevels;
+    void* boxes = c->refitBoxes.p;
+    void* tight = c->tlasTightBoxes.p;
+    void* args[8] = {(void*)&nodes, (void*)&primIdx, (void*)&inst, (void*)&order, (void*)&levelStart, (void*)&levels, (void*)&boxes, (void*)&tight};
+    NX_HIP(hipLaunchKernel(tlas_refit_kernel_ptr(), dim3(1), dim3(1024), args, 0, c->stream));
+    return NXHIP_OK;
+}
+
+// What follows a BLAS's root, brought up to date after nxhip_update_blas refitted some BLASes: for every instance of one of them
+// (its matrix as it is) the world bounds, the tight box and the root-node copy of its traversal record, then ONE refit of the TLAS.
+// Deferred to the next call that needs the scene — a render, the ray-batch hooks, nxhip_read_tlas — so that ten meshes updated in
+// a frame pay it once; running it again changes nothing.  Works on a TLAS from nxhip_set_tlas and on a device-built one alike
+// (the refit schedule and the tight boxes are the ones nxhip_set_instance_transforms uses).
+static int refresh_updated_blas(nxhip_ctx* c)
+{
+    if (!c->blasRefreshPending) return NXHIP_OK;
+    if (!c->h.tlasNodes || c->refitLevels == 0 || c->hostInstances.empty()) return NXHIP_OK;  // (no TLAS yet: nxhip_set_tlas reads the new roots)
+    std::vector<uint32_t> ids;
+    for (size_t i = 0; i < c->hostInstances.size(); i++) {
+        const uint32_t b = c->hostInstances[i].bvhIdx;
+        if (b < c->blas.size() && c->blas[b].refreshPending) ids.push_back((uint32_t)i);
+    }
+    for (BlasHost& b : c->blas) b.refreshPending = false;
+    c->blasRefreshPending = false;
+    const uint32_t count = (uint32_t)ids.size();
+    if (count == 0) return NXHIP_OK;
+    int rc = upload_state(c);
+    if (rc != NXHIP_OK) return rc;
+    // the list goes up when it differs from the last refresh's (the same meshes deforming frame after frame: never again)
+    if (ids != c->blasRefreshIds || !c->blasRefreshIdsDev.p) {
+        NX_SYNC_ALL(c);
+        if (c->blasRefreshIdsDev.bytes < (size_t)count * 4) NX_ALLOC(c->blasRefreshIdsDev, (size_t)count * 4);
+        NX_HIP(hipMemcpy(c->blasRefreshIdsDev.p, ids.data(), (size_t)count * 4, hipMemcpyHostToDevice));
+        c->blasRefreshIds.swap(ids);
+    }
+    if ((rc = launch_instance_transform(c, c->blasRefreshIdsDev.as<uint32_t>(), count, true)) != NXHIP_OK) return rc;
+    if ((rc = launch_tlas_refit(c)) != NXHIP_OK) return rc;
+    // passes on the other slots' streams must not start on the old bounds
+    if (slot_count(c) > 1) NX_HIP(hipStreamSynchronize(c->stream));
+    return NXHIP_OK;
+}
+
 int nxhip_set_instance_transforms(nxhip_ctx* c, const uint32_t* instanceIds, const float* transforms16, uint32_t count)
 try {
     NX_CHECK_CTX(c);
@@ -1418,32 +1490,8 @@ try {
     // stream order does the rest: a frame already in flight finishes with the old placement, the next one sees the new
     NX_HIP(hipMemcpyAsync(c->refitIds.p, instanceIds, (size_t)count * 4, hipMemcpyHostToDevice, c->stream));
     NX_HIP(hipMemcpyAsync(c->refitMatrices.p, transforms16, (size_t)count * 64, hipMemcpyHostToDevice, c->stream));
-    {
-        const DeviceState* S = c->dState.as<DeviceState>();
-        nx_bvh_instance* inst = c->instances.as<nx_bvh_instance>();
-        InstTrav* trav = c->instTrav.as<InstTrav>();
-        const uint32_t* leafOf = c->leafOfInstance.as<uint32_t>();
-        const uint32_t* ids = c->refitIds.as<uint32_t>();
-        const float* mats = c->refitMatrices.as<float>();
-        void* tight = c->tlasTightBoxes.p;
-        // (the shading records follow the matrices when they are current; a stale set is rebuilt from the device's instance table)
-        ShadeInst* shadeInst = c->shadeInstDirty ? nullptr : c->shadeInst.as<ShadeInst>();
-        void* args[9] = {(void*)&S, (void*)&inst, (void*)&trav, (void*)&leafOf, (void*)&ids, (void*)&mats, (void*)&count, (void*)&tight, (void*)&shadeInst};
-        const unsigned grid = std::min<unsigned>((count + 255u) / 256u, (unsigned)c->wideBlocks);
-        NX_HIP(hipLaunchKernel(instance_transform_kernel_ptr(), dim3(grid), dim3(256), args, 0, c->stream));
-    }
-    {
-        nx_bvh8_node* nodes = c->tlasNodes.as<nx_bvh8_node>();
-        const uint32_t* primIdx = c->tlasInstIdx.as<uint32_t>();
-        const nx_bvh_instance* inst = c->instances.as<nx_bvh_instance>();
-        const uint32_t* order = c->refitOrder.as<uint32_t>();
-        const uint32_t* levelStart = c->refitLevelStart.as<uint32_t>();
-        const uint32_t levels = c->refitLevels;
-        void* boxes = c->refitBoxes.p;
-        void* tight = c->tlasTightBoxes.p;
-        void* args[8] = {(void*)&nodes, (void*)&primIdx, (void*)&inst, (void*)&order, (void*)&levelStart, (void*)&levels, (void*)&boxes, (void*)&tight};
-        NX_HIP(hipLaunchKernel(tlas_refit_kernel_ptr(), dim3(1), dim3(1024), args, 0, c->stream));
-    }
+    if ((rc = launch_instance_transform(c, c->refitIds.as<uint32_t>(), count, false)) != NXHIP_OK) return rc;
+    if ((rc = launch_tlas_refit(c)) != NXHIP_OK) return rc;
     // pageable host arrays: the copies above are staged before hipMemcpyAsync returns on this runtime, but that is not a
     // documented guarantee — wait, the call is not on the per-frame path
     NX_SYNC_ALL(c);
@@ -1468,12 +1516,123 @@ try {
     return NXHIP_ERR_INVALID;
 }
 
+// The refit plan of a BLAS (BlasHost::refitOrder ...): the one place where the tree comes back to the host, once per BLAS.  Depth is
+// derived from the tree itself, root down — a device-built tree need not number children after their parents.
+static int ensure_blas_refit_plan(nxhip_ctx* c, BlasHost& b)
+{
+    if (!b.refitLevels.empty()) return NXHIP_OK;
+    if (kNodeStride != 5) return fail_invalid("nxhip_update_blas: built with padded node records");
+    NX_SYNC_ALL(c);
+    std::vector<nx_bvh8_node> nodes(b.nodeCount);
+    NX_HIP(hipMemcpy(nodes.data(), b.nodes.p, (size_t)b.nodeCount * sizeof(nx_bvh8_node), hipMemcpyDeviceToHost));
+    constexpr uint32_t kUnseen = 0xffffffffu;
+    std::vector<uint32_t> depth(b.nodeCount, kUnseen), queue;
+    queue.reserve(b.nodeCount);
+    queue.push_back(0u);
+    depth[0] = 0;
+    uint32_t maxDepth = 0;
+    for (size_t at = 0; at < queue.size(); at++) {  // breadth first: `queue` ends up sorted by depth
+        const uint32_t i = queue[at];
+        // (what the kernel will index with, checked like an upload: nothing it reads may lie outside the BLAS's arrays)
+        if (const char* defect = wide_node_defect(nodes[i], i, b.nodeCount, b.triCount, false)) return fail_invalid(std::string("nxhip_update_blas: ") + defect);
+        const uint32_t inner = (uint32_t)__builtin_popcount(nodes[i].imask);
+        for (uint32_t k = 0; k < inner; k++) {
+            const uint32_t child = nodes[i].childBaseIdx + k;
+            if (depth[child] != kUnseen) return fail_invalid("nxhip_update_blas: the BLAS is not a tree (a node has two parents)");
+            depth[child] = depth[i] + 1;
+            maxDepth = std::max(maxDepth, depth[child]);
+            queue.push_back(child);
+        }
+    }
+    // deepest level first; nodes no parent names (none in a builder's output) are left alone
+    std::vector<uint32_t> levelStart(maxDepth + 2, 0u), order(queue.size());
+    for (const uint32_t i : queue) levelStart[(maxDepth - depth[i]) + 1]++;
+    for (uint32_t l = 0; l <= maxDepth; l++) levelStart[l + 1] += levelStart[l];
+    std::vector<uint32_t> cursor(levelStart.begin(), levelStart.end() - 1);
+    for (const uint32_t i : queue) order[cursor[maxDepth - depth[i]]++] = i;
+    NX_ALLOC(b.refitOrder, order.size() * 4);
+    NX_ALLOC(b.refitLevelStart, levelStart.size() * 4);
+    NX_ALLOC(b.refitBoxes, (size_t)b.nodeCount * 32);
+    NX_HIP(hipMemcpy(b.refitOrder.p, order.data(), order.size() * 4, hipMemcpyHostToDevice));
+    NX_HIP(hipMemcpy(b.refitLevelStart.p, levelStart.data(), levelStart.size() * 4, hipMemcpyHostToDevice));
+    b.refitLevels = std::move(levelStart);
+    return NXHIP_OK;
+}
+
+// A level of more than kBlasRefitWide nodes gets a grid launch of its own: below that a single 256-thread workgroup covers it
+// in at most four strides, and a launch (~5 us of latency between dependent kernels) costs more than the stride it would save.
+constexpr uint32_t kBlasRefitWide = 1024, kBlasRefitBlock = 256;
+
+static int update_blas(nxhip_ctx* c, int32_t blasId, const void* tris, uint32_t triCount, bool fromDevice, const char* who)
+{
+    NX_CHECK_CTX(c);
+    if (blasId < 0 || (size_t)blasId >= c->blas.size()) return fail_invalid(std::string(who) + ": no such BLAS");
+    if (!tris) return fail_invalid(std::string(who) + ": null triangles");
+    BlasHost& b = c->blas[(size_t)blasId];
+    if (triCount != b.triCount) return fail_invalid(std::string(who) + ": the triangle count differs from the BLAS's (a refit keeps the topology)");
+    NX_HIP(hipSetDevice(c->device));
+    int rc = ensure_blas_refit_plan(c, b);
+    if (rc != NXHIP_OK) return rc;
+    if (slot_count(c) > 1) NX_SYNC_ALL(c);  // passes on the other slots' streams still traverse the old shape
+    // stream order does the rest: a pass already issued finishes with the old triangles, the next one sees the new
+    const size_t bytes = (size_t)triCount * sizeof(nx_triangle);
+    NX_HIP(hipMemcpyAsync(b.tris.p, tris, bytes, fromDevice ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
+    if (kShadeTriStride != (int)sizeof(nx_triangle))
+        NX_HIP(hipMemcpy2DAsync(b.shadeTris.p, kShadeTriStride, b.tris.p, sizeof(nx_triangle), sizeof(nx_triangle), triCount, hipMemcpyDeviceToDevice, c->stream));
+    if ((rc = lbvh_write_isect(c, b.tris.as<nx_triangle>(), b.triIdx.as<uint32_t>(), triCount, b.isect.as<float4>())) != NXHIP_OK) return rc;
+    {
+        uint4* nodes = b.nodes.as<uint4>();
+        const uint32_t* triIdx = b.triIdx.as<uint32_t>();
+        const nx_triangle* dTris = b.tris.as<nx_triangle>();
+        const uint32_t* order = b.refitOrder.as<uint32_t>();
+        const uint32_t* levelStart = b.refitLevelStart.as<uint32_t>();
+        void* boxes = b.refitBoxes.p;
+        const uint32_t levels = (uint32_t)b.refitLevels.size() - 1u;
+        auto width = [&](uint32_t l) { return b.refitLevels[l + 1] - b.refitLevels[l]; };
+        for (uint32_t first = 0; first < levels;) {
+            uint32_t count = 1;
+            unsigned grid = 1;
+            if (width(first) > kBlasRefitWide) {
+                grid = std::min<unsigned>((width(first) + kBlasRefitBlock - 1u) / kBlasRefitBlock, (unsigned)(8 * std::max(1, c->numCUs)));
+            } else {
+                while (first + count < levels && width(first + count) <= kBlasRefitWide) count++;  // the run of narrow levels: one workgroup
+            }
+            void* args[8] = {(void*)&nodes, (void*)&triIdx, (void*)&dTris, (void*)&order, (void*)&levelStart, (void*)&first, (void*)&count, (void*)&boxes};
+            NX_HIP(hipLaunchKernel(blas_refit_kernel_ptr(), dim3(grid), dim3(kBlasRefitBlock), args, 0, c->stream));
+            first += count;
+        }
+    }
+    b.rootKnown = false;  // (read again by whoever next needs the host copy: refresh_inst_trav)
+    b.refreshPending = true;
+    c->blasRefreshPending = true;
+    // a pageable host array: see nxhip_set_instance_transforms
+    if (!fromDevice) NX_HIP(hipStreamSynchronize(c->stream));
+    return NXHIP_OK;
+}
+
+int nxhip_update_blas(nxhip_ctx* c, int32_t blasId, const nx_triangle* tris, uint32_t triCount)
+try {
+    return update_blas(c, blasId, tris, triCount, false, "nxhip_update_blas");
+} catch (const std::exception& e) {  // nothing may unwind through the C boundary
+    set_error(std::string("nxhip_update_blas: ") + e.what());
+    return NXHIP_ERR_INVALID;
+}
+
+int nxhip_update_blas_device(nxhip_ctx* c, int32_t blasId, const void* trisDevice, uint32_t triCount)
+try {
+    return update_blas(c, blasId, trisDevice, triCount, true, "nxhip_update_blas_device");
+} catch (const std::exception& e) {  // nothing may unwind through the C boundary
+    set_error(std::string("nxhip_update_blas_device: ") + e.what());
+    return NXHIP_ERR_INVALID;
+}
+
 int nxhip_read_tlas(nxhip_ctx* c, nx_bvh8_node* nodes, uint32_t nodeCapacity, nx_bvh_instance* instances, uint32_t instanceCapacity)
 {
     NX_CHECK_CTX(c);
     if (!c->h.tlasNodes) return fail_invalid("nxhip_read_tlas: no TLAS has been set");
     if ((nodes && nodeCapacity < c->tlasNodeCount) || (instances && instanceCapacity < c->h.instanceCount)) return fail_invalid("nxhip_read_tlas: destination too small");
     NX_HIP(hipSetDevice(c->device));
+    if (const int rcRefresh = refresh_updated_blas(c)) return rcRefresh;
     NX_SYNC_ALL(c);
     if (nodes) {
         if (kNodeStride == 5) NX_HIP(hipMemcpy(nodes, c->tlasNodes.p, (size_t)c->tlasNodeCount * sizeof(nx_bvh8_node), hipMemcpyDeviceToHost));
@@ -2296,6 +2455,7 @@ try {
     }
     rc = upload_state(c);
     if (rc != NXHIP_OK) return rc;
+    if ((rc = refresh_updated_blas(c)) != NXHIP_OK) return rc;  // (BLASes refitted since the last pass: nxhip_update_blas)
     if (!slot_queues_ready(c, q)) {
         rc = ensure_slot_queues(c, q);
         if (rc != NXHIP_OK) return rc;
@@ -3267,6 +3427,7 @@ try {
     if (rc != NXHIP_OK) return rc;
     rc = upload_state(c);
     if (rc != NXHIP_OK) return rc;
+    if ((rc = refresh_updated_blas(c)) != NXHIP_OK) return rc;
     const uint32_t cap = c->pathCount;
     std::vector<float4> o(std::min(cap, count)), d(std::min(cap, count)), h(std::min(cap, count));
     std::vector<uint32_t> hi(std::min(cap, count));
@@ -3313,6 +3474,7 @@ try {
     if (rc != NXHIP_OK) return rc;
     rc = upload_state(c);
     if (rc != NXHIP_OK) return rc;
+    if ((rc = refresh_updated_blas(c)) != NXHIP_OK) return rc;
     const uint32_t cap = c->pathCount;
     const uint32_t m = std::min(cap, count);
     std::vector<float4> o(m), d(m), rad(m, make_float4(1.0f, 0.0f, 0.0f, 0.0f)), res(m);

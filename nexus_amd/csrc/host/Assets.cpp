@@ -1,6 +1,8 @@
 // Assets.cpp — AssetManager (see include/nexus/Assets.h); behaviour of /root/reference/Nexus/src/Assets/AssetManager.cpp:12-116.
 #include "nexus/Assets.h"
 
+#include <stdexcept>
+
 #include "nexus/BVH8Builder.h"
 
 namespace nexus {
@@ -13,6 +15,8 @@ void AssetManager::Reset()
     m_EmissiveMaps.clear();
     m_Meshes.clear();
     m_Bvhs.clear();
+    m_DeformedBvhs.clear();
+    deformedBvhs.clear();
     uploadedBvhs = 0;
     materialsDirty = texturesDirty = true;
 }
@@ -45,6 +49,23 @@ int32_t AssetManager::AddMesh(Mesh&& mesh)
 {
     m_Meshes.push_back(std::move(mesh));
     return static_cast<int32_t>(m_Meshes.size()) - 1;
+}
+
+void AssetManager::UpdateMeshTriangles(int32_t bvhId, const std::vector<Triangle>& triangles)
+{
+    if (bvhId < 0 || static_cast<size_t>(bvhId) >= m_Bvhs.size()) throw std::runtime_error("AssetManager::UpdateMeshTriangles: no such BVH");
+    BVH8& bvh = m_Bvhs[static_cast<size_t>(bvhId)];
+    if (triangles.size() != bvh.triangleIdx.size()) throw std::runtime_error("AssetManager::UpdateMeshTriangles: the triangle count differs from the mesh's (a refit keeps the topology)");
+    bvh.Refit(triangles);  // (nodes and the tree's copy of the triangles)
+    m_DeformedBvhs.insert(bvhId);
+    deformedBvhs.insert(bvhId);
+}
+
+std::set<int32_t> AssetManager::TakeDeformedBvhs()
+{
+    std::set<int32_t> out;
+    out.swap(m_DeformedBvhs);
+    return out;
 }
 
 void AssetManager::AddMaterial()

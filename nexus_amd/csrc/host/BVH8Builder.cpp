@@ -47,6 +47,21 @@ BVH8::BVH8(const std::vector<Triangle>& tri) : triangles(tri), triangleIdx(tri.s
     std::iota(triangleIdx.begin(), triangleIdx.end(), 0u);
 }
 
+// Deforming meshes: same triangles in the same order at new positions.  The tree keeps its topology; every node's frame and
+// its children's quantised boxes are recomputed from the triangles' vertex boxes (pos0, pos1, pos2 grown from the empty box).
+// The reference rebuilds instead (Assets/AssetManager.cpp:23-37).
+void BVH8::Refit(const std::vector<Triangle>& tri)
+{
+    std::vector<AABB> bounds(tri.size());
+    for (size_t i = 0; i < tri.size(); i++) {
+        bounds[i].Grow(tri[i].pos0);
+        bounds[i].Grow(tri[i].pos1);
+        bounds[i].Grow(tri[i].pos2);
+    }
+    collapse::Refit(nodes, triangleIdx.data(), bounds.data());
+    if (!triangles.empty()) triangles = tri;  // (a tree that keeps its triangles keeps the new ones)
+}
+
 BVH8Builder::BVH8Builder(const std::vector<Triangle>& triangles) : m_Bvh2(triangles) {}
 
 void BVH8Builder::Init(unsigned threads)

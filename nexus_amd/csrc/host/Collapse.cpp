@@ -235,8 +235,23 @@ AABB Refit(std::vector<BVH8Node>& nodes, const uint32_t* primIdx, const AABB* pr
 {
     const size_t n = nodes.size();
     std::vector<AABB> nodeBox(n);
-    // children are emitted after their parent (childBaseIdx > own index), so a descending sweep sees children first
-    for (size_t k = n; k-- > 0;) {
+    // The host builders emit children after their parent (childBaseIdx > own index): a descending sweep sees children first.
+    // A tree that does not (the device builders' need not) is swept in the reverse of a breadth-first walk from the root;
+    // a node's result depends on its children's boxes only, so any children-first order gives the same bytes.
+    bool childrenFollow = true;
+    for (size_t k = 0; k < n && childrenFollow; k++) childrenFollow = !nodes[k].imask || nodes[k].childBaseIdx > k;
+    std::vector<uint32_t> walk;
+    if (!childrenFollow) {
+        walk.reserve(n);
+        walk.push_back(0u);
+        for (size_t at = 0; at < walk.size() && walk.size() <= n; at++) {
+            const BVH8Node& node = nodes[walk[at]];
+            for (int c = 0, inner = __builtin_popcount(node.imask); c < inner; c++) walk.push_back(node.childBaseIdx + static_cast<uint32_t>(c));
+        }
+    }
+    const size_t sweep = childrenFollow ? n : walk.size();
+    for (size_t at = sweep; at-- > 0;) {
+        const size_t k = childrenFollow ? at : walk[at];
         BVH8Node& node = nodes[k];
         AABB childBox[8];
         bool used[8] = {false, false, false, false, false, false, false, false};

@@ -146,7 +146,19 @@ void PathTracer::UpdateDeviceScene(const Scene& scene)
 {
     const AssetManager& assets = scene.GetAssetManager();
     AssetManager& mutableAssets = const_cast<AssetManager&>(assets);
+    // deformed meshes the device already holds: new vertices through nxhip_update_blas (triangles, intersection stream and nodes
+    // are redone in HBM; same BLAS id, same instances).  Before the TLAS below, whose upload or refit reads the new roots.  A
+    // mesh the device has not seen yet goes up with its new shape like any other.
+    const size_t onDevice = assets.uploadedBvhs;
     UploadPendingBlas(mutableAssets);
+    for (const int32_t bvhId : assets.deformedBvhs) {
+        if (static_cast<size_t>(bvhId) >= onDevice) continue;
+        const BVH8& bvh = assets.GetBVHs()[static_cast<size_t>(bvhId)];
+        std::vector<nx_triangle> tris(bvh.triangles.size());
+        for (size_t t = 0; t < tris.size(); t++) tris[t] = Triangle::ToDevice(bvh.triangles[t]);
+        Check(nxhip_update_blas(m_Ctx, bvh.deviceBlasId, tris.data(), static_cast<uint32_t>(tris.size())), "nxhip_update_blas");
+    }
+    mutableAssets.deformedBvhs.clear();
     if (assets.texturesDirty) {
         Check(nxhip_clear_textures(m_Ctx), "nxhip_clear_textures");
         for (const Texture& t : assets.GetDiffuseMaps()) Check(nxhip_upload_texture(m_Ctx, 0, t.pixels.data(), t.width, t.height, nullptr), "nxhip_upload_texture");

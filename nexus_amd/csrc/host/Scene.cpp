@@ -33,6 +33,13 @@ void Scene::Update()
 {
     m_Camera->SetInvalid(false);
     m_AssetManager.SendDataToDevice();
+    // Deformed meshes (AssetManager::UpdateMeshTriangles refitted their BVH8): their instances are placed again, as they are —
+    // SetTransform below re-derives the world bounds from the new root frame — and the TLAS follows by the mode in force.
+    for (const int32_t bvhId : m_AssetManager.TakeDeformedBvhs())
+        for (size_t id = 0; id < m_MeshInstances.size(); id++) {
+            const BVHInstance& placed = m_BVHInstances[static_cast<size_t>(m_MeshInstances[id].bvhInstanceIdx)];
+            if (m_AssetManager.GetMeshes()[placed.GetBvhIdx()].bvhId == bvhId) m_InvalidMeshInstances.insert(static_cast<uint32_t>(id));
+        }
     if (m_InvalidMeshInstances.empty()) {
         m_Invalid = false;
         return;
