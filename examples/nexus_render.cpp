@@ -1,12 +1,14 @@
 // nexus_render — the reference's render loop (Renderer.cpp:41-77: scene.Update, UpdateDeviceScene, Render) driven headless
 // through the kept C++ host API: load a .glb / .obj, path-trace `frames` frames on an MI355X, write the image as a PPM.
 //
-//   nexus_render [--denoise] [--adaptive THRESHOLD [--max-frames N]] <dir/> <file.glb|file.obj> <out.ppm> [width height frames pathLength]
+//   nexus_render [--denoise] [--adaptive THRESHOLD [--max-frames N]] [--light-sampling uniform|power] <dir/> <file.glb|file.obj> <out.ppm> [width height frames pathLength]
 //                [eyeX eyeY eyeZ fwdX fwdY fwdZ hfovDeg]
 // --denoise: the feature buffers are accumulated with the colour and the image written is the a-trous filtered one (nxhip_denoise)
 // --adaptive THRESHOLD: render to a noise target instead of a frame count (nxhip_render_adaptive: blocks of 64 pixels stop when the
 //   relative standard error of every pixel's mean luminance is at most THRESHOLD; pixel-keyed random numbers; decided every 8 frames;
 //   at most N frames, default 1024; `frames` is ignored).  Combines with --denoise.  The image is not an unbiased estimate.
+// --light-sampling power: the light sample picks among the mesh lights' triangles in proportion to area x emitted luminance
+//   (nxhip_set_light_sampling; default uniform: the reference's rule).  Same expectation, less noise under small or dim emitters.
 //
 // Build: make example   (links nexus_amd/lib/libnexus_amd.so)
 #include <cstdint>
@@ -25,6 +27,7 @@ int main(int argc, char** argv)
     bool denoise = false, adaptive = false;
     float threshold = 0.0f;
     uint32_t maxFrames = 1024;
+    int lightSampling = NXHIP_LIGHTS_UNIFORM;
     for (;;) {  // leading options, in any order
         const std::string opt = argc > 1 ? argv[1] : "";
         int used = 0;
@@ -38,6 +41,14 @@ int main(int argc, char** argv)
         } else if (opt == "--max-frames" && argc > 2) {
             maxFrames = static_cast<uint32_t>(std::atoi(argv[2]));
             used = 2;
+        } else if (opt == "--light-sampling" && argc > 2) {
+            const std::string mode = argv[2];
+            if (mode != "uniform" && mode != "power") {
+                std::fprintf(stderr, "--light-sampling: uniform or power\n");
+                return 2;
+            }
+            lightSampling = mode == "power" ? NXHIP_LIGHTS_POWER : NXHIP_LIGHTS_UNIFORM;
+            used = 2;
         }
         if (!used) break;
         argv[used] = argv[0];
@@ -45,7 +56,7 @@ int main(int argc, char** argv)
         argc -= used;
     }
     if (argc < 4) {
-        std::fprintf(stderr, "usage: %s [--denoise] [--adaptive THRESHOLD [--max-frames N]] <dir/> <file.glb|file.obj> <out.ppm> [width height frames pathLength] [eye(3) forward(3) hfov]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s [--denoise] [--adaptive THRESHOLD [--max-frames N]] [--light-sampling uniform|power] <dir/> <file.glb|file.obj> <out.ppm> [width height frames pathLength] [eye(3) forward(3) hfov]\n", argv[0]);
         return 2;
     }
     // a program built against these headers and run with another build of libnexus_amd.so gets an error string here, not a GPU fault
@@ -83,6 +94,7 @@ int main(int argc, char** argv)
         if (std::getenv("NEXUS_DETERMINISTIC") || adaptive) pathTracer.SetModes(NX_RNG_PIXEL_KEYED, NX_COMPACT_FAST, NX_CONDUCTOR_REFERENCE);
         pathTracer.UpdateDeviceScene(scene);
         if (denoise) pathTracer.SetFeatureBuffers(true);
+        pathTracer.SetLightSampling(lightSampling);
         uint32_t activePixels = 0;
         if (adaptive) {
             nx_adaptive_params params;

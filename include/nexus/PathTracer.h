@@ -47,6 +47,10 @@ public:
     // Primary rays start from the traversal state the first node steps of their run of 64 paths provably share instead of the TLAS
     // root (nxhip_set_entry_points: hit records unchanged, pinhole cameras only).  Off by default.
     void SetEntryPoints(bool on);
+    // How the light sample chooses among the mesh lights' triangles (nxhip_set_light_sampling): NXHIP_LIGHTS_UNIFORM (0, the reference's
+    // rule and the default) or NXHIP_LIGHTS_POWER (1: in proportion to area x emitted luminance, from a table built on the device).
+    // Same expectation either way: may be switched between frames.
+    void SetLightSampling(int mode);
     // The order of the frame's paths: NXHIP_ORDER_ROWS (the reference's, default) or NXHIP_ORDER_TILES (8 x 8 pixel tiles: the rays a
     // wave fetches together are a compact block of the image; kept across OnResize).  nxhip_set_pixel_order.
     void SetPixelOrder(int order);

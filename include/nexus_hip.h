@@ -162,6 +162,35 @@ int nxhip_clear_textures(nxhip_ctx *ctx);
  * against that sampler with the power heuristic.  Unbiased either way; the expectation of a frame is unchanged.  Needs an
  * uploaded environment map (kind 2); off by default. */
 int nxhip_set_env_sampling(nxhip_ctx *ctx, int enable);
+/* Extension: how the next-event estimation chooses its mesh-light sample.
+ *   NXHIP_LIGHTS_UNIFORM (default)  the reference's rule, bit for bit: one light uniformly, then one of its triangles uniformly
+ *                                   (PathTracer.cu:227-240) — a candle as often as a ceiling panel, the slivers of a tessellated
+ *                                   emitter as often as its large triangles.
+ *   NXHIP_LIGHTS_POWER              every emissive triangle of every mesh light in proportion to w = world-space area x Y, with
+ *                                   Y = intensity x (0.2126 r + 0.7152 g + 0.0722 b) of the light's material; (r, g, b) is the emissive
+ *                                   factor or, with an emissive map, the mean of the map's sRGB-decoded texels (alpha ignored).  A weight
+ *                                   that is negative or not finite counts as 0.
+ * The table (entries ordered by light — the order of nxhip_set_lights — then by triangle index; N = the mesh lights' triangles) is built
+ * on the device with no read-back: binary64 prefix sums of w, cdf[i] = binary32(prefix[i] / total) with the last entry exactly 1, and a
+ * guide table of G = the power of two >= N (at most 2^23) cut points, so that a pick costs one random number and an expected two loads:
+ * k = floor(u G), i = guide[k], while (cdf[i] <= u) i++  —  by definition min(searchsorted(cdf, u, 'right'), N - 1).  P(i) = cdf[i] -
+ * cdf[i - 1] is the probability both the sampler and the MIS weight of an emissive hit use, read from the table, never recomputed.
+ * The light sample draws as many random numbers as in the default mode (the one u replaces the uniform triangle index); the uniform
+ * pick among lightCount (+ 1 with nxhip_set_env_sampling) still decides between "a mesh light" and the environment.  An emissive hit
+ * whose instance is no light, or whose entry has P = 0, gets the MIS weight 1: the sampler cannot reach it.  A total weight of 0: no
+ * mesh-light samples at all.  Unbiased either way; the expectation of a frame does not change, so the mode may be switched at any
+ * time, also between accumulated frames.
+ * Granularity: u has 23 bits (rng_next), the limit the reference's uniform index has too; an entry whose share is below about 2^-25
+ * can round to P = 0 and is then never sampled (and weighted 1 when hit).
+ * The table is rebuilt, once, by the next render or hook call after anything it depends on has changed: nxhip_set_lights,
+ * nxhip_set_materials, nxhip_set_tlas / nxhip_rebuild_tlas, an emissive texture upload or clear, nxhip_set_instance_transforms (a scale
+ * changes areas), nxhip_update_blas(_device), the mode itself.  In the default mode nothing is allocated, built or launched.
+ * With more than one pass in flight (nxhip_set_passes_in_flight) a rebuild waits for every pass issued and the next pass waits for the
+ * rebuild — the passes read ONE table — so a light that deforms every frame serialises the passes in flight; one pass at a time the
+ * rebuild is just ahead of the pass in stream order.
+ * In POWER mode a light list that names one instance twice is refused by the render (NXHIP_ERR_INVALID).  Another mode: NXHIP_ERR_INVALID. */
+enum { NXHIP_LIGHTS_UNIFORM = 0, NXHIP_LIGHTS_POWER = 1 };
+int nxhip_set_light_sampling(nxhip_ctx *ctx, int mode);
 /* PathTracer::UpdateDeviceScene / Scene::ToDevice — Renderer/PathTracer.cpp:305-308, Scene/Scene.cpp:115-140 */
 int nxhip_set_camera(nxhip_ctx *ctx, const nx_camera *camera);
 int nxhip_set_render_settings(nxhip_ctx *ctx, const nx_render_settings *settings);
@@ -465,6 +494,14 @@ int nxhip_bsdf_eval_batch(nxhip_ctx *ctx, const nx_material *material, const nx_
 /* kind as in nxhip_upload_texture (0 diffuse, 1 emissive, 2 hdr; textureId ignored for hdr); uv = 2*count floats,
  * rgba = 4*count floats (sRGB-decoded, bilinear, wrap addressing: what the shade kernels see). */
 int nxhip_tex2d_batch(nxhip_ctx *ctx, int kind, int textureId, const float *uv, uint32_t count, float *rgba);
+
+/* Test hooks of the light table (NXHIP_LIGHTS_POWER only, else NXHIP_ERR_INVALID; both bring the table up to date first).
+ * read: cdf / entryLight (either may be NULL) hold `capacity` entries, lightBase (may be NULL) lightCount + 1 words; *entries = N.
+ * pick: entry[k], prob[k] = the device's pick for u[k] and its P.  A u outside [0, 1) — NaN included, which would index the guide
+ * table wildly — is refused on the host before anything is launched; so is an empty table, and a table whose weights sum to
+ * nothing (`valid` = 0: the renderer never samples it; the hook reads the flag back). */
+int nxhip_read_light_table(nxhip_ctx *ctx, float *cdf, uint32_t *entryLight, uint32_t capacity, uint32_t *lightBase, uint32_t *entries);
+int nxhip_light_pick_batch(nxhip_ctx *ctx, const float *u, uint32_t count, uint32_t *entry, float *prob);
 
 /* The transcendental functions of the shading path (include/nexus_fmath.h: the ONE text the kernels and the CPU oracle both
  * compile — sin / cos / exp / log / pow / atan2 / asin replacing the libm calls of Random.cuh:119-121, Microfacet.cuh:18,75,

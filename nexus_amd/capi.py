@@ -31,6 +31,7 @@ HIP_SYMBOLS = [
     "nxhip_set_aov", "nxhip_read_aov", "nxhip_read_aov_frame", "nxhip_write_aov", "nxhip_denoise", "nxhip_denoise_defaults", "nxhip_read_denoised", "nxhip_read_denoised_rgba8",
     "nxhip_adaptive_defaults", "nxhip_set_adaptive", "nxhip_adaptive_update", "nxhip_render_adaptive", "nxhip_read_sample_counts", "nxhip_read_noise_stats",
     "nxhip_read_block_noise", "nxhip_read_active_map", "nxhip_update_blas", "nxhip_update_blas_device",
+    "nxhip_set_light_sampling", "nxhip_read_light_table", "nxhip_light_pick_batch",
 ]
 HOST_SYMBOLS = [
     "nxh_bvh8_build", "nxh_tlas_build", "nxh_tlas_refit", "nxh_bvh8_refit", "nxh_bvh8_node_count", "nxh_bvh8_prim_count", "nxh_bvh8_nodes",
@@ -45,7 +46,7 @@ HOST_SYMBOLS = [
     "nxh_loaded_material_count", "nxh_loaded_materials", "nxh_loaded_instance_count", "nxh_loaded_instances", "nxs_scene_load_file", "nxs_scene_set_instance_transform", "nxs_scene_assign_material", "nxs_scene_set_tlas_refit", "nxs_scene_set_device_tlas", "nxs_scene_update_mesh", "nxs_pathtracer_set_device_blas_build",
     "nxs_last_error", "nxs_scene_create", "nxs_scene_destroy", "nxs_scene_add_material", "nxs_scene_add_texture", "nxs_scene_set_hdr_map",
     "nxs_scene_add_mesh", "nxs_scene_create_instance", "nxs_scene_set_camera", "nxs_scene_set_render_settings", "nxs_scene_update",
-    "nxs_scene_light_count", "nxs_scene_instance_count", "nxs_pathtracer_create", "nxs_pathtracer_destroy", "nxs_pathtracer_set_modes", "nxs_pathtracer_set_frames_per_pass", "nxs_pathtracer_set_passes_in_flight", "nxs_pathtracer_set_pixel_order", "nxs_pathtracer_set_entry_points",
+    "nxs_scene_light_count", "nxs_scene_instance_count", "nxs_pathtracer_create", "nxs_pathtracer_destroy", "nxs_pathtracer_set_modes", "nxs_pathtracer_set_frames_per_pass", "nxs_pathtracer_set_passes_in_flight", "nxs_pathtracer_set_pixel_order", "nxs_pathtracer_set_entry_points", "nxs_pathtracer_set_light_sampling",
     "nxs_pathtracer_update_device_scene", "nxs_pathtracer_render", "nxs_pathtracer_reset_frame_number", "nxs_pathtracer_frame_number",
     "nxs_pathtracer_read_pixels", "nxs_pathtracer_device_context",
 ]
@@ -731,6 +732,33 @@ class Context:
         self.L.nxhip_set_env_sampling.argtypes = [C.c_void_p, C.c_int]
         check(self.L.nxhip_set_env_sampling(self.h, 1 if on else 0), "nxhip_set_env_sampling")
 
+    def set_light_sampling(self, mode):
+        """LIGHTS_UNIFORM (0, the reference's rule) or LIGHTS_POWER (1): the light sample picks among the mesh lights' triangles in
+        proportion to area x emitted luminance, from a table built on the device (include/nexus_hip.h)"""
+        self.L.nxhip_set_light_sampling.argtypes = [C.c_void_p, C.c_int]
+        check(self.L.nxhip_set_light_sampling(self.h, int(mode)), "nxhip_set_light_sampling")
+
+    def read_light_table(self, light_count):
+        """the light table of LIGHTS_POWER (brought up to date first): (cdf float32[N], entryLight uint32[N], lightBase uint32[light_count + 1])"""
+        self.L.nxhip_read_light_table.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32)]
+        n = C.c_uint32(0)
+        base = np.zeros(int(light_count) + 1, dtype=np.uint32)
+        check(self.L.nxhip_read_light_table(self.h, None, None, 0, _ptr(base), C.byref(n)), "nxhip_read_light_table")
+        cdf = np.zeros(n.value, dtype=np.float32)
+        light = np.zeros(n.value, dtype=np.uint32)
+        if n.value:
+            check(self.L.nxhip_read_light_table(self.h, _ptr(cdf), _ptr(light), n.value, _ptr(base), C.byref(n)), "nxhip_read_light_table")
+        return cdf, light, base
+
+    def light_pick_batch(self, u):
+        """the device's pick for every u in [0, 1): (entry uint32[], prob float32[]) — the table's walk and its P(entry)"""
+        u = np.ascontiguousarray(u, dtype=np.float32)
+        entry = np.zeros(len(u), dtype=np.uint32)
+        prob = np.zeros(len(u), dtype=np.float32)
+        self.L.nxhip_light_pick_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+        check(self.L.nxhip_light_pick_batch(self.h, _ptr(u), len(u), _ptr(entry), _ptr(prob)), "nxhip_light_pick_batch")
+        return entry, prob
+
     def set_entry_points(self, on=True):
         """primary rays start from the state their run's first node steps provably share (include/nexus_hip.h)"""
         self.L.nxhip_set_entry_points.argtypes = [C.c_void_p, C.c_int]
@@ -1348,6 +1376,17 @@ class PathTracer:
     def set_entry_points(self, on=True):
         self.L.nxs_pathtracer_set_entry_points.argtypes = [C.c_void_p, C.c_int]
         _scheck(self.L.nxs_pathtracer_set_entry_points(self.h, 1 if on else 0), "nxs_pathtracer_set_entry_points")
+
+    def set_light_sampling(self, mode):
+        """PathTracer::SetLightSampling: pod.LIGHTS_UNIFORM (the reference's rule) or pod.LIGHTS_POWER (area x emitted luminance)"""
+        self.L.nxs_pathtracer_set_light_sampling.argtypes = [C.c_void_p, C.c_int]
+        _scheck(self.L.nxs_pathtracer_set_light_sampling(self.h, int(mode)), "nxs_pathtracer_set_light_sampling")
+
+    def read_accumulation(self):
+        """the running mean over the frames rendered so far, (pixels, 3) float32, from this path tracer's device context"""
+        out = np.zeros((self.width * self.height, 3), np.float32)
+        check(self.L.nxhip_read_accumulation(self.L.nxs_pathtracer_device_context(self.h), _ptr(out)), "nxhip_read_accumulation")
+        return out
 
     def set_feature_buffers(self, on=True):
         """PathTracer::SetFeatureBuffers: albedo / normal / depth of the camera ray's hit, accumulated like the colour"""

@@ -216,6 +216,7 @@ struct nxhip_ctx : nxd::PassSlot {
 
     int traceBlocks = 0, shadowBlocks = 0, wideBlocks = 0;  // full-chip persistent grids (see trace_blocks)
     int tailBlocks = 0;
+    int tailBlocksPower = 0;  // grid of tail_kernel<true> (NXHIP_LIGHTS_POWER), from that instance's own occupancy
     int tailBounce = -1;  // first bounce of the tail kernel, 0 = off, -1 = automatic (see tail_bounce in nxhip_api.hip)
     bool traceGridForced = false;                            // NX_TRACE_BLOCKS_*: use them as they are
     int shadeBlocksPerCU = 10, logicBlocksPerCU = 2;  // grid-stride kernels: workgroups per CU
@@ -246,4 +247,14 @@ struct nxhip_ctx : nxd::PassSlot {
     uint32_t activeCount = 0;                        // paths per frame slice of the next pass (cull == 0: always localCount)
     uint32_t unsettledPixels = 0, unsettledBlocks = 0;  // of the flagged blocks
     uint32_t passFrames = 0;                         // frames of the pass being issued (nxhip_render_adaptive packs frames; 0: framesPerPass)
+    // light sampling by emitted power (nx_lights.hip; nxhip_set_light_sampling).  Everything below stays empty in NXHIP_LIGHTS_UNIFORM.
+    int lightSampling = 0;          // NXHIP_LIGHTS_*
+    bool lightTableDirty = true;    // something the table depends on has changed: rebuilt by the next render / hook call in POWER mode
+    std::vector<uint32_t> hostLightBase, hostInstLight;  // the entry layout the device buffers were sized and filled for
+    nxd::DevBuf lightTable, lightGuide, lightBase, instLight, lightHeader;
+    nxd::DevBuf lightWeight, lightPrefix, lightScanTemp;  // the build's scratch, kept: a deforming light rebuilds every frame
+    size_t lightScanBytes = 0;
+    uint32_t lightEntries = 0, lightGuideSize = 0;
+    nxd::DevBuf lightMapMean;       // [capacity] x 4 floats: mean sRGB-decoded texel of the emissive maps, computed once per uploaded map
+    size_t lightMapMeanCapacity = 0, lightMapMeans = 0;  // maps the buffer holds / maps whose mean is in it
 };

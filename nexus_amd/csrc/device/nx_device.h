@@ -317,6 +317,34 @@ struct TraceStatsDev {
     unsigned long long cycles[8];
 };
 
+// Light sampling by emitted power: one record per emissive triangle, so that a pick reads the cumulative probability and the light behind
+// ONE 8-byte load; the probability of entry i is cdf[i] - cdf[i - 1], for the sampler and for the MIS lookup alike.
+struct __attribute__((aligned(8))) LightEntry {
+    float cdf;       // inclusive, non-decreasing, the last entry exactly 1
+    uint32_t light;  // index into DeviceState::lights
+};
+struct LightHeader {
+    uint32_t valid;  // 0: the weights sum to nothing (or to nothing finite): the mesh branch of the light sample returns false
+    uint32_t pad_;
+    double total;    // sum of the weights
+};
+constexpr uint32_t kNotALight = 0xffffffffu;
+constexpr uint32_t kLightGuideMax = 1u << 23;  // rng_next's resolution
+
+// Argument block of the light table's kernels (nx_lights.hip; filled by refresh_light_table in nxhip_api.hip)
+struct LightBuild {
+    const ShadeInst* shadeInst;
+    const nx_light* lights;
+    const uint32_t* lightBase;   // [lightCount + 1]
+    const float* mapMean;        // [emissive maps] x 4: mean of the sRGB-decoded texels (rgb, unused)
+    double* weight;              // [entries]
+    double* prefix;              // [entries] inclusive prefix sums of the weights
+    LightEntry* table;
+    uint32_t* guide;
+    LightHeader* header;
+    uint32_t lightCount, entries, guideSize, pad_;
+};
+
 struct DeviceState {
     // scene
     const NX_G uint4* tlasNodes;
@@ -394,6 +422,16 @@ struct DeviceState {
     NX_G float2* adStats;               // [baseCount] Welford (meanY, M2) of the luminance
     uint32_t baseCount;
     uint32_t padAdaptive_;
+    // Light sampling by emitted power (nxhip_set_light_sampling; nx_lights.hip), all nullptr / 0 in NXHIP_LIGHTS_UNIFORM.  One entry per
+    // triangle of every mesh light, ordered by light (the order of `lights`), then by triangle index.  Read only by the kernel variants
+    // that POWER-mode pass graphs launch.
+    const NX_G LightEntry* lightTable;    // [lightEntries]
+    const NX_G uint32_t* lightGuide;      // [lightGuideSize]: entry k = the first entry whose cdf exceeds k / lightGuideSize
+    const NX_G uint32_t* lightBase;       // [lightCount + 1]: first entry of every light
+    const NX_G uint32_t* instLight;       // [instanceCount]: the light an instance is, kNotALight: none
+    const NX_G LightHeader* lightHeader;
+    uint32_t lightEntries;
+    uint32_t lightGuideSize;              // a power of two: u * lightGuideSize is exact in binary32
 };
 
 // Argument block of the adaptive update's kernels (nx_adaptive.hip; filled by nxhip_adaptive_update)
@@ -437,7 +475,7 @@ constexpr uint64_t layout_stamp()
     const uint64_t w[] = {
         sizeof(DeviceState), offsetof(DeviceState, camera), offsetof(DeviceState, envSampling), offsetof(DeviceState, localCount), offsetof(DeviceState, pixelMap),
         offsetof(DeviceState, radiance), offsetof(DeviceState, trace), offsetof(DeviceState, shadow), offsetof(DeviceState, material), offsetof(DeviceState, counters),
-        offsetof(DeviceState, frame), offsetof(DeviceState, traceStats), offsetof(DeviceState, scanStatus), offsetof(DeviceState, entry), offsetof(DeviceState, entryRuns), offsetof(DeviceState, debugRequeue), offsetof(DeviceState, aovAlbedo), offsetof(DeviceState, aovAccumNormalDepth), offsetof(DeviceState, basePixelMap), offsetof(DeviceState, adStats), offsetof(DeviceState, baseCount), sizeof(AdaptiveLaunch), offsetof(AdaptiveLaunch, baseCount), offsetof(DeviceState, thinStates), offsetof(DeviceState, leafOfInstance), sizeof(ThinState), offsetof(ThinState, stack), offsetof(DeviceState, thinClosest), offsetof(DeviceState, thinCapacity), offsetof(DeviceState, thinIters), offsetof(DeviceState, thinPoolLimit), offsetof(Counters, thinCount), sizeof(EntryState), offsetof(EntryState, sp), offsetof(EntryState, triP0), offsetof(EntryState, triInst), offsetof(Counters, scanTicket), offsetof(FrameState, scanEpoch),
+        offsetof(DeviceState, frame), offsetof(DeviceState, traceStats), offsetof(DeviceState, scanStatus), offsetof(DeviceState, entry), offsetof(DeviceState, entryRuns), offsetof(DeviceState, debugRequeue), offsetof(DeviceState, aovAlbedo), offsetof(DeviceState, aovAccumNormalDepth), offsetof(DeviceState, basePixelMap), offsetof(DeviceState, adStats), offsetof(DeviceState, baseCount), offsetof(DeviceState, lightTable), offsetof(DeviceState, lightHeader), offsetof(DeviceState, lightGuideSize), sizeof(LightEntry), sizeof(LightHeader), sizeof(LightBuild), offsetof(LightBuild, lightCount), sizeof(AdaptiveLaunch), offsetof(AdaptiveLaunch, baseCount), offsetof(DeviceState, thinStates), offsetof(DeviceState, leafOfInstance), sizeof(ThinState), offsetof(ThinState, stack), offsetof(DeviceState, thinClosest), offsetof(DeviceState, thinCapacity), offsetof(DeviceState, thinIters), offsetof(DeviceState, thinPoolLimit), offsetof(Counters, thinCount), sizeof(EntryState), offsetof(EntryState, sp), offsetof(EntryState, triP0), offsetof(EntryState, triInst), offsetof(Counters, scanTicket), offsetof(FrameState, scanEpoch),
         (uint64_t)kScanKinds, (uint64_t)kScanWords, (uint64_t)kScanEpochLimit, (uint64_t)kShadeBlockOrderedThreads,
         sizeof(Counters), sizeof(RegionCounters), offsetof(RegionCounters, traceShadowSize), offsetof(RegionCounters, materialSize), offsetof(RegionCounters, traceHead),
         offsetof(RegionCounters, shadowHead), offsetof(RegionCounters, scanTile), offsetof(RegionCounters, endedSize), offsetof(Counters, orderedBase), offsetof(Counters, tailHead),

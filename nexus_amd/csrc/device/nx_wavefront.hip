@@ -18,6 +18,7 @@
 #include "nx_bsdf.h"
 #include "nx_device.h"
 #include "nx_math.h"
+#include "nx_lights.h"
 #include "nx_queue.h"
 #include "nx_texture.h"
 #include "nx_tonemap.h"
@@ -670,14 +671,16 @@ NXD MatParams load_params(const nx_material& m)
     return p;
 }
 
-NXD float tri_area(f3 p0, f3 p1, f3 p2) { return 0.5f * length3(cross3(p1 - p0, p2 - p0)); }
-
 struct ShadowPayload {
     f3 origin, direction, radiance;
     float distance;
 };
 
-template <int TYPE>
+// POWER (nxhip_set_light_sampling, NXHIP_LIGHTS_POWER): the triangle of the mesh-light sample comes from the light table (nx_lights.h) —
+// every emissive triangle of every mesh light in proportion to area x emitted luminance — with ONE random number in place of
+// the uniform triangle index, so a path draws as many numbers as in the default mode.  A template parameter, not a run-time
+// branch: the default mode's kernels are the instances with POWER = false, whose code does not change.
+template <int TYPE, bool POWER>
 NXD bool next_event_estimation(const DeviceState* S, f3 wi, const MatParams& mp, f3 hitPoint, f3 normal, f3 hitGNormal, f3 throughput,
                                uint32_t& rng, ShadowPayload& out)
 {
@@ -706,12 +709,26 @@ NXD bool next_event_estimation(const DeviceState* S, f3 wi, const MatParams& mp,
         out.distance = 1e30f;
         return true;
     }
-    const nx_light light = S->lights[pick];
-    if (light.type != NX_LIGHT_MESH) return false;
+    uint32_t meshId, triangleIdx, lightTriCount = 0u;
+    float pickProb = 0.0f;  // POWER: the table's probability of the entry
+    if constexpr (POWER) {
+        // (the uniform pick above only decided "a mesh light": which one, and which triangle, is the table's choice)
+        if (S->lightHeader->valid == 0u) return false;  // nothing emits: no light sample, no number drawn
+        const LightPick lp = light_pick(S->lightTable, S->lightGuide, S->lightGuideSize, S->lightEntries, rng_next(rng));
+        meshId = S->lights[lp.light].mesh.meshId;
+        triangleIdx = lp.entry - S->lightBase[lp.light];
+        pickProb = lp.prob;
+    } else {
+        const nx_light light = S->lights[pick];
+        if (light.type != NX_LIGHT_MESH) return false;
+        meshId = light.mesh.meshId;
+    }
     // the light's instance: its shading record (transform, triangles, material behind one load)
-    const NX_G ShadeInst* inst = &S->shadeInst[light.mesh.meshId];
-    const uint32_t lightTriCount = inst->triCount;
-    const uint32_t triangleIdx = uniform_index(lightTriCount, rng);
+    const NX_G ShadeInst* inst = &S->shadeInst[meshId];
+    if constexpr (!POWER) {
+        lightTriCount = inst->triCount;
+        triangleIdx = uniform_index(lightTriCount, rng);
+    }
     const f2 uv = uniform_triangle(rng);
     const NX_G nx_triangle* tri = shade_tri(inst->tris, triangleIdx);
     const f3 tp0 = ld3(tri->pos0), tp1 = ld3(tri->pos1), tp2 = ld3(tri->pos2);
@@ -737,7 +754,9 @@ NXD bool next_event_estimation(const DeviceState* S, f3 wi, const MatParams& mp,
     const float cosThetaO = fabsf(dot3(lightNormal, out.direction));
     const float dSquared = dot3(toLight, toLight);
     const float area = tri_area(mat_point(T, tp0), mat_point(T, tp1), mat_point(T, tp2));
-    float lightPdf = 1.0f / ((float)(nLights * lightTriCount) * area);
+    float lightPdf;
+    if constexpr (POWER) lightPdf = (pickProb * ((float)S->lightCount / (float)nLights)) / area;  // (lightCount / nLights: the pick fell on a mesh light)
+    else lightPdf = 1.0f / ((float)(nLights * lightTriCount) * area);
     lightPdf *= dSquared / cosThetaO;
     if (!pdf_valid(lightPdf)) return false;
 
@@ -764,7 +783,7 @@ NXD bool next_event_estimation(const DeviceState* S, f3 wi, const MatParams& mp,
 // (only read for an emissive hit under MIS).  emit(radiance, instance) receives what the hit emits towards the path; what comes out: the shadow ray of its
 // light sample, the continuation ray and the path state that goes with it.  (Separate references, not a struct: the
 // compiler kept a struct of these in scratch memory, +30 % on the material kernels.)
-template <int TYPE, class PrevOrigin, class Emit>
+template <int TYPE, bool POWER, class PrevOrigin, class Emit>
 NXD void shade_path(const DeviceState* S, const int bounce, const uint32_t frame, const uint32_t seedSlot, const uint32_t pixelIdx, const float hu, const float hv,
                     const uint32_t triIdx, const uint32_t instanceIdx, const f3 rayDirection, const float4 tpdf, PrevOrigin prevOrigin, Emit emit,
                     bool& wantShadow, ShadowPayload& sh, bool& wantTrace, bool& updatePath, f3& nextOrigin, f3& nextDir, f3& nextThroughput, float& nextPdf)
@@ -805,10 +824,24 @@ NXD void shade_path(const DeviceState* S, const int bounce, const uint32_t frame
             const float4 ro = prevOrigin();
             const float dSquared = squaref(length3(p - mk3(ro.x, ro.y, ro.z)));
             const float area = tri_area(mat_point(T, tp0), mat_point(T, tp1), mat_point(T, tp2));
-            float lightPdf = 1.0f / ((float)(nee_light_count(S) * inst->triCount) * area);
-            lightPdf *= dSquared / cosThetaO;
-            if (!pdf_valid(lightPdf)) weight = 0.0f;
-            else weight = power_heuristic(lastPdf, lightPdf);
+            if constexpr (POWER) {
+                // the density the light sample has for this point: the table's probability of this very triangle.  An instance that
+                // is no light, or an entry of probability 0: the sampler cannot reach it, BSDF sampling carries all of it (weight 1)
+                float P = 0.0f;
+                const uint32_t l = S->instLight[instanceIdx];
+                if (l != kNotALight && S->lightHeader->valid != 0u) P = light_entry_prob(S->lightTable, S->lightBase[l] + triIdx);
+                if (P > 0.0f) {
+                    float lightPdf = (P * ((float)S->lightCount / (float)nee_light_count(S))) / area;
+                    lightPdf *= dSquared / cosThetaO;
+                    if (!pdf_valid(lightPdf)) weight = 0.0f;
+                    else weight = power_heuristic(lastPdf, lightPdf);
+                }
+            } else {
+                float lightPdf = 1.0f / ((float)(nee_light_count(S) * inst->triCount) * area);
+                lightPdf *= dSquared / cosThetaO;
+                if (!pdf_valid(lightPdf)) weight = 0.0f;
+                else weight = power_heuristic(lastPdf, lightPdf);
+            }
         }
         radiance = ((emissive * weight) * material.intensity) * throughput;
     }
@@ -833,7 +866,7 @@ NXD void shade_path(const DeviceState* S, const int bounce, const uint32_t frame
             nextDir = wo;
             wantTrace = true;
         } else {
-            if (useMIS) wantShadow = next_event_estimation<TYPE>(S, wi, mp, p, normal, gNormal, throughput, rng, sh);
+            if (useMIS) wantShadow = next_event_estimation<TYPE, POWER>(S, wi, mp, p, normal, gNormal, throughput, rng, sh);
             float pdf;
             f3 sampleThroughput;
             if (Bsdf<TYPE>::sample(mp, wi, rng, wo, sampleThroughput, pdf)) {
@@ -854,7 +887,7 @@ NXD void shade_path(const DeviceState* S, const int bounce, const uint32_t frame
 // at 4 waves (126 VGPRs) for one large pass, +4.5 % for one-frame passes in flight, where a smaller register footprint lets
 // the material kernels of one slot share SIMDs with the trace waves of another.  6 and 8 waves per SIMD spill 30-87 VGPRs and
 // double the kernel's time: it is sensitive to memory traffic, not short of waves.
-template <int TYPE, bool ORDERED>
+template <int TYPE, bool ORDERED, bool POWER>
 #ifndef NX_SHADE_WAVES
 #define NX_SHADE_WAVES 5
 #endif
@@ -890,7 +923,7 @@ __global__ void __launch_bounds__(ORDERED ? kShadeBlockOrderedThreads : kShadeBl
             pixelIdx = __float_as_uint(hit.x);
             const uint32_t instanceIdx = __float_as_uint(dirInst.w);
             tpdf = bounce == 1 ? make_float4(1.0f, 1.0f, 1.0f, 1.0e10f) : mq.tp[at];
-            shade_path<TYPE>(S, bounce, frame, (uint32_t)requestIdx, pixelIdx, hit.y, hit.z, __float_as_uint(hit.w), instanceIdx, mk3(dirInst.x, dirInst.y, dirInst.z), tpdf,
+            shade_path<TYPE, POWER>(S, bounce, frame, (uint32_t)requestIdx, pixelIdx, hit.y, hit.z, __float_as_uint(hit.w), instanceIdx, mk3(dirInst.x, dirInst.y, dirInst.z), tpdf,
                              [&]() { return S->rayOrigin[pixelIdx]; },
                              [&](f3 emitted, uint32_t instIdx) {
                                  if (bounce == 1 && bounce != (int)S->settings.pathLength && pixelIdx < S->localCount && S->frame->pixelQueryPixel == (int)global_pixel(S, pixelIdx))
@@ -952,7 +985,7 @@ static_assert(kScanRing >= kShadeBlock + 4 * kShadeBlock && (kScanRing & (kScanR
 // from `staticTiles` on are handed out by ticket — one returning atomic per tile on the region's own word.  The share of a tile
 // that is this type's to shade varies from none to all with what the camera sees there, so a static split leaves most workgroups
 // waiting for the few whose tiles were full (measured: +40 % on the kernels).
-template <int TYPE>
+template <int TYPE, bool POWER>
 NXD void shade_scan_type(const DeviceState* __restrict__ S, const int bounce, const bool dropEnded, const int region, const int inRegion, const int per, const int firstTile,
                          const int staticTiles, int* const sRing, int* const sHead, int* const sTicket)
 {
@@ -1034,7 +1067,7 @@ NXD void shade_scan_type(const DeviceState* __restrict__ S, const int bounce, co
             // ... and the path's previous vertex, for hits that can need it (keep_previous_vertex)
             const uint32_t typeAndFlag = *(const NX_G uint32_t*)((const NX_G char*)&S->shadeInst[instanceIdx].material + kMaterialTypeOffset);
             if ((typeAndFlag >> 8) & 1u) keep_previous_vertex(S, pixelIdx, in.rayO[at]);
-            shade_path<TYPE>(S, bounce, frame, (uint32_t)at, pixelIdx, hit.y, hit.z, __float_as_uint(hit.w), instanceIdx, mk3(dirPix.x, dirPix.y, dirPix.z), tpdf,
+            shade_path<TYPE, POWER>(S, bounce, frame, (uint32_t)at, pixelIdx, hit.y, hit.z, __float_as_uint(hit.w), instanceIdx, mk3(dirPix.x, dirPix.y, dirPix.z), tpdf,
                              [&]() { return S->rayOrigin[pixelIdx]; },
                              [&](f3 emitted, uint32_t instIdx) {
                                  if (bounce == 1 && bounce != (int)S->settings.pathLength && pixelIdx < S->localCount && S->frame->pixelQueryPixel == (int)global_pixel(S, pixelIdx))
@@ -1148,6 +1181,7 @@ NXD void shade_scan_type(const DeviceState* __restrict__ S, const int bounce, co
 // workgroups start on different types (rank modulo the number of types) and move on to the next type when theirs has no tile
 // left, so the types run side by side, the launch ends when the last tile of the last type does, and a bounce costs one material
 // launch instead of one per type (the reference: four, PathTracer.cpp:116-120).  A single-bit mask is a per-type launch.
+template <bool POWER>  // (the light sample's mode: next_event_estimation)
 __global__ void __launch_bounds__(kShadeBlock, NX_SHADE_WAVES) shade_scan_kernel(const DeviceState* __restrict__ S, const int bounceArg, const int typeMask)
 {
     const int bounce = bounceArg & 0xff;
@@ -1182,11 +1216,11 @@ __global__ void __launch_bounds__(kShadeBlock, NX_SHADE_WAVES) shade_scan_kernel
         const int starters = (ranks - want + nTypes - 1) / nTypes;  // workgroups whose first type this is: each takes the tile of its index
         const int first = step == 0 ? myIndex : -1;
         switch (type) {
-        case NX_MAT_DIFFUSE: shade_scan_type<NX_MAT_DIFFUSE>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket); break;
-        case NX_MAT_PLASTIC: shade_scan_type<NX_MAT_PLASTIC>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket); break;
-        case NX_MAT_DIELECTRIC: shade_scan_type<NX_MAT_DIELECTRIC>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket); break;
-        case NX_MAT_CONDUCTOR: shade_scan_type<NX_MAT_CONDUCTOR>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket); break;
-        case kScanMiss: shade_scan_type<kScanMiss>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket); break;
+        case NX_MAT_DIFFUSE: shade_scan_type<NX_MAT_DIFFUSE, POWER>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket); break;
+        case NX_MAT_PLASTIC: shade_scan_type<NX_MAT_PLASTIC, POWER>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket); break;
+        case NX_MAT_DIELECTRIC: shade_scan_type<NX_MAT_DIELECTRIC, POWER>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket); break;
+        case NX_MAT_CONDUCTOR: shade_scan_type<NX_MAT_CONDUCTOR, POWER>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket); break;
+        case kScanMiss: shade_scan_type<kScanMiss, POWER>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket); break;
         default: break;
         }
     }
@@ -1217,6 +1251,7 @@ __global__ void __launch_bounds__(kWideBlock) count_scan_kernel(const DeviceStat
 #ifndef NX_TAIL_REFILL_BELOW
 #define NX_TAIL_REFILL_BELOW 40
 #endif
+template <bool POWER>  // (the light sample's mode: next_event_estimation)
 __global__ void __launch_bounds__(kTraceBlock) tail_kernel(const DeviceState* __restrict__ S, const int firstBounceArg)
 {
     // firstBounce | kTraceScanFlag: the pass ran the SCAN pipeline so far — the rays of trace(firstBounce - 1) are in the set of
@@ -1301,20 +1336,20 @@ __global__ void __launch_bounds__(kTraceBlock) tail_kernel(const DeviceState* __
         };
         if (__ballot(alive && type == NX_MAT_DIFFUSE) != 0ull) {
             if (alive && type == NX_MAT_DIFFUSE)
-                shade_path<NX_MAT_DIFFUSE>(S, bounce, frame, (uint32_t)index, pixelIdx, hu, hv, tri, inst, dir, tp, prevOrigin, emit, wantShadowRay, sh, wantTrace, updatePath, nextOrigin, nextDir, nextThroughput, nextPdf);
+                shade_path<NX_MAT_DIFFUSE, POWER>(S, bounce, frame, (uint32_t)index, pixelIdx, hu, hv, tri, inst, dir, tp, prevOrigin, emit, wantShadowRay, sh, wantTrace, updatePath, nextOrigin, nextDir, nextThroughput, nextPdf);
         }
         if (__ballot(alive && type == NX_MAT_PLASTIC) != 0ull) {
             if (alive && type == NX_MAT_PLASTIC)
-                shade_path<NX_MAT_PLASTIC>(S, bounce, frame, (uint32_t)index, pixelIdx, hu, hv, tri, inst, dir, tp, prevOrigin, emit, wantShadowRay, sh, wantTrace, updatePath, nextOrigin, nextDir, nextThroughput, nextPdf);
+                shade_path<NX_MAT_PLASTIC, POWER>(S, bounce, frame, (uint32_t)index, pixelIdx, hu, hv, tri, inst, dir, tp, prevOrigin, emit, wantShadowRay, sh, wantTrace, updatePath, nextOrigin, nextDir, nextThroughput, nextPdf);
         }
         if (__ballot(alive && type == NX_MAT_DIELECTRIC) != 0ull) {
             if (alive && type == NX_MAT_DIELECTRIC)
-                shade_path<NX_MAT_DIELECTRIC>(S, bounce, frame, (uint32_t)index, pixelIdx, hu, hv, tri, inst, dir, tp, prevOrigin, emit, wantShadowRay, sh, wantTrace, updatePath, nextOrigin, nextDir, nextThroughput, nextPdf);
+                shade_path<NX_MAT_DIELECTRIC, POWER>(S, bounce, frame, (uint32_t)index, pixelIdx, hu, hv, tri, inst, dir, tp, prevOrigin, emit, wantShadowRay, sh, wantTrace, updatePath, nextOrigin, nextDir, nextThroughput, nextPdf);
         }
         if (__ballot(alive && type == NX_MAT_CONDUCTOR) != 0ull) {
             if (alive && type == NX_MAT_CONDUCTOR) {
                 if (S->conductorMode == NX_CONDUCTOR_EXTENDED)
-                    shade_path<NX_MAT_CONDUCTOR>(S, bounce, frame, (uint32_t)index, pixelIdx, hu, hv, tri, inst, dir, tp, prevOrigin, emit, wantShadowRay, sh, wantTrace, updatePath, nextOrigin, nextDir, nextThroughput, nextPdf);
+                    shade_path<NX_MAT_CONDUCTOR, POWER>(S, bounce, frame, (uint32_t)index, pixelIdx, hu, hv, tri, inst, dir, tp, prevOrigin, emit, wantShadowRay, sh, wantTrace, updatePath, nextOrigin, nextDir, nextThroughput, nextPdf);
                 else alive = false;  // (the reference's graph has no conductor kernel: such a path ends unshaded)
             }
         }
@@ -1457,18 +1492,19 @@ const void* logic_kernel_ptr(int items)
 }
 
 // (the classic pipeline — logic kernel and per-type material kernels — runs under the ordered compaction only: see frame_levels)
-const void* shade_kernel_ptr(int type)
+// (lightPower: the variants only the pass graphs of NXHIP_LIGHTS_POWER launch — nxhip_api.hip pass_flavor)
+const void* shade_kernel_ptr(int type, bool lightPower)
 {
     switch (type) {
-    case NX_MAT_DIFFUSE: return (const void*)shade_kernel<NX_MAT_DIFFUSE, true>;
-    case NX_MAT_DIELECTRIC: return (const void*)shade_kernel<NX_MAT_DIELECTRIC, true>;
-    case NX_MAT_PLASTIC: return (const void*)shade_kernel<NX_MAT_PLASTIC, true>;
-    default: return (const void*)shade_kernel<NX_MAT_CONDUCTOR, true>;
+    case NX_MAT_DIFFUSE: return lightPower ? (const void*)shade_kernel<NX_MAT_DIFFUSE, true, true> : (const void*)shade_kernel<NX_MAT_DIFFUSE, true, false>;
+    case NX_MAT_DIELECTRIC: return lightPower ? (const void*)shade_kernel<NX_MAT_DIELECTRIC, true, true> : (const void*)shade_kernel<NX_MAT_DIELECTRIC, true, false>;
+    case NX_MAT_PLASTIC: return lightPower ? (const void*)shade_kernel<NX_MAT_PLASTIC, true, true> : (const void*)shade_kernel<NX_MAT_PLASTIC, true, false>;
+    default: return lightPower ? (const void*)shade_kernel<NX_MAT_CONDUCTOR, true, true> : (const void*)shade_kernel<NX_MAT_CONDUCTOR, true, false>;
     }
 }
-const void* shade_scan_kernel_ptr() { return (const void*)shade_scan_kernel; }
+const void* shade_scan_kernel_ptr(bool lightPower) { return lightPower ? (const void*)shade_scan_kernel<true> : (const void*)shade_scan_kernel<false>; }
 const void* count_scan_kernel_ptr() { return (const void*)count_scan_kernel; }
-const void* tail_kernel_ptr() { return (const void*)tail_kernel; }
+const void* tail_kernel_ptr(bool lightPower) { return lightPower ? (const void*)tail_kernel<true> : (const void*)tail_kernel<false>; }
 const void* begin_frame_kernel_ptr() { return (const void*)begin_frame_kernel; }
 const void* hook_sizes_kernel_ptr() { return (const void*)hook_sizes_kernel; }
 const void* generate_kernel_ptr() { return (const void*)generate_kernel; }

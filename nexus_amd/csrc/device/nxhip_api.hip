@@ -17,10 +17,10 @@
 namespace nxd {
 
 const void* trace_kernel_ptr(bool anyHit, bool stats);
-const void* tail_kernel_ptr();
+const void* tail_kernel_ptr(bool lightPower);
 const void* logic_kernel_ptr(int items);
-const void* shade_kernel_ptr(int type);
-const void* shade_scan_kernel_ptr();
+const void* shade_kernel_ptr(int type, bool lightPower);
+const void* shade_scan_kernel_ptr(bool lightPower);
 const void* count_scan_kernel_ptr();
 const void* inst_code_kernel_ptr();
 const void* entry_state_kernel_ptr();
@@ -48,6 +48,11 @@ const void* adaptive_decide_kernel_ptr();
 const void* adaptive_scan_kernel_ptr();
 const void* adaptive_fill_kernel_ptr();
 uint64_t layout_stamp_adaptive();
+int light_scan_bytes(size_t entries, size_t* bytes);
+int light_map_mean(hipStream_t st, const TextureDev& t, const float* srgbLut, float* mean4);
+int light_table_build(hipStream_t st, const LightBuild& b, void* scanTemp, size_t scanBytes);
+const void* light_pick_kernel_ptr();
+uint64_t layout_stamp_lights();
 const void* bsdf_hook_kernel_ptr();
 const void* fmath_hook_kernel_ptr();
 const void* tex2d_hook_kernel_ptr();
@@ -139,7 +144,7 @@ static int check_layouts()
     const struct { const char* unit; uint64_t stamp; } units[] = {
         {"nx_trace.hip", layout_stamp_trace()}, {"nx_wavefront.hip", layout_stamp_wavefront()}, {"nx_refit.hip", layout_stamp_refit()},
         {"nx_lbvh.hip", layout_stamp_lbvh()}, {"nxhip_multigpu.hip", layout_stamp_multigpu()}, {"nx_entry.hip", layout_stamp_entry()}, {"nx_aov.hip", layout_stamp_aov()},
-        {"nx_adaptive.hip", layout_stamp_adaptive()},
+        {"nx_adaptive.hip", layout_stamp_adaptive()}, {"nx_lights.hip", layout_stamp_lights()},
     };
     for (const auto& u : units) {
         if (u.stamp != layout_stamp()) {
@@ -663,8 +668,11 @@ int nxhip_create(int device, uint32_t width, uint32_t height, void* stream, nxhi
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, trace_kernel_ptr(true, false), kTraceBlockThreads, 0) != hipSuccess || perCU < 1) perCU = 4;
         c->shadowBlocks = std::max(1, perCU) * c->numCUs;
         c->wideBlocks = 8 * c->numCUs;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, tail_kernel_ptr(), kTraceBlockThreads, 0) != hipSuccess || perCU < 1) perCU = 2;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, tail_kernel_ptr(false), kTraceBlockThreads, 0) != hipSuccess || perCU < 1) perCU = 2;
         c->tailBlocks = std::max(1, perCU) * c->numCUs;
+        // (the POWER instance of the tail kernel fills the chip by its OWN occupancy: the default mode's grid does not depend on it)
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, tail_kernel_ptr(true), kTraceBlockThreads, 0) != hipSuccess || perCU < 1) perCU = 2;
+        c->tailBlocksPower = std::max(1, perCU) * c->numCUs;
         // Launch-geometry knobs of the measurement sweeps.  They are read only when NX_TUNING_KNOBS=1 says
         // that a sweep is running: a stray variable in a user's environment does not reconfigure the product.
         if (const char* on = std::getenv("NX_TUNING_KNOBS"); on && std::atoi(on) == 1) {
@@ -1325,6 +1333,7 @@ try {
     c->h.instanceCount = instanceCount;
     c->stateDirty = true;
     c->shadeInstDirty = true;
+    c->lightTableDirty = true;
     {
         // schedule of the device-side refit (nxhip_set_instance_transforms): node indices grouped by depth, deepest first
         std::vector<uint32_t> depth(nodeCount, 0u);
@@ -1496,6 +1505,7 @@ try {
     // documented guarantee — wait, the call is not on the per-frame path
     NX_SYNC_ALL(c);
     for (uint32_t i = 0; i < count; i++) std::memcpy(c->hostInstances[instanceIds[i]].transform.cell, transforms16 + 16 * (size_t)i, 64);
+    c->lightTableDirty = true;  // (a scale changes areas)
     // The kernel has set each moved record's identity flag from the inverse it computed.  The scene-wide "no instance transforms
     // a ray" flag is the host's to keep: it survives only if every new matrix is the identity itself (whose inverse, by the
     // cofactor formula, is the identity bit for bit).
@@ -1605,6 +1615,7 @@ static int update_blas(nxhip_ctx* c, int32_t blasId, const void* tris, uint32_t 
     b.rootKnown = false;  // (read again by whoever next needs the host copy: refresh_inst_trav)
     b.refreshPending = true;
     c->blasRefreshPending = true;
+    c->lightTableDirty = true;
     // a pageable host array: see nxhip_set_instance_transforms
     if (!fromDevice) NX_HIP(hipStreamSynchronize(c->stream));
     return NXHIP_OK;
@@ -1666,6 +1677,7 @@ try {
     c->hostMaterialsDev = dev;
     c->stateDirty = true;
     c->shadeInstDirty = true;  // (the records hold a copy of their instance's material)
+    c->lightTableDirty = true;
     uint32_t mask = 0u;
     for (const nx_material& m : dev)
         if (m.type >= 0 && m.type <= 3) mask |= 1u << m.type;
@@ -1690,6 +1702,7 @@ try {
     c->h.lights = c->lights.as<nx_light>();
     c->h.lightCount = count;
     c->stateDirty = true;
+    c->lightTableDirty = true;
     return NXHIP_OK;
 } catch (const std::exception& e) {  // nothing may unwind through the C boundary
     set_error(std::string("nxhip_set_lights: ") + e.what());
@@ -1820,7 +1833,7 @@ try {
     NX_HIP(hipMemcpy(t.texels.p, rgba8, (size_t)width * height * 4, hipMemcpyHostToDevice));
     int32_t id = 0;
     if (kind == 0) { c->diffuseMaps.push_back(std::move(t)); id = (int32_t)c->diffuseMaps.size() - 1; }
-    else if (kind == 1) { c->emissiveMaps.push_back(std::move(t)); id = (int32_t)c->emissiveMaps.size() - 1; }
+    else if (kind == 1) { c->emissiveMaps.push_back(std::move(t)); id = (int32_t)c->emissiveMaps.size() - 1; c->lightTableDirty = true; }
     else {
         NX_SYNC_ALL(c);
         c->hdrMap = std::move(t);
@@ -1842,6 +1855,8 @@ try {
     NX_SYNC_ALL(c);
     c->diffuseMaps.clear();
     c->emissiveMaps.clear();
+    c->lightMapMeans = 0;
+    c->lightTableDirty = true;
     c->hdrMap = TextureHost();
     c->hostHdr.clear();
     c->envSampling = false;
@@ -1990,6 +2005,14 @@ static int check_scene_ready(nxhip_ctx* c)
     }
     for (const nx_light& l : c->hostLights)
         if (l.type == NX_LIGHT_MESH && l.mesh.meshId >= c->hostInstances.size()) return fail_invalid("a mesh light refers to an instance that does not exist");
+    if (c->lightSampling == NXHIP_LIGHTS_POWER) {  // an instance has ONE place in the light table (DeviceState::instLight)
+        std::vector<bool> seen(c->hostInstances.size(), false);
+        for (const nx_light& l : c->hostLights) {
+            if (l.type != NX_LIGHT_MESH) continue;
+            if (seen[l.mesh.meshId]) return fail_invalid("NXHIP_LIGHTS_POWER: the light list names one instance twice");
+            seen[l.mesh.meshId] = true;
+        }
+    }
     return NXHIP_OK;
 }
 
@@ -2120,7 +2143,7 @@ int tail_bounce(const nxhip_ctx* c)
 // kernel is in the graph only for a scene with an environment map or a background that is not exactly black — PathTracer.cu:
 // 152-164 adds throughput x background, and +0 changes nothing), and the logic kernel's variant (one item per thread under an
 // environment map).  Part of a graph instance's key, so a change of any of them picks or builds the matching instance.
-constexpr int kFlavorScan = 1, kFlavorMissKernel = 2, kFlavorEnvMap = 4, kFlavorEntry = 8, kFlavorThin = 16, kFlavorDropEnded = 32, kFlavorAov = 64;
+constexpr int kFlavorScan = 1, kFlavorMissKernel = 2, kFlavorEnvMap = 4, kFlavorEntry = 8, kFlavorThin = 16, kFlavorDropEnded = 32, kFlavorAov = 64, kFlavorLightPower = 128;
 int pass_flavor(const nxhip_ctx* c)
 {
     int f = 0;
@@ -2139,6 +2162,7 @@ int pass_flavor(const nxhip_ctx* c)
     // dropped by code 0, its miss adds a black background no kernel is launched for — so the material launch does not queue it
     // (kShadeDropEnded).  Pixel-keyed random numbers only: a slot-keyed draw needs the slot the ray goes to.
     if (scan_pipeline(c) && !(f & kFlavorMissKernel) && c->h.rngMode == NX_RNG_PIXEL_KEYED) f |= kFlavorDropEnded;
+    if (c->lightSampling == NXHIP_LIGHTS_POWER) f |= kFlavorLightPower;  // (the material kernels' POWER variants: a graph of one mode is never replayed in the other)
     if (c->aov) f |= kFlavorAov;  // (one more branch beside the bounce-1 material step: frame_levels)
     if (c->entryPoints) f |= kFlavorEntry;  // (the slot's table exists before its graph is asked for: ensure_entry_table)
     // The thin kernel (nx_trace.hip) pays when ONE pass runs at a time: the lanes a dry wave leaves idle are then idle SIMD time, and
@@ -2163,6 +2187,7 @@ std::vector<std::vector<Launch>> frame_levels(nxhip_ctx* c, PassSlot* q)
     std::vector<std::vector<Launch>> levels;
     levels.push_back({make_launch(generate_kernel_ptr(), wide, wideThreads, NXHIP_K_GENERATE, S)});
     const bool entry = (pass_flavor(c) & kFlavorEntry) != 0;
+    const bool lightPower = (pass_flavor(c) & kFlavorLightPower) != 0;
     if (entry) {  // beside the generate kernel: the entry states of the primary rays' runs (nx_entry.hip), read by the launch below
         // (table and count come from the slot's DeviceState: a graph node holds no pointer that a re-allocation could leave dangling)
         // (eight lanes per run: a workgroup of 64 walks eight runs)
@@ -2216,14 +2241,14 @@ std::vector<std::vector<Launch>> frame_levels(nxhip_ctx* c, PassSlot* q)
         const int tailFrom = tail_bounce(c);
         for (int bounce = 1; bounce <= pathLength; bounce++) {
             if (bounce == tailFrom) {  // the rest of the pass in one launch
-                levels.push_back({make_launch(tail_kernel_ptr(), c->tailBlocks, kTraceBlockThreads, NXHIP_K_SHADE, S, bounce | kTraceScanFlag)});
+                levels.push_back({make_launch(tail_kernel_ptr(lightPower), lightPower ? c->tailBlocksPower : c->tailBlocks, kTraceBlockThreads, NXHIP_K_SHADE, S, bounce | kTraceScanFlag)});
                 break;
             }
             int mask = (int)(c->materialTypeMask & 0xfu);
             if (c->h.conductorMode != NX_CONDUCTOR_EXTENDED) mask &= ~(1 << NX_MAT_CONDUCTOR);
             if (mask == 0) mask = 1 << NX_MAT_DIFFUSE;  // (a level cannot be empty)
             if (misses) mask |= 1 << kScanMiss;
-            Launch shade = make_launch(shade_scan_kernel_ptr(), og, kShadeBlockThreads, NXHIP_K_SHADE, S, bounce | dropFlag);
+            Launch shade = make_launch(shade_scan_kernel_ptr(lightPower), og, kShadeBlockThreads, NXHIP_K_SHADE, S, bounce | dropFlag);
             shade.type = mask;
             shade.nargs = 3;
             levels.push_back({shade});
@@ -2250,11 +2275,11 @@ std::vector<std::vector<Launch>> frame_levels(nxhip_ctx* c, PassSlot* q)
         // graph insertion order of the reference: Diffuse, Plastic, Dielectric, Conductor (PathTracer.cpp:116-120)
         // (only the types some material of the scene has: a queue no material feeds stays empty)
         std::vector<Launch> shade;
-        if (in_use(NX_MAT_DIFFUSE)) shade.push_back(make_launch(shade_kernel_ptr(NX_MAT_DIFFUSE), og, ob, NXHIP_K_SHADE, S, bounce));
-        if (in_use(NX_MAT_PLASTIC)) shade.push_back(make_launch(shade_kernel_ptr(NX_MAT_PLASTIC), og, ob, NXHIP_K_SHADE, S, bounce));
-        if (in_use(NX_MAT_DIELECTRIC)) shade.push_back(make_launch(shade_kernel_ptr(NX_MAT_DIELECTRIC), og, ob, NXHIP_K_SHADE, S, bounce));
-        if (in_use(NX_MAT_CONDUCTOR) && c->h.conductorMode == NX_CONDUCTOR_EXTENDED) shade.push_back(make_launch(shade_kernel_ptr(NX_MAT_CONDUCTOR), og, ob, NXHIP_K_SHADE, S, bounce));
-        if (shade.empty()) shade.push_back(make_launch(shade_kernel_ptr(NX_MAT_DIFFUSE), og, ob, NXHIP_K_SHADE, S, bounce));  // (a level cannot be empty)
+        if (in_use(NX_MAT_DIFFUSE)) shade.push_back(make_launch(shade_kernel_ptr(NX_MAT_DIFFUSE, lightPower), og, ob, NXHIP_K_SHADE, S, bounce));
+        if (in_use(NX_MAT_PLASTIC)) shade.push_back(make_launch(shade_kernel_ptr(NX_MAT_PLASTIC, lightPower), og, ob, NXHIP_K_SHADE, S, bounce));
+        if (in_use(NX_MAT_DIELECTRIC)) shade.push_back(make_launch(shade_kernel_ptr(NX_MAT_DIELECTRIC, lightPower), og, ob, NXHIP_K_SHADE, S, bounce));
+        if (in_use(NX_MAT_CONDUCTOR) && c->h.conductorMode == NX_CONDUCTOR_EXTENDED) shade.push_back(make_launch(shade_kernel_ptr(NX_MAT_CONDUCTOR, lightPower), og, ob, NXHIP_K_SHADE, S, bounce));
+        if (shade.empty()) shade.push_back(make_launch(shade_kernel_ptr(NX_MAT_DIFFUSE, lightPower), og, ob, NXHIP_K_SHADE, S, bounce));  // (a level cannot be empty)
         // serial slot order needs the kernels one after the other
         for (auto& l : shade) levels.push_back({l});
         levels.push_back({make_launch(trace_kernel_ptr(false, stats), traceBlocks, kTraceBlockThreads, NXHIP_K_TRACE, S, bounce | thinFlag),
@@ -2424,6 +2449,102 @@ static int ensure_slot_events(PassSlot* q)
     return NXHIP_OK;
 }
 
+// NXHIP_LIGHTS_POWER: the light table (nx_lights.hip) brought up to date, once, before the next pass or hook call that reads it —
+// in the manner of refresh_updated_blas.  The shading records and the triangles it reads are current by then (the caller has run
+// refresh_shade_inst; transforms and refits are ahead of it in stream order).  The host knows the entry LAYOUT (lights, instances,
+// triangle counts) and re-allocates only when that changes; the weights never come back.  Nothing happens in the default mode.
+static int refresh_light_table(nxhip_ctx* c)
+{
+    if (c->lightSampling != NXHIP_LIGHTS_POWER || !c->lightTableDirty) return NXHIP_OK;
+    const size_t nLights = c->hostLights.size(), nInst = c->hostInstances.size();
+    std::vector<uint32_t> base(nLights + 1, 0u), instLight(std::max<size_t>(1, nInst), kNotALight);
+    uint64_t n = 0;
+    for (size_t l = 0; l < nLights; l++) {
+        base[l] = (uint32_t)n;
+        const nx_light& light = c->hostLights[l];
+        if (light.type != NX_LIGHT_MESH) continue;  // (no triangles: no entries)
+        const nx_bvh_instance& inst = c->hostInstances[light.mesh.meshId];
+        if (inst.bvhIdx >= c->blas.size()) return fail_invalid("instance refers to a BLAS id that has not been uploaded");
+        n += c->blas[inst.bvhIdx].triCount;
+        if (n >= 0xffffffffull) return fail_invalid("NXHIP_LIGHTS_POWER: the mesh lights have 2^32 triangles or more");
+        instLight[light.mesh.meshId] = (uint32_t)l;
+    }
+    base[nLights] = (uint32_t)n;
+    uint32_t guide = 1u;
+    while (guide < n && guide < kLightGuideMax) guide <<= 1;
+    int rc;
+    if (slot_count(c) > 1) NX_SYNC_ALL(c);  // passes on the other slots' streams still read the old table
+    if (!c->lightHeader.p || base != c->hostLightBase || instLight != c->hostInstLight) {
+        NX_SYNC_ALL(c);
+        NX_ALLOC(c->lightHeader, sizeof(LightHeader));
+        NX_ALLOC(c->lightBase, base.size() * 4);
+        NX_ALLOC(c->instLight, instLight.size() * 4);
+        NX_HIP(hipMemcpy(c->lightBase.p, base.data(), base.size() * 4, hipMemcpyHostToDevice));
+        NX_HIP(hipMemcpy(c->instLight.p, instLight.data(), instLight.size() * 4, hipMemcpyHostToDevice));
+        if ((uint32_t)n != c->lightEntries || !c->lightTable.p) {
+            size_t scanBytes = 0;
+            if ((rc = light_scan_bytes((size_t)std::max<uint64_t>(n, 1), &scanBytes)) != NXHIP_OK) return rc;
+            NX_ALLOC(c->lightTable, (size_t)std::max<uint64_t>(n, 1) * sizeof(LightEntry));
+            NX_ALLOC(c->lightWeight, (size_t)std::max<uint64_t>(n, 1) * sizeof(double));
+            NX_ALLOC(c->lightPrefix, (size_t)std::max<uint64_t>(n, 1) * sizeof(double));
+            NX_ALLOC(c->lightGuide, (size_t)guide * 4);
+            NX_ALLOC(c->lightScanTemp, std::max<size_t>(scanBytes, 16));
+            c->lightScanBytes = scanBytes;
+        }
+        c->lightEntries = (uint32_t)n;
+        c->lightGuideSize = guide;
+        c->hostLightBase.swap(base);
+        c->hostInstLight.swap(instLight);
+        c->h.lightTable = n ? c->lightTable.as<LightEntry>() : nullptr;
+        c->h.lightGuide = n ? c->lightGuide.as<uint32_t>() : nullptr;
+        c->h.lightBase = c->lightBase.as<uint32_t>();
+        c->h.instLight = c->instLight.as<uint32_t>();
+        c->h.lightHeader = c->lightHeader.as<LightHeader>();
+        c->h.lightEntries = c->lightEntries;
+        c->h.lightGuideSize = c->lightGuideSize;
+        c->stateDirty = true;
+        if ((rc = upload_state(c)) != NXHIP_OK) return rc;
+    }
+    if (c->lightEntries == 0u) {
+        NX_HIP(hipMemsetAsync(c->lightHeader.p, 0, sizeof(LightHeader), c->stream));  // valid = 0: no mesh-light samples
+    } else {
+        // the emissive maps' means, for the maps uploaded since the last build
+        const size_t maps = c->emissiveMaps.size();
+        if (c->lightMapMeans < maps) {
+            if (c->lightMapMeanCapacity < maps) {
+                NX_SYNC_ALL(c);
+                NX_ALLOC(c->lightMapMean, 2 * maps * 16);
+                c->lightMapMeanCapacity = 2 * maps;
+                c->lightMapMeans = 0;
+            }
+            for (size_t m = c->lightMapMeans; m < maps; m++) {
+                const TextureHost& th = c->emissiveMaps[m];
+                const TextureDev t{th.texels.as<uint32_t>(), th.width, th.height};
+                if ((rc = light_map_mean(c->stream, t, c->srgbLut.as<float>(), c->lightMapMean.as<float>() + 4 * m)) != NXHIP_OK) return rc;
+            }
+            c->lightMapMeans = maps;
+        }
+        LightBuild b{};
+        b.shadeInst = c->shadeInst.as<ShadeInst>();
+        b.lights = c->lights.as<nx_light>();
+        b.lightBase = c->lightBase.as<uint32_t>();
+        b.mapMean = c->lightMapMean.as<float>();
+        b.weight = c->lightWeight.as<double>();
+        b.prefix = c->lightPrefix.as<double>();
+        b.table = c->lightTable.as<LightEntry>();
+        b.guide = c->lightGuide.as<uint32_t>();
+        b.header = c->lightHeader.as<LightHeader>();
+        b.lightCount = (uint32_t)nLights;
+        b.entries = c->lightEntries;
+        b.guideSize = c->lightGuideSize;
+        if ((rc = light_table_build(c->stream, b, c->lightScanTemp.p, c->lightScanBytes)) != NXHIP_OK) return rc;
+    }
+    // passes on the other slots' streams must not start on a table half built
+    if (slot_count(c) > 1) NX_HIP(hipStreamSynchronize(c->stream));
+    c->lightTableDirty = false;
+    return NXHIP_OK;
+}
+
 extern "C" {
 
 // One pass of `frames` frames (0: the context's frames per pass) through the pixels of the pass set.
@@ -2456,6 +2577,7 @@ try {
     rc = upload_state(c);
     if (rc != NXHIP_OK) return rc;
     if ((rc = refresh_updated_blas(c)) != NXHIP_OK) return rc;  // (BLASes refitted since the last pass: nxhip_update_blas)
+    if ((rc = refresh_light_table(c)) != NXHIP_OK) return rc;   // (NXHIP_LIGHTS_POWER: lights, materials, instances or meshes changed)
     if (!slot_queues_ready(c, q)) {
         rc = ensure_slot_queues(c, q);
         if (rc != NXHIP_OK) return rc;
@@ -3584,6 +3706,92 @@ int nxhip_tex2d_batch(nxhip_ctx* c, int kind, int textureId, const float* uv, ui
     NX_SYNC_ALL(c);
     NX_HIP(hipMemcpy(rgba, dOut.p, (size_t)count * 16, hipMemcpyDeviceToHost));
     return NXHIP_OK;
+}
+
+int nxhip_set_light_sampling(nxhip_ctx* c, int mode)
+{
+    NX_CHECK_CTX(c);
+    if (mode != NXHIP_LIGHTS_UNIFORM && mode != NXHIP_LIGHTS_POWER) return fail_invalid("nxhip_set_light_sampling: unknown mode");
+    if (mode == c->lightSampling) return NXHIP_OK;
+    // (frames accumulated so far stay: the expectation is the same.  The pass graphs are keyed by the mode: pass_flavor)
+    c->lightSampling = mode;
+    c->lightTableDirty = true;
+    return NXHIP_OK;
+}
+
+// What a render does before its pass, for the hooks that read the light table
+static int light_table_ready(nxhip_ctx* c, const char* who)
+{
+    NX_CHECK_CTX(c);
+    if (c->lightSampling != NXHIP_LIGHTS_POWER) return fail_invalid(std::string(who) + ": the context is not in NXHIP_LIGHTS_POWER");
+    NX_HIP(hipSetDevice(c->device));
+    int rc = check_scene_ready(c);
+    if (rc != NXHIP_OK) return rc;
+    if (c->shadeInstDirty && (rc = refresh_shade_inst(c)) != NXHIP_OK) return rc;
+    if ((rc = upload_state(c)) != NXHIP_OK) return rc;
+    if ((rc = refresh_updated_blas(c)) != NXHIP_OK) return rc;
+    return refresh_light_table(c);
+}
+
+int nxhip_read_light_table(nxhip_ctx* c, float* cdf, uint32_t* entryLight, uint32_t capacity, uint32_t* lightBase, uint32_t* entries)
+try {
+    const int rc = light_table_ready(c, "nxhip_read_light_table");
+    if (rc != NXHIP_OK) return rc;
+    const uint32_t n = c->lightEntries;
+    if (entries) *entries = n;
+    if (lightBase) std::memcpy(lightBase, c->hostLightBase.data(), c->hostLightBase.size() * 4);
+    if (!cdf && !entryLight) return NXHIP_OK;
+    if (capacity < n) return fail_invalid("nxhip_read_light_table: destination too small");
+    std::vector<LightEntry> table(n);
+    NX_SYNC_ALL(c);
+    if (n) NX_HIP(hipMemcpy(table.data(), c->lightTable.p, (size_t)n * sizeof(LightEntry), hipMemcpyDeviceToHost));
+    for (uint32_t i = 0; i < n; i++) {
+        if (cdf) cdf[i] = table[i].cdf;
+        if (entryLight) entryLight[i] = table[i].light;
+    }
+    return NXHIP_OK;
+} catch (const std::exception& e) {  // nothing may unwind through the C boundary
+    set_error(std::string("nxhip_read_light_table: ") + e.what());
+    return NXHIP_ERR_INVALID;
+}
+
+int nxhip_light_pick_batch(nxhip_ctx* c, const float* u, uint32_t count, uint32_t* entry, float* prob)
+try {
+    NX_CHECK_CTX(c);
+    if ((!u || !entry || !prob) && count) return fail_invalid("nxhip_light_pick_batch: null buffer");
+    // before anything is launched: floor(u G) of a u outside [0, 1) — or of a NaN — is no index of the guide table
+    for (uint32_t k = 0; k < count; k++)
+        if (!(u[k] >= 0.0f && u[k] < 1.0f)) return fail_invalid("nxhip_light_pick_batch: u must be in [0, 1)");
+    const int rc = light_table_ready(c, "nxhip_light_pick_batch");
+    if (rc != NXHIP_OK) return rc;
+    if (count == 0) return NXHIP_OK;
+    if (c->lightEntries == 0u) return fail_invalid("nxhip_light_pick_batch: the light table is empty (no mesh light has a triangle)");
+    {   // a table whose weights sum to nothing is never sampled by the renderer (its cdf is a filler of ones): the hook refuses it too
+        LightHeader header{};
+        NX_SYNC_ALL(c);
+        NX_HIP(hipMemcpy(&header, c->lightHeader.p, sizeof header, hipMemcpyDeviceToHost));
+        if (header.valid == 0u) return fail_invalid("nxhip_light_pick_batch: the light table is invalid (the lights' weights sum to nothing): nothing can be picked");
+    }
+    DevBuf dU, dEntry, dProb;
+    NX_ALLOC(dU, (size_t)count * 4);
+    NX_ALLOC(dEntry, (size_t)count * 4);
+    NX_ALLOC(dProb, (size_t)count * 4);
+    NX_HIP(hipMemcpy(dU.p, u, (size_t)count * 4, hipMemcpyHostToDevice));
+    const LightEntry* table = c->lightTable.as<LightEntry>();
+    const uint32_t* guide = c->lightGuide.as<uint32_t>();
+    const uint32_t guideSize = c->lightGuideSize, entries = c->lightEntries;
+    const float* pu = dU.as<float>();
+    uint32_t* pe = dEntry.as<uint32_t>();
+    float* pp = dProb.as<float>();
+    void* args[8] = {(void*)&table, (void*)&guide, (void*)&guideSize, (void*)&entries, (void*)&pu, (void*)&count, (void*)&pe, (void*)&pp};
+    NX_HIP(hipLaunchKernel(light_pick_kernel_ptr(), dim3(c->wideBlocks), dim3(kWideBlockThreads), args, 0, c->stream));
+    NX_SYNC_ALL(c);
+    NX_HIP(hipMemcpy(entry, dEntry.p, (size_t)count * 4, hipMemcpyDeviceToHost));
+    NX_HIP(hipMemcpy(prob, dProb.p, (size_t)count * 4, hipMemcpyDeviceToHost));
+    return NXHIP_OK;
+} catch (const std::exception& e) {  // nothing may unwind through the C boundary
+    set_error(std::string("nxhip_light_pick_batch: ") + e.what());
+    return NXHIP_ERR_INVALID;
 }
 
 int nxhip_fmath_batch(nxhip_ctx* c, int op, const double* a, const double* b, uint32_t count, double* out)

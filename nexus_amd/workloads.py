@@ -45,6 +45,9 @@ def checker_texture(w=64, h=32, seed=0, alpha=False):
 
 
 class Workload:
+    # extension: pod.LIGHTS_POWER picks the mesh lights' triangles by area x emitted luminance (nxhip_set_light_sampling); applied by upload
+    light_sampling = pod.LIGHTS_UNIFORM
+
     def __init__(self, meshes, placements, materials=None, lights=None, camera=None, settings=None, diffuse_maps=(), emissive_maps=(),
                  hdr_map=None, build_threads=4):
         """meshes: list of TRI_DT arrays; placements: list of (meshIdx, materialId, transform16); build_threads 0 = all cores."""
@@ -115,6 +118,7 @@ class Workload:
         if self.camera is not None:
             ctx.set_camera(self.camera)
         ctx.set_render_settings(self.settings)
+        ctx.set_light_sampling(self.light_sampling)
 
 
 def _look(eye, target, hfov, width, height):
