@@ -79,6 +79,7 @@ struct TextureHost {
 
 struct KernelTimer {
     hipEvent_t start = nullptr, stop = nullptr;
+    int klass = 0;  // NXHIP_K_*: the kernel class the pair brackets
 };
 
 }  // namespace nxd
@@ -117,7 +118,7 @@ struct PassSlot {
     bool errorFresh = false;
     size_t pathCapacity = 0;  // paths this slot's queue buffers hold right now; 0: released (nxhip_ctx::queueCapacity is the nominal size)
     // Instances of the pass graph, one per SHAPE it has been asked for (see trace_blocks, tail_bounce, pass_flavor in
-    // nxhip_api.hip: a small pass, a large pass and a pass among several in flight are different graphs).  A pass of another
+    // nxhip_render.hip: a small pass, a large pass and a pass among several in flight are different graphs).  A pass of another
     // size class replays the instance built for that class instead of re-instantiating one inside the frame loop.
     struct GraphInstance {
         hipGraph_t graph = nullptr;
@@ -199,11 +200,9 @@ struct nxhip_ctx : nxd::PassSlot {
     bool timingEnabled = false;
     int timingMode = 0;  // 0 off, 1 eager launches with an event pair each, 2 / 3 event-record nodes inside the frame graph
     std::vector<nxd::KernelTimer> graphTimers;
-    std::vector<int> graphTimerClass;
     bool graphTimersPending = false;  // mode 3: the graph's events hold an unread replay
     nxhip_kernel_times times{};
-    std::vector<nxd::KernelTimer> timerPool;
-    std::vector<int> timerClass;  // kernel class of timerPool[i]
+    std::vector<nxd::KernelTimer> timerPool;  // eager launches (launch_now), resolved and emptied by nxhip_read_kernel_times
 
     // multi-GPU tile split (nxhip_multigpu.hip): RCCL communicator (opaque), root-side gather / full-image buffers
     void* mgpuComm = nullptr;
@@ -217,7 +216,7 @@ struct nxhip_ctx : nxd::PassSlot {
     int traceBlocks = 0, shadowBlocks = 0, wideBlocks = 0;  // full-chip persistent grids (see trace_blocks)
     int tailBlocks = 0;
     int tailBlocksPower = 0;  // grid of tail_kernel<true> (NXHIP_LIGHTS_POWER), from that instance's own occupancy
-    int tailBounce = -1;  // first bounce of the tail kernel, 0 = off, -1 = automatic (see tail_bounce in nxhip_api.hip)
+    int tailBounce = -1;  // first bounce of the tail kernel, 0 = off, -1 = automatic (see tail_bounce in nxhip_render.hip)
     bool traceGridForced = false;                            // NX_TRACE_BLOCKS_*: use them as they are
     int shadeBlocksPerCU = 10, logicBlocksPerCU = 2;  // grid-stride kernels: workgroups per CU
     // material types the scene's materials use (bit NX_MAT_*): a type no material has can never receive a queue item, so its

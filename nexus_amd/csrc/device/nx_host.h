@@ -1,0 +1,274 @@
+// nx_host.h — what the host units of the device layer (nxhip_*.hip) share, and what the kernel units export to them: the kernel
+// getters with their argument lists, typed launches, the builders' entry points (internal to the device layer).
+#pragma once
+
+#include <cstring>
+#include <type_traits>
+#include <vector>
+
+#include "nx_context.h"
+
+namespace nxd {
+
+// ---- what the kernel units export ---------------------------------------------------------------------
+// nx_lbvh.hip, nx_lights.hip and nxhip_multigpu.hip include this header, so the compiler checks their declarations against the
+// definitions.  The getters of the other kernel units are declared here as they are defined there (nx_trace.hip, nx_entry.hip
+// and nx_wavefront.hip cannot include it: their text is pinned by bench.py's source hash).
+const void* trace_kernel_ptr(bool anyHit, bool stats);  // nx_trace.hip
+const void* trace_entry_kernel_ptr();
+const void* thin_kernel_ptr();
+const void* entry_state_kernel_ptr();  // nx_entry.hip
+const void* tail_kernel_ptr(bool lightPower);  // nx_wavefront.hip
+const void* logic_kernel_ptr(int items);
+const void* shade_kernel_ptr(int type, bool lightPower);
+const void* shade_scan_kernel_ptr(bool lightPower);
+const void* count_scan_kernel_ptr();
+const void* begin_frame_kernel_ptr();
+const void* hook_sizes_kernel_ptr();
+const void* generate_kernel_ptr();
+const void* accumulate_kernel_ptr();
+const void* compose_kernel_ptr();
+const void* bsdf_hook_kernel_ptr();
+const void* fmath_hook_kernel_ptr();
+const void* tex2d_hook_kernel_ptr();
+const void* aov_kernel_ptr();  // nx_aov.hip
+const void* aov_fold_kernel_ptr();
+const void* denoise_gather_kernel_ptr();
+const void* denoise_iteration_kernel_ptr(int step, bool forceDirect);
+const void* adaptive_accumulate_kernel_ptr();  // nx_adaptive.hip
+const void* adaptive_aov_fold_kernel_ptr();
+const void* adaptive_decide_kernel_ptr();
+const void* adaptive_scan_kernel_ptr();
+const void* adaptive_fill_kernel_ptr();
+const void* light_pick_kernel_ptr();  // nx_lights.hip
+const void* inst_code_kernel_ptr();  // nx_refit.hip
+const void* instance_transform_kernel_ptr();
+const void* tlas_refit_kernel_ptr();
+const void* blas_refit_kernel_ptr();
+uint64_t layout_stamp_trace();
+uint64_t layout_stamp_wavefront();
+uint64_t layout_stamp_refit();
+uint64_t layout_stamp_lbvh();
+uint64_t layout_stamp_multigpu();
+uint64_t layout_stamp_entry();
+uint64_t layout_stamp_aov();
+uint64_t layout_stamp_adaptive();
+uint64_t layout_stamp_lights();
+uint64_t layout_stamp_scene();  // the host units nxhip_*.hip that fill DeviceState, each its own
+uint64_t layout_stamp_render();
+uint64_t layout_stamp_features();
+uint64_t layout_stamp_hooks();
+int light_scan_bytes(size_t entries, size_t* bytes);
+int light_map_mean(hipStream_t st, const TextureDev& t, const float* srgbLut, float* mean4);
+int light_table_build(hipStream_t st, const LightBuild& b, void* scanTemp, size_t scanBytes);
+int lbvh_build(nxhip_ctx* c, const nx_triangle* dTris, uint32_t n, int plocRadius, DevBuf& nodes, DevBuf& primIdx, DevBuf& isect, uint32_t* nodeCount);
+int lbvh_build_batch(nxhip_ctx* c, const nx_triangle* dTris, const std::vector<uint32_t>& counts, DevBuf& nodes, DevBuf& primIdx, DevBuf& isect, std::vector<uint32_t>& nodeFirst,
+                     std::vector<uint32_t>& nodeCounts);
+int lbvh_write_isect(nxhip_ctx* c, const nx_triangle* dTris, const uint32_t* dPrimIdx, uint32_t n, float4* dIsect);
+int lbvh_build_tlas(nxhip_ctx* c, const nx_bvh_instance* dInstances, uint32_t n, int plocRadius, DevBuf& nodes, DevBuf& primIdx, DevBuf& box, bool* boxesAreTight, uint32_t* nodeCount);
+
+// Threads per workgroup of the kernels the host sizes grids for.  NX_TRACE_BLOCK / NX_SHADE_BLOCK / NX_LOGIC_BLOCK are build knobs
+// given on the command line of the WHOLE library (nx_traverse.h, nx_wavefront.hip hold their defaults and define the macros; this
+// header defines none, only repeats the defaults).
+#ifdef NX_TRACE_BLOCK
+constexpr int kTraceBlockThreads = NX_TRACE_BLOCK;
+#else
+constexpr int kTraceBlockThreads = 256;
+#endif
+#ifdef NX_SHADE_BLOCK
+constexpr int kShadeBlockThreads = NX_SHADE_BLOCK;
+#else
+constexpr int kShadeBlockThreads = 256;
+#endif
+#ifdef NX_LOGIC_BLOCK
+constexpr int kLogicBlockThreads = NX_LOGIC_BLOCK;
+#else
+constexpr int kLogicBlockThreads = 1024;
+#endif
+constexpr int kWideBlockThreads = 256;
+constexpr int kHookBounceSlot = NX_PATH_MAX_LENGTH - 1;  // queue-size slot used by the batch test hooks
+
+// ---- typed launches ------------------------------------------------------------------------------------
+// A kernel with its parameter list: the one place that says what a launch of it must pass.  make_launch / launch_untimed take
+// exactly these types (converting at the call site), so a call that does not fit the list does not compile.
+template <class... A> struct Kernel { const void* fn; };
+
+// The parameter lists, each read against the kernel's __global__ definition.  (Pointers to structures private to nx_refit.hip —
+// InstBox, Box, NodeBox32 — are stated as void*: the same 8 bytes.)
+namespace kernels {
+using State = const DeviceState*;
+using U32 = uint32_t;
+using StateKernel = Kernel<State>;            // (S)
+using BounceKernel = Kernel<State, int>;      // (S, bounce | flags)
+using TypeKernel = Kernel<State, int, int>;   // (S, bounce | flags, type or type mask)
+inline BounceKernel trace(bool anyHit, bool stats) { return {trace_kernel_ptr(anyHit, stats)}; }
+inline BounceKernel trace_entry() { return {trace_entry_kernel_ptr()}; }
+inline BounceKernel thin() { return {thin_kernel_ptr()}; }
+inline StateKernel entry_state() { return {entry_state_kernel_ptr()}; }
+inline BounceKernel tail(bool lightPower) { return {tail_kernel_ptr(lightPower)}; }
+inline BounceKernel logic(int items) { return {logic_kernel_ptr(items)}; }
+inline BounceKernel shade(int type, bool lightPower) { return {shade_kernel_ptr(type, lightPower)}; }
+inline TypeKernel shade_scan(bool lightPower) { return {shade_scan_kernel_ptr(lightPower)}; }
+inline TypeKernel count_scan() { return {count_scan_kernel_ptr()}; }
+inline Kernel<DeviceState*, U32, U32, U32> begin_frame() { return {begin_frame_kernel_ptr()}; }  // (S, frames, frameLast, scanEpoch)
+inline Kernel<DeviceState*, U32, int, int> hook_sizes() { return {hook_sizes_kernel_ptr()}; }    // (S, n, anyHit, slot)
+inline StateKernel generate() { return {generate_kernel_ptr()}; }
+// (S, src, count, slices, sliceStride, firstFrame, dstMap)
+inline Kernel<State, const float4*, U32, U32, U32, U32, const U32*> accumulate() { return {accumulate_kernel_ptr()}; }
+inline Kernel<const float4*, U32, const U32*, float4*, U32*> compose() { return {compose_kernel_ptr()}; }  // (src, count, dstMap, dstAccum, dstRgba8)
+inline Kernel<const nx_material*, const nx_bsdf_query*, U32, int, nx_bsdf_result*> bsdf_hook() { return {bsdf_hook_kernel_ptr()}; }  // (material, q, count, sample, out)
+inline Kernel<int, const double*, const double*, U32, double*> fmath_hook() { return {fmath_hook_kernel_ptr()}; }                   // (op, a, b, count, out)
+inline Kernel<TextureDev, const float*, const float*, U32, float4*> tex2d_hook() { return {tex2d_hook_kernel_ptr()}; }              // (t, srgbLut, uv, count, out)
+inline StateKernel aov() { return {aov_kernel_ptr()}; }
+inline StateKernel aov_fold() { return {aov_fold_kernel_ptr()}; }
+inline Kernel<State, float4*, float4*, float4*, U32*> denoise_gather() { return {denoise_gather_kernel_ptr()}; }  // (S, colour, albedo, normalDepth, rgba8)
+inline Kernel<DenoiseLaunch> denoise_iteration(int step, bool forceDirect) { return {denoise_iteration_kernel_ptr(step, forceDirect)}; }
+inline StateKernel adaptive_accumulate() { return {adaptive_accumulate_kernel_ptr()}; }
+inline StateKernel adaptive_aov_fold() { return {adaptive_aov_fold_kernel_ptr()}; }
+inline Kernel<AdaptiveLaunch> adaptive_decide() { return {adaptive_decide_kernel_ptr()}; }
+inline Kernel<AdaptiveLaunch> adaptive_scan() { return {adaptive_scan_kernel_ptr()}; }
+inline Kernel<AdaptiveLaunch> adaptive_fill() { return {adaptive_fill_kernel_ptr()}; }
+// (table, guide, guideSize, entries, u, count, entry, prob)
+inline Kernel<const LightEntry*, const U32*, U32, U32, const float*, U32, U32*, float*> light_pick() { return {light_pick_kernel_ptr()}; }
+inline Kernel<State, InstTrav*, const ShadeInst*, U32> inst_code() { return {inst_code_kernel_ptr()}; }  // (S, trav, shadeInst, count)
+// (S, instances, trav, leafOfInstance, ids, transforms, count, tightBoxes, shadeInst, blasRefresh)
+inline Kernel<State, nx_bvh_instance*, InstTrav*, const U32*, const U32*, const float*, U32, void*, ShadeInst*, U32> instance_transform() { return {instance_transform_kernel_ptr()}; }
+// (nodes, primIdx, instances, order, levelStart, levels, nodeBox, tightBoxes)
+inline Kernel<nx_bvh8_node*, const U32*, const nx_bvh_instance*, const U32*, const U32*, U32, void*, const void*> tlas_refit() { return {tlas_refit_kernel_ptr()}; }
+// (nodes, triIdx, tris, order, levelStart, firstLevel, levelCount, nodeBox)
+inline Kernel<uint4*, const U32*, const nx_triangle*, const U32*, const U32*, U32, U32, void*> blas_refit() { return {blas_refit_kernel_ptr()}; }
+}  // namespace kernels
+
+constexpr size_t arg_end(size_t at, size_t size, size_t align) { return (at + align - 1) / align * align + size; }
+template <class... A> constexpr size_t args_bytes()
+{
+    size_t at = 0;
+    ((at = arg_end(at, sizeof(A), alignof(A))), ...);
+    return at;
+}
+
+// One kernel launch of a pass, kept until it is issued (launch_now) or becomes a graph node (pass_graph).  The argument VALUES live
+// in `bytes`, each at its `offset`: a Launch is copied into vectors between construction and use, so it holds no pointer into
+// itself — params() makes the void* array at the moment of the HIP call, which copies the values out during the call.
+struct Launch {
+    static constexpr size_t kMaxArgs = 8, kArgBytes = sizeof(DenoiseLaunch);  // the largest block any kernel of a pass takes
+    const void* fn = nullptr;
+    dim3 grid, block;
+    int klass = 0;   // NXHIP_K_*
+    int after = -1;  // -1: depends on the previous level; k: on launch k of ITS OWN level only (a chain inside the level)
+    uint8_t argCount = 0, offset[kMaxArgs] = {};
+    alignas(8) unsigned char bytes[kArgBytes] = {};
+    void params(void** out) const
+    {
+        for (int i = 0; i < argCount; i++) out[i] = const_cast<unsigned char*>(bytes) + offset[i];
+    }
+};
+
+template <class... A> Launch make_launch(Kernel<A...> k, dim3 grid, dim3 block, int klass, std::common_type_t<A>... args)
+{
+    static_assert(sizeof...(A) <= Launch::kMaxArgs && args_bytes<A...>() <= Launch::kArgBytes, "the arguments do not fit a Launch");
+    static_assert((std::is_trivially_copyable<A>::value && ...) && ((alignof(A) <= 8) && ...), "kernel arguments are plain values");
+    Launch l;
+    l.fn = k.fn;
+    l.grid = grid;
+    l.block = block;
+    l.klass = klass;
+    size_t at = 0;
+    ((at = arg_end(at, 0, alignof(A)), l.offset[l.argCount++] = (uint8_t)at, std::memcpy(l.bytes + at, &args, sizeof(A)), at += sizeof(A)), ...);
+    return l;
+}
+
+// A launch outside the passes (scene edits, test hooks): not timed, and the slot's error word is none of its business.
+template <class... A> hipError_t launch_untimed(Kernel<A...> k, dim3 grid, dim3 block, hipStream_t stream, std::common_type_t<A>... args)
+{
+    void* params[] = {(void*)&args...};
+    return hipLaunchKernel(k.fn, grid, block, params, 0, stream);
+}
+
+// ---- what the host units share ---------------------------------------------------------------------------
+int fail_invalid(const char* msg);  // sets the error string; returns NXHIP_ERR_INVALID
+int fail_invalid(const std::string& msg);
+
+#define NX_CHECK_CTX(ctx)                      \
+    do {                                       \
+        if (!(ctx)) {                          \
+            ::nxd::set_error("null context");  \
+            return NXHIP_ERR_INVALID;          \
+        }                                      \
+        if ((ctx)->dead) {                     \
+            ::nxd::set_error("the context is dead: nxhip_sync_timeout gave up waiting for the device (see include/nexus_hip.h)"); \
+            return NXHIP_ERR_TIMEOUT;          \
+        }                                      \
+    } while (0)
+
+// `} NX_CATCH("nxhip_name")` closes the function-try-block of an entry point: nothing may unwind through the C boundary
+#define NX_CATCH(name)                                          \
+    catch (const std::exception& e) {                           \
+        ::nxd::set_error(std::string(name ": ") + e.what());    \
+        return NXHIP_ERR_INVALID;                               \
+    }
+
+// a step of an entry point that returns a status: on anything but NXHIP_OK the entry point returns it
+#define NX_TRY(call)                                    \
+    do {                                                \
+        const int rcTry_ = (call);                      \
+        if (rcTry_ != NXHIP_OK) return rcTry_;          \
+    } while (0)
+
+#define NX_ALLOC(buf, n)                                  \
+    do {                                                  \
+        if (!(buf).alloc(n)) return NXHIP_ERR_HIP;        \
+    } while (0)
+
+// slot k of the context: 0 is the context itself, k >= 1 the extra in-flight passes
+inline PassSlot* slot_at(nxhip_ctx* c, uint32_t k) { return k == 0 ? static_cast<PassSlot*>(c) : c->extra[k - 1].get(); }
+inline uint32_t slot_count(const nxhip_ctx* c) { return 1u + (uint32_t)c->extra.size(); }
+
+// Wait for everything the context has issued, on every slot's stream (scene edits, re-allocations, read-backs).
+int sync_all(nxhip_ctx* c);
+#define NX_SYNC_ALL(c)                                  \
+    do {                                                \
+        const int rcSync_ = ::nxd::sync_all(c);         \
+        if (rcSync_ != NXHIP_OK) return rcSync_;        \
+    } while (0)
+
+// The nxhip_debug_* entry points exist for the tests (one of them plants a cycle in an uploaded BVH).  A `make release` library
+// (NX_NO_DEBUG_HOOKS) keeps the symbols — the header and the ABI stamp are the same — and refuses the calls.
+#ifdef NX_NO_DEBUG_HOOKS
+#define NX_DEBUG_HOOK(name) return ::nxd::fail_invalid(name ": this library was built without the test hooks (make release)")
+#else
+#define NX_DEBUG_HOOK(name) do { } while (0)
+#endif
+
+// Which pipeline a pass runs (nx_wavefront.hip): SCAN — the logic step's decision rides in the hit records and the material kernels
+// pick their items out of the trace queue — whenever slots are handed out by racing atomics; the CLASSIC logic kernel + material
+// queues for the ordered compaction, whose serial slot order IS the reference's copy order (PathTracer.cu:183-206).
+inline bool scan_pipeline(const nxhip_ctx* c) { return c->h.compactMode == NX_COMPACT_FAST; }
+
+// Pixels per frame slice of the next pass: the context's pixel set, or the active part of it (adaptive sampling).  c->localCount stays
+// the size of the image and of every read-back.
+inline uint32_t pass_pixels(const nxhip_ctx* c) { return c->adaptive ? c->activeCount : c->localCount; }
+
+// nxhip_api.hip: the context's state block, queues and pixel set
+void invalidate_graph(nxhip_ctx* c);
+int upload_state(nxhip_ctx* c);
+int alloc_queues(nxhip_ctx* c, size_t n);
+bool slot_queues_ready(const nxhip_ctx* c, const PassSlot* q);
+int ensure_slot_queues(nxhip_ctx* c, PassSlot* q);
+void release_slot_queues(nxhip_ctx* c, PassSlot* q);
+void release_denoise_planes(nxhip_ctx* c);
+void publish_pixel_set(nxhip_ctx* c);
+int set_frame_number_device(nxhip_ctx* c, uint32_t f);
+// nxhip_scene.hip: what a pass or a hook brings up to date before it reads the scene
+int refresh_shade_inst(nxhip_ctx* c);
+int refresh_updated_blas(nxhip_ctx* c);
+// nxhip_render.hip
+int check_scene_ready(nxhip_ctx* c);
+int launch_now(nxhip_ctx* c, const Launch& l);
+int render_pass(nxhip_ctx* c, uint32_t framesArg);
+int read_float4_as_float3(nxhip_ctx* c, const void* dev, uint32_t count, float* dst);
+// nxhip_features.hip
+int adaptive_restart(nxhip_ctx* c);
+int refresh_light_table(nxhip_ctx* c);
+
+}  // namespace nxd

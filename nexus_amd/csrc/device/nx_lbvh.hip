@@ -25,7 +25,7 @@
 #include <string>
 #include <vector>
 
-#include "nx_context.h"
+#include "nx_host.h"
 #include "nx_instbox.h"
 #include "nx_math.h"
 

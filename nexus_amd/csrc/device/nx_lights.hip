@@ -19,7 +19,7 @@
 
 #include <rocprim/rocprim.hpp>
 
-#include "nx_context.h"
+#include "nx_host.h"
 #include "nx_lights.h"
 
 namespace nxd {

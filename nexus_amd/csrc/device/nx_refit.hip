@@ -19,7 +19,7 @@
 namespace nxd {
 
 constexpr int kRefitBlock = 1024;
-constexpr int kBlasRefitBlock = 256;  // (nxhip_api.hip launches blas_refit_kernel with the same figure)
+constexpr int kBlasRefitBlock = 256;  // (nxhip_scene.hip launches blas_refit_kernel with the same figure)
 
 struct Box {
     float lo[3], hi[3];

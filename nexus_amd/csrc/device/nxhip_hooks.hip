@@ -1,0 +1,293 @@
+// nxhip_hooks.hip — kernel-level test hooks (ray batches, BSDF, texture, binary64 functions), trace statistics, kernel times.
+// (the C-ABI device layer declared in include/nexus_hip.h; helpers shared with the other nxhip_*.hip units: nx_host.h)
+#include <algorithm>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "nx_host.h"
+
+using namespace nxd;
+
+extern "C" {
+
+// ---- kernel-level hooks -----------------------------------------------------------------------------
+
+// The ray-batch hooks number their n rays densely and cut them into one contiguous piece per queue region in use (as
+// generate_kernel does for the primary rays): ray i lives in slot (i / piece) * cap + i % piece.
+struct HookLayout {
+    uint32_t shards, cap, piece;
+    int32_t sizes[kQueueShards];
+};
+static HookLayout hook_layout(const nxhip_ctx* c, uint32_t n)
+{
+    HookLayout l{};
+    l.shards = c->view.queueShards;
+    l.cap = c->view.queueShardCap;
+    l.piece = ((n + l.shards * 64u - 1u) / (l.shards * 64u)) * 64u;
+    for (uint32_t k = 0; k < (uint32_t)kQueueShards; k++) l.sizes[k] = k < l.shards ? (int32_t)std::min(l.piece, n - std::min(n, k * l.piece)) : 0;
+    return l;
+}
+// host array (n elements of `elem` bytes, dense numbering) <-> a queue buffer's regions
+static int hook_copy(nxhip_ctx* c, const HookLayout& l, void* dev, void* host, size_t elem, bool toDevice)
+{
+    for (uint32_t k = 0; k < l.shards; k++) {
+        if (l.sizes[k] <= 0) continue;
+        char* d = static_cast<char*>(dev) + (size_t)k * l.cap * elem;
+        char* h = static_cast<char*>(host) + (size_t)k * l.piece * elem;
+        if (toDevice) NX_HIP(hipMemcpyAsync(d, h, (size_t)l.sizes[k] * elem, hipMemcpyHostToDevice, c->stream));
+        else NX_HIP(hipMemcpyAsync(h, d, (size_t)l.sizes[k] * elem, hipMemcpyDeviceToHost, c->stream));
+    }
+    return NXHIP_OK;
+}
+
+static int run_trace_chunk(nxhip_ctx* c, bool anyHit, uint32_t n)
+{
+    // region sizes + zeroed fetch heads for the reserved bounce slot, computed on the device from n (hook_layout's rule): no copy
+    // from a stack-local of this function is left in flight when it returns
+    NX_HIP(launch_untimed(kernels::hook_sizes(), 1, 64, c->stream, c->dState.as<DeviceState>(), n, anyHit ? 1 : 0, kHookBounceSlot));
+    c->errorFresh = false;  // (this launch may set the error word after the last pass's copy of it)
+    const bool thin = c->thinInHooks && !c->statsEnabled;
+    Launch l = make_launch(kernels::trace(anyHit, c->statsEnabled), anyHit ? c->shadowBlocks : c->traceBlocks, kTraceBlockThreads,
+                           anyHit ? NXHIP_K_SHADOW : NXHIP_K_TRACE, c->dState.as<DeviceState>(), kHookBounceSlot | (thin ? kTraceThinFlag : 0));
+    int rc = launch_now(c, l);
+    if (rc == NXHIP_OK && thin) {  // (nxhip_debug_set_thin: what the dry waves handed over, a wave each)
+        Launch t = make_launch(kernels::thin(), 3 * c->numCUs, kTraceBlockThreads, NXHIP_K_THIN, c->dState.as<DeviceState>(), kHookBounceSlot);
+        rc = launch_now(c, t);
+    }
+    return rc;
+}
+
+int nxhip_trace_batch(nxhip_ctx* c, const nx_ray* rays, uint32_t count, nx_hit* hits)
+try {
+    NX_CHECK_CTX(c);
+    if (count == 0) return NXHIP_OK;
+    if (!rays || !hits) return fail_invalid("nxhip_trace_batch: null buffer");
+    NX_HIP(hipSetDevice(c->device));
+    if (!c->h.tlasNodes) return fail_invalid("no TLAS has been set");
+    NX_TRY(ensure_slot_queues(c, c));
+    NX_TRY(upload_state(c));
+    NX_TRY(refresh_updated_blas(c));
+    const uint32_t cap = c->pathCount;
+    std::vector<float4> o(std::min(cap, count)), d(std::min(cap, count)), h(std::min(cap, count));
+    std::vector<uint32_t> hi(std::min(cap, count));
+    for (uint32_t first = 0; first < count; first += cap) {
+        const uint32_t n = std::min(cap, count - first);
+        for (uint32_t i = 0; i < n; i++) {
+            const nx_ray& r = rays[first + i];
+            float idx;
+            std::memcpy(&idx, &i, 4);
+            o[i] = make_float4(r.origin[0], r.origin[1], r.origin[2], 0.0f);
+            d[i] = make_float4(r.direction[0], r.direction[1], r.direction[2], idx);
+        }
+        const HookLayout l = hook_layout(c, n);
+        NX_TRY(hook_copy(c, l, c->trRayO.p, o.data(), 16, true));
+        NX_TRY(hook_copy(c, l, c->trRayD.p, d.data(), 16, true));
+        NX_TRY(run_trace_chunk(c, false, n));
+        NX_TRY(hook_copy(c, l, c->trHit.p, h.data(), 16, false));
+        NX_TRY(hook_copy(c, l, c->trHitInst.p, hi.data(), 4, false));
+        NX_SYNC_ALL(c);
+        for (uint32_t i = 0; i < n; i++) {
+            nx_hit& out = hits[first + i];
+            out.hitDistance = h[i].x;
+            out.u = h[i].y;
+            out.v = h[i].z;
+            std::memcpy(&out.triIdx, &h[i].w, 4);
+            out.instanceIdx = hi[i];
+        }
+    }
+    return NXHIP_OK;
+} NX_CATCH("nxhip_trace_batch")
+
+int nxhip_trace_shadow_batch(nxhip_ctx* c, const nx_ray* rays, const float* tmax, uint32_t count, uint8_t* occluded)
+try {
+    NX_CHECK_CTX(c);
+    if (count == 0) return NXHIP_OK;
+    if (!rays || !tmax || !occluded) return fail_invalid("nxhip_trace_shadow_batch: null buffer");
+    NX_HIP(hipSetDevice(c->device));
+    if (!c->h.tlasNodes) return fail_invalid("no TLAS has been set");
+    NX_TRY(ensure_slot_queues(c, c));
+    NX_TRY(upload_state(c));
+    NX_TRY(refresh_updated_blas(c));
+    const uint32_t cap = c->pathCount;
+    const uint32_t m = std::min(cap, count);
+    std::vector<float4> o(m), d(m), rad(m, make_float4(1.0f, 0.0f, 0.0f, 0.0f)), res(m);
+    for (uint32_t first = 0; first < count; first += cap) {
+        const uint32_t n = std::min(cap, count - first);
+        for (uint32_t i = 0; i < n; i++) {
+            const nx_ray& r = rays[first + i];
+            float idx;
+            std::memcpy(&idx, &i, 4);
+            o[i] = make_float4(r.origin[0], r.origin[1], r.origin[2], tmax[first + i]);
+            d[i] = make_float4(r.direction[0], r.direction[1], r.direction[2], idx);
+        }
+        // the kernel's tail adds the request's radiance to the path's pixel when unoccluded: radiance 1 into a zeroed buffer
+        const HookLayout l = hook_layout(c, n);
+        NX_TRY(hook_copy(c, l, c->shRayO.p, o.data(), 16, true));
+        NX_TRY(hook_copy(c, l, c->shRayD.p, d.data(), 16, true));
+        NX_TRY(hook_copy(c, l, c->shRadiance.p, rad.data(), 16, true));
+        NX_HIP(hipMemsetAsync(c->h.radiance, 0, (size_t)n * 16, c->stream));  // the buffer the kernel adds into (own or bound)
+        NX_TRY(run_trace_chunk(c, true, n));
+        NX_HIP(hipMemcpyAsync(res.data(), c->h.radiance, (size_t)n * 16, hipMemcpyDeviceToHost, c->stream));
+        NX_SYNC_ALL(c);
+        for (uint32_t i = 0; i < n; i++) occluded[first + i] = res[i].x == 1.0f ? 0 : 1;
+    }
+    return NXHIP_OK;
+} NX_CATCH("nxhip_trace_shadow_batch")
+
+int nxhip_enable_trace_stats(nxhip_ctx* c, int enable)
+{
+    NX_CHECK_CTX(c);
+    if ((enable != 0) != c->statsEnabled) invalidate_graph(c);
+    c->statsEnabled = enable != 0;
+    return NXHIP_OK;
+}
+
+int nxhip_read_trace_stats(nxhip_ctx* c, nxhip_trace_stats* closest, nxhip_trace_stats* shadow, int reset)
+{
+    NX_CHECK_CTX(c);
+    NX_HIP(hipSetDevice(c->device));
+    NX_SYNC_ALL(c);
+    TraceStatsDev h[2];
+    NX_HIP(hipMemcpy(h, c->traceStats.p, sizeof h, hipMemcpyDeviceToHost));
+    static_assert(sizeof(nxhip_trace_stats) == sizeof(TraceStatsDev), "stats layouts must match");
+    if (closest) std::memcpy(closest, &h[0], sizeof h[0]);
+    if (shadow) std::memcpy(shadow, &h[1], sizeof h[1]);
+    if (reset) NX_HIP(hipMemset(c->traceStats.p, 0, sizeof h));
+    return NXHIP_OK;
+}
+
+static int bsdf_hook(nxhip_ctx* c, const nx_material* material, const nx_bsdf_query* queries, uint32_t count, nx_bsdf_result* results, int sample)
+{
+    NX_CHECK_CTX(c);
+    if (!material || (!queries && count) || (!results && count)) return fail_invalid("nxhip_bsdf_*_batch: null buffer");
+    if (material->type < NX_MAT_DIFFUSE || material->type > NX_MAT_CONDUCTOR) return fail_invalid("nxhip_bsdf_*_batch: unknown material type");
+    if (count == 0) return NXHIP_OK;
+    NX_HIP(hipSetDevice(c->device));
+    DevBuf dMat, dQ, dR;
+    NX_ALLOC(dMat, sizeof(nx_material));
+    NX_ALLOC(dQ, (size_t)count * sizeof(nx_bsdf_query));
+    NX_ALLOC(dR, (size_t)count * sizeof(nx_bsdf_result));
+    NX_HIP(hipMemcpy(dMat.p, material, sizeof(nx_material), hipMemcpyHostToDevice));
+    NX_HIP(hipMemcpy(dQ.p, queries, (size_t)count * sizeof(nx_bsdf_query), hipMemcpyHostToDevice));
+    NX_HIP(launch_untimed(kernels::bsdf_hook(), c->wideBlocks, kWideBlockThreads, c->stream, dMat.as<nx_material>(), dQ.as<nx_bsdf_query>(), count, sample, dR.as<nx_bsdf_result>()));
+    NX_SYNC_ALL(c);
+    NX_HIP(hipMemcpy(results, dR.p, (size_t)count * sizeof(nx_bsdf_result), hipMemcpyDeviceToHost));
+    return NXHIP_OK;
+}
+
+int nxhip_bsdf_sample_batch(nxhip_ctx* c, const nx_material* material, const nx_bsdf_query* queries, uint32_t count, nx_bsdf_result* results)
+{
+    return bsdf_hook(c, material, queries, count, results, 1);
+}
+
+int nxhip_bsdf_eval_batch(nxhip_ctx* c, const nx_material* material, const nx_bsdf_query* queries, uint32_t count, nx_bsdf_result* results)
+{
+    return bsdf_hook(c, material, queries, count, results, 0);
+}
+
+int nxhip_tex2d_batch(nxhip_ctx* c, int kind, int textureId, const float* uv, uint32_t count, float* rgba)
+{
+    NX_CHECK_CTX(c);
+    if ((!uv || !rgba) && count) return fail_invalid("nxhip_tex2d_batch: null buffer");
+    if (kind < 0 || kind > 2) return fail_invalid("nxhip_tex2d_batch: kind must be 0, 1 or 2");
+    if (kind == 0 && (textureId < 0 || (size_t)textureId >= c->diffuseMaps.size())) return fail_invalid("nxhip_tex2d_batch: no such diffuse map");
+    if (kind == 1 && (textureId < 0 || (size_t)textureId >= c->emissiveMaps.size())) return fail_invalid("nxhip_tex2d_batch: no such emissive map");
+    if (kind == 2 && !c->hdrMap.texels.p) return fail_invalid("nxhip_tex2d_batch: no environment map has been uploaded");
+    if (count == 0) return NXHIP_OK;
+    NX_HIP(hipSetDevice(c->device));
+    const TextureHost& th = kind == 0 ? c->diffuseMaps[textureId] : kind == 1 ? c->emissiveMaps[textureId] : c->hdrMap;
+    TextureDev t{th.texels.as<uint32_t>(), th.width, th.height};
+    DevBuf dUv, dOut;
+    NX_ALLOC(dUv, (size_t)count * 8);
+    NX_ALLOC(dOut, (size_t)count * 16);
+    NX_HIP(hipMemcpy(dUv.p, uv, (size_t)count * 8, hipMemcpyHostToDevice));
+    NX_HIP(launch_untimed(kernels::tex2d_hook(), c->wideBlocks, kWideBlockThreads, c->stream, t, c->srgbLut.as<float>(), dUv.as<float>(), count, dOut.as<float4>()));
+    NX_SYNC_ALL(c);
+    NX_HIP(hipMemcpy(rgba, dOut.p, (size_t)count * 16, hipMemcpyDeviceToHost));
+    return NXHIP_OK;
+}
+
+int nxhip_fmath_batch(nxhip_ctx* c, int op, const double* a, const double* b, uint32_t count, double* out)
+{
+    NX_CHECK_CTX(c);
+    if (op < 0 || op >= NXF_OP_COUNT) return fail_invalid("nxhip_fmath_batch: op must be one of NXF_OP_*");
+    if ((!a || !out) && count) return fail_invalid("nxhip_fmath_batch: null buffer");
+    if (count == 0) return NXHIP_OK;
+    NX_HIP(hipSetDevice(c->device));
+    DevBuf dA, dB, dOut;
+    NX_ALLOC(dA, (size_t)count * 8);
+    NX_ALLOC(dOut, (size_t)count * 8);
+    NX_HIP(hipMemcpy(dA.p, a, (size_t)count * 8, hipMemcpyHostToDevice));
+    if (b) {
+        NX_ALLOC(dB, (size_t)count * 8);
+        NX_HIP(hipMemcpy(dB.p, b, (size_t)count * 8, hipMemcpyHostToDevice));
+    }
+    NX_HIP(launch_untimed(kernels::fmath_hook(), c->wideBlocks, kWideBlockThreads, c->stream, op, dA.as<double>(), b ? dB.as<double>() : nullptr, count, dOut.as<double>()));
+    NX_SYNC_ALL(c);
+    NX_HIP(hipMemcpy(out, dOut.p, (size_t)count * 8, hipMemcpyDeviceToHost));
+    return NXHIP_OK;
+}
+
+int nxhip_enable_kernel_timing(nxhip_ctx* c, int enable)
+{
+    NX_CHECK_CTX(c);
+    if (enable < 0 || enable > 3) return fail_invalid("nxhip_enable_kernel_timing: mode must be 0, 1, 2 or 3");
+    if (enable != c->timingMode) invalidate_graph(c);
+    c->timingMode = enable;
+    c->graphTimersPending = false;
+    c->timingEnabled = enable != 0;
+    return NXHIP_OK;
+}
+
+int nxhip_read_graph_timeline(nxhip_ctx* c, int32_t* klass, float* startMs, float* durationMs, uint32_t capacity, uint32_t* count)
+{
+    NX_CHECK_CTX(c);
+    if (!count) return fail_invalid("nxhip_read_graph_timeline: null count");
+    if (capacity && (!klass || !startMs || !durationMs)) return fail_invalid("nxhip_read_graph_timeline: null destination");
+    NX_HIP(hipSetDevice(c->device));
+    NX_SYNC_ALL(c);
+    *count = (uint32_t)c->graphTimers.size();
+    if (c->graphTimers.empty() || !c->lastRendered) return NXHIP_OK;
+    for (size_t i = 0; i < c->graphTimers.size() && i < capacity; i++) {
+        float s = 0.0f, d = 0.0f;
+        NX_HIP(hipEventElapsedTime(&s, c->graphTimers[0].start, c->graphTimers[i].start));
+        NX_HIP(hipEventElapsedTime(&d, c->graphTimers[i].start, c->graphTimers[i].stop));
+        klass[i] = c->graphTimers[i].klass;
+        startMs[i] = s;
+        durationMs[i] = d;
+    }
+    return NXHIP_OK;
+}
+
+int nxhip_read_kernel_times(nxhip_ctx* c, nxhip_kernel_times* out, int reset)
+{
+    NX_CHECK_CTX(c);
+    if (!out) return fail_invalid("null destination");
+    NX_HIP(hipSetDevice(c->device));
+    NX_SYNC_ALL(c);
+    for (size_t i = 0; i < c->timerPool.size(); i++) {
+        float ms = 0.0f;
+        NX_HIP(hipEventElapsedTime(&ms, c->timerPool[i].start, c->timerPool[i].stop));
+        c->times.ms[c->timerPool[i].klass] += ms;
+        (void)hipEventDestroy(c->timerPool[i].start);
+        (void)hipEventDestroy(c->timerPool[i].stop);
+    }
+    c->timerPool.clear();
+    if (c->graphTimersPending) {  // mode 3: the events hold the last replay of a back-to-back series
+        for (size_t i = 0; i < c->graphTimers.size(); i++) {
+            float ms = 0.0f;
+            NX_HIP(hipEventElapsedTime(&ms, c->graphTimers[i].start, c->graphTimers[i].stop));
+            c->times.ms[c->graphTimers[i].klass] += ms;
+            c->times.launches[c->graphTimers[i].klass]++;
+        }
+        c->graphTimersPending = false;
+    }
+    *out = c->times;
+    if (reset) std::memset(&c->times, 0, sizeof c->times);
+    return NXHIP_OK;
+}
+
+}  // extern "C"
+
+uint64_t nxd::layout_stamp_hooks() { return layout_stamp(); }

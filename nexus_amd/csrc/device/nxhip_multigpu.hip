@@ -14,10 +14,9 @@
 #include <string>
 #include <vector>
 
-#include "nx_context.h"
+#include "nx_host.h"
 
 namespace nxd {
-const void* compose_kernel_ptr();
 
 namespace {
 
@@ -135,8 +134,7 @@ int nxhip_mgpu_unique_id(void* id128)
     Rccl& r = rccl();
     if (!r.handle) return fail(NXHIP_ERR_INVALID, r.error);
     ncclUniqueId id;
-    const int rc = nccl_ok(r.GetUniqueId(&id), "ncclGetUniqueId");
-    if (rc != NXHIP_OK) return rc;
+    NX_TRY(nccl_ok(r.GetUniqueId(&id), "ncclGetUniqueId"));
     std::memcpy(id128, id.internal, 128);
     return NXHIP_OK;
 }
@@ -146,13 +144,10 @@ try {
     if (worldSize < 1 || rank < 0 || rank >= worldSize) return fail(NXHIP_ERR_INVALID, "nxhip_mgpu: rank / world size out of range");
     std::vector<uint32_t> map;
     uint32_t n = 0;
-    int rc = nxhip_tile_pixel_map(c->width, c->height, worldSize, rank, tileRows, 1, nullptr, &n);
-    if (rc != NXHIP_OK) return rc;
+    NX_TRY(nxhip_tile_pixel_map(c->width, c->height, worldSize, rank, tileRows, 1, nullptr, &n));
     map.resize(n);
-    rc = nxhip_tile_pixel_map(c->width, c->height, worldSize, rank, tileRows, 1, map.data(), &n);
-    if (rc != NXHIP_OK) return rc;
-    rc = nxhip_set_pixel_map(c, map.data(), n);
-    if (rc != NXHIP_OK) return rc;
+    NX_TRY(nxhip_tile_pixel_map(c->width, c->height, worldSize, rank, tileRows, 1, map.data(), &n));
+    NX_TRY(nxhip_set_pixel_map(c, map.data(), n));
     // (the context is marked as split only when everything below has succeeded: a failed setup leaves no half-initialised state)
     DevBuf gathered, maps, fullAccum, fullRgba8;
     if (rank == 0) {
@@ -165,8 +160,7 @@ try {
         std::vector<uint32_t> all((size_t)worldSize * n);
         for (int r = 0; r < worldSize; r++) {
             uint32_t m = 0;
-            rc = nxhip_tile_pixel_map(c->width, c->height, worldSize, r, tileRows, 1, all.data() + (size_t)r * n, &m);
-            if (rc != NXHIP_OK) return rc;
+            NX_TRY(nxhip_tile_pixel_map(c->width, c->height, worldSize, r, tileRows, 1, all.data() + (size_t)r * n, &m));
             if (m != n) return fail(NXHIP_ERR_INVALID, "nxhip_mgpu: ranks have unequal tile sizes");
         }
         NX_HIP(hipMemcpy(maps.p, all.data(), all.size() * 4, hipMemcpyHostToDevice));
@@ -198,9 +192,8 @@ int nxhip_mgpu_init(nxhip_ctx* c, int worldSize, int rank, const void* id128, ui
     ncclUniqueId id;
     std::memcpy(id.internal, id128, 128);
     ncclComm_t comm = nullptr;
-    int rc = nccl_ok(r.CommInitRank(&comm, worldSize, id, rank), "ncclCommInitRank");
-    if (rc != NXHIP_OK) return rc;
-    rc = mgpu_setup(c, worldSize, rank, tileRows, comm, true);
+    NX_TRY(nccl_ok(r.CommInitRank(&comm, worldSize, id, rank), "ncclCommInitRank"));
+    const int rc = mgpu_setup(c, worldSize, rank, tileRows, comm, true);
     if (rc != NXHIP_OK) {
         (void)r.CommDestroy(comm);
         c->mgpuComm = nullptr;
@@ -238,13 +231,8 @@ int nxhip_mgpu_gather(nxhip_ctx* c)
     if (rc != NXHIP_OK) return rc;
     if (c->mgpuRank == 0) {
         for (int k = 0; k < c->mgpuWorld; k++) {
-            const float4* src = c->mgpuGathered.as<float4>() + (size_t)k * n;
-            const uint32_t* map = c->mgpuMaps.as<uint32_t>() + (size_t)k * n;
-            float4* dstA = c->mgpuFullAccum.as<float4>();
-            uint32_t* dstP = c->mgpuFullRgba8.as<uint32_t>();
-            uint32_t count = n;
-            void* args[5] = {(void*)&src, (void*)&count, (void*)&map, (void*)&dstA, (void*)&dstP};
-            NX_HIP(hipLaunchKernel(compose_kernel_ptr(), dim3(c->wideBlocks), dim3(256), args, 0, c->stream));
+            NX_HIP(launch_untimed(kernels::compose(), c->wideBlocks, kWideBlockThreads, c->stream, c->mgpuGathered.as<float4>() + (size_t)k * n, n,
+                                  c->mgpuMaps.as<uint32_t>() + (size_t)k * n, c->mgpuFullAccum.as<float4>(), c->mgpuFullRgba8.as<uint32_t>()));
         }
     }
     return NXHIP_OK;

@@ -1,0 +1,967 @@
+// nxhip_scene.hip — scene upload: BLASes and the TLAS (uploaded, device-built, refitted), materials, lights, textures, environment tables.
+// (the C-ABI device layer declared in include/nexus_hip.h; helpers shared with the other nxhip_*.hip units: nx_host.h)
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "nx_host.h"
+
+using namespace nxd;
+
+extern "C" {
+
+// ---- scene upload -----------------------------------------------------------------------------------
+
+// 80-byte nodes at a stride of kNodeStride 16-byte chunks (5 = packed as uploaded)
+static std::vector<uint4> pad_nodes(const nx_bvh8_node* nodes, uint32_t nodeCount)
+{
+    std::vector<uint4> out((size_t)nodeCount * kNodeStride, make_uint4(0u, 0u, 0u, 0u));
+    for (uint32_t i = 0; i < nodeCount; i++) std::memcpy(&out[(size_t)i * kNodeStride], &nodes[i], sizeof(nx_bvh8_node));
+    return out;
+}
+
+// The shading copy of a BLAS's triangles when they are kept one per kShadeTriStride bytes (nx_device.h): a strided device copy
+// of the packed array.
+static int make_shade_tris(BlasHost& b)
+{
+    if (kShadeTriStride == (int)sizeof(nx_triangle)) return NXHIP_OK;
+    NX_ALLOC(b.shadeTris, (size_t)b.triCount * kShadeTriStride);
+    NX_HIP(hipMemset(b.shadeTris.p, 0, (size_t)b.triCount * kShadeTriStride));
+    NX_HIP(hipMemcpy2D(b.shadeTris.p, kShadeTriStride, b.tris.p, sizeof(nx_triangle), sizeof(nx_triangle), b.triCount, hipMemcpyDeviceToDevice));
+    return NXHIP_OK;
+}
+
+static int refresh_blas_table(nxhip_ctx* c)
+{
+    std::vector<BlasDev> table(std::max<size_t>(1, c->blas.size()));
+    std::memset(table.data(), 0, table.size() * sizeof(BlasDev));
+    for (size_t i = 0; i < c->blas.size(); i++) {
+        const BlasHost& b = c->blas[i];
+        table[i].nodes = b.nodes.as<uint4>();
+        table[i].isect = b.isect.as<float4>();
+        table[i].tris = kShadeTriStride == (int)sizeof(nx_triangle) ? b.tris.as<nx_triangle>() : b.shadeTris.as<nx_triangle>();
+        table[i].triIdx = b.triIdx.as<uint32_t>();
+        table[i].nodeCount = b.nodeCount;
+        table[i].triCount = b.triCount;
+    }
+    NX_SYNC_ALL(c);  // nothing may still read the old table
+    NX_ALLOC(c->blasTable, table.size() * sizeof(BlasDev));
+    NX_HIP(hipMemcpy(c->blasTable.p, table.data(), table.size() * sizeof(BlasDev), hipMemcpyHostToDevice));
+    c->h.blas = c->blasTable.as<BlasDev>();
+    c->stateDirty = true;
+    c->shadeInstDirty = true;  // (the records hold the BLASes' triangle arrays)
+    return NXHIP_OK;
+}
+
+}  // extern "C"
+
+// The shading records of the instances (nx_device.h ShadeInst) from the instance, BLAS and material tables.  Called before a
+// render when one of them has changed (shadeInstDirty); the cross-table indices have been checked by then (check_scene_ready).
+// The matrices come from the DEVICE's instance table: nxhip_set_instance_transforms computes the inverses there.
+int nxd::refresh_shade_inst(nxhip_ctx* c)
+{
+    const size_t n = c->hostInstances.size();
+    std::vector<nx_bvh_instance> inst(n);
+    NX_SYNC_ALL(c);
+    if (n) NX_HIP(hipMemcpy(inst.data(), c->instances.p, n * sizeof(nx_bvh_instance), hipMemcpyDeviceToHost));
+    std::vector<ShadeInst> rec(std::max<size_t>(1, n));
+    std::memset(rec.data(), 0, rec.size() * sizeof(ShadeInst));
+    for (size_t i = 0; i < n; i++) {
+        const nx_bvh_instance& in = inst[i];
+        if (in.bvhIdx >= c->blas.size()) return fail_invalid("instance refers to a BLAS id that has not been uploaded");
+        if (in.materialId < 0 || (size_t)in.materialId >= c->hostMaterialsDev.size()) return fail_invalid("an instance refers to a material id that has not been set");
+        const BlasHost& b = c->blas[in.bvhIdx];
+        std::memcpy(rec[i].transform, in.transform.cell, sizeof rec[i].transform);
+        std::memcpy(rec[i].invTransform, in.invTransform.cell, sizeof rec[i].invTransform);
+        rec[i].tris = kShadeTriStride == (int)sizeof(nx_triangle) ? b.tris.as<nx_triangle>() : b.shadeTris.as<nx_triangle>();
+        rec[i].triCount = b.triCount;
+        rec[i].materialId = in.materialId;
+        rec[i].material = c->hostMaterialsDev[(size_t)in.materialId];
+    }
+    NX_ALLOC(c->shadeInst, rec.size() * sizeof(ShadeInst));
+    NX_HIP(hipMemcpy(c->shadeInst.p, rec.data(), rec.size() * sizeof(ShadeInst), hipMemcpyHostToDevice));
+    c->h.shadeInst = c->shadeInst.as<ShadeInst>();
+    c->stateDirty = true;
+    c->shadeInstDirty = false;
+    // the traversal records' material codes follow the shading records (nx_refit.hip inst_code_kernel)
+    if (c->instTrav.p && !c->hostInstIdx.empty()) {
+        const uint32_t count = (uint32_t)c->hostInstIdx.size();
+        NX_HIP(launch_untimed(kernels::inst_code(), (count + 255u) / 256u, 256, c->stream, c->dState.as<DeviceState>(), c->instTrav.as<InstTrav>(), c->shadeInst.as<ShadeInst>(), count));
+        NX_HIP(hipStreamSynchronize(c->stream));
+    }
+    return NXHIP_OK;
+}
+
+extern "C" {
+
+static int refresh_inst_trav(nxhip_ctx* c)
+{
+    // one record per TLAS leaf, in leaf order
+    const size_t n = c->hostInstIdx.size();
+    std::vector<InstTrav> trav(std::max<size_t>(1, n));
+    std::memset(trav.data(), 0, trav.size() * sizeof(InstTrav));
+    bool allIdentity = n > 0;
+    for (size_t k = 0; k < n; k++) {
+        const uint32_t i = c->hostInstIdx[k];
+        const nx_bvh_instance& inst = c->hostInstances[i];
+        if (inst.bvhIdx >= c->blas.size()) return fail_invalid("instance refers to a BLAS id that has not been uploaded");
+        const float* m = inst.invTransform.cell;
+        trav[k].r0 = make_float4(m[0], m[1], m[2], m[3]);
+        trav[k].r1 = make_float4(m[4], m[5], m[6], m[7]);
+        trav[k].r2 = make_float4(m[8], m[9], m[10], m[11]);
+        BlasHost& b = c->blas[inst.bvhIdx];
+        if (!b.rootKnown) {
+            if (b.nodeCount) NX_HIP(hipMemcpy(b.root, b.nodes.p, sizeof b.root, hipMemcpyDeviceToHost));
+            b.rootKnown = true;
+        }
+        trav[k].nodes = b.nodes.as<uint4>();
+        trav[k].isect = b.isect.as<float4>();
+        trav[k].instIdx = i;
+        trav[k].flags = rows_are_identity(m) ? kInstIdentity : 0u;
+        allIdentity = allIdentity && trav[k].flags != 0u;
+        for (int q = 0; q < 5; q++) trav[k].root[q] = b.root[q];
+    }
+    NX_SYNC_ALL(c);
+    NX_ALLOC(c->instTrav, trav.size() * sizeof(InstTrav));
+    NX_HIP(hipMemcpy(c->instTrav.p, trav.data(), trav.size() * sizeof(InstTrav), hipMemcpyHostToDevice));
+    c->h.instTrav = c->instTrav.as<InstTrav>();
+    c->h.sceneFlags = allIdentity ? kSceneAllIdentity : 0u;
+    c->stateDirty = true;
+    c->shadeInstDirty = true;  // (the records' material codes are written when the shading records are rebuilt: refresh_shade_inst)
+    return NXHIP_OK;
+}
+
+// What the traversal kernels assume of 8-wide nodes, checked before anything reaches the GPU (BLAS: primitives = triangles of
+// the leaf-ordered list; TLAS: instances).  The kernels decode a slot from its META byte alone — bits 3 and 4 both set: an
+// inner child whose hit bit goes to position 24 .. 31 and whose node is childBaseIdx + (imask bits below its slot); otherwise
+// a leaf whose (meta >> 5) bits go to position (meta & 31) ... of the 24-bit primitive mask — so the check follows the meta
+// bytes: an inner slot must be announced in imask and carry exactly one bit (more would land on other slots' positions and
+// index one node past the children), a leaf's bits must stay below position 24 (beyond it they read as inner hits) and
+// inside the primitive list, children must exist and follow their parent (no cycles: the traversal would never end).
+static const char* wide_node_defect(const nx_bvh8_node& n, uint32_t i, uint32_t nodeCount, uint32_t primCount, bool childrenMustFollow)
+{
+    int inner = 0, prims = 0;
+    for (int s = 0; s < 8; s++) {
+        const uint32_t m = n.meta[s];
+        if (n.imask & (1u << s)) inner++;
+        if ((m & 0x18u) == 0x18u && (m >> 5) != 0u) {  // decoded as an inner child
+            if (!(n.imask & (1u << s))) return "a slot is encoded as an inner child but not announced in imask";
+            if ((m >> 5) != 1u) return "an inner slot carries more than one hit bit";
+            if ((m & 0x07u) != (uint32_t)s) return "an inner slot is encoded with another slot's number";
+        } else if (m >> 5) {  // decoded as a leaf of 1 .. 3 primitives at offset (m & 31)
+            const int top = 32 - __builtin_clz(m >> 5);
+            if ((int)(m & 0x1fu) + top > 24) return "a leaf slot's primitive bits leave the 24-bit primitive mask";
+            prims = std::max(prims, (int)(m & 0x1fu) + top);
+        }
+    }
+    if (inner && (uint64_t)n.childBaseIdx + (uint64_t)inner > nodeCount) return "child index out of range";
+    if (childrenMustFollow && inner && n.childBaseIdx <= i) return "child nodes must follow their parent";
+    if (prims && (uint64_t)n.triangleBaseIdx + (uint64_t)prims > primCount) return "leaf range out of range";
+    return nullptr;
+}
+static const char* wide_nodes_defect(const nx_bvh8_node* nodes, uint32_t nodeCount, uint32_t primCount)
+{
+    for (uint32_t i = 0; i < nodeCount; i++)
+        if (const char* defect = wide_node_defect(nodes[i], i, nodeCount, primCount, true)) return defect;
+    return nullptr;
+}
+
+int nxhip_upload_blas(nxhip_ctx* c, const nx_bvh8_node* nodes, uint32_t nodeCount, const nx_triangle* tris, uint32_t triCount,
+                      const uint32_t* triIdx, int32_t* blasId)
+try {
+    NX_CHECK_CTX(c);
+    if (!nodes || !tris || !triIdx || nodeCount == 0 || triCount == 0) return fail_invalid("nxhip_upload_blas: empty input");
+    NX_HIP(hipSetDevice(c->device));
+    // validate what the kernels assume before anything reaches the GPU: indices in range
+    for (uint32_t i = 0; i < triCount; i++)
+        if (triIdx[i] >= triCount) return fail_invalid("nxhip_upload_blas: triangle index out of range");
+    if (const char* defect = wide_nodes_defect(nodes, nodeCount, triCount)) return fail_invalid(std::string("nxhip_upload_blas: ") + defect);
+    BlasHost b;
+    b.nodeCount = nodeCount;
+    b.triCount = triCount;
+    // leaf-ordered intersection stream: {p0 | original index}, {edge0}, {edge1}; the edges are the same float
+    // subtractions the reference performs per test (Triangle.cuh:55-56), done once here
+    std::vector<float4> isect((size_t)triCount * kTriStride, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
+    for (uint32_t k = 0; k < triCount; k++) {
+        const uint32_t t = triIdx[k];
+        const nx_triangle& tr = tris[t];
+        float idBits;
+        std::memcpy(&idBits, &t, 4);
+        isect[kTriStride * (size_t)k + 0] = make_float4(tr.pos0[0], tr.pos0[1], tr.pos0[2], idBits);
+        isect[kTriStride * (size_t)k + 1] = make_float4(tr.pos1[0] - tr.pos0[0], tr.pos1[1] - tr.pos0[1], tr.pos1[2] - tr.pos0[2], 0.0f);
+        isect[kTriStride * (size_t)k + 2] = make_float4(tr.pos2[0] - tr.pos0[0], tr.pos2[1] - tr.pos0[1], tr.pos2[2] - tr.pos0[2], 0.0f);
+    }
+    std::vector<uint4> padded = pad_nodes(nodes, nodeCount);
+    NX_ALLOC(b.nodes, padded.size() * sizeof(uint4));
+    NX_ALLOC(b.isect, isect.size() * sizeof(float4));
+    NX_ALLOC(b.tris, (size_t)triCount * sizeof(nx_triangle));
+    NX_ALLOC(b.triIdx, (size_t)triCount * 4);
+    NX_HIP(hipMemcpy(b.nodes.p, padded.data(), padded.size() * sizeof(uint4), hipMemcpyHostToDevice));
+    NX_HIP(hipMemcpy(b.isect.p, isect.data(), isect.size() * sizeof(float4), hipMemcpyHostToDevice));
+    NX_HIP(hipMemcpy(b.tris.p, tris, (size_t)triCount * sizeof(nx_triangle), hipMemcpyHostToDevice));
+    NX_HIP(hipMemcpy(b.triIdx.p, triIdx, (size_t)triCount * 4, hipMemcpyHostToDevice));
+    if (const int rcs = make_shade_tris(b)) return rcs;
+    c->blas.push_back(std::move(b));
+    if (blasId) *blasId = (int32_t)c->blas.size() - 1;
+    return refresh_blas_table(c);
+} NX_CATCH("nxhip_upload_blas")
+
+int nxhip_build_blas(nxhip_ctx* c, const nx_triangle* tris, uint32_t triCount, int32_t* blasId)
+try {
+    NX_CHECK_CTX(c);
+    if (!tris || triCount == 0) return fail_invalid("nxhip_build_blas: empty input");
+    if (kNodeStride != 5) return fail_invalid("nxhip_build_blas: built with padded node records");
+    NX_HIP(hipSetDevice(c->device));
+    NX_SYNC_ALL(c);
+    BlasHost b;
+    b.triCount = triCount;
+    NX_ALLOC(b.tris, (size_t)triCount * sizeof(nx_triangle));
+    NX_HIP(hipMemcpy(b.tris.p, tris, (size_t)triCount * sizeof(nx_triangle), hipMemcpyHostToDevice));
+    DevBuf wide;
+    uint32_t nodeCount = 0;
+    NX_TRY(lbvh_build(c, b.tris.as<nx_triangle>(), triCount, c->deviceBuilderRadius, wide, b.triIdx, b.isect, &nodeCount));
+    NX_ALLOC(b.nodes, (size_t)nodeCount * sizeof(nx_bvh8_node));  // the builder's array is sized for the worst case
+    NX_HIP(hipMemcpy(b.nodes.p, wide.p, (size_t)nodeCount * sizeof(nx_bvh8_node), hipMemcpyDeviceToDevice));
+    b.nodeCount = nodeCount;
+    if (const int rcs = make_shade_tris(b)) return rcs;
+    c->blas.push_back(std::move(b));
+    if (blasId) *blasId = (int32_t)c->blas.size() - 1;
+    return refresh_blas_table(c);
+} NX_CATCH("nxhip_build_blas")
+
+int nxhip_build_blas_batch(nxhip_ctx* c, const nx_triangle* const* tris, const uint32_t* triCounts, uint32_t meshCount, int32_t* blasIds)
+try {
+    NX_CHECK_CTX(c);
+    if (!tris || !triCounts || meshCount == 0) return fail_invalid("nxhip_build_blas_batch: empty input");
+    if (kNodeStride != 5) return fail_invalid("nxhip_build_blas_batch: built with padded node records");
+    uint64_t total = 0;
+    for (uint32_t m = 0; m < meshCount; m++) {
+        if (!tris[m] || triCounts[m] == 0) return fail_invalid("nxhip_build_blas_batch: a mesh without triangles");
+        total += triCounts[m];
+    }
+    if (total > 0x7fffffffull) return fail_invalid("nxhip_build_blas_batch: more than 2^31 triangles in one batch");
+    if (c->deviceBuilderRadius != NXHIP_BUILDER_SAH || meshCount == 1) {
+        // the other builders (radix tree, clustering) have no forest form: one build per mesh
+        for (uint32_t m = 0; m < meshCount; m++) {
+            int32_t id = -1;
+            NX_TRY(nxhip_build_blas(c, tris[m], triCounts[m], &id));
+            if (blasIds) blasIds[m] = id;
+        }
+        return NXHIP_OK;
+    }
+    NX_HIP(hipSetDevice(c->device));
+    NX_SYNC_ALL(c);
+    // NX_TUNING_KNOBS=1 NX_BATCH_TIMING=1: where the call's time goes, to stderr (tools / tests only)
+    const bool timing = std::getenv("NX_TUNING_KNOBS") && std::atoi(std::getenv("NX_TUNING_KNOBS")) == 1 && std::getenv("NX_BATCH_TIMING");
+    auto now = [] { return std::chrono::steady_clock::now(); };
+    auto lap = [&](const char* what, std::chrono::steady_clock::time_point& t0) {
+        if (!timing) return;
+        (void)hipStreamSynchronize(c->stream);
+        const auto t1 = now();
+        std::fprintf(stderr, "[nxhip_build_blas_batch] %-34s %7.2f ms\n", what, std::chrono::duration<double, std::milli>(t1 - t0).count());
+        t0 = t1;
+    };
+    auto tLap = now();
+    // the triangles of all meshes, concatenated, through a pinned staging buffer the context keeps (one transfer instead of one
+    // per mesh)
+    const size_t bytes = (size_t)total * sizeof(nx_triangle);
+    constexpr size_t kHalf = (size_t)16 << 20;  // two halves of a 32 MiB pinned buffer, allocated once per context: a staging buffer
+                                                // as large as the batch would cost more to pin than the transfer takes
+    if (!c->hostStaging) {
+        NX_HIP(hipHostMalloc(&c->hostStaging, 2 * kHalf, hipHostMallocDefault));
+        c->hostStagingBytes = 2 * kHalf;
+        NX_HIP(hipEventCreateWithFlags(&c->stagingDone[0], hipEventDisableTiming));
+        NX_HIP(hipEventCreateWithFlags(&c->stagingDone[1], hipEventDisableTiming));
+    }
+    std::vector<uint32_t> counts(triCounts, triCounts + meshCount);
+    auto trisPool = std::make_shared<DevBuf>();
+    auto nodesPool = std::make_shared<DevBuf>(), idxPool = std::make_shared<DevBuf>(), isectPool = std::make_shared<DevBuf>();
+    if (!trisPool->alloc(bytes)) return NXHIP_ERR_HIP;
+    {
+        // the meshes as one byte stream through the two halves: while one half is on its way to the device the other is filled
+        size_t sent = 0, inHalf = 0;
+        int half = 0;
+        bool used[2] = {false, false};
+        char* const base = static_cast<char*>(c->hostStaging);
+        auto flush = [&]() -> int {
+            if (inHalf == 0) return NXHIP_OK;
+            NX_HIP(hipMemcpyAsync(static_cast<char*>(trisPool->p) + sent, base + (size_t)half * kHalf, inHalf, hipMemcpyHostToDevice, c->stream));
+            NX_HIP(hipEventRecord(c->stagingDone[half], c->stream));
+            used[half] = true;
+            sent += inHalf;
+            inHalf = 0;
+            half ^= 1;
+            if (used[half]) NX_HIP(hipEventSynchronize(c->stagingDone[half]));  // the half about to be refilled has left
+            return NXHIP_OK;
+        };
+        for (uint32_t m = 0; m < meshCount; m++) {
+            const char* src = reinterpret_cast<const char*>(tris[m]);
+            size_t left = (size_t)counts[m] * sizeof(nx_triangle);
+            while (left) {
+                const size_t take = std::min(left, kHalf - inHalf);
+                std::memcpy(base + (size_t)half * kHalf + inHalf, src, take);
+                inHalf += take;
+                src += take;
+                left -= take;
+                if (inHalf == kHalf)
+                    if (const int rcf = flush()) return rcf;
+            }
+        }
+        if (const int rcf = flush()) return rcf;
+    }
+    std::vector<uint32_t> nodeFirst, nodeCounts;
+    lap("triangles through pinned staging", tLap);
+    NX_TRY(lbvh_build_batch(c, trisPool->as<nx_triangle>(), counts, *nodesPool, *idxPool, *isectPool, nodeFirst, nodeCounts));
+    lap("device build", tLap);
+    // every mesh's root node, for the instance records (refresh_inst_trav would otherwise fetch them one by one)
+    std::vector<nx_bvh8_node> allNodes(nodesPool->bytes / sizeof(nx_bvh8_node));
+    NX_HIP(hipMemcpy(allNodes.data(), nodesPool->p, allNodes.size() * sizeof(nx_bvh8_node), hipMemcpyDeviceToHost));
+    size_t first = 0;
+    for (uint32_t m = 0; m < meshCount; m++) {
+        BlasHost b;
+        b.triCount = counts[m];
+        b.nodeCount = nodeCounts[m];
+        b.nodes = DevBuf::view(nodesPool, (size_t)nodeFirst[m] * sizeof(nx_bvh8_node), (size_t)nodeCounts[m] * sizeof(nx_bvh8_node));
+        b.isect = DevBuf::view(isectPool, first * kTriStride * sizeof(float4), (size_t)counts[m] * kTriStride * sizeof(float4));
+        b.tris = DevBuf::view(trisPool, first * sizeof(nx_triangle), (size_t)counts[m] * sizeof(nx_triangle));
+        b.triIdx = DevBuf::view(idxPool, first * 4, (size_t)counts[m] * 4);
+        std::memcpy(b.root, &allNodes[nodeFirst[m]], sizeof b.root);
+        b.rootKnown = true;
+        if (const int rcs = make_shade_tris(b)) return rcs;
+        c->blas.push_back(std::move(b));
+        if (blasIds) blasIds[m] = (int32_t)c->blas.size() - 1;
+        first += counts[m];
+    }
+    lap("roots read back, BLAS records", tLap);
+    const int rcTable = refresh_blas_table(c);
+    lap("BLAS table", tLap);
+    return rcTable;
+} NX_CATCH("nxhip_build_blas_batch")
+
+int nxhip_read_blas_batch(nxhip_ctx* c, int32_t firstBlasId, uint32_t count, nx_bvh8_node* nodes, uint32_t nodeCapacity, uint32_t* nodeCounts, uint32_t* primIdx, uint32_t primCapacity)
+{
+    NX_CHECK_CTX(c);
+    if (firstBlasId < 0 || (size_t)firstBlasId + count > c->blas.size()) return fail_invalid("nxhip_read_blas_batch: no such BLAS range");
+    if (count == 0) return NXHIP_OK;
+    if (kNodeStride != 5) return fail_invalid("nxhip_read_blas_batch: built with padded node records");
+    uint64_t nodeTotal = 0, primTotal = 0;
+    bool oneRun = true;  // the BLASes of one nxhip_build_blas_batch call lie back to back in their pools: one copy each for nodes and indices
+    for (uint32_t k = 0; k < count; k++) {
+        const BlasHost& b = c->blas[(size_t)firstBlasId + k];
+        if (nodeCounts) nodeCounts[k] = b.nodeCount;
+        if (k) {
+            const BlasHost& a = c->blas[(size_t)firstBlasId + k - 1];
+            oneRun = oneRun && a.nodes.pool && a.nodes.pool == b.nodes.pool && static_cast<char*>(a.nodes.p) + a.nodes.bytes == b.nodes.p &&
+                     a.triIdx.pool == b.triIdx.pool && static_cast<char*>(a.triIdx.p) + a.triIdx.bytes == b.triIdx.p;
+        }
+        nodeTotal += b.nodeCount;
+        primTotal += b.triCount;
+    }
+    if ((nodes && nodeCapacity < nodeTotal) || (primIdx && primCapacity < primTotal)) return fail_invalid("nxhip_read_blas_batch: destination too small");
+    NX_HIP(hipSetDevice(c->device));
+    NX_SYNC_ALL(c);
+    const BlasHost& b0 = c->blas[(size_t)firstBlasId];
+    if (oneRun) {
+        if (nodes) NX_HIP(hipMemcpy(nodes, b0.nodes.p, (size_t)nodeTotal * sizeof(nx_bvh8_node), hipMemcpyDeviceToHost));
+        if (primIdx) NX_HIP(hipMemcpy(primIdx, b0.triIdx.p, (size_t)primTotal * 4, hipMemcpyDeviceToHost));
+        return NXHIP_OK;
+    }
+    size_t nodeAt = 0, primAt = 0;
+    for (uint32_t k = 0; k < count; k++) {
+        const BlasHost& b = c->blas[(size_t)firstBlasId + k];
+        if (nodes) NX_HIP(hipMemcpy(nodes + nodeAt, b.nodes.p, (size_t)b.nodeCount * sizeof(nx_bvh8_node), hipMemcpyDeviceToHost));
+        if (primIdx) NX_HIP(hipMemcpy(primIdx + primAt, b.triIdx.p, (size_t)b.triCount * 4, hipMemcpyDeviceToHost));
+        nodeAt += b.nodeCount;
+        primAt += b.triCount;
+    }
+    return NXHIP_OK;
+}
+
+int nxhip_set_device_builder(nxhip_ctx* c, int clusteringRadius)
+{
+    NX_CHECK_CTX(c);
+    if (clusteringRadius < NXHIP_BUILDER_SAH || clusteringRadius > 256) return fail_invalid("nxhip_set_device_builder: NXHIP_BUILDER_SAH (-1), 0 (radix tree) or a clustering radius up to 256");
+    c->deviceBuilderRadius = clusteringRadius;
+    return NXHIP_OK;
+}
+
+int nxhip_read_blas(nxhip_ctx* c, int32_t blasId, nx_bvh8_node* nodes, uint32_t nodeCapacity, uint32_t* primIdx, uint32_t primCapacity, uint32_t* nodeCount)
+{
+    NX_CHECK_CTX(c);
+    if (blasId < 0 || (size_t)blasId >= c->blas.size()) return fail_invalid("nxhip_read_blas: no such BLAS");
+    const BlasHost& b = c->blas[(size_t)blasId];
+    if (nodeCount) *nodeCount = b.nodeCount;
+    if ((nodes && nodeCapacity < b.nodeCount) || (primIdx && primCapacity < b.triCount)) return fail_invalid("nxhip_read_blas: destination too small");
+    if (kNodeStride != 5) return fail_invalid("nxhip_read_blas: built with padded node records");
+    NX_HIP(hipSetDevice(c->device));
+    NX_SYNC_ALL(c);
+    if (nodes) NX_HIP(hipMemcpy(nodes, b.nodes.p, (size_t)b.nodeCount * sizeof(nx_bvh8_node), hipMemcpyDeviceToHost));
+    if (primIdx) NX_HIP(hipMemcpy(primIdx, b.triIdx.p, (size_t)b.triCount * 4, hipMemcpyDeviceToHost));
+    return NXHIP_OK;
+}
+
+int nxhip_debug_write_blas_node(nxhip_ctx* c, int32_t blasId, uint32_t nodeIdx, const nx_bvh8_node* node)
+{
+    NX_DEBUG_HOOK("nxhip_debug_write_blas_node");  // (first: a release library refuses whatever it is handed)
+    NX_CHECK_CTX(c);
+    if (!node || blasId < 0 || (size_t)blasId >= c->blas.size()) return fail_invalid("nxhip_debug_write_blas_node: no such BLAS");
+    BlasHost& b = c->blas[(size_t)blasId];
+    if (nodeIdx >= b.nodeCount) return fail_invalid("nxhip_debug_write_blas_node: no such node");
+    // the upload checks, as the traversal decodes a node (meta bytes), minus "children follow their parent": a node that points back
+    // at itself is what the hook exists for (the stall guard's test); everything that could index past an array is refused
+    if (const char* defect = wide_node_defect(*node, nodeIdx, b.nodeCount, b.triCount, false)) return fail_invalid(std::string("nxhip_debug_write_blas_node: ") + defect);
+    NX_HIP(hipSetDevice(c->device));
+    NX_SYNC_ALL(c);
+    NX_HIP(hipMemcpy(b.nodes.as<uint4>() + (size_t)nodeIdx * kNodeStride, node, sizeof(nx_bvh8_node), hipMemcpyHostToDevice));
+    if (nodeIdx == 0) {  // the root is also embedded in the instance records
+        std::memcpy(b.root, node, sizeof b.root);
+        b.rootKnown = true;
+        if (!c->hostInstIdx.empty()) return refresh_inst_trav(c);
+    }
+    return NXHIP_OK;
+}
+
+int nxhip_debug_set_scan_epoch(nxhip_ctx* c, uint32_t epoch)
+{
+    NX_DEBUG_HOOK("nxhip_debug_set_scan_epoch");  // (first: a release library refuses whatever it is handed)
+    NX_CHECK_CTX(c);
+    NX_SYNC_ALL(c);
+    for (uint32_t k = 0; k < slot_count(c); k++) slot_at(c, k)->scanEpoch = std::min(epoch, kScanEpochLimit - 1u);
+    return NXHIP_OK;
+}
+
+int nxhip_clear_blas(nxhip_ctx* c)
+try {
+    NX_CHECK_CTX(c);
+    NX_HIP(hipSetDevice(c->device));
+    NX_SYNC_ALL(c);
+    c->blas.clear();  // (with their refit plans)
+    c->blasRefreshPending = false;
+    c->tlasTightBoxes.release();
+    c->hostInstances.clear();
+    c->hostInstIdx.clear();
+    c->h.tlasNodes = nullptr;
+    c->h.instanceCount = 0;
+    return refresh_blas_table(c);
+} NX_CATCH("nxhip_clear_blas")
+
+int nxhip_set_tlas(nxhip_ctx* c, const nx_bvh8_node* nodes, uint32_t nodeCount, const uint32_t* instanceIdx, const nx_bvh_instance* instances,
+                   uint32_t instanceCount)
+try {
+    NX_CHECK_CTX(c);
+    if (!nodes || !instanceIdx || !instances || nodeCount == 0 || instanceCount == 0) return fail_invalid("nxhip_set_tlas: empty input");
+    if (instanceCount > kHitInstMask) return fail_invalid("nxhip_set_tlas: more than 2^29 - 1 instances (a hit record keeps the instance in 29 bits)");
+    NX_HIP(hipSetDevice(c->device));
+    for (uint32_t i = 0; i < instanceCount; i++) {
+        if (instanceIdx[i] >= instanceCount) return fail_invalid("nxhip_set_tlas: instance index out of range");
+        if (instances[i].bvhIdx >= c->blas.size()) return fail_invalid("nxhip_set_tlas: instance refers to a BLAS id that has not been uploaded");
+    }
+    // (checked here, before the context is touched: a failure must leave the previous TLAS and its traversal records in place)
+    if (const char* defect = wide_nodes_defect(nodes, nodeCount, instanceCount)) return fail_invalid(std::string("nxhip_set_tlas: ") + defect);
+    NX_SYNC_ALL(c);
+    c->tlasTightBoxes.release();  // (a tree from outside: its boxes are the records')
+    std::vector<uint4> padded = pad_nodes(nodes, nodeCount);
+    NX_ALLOC(c->tlasNodes, padded.size() * sizeof(uint4));
+    NX_ALLOC(c->tlasInstIdx, (size_t)instanceCount * 4);
+    NX_ALLOC(c->instances, (size_t)instanceCount * sizeof(nx_bvh_instance));
+    NX_HIP(hipMemcpy(c->tlasNodes.p, padded.data(), padded.size() * sizeof(uint4), hipMemcpyHostToDevice));
+    NX_HIP(hipMemcpy(c->tlasInstIdx.p, instanceIdx, (size_t)instanceCount * 4, hipMemcpyHostToDevice));
+    NX_HIP(hipMemcpy(c->instances.p, instances, (size_t)instanceCount * sizeof(nx_bvh_instance), hipMemcpyHostToDevice));
+    c->hostInstances.assign(instances, instances + instanceCount);
+    c->hostInstIdx.assign(instanceIdx, instanceIdx + instanceCount);
+    c->h.tlasNodes = c->tlasNodes.as<uint4>();
+    c->h.tlasInstIdx = c->tlasInstIdx.as<uint32_t>();
+    c->h.instances = c->instances.as<nx_bvh_instance>();
+    c->h.instanceCount = instanceCount;
+    c->stateDirty = true;
+    c->shadeInstDirty = true;
+    c->lightTableDirty = true;
+    {
+        // schedule of the device-side refit (nxhip_set_instance_transforms): node indices grouped by depth, deepest first
+        std::vector<uint32_t> depth(nodeCount, 0u);
+        uint32_t maxDepth = 0;
+        for (uint32_t i = 0; i < nodeCount; i++) {  // children follow their parent in the array: one ascending sweep
+            const nx_bvh8_node& n = nodes[i];
+            const uint32_t inner = (uint32_t)__builtin_popcount(n.imask);
+            for (uint32_t k = 0; k < inner; k++) {
+                depth[n.childBaseIdx + k] = depth[i] + 1;
+                maxDepth = std::max(maxDepth, depth[i] + 1);
+            }
+        }
+        std::vector<uint32_t> levelStart(maxDepth + 2, 0u), order(nodeCount);
+        for (uint32_t i = 0; i < nodeCount; i++) levelStart[(maxDepth - depth[i]) + 1]++;
+        for (uint32_t l = 0; l <= maxDepth; l++) levelStart[l + 1] += levelStart[l];
+        std::vector<uint32_t> cursor(levelStart.begin(), levelStart.end() - 1);
+        for (uint32_t i = 0; i < nodeCount; i++) order[cursor[maxDepth - depth[i]]++] = i;
+        std::vector<uint32_t> leafOf(instanceCount, 0u);
+        for (uint32_t k = 0; k < instanceCount; k++) leafOf[instanceIdx[k]] = k;
+        NX_ALLOC(c->refitOrder, (size_t)nodeCount * 4);
+        NX_ALLOC(c->refitLevelStart, levelStart.size() * 4);
+        NX_ALLOC(c->leafOfInstance, (size_t)instanceCount * 4);
+        NX_ALLOC(c->refitBoxes, (size_t)nodeCount * 24);
+        NX_HIP(hipMemcpy(c->refitOrder.p, order.data(), order.size() * 4, hipMemcpyHostToDevice));
+        NX_HIP(hipMemcpy(c->refitLevelStart.p, levelStart.data(), levelStart.size() * 4, hipMemcpyHostToDevice));
+        NX_HIP(hipMemcpy(c->leafOfInstance.p, leafOf.data(), leafOf.size() * 4, hipMemcpyHostToDevice));
+        c->h.leafOfInstance = c->leafOfInstance.as<uint32_t>();  // (also what a handed-over ray names its instance record by: ThinState::leaf)
+        c->refitLevels = maxDepth + 1;
+        c->tlasNodeCount = nodeCount;
+    }
+    return refresh_inst_trav(c);
+} NX_CATCH("nxhip_set_tlas")
+
+int nxhip_rebuild_tlas(nxhip_ctx* c, const nx_bvh_instance* instances, uint32_t instanceCount)
+try {
+    NX_CHECK_CTX(c);
+    if (!instances || instanceCount == 0) return fail_invalid("nxhip_rebuild_tlas: empty input");
+    if (kNodeStride != 5) return fail_invalid("nxhip_rebuild_tlas: built with padded node records");
+    for (uint32_t i = 0; i < instanceCount; i++)
+        if (instances[i].bvhIdx >= c->blas.size()) return fail_invalid("nxhip_rebuild_tlas: instance refers to a BLAS id that has not been uploaded");
+    NX_HIP(hipSetDevice(c->device));
+    NX_SYNC_ALL(c);
+    DevBuf dInst, wide, primIdx, boxes;
+    bool boxesAreTight = false;
+    NX_ALLOC(dInst, (size_t)instanceCount * sizeof(nx_bvh_instance));
+    NX_HIP(hipMemcpy(dInst.p, instances, (size_t)instanceCount * sizeof(nx_bvh_instance), hipMemcpyHostToDevice));
+    uint32_t nodeCount = 0;
+    NX_TRY(lbvh_build_tlas(c, dInst.as<nx_bvh_instance>(), instanceCount, c->deviceBuilderRadius, wide, primIdx, boxes, &boxesAreTight, &nodeCount));
+    // The tree is a few hundred nodes per thousand instances: it comes back once so that nxhip_set_tlas — range checks, the
+    // traversal records in leaf order, the schedule of the device-side refit — installs it like any other TLAS.
+    std::vector<nx_bvh8_node> nodes(nodeCount);
+    std::vector<uint32_t> idx(instanceCount);
+    NX_HIP(hipMemcpy(nodes.data(), wide.p, (size_t)nodeCount * sizeof(nx_bvh8_node), hipMemcpyDeviceToHost));
+    NX_HIP(hipMemcpy(idx.data(), primIdx.p, (size_t)instanceCount * 4, hipMemcpyDeviceToHost));
+    const int rc = nxhip_set_tlas(c, nodes.data(), nodeCount, idx.data(), instances, instanceCount);
+    // the boxes the tree was built from stay with it: the device-side refit keeps using them instead of the records' looser ones
+    if (rc == NXHIP_OK && boxesAreTight) c->tlasTightBoxes = std::move(boxes);
+    return rc;
+} NX_CATCH("nxhip_rebuild_tlas")
+
+int nxhip_read_tlas_index(nxhip_ctx* c, uint32_t* instanceIdx, uint32_t capacity, uint32_t* nodeCount)
+{
+    NX_CHECK_CTX(c);
+    if (!c->h.tlasNodes) return fail_invalid("nxhip_read_tlas_index: no TLAS has been set");
+    if (nodeCount) *nodeCount = c->tlasNodeCount;
+    if (instanceIdx) {
+        if (capacity < c->hostInstIdx.size()) return fail_invalid("nxhip_read_tlas_index: destination too small");
+        std::memcpy(instanceIdx, c->hostInstIdx.data(), c->hostInstIdx.size() * 4);
+    }
+    return NXHIP_OK;
+}
+
+// The two launches of the device-side refit, on the context's stream: BVHInstance::SetTransform for the `count` instances listed
+// in `ids` (device; matrices in c->refitMatrices; blasRefresh: each keeps its own and only what follows its BLAS's root is redone),
+// then the bottom-up sweep of the TLAS (nx_refit.hip).
+static int launch_instance_transform(nxhip_ctx* c, const uint32_t* ids, uint32_t count, bool blasRefresh)
+{
+    // (the shading records follow the matrices when they are current; a stale set is rebuilt from the device's instance table)
+    ShadeInst* shadeInst = c->shadeInstDirty ? nullptr : c->shadeInst.as<ShadeInst>();
+    const unsigned grid = std::min<unsigned>((count + 255u) / 256u, (unsigned)c->wideBlocks);
+    NX_HIP(launch_untimed(kernels::instance_transform(), grid, 256, c->stream, c->dState.as<DeviceState>(), c->instances.as<nx_bvh_instance>(), c->instTrav.as<InstTrav>(),
+                          c->leafOfInstance.as<uint32_t>(), ids, c->refitMatrices.as<float>(), count, c->tlasTightBoxes.p, shadeInst, blasRefresh ? 1u : 0u));
+    return NXHIP_OK;
+}
+
+static int launch_tlas_refit(nxhip_ctx* c)
+{
+    NX_HIP(launch_untimed(kernels::tlas_refit(), 1, 1024, c->stream, c->tlasNodes.as<nx_bvh8_node>(), c->tlasInstIdx.as<uint32_t>(), c->instances.as<nx_bvh_instance>(),
+                          c->refitOrder.as<uint32_t>(), c->refitLevelStart.as<uint32_t>(), c->refitLevels, c->refitBoxes.p, c->tlasTightBoxes.p));
+    return NXHIP_OK;
+}
+
+}  // extern "C"
+
+// What follows a BLAS's root, brought up to date after nxhip_update_blas refitted some BLASes: for every instance of one of them
+// (its matrix as it is) the world bounds, the tight box and the root-node copy of its traversal record, then ONE refit of the TLAS.
+// Deferred to the next call that needs the scene — a render, the ray-batch hooks, nxhip_read_tlas — so that ten meshes updated in
+// a frame pay it once; running it again changes nothing.  Works on a TLAS from nxhip_set_tlas and on a device-built one alike
+// (the refit schedule and the tight boxes are the ones nxhip_set_instance_transforms uses).
+int nxd::refresh_updated_blas(nxhip_ctx* c)
+{
+    if (!c->blasRefreshPending) return NXHIP_OK;
+    if (!c->h.tlasNodes || c->refitLevels == 0 || c->hostInstances.empty()) return NXHIP_OK;  // (no TLAS yet: nxhip_set_tlas reads the new roots)
+    std::vector<uint32_t> ids;
+    for (size_t i = 0; i < c->hostInstances.size(); i++) {
+        const uint32_t b = c->hostInstances[i].bvhIdx;
+        if (b < c->blas.size() && c->blas[b].refreshPending) ids.push_back((uint32_t)i);
+    }
+    for (BlasHost& b : c->blas) b.refreshPending = false;
+    c->blasRefreshPending = false;
+    const uint32_t count = (uint32_t)ids.size();
+    if (count == 0) return NXHIP_OK;
+    NX_TRY(upload_state(c));
+    // the list goes up when it differs from the last refresh's (the same meshes deforming frame after frame: never again)
+    if (ids != c->blasRefreshIds || !c->blasRefreshIdsDev.p) {
+        NX_SYNC_ALL(c);
+        if (c->blasRefreshIdsDev.bytes < (size_t)count * 4) NX_ALLOC(c->blasRefreshIdsDev, (size_t)count * 4);
+        NX_HIP(hipMemcpy(c->blasRefreshIdsDev.p, ids.data(), (size_t)count * 4, hipMemcpyHostToDevice));
+        c->blasRefreshIds.swap(ids);
+    }
+    NX_TRY(launch_instance_transform(c, c->blasRefreshIdsDev.as<uint32_t>(), count, true));
+    NX_TRY(launch_tlas_refit(c));
+    // passes on the other slots' streams must not start on the old bounds
+    if (slot_count(c) > 1) NX_HIP(hipStreamSynchronize(c->stream));
+    return NXHIP_OK;
+}
+
+extern "C" {
+
+int nxhip_set_instance_transforms(nxhip_ctx* c, const uint32_t* instanceIds, const float* transforms16, uint32_t count)
+try {
+    NX_CHECK_CTX(c);
+    if (count == 0) return NXHIP_OK;
+    if (!instanceIds || !transforms16) return fail_invalid("nxhip_set_instance_transforms: null argument");
+    if (!c->h.tlasNodes || c->refitLevels == 0) return fail_invalid("nxhip_set_instance_transforms: no TLAS has been set");
+    for (uint32_t i = 0; i < count; i++)
+        if (instanceIds[i] >= c->h.instanceCount) return fail_invalid("nxhip_set_instance_transforms: instance id out of range");
+    NX_HIP(hipSetDevice(c->device));
+    NX_TRY(upload_state(c));
+    if (slot_count(c) > 1) NX_SYNC_ALL(c);  // passes on the other slots' streams still traverse the old placement
+    if (c->refitIds.bytes < (size_t)count * 4) NX_ALLOC(c->refitIds, (size_t)count * 4);
+    if (c->refitMatrices.bytes < (size_t)count * 64) NX_ALLOC(c->refitMatrices, (size_t)count * 64);
+    // stream order does the rest: a frame already in flight finishes with the old placement, the next one sees the new
+    NX_HIP(hipMemcpyAsync(c->refitIds.p, instanceIds, (size_t)count * 4, hipMemcpyHostToDevice, c->stream));
+    NX_HIP(hipMemcpyAsync(c->refitMatrices.p, transforms16, (size_t)count * 64, hipMemcpyHostToDevice, c->stream));
+    NX_TRY(launch_instance_transform(c, c->refitIds.as<uint32_t>(), count, false));
+    NX_TRY(launch_tlas_refit(c));
+    // pageable host arrays: the copies above are staged before hipMemcpyAsync returns on this runtime, but that is not a
+    // documented guarantee — wait, the call is not on the per-frame path
+    NX_SYNC_ALL(c);
+    for (uint32_t i = 0; i < count; i++) std::memcpy(c->hostInstances[instanceIds[i]].transform.cell, transforms16 + 16 * (size_t)i, 64);
+    c->lightTableDirty = true;  // (a scale changes areas)
+    // The kernel has set each moved record's identity flag from the inverse it computed.  The scene-wide "no instance transforms
+    // a ray" flag is the host's to keep: it survives only if every new matrix is the identity itself (whose inverse, by the
+    // cofactor formula, is the identity bit for bit).
+    if (c->h.sceneFlags & kSceneAllIdentity) {
+        bool still = true;
+        for (uint32_t i = 0; i < count && still; i++) {
+            const float* m = transforms16 + 16 * (size_t)i;
+            still = rows_are_identity(m) && m[12] == 0.0f && m[13] == 0.0f && m[14] == 0.0f && m[15] == 1.0f;
+        }
+        if (!still) {
+            c->h.sceneFlags &= ~kSceneAllIdentity;
+            c->stateDirty = true;
+        }
+    }
+    return NXHIP_OK;
+} NX_CATCH("nxhip_set_instance_transforms")
+
+// The refit plan of a BLAS (BlasHost::refitOrder ...): the one place where the tree comes back to the host, once per BLAS.  Depth is
+// derived from the tree itself, root down — a device-built tree need not number children after their parents.
+static int ensure_blas_refit_plan(nxhip_ctx* c, BlasHost& b)
+{
+    if (!b.refitLevels.empty()) return NXHIP_OK;
+    if (kNodeStride != 5) return fail_invalid("nxhip_update_blas: built with padded node records");
+    NX_SYNC_ALL(c);
+    std::vector<nx_bvh8_node> nodes(b.nodeCount);
+    NX_HIP(hipMemcpy(nodes.data(), b.nodes.p, (size_t)b.nodeCount * sizeof(nx_bvh8_node), hipMemcpyDeviceToHost));
+    constexpr uint32_t kUnseen = 0xffffffffu;
+    std::vector<uint32_t> depth(b.nodeCount, kUnseen), queue;
+    queue.reserve(b.nodeCount);
+    queue.push_back(0u);
+    depth[0] = 0;
+    uint32_t maxDepth = 0;
+    for (size_t at = 0; at < queue.size(); at++) {  // breadth first: `queue` ends up sorted by depth
+        const uint32_t i = queue[at];
+        // (what the kernel will index with, checked like an upload: nothing it reads may lie outside the BLAS's arrays)
+        if (const char* defect = wide_node_defect(nodes[i], i, b.nodeCount, b.triCount, false)) return fail_invalid(std::string("nxhip_update_blas: ") + defect);
+        const uint32_t inner = (uint32_t)__builtin_popcount(nodes[i].imask);
+        for (uint32_t k = 0; k < inner; k++) {
+            const uint32_t child = nodes[i].childBaseIdx + k;
+            if (depth[child] != kUnseen) return fail_invalid("nxhip_update_blas: the BLAS is not a tree (a node has two parents)");
+            depth[child] = depth[i] + 1;
+            maxDepth = std::max(maxDepth, depth[child]);
+            queue.push_back(child);
+        }
+    }
+    // deepest level first; nodes no parent names (none in a builder's output) are left alone
+    std::vector<uint32_t> levelStart(maxDepth + 2, 0u), order(queue.size());
+    for (const uint32_t i : queue) levelStart[(maxDepth - depth[i]) + 1]++;
+    for (uint32_t l = 0; l <= maxDepth; l++) levelStart[l + 1] += levelStart[l];
+    std::vector<uint32_t> cursor(levelStart.begin(), levelStart.end() - 1);
+    for (const uint32_t i : queue) order[cursor[maxDepth - depth[i]]++] = i;
+    NX_ALLOC(b.refitOrder, order.size() * 4);
+    NX_ALLOC(b.refitLevelStart, levelStart.size() * 4);
+    NX_ALLOC(b.refitBoxes, (size_t)b.nodeCount * 32);
+    NX_HIP(hipMemcpy(b.refitOrder.p, order.data(), order.size() * 4, hipMemcpyHostToDevice));
+    NX_HIP(hipMemcpy(b.refitLevelStart.p, levelStart.data(), levelStart.size() * 4, hipMemcpyHostToDevice));
+    b.refitLevels = std::move(levelStart);
+    return NXHIP_OK;
+}
+
+// A level of more than kBlasRefitWide nodes gets a grid launch of its own: below that a single 256-thread workgroup covers it
+// in at most four strides, and a launch (~5 us of latency between dependent kernels) costs more than the stride it would save.
+constexpr uint32_t kBlasRefitWide = 1024, kBlasRefitBlock = 256;
+
+static int update_blas(nxhip_ctx* c, int32_t blasId, const void* tris, uint32_t triCount, bool fromDevice, const char* who)
+{
+    NX_CHECK_CTX(c);
+    if (blasId < 0 || (size_t)blasId >= c->blas.size()) return fail_invalid(std::string(who) + ": no such BLAS");
+    if (!tris) return fail_invalid(std::string(who) + ": null triangles");
+    BlasHost& b = c->blas[(size_t)blasId];
+    if (triCount != b.triCount) return fail_invalid(std::string(who) + ": the triangle count differs from the BLAS's (a refit keeps the topology)");
+    NX_HIP(hipSetDevice(c->device));
+    NX_TRY(ensure_blas_refit_plan(c, b));
+    if (slot_count(c) > 1) NX_SYNC_ALL(c);  // passes on the other slots' streams still traverse the old shape
+    // stream order does the rest: a pass already issued finishes with the old triangles, the next one sees the new
+    const size_t bytes = (size_t)triCount * sizeof(nx_triangle);
+    NX_HIP(hipMemcpyAsync(b.tris.p, tris, bytes, fromDevice ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
+    if (kShadeTriStride != (int)sizeof(nx_triangle))
+        NX_HIP(hipMemcpy2DAsync(b.shadeTris.p, kShadeTriStride, b.tris.p, sizeof(nx_triangle), sizeof(nx_triangle), triCount, hipMemcpyDeviceToDevice, c->stream));
+    NX_TRY(lbvh_write_isect(c, b.tris.as<nx_triangle>(), b.triIdx.as<uint32_t>(), triCount, b.isect.as<float4>()));
+    {
+        const uint32_t levels = (uint32_t)b.refitLevels.size() - 1u;
+        auto width = [&](uint32_t l) { return b.refitLevels[l + 1] - b.refitLevels[l]; };
+        for (uint32_t first = 0; first < levels;) {
+            uint32_t count = 1;
+            unsigned grid = 1;
+            if (width(first) > kBlasRefitWide) {
+                grid = std::min<unsigned>((width(first) + kBlasRefitBlock - 1u) / kBlasRefitBlock, (unsigned)(8 * std::max(1, c->numCUs)));
+            } else {
+                while (first + count < levels && width(first + count) <= kBlasRefitWide) count++;  // the run of narrow levels: one workgroup
+            }
+            NX_HIP(launch_untimed(kernels::blas_refit(), grid, kBlasRefitBlock, c->stream, b.nodes.as<uint4>(), b.triIdx.as<uint32_t>(), b.tris.as<nx_triangle>(),
+                                  b.refitOrder.as<uint32_t>(), b.refitLevelStart.as<uint32_t>(), first, count, b.refitBoxes.p));
+            first += count;
+        }
+    }
+    b.rootKnown = false;  // (read again by whoever next needs the host copy: refresh_inst_trav)
+    b.refreshPending = true;
+    c->blasRefreshPending = true;
+    c->lightTableDirty = true;
+    // a pageable host array: see nxhip_set_instance_transforms
+    if (!fromDevice) NX_HIP(hipStreamSynchronize(c->stream));
+    return NXHIP_OK;
+}
+
+int nxhip_update_blas(nxhip_ctx* c, int32_t blasId, const nx_triangle* tris, uint32_t triCount)
+try {
+    return update_blas(c, blasId, tris, triCount, false, "nxhip_update_blas");
+} NX_CATCH("nxhip_update_blas")
+
+int nxhip_update_blas_device(nxhip_ctx* c, int32_t blasId, const void* trisDevice, uint32_t triCount)
+try {
+    return update_blas(c, blasId, trisDevice, triCount, true, "nxhip_update_blas_device");
+} NX_CATCH("nxhip_update_blas_device")
+
+int nxhip_read_tlas(nxhip_ctx* c, nx_bvh8_node* nodes, uint32_t nodeCapacity, nx_bvh_instance* instances, uint32_t instanceCapacity)
+{
+    NX_CHECK_CTX(c);
+    if (!c->h.tlasNodes) return fail_invalid("nxhip_read_tlas: no TLAS has been set");
+    if ((nodes && nodeCapacity < c->tlasNodeCount) || (instances && instanceCapacity < c->h.instanceCount)) return fail_invalid("nxhip_read_tlas: destination too small");
+    NX_HIP(hipSetDevice(c->device));
+    if (const int rcRefresh = refresh_updated_blas(c)) return rcRefresh;
+    NX_SYNC_ALL(c);
+    if (nodes) {
+        if (kNodeStride == 5) NX_HIP(hipMemcpy(nodes, c->tlasNodes.p, (size_t)c->tlasNodeCount * sizeof(nx_bvh8_node), hipMemcpyDeviceToHost));
+        else return fail_invalid("nxhip_read_tlas: built with padded node records");
+    }
+    if (instances) NX_HIP(hipMemcpy(instances, c->instances.p, (size_t)c->h.instanceCount * sizeof(nx_bvh_instance), hipMemcpyDeviceToHost));
+    return NXHIP_OK;
+}
+
+int nxhip_set_materials(nxhip_ctx* c, const nx_material* materials, uint32_t count)
+try {
+    NX_CHECK_CTX(c);
+    if (!materials || count == 0) return fail_invalid("nxhip_set_materials: empty input");
+    NX_HIP(hipSetDevice(c->device));
+    NX_SYNC_ALL(c);
+    NX_ALLOC(c->materials, (size_t)count * sizeof(nx_material));
+    c->hostMaterials.assign(materials, materials + count);
+    // The device copy carries one derived flag in the padding byte behind `type` (offset 57 of the 60-byte record): the
+    // material can emit or let a path pass through, i.e. its shading may look at / must keep the path's previous vertex
+    // (nx_wavefront.hip keep_previous_vertex).  The logic kernel reads type and flag with the one load it already does.
+    std::vector<nx_material> dev(materials, materials + count);
+    for (nx_material& m : dev) {
+        // "can emit" exactly as shade_path tests it: maxcomp3(emissive * intensity) > 0 (a negative intensity with a negative
+        // component emits too)
+        const bool flag = m.emissiveMapId != -1 || m.diffuseMapId != -1 || m.opacity < 1.0f ||
+                          std::max(std::max(m.emissive[0] * m.intensity, m.emissive[1] * m.intensity), m.emissive[2] * m.intensity) > 0.0f;
+        reinterpret_cast<unsigned char*>(&m)[kMaterialFlagOffset] = flag ? 1u : 0u;
+    }
+    NX_HIP(hipMemcpy(c->materials.p, dev.data(), (size_t)count * sizeof(nx_material), hipMemcpyHostToDevice));
+    c->h.materials = c->materials.as<nx_material>();
+    c->hostMaterialsDev = dev;
+    c->stateDirty = true;
+    c->shadeInstDirty = true;  // (the records hold a copy of their instance's material)
+    c->lightTableDirty = true;
+    uint32_t mask = 0u;
+    for (const nx_material& m : dev)
+        if (m.type >= 0 && m.type <= 3) mask |= 1u << m.type;
+    if (mask != c->materialTypeMask) {  // the pass graphs hold one material kernel per type in use
+        c->materialTypeMask = mask;
+        invalidate_graph(c);
+    }
+    return NXHIP_OK;
+} NX_CATCH("nxhip_set_materials")
+
+int nxhip_set_lights(nxhip_ctx* c, const nx_light* lights, uint32_t count)
+try {
+    NX_CHECK_CTX(c);
+    NX_HIP(hipSetDevice(c->device));
+    NX_SYNC_ALL(c);
+    NX_ALLOC(c->lights, std::max<size_t>(1, count) * sizeof(nx_light));
+    if (count) NX_HIP(hipMemcpy(c->lights.p, lights, (size_t)count * sizeof(nx_light), hipMemcpyHostToDevice));
+    c->hostLights.assign(lights, lights + (lights ? count : 0));
+    c->h.lights = c->lights.as<nx_light>();
+    c->h.lightCount = count;
+    c->stateDirty = true;
+    c->lightTableDirty = true;
+    return NXHIP_OK;
+} NX_CATCH("nxhip_set_lights")
+
+static int refresh_texture_tables(nxhip_ctx* c)
+{
+    auto build = [&](std::vector<TextureHost>& v, DevBuf& table, const TextureDev*& dst) -> int {
+        std::vector<TextureDev> t(std::max<size_t>(1, v.size()));
+        std::memset(t.data(), 0, t.size() * sizeof(TextureDev));
+        for (size_t i = 0; i < v.size(); i++) t[i] = TextureDev{v[i].texels.as<uint32_t>(), v[i].width, v[i].height};
+        NX_ALLOC(table, t.size() * sizeof(TextureDev));
+        NX_HIP(hipMemcpy(table.p, t.data(), t.size() * sizeof(TextureDev), hipMemcpyHostToDevice));
+        dst = table.as<TextureDev>();
+        return NXHIP_OK;
+    };
+    NX_SYNC_ALL(c);
+    NX_TRY(build(c->diffuseMaps, c->diffuseTable, c->h.diffuseMaps));
+    NX_TRY(build(c->emissiveMaps, c->emissiveTable, c->h.emissiveMaps));
+    c->h.hdrMap = TextureDev{c->hdrMap.texels.as<uint32_t>(), c->hdrMap.width, c->hdrMap.height};
+    c->stateDirty = true;
+    return NXHIP_OK;
+}
+
+// Sampling distribution of the environment map (see nx_wavefront.hip, "Environment importance sampling"): texel weight =
+// luminance of the sRGB-decoded texel x sin(polar angle of its row) + 1e-6, accumulated in double; cdfs as float ending in
+// exactly 1; density = weight / total x width x height / (2 pi^2) = pdf per solid angle x cos(latitude).
+static int build_env_tables(nxhip_ctx* c)
+{
+    const uint32_t W = c->hdrMap.width, H = c->hdrMap.height;
+    if (!c->envSampling || W == 0 || H == 0 || c->hostHdr.size() != (size_t)W * H * 4) {
+        c->h.envSampling = 0;
+        c->h.envMarginalCdf = c->h.envRowCdf = c->h.envDensity = nullptr;
+        c->h.envMarginalGuide = c->h.envRowGuide = nullptr;
+        c->stateDirty = true;
+        return NXHIP_OK;
+    }
+    float lut[256];
+    for (int i = 0; i < 256; i++) {
+        const float x = (float)i / 255.0f;
+        lut[i] = x <= 0.04045f ? x / 12.92f : std::pow((x + 0.055f) / 1.055f, 2.4f);
+    }
+    const double pi = 3.14159265358979323846;
+    std::vector<float> marginal(H), row((size_t)W * H), density((size_t)W * H);
+    std::vector<double> rowSum(H);
+    double total = 0.0;
+    for (uint32_t y = 0; y < H; y++) {
+        const double sinTheta = std::sin(pi * ((double)y + 0.5) / (double)H);
+        double run = 0.0;
+        for (uint32_t x = 0; x < W; x++) {
+            const uint8_t* t = &c->hostHdr[4 * ((size_t)y * W + x)];
+            const double lum = 0.2126 * (double)lut[t[0]] + 0.7152 * (double)lut[t[1]] + 0.0722 * (double)lut[t[2]];
+            const double wgt = lum * sinTheta + 1e-6;
+            density[(size_t)y * W + x] = (float)wgt;
+            run += wgt;
+            row[(size_t)y * W + x] = (float)run;
+        }
+        rowSum[y] = run;
+        total += run;
+    }
+    double run = 0.0;
+    for (uint32_t y = 0; y < H; y++) {
+        for (uint32_t x = 0; x < W; x++) {
+            const size_t i = (size_t)y * W + x;
+            row[i] = x == W - 1 ? 1.0f : (float)((double)row[i] / rowSum[y]);
+            density[i] = (float)((double)density[i] / total * (double)W * (double)H / (2.0 * pi * pi));
+        }
+        run += rowSum[y];
+        marginal[y] = y == H - 1 ? 1.0f : (float)(run / total);
+    }
+    // guides for the device's cdf inversion (nx_wavefront.hip cdf_find): bracket per bucket of the random number
+    auto make_guide = [](const float* cdf, uint32_t n, uint32_t* guide) {
+        uint32_t idx = 0;
+        for (int b = 0; b <= kEnvGuide; b++) {
+            const float bound = (float)b / (float)kEnvGuide;
+            while (idx < n - 1 && !(cdf[idx] > bound)) idx++;
+            guide[b] = idx;
+        }
+    };
+    std::vector<uint32_t> marginalGuide(kEnvGuide + 1), rowGuide((size_t)H * (kEnvGuide + 1));
+    make_guide(marginal.data(), H, marginalGuide.data());
+    for (uint32_t y = 0; y < H; y++) make_guide(&row[(size_t)y * W], W, &rowGuide[(size_t)y * (kEnvGuide + 1)]);
+    NX_SYNC_ALL(c);
+    NX_ALLOC(c->envMarginalGuide, marginalGuide.size() * 4);
+    NX_ALLOC(c->envRowGuide, rowGuide.size() * 4);
+    NX_HIP(hipMemcpy(c->envMarginalGuide.p, marginalGuide.data(), marginalGuide.size() * 4, hipMemcpyHostToDevice));
+    NX_HIP(hipMemcpy(c->envRowGuide.p, rowGuide.data(), rowGuide.size() * 4, hipMemcpyHostToDevice));
+    c->h.envMarginalGuide = c->envMarginalGuide.as<uint32_t>();
+    c->h.envRowGuide = c->envRowGuide.as<uint32_t>();
+    NX_ALLOC(c->envMarginalCdf, marginal.size() * 4);
+    NX_ALLOC(c->envRowCdf, row.size() * 4);
+    NX_ALLOC(c->envDensity, density.size() * 4);
+    NX_HIP(hipMemcpy(c->envMarginalCdf.p, marginal.data(), marginal.size() * 4, hipMemcpyHostToDevice));
+    NX_HIP(hipMemcpy(c->envRowCdf.p, row.data(), row.size() * 4, hipMemcpyHostToDevice));
+    NX_HIP(hipMemcpy(c->envDensity.p, density.data(), density.size() * 4, hipMemcpyHostToDevice));
+    c->h.envSampling = 1;
+    c->h.envMarginalCdf = c->envMarginalCdf.as<float>();
+    c->h.envRowCdf = c->envRowCdf.as<float>();
+    c->h.envDensity = c->envDensity.as<float>();
+    c->stateDirty = true;
+    return NXHIP_OK;
+}
+
+int nxhip_set_env_sampling(nxhip_ctx* c, int enable)
+try {
+    NX_CHECK_CTX(c);
+    NX_HIP(hipSetDevice(c->device));
+    if (enable && !c->hdrMap.texels.p) return fail_invalid("nxhip_set_env_sampling: upload the environment map first (nxhip_upload_texture kind 2)");
+    c->envSampling = enable != 0;
+    return build_env_tables(c);
+} NX_CATCH("nxhip_set_env_sampling")
+
+int nxhip_upload_texture(nxhip_ctx* c, int kind, const uint8_t* rgba8, uint32_t width, uint32_t height, int32_t* texId)
+try {
+    NX_CHECK_CTX(c);
+    if (!rgba8 || width == 0 || height == 0 || kind < 0 || kind > 2) return fail_invalid("nxhip_upload_texture: bad arguments");
+    NX_HIP(hipSetDevice(c->device));
+    TextureHost t;
+    t.width = width;
+    t.height = height;
+    NX_ALLOC(t.texels, (size_t)width * height * 4);
+    NX_HIP(hipMemcpy(t.texels.p, rgba8, (size_t)width * height * 4, hipMemcpyHostToDevice));
+    int32_t id = 0;
+    if (kind == 0) { c->diffuseMaps.push_back(std::move(t)); id = (int32_t)c->diffuseMaps.size() - 1; }
+    else if (kind == 1) { c->emissiveMaps.push_back(std::move(t)); id = (int32_t)c->emissiveMaps.size() - 1; c->lightTableDirty = true; }
+    else {
+        NX_SYNC_ALL(c);
+        c->hdrMap = std::move(t);
+        c->hostHdr.assign(rgba8, rgba8 + (size_t)width * height * 4);
+    }
+    if (texId) *texId = id;
+    const int rc = refresh_texture_tables(c);
+    if (rc != NXHIP_OK || kind != 2) return rc;
+    return build_env_tables(c);  // a new map under an enabled sampler gets new tables
+} NX_CATCH("nxhip_upload_texture")
+
+int nxhip_clear_textures(nxhip_ctx* c)
+try {
+    NX_CHECK_CTX(c);
+    NX_HIP(hipSetDevice(c->device));
+    NX_SYNC_ALL(c);
+    c->diffuseMaps.clear();
+    c->emissiveMaps.clear();
+    c->lightMapMeans = 0;
+    c->lightTableDirty = true;
+    c->hdrMap = TextureHost();
+    c->hostHdr.clear();
+    c->envSampling = false;
+    NX_TRY(build_env_tables(c));
+    return refresh_texture_tables(c);
+} NX_CATCH("nxhip_clear_textures")
+
+}  // extern "C"
+
+uint64_t nxd::layout_stamp_scene() { return layout_stamp(); }

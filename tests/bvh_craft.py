@@ -11,7 +11,7 @@ stack position i.  The same ray going up visits the stub first and never holds m
 with them the directions.
 
 The node layout is include/nexus_pod.h's nx_bvh8_node (pod.NODE_DT); what the kernels require of a node array is
-nxhip_api.hip's wide_node_defect, and `check_nodes` below restates it."""
+nxhip_scene.hip's wide_node_defect, and `check_nodes` below restates it."""
 import ctypes as C
 import math
 

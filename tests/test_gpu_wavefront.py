@@ -270,6 +270,7 @@ def test_kernel_timing_modes_do_not_change_results(gpu_ctx_factory):
     scene.upload(ctx)
     ctx.set_modes(pod.RNG_PIXEL_KEYED, pod.COMPACT_FAST, pod.CONDUCTOR_EXTENDED)
     want = _render_gpu(ctx, 2)[-1]
+    launches = []
     for in_graph in (False, True):
         ctx.enable_kernel_timing(True, in_graph=in_graph)
         ctx.read_kernel_times(reset=True)
@@ -278,8 +279,26 @@ def test_kernel_timing_modes_do_not_change_results(gpu_ctx_factory):
         assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
         assert kt["trace"]["launches"] == 2 * 4 and kt["shadow"]["launches"] == 2 * 3 and kt["accumulate"]["launches"] == 2
         assert all(v["ms"] > 0 for k, v in kt.items() if v["launches"])
+        launches.append({k: v["launches"] for k, v in kt.items()})
+    assert launches[0] == launches[1]  # launch by launch and inside the graph: the same kernels, class by class
     ctx.enable_kernel_timing(False)
     assert np.array_equal(_render_gpu(ctx, 2)[-1].view(np.uint32), want.view(np.uint32))
+    # feature buffers and the denoiser: every launch behind a pass is counted in the accumulate class, in both modes —
+    # per frame the accumulate and the fold of the feature buffers, then the filter's gather and its two iterations
+    ctx.reset_frame_number()  # (feature buffers start with the image)
+    ctx.set_aov(True)
+    launches = []
+    for in_graph in (False, True):
+        ctx.enable_kernel_timing(True, in_graph=in_graph)
+        ctx.read_kernel_times(reset=True)
+        _render_gpu(ctx, 2)
+        ctx.denoise(iterations=2)
+        kt = ctx.read_kernel_times(reset=True)
+        assert kt["accumulate"]["launches"] == 2 * 2 + 1 + 2
+        assert all(v["ms"] > 0 for k, v in kt.items() if v["launches"])
+        launches.append({k: v["launches"] for k, v in kt.items()})
+    assert launches[0] == launches[1]
+    ctx.enable_kernel_timing(False)
 
 
 def test_cross_table_indices_are_validated_before_launch(gpu_ctx_factory):
@@ -412,6 +431,36 @@ def test_passes_in_flight_render_the_same_image(gpu_ctx_factory):
         assert np.array_equal(got[1], results[0][1])
         assert np.array_equal(got[2].view(np.uint32), results[0][2].view(np.uint32))
         assert np.array_equal(got[3], results[0][3]) and got[4] == results[0][4] and got[5] == results[0][5] == sum(schedule)
+
+
+def test_pipeline_switch_on_a_live_context(gpu_ctx_factory):
+    """The compaction mode decides the pipeline, and the pipeline which queue buffers a slot holds (racing: a second set of rays;
+    ordered: the material queues).  One context switched there and back renders, in each mode, the accumulation a fresh context
+    renders in that mode, bit for bit; with three passes in flight for the racing legs too, where slot 0's buffers are given
+    back while the extra slots allocate theirs, and come back for the ordered leg."""
+    W, H = 64, 48
+    scene = SH.material_zoo_scene(W, H, path_length=3)
+
+    def leg(ctx, compact_mode):
+        ctx.set_modes(pod.RNG_PIXEL_KEYED, compact_mode, pod.CONDUCTOR_EXTENDED)
+        ctx.reset_frame_number()
+        for _ in range(2):
+            ctx.render_frame()
+            ctx.accumulate()
+        return ctx.read_accumulation()
+
+    want = {}
+    for compact_mode in (pod.COMPACT_FAST, pod.COMPACT_ORDERED):
+        fresh = gpu_ctx_factory(W, H)
+        scene.upload(fresh)
+        want[compact_mode] = leg(fresh, compact_mode)
+    for in_flight in (1, 3):
+        ctx = gpu_ctx_factory(W, H)
+        scene.upload(ctx)
+        for compact_mode in (pod.COMPACT_FAST, pod.COMPACT_ORDERED, pod.COMPACT_FAST):
+            ctx.set_passes_in_flight(in_flight if compact_mode == pod.COMPACT_FAST else 1)
+            got = leg(ctx, compact_mode)
+            assert np.array_equal(got.view(np.uint32), want[compact_mode].view(np.uint32)), (in_flight, compact_mode)
 
 
 def test_pass_through_at_the_first_hit_keeps_the_camera_origin_for_mis(gpu_ctx_factory):
