@@ -503,6 +503,28 @@ int nxhip_tex2d_batch(nxhip_ctx *ctx, int kind, int textureId, const float *uv, 
 int nxhip_read_light_table(nxhip_ctx *ctx, float *cdf, uint32_t *entryLight, uint32_t capacity, uint32_t *lightBase, uint32_t *entries);
 int nxhip_light_pick_batch(nxhip_ctx *ctx, const float *u, uint32_t count, uint32_t *entry, float *prob);
 
+/* Test hooks of the environment lookup and of its importance sampler (nxhip_set_env_sampling).  All three refuse with
+ * NXHIP_ERR_INVALID while no environment map is uploaded; read and sample — and eval when it is asked for a pdf or a texel —
+ * also while environment sampling is off.  count == 0 returns NXHIP_OK after those checks; a null array with count > 0 is refused.
+ * read:   the three float tables as uploaded (any of them may be NULL; all NULL: only *width / *height are written, which may be
+ *         NULL too).  marginalCdf receives `height` entries, rowCdf and density width x height each; `capacityTexels` is the number
+ *         of entries every destination given can hold: >= width x height when rowCdf or density is asked for, >= height for the
+ *         marginal cdf alone, else NXHIP_ERR_INVALID.  marginalCdf[y] and rowCdf[y * width + x]:
+ *         non-decreasing, each cdf ends in exactly 1; density[y * width + x] = P(texel) x width x height / (2 pi^2), i.e. the pdf per
+ *         solid angle x cos(latitude).  P(texel) is proportional to luminance(sRGB-decoded texel) x sin(pi (y + 1/2) / height) + 1e-6,
+ *         luminance = 0.2126 R + 0.7152 G + 0.0722 B; the additive floor keeps a black map samplable.
+ * sample: r = count x 2 numbers, each in [0, 1) (anything else — NaN included — is refused on the host before anything is launched);
+ *         direction[3k..] = the unit direction the NEE draws for (r[2k], r[2k + 1]): row from the first, column from the second;
+ *         pdf[k] its pdf per solid angle (light-selection probability excluded), formed as the NEE forms it, from the direction;
+ *         texel[k] = y * width + x that the cdf inversion PICKED (the first index whose cdf exceeds r, on both axes).
+ * eval:   direction = count x 3 finite numbers (unit length is the caller's business; a non-finite component is refused);
+ *         rgb[3k..] = the background a ray leaving in that direction sees (SampleBackground, PathTracer.cu:65-83); pdf[k] (may be
+ *         NULL) = the sampler's pdf per solid angle there, density[texel] / max(cos(latitude), 1e-6); texel[k] (may be NULL) = the
+ *         texel the direction's map coordinates fall in.  With sampling off it returns the colours only: pdf and texel must be NULL. */
+int nxhip_read_env_tables(nxhip_ctx *ctx, float *marginalCdf, float *rowCdf, float *density, uint32_t capacityTexels, uint32_t *width, uint32_t *height);
+int nxhip_env_sample_batch(nxhip_ctx *ctx, const float *r, uint32_t count, float *direction, float *pdf, uint32_t *texel);
+int nxhip_env_eval_batch(nxhip_ctx *ctx, const float *direction, uint32_t count, float *rgb, float *pdf, uint32_t *texel);
+
 /* The transcendental functions of the shading path (include/nexus_fmath.h: the ONE text the kernels and the CPU oracle both
  * compile — sin / cos / exp / log / pow / atan2 / asin replacing the libm calls of Random.cuh:119-121, Microfacet.cuh:18,75,
  * PathTracer.cu:65-83, Utils.h:51-54) on host arrays: out[i] = nxf_apply(op, a[i], b[i]), op = NXF_OP_*; b may be NULL for the

@@ -32,6 +32,7 @@ HIP_SYMBOLS = [
     "nxhip_adaptive_defaults", "nxhip_set_adaptive", "nxhip_adaptive_update", "nxhip_render_adaptive", "nxhip_read_sample_counts", "nxhip_read_noise_stats",
     "nxhip_read_block_noise", "nxhip_read_active_map", "nxhip_update_blas", "nxhip_update_blas_device",
     "nxhip_set_light_sampling", "nxhip_read_light_table", "nxhip_light_pick_batch",
+    "nxhip_read_env_tables", "nxhip_env_sample_batch", "nxhip_env_eval_batch",
 ]
 HOST_SYMBOLS = [
     "nxh_bvh8_build", "nxh_tlas_build", "nxh_tlas_refit", "nxh_bvh8_refit", "nxh_bvh8_node_count", "nxh_bvh8_prim_count", "nxh_bvh8_nodes",
@@ -731,6 +732,38 @@ class Context:
     def set_env_sampling(self, on=True):
         self.L.nxhip_set_env_sampling.argtypes = [C.c_void_p, C.c_int]
         check(self.L.nxhip_set_env_sampling(self.h, 1 if on else 0), "nxhip_set_env_sampling")
+
+    def read_env_tables(self):
+        """the environment sampler's tables as uploaded: (marginalCdf float32[H], rowCdf float32[H, W], density float32[H, W])"""
+        self.L.nxhip_read_env_tables.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        w, h = C.c_uint32(0), C.c_uint32(0)
+        check(self.L.nxhip_read_env_tables(self.h, None, None, None, 0, C.byref(w), C.byref(h)), "nxhip_read_env_tables")
+        n = w.value * h.value
+        marginal, row, density = np.zeros(n, dtype=np.float32), np.zeros(n, dtype=np.float32), np.zeros(n, dtype=np.float32)
+        check(self.L.nxhip_read_env_tables(self.h, _ptr(marginal), _ptr(row), _ptr(density), n, C.byref(w), C.byref(h)), "nxhip_read_env_tables")
+        return marginal[:h.value].copy(), row.reshape(h.value, w.value), density.reshape(h.value, w.value)
+
+    def env_sample_batch(self, r):
+        """the environment sampler's draw for every pair r[k] in [0, 1)^2: (direction float32[n, 3], pdf float32[n], texel uint32[n] —
+        y * W + x that the cdf inversion picked)"""
+        r = np.ascontiguousarray(r, dtype=np.float32).reshape(-1, 2)
+        direction = np.zeros((len(r), 3), dtype=np.float32)
+        pdf = np.zeros(len(r), dtype=np.float32)
+        texel = np.zeros(len(r), dtype=np.uint32)
+        self.L.nxhip_env_sample_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        check(self.L.nxhip_env_sample_batch(self.h, _ptr(r), len(r), _ptr(direction), _ptr(pdf), _ptr(texel)), "nxhip_env_sample_batch")
+        return direction, pdf, texel
+
+    def env_eval_batch(self, directions, with_pdf=True):
+        """the background for every direction, and (with_pdf, sampler on) the sampler's pdf there and the texel the direction's map
+        coordinates fall in: (rgb float32[n, 3], pdf float32[n] or None, texel uint32[n] or None)"""
+        d = np.ascontiguousarray(directions, dtype=np.float32).reshape(-1, 3)
+        rgb = np.zeros((len(d), 3), dtype=np.float32)
+        pdf = np.zeros(len(d), dtype=np.float32) if with_pdf else None
+        texel = np.zeros(len(d), dtype=np.uint32) if with_pdf else None
+        self.L.nxhip_env_eval_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        check(self.L.nxhip_env_eval_batch(self.h, _ptr(d), len(d), _ptr(rgb), _ptr(pdf) if with_pdf else None, _ptr(texel) if with_pdf else None), "nxhip_env_eval_batch")
+        return rgb, pdf, texel
 
     def set_light_sampling(self, mode):
         """LIGHTS_UNIFORM (0, the reference's rule) or LIGHTS_POWER (1): the light sample picks among the mesh lights' triangles in

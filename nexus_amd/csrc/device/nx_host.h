@@ -31,6 +31,7 @@ const void* compose_kernel_ptr();
 const void* bsdf_hook_kernel_ptr();
 const void* fmath_hook_kernel_ptr();
 const void* tex2d_hook_kernel_ptr();
+const void* env_hook_kernel_ptr();
 const void* aov_kernel_ptr();  // nx_aov.hip
 const void* aov_fold_kernel_ptr();
 const void* denoise_gather_kernel_ptr();
@@ -119,6 +120,7 @@ inline Kernel<const float4*, U32, const U32*, float4*, U32*> compose() { return 
 inline Kernel<const nx_material*, const nx_bsdf_query*, U32, int, nx_bsdf_result*> bsdf_hook() { return {bsdf_hook_kernel_ptr()}; }  // (material, q, count, sample, out)
 inline Kernel<int, const double*, const double*, U32, double*> fmath_hook() { return {fmath_hook_kernel_ptr()}; }                   // (op, a, b, count, out)
 inline Kernel<TextureDev, const float*, const float*, U32, float4*> tex2d_hook() { return {tex2d_hook_kernel_ptr()}; }              // (t, srgbLut, uv, count, out)
+inline Kernel<State, int, const float*, U32, float*, float*, U32*> env_hook() { return {env_hook_kernel_ptr()}; }                    // (S, sample, in, count, vec, pdf, texel)
 inline StateKernel aov() { return {aov_kernel_ptr()}; }
 inline StateKernel aov_fold() { return {aov_fold_kernel_ptr()}; }
 inline Kernel<State, float4*, float4*, float4*, U32*> denoise_gather() { return {denoise_gather_kernel_ptr()}; }  // (S, colour, albedo, normalDepth, rgba8)

@@ -495,7 +495,10 @@ NXD int cdf_find(const NX_G float* cdf, const NX_G uint32_t* guide, int n, float
     return lo;
 }
 
-NXD f3 env_sample(const DeviceState* S, float r1, float r2)
+// The sampler in two steps, so that the test hook (env_hook_kernel) can say which texel the inversion PICKED: the inversion of
+// the two cdfs — row y from r1, column x of that row from r2, and the map coordinates (u, v) inside that texel — ...
+struct EnvPick { int x, y; float u, v; };
+NXD EnvPick env_invert(const DeviceState* S, float r1, float r2)
 {
     const int W = (int)S->hdrMap.width, H = (int)S->hdrMap.height;
     const int y = cdf_find(S->envMarginalCdf, S->envMarginalGuide, H, r1);
@@ -505,10 +508,19 @@ NXD f3 env_sample(const DeviceState* S, float r1, float r2)
     const int x = cdf_find(row, S->envRowGuide + (size_t)y * (size_t)(kEnvGuide + 1), W, r2);
     const float xlo = x ? row[x - 1] : 0.0f;
     const float fx = (r2 - xlo) / (row[x] - xlo);
-    const float u = ((float)x + fx) / (float)W, v = ((float)y + fy) / (float)H;
+    return EnvPick{x, y, ((float)x + fx) / (float)W, ((float)y + fy) / (float)H};
+}
+// ... and the direction of map coordinates (u, v)
+NXD f3 env_direction(float u, float v)
+{
     const float phi = (1.0f - v) * 3.14159265f - 1.57079633f, theta = u * 6.28318531f - 3.14159265f;
     const float c = nxf_cosf(phi);
     return mk3(c * nxf_cosf(theta), nxf_sinf(phi), c * nxf_sinf(theta));
+}
+NXD f3 env_sample(const DeviceState* S, float r1, float r2)
+{
+    const EnvPick p = env_invert(S, r1, r2);
+    return env_direction(p.u, p.v);
 }
 
 // lights the NEE chooses among: the mesh lights, plus the environment when it is importance sampled
@@ -1480,6 +1492,32 @@ __global__ void __launch_bounds__(kWideBlock) tex2d_hook_kernel(const TextureDev
         out[k] = tex2d(t, srgbLut, uv[2 * k], uv[2 * k + 1]);
 }
 
+// The environment lookup and its sampler on arrays (nxhip_env_sample_batch / nxhip_env_eval_batch): the product's own env_invert,
+// env_direction, env_uv, env_pdf, env_texel and sample_background.  sample != 0: in = count x 2 random numbers; the direction
+// drawn, its pdf formed as the NEE forms it (from env_uv of the direction) and the texel the inversion picked.  sample == 0: in =
+// count x 3 directions; the background colour and — pdf / texel may be null: the host passes them only with the sampler on —
+// the sampler's pdf and the texel of the direction's map coordinates.
+__global__ void __launch_bounds__(kWideBlock) env_hook_kernel(const DeviceState* __restrict__ S, const int sample, const float* __restrict__ in, const uint32_t count,
+                                                               float* __restrict__ vec, float* __restrict__ pdf, uint32_t* __restrict__ texel)
+{
+    for (uint32_t k = blockIdx.x * blockDim.x + threadIdx.x; k < count; k += gridDim.x * blockDim.x) {
+        if (sample) {
+            const EnvPick p = env_invert(S, in[2 * k], in[2 * k + 1]);
+            const f3 d = env_direction(p.u, p.v);
+            vec[3 * k] = d.x; vec[3 * k + 1] = d.y; vec[3 * k + 2] = d.z;
+            pdf[k] = env_pdf(S, d, env_uv(d));
+            texel[k] = (uint32_t)p.y * S->hdrMap.width + (uint32_t)p.x;
+        } else {
+            const f3 d = mk3(in[3 * k], in[3 * k + 1], in[3 * k + 2]);
+            const f3 c = sample_background(S, d);
+            vec[3 * k] = c.x; vec[3 * k + 1] = c.y; vec[3 * k + 2] = c.z;
+            const EnvUv uv = env_uv(d);
+            if (pdf) pdf[k] = env_pdf(S, d, uv);
+            if (texel) texel[k] = env_texel(S, uv);
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------------------
 
 // `items` per thread: kLogicItems (2) unless the caller asks for 1 — what a scene with an environment map gets, whose misses run the
@@ -1512,6 +1550,7 @@ const void* accumulate_kernel_ptr() { return (const void*)accumulate_kernel; }
 const void* compose_kernel_ptr() { return (const void*)compose_kernel; }
 const void* bsdf_hook_kernel_ptr() { return (const void*)bsdf_hook_kernel; }
 const void* tex2d_hook_kernel_ptr() { return (const void*)tex2d_hook_kernel; }
+const void* env_hook_kernel_ptr() { return (const void*)env_hook_kernel; }
 const void* fmath_hook_kernel_ptr() { return (const void*)fmath_hook_kernel; }
 
 // the device-side layouts this translation unit was compiled with (nx_device.h layout_stamp; compared by nxhip_create)

@@ -208,6 +208,77 @@ int nxhip_tex2d_batch(nxhip_ctx* c, int kind, int textureId, const float* uv, ui
     return NXHIP_OK;
 }
 
+// ---- the environment sampler's hooks (env_hook_kernel) ----------------------------------------------
+
+// what the three hooks share: a map must be there, and for everything but the colours the sampler must be on
+static int env_hook_ready(nxhip_ctx* c, const char* who, bool needSampling)
+{
+    if (!c->hdrMap.texels.p) return fail_invalid(std::string(who) + ": no environment map has been uploaded");
+    if (needSampling && !c->h.envSampling) return fail_invalid(std::string(who) + ": environment sampling is off (nxhip_set_env_sampling)");
+    return NXHIP_OK;
+}
+
+int nxhip_read_env_tables(nxhip_ctx* c, float* marginalCdf, float* rowCdf, float* density, uint32_t capacityTexels, uint32_t* width, uint32_t* height)
+try {
+    NX_CHECK_CTX(c);
+    NX_TRY(env_hook_ready(c, "nxhip_read_env_tables", true));
+    const uint32_t W = c->hdrMap.width, H = c->hdrMap.height;
+    if (width) *width = W;
+    if (height) *height = H;
+    if (!marginalCdf && !rowCdf && !density) return NXHIP_OK;
+    // (the marginal cdf has one entry per row; the two per-texel tables decide the capacity only when one of them is asked for)
+    if ((size_t)capacityTexels < ((rowCdf || density) ? (size_t)W * H : (size_t)H)) return fail_invalid("nxhip_read_env_tables: destination too small");
+    NX_HIP(hipSetDevice(c->device));
+    NX_SYNC_ALL(c);
+    if (marginalCdf) NX_HIP(hipMemcpy(marginalCdf, c->envMarginalCdf.p, (size_t)H * 4, hipMemcpyDeviceToHost));
+    if (rowCdf) NX_HIP(hipMemcpy(rowCdf, c->envRowCdf.p, (size_t)W * H * 4, hipMemcpyDeviceToHost));
+    if (density) NX_HIP(hipMemcpy(density, c->envDensity.p, (size_t)W * H * 4, hipMemcpyDeviceToHost));
+    return NXHIP_OK;
+} NX_CATCH("nxhip_read_env_tables")
+
+// in: count x inWidth floats; vec: count x 3; pdf / texel: count each, or null
+static int env_hook(nxhip_ctx* c, int sample, const float* in, uint32_t inWidth, uint32_t count, float* vec, float* pdf, uint32_t* texel)
+{
+    NX_HIP(hipSetDevice(c->device));
+    NX_TRY(upload_state(c));
+    DevBuf dIn, dVec, dPdf, dTexel;
+    NX_ALLOC(dIn, (size_t)count * inWidth * 4);
+    NX_ALLOC(dVec, (size_t)count * 12);
+    if (pdf) NX_ALLOC(dPdf, (size_t)count * 4);
+    if (texel) NX_ALLOC(dTexel, (size_t)count * 4);
+    NX_HIP(hipMemcpy(dIn.p, in, (size_t)count * inWidth * 4, hipMemcpyHostToDevice));
+    NX_HIP(launch_untimed(kernels::env_hook(), c->wideBlocks, kWideBlockThreads, c->stream, c->dState.as<DeviceState>(), sample, dIn.as<float>(), count, dVec.as<float>(),
+                          pdf ? dPdf.as<float>() : nullptr, texel ? dTexel.as<uint32_t>() : nullptr));
+    NX_SYNC_ALL(c);
+    NX_HIP(hipMemcpy(vec, dVec.p, (size_t)count * 12, hipMemcpyDeviceToHost));
+    if (pdf) NX_HIP(hipMemcpy(pdf, dPdf.p, (size_t)count * 4, hipMemcpyDeviceToHost));
+    if (texel) NX_HIP(hipMemcpy(texel, dTexel.p, (size_t)count * 4, hipMemcpyDeviceToHost));
+    return NXHIP_OK;
+}
+
+int nxhip_env_sample_batch(nxhip_ctx* c, const float* r, uint32_t count, float* direction, float* pdf, uint32_t* texel)
+try {
+    NX_CHECK_CTX(c);
+    if ((!r || !direction || !pdf || !texel) && count) return fail_invalid("nxhip_env_sample_batch: null buffer");
+    // before anything is launched: floor(r G) of an r outside [0, 1) — or of a NaN — is no bucket of the guide tables
+    for (size_t k = 0; k < (size_t)count * 2; k++)
+        if (!(r[k] >= 0.0f && r[k] < 1.0f)) return fail_invalid("nxhip_env_sample_batch: r must be in [0, 1)");
+    NX_TRY(env_hook_ready(c, "nxhip_env_sample_batch", true));
+    if (count == 0) return NXHIP_OK;
+    return env_hook(c, 1, r, 2, count, direction, pdf, texel);
+} NX_CATCH("nxhip_env_sample_batch")
+
+int nxhip_env_eval_batch(nxhip_ctx* c, const float* direction, uint32_t count, float* rgb, float* pdf, uint32_t* texel)
+try {
+    NX_CHECK_CTX(c);
+    if ((!direction || !rgb) && count) return fail_invalid("nxhip_env_eval_batch: null buffer");
+    for (size_t k = 0; k < (size_t)count * 3; k++)
+        if (!(direction[k] >= -3.0e38f && direction[k] <= 3.0e38f)) return fail_invalid("nxhip_env_eval_batch: directions must be finite");
+    NX_TRY(env_hook_ready(c, "nxhip_env_eval_batch", pdf || texel));  // (the colours alone need no sampler)
+    if (count == 0) return NXHIP_OK;
+    return env_hook(c, 0, direction, 3, count, rgb, pdf, texel);
+} NX_CATCH("nxhip_env_eval_batch")
+
 int nxhip_fmath_batch(nxhip_ctx* c, int op, const double* a, const double* b, uint32_t count, double* out)
 {
     NX_CHECK_CTX(c);

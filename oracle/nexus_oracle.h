@@ -117,6 +117,13 @@ void orc_env_distribution(const nx_texture_desc *hdr, float *marginalCdf, float 
 /* SampleBackground (PathTracer.cu:65-83) for n directions (3 floats each) -> n RGB triples */
 void orc_sample_background(const orc_scene *s, const float *directions, uint32_t n, float *rgb);
 
+/* The environment sampler on arrays — the twins of nxhip_env_sample_batch / nxhip_env_eval_batch (include/nexus_hip.h), s->hdrMap
+ * set.  sample (s->envSampling on): r = n x 2 numbers in [0, 1) -> the direction drawn, its pdf per solid angle and the texel
+ * y * width + x the inversion picked.  eval: n directions -> SampleBackground, and (pdf / texel may be NULL; s->envSampling on)
+ * the sampler's pdf there and the texel the direction's map coordinates fall in. */
+void orc_env_sample_batch(const orc_scene *s, const float *r, uint32_t n, float *direction, float *pdf, uint32_t *texel);
+void orc_env_eval_batch(const orc_scene *s, const float *direction, uint32_t n, float *rgb, float *pdf, uint32_t *texel);
+
 /* Visit counters for the roofline's algorithmic bytes. */
 typedef struct orc_trace_stats {
     uint64_t rays, nodes, tris, instances, maxStack;

@@ -198,7 +198,8 @@ static int cdf_find(const float *cdf, int n, float r)  /* first index whose cdf 
     return lo;
 }
 
-static f3 env_sample(const orc_scene *s, float r1, float r2)
+/* the sampler in two steps (orc_env_sample_batch reports the texel picked): the inversion of the two cdfs ... */
+static void env_invert(const orc_scene *s, float r1, float r2, int *px, int *py, float *pu, float *pv)
 {
     const int W = (int)s->hdrMap->width, H = (int)s->hdrMap->height;
     const int y = cdf_find(s->envMarginalCdf, H, r1);
@@ -208,10 +209,53 @@ static f3 env_sample(const orc_scene *s, float r1, float r2)
     const int x = cdf_find(row, W, r2);
     const float xlo = x ? row[x - 1] : 0.0f;
     const float fx = (r2 - xlo) / (row[x] - xlo);
-    const float u = ((float)x + fx) / (float)W, v = ((float)y + fy) / (float)H;
+    *px = x; *py = y;
+    *pu = ((float)x + fx) / (float)W; *pv = ((float)y + fy) / (float)H;
+}
+
+/* ... and the direction of map coordinates (u, v) */
+static f3 env_direction(float u, float v)
+{
     const float phi = (1.0f - v) * 3.14159265f - 1.57079633f, theta = u * 6.28318531f - 3.14159265f;
     const float c = nxf_cosf(phi);
     return mk3(c * nxf_cosf(theta), nxf_sinf(phi), c * nxf_sinf(theta));
+}
+
+static f3 env_sample(const orc_scene *s, float r1, float r2)
+{
+    int x, y;
+    float u, v;
+    env_invert(s, r1, r2, &x, &y, &u, &v);
+    return env_direction(u, v);
+}
+
+/* the twins of nxhip_env_sample_batch / nxhip_env_eval_batch (include/nexus_hip.h), over the functions above */
+void orc_env_sample_batch(const orc_scene *s, const float *r, uint32_t n, float *direction, float *pdf, uint32_t *texel)
+{
+    for (uint32_t i = 0; i < n; i++) {
+        int x, y;
+        float u, v;
+        env_invert(s, r[2 * (size_t)i], r[2 * (size_t)i + 1], &x, &y, &u, &v);
+        const f3 d = env_direction(u, v);
+        direction[3 * (size_t)i] = d.x; direction[3 * (size_t)i + 1] = d.y; direction[3 * (size_t)i + 2] = d.z;
+        pdf[i] = env_pdf(s, d);
+        texel[i] = (uint32_t)y * s->hdrMap->width + (uint32_t)x;
+    }
+}
+
+void orc_env_eval_batch(const orc_scene *s, const float *direction, uint32_t n, float *rgb, float *pdf, uint32_t *texel)
+{
+    for (uint32_t i = 0; i < n; i++) {
+        const f3 d = ld3(direction + 3 * (size_t)i);
+        const f3 c = sample_background(s, d);
+        rgb[3 * (size_t)i] = c.x; rgb[3 * (size_t)i + 1] = c.y; rgb[3 * (size_t)i + 2] = c.z;
+        if (pdf) pdf[i] = env_pdf(s, d);
+        if (texel) {
+            int x, y;
+            env_texel(s, d, &x, &y);
+            texel[i] = (uint32_t)y * s->hdrMap->width + (uint32_t)x;
+        }
+    }
 }
 
 /* lights the NEE chooses among: the mesh lights, plus the environment when it is importance sampled */

@@ -319,6 +319,34 @@ class OracleScene:
         lib().orc_sample_background(C.byref(self.c), _ptr(d), len(d), _ptr(out))
         return out
 
+    def env_sample_batch(self, r):
+        """the oracle twin of capi.Context.env_sample_batch: (direction, pdf, texel picked) for every pair r[k] in [0, 1)^2"""
+        assert self.c.envSampling
+        r = np.ascontiguousarray(r, dtype=np.float32).reshape(-1, 2)
+        direction = np.zeros((len(r), 3), dtype=np.float32)
+        pdf = np.zeros(len(r), dtype=np.float32)
+        texel = np.zeros(len(r), dtype=np.uint32)
+        lib().orc_env_sample_batch.argtypes = [C.POINTER(_Scene), C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib().orc_env_sample_batch(C.byref(self.c), _ptr(r), len(r), _ptr(direction), _ptr(pdf), _ptr(texel))
+        return direction, pdf, texel
+
+    def env_eval_batch(self, directions, with_pdf=True):
+        """the oracle twin of capi.Context.env_eval_batch: (rgb, pdf or None, texel or None)"""
+        assert self.c.hdrMap and (self.c.envSampling or not with_pdf)
+        d = np.ascontiguousarray(directions, dtype=np.float32).reshape(-1, 3)
+        rgb = np.zeros((len(d), 3), dtype=np.float32)
+        pdf = np.zeros(len(d), dtype=np.float32) if with_pdf else None
+        texel = np.zeros(len(d), dtype=np.uint32) if with_pdf else None
+        lib().orc_env_eval_batch.argtypes = [C.POINTER(_Scene), C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib().orc_env_eval_batch(C.byref(self.c), _ptr(d), len(d), _ptr(rgb), _ptr(pdf) if with_pdf else None, _ptr(texel) if with_pdf else None)
+        return rgb, pdf, texel
+
+    def env_tables(self):
+        """(marginalCdf float32[H], rowCdf float32[H, W], density float32[H, W]) of orc_env_distribution"""
+        assert self.c.envSampling
+        h = len(self.env_marginal)
+        return self.env_marginal.copy(), self.env_row.reshape(h, -1).copy(), self.env_density.reshape(h, -1).copy()
+
     def brute_any(self, rays, tmax):
         rays = np.ascontiguousarray(rays, dtype=pod.RAY_DT)
         tmax = np.ascontiguousarray(tmax, dtype=np.float32)

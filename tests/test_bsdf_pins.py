@@ -388,11 +388,9 @@ def _block_mean(values, W, H):
     return np.stack([np.bincount(ids, weights=values[:, c], minlength=nb) for c in range(3)], 1) / np.bincount(ids, minlength=nb)[:, None]
 
 
-def _floor_expectation(mat, scene, W, H, n_light=28, n_m=96):
-    """E[radiance] per block of the two estimators, from the formulas of (A) and the reference's estimator structure
-    (PathTracer.cu:213-308 NEE, :352-385 emission MIS, the BSDFs' Sample): (naive, mis), each (blocks, 3)."""
-    lob = Lobes(mat)
-    P, WI = _pixel_geometry(scene, W, H)
+def _rectangle_nodes(n_light=28):
+    """the rectangular emitter FLOOR_LIGHT as a light for _floor_expectation: seen from the floor point p (local frame), the unit
+    directions to n_light x n_light midpoints, their solid angles, the radiance and the light sample's pdf per solid angle"""
     x0, x1, z0, z1, h = FLOOR_LIGHT
     area = (x1 - x0) * (z1 - z0)
     gx = x0 + (np.arange(n_light) + 0.5) * (x1 - x0) / n_light
@@ -400,18 +398,42 @@ def _floor_expectation(mat, scene, W, H, n_light=28, n_m=96):
     lx, lz = np.meshgrid(gx, gz, indexing="ij")
     Y = np.stack([lx.reshape(-1), lz.reshape(-1), np.full(lx.size, h)], -1)  # local frame: (x, z, height)
     dA = area / Y.shape[0]
+
+    def nodes(p):
+        v = Y - p
+        d2 = np.sum(v * v, -1)
+        wo = v / np.sqrt(d2)[:, None]
+        cos_l = np.abs(wo[:, 2])                  # the emitter is parallel to the floor
+        # p_light: 1 / (lights x triangles x triangle area) x d^2 / cos (PathTracer.cu:262-266)
+        return wo, cos_l * dA / d2, FLOOR_LE, d2 / (area * cos_l)
+
+    return nodes
+
+
+def _floor_expectation(mat, scene, W, H, light=None, n_m=96, light_is_hit=True, pixels=None):
+    """E[radiance] per block of the two estimators, from the formulas of (A) and the reference's estimator structure
+    (PathTracer.cu:213-308 NEE, :352-385 emission MIS, the BSDFs' Sample): (naive, mis), each (blocks, 3).
+
+    `light(p)`: the light as quadrature nodes seen from the floor point p — (omega (n, 3) in the local frame, d(omega) (n,), radiance
+    L (scalar or (n, 3)), p_light (n,): the pdf per solid angle with which the light sample draws that direction; optionally a fifth,
+    the light pdf the BSDF sample's weight is formed with, where a test of the checker makes the two differ); default: the
+    rectangular emitter.  `light_is_hit`: a BSDF-sampled ray that finds the light HITS a surface (an emitter): it goes through the
+    roulette and, under MIS, an invalid p_light gives it weight 0; False (the environment): it leaves the scene, which is accounted
+    before the roulette, and an invalid p_light leaves it unweighted.  `pixels`: the pixels (a boolean mask) the blocks' means are
+    taken over — default all; a regular subset where the light costs many nodes."""
+    lob = Lobes(mat)
+    P, WI = _pixel_geometry(scene, W, H)
+    light = light if light is not None else _rectangle_nodes()
+    use = np.ones(len(P), bool) if pixels is None else pixels
     naive, mis = np.zeros((len(P), 3)), np.zeros((len(P), 3))
     wsum = np.ones(len(P))  # the two techniques' weights on the SPECULAR part of the integrand, summed and averaged over the highlight
     rs = np.random.RandomState(11)
     power = lambda a, b: a * a / (a * a + b * b)
-    for k in range(len(P)):
+    for k in np.flatnonzero(use):
         wi = WI[k]
-        v = Y - P[k]
-        d2 = np.sum(v * v, -1)
-        wo = v / np.sqrt(d2)[:, None]
-        cos_l = np.abs(wo[:, 2])                  # the emitter is parallel to the floor
-        dw = cos_l * dA / d2
-        p_l = d2 / (area * cos_l)                 # 1 / (lights x triangles x triangle area) x d^2 / cos (PathTracer.cu:262-266)
+        wo, dw, L, p_l, *other = light(P[k])
+        p_b = other[0] if other else p_l  # (a checker's edit: another light pdf in the BSDF sample's weight than in the light sample's)
+        L = np.asarray(L, np.float64) * np.ones((len(wo), 3))
         spec_f, spec_p, F = lob.reflection(wi, wo)
         f_e, p_e = lob.eval(wi, wo)
         sel = np.ones(len(wo)) if lob.type == pod.MAT_CONDUCTOR else F[:, 0]
@@ -426,9 +448,10 @@ def _floor_expectation(mat, scene, W, H, n_light=28, n_m=96):
         # (the furnace below is free of it: a miss is accounted before the roulette, :151-164).
         with np.errstate(divide="ignore", invalid="ignore"):
             T = np.where(p_s[:, None] > 0.0, spec_f / p_s[:, None], 0.0)
-        rr = np.minimum(1.0, 1.0 / np.maximum(T.max(-1), 1e-30))
-        n = (spec_f * (ok_s * rr * dw)[:, None]).sum(0)
-        m = (f_e * (ok_e * ok_l * power(p_l, p_e) * dw)[:, None]).sum(0) + (spec_f * (ok_s * rr * np.where(ok_l, power(p_s, p_l), 0.0) * dw)[:, None]).sum(0)
+        rr = np.minimum(1.0, 1.0 / np.maximum(T.max(-1), 1e-30)) if light_is_hit else 1.0
+        w_s = np.where(p_b > 1e-4, power(p_s, p_b), 0.0 if light_is_hit else 1.0)  # the BSDF sample's weight under MIS
+        n = (spec_f * L * (ok_s * rr * dw)[:, None]).sum(0)
+        m = (f_e * L * (ok_e * ok_l * power(p_l, p_e) * dw)[:, None]).sum(0) + (spec_f * L * (ok_s * rr * w_s * dw)[:, None]).sum(0)
         g = spec_f[:, 1] * ok_l * dw
         if g.sum() > 0.0:
             wsum[k] = float((g * (ok_e * power(p_l, p_e) + ok_s * power(p_s, p_l))).sum() / g.sum())
@@ -445,9 +468,13 @@ def _floor_expectation(mat, scene, W, H, n_light=28, n_m=96):
             ok_d = p_d > 1e-4
             pick = ((1.0 - Fm)[:, None] * ok_d).mean(0)                                 # E_m[(1 - F_m) valid]
             pick_w = ((1.0 - Fm)[:, None] * ok_d * np.where(ok_l[None, :], power(p_d, p_l[None, :]), 0.0)).mean(0)
-            n = n + lob.albedo * (pick * c * dw).sum()
-            m = m + lob.albedo * (pick_w * c * dw).sum()
-        naive[k], mis[k] = FLOOR_LE * n, FLOOR_LE * m
+            n = n + lob.albedo * (L * (pick * c * dw)[:, None]).sum(0)
+            m = m + lob.albedo * (L * (pick_w * c * dw)[:, None]).sum(0)
+        naive[k], mis[k] = n, m
+    if pixels is not None:  # the blocks' means over the chosen pixels only
+        count = _block_mean(np.repeat(use[:, None].astype(np.float64), 3, 1), W, H)
+        assert np.all(count > 0)
+        return _block_mean(naive * use[:, None], W, H) / count, _block_mean(mis * use[:, None], W, H) / count, _block_mean(wsum[:, None] * use[:, None] * np.ones(3), W, H)[:, 0] / count[:, 0]
     return _block_mean(naive, W, H), _block_mean(mis, W, H), _block_mean(np.repeat(wsum[:, None], 3, 1), W, H)[:, 0]
 
 
@@ -465,7 +492,7 @@ def _check_glossy_floor(estimate, frames, rel_se_bar):
         want_naive, want_mis, wsum = _floor_expectation(mat, _floor_scene(e.W, e.H, mat, True), e.W, e.H)
         lit = want_naive.max(1) > 0.05 * want_naive.max()
         assert lit.mean() > 0.3, "the camera must see the emitter's reflection"
-        assert np.median((est[True].se / want_mis)[lit]) < rel_se_bar, "the estimate is too noisy for its pass to mean anything"
+        assert np.median(est[True].se[lit] / want_mis[lit]) < rel_se_bar, "the estimate is too noisy for its pass to mean anything"
         ratio = (want_mis[lit] / want_naive[lit])
         print("%s floor: predicted E[NEE + MIS] / E[BSDF sampling] over the lit blocks: min %.3f, mean %.3f, max %.3f" % (name, ratio.min(), ratio.mean(), ratio.max()))
         # (1 %: pixel-centre evaluation of the expectation inside a block, the quadrature over the emitter, the offset of the shadow rays' origins)

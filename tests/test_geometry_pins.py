@@ -45,8 +45,8 @@ a bound of its own: they see a dark part of the ramp, where a shift of half a te
 
 Observed where: every figure above on the CPU (oracle walk and oracle brute force alike; host inverse through instance_init,
 mat4_invert and the oracle's).  On an MI355X all 15 device cases gave the same figures to every printed digit — the records are
-the oracle's bit for bit — including the device-side inverse after set_instance_transforms; the seam / pole directions are CPU
-only (the device has no entry point for a lone background lookup).
+the oracle's bit for bit — including the device-side inverse after set_instance_transforms; the seam / pole directions go
+through the device's own lookup too (nxhip_env_eval_batch).
 
 The inputs were changed once, not a cap: hitDistance is compared relatively, but its error is absolute (about 1e-7 here: the
 rounding of the origin's coordinates, eps x |origin| / |direction| in object space), so rays starting 1e-4 in front of the triangle
@@ -519,3 +519,14 @@ def test_gpu_features_and_environment(gpu_ctx_factory, order, entry):
                 dst[pm] = src
             albedo, nd, radiance = rows
         _check_features(albedo, nd, radiance, f["frames"][frame], "device, order %d, entry points %s, frame %d" % (order, entry, frame))
+
+
+@pytest.mark.gpu
+def test_gpu_environment_at_the_seam_and_the_poles(gpu_ctx_factory):
+    """the device twin of test_oracle_environment_at_the_seam_and_the_poles: the product's own background lookup on lone directions"""
+    f = _scene_f()
+    ctx = gpu_ctx_factory(W, H)
+    f["scene"].upload(ctx)
+    d = _aimed_directions()
+    rgb, _pdf, _texel = ctx.env_eval_batch(d, with_pdf=False)
+    _check_environment(rgb, d, f["scene"].hdr_map, "device, seam and poles")

@@ -115,6 +115,76 @@ def test_settings_modes_and_viewport_arguments(gpu_ctx_factory):
     assert SH.frames_identical(ctx.read_radiance(), w.radiance(), "after the refused calls")
 
 
+def test_environment_hooks_refuse_what_they_cannot_answer(gpu_ctx_factory):
+    """nxhip_read_env_tables / nxhip_env_sample_batch / nxhip_env_eval_batch: no map, sampler off, null arrays, numbers outside [0, 1),
+    non-finite directions, a destination too small — a status each, nothing launched; count == 0 is fine"""
+    import ctypes as C
+
+    ctx = gpu_ctx_factory(16, 16)
+    L = ctx.L
+    d = np.array([[0.0, 1.0, 0.0], [0.6, 0.0, -0.8]], np.float32)
+    r = np.array([[0.5, 0.25]], np.float32)
+    for call in (ctx.read_env_tables, lambda: ctx.env_sample_batch(r), lambda: ctx.env_eval_batch(d), lambda: ctx.env_eval_batch(d, with_pdf=False),
+                 lambda: ctx.env_sample_batch(np.zeros((0, 2), np.float32))):
+        with pytest.raises(NexusError, match="no environment map"):
+            call()
+    ctx.upload_texture("hdr", SH.checker_texture(16, 8, 5))
+    rgb, pdf, texel = ctx.env_eval_batch(d, with_pdf=False)  # the colours alone need no sampler
+    assert pdf is None and texel is None and np.all(np.isfinite(rgb)) and rgb.max() > 0
+    for call in (ctx.read_env_tables, lambda: ctx.env_sample_batch(r), lambda: ctx.env_eval_batch(d)):
+        with pytest.raises(NexusError, match="sampling is off"):
+            call()
+    ctx.set_env_sampling(True)
+    marginal, row, density = ctx.read_env_tables()
+    assert marginal.shape == (8,) and row.shape == (8, 16) and density.shape == (8, 16)
+    for bad in (1.0, -0.125, 2.0, np.nan, np.inf):
+        for column in (0, 1):
+            rr = np.array([[0.5, 0.5], [0.5, 0.5]], np.float32)
+            rr[1, column] = bad
+            with pytest.raises(NexusError, match=r"r must be in \[0, 1\)"):
+                ctx.env_sample_batch(rr)
+    for bad in (np.nan, np.inf, -np.inf):
+        dd = d.copy()
+        dd[1, 2] = bad
+        with pytest.raises(NexusError, match="finite"):
+            ctx.env_eval_batch(dd)
+    # count == 0
+    assert [len(a) for a in ctx.env_sample_batch(np.zeros((0, 2), np.float32))] == [0, 0, 0]
+    assert len(ctx.env_eval_batch(np.zeros((0, 3), np.float32))[0]) == 0
+    # null arrays with count > 0, a destination too small, a null context
+    vp, u32 = C.c_void_p, C.c_uint32
+    L.nxhip_env_sample_batch.argtypes = [vp, vp, u32, vp, vp, vp]
+    L.nxhip_env_eval_batch.argtypes = [vp, vp, u32, vp, vp, vp]
+    L.nxhip_read_env_tables.argtypes = [vp, vp, vp, vp, u32, vp, vp]
+    out3, out1, outi = np.zeros(3, np.float32), np.zeros(1, np.float32), np.zeros(1, np.uint32)
+    p = capi._ptr
+    assert L.nxhip_env_sample_batch(ctx.h, None, 1, p(out3), p(out1), p(outi)) == 1
+    assert L.nxhip_env_sample_batch(ctx.h, p(r), 1, None, p(out1), p(outi)) == 1
+    assert L.nxhip_env_sample_batch(ctx.h, p(r), 1, p(out3), None, p(outi)) == 1
+    assert L.nxhip_env_sample_batch(ctx.h, p(r), 1, p(out3), p(out1), None) == 1
+    assert L.nxhip_env_eval_batch(ctx.h, None, 1, p(out3), None, None) == 1
+    assert L.nxhip_env_eval_batch(ctx.h, p(d), 1, None, None, None) == 1
+    assert L.nxhip_env_eval_batch(ctx.h, None, 0, None, None, None) == 0
+    small = np.zeros(127, np.float32)
+    assert L.nxhip_read_env_tables(ctx.h, None, p(small), None, 127, None, None) == 1
+    assert b"too small" in capi.lib().nxhip_last_error()
+    rows = np.zeros(8, np.float32)  # the marginal cdf alone: one entry per row is room enough
+    assert L.nxhip_read_env_tables(ctx.h, p(rows), None, None, 8, None, None) == 0 and np.array_equal(rows, marginal)
+    assert L.nxhip_read_env_tables(ctx.h, p(rows), None, None, 7, None, None) == 1
+    assert L.nxhip_read_env_tables(None, None, None, None, 0, None, None) == 1
+    assert L.nxhip_env_sample_batch(None, p(r), 1, p(out3), p(out1), p(outi)) == 1
+    assert L.nxhip_env_eval_batch(None, p(d), 1, p(out3), None, None) == 1
+    # the context is undisturbed, and turning the sampler off is heard by the hooks
+    assert np.array_equal(ctx.env_eval_batch(d, with_pdf=False)[0], rgb)
+    assert np.all(ctx.env_eval_batch(d)[1] > 0)
+    ctx.set_env_sampling(False)
+    with pytest.raises(NexusError, match="sampling is off"):
+        ctx.env_sample_batch(r)
+    ctx.clear_textures()
+    with pytest.raises(NexusError, match="no environment map"):
+        ctx.env_eval_batch(d, with_pdf=False)
+
+
 def test_contexts_are_independent_and_closing_is_idempotent(gpu_ctx_factory):
     a = gpu_ctx_factory(16, 16)
     b = gpu_ctx_factory(16, 16)

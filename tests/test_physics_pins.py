@@ -58,9 +58,10 @@ class _Estimate:
         return np.sqrt(var / self.n)
 
 
-def _oracle_estimate(scene, W, H, frames, threads=8):
+def _oracle_estimate(scene, W, H, frames, threads=8, estimate=None):
+    """`estimate`: the class that collects the frames (default _Estimate: 16 x 16 blocks)"""
     w = O.Wavefront(scene.oracle(), W * H, None, pod.RNG_PIXEL_KEYED, pod.CONDUCTOR_REFERENCE)
-    e = _Estimate(W, H)
+    e = (estimate or _Estimate)(W, H)
     for f in range(1, frames + 1):
         w.render(f, threads=threads)
         e.add(w.radiance())
@@ -68,12 +69,12 @@ def _oracle_estimate(scene, W, H, frames, threads=8):
     return e
 
 
-def _gpu_estimate(ctx, scene, W, H, frames, per_pass=64):
+def _gpu_estimate(ctx, scene, W, H, frames, per_pass=64, estimate=None):
     scene.upload(ctx)
     ctx.set_modes(pod.RNG_PIXEL_KEYED, pod.COMPACT_FAST, pod.CONDUCTOR_REFERENCE)
     ctx.set_frames_per_pass(per_pass)
     ctx.reset_frame_number()
-    e = _Estimate(W, H)
+    e = (estimate or _Estimate)(W, H)
     assert frames % per_pass == 0
     for _ in range(frames // per_pass):
         ctx.render_frame()
