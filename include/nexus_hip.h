@@ -249,6 +249,10 @@ int nxhip_set_entry_points(nxhip_ctx *ctx, int on);
  * int32 sp, instSp, leafSlot, steps, the instance's BLAS pointers, then the consumed triangle's record and bookkeeping) — a test
  * hook: how many node steps the walk saved per run, which triangles it consumed or skipped.  *count = number of runs. */
 int nxhip_read_entry_states(nxhip_ctx *ctx, void *out, uint32_t capacityRuns, uint32_t *count);
+/* Test hook: how many times the context has launched the entry-state walk since it was created.  A slot's table outlives the pass:
+ * it is walked again, in front of the slot's next pass, only after a call that changed something the walk reads (camera, pixel set,
+ * TLAS, instances, BLASes, materials' types, entry points switched on) — one launch per slot that renders afterwards. */
+int nxhip_debug_entry_walks(nxhip_ctx *ctx, uint64_t *count);
 /* Test hook for the thin kernel (nx_trace.hip): the hand-over rule — at most `lanes` busy lanes of a dry wave for at least `iters`
  * iterations (product: 16 / 16; 64 / 0 makes every wave hand over the first rays it takes, after one iteration) — and whether the ray-batch
  * hooks (nxhip_trace_batch, nxhip_trace_shadow_batch) use the hand-over + thin launch too, so that a test can put arbitrary rays

@@ -19,6 +19,10 @@
 // hit-distance interval bounds the box tests behind it.  It ends at an undecided child or triangle, at a second triangle every ray
 // hits in front of the first, or at its depth limit.  What it leaves is a loop-top state of the traversal.
 //
+// The states depend on the camera, the pixel set and the scene — not on the frame number or the pass size — so a table outlives the
+// pass: the host launches the walk on a slot's stream, in front of the slot's next pass, only after a call that changed one of its
+// inputs (nxhip_render.hip walk_entry_states; the list: nx_context.h entryGeneration), and every pass until then reads the table.
+//
 // Conditions, checked here: pinhole camera (no lens: one origin), one octant for the whole bundle, an origin without negative zero,
 // infinity, NaN or denormal components, and — to go through an instance — a scene of identity instances (the ray is then the
 // same in the BLAS's frame; a transformed instance ends the walk in front of it).
@@ -486,8 +490,9 @@ NXD void walk_run(const DeviceState* __restrict__ S, const uint32_t run, const i
     store();
 }
 
-// Eight lanes per run, eight runs per workgroup.  The table is the SLOT's own (DeviceState::entry / entryRuns of the slot whose pass
-// graph this launch is part of): written here, read by the same pass's primary closest-hit launch one level later, by nobody else.
+// Eight lanes per run, eight runs per workgroup.  The table is the SLOT's own (DeviceState::entry / entryRuns of the slot on whose
+// stream this launch is issued — a plain launch, no node of the pass graph): written here, read by the primary closest-hit launches
+// of the slot's passes behind it in stream order, by nobody else.
 __global__ void __launch_bounds__(64) entry_state_kernel(const DeviceState* __restrict__ S)
 {
     const uint32_t run = (blockIdx.x * blockDim.x + threadIdx.x) / (unsigned)kGroup;

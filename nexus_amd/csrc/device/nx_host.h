@@ -251,6 +251,9 @@ inline bool scan_pipeline(const nxhip_ctx* c) { return c->h.compactMode == NX_CO
 // the size of the image and of every read-back.
 inline uint32_t pass_pixels(const nxhip_ctx* c) { return c->adaptive ? c->activeCount : c->localCount; }
 
+// Something the entry-state walk reads has changed (the list: nxhip_ctx::entryGeneration): every slot's table is stale from here on.
+inline void entry_inputs_changed(nxhip_ctx* c) { c->entryGeneration++; }
+
 // nxhip_api.hip: the context's state block, queues and pixel set
 void invalidate_graph(nxhip_ctx* c);
 int upload_state(nxhip_ctx* c);
@@ -266,7 +269,7 @@ int refresh_shade_inst(nxhip_ctx* c);
 int refresh_updated_blas(nxhip_ctx* c);
 // nxhip_render.hip
 int check_scene_ready(nxhip_ctx* c);
-int launch_now(nxhip_ctx* c, const Launch& l);
+int launch_now(nxhip_ctx* c, const Launch& l, hipStream_t stream = nullptr);  // (stream: the context's own unless given)
 int render_pass(nxhip_ctx* c, uint32_t framesArg);
 int read_float4_as_float3(nxhip_ctx* c, const void* dev, uint32_t count, float* dst);
 // nxhip_features.hip

@@ -319,6 +319,7 @@ void nxd::publish_pixel_set(nxhip_ctx* c)
     h.framesPerPass = c->framesPerPass;
     h.pathCount = h.localCount * c->framesPerPass;
     c->stateDirty = true;
+    entry_inputs_changed(c);  // (the runs of 64 the entry states are walked for: count, map — its content too: the adaptive set is refilled in place)
 }
 
 // Everything sized by the pixel set of this context: queues for localCount * framesPerPass paths and a zeroed image.
@@ -679,6 +680,7 @@ int nxhip_set_camera(nxhip_ctx* c, const nx_camera* camera)
     if (std::memcmp(&c->h.camera, camera, sizeof *camera) == 0) return NXHIP_OK;
     c->h.camera = *camera;
     c->stateDirty = true;
+    entry_inputs_changed(c);
     return NXHIP_OK;
 }
 

@@ -359,6 +359,15 @@ int nxhip_read_kernel_times(nxhip_ctx* c, nxhip_kernel_times* out, int reset)
     return NXHIP_OK;
 }
 
+int nxhip_debug_entry_walks(nxhip_ctx* c, uint64_t* count)
+{
+    NX_DEBUG_HOOK("nxhip_debug_entry_walks");  // (first: a release library refuses whatever it is handed)
+    NX_CHECK_CTX(c);
+    if (!count) return fail_invalid("nxhip_debug_entry_walks: null count");
+    *count = c->entryWalks;  // (host bookkeeping: nothing to wait for)
+    return NXHIP_OK;
+}
+
 }  // extern "C"
 
 uint64_t nxd::layout_stamp_hooks() { return layout_stamp(); }

@@ -194,13 +194,10 @@ std::vector<std::vector<Launch>> frame_levels(nxhip_ctx* c, PassSlot* q)
     const int wideThreads = kWideBlockThreads;
     std::vector<std::vector<Launch>> levels;
     levels.push_back({make_launch(kernels::generate(), wide, wideThreads, NXHIP_K_GENERATE, S)});
+    // (the entry states the primary launch below installs are not a pass's work: the slot's table is walked in front of the pass
+    //  that finds it stale — walk_entry_states — and read by every pass until an input of the walk changes)
     const bool entry = (pass_flavor(c) & kFlavorEntry) != 0;
     const bool lightPower = (pass_flavor(c) & kFlavorLightPower) != 0;
-    if (entry) {  // beside the generate kernel: the entry states of the primary rays' runs (nx_entry.hip), read by the launch below
-        // (table and count come from the slot's DeviceState: a graph node holds no pointer that a re-allocation could leave dangling)
-        // (eight lanes per run: a workgroup of 64 walks eight runs)
-        levels.back().push_back(make_launch(kernels::entry_state(), (int)((q->entryRuns + 7u) / 8u), 64, NXHIP_K_GENERATE, S));
-    }
     const int traceBlocks = trace_blocks(c, c->traceBlocks), shadowBlocks = trace_blocks(c, c->shadowBlocks);
     // (the dry waves of a pass's trace launches may hand their last long rays to the thin kernel: nx_trace.hip)
     const int thinFlag = (pass_flavor(c) & kFlavorThin) ? kTraceThinFlag : 0;
@@ -292,10 +289,11 @@ std::vector<std::vector<Launch>> frame_levels(nxhip_ctx* c, PassSlot* q)
 
 }  // namespace
 
-// Issue one launch on the context's stream; with kernel timing on, between an event pair of its own that joins the pool only once
+// Issue one launch on the context's stream (or the slot's, when given); with kernel timing on, between an event pair of its own that joins the pool only once
 // everything has been issued (a failure leaves no entry behind for nxhip_read_kernel_times to trip over).
-int nxd::launch_now(nxhip_ctx* c, const Launch& l)
+int nxd::launch_now(nxhip_ctx* c, const Launch& l, hipStream_t stream)
 {
+    if (!stream) stream = c->stream;
     void* params[Launch::kMaxArgs];
     l.params(params);
     KernelTimer t;
@@ -304,15 +302,15 @@ int nxd::launch_now(nxhip_ctx* c, const Launch& l)
         if (c->timingEnabled) {
             NX_HIP(hipEventCreate(&t.start));
             NX_HIP(hipEventCreate(&t.stop));
-            NX_HIP(hipEventRecord(t.start, c->stream));
+            NX_HIP(hipEventRecord(t.start, stream));
         }
-        NX_HIP(hipLaunchKernel(l.fn, l.grid, l.block, params, 0, c->stream));
+        NX_HIP(hipLaunchKernel(l.fn, l.grid, l.block, params, 0, stream));
         // Any launch outside a pass graph that can set the slot's error word (traversal / ordered-scan stall guards) makes the pinned copy
         // the last pass left behind stale: nxhip_sync then reads the word itself.  Here, once, for every such launch — the eager timing
         // path, the ray-batch hooks, the thin kernel behind them and whatever comes later (accumulate cannot set it and is issued after
         // every pass: it keeps the copy fresh).
         if (l.klass != NXHIP_K_ACCUMULATE) c->errorFresh = false;
-        if (c->timingEnabled) NX_HIP(hipEventRecord(t.stop, c->stream));
+        if (c->timingEnabled) NX_HIP(hipEventRecord(t.stop, stream));
         return NXHIP_OK;
     };
     const int rc = issue();
@@ -411,18 +409,33 @@ static int pass_graph(nxhip_ctx* c, PassSlot* q, hipGraphExec_t* execOut)
 // puts behind them, e.g. the multi-GPU gather), so that no pass ever queues behind the accumulate of its predecessor.
 static PassSlot* render_slot(nxhip_ctx* c, uint32_t R, uint32_t i) { return R <= 1 ? static_cast<PassSlot*>(c) : c->extra[i].get(); }
 
-// Entry points on: slot q has a table of one state per run of 64 local pixels.  The graph instances of a slot are keyed by shape,
-// not by table size, and entry_state_kernel's grid is the run count: a slot whose run count changes drops its graphs.
+// Entry points on: slot q has a table of one state per run of 64 local pixels (no graph node depends on its size: the walk is a
+// plain launch).
 static int ensure_entry_table(nxhip_ctx* c, PassSlot* q)
 {
     const uint32_t runs = (c->localCount + 63u) / 64u;
     if (q->entryRuns == runs && q->entryTable.p) return NXHIP_OK;
     NX_SYNC_ALL(c);
-    if (q->entryRuns != runs) invalidate_graph(c);
     NX_ALLOC(q->entryTable, (size_t)std::max(1u, runs) * sizeof(EntryState));
     NX_HIP(hipMemset(q->entryTable.p, 0, (size_t)std::max(1u, runs) * sizeof(EntryState)));  // (steps 0: "start at the root")
     q->entryRuns = runs;
+    q->entryStamp = 0;  // (never walked)
     c->stateDirty = true;
+    return NXHIP_OK;
+}
+
+// The slot's entry states for the camera, pixel set and scene as they are now: entry_state_kernel (nx_entry.hip; eight lanes per run, a
+// workgroup of 64 walks eight runs) as a plain launch on the slot's stream, in front of the pass that is about to read the table —
+// only when something the walk reads has changed since the table was written (nxhip_ctx::entryGeneration).  The slot's device state
+// and everything it points to are current by now (upload_state, refresh_shade_inst, refresh_updated_blas have run); the passes this
+// slot has issued are ahead of the launch in stream order, the other slots have tables of their own.
+static int walk_entry_states(nxhip_ctx* c, PassSlot* q)
+{
+    if (q->entryStamp == c->entryGeneration) return NXHIP_OK;
+    const Launch walk = make_launch(kernels::entry_state(), (int)((std::max(1u, q->entryRuns) + 7u) / 8u), 64, NXHIP_K_GENERATE, q->dState.as<DeviceState>());
+    NX_TRY(launch_now(c, walk, q->stream));
+    q->entryStamp = c->entryGeneration;
+    c->entryWalks++;
     return NXHIP_OK;
 }
 
@@ -496,6 +509,7 @@ try {
         q->awaitingAccumulate = false;
     }
     NX_TRY(launch_begin_frame(c, q, frames, frameLast));
+    if (c->entryPoints) NX_TRY(walk_entry_states(c, q));
     if (c->timingEnabled && c->timingMode == 1) {
         // eager path: one event pair per launch, launches strictly in level order on one stream
         auto levels = frame_levels(c, q);
@@ -611,6 +625,7 @@ int nxhip_set_entry_points(nxhip_ctx* c, int on)
     NX_HIP(hipSetDevice(c->device));
     NX_SYNC_ALL(c);
     c->entryPoints = on != 0;
+    entry_inputs_changed(c);
     if (!c->entryPoints)
         for (uint32_t k = 0; k < slot_count(c); k++) {
             slot_at(c, k)->entryTable.release();
@@ -703,7 +718,8 @@ int nxhip_read_entry_states(nxhip_ctx* c, void* out, uint32_t capacityRuns, uint
     if (!count) return fail_invalid("nxhip_read_entry_states: null count");
     NX_HIP(hipSetDevice(c->device));
     NX_SYNC_ALL(c);
-    // the table of the slot that rendered last (every slot's table holds the same states: camera, pixel set and scene are the context's)
+    // the table of the slot that rendered last (every slot's table holds the same states: camera, pixel set and scene are the context's,
+    // and a slot walks again before it renders with a table older than their last change)
     const PassSlot* q = c->lastRendered ? c->lastRendered : static_cast<const PassSlot*>(c);
     const bool have = c->entryPoints && q->entryTable.p;
     *count = have ? q->entryRuns : 0u;

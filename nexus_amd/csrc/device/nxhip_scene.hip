@@ -56,6 +56,7 @@ static int refresh_blas_table(nxhip_ctx* c)
     c->h.blas = c->blasTable.as<BlasDev>();
     c->stateDirty = true;
     c->shadeInstDirty = true;  // (the records hold the BLASes' triangle arrays)
+    entry_inputs_changed(c);
     return NXHIP_OK;
 }
 
@@ -91,6 +92,7 @@ int nxd::refresh_shade_inst(nxhip_ctx* c)
     c->shadeInstDirty = false;
     // the traversal records' material codes follow the shading records (nx_refit.hip inst_code_kernel)
     if (c->instTrav.p && !c->hostInstIdx.empty()) {
+        entry_inputs_changed(c);  // (an entry state carries its instance's index + material code: InstTrav::instIdx)
         const uint32_t count = (uint32_t)c->hostInstIdx.size();
         NX_HIP(launch_untimed(kernels::inst_code(), (count + 255u) / 256u, 256, c->stream, c->dState.as<DeviceState>(), c->instTrav.as<InstTrav>(), c->shadeInst.as<ShadeInst>(), count));
         NX_HIP(hipStreamSynchronize(c->stream));
@@ -133,6 +135,7 @@ static int refresh_inst_trav(nxhip_ctx* c)
     c->h.instTrav = c->instTrav.as<InstTrav>();
     c->h.sceneFlags = allIdentity ? kSceneAllIdentity : 0u;
     c->stateDirty = true;
+    entry_inputs_changed(c);
     c->shadeInstDirty = true;  // (the records' material codes are written when the shading records are rebuilt: refresh_shade_inst)
     return NXHIP_OK;
 }
@@ -419,6 +422,7 @@ int nxhip_debug_write_blas_node(nxhip_ctx* c, int32_t blasId, uint32_t nodeIdx, 
     NX_HIP(hipSetDevice(c->device));
     NX_SYNC_ALL(c);
     NX_HIP(hipMemcpy(b.nodes.as<uint4>() + (size_t)nodeIdx * kNodeStride, node, sizeof(nx_bvh8_node), hipMemcpyHostToDevice));
+    entry_inputs_changed(c);
     if (nodeIdx == 0) {  // the root is also embedded in the instance records
         std::memcpy(b.root, node, sizeof b.root);
         b.rootKnown = true;
@@ -482,6 +486,7 @@ try {
     c->stateDirty = true;
     c->shadeInstDirty = true;
     c->lightTableDirty = true;
+    entry_inputs_changed(c);
     {
         // schedule of the device-side refit (nxhip_set_instance_transforms): node indices grouped by depth, deepest first
         std::vector<uint32_t> depth(nodeCount, 0u);
@@ -604,6 +609,7 @@ int nxd::refresh_updated_blas(nxhip_ctx* c)
     }
     NX_TRY(launch_instance_transform(c, c->blasRefreshIdsDev.as<uint32_t>(), count, true));
     NX_TRY(launch_tlas_refit(c));
+    entry_inputs_changed(c);  // (the instances' root copies and the TLAS's boxes)
     // passes on the other slots' streams must not start on the old bounds
     if (slot_count(c) > 1) NX_HIP(hipStreamSynchronize(c->stream));
     return NXHIP_OK;
@@ -629,6 +635,7 @@ try {
     NX_HIP(hipMemcpyAsync(c->refitMatrices.p, transforms16, (size_t)count * 64, hipMemcpyHostToDevice, c->stream));
     NX_TRY(launch_instance_transform(c, c->refitIds.as<uint32_t>(), count, false));
     NX_TRY(launch_tlas_refit(c));
+    entry_inputs_changed(c);  // (the instance records, their identity flags, the TLAS's boxes)
     // pageable host arrays: the copies above are staged before hipMemcpyAsync returns on this runtime, but that is not a
     // documented guarantee — wait, the call is not on the per-frame path
     NX_SYNC_ALL(c);
@@ -732,6 +739,7 @@ static int update_blas(nxhip_ctx* c, int32_t blasId, const void* tris, uint32_t 
     }
     b.rootKnown = false;  // (read again by whoever next needs the host copy: refresh_inst_trav)
     b.refreshPending = true;
+    entry_inputs_changed(c);  // (the BLAS's nodes and triangle records; the deferred refresh bumps again for what follows its root)
     c->blasRefreshPending = true;
     c->lightTableDirty = true;
     // a pageable host array: see nxhip_set_instance_transforms
