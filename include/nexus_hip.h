@@ -253,6 +253,10 @@ int nxhip_read_entry_states(nxhip_ctx *ctx, void *out, uint32_t capacityRuns, ui
  * it is walked again, in front of the slot's next pass, only after a call that changed something the walk reads (camera, pixel set,
  * TLAS, instances, BLASes, materials' types, entry points switched on) — one launch per slot that renders afterwards. */
 int nxhip_debug_entry_walks(nxhip_ctx *ctx, uint64_t *count);
+/* Test hook for the kernel instances a pass graph picks by scene (pass_flavor, nxhip_render.hip).  *flavor (may be NULL): the flavor
+ * bits of the graph the last pass replayed; 256 = trace instances without the transform path, 512 = map-free material launch.
+ * forceGeneral: those of the two bits whose specialised instances later passes must not use (0xffffffff: unchanged). */
+int nxhip_debug_pass_flavor(nxhip_ctx *ctx, uint32_t forceGeneral, uint32_t *flavor);
 /* Test hook for the thin kernel (nx_trace.hip): the hand-over rule — at most `lanes` busy lanes of a dry wave for at least `iters`
  * iterations (product: 16 / 16; 64 / 0 makes every wave hand over the first rays it takes, after one iteration) — and whether the ray-batch
  * hooks (nxhip_trace_batch, nxhip_trace_shadow_batch) use the hand-over + thin launch too, so that a test can put arbitrary rays

@@ -27,7 +27,7 @@ HIP_SYMBOLS = [
     "nxhip_read_kernel_times", "nxhip_read_graph_timeline", "nxhip_has_gfx950_code", "nxhip_build_info", "nxhip_set_pixel_order", "nxhip_sync_timeout", "nxhip_debug_set_requeue", "nxhip_debug_thin_counts_of_pass", "nxhip_debug_write_blas_node", "nxhip_rebuild_tlas", "nxhip_read_tlas_index", "nxhip_release_queues", "nxhip_set_device_builder",
     "nxhip_set_instance_transforms", "nxhip_read_tlas", "nxhip_set_passes_in_flight", "nxhip_set_tail_bounce", "nxhip_set_entry_points", "nxhip_read_entry_states", "nxhip_debug_set_thin", "nxhip_debug_set_thin_pool", "nxhip_debug_thin_counts", "nxhip_build_blas", "nxhip_read_blas", "nxhip_set_env_sampling",
     "nxhip_tile_pixel_map", "nxhip_mgpu_unique_id", "nxhip_mgpu_init", "nxhip_mgpu_attach", "nxhip_mgpu_gather", "nxhip_mgpu_read_rgba8",
-    "nxhip_mgpu_read_accumulation", "nxhip_mgpu_shutdown", "nxhip_fmath_batch", "nxhip_abi_stamp", "nxhip_check_library", "nxhip_build_blas_batch", "nxhip_read_blas_batch", "nxhip_debug_set_scan_epoch", "nxhip_debug_ended_rays_of_pass", "nxhip_debug_entry_walks",
+    "nxhip_mgpu_read_accumulation", "nxhip_mgpu_shutdown", "nxhip_fmath_batch", "nxhip_abi_stamp", "nxhip_check_library", "nxhip_build_blas_batch", "nxhip_read_blas_batch", "nxhip_debug_set_scan_epoch", "nxhip_debug_ended_rays_of_pass", "nxhip_debug_entry_walks", "nxhip_debug_pass_flavor",
     "nxhip_set_aov", "nxhip_read_aov", "nxhip_read_aov_frame", "nxhip_write_aov", "nxhip_denoise", "nxhip_denoise_defaults", "nxhip_read_denoised", "nxhip_read_denoised_rgba8",
     "nxhip_adaptive_defaults", "nxhip_set_adaptive", "nxhip_adaptive_update", "nxhip_render_adaptive", "nxhip_read_sample_counts", "nxhip_read_noise_stats",
     "nxhip_read_block_noise", "nxhip_read_active_map", "nxhip_update_blas", "nxhip_update_blas_device",
@@ -479,6 +479,9 @@ def decode_image(data):
     return decode_png(data)
 
 
+FLAVOR_IDENTITY, FLAVOR_NO_MAPS = 256, 512  # Context.debug_pass_flavor: the specialised kernel instances of a pass graph
+
+
 class Context:
     """One ``nxhip_ctx`` (one GPU).  Thin 1:1 wrapper of the C-ABI; raises NexusError on any failure."""
 
@@ -845,6 +848,15 @@ class Context:
         self.L.nxhip_debug_entry_walks.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
         check(self.L.nxhip_debug_entry_walks(self.h, C.byref(n)), "nxhip_debug_entry_walks")
         return int(n.value)
+
+    def debug_pass_flavor(self, force_general=None):
+        """flavor bits of the graph the last pass replayed (FLAVOR_IDENTITY: trace instances without the transform path, FLAVOR_NO_MAPS:
+        map-free material launch); force_general: the bits whose specialised instances later passes must not use (None: unchanged) —
+        a test hook: include/nexus_hip.h"""
+        f = C.c_uint32(0)
+        self.L.nxhip_debug_pass_flavor.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
+        check(self.L.nxhip_debug_pass_flavor(self.h, 0xffffffff if force_general is None else int(force_general), C.byref(f)), "nxhip_debug_pass_flavor")
+        return int(f.value)
 
     def read_entry_states(self):
         """(runs, 40) int32: the entry states of the last pass; column 19 = node steps saved, 16 = stack entries, 18 = instance record,

@@ -126,7 +126,7 @@ struct PassSlot {
         hipGraph_t graph = nullptr;
         hipGraphExec_t exec = nullptr;
         int traceBlocks = 0, tailBounce = 0;
-        int flavor = 0;  // pass_flavor(): pipeline, miss kernel, logic kernel variant
+        int flavor = 0;  // pass_flavor(): pipeline, miss kernel, logic kernel variant, ..., the scene-specialised kernel instances
     };
     std::vector<GraphInstance> graphs;
     // pass bookkeeping (slots >= 1 and slot 0 alike)
@@ -224,6 +224,11 @@ struct nxhip_ctx : nxd::PassSlot {
     // material types the scene's materials use (bit NX_MAT_*): a type no material has can never receive a queue item, so its
     // kernel is left out of the pass graph (a launch on the critical path of every bounce, however empty)
     uint32_t materialTypeMask = 0xfu;
+    // some material of the table names a diffuse or an emissive map (nxhip_set_materials; whatever has or has not been uploaded): the
+    // map-free instance of the material launch is for contexts where none does (kFlavorNoMaps, nxhip_render.hip pass_flavor)
+    bool materialsNameMaps = true;
+    int flavorForceGeneral = 0;  // nxhip_debug_pass_flavor: the kFlavor* bits of specialised kernel instances a pass must not use
+    int lastPassFlavor = 0;      // pass_flavor() of the last pass issued (nxhip_debug_pass_flavor)
     bool thinInHooks = false;  // nxhip_debug_set_thin: the ray-batch hooks hand over and launch the thin kernel too
     bool dead = false;          // nxhip_sync_timeout gave up: no further device work is issued or waited for
     int pixelOrder = 0;         // nxhip_set_pixel_order: NXHIP_ORDER_* of the full frame, re-applied by nxhip_resize (a caller's own map is not)

@@ -14,14 +14,14 @@ namespace nxd {
 // nx_lbvh.hip, nx_lights.hip and nxhip_multigpu.hip include this header, so the compiler checks their declarations against the
 // definitions.  The getters of the other kernel units are declared here as they are defined there (nx_trace.hip, nx_entry.hip
 // and nx_wavefront.hip cannot include it: their text is pinned by bench.py's source hash).
-const void* trace_kernel_ptr(bool anyHit, bool stats);  // nx_trace.hip
-const void* trace_entry_kernel_ptr();
+const void* trace_kernel_ptr(bool anyHit, bool stats, bool identity = false);  // nx_trace.hip
+const void* trace_entry_kernel_ptr(bool identity = false);
 const void* thin_kernel_ptr();
 const void* entry_state_kernel_ptr();  // nx_entry.hip
 const void* tail_kernel_ptr(bool lightPower);  // nx_wavefront.hip
 const void* logic_kernel_ptr(int items);
 const void* shade_kernel_ptr(int type, bool lightPower);
-const void* shade_scan_kernel_ptr(bool lightPower);
+const void* shade_scan_kernel_ptr(bool lightPower, bool noMaps = false);
 const void* count_scan_kernel_ptr();
 const void* begin_frame_kernel_ptr();
 const void* hook_sizes_kernel_ptr();
@@ -102,14 +102,14 @@ using U32 = uint32_t;
 using StateKernel = Kernel<State>;            // (S)
 using BounceKernel = Kernel<State, int>;      // (S, bounce | flags)
 using TypeKernel = Kernel<State, int, int>;   // (S, bounce | flags, type or type mask)
-inline BounceKernel trace(bool anyHit, bool stats) { return {trace_kernel_ptr(anyHit, stats)}; }
-inline BounceKernel trace_entry() { return {trace_entry_kernel_ptr()}; }
+inline BounceKernel trace(bool anyHit, bool stats, bool identity = false) { return {trace_kernel_ptr(anyHit, stats, identity)}; }  // (identity: pass graphs only)
+inline BounceKernel trace_entry(bool identity = false) { return {trace_entry_kernel_ptr(identity)}; }
 inline BounceKernel thin() { return {thin_kernel_ptr()}; }
 inline StateKernel entry_state() { return {entry_state_kernel_ptr()}; }
 inline BounceKernel tail(bool lightPower) { return {tail_kernel_ptr(lightPower)}; }
 inline BounceKernel logic(int items) { return {logic_kernel_ptr(items)}; }
 inline BounceKernel shade(int type, bool lightPower) { return {shade_kernel_ptr(type, lightPower)}; }
-inline TypeKernel shade_scan(bool lightPower) { return {shade_scan_kernel_ptr(lightPower)}; }
+inline TypeKernel shade_scan(bool lightPower, bool noMaps = false) { return {shade_scan_kernel_ptr(lightPower, noMaps)}; }
 inline TypeKernel count_scan() { return {count_scan_kernel_ptr()}; }
 inline Kernel<DeviceState*, U32, U32, U32> begin_frame() { return {begin_frame_kernel_ptr()}; }  // (S, frames, frameLast, scanEpoch)
 inline Kernel<DeviceState*, U32, int, int> hook_sizes() { return {hook_sizes_kernel_ptr()}; }    // (S, n, anyHit, slot)

@@ -400,7 +400,11 @@ NXD ThinResult thin_wave_search(const DeviceState* __restrict__ S, lds_u64* cons
 // ENTRY: the primary launch of a pass with entry points (nx_entry.hip) — the only launch that installs entry states at refill; the
 // other launches are compiled without that code (its loads and the consumed triangle's test would cost every closest-hit launch's
 // refill registers).  The counting variant keeps it either way.
-template <bool ANY_HIT, bool STATS, bool ENTRY = false>
+// IDENTITY: the launches of a pass over a scene whose instances all carry the identity (the host knows: kSceneAllIdentity, pass_flavor
+// in nxhip_render.hip) — what the general instances read from DeviceState::sceneFlags is the constant `true` here, so the transform
+// rows, their loads and the general branch of enter_instance are not compiled in and cost no registers (rays that are not "ordinary"
+// still go through the identity's rows as constants: nx_traverse.h).  The counting variants and the ray-batch hooks keep the flag.
+template <bool ANY_HIT, bool STATS, bool ENTRY = false, bool IDENTITY = false>
 // 5 waves per SIMD for both variants (96 VGPRs, no spills in the loop).  Before an instance entry also carried its BLAS
 // root (17 more live registers in the fetch), 6 waves at 80 VGPRs was the best point (5: -3 %, 7: -0.3 %, 8: -1.5 %); with it,
 // 6 waves spill 23 VGPRs inside the loop (-10 %), 5 and 4 measure +4.5 % and +1 % over the old kernel at 6.
@@ -462,7 +466,7 @@ __global__ void __launch_bounds__(kTraceBlock) trace_kernel(const DeviceState* _
     GF4 rayD = ANY_HIT ? S->shadow.rayD : S->trace.rays[raySet].rayD;
     GU4 tlasNodes = S->tlasNodes;
     const NX_G InstTrav* instTrav = S->instTrav;
-    const bool sceneIdentity = (S->sceneFlags & kSceneAllIdentity) != 0u;  // wave-uniform: no instance of the scene transforms a ray
+    const bool sceneIdentity = IDENTITY || (S->sceneFlags & kSceneAllIdentity) != 0u;  // wave-uniform: no instance of the scene transforms a ray
 
     const int lane = threadIdx.x & (kWave - 1);
     const unsigned long long laneLt = (1ull << lane) - 1ull;
@@ -949,6 +953,9 @@ template __global__ void trace_kernel<false, false, true>(const DeviceState*, in
 template __global__ void trace_kernel<false, true>(const DeviceState*, int);
 template __global__ void trace_kernel<true, false>(const DeviceState*, int);
 template __global__ void trace_kernel<true, true>(const DeviceState*, int);
+template __global__ void trace_kernel<false, false, false, true>(const DeviceState*, int);
+template __global__ void trace_kernel<false, false, true, true>(const DeviceState*, int);
+template __global__ void trace_kernel<true, false, false, true>(const DeviceState*, int);
 
 // The listed rays of one level (closest-hit first, then any-hit; kThinClosestOnly / kThinAnyOnly: one list), one wave per ray,
 // grid-stride.  `bounceArg` as the trace launches got it: the ray set and the meaning of the closest-hit record follow kTraceScanFlag.
@@ -1050,10 +1057,13 @@ __global__ void __launch_bounds__(kTraceBlock) thin_kernel(const DeviceState* __
 }
 
 const void* thin_kernel_ptr() { return (const void*)thin_kernel; }
-const void* trace_entry_kernel_ptr() { return (const void*)trace_kernel<false, false, true>; }  // the primary launch with entry points
+// the primary launch with entry points
+const void* trace_entry_kernel_ptr(bool identity) { return identity ? (const void*)trace_kernel<false, false, true, true> : (const void*)trace_kernel<false, false, true>; }
 
-const void* trace_kernel_ptr(bool anyHit, bool stats)
+// identity: the instances of an identity-only scene's pass graphs (the counting variants have none)
+const void* trace_kernel_ptr(bool anyHit, bool stats, bool identity)
 {
+    if (identity && !stats) return anyHit ? (const void*)trace_kernel<true, false, false, true> : (const void*)trace_kernel<false, false, false, true>;
     if (anyHit) return stats ? (const void*)trace_kernel<true, true> : (const void*)trace_kernel<true, false>;
     return stats ? (const void*)trace_kernel<false, true> : (const void*)trace_kernel<false, false>;
 }

@@ -692,7 +692,10 @@ struct ShadowPayload {
 // every emissive triangle of every mesh light in proportion to area x emitted luminance — with ONE random number in place of
 // the uniform triangle index, so a path draws as many numbers as in the default mode.  A template parameter, not a run-time
 // branch: the default mode's kernels are the instances with POWER = false, whose code does not change.
-template <int TYPE, bool POWER>
+// NO_MAPS (the SCAN pipeline's material launch only: shade_scan_kernel): no material of the context names a diffuse or an emissive
+// map (the host knows: kFlavorNoMaps, pass_flavor in nxhip_render.hip), so the lookups, the texture coordinates they need and the alpha
+// pass-through draw — made only behind `diffuseMapId != -1` — are not compiled in.  No arithmetic of an executed path changes.
+template <int TYPE, bool POWER, bool NO_MAPS = false>
 NXD bool next_event_estimation(const DeviceState* S, f3 wi, const MatParams& mp, f3 hitPoint, f3 normal, f3 hitGNormal, f3 throughput,
                                uint32_t& rng, ShadowPayload& out)
 {
@@ -779,7 +782,7 @@ NXD bool next_event_estimation(const DeviceState* S, f3 wi, const MatParams& mp,
     const float weight = power_heuristic(lightPdf, bsdfPdf);
 
     f3 emissive;
-    if (lightMaterial->emissiveMapId != -1) {
+    if (!NO_MAPS && lightMaterial->emissiveMapId != -1) {
         const f2 t = bary2(tri->texCoord0, tri->texCoord1, tri->texCoord2, uv.x, uv.y);
         const float4 c = tex2d(S->emissiveMaps[lightMaterial->emissiveMapId], S->srgbLut, t.x, t.y);
         emissive = mk3(c.x, c.y, c.z);
@@ -795,7 +798,7 @@ NXD bool next_event_estimation(const DeviceState* S, f3 wi, const MatParams& mp,
 // (only read for an emissive hit under MIS).  emit(radiance, instance) receives what the hit emits towards the path; what comes out: the shadow ray of its
 // light sample, the continuation ray and the path state that goes with it.  (Separate references, not a struct: the
 // compiler kept a struct of these in scratch memory, +30 % on the material kernels.)
-template <int TYPE, bool POWER, class PrevOrigin, class Emit>
+template <int TYPE, bool POWER, bool NO_MAPS = false, class PrevOrigin, class Emit>
 NXD void shade_path(const DeviceState* S, const int bounce, const uint32_t frame, const uint32_t seedSlot, const uint32_t pixelIdx, const float hu, const float hv,
                     const uint32_t triIdx, const uint32_t instanceIdx, const f3 rayDirection, const float4 tpdf, PrevOrigin prevOrigin, Emit emit,
                     bool& wantShadow, ShadowPayload& sh, bool& wantTrace, bool& updatePath, f3& nextOrigin, f3& nextDir, f3& nextThroughput, float& nextPdf)
@@ -821,7 +824,7 @@ NXD void shade_path(const DeviceState* S, const int bounce, const uint32_t frame
     f3 gNormal = normalize3(mat_vec_transposed(IT, cross3(tp1 - tp0, tp2 - tp0)));
 
     f3 emissive = ld3(material.emissive);
-    if (material.emissiveMapId != -1) {
+    if (!NO_MAPS && material.emissiveMapId != -1) {
         const float4 c = tex2d(S->emissiveMaps[material.emissiveMapId], S->srgbLut, texUv.x, texUv.y);
         emissive = mk3(c.x, c.y, c.z);
     }
@@ -861,7 +864,7 @@ NXD void shade_path(const DeviceState* S, const int bounce, const uint32_t frame
 
     if (bounce != (int)S->settings.pathLength) {
         float4 color = make_float4(1.0f, 1.0f, 1.0f, 1.0f);
-        if (material.diffuseMapId != -1) {
+        if (!NO_MAPS && material.diffuseMapId != -1) {
             color = tex2d(S->diffuseMaps[material.diffuseMapId], S->srgbLut, texUv.x, texUv.y);
             mp.albedo = mk3(color.x, color.y, color.z);
         }
@@ -870,7 +873,7 @@ NXD void shade_path(const DeviceState* S, const int bounce, const uint32_t frame
         const float4 q = rotation_to_z(normal);
         const f3 wi = rotate_point(q, -rayDirection);
         f3 wo;
-        if (rng_next(rng) > material.opacity || (material.diffuseMapId != -1 && rng_next(rng) > color.w)) {
+        if (rng_next(rng) > material.opacity || (!NO_MAPS && material.diffuseMapId != -1 && rng_next(rng) > color.w)) {
             // texture / opacity pass-through: continue straight, path state untouched
             wo = normalize3(rotate_point(invert_rotation(q), -wi));
             const float od = sgnE(dot3(wo, normal));
@@ -878,7 +881,7 @@ NXD void shade_path(const DeviceState* S, const int bounce, const uint32_t frame
             nextDir = wo;
             wantTrace = true;
         } else {
-            if (useMIS) wantShadow = next_event_estimation<TYPE, POWER>(S, wi, mp, p, normal, gNormal, throughput, rng, sh);
+            if (useMIS) wantShadow = next_event_estimation<TYPE, POWER, NO_MAPS>(S, wi, mp, p, normal, gNormal, throughput, rng, sh);
             float pdf;
             f3 sampleThroughput;
             if (Bsdf<TYPE>::sample(mp, wi, rng, wo, sampleThroughput, pdf)) {
@@ -997,7 +1000,7 @@ static_assert(kScanRing >= kShadeBlock + 4 * kShadeBlock && (kScanRing & (kScanR
 // from `staticTiles` on are handed out by ticket — one returning atomic per tile on the region's own word.  The share of a tile
 // that is this type's to shade varies from none to all with what the camera sees there, so a static split leaves most workgroups
 // waiting for the few whose tiles were full (measured: +40 % on the kernels).
-template <int TYPE, bool POWER>
+template <int TYPE, bool POWER, bool NO_MAPS = false>
 NXD void shade_scan_type(const DeviceState* __restrict__ S, const int bounce, const bool dropEnded, const int region, const int inRegion, const int per, const int firstTile,
                          const int staticTiles, int* const sRing, int* const sHead, int* const sTicket)
 {
@@ -1079,7 +1082,7 @@ NXD void shade_scan_type(const DeviceState* __restrict__ S, const int bounce, co
             // ... and the path's previous vertex, for hits that can need it (keep_previous_vertex)
             const uint32_t typeAndFlag = *(const NX_G uint32_t*)((const NX_G char*)&S->shadeInst[instanceIdx].material + kMaterialTypeOffset);
             if ((typeAndFlag >> 8) & 1u) keep_previous_vertex(S, pixelIdx, in.rayO[at]);
-            shade_path<TYPE, POWER>(S, bounce, frame, (uint32_t)at, pixelIdx, hit.y, hit.z, __float_as_uint(hit.w), instanceIdx, mk3(dirPix.x, dirPix.y, dirPix.z), tpdf,
+            shade_path<TYPE, POWER, NO_MAPS>(S, bounce, frame, (uint32_t)at, pixelIdx, hit.y, hit.z, __float_as_uint(hit.w), instanceIdx, mk3(dirPix.x, dirPix.y, dirPix.z), tpdf,
                              [&]() { return S->rayOrigin[pixelIdx]; },
                              [&](f3 emitted, uint32_t instIdx) {
                                  if (bounce == 1 && bounce != (int)S->settings.pathLength && pixelIdx < S->localCount && S->frame->pixelQueryPixel == (int)global_pixel(S, pixelIdx))
@@ -1193,7 +1196,7 @@ NXD void shade_scan_type(const DeviceState* __restrict__ S, const int bounce, co
 // workgroups start on different types (rank modulo the number of types) and move on to the next type when theirs has no tile
 // left, so the types run side by side, the launch ends when the last tile of the last type does, and a bounce costs one material
 // launch instead of one per type (the reference: four, PathTracer.cpp:116-120).  A single-bit mask is a per-type launch.
-template <bool POWER>  // (the light sample's mode: next_event_estimation)
+template <bool POWER, bool NO_MAPS = false>  // (the light sample's mode, a map-free context: next_event_estimation)
 __global__ void __launch_bounds__(kShadeBlock, NX_SHADE_WAVES) shade_scan_kernel(const DeviceState* __restrict__ S, const int bounceArg, const int typeMask)
 {
     const int bounce = bounceArg & 0xff;
@@ -1228,11 +1231,11 @@ __global__ void __launch_bounds__(kShadeBlock, NX_SHADE_WAVES) shade_scan_kernel
         const int starters = (ranks - want + nTypes - 1) / nTypes;  // workgroups whose first type this is: each takes the tile of its index
         const int first = step == 0 ? myIndex : -1;
         switch (type) {
-        case NX_MAT_DIFFUSE: shade_scan_type<NX_MAT_DIFFUSE, POWER>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket); break;
-        case NX_MAT_PLASTIC: shade_scan_type<NX_MAT_PLASTIC, POWER>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket); break;
-        case NX_MAT_DIELECTRIC: shade_scan_type<NX_MAT_DIELECTRIC, POWER>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket); break;
-        case NX_MAT_CONDUCTOR: shade_scan_type<NX_MAT_CONDUCTOR, POWER>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket); break;
-        case kScanMiss: shade_scan_type<kScanMiss, POWER>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket); break;
+        case NX_MAT_DIFFUSE: shade_scan_type<NX_MAT_DIFFUSE, POWER, NO_MAPS>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket); break;
+        case NX_MAT_PLASTIC: shade_scan_type<NX_MAT_PLASTIC, POWER, NO_MAPS>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket); break;
+        case NX_MAT_DIELECTRIC: shade_scan_type<NX_MAT_DIELECTRIC, POWER, NO_MAPS>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket); break;
+        case NX_MAT_CONDUCTOR: shade_scan_type<NX_MAT_CONDUCTOR, POWER, NO_MAPS>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket); break;
+        case kScanMiss: shade_scan_type<kScanMiss, POWER, NO_MAPS>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket); break;
         default: break;
         }
     }
@@ -1540,7 +1543,11 @@ const void* shade_kernel_ptr(int type, bool lightPower)
     default: return lightPower ? (const void*)shade_kernel<NX_MAT_CONDUCTOR, true, true> : (const void*)shade_kernel<NX_MAT_CONDUCTOR, true, false>;
     }
 }
-const void* shade_scan_kernel_ptr(bool lightPower) { return lightPower ? (const void*)shade_scan_kernel<true> : (const void*)shade_scan_kernel<false>; }
+const void* shade_scan_kernel_ptr(bool lightPower, bool noMaps)
+{
+    if (noMaps) return lightPower ? (const void*)shade_scan_kernel<true, true> : (const void*)shade_scan_kernel<false, true>;
+    return lightPower ? (const void*)shade_scan_kernel<true> : (const void*)shade_scan_kernel<false>;
+}
 const void* count_scan_kernel_ptr() { return (const void*)count_scan_kernel; }
 const void* tail_kernel_ptr(bool lightPower) { return lightPower ? (const void*)tail_kernel<true> : (const void*)tail_kernel<false>; }
 const void* begin_frame_kernel_ptr() { return (const void*)begin_frame_kernel; }

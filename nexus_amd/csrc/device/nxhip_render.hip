@@ -152,6 +152,18 @@ int tail_bounce(const nxhip_ctx* c)
 // 152-164 adds throughput x background, and +0 changes nothing), and the logic kernel's variant (one item per thread under an
 // environment map).  Part of a graph instance's key, so a change of any of them picks or builds the matching instance.
 constexpr int kFlavorScan = 1, kFlavorMissKernel = 2, kFlavorEnvMap = 4, kFlavorEntry = 8, kFlavorThin = 16, kFlavorDropEnded = 32, kFlavorAov = 64, kFlavorLightPower = 128;
+// ... and what the scene lets the kernels leave out (compile-time instances; a graph of one flavor is never replayed in another):
+// kFlavorIdentity: every instance carries the identity — the trace launches are the IDENTITY instances (nx_trace.hip).  The fact is the
+//   host's DeviceState::sceneFlags, kept current by the instance upload (refresh_inst_trav: nxhip_set_tlas, nxhip_rebuild_tlas) and by
+//   nxhip_set_instance_transforms; the BLAS refit and its deferred refresh (nxhip_update_blas, refresh_updated_blas) leave every matrix
+//   as it is.
+// kFlavorNoMaps: no material names a diffuse or an emissive map — the SCAN pipeline's material launch is its map-free instance
+//   (nx_wavefront.hip).  The fact is recomputed by nxhip_set_materials, the one call that writes the material table.  Not under an
+//   environment map: there the instance measured slower than the general one (configs[3]: material launch +2.2 %, the run -0.65 %;
+//   profiles/r14_kernel_instances.txt), so such a scene keeps the general launch.
+// Both are read at every pass (here), so a change between two passes picks the other graph.
+constexpr int kFlavorIdentity = 256, kFlavorNoMaps = 512;
+constexpr int kFlavorSpecialised = kFlavorIdentity | kFlavorNoMaps;
 int pass_flavor(const nxhip_ctx* c)
 {
     int f = 0;
@@ -181,7 +193,9 @@ int pass_flavor(const nxhip_ctx* c)
     // 4.6-4.7 ms, an extra launch per level), but one pass in seven holds an outlier ray (6.2 ms instead of 4.6) and sequences of small
     // passes are what a viewer or a rank of a tile split renders: four frames per pass 1 223 -> 1 335 Msamples/s, one frame 602 -> 620.
     if (!c->statsEnabled && c->passesInFlight <= 1u) f |= kFlavorThin;  // (the caller's setting, not effective_slots(): a timing replay of a run with passes in flight keeps that run's kernels)
-    return f;
+    if ((c->h.sceneFlags & kSceneAllIdentity) && !c->statsEnabled) f |= kFlavorIdentity;  // (the counting variants have no such instance)
+    if (scan_pipeline(c) && !c->materialsNameMaps && !(f & kFlavorEnvMap)) f |= kFlavorNoMaps;
+    return f & ~(c->flavorForceGeneral & kFlavorSpecialised);  // (test hook: nxhip_debug_pass_flavor)
 }
 
 // The per-frame kernel sequence, in dependency "levels": launches of one level may run concurrently, a level
@@ -198,11 +212,12 @@ std::vector<std::vector<Launch>> frame_levels(nxhip_ctx* c, PassSlot* q)
     //  that finds it stale — walk_entry_states — and read by every pass until an input of the walk changes)
     const bool entry = (pass_flavor(c) & kFlavorEntry) != 0;
     const bool lightPower = (pass_flavor(c) & kFlavorLightPower) != 0;
+    const bool identity = (pass_flavor(c) & kFlavorIdentity) != 0, noMaps = (pass_flavor(c) & kFlavorNoMaps) != 0;
     const int traceBlocks = trace_blocks(c, c->traceBlocks), shadowBlocks = trace_blocks(c, c->shadowBlocks);
     // (the dry waves of a pass's trace launches may hand their last long rays to the thin kernel: nx_trace.hip)
     const int thinFlag = (pass_flavor(c) & kFlavorThin) ? kTraceThinFlag : 0;
     // (with entry points the primary launch is its own kernel instance: the only one that carries the install code)
-    levels.push_back({make_launch((entry && !stats) ? kernels::trace_entry() : kernels::trace(false, stats), traceBlocks, kTraceBlockThreads, NXHIP_K_TRACE, S,
+    levels.push_back({make_launch((entry && !stats) ? kernels::trace_entry(identity) : kernels::trace(false, stats, identity), traceBlocks, kTraceBlockThreads, NXHIP_K_TRACE, S,
                                   (entry ? kTraceEntryFlag : 0) | thinFlag | (scan_pipeline(c) ? kTraceScanFlag : 0))});
     // behind the trace launch(es) of a level: the rays their dry waves handed over, a wave each (thin_kernel)
     // — each trace launch of the level gets its own, chained to it alone, so that the closest-hit rays' searches run beside whatever
@@ -252,13 +267,13 @@ std::vector<std::vector<Launch>> frame_levels(nxhip_ctx* c, PassSlot* q)
             if (c->h.conductorMode != NX_CONDUCTOR_EXTENDED) mask &= ~(1 << NX_MAT_CONDUCTOR);
             if (mask == 0) mask = 1 << NX_MAT_DIFFUSE;  // (a level cannot be empty)
             if (misses) mask |= 1 << kScanMiss;
-            levels.push_back({make_launch(kernels::shade_scan(lightPower), og, kShadeBlockThreads, NXHIP_K_SHADE, S, bounce | dropFlag, mask)});
+            levels.push_back({make_launch(kernels::shade_scan(lightPower, noMaps), og, kShadeBlockThreads, NXHIP_K_SHADE, S, bounce | dropFlag, mask)});
             if (bounce == 1) aov_beside(levels.back());
             if (in_use(NX_MAT_CONDUCTOR) && c->h.conductorMode != NX_CONDUCTOR_EXTENDED) {  // (counted, not shaded: count_scan_kernel)
                 levels.push_back({make_launch(kernels::count_scan(), lg, kWideBlockThreads, NXHIP_K_LOGIC, S, bounce, NX_MAT_CONDUCTOR)});
             }
-            levels.push_back({make_launch(kernels::trace(false, stats), traceBlocks, kTraceBlockThreads, NXHIP_K_TRACE, S, bounce | kTraceScanFlag | thinFlag),
-                              make_launch(kernels::trace(true, stats), shadowBlocks, kTraceBlockThreads, NXHIP_K_SHADOW, S, bounce | thinFlag)});
+            levels.push_back({make_launch(kernels::trace(false, stats, identity), traceBlocks, kTraceBlockThreads, NXHIP_K_TRACE, S, bounce | kTraceScanFlag | thinFlag),
+                              make_launch(kernels::trace(true, stats, identity), shadowBlocks, kTraceBlockThreads, NXHIP_K_SHADOW, S, bounce | thinFlag)});
             thin_level(bounce | kTraceScanFlag);
         }
         return levels;
@@ -280,8 +295,8 @@ std::vector<std::vector<Launch>> frame_levels(nxhip_ctx* c, PassSlot* q)
         if (shade.empty()) shade.push_back(make_launch(kernels::shade(NX_MAT_DIFFUSE, lightPower), og, ob, NXHIP_K_SHADE, S, bounce));  // (a level cannot be empty)
         // serial slot order needs the kernels one after the other
         for (auto& l : shade) levels.push_back({l});
-        levels.push_back({make_launch(kernels::trace(false, stats), traceBlocks, kTraceBlockThreads, NXHIP_K_TRACE, S, bounce | thinFlag),
-                          make_launch(kernels::trace(true, stats), shadowBlocks, kTraceBlockThreads, NXHIP_K_SHADOW, S, bounce | thinFlag)});
+        levels.push_back({make_launch(kernels::trace(false, stats, identity), traceBlocks, kTraceBlockThreads, NXHIP_K_TRACE, S, bounce | thinFlag),
+                          make_launch(kernels::trace(true, stats, identity), shadowBlocks, kTraceBlockThreads, NXHIP_K_SHADOW, S, bounce | thinFlag)});
         thin_level(bounce);
     }
     return levels;
@@ -510,6 +525,7 @@ try {
     }
     NX_TRY(launch_begin_frame(c, q, frames, frameLast));
     if (c->entryPoints) NX_TRY(walk_entry_states(c, q));
+    c->lastPassFlavor = pass_flavor(c);  // (what the eager path's launches and the graph below are chosen by)
     if (c->timingEnabled && c->timingMode == 1) {
         // eager path: one event pair per launch, launches strictly in level order on one stream
         auto levels = frame_levels(c, q);
@@ -647,6 +663,20 @@ int nxhip_debug_set_thin(nxhip_ctx* c, uint32_t lanes, uint32_t iters, int inHoo
     c->h.thinIters = iters;
     c->thinInHooks = (inHooks & 1) != 0;
     c->stateDirty = true;
+    return NXHIP_OK;
+}
+
+// The flavor of the last pass issued (the key of the graph it replayed: pass_flavor) — bit 8: the trace launches were the IDENTITY
+// instances, bit 9: the material launch was the map-free one, the lower bits as kFlavor* above — and, for the passes to come, the bits of
+// specialised instances that must NOT be used (`forceGeneral`, of bits 8 and 9; 0xffffffff: leave it as it is), so that a test can
+// render one scene with the specialised and with the general kernels.
+int nxhip_debug_pass_flavor(nxhip_ctx* c, uint32_t forceGeneral, uint32_t* flavor)
+{
+    NX_DEBUG_HOOK("nxhip_debug_pass_flavor");  // (first: a release library refuses whatever it is handed)
+    NX_CHECK_CTX(c);
+    if (forceGeneral != 0xffffffffu && (forceGeneral & ~(uint32_t)kFlavorSpecialised)) return fail_invalid("nxhip_debug_pass_flavor: forceGeneral may name bits 8 (identity) and 9 (no maps) only");
+    if (flavor) *flavor = (uint32_t)c->lastPassFlavor;
+    if (forceGeneral != 0xffffffffu) c->flavorForceGeneral = (int)forceGeneral;  // (read by pass_flavor at the next pass: another graph)
     return NXHIP_OK;
 }
 

@@ -795,6 +795,8 @@ try {
     NX_HIP(hipMemcpy(c->materials.p, dev.data(), (size_t)count * sizeof(nx_material), hipMemcpyHostToDevice));
     c->h.materials = c->materials.as<nx_material>();
     c->hostMaterialsDev = dev;
+    c->materialsNameMaps = false;  // (the table as it is now, not what has been uploaded: a material may name a map id before its texture exists)
+    for (const nx_material& m : dev) c->materialsNameMaps = c->materialsNameMaps || m.diffuseMapId != -1 || m.emissiveMapId != -1;
     c->stateDirty = true;
     c->shadeInstDirty = true;  // (the records hold a copy of their instance's material)
     c->lightTableDirty = true;
