@@ -42,6 +42,12 @@ struct Texture {
     Type type = Type::DIFFUSE;
 };
 
+// A float image: linear RGB radiance, nothing clamped (IMGLoader::LoadHDRFloat, Scene::AddHDRMapFloat)
+struct FloatImage {
+    uint32_t width = 0, height = 0;
+    std::vector<float> pixels;  // RGB, width x height x 3, row 0 first
+};
+
 struct Mesh {
     Mesh() = default;
     Mesh(const std::string& n, int32_t bId = -1, int32_t mId = -1, float3 p = make_float3(0.0f), float3 r = make_float3(0.0f), float3 s = make_float3(1.0f))

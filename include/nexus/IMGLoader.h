@@ -20,6 +20,11 @@ public:
     // Throw std::runtime_error with a message on malformed / unsupported input.
     static Texture LoadIMG(const std::string& filepath);
     static Texture LoadIMG(const unsigned char* data, size_t size);
+    // Extension: a Radiance .hdr file as what it holds — linear radiance, component = mantissa x 2^(e - 136), e = 0: 0 — instead of
+    // the 8 bits LoadIMG reduces it to (pow(c, 1 / 2.2) x 255, clamped: a sun 10^5 times the sky comes out 50 times the sky).
+    // The same RGBE reader (flat and run-length encoded scanlines), the same errors.
+    static FloatImage LoadHDRFloat(const std::string& filepath);
+    static FloatImage LoadHDRFloat(const unsigned char* data, size_t size);
 };
 
 }  // namespace nexus

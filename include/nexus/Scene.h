@@ -30,6 +30,10 @@ public:
     void AddMaterial(Material& material) { m_AssetManager.AddMaterial(material); }
     void AddHDRMap(const Texture& texture);
     void AddHDRMap(const std::string& filePath, const std::string& fileName);  // Scene.cpp:93-97: IMGLoader::LoadIMG (.hdr or .png)
+    // Extension: the environment as linear float radiance (nxhip_upload_env_float) — a .hdr file decoded by IMGLoader::LoadHDRFloat, or
+    // width x height x 3 floats, row 0 the top row.  Either kind of map replaces the other.
+    void AddHDRMapFloat(const std::string& filePath, const std::string& fileName);
+    void AddHDRMapFloat(uint32_t width, uint32_t height, const float* rgb);
     size_t AddLight(const Light& light);
     void RemoveLight(size_t index);
 
@@ -65,6 +69,7 @@ public:
     const std::vector<BVHInstance>& GetBVHInstances() const { return m_BVHInstances; }
     const std::vector<Light>& GetLights() const { return m_Lights; }
     const Texture& GetHDRMap() const { return m_HdrMap; }
+    const FloatImage& GetHDRMapFloat() const { return m_HdrMapFloat; }  // pixels empty: the map is GetHDRMap()'s, or there is none
 
     // what the device has not seen yet (set here, cleared by PathTracer::UpdateDeviceScene)
     mutable bool tlasDirty = true, lightsDirty = true, hdrDirty = false;
@@ -81,6 +86,7 @@ private:
     RenderSettings m_RenderSettings;
     std::shared_ptr<Camera> m_Camera;
     Texture m_HdrMap;
+    FloatImage m_HdrMapFloat;
 
     std::vector<MeshInstance> m_MeshInstances;  // what the user edits
     std::vector<BVHInstance> m_BVHInstances;    // what the TLAS and the device see, one per mesh instance

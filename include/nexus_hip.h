@@ -155,12 +155,34 @@ int nxhip_set_lights(nxhip_ctx *ctx, const nx_light *lights, uint32_t count);
  * Diffuse/emissive maps get ids in upload order; the hdr map replaces the previous one. */
 int nxhip_upload_texture(nxhip_ctx *ctx, int kind, const uint8_t *rgba8, uint32_t width, uint32_t height, int32_t *texId);
 int nxhip_clear_textures(nxhip_ctx *ctx);
+/* Extension: a FLOAT environment map — linear radiance, nothing clamped to 1 (the RGBA8 map above runs through the sRGB table: no
+ * texel brighter than 1, a sun 10^5 times the sky arrives as a dot 50 times the sky).  rgb = width x height x 3 floats, row 0 the
+ * top row (d.y = +1); orientation and the (u, v) of a direction are the RGBA8 map's.  The array is copied before the call returns.
+ * It replaces the environment map of either kind; nxhip_upload_texture(kind 2) replaces a float one, nxhip_clear_textures removes it.
+ *   lookup:  bilinear, wrap on both axes, texel centres at +0.5: xb = u width - 1/2, x0 = floor(xb), a = xb - x0 (likewise in v),
+ *            value = lerp(lerp(t00, t10, a), lerp(t01, t11, a), b) in binary32 with the EXACT fractional weights — not the 1/256
+ *            steps of the RGBA8 lookup, which imitate a texture unit that only ever filtered 8-bit texels: next to a texel of 6e4,
+ *            1/512 of a weight is not a rounding error.
+ *   sampler: under nxhip_set_env_sampling the texel weight is the integral of the FILTERED luminance over the texel's footprint,
+ *              Lf(x, y) = sum over dy, dx in {-1, 0, 1} of k[dy] k[dx] lum(x + dx, y + dy),  k = (1/8, 3/4, 1/8)  (sums to 1 exactly),
+ *              weight(x, y) = Lf(x, y) x sin(pi (y + 1/2) / height) + 1e-6,  lum = 0.2126 R + 0.7152 G + 0.0722 B (linear),
+ *            neighbours wrapping on both axes as the lookup's do; the floor is absolute, as for the RGBA8 maps.  The RGBA8 rule — the
+ *            texel's own luminance — is wrong here: the bilinear lookup bleeds a bright texel half a texel into its neighbours, whose
+ *            pdf would know nothing of it, so value / pdf is bounded by sun / sky (10^6) instead of about 255 and the estimator has a
+ *            tail no frame count meets (a 32 x 16 map with a one-texel sun of 6e4: 400 000 draws 43 % low).  The RGBA8 map keeps
+ *            its own rule bit for bit.
+ *   tables:  built on the device (binary64 weights and scans, cdfs and density rounded once to binary32, each cdf ending in exactly
+ *            1), with no read-back and no host copy of the texels: by this call when the sampler is on (a new map under an enabled
+ *            sampler gets new tables), by nxhip_set_env_sampling(1) on a float map otherwise.
+ * NXHIP_ERR_INVALID, the previous map and tables left in place: rgb NULL or a zero size; width or height above 32768 or more than
+ * 2^27 texels; any component negative or not finite (checked on the host before anything is allocated). */
+int nxhip_upload_env_float(nxhip_ctx *ctx, const float *rgb, uint32_t width, uint32_t height);
 /* Extension (BASELINE.json configs[3] asks for "HDR envmap NEE/MIS"; the reference only adds the environment when a ray
  * misses, PathTracer.cu:152-164, and its NEE knows mesh lights only, :227): with enable != 0 the next-event estimation
  * treats the environment map as one more light — picked with probability 1 / (lightCount + 1), direction drawn from the
  * map's luminance x sin(theta) distribution, shadow ray to infinity — and a BSDF-sampled ray that misses is weighted
  * against that sampler with the power heuristic.  Unbiased either way; the expectation of a frame is unchanged.  Needs an
- * uploaded environment map (kind 2); off by default. */
+ * uploaded environment map (kind 2, or nxhip_upload_env_float — whose texel weight is its own, see there); off by default. */
 int nxhip_set_env_sampling(nxhip_ctx *ctx, int enable);
 /* Extension: how the next-event estimation chooses its mesh-light sample.
  *   NXHIP_LIGHTS_UNIFORM (default)  the reference's rule, bit for bit: one light uniformly, then one of its triangles uniformly
@@ -500,7 +522,8 @@ int nxhip_debug_set_requeue(nxhip_ctx *ctx, int on);
 int nxhip_bsdf_sample_batch(nxhip_ctx *ctx, const nx_material *material, const nx_bsdf_query *queries, uint32_t count, nx_bsdf_result *results);
 int nxhip_bsdf_eval_batch(nxhip_ctx *ctx, const nx_material *material, const nx_bsdf_query *queries, uint32_t count, nx_bsdf_result *results);
 /* kind as in nxhip_upload_texture (0 diffuse, 1 emissive, 2 hdr; textureId ignored for hdr); uv = 2*count floats,
- * rgba = 4*count floats (sRGB-decoded, bilinear, wrap addressing: what the shade kernels see). */
+ * rgba = 4*count floats (sRGB-decoded, bilinear, wrap addressing: what the shade kernels see).  kind 2 on a float environment map
+ * (nxhip_upload_env_float): that map's own lookup, linear, alpha 1. */
 int nxhip_tex2d_batch(nxhip_ctx *ctx, int kind, int textureId, const float *uv, uint32_t count, float *rgba);
 
 /* Test hooks of the light table (NXHIP_LIGHTS_POWER only, else NXHIP_ERR_INVALID; both bring the table up to date first).
@@ -532,6 +555,15 @@ int nxhip_light_pick_batch(nxhip_ctx *ctx, const float *u, uint32_t count, uint3
 int nxhip_read_env_tables(nxhip_ctx *ctx, float *marginalCdf, float *rowCdf, float *density, uint32_t capacityTexels, uint32_t *width, uint32_t *height);
 int nxhip_env_sample_batch(nxhip_ctx *ctx, const float *r, uint32_t count, float *direction, float *pdf, uint32_t *texel);
 int nxhip_env_eval_batch(nxhip_ctx *ctx, const float *direction, uint32_t count, float *rgb, float *pdf, uint32_t *texel);
+/* The three above work on an environment map of either kind (a float map's P(texel) follows nxhip_upload_env_float's weight).
+ * read_env_float: the float map as it is stored, rgb = width x height x 3 floats, bit for bit what was uploaded (rgb NULL: only
+ * *width / *height are written, which may be NULL too); NXHIP_ERR_INVALID while the environment map is not a float one or
+ * capacityTexels < width x height. */
+int nxhip_read_env_float(nxhip_ctx *ctx, float *rgb, uint32_t capacityTexels, uint32_t *width, uint32_t *height);
+/* The cut points the cdf inversion starts from (either kind of map, sampler on): 65 entries per cdf, entry b = the first index whose
+ * cdf exceeds b / 64, clamped to the cdf's last index.  marginalGuide receives 65 words, rowGuide height x 65 (either may be NULL);
+ * capacityRows >= height when rowGuide is given, else NXHIP_ERR_INVALID. */
+int nxhip_read_env_guides(nxhip_ctx *ctx, uint32_t *marginalGuide, uint32_t *rowGuide, uint32_t capacityRows);
 
 /* The transcendental functions of the shading path (include/nexus_fmath.h: the ONE text the kernels and the CPU oracle both
  * compile — sin / cos / exp / log / pow / atan2 / asin replacing the libm calls of Random.cuh:119-121, Microfacet.cuh:18,75,

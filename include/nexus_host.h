@@ -98,6 +98,9 @@ void nxs_scene_destroy(nxs_scene *s);
 int nxs_scene_add_material(nxs_scene *s, const nx_material *m, int32_t *materialId);
 int nxs_scene_add_texture(nxs_scene *s, int kind /*0 diffuse, 1 emissive*/, const uint8_t *rgba8, uint32_t w, uint32_t h, int32_t *texId);
 int nxs_scene_set_hdr_map(nxs_scene *s, const uint8_t *rgba8, uint32_t w, uint32_t h);
+/* Extension — Scene::AddHDRMapFloat(width, height, rgb): the environment as w x h x 3 floats of linear radiance, row 0 the top row
+ * (nxhip_upload_env_float at the next device update).  Either kind of map replaces the other. */
+int nxs_scene_set_hdr_map_float(nxs_scene *s, const float *rgb, uint32_t w, uint32_t h);
 int nxs_scene_add_mesh(nxs_scene *s, const nx_triangle *tris, uint32_t triCount, int32_t materialId, int32_t *meshId);
 int nxs_scene_create_instance(nxs_scene *s, uint32_t meshId, int32_t materialId, const float pos[3], const float rotDeg[3],
                               const float scale[3], int32_t *instanceId);
@@ -152,6 +155,12 @@ struct nxhip_ctx *nxs_pathtracer_device_context(nxs_pathtracer *p);
 
 /* Scene::AddHDRMap(filePath, fileName) — Scene/Scene.cpp:93-97: environment map from a Radiance .hdr (or .png) file. */
 int nxs_scene_add_hdr_map_file(nxs_scene *s, const char *path, const char *fileName);
+/* Extension — Scene::AddHDRMapFloat(filePath, fileName): a Radiance .hdr file as linear float radiance (IMGLoader::LoadHDRFloat:
+ * component = mantissa x 2^(e - 136), e = 0: 0) instead of the 8 bits nxs_scene_add_hdr_map_file reduces it to. */
+int nxs_scene_add_hdr_map_file_float(nxs_scene *s, const char *path, const char *fileName);
+/* IMGLoader::LoadHDRFloat on a file in memory: *width / *height, and into dstRgb (may be NULL: sizes only; dstCapacity in floats)
+ * width x height x 3 floats. */
+int nxh_decode_hdr_float(const uint8_t *data, size_t size, uint32_t *width, uint32_t *height, float *dstRgb, size_t dstCapacity);
 
 /* ---- nexus::Renderer (include/nexus/Renderer.h): the reference's frame driver without its window ---------------------
  * Renderer::Render (Renderer/Renderer.cpp:41-77): scene.Update() + ResetFrameNumber when the scene is invalid, then

@@ -33,6 +33,7 @@ HIP_SYMBOLS = [
     "nxhip_read_block_noise", "nxhip_read_active_map", "nxhip_update_blas", "nxhip_update_blas_device",
     "nxhip_set_light_sampling", "nxhip_read_light_table", "nxhip_light_pick_batch",
     "nxhip_read_env_tables", "nxhip_env_sample_batch", "nxhip_env_eval_batch",
+    "nxhip_upload_env_float", "nxhip_read_env_float", "nxhip_read_env_guides",
 ]
 HOST_SYMBOLS = [
     "nxh_bvh8_build", "nxh_tlas_build", "nxh_tlas_refit", "nxh_bvh8_refit", "nxh_bvh8_node_count", "nxh_bvh8_prim_count", "nxh_bvh8_nodes",
@@ -50,6 +51,7 @@ HOST_SYMBOLS = [
     "nxs_scene_light_count", "nxs_scene_instance_count", "nxs_pathtracer_create", "nxs_pathtracer_destroy", "nxs_pathtracer_set_modes", "nxs_pathtracer_set_frames_per_pass", "nxs_pathtracer_set_passes_in_flight", "nxs_pathtracer_set_pixel_order", "nxs_pathtracer_set_entry_points", "nxs_pathtracer_set_light_sampling",
     "nxs_pathtracer_update_device_scene", "nxs_pathtracer_render", "nxs_pathtracer_reset_frame_number", "nxs_pathtracer_frame_number",
     "nxs_pathtracer_read_pixels", "nxs_pathtracer_device_context",
+    "nxs_scene_set_hdr_map_float", "nxs_scene_add_hdr_map_file_float", "nxh_decode_hdr_float",
 ]
 
 
@@ -474,6 +476,20 @@ def decode_png(data):
     return out, int(ch.value)
 
 
+def decode_hdr_float(data):
+    """IMGLoader::LoadHDRFloat on a Radiance .hdr file in memory: HxWx3 float32 of linear radiance."""
+    L = lib()
+    L.nxh_decode_hdr_float.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_void_p, C.c_size_t]
+    buf = np.frombuffer(bytes(data), dtype=np.uint8).copy()
+    w, h = C.c_uint32(0), C.c_uint32(0)
+    if L.nxh_decode_hdr_float(_ptr(buf), len(buf), C.byref(w), C.byref(h), None, 0) != 0:
+        raise NexusError("nxh_decode_hdr_float: " + L.nxs_last_error().decode())
+    out = np.zeros((h.value, w.value, 3), dtype=np.float32)
+    if L.nxh_decode_hdr_float(_ptr(buf), len(buf), C.byref(w), C.byref(h), _ptr(out), out.size) != 0:
+        raise NexusError("nxh_decode_hdr_float: " + L.nxs_last_error().decode())
+    return out
+
+
 def decode_image(data):
     """IMGLoader::LoadIMG on an image file in memory — PNG, JPEG or Radiance .hdr by its signature: (HxWx4 uint8, channels)."""
     return decode_png(data)
@@ -547,6 +563,32 @@ class Context:
         check(self.L.nxhip_upload_texture(self.h, {"diffuse": 0, "emissive": 1, "hdr": 2}[kind], _ptr(img), img.shape[1], img.shape[0], C.byref(tid)),
               "nxhip_upload_texture")
         return tid.value
+
+    def upload_env_float(self, rgb):
+        """the environment map as linear float radiance: H x W x 3 float32, row 0 the top row (nxhip_upload_env_float)"""
+        img = np.ascontiguousarray(rgb, dtype=np.float32)
+        assert img.ndim == 3 and img.shape[2] == 3
+        self.L.nxhip_upload_env_float.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
+        check(self.L.nxhip_upload_env_float(self.h, _ptr(img), img.shape[1], img.shape[0]), "nxhip_upload_env_float")
+
+    def read_env_float(self):
+        """the float environment map as it is stored: H x W x 3 float32"""
+        self.L.nxhip_read_env_float.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        w, h = C.c_uint32(0), C.c_uint32(0)
+        check(self.L.nxhip_read_env_float(self.h, None, 0, C.byref(w), C.byref(h)), "nxhip_read_env_float")
+        out = np.zeros((h.value, w.value, 3), dtype=np.float32)
+        check(self.L.nxhip_read_env_float(self.h, _ptr(out), w.value * h.value, C.byref(w), C.byref(h)), "nxhip_read_env_float")
+        return out
+
+    def read_env_guides(self):
+        """the cut points of the environment sampler's cdf inversion: (marginal uint32[65], rows uint32[H, 65])"""
+        self.L.nxhip_read_env_tables.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        w, h = C.c_uint32(0), C.c_uint32(0)
+        check(self.L.nxhip_read_env_tables(self.h, None, None, None, 0, C.byref(w), C.byref(h)), "nxhip_read_env_tables")
+        marginal, rows = np.zeros(65, np.uint32), np.zeros((h.value, 65), np.uint32)
+        self.L.nxhip_read_env_guides.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
+        check(self.L.nxhip_read_env_guides(self.h, _ptr(marginal), _ptr(rows), h.value), "nxhip_read_env_guides")
+        return marginal, rows
 
     def clear_textures(self):
         check(self.L.nxhip_clear_textures(self.h), "nxhip_clear_textures")
@@ -1210,6 +1252,17 @@ class Scene:
     def set_hdr_map(self, rgba8):
         img = np.ascontiguousarray(rgba8, dtype=np.uint8)
         _scheck(self.L.nxs_scene_set_hdr_map(self.h, _ptr(img), img.shape[1], img.shape[0]), "nxs_scene_set_hdr_map")
+
+    def set_hdr_map_float(self, rgb):
+        """Scene::AddHDRMapFloat: H x W x 3 float32 of linear radiance"""
+        img = np.ascontiguousarray(rgb, dtype=np.float32)
+        self.L.nxs_scene_set_hdr_map_float.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
+        _scheck(self.L.nxs_scene_set_hdr_map_float(self.h, _ptr(img), img.shape[1], img.shape[0]), "nxs_scene_set_hdr_map_float")
+
+    def add_hdr_map_file_float(self, path, file_name):
+        """Scene::AddHDRMapFloat(filePath, fileName): a Radiance .hdr file as linear float radiance"""
+        self.L.nxs_scene_add_hdr_map_file_float.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p]
+        _scheck(self.L.nxs_scene_add_hdr_map_file_float(self.h, path.encode(), file_name.encode()), "nxs_scene_add_hdr_map_file_float")
 
     def add_mesh(self, tris, material_id=-1):
         t = np.ascontiguousarray(tris, dtype=pod.TRI_DT)

@@ -217,6 +217,33 @@ int nxh_decode_png(const uint8_t* data, size_t size, uint32_t* width, uint32_t* 
     });
 }
 
+int nxh_decode_hdr_float(const uint8_t* data, size_t size, uint32_t* width, uint32_t* height, float* dstRgb, size_t dstCapacity)
+{
+    return guarded([&] {
+        if (!data || !width || !height) throw std::runtime_error("nxh_decode_hdr_float: null argument");
+        const FloatImage img = IMGLoader::LoadHDRFloat(data, size);
+        *width = img.width;
+        *height = img.height;
+        if (dstRgb) {
+            if (dstCapacity < img.pixels.size()) throw std::runtime_error("nxh_decode_hdr_float: destination too small");
+            std::memcpy(dstRgb, img.pixels.data(), img.pixels.size() * sizeof(float));
+        }
+    });
+}
+
+int nxs_scene_set_hdr_map_float(nxs_scene* s, const float* rgb, uint32_t w, uint32_t h)
+{
+    return guarded([&] { s->scene.AddHDRMapFloat(w, h, rgb); });
+}
+
+int nxs_scene_add_hdr_map_file_float(nxs_scene* s, const char* path, const char* fileName)
+{
+    return guarded([&] {
+        if (!path || !fileName) throw std::runtime_error("nxs_scene_add_hdr_map_file_float: null argument");
+        s->scene.AddHDRMapFloat(path, fileName);
+    });
+}
+
 int nxs_scene_set_instance_transform(nxs_scene* s, uint32_t instanceId, const float pos[3], const float rotDeg[3], const float scale[3])
 {
     return guarded([&] {

@@ -189,6 +189,8 @@ struct nxhip_ctx : nxd::PassSlot {
     std::vector<uint8_t> hostHdr;
     bool envSampling = false;
     nxd::DevBuf envMarginalCdf, envRowCdf, envDensity, envMarginalGuide, envRowGuide;
+    bool hdrFloat = false;       // hdrMap.texels holds float4 texels (nxhip_upload_env_float) instead of RGBA8; hostHdr is then empty
+    nxd::DevBuf envBuildTemp;    // scratch of the float map's device-side table build (nx_envmap.hip): 2 x height doubles
     // paths / queues
     nxd::DevBuf pixelMap, accumulation, rgba8;
     nxd::DevBuf traceStats;

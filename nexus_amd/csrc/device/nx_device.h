@@ -432,6 +432,10 @@ struct DeviceState {
     const NX_G LightHeader* lightHeader;
     uint32_t lightEntries;
     uint32_t lightGuideSize;              // a power of two: u * lightGuideSize is exact in binary32
+    // Float environment map (nxhip_upload_env_float; nx_envmap.hip): one float4 of linear radiance per texel (w unused), nullptr while the
+    // map is an 8-bit one or there is none.  hdrMap then carries the map's size and a texels pointer that is only TESTED (is there a map),
+    // never read: the colour comes from here (nx_texture.h tex2d_float), the sampler's tables above have the 8-bit maps' layout and meaning.
+    const NX_G float4* envFloat;
 };
 
 // Argument block of the adaptive update's kernels (nx_adaptive.hip; filled by nxhip_adaptive_update)
@@ -475,7 +479,7 @@ constexpr uint64_t layout_stamp()
     const uint64_t w[] = {
         sizeof(DeviceState), offsetof(DeviceState, camera), offsetof(DeviceState, envSampling), offsetof(DeviceState, localCount), offsetof(DeviceState, pixelMap),
         offsetof(DeviceState, radiance), offsetof(DeviceState, trace), offsetof(DeviceState, shadow), offsetof(DeviceState, material), offsetof(DeviceState, counters),
-        offsetof(DeviceState, frame), offsetof(DeviceState, traceStats), offsetof(DeviceState, scanStatus), offsetof(DeviceState, entry), offsetof(DeviceState, entryRuns), offsetof(DeviceState, debugRequeue), offsetof(DeviceState, aovAlbedo), offsetof(DeviceState, aovAccumNormalDepth), offsetof(DeviceState, basePixelMap), offsetof(DeviceState, adStats), offsetof(DeviceState, baseCount), offsetof(DeviceState, lightTable), offsetof(DeviceState, lightHeader), offsetof(DeviceState, lightGuideSize), sizeof(LightEntry), sizeof(LightHeader), sizeof(LightBuild), offsetof(LightBuild, lightCount), sizeof(AdaptiveLaunch), offsetof(AdaptiveLaunch, baseCount), offsetof(DeviceState, thinStates), offsetof(DeviceState, leafOfInstance), sizeof(ThinState), offsetof(ThinState, stack), offsetof(DeviceState, thinClosest), offsetof(DeviceState, thinCapacity), offsetof(DeviceState, thinIters), offsetof(DeviceState, thinPoolLimit), offsetof(Counters, thinCount), sizeof(EntryState), offsetof(EntryState, sp), offsetof(EntryState, triP0), offsetof(EntryState, triInst), offsetof(Counters, scanTicket), offsetof(FrameState, scanEpoch),
+        offsetof(DeviceState, frame), offsetof(DeviceState, traceStats), offsetof(DeviceState, scanStatus), offsetof(DeviceState, entry), offsetof(DeviceState, entryRuns), offsetof(DeviceState, debugRequeue), offsetof(DeviceState, aovAlbedo), offsetof(DeviceState, aovAccumNormalDepth), offsetof(DeviceState, basePixelMap), offsetof(DeviceState, adStats), offsetof(DeviceState, baseCount), offsetof(DeviceState, lightTable), offsetof(DeviceState, lightHeader), offsetof(DeviceState, lightGuideSize), offsetof(DeviceState, envFloat), sizeof(LightEntry), sizeof(LightHeader), sizeof(LightBuild), offsetof(LightBuild, lightCount), sizeof(AdaptiveLaunch), offsetof(AdaptiveLaunch, baseCount), offsetof(DeviceState, thinStates), offsetof(DeviceState, leafOfInstance), sizeof(ThinState), offsetof(ThinState, stack), offsetof(DeviceState, thinClosest), offsetof(DeviceState, thinCapacity), offsetof(DeviceState, thinIters), offsetof(DeviceState, thinPoolLimit), offsetof(Counters, thinCount), sizeof(EntryState), offsetof(EntryState, sp), offsetof(EntryState, triP0), offsetof(EntryState, triInst), offsetof(Counters, scanTicket), offsetof(FrameState, scanEpoch),
         (uint64_t)kScanKinds, (uint64_t)kScanWords, (uint64_t)kScanEpochLimit, (uint64_t)kShadeBlockOrderedThreads,
         sizeof(Counters), sizeof(RegionCounters), offsetof(RegionCounters, traceShadowSize), offsetof(RegionCounters, materialSize), offsetof(RegionCounters, traceHead),
         offsetof(RegionCounters, shadowHead), offsetof(RegionCounters, scanTile), offsetof(RegionCounters, endedSize), offsetof(Counters, orderedBase), offsetof(Counters, tailHead),

@@ -32,6 +32,7 @@ const void* bsdf_hook_kernel_ptr();
 const void* fmath_hook_kernel_ptr();
 const void* tex2d_hook_kernel_ptr();
 const void* env_hook_kernel_ptr();
+const void* tex2d_float_hook_kernel_ptr();
 const void* aov_kernel_ptr();  // nx_aov.hip
 const void* aov_fold_kernel_ptr();
 const void* denoise_gather_kernel_ptr();
@@ -55,6 +56,7 @@ uint64_t layout_stamp_entry();
 uint64_t layout_stamp_aov();
 uint64_t layout_stamp_adaptive();
 uint64_t layout_stamp_lights();
+uint64_t layout_stamp_envmap();
 uint64_t layout_stamp_scene();  // the host units nxhip_*.hip that fill DeviceState, each its own
 uint64_t layout_stamp_render();
 uint64_t layout_stamp_features();
@@ -62,6 +64,9 @@ uint64_t layout_stamp_hooks();
 int light_scan_bytes(size_t entries, size_t* bytes);
 int light_map_mean(hipStream_t st, const TextureDev& t, const float* srgbLut, float* mean4);
 int light_table_build(hipStream_t st, const LightBuild& b, void* scanTemp, size_t scanBytes);
+// nx_envmap.hip: the float environment map's sampler tables, built on the device in stream order (temp: 2 x height doubles)
+int env_float_tables_build(hipStream_t st, const float4* texels, uint32_t width, uint32_t height, double* temp, float* marginalCdf, float* rowCdf, float* density,
+                           uint32_t* marginalGuide, uint32_t* rowGuide);
 int lbvh_build(nxhip_ctx* c, const nx_triangle* dTris, uint32_t n, int plocRadius, DevBuf& nodes, DevBuf& primIdx, DevBuf& isect, uint32_t* nodeCount);
 int lbvh_build_batch(nxhip_ctx* c, const nx_triangle* dTris, const std::vector<uint32_t>& counts, DevBuf& nodes, DevBuf& primIdx, DevBuf& isect, std::vector<uint32_t>& nodeFirst,
                      std::vector<uint32_t>& nodeCounts);
@@ -120,6 +125,7 @@ inline Kernel<const float4*, U32, const U32*, float4*, U32*> compose() { return 
 inline Kernel<const nx_material*, const nx_bsdf_query*, U32, int, nx_bsdf_result*> bsdf_hook() { return {bsdf_hook_kernel_ptr()}; }  // (material, q, count, sample, out)
 inline Kernel<int, const double*, const double*, U32, double*> fmath_hook() { return {fmath_hook_kernel_ptr()}; }                   // (op, a, b, count, out)
 inline Kernel<TextureDev, const float*, const float*, U32, float4*> tex2d_hook() { return {tex2d_hook_kernel_ptr()}; }              // (t, srgbLut, uv, count, out)
+inline Kernel<const float4*, int, int, const float*, U32, float4*> tex2d_float_hook() { return {tex2d_float_hook_kernel_ptr()}; }       // (texels, W, H, uv, count, out)
 inline Kernel<State, int, const float*, U32, float*, float*, U32*> env_hook() { return {env_hook_kernel_ptr()}; }                    // (S, sample, in, count, vec, pdf, texel)
 inline StateKernel aov() { return {aov_kernel_ptr()}; }
 inline StateKernel aov_fold() { return {aov_fold_kernel_ptr()}; }

@@ -42,4 +42,25 @@ NXD float4 tex2d(const TextureDev& t, const float* __restrict__ srgbLut, float u
     return make_float4(out[0], out[1], out[2], out[3]);
 }
 
+// The float environment map's lookup (nxhip_upload_env_float): the same addressing — normalised coordinates, texel centres at +0.5,
+// wrap on both axes — over one float4 of linear radiance per texel, with the EXACT binary32 fractional weights.  The 1/256 steps
+// above imitate a texture unit that only ever filtered 8-bit texels; next to a texel of 6e4, 1/512 of a weight is 117, not a
+// rounding error.  Three roundings per lerp (no contraction: -ffp-contract=off), two lerps deep: within 6 x 2^-24 x the largest tap
+// of the exact bilinear value.
+template <class Texels>  // (const float4*: global in a device-state block, plain as a kernel argument)
+NXD float4 tex2d_float(const Texels texels, const int W, const int H, float u, float v)
+{
+    const float xb = u * (float)W - 0.5f, yb = v * (float)H - 0.5f;
+    const float fx = floorf(xb), fy = floorf(yb);
+    const float ax = xb - fx, ay = yb - fy;
+    const int i0 = wrapi((int)fx, W), i1 = wrapi((int)fx + 1, W);
+    const int j0 = wrapi((int)fy, H), j1 = wrapi((int)fy + 1, H);
+    const float4 t00 = texels[(size_t)j0 * W + i0], t10 = texels[(size_t)j0 * W + i1];
+    const float4 t01 = texels[(size_t)j1 * W + i0], t11 = texels[(size_t)j1 * W + i1];
+    const float tx = t00.x + ax * (t10.x - t00.x), bx = t01.x + ax * (t11.x - t01.x);
+    const float ty = t00.y + ax * (t10.y - t00.y), by = t01.y + ax * (t11.y - t01.y);
+    const float tz = t00.z + ax * (t10.z - t00.z), bz = t01.z + ax * (t11.z - t01.z);
+    return make_float4(tx + ay * (bx - tx), ty + ay * (by - ty), tz + ay * (bz - tz), 1.0f);
+}
+
 }  // namespace nxd

@@ -448,14 +448,21 @@ NXD EnvUv env_uv(f3 d)
     const float phi = nxf_asinf(d.y);
     return EnvUv{(float)((theta + kPiD) * kInvPi * 0.5), (float)(1.0f - (phi + kPiD * 0.5f) * kInvPi)};
 }
+// kFloat = false: an instance that never runs under a map (the two-item logic kernel) leaves the float lookup out and keeps its code
+template <bool kFloat = true>
 NXD f3 env_colour(const DeviceState* S, EnvUv uv)
 {
+    if (kFloat && S->envFloat) {  // (wave-uniform: a float map, linear radiance — nx_texture.h tex2d_float)
+        const float4 c = tex2d_float(S->envFloat, (int)S->hdrMap.width, (int)S->hdrMap.height, uv.u, uv.v);
+        return mk3(c.x, c.y, c.z);
+    }
     const float4 c = tex2d(S->hdrMap, S->srgbLut, uv.u, uv.v);
     return mk3(c.x, c.y, c.z);
 }
+template <bool kFloat = true>
 NXD f3 sample_background(const DeviceState* S, f3 d)
 {
-    if (S->hdrMap.texels) return env_colour(S, env_uv(d));
+    if (S->hdrMap.texels) return env_colour<kFloat>(S, env_uv(d));
     return ld3(S->settings.backgroundColor) * S->settings.backgroundIntensity;
 }
 
@@ -532,7 +539,7 @@ NXD uint32_t nee_light_count(const DeviceState* S) { return S->lightCount + ((S-
 // LogicKernel's decision for one path (PathTracer.cu:136-210), without the queue traffic: a miss ends the path and adds the
 // (MIS-weighted) environment `bg`; a hit survives Russian roulette with probability max(throughput) — `survived`, the
 // throughput divided by it in `throughputOut` — and is shaded as the returned material type, or ends (-1).
-template <class HitInst>
+template <bool kEnvFloat = true, class HitInst>
 NXD int logic_path(const DeviceState* S, const int bounce, const uint32_t frame, const uint32_t seedSlot, const uint32_t pixelIdx, const float hitT, const f3 dir,
                    const float4 tp, HitInst hitInst, bool& miss, f3& bg, bool& survived, f3& throughputOut, uint32_t& inst, bool& needsPrevVertex)
 {
@@ -546,9 +553,9 @@ NXD int logic_path(const DeviceState* S, const int bounce, const uint32_t frame,
         EnvUv uv{0.0f, 0.0f};
         if (S->hdrMap.texels) {
             uv = env_uv(dir);
-            bg = throughput * env_colour(S, uv);
+            bg = throughput * env_colour<kEnvFloat>(S, uv);
         } else {
-            bg = throughput * sample_background(S, dir);
+            bg = throughput * sample_background<kEnvFloat>(S, dir);
         }
         if (S->envSampling && S->hdrMap.texels && bounce > 1 && S->settings.useMIS) {
             // the NEE samples the environment too: weight the BSDF-sampled miss against it (extension)
@@ -628,7 +635,8 @@ __global__ void __launch_bounds__(kLogicBlock, NX_LOGIC_WAVES) logic_kernel(cons
                 const uint32_t hitInstance = S->trace.hitInst[at];
                 bool miss, survived, needsPrevVertex;
                 f3 bg = mk3(0.0f), t = mk3(0.0f);
-                type[u] = logic_path(S, bounce, frame, (uint32_t)index, pixelIdx[u], hit[u].x, mk3(dirPix[u].x, dirPix[u].y, dirPix[u].z), tp, [&]() { return hitInstance; }, miss, bg, survived, t,
+                // (U > 1: the instance of scenes without an environment map — logic_kernel_ptr — whose misses never reach a map lookup)
+                type[u] = logic_path<U == 1>(S, bounce, frame, (uint32_t)index, pixelIdx[u], hit[u].x, mk3(dirPix[u].x, dirPix[u].y, dirPix[u].z), tp, [&]() { return hitInstance; }, miss, bg, survived, t,
                                      inst[u], needsPrevVertex);
                 if (needsPrevVertex) keep_previous_vertex(S, pixelIdx[u], S->trace.rays[0].rayO[at]);
                 if (miss) {
@@ -695,6 +703,7 @@ struct ShadowPayload {
 // NO_MAPS (the SCAN pipeline's material launch only: shade_scan_kernel): no material of the context names a diffuse or an emissive
 // map (the host knows: kFlavorNoMaps, pass_flavor in nxhip_render.hip), so the lookups, the texture coordinates they need and the alpha
 // pass-through draw — made only behind `diffuseMapId != -1` — are not compiled in.  No arithmetic of an executed path changes.
+// Such a context has no environment map either (pass_flavor), so the instance leaves the float map's lookup out as well.
 template <int TYPE, bool POWER, bool NO_MAPS = false>
 NXD bool next_event_estimation(const DeviceState* S, f3 wi, const MatParams& mp, f3 hitPoint, f3 normal, f3 hitGNormal, f3 throughput,
                                uint32_t& rng, ShadowPayload& out)
@@ -718,7 +727,7 @@ NXD bool next_event_estimation(const DeviceState* S, f3 wi, const MatParams& mp,
         const float lightPdf = env_pdf(S, shDir, uv) / (float)nLights;
         if (!pdf_valid(lightPdf)) return false;
         const float weight = power_heuristic(lightPdf, bsdfPdf);
-        out.radiance = (((throughput * weight) * sampleThroughput) * env_colour(S, uv)) / lightPdf;
+        out.radiance = (((throughput * weight) * sampleThroughput) * env_colour<!NO_MAPS>(S, uv)) / lightPdf;
         out.origin = offset_ray(hitPoint, hitGNormal * sgnE(dot3(shDir, normal)));
         out.direction = shDir;
         out.distance = 1e30f;
@@ -1049,7 +1058,7 @@ NXD void shade_scan_type(const DeviceState* __restrict__ S, const int bounce, co
                 bool miss, survived, needsPrevVertex;
                 f3 bg = mk3(0.0f), t = mk3(0.0f);
                 uint32_t inst = 0;
-                logic_path(S, bounce, frame, (uint32_t)at, pixelIdx, 1e30f, mk3(dirPix.x, dirPix.y, dirPix.z), tp, [&]() { return 0u; }, miss, bg, survived, t, inst, needsPrevVertex);
+                logic_path<!NO_MAPS>(S, bounce, frame, (uint32_t)at, pixelIdx, 1e30f, mk3(dirPix.x, dirPix.y, dirPix.z), tp, [&]() { return 0u; }, miss, bg, survived, t, inst, needsPrevVertex);
                 if ((__float_as_uint(bg.x) | __float_as_uint(bg.y) | __float_as_uint(bg.z)) != 0u) {  // (as the logic kernel: +0 changes nothing)
                     float4 r = bounce == 1 ? make_float4(0, 0, 0, 0) : S->radiance[pixelIdx];
                     r.x += bg.x; r.y += bg.y; r.z += bg.z;
@@ -1495,6 +1504,14 @@ __global__ void __launch_bounds__(kWideBlock) tex2d_hook_kernel(const TextureDev
         out[k] = tex2d(t, srgbLut, uv[2 * k], uv[2 * k + 1]);
 }
 
+// ... and the float environment map's lookup (nxhip_tex2d_batch kind 2 on a float map)
+__global__ void __launch_bounds__(kWideBlock) tex2d_float_hook_kernel(const float4* __restrict__ texels, const int W, const int H, const float* __restrict__ uv,
+                                                                       const uint32_t count, float4* __restrict__ out)
+{
+    for (uint32_t k = blockIdx.x * blockDim.x + threadIdx.x; k < count; k += gridDim.x * blockDim.x)
+        out[k] = tex2d_float(texels, W, H, uv[2 * k], uv[2 * k + 1]);
+}
+
 // The environment lookup and its sampler on arrays (nxhip_env_sample_batch / nxhip_env_eval_batch): the product's own env_invert,
 // env_direction, env_uv, env_pdf, env_texel and sample_background.  sample != 0: in = count x 2 random numbers; the direction
 // drawn, its pdf formed as the NEE forms it (from env_uv of the direction) and the texel the inversion picked.  sample == 0: in =
@@ -1558,6 +1575,7 @@ const void* compose_kernel_ptr() { return (const void*)compose_kernel; }
 const void* bsdf_hook_kernel_ptr() { return (const void*)bsdf_hook_kernel; }
 const void* tex2d_hook_kernel_ptr() { return (const void*)tex2d_hook_kernel; }
 const void* env_hook_kernel_ptr() { return (const void*)env_hook_kernel; }
+const void* tex2d_float_hook_kernel_ptr() { return (const void*)tex2d_float_hook_kernel; }
 const void* fmath_hook_kernel_ptr() { return (const void*)fmath_hook_kernel; }
 
 // the device-side layouts this translation unit was compiled with (nx_device.h layout_stamp; compared by nxhip_create)

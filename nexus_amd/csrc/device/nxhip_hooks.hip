@@ -197,12 +197,17 @@ int nxhip_tex2d_batch(nxhip_ctx* c, int kind, int textureId, const float* uv, ui
     if (count == 0) return NXHIP_OK;
     NX_HIP(hipSetDevice(c->device));
     const TextureHost& th = kind == 0 ? c->diffuseMaps[textureId] : kind == 1 ? c->emissiveMaps[textureId] : c->hdrMap;
-    TextureDev t{th.texels.as<uint32_t>(), th.width, th.height};
     DevBuf dUv, dOut;
     NX_ALLOC(dUv, (size_t)count * 8);
     NX_ALLOC(dOut, (size_t)count * 16);
     NX_HIP(hipMemcpy(dUv.p, uv, (size_t)count * 8, hipMemcpyHostToDevice));
-    NX_HIP(launch_untimed(kernels::tex2d_hook(), c->wideBlocks, kWideBlockThreads, c->stream, t, c->srgbLut.as<float>(), dUv.as<float>(), count, dOut.as<float4>()));
+    if (kind == 2 && c->hdrFloat) {  // a float environment map: its own lookup (nx_texture.h tex2d_float), alpha 1
+        NX_HIP(launch_untimed(kernels::tex2d_float_hook(), c->wideBlocks, kWideBlockThreads, c->stream, th.texels.as<float4>(), (int)th.width, (int)th.height, dUv.as<float>(), count,
+                              dOut.as<float4>()));
+    } else {
+        const TextureDev t{th.texels.as<uint32_t>(), th.width, th.height};
+        NX_HIP(launch_untimed(kernels::tex2d_hook(), c->wideBlocks, kWideBlockThreads, c->stream, t, c->srgbLut.as<float>(), dUv.as<float>(), count, dOut.as<float4>()));
+    }
     NX_SYNC_ALL(c);
     NX_HIP(hipMemcpy(rgba, dOut.p, (size_t)count * 16, hipMemcpyDeviceToHost));
     return NXHIP_OK;
@@ -235,6 +240,37 @@ try {
     if (density) NX_HIP(hipMemcpy(density, c->envDensity.p, (size_t)W * H * 4, hipMemcpyDeviceToHost));
     return NXHIP_OK;
 } NX_CATCH("nxhip_read_env_tables")
+
+int nxhip_read_env_guides(nxhip_ctx* c, uint32_t* marginalGuide, uint32_t* rowGuide, uint32_t capacityRows)
+try {
+    NX_CHECK_CTX(c);
+    NX_TRY(env_hook_ready(c, "nxhip_read_env_guides", true));
+    const uint32_t H = c->hdrMap.height;
+    if (rowGuide && capacityRows < H) return fail_invalid("nxhip_read_env_guides: destination too small");
+    NX_HIP(hipSetDevice(c->device));
+    NX_SYNC_ALL(c);
+    if (marginalGuide) NX_HIP(hipMemcpy(marginalGuide, c->envMarginalGuide.p, (size_t)(kEnvGuide + 1) * 4, hipMemcpyDeviceToHost));
+    if (rowGuide) NX_HIP(hipMemcpy(rowGuide, c->envRowGuide.p, (size_t)H * (kEnvGuide + 1) * 4, hipMemcpyDeviceToHost));
+    return NXHIP_OK;
+} NX_CATCH("nxhip_read_env_guides")
+
+int nxhip_read_env_float(nxhip_ctx* c, float* rgb, uint32_t capacityTexels, uint32_t* width, uint32_t* height)
+try {
+    NX_CHECK_CTX(c);
+    if (!c->hdrMap.texels.p || !c->hdrFloat) return fail_invalid("nxhip_read_env_float: no float environment map has been uploaded");
+    const uint32_t W = c->hdrMap.width, H = c->hdrMap.height;
+    if (width) *width = W;
+    if (height) *height = H;
+    if (!rgb) return NXHIP_OK;
+    const size_t texels = (size_t)W * H;
+    if ((size_t)capacityTexels < texels) return fail_invalid("nxhip_read_env_float: destination too small");
+    NX_HIP(hipSetDevice(c->device));
+    NX_SYNC_ALL(c);
+    std::vector<float4> staged(texels);
+    NX_HIP(hipMemcpy(staged.data(), c->hdrMap.texels.p, texels * sizeof(float4), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < texels; i++) { rgb[3 * i] = staged[i].x; rgb[3 * i + 1] = staged[i].y; rgb[3 * i + 2] = staged[i].z; }
+    return NXHIP_OK;
+} NX_CATCH("nxhip_read_env_float")
 
 // in: count x inWidth floats; vec: count x 3; pdf / texel: count each, or null
 static int env_hook(nxhip_ctx* c, int sample, const float* in, uint32_t inWidth, uint32_t count, float* vec, float* pdf, uint32_t* texel)

@@ -283,6 +283,9 @@ std::vector<std::vector<Launch>> frame_levels(nxhip_ctx* c, PassSlot* q)
     thin_level(0);
     const int ob = kShadeBlockOrderedThreads;
     for (int bounce = 1; bounce <= pathLength; bounce++) {
+        // Not only a tuning choice: logic_kernel<true, 2> is compiled WITHOUT the float lookup (nx_wavefront.hip logic_kernel), so under a
+        // float map it would read float4 texels as RGBA8.  The two-item instance is for scenes with no environment map of either kind;
+        // the same test as pass_flavor's kFlavorEnvMap (hdrMap.texels is set for both kinds: nxhip_scene.hip).
         levels.push_back({make_launch(kernels::logic(c->hdrMap.texels.p ? 1 : 2), lg, lb, NXHIP_K_LOGIC, S, bounce)});
         if (bounce == 1) aov_beside(levels.back());
         // graph insertion order of the reference: Diffuse, Plastic, Dielectric, Conductor (PathTracer.cpp:116-120)

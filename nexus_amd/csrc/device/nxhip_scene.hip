@@ -840,16 +840,29 @@ static int refresh_texture_tables(nxhip_ctx* c)
     NX_TRY(build(c->diffuseMaps, c->diffuseTable, c->h.diffuseMaps));
     NX_TRY(build(c->emissiveMaps, c->emissiveTable, c->h.emissiveMaps));
     c->h.hdrMap = TextureDev{c->hdrMap.texels.as<uint32_t>(), c->hdrMap.width, c->hdrMap.height};
+    c->h.envFloat = c->hdrFloat ? c->hdrMap.texels.as<float4>() : nullptr;  // (a float map: hdrMap's pointer is tested, this one read)
     c->stateDirty = true;
     return NXHIP_OK;
 }
 
+// NX_TUNING_KNOBS=1 NX_ENV_TIMING=1: what a build of the tables takes, to stderr (tools only)
+static bool env_timing()
+{
+    const char* on = std::getenv("NX_TUNING_KNOBS");
+    return on && std::atoi(on) == 1 && std::getenv("NX_ENV_TIMING");
+}
+
+static int build_env_tables_float(nxhip_ctx* c);
+
 // Sampling distribution of the environment map (see nx_wavefront.hip, "Environment importance sampling"): texel weight =
 // luminance of the sRGB-decoded texel x sin(polar angle of its row) + 1e-6, accumulated in double; cdfs as float ending in
-// exactly 1; density = weight / total x width x height / (2 pi^2) = pdf per solid angle x cos(latitude).
+// exactly 1; density = weight / total x width x height / (2 pi^2) = pdf per solid angle x cos(latitude).  (An 8-bit map; a float
+// map's tables have the same layout and meaning and are built by build_env_tables_float below.)
 static int build_env_tables(nxhip_ctx* c)
 {
     const uint32_t W = c->hdrMap.width, H = c->hdrMap.height;
+    if (c->envSampling && c->hdrFloat && c->hdrMap.texels.p && W && H) return build_env_tables_float(c);
+    const auto tStart = std::chrono::steady_clock::now();
     if (!c->envSampling || W == 0 || H == 0 || c->hostHdr.size() != (size_t)W * H * 4) {
         c->h.envSampling = 0;
         c->h.envMarginalCdf = c->h.envRowCdf = c->h.envDensity = nullptr;
@@ -902,6 +915,7 @@ static int build_env_tables(nxhip_ctx* c)
     std::vector<uint32_t> marginalGuide(kEnvGuide + 1), rowGuide((size_t)H * (kEnvGuide + 1));
     make_guide(marginal.data(), H, marginalGuide.data());
     for (uint32_t y = 0; y < H; y++) make_guide(&row[(size_t)y * W], W, &rowGuide[(size_t)y * (kEnvGuide + 1)]);
+    const auto tLoops = std::chrono::steady_clock::now();
     NX_SYNC_ALL(c);
     NX_ALLOC(c->envMarginalGuide, marginalGuide.size() * 4);
     NX_ALLOC(c->envRowGuide, rowGuide.size() * 4);
@@ -920,6 +934,55 @@ static int build_env_tables(nxhip_ctx* c)
     c->h.envRowCdf = c->envRowCdf.as<float>();
     c->h.envDensity = c->envDensity.as<float>();
     c->stateDirty = true;
+    if (env_timing())
+        std::fprintf(stderr, "[env tables] host build %u x %u: %.3f ms (the loops %.3f ms, allocations and uploads the rest)\n", W, H,
+                     std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tStart).count(), std::chrono::duration<double, std::milli>(tLoops - tStart).count());
+    return NXHIP_OK;
+}
+
+// The tables of a FLOAT map: the same five arrays, built on the device from the texels that are already there (nx_envmap.hip: the
+// footprint weight, binary64 scans), on the context's stream.  No texel and no table comes back to the host.
+static int build_env_tables_float(nxhip_ctx* c)
+{
+    const uint32_t W = c->hdrMap.width, H = c->hdrMap.height;
+    NX_SYNC_ALL(c);  // nothing may still read the old tables
+    NX_ALLOC(c->envMarginalGuide, (size_t)(kEnvGuide + 1) * 4);
+    NX_ALLOC(c->envRowGuide, (size_t)H * (kEnvGuide + 1) * 4);
+    NX_ALLOC(c->envMarginalCdf, (size_t)H * 4);
+    NX_ALLOC(c->envRowCdf, (size_t)W * H * 4);
+    NX_ALLOC(c->envDensity, (size_t)W * H * 4);
+    NX_ALLOC(c->envBuildTemp, (size_t)H * 2 * sizeof(double));
+    const bool timing = env_timing();
+    struct Events {  // (destroyed on every way out, the early returns of NX_HIP / NX_TRY included)
+        hipEvent_t t0 = nullptr, t1 = nullptr;
+        ~Events()
+        {
+            if (t0) (void)hipEventDestroy(t0);
+            if (t1) (void)hipEventDestroy(t1);
+        }
+    } ev;
+    if (timing) {
+        NX_HIP(hipEventCreate(&ev.t0));
+        NX_HIP(hipEventCreate(&ev.t1));
+        NX_HIP(hipEventRecord(ev.t0, c->stream));
+    }
+    NX_TRY(env_float_tables_build(c->stream, c->hdrMap.texels.as<float4>(), W, H, c->envBuildTemp.as<double>(), c->envMarginalCdf.as<float>(), c->envRowCdf.as<float>(),
+                                  c->envDensity.as<float>(), c->envMarginalGuide.as<uint32_t>(), c->envRowGuide.as<uint32_t>()));
+    if (timing) NX_HIP(hipEventRecord(ev.t1, c->stream));
+    // passes on the other slots' streams must not start on half-built tables (not on the per-frame path)
+    NX_HIP(hipStreamSynchronize(c->stream));
+    if (timing) {
+        float ms = 0.0f;
+        NX_HIP(hipEventElapsedTime(&ms, ev.t0, ev.t1));
+        std::fprintf(stderr, "[env tables] device build %u x %u: %.3f ms (events around the three launches)\n", W, H, ms);
+    }
+    c->h.envMarginalGuide = c->envMarginalGuide.as<uint32_t>();
+    c->h.envRowGuide = c->envRowGuide.as<uint32_t>();
+    c->h.envSampling = 1;
+    c->h.envMarginalCdf = c->envMarginalCdf.as<float>();
+    c->h.envRowCdf = c->envRowCdf.as<float>();
+    c->h.envDensity = c->envDensity.as<float>();
+    c->stateDirty = true;
     return NXHIP_OK;
 }
 
@@ -927,7 +990,7 @@ int nxhip_set_env_sampling(nxhip_ctx* c, int enable)
 try {
     NX_CHECK_CTX(c);
     NX_HIP(hipSetDevice(c->device));
-    if (enable && !c->hdrMap.texels.p) return fail_invalid("nxhip_set_env_sampling: upload the environment map first (nxhip_upload_texture kind 2)");
+    if (enable && !c->hdrMap.texels.p) return fail_invalid("nxhip_set_env_sampling: upload the environment map first (nxhip_upload_texture kind 2 or nxhip_upload_env_float)");
     c->envSampling = enable != 0;
     return build_env_tables(c);
 } NX_CATCH("nxhip_set_env_sampling")
@@ -948,6 +1011,7 @@ try {
     else {
         NX_SYNC_ALL(c);
         c->hdrMap = std::move(t);
+        c->hdrFloat = false;
         c->hostHdr.assign(rgba8, rgba8 + (size_t)width * height * 4);
     }
     if (texId) *texId = id;
@@ -955,6 +1019,33 @@ try {
     if (rc != NXHIP_OK || kind != 2) return rc;
     return build_env_tables(c);  // a new map under an enabled sampler gets new tables
 } NX_CATCH("nxhip_upload_texture")
+
+int nxhip_upload_env_float(nxhip_ctx* c, const float* rgb, uint32_t width, uint32_t height)
+try {
+    NX_CHECK_CTX(c);
+    if (!rgb || width == 0 || height == 0) return fail_invalid("nxhip_upload_env_float: bad arguments");
+    if (width > 32768u || height > 32768u || (uint64_t)width * height > (1ull << 27)) return fail_invalid("nxhip_upload_env_float: at most 32768 texels per axis and 2^27 in all");
+    // before anything is allocated: radiance is finite and not negative (a NaN would poison the sampler's sums, a negative weight its cdfs)
+    const size_t texels = (size_t)width * height;
+    for (size_t i = 0; i < texels * 3; i++)
+        if (!(rgb[i] >= 0.0f && rgb[i] <= 3.402823466e38f)) return fail_invalid("nxhip_upload_env_float: components must be finite and not negative");
+    NX_HIP(hipSetDevice(c->device));
+    TextureHost t;
+    t.width = width;
+    t.height = height;
+    NX_ALLOC(t.texels, texels * sizeof(float4));
+    {
+        std::vector<float4> staged(texels);  // one 16-byte tap per texel (w unused)
+        for (size_t i = 0; i < texels; i++) staged[i] = make_float4(rgb[3 * i], rgb[3 * i + 1], rgb[3 * i + 2], 0.0f);
+        NX_HIP(hipMemcpy(t.texels.p, staged.data(), texels * sizeof(float4), hipMemcpyHostToDevice));
+    }
+    NX_SYNC_ALL(c);
+    c->hdrMap = std::move(t);
+    c->hdrFloat = true;
+    c->hostHdr.clear();
+    NX_TRY(refresh_texture_tables(c));
+    return build_env_tables(c);  // a new map under an enabled sampler gets new tables
+} NX_CATCH("nxhip_upload_env_float")
 
 int nxhip_clear_textures(nxhip_ctx* c)
 try {
@@ -966,6 +1057,7 @@ try {
     c->lightMapMeans = 0;
     c->lightTableDirty = true;
     c->hdrMap = TextureHost();
+    c->hdrFloat = false;
     c->hostHdr.clear();
     c->envSampling = false;
     NX_TRY(build_env_tables(c));

@@ -36,9 +36,9 @@ int paeth(int a, int b, int c)
 
 namespace {
 
-// Radiance .hdr (RGBE, flat or run-length encoded scanlines) reduced to 8 bits the way stbi_load does for an HDR file
-// (stb_image: stbi__hdr_load then stbi__hdr_to_ldr with gamma 2.2, scale 1): c8 = clamp(pow(c, 1 / 2.2) * 255 + 0.5), alpha 255.
-Texture load_radiance_hdr(const unsigned char* data, size_t size)
+// Radiance .hdr (RGBE, flat or run-length encoded scanlines): the file's RGBE records, width x height x 4 bytes, row 0 first — what
+// both decodes (load_radiance_hdr below, IMGLoader::LoadHDRFloat) start from.
+std::vector<unsigned char> read_radiance_rgbe(const unsigned char* data, size_t size, int& w, int& h)
 {
     size_t pos = 0;
     auto line = [&]() {
@@ -58,7 +58,7 @@ Texture load_radiance_hdr(const unsigned char* data, size_t size)
     }
     if (!format) fail("unsupported HDR format (need 32-bit_rle_rgbe)");
     const std::string res = line();
-    int h = 0, w = 0;
+    h = 0, w = 0;
     if (std::sscanf(res.c_str(), "-Y %d +X %d", &h, &w) != 2 || w <= 0 || h <= 0 || w > 32768 || h > 32768) fail("unsupported HDR orientation / size");
     std::vector<unsigned char> rgbe(static_cast<size_t>(w) * h * 4);
     for (int y = 0; y < h; y++) {
@@ -87,6 +87,18 @@ Texture load_radiance_hdr(const unsigned char* data, size_t size)
             pos += static_cast<size_t>(w) * 4;
         }
     }
+    return rgbe;
+}
+
+// component = mantissa x 2^(e - 136); e = 0: 0 (stb_image's stbi__hdr_convert, which both decodes share)
+float rgbe_component(const unsigned char* p, int c) { return p[3] != 0 ? static_cast<float>(p[c]) * std::ldexp(1.0f, static_cast<int>(p[3]) - (128 + 8)) : 0.0f; }
+
+// The records reduced to 8 bits the way stbi_load does for an HDR file (stb_image: stbi__hdr_load then stbi__hdr_to_ldr with
+// gamma 2.2, scale 1): c8 = clamp(pow(c, 1 / 2.2) * 255 + 0.5), alpha 255.
+Texture load_radiance_hdr(const unsigned char* data, size_t size)
+{
+    int w = 0, h = 0;
+    const std::vector<unsigned char> rgbe = read_radiance_rgbe(data, size, w, h);
     Texture tex;
     tex.width = static_cast<uint32_t>(w);
     tex.height = static_cast<uint32_t>(h);
@@ -95,8 +107,7 @@ Texture load_radiance_hdr(const unsigned char* data, size_t size)
     for (size_t i = 0; i < static_cast<size_t>(w) * h; i++) {
         const unsigned char* p = &rgbe[4 * i];
         for (int c = 0; c < 3; c++) {
-            float f = 0.0f;
-            if (p[3] != 0) f = static_cast<float>(p[c]) * std::ldexp(1.0f, static_cast<int>(p[3]) - (128 + 8));
+            const float f = rgbe_component(p, c);
             float z = static_cast<float>(std::pow(static_cast<double>(f), static_cast<double>(1.0f / 2.2f))) * 255.0f + 0.5f;  // stb: (float)pow(x, gamma)
             if (z < 0.0f) z = 0.0f;
             if (z > 255.0f) z = 255.0f;
@@ -263,6 +274,27 @@ Texture IMGLoader::LoadIMG(const unsigned char* data, size_t size)
       passOff += (stride + 1) * ps.h;
     }
     return tex;
+}
+
+FloatImage IMGLoader::LoadHDRFloat(const unsigned char* data, size_t size)
+{
+    int w = 0, h = 0;
+    const std::vector<unsigned char> rgbe = read_radiance_rgbe(data, size, w, h);
+    FloatImage img;
+    img.width = static_cast<uint32_t>(w);
+    img.height = static_cast<uint32_t>(h);
+    img.pixels.resize(static_cast<size_t>(w) * h * 3);
+    for (size_t i = 0; i < static_cast<size_t>(w) * h; i++)
+        for (int c = 0; c < 3; c++) img.pixels[3 * i + static_cast<size_t>(c)] = rgbe_component(&rgbe[4 * i], c);
+    return img;
+}
+
+FloatImage IMGLoader::LoadHDRFloat(const std::string& filepath)
+{
+    std::ifstream f(filepath, std::ios::binary);
+    if (!f) fail("cannot open " + filepath);
+    const std::vector<unsigned char> data((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+    return LoadHDRFloat(data.data(), data.size());
 }
 
 Texture IMGLoader::LoadIMG(const std::string& filepath)

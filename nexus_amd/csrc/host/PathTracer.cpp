@@ -163,11 +163,14 @@ void PathTracer::UpdateDeviceScene(const Scene& scene)
         Check(nxhip_clear_textures(m_Ctx), "nxhip_clear_textures");
         for (const Texture& t : assets.GetDiffuseMaps()) Check(nxhip_upload_texture(m_Ctx, 0, t.pixels.data(), t.width, t.height, nullptr), "nxhip_upload_texture");
         for (const Texture& t : assets.GetEmissiveMaps()) Check(nxhip_upload_texture(m_Ctx, 1, t.pixels.data(), t.width, t.height, nullptr), "nxhip_upload_texture");
-        if (!scene.GetHDRMap().pixels.empty()) Check(nxhip_upload_texture(m_Ctx, 2, scene.GetHDRMap().pixels.data(), scene.GetHDRMap().width, scene.GetHDRMap().height, nullptr), "nxhip_upload_texture");
+        if (!scene.GetHDRMapFloat().pixels.empty()) Check(nxhip_upload_env_float(m_Ctx, scene.GetHDRMapFloat().pixels.data(), scene.GetHDRMapFloat().width, scene.GetHDRMapFloat().height), "nxhip_upload_env_float");
+        else if (!scene.GetHDRMap().pixels.empty()) Check(nxhip_upload_texture(m_Ctx, 2, scene.GetHDRMap().pixels.data(), scene.GetHDRMap().width, scene.GetHDRMap().height, nullptr), "nxhip_upload_texture");
         mutableAssets.texturesDirty = false;
         scene.hdrDirty = false;
     } else if (scene.hdrDirty) {
-        Check(nxhip_upload_texture(m_Ctx, 2, scene.GetHDRMap().pixels.data(), scene.GetHDRMap().width, scene.GetHDRMap().height, nullptr), "nxhip_upload_texture");
+        // whichever kind the scene holds (Scene::AddHDRMap / AddHDRMapFloat: the one replaces the other, here and on the device)
+        if (!scene.GetHDRMapFloat().pixels.empty()) Check(nxhip_upload_env_float(m_Ctx, scene.GetHDRMapFloat().pixels.data(), scene.GetHDRMapFloat().width, scene.GetHDRMapFloat().height), "nxhip_upload_env_float");
+        else Check(nxhip_upload_texture(m_Ctx, 2, scene.GetHDRMap().pixels.data(), scene.GetHDRMap().width, scene.GetHDRMap().height, nullptr), "nxhip_upload_texture");
         scene.hdrDirty = false;
     }
     if (assets.materialsDirty && !assets.GetMaterials().empty()) {

@@ -3,6 +3,8 @@
 // emissive map or intensity * max(emissive) > 0; the TLAS is rebuilt whenever an instance changed.
 #include "nexus/Scene.h"
 
+#include <stdexcept>
+
 #include "nexus/IMGLoader.h"
 #include "nexus/OBJLoader.h"
 
@@ -121,7 +123,24 @@ void Scene::CreateMeshInstanceFromFile(const std::string& path, const std::strin
 void Scene::AddHDRMap(const Texture& texture)
 {
     m_HdrMap = texture;
+    m_HdrMapFloat = FloatImage();
     hdrDirty = true;
+}
+
+void Scene::AddHDRMapFloat(uint32_t width, uint32_t height, const float* rgb)
+{
+    if (!rgb || width == 0 || height == 0) throw std::runtime_error("Scene::AddHDRMapFloat: empty image");
+    m_HdrMapFloat.width = width;
+    m_HdrMapFloat.height = height;
+    m_HdrMapFloat.pixels.assign(rgb, rgb + static_cast<size_t>(width) * height * 3);
+    m_HdrMap = Texture();
+    hdrDirty = true;
+}
+
+void Scene::AddHDRMapFloat(const std::string& filePath, const std::string& fileName)
+{
+    const FloatImage img = IMGLoader::LoadHDRFloat(filePath + fileName);
+    AddHDRMapFloat(img.width, img.height, img.pixels.data());
 }
 
 void Scene::AddHDRMap(const std::string& filePath, const std::string& fileName) { AddHDRMap(IMGLoader::LoadIMG(filePath + fileName)); }

@@ -78,9 +78,8 @@ class LoadedScene:
         self.warnings = []
 
 
-def decode_hdr(data):
-    """Radiance .hdr (RGBE, flat or run-length encoded) -> HxWx4 uint8 the way stbi_load reduces an HDR file to 8 bits
-    (stb_image stbi__hdr_to_ldr: gamma 2.2, scale 1, alpha 255) — what Scene::AddHDRMap gets from IMGLoader (Scene.cpp:93-97)."""
+def _read_rgbe(data):
+    """the RGBE records of a Radiance .hdr file (flat or run-length encoded scanlines): HxWx4 uint8"""
     data = bytes(data)
     pos = 0
 
@@ -125,9 +124,28 @@ def decode_hdr(data):
         else:
             rgbe[y] = np.frombuffer(data, dtype=np.uint8, count=4 * w, offset=pos).reshape(w, 4)
             pos += 4 * w
+    return rgbe
+
+
+def _rgbe_to_float(rgbe):
+    """component = mantissa x 2^(e - 136) in binary32; e = 0: 0 (stb_image's stbi__hdr_convert)"""
     e = rgbe[..., 3].astype(np.int32)
     scale = np.where(e != 0, np.ldexp(np.float32(1.0), e - 136), np.float32(0.0)).astype(np.float32)
-    f = rgbe[..., :3].astype(np.float32) * scale[..., None]
+    return rgbe[..., :3].astype(np.float32) * scale[..., None]
+
+
+def decode_hdr_float(data):
+    """Radiance .hdr -> HxWx3 float32 of linear radiance, nothing clamped: the twin of the C++ IMGLoader::LoadHDRFloat, bit for bit
+    (what Context.upload_env_float takes)."""
+    return np.ascontiguousarray(_rgbe_to_float(_read_rgbe(data)), dtype=np.float32)
+
+
+def decode_hdr(data):
+    """Radiance .hdr (RGBE, flat or run-length encoded) -> HxWx4 uint8 the way stbi_load reduces an HDR file to 8 bits
+    (stb_image stbi__hdr_to_ldr: gamma 2.2, scale 1, alpha 255) — what Scene::AddHDRMap gets from IMGLoader (Scene.cpp:93-97)."""
+    rgbe = _read_rgbe(data)
+    h, w = rgbe.shape[:2]
+    f = _rgbe_to_float(rgbe)
     z = np.power(f.astype(np.float64), np.float64(np.float32(1.0) / np.float32(2.2))).astype(np.float32) * np.float32(255.0) + np.float32(0.5)
     out = np.full((h, w, 4), 255, dtype=np.uint8)
     out[..., :3] = np.clip(z, 0.0, 255.0).astype(np.int32).astype(np.uint8)

@@ -113,7 +113,11 @@ class Workload:
         for img in self.emissive_maps:
             ctx.upload_texture("emissive", img)
         if self.hdr_map is not None:
-            ctx.upload_texture("hdr", self.hdr_map)
+            # a float32 H x W x 3 array is linear radiance (nxhip_upload_env_float); anything else the RGBA8 map it has always been
+            if isinstance(self.hdr_map, np.ndarray) and self.hdr_map.dtype == np.float32:
+                ctx.upload_env_float(self.hdr_map)
+            else:
+                ctx.upload_texture("hdr", self.hdr_map)
             ctx.set_env_sampling(self.env_sampling)
         if self.camera is not None:
             ctx.set_camera(self.camera)
