@@ -1,7 +1,8 @@
 // nexus_render — the reference's render loop (Renderer.cpp:41-77: scene.Update, UpdateDeviceScene, Render) driven headless
 // through the kept C++ host API: load a .glb / .obj, path-trace `frames` frames on an MI355X, write the image as a PPM.
 //
-//   nexus_render [--denoise] [--adaptive THRESHOLD [--max-frames N]] [--light-sampling uniform|power] [--env-float FILE.hdr] [--env-sampling] <dir/> <file.glb|file.obj> <out.ppm> [width height frames pathLength]
+//   nexus_render [--denoise] [--adaptive THRESHOLD [--max-frames N]] [--light-sampling uniform|power] [--env-float FILE.hdr] [--env-sampling]
+//                [--point-light X Y Z INTENSITY] [--sun DX DY DZ IRRADIANCE] <dir/> <file.glb|file.obj> <out.ppm> [width height frames pathLength]
 //                [eyeX eyeY eyeZ fwdX fwdY fwdZ hfovDeg]
 // --denoise: the feature buffers are accumulated with the colour and the image written is the a-trous filtered one (nxhip_denoise)
 // --adaptive THRESHOLD: render to a noise target instead of a frame count (nxhip_render_adaptive: blocks of 64 pixels stop when the
@@ -12,6 +13,9 @@
 // --env-float FILE.hdr: a Radiance .hdr file as the environment, as the linear float radiance it holds (Scene::AddHDRMapFloat,
 //   nxhip_upload_env_float) instead of the 8 bits "Load HDR map" reduces it to.
 // --env-sampling: the light sample may pick the environment map (nxhip_set_env_sampling): what a map with a small bright sun needs.
+// A .glb's KHR_lights_punctual lights (point, spot, directional) are rendered as the file places them, without a flag.
+// --point-light X Y Z INTENSITY: one more white point light at (X, Y, Z), radiant intensity INTENSITY per steradian (Scene::AddAnalyticLight).
+// --sun DX DY DZ IRRADIANCE: a white sun whose light travels along (DX, DY, DZ), irradiance IRRADIANCE on a surface facing it.
 //
 // Build: make example   (links nexus_amd/lib/libnexus_amd.so)
 #include <cstdint>
@@ -33,6 +37,7 @@ int main(int argc, char** argv)
     int lightSampling = NXHIP_LIGHTS_UNIFORM;
     std::string envFloat;
     bool envSampling = false;
+    std::vector<nexus::AnalyticLight> extraLights;
     for (;;) {  // leading options, in any order
         const std::string opt = argc > 1 ? argv[1] : "";
         int used = 0;
@@ -60,6 +65,14 @@ int main(int argc, char** argv)
         } else if (opt == "--env-sampling") {
             envSampling = true;
             used = 1;
+        } else if ((opt == "--point-light" || opt == "--sun") && argc > 5) {
+            nexus::AnalyticLight l;
+            const bool sun = opt == "--sun";
+            l.type = sun ? NX_ALIGHT_DIRECTIONAL : NX_ALIGHT_POINT;
+            for (int k = 0; k < 3; k++) (sun ? l.direction : l.position)[k] = static_cast<float>(std::atof(argv[2 + k]));
+            l.intensity = static_cast<float>(std::atof(argv[5]));
+            extraLights.push_back(l);
+            used = 5;
         }
         if (!used) break;
         argv[used] = argv[0];
@@ -67,7 +80,7 @@ int main(int argc, char** argv)
         argc -= used;
     }
     if (argc < 4) {
-        std::fprintf(stderr, "usage: %s [--denoise] [--adaptive THRESHOLD [--max-frames N]] [--light-sampling uniform|power] [--env-float FILE.hdr] [--env-sampling] <dir/> <file.glb|file.obj> <out.ppm> [width height frames pathLength] [eye(3) forward(3) hfov]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s [--denoise] [--adaptive THRESHOLD [--max-frames N]] [--light-sampling uniform|power] [--env-float FILE.hdr] [--env-sampling] [--point-light X Y Z INTENSITY] [--sun DX DY DZ IRRADIANCE] <dir/> <file.glb|file.obj> <out.ppm> [width height frames pathLength] [eye(3) forward(3) hfov]\n", argv[0]);
         return 2;
     }
     // a program built against these headers and run with another build of libnexus_amd.so gets an error string here, not a GPU fault
@@ -94,7 +107,8 @@ int main(int argc, char** argv)
             pathTracer.SetDeviceBlasBuild(scene, true);
             scene.SetDeviceTlasBuild(true);
         }
-        scene.CreateMeshInstanceFromFile(dir, file);
+        scene.CreateMeshInstanceFromFile(dir, file);  // (a .glb's KHR_lights_punctual lights come with it)
+        for (const nexus::AnalyticLight& l : extraLights) scene.AddAnalyticLight(l);
         scene.GetCamera()->LookAt(nexus::make_float3(cam[0], cam[1], cam[2]), nexus::make_float3(cam[3], cam[4], cam[5]));
         scene.GetCamera()->SetHorizontalFOV(cam[6]);
         scene.GetRenderSettings().pathLength = static_cast<unsigned char>(pathLength);

@@ -33,6 +33,20 @@ struct Light : nx_light {
 };
 static_assert(sizeof(Light) == sizeof(nx_light), "Light must alias nx_light");
 
+// Extension: a light that is no geometry — point, sphere, spot, sun (nx_analytic_light of nexus_pod.h; the sampling rule: nexus_hip.h).
+// Scene::AddAnalyticLight places one; the .glb reader makes one of every KHR_lights_punctual light a node carries.
+struct AnalyticLight : nx_analytic_light {
+    AnalyticLight()
+    {
+        std::memset(static_cast<nx_analytic_light*>(this), 0, sizeof(nx_analytic_light));
+        direction[2] = -1.0f;  // glTF's convention: a light looks down its node's -Z
+        colour[0] = colour[1] = colour[2] = 1.0f;
+        intensity = 1.0f;
+        outerConeAngle = 0.78539816339744830962f;
+    }
+};
+static_assert(sizeof(AnalyticLight) == sizeof(nx_analytic_light), "AnalyticLight must alias nx_analytic_light");
+
 struct Texture {
     enum struct Type { DIFFUSE, ROUGHNESS, METALLIC, EMISSIVE };
     Texture() = default;

@@ -31,6 +31,7 @@ struct LoadedScene {
     // materials' diffuseMapId / emissiveMapId stay -1 here: ids are handed out by the AssetManager in LoadOBJ.
     std::vector<Texture> textures;
     std::vector<int> materialDiffuseTexture, materialEmissiveTexture;
+    std::vector<AnalyticLight> analyticLights;  // glTF KHR_lights_punctual: one per node that carries a light, in world space
     std::vector<std::string> warnings;  // images that could not be decoded (the reference prints and carries on, IMGLoader.cpp:24-25)
 };
 

@@ -36,6 +36,9 @@ public:
     void AddHDRMapFloat(uint32_t width, uint32_t height, const float* rgb);
     size_t AddLight(const Light& light);
     void RemoveLight(size_t index);
+    // Extension: lights that are no geometry (Assets.h AnalyticLight).  Sampled by the light sample only: invisible to camera and bounce rays.
+    size_t AddAnalyticLight(const AnalyticLight& light);
+    void RemoveAnalyticLight(size_t index);
 
     // ---- editing: change a MeshInstance, then tell the scene which one --------------------------------------------
     std::vector<MeshInstance>& GetMeshInstances() { return m_MeshInstances; }
@@ -68,11 +71,12 @@ public:
     const RenderSettings& GetRenderSettings() const { return m_RenderSettings; }
     const std::vector<BVHInstance>& GetBVHInstances() const { return m_BVHInstances; }
     const std::vector<Light>& GetLights() const { return m_Lights; }
+    const std::vector<AnalyticLight>& GetAnalyticLights() const { return m_AnalyticLights; }
     const Texture& GetHDRMap() const { return m_HdrMap; }
     const FloatImage& GetHDRMapFloat() const { return m_HdrMapFloat; }  // pixels empty: the map is GetHDRMap()'s, or there is none
 
     // what the device has not seen yet (set here, cleared by PathTracer::UpdateDeviceScene)
-    mutable bool tlasDirty = true, lightsDirty = true, hdrDirty = false;
+    mutable bool tlasDirty = true, lightsDirty = true, hdrDirty = false, analyticLightsDirty = false;
     // With SetTlasRefit(true): BVH-instance ids whose transform (and nothing else) changed since the device last saw the TLAS.
     // PathTracer::UpdateDeviceScene hands them to nxhip_set_instance_transforms — inverse, bounds, traversal records and the
     // TLAS refit happen in HBM — instead of uploading the tree again.
@@ -91,6 +95,7 @@ private:
     std::vector<MeshInstance> m_MeshInstances;  // what the user edits
     std::vector<BVHInstance> m_BVHInstances;    // what the TLAS and the device see, one per mesh instance
     std::vector<Light> m_Lights;
+    std::vector<AnalyticLight> m_AnalyticLights;
     std::shared_ptr<TLAS> m_Tlas;
 
     std::set<uint32_t> m_InvalidMeshInstances;

@@ -149,8 +149,51 @@ int nxhip_update_blas_device(nxhip_ctx *ctx, int32_t blasId, const void *trisDev
 int nxhip_read_tlas(nxhip_ctx *ctx, nx_bvh8_node *nodes, uint32_t nodeCapacity, nx_bvh_instance *instances, uint32_t instanceCapacity);
 /* AssetManager device materials — Assets/AssetManager.cpp:57-62,106-116 */
 int nxhip_set_materials(nxhip_ctx *ctx, const nx_material *materials, uint32_t count);
-/* Scene::m_DeviceLights — Scene/Scene.cpp:142-176 */
+/* Scene::m_DeviceLights — Scene/Scene.cpp:142-176.  Only NX_LIGHT_MESH entries are sampled: an NX_LIGHT_POINT or NX_LIGHT_AREA entry yields
+ * no light sample (the 12-byte record has no position).  Lights that are not geometry go through nxhip_set_analytic_lights below. */
 int nxhip_set_lights(nxhip_ctx *ctx, const nx_light *lights, uint32_t count);
+/* Extension — analytic lights: point, sphere, spot, and sun (delta or disc), nx_analytic_light of nexus_pod.h, world space.  Radiometric RGB
+ * throughout (no 683 lm/W); glTF `range` is ignored.  The call replaces the table; count 0 removes it, and the context is then exactly
+ * what it was before the first call (the default kernel instances, the same frames bit for bit).  nxhip_set_lights is untouched by it.
+ *
+ * Validation, on the host before anything is allocated — NXHIP_ERR_INVALID and the previous table stays in place: lights NULL with
+ * count > 0; any field not finite; radius, intensity, a colour component or angularRadius below 0; angularRadius >= pi/2; a direction of
+ * length 0, whatever the kind (any other length is normalised on the host, in binary64); SPOT cone angles outside
+ * 0 <= inner < outer <= pi/2; an unknown type; lightCount + count + 1 > 2^23 (the resolution of the random number that picks — while the
+ * table is not empty nxhip_set_lights refuses a count that would pass the same bound).
+ * The device table is derived on the host in binary64 and rounded once: the unit axis, colour x intensity, radius^2,
+ * angleScale = 1 / max(1e-3, cos inner - cos outer), angleOffset = -cos outer x angleScale, q = 1 - cos(angularRadius) =
+ * 2 sin^2(angularRadius / 2).
+ *
+ * THE SAMPLING RULE.  A = the number of analytic lights.  The light sample picks uniformly among
+ *   nLights = lightCount + A + [environment sampled],
+ * in the order mesh lights, analytic lights, environment — in NXHIP_LIGHTS_UNIFORM and in NXHIP_LIGHTS_POWER alike (there the table still
+ * decides which mesh triangle; analytic lights are uniform among themselves).  For a pick of analytic light l at shading point x:
+ *   origin     o = x offset along the geometric normal to the light's side (the side of the light's centre; of -direction for a
+ *              DIRECTIONAL light), as the environment branch offsets its origin.
+ *   axis       a = (P - o) / d, d = |P - o| (POINT, SPOT);  a = -direction, d := 1 (DIRECTIONAL).
+ *   cone       s^2 = radius^2 / d^2; no sample when d <= radius.  q = 1 - cos thetaMax = s^2 / (1 + sqrt(1 - s^2)) (POINT, SPOT); q from
+ *              the table (DIRECTIONAL).  Never 1 - sqrt(1 - s^2): in binary32 that is 7 % off at radius / d = 1e-3 and 32 % off at
+ *              3e-4; the stated form is good to 1e-7.
+ *   direction  cos theta = 1 - r1 q;  sin^2 theta = r1 q (2 - r1 q) (no 1 - cos^2);  phi = 2 pi r2 about a.  Two random numbers are
+ *              drawn whatever the kind, so a path's stream does not depend on the kind.  direction = t0 cos phi sin theta +
+ *              t1 sin phi sin theta + a cos theta in the branch-free frame of Duff et al. 2017: s = copysign(1, a.z), k = -1 / (s + a.z),
+ *              b = a.x a.y k, t0 = (1 + s a.x^2 k, s b, -s a.x), t1 = (b, s + a.y^2 k, -a.y).
+ *   shadow ray tmax = d cos theta - sqrt(max(0, radius^2 - d^2 sin^2 theta)), the near intersection with the sphere (POINT, SPOT);
+ *              1e30 (DIRECTIONAL).
+ *   radiance   throughput x fcos x colour x intensity x att x 2 / (d^2 (1 + cos thetaMax)) x nLights, fcos = the BSDF evaluation's
+ *              throughput (Bsdf::eval, whose own validity rule stays in force as for mesh lights).  The factor is radiance / pdf of the
+ *              uniform cone — L = I / (pi r^2) for the sphere, E / (pi sin^2 alpha) for the disc — and tends to I / d^2 and E as the
+ *              radius goes to 0.
+ *   att        SPOT only, else 1: clamp(cd x angleScale + angleOffset, 0, 1)^2, cd = the cosine between the spot's axis and the
+ *              direction from the light's centre to o — KHR_lights_punctual's formula, taken at the centre, not per sampled point.
+ *   weight     none.  Analytic lights are not geometry: camera and bounce rays do not see them, no BSDF-sampled ray can reach one, the
+ *              MIS weight is 1.  No validity test on the cone's density either (it is never below 1 / 4 pi).
+ * useMIS == 0: without analytic lights no light sample is taken at all; with A > 0 one is taken among the analytic lights alone
+ * (nLights := A), because nothing else can find them.  The MIS weight of an emissive hit and of a weighted miss uses the same nLights,
+ * A included.
+ * The kernels that know these lights are compile-time instances launched only while A > 0 (bit 10 of nxhip_debug_pass_flavor's word). */
+int nxhip_set_analytic_lights(nxhip_ctx *ctx, const nx_analytic_light *lights, uint32_t count);
 /* Texture::ToDevice — Assets/Texture.cpp:10-39 (RGBA8, sRGB, wrap, bilinear).  kind: 0 diffuse, 1 emissive, 2 hdr map.
  * Diffuse/emissive maps get ids in upload order; the hdr map replaces the previous one. */
 int nxhip_upload_texture(nxhip_ctx *ctx, int kind, const uint8_t *rgba8, uint32_t width, uint32_t height, int32_t *texId);
@@ -555,6 +598,13 @@ int nxhip_light_pick_batch(nxhip_ctx *ctx, const float *u, uint32_t count, uint3
 int nxhip_read_env_tables(nxhip_ctx *ctx, float *marginalCdf, float *rowCdf, float *density, uint32_t capacityTexels, uint32_t *width, uint32_t *height);
 int nxhip_env_sample_batch(nxhip_ctx *ctx, const float *r, uint32_t count, float *direction, float *pdf, uint32_t *texel);
 int nxhip_env_eval_batch(nxhip_ctx *ctx, const float *direction, uint32_t count, float *rgb, float *pdf, uint32_t *texel);
+/* The analytic lights' draw on arrays — a test hook over the product's own sampling function (a `make release` library refuses it):
+ * for light `lightIndex` of the table and every k < count, origins3[3k..] = o as the rule above uses it (already offset), r2[2k..] = (r1, r2)
+ * in [0, 1): direction3[3k..], tmax[k], factor3[3k..] = colour x intensity x att x 2 / (d^2 (1 + cos thetaMax)), ok[k] = 0 when d <= radius
+ * (the other outputs of that k are then meaningless).  NXHIP_ERR_INVALID: no such light, a NULL array, an origin that is not finite, an
+ * r outside [0, 1). */
+int nxhip_analytic_light_sample_batch(nxhip_ctx *ctx, uint32_t lightIndex, const float *origins3, const float *r2, uint32_t count,
+                                      float *direction3, float *tmax, float *factor3, uint32_t *ok);
 /* The three above work on an environment map of either kind (a float map's P(texel) follows nxhip_upload_env_float's weight).
  * read_env_float: the float map as it is stored, rgb = width x height x 3 floats, bit for bit what was uploaded (rgb NULL: only
  * *width / *height are written, which may be NULL too); NXHIP_ERR_INVALID while the environment map is not a float one or
@@ -640,6 +690,7 @@ static inline uint64_t nxhip_header_abi_stamp(void)
         sizeof(nx_bvh8_node), offsetof(nx_bvh8_node, meta), sizeof(nx_triangle), offsetof(nx_triangle, texCoord0),
         sizeof(nx_bvh_instance), offsetof(nx_bvh_instance, transform), offsetof(nx_bvh_instance, materialId),
         sizeof(nx_material), offsetof(nx_material, emissive), offsetof(nx_material, type), sizeof(nx_light), offsetof(nx_light, type),
+        sizeof(nx_analytic_light), offsetof(nx_analytic_light, direction), offsetof(nx_analytic_light, colour), offsetof(nx_analytic_light, innerConeAngle), offsetof(nx_analytic_light, type),
         sizeof(nx_camera), offsetof(nx_camera, resolution), sizeof(nx_render_settings), offsetof(nx_render_settings, backgroundColor),
         sizeof(nx_ray), sizeof(nx_hit), sizeof(nx_bsdf_query), sizeof(nx_bsdf_result), offsetof(nx_bsdf_result, rngOut),
         sizeof(nxhip_queue_sizes), sizeof(nxhip_trace_stats), offsetof(nxhip_trace_stats, cycles), sizeof(nxhip_kernel_times), NXHIP_K_COUNT,

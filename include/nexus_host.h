@@ -82,6 +82,11 @@ uint32_t nxh_loaded_texture_count(const nxh_loaded_scene *s);
 int nxh_loaded_texture_info(const nxh_loaded_scene *s, uint32_t index, uint32_t *width, uint32_t *height, int32_t *kind);
 int nxh_loaded_texture_pixels(const nxh_loaded_scene *s, uint32_t index, uint8_t *dstRgba8);
 int nxh_loaded_material_textures(const nxh_loaded_scene *s, int32_t *diffuseTexture, int32_t *emissiveTexture);
+/* glTF KHR_lights_punctual: one record per node that carries a light — position = the node's world translation, direction = its -Z axis,
+ * colour x intensity as written (radiometric, no 683 lm/W), spot cone angles defaulting to 0 and pi/4, radius and angular radius 0;
+ * `range` is ignored.  dst receives nxh_loaded_analytic_light_count records. */
+uint32_t nxh_loaded_analytic_light_count(const nxh_loaded_scene *s);
+int nxh_loaded_analytic_lights(const nxh_loaded_scene *s, nx_analytic_light *dst);
 uint32_t nxh_loaded_warning_count(const nxh_loaded_scene *s);
 const char *nxh_loaded_warning(const nxh_loaded_scene *s, uint32_t index);
 /* IMGLoader::LoadIMG (Assets/IMGLoader.cpp:17-41: stbi_load with 4 channels) for PNG data: RGBA8, row 0 first.
@@ -127,6 +132,13 @@ int nxs_scene_set_camera(nxs_scene *s, const float pos[3], const float forward[3
 int nxs_scene_set_render_settings(nxs_scene *s, const nx_render_settings *settings);
 int nxs_scene_update(nxs_scene *s);
 uint32_t nxs_scene_light_count(const nxs_scene *s);
+/* Extension: Scene::AddAnalyticLight / GetAnalyticLights — point, sphere, spot and sun lights (nx_analytic_light, nexus_pod.h), uploaded by
+ * the next device update (nxhip_set_analytic_lights, which validates them).  nxs_scene_load_file adds a .glb's KHR_lights_punctual lights.
+ * *index (may be NULL) = the light's place in the list; nxs_scene_analytic_lights copies up to `capacity` records out. */
+int nxs_scene_add_analytic_light(nxs_scene *s, const nx_analytic_light *light, uint32_t *index);
+int nxs_scene_remove_analytic_light(nxs_scene *s, uint32_t index);
+uint32_t nxs_scene_analytic_light_count(const nxs_scene *s);
+int nxs_scene_analytic_lights(const nxs_scene *s, nx_analytic_light *dst, uint32_t capacity);
 uint32_t nxs_scene_instance_count(const nxs_scene *s);
 
 int nxs_pathtracer_create(uint32_t width, uint32_t height, int device, nxs_pathtracer **out);

@@ -10,6 +10,7 @@
  *   nx_bvh_instance 160 B  Cuda/BVH/BVHInstance.cuh:7-14
  *   nx_material      60 B  Cuda/Scene/Material.cuh:5-51
  *   nx_light         12 B  Cuda/Scene/Light.cuh:4-33
+ *   (nx_analytic_light 64 B: an extension, no reference layout)
  *   nx_camera        88 B  Cuda/Scene/Camera.cuh:5-15
  *   nx_render_settings 20 B Cuda/Scene/Scene.cuh:10-17, Renderer/RenderSettings.h:4-10
  */
@@ -88,6 +89,21 @@ typedef struct nx_light {
     int8_t type;
 } nx_light;
 NX_STATIC_ASSERT(sizeof(nx_light) == 12, "nx_light must be 12 bytes");
+
+/* Extension: an analytic light (nxhip_set_analytic_lights; the sampling rule is stated in full in include/nexus_hip.h).  The 12-byte
+ * nx_light above carries no position, so its NX_LIGHT_POINT can never be placed; this record can.  World space.  Radiometric RGB
+ * throughout: no 683 lm/W enters anywhere.  glTF's `range` has no counterpart and is ignored by the loaders. */
+enum { NX_ALIGHT_POINT = 0, NX_ALIGHT_SPOT = 1, NX_ALIGHT_DIRECTIONAL = 2 };
+typedef struct NX_ALIGN(16) nx_analytic_light {
+    float position[3];  float radius;         /* POINT, SPOT: centre; sphere radius, 0 = a point            */
+    float direction[3]; float angularRadius;  /* SPOT: axis, away from the light.  DIRECTIONAL: the way the  */
+                                              /* light travels; half-angle of the disc in radians, 0 = delta */
+    float colour[3];    float intensity;      /* POINT, SPOT: colour x intensity = radiant intensity per sr  */
+                                              /* DIRECTIONAL: irradiance of a surface facing the light       */
+    float innerConeAngle, outerConeAngle;     /* SPOT, radians, 0 <= inner < outer <= pi/2                   */
+    uint32_t type, pad_;
+} nx_analytic_light;
+NX_STATIC_ASSERT(sizeof(nx_analytic_light) == 64, "nx_analytic_light must be 64 bytes");
 
 typedef struct NX_ALIGN(8) nx_camera {
     float position[3];

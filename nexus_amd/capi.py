@@ -34,6 +34,7 @@ HIP_SYMBOLS = [
     "nxhip_set_light_sampling", "nxhip_read_light_table", "nxhip_light_pick_batch",
     "nxhip_read_env_tables", "nxhip_env_sample_batch", "nxhip_env_eval_batch",
     "nxhip_upload_env_float", "nxhip_read_env_float", "nxhip_read_env_guides",
+    "nxhip_set_analytic_lights", "nxhip_analytic_light_sample_batch",
 ]
 HOST_SYMBOLS = [
     "nxh_bvh8_build", "nxh_tlas_build", "nxh_tlas_refit", "nxh_bvh8_refit", "nxh_bvh8_node_count", "nxh_bvh8_prim_count", "nxh_bvh8_nodes",
@@ -52,6 +53,8 @@ HOST_SYMBOLS = [
     "nxs_pathtracer_update_device_scene", "nxs_pathtracer_render", "nxs_pathtracer_reset_frame_number", "nxs_pathtracer_frame_number",
     "nxs_pathtracer_read_pixels", "nxs_pathtracer_device_context",
     "nxs_scene_set_hdr_map_float", "nxs_scene_add_hdr_map_file_float", "nxh_decode_hdr_float",
+    "nxh_loaded_analytic_light_count", "nxh_loaded_analytic_lights",
+    "nxs_scene_add_analytic_light", "nxs_scene_remove_analytic_light", "nxs_scene_analytic_light_count", "nxs_scene_analytic_lights",
 ]
 
 
@@ -92,6 +95,7 @@ def abi_words():
         pod.NODE_DT.itemsize, off(pod.NODE_DT, "meta"), pod.TRI_DT.itemsize, off(pod.TRI_DT, "texCoord0"),
         pod.INST_DT.itemsize, off(pod.INST_DT, "transform"), off(pod.INST_DT, "materialId"),
         pod.MAT_DT.itemsize, off(pod.MAT_DT, "emissive"), off(pod.MAT_DT, "type"), pod.LIGHT_DT.itemsize, off(pod.LIGHT_DT, "type"),
+        pod.ALIGHT_DT.itemsize, off(pod.ALIGHT_DT, "direction"), off(pod.ALIGHT_DT, "colour"), off(pod.ALIGHT_DT, "innerConeAngle"), off(pod.ALIGHT_DT, "type"),
         pod.CAM_DT.itemsize, off(pod.CAM_DT, "resolution"), pod.SETTINGS_DT.itemsize, off(pod.SETTINGS_DT, "backgroundColor"),
         pod.RAY_DT.itemsize, pod.HIT_DT.itemsize, pod.BSDF_QUERY_DT.itemsize, pod.BSDF_RESULT_DT.itemsize, off(pod.BSDF_RESULT_DT, "rngOut"),
         C.sizeof(QueueSizes), C.sizeof(TraceStats), TraceStats.cycles.offset, C.sizeof(KernelTimes), len(KERNEL_CLASSES),
@@ -428,6 +432,24 @@ def load_scene_file(path):
     return meshes, mats, insts
 
 
+def load_scene_analytic_lights(path):
+    """the KHR_lights_punctual lights of a .glb as the C++ reader makes them: pod.ALIGHT_DT records, one per node that carries a light"""
+    L = lib()
+    h = C.c_void_p()
+    if L.nxh_load_scene_file(str(path).encode(), C.byref(h)) != 0:
+        raise NexusError("nxh_load_scene_file: " + L.nxs_last_error().decode())
+    try:
+        L.nxh_loaded_analytic_light_count.argtypes = [C.c_void_p]
+        L.nxh_loaded_analytic_light_count.restype = C.c_uint32
+        L.nxh_loaded_analytic_lights.argtypes = [C.c_void_p, C.c_void_p]
+        lights = np.zeros(L.nxh_loaded_analytic_light_count(h), dtype=pod.ALIGHT_DT)
+        if len(lights) and L.nxh_loaded_analytic_lights(h, _ptr(lights)) != 0:
+            raise NexusError(L.nxs_last_error().decode())
+    finally:
+        L.nxh_loaded_scene_free(h)
+    return lights
+
+
 def load_scene_textures(path):
     """The images of a scene file as the C++ reader decodes them: (textures [(kind, HxWx4 uint8)], diffuse texture index
     per material, emissive texture index per material, warnings)."""
@@ -496,6 +518,7 @@ def decode_image(data):
 
 
 FLAVOR_IDENTITY, FLAVOR_NO_MAPS = 256, 512  # Context.debug_pass_flavor: the specialised kernel instances of a pass graph
+FLAVOR_ANALYTIC = 1024  # ... and the instances of a context with analytic lights (set_analytic_lights)
 
 
 class Context:
@@ -555,6 +578,28 @@ class Context:
     def set_lights(self, lights):
         lights = np.ascontiguousarray(lights, dtype=pod.LIGHT_DT)
         check(self.L.nxhip_set_lights(self.h, _ptr(lights) if len(lights) else None, len(lights)), "nxhip_set_lights")
+
+    def set_analytic_lights(self, lights):
+        """point, sphere, spot and sun lights (pod.ALIGHT_DT records, pod.make_analytic_light); an empty list removes them
+        (nxhip_set_analytic_lights: the sampling rule is in include/nexus_hip.h)"""
+        lights = np.ascontiguousarray(lights, dtype=pod.ALIGHT_DT).reshape(-1)
+        self.L.nxhip_set_analytic_lights.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+        check(self.L.nxhip_set_analytic_lights(self.h, _ptr(lights) if len(lights) else None, len(lights)), "nxhip_set_analytic_lights")
+
+    def analytic_light_sample_batch(self, light_index, origins, r):
+        """the light sample's draw for analytic light `light_index` from every origin[k] with the random pair r[k] in [0, 1)^2 — a test hook:
+        (direction float32[n, 3], tmax float32[n], factor float32[n, 3], ok bool[n])"""
+        o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
+        r = np.ascontiguousarray(r, dtype=np.float32).reshape(-1, 2)
+        assert len(o) == len(r)
+        direction = np.zeros((len(o), 3), dtype=np.float32)
+        tmax = np.zeros(len(o), dtype=np.float32)
+        factor = np.zeros((len(o), 3), dtype=np.float32)
+        ok = np.zeros(len(o), dtype=np.uint32)
+        self.L.nxhip_analytic_light_sample_batch.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        check(self.L.nxhip_analytic_light_sample_batch(self.h, int(light_index), _ptr(o), _ptr(r), len(o), _ptr(direction), _ptr(tmax), _ptr(factor), _ptr(ok)),
+              "nxhip_analytic_light_sample_batch")
+        return direction, tmax, factor, ok != 0
 
     def upload_texture(self, kind, rgba8):
         img = np.ascontiguousarray(rgba8, dtype=np.uint8)
@@ -1314,6 +1359,27 @@ class Scene:
 
     def light_count(self):
         return int(self.L.nxs_scene_light_count(self.h))
+
+    def add_analytic_light(self, light):
+        """Scene::AddAnalyticLight: a pod.ALIGHT_DT record (pod.make_analytic_light); returns its index"""
+        l = np.ascontiguousarray(light, dtype=pod.ALIGHT_DT).reshape(1)
+        i = C.c_uint32(0)
+        self.L.nxs_scene_add_analytic_light.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]
+        _scheck(self.L.nxs_scene_add_analytic_light(self.h, _ptr(l), C.byref(i)), "nxs_scene_add_analytic_light")
+        return int(i.value)
+
+    def remove_analytic_light(self, index):
+        self.L.nxs_scene_remove_analytic_light.argtypes = [C.c_void_p, C.c_uint32]
+        _scheck(self.L.nxs_scene_remove_analytic_light(self.h, int(index)), "nxs_scene_remove_analytic_light")
+
+    def analytic_lights(self):
+        """Scene::GetAnalyticLights: the records as the scene holds them (added by hand or read from a .glb's KHR_lights_punctual)"""
+        self.L.nxs_scene_analytic_light_count.argtypes = [C.c_void_p]
+        self.L.nxs_scene_analytic_light_count.restype = C.c_uint32
+        self.L.nxs_scene_analytic_lights.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+        out = np.zeros(int(self.L.nxs_scene_analytic_light_count(self.h)), dtype=pod.ALIGHT_DT)
+        _scheck(self.L.nxs_scene_analytic_lights(self.h, _ptr(out) if len(out) else None, len(out)), "nxs_scene_analytic_lights")
+        return out
 
     def instance_count(self):
         return int(self.L.nxs_scene_instance_count(self.h))

@@ -199,6 +199,14 @@ int nxh_loaded_material_textures(const nxh_loaded_scene* s, int32_t* diffuseText
         }
     });
 }
+uint32_t nxh_loaded_analytic_light_count(const nxh_loaded_scene* s) { return static_cast<uint32_t>(s->ls.analyticLights.size()); }
+int nxh_loaded_analytic_lights(const nxh_loaded_scene* s, nx_analytic_light* dst)
+{
+    return guarded([&] {
+        if (!dst) throw std::runtime_error("nxh_loaded_analytic_lights: null destination");
+        for (size_t i = 0; i < s->ls.analyticLights.size(); i++) dst[i] = s->ls.analyticLights[i];
+    });
+}
 uint32_t nxh_loaded_warning_count(const nxh_loaded_scene* s) { return static_cast<uint32_t>(s->ls.warnings.size()); }
 const char* nxh_loaded_warning(const nxh_loaded_scene* s, uint32_t index) { return index < s->ls.warnings.size() ? s->ls.warnings[index].c_str() : ""; }
 
@@ -296,6 +304,26 @@ int nxs_scene_update(nxs_scene* s)
 }
 
 uint32_t nxs_scene_light_count(const nxs_scene* s) { return static_cast<uint32_t>(s->scene.GetLights().size()); }
+int nxs_scene_add_analytic_light(nxs_scene* s, const nx_analytic_light* light, uint32_t* index)
+{
+    return guarded([&] {
+        if (!light) throw std::runtime_error("nxs_scene_add_analytic_light: null light");
+        AnalyticLight l;
+        static_cast<nx_analytic_light&>(l) = *light;
+        const size_t at = s->scene.AddAnalyticLight(l);
+        if (index) *index = static_cast<uint32_t>(at);
+    });
+}
+int nxs_scene_remove_analytic_light(nxs_scene* s, uint32_t index) { return guarded([&] { s->scene.RemoveAnalyticLight(index); }); }
+uint32_t nxs_scene_analytic_light_count(const nxs_scene* s) { return static_cast<uint32_t>(s->scene.GetAnalyticLights().size()); }
+int nxs_scene_analytic_lights(const nxs_scene* s, nx_analytic_light* dst, uint32_t capacity)
+{
+    return guarded([&] {
+        if (!dst && capacity) throw std::runtime_error("nxs_scene_analytic_lights: null destination");
+        const std::vector<AnalyticLight>& al = s->scene.GetAnalyticLights();
+        for (size_t i = 0; i < al.size() && i < capacity; i++) dst[i] = al[i];
+    });
+}
 uint32_t nxs_scene_instance_count(const nxs_scene* s) { return static_cast<uint32_t>(s->scene.GetBVHInstances().size()); }
 
 int nxs_pathtracer_create(uint32_t width, uint32_t height, int device, nxs_pathtracer** out)

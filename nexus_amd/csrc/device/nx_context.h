@@ -173,6 +173,7 @@ struct nxhip_ctx : nxd::PassSlot {
     nxd::DevBuf shadeInst;        // [instanceCount] ShadeInst (nx_device.h): rebuilt before a render when an instance, BLAS or material table changed
     bool shadeInstDirty = true;
     std::vector<nx_light> hostLights;
+    nxd::DevBuf alights;  // [h.alightCount] ALight: the analytic lights' device table (nxhip_set_analytic_lights)
     std::vector<uint32_t> hostInstIdx;  // TLAS leaf order
     nxd::DevBuf materials, lights;
     // device-side dynamic transforms (nx_refit.hip): TLAS nodes grouped by depth (deepest first), leaf slot of every instance,
@@ -220,6 +221,7 @@ struct nxhip_ctx : nxd::PassSlot {
     int traceBlocks = 0, shadowBlocks = 0, wideBlocks = 0;  // full-chip persistent grids (see trace_blocks)
     int tailBlocks = 0;
     int tailBlocksPower = 0;  // grid of tail_kernel<true> (NXHIP_LIGHTS_POWER), from that instance's own occupancy
+    int tailBlocksAnalytic[2] = {0, 0};  // grids of tail_kernel<POWER, true> (analytic lights: kFlavorAnalytic), [0] uniform, [1] POWER
     int tailBounce = -1;  // first bounce of the tail kernel, 0 = off, -1 = automatic (see tail_bounce in nxhip_render.hip)
     bool traceGridForced = false;                            // NX_TRACE_BLOCKS_*: use them as they are
     int shadeBlocksPerCU = 10, logicBlocksPerCU = 2;  // grid-stride kernels: workgroups per CU

@@ -345,6 +345,17 @@ struct LightBuild {
     uint32_t lightCount, entries, guideSize, pad_;
 };
 
+// One analytic light as the kernels read it (nxhip_set_analytic_lights; sampled by nx_alights.h alight_sample): four 16-byte loads.
+// Derived on the host in binary64 from the caller's nx_analytic_light and rounded once (nxhip_scene.hip):
+//   v0  centre xyz, radius                            (DIRECTIONAL: 0)
+//   v1  axis xyz (unit; SPOT: away from the light, DIRECTIONAL: the way the light travels), q = 1 - cos(angularRadius) (DIRECTIONAL; else 0)
+//   v2  colour x intensity rgb, w = 1 for a DIRECTIONAL light, else 0
+//   v3  angleScale, angleOffset (SPOT; every other kind 0 and 1: the falloff is then 1 without a select), radius^2, unused
+struct alignas(16) ALight {
+    float4 v0, v1, v2, v3;
+};
+static_assert(sizeof(ALight) == 64, "ALight is four 16-byte loads");
+
 struct DeviceState {
     // scene
     const NX_G uint4* tlasNodes;
@@ -436,6 +447,11 @@ struct DeviceState {
     // map is an 8-bit one or there is none.  hdrMap then carries the map's size and a texels pointer that is only TESTED (is there a map),
     // never read: the colour comes from here (nx_texture.h tex2d_float), the sampler's tables above have the 8-bit maps' layout and meaning.
     const NX_G float4* envFloat;
+    // Analytic lights (nxhip_set_analytic_lights; nx_alights.h), nullptr / 0 while there are none.  Read only by the ANALYTIC instances of
+    // the material kernels, which pass graphs launch while alightCount > 0 (kFlavorAnalytic).  Last in the block: nothing in front moves.
+    const NX_G ALight* alights;  // [alightCount]
+    uint32_t alightCount;
+    uint32_t padAlights_;
 };
 
 // Argument block of the adaptive update's kernels (nx_adaptive.hip; filled by nxhip_adaptive_update)
@@ -479,7 +495,7 @@ constexpr uint64_t layout_stamp()
     const uint64_t w[] = {
         sizeof(DeviceState), offsetof(DeviceState, camera), offsetof(DeviceState, envSampling), offsetof(DeviceState, localCount), offsetof(DeviceState, pixelMap),
         offsetof(DeviceState, radiance), offsetof(DeviceState, trace), offsetof(DeviceState, shadow), offsetof(DeviceState, material), offsetof(DeviceState, counters),
-        offsetof(DeviceState, frame), offsetof(DeviceState, traceStats), offsetof(DeviceState, scanStatus), offsetof(DeviceState, entry), offsetof(DeviceState, entryRuns), offsetof(DeviceState, debugRequeue), offsetof(DeviceState, aovAlbedo), offsetof(DeviceState, aovAccumNormalDepth), offsetof(DeviceState, basePixelMap), offsetof(DeviceState, adStats), offsetof(DeviceState, baseCount), offsetof(DeviceState, lightTable), offsetof(DeviceState, lightHeader), offsetof(DeviceState, lightGuideSize), offsetof(DeviceState, envFloat), sizeof(LightEntry), sizeof(LightHeader), sizeof(LightBuild), offsetof(LightBuild, lightCount), sizeof(AdaptiveLaunch), offsetof(AdaptiveLaunch, baseCount), offsetof(DeviceState, thinStates), offsetof(DeviceState, leafOfInstance), sizeof(ThinState), offsetof(ThinState, stack), offsetof(DeviceState, thinClosest), offsetof(DeviceState, thinCapacity), offsetof(DeviceState, thinIters), offsetof(DeviceState, thinPoolLimit), offsetof(Counters, thinCount), sizeof(EntryState), offsetof(EntryState, sp), offsetof(EntryState, triP0), offsetof(EntryState, triInst), offsetof(Counters, scanTicket), offsetof(FrameState, scanEpoch),
+        offsetof(DeviceState, frame), offsetof(DeviceState, traceStats), offsetof(DeviceState, scanStatus), offsetof(DeviceState, entry), offsetof(DeviceState, entryRuns), offsetof(DeviceState, debugRequeue), offsetof(DeviceState, aovAlbedo), offsetof(DeviceState, aovAccumNormalDepth), offsetof(DeviceState, basePixelMap), offsetof(DeviceState, adStats), offsetof(DeviceState, baseCount), offsetof(DeviceState, lightTable), offsetof(DeviceState, lightHeader), offsetof(DeviceState, lightGuideSize), offsetof(DeviceState, envFloat), offsetof(DeviceState, alights), offsetof(DeviceState, alightCount), sizeof(ALight), sizeof(LightEntry), sizeof(LightHeader), sizeof(LightBuild), offsetof(LightBuild, lightCount), sizeof(AdaptiveLaunch), offsetof(AdaptiveLaunch, baseCount), offsetof(DeviceState, thinStates), offsetof(DeviceState, leafOfInstance), sizeof(ThinState), offsetof(ThinState, stack), offsetof(DeviceState, thinClosest), offsetof(DeviceState, thinCapacity), offsetof(DeviceState, thinIters), offsetof(DeviceState, thinPoolLimit), offsetof(Counters, thinCount), sizeof(EntryState), offsetof(EntryState, sp), offsetof(EntryState, triP0), offsetof(EntryState, triInst), offsetof(Counters, scanTicket), offsetof(FrameState, scanEpoch),
         (uint64_t)kScanKinds, (uint64_t)kScanWords, (uint64_t)kScanEpochLimit, (uint64_t)kShadeBlockOrderedThreads,
         sizeof(Counters), sizeof(RegionCounters), offsetof(RegionCounters, traceShadowSize), offsetof(RegionCounters, materialSize), offsetof(RegionCounters, traceHead),
         offsetof(RegionCounters, shadowHead), offsetof(RegionCounters, scanTile), offsetof(RegionCounters, endedSize), offsetof(Counters, orderedBase), offsetof(Counters, tailHead),

@@ -18,10 +18,10 @@ const void* trace_kernel_ptr(bool anyHit, bool stats, bool identity = false);  /
 const void* trace_entry_kernel_ptr(bool identity = false);
 const void* thin_kernel_ptr();
 const void* entry_state_kernel_ptr();  // nx_entry.hip
-const void* tail_kernel_ptr(bool lightPower);  // nx_wavefront.hip
-const void* logic_kernel_ptr(int items);
-const void* shade_kernel_ptr(int type, bool lightPower);
-const void* shade_scan_kernel_ptr(bool lightPower, bool noMaps = false);
+const void* tail_kernel_ptr(bool lightPower, bool analytic = false);  // nx_wavefront.hip
+const void* logic_kernel_ptr(int items, bool analytic = false);
+const void* shade_kernel_ptr(int type, bool lightPower, bool analytic = false);
+const void* shade_scan_kernel_ptr(bool lightPower, bool noMaps = false, bool analytic = false);
 const void* count_scan_kernel_ptr();
 const void* begin_frame_kernel_ptr();
 const void* hook_sizes_kernel_ptr();
@@ -32,6 +32,7 @@ const void* bsdf_hook_kernel_ptr();
 const void* fmath_hook_kernel_ptr();
 const void* tex2d_hook_kernel_ptr();
 const void* env_hook_kernel_ptr();
+const void* alight_hook_kernel_ptr();
 const void* tex2d_float_hook_kernel_ptr();
 const void* aov_kernel_ptr();  // nx_aov.hip
 const void* aov_fold_kernel_ptr();
@@ -111,10 +112,10 @@ inline BounceKernel trace(bool anyHit, bool stats, bool identity = false) { retu
 inline BounceKernel trace_entry(bool identity = false) { return {trace_entry_kernel_ptr(identity)}; }
 inline BounceKernel thin() { return {thin_kernel_ptr()}; }
 inline StateKernel entry_state() { return {entry_state_kernel_ptr()}; }
-inline BounceKernel tail(bool lightPower) { return {tail_kernel_ptr(lightPower)}; }
-inline BounceKernel logic(int items) { return {logic_kernel_ptr(items)}; }
-inline BounceKernel shade(int type, bool lightPower) { return {shade_kernel_ptr(type, lightPower)}; }
-inline TypeKernel shade_scan(bool lightPower, bool noMaps = false) { return {shade_scan_kernel_ptr(lightPower, noMaps)}; }
+inline BounceKernel tail(bool lightPower, bool analytic = false) { return {tail_kernel_ptr(lightPower, analytic)}; }
+inline BounceKernel logic(int items, bool analytic = false) { return {logic_kernel_ptr(items, analytic)}; }
+inline BounceKernel shade(int type, bool lightPower, bool analytic = false) { return {shade_kernel_ptr(type, lightPower, analytic)}; }
+inline TypeKernel shade_scan(bool lightPower, bool noMaps = false, bool analytic = false) { return {shade_scan_kernel_ptr(lightPower, noMaps, analytic)}; }
 inline TypeKernel count_scan() { return {count_scan_kernel_ptr()}; }
 inline Kernel<DeviceState*, U32, U32, U32> begin_frame() { return {begin_frame_kernel_ptr()}; }  // (S, frames, frameLast, scanEpoch)
 inline Kernel<DeviceState*, U32, int, int> hook_sizes() { return {hook_sizes_kernel_ptr()}; }    // (S, n, anyHit, slot)
@@ -127,6 +128,8 @@ inline Kernel<int, const double*, const double*, U32, double*> fmath_hook() { re
 inline Kernel<TextureDev, const float*, const float*, U32, float4*> tex2d_hook() { return {tex2d_hook_kernel_ptr()}; }              // (t, srgbLut, uv, count, out)
 inline Kernel<const float4*, int, int, const float*, U32, float4*> tex2d_float_hook() { return {tex2d_float_hook_kernel_ptr()}; }       // (texels, W, H, uv, count, out)
 inline Kernel<State, int, const float*, U32, float*, float*, U32*> env_hook() { return {env_hook_kernel_ptr()}; }                    // (S, sample, in, count, vec, pdf, texel)
+// (S, light, origin, r, count, direction, tmax, factor, ok)
+inline Kernel<State, U32, const float*, const float*, U32, float*, float*, float*, U32*> alight_hook() { return {alight_hook_kernel_ptr()}; }
 inline StateKernel aov() { return {aov_kernel_ptr()}; }
 inline StateKernel aov_fold() { return {aov_fold_kernel_ptr()}; }
 inline Kernel<State, float4*, float4*, float4*, U32*> denoise_gather() { return {denoise_gather_kernel_ptr()}; }  // (S, colour, albedo, normalDepth, rgba8)

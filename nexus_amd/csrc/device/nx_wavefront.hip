@@ -19,6 +19,7 @@
 #include "nx_device.h"
 #include "nx_math.h"
 #include "nx_lights.h"
+#include "nx_alights.h"
 #include "nx_queue.h"
 #include "nx_texture.h"
 #include "nx_tonemap.h"
@@ -531,7 +532,13 @@ NXD f3 env_sample(const DeviceState* S, float r1, float r2)
 }
 
 // lights the NEE chooses among: the mesh lights, plus the environment when it is importance sampled
-NXD uint32_t nee_light_count(const DeviceState* S) { return S->lightCount + ((S->envSampling && S->hdrMap.texels) ? 1u : 0u); }
+// (ANALYTIC: ... and the analytic lights between the two — only the instances of contexts that have some read their count)
+template <bool ANALYTIC = false>
+NXD uint32_t nee_light_count(const DeviceState* S)
+{
+    if constexpr (ANALYTIC) return S->lightCount + S->alightCount + ((S->envSampling && S->hdrMap.texels) ? 1u : 0u);
+    else return S->lightCount + ((S->envSampling && S->hdrMap.texels) ? 1u : 0u);
+}
 
 // ------------------------------------------------------------------------------------------------------
 // LogicKernel — PathTracer.cu:136-210
@@ -539,7 +546,7 @@ NXD uint32_t nee_light_count(const DeviceState* S) { return S->lightCount + ((S-
 // LogicKernel's decision for one path (PathTracer.cu:136-210), without the queue traffic: a miss ends the path and adds the
 // (MIS-weighted) environment `bg`; a hit survives Russian roulette with probability max(throughput) — `survived`, the
 // throughput divided by it in `throughputOut` — and is shaded as the returned material type, or ends (-1).
-template <bool kEnvFloat = true, class HitInst>
+template <bool kEnvFloat = true, bool ANALYTIC = false, class HitInst>
 NXD int logic_path(const DeviceState* S, const int bounce, const uint32_t frame, const uint32_t seedSlot, const uint32_t pixelIdx, const float hitT, const f3 dir,
                    const float4 tp, HitInst hitInst, bool& miss, f3& bg, bool& survived, f3& throughputOut, uint32_t& inst, bool& needsPrevVertex)
 {
@@ -559,7 +566,7 @@ NXD int logic_path(const DeviceState* S, const int bounce, const uint32_t frame,
         }
         if (S->envSampling && S->hdrMap.texels && bounce > 1 && S->settings.useMIS) {
             // the NEE samples the environment too: weight the BSDF-sampled miss against it (extension)
-            const float envPdf = env_pdf(S, dir, uv) / (float)nee_light_count(S);
+            const float envPdf = env_pdf(S, dir, uv) / (float)nee_light_count<ANALYTIC>(S);
             if (pdf_valid(envPdf)) bg = bg * power_heuristic(tp.w, envPdf);
         }
     } else {
@@ -592,7 +599,7 @@ NXD void keep_previous_vertex(const DeviceState* S, const uint32_t pixelIdx, con
     if ((__float_as_uint(rayOrigin.w) & kRayPassThrough) == 0u) S->rayOrigin[pixelIdx] = make_float4(rayOrigin.x, rayOrigin.y, rayOrigin.z, 0.0f);
 }
 
-template <bool ORDERED, int U>
+template <bool ORDERED, int U, bool ANALYTIC = false>  // (ANALYTIC: the weighted miss counts the analytic lights — nee_light_count)
 // 8 waves per SIMD (60 VGPRs, no spills): two of the 1024-thread workgroups fit a CU instead of one, so the barriers of the
 // slot allocation in one overlap with the streaming of the other (logic kernel -16 %, bench +1 %)
 #ifndef NX_LOGIC_WAVES
@@ -636,7 +643,7 @@ __global__ void __launch_bounds__(kLogicBlock, NX_LOGIC_WAVES) logic_kernel(cons
                 bool miss, survived, needsPrevVertex;
                 f3 bg = mk3(0.0f), t = mk3(0.0f);
                 // (U > 1: the instance of scenes without an environment map — logic_kernel_ptr — whose misses never reach a map lookup)
-                type[u] = logic_path<U == 1>(S, bounce, frame, (uint32_t)index, pixelIdx[u], hit[u].x, mk3(dirPix[u].x, dirPix[u].y, dirPix[u].z), tp, [&]() { return hitInstance; }, miss, bg, survived, t,
+                type[u] = logic_path<U == 1, ANALYTIC>(S, bounce, frame, (uint32_t)index, pixelIdx[u], hit[u].x, mk3(dirPix[u].x, dirPix[u].y, dirPix[u].z), tp, [&]() { return hitInstance; }, miss, bg, survived, t,
                                      inst[u], needsPrevVertex);
                 if (needsPrevVertex) keep_previous_vertex(S, pixelIdx[u], S->trace.rays[0].rayO[at]);
                 if (miss) {
@@ -704,15 +711,42 @@ struct ShadowPayload {
 // map (the host knows: kFlavorNoMaps, pass_flavor in nxhip_render.hip), so the lookups, the texture coordinates they need and the alpha
 // pass-through draw — made only behind `diffuseMapId != -1` — are not compiled in.  No arithmetic of an executed path changes.
 // Such a context has no environment map either (pass_flavor), so the instance leaves the float map's lookup out as well.
-template <int TYPE, bool POWER, bool NO_MAPS = false>
+// ANALYTIC (nxhip_set_analytic_lights with count > 0: kFlavorAnalytic): the pick is among mesh lights, then analytic lights, then the
+// environment; an analytic pick draws its direction from the cone the light subtends (nx_alights.h alight_sample) and carries no MIS
+// weight — no other ray can find such a light.  With useMIS off the sample is taken among the analytic lights alone.  The instances
+// with ANALYTIC = false are the code of a context without such lights.
+template <int TYPE, bool POWER, bool NO_MAPS = false, bool ANALYTIC = false>
 NXD bool next_event_estimation(const DeviceState* S, f3 wi, const MatParams& mp, f3 hitPoint, f3 normal, f3 hitGNormal, f3 throughput,
                                uint32_t& rng, ShadowPayload& out)
 {
     // no lights: the reference indexes an empty array here (undefined); defined as "no light sample, no random numbers
     // drawn", identically in the CPU restatement used by the tests
-    const uint32_t nLights = nee_light_count(S);
+    uint32_t nLights = nee_light_count<ANALYTIC>(S);
+    uint32_t firstPick = 0u;
+    if constexpr (ANALYTIC) {
+        if (S->settings.useMIS == 0) { nLights = S->alightCount; firstPick = S->lightCount; }  // (nothing else can find them)
+    }
     if (nLights == 0u) return false;
-    const uint32_t pick = uniform_index(nLights, rng);
+    const uint32_t pick = firstPick + uniform_index(nLights, rng);
+    if constexpr (ANALYTIC) {
+        if (pick >= S->lightCount && pick - S->lightCount < S->alightCount) {
+            const NX_G ALight* L = &S->alights[pick - S->lightCount];
+            const float r1 = rng_next(rng), r2 = rng_next(rng);  // (two numbers whatever the kind)
+            // the origin goes to the light's side of the surface, as the environment branch's does: by the direction to the centre
+            const float4 l0 = L->v0, l1 = L->v1, l2 = L->v2;
+            const f3 toLight = l2.w != 0.0f ? -mk3(l1.x, l1.y, l1.z) : mk3(l0.x, l0.y, l0.z) - hitPoint;
+            out.origin = offset_ray(hitPoint, hitGNormal * sgnE(dot3(toLight, normal)));
+            f3 factor;
+            if (!alight_sample(L, out.origin, r1, r2, out.direction, out.distance, factor)) return false;
+            const float4 q = rotation_to_z(normal);
+            const f3 wo = rotate_point(q, out.direction);
+            f3 sampleThroughput;
+            float bsdfPdf;
+            if (!Bsdf<TYPE>::eval(mp, wi, wo, sampleThroughput, bsdfPdf)) return false;
+            out.radiance = ((throughput * sampleThroughput) * factor) * (float)nLights;
+            return true;
+        }
+    }
     if (pick >= S->lightCount) {
         // the environment (extension): direction from the map's luminance distribution, shadow ray to infinity
         const float r1 = rng_next(rng), r2 = rng_next(rng);
@@ -807,7 +841,7 @@ NXD bool next_event_estimation(const DeviceState* S, f3 wi, const MatParams& mp,
 // (only read for an emissive hit under MIS).  emit(radiance, instance) receives what the hit emits towards the path; what comes out: the shadow ray of its
 // light sample, the continuation ray and the path state that goes with it.  (Separate references, not a struct: the
 // compiler kept a struct of these in scratch memory, +30 % on the material kernels.)
-template <int TYPE, bool POWER, bool NO_MAPS = false, class PrevOrigin, class Emit>
+template <int TYPE, bool POWER, bool NO_MAPS = false, bool ANALYTIC = false, class PrevOrigin, class Emit>
 NXD void shade_path(const DeviceState* S, const int bounce, const uint32_t frame, const uint32_t seedSlot, const uint32_t pixelIdx, const float hu, const float hv,
                     const uint32_t triIdx, const uint32_t instanceIdx, const f3 rayDirection, const float4 tpdf, PrevOrigin prevOrigin, Emit emit,
                     bool& wantShadow, ShadowPayload& sh, bool& wantTrace, bool& updatePath, f3& nextOrigin, f3& nextDir, f3& nextThroughput, float& nextPdf)
@@ -855,13 +889,13 @@ NXD void shade_path(const DeviceState* S, const int bounce, const uint32_t frame
                 const uint32_t l = S->instLight[instanceIdx];
                 if (l != kNotALight && S->lightHeader->valid != 0u) P = light_entry_prob(S->lightTable, S->lightBase[l] + triIdx);
                 if (P > 0.0f) {
-                    float lightPdf = (P * ((float)S->lightCount / (float)nee_light_count(S))) / area;
+                    float lightPdf = (P * ((float)S->lightCount / (float)nee_light_count<ANALYTIC>(S))) / area;
                     lightPdf *= dSquared / cosThetaO;
                     if (!pdf_valid(lightPdf)) weight = 0.0f;
                     else weight = power_heuristic(lastPdf, lightPdf);
                 }
             } else {
-                float lightPdf = 1.0f / ((float)(nee_light_count(S) * inst->triCount) * area);
+                float lightPdf = 1.0f / ((float)(nee_light_count<ANALYTIC>(S) * inst->triCount) * area);
                 lightPdf *= dSquared / cosThetaO;
                 if (!pdf_valid(lightPdf)) weight = 0.0f;
                 else weight = power_heuristic(lastPdf, lightPdf);
@@ -890,7 +924,7 @@ NXD void shade_path(const DeviceState* S, const int bounce, const uint32_t frame
             nextDir = wo;
             wantTrace = true;
         } else {
-            if (useMIS) wantShadow = next_event_estimation<TYPE, POWER, NO_MAPS>(S, wi, mp, p, normal, gNormal, throughput, rng, sh);
+            if (useMIS || ANALYTIC) wantShadow = next_event_estimation<TYPE, POWER, NO_MAPS, ANALYTIC>(S, wi, mp, p, normal, gNormal, throughput, rng, sh);
             float pdf;
             f3 sampleThroughput;
             if (Bsdf<TYPE>::sample(mp, wi, rng, wo, sampleThroughput, pdf)) {
@@ -911,7 +945,7 @@ NXD void shade_path(const DeviceState* S, const int bounce, const uint32_t frame
 // at 4 waves (126 VGPRs) for one large pass, +4.5 % for one-frame passes in flight, where a smaller register footprint lets
 // the material kernels of one slot share SIMDs with the trace waves of another.  6 and 8 waves per SIMD spill 30-87 VGPRs and
 // double the kernel's time: it is sensitive to memory traffic, not short of waves.
-template <int TYPE, bool ORDERED, bool POWER>
+template <int TYPE, bool ORDERED, bool POWER, bool ANALYTIC = false>
 #ifndef NX_SHADE_WAVES
 #define NX_SHADE_WAVES 5
 #endif
@@ -947,7 +981,7 @@ __global__ void __launch_bounds__(ORDERED ? kShadeBlockOrderedThreads : kShadeBl
             pixelIdx = __float_as_uint(hit.x);
             const uint32_t instanceIdx = __float_as_uint(dirInst.w);
             tpdf = bounce == 1 ? make_float4(1.0f, 1.0f, 1.0f, 1.0e10f) : mq.tp[at];
-            shade_path<TYPE, POWER>(S, bounce, frame, (uint32_t)requestIdx, pixelIdx, hit.y, hit.z, __float_as_uint(hit.w), instanceIdx, mk3(dirInst.x, dirInst.y, dirInst.z), tpdf,
+            shade_path<TYPE, POWER, false, ANALYTIC>(S, bounce, frame, (uint32_t)requestIdx, pixelIdx, hit.y, hit.z, __float_as_uint(hit.w), instanceIdx, mk3(dirInst.x, dirInst.y, dirInst.z), tpdf,
                              [&]() { return S->rayOrigin[pixelIdx]; },
                              [&](f3 emitted, uint32_t instIdx) {
                                  if (bounce == 1 && bounce != (int)S->settings.pathLength && pixelIdx < S->localCount && S->frame->pixelQueryPixel == (int)global_pixel(S, pixelIdx))
@@ -1009,7 +1043,7 @@ static_assert(kScanRing >= kShadeBlock + 4 * kShadeBlock && (kScanRing & (kScanR
 // from `staticTiles` on are handed out by ticket — one returning atomic per tile on the region's own word.  The share of a tile
 // that is this type's to shade varies from none to all with what the camera sees there, so a static split leaves most workgroups
 // waiting for the few whose tiles were full (measured: +40 % on the kernels).
-template <int TYPE, bool POWER, bool NO_MAPS = false>
+template <int TYPE, bool POWER, bool NO_MAPS = false, bool ANALYTIC = false>
 NXD void shade_scan_type(const DeviceState* __restrict__ S, const int bounce, const bool dropEnded, const int region, const int inRegion, const int per, const int firstTile,
                          const int staticTiles, int* const sRing, int* const sHead, int* const sTicket)
 {
@@ -1058,7 +1092,7 @@ NXD void shade_scan_type(const DeviceState* __restrict__ S, const int bounce, co
                 bool miss, survived, needsPrevVertex;
                 f3 bg = mk3(0.0f), t = mk3(0.0f);
                 uint32_t inst = 0;
-                logic_path<!NO_MAPS>(S, bounce, frame, (uint32_t)at, pixelIdx, 1e30f, mk3(dirPix.x, dirPix.y, dirPix.z), tp, [&]() { return 0u; }, miss, bg, survived, t, inst, needsPrevVertex);
+                logic_path<!NO_MAPS, ANALYTIC>(S, bounce, frame, (uint32_t)at, pixelIdx, 1e30f, mk3(dirPix.x, dirPix.y, dirPix.z), tp, [&]() { return 0u; }, miss, bg, survived, t, inst, needsPrevVertex);
                 if ((__float_as_uint(bg.x) | __float_as_uint(bg.y) | __float_as_uint(bg.z)) != 0u) {  // (as the logic kernel: +0 changes nothing)
                     float4 r = bounce == 1 ? make_float4(0, 0, 0, 0) : S->radiance[pixelIdx];
                     r.x += bg.x; r.y += bg.y; r.z += bg.z;
@@ -1091,7 +1125,7 @@ NXD void shade_scan_type(const DeviceState* __restrict__ S, const int bounce, co
             // ... and the path's previous vertex, for hits that can need it (keep_previous_vertex)
             const uint32_t typeAndFlag = *(const NX_G uint32_t*)((const NX_G char*)&S->shadeInst[instanceIdx].material + kMaterialTypeOffset);
             if ((typeAndFlag >> 8) & 1u) keep_previous_vertex(S, pixelIdx, in.rayO[at]);
-            shade_path<TYPE, POWER, NO_MAPS>(S, bounce, frame, (uint32_t)at, pixelIdx, hit.y, hit.z, __float_as_uint(hit.w), instanceIdx, mk3(dirPix.x, dirPix.y, dirPix.z), tpdf,
+            shade_path<TYPE, POWER, NO_MAPS, ANALYTIC>(S, bounce, frame, (uint32_t)at, pixelIdx, hit.y, hit.z, __float_as_uint(hit.w), instanceIdx, mk3(dirPix.x, dirPix.y, dirPix.z), tpdf,
                              [&]() { return S->rayOrigin[pixelIdx]; },
                              [&](f3 emitted, uint32_t instIdx) {
                                  if (bounce == 1 && bounce != (int)S->settings.pathLength && pixelIdx < S->localCount && S->frame->pixelQueryPixel == (int)global_pixel(S, pixelIdx))
@@ -1205,7 +1239,7 @@ NXD void shade_scan_type(const DeviceState* __restrict__ S, const int bounce, co
 // workgroups start on different types (rank modulo the number of types) and move on to the next type when theirs has no tile
 // left, so the types run side by side, the launch ends when the last tile of the last type does, and a bounce costs one material
 // launch instead of one per type (the reference: four, PathTracer.cpp:116-120).  A single-bit mask is a per-type launch.
-template <bool POWER, bool NO_MAPS = false>  // (the light sample's mode, a map-free context: next_event_estimation)
+template <bool POWER, bool NO_MAPS = false, bool ANALYTIC = false>  // (the light sample's mode, a map-free context, analytic lights: next_event_estimation)
 __global__ void __launch_bounds__(kShadeBlock, NX_SHADE_WAVES) shade_scan_kernel(const DeviceState* __restrict__ S, const int bounceArg, const int typeMask)
 {
     const int bounce = bounceArg & 0xff;
@@ -1240,11 +1274,11 @@ __global__ void __launch_bounds__(kShadeBlock, NX_SHADE_WAVES) shade_scan_kernel
         const int starters = (ranks - want + nTypes - 1) / nTypes;  // workgroups whose first type this is: each takes the tile of its index
         const int first = step == 0 ? myIndex : -1;
         switch (type) {
-        case NX_MAT_DIFFUSE: shade_scan_type<NX_MAT_DIFFUSE, POWER, NO_MAPS>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket); break;
-        case NX_MAT_PLASTIC: shade_scan_type<NX_MAT_PLASTIC, POWER, NO_MAPS>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket); break;
-        case NX_MAT_DIELECTRIC: shade_scan_type<NX_MAT_DIELECTRIC, POWER, NO_MAPS>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket); break;
-        case NX_MAT_CONDUCTOR: shade_scan_type<NX_MAT_CONDUCTOR, POWER, NO_MAPS>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket); break;
-        case kScanMiss: shade_scan_type<kScanMiss, POWER, NO_MAPS>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket); break;
+        case NX_MAT_DIFFUSE: shade_scan_type<NX_MAT_DIFFUSE, POWER, NO_MAPS, ANALYTIC>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket); break;
+        case NX_MAT_PLASTIC: shade_scan_type<NX_MAT_PLASTIC, POWER, NO_MAPS, ANALYTIC>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket); break;
+        case NX_MAT_DIELECTRIC: shade_scan_type<NX_MAT_DIELECTRIC, POWER, NO_MAPS, ANALYTIC>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket); break;
+        case NX_MAT_CONDUCTOR: shade_scan_type<NX_MAT_CONDUCTOR, POWER, NO_MAPS, ANALYTIC>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket); break;
+        case kScanMiss: shade_scan_type<kScanMiss, POWER, NO_MAPS, ANALYTIC>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket); break;
         default: break;
         }
     }
@@ -1275,7 +1309,7 @@ __global__ void __launch_bounds__(kWideBlock) count_scan_kernel(const DeviceStat
 #ifndef NX_TAIL_REFILL_BELOW
 #define NX_TAIL_REFILL_BELOW 40
 #endif
-template <bool POWER>  // (the light sample's mode: next_event_estimation)
+template <bool POWER, bool ANALYTIC = false>  // (the light sample's mode, analytic lights: next_event_estimation)
 __global__ void __launch_bounds__(kTraceBlock) tail_kernel(const DeviceState* __restrict__ S, const int firstBounceArg)
 {
     // firstBounce | kTraceScanFlag: the pass ran the SCAN pipeline so far — the rays of trace(firstBounce - 1) are in the set of
@@ -1341,7 +1375,7 @@ __global__ void __launch_bounds__(kTraceBlock) tail_kernel(const DeviceState* __
         if (alive) {
             bool miss, survived, needsPrevVertex;
             f3 bg = mk3(0.0f), t = mk3(0.0f);
-            type = logic_path(S, bounce, frame, (uint32_t)index, pixelIdx, hitT, dir, tp, [&]() { return inst; }, miss, bg, survived, t, inst, needsPrevVertex);
+            type = logic_path<true, ANALYTIC>(S, bounce, frame, (uint32_t)index, pixelIdx, hitT, dir, tp, [&]() { return inst; }, miss, bg, survived, t, inst, needsPrevVertex);
             if (miss) { rad.x += bg.x; rad.y += bg.y; rad.z += bg.z; dirty = true; }
             if (survived) { tp.x = t.x; tp.y = t.y; tp.z = t.z; }
             if (type < 0) alive = false;
@@ -1360,20 +1394,20 @@ __global__ void __launch_bounds__(kTraceBlock) tail_kernel(const DeviceState* __
         };
         if (__ballot(alive && type == NX_MAT_DIFFUSE) != 0ull) {
             if (alive && type == NX_MAT_DIFFUSE)
-                shade_path<NX_MAT_DIFFUSE, POWER>(S, bounce, frame, (uint32_t)index, pixelIdx, hu, hv, tri, inst, dir, tp, prevOrigin, emit, wantShadowRay, sh, wantTrace, updatePath, nextOrigin, nextDir, nextThroughput, nextPdf);
+                shade_path<NX_MAT_DIFFUSE, POWER, false, ANALYTIC>(S, bounce, frame, (uint32_t)index, pixelIdx, hu, hv, tri, inst, dir, tp, prevOrigin, emit, wantShadowRay, sh, wantTrace, updatePath, nextOrigin, nextDir, nextThroughput, nextPdf);
         }
         if (__ballot(alive && type == NX_MAT_PLASTIC) != 0ull) {
             if (alive && type == NX_MAT_PLASTIC)
-                shade_path<NX_MAT_PLASTIC, POWER>(S, bounce, frame, (uint32_t)index, pixelIdx, hu, hv, tri, inst, dir, tp, prevOrigin, emit, wantShadowRay, sh, wantTrace, updatePath, nextOrigin, nextDir, nextThroughput, nextPdf);
+                shade_path<NX_MAT_PLASTIC, POWER, false, ANALYTIC>(S, bounce, frame, (uint32_t)index, pixelIdx, hu, hv, tri, inst, dir, tp, prevOrigin, emit, wantShadowRay, sh, wantTrace, updatePath, nextOrigin, nextDir, nextThroughput, nextPdf);
         }
         if (__ballot(alive && type == NX_MAT_DIELECTRIC) != 0ull) {
             if (alive && type == NX_MAT_DIELECTRIC)
-                shade_path<NX_MAT_DIELECTRIC, POWER>(S, bounce, frame, (uint32_t)index, pixelIdx, hu, hv, tri, inst, dir, tp, prevOrigin, emit, wantShadowRay, sh, wantTrace, updatePath, nextOrigin, nextDir, nextThroughput, nextPdf);
+                shade_path<NX_MAT_DIELECTRIC, POWER, false, ANALYTIC>(S, bounce, frame, (uint32_t)index, pixelIdx, hu, hv, tri, inst, dir, tp, prevOrigin, emit, wantShadowRay, sh, wantTrace, updatePath, nextOrigin, nextDir, nextThroughput, nextPdf);
         }
         if (__ballot(alive && type == NX_MAT_CONDUCTOR) != 0ull) {
             if (alive && type == NX_MAT_CONDUCTOR) {
                 if (S->conductorMode == NX_CONDUCTOR_EXTENDED)
-                    shade_path<NX_MAT_CONDUCTOR, POWER>(S, bounce, frame, (uint32_t)index, pixelIdx, hu, hv, tri, inst, dir, tp, prevOrigin, emit, wantShadowRay, sh, wantTrace, updatePath, nextOrigin, nextDir, nextThroughput, nextPdf);
+                    shade_path<NX_MAT_CONDUCTOR, POWER, false, ANALYTIC>(S, bounce, frame, (uint32_t)index, pixelIdx, hu, hv, tri, inst, dir, tp, prevOrigin, emit, wantShadowRay, sh, wantTrace, updatePath, nextOrigin, nextDir, nextThroughput, nextPdf);
                 else alive = false;  // (the reference's graph has no conductor kernel: such a path ends unshaded)
             }
         }
@@ -1538,21 +1572,48 @@ __global__ void __launch_bounds__(kWideBlock) env_hook_kernel(const DeviceState*
     }
 }
 
+// The analytic lights' draw on arrays (nxhip_analytic_light_sample_batch): the product's own alight_sample for light `index`, from the
+// origins as given (the caller's business to offset them) with r = count x 2 random numbers.
+__global__ void __launch_bounds__(kWideBlock) alight_hook_kernel(const DeviceState* __restrict__ S, const uint32_t index, const float* __restrict__ origin,
+                                                                  const float* __restrict__ r, const uint32_t count, float* __restrict__ direction,
+                                                                  float* __restrict__ tmax, float* __restrict__ factor, uint32_t* __restrict__ ok)
+{
+    for (uint32_t k = blockIdx.x * blockDim.x + threadIdx.x; k < count; k += gridDim.x * blockDim.x) {
+        f3 d, f;
+        float t;
+        const bool good = alight_sample(&S->alights[index], mk3(origin[3 * k], origin[3 * k + 1], origin[3 * k + 2]), r[2 * k], r[2 * k + 1], d, t, f);
+        direction[3 * k] = d.x; direction[3 * k + 1] = d.y; direction[3 * k + 2] = d.z;
+        tmax[k] = t;
+        factor[3 * k] = f.x; factor[3 * k + 1] = f.y; factor[3 * k + 2] = f.z;
+        ok[k] = good ? 1u : 0u;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------------
 
 // `items` per thread: kLogicItems (2) unless the caller asks for 1 — what a scene with an environment map gets, whose misses run the
 // map lookups (binary64 arc functions) in this kernel: with a second item's state live beside them the 64-register budget spills
 // into that path (configs[3]: logic kernel +8 % with two items, -6 % on configs[1])
-const void* logic_kernel_ptr(int items)
+const void* logic_kernel_ptr(int items, bool analytic)
 {
+    // (analytic: only the one-item instance differs — the count enters the weighted miss, which needs an environment map)
+    if (analytic && (items == 1 || kLogicItems == 1)) return (const void*)logic_kernel<true, 1, true>;
     if (items == 1 || kLogicItems == 1) return (const void*)logic_kernel<true, 1>;
     return (const void*)logic_kernel<true, kLogicItems>;
 }
 
 // (the classic pipeline — logic kernel and per-type material kernels — runs under the ordered compaction only: see frame_levels)
 // (lightPower: the variants only the pass graphs of NXHIP_LIGHTS_POWER launch — nxhip_api.hip pass_flavor)
-const void* shade_kernel_ptr(int type, bool lightPower)
+const void* shade_kernel_ptr(int type, bool lightPower, bool analytic)
 {
+    if (analytic) {  // (the variants only the pass graphs of a context with analytic lights launch)
+        switch (type) {
+        case NX_MAT_DIFFUSE: return lightPower ? (const void*)shade_kernel<NX_MAT_DIFFUSE, true, true, true> : (const void*)shade_kernel<NX_MAT_DIFFUSE, true, false, true>;
+        case NX_MAT_DIELECTRIC: return lightPower ? (const void*)shade_kernel<NX_MAT_DIELECTRIC, true, true, true> : (const void*)shade_kernel<NX_MAT_DIELECTRIC, true, false, true>;
+        case NX_MAT_PLASTIC: return lightPower ? (const void*)shade_kernel<NX_MAT_PLASTIC, true, true, true> : (const void*)shade_kernel<NX_MAT_PLASTIC, true, false, true>;
+        default: return lightPower ? (const void*)shade_kernel<NX_MAT_CONDUCTOR, true, true, true> : (const void*)shade_kernel<NX_MAT_CONDUCTOR, true, false, true>;
+        }
+    }
     switch (type) {
     case NX_MAT_DIFFUSE: return lightPower ? (const void*)shade_kernel<NX_MAT_DIFFUSE, true, true> : (const void*)shade_kernel<NX_MAT_DIFFUSE, true, false>;
     case NX_MAT_DIELECTRIC: return lightPower ? (const void*)shade_kernel<NX_MAT_DIELECTRIC, true, true> : (const void*)shade_kernel<NX_MAT_DIELECTRIC, true, false>;
@@ -1560,13 +1621,21 @@ const void* shade_kernel_ptr(int type, bool lightPower)
     default: return lightPower ? (const void*)shade_kernel<NX_MAT_CONDUCTOR, true, true> : (const void*)shade_kernel<NX_MAT_CONDUCTOR, true, false>;
     }
 }
-const void* shade_scan_kernel_ptr(bool lightPower, bool noMaps)
+const void* shade_scan_kernel_ptr(bool lightPower, bool noMaps, bool analytic)
 {
+    if (analytic) {
+        if (noMaps) return lightPower ? (const void*)shade_scan_kernel<true, true, true> : (const void*)shade_scan_kernel<false, true, true>;
+        return lightPower ? (const void*)shade_scan_kernel<true, false, true> : (const void*)shade_scan_kernel<false, false, true>;
+    }
     if (noMaps) return lightPower ? (const void*)shade_scan_kernel<true, true> : (const void*)shade_scan_kernel<false, true>;
     return lightPower ? (const void*)shade_scan_kernel<true> : (const void*)shade_scan_kernel<false>;
 }
 const void* count_scan_kernel_ptr() { return (const void*)count_scan_kernel; }
-const void* tail_kernel_ptr(bool lightPower) { return lightPower ? (const void*)tail_kernel<true> : (const void*)tail_kernel<false>; }
+const void* tail_kernel_ptr(bool lightPower, bool analytic)
+{
+    if (analytic) return lightPower ? (const void*)tail_kernel<true, true> : (const void*)tail_kernel<false, true>;
+    return lightPower ? (const void*)tail_kernel<true> : (const void*)tail_kernel<false>;
+}
 const void* begin_frame_kernel_ptr() { return (const void*)begin_frame_kernel; }
 const void* hook_sizes_kernel_ptr() { return (const void*)hook_sizes_kernel; }
 const void* generate_kernel_ptr() { return (const void*)generate_kernel; }
@@ -1575,6 +1644,7 @@ const void* compose_kernel_ptr() { return (const void*)compose_kernel; }
 const void* bsdf_hook_kernel_ptr() { return (const void*)bsdf_hook_kernel; }
 const void* tex2d_hook_kernel_ptr() { return (const void*)tex2d_hook_kernel; }
 const void* env_hook_kernel_ptr() { return (const void*)env_hook_kernel; }
+const void* alight_hook_kernel_ptr() { return (const void*)alight_hook_kernel; }
 const void* tex2d_float_hook_kernel_ptr() { return (const void*)tex2d_float_hook_kernel; }
 const void* fmath_hook_kernel_ptr() { return (const void*)fmath_hook_kernel; }
 

@@ -489,6 +489,10 @@ int nxhip_create(int device, uint32_t width, uint32_t height, void* stream, nxhi
         // (the POWER instance of the tail kernel fills the chip by its OWN occupancy: the default mode's grid does not depend on it)
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, tail_kernel_ptr(true), kTraceBlockThreads, 0) != hipSuccess || perCU < 1) perCU = 2;
         c->tailBlocksPower = std::max(1, perCU) * c->numCUs;
+        for (int power = 0; power < 2; power++) {  // (... and so do the instances of a context with analytic lights)
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, tail_kernel_ptr(power != 0, true), kTraceBlockThreads, 0) != hipSuccess || perCU < 1) perCU = 2;
+            c->tailBlocksAnalytic[power] = std::max(1, perCU) * c->numCUs;
+        }
         // Launch-geometry knobs of the measurement sweeps.  They are read only when NX_TUNING_KNOBS=1 says
         // that a sweep is running: a stray variable in a user's environment does not reconfigure the product.
         if (const char* on = std::getenv("NX_TUNING_KNOBS"); on && std::atoi(on) == 1) {

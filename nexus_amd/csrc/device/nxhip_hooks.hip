@@ -315,6 +315,41 @@ try {
     return env_hook(c, 0, direction, 3, count, rgb, pdf, texel);
 } NX_CATCH("nxhip_env_eval_batch")
 
+// ---- the analytic lights' hook (alight_hook_kernel) -------------------------------------------------
+
+int nxhip_analytic_light_sample_batch(nxhip_ctx* c, uint32_t lightIndex, const float* origins3, const float* r2, uint32_t count, float* direction3, float* tmax,
+                                      float* factor3, uint32_t* ok)
+try {
+    NX_DEBUG_HOOK("nxhip_analytic_light_sample_batch");  // (first: a release library refuses whatever it is handed)
+    NX_CHECK_CTX(c);
+    if (lightIndex >= c->h.alightCount) return fail_invalid("nxhip_analytic_light_sample_batch: no such analytic light (nxhip_set_analytic_lights)");
+    if ((!origins3 || !r2 || !direction3 || !tmax || !factor3 || !ok) && count) return fail_invalid("nxhip_analytic_light_sample_batch: null buffer");
+    for (size_t k = 0; k < (size_t)count * 3; k++)
+        if (!(origins3[k] >= -3.0e38f && origins3[k] <= 3.0e38f)) return fail_invalid("nxhip_analytic_light_sample_batch: origins must be finite");
+    for (size_t k = 0; k < (size_t)count * 2; k++)
+        if (!(r2[k] >= 0.0f && r2[k] < 1.0f)) return fail_invalid("nxhip_analytic_light_sample_batch: r must be in [0, 1)");
+    if (count == 0) return NXHIP_OK;
+    NX_HIP(hipSetDevice(c->device));
+    NX_TRY(upload_state(c));
+    DevBuf dO, dR, dDir, dT, dF, dOk;
+    NX_ALLOC(dO, (size_t)count * 12);
+    NX_ALLOC(dR, (size_t)count * 8);
+    NX_ALLOC(dDir, (size_t)count * 12);
+    NX_ALLOC(dT, (size_t)count * 4);
+    NX_ALLOC(dF, (size_t)count * 12);
+    NX_ALLOC(dOk, (size_t)count * 4);
+    NX_HIP(hipMemcpy(dO.p, origins3, (size_t)count * 12, hipMemcpyHostToDevice));
+    NX_HIP(hipMemcpy(dR.p, r2, (size_t)count * 8, hipMemcpyHostToDevice));
+    NX_HIP(launch_untimed(kernels::alight_hook(), c->wideBlocks, kWideBlockThreads, c->stream, c->dState.as<DeviceState>(), lightIndex, dO.as<float>(), dR.as<float>(), count,
+                          dDir.as<float>(), dT.as<float>(), dF.as<float>(), dOk.as<uint32_t>()));
+    NX_SYNC_ALL(c);
+    NX_HIP(hipMemcpy(direction3, dDir.p, (size_t)count * 12, hipMemcpyDeviceToHost));
+    NX_HIP(hipMemcpy(tmax, dT.p, (size_t)count * 4, hipMemcpyDeviceToHost));
+    NX_HIP(hipMemcpy(factor3, dF.p, (size_t)count * 12, hipMemcpyDeviceToHost));
+    NX_HIP(hipMemcpy(ok, dOk.p, (size_t)count * 4, hipMemcpyDeviceToHost));
+    return NXHIP_OK;
+} NX_CATCH("nxhip_analytic_light_sample_batch")
+
 int nxhip_fmath_batch(nxhip_ctx* c, int op, const double* a, const double* b, uint32_t count, double* out)
 {
     NX_CHECK_CTX(c);

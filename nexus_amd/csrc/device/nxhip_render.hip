@@ -164,6 +164,10 @@ constexpr int kFlavorScan = 1, kFlavorMissKernel = 2, kFlavorEnvMap = 4, kFlavor
 // Both are read at every pass (here), so a change between two passes picks the other graph.
 constexpr int kFlavorIdentity = 256, kFlavorNoMaps = 512;
 constexpr int kFlavorSpecialised = kFlavorIdentity | kFlavorNoMaps;
+// kFlavorAnalytic: the context has analytic lights (nxhip_set_analytic_lights, count > 0) — the material kernels, the tail kernel and the
+// one-item logic kernel are their ANALYTIC instances (nx_wavefront.hip), whose light sample picks among them too.  Not a specialisation
+// a test may switch off: the default instances do not know such lights.  Without any the bit is clear and the graphs are the default ones.
+constexpr int kFlavorAnalytic = 1024;
 int pass_flavor(const nxhip_ctx* c)
 {
     int f = 0;
@@ -195,6 +199,7 @@ int pass_flavor(const nxhip_ctx* c)
     if (!c->statsEnabled && c->passesInFlight <= 1u) f |= kFlavorThin;  // (the caller's setting, not effective_slots(): a timing replay of a run with passes in flight keeps that run's kernels)
     if ((c->h.sceneFlags & kSceneAllIdentity) && !c->statsEnabled) f |= kFlavorIdentity;  // (the counting variants have no such instance)
     if (scan_pipeline(c) && !c->materialsNameMaps && !(f & kFlavorEnvMap)) f |= kFlavorNoMaps;
+    if (c->h.alightCount) f |= kFlavorAnalytic;
     return f & ~(c->flavorForceGeneral & kFlavorSpecialised);  // (test hook: nxhip_debug_pass_flavor)
 }
 
@@ -213,6 +218,7 @@ std::vector<std::vector<Launch>> frame_levels(nxhip_ctx* c, PassSlot* q)
     const bool entry = (pass_flavor(c) & kFlavorEntry) != 0;
     const bool lightPower = (pass_flavor(c) & kFlavorLightPower) != 0;
     const bool identity = (pass_flavor(c) & kFlavorIdentity) != 0, noMaps = (pass_flavor(c) & kFlavorNoMaps) != 0;
+    const bool analytic = (pass_flavor(c) & kFlavorAnalytic) != 0;
     const int traceBlocks = trace_blocks(c, c->traceBlocks), shadowBlocks = trace_blocks(c, c->shadowBlocks);
     // (the dry waves of a pass's trace launches may hand their last long rays to the thin kernel: nx_trace.hip)
     const int thinFlag = (pass_flavor(c) & kFlavorThin) ? kTraceThinFlag : 0;
@@ -260,14 +266,14 @@ std::vector<std::vector<Launch>> frame_levels(nxhip_ctx* c, PassSlot* q)
         const int tailFrom = tail_bounce(c);
         for (int bounce = 1; bounce <= pathLength; bounce++) {
             if (bounce == tailFrom) {  // the rest of the pass in one launch
-                levels.push_back({make_launch(kernels::tail(lightPower), lightPower ? c->tailBlocksPower : c->tailBlocks, kTraceBlockThreads, NXHIP_K_SHADE, S, bounce | kTraceScanFlag)});
+                levels.push_back({make_launch(kernels::tail(lightPower, analytic), analytic ? c->tailBlocksAnalytic[lightPower ? 1 : 0] : (lightPower ? c->tailBlocksPower : c->tailBlocks), kTraceBlockThreads, NXHIP_K_SHADE, S, bounce | kTraceScanFlag)});
                 break;
             }
             int mask = (int)(c->materialTypeMask & 0xfu);
             if (c->h.conductorMode != NX_CONDUCTOR_EXTENDED) mask &= ~(1 << NX_MAT_CONDUCTOR);
             if (mask == 0) mask = 1 << NX_MAT_DIFFUSE;  // (a level cannot be empty)
             if (misses) mask |= 1 << kScanMiss;
-            levels.push_back({make_launch(kernels::shade_scan(lightPower, noMaps), og, kShadeBlockThreads, NXHIP_K_SHADE, S, bounce | dropFlag, mask)});
+            levels.push_back({make_launch(kernels::shade_scan(lightPower, noMaps, analytic), og, kShadeBlockThreads, NXHIP_K_SHADE, S, bounce | dropFlag, mask)});
             if (bounce == 1) aov_beside(levels.back());
             if (in_use(NX_MAT_CONDUCTOR) && c->h.conductorMode != NX_CONDUCTOR_EXTENDED) {  // (counted, not shaded: count_scan_kernel)
                 levels.push_back({make_launch(kernels::count_scan(), lg, kWideBlockThreads, NXHIP_K_LOGIC, S, bounce, NX_MAT_CONDUCTOR)});
@@ -286,16 +292,16 @@ std::vector<std::vector<Launch>> frame_levels(nxhip_ctx* c, PassSlot* q)
         // Not only a tuning choice: logic_kernel<true, 2> is compiled WITHOUT the float lookup (nx_wavefront.hip logic_kernel), so under a
         // float map it would read float4 texels as RGBA8.  The two-item instance is for scenes with no environment map of either kind;
         // the same test as pass_flavor's kFlavorEnvMap (hdrMap.texels is set for both kinds: nxhip_scene.hip).
-        levels.push_back({make_launch(kernels::logic(c->hdrMap.texels.p ? 1 : 2), lg, lb, NXHIP_K_LOGIC, S, bounce)});
+        levels.push_back({make_launch(kernels::logic(c->hdrMap.texels.p ? 1 : 2, analytic), lg, lb, NXHIP_K_LOGIC, S, bounce)});
         if (bounce == 1) aov_beside(levels.back());
         // graph insertion order of the reference: Diffuse, Plastic, Dielectric, Conductor (PathTracer.cpp:116-120)
         // (only the types some material of the scene has: a queue no material feeds stays empty)
         std::vector<Launch> shade;
-        if (in_use(NX_MAT_DIFFUSE)) shade.push_back(make_launch(kernels::shade(NX_MAT_DIFFUSE, lightPower), og, ob, NXHIP_K_SHADE, S, bounce));
-        if (in_use(NX_MAT_PLASTIC)) shade.push_back(make_launch(kernels::shade(NX_MAT_PLASTIC, lightPower), og, ob, NXHIP_K_SHADE, S, bounce));
-        if (in_use(NX_MAT_DIELECTRIC)) shade.push_back(make_launch(kernels::shade(NX_MAT_DIELECTRIC, lightPower), og, ob, NXHIP_K_SHADE, S, bounce));
-        if (in_use(NX_MAT_CONDUCTOR) && c->h.conductorMode == NX_CONDUCTOR_EXTENDED) shade.push_back(make_launch(kernels::shade(NX_MAT_CONDUCTOR, lightPower), og, ob, NXHIP_K_SHADE, S, bounce));
-        if (shade.empty()) shade.push_back(make_launch(kernels::shade(NX_MAT_DIFFUSE, lightPower), og, ob, NXHIP_K_SHADE, S, bounce));  // (a level cannot be empty)
+        if (in_use(NX_MAT_DIFFUSE)) shade.push_back(make_launch(kernels::shade(NX_MAT_DIFFUSE, lightPower, analytic), og, ob, NXHIP_K_SHADE, S, bounce));
+        if (in_use(NX_MAT_PLASTIC)) shade.push_back(make_launch(kernels::shade(NX_MAT_PLASTIC, lightPower, analytic), og, ob, NXHIP_K_SHADE, S, bounce));
+        if (in_use(NX_MAT_DIELECTRIC)) shade.push_back(make_launch(kernels::shade(NX_MAT_DIELECTRIC, lightPower, analytic), og, ob, NXHIP_K_SHADE, S, bounce));
+        if (in_use(NX_MAT_CONDUCTOR) && c->h.conductorMode == NX_CONDUCTOR_EXTENDED) shade.push_back(make_launch(kernels::shade(NX_MAT_CONDUCTOR, lightPower, analytic), og, ob, NXHIP_K_SHADE, S, bounce));
+        if (shade.empty()) shade.push_back(make_launch(kernels::shade(NX_MAT_DIFFUSE, lightPower, analytic), og, ob, NXHIP_K_SHADE, S, bounce));  // (a level cannot be empty)
         // serial slot order needs the kernels one after the other
         for (auto& l : shade) levels.push_back({l});
         levels.push_back({make_launch(kernels::trace(false, stats, identity), traceBlocks, kTraceBlockThreads, NXHIP_K_TRACE, S, bounce | thinFlag),

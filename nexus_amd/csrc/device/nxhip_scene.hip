@@ -813,6 +813,9 @@ try {
 int nxhip_set_lights(nxhip_ctx* c, const nx_light* lights, uint32_t count)
 try {
     NX_CHECK_CTX(c);
+    // (only a context with analytic lights can meet this: the light sample's pick among lightCount + A + 1 has 23 bits — nxhip_set_analytic_lights)
+    if (c->h.alightCount && (uint64_t)count + (uint64_t)c->h.alightCount + 1u > (uint64_t)kLightGuideMax)
+        return fail_invalid("nxhip_set_lights: lightCount + analytic lights + 1 may not exceed 2^23");
     NX_HIP(hipSetDevice(c->device));
     NX_SYNC_ALL(c);
     NX_ALLOC(c->lights, std::max<size_t>(1, count) * sizeof(nx_light));
@@ -824,6 +827,64 @@ try {
     c->lightTableDirty = true;
     return NXHIP_OK;
 } NX_CATCH("nxhip_set_lights")
+
+// Analytic lights (include/nexus_hip.h): checked on the host before anything is allocated — a refused call leaves the previous table
+// where it is —, the device records (nx_alights.h ALight) derived in binary64 and rounded once.
+int nxhip_set_analytic_lights(nxhip_ctx* c, const nx_analytic_light* lights, uint32_t count)
+try {
+    NX_CHECK_CTX(c);
+    if (count && !lights) return fail_invalid("nxhip_set_analytic_lights: null array");
+    if ((uint64_t)c->h.lightCount + (uint64_t)count + 1u > (uint64_t)kLightGuideMax) return fail_invalid("nxhip_set_analytic_lights: lightCount + count + 1 may not exceed 2^23");
+    const double halfPi = 1.57079632679489661923;
+    std::vector<ALight> table(count);
+    for (uint32_t i = 0; i < count; i++) {
+        const nx_analytic_light& l = lights[i];
+        const std::string who = "nxhip_set_analytic_lights: light " + std::to_string(i);
+        const float fields[] = {l.position[0], l.position[1], l.position[2], l.radius, l.direction[0], l.direction[1], l.direction[2], l.angularRadius,
+                                l.colour[0], l.colour[1], l.colour[2], l.intensity, l.innerConeAngle, l.outerConeAngle};
+        for (const float f : fields)
+            if (!std::isfinite(f)) return fail_invalid(who + ": a field is not finite");
+        if (l.type != NX_ALIGHT_POINT && l.type != NX_ALIGHT_SPOT && l.type != NX_ALIGHT_DIRECTIONAL) return fail_invalid(who + ": unknown type");
+        if (l.radius < 0.0f || l.intensity < 0.0f || l.colour[0] < 0.0f || l.colour[1] < 0.0f || l.colour[2] < 0.0f || l.angularRadius < 0.0f)
+            return fail_invalid(who + ": radius, intensity, colour and angularRadius may not be negative");
+        if (!((double)l.angularRadius < halfPi)) return fail_invalid(who + ": angularRadius must be below pi/2");
+        const double dx = l.direction[0], dy = l.direction[1], dz = l.direction[2];
+        const double len = std::sqrt(dx * dx + dy * dy + dz * dz);
+        const bool spot = l.type == NX_ALIGHT_SPOT, directional = l.type == NX_ALIGHT_DIRECTIONAL;
+        if (!(len > 0.0)) return fail_invalid(who + ": the direction has length 0");  // (every kind: a POINT light does not read it, the record stays one rule)
+        if (spot && !(l.innerConeAngle >= 0.0f && l.innerConeAngle < l.outerConeAngle && (double)l.outerConeAngle <= halfPi + 1e-7))
+            return fail_invalid(who + ": cone angles must satisfy 0 <= inner < outer <= pi/2");
+        ALight& d = table[i];
+        const float r = directional ? 0.0f : l.radius;
+        d.v0 = directional ? make_float4(0.0f, 0.0f, 0.0f, 0.0f) : make_float4(l.position[0], l.position[1], l.position[2], r);
+        const double sinHalf = std::sin(0.5 * (double)l.angularRadius);
+        d.v1 = make_float4((float)(dx / len), (float)(dy / len), (float)(dz / len), 0.0f);
+        d.v1.w = directional ? (float)(2.0 * sinHalf * sinHalf) : 0.0f;
+        d.v2 = make_float4((float)((double)l.colour[0] * (double)l.intensity), (float)((double)l.colour[1] * (double)l.intensity),
+                           (float)((double)l.colour[2] * (double)l.intensity), directional ? 1.0f : 0.0f);
+        double scale = 0.0, offset = 1.0;  // (falloff 1 for everything but a SPOT)
+        if (spot) {
+            const double ci = std::cos((double)l.innerConeAngle), co = std::cos((double)l.outerConeAngle);
+            scale = 1.0 / std::max(1e-3, ci - co);
+            offset = -co * scale;
+        }
+        d.v3 = make_float4((float)scale, (float)offset, (float)((double)r * (double)r), 0.0f);
+    }
+    NX_HIP(hipSetDevice(c->device));
+    NX_SYNC_ALL(c);
+    if (count) {
+        DevBuf fresh;  // (the old table goes only once the new one is there)
+        NX_ALLOC(fresh, (size_t)count * sizeof(ALight));
+        NX_HIP(hipMemcpy(fresh.p, table.data(), (size_t)count * sizeof(ALight), hipMemcpyHostToDevice));
+        c->alights = std::move(fresh);
+    } else {
+        c->alights = DevBuf();
+    }
+    c->h.alights = count ? c->alights.as<ALight>() : nullptr;
+    c->h.alightCount = count;
+    c->stateDirty = true;  // (the pass graphs follow by their flavor: kFlavorAnalytic)
+    return NXHIP_OK;
+} NX_CATCH("nxhip_set_analytic_lights")
 
 static int refresh_texture_tables(nxhip_ctx* c)
 {

@@ -475,9 +475,37 @@ LoadedScene parse_glb(const std::string& file)
         }
     }
 
+    // KHR_lights_punctual: the light list of the root extension; a node names one by index (walk below).  Radiometric as written —
+    // colour x intensity goes to the record unconverted (no 683 lm/W) —, `range` is ignored, radius and angular radius are 0.
+    std::vector<AnalyticLight> punctual;
+    if (const Json* ext = doc.find("extensions"))
+        if (const Json* khr = ext->find("KHR_lights_punctual"))
+            if (const Json* list = khr->find("lights"))
+                for (size_t i = 0; i < list->size(); i++) {
+                    const Json& l = list->at(i);
+                    AnalyticLight a;
+                    const std::string& type = l.at("type").str;
+                    if (type == "point") a.type = NX_ALIGHT_POINT;
+                    else if (type == "spot") a.type = NX_ALIGHT_SPOT;
+                    else if (type == "directional") a.type = NX_ALIGHT_DIRECTIONAL;
+                    else fail("glb: KHR_lights_punctual light of unknown type " + type);
+                    if (const Json* c = l.find("color"))
+                        for (size_t k = 0; k < 3 && k < c->size(); k++) a.colour[k] = static_cast<float>(c->at(k).num);
+                    a.intensity = static_cast<float>(l.number("intensity", 1.0));
+                    a.innerConeAngle = a.outerConeAngle = 0.0f;
+                    if (a.type == NX_ALIGHT_SPOT) {
+                        static const Json none;
+                        const Json* spot = l.find("spot");
+                        a.innerConeAngle = static_cast<float>((spot ? *spot : none).number("innerConeAngle", 0.0));
+                        a.outerConeAngle = static_cast<float>((spot ? *spot : none).number("outerConeAngle", 0.78539816339744830962));
+                    }
+                    punctual.push_back(a);
+                }
+
     const Json& nodes = doc.at("nodes");
     struct Walker {
         const Json& nodes;
+        const std::vector<AnalyticLight>& punctual;
         const std::map<std::pair<size_t, size_t>, std::pair<int, int>>& primMesh;
         LoadedScene& out;
         int depth = 0;
@@ -498,11 +526,23 @@ LoadedScene parse_glb(const std::string& file)
                         out.instances.push_back(inst);
                     }
             }
+            if (const Json* ext = node.find("extensions"))
+                if (const Json* khr = ext->find("KHR_lights_punctual")) {
+                    const size_t li = static_cast<size_t>(khr->at("light").num);
+                    if (li >= punctual.size()) fail("glb: a node refers to a KHR_lights_punctual light that does not exist");
+                    AnalyticLight a = punctual[li];
+                    // position: the node's world translation; direction: its -Z axis (the length is the device layer's to normalise)
+                    for (int i = 0; i < 3; i++) {
+                        a.position[i] = static_cast<float>(m.m[i][3]);
+                        a.direction[i] = static_cast<float>(-m.m[i][2]);
+                    }
+                    out.analyticLights.push_back(a);
+                }
             if (const Json* ch = node.find("children"))
                 for (size_t k = 0; k < ch->size(); k++) walk(static_cast<size_t>(ch->at(k).num), m);
             depth--;
         }
-    } walker{nodes, primMesh, out};
+    } walker{nodes, punctual, primMesh, out};
     const Json& scenes = doc.at("scenes");
     const Json& scene = scenes.at(static_cast<size_t>(doc.number("scene", 0)));
     const Json& roots = scene.at("nodes");
@@ -645,6 +685,7 @@ void OBJLoader::LoadOBJ(const std::string& path, const std::string& filename, Sc
         mi.AssignMaterial(materialBase + inst.material);
         mi.SetTransform(inst.position, inst.rotation, inst.scale);
     }
+    for (const AnalyticLight& l : ls.analyticLights) scene->AddAnalyticLight(l);
 }
 
 }  // namespace nexus

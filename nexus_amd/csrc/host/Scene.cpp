@@ -22,6 +22,8 @@ void Scene::Reset()
     m_InvalidMeshInstances.clear();
     m_MeshInstances.clear();
     m_Lights.clear();
+    if (!m_AnalyticLights.empty()) analyticLightsDirty = true;  // (the device must hear that they are gone)
+    m_AnalyticLights.clear();
     m_AssetManager.Reset();
     m_Camera->Invalidate();
     m_TlasBuiltFor = 0;
@@ -150,6 +152,20 @@ size_t Scene::AddLight(const Light& light)
     m_Lights.push_back(light);
     lightsDirty = true;
     return m_Lights.size() - 1;
+}
+
+size_t Scene::AddAnalyticLight(const AnalyticLight& light)
+{
+    m_AnalyticLights.push_back(light);
+    analyticLightsDirty = true;
+    return m_AnalyticLights.size() - 1;
+}
+
+void Scene::RemoveAnalyticLight(size_t index)
+{
+    if (index >= m_AnalyticLights.size()) throw std::out_of_range("Scene::RemoveAnalyticLight: no such light");
+    m_AnalyticLights.erase(m_AnalyticLights.begin() + static_cast<std::ptrdiff_t>(index));
+    analyticLightsDirty = true;
 }
 
 void Scene::RemoveLight(size_t index)

@@ -75,6 +75,7 @@ class LoadedScene:
         self.textures = []            # list of (kind "diffuse" / "emissive", HxWx4 uint8 RGBA, row 0 = top)
         self.material_diffuse_texture = []   # per material: index into textures, -1 = none
         self.material_emissive_texture = []
+        self.analytic_lights = np.zeros(0, dtype=pod.ALIGHT_DT)  # glTF KHR_lights_punctual: one per node that carries a light, world space
         self.warnings = []
 
 
@@ -409,9 +410,22 @@ def load_glb(path):
             out.meshes.append(t)
             out.mesh_names.append(mesh.get("name", "mesh%d" % mi))
 
+    # KHR_lights_punctual: the root extension's light list; radiometric as written (no 683 lm/W), `range` ignored, radius and angular radius 0
+    punctual, lights = doc.get("extensions", {}).get("KHR_lights_punctual", {}).get("lights", []), []
+    kinds = {"point": pod.ALIGHT_POINT, "spot": pod.ALIGHT_SPOT, "directional": pod.ALIGHT_DIRECTIONAL}
+
     def walk(ni, parent):
         node = doc["nodes"][ni]
         m = parent @ _node_local_matrix(node)
+        if "KHR_lights_punctual" in node.get("extensions", {}):
+            l = punctual[node["extensions"]["KHR_lights_punctual"]["light"]]
+            if l["type"] not in kinds:
+                raise ValueError("glb: KHR_lights_punctual light of unknown type %s" % l["type"])
+            spot = l.get("spot", {})
+            # position: the node's world translation; direction: its -Z axis
+            lights.append(pod.make_analytic_light(kinds[l["type"]], position=m[:3, 3], direction=-m[:3, 2], colour=l.get("color", (1.0, 1.0, 1.0)),
+                                                  intensity=l.get("intensity", 1.0), inner_cone=spot.get("innerConeAngle", 0.0),
+                                                  outer_cone=spot.get("outerConeAngle", np.pi / 4)))
         if "mesh" in node:
             pos, rot, scale = decompose_trs(m)
             for (mi, pi), (mesh_id, mat_id) in prim_mesh.items():
@@ -424,6 +438,7 @@ def load_glb(path):
     scene = doc["scenes"][doc.get("scene", 0)]
     for ni in scene["nodes"]:
         walk(ni, np.eye(4))
+    out.analytic_lights = np.array(lights, dtype=pod.ALIGHT_DT) if lights else np.zeros(0, dtype=pod.ALIGHT_DT)
     return out
 
 

@@ -68,6 +68,11 @@ LIGHT_DT = np.dtype(
     {"names": ["meshId", "aux", "type"], "formats": ["<u4", "<u4", "i1"], "offsets": [0, 4, 8], "itemsize": 12}
 )
 
+# nx_analytic_light (extension, nxhip_set_analytic_lights): 64 bytes, world space
+ALIGHT_DT = np.dtype([("position", "<f4", 3), ("radius", "<f4"), ("direction", "<f4", 3), ("angularRadius", "<f4"), ("colour", "<f4", 3), ("intensity", "<f4"),
+                      ("innerConeAngle", "<f4"), ("outerConeAngle", "<f4"), ("type", "<u4"), ("pad_", "<u4")])
+assert ALIGHT_DT.itemsize == 64
+
 CAM_DT = np.dtype(
     {
         "names": ["position", "right", "up", "lensRadius", "lowerLeftCorner", "viewportX", "viewportY", "resolution"],
@@ -103,6 +108,7 @@ assert ADAPTIVE_DT.itemsize == 16
 
 MAT_DIFFUSE, MAT_DIELECTRIC, MAT_PLASTIC, MAT_CONDUCTOR = 0, 1, 2, 3
 LIGHT_POINT, LIGHT_AREA, LIGHT_MESH = 0, 1, 2
+ALIGHT_POINT, ALIGHT_SPOT, ALIGHT_DIRECTIONAL = 0, 1, 2  # nx_analytic_light.type
 RNG_REFERENCE_SLOT, RNG_PIXEL_KEYED = 0, 1
 COMPACT_FAST, COMPACT_ORDERED = 0, 1
 CONDUCTOR_REFERENCE, CONDUCTOR_EXTENDED = 0, 1
@@ -152,3 +158,20 @@ def make_material(type=MAT_DIFFUSE, albedo=(0.8, 0.8, 0.8), roughness=0.0, ior=1
     m["emissiveMapId"] = emissive_map
     m["type"] = type
     return m
+
+
+def make_analytic_light(type=ALIGHT_POINT, position=(0, 0, 0), direction=(0, 0, -1), colour=(1, 1, 1), intensity=1.0, radius=0.0, angular_radius=0.0,
+                        inner_cone=0.0, outer_cone=np.pi / 4):
+    """one nx_analytic_light: a point or sphere (radius), a spot (direction = its axis, cone angles in radians) or a sun (direction = the way
+    the light travels, angular_radius = half-angle of its disc)"""
+    l = np.zeros((), dtype=ALIGHT_DT)
+    l["type"] = type
+    l["position"] = position
+    l["direction"] = direction
+    l["colour"] = colour
+    l["intensity"] = intensity
+    l["radius"] = radius
+    l["angularRadius"] = angular_radius
+    if type == ALIGHT_SPOT:
+        l["innerConeAngle"], l["outerConeAngle"] = inner_cone, outer_cone
+    return l
