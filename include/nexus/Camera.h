@@ -25,7 +25,9 @@ public:
     Camera(float3 position, float3 forward, float horizontalFOV, uint32_t width, uint32_t height, float focusDistance, float defocusAngle);
 
     // ---- pose
-    void LookAt(float3 position, float3 forward);  // right := forward x +Y
+    // right := forward x +Y, NOT normalised (as the reference's constructor): a forward pitched by theta gives a viewport and a lens disk
+    // cos(theta) of what the lens asks for.  forward must be a unit vector: any other length is the caller's error.
+    void LookAt(float3 position, float3 forward);
     float3& GetPosition() { return m_Pose.position; }
     float3& GetForwardDirection() { return m_Pose.forward; }
     float3& GetRightDirection() { return m_Pose.right; }

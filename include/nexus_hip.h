@@ -318,6 +318,17 @@ int nxhip_read_entry_states(nxhip_ctx *ctx, void *out, uint32_t capacityRuns, ui
  * it is walked again, in front of the slot's next pass, only after a call that changed something the walk reads (camera, pixel set,
  * TLAS, instances, BLASes, materials' types, entry points switched on) — one launch per slot that renders afterwards. */
 int nxhip_debug_entry_walks(nxhip_ctx *ctx, uint64_t *count);
+/* Test hook: the primary rays of the pass rendered last, as GenerateKernel left them in the trace queue (PathTracer.cu:85-122).  Nothing
+ * is launched: the call waits for the pass and copies the queue regions out into dense path order, path k = slice x localCount + local
+ * pixel (slice s of a pass of F frames is frame frameLast - F + 1 + s; local pixel p is global pixel pixelMap[p], or p).  The ray of
+ * global pixel g = i + j x width goes through the point lowerLeftCorner + viewportX (i + r1) / width + viewportY (j + r2) / height of the
+ * focal plane: image row 0 is the BOTTOM row of the viewport (Renderer.h: screenshots are written last row first).
+ * origin3[3k..], direction3[3k..] = x, y, z of the ray (the w words are not part of them: origin.w carries the entry bits, direction.w
+ * the path number); pathIndex[k] = the bit pattern of direction.w, which must be k.  *count = the pass's paths, also when the call
+ * refuses for capacity.  NXHIP_ERR_INVALID with a message: no pass has been rendered; settings.pathLength != 1 (the later bounces of a
+ * pass write their rays over the primary ones); more than one pass in flight; capacity < *count or a NULL array; the queues of that pass
+ * released or re-allocated since. */
+int nxhip_debug_read_primary_rays(nxhip_ctx *ctx, float *origin3, float *direction3, uint32_t *pathIndex, uint32_t capacity, uint32_t *count);
 /* Test hook for the kernel instances a pass graph picks by scene (pass_flavor, nxhip_render.hip).  *flavor (may be NULL): the flavor
  * bits of the graph the last pass replayed; 256 = trace instances without the transform path, 512 = map-free material launch.
  * forceGeneral: those of the two bits whose specialised instances later passes must not use (0xffffffff: unchanged). */

@@ -35,6 +35,7 @@ HIP_SYMBOLS = [
     "nxhip_read_env_tables", "nxhip_env_sample_batch", "nxhip_env_eval_batch",
     "nxhip_upload_env_float", "nxhip_read_env_float", "nxhip_read_env_guides",
     "nxhip_set_analytic_lights", "nxhip_analytic_light_sample_batch",
+    "nxhip_debug_read_primary_rays",
 ]
 HOST_SYMBOLS = [
     "nxh_bvh8_build", "nxh_tlas_build", "nxh_tlas_refit", "nxh_bvh8_refit", "nxh_bvh8_node_count", "nxh_bvh8_prim_count", "nxh_bvh8_nodes",
@@ -935,6 +936,23 @@ class Context:
         self.L.nxhip_debug_entry_walks.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
         check(self.L.nxhip_debug_entry_walks(self.h, C.byref(n)), "nxhip_debug_entry_walks")
         return int(n.value)
+
+    def debug_read_primary_rays(self, capacity=None):
+        """the primary rays of the last pass as the generate kernel left them, in path order (path k = slice x local_count + local pixel):
+        (origin float32[n, 3], direction float32[n, 3], path_index uint32[n]) — a test hook: include/nexus_hip.h.  Needs pathLength 1 and one
+        pass in flight; `capacity`: the size of the arrays handed over (None: the pass's own path count)."""
+        self.L.nxhip_debug_read_primary_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
+        n = C.c_uint32(0)
+        if capacity is None:
+            rc = self.L.nxhip_debug_read_primary_rays(self.h, None, None, None, 0, C.byref(n))
+            if n.value == 0:
+                check(rc, "nxhip_debug_read_primary_rays")
+            capacity = n.value
+        origin = np.zeros((capacity, 3), np.float32)
+        direction = np.zeros((capacity, 3), np.float32)
+        index = np.zeros(capacity, np.uint32)
+        check(self.L.nxhip_debug_read_primary_rays(self.h, _ptr(origin), _ptr(direction), _ptr(index), capacity, C.byref(n)), "nxhip_debug_read_primary_rays")
+        return origin[:n.value], direction[:n.value], index[:n.value]
 
     def debug_pass_flavor(self, force_general=None):
         """flavor bits of the graph the last pass replayed (FLAVOR_IDENTITY: trace instances without the transform path, FLAVOR_NO_MAPS:

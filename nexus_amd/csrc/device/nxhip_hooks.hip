@@ -439,6 +439,46 @@ int nxhip_debug_entry_walks(nxhip_ctx* c, uint64_t* count)
     return NXHIP_OK;
 }
 
+// The primary rays of the last pass as generate_kernel left them in trace.rays[0]: nothing is launched, the queue regions are copied
+// out into dense path order (hook_layout's numbering IS generate_kernel's: region index / piece, slot index % piece).
+int nxhip_debug_read_primary_rays(nxhip_ctx* c, float* origin3, float* direction3, uint32_t* pathIndex, uint32_t capacity, uint32_t* count)
+try {
+    NX_DEBUG_HOOK("nxhip_debug_read_primary_rays");  // (first: a release library refuses whatever it is handed)
+    NX_CHECK_CTX(c);
+    if (!count) return fail_invalid("nxhip_debug_read_primary_rays: null count");
+    if (!c->lastRendered) return fail_invalid("nxhip_debug_read_primary_rays: no pass has been rendered");
+    if (c->h.settings.pathLength != 1)
+        return fail_invalid("nxhip_debug_read_primary_rays: needs settings.pathLength == 1 (the later bounces of a pass write their rays over the primary ones)");
+    if (c->passesInFlight > 1 || c->lastRendered != static_cast<PassSlot*>(c))
+        return fail_invalid("nxhip_debug_read_primary_rays: needs one pass in flight (nxhip_set_passes_in_flight(1))");
+    const PassSlot* q = c->lastRendered;
+    const uint64_t n64 = (uint64_t)q->passPixels * q->frames;
+    const uint32_t n = (uint32_t)n64;
+    *count = n;
+    if (n == 0) return NXHIP_OK;
+    if (capacity < n || !origin3 || !direction3 || !pathIndex) return fail_invalid("nxhip_debug_read_primary_rays: capacity too small (*count holds the pass's paths)");
+    NX_HIP(hipSetDevice(c->device));
+    NX_SYNC_ALL(c);
+    const HookLayout l = hook_layout(c, n);
+    // (the pass's queues may have been released or re-allocated since: nxhip_release_queues, nxhip_resize, a pixel map)
+    if (n64 > q->pathCapacity || l.shards == 0 || l.piece > l.cap || q->trRayO.bytes < (size_t)l.shards * l.cap * 16 || q->trRayD.bytes < (size_t)l.shards * l.cap * 16)
+        return fail_invalid("nxhip_debug_read_primary_rays: the queues of the last pass are gone (released or re-allocated since it was rendered)");
+    std::vector<float4> o((size_t)l.shards * l.piece), d((size_t)l.shards * l.piece);
+    NX_TRY(hook_copy(c, l, q->trRayO.p, o.data(), 16, false));
+    NX_TRY(hook_copy(c, l, q->trRayD.p, d.data(), 16, false));
+    NX_SYNC_ALL(c);
+    for (uint32_t k = 0; k < n; k++) {
+        origin3[3 * (size_t)k + 0] = o[k].x;
+        origin3[3 * (size_t)k + 1] = o[k].y;
+        origin3[3 * (size_t)k + 2] = o[k].z;
+        direction3[3 * (size_t)k + 0] = d[k].x;
+        direction3[3 * (size_t)k + 1] = d[k].y;
+        direction3[3 * (size_t)k + 2] = d[k].z;
+        std::memcpy(&pathIndex[k], &d[k].w, 4);
+    }
+    return NXHIP_OK;
+} NX_CATCH("nxhip_debug_read_primary_rays")
+
 }  // extern "C"
 
 uint64_t nxd::layout_stamp_hooks() { return layout_stamp(); }

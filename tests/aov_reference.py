@@ -1,7 +1,7 @@
 """References for the feature buffers (AOVs) and the edge-avoiding a-trous filter, shared by tests/test_aov.py (CPU) and the GPU tests.
 
-* primary_rays: generate_kernel's ray of a pinhole camera, restated in numpy float32 in the kernel's order of operations (jitter from
-  the oracle's orc_rng_init_pixel / orc_rand; an fmaf is a float64 product-sum rounded once to float32).
+* primary_rays: generate_kernel's ray of a pinhole or thin-lens camera, restated in numpy float32 in the kernel's order of operations
+  (jitter and lens point from the oracle's orc_rng_init_pixel / orc_rand; an fmaf is a float64 product-sum rounded once to float32).
 * primary_features: albedo + coverage and depth from the ORACLE's hit record of that ray (exact values: the device must give the same
   bits) and the shading normal recomputed from the hit record in a dtype of the caller's choice.
 * atrous: the filter of include/nexus_hip.h (nxhip_denoise) in numpy — float64 as the definition is written, or float32 in the
@@ -23,17 +23,28 @@ def fma32(a, b, c):
 
 
 def primary_rays(cam, W, H, frame):
-    """The rays generate_kernel makes for frame `frame` (pinhole: lens radius 0), row-major over the image"""
-    assert float(cam["lensRadius"]) == 0.0, "the restatement covers the pinhole camera"
+    """The rays generate_kernel makes for frame `frame`, row-major over the image: pinhole or thin lens (unit_disk's rejection loop on the
+    oracle's random numbers, the lens offset right * rdx + up * rdy added to the origin and taken off the direction).  Both are held
+    against the float64 camera of tests/camera_reference.py by tests/test_camera_reference.py."""
     L = O.lib()
     n = W * H
+    lens_radius = f32(cam["lensRadius"])
     xs = np.empty(n, f32)
     ys = np.empty(n, f32)
+    disk = np.zeros((n, 2), f32)
     for g in range(n):
         j, i = divmod(g, W)
         st = C.c_uint32(L.orc_rng_init_pixel(i, j, W, frame))
         xs[g] = L.orc_rand(C.byref(st))
         ys[g] = L.orc_rand(C.byref(st))
+        while True:  # (unit_disk is drawn whatever the lens radius)
+            a = f32(L.orc_rand(C.byref(st)))
+            b = f32(L.orc_rand(C.byref(st)))
+            px = f32(2.0) * (a - f32(0.5))
+            py = f32(2.0) * (b - f32(0.5))
+            if np.sqrt(px * px + py * py) < f32(1.0):
+                break
+        disk[g] = (px, py)
     g = np.arange(n)
     i = (g % W).astype(f32)
     j = (g // W).astype(f32)
@@ -43,13 +54,18 @@ def primary_rays(cam, W, H, frame):
     llc = np.asarray(cam["lowerLeftCorner"], f32).reshape(3)
     vx = np.asarray(cam["viewportX"], f32).reshape(3)
     vy = np.asarray(cam["viewportY"], f32).reshape(3)
+    right = np.asarray(cam["right"], f32).reshape(3)
+    up = np.asarray(cam["up"], f32).reshape(3)
+    rdx = lens_radius * disk[:, 0]
+    rdy = lens_radius * disk[:, 1]
+    offset = right[None, :] * rdx[:, None] + up[None, :] * rdy[:, None]  # (a pinhole: +0 or -0, which changes no bit below)
     d = ((llc[None, :] + vx[None, :] * x[:, None]) + vy[None, :] * y[:, None]) - pos[None, :]
-    d = d - f32(0.0)  # (the lens offset of a pinhole)
+    d = d - offset
     dd = fma32(d[:, 2], d[:, 2], fma32(d[:, 1], d[:, 1], d[:, 0] * d[:, 0]))
     inv = f32(1.0) / np.sqrt(dd)
     d = d * inv[:, None]
     rays = np.zeros(n, pod.RAY_DT)
-    rays["origin"] = pos
+    rays["origin"] = pos[None, :] + offset
     rays["direction"] = d
     return rays
 

@@ -154,7 +154,7 @@ def test_nothing_else_moves(gpu_ctx_factory, name, compact):
 
 
 def test_lens_camera_albedo_is_the_radiance_of_the_emission_twin(gpu_ctx_factory):
-    """Lens radius > 0 (the zoo's own camera, outside the numpy restatement): albedo and coverage equal the radiance the device itself
+    """Lens radius > 0 (the zoo's own camera): albedo and coverage equal the radiance the device itself
     renders for the pathLength-1 twin whose emission is the albedo (at bounce 1 no MIS weight applies: the radiance IS the emission)."""
     W, H = 96, 64
     sc = SH.material_zoo_scene(W, H, hdr=False, textures=True)
@@ -180,6 +180,13 @@ def test_lens_camera_albedo_is_the_radiance_of_the_emission_twin(gpu_ctx_factory
         print("lens camera frame %d: %d of %d pixels equal bits, coverage %.3f" % (frame, same.sum(), len(same), albedo[:, 3].mean()))
         assert same.all()
         assert np.array_equal(albedo[:, 3] == 1.0, nd[:, 3] > 0.0) and set(np.unique(albedo[:, 3])) <= {0.0, 1.0}
+        # ... and, since the restatement has the lens path (held to the float64 camera by tests/test_camera_reference.py): the oracle's hit of
+        # the restated lens ray, bit for bit
+        want_albedo, want_depth, _, _ = R.primary_features(sc, W, H, frame)
+        same_a = np.all(albedo.view(np.uint32) == want_albedo.view(np.uint32), axis=1)
+        same_z = nd[:, 3].view(np.uint32) == want_depth.view(np.uint32)
+        print("lens camera frame %d against the restated lens rays: albedo+coverage %d of %d equal bits, depth %d of %d" % (frame, same_a.sum(), len(same_a), same_z.sum(), len(same_z)))
+        assert same_a.all() and same_z.all()
 
 
 def test_write_read_round_trip_and_statuses(gpu_ctx_factory):
