@@ -1,7 +1,7 @@
 // nexus_render — the reference's render loop (Renderer.cpp:41-77: scene.Update, UpdateDeviceScene, Render) driven headless
 // through the kept C++ host API: load a .glb / .obj, path-trace `frames` frames on an MI355X, write the image as a PPM.
 //
-//   nexus_render [--denoise] [--adaptive THRESHOLD [--max-frames N]] [--light-sampling uniform|power] [--env-float FILE.hdr] [--env-sampling]
+//   nexus_render [--denoise] [--adaptive THRESHOLD [--max-frames N]] [--light-sampling uniform|power] [--transparent-shadows] [--env-float FILE.hdr] [--env-sampling]
 //                [--point-light X Y Z INTENSITY] [--sun DX DY DZ IRRADIANCE] <dir/> <file.glb|file.obj> <out.ppm> [width height frames pathLength]
 //                [eyeX eyeY eyeZ fwdX fwdY fwdZ hfovDeg]
 // --denoise: the feature buffers are accumulated with the colour and the image written is the a-trous filtered one (nxhip_denoise)
@@ -10,6 +10,8 @@
 //   at most N frames, default 1024; `frames` is ignored).  Combines with --denoise.  The image is not an unbiased estimate.
 // --light-sampling power: the light sample picks among the mesh lights' triangles in proportion to area x emitted luminance
 //   (nxhip_set_light_sampling; default uniform: the reference's rule).  Same expectation, less noise under small or dim emitters.
+// --transparent-shadows: opacity (glTF baseColorFactor[3]) and the alpha of the base colour texture attenuate shadow rays instead of
+//   blocking them (nxhip_set_shadow_transmittance; default off: the reference's rule, under which a see-through surface casts a solid shadow).
 // --env-float FILE.hdr: a Radiance .hdr file as the environment, as the linear float radiance it holds (Scene::AddHDRMapFloat,
 //   nxhip_upload_env_float) instead of the 8 bits "Load HDR map" reduces it to.
 // --env-sampling: the light sample may pick the environment map (nxhip_set_env_sampling): what a map with a small bright sun needs.
@@ -35,6 +37,7 @@ int main(int argc, char** argv)
     float threshold = 0.0f;
     uint32_t maxFrames = 1024;
     int lightSampling = NXHIP_LIGHTS_UNIFORM;
+    bool transparentShadows = false;
     std::string envFloat;
     bool envSampling = false;
     std::vector<nexus::AnalyticLight> extraLights;
@@ -59,6 +62,9 @@ int main(int argc, char** argv)
             }
             lightSampling = mode == "power" ? NXHIP_LIGHTS_POWER : NXHIP_LIGHTS_UNIFORM;
             used = 2;
+        } else if (opt == "--transparent-shadows") {
+            transparentShadows = true;
+            used = 1;
         } else if (opt == "--env-float" && argc > 2) {
             envFloat = argv[2];
             used = 2;
@@ -80,7 +86,7 @@ int main(int argc, char** argv)
         argc -= used;
     }
     if (argc < 4) {
-        std::fprintf(stderr, "usage: %s [--denoise] [--adaptive THRESHOLD [--max-frames N]] [--light-sampling uniform|power] [--env-float FILE.hdr] [--env-sampling] [--point-light X Y Z INTENSITY] [--sun DX DY DZ IRRADIANCE] <dir/> <file.glb|file.obj> <out.ppm> [width height frames pathLength] [eye(3) forward(3) hfov]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s [--denoise] [--adaptive THRESHOLD [--max-frames N]] [--light-sampling uniform|power] [--transparent-shadows] [--env-float FILE.hdr] [--env-sampling] [--point-light X Y Z INTENSITY] [--sun DX DY DZ IRRADIANCE] <dir/> <file.glb|file.obj> <out.ppm> [width height frames pathLength] [eye(3) forward(3) hfov]\n", argv[0]);
         return 2;
     }
     // a program built against these headers and run with another build of libnexus_amd.so gets an error string here, not a GPU fault
@@ -126,6 +132,7 @@ int main(int argc, char** argv)
         }
         if (denoise) pathTracer.SetFeatureBuffers(true);
         pathTracer.SetLightSampling(lightSampling);
+        pathTracer.SetShadowTransmittance(transparentShadows ? NXHIP_SHADOWS_TRANSMIT : NXHIP_SHADOWS_OPAQUE);
         uint32_t activePixels = 0;
         if (adaptive) {
             nx_adaptive_params params;

@@ -51,6 +51,9 @@ public:
     // rule and the default) or NXHIP_LIGHTS_POWER (1: in proportion to area x emitted luminance, from a table built on the device).
     // Same expectation either way: may be switched between frames.
     void SetLightSampling(int mode);
+    // Transparent shadows (nxhip_set_shadow_transmittance): NXHIP_SHADOWS_OPAQUE (0, the reference's rule and the default: a shadow ray ends
+    // at the first triangle) or NXHIP_SHADOWS_TRANSMIT (1: every crossing multiplies the ray's transmittance by 1 - opacity x alpha(uv)).
+    void SetShadowTransmittance(int mode);
     // The order of the frame's paths: NXHIP_ORDER_ROWS (the reference's, default) or NXHIP_ORDER_TILES (8 x 8 pixel tiles: the rays a
     // wave fetches together are a compact block of the image; kept across OnResize).  nxhip_set_pixel_order.
     void SetPixelOrder(int order);

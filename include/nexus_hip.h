@@ -256,6 +256,32 @@ int nxhip_set_env_sampling(nxhip_ctx *ctx, int enable);
  * In POWER mode a light list that names one instance twice is refused by the render (NXHIP_ERR_INVALID).  Another mode: NXHIP_ERR_INVALID. */
 enum { NXHIP_LIGHTS_UNIFORM = 0, NXHIP_LIGHTS_POWER = 1 };
 int nxhip_set_light_sampling(nxhip_ctx *ctx, int mode);
+/* Extension: transparent shadows.  A material's `opacity` and the alpha of its diffuse map let a PATH pass a surface with probability
+ * 1 - opacity x alpha(uv) (the material kernels, the reference's rule); the reference's shadow rays end at the first triangle whatever its
+ * material, so a delta light behind a see-through surface contributes 0 and, with useMIS, the light-sample share of every emitter
+ * behind one is lost (the image converges to the BSDF-sampled share alone: "MIS == naive" fails for such scenes).
+ *   NXHIP_SHADOWS_OPAQUE (default)  the reference's rule, bit for bit.
+ *   NXHIP_SHADOWS_TRANSMIT          a shadow ray carries a transmittance T, binary32, 1.0f at the start.  Every triangle the any-hit
+ *                                   traversal accepts (its test of today: 0 < t < tmax, u, v inside) is a crossing and multiplies
+ *                                   T by 1.0f - s, in the traversal's own visiting order, with s = o * a:
+ *                                     o = the instance material's opacity clamped to [0, 1]; `!(opacity < 1)` is opaque, a NaN included
+ *                                         (rng_next > NaN never passes in the material kernel);
+ *                                     a = 1 without a diffuse map, else the .w of the bilinear lookup of diffuseMaps[diffuseMapId] at the
+ *                                         texture coordinates of the ORIGINAL triangle interpolated with the u, v of this very test —
+ *                                         the arithmetic of the material kernel, so the alpha it would fetch at that hit.
+ *                                   T == 0.0f ends the ray (occluded); there is no other threshold.  At retirement T x the request's
+ *                                   radiance is added to the path: exactly the default's addition when nothing was crossed (T is 1.0f),
+ *                                   exactly nothing when only opaque surfaces were.
+ * In expectation this is the stochastic pass-through of the material kernels (pass probability 1 - o a, up to the 2^-23 granularity of
+ * rng_next).  Deterministic: no random number is drawn, no random stream moves.  Limits: dielectrics block shadow rays as before (only
+ * opacity and alpha count); a pass-through on the path side spends a bounce, a crossing of a shadow ray does not, so at the pathLength
+ * cut-off the two strategies see one segment more or less; glTF alphaMode / alphaCutoff stay ignored.
+ * The mode changes a pass only while some material of the table is see-through (opacity < 1, or a diffuse map with a texel of alpha <
+ * 255): otherwise the default kernels run.  While it does, the any-hit launches do not hand rays to the thin kernel and the tail kernel
+ * is off (nxhip_set_tail_bounce is ignored): restrictions of a first version.  Results do not depend on nxhip_enable_trace_stats.
+ * May be switched at any time, also between accumulated frames.  Another mode: NXHIP_ERR_INVALID. */
+enum { NXHIP_SHADOWS_OPAQUE = 0, NXHIP_SHADOWS_TRANSMIT = 1 };
+int nxhip_set_shadow_transmittance(nxhip_ctx *ctx, int mode);
 /* PathTracer::UpdateDeviceScene / Scene::ToDevice — Renderer/PathTracer.cpp:305-308, Scene/Scene.cpp:115-140 */
 int nxhip_set_camera(nxhip_ctx *ctx, const nx_camera *camera);
 int nxhip_set_render_settings(nxhip_ctx *ctx, const nx_render_settings *settings);
@@ -552,6 +578,11 @@ int nxhip_get_selected_instance(nxhip_ctx *ctx, int32_t *instanceIdx);
 int nxhip_trace_batch(nxhip_ctx *ctx, const nx_ray *rays, uint32_t count, nx_hit *hits);
 /* TraceShadowKernel's any-hit test — BVH8Traversal.cuh:326-518.  occluded[i] = 1 if blocked within tmax[i]. */
 int nxhip_trace_shadow_batch(nxhip_ctx *ctx, const nx_ray *rays, const float *tmax, uint32_t count, uint8_t *occluded);
+/* The same batch through the any-hit TRANSMIT instance (nxhip_set_shadow_transmittance), whatever the context's mode: transmittance[i] =
+ * the ray's T (0 = occluded).  Needs what a render needs (TLAS, materials, every diffuse map a material names): the kernel follows
+ * instance -> material -> texture -> triangle without bounds tests, so the tables are checked and brought up to date first.
+ * nxhip_trace_shadow_batch itself launches the plain instance in every mode. */
+int nxhip_trace_transmittance_batch(nxhip_ctx *ctx, const nx_ray *rays, const float *tmax, uint32_t count, float *transmittance);
 
 /* Test hook: overwrite ONE node of an uploaded BLAS in device memory WITHOUT the checks of nxhip_upload_blas.  Exists so that
  * the trace kernels' behaviour on a BVH that is not a tree (a child that points back at its parent) can be tested: they must

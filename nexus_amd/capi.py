@@ -36,6 +36,7 @@ HIP_SYMBOLS = [
     "nxhip_upload_env_float", "nxhip_read_env_float", "nxhip_read_env_guides",
     "nxhip_set_analytic_lights", "nxhip_analytic_light_sample_batch",
     "nxhip_debug_read_primary_rays",
+    "nxhip_set_shadow_transmittance", "nxhip_trace_transmittance_batch",
 ]
 HOST_SYMBOLS = [
     "nxh_bvh8_build", "nxh_tlas_build", "nxh_tlas_refit", "nxh_bvh8_refit", "nxh_bvh8_node_count", "nxh_bvh8_prim_count", "nxh_bvh8_nodes",
@@ -56,6 +57,7 @@ HOST_SYMBOLS = [
     "nxs_scene_set_hdr_map_float", "nxs_scene_add_hdr_map_file_float", "nxh_decode_hdr_float",
     "nxh_loaded_analytic_light_count", "nxh_loaded_analytic_lights",
     "nxs_scene_add_analytic_light", "nxs_scene_remove_analytic_light", "nxs_scene_analytic_light_count", "nxs_scene_analytic_lights",
+    "nxs_pathtracer_set_shadow_transmittance",
 ]
 
 
@@ -520,6 +522,7 @@ def decode_image(data):
 
 FLAVOR_IDENTITY, FLAVOR_NO_MAPS = 256, 512  # Context.debug_pass_flavor: the specialised kernel instances of a pass graph
 FLAVOR_ANALYTIC = 1024  # ... and the instances of a context with analytic lights (set_analytic_lights)
+FLAVOR_TRANSMIT = 2048  # ... and the any-hit TRANSMIT instance: SHADOWS_TRANSMIT over a table with a see-through material (set_shadow_transmittance)
 
 
 class Context:
@@ -862,6 +865,13 @@ class Context:
         self.L.nxhip_set_light_sampling.argtypes = [C.c_void_p, C.c_int]
         check(self.L.nxhip_set_light_sampling(self.h, int(mode)), "nxhip_set_light_sampling")
 
+    def set_shadow_transmittance(self, mode):
+        """SHADOWS_OPAQUE (0, the reference's rule: a shadow ray ends at the first triangle) or SHADOWS_TRANSMIT (1): every crossing
+        multiplies the ray's transmittance by 1 - opacity x alpha(uv) (nxhip_set_shadow_transmittance; deterministic, same expectation as
+        the paths' own pass-through)"""
+        self.L.nxhip_set_shadow_transmittance.argtypes = [C.c_void_p, C.c_int]
+        check(self.L.nxhip_set_shadow_transmittance(self.h, int(mode)), "nxhip_set_shadow_transmittance")
+
     def read_light_table(self, light_count):
         """the light table of LIGHTS_POWER (brought up to date first): (cdf float32[N], entryLight uint32[N], lightBase uint32[light_count + 1])"""
         self.L.nxhip_read_light_table.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32)]
@@ -1177,6 +1187,15 @@ class Context:
         occ = np.zeros(len(rays), dtype=np.uint8)
         check(self.L.nxhip_trace_shadow_batch(self.h, _ptr(rays), _ptr(tmax), len(rays), _ptr(occ)), "nxhip_trace_shadow_batch")
         return occ
+
+    def trace_transmittance_batch(self, rays, tmax):
+        """the rays' transmittance T (float32; 0 = occluded) through the any-hit TRANSMIT instance, whatever the context's mode"""
+        rays = np.ascontiguousarray(rays, dtype=pod.RAY_DT)
+        tmax = np.ascontiguousarray(tmax, dtype=np.float32)
+        out = np.zeros(len(rays), dtype=np.float32)
+        self.L.nxhip_trace_transmittance_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+        check(self.L.nxhip_trace_transmittance_batch(self.h, _ptr(rays), _ptr(tmax), len(rays), _ptr(out)), "nxhip_trace_transmittance_batch")
+        return out
 
     def _bsdf_batch(self, fn, name, material, queries):
         mat = np.ascontiguousarray(material, dtype=pod.MAT_DT).reshape(1)
@@ -1565,6 +1584,11 @@ class PathTracer:
     def set_entry_points(self, on=True):
         self.L.nxs_pathtracer_set_entry_points.argtypes = [C.c_void_p, C.c_int]
         _scheck(self.L.nxs_pathtracer_set_entry_points(self.h, 1 if on else 0), "nxs_pathtracer_set_entry_points")
+
+    def set_shadow_transmittance(self, mode):
+        """PathTracer::SetShadowTransmittance: pod.SHADOWS_OPAQUE (the reference's rule) or pod.SHADOWS_TRANSMIT (opacity and texture alpha attenuate shadow rays)"""
+        self.L.nxs_pathtracer_set_shadow_transmittance.argtypes = [C.c_void_p, C.c_int]
+        _scheck(self.L.nxs_pathtracer_set_shadow_transmittance(self.h, int(mode)), "nxs_pathtracer_set_shadow_transmittance")
 
     def set_light_sampling(self, mode):
         """PathTracer::SetLightSampling: pod.LIGHTS_UNIFORM (the reference's rule) or pod.LIGHTS_POWER (area x emitted luminance)"""

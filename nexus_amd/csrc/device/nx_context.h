@@ -75,6 +75,7 @@ struct BlasHost {
 struct TextureHost {
     DevBuf texels;
     uint32_t width = 0, height = 0;
+    bool hasAlpha = false;  // RGBA8 maps: some texel has alpha < 255 (known at upload; refresh_see_through)
 };
 
 struct KernelTimer {
@@ -231,6 +232,11 @@ struct nxhip_ctx : nxd::PassSlot {
     // some material of the table names a diffuse or an emissive map (nxhip_set_materials; whatever has or has not been uploaded): the
     // map-free instance of the material launch is for contexts where none does (kFlavorNoMaps, nxhip_render.hip pass_flavor)
     bool materialsNameMaps = true;
+    // nxhip_set_shadow_transmittance: the mode, and whether some material of the table is see-through — opacity < 1, or a diffuse map
+    // with a texel of alpha < 255 (refresh_see_through: nxhip_set_materials, diffuse texture uploads, nxhip_clear_textures).  Only both
+    // together change a pass (kFlavorTransmit): a TRANSMIT context over an all-opaque scene launches the default kernels.
+    int shadowTransmittance = 0;  // NXHIP_SHADOWS_*
+    bool materialsSeeThrough = false;
     int flavorForceGeneral = 0;  // nxhip_debug_pass_flavor: the kFlavor* bits of specialised kernel instances a pass must not use
     int lastPassFlavor = 0;      // pass_flavor() of the last pass issued (nxhip_debug_pass_flavor)
     bool thinInHooks = false;  // nxhip_debug_set_thin: the ray-batch hooks hand over and launch the thin kernel too

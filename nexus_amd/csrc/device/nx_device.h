@@ -118,7 +118,8 @@ struct __attribute__((aligned(16))) ShadeInst {
     uint32_t triCount;
     int32_t materialId;
     nx_material material;    // the device copy (derived flag byte behind `type` included: kMaterialFlagOffset)
-    uint32_t pad_;
+    uint32_t seeThrough;     // derived (refresh_shade_inst): 1 = a shadow ray of NXHIP_SHADOWS_TRANSMIT may pass — opacity < 1, or the diffuse
+                             // map has a texel with alpha < 255; 0 = every crossing ends the ray (the any-hit TRANSMIT instance, nx_trace.hip)
 };
 static_assert(sizeof(ShadeInst) == 176 && offsetof(ShadeInst, material) == 112, "ShadeInst layout");
 

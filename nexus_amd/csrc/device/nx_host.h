@@ -15,6 +15,7 @@ namespace nxd {
 // definitions.  The getters of the other kernel units are declared here as they are defined there (nx_trace.hip, nx_entry.hip
 // and nx_wavefront.hip cannot include it: their text is pinned by bench.py's source hash).
 const void* trace_kernel_ptr(bool anyHit, bool stats, bool identity = false);  // nx_trace.hip
+const void* trace_transmit_kernel_ptr(bool stats);  // the any-hit TRANSMIT instance (nxhip_set_shadow_transmittance)
 const void* trace_entry_kernel_ptr(bool identity = false);
 const void* thin_kernel_ptr();
 const void* entry_state_kernel_ptr();  // nx_entry.hip
@@ -109,6 +110,7 @@ using StateKernel = Kernel<State>;            // (S)
 using BounceKernel = Kernel<State, int>;      // (S, bounce | flags)
 using TypeKernel = Kernel<State, int, int>;   // (S, bounce | flags, type or type mask)
 inline BounceKernel trace(bool anyHit, bool stats, bool identity = false) { return {trace_kernel_ptr(anyHit, stats, identity)}; }  // (identity: pass graphs only)
+inline BounceKernel trace_transmit(bool stats) { return {trace_transmit_kernel_ptr(stats)}; }  // (any hit; pass graphs of kFlavorTransmit and nxhip_trace_transmittance_batch)
 inline BounceKernel trace_entry(bool identity = false) { return {trace_entry_kernel_ptr(identity)}; }
 inline BounceKernel thin() { return {thin_kernel_ptr()}; }
 inline StateKernel entry_state() { return {entry_state_kernel_ptr()}; }
@@ -275,6 +277,8 @@ void publish_pixel_set(nxhip_ctx* c);
 int set_frame_number_device(nxhip_ctx* c, uint32_t f);
 // nxhip_scene.hip: what a pass or a hook brings up to date before it reads the scene
 int refresh_shade_inst(nxhip_ctx* c);
+bool material_see_through(const nxhip_ctx* c, const nx_material& m);  // a shadow ray of NXHIP_SHADOWS_TRANSMIT may pass it
+void refresh_see_through(nxhip_ctx* c);  // nxhip_ctx::materialsSeeThrough, and the shading records' copy of the fact
 int refresh_updated_blas(nxhip_ctx* c);
 // nxhip_render.hip
 int check_scene_ready(nxhip_ctx* c);

@@ -42,6 +42,26 @@ NXD float4 tex2d(const TextureDev& t, const float* __restrict__ srgbLut, float u
     return make_float4(out[0], out[1], out[2], out[3]);
 }
 
+// Channel 3 of tex2d alone, for a reader that wants the alpha only (the any-hit TRANSMIT instance, nx_trace.hip): the same addressing
+// and, for that channel, the same expression sequence — so the same bits as tex2d(...).w — without the twelve LUT reads of the others.
+NXD float tex2d_alpha(const TextureDev& t, float u, float v)
+{
+    const int W = (int)t.width, H = (int)t.height;
+    const float xb = u * (float)W - 0.5f, yb = v * (float)H - 0.5f;
+    const float fx = floorf(xb), fy = floorf(yb);
+    const float ax = floorf((xb - fx) * 256.0f + 0.5f) * (1.0f / 256.0f);
+    const float ay = floorf((yb - fy) * 256.0f + 0.5f) * (1.0f / 256.0f);
+    const int i0 = wrapi((int)fx, W), i1 = wrapi((int)fx + 1, W);
+    const int j0 = wrapi((int)fy, H), j1 = wrapi((int)fy + 1, H);
+    const uint32_t p00 = t.texels[(size_t)j0 * W + i0], p10 = t.texels[(size_t)j0 * W + i1];
+    const uint32_t p01 = t.texels[(size_t)j1 * W + i0], p11 = t.texels[(size_t)j1 * W + i1];
+    const float t00 = (float)(p00 >> 24) / 255.0f, t10 = (float)(p10 >> 24) / 255.0f;
+    const float t01 = (float)(p01 >> 24) / 255.0f, t11 = (float)(p11 >> 24) / 255.0f;
+    const float top = t00 + ax * (t10 - t00);
+    const float bot = t01 + ax * (t11 - t01);
+    return top + ay * (bot - top);
+}
+
 // The float environment map's lookup (nxhip_upload_env_float): the same addressing — normalised coordinates, texel centres at +0.5,
 // wrap on both axes — over one float4 of linear radiance per texel, with the EXACT binary32 fractional weights.  The 1/256 steps
 // above imitate a texture unit that only ever filtered 8-bit texels; next to a texel of 6e4, 1/512 of a weight is 117, not a

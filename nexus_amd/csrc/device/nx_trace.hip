@@ -31,6 +31,7 @@
 #define NX_KERNEL_TU 1
 #include "nx_queue.h"
 #include "nx_traverse.h"
+#include "nx_texture.h"
 
 namespace nxd {
 
@@ -404,7 +405,14 @@ NXD ThinResult thin_wave_search(const DeviceState* __restrict__ S, lds_u64* cons
 // in nxhip_render.hip) — what the general instances read from DeviceState::sceneFlags is the constant `true` here, so the transform
 // rows, their loads and the general branch of enter_instance are not compiled in and cost no registers (rays that are not "ordinary"
 // still go through the identity's rows as constants: nx_traverse.h).  The counting variants and the ray-batch hooks keep the flag.
-template <bool ANY_HIT, bool STATS, bool ENTRY = false, bool IDENTITY = false>
+// TRANSMIT (any hit only; nxhip_set_shadow_transmittance, kFlavorTransmit): the ray carries a transmittance T, 1.0f at the start.  An
+// accepted triangle does not end it: the lane fetches its instance's shading record (ShadeInst, one dependent load) and, if the material
+// is see-through, the original triangle's texture coordinates and the diffuse map's alpha at this test's own u, v — shade_path's
+// arithmetic, so the alpha the material kernel would fetch there — and T *= 1 - opacity x alpha, in the ray's own visiting order.  T == 0
+// ends the ray; the flush adds T x radiance.  No random number is drawn.  The pass graph launches this instance without the hand-over
+// (a wave-wide search would multiply in an order of its own); check_scene_ready and refresh_shade_inst have run before any launch:
+// instance -> material -> texture -> triangle are followed without bounds tests, as in the material kernels.
+template <bool ANY_HIT, bool STATS, bool ENTRY = false, bool IDENTITY = false, bool TRANSMIT = false>
 // 5 waves per SIMD for both variants (96 VGPRs, no spills in the loop).  Before an instance entry also carried its BLAS
 // root (17 more live registers in the fetch), 6 waves at 80 VGPRs was the best point (5: -3 %, 7: -0.3 %, 8: -1.5 %); with it,
 // 6 waves spill 23 VGPRs inside the loop (-10 %), 5 and 4 measure +4.5 % and +1 % over the old kernel at 6.
@@ -421,7 +429,8 @@ __global__ void __launch_bounds__(kTraceBlock) trace_kernel(const DeviceState* _
     // ... | kTraceEntryFlag: the rays name the entry state of their run (rayO.w): installed at refill instead of the root's
     const bool entryLaunch = !ANY_HIT && (ENTRY || STATS) && (bounceArg & kTraceEntryFlag) != 0 && S->entry != nullptr;
     // ... | kTraceThinFlag: the last long rays of a dry wave may be handed to the thin kernel (below)
-    bool thinAllowed = !STATS && (bounceArg & kTraceThinFlag) != 0;
+    static_assert(!TRANSMIT || (ANY_HIT && !ENTRY && !IDENTITY), "TRANSMIT: the general any-hit instance and its counting variant only");
+    bool thinAllowed = !STATS && !TRANSMIT && (bounceArg & kTraceThinFlag) != 0;
     const int thinLanes = (int)(S->thinLanes & 0xffu);
     // (test hook, nxhip_debug_set_thin inHooks bit 1: hand over after thinIters iterations of EVERY stretch between two refill points, dry
     //  queue or not — rays then arrive at the thin kernel with the state of exactly that many steps)
@@ -511,6 +520,7 @@ __global__ void __launch_bounds__(kTraceBlock) trace_kernel(const DeviceState* _
     bool resultPending = false;  // this lane's ray has finished and its result has not been written yet
     f3 org = mk3(0.0f), dir = mk3(0.0f), idir = mk3(0.0f);
     float hitT = 0.0f, hitU = 0.0f, hitV = 0.0f;
+    float transT = 1.0f;  // (TRANSMIT: the ray's transmittance so far; live across the loop of that instance only)
     uint32_t hitTri = 0xffffffffu, hitInst = 0xffffffffu;
     uint32_t rayIdx = 0, pixelBits = 0, instIdx = 0, invOct4 = 0;
     int instSp = -1;
@@ -537,7 +547,8 @@ __global__ void __launch_bounds__(kTraceBlock) trace_kernel(const DeviceState* _
                 const float4 r = S->shadow.radiance[rayIdx];
                 NX_G float4* dst = &S->radiance[pixelBits];
                 float4 cur = *dst;
-                cur.x += r.x; cur.y += r.y; cur.z += r.z;
+                if constexpr (TRANSMIT) { cur.x += transT * r.x; cur.y += transT * r.y; cur.z += transT * r.z; }  // (T is exactly 1.0f when nothing was crossed)
+                else { cur.x += r.x; cur.y += r.y; cur.z += r.z; }
                 *dst = cur;
             } else {
                 // The hit's instance arrives with its material type + 1 above kHitCodeShift (InstTrav::instIdx), the ray with the
@@ -671,6 +682,7 @@ __global__ void __launch_bounds__(kTraceBlock) trace_kernel(const DeviceState* _
                     idir = mk3(1.0f / dir.x, 1.0f / dir.y, 1.0f / dir.z);
                     hitT = ANY_HIT ? o.w : 1e30f;
                     hitU = 0.0f; hitV = 0.0f; hitTri = 0xffffffffu; hitInst = 0xffffffffu;
+                    if (TRANSMIT) transT = 1.0f;
                     const uint32_t oct = ((dir.x < 0.0f ? 1u : 0u) << 2) | ((dir.y < 0.0f ? 1u : 0u) << 1) | (dir.z < 0.0f ? 1u : 0u);
                     invOct4 = (7u - oct) * 0x01010101u;
                     ng = make_uint2(0u, 0x80000000u);
@@ -860,7 +872,25 @@ __global__ void __launch_bounds__(kTraceBlock) trace_kernel(const DeviceState* _
                 const bool hit = !(u < 0.0f || u > 1.0f) && !(v < 0.0f || u + v > 1.0f) && (t > 0.0f && t < hitT);
                 if (STATS) nTris++;
                 if (hit) {
-                    if (ANY_HIT) {
+                    if (ANY_HIT && TRANSMIT) {
+                        // a crossing: T *= 1 - o * a (include/nexus_hip.h, nxhip_set_shadow_transmittance)
+                        const NX_G ShadeInst* si = &S->shadeInst[instIdx & kHitInstMask];
+                        if (si->seeThrough == 0u) {
+                            active = false;  // an opaque material: occluded, no triangle or texture fetch
+                        } else {
+                            float o = si->material.opacity;
+                            o = !(o < 1.0f) ? 1.0f : fmaxf(o, 0.0f);  // (a NaN opacity is opaque: rng_next > NaN never passes in the material kernel)
+                            float a = 1.0f;
+                            const int32_t map = si->material.diffuseMapId;
+                            if (map != -1) {
+                                const NX_G nx_triangle* tri = shade_tri(si->tris, rc[0].w);  // the ORIGINAL triangle: p0.w of the leaf stream
+                                const f2 texUv = bary2(tri->texCoord0, tri->texCoord1, tri->texCoord2, u, v);
+                                a = tex2d_alpha(S->diffuseMaps[map], texUv.x, texUv.y);
+                            }
+                            transT *= 1.0f - o * a;
+                            if (transT == 0.0f) active = false;  // occluded; no other threshold
+                        }
+                    } else if (ANY_HIT) {
                         active = false;  // occluded: nothing to add
                     } else {
                         hitT = t; hitU = u; hitV = v;
@@ -956,6 +986,8 @@ template __global__ void trace_kernel<true, true>(const DeviceState*, int);
 template __global__ void trace_kernel<false, false, false, true>(const DeviceState*, int);
 template __global__ void trace_kernel<false, false, true, true>(const DeviceState*, int);
 template __global__ void trace_kernel<true, false, false, true>(const DeviceState*, int);
+template __global__ void trace_kernel<true, false, false, false, true>(const DeviceState*, int);
+template __global__ void trace_kernel<true, true, false, false, true>(const DeviceState*, int);
 
 // The listed rays of one level (closest-hit first, then any-hit; kThinClosestOnly / kThinAnyOnly: one list), one wave per ray,
 // grid-stride.  `bounceArg` as the trace launches got it: the ray set and the meaning of the closest-hit record follow kTraceScanFlag.
@@ -1067,6 +1099,9 @@ const void* trace_kernel_ptr(bool anyHit, bool stats, bool identity)
     if (anyHit) return stats ? (const void*)trace_kernel<true, true> : (const void*)trace_kernel<true, false>;
     return stats ? (const void*)trace_kernel<false, true> : (const void*)trace_kernel<false, false>;
 }
+
+// the any-hit TRANSMIT instance (reads sceneFlags: no IDENTITY form) and its counting variant
+const void* trace_transmit_kernel_ptr(bool stats) { return stats ? (const void*)trace_kernel<true, true, false, false, true> : (const void*)trace_kernel<true, false, false, false, true>; }
 
 // the device-side layouts this translation unit was compiled with (nx_device.h layout_stamp; compared by nxhip_create)
 uint64_t layout_stamp_trace() { return layout_stamp(); }

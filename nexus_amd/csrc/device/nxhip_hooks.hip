@@ -41,14 +41,14 @@ static int hook_copy(nxhip_ctx* c, const HookLayout& l, void* dev, void* host, s
     return NXHIP_OK;
 }
 
-static int run_trace_chunk(nxhip_ctx* c, bool anyHit, uint32_t n)
+static int run_trace_chunk(nxhip_ctx* c, bool anyHit, uint32_t n, bool transmit = false)
 {
     // region sizes + zeroed fetch heads for the reserved bounce slot, computed on the device from n (hook_layout's rule): no copy
     // from a stack-local of this function is left in flight when it returns
     NX_HIP(launch_untimed(kernels::hook_sizes(), 1, 64, c->stream, c->dState.as<DeviceState>(), n, anyHit ? 1 : 0, kHookBounceSlot));
     c->errorFresh = false;  // (this launch may set the error word after the last pass's copy of it)
-    const bool thin = c->thinInHooks && !c->statsEnabled;
-    Launch l = make_launch(kernels::trace(anyHit, c->statsEnabled), anyHit ? c->shadowBlocks : c->traceBlocks, kTraceBlockThreads,
+    const bool thin = c->thinInHooks && !c->statsEnabled && !transmit;  // (the TRANSMIT instance never hands over)
+    Launch l = make_launch(transmit ? kernels::trace_transmit(c->statsEnabled) : kernels::trace(anyHit, c->statsEnabled), anyHit ? c->shadowBlocks : c->traceBlocks, kTraceBlockThreads,
                            anyHit ? NXHIP_K_SHADOW : NXHIP_K_TRACE, c->dState.as<DeviceState>(), kHookBounceSlot | (thin ? kTraceThinFlag : 0));
     int rc = launch_now(c, l);
     if (rc == NXHIP_OK && thin) {  // (nxhip_debug_set_thin: what the dry waves handed over, a wave each)
@@ -99,13 +99,18 @@ try {
     return NXHIP_OK;
 } NX_CATCH("nxhip_trace_batch")
 
-int nxhip_trace_shadow_batch(nxhip_ctx* c, const nx_ray* rays, const float* tmax, uint32_t count, uint8_t* occluded)
-try {
+// transmittance != nullptr: nxhip_trace_transmittance_batch — the TRANSMIT instance, and T itself instead of "occluded"
+static int shadow_batch(nxhip_ctx* c, const char* who, const nx_ray* rays, const float* tmax, uint32_t count, uint8_t* occluded, float* transmittance)
+{
     NX_CHECK_CTX(c);
     if (count == 0) return NXHIP_OK;
-    if (!rays || !tmax || !occluded) return fail_invalid("nxhip_trace_shadow_batch: null buffer");
+    if (!rays || !tmax || (!occluded && !transmittance)) return fail_invalid(std::string(who) + ": null buffer");
     NX_HIP(hipSetDevice(c->device));
     if (!c->h.tlasNodes) return fail_invalid("no TLAS has been set");
+    if (transmittance) {  // what a render does before its pass: the instance reads the shading records, the maps and the triangles
+        NX_TRY(check_scene_ready(c));
+        if (c->shadeInstDirty) NX_TRY(refresh_shade_inst(c));
+    }
     NX_TRY(ensure_slot_queues(c, c));
     NX_TRY(upload_state(c));
     NX_TRY(refresh_updated_blas(c));
@@ -127,13 +132,26 @@ try {
         NX_TRY(hook_copy(c, l, c->shRayD.p, d.data(), 16, true));
         NX_TRY(hook_copy(c, l, c->shRadiance.p, rad.data(), 16, true));
         NX_HIP(hipMemsetAsync(c->h.radiance, 0, (size_t)n * 16, c->stream));  // the buffer the kernel adds into (own or bound)
-        NX_TRY(run_trace_chunk(c, true, n));
+        NX_TRY(run_trace_chunk(c, true, n, transmittance != nullptr));
         NX_HIP(hipMemcpyAsync(res.data(), c->h.radiance, (size_t)n * 16, hipMemcpyDeviceToHost, c->stream));
         NX_SYNC_ALL(c);
-        for (uint32_t i = 0; i < n; i++) occluded[first + i] = res[i].x == 1.0f ? 0 : 1;
+        for (uint32_t i = 0; i < n; i++) {
+            if (transmittance) transmittance[first + i] = res[i].x;  // (radiance 1 into a zeroed buffer: .x is T)
+            else occluded[first + i] = res[i].x == 1.0f ? 0 : 1;
+        }
     }
     return NXHIP_OK;
+}
+
+int nxhip_trace_shadow_batch(nxhip_ctx* c, const nx_ray* rays, const float* tmax, uint32_t count, uint8_t* occluded)
+try {
+    return shadow_batch(c, "nxhip_trace_shadow_batch", rays, tmax, count, occluded, nullptr);
 } NX_CATCH("nxhip_trace_shadow_batch")
+
+int nxhip_trace_transmittance_batch(nxhip_ctx* c, const nx_ray* rays, const float* tmax, uint32_t count, float* transmittance)
+try {
+    return shadow_batch(c, "nxhip_trace_transmittance_batch", rays, tmax, count, nullptr, transmittance);
+} NX_CATCH("nxhip_trace_transmittance_batch")
 
 int nxhip_enable_trace_stats(nxhip_ctx* c, int enable)
 {

@@ -129,8 +129,14 @@ int trace_blocks(const nxhip_ctx* c, int fullGrid)
 //     driver's 20-frame job is such a pass (rank of 4: 8.65 -> 8.2 ms).
 // Larger passes lose (12 frames +-1 %, 20 frames -2 % from bounce 6 and -3 % from 5, 64 frames -7 %: a wave of the tail kernel keeps
 // 64 lanes for as long as its longest path, and there the level-by-level launches are already amortised).
+// NXHIP_SHADOWS_TRANSMIT takes effect in a pass (kFlavorTransmit, below): the mode is on AND some material of the table is see-through.
+bool transmit_active(const nxhip_ctx* c) { return c->shadowTransmittance == NXHIP_SHADOWS_TRANSMIT && c->materialsSeeThrough; }
+
 int tail_bounce(const nxhip_ctx* c)
 {
+    // (the tail kernel traces its shadow rays with traverse_wave<true>, which knows no transmittance: a first version's restriction,
+    //  DESIGN.md section 4 — the setting is ignored while the mode is in effect)
+    if (transmit_active(c)) return 0;
     int bounce = c->tailBounce;
     if (bounce < 0) {
         const double frames = pass_size_in_frames(c);
@@ -168,6 +174,11 @@ constexpr int kFlavorSpecialised = kFlavorIdentity | kFlavorNoMaps;
 // one-item logic kernel are their ANALYTIC instances (nx_wavefront.hip), whose light sample picks among them too.  Not a specialisation
 // a test may switch off: the default instances do not know such lights.  Without any the bit is clear and the graphs are the default ones.
 constexpr int kFlavorAnalytic = 1024;
+// kFlavorTransmit: nxhip_set_shadow_transmittance(NXHIP_SHADOWS_TRANSMIT) over a material table with a see-through material — the any-hit
+// launches are the TRANSMIT instance (nx_trace.hip), without the hand-over to the thin kernel and without a thin launch of their own
+// (a wave-wide search multiplies in an order of its own; frames must be reproducible), and there is no tail kernel (tail_bounce).  A
+// TRANSMIT context over an all-opaque table keeps the bit clear and launches the default kernels.
+constexpr int kFlavorTransmit = 2048;
 int pass_flavor(const nxhip_ctx* c)
 {
     int f = 0;
@@ -200,6 +211,7 @@ int pass_flavor(const nxhip_ctx* c)
     if ((c->h.sceneFlags & kSceneAllIdentity) && !c->statsEnabled) f |= kFlavorIdentity;  // (the counting variants have no such instance)
     if (scan_pipeline(c) && !c->materialsNameMaps && !(f & kFlavorEnvMap)) f |= kFlavorNoMaps;
     if (c->h.alightCount) f |= kFlavorAnalytic;
+    if (transmit_active(c)) f |= kFlavorTransmit;
     return f & ~(c->flavorForceGeneral & kFlavorSpecialised);  // (test hook: nxhip_debug_pass_flavor)
 }
 
@@ -219,6 +231,12 @@ std::vector<std::vector<Launch>> frame_levels(nxhip_ctx* c, PassSlot* q)
     const bool lightPower = (pass_flavor(c) & kFlavorLightPower) != 0;
     const bool identity = (pass_flavor(c) & kFlavorIdentity) != 0, noMaps = (pass_flavor(c) & kFlavorNoMaps) != 0;
     const bool analytic = (pass_flavor(c) & kFlavorAnalytic) != 0;
+    const bool transmit = (pass_flavor(c) & kFlavorTransmit) != 0;
+    // the any-hit launch of a bounce: the TRANSMIT instance never hands over (no kTraceThinFlag) and has no IDENTITY form
+    auto shadow_launch = [&](int shadowBlocksArg, int bounceArg, int thinFlagArg) {
+        return transmit ? make_launch(kernels::trace_transmit(stats), shadowBlocksArg, kTraceBlockThreads, NXHIP_K_SHADOW, S, bounceArg)
+                        : make_launch(kernels::trace(true, stats, identity), shadowBlocksArg, kTraceBlockThreads, NXHIP_K_SHADOW, S, bounceArg | thinFlagArg);
+    };
     const int traceBlocks = trace_blocks(c, c->traceBlocks), shadowBlocks = trace_blocks(c, c->shadowBlocks);
     // (the dry waves of a pass's trace launches may hand their last long rays to the thin kernel: nx_trace.hip)
     const int thinFlag = (pass_flavor(c) & kFlavorThin) ? kTraceThinFlag : 0;
@@ -236,6 +254,7 @@ std::vector<std::vector<Launch>> frame_levels(nxhip_ctx* c, PassSlot* q)
         std::vector<Launch>& level = levels.back();
         const int n = (int)level.size();  // 1: the primary level (closest-hit only); 2: closest-hit, any-hit
         for (int k = 0; k < n; k++) {
+            if (k == 1 && transmit) continue;  // (no kThinAnyOnly launch: the TRANSMIT any-hit launch lists nothing)
             Launch t = make_launch(kernels::thin(), thinBlocks, kTraceBlockThreads, NXHIP_K_THIN, S, bounceArg | (k == 0 ? kThinClosestOnly : kThinAnyOnly));
             t.after = k;
             level.push_back(t);
@@ -279,7 +298,7 @@ std::vector<std::vector<Launch>> frame_levels(nxhip_ctx* c, PassSlot* q)
                 levels.push_back({make_launch(kernels::count_scan(), lg, kWideBlockThreads, NXHIP_K_LOGIC, S, bounce, NX_MAT_CONDUCTOR)});
             }
             levels.push_back({make_launch(kernels::trace(false, stats, identity), traceBlocks, kTraceBlockThreads, NXHIP_K_TRACE, S, bounce | kTraceScanFlag | thinFlag),
-                              make_launch(kernels::trace(true, stats, identity), shadowBlocks, kTraceBlockThreads, NXHIP_K_SHADOW, S, bounce | thinFlag)});
+                              shadow_launch(shadowBlocks, bounce, thinFlag)});
             thin_level(bounce | kTraceScanFlag);
         }
         return levels;
@@ -305,7 +324,7 @@ std::vector<std::vector<Launch>> frame_levels(nxhip_ctx* c, PassSlot* q)
         // serial slot order needs the kernels one after the other
         for (auto& l : shade) levels.push_back({l});
         levels.push_back({make_launch(kernels::trace(false, stats, identity), traceBlocks, kTraceBlockThreads, NXHIP_K_TRACE, S, bounce | thinFlag),
-                          make_launch(kernels::trace(true, stats, identity), shadowBlocks, kTraceBlockThreads, NXHIP_K_SHADOW, S, bounce | thinFlag)});
+                          shadow_launch(shadowBlocks, bounce, thinFlag)});
         thin_level(bounce);
     }
     return levels;
@@ -634,6 +653,16 @@ int nxhip_accumulate(nxhip_ctx* c)
 // Tail kernel: from `bounce` on (2 .. pathLength; 0 = off; NXHIP_TAIL_AUTO = the default) every path is finished by one launch
 // instead of a graph level per kernel and bounce.  Takes effect with pixel-keyed random numbers and the workgroup-aggregated
 // compaction only.
+int nxhip_set_shadow_transmittance(nxhip_ctx* c, int mode)
+{
+    NX_CHECK_CTX(c);
+    if (mode != NXHIP_SHADOWS_OPAQUE && mode != NXHIP_SHADOWS_TRANSMIT) return fail_invalid("nxhip_set_shadow_transmittance: unknown mode");
+    // (frames accumulated so far stay.  The pass graphs are keyed by the mode's effect — pass_flavor's kFlavorTransmit, tail_bounce —
+    //  so the next pass picks or builds the matching instance; nothing the kernels read changes)
+    c->shadowTransmittance = mode;
+    return NXHIP_OK;
+}
+
 int nxhip_set_tail_bounce(nxhip_ctx* c, uint32_t bounce)
 {
     NX_CHECK_CTX(c);

@@ -65,6 +65,23 @@ static int refresh_blas_table(nxhip_ctx* c)
 // The shading records of the instances (nx_device.h ShadeInst) from the instance, BLAS and material tables.  Called before a
 // render when one of them has changed (shadeInstDirty); the cross-table indices have been checked by then (check_scene_ready).
 // The matrices come from the DEVICE's instance table: nxhip_set_instance_transforms computes the inverses there.
+// See-through for a shadow ray of NXHIP_SHADOWS_TRANSMIT (include/nexus_hip.h): `opacity < 1` — a NaN opacity is opaque, as in the
+// material kernel — or a diffuse map that has a texel with alpha < 255.  (A map id without its texture: opaque by the map; no pass
+// or hook launches with such a table — check_scene_ready.)
+bool nxd::material_see_through(const nxhip_ctx* c, const nx_material& m)
+{
+    if (m.opacity < 1.0f) return true;
+    return m.diffuseMapId >= 0 && (size_t)m.diffuseMapId < c->diffuseMaps.size() && c->diffuseMaps[(size_t)m.diffuseMapId].hasAlpha;
+}
+
+// After anything that can change the answer above: the material table, a diffuse texture upload, nxhip_clear_textures.
+void nxd::refresh_see_through(nxhip_ctx* c)
+{
+    c->materialsSeeThrough = false;
+    for (const nx_material& m : c->hostMaterials) c->materialsSeeThrough = c->materialsSeeThrough || material_see_through(c, m);
+    c->shadeInstDirty = true;  // (ShadeInst::seeThrough)
+}
+
 int nxd::refresh_shade_inst(nxhip_ctx* c)
 {
     const size_t n = c->hostInstances.size();
@@ -84,6 +101,7 @@ int nxd::refresh_shade_inst(nxhip_ctx* c)
         rec[i].triCount = b.triCount;
         rec[i].materialId = in.materialId;
         rec[i].material = c->hostMaterialsDev[(size_t)in.materialId];
+        rec[i].seeThrough = material_see_through(c, rec[i].material) ? 1u : 0u;
     }
     NX_ALLOC(c->shadeInst, rec.size() * sizeof(ShadeInst));
     NX_HIP(hipMemcpy(c->shadeInst.p, rec.data(), rec.size() * sizeof(ShadeInst), hipMemcpyHostToDevice));
@@ -798,7 +816,7 @@ try {
     c->materialsNameMaps = false;  // (the table as it is now, not what has been uploaded: a material may name a map id before its texture exists)
     for (const nx_material& m : dev) c->materialsNameMaps = c->materialsNameMaps || m.diffuseMapId != -1 || m.emissiveMapId != -1;
     c->stateDirty = true;
-    c->shadeInstDirty = true;  // (the records hold a copy of their instance's material)
+    refresh_see_through(c);    // (sets shadeInstDirty: the records hold a copy of their instance's material)
     c->lightTableDirty = true;
     uint32_t mask = 0u;
     for (const nx_material& m : dev)
@@ -1067,7 +1085,12 @@ try {
     NX_ALLOC(t.texels, (size_t)width * height * 4);
     NX_HIP(hipMemcpy(t.texels.p, rgba8, (size_t)width * height * 4, hipMemcpyHostToDevice));
     int32_t id = 0;
-    if (kind == 0) { c->diffuseMaps.push_back(std::move(t)); id = (int32_t)c->diffuseMaps.size() - 1; }
+    if (kind == 0) {
+        for (size_t i = 0; i < (size_t)width * height && !t.hasAlpha; i++) t.hasAlpha = rgba8[4 * i + 3] != 255u;
+        c->diffuseMaps.push_back(std::move(t));
+        id = (int32_t)c->diffuseMaps.size() - 1;
+        refresh_see_through(c);  // (a material may have named this id before its texture existed)
+    }
     else if (kind == 1) { c->emissiveMaps.push_back(std::move(t)); id = (int32_t)c->emissiveMaps.size() - 1; c->lightTableDirty = true; }
     else {
         NX_SYNC_ALL(c);
@@ -1115,6 +1138,7 @@ try {
     NX_SYNC_ALL(c);
     c->diffuseMaps.clear();
     c->emissiveMaps.clear();
+    refresh_see_through(c);
     c->lightMapMeans = 0;
     c->lightTableDirty = true;
     c->hdrMap = TextureHost();

@@ -47,6 +47,8 @@ def checker_texture(w=64, h=32, seed=0, alpha=False):
 class Workload:
     # extension: pod.LIGHTS_POWER picks the mesh lights' triangles by area x emitted luminance (nxhip_set_light_sampling); applied by upload
     light_sampling = pod.LIGHTS_UNIFORM
+    # extension: pod.SHADOWS_TRANSMIT lets opacity and texture alpha attenuate shadow rays (nxhip_set_shadow_transmittance); applied by upload
+    shadow_transmittance = pod.SHADOWS_OPAQUE
 
     def __init__(self, meshes, placements, materials=None, lights=None, camera=None, settings=None, diffuse_maps=(), emissive_maps=(),
                  hdr_map=None, build_threads=4):
@@ -123,6 +125,7 @@ class Workload:
             ctx.set_camera(self.camera)
         ctx.set_render_settings(self.settings)
         ctx.set_light_sampling(self.light_sampling)
+        ctx.set_shadow_transmittance(self.shadow_transmittance)
 
 
 def _look(eye, target, hfov, width, height):
