@@ -51,6 +51,9 @@ $(OBJDIR)/%.o: %.hip $(HDRS)
 	@mkdir -p $(dir $@)
 	$(HIPCC) $(DEVFLAGS) -c $< -o $@
 
+# (the DETAIL instances are compiled from the kernel templates of nx_wavefront.hip, which that unit includes)
+$(OBJDIR)/nexus_amd/csrc/device/nx_wavefront_detail.o: nexus_amd/csrc/device/nx_wavefront.hip
+
 $(OBJDIR)/%.o: %.cpp $(HDRS)
 	@mkdir -p $(dir $@)
 	$(HIPCC) $(HOSTFLAGS) -c $< -o $@

@@ -2,6 +2,7 @@
 // through the kept C++ host API: load a .glb / .obj, path-trace `frames` frames on an MI355X, write the image as a PPM.
 //
 //   nexus_render [--denoise] [--adaptive THRESHOLD [--max-frames N]] [--light-sampling uniform|power] [--transparent-shadows] [--env-float FILE.hdr] [--env-sampling]
+//                [--no-detail-maps]
 //                [--point-light X Y Z INTENSITY] [--sun DX DY DZ IRRADIANCE] <dir/> <file.glb|file.obj> <out.ppm> [width height frames pathLength]
 //                [eyeX eyeY eyeZ fwdX fwdY fwdZ hfovDeg]
 // --denoise: the feature buffers are accumulated with the colour and the image written is the a-trous filtered one (nxhip_denoise)
@@ -16,6 +17,8 @@
 //   nxhip_upload_env_float) instead of the 8 bits "Load HDR map" reduces it to.
 // --env-sampling: the light sample may pick the environment map (nxhip_set_env_sampling): what a map with a small bright sun needs.
 // A .glb's KHR_lights_punctual lights (point, spot, directional) are rendered as the file places them, without a flag.
+// A .glb's normalTexture and metallicRoughnessTexture (its G channel: roughness) are used as the file's materials name them, without a flag.
+// --no-detail-maps: drop them (AssetManager::ClearMaterialDetails), for an A/B against the flat, uniformly glossy surfaces.
 // --point-light X Y Z INTENSITY: one more white point light at (X, Y, Z), radiant intensity INTENSITY per steradian (Scene::AddAnalyticLight).
 // --sun DX DY DZ IRRADIANCE: a white sun whose light travels along (DX, DY, DZ), irradiance IRRADIANCE on a surface facing it.
 //
@@ -40,6 +43,7 @@ int main(int argc, char** argv)
     bool transparentShadows = false;
     std::string envFloat;
     bool envSampling = false;
+    bool detailMaps = true;
     std::vector<nexus::AnalyticLight> extraLights;
     for (;;) {  // leading options, in any order
         const std::string opt = argc > 1 ? argv[1] : "";
@@ -71,6 +75,9 @@ int main(int argc, char** argv)
         } else if (opt == "--env-sampling") {
             envSampling = true;
             used = 1;
+        } else if (opt == "--no-detail-maps") {
+            detailMaps = false;
+            used = 1;
         } else if ((opt == "--point-light" || opt == "--sun") && argc > 5) {
             nexus::AnalyticLight l;
             const bool sun = opt == "--sun";
@@ -86,7 +93,7 @@ int main(int argc, char** argv)
         argc -= used;
     }
     if (argc < 4) {
-        std::fprintf(stderr, "usage: %s [--denoise] [--adaptive THRESHOLD [--max-frames N]] [--light-sampling uniform|power] [--transparent-shadows] [--env-float FILE.hdr] [--env-sampling] [--point-light X Y Z INTENSITY] [--sun DX DY DZ IRRADIANCE] <dir/> <file.glb|file.obj> <out.ppm> [width height frames pathLength] [eye(3) forward(3) hfov]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s [--denoise] [--adaptive THRESHOLD [--max-frames N]] [--light-sampling uniform|power] [--transparent-shadows] [--env-float FILE.hdr] [--env-sampling] [--no-detail-maps] [--point-light X Y Z INTENSITY] [--sun DX DY DZ IRRADIANCE] <dir/> <file.glb|file.obj> <out.ppm> [width height frames pathLength] [eye(3) forward(3) hfov]\n", argv[0]);
         return 2;
     }
     // a program built against these headers and run with another build of libnexus_amd.so gets an error string here, not a GPU fault
@@ -114,6 +121,7 @@ int main(int argc, char** argv)
             scene.SetDeviceTlasBuild(true);
         }
         scene.CreateMeshInstanceFromFile(dir, file);  // (a .glb's KHR_lights_punctual lights come with it)
+        if (!detailMaps) scene.GetAssetManager().ClearMaterialDetails();  // (the file's normal and roughness maps: loaded, not used)
         for (const nexus::AnalyticLight& l : extraLights) scene.AddAnalyticLight(l);
         scene.GetCamera()->LookAt(nexus::make_float3(cam[0], cam[1], cam[2]), nexus::make_float3(cam[3], cam[4], cam[5]));
         scene.GetCamera()->SetHorizontalFOV(cam[6]);

@@ -47,8 +47,21 @@ struct AnalyticLight : nx_analytic_light {
 };
 static_assert(sizeof(AnalyticLight) == sizeof(nx_analytic_light), "AnalyticLight must alias nx_analytic_light");
 
+// Extension: the detail maps of one material (nx_material_detail of nexus_pod.h; the shading rule: nexus_hip.h).  Ids are those
+// AssetManager::AddTexture returned for a NORMAL / a ROUGHNESS texture; -1: none.  AssetManager::SetMaterialDetail attaches one to a material.
+struct MaterialDetail : nx_material_detail {
+    MaterialDetail()
+    {
+        normalMapId = roughnessMapId = -1;
+        normalScale = 1.0f;
+        pad_ = 0u;
+    }
+};
+static_assert(sizeof(MaterialDetail) == sizeof(nx_material_detail), "MaterialDetail must alias nx_material_detail");
+
 struct Texture {
-    enum struct Type { DIFFUSE, ROUGHNESS, METALLIC, EMISSIVE };
+    // (NORMAL and ROUGHNESS hold linear data: a tangent-space normal map; glTF's metallic-roughness image, whose G channel is read)
+    enum struct Type { DIFFUSE, ROUGHNESS, METALLIC, EMISSIVE, NORMAL };
     Texture() = default;
     Texture(uint32_t w, uint32_t h, uint32_t c, const unsigned char* d) : width(w), height(h), channels(c), pixels(d, d + static_cast<size_t>(w) * h * 4) {}
     uint32_t width = 0, height = 0, channels = 0;
@@ -124,7 +137,15 @@ public:
     std::vector<BVH8>& GetBVHs() { return m_Bvhs; }
     const std::vector<BVH8>& GetBVHs() const { return m_Bvhs; }
     std::vector<Mesh>& GetMeshes() { return m_Meshes; }
-    int AddTexture(const Texture& texture);  // -1 if it has no pixels; id within its kind (diffuse / emissive)
+    int AddTexture(const Texture& texture);  // -1 if it has no pixels; id within its kind (diffuse / emissive / normal / roughness)
+    // Extension: the detail maps of material `materialId` (throws on an id that does not exist).  GetMaterialDetails: one record per
+    // material, in the materials' order — empty while no material was ever given one, or after ClearMaterialDetails (the device then
+    // has no table at all: PathTracer::UpdateDeviceScene sends count 0).
+    void SetMaterialDetail(int materialId, const MaterialDetail& detail);
+    void ClearMaterialDetails();
+    std::vector<MaterialDetail> GetMaterialDetails() const;
+    const std::vector<Texture>& GetNormalMaps() const { return m_NormalMaps; }
+    const std::vector<Texture>& GetRoughnessMaps() const { return m_RoughnessMaps; }
     void ApplyTextureToMaterial(int materialId, int diffuseMapId);
     const std::vector<Texture>& GetDiffuseMaps() const { return m_DiffuseMaps; }
     const std::vector<Texture>& GetEmissiveMaps() const { return m_EmissiveMaps; }
@@ -132,7 +153,7 @@ public:
     bool IsInvalid() const { return !m_InvalidMaterials.empty() || !m_DeformedBvhs.empty(); }
 
     // what the device still has to receive (consumed by PathTracer::UpdateDeviceScene)
-    bool materialsDirty = true, texturesDirty = true;
+    bool materialsDirty = true, texturesDirty = true, detailsDirty = false;
     size_t uploadedBvhs = 0;
     std::set<int32_t> deformedBvhs;  // changed by UpdateMeshTriangles and not yet sent through nxhip_update_blas
 
@@ -141,6 +162,8 @@ private:
     std::set<uint32_t> m_InvalidMaterials;
     std::set<int32_t> m_DeformedBvhs;
     std::vector<Texture> m_DiffuseMaps, m_EmissiveMaps;
+    std::vector<Texture> m_NormalMaps, m_RoughnessMaps;
+    std::vector<MaterialDetail> m_MaterialDetails;  // sparse: shorter than m_Materials while later materials have none
     std::vector<BVH8> m_Bvhs;
     std::vector<Mesh> m_Meshes;
     BlasBuilder m_BlasBuilder;

@@ -31,6 +31,12 @@ struct LoadedScene {
     // materials' diffuseMapId / emissiveMapId stay -1 here: ids are handed out by the AssetManager in LoadOBJ.
     std::vector<Texture> textures;
     std::vector<int> materialDiffuseTexture, materialEmissiveTexture;
+    // Detail maps (glTF normalTexture and pbrMetallicRoughness.metallicRoughnessTexture -> NORMAL, ROUGHNESS: linear data), in a list of
+    // their own — `textures` and its order are what they were — and per material the index into it (-1: none) and normalTexture.scale.
+    // texCoord sets other than 0 and KHR_texture_transform are not carried: the map is used with set 0 as it is, with a warning.
+    std::vector<Texture> detailTextures;
+    std::vector<int> materialNormalTexture, materialRoughnessTexture;
+    std::vector<float> materialNormalScale;
     std::vector<AnalyticLight> analyticLights;  // glTF KHR_lights_punctual: one per node that carries a light, in world space
     std::vector<std::string> warnings;  // images that could not be decoded (the reference prints and carries on, IMGLoader.cpp:24-25)
 };

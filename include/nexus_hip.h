@@ -194,10 +194,50 @@ int nxhip_set_lights(nxhip_ctx *ctx, const nx_light *lights, uint32_t count);
  * A included.
  * The kernels that know these lights are compile-time instances launched only while A > 0 (bit 10 of nxhip_debug_pass_flavor's word). */
 int nxhip_set_analytic_lights(nxhip_ctx *ctx, const nx_analytic_light *lights, uint32_t count);
-/* Texture::ToDevice — Assets/Texture.cpp:10-39 (RGBA8, sRGB, wrap, bilinear).  kind: 0 diffuse, 1 emissive, 2 hdr map.
- * Diffuse/emissive maps get ids in upload order; the hdr map replaces the previous one. */
+/* Texture::ToDevice — Assets/Texture.cpp:10-39 (RGBA8, sRGB, wrap, bilinear).  kind: 0 diffuse, 1 emissive, 2 hdr map, and — an
+ * extension, see nxhip_set_material_detail — 3 normal map, 4 roughness map (RGBA8 holding LINEAR data: no sRGB decode).
+ * Diffuse, emissive, normal and roughness maps get ids in upload order, counted per kind; the hdr map replaces the previous one.
+ * nxhip_clear_textures removes the maps of every kind. */
 int nxhip_upload_texture(nxhip_ctx *ctx, int kind, const uint8_t *rgba8, uint32_t width, uint32_t height, int32_t *texId);
 int nxhip_clear_textures(nxhip_ctx *ctx);
+/* Extension — detail maps: a tangent-space normal map and a roughness map per material (glTF normalTexture and the G channel of
+ * pbrMetallicRoughness.metallicRoughnessTexture).  `details` is index-parallel to the material table (nx_material_detail of nexus_pod.h:
+ * normalMapId, roughnessMapId — ids of nxhip_upload_texture kind 3 / 4, -1 = none — and normalScale); the call replaces the table; count 0
+ * removes it, and the context is then exactly what it was before the first call (the same flavor word, the same frames bit for bit).  So
+ * is a context whose table names no map at all.
+ *
+ * Validation — NXHIP_ERR_INVALID and the previous table stays in place: details NULL with count > 0; an id below -1; a normalScale that is
+ * not finite.  A render (and every hook that reads the shading records) refuses, next to the checks of the diffuse and emissive ids: a
+ * table whose count differs from the material count; an id with no uploaded texture.
+ *
+ * THE SHADING RULE.
+ *   lookup     tex2d_linear: the addressing (normalised coordinates, wrap, texel centres at +0.5) and the 1/256 bilinear weights of the
+ *              diffuse maps' lookup; every channel is byte / 255.0f, there is no sRGB table.  Texture coordinate set 0, at the hit.
+ *   roughness  only if the material names a roughness map: roughness := roughness x g, g = the lookup's G channel (glTF's assignment),
+ *              before the BSDF sees it.  No effect on NX_MAT_DIFFUSE.
+ *   normal     only if the material names a normal map, and only where a path is continued (bounce != pathLength): there ns takes the
+ *              place of the interpolated normal in the shading frame, in the light sample and in the signs of the ray offsets (the
+ *              offsets themselves stay along the geometric normal).  The MIS weight of an emissive hit keeps the interpolated normal,
+ *              and so does the light sample OF an emitter.
+ *              N = the interpolated world normal before the back-face flip; c = the lookup; s = normalScale;
+ *                m = ((2 c.r - 1) s, (2 c.g - 1) s, 2 c.b - 1).
+ *              Object space, per triangle: e1 = p1 - p0, e2 = p2 - p0, (du1, dv1) = uv1 - uv0, (du2, dv2) = uv2 - uv0,
+ *                det = du1 dv2 - du2 dv1,  Tu = (e1 dv2 - e2 dv1) sgn(det),  Tv = (e2 du1 - e1 du2) sgn(det).
+ *              World space: Tu_w, Tv_w = the instance's forward 3 x 3 applied to Tu, Tv as vectors.
+ *              Frame: t = normalize(Tu_w - N (N . Tu_w));  b = +-cross(N, t) with the sign that makes b . (-Tv_w) >= 0 — glTF's v runs down
+ *              the image and green points up; mirrored UVs and mirroring transforms need no case of their own.
+ *              ns = normalize(t m.x + b m.y + N m.z); then the existing flip (dot(gNormal, rayDirection) > 0 and the material is not a
+ *              DIELECTRIC) negates ns as it negates N and gNormal.
+ *   fallback   ns := N when: !(|det| > 0); the projected tangent is not finite or has length 0; ns is not finite or has length 0; or, with
+ *              v = -rayDirection, (ns . v)(N . v) <= 0 — the view is below the mapped horizon.  One rule for all four material types.
+ * Tangents are per triangle, from positions and UVs: the 96-byte triangle has no room for glTF's TANGENT attribute.
+ * Out of scope: vertex TANGENT attributes; per-texel metalness (the material type picks the queue before any lookup — metallicFactor and
+ * the B channel stay unused); the AOV normal and the denoiser's normal term keep the interpolated normal; .mtl bump maps; mip-mapping;
+ * texCoord sets other than 0 and KHR_texture_transform (the loaders warn).  The closest-hit and any-hit kernels and the feature buffers do
+ * not change.
+ * The kernels that know these maps are compile-time instances launched only while some material names one (bit 12 of
+ * nxhip_debug_pass_flavor's word); they imply the general material launch. */
+int nxhip_set_material_detail(nxhip_ctx *ctx, const nx_material_detail *details, uint32_t count);
 /* Extension: a FLOAT environment map — linear radiance, nothing clamped to 1 (the RGBA8 map above runs through the sRGB table: no
  * texel brighter than 1, a sun 10^5 times the sky arrives as a dot 50 times the sky).  rgb = width x height x 3 floats, row 0 the
  * top row (d.y = +1); orientation and the (u, v) of a direction are the RGBA8 map's.  The array is copied before the call returns.
@@ -610,6 +650,15 @@ int nxhip_bsdf_eval_batch(nxhip_ctx *ctx, const nx_material *material, const nx_
  * rgba = 4*count floats (sRGB-decoded, bilinear, wrap addressing: what the shade kernels see).  kind 2 on a float environment map
  * (nxhip_upload_env_float): that map's own lookup, linear, alpha 1. */
 int nxhip_tex2d_batch(nxhip_ctx *ctx, int kind, int textureId, const float *uv, uint32_t count, float *rgba);
+/* (kind 3 / 4: a normal / roughness map through tex2d_linear — linear, every channel byte / 255) */
+/* The detail maps' rule on arrays — a test hook over the device function the material kernels call (a `make release` library refuses
+ * it): for every k < count, the hit on triangle triIdx[k] of instance `instanceIdx` at barycentrics hitUv[2k..] (the hit record's u, v),
+ * reached along rayDir[3k..]: normalOut[3k..] = the world-space shading normal after fallback and flip (the interpolated normal, flipped,
+ * when the material names no normal map), roughnessOut[k] = the roughness handed to the BSDF, fellBack[k] = 1 when a normal map was named
+ * and a fallback condition took ns back to N.  NXHIP_ERR_INVALID: a NULL array, no such instance, a triangle index out of range, a scene
+ * a render would refuse. */
+int nxhip_shading_frame_batch(nxhip_ctx *ctx, uint32_t instanceIdx, const uint32_t *triIdx, const float *hitUv, const float *rayDir, uint32_t count,
+                              float *normalOut, float *roughnessOut, uint32_t *fellBack);
 
 /* Test hooks of the light table (NXHIP_LIGHTS_POWER only, else NXHIP_ERR_INVALID; both bring the table up to date first).
  * read: cdf / entryLight (either may be NULL) hold `capacity` entries, lightBase (may be NULL) lightCount + 1 words; *entries = N.
@@ -733,6 +782,7 @@ static inline uint64_t nxhip_header_abi_stamp(void)
         sizeof(nx_bvh_instance), offsetof(nx_bvh_instance, transform), offsetof(nx_bvh_instance, materialId),
         sizeof(nx_material), offsetof(nx_material, emissive), offsetof(nx_material, type), sizeof(nx_light), offsetof(nx_light, type),
         sizeof(nx_analytic_light), offsetof(nx_analytic_light, direction), offsetof(nx_analytic_light, colour), offsetof(nx_analytic_light, innerConeAngle), offsetof(nx_analytic_light, type),
+        sizeof(nx_material_detail), offsetof(nx_material_detail, normalScale),
         sizeof(nx_camera), offsetof(nx_camera, resolution), sizeof(nx_render_settings), offsetof(nx_render_settings, backgroundColor),
         sizeof(nx_ray), sizeof(nx_hit), sizeof(nx_bsdf_query), sizeof(nx_bsdf_result), offsetof(nx_bsdf_result, rngOut),
         sizeof(nxhip_queue_sizes), sizeof(nxhip_trace_stats), offsetof(nxhip_trace_stats, cycles), sizeof(nxhip_kernel_times), NXHIP_K_COUNT,

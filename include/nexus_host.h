@@ -87,6 +87,13 @@ int nxh_loaded_material_textures(const nxh_loaded_scene *s, int32_t *diffuseText
  * `range` is ignored.  dst receives nxh_loaded_analytic_light_count records. */
 uint32_t nxh_loaded_analytic_light_count(const nxh_loaded_scene *s);
 int nxh_loaded_analytic_lights(const nxh_loaded_scene *s, nx_analytic_light *dst);
+/* Detail maps (glTF normalTexture -> kind 3, pbrMetallicRoughness.metallicRoughnessTexture -> kind 4: linear data, the kinds of
+ * nxhip_upload_texture), a list of their own beside the one above.  Per material the index of its normal / roughness texture in THIS
+ * list (-1: none) and normalTexture.scale (1 without one).  texCoord sets other than 0 and KHR_texture_transform produce a warning. */
+uint32_t nxh_loaded_detail_texture_count(const nxh_loaded_scene *s);
+int nxh_loaded_detail_texture_info(const nxh_loaded_scene *s, uint32_t index, uint32_t *width, uint32_t *height, int32_t *kind);
+int nxh_loaded_detail_texture_pixels(const nxh_loaded_scene *s, uint32_t index, uint8_t *dstRgba8);
+int nxh_loaded_material_detail(const nxh_loaded_scene *s, int32_t *normalTexture, int32_t *roughnessTexture, float *normalScale);
 uint32_t nxh_loaded_warning_count(const nxh_loaded_scene *s);
 const char *nxh_loaded_warning(const nxh_loaded_scene *s, uint32_t index);
 /* IMGLoader::LoadIMG (Assets/IMGLoader.cpp:17-41: stbi_load with 4 channels) for PNG data: RGBA8, row 0 first.
@@ -101,7 +108,7 @@ const char *nxs_last_error(void);
 int nxs_scene_create(uint32_t width, uint32_t height, nxs_scene **out);
 void nxs_scene_destroy(nxs_scene *s);
 int nxs_scene_add_material(nxs_scene *s, const nx_material *m, int32_t *materialId);
-int nxs_scene_add_texture(nxs_scene *s, int kind /*0 diffuse, 1 emissive*/, const uint8_t *rgba8, uint32_t w, uint32_t h, int32_t *texId);
+int nxs_scene_add_texture(nxs_scene *s, int kind /*0 diffuse, 1 emissive, 3 normal, 4 roughness*/, const uint8_t *rgba8, uint32_t w, uint32_t h, int32_t *texId);
 int nxs_scene_set_hdr_map(nxs_scene *s, const uint8_t *rgba8, uint32_t w, uint32_t h);
 /* Extension — Scene::AddHDRMapFloat(width, height, rgb): the environment as w x h x 3 floats of linear radiance, row 0 the top row
  * (nxhip_upload_env_float at the next device update).  Either kind of map replaces the other. */
@@ -136,6 +143,12 @@ uint32_t nxs_scene_light_count(const nxs_scene *s);
  * the next device update (nxhip_set_analytic_lights, which validates them).  nxs_scene_load_file adds a .glb's KHR_lights_punctual lights.
  * *index (may be NULL) = the light's place in the list; nxs_scene_analytic_lights copies up to `capacity` records out. */
 int nxs_scene_add_analytic_light(nxs_scene *s, const nx_analytic_light *light, uint32_t *index);
+/* AssetManager::SetMaterialDetail / ClearMaterialDetails / GetMaterialDetails: the detail maps of a material (ids of nxs_scene_add_texture
+ * kind 3 / 4); the list is empty while no material has any, else one record per material. */
+int nxs_scene_set_material_detail(nxs_scene *s, int32_t materialId, const nx_material_detail *detail);
+int nxs_scene_clear_material_details(nxs_scene *s);
+uint32_t nxs_scene_material_detail_count(const nxs_scene *s);
+int nxs_scene_material_details(const nxs_scene *s, nx_material_detail *dst, uint32_t capacity);
 int nxs_scene_remove_analytic_light(nxs_scene *s, uint32_t index);
 uint32_t nxs_scene_analytic_light_count(const nxs_scene *s);
 int nxs_scene_analytic_lights(const nxs_scene *s, nx_analytic_light *dst, uint32_t capacity);

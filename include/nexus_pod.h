@@ -11,6 +11,7 @@
  *   nx_material      60 B  Cuda/Scene/Material.cuh:5-51
  *   nx_light         12 B  Cuda/Scene/Light.cuh:4-33
  *   (nx_analytic_light 64 B: an extension, no reference layout)
+ *   (nx_material_detail 16 B: an extension, no reference layout)
  *   nx_camera        88 B  Cuda/Scene/Camera.cuh:5-15
  *   nx_render_settings 20 B Cuda/Scene/Scene.cuh:10-17, Renderer/RenderSettings.h:4-10
  */
@@ -104,6 +105,16 @@ typedef struct NX_ALIGN(16) nx_analytic_light {
     uint32_t type, pad_;
 } nx_analytic_light;
 NX_STATIC_ASSERT(sizeof(nx_analytic_light) == 64, "nx_analytic_light must be 64 bytes");
+
+/* Extension: the detail maps of one material (nxhip_set_material_detail; the shading rule is stated in full in include/nexus_hip.h).
+ * A table of these runs index-parallel to the material table: the 60-byte nx_material keeps the reference's layout.  Ids are those
+ * nxhip_upload_texture returned for kind 3 (normal) and kind 4 (roughness); -1 = none. */
+typedef struct nx_material_detail {
+    int32_t normalMapId, roughnessMapId;
+    float normalScale;  /* glTF normalTexture.scale: multiplies the x and y of the decoded normal */
+    uint32_t pad_;
+} nx_material_detail;
+NX_STATIC_ASSERT(sizeof(nx_material_detail) == 16, "nx_material_detail must be 16 bytes");
 
 typedef struct NX_ALIGN(8) nx_camera {
     float position[3];

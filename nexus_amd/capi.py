@@ -37,6 +37,7 @@ HIP_SYMBOLS = [
     "nxhip_set_analytic_lights", "nxhip_analytic_light_sample_batch",
     "nxhip_debug_read_primary_rays",
     "nxhip_set_shadow_transmittance", "nxhip_trace_transmittance_batch",
+    "nxhip_set_material_detail", "nxhip_shading_frame_batch",
 ]
 HOST_SYMBOLS = [
     "nxh_bvh8_build", "nxh_tlas_build", "nxh_tlas_refit", "nxh_bvh8_refit", "nxh_bvh8_node_count", "nxh_bvh8_prim_count", "nxh_bvh8_nodes",
@@ -58,6 +59,8 @@ HOST_SYMBOLS = [
     "nxh_loaded_analytic_light_count", "nxh_loaded_analytic_lights",
     "nxs_scene_add_analytic_light", "nxs_scene_remove_analytic_light", "nxs_scene_analytic_light_count", "nxs_scene_analytic_lights",
     "nxs_pathtracer_set_shadow_transmittance",
+    "nxh_loaded_detail_texture_count", "nxh_loaded_detail_texture_info", "nxh_loaded_detail_texture_pixels", "nxh_loaded_material_detail",
+    "nxs_scene_set_material_detail", "nxs_scene_clear_material_details", "nxs_scene_material_detail_count", "nxs_scene_material_details",
 ]
 
 
@@ -99,6 +102,7 @@ def abi_words():
         pod.INST_DT.itemsize, off(pod.INST_DT, "transform"), off(pod.INST_DT, "materialId"),
         pod.MAT_DT.itemsize, off(pod.MAT_DT, "emissive"), off(pod.MAT_DT, "type"), pod.LIGHT_DT.itemsize, off(pod.LIGHT_DT, "type"),
         pod.ALIGHT_DT.itemsize, off(pod.ALIGHT_DT, "direction"), off(pod.ALIGHT_DT, "colour"), off(pod.ALIGHT_DT, "innerConeAngle"), off(pod.ALIGHT_DT, "type"),
+        pod.DETAIL_DT.itemsize, off(pod.DETAIL_DT, "normalScale"),
         pod.CAM_DT.itemsize, off(pod.CAM_DT, "resolution"), pod.SETTINGS_DT.itemsize, off(pod.SETTINGS_DT, "backgroundColor"),
         pod.RAY_DT.itemsize, pod.HIT_DT.itemsize, pod.BSDF_QUERY_DT.itemsize, pod.BSDF_RESULT_DT.itemsize, off(pod.BSDF_RESULT_DT, "rngOut"),
         C.sizeof(QueueSizes), C.sizeof(TraceStats), TraceStats.cycles.offset, C.sizeof(KernelTimes), len(KERNEL_CLASSES),
@@ -453,6 +457,41 @@ def load_scene_analytic_lights(path):
     return lights
 
 
+def load_scene_detail(path):
+    """The detail maps of a scene file as the C++ reader makes them: (detail textures [(kind "normal" / "roughness", HxWx4 uint8)], normal
+    texture index per material, roughness texture index per material, normal scale per material, warnings)."""
+    L = lib()
+    h = C.c_void_p()
+    if L.nxh_load_scene_file(str(path).encode(), C.byref(h)) != 0:
+        raise NexusError("nxh_load_scene_file: " + L.nxs_last_error().decode())
+    try:
+        L.nxh_loaded_detail_texture_count.argtypes = [C.c_void_p]
+        L.nxh_loaded_detail_texture_info.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_int32)]
+        L.nxh_loaded_detail_texture_pixels.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
+        L.nxh_loaded_material_detail.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.nxh_loaded_material_count.argtypes = [C.c_void_p]
+        L.nxh_loaded_warning_count.argtypes = [C.c_void_p]
+        L.nxh_loaded_warning.argtypes = [C.c_void_p, C.c_uint32]
+        L.nxh_loaded_warning.restype = C.c_char_p
+        textures = []
+        for i in range(L.nxh_loaded_detail_texture_count(h)):
+            w, hh, kind = C.c_uint32(), C.c_uint32(), C.c_int32()
+            if L.nxh_loaded_detail_texture_info(h, i, C.byref(w), C.byref(hh), C.byref(kind)) != 0:
+                raise NexusError(L.nxs_last_error().decode())
+            px = np.zeros((hh.value, w.value, 4), dtype=np.uint8)
+            if L.nxh_loaded_detail_texture_pixels(h, i, _ptr(px)) != 0:
+                raise NexusError(L.nxs_last_error().decode())
+            textures.append(("normal" if kind.value == 3 else "roughness", px))
+        n = L.nxh_loaded_material_count(h)
+        normal, rough, scale = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.float32)
+        if L.nxh_loaded_material_detail(h, _ptr(normal), _ptr(rough), _ptr(scale)) != 0:
+            raise NexusError(L.nxs_last_error().decode())
+        warnings = [L.nxh_loaded_warning(h, i).decode() for i in range(L.nxh_loaded_warning_count(h))]
+    finally:
+        L.nxh_loaded_scene_free(h)
+    return textures, normal.tolist(), rough.tolist(), scale.tolist(), warnings
+
+
 def load_scene_textures(path):
     """The images of a scene file as the C++ reader decodes them: (textures [(kind, HxWx4 uint8)], diffuse texture index
     per material, emissive texture index per material, warnings)."""
@@ -522,6 +561,8 @@ def decode_image(data):
 
 FLAVOR_IDENTITY, FLAVOR_NO_MAPS = 256, 512  # Context.debug_pass_flavor: the specialised kernel instances of a pass graph
 FLAVOR_ANALYTIC = 1024  # ... and the instances of a context with analytic lights (set_analytic_lights)
+FLAVOR_DETAIL = 4096  # ... and the DETAIL instances of the material kernels: some material names a normal or a roughness map (set_material_detail)
+TEXTURE_KINDS = {"diffuse": 0, "emissive": 1, "hdr": 2, "normal": 3, "roughness": 4}  # nxhip_upload_texture / nxhip_tex2d_batch
 FLAVOR_TRANSMIT = 2048  # ... and the any-hit TRANSMIT instance: SHADOWS_TRANSMIT over a table with a see-through material (set_shadow_transmittance)
 
 
@@ -590,6 +631,28 @@ class Context:
         self.L.nxhip_set_analytic_lights.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
         check(self.L.nxhip_set_analytic_lights(self.h, _ptr(lights) if len(lights) else None, len(lights)), "nxhip_set_analytic_lights")
 
+    def set_material_detail(self, details):
+        """the materials' detail maps: pod.DETAIL_DT records (pod.make_material_detail), one per material of the table; an empty list
+        removes the table (nxhip_set_material_detail: the shading rule is in include/nexus_hip.h)"""
+        details = np.ascontiguousarray(details, dtype=pod.DETAIL_DT).reshape(-1)
+        self.L.nxhip_set_material_detail.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+        check(self.L.nxhip_set_material_detail(self.h, _ptr(details) if len(details) else None, len(details)), "nxhip_set_material_detail")
+
+    def shading_frame_batch(self, instance, tri_idx, hit_uv, ray_dir):
+        """what the material kernels hand their sampling code for hits on triangles tri_idx[k] of `instance` at barycentrics hit_uv[k],
+        reached along ray_dir[k] — a test hook: (shading normal float32[n, 3], roughness float32[n], fell_back bool[n])"""
+        t = np.ascontiguousarray(tri_idx, dtype=np.uint32).reshape(-1)
+        uv = np.ascontiguousarray(hit_uv, dtype=np.float32).reshape(-1, 2)
+        d = np.ascontiguousarray(ray_dir, dtype=np.float32).reshape(-1, 3)
+        assert len(t) == len(uv) == len(d)
+        normal = np.zeros((len(t), 3), dtype=np.float32)
+        roughness = np.zeros(len(t), dtype=np.float32)
+        fell = np.zeros(len(t), dtype=np.uint32)
+        self.L.nxhip_shading_frame_batch.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        check(self.L.nxhip_shading_frame_batch(self.h, int(instance), _ptr(t), _ptr(uv), _ptr(d), len(t), _ptr(normal), _ptr(roughness), _ptr(fell)),
+              "nxhip_shading_frame_batch")
+        return normal, roughness, fell != 0
+
     def analytic_light_sample_batch(self, light_index, origins, r):
         """the light sample's draw for analytic light `light_index` from every origin[k] with the random pair r[k] in [0, 1)^2 — a test hook:
         (direction float32[n, 3], tmax float32[n], factor float32[n, 3], ok bool[n])"""
@@ -609,7 +672,7 @@ class Context:
         img = np.ascontiguousarray(rgba8, dtype=np.uint8)
         assert img.ndim == 3 and img.shape[2] == 4
         tid = C.c_int32(-1)
-        check(self.L.nxhip_upload_texture(self.h, {"diffuse": 0, "emissive": 1, "hdr": 2}[kind], _ptr(img), img.shape[1], img.shape[0], C.byref(tid)),
+        check(self.L.nxhip_upload_texture(self.h, TEXTURE_KINDS[kind], _ptr(img), img.shape[1], img.shape[0], C.byref(tid)),
               "nxhip_upload_texture")
         return tid.value
 
@@ -1213,7 +1276,7 @@ class Context:
     def tex2d_batch(self, kind, texture_id, uv):
         uv = np.ascontiguousarray(uv, dtype=np.float32).reshape(-1, 2)
         out = np.zeros((len(uv), 4), dtype=np.float32)
-        check(self.L.nxhip_tex2d_batch(self.h, {"diffuse": 0, "emissive": 1, "hdr": 2}[kind], int(texture_id), _ptr(uv), len(uv), _ptr(out)), "nxhip_tex2d_batch")
+        check(self.L.nxhip_tex2d_batch(self.h, TEXTURE_KINDS[kind], int(texture_id), _ptr(uv), len(uv), _ptr(out)), "nxhip_tex2d_batch")
         return out
 
     def fmath_batch(self, op, a, b=None):
@@ -1328,7 +1391,7 @@ class Scene:
     def add_texture(self, kind, rgba8):
         img = np.ascontiguousarray(rgba8, dtype=np.uint8)
         i = C.c_int32(-1)
-        _scheck(self.L.nxs_scene_add_texture(self.h, {"diffuse": 0, "emissive": 1}[kind], _ptr(img), img.shape[1], img.shape[0], C.byref(i)), "nxs_scene_add_texture")
+        _scheck(self.L.nxs_scene_add_texture(self.h, TEXTURE_KINDS[kind], _ptr(img), img.shape[1], img.shape[0], C.byref(i)), "nxs_scene_add_texture")
         return i.value
 
     def set_hdr_map(self, rgba8):
@@ -1404,6 +1467,26 @@ class Scene:
         self.L.nxs_scene_add_analytic_light.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]
         _scheck(self.L.nxs_scene_add_analytic_light(self.h, _ptr(l), C.byref(i)), "nxs_scene_add_analytic_light")
         return int(i.value)
+
+    def set_material_detail(self, material_id, detail):
+        """AssetManager::SetMaterialDetail: a pod.DETAIL_DT record (pod.make_material_detail) with ids of add_texture("normal" / "roughness", ...)"""
+        d = np.ascontiguousarray(detail, dtype=pod.DETAIL_DT).reshape(1)
+        self.L.nxs_scene_set_material_detail.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+        _scheck(self.L.nxs_scene_set_material_detail(self.h, int(material_id), _ptr(d)), "nxs_scene_set_material_detail")
+
+    def clear_material_details(self):
+        """AssetManager::ClearMaterialDetails: no material has detail maps any more (what nexus_render --no-detail-maps does)"""
+        self.L.nxs_scene_clear_material_details.argtypes = [C.c_void_p]
+        _scheck(self.L.nxs_scene_clear_material_details(self.h), "nxs_scene_clear_material_details")
+
+    def material_details(self):
+        """AssetManager::GetMaterialDetails: pod.DETAIL_DT records, one per material, or none at all"""
+        self.L.nxs_scene_material_detail_count.argtypes = [C.c_void_p]
+        self.L.nxs_scene_material_detail_count.restype = C.c_uint32
+        self.L.nxs_scene_material_details.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+        out = np.zeros(int(self.L.nxs_scene_material_detail_count(self.h)), dtype=pod.DETAIL_DT)
+        _scheck(self.L.nxs_scene_material_details(self.h, _ptr(out) if len(out) else None, len(out)), "nxs_scene_material_details")
+        return out
 
     def remove_analytic_light(self, index):
         self.L.nxs_scene_remove_analytic_light.argtypes = [C.c_void_p, C.c_uint32]

@@ -68,7 +68,7 @@ int nxs_scene_add_texture(nxs_scene* s, int kind, const uint8_t* rgba8, uint32_t
 {
     return guarded([&] {
         Texture t(w, h, 4, rgba8);
-        t.type = kind == 1 ? Texture::Type::EMISSIVE : Texture::Type::DIFFUSE;
+        t.type = kind == 1 ? Texture::Type::EMISSIVE : kind == 3 ? Texture::Type::NORMAL : kind == 4 ? Texture::Type::ROUGHNESS : Texture::Type::DIFFUSE;
         const int id = s->scene.GetAssetManager().AddTexture(t);
         if (texId) *texId = id;
     });
@@ -199,6 +199,36 @@ int nxh_loaded_material_textures(const nxh_loaded_scene* s, int32_t* diffuseText
         }
     });
 }
+uint32_t nxh_loaded_detail_texture_count(const nxh_loaded_scene* s) { return static_cast<uint32_t>(s->ls.detailTextures.size()); }
+int nxh_loaded_detail_texture_info(const nxh_loaded_scene* s, uint32_t index, uint32_t* width, uint32_t* height, int32_t* kind)
+{
+    return guarded([&] {
+        if (index >= s->ls.detailTextures.size()) throw std::runtime_error("nxh_loaded_detail_texture_info: no such texture");
+        const Texture& t = s->ls.detailTextures[index];
+        if (width) *width = t.width;
+        if (height) *height = t.height;
+        if (kind) *kind = t.type == Texture::Type::NORMAL ? 3 : 4;
+    });
+}
+int nxh_loaded_detail_texture_pixels(const nxh_loaded_scene* s, uint32_t index, uint8_t* dstRgba8)
+{
+    return guarded([&] {
+        if (index >= s->ls.detailTextures.size() || !dstRgba8) throw std::runtime_error("nxh_loaded_detail_texture_pixels: bad argument");
+        const Texture& t = s->ls.detailTextures[index];
+        std::memcpy(dstRgba8, t.pixels.data(), t.pixels.size());
+    });
+}
+int nxh_loaded_material_detail(const nxh_loaded_scene* s, int32_t* normalTexture, int32_t* roughnessTexture, float* normalScale)
+{
+    return guarded([&] {
+        if (!normalTexture || !roughnessTexture || !normalScale) throw std::runtime_error("nxh_loaded_material_detail: null destination");
+        for (size_t i = 0; i < s->ls.materials.size(); i++) {
+            normalTexture[i] = s->ls.materialNormalTexture[i];
+            roughnessTexture[i] = s->ls.materialRoughnessTexture[i];
+            normalScale[i] = s->ls.materialNormalScale[i];
+        }
+    });
+}
 uint32_t nxh_loaded_analytic_light_count(const nxh_loaded_scene* s) { return static_cast<uint32_t>(s->ls.analyticLights.size()); }
 int nxh_loaded_analytic_lights(const nxh_loaded_scene* s, nx_analytic_light* dst)
 {
@@ -303,6 +333,25 @@ int nxs_scene_update(nxs_scene* s)
     return guarded([&] { s->scene.Update(); });
 }
 
+int nxs_scene_set_material_detail(nxs_scene* s, int32_t materialId, const nx_material_detail* detail)
+{
+    return guarded([&] {
+        if (!detail) throw std::runtime_error("nxs_scene_set_material_detail: null record");
+        MaterialDetail d;
+        static_cast<nx_material_detail&>(d) = *detail;
+        s->scene.GetAssetManager().SetMaterialDetail(materialId, d);
+    });
+}
+int nxs_scene_clear_material_details(nxs_scene* s) { return guarded([&] { s->scene.GetAssetManager().ClearMaterialDetails(); }); }
+uint32_t nxs_scene_material_detail_count(const nxs_scene* s) { return static_cast<uint32_t>(s->scene.GetAssetManager().GetMaterialDetails().size()); }
+int nxs_scene_material_details(const nxs_scene* s, nx_material_detail* dst, uint32_t capacity)
+{
+    return guarded([&] {
+        const std::vector<MaterialDetail> d = s->scene.GetAssetManager().GetMaterialDetails();
+        if (capacity < d.size() || (!dst && !d.empty())) throw std::runtime_error("nxs_scene_material_details: destination too small");
+        for (size_t i = 0; i < d.size(); i++) dst[i] = d[i];
+    });
+}
 uint32_t nxs_scene_light_count(const nxs_scene* s) { return static_cast<uint32_t>(s->scene.GetLights().size()); }
 int nxs_scene_add_analytic_light(nxs_scene* s, const nx_analytic_light* light, uint32_t* index)
 {

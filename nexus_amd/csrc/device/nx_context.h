@@ -173,6 +173,11 @@ struct nxhip_ctx : nxd::PassSlot {
     std::vector<nx_material> hostMaterialsDev;  // the device copy (derived flag byte included), for the instances' shading records
     nxd::DevBuf shadeInst;        // [instanceCount] ShadeInst (nx_device.h): rebuilt before a render when an instance, BLAS or material table changed
     bool shadeInstDirty = true;
+    // detail maps (nxhip_set_material_detail): the table, index-parallel to hostMaterials (empty: none); the per-instance records that
+    // run parallel to shadeInst (refresh_shade_inst); whether some entry names a map — only then does a pass change (kFlavorDetail)
+    std::vector<nx_material_detail> hostMaterialDetail;
+    nxd::DevBuf shadeDetail;
+    bool materialsNameDetail = false;
     std::vector<nx_light> hostLights;
     nxd::DevBuf alights;  // [h.alightCount] ALight: the analytic lights' device table (nxhip_set_analytic_lights)
     std::vector<uint32_t> hostInstIdx;  // TLAS leaf order
@@ -185,6 +190,8 @@ struct nxhip_ctx : nxd::PassSlot {
     std::vector<uint32_t> blasRefreshIds;     // the instances of the BLASes the last refresh served, and the list on the device
     nxd::DevBuf blasRefreshIdsDev;
     std::vector<nxd::TextureHost> diffuseMaps, emissiveMaps;
+    std::vector<nxd::TextureHost> normalMaps, roughnessMaps;  // linear data (nxhip_upload_texture kind 3 / 4)
+    nxd::DevBuf normalTable, roughnessTable;
     nxd::TextureHost hdrMap;
     nxd::DevBuf diffuseTable, emissiveTable, srgbLut;
     // environment importance sampling (extension): host copy of the hdr map and the tables built from it
@@ -223,6 +230,7 @@ struct nxhip_ctx : nxd::PassSlot {
     int tailBlocks = 0;
     int tailBlocksPower = 0;  // grid of tail_kernel<true> (NXHIP_LIGHTS_POWER), from that instance's own occupancy
     int tailBlocksAnalytic[2] = {0, 0};  // grids of tail_kernel<POWER, true> (analytic lights: kFlavorAnalytic), [0] uniform, [1] POWER
+    int tailBlocksDetail[2][2] = {{0, 0}, {0, 0}};  // grids of tail_kernel<POWER, ANALYTIC, true> (detail maps: kFlavorDetail), [power][analytic]
     int tailBounce = -1;  // first bounce of the tail kernel, 0 = off, -1 = automatic (see tail_bounce in nxhip_render.hip)
     bool traceGridForced = false;                            // NX_TRACE_BLOCKS_*: use them as they are
     int shadeBlocksPerCU = 10, logicBlocksPerCU = 2;  // grid-stride kernels: workgroups per CU

@@ -453,6 +453,13 @@ struct DeviceState {
     const NX_G ALight* alights;  // [alightCount]
     uint32_t alightCount;
     uint32_t padAlights_;
+    // Detail maps (nxhip_set_material_detail; nx_detail.h), nullptr while no material names one.  Read only by the DETAIL instances of the
+    // material kernels, which pass graphs launch while some material names a normal or a roughness map (kFlavorDetail).  shadeDetail runs
+    // parallel to shadeInst: the detail record of the instance's material, filled where the shading records are (refresh_shade_inst).
+    // Last in the block: nothing in front moves.
+    const NX_G TextureDev* normalMaps;
+    const NX_G TextureDev* roughnessMaps;
+    const NX_G nx_material_detail* shadeDetail;  // [instanceCount]
 };
 
 // Argument block of the adaptive update's kernels (nx_adaptive.hip; filled by nxhip_adaptive_update)
@@ -496,7 +503,7 @@ constexpr uint64_t layout_stamp()
     const uint64_t w[] = {
         sizeof(DeviceState), offsetof(DeviceState, camera), offsetof(DeviceState, envSampling), offsetof(DeviceState, localCount), offsetof(DeviceState, pixelMap),
         offsetof(DeviceState, radiance), offsetof(DeviceState, trace), offsetof(DeviceState, shadow), offsetof(DeviceState, material), offsetof(DeviceState, counters),
-        offsetof(DeviceState, frame), offsetof(DeviceState, traceStats), offsetof(DeviceState, scanStatus), offsetof(DeviceState, entry), offsetof(DeviceState, entryRuns), offsetof(DeviceState, debugRequeue), offsetof(DeviceState, aovAlbedo), offsetof(DeviceState, aovAccumNormalDepth), offsetof(DeviceState, basePixelMap), offsetof(DeviceState, adStats), offsetof(DeviceState, baseCount), offsetof(DeviceState, lightTable), offsetof(DeviceState, lightHeader), offsetof(DeviceState, lightGuideSize), offsetof(DeviceState, envFloat), offsetof(DeviceState, alights), offsetof(DeviceState, alightCount), sizeof(ALight), sizeof(LightEntry), sizeof(LightHeader), sizeof(LightBuild), offsetof(LightBuild, lightCount), sizeof(AdaptiveLaunch), offsetof(AdaptiveLaunch, baseCount), offsetof(DeviceState, thinStates), offsetof(DeviceState, leafOfInstance), sizeof(ThinState), offsetof(ThinState, stack), offsetof(DeviceState, thinClosest), offsetof(DeviceState, thinCapacity), offsetof(DeviceState, thinIters), offsetof(DeviceState, thinPoolLimit), offsetof(Counters, thinCount), sizeof(EntryState), offsetof(EntryState, sp), offsetof(EntryState, triP0), offsetof(EntryState, triInst), offsetof(Counters, scanTicket), offsetof(FrameState, scanEpoch),
+        offsetof(DeviceState, frame), offsetof(DeviceState, traceStats), offsetof(DeviceState, scanStatus), offsetof(DeviceState, entry), offsetof(DeviceState, entryRuns), offsetof(DeviceState, debugRequeue), offsetof(DeviceState, aovAlbedo), offsetof(DeviceState, aovAccumNormalDepth), offsetof(DeviceState, basePixelMap), offsetof(DeviceState, adStats), offsetof(DeviceState, baseCount), offsetof(DeviceState, lightTable), offsetof(DeviceState, lightHeader), offsetof(DeviceState, lightGuideSize), offsetof(DeviceState, envFloat), offsetof(DeviceState, alights), offsetof(DeviceState, alightCount), offsetof(DeviceState, normalMaps), offsetof(DeviceState, shadeDetail), sizeof(nx_material_detail), sizeof(ALight), sizeof(LightEntry), sizeof(LightHeader), sizeof(LightBuild), offsetof(LightBuild, lightCount), sizeof(AdaptiveLaunch), offsetof(AdaptiveLaunch, baseCount), offsetof(DeviceState, thinStates), offsetof(DeviceState, leafOfInstance), sizeof(ThinState), offsetof(ThinState, stack), offsetof(DeviceState, thinClosest), offsetof(DeviceState, thinCapacity), offsetof(DeviceState, thinIters), offsetof(DeviceState, thinPoolLimit), offsetof(Counters, thinCount), sizeof(EntryState), offsetof(EntryState, sp), offsetof(EntryState, triP0), offsetof(EntryState, triInst), offsetof(Counters, scanTicket), offsetof(FrameState, scanEpoch),
         (uint64_t)kScanKinds, (uint64_t)kScanWords, (uint64_t)kScanEpochLimit, (uint64_t)kShadeBlockOrderedThreads,
         sizeof(Counters), sizeof(RegionCounters), offsetof(RegionCounters, traceShadowSize), offsetof(RegionCounters, materialSize), offsetof(RegionCounters, traceHead),
         offsetof(RegionCounters, shadowHead), offsetof(RegionCounters, scanTile), offsetof(RegionCounters, endedSize), offsetof(Counters, orderedBase), offsetof(Counters, tailHead),

@@ -35,6 +35,11 @@ const void* tex2d_hook_kernel_ptr();
 const void* env_hook_kernel_ptr();
 const void* alight_hook_kernel_ptr();
 const void* tex2d_float_hook_kernel_ptr();
+const void* shade_detail_kernel_ptr(int type, bool lightPower, bool analytic);  // nx_wavefront_detail.hip: the DETAIL instances (kFlavorDetail)
+const void* shade_scan_detail_kernel_ptr(bool lightPower, bool analytic);
+const void* tail_detail_kernel_ptr(bool lightPower, bool analytic);
+const void* shading_frame_hook_kernel_ptr();
+const void* tex2d_linear_hook_kernel_ptr();
 const void* aov_kernel_ptr();  // nx_aov.hip
 const void* aov_fold_kernel_ptr();
 const void* denoise_gather_kernel_ptr();
@@ -51,6 +56,7 @@ const void* tlas_refit_kernel_ptr();
 const void* blas_refit_kernel_ptr();
 uint64_t layout_stamp_trace();
 uint64_t layout_stamp_wavefront();
+uint64_t layout_stamp_wavefront_detail();
 uint64_t layout_stamp_refit();
 uint64_t layout_stamp_lbvh();
 uint64_t layout_stamp_multigpu();
@@ -114,10 +120,14 @@ inline BounceKernel trace_transmit(bool stats) { return {trace_transmit_kernel_p
 inline BounceKernel trace_entry(bool identity = false) { return {trace_entry_kernel_ptr(identity)}; }
 inline BounceKernel thin() { return {thin_kernel_ptr()}; }
 inline StateKernel entry_state() { return {entry_state_kernel_ptr()}; }
-inline BounceKernel tail(bool lightPower, bool analytic = false) { return {tail_kernel_ptr(lightPower, analytic)}; }
+// (detail: the DETAIL instances of a context whose materials name normal or roughness maps — nx_wavefront_detail.hip)
+inline BounceKernel tail(bool lightPower, bool analytic = false, bool detail = false) { return {detail ? tail_detail_kernel_ptr(lightPower, analytic) : tail_kernel_ptr(lightPower, analytic)}; }
 inline BounceKernel logic(int items, bool analytic = false) { return {logic_kernel_ptr(items, analytic)}; }
-inline BounceKernel shade(int type, bool lightPower, bool analytic = false) { return {shade_kernel_ptr(type, lightPower, analytic)}; }
-inline TypeKernel shade_scan(bool lightPower, bool noMaps = false, bool analytic = false) { return {shade_scan_kernel_ptr(lightPower, noMaps, analytic)}; }
+inline BounceKernel shade(int type, bool lightPower, bool analytic = false, bool detail = false) { return {detail ? shade_detail_kernel_ptr(type, lightPower, analytic) : shade_kernel_ptr(type, lightPower, analytic)}; }
+inline TypeKernel shade_scan(bool lightPower, bool noMaps = false, bool analytic = false, bool detail = false)
+{
+    return {detail ? shade_scan_detail_kernel_ptr(lightPower, analytic) : shade_scan_kernel_ptr(lightPower, noMaps, analytic)};
+}
 inline TypeKernel count_scan() { return {count_scan_kernel_ptr()}; }
 inline Kernel<DeviceState*, U32, U32, U32> begin_frame() { return {begin_frame_kernel_ptr()}; }  // (S, frames, frameLast, scanEpoch)
 inline Kernel<DeviceState*, U32, int, int> hook_sizes() { return {hook_sizes_kernel_ptr()}; }    // (S, n, anyHit, slot)
@@ -130,6 +140,9 @@ inline Kernel<int, const double*, const double*, U32, double*> fmath_hook() { re
 inline Kernel<TextureDev, const float*, const float*, U32, float4*> tex2d_hook() { return {tex2d_hook_kernel_ptr()}; }              // (t, srgbLut, uv, count, out)
 inline Kernel<const float4*, int, int, const float*, U32, float4*> tex2d_float_hook() { return {tex2d_float_hook_kernel_ptr()}; }       // (texels, W, H, uv, count, out)
 inline Kernel<State, int, const float*, U32, float*, float*, U32*> env_hook() { return {env_hook_kernel_ptr()}; }                    // (S, sample, in, count, vec, pdf, texel)
+inline Kernel<TextureDev, const float*, U32, float4*> tex2d_linear_hook() { return {tex2d_linear_hook_kernel_ptr()}; }                  // (t, uv, count, out)
+// (S, instance, triIdx, hitUv, rayDir, count, normal, roughness, fellBack)
+inline Kernel<State, U32, const U32*, const float*, const float*, U32, float*, float*, U32*> shading_frame_hook() { return {shading_frame_hook_kernel_ptr()}; }
 // (S, light, origin, r, count, direction, tmax, factor, ok)
 inline Kernel<State, U32, const float*, const float*, U32, float*, float*, float*, U32*> alight_hook() { return {alight_hook_kernel_ptr()}; }
 inline StateKernel aov() { return {aov_kernel_ptr()}; }
@@ -278,6 +291,7 @@ int set_frame_number_device(nxhip_ctx* c, uint32_t f);
 // nxhip_scene.hip: what a pass or a hook brings up to date before it reads the scene
 int refresh_shade_inst(nxhip_ctx* c);
 bool material_see_through(const nxhip_ctx* c, const nx_material& m);  // a shadow ray of NXHIP_SHADOWS_TRANSMIT may pass it
+void refresh_detail_maps(nxhip_ctx* c);  // nxhip_ctx::materialsNameDetail, after the detail table has changed
 void refresh_see_through(nxhip_ctx* c);  // nxhip_ctx::materialsSeeThrough, and the shading records' copy of the fact
 int refresh_updated_blas(nxhip_ctx* c);
 // nxhip_render.hip

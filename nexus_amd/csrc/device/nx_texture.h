@@ -62,6 +62,31 @@ NXD float tex2d_alpha(const TextureDev& t, float u, float v)
     return top + ay * (bot - top);
 }
 
+// The detail maps' lookup (normal and roughness maps: nxhip_upload_texture kind 3 / 4): linear data, so no sRGB table — every channel is
+// byte / 255.0f, as tex2d's alpha — with tex2d's addressing and its 1/256 bilinear weights.
+NXD float4 tex2d_linear(const TextureDev& t, float u, float v)
+{
+    const int W = (int)t.width, H = (int)t.height;
+    const float xb = u * (float)W - 0.5f, yb = v * (float)H - 0.5f;
+    const float fx = floorf(xb), fy = floorf(yb);
+    const float ax = floorf((xb - fx) * 256.0f + 0.5f) * (1.0f / 256.0f);
+    const float ay = floorf((yb - fy) * 256.0f + 0.5f) * (1.0f / 256.0f);
+    const int i0 = wrapi((int)fx, W), i1 = wrapi((int)fx + 1, W);
+    const int j0 = wrapi((int)fy, H), j1 = wrapi((int)fy + 1, H);
+    const uint32_t p00 = t.texels[(size_t)j0 * W + i0], p10 = t.texels[(size_t)j0 * W + i1];
+    const uint32_t p01 = t.texels[(size_t)j1 * W + i0], p11 = t.texels[(size_t)j1 * W + i1];
+    float out[4];
+#pragma unroll
+    for (int c = 0; c < 4; c++) {
+        const float t00 = (float)((p00 >> (8 * c)) & 0xffu) / 255.0f, t10 = (float)((p10 >> (8 * c)) & 0xffu) / 255.0f;
+        const float t01 = (float)((p01 >> (8 * c)) & 0xffu) / 255.0f, t11 = (float)((p11 >> (8 * c)) & 0xffu) / 255.0f;
+        const float top = t00 + ax * (t10 - t00);
+        const float bot = t01 + ax * (t11 - t01);
+        out[c] = top + ay * (bot - top);
+    }
+    return make_float4(out[0], out[1], out[2], out[3]);
+}
+
 // The float environment map's lookup (nxhip_upload_env_float): the same addressing — normalised coordinates, texel centres at +0.5,
 // wrap on both axes — over one float4 of linear radiance per texel, with the EXACT binary32 fractional weights.  The 1/256 steps
 // above imitate a texture unit that only ever filtered 8-bit texels; next to a texel of 6e4, 1/512 of a weight is 117, not a

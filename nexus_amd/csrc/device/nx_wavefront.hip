@@ -14,12 +14,16 @@
 //     allocation, outside divergent control flow;
 //   * the frame number lives on the device and is advanced by begin_frame_kernel, so a frame is one
 //     hipGraph replay with no host-side writes in between.
+// NX_WAVEFRONT_INSTANCES_ONLY: nx_wavefront_detail.hip compiles this text for the kernel TEMPLATES alone and instantiates their DETAIL
+// family there (a translation unit of its own: profiles/analytic_lights.txt section 3); everything that is not a template — the plain
+// kernels, the getters, the layout stamp — is then left out, so nothing is defined twice.
 #define NX_KERNEL_TU 1
 #include "nx_bsdf.h"
 #include "nx_device.h"
 #include "nx_math.h"
 #include "nx_lights.h"
 #include "nx_alights.h"
+#include "nx_detail.h"
 #include "nx_queue.h"
 #include "nx_texture.h"
 #include "nx_tonemap.h"
@@ -359,6 +363,7 @@ NXD uint32_t seed_for(const DeviceState* S, uint32_t slot, uint32_t pathIdx, uin
 // every counter, traceSize[0] = localCount * frames (GenerateKernel's thread 0 in the reference, PathTracer.cu:112-113; the
 // memset of PathTracer.cpp:263; the frame counter of PathTracer.cpp:250).
 
+#ifndef NX_WAVEFRONT_INSTANCES_ONLY
 __global__ void __launch_bounds__(kWideBlock) begin_frame_kernel(DeviceState* __restrict__ S, const uint32_t frames, const uint32_t frameLast, const uint32_t scanEpoch)
 {
     int* c = reinterpret_cast<int*>(S->counters);
@@ -435,6 +440,8 @@ __global__ void __launch_bounds__(kWideBlock) generate_kernel(const DeviceState*
         S->trace.rays[0].rayD[slot] = make_float4(direction.x, direction.y, direction.z, __uint_as_float(index));
     }
 }
+
+#endif  // NX_WAVEFRONT_INSTANCES_ONLY
 
 // ------------------------------------------------------------------------------------------------------
 // SampleBackground — PathTracer.cu:65-83
@@ -841,7 +848,11 @@ NXD bool next_event_estimation(const DeviceState* S, f3 wi, const MatParams& mp,
 // (only read for an emissive hit under MIS).  emit(radiance, instance) receives what the hit emits towards the path; what comes out: the shadow ray of its
 // light sample, the continuation ray and the path state that goes with it.  (Separate references, not a struct: the
 // compiler kept a struct of these in scratch memory, +30 % on the material kernels.)
-template <int TYPE, bool POWER, bool NO_MAPS = false, bool ANALYTIC = false, class PrevOrigin, class Emit>
+// DETAIL (nxhip_set_material_detail with a material that names a normal or a roughness map: kFlavorDetail): the roughness map scales the
+// BSDF's roughness and the normal map's shading normal ns (nx_detail.h: the rule is stated in include/nexus_hip.h) takes the place of the
+// interpolated normal in the frame, in the light sample and in the offset signs; the emissive hit's MIS weight keeps the interpolated
+// normal.  The instances with DETAIL = false are the code of a context without such maps.
+template <int TYPE, bool POWER, bool NO_MAPS = false, bool ANALYTIC = false, bool DETAIL = false, class PrevOrigin, class Emit>
 NXD void shade_path(const DeviceState* S, const int bounce, const uint32_t frame, const uint32_t seedSlot, const uint32_t pixelIdx, const float hu, const float hv,
                     const uint32_t triIdx, const uint32_t instanceIdx, const f3 rayDirection, const float4 tpdf, PrevOrigin prevOrigin, Emit emit,
                     bool& wantShadow, ShadowPayload& sh, bool& wantTrace, bool& updatePath, f3& nextOrigin, f3& nextDir, f3& nextThroughput, float& nextPdf)
@@ -911,7 +922,13 @@ NXD void shade_path(const DeviceState* S, const int bounce, const uint32_t frame
             color = tex2d(S->diffuseMaps[material.diffuseMapId], S->srgbLut, texUv.x, texUv.y);
             mp.albedo = mk3(color.x, color.y, color.z);
         }
-        if (dot3(gNormal, rayDirection) > 0.0f && TYPE != NX_MAT_DIELECTRIC) { normal = -normal; gNormal = -gNormal; }
+        if constexpr (DETAIL) {
+            // (from here on `normal` IS the shading normal: the interpolated one is not read again, so only three registers cross the sampling code)
+            bool fellBack;
+            normal = detail_shading_frame<TYPE>(S, S->shadeDetail[instanceIdx], tri, T, tp0, tp1, tp2, texUv, rayDirection, normal, gNormal, mp.roughness, fellBack);
+        } else {
+            if (dot3(gNormal, rayDirection) > 0.0f && TYPE != NX_MAT_DIELECTRIC) { normal = -normal; gNormal = -gNormal; }
+        }
 
         const float4 q = rotation_to_z(normal);
         const f3 wi = rotate_point(q, -rayDirection);
@@ -945,7 +962,7 @@ NXD void shade_path(const DeviceState* S, const int bounce, const uint32_t frame
 // at 4 waves (126 VGPRs) for one large pass, +4.5 % for one-frame passes in flight, where a smaller register footprint lets
 // the material kernels of one slot share SIMDs with the trace waves of another.  6 and 8 waves per SIMD spill 30-87 VGPRs and
 // double the kernel's time: it is sensitive to memory traffic, not short of waves.
-template <int TYPE, bool ORDERED, bool POWER, bool ANALYTIC = false>
+template <int TYPE, bool ORDERED, bool POWER, bool ANALYTIC = false, bool DETAIL = false>
 #ifndef NX_SHADE_WAVES
 #define NX_SHADE_WAVES 5
 #endif
@@ -981,7 +998,7 @@ __global__ void __launch_bounds__(ORDERED ? kShadeBlockOrderedThreads : kShadeBl
             pixelIdx = __float_as_uint(hit.x);
             const uint32_t instanceIdx = __float_as_uint(dirInst.w);
             tpdf = bounce == 1 ? make_float4(1.0f, 1.0f, 1.0f, 1.0e10f) : mq.tp[at];
-            shade_path<TYPE, POWER, false, ANALYTIC>(S, bounce, frame, (uint32_t)requestIdx, pixelIdx, hit.y, hit.z, __float_as_uint(hit.w), instanceIdx, mk3(dirInst.x, dirInst.y, dirInst.z), tpdf,
+            shade_path<TYPE, POWER, false, ANALYTIC, DETAIL>(S, bounce, frame, (uint32_t)requestIdx, pixelIdx, hit.y, hit.z, __float_as_uint(hit.w), instanceIdx, mk3(dirInst.x, dirInst.y, dirInst.z), tpdf,
                              [&]() { return S->rayOrigin[pixelIdx]; },
                              [&](f3 emitted, uint32_t instIdx) {
                                  if (bounce == 1 && bounce != (int)S->settings.pathLength && pixelIdx < S->localCount && S->frame->pixelQueryPixel == (int)global_pixel(S, pixelIdx))
@@ -1043,7 +1060,7 @@ static_assert(kScanRing >= kShadeBlock + 4 * kShadeBlock && (kScanRing & (kScanR
 // from `staticTiles` on are handed out by ticket — one returning atomic per tile on the region's own word.  The share of a tile
 // that is this type's to shade varies from none to all with what the camera sees there, so a static split leaves most workgroups
 // waiting for the few whose tiles were full (measured: +40 % on the kernels).
-template <int TYPE, bool POWER, bool NO_MAPS = false, bool ANALYTIC = false>
+template <int TYPE, bool POWER, bool NO_MAPS = false, bool ANALYTIC = false, bool DETAIL = false>
 NXD void shade_scan_type(const DeviceState* __restrict__ S, const int bounce, const bool dropEnded, const int region, const int inRegion, const int per, const int firstTile,
                          const int staticTiles, int* const sRing, int* const sHead, int* const sTicket)
 {
@@ -1125,7 +1142,7 @@ NXD void shade_scan_type(const DeviceState* __restrict__ S, const int bounce, co
             // ... and the path's previous vertex, for hits that can need it (keep_previous_vertex)
             const uint32_t typeAndFlag = *(const NX_G uint32_t*)((const NX_G char*)&S->shadeInst[instanceIdx].material + kMaterialTypeOffset);
             if ((typeAndFlag >> 8) & 1u) keep_previous_vertex(S, pixelIdx, in.rayO[at]);
-            shade_path<TYPE, POWER, NO_MAPS, ANALYTIC>(S, bounce, frame, (uint32_t)at, pixelIdx, hit.y, hit.z, __float_as_uint(hit.w), instanceIdx, mk3(dirPix.x, dirPix.y, dirPix.z), tpdf,
+            shade_path<TYPE, POWER, NO_MAPS, ANALYTIC, DETAIL>(S, bounce, frame, (uint32_t)at, pixelIdx, hit.y, hit.z, __float_as_uint(hit.w), instanceIdx, mk3(dirPix.x, dirPix.y, dirPix.z), tpdf,
                              [&]() { return S->rayOrigin[pixelIdx]; },
                              [&](f3 emitted, uint32_t instIdx) {
                                  if (bounce == 1 && bounce != (int)S->settings.pathLength && pixelIdx < S->localCount && S->frame->pixelQueryPixel == (int)global_pixel(S, pixelIdx))
@@ -1239,7 +1256,7 @@ NXD void shade_scan_type(const DeviceState* __restrict__ S, const int bounce, co
 // workgroups start on different types (rank modulo the number of types) and move on to the next type when theirs has no tile
 // left, so the types run side by side, the launch ends when the last tile of the last type does, and a bounce costs one material
 // launch instead of one per type (the reference: four, PathTracer.cpp:116-120).  A single-bit mask is a per-type launch.
-template <bool POWER, bool NO_MAPS = false, bool ANALYTIC = false>  // (the light sample's mode, a map-free context, analytic lights: next_event_estimation)
+template <bool POWER, bool NO_MAPS = false, bool ANALYTIC = false, bool DETAIL = false>  // (the light sample's mode, a map-free context, analytic lights: next_event_estimation; detail maps: shade_path)
 __global__ void __launch_bounds__(kShadeBlock, NX_SHADE_WAVES) shade_scan_kernel(const DeviceState* __restrict__ S, const int bounceArg, const int typeMask)
 {
     const int bounce = bounceArg & 0xff;
@@ -1274,11 +1291,11 @@ __global__ void __launch_bounds__(kShadeBlock, NX_SHADE_WAVES) shade_scan_kernel
         const int starters = (ranks - want + nTypes - 1) / nTypes;  // workgroups whose first type this is: each takes the tile of its index
         const int first = step == 0 ? myIndex : -1;
         switch (type) {
-        case NX_MAT_DIFFUSE: shade_scan_type<NX_MAT_DIFFUSE, POWER, NO_MAPS, ANALYTIC>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket); break;
-        case NX_MAT_PLASTIC: shade_scan_type<NX_MAT_PLASTIC, POWER, NO_MAPS, ANALYTIC>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket); break;
-        case NX_MAT_DIELECTRIC: shade_scan_type<NX_MAT_DIELECTRIC, POWER, NO_MAPS, ANALYTIC>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket); break;
-        case NX_MAT_CONDUCTOR: shade_scan_type<NX_MAT_CONDUCTOR, POWER, NO_MAPS, ANALYTIC>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket); break;
-        case kScanMiss: shade_scan_type<kScanMiss, POWER, NO_MAPS, ANALYTIC>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket); break;
+        case NX_MAT_DIFFUSE: shade_scan_type<NX_MAT_DIFFUSE, POWER, NO_MAPS, ANALYTIC, DETAIL>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket); break;
+        case NX_MAT_PLASTIC: shade_scan_type<NX_MAT_PLASTIC, POWER, NO_MAPS, ANALYTIC, DETAIL>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket); break;
+        case NX_MAT_DIELECTRIC: shade_scan_type<NX_MAT_DIELECTRIC, POWER, NO_MAPS, ANALYTIC, DETAIL>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket); break;
+        case NX_MAT_CONDUCTOR: shade_scan_type<NX_MAT_CONDUCTOR, POWER, NO_MAPS, ANALYTIC, DETAIL>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket); break;
+        case kScanMiss: shade_scan_type<kScanMiss, POWER, NO_MAPS, ANALYTIC, DETAIL>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket); break;
         default: break;
         }
     }
@@ -1287,6 +1304,7 @@ __global__ void __launch_bounds__(kShadeBlock, NX_SHADE_WAVES) shade_scan_kernel
 // The reference's queue sizes count the hits of a material type whether or not a kernel shades them (its conductor kernel's body is
 // commented out, PathTracer.cu:475-478, but the logic kernel still fills that queue): with NX_CONDUCTOR_REFERENCE the SCAN
 // pipeline has no conductor kernel to count its items, so this one does (4 B per ray; in the graph only in that mode).
+#ifndef NX_WAVEFRONT_INSTANCES_ONLY
 __global__ void __launch_bounds__(kWideBlock) count_scan_kernel(const DeviceState* __restrict__ S, const int bounce, const int type)
 {
     Counters* C = S->counters;
@@ -1297,6 +1315,8 @@ __global__ void __launch_bounds__(kWideBlock) count_scan_kernel(const DeviceStat
     n = wave_sum(n);
     if ((threadIdx.x & (kWave - 1)) == 0 && n) atomicAdd(&C->region[0].materialSize[type][bounce], n);
 }
+
+#endif  // NX_WAVEFRONT_INSTANCES_ONLY
 
 // ------------------------------------------------------------------------------------------------------
 // Tail kernel: the late bounces of a pass without the graph.  From bounce `firstBounce` on a pass carries a few per cent of
@@ -1309,7 +1329,7 @@ __global__ void __launch_bounds__(kWideBlock) count_scan_kernel(const DeviceStat
 #ifndef NX_TAIL_REFILL_BELOW
 #define NX_TAIL_REFILL_BELOW 40
 #endif
-template <bool POWER, bool ANALYTIC = false>  // (the light sample's mode, analytic lights: next_event_estimation)
+template <bool POWER, bool ANALYTIC = false, bool DETAIL = false>  // (the light sample's mode, analytic lights: next_event_estimation; detail maps: shade_path)
 __global__ void __launch_bounds__(kTraceBlock) tail_kernel(const DeviceState* __restrict__ S, const int firstBounceArg)
 {
     // firstBounce | kTraceScanFlag: the pass ran the SCAN pipeline so far — the rays of trace(firstBounce - 1) are in the set of
@@ -1394,20 +1414,20 @@ __global__ void __launch_bounds__(kTraceBlock) tail_kernel(const DeviceState* __
         };
         if (__ballot(alive && type == NX_MAT_DIFFUSE) != 0ull) {
             if (alive && type == NX_MAT_DIFFUSE)
-                shade_path<NX_MAT_DIFFUSE, POWER, false, ANALYTIC>(S, bounce, frame, (uint32_t)index, pixelIdx, hu, hv, tri, inst, dir, tp, prevOrigin, emit, wantShadowRay, sh, wantTrace, updatePath, nextOrigin, nextDir, nextThroughput, nextPdf);
+                shade_path<NX_MAT_DIFFUSE, POWER, false, ANALYTIC, DETAIL>(S, bounce, frame, (uint32_t)index, pixelIdx, hu, hv, tri, inst, dir, tp, prevOrigin, emit, wantShadowRay, sh, wantTrace, updatePath, nextOrigin, nextDir, nextThroughput, nextPdf);
         }
         if (__ballot(alive && type == NX_MAT_PLASTIC) != 0ull) {
             if (alive && type == NX_MAT_PLASTIC)
-                shade_path<NX_MAT_PLASTIC, POWER, false, ANALYTIC>(S, bounce, frame, (uint32_t)index, pixelIdx, hu, hv, tri, inst, dir, tp, prevOrigin, emit, wantShadowRay, sh, wantTrace, updatePath, nextOrigin, nextDir, nextThroughput, nextPdf);
+                shade_path<NX_MAT_PLASTIC, POWER, false, ANALYTIC, DETAIL>(S, bounce, frame, (uint32_t)index, pixelIdx, hu, hv, tri, inst, dir, tp, prevOrigin, emit, wantShadowRay, sh, wantTrace, updatePath, nextOrigin, nextDir, nextThroughput, nextPdf);
         }
         if (__ballot(alive && type == NX_MAT_DIELECTRIC) != 0ull) {
             if (alive && type == NX_MAT_DIELECTRIC)
-                shade_path<NX_MAT_DIELECTRIC, POWER, false, ANALYTIC>(S, bounce, frame, (uint32_t)index, pixelIdx, hu, hv, tri, inst, dir, tp, prevOrigin, emit, wantShadowRay, sh, wantTrace, updatePath, nextOrigin, nextDir, nextThroughput, nextPdf);
+                shade_path<NX_MAT_DIELECTRIC, POWER, false, ANALYTIC, DETAIL>(S, bounce, frame, (uint32_t)index, pixelIdx, hu, hv, tri, inst, dir, tp, prevOrigin, emit, wantShadowRay, sh, wantTrace, updatePath, nextOrigin, nextDir, nextThroughput, nextPdf);
         }
         if (__ballot(alive && type == NX_MAT_CONDUCTOR) != 0ull) {
             if (alive && type == NX_MAT_CONDUCTOR) {
                 if (S->conductorMode == NX_CONDUCTOR_EXTENDED)
-                    shade_path<NX_MAT_CONDUCTOR, POWER, false, ANALYTIC>(S, bounce, frame, (uint32_t)index, pixelIdx, hu, hv, tri, inst, dir, tp, prevOrigin, emit, wantShadowRay, sh, wantTrace, updatePath, nextOrigin, nextDir, nextThroughput, nextPdf);
+                    shade_path<NX_MAT_CONDUCTOR, POWER, false, ANALYTIC, DETAIL>(S, bounce, frame, (uint32_t)index, pixelIdx, hu, hv, tri, inst, dir, tp, prevOrigin, emit, wantShadowRay, sh, wantTrace, updatePath, nextOrigin, nextDir, nextThroughput, nextPdf);
                 else alive = false;  // (the reference's graph has no conductor kernel: such a path ends unshaded)
             }
         }
@@ -1443,6 +1463,7 @@ __global__ void __launch_bounds__(kTraceBlock) tail_kernel(const DeviceState* __
 // AccumulateKernel, Tonemap, LinearToGamma, ToColorUInt — PathTracer.cu:37-62, 480-496; Utils/Utils.h:51-54
 
 // (tonemap_rgba8: nx_tonemap.h — the denoiser's kernels write their RGBA8 image through the same text)
+#ifndef NX_WAVEFRONT_INSTANCES_ONLY
 
 // Running mean over `slices` consecutive frames per pixel, then tonemap.  src == nullptr: this context's own radiance
 // (slices = framesPerPass, the pass's frame numbers); otherwise externally gathered radiance laid out
@@ -1650,5 +1671,6 @@ const void* fmath_hook_kernel_ptr() { return (const void*)fmath_hook_kernel; }
 
 // the device-side layouts this translation unit was compiled with (nx_device.h layout_stamp; compared by nxhip_create)
 uint64_t layout_stamp_wavefront() { return layout_stamp(); }
+#endif  // NX_WAVEFRONT_INSTANCES_ONLY
 
 }  // namespace nxd

@@ -62,7 +62,7 @@ int nxd::fail_invalid(const std::string& msg) { return fail_invalid(msg.c_str())
 static int check_layouts()
 {
     const struct { const char* unit; uint64_t stamp; } units[] = {
-        {"nx_trace.hip", layout_stamp_trace()}, {"nx_wavefront.hip", layout_stamp_wavefront()}, {"nx_refit.hip", layout_stamp_refit()},
+        {"nx_trace.hip", layout_stamp_trace()}, {"nx_wavefront.hip", layout_stamp_wavefront()}, {"nx_wavefront_detail.hip", layout_stamp_wavefront_detail()}, {"nx_refit.hip", layout_stamp_refit()},
         {"nx_lbvh.hip", layout_stamp_lbvh()}, {"nxhip_multigpu.hip", layout_stamp_multigpu()}, {"nx_entry.hip", layout_stamp_entry()}, {"nx_aov.hip", layout_stamp_aov()},
         {"nx_adaptive.hip", layout_stamp_adaptive()}, {"nx_lights.hip", layout_stamp_lights()}, {"nx_envmap.hip", layout_stamp_envmap()}, {"nxhip_scene.hip", layout_stamp_scene()},
         {"nxhip_render.hip", layout_stamp_render()}, {"nxhip_features.hip", layout_stamp_features()}, {"nxhip_hooks.hip", layout_stamp_hooks()},
@@ -493,6 +493,11 @@ int nxhip_create(int device, uint32_t width, uint32_t height, void* stream, nxhi
             if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, tail_kernel_ptr(power != 0, true), kTraceBlockThreads, 0) != hipSuccess || perCU < 1) perCU = 2;
             c->tailBlocksAnalytic[power] = std::max(1, perCU) * c->numCUs;
         }
+        for (int power = 0; power < 2; power++)  // (... and the DETAIL instances of a context with normal or roughness maps)
+            for (int analytic = 0; analytic < 2; analytic++) {
+                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, tail_detail_kernel_ptr(power != 0, analytic != 0), kTraceBlockThreads, 0) != hipSuccess || perCU < 1) perCU = 2;
+                c->tailBlocksDetail[power][analytic] = std::max(1, perCU) * c->numCUs;
+            }
         // Launch-geometry knobs of the measurement sweeps.  They are read only when NX_TUNING_KNOBS=1 says
         // that a sweep is running: a stray variable in a user's environment does not reconfigure the product.
         if (const char* on = std::getenv("NX_TUNING_KNOBS"); on && std::atoi(on) == 1) {

@@ -208,18 +208,23 @@ int nxhip_tex2d_batch(nxhip_ctx* c, int kind, int textureId, const float* uv, ui
 {
     NX_CHECK_CTX(c);
     if ((!uv || !rgba) && count) return fail_invalid("nxhip_tex2d_batch: null buffer");
-    if (kind < 0 || kind > 2) return fail_invalid("nxhip_tex2d_batch: kind must be 0, 1 or 2");
+    if (kind < 0 || kind > 4) return fail_invalid("nxhip_tex2d_batch: kind must be 0 .. 4");
+    if (kind == 3 && (textureId < 0 || (size_t)textureId >= c->normalMaps.size())) return fail_invalid("nxhip_tex2d_batch: no such normal map");
+    if (kind == 4 && (textureId < 0 || (size_t)textureId >= c->roughnessMaps.size())) return fail_invalid("nxhip_tex2d_batch: no such roughness map");
     if (kind == 0 && (textureId < 0 || (size_t)textureId >= c->diffuseMaps.size())) return fail_invalid("nxhip_tex2d_batch: no such diffuse map");
     if (kind == 1 && (textureId < 0 || (size_t)textureId >= c->emissiveMaps.size())) return fail_invalid("nxhip_tex2d_batch: no such emissive map");
     if (kind == 2 && !c->hdrMap.texels.p) return fail_invalid("nxhip_tex2d_batch: no environment map has been uploaded");
     if (count == 0) return NXHIP_OK;
     NX_HIP(hipSetDevice(c->device));
-    const TextureHost& th = kind == 0 ? c->diffuseMaps[textureId] : kind == 1 ? c->emissiveMaps[textureId] : c->hdrMap;
+    const TextureHost& th = kind == 0 ? c->diffuseMaps[textureId] : kind == 1 ? c->emissiveMaps[textureId] : kind == 3 ? c->normalMaps[textureId] : kind == 4 ? c->roughnessMaps[textureId] : c->hdrMap;
     DevBuf dUv, dOut;
     NX_ALLOC(dUv, (size_t)count * 8);
     NX_ALLOC(dOut, (size_t)count * 16);
     NX_HIP(hipMemcpy(dUv.p, uv, (size_t)count * 8, hipMemcpyHostToDevice));
-    if (kind == 2 && c->hdrFloat) {  // a float environment map: its own lookup (nx_texture.h tex2d_float), alpha 1
+    if (kind >= 3) {  // a detail map: linear data, its own lookup (nx_texture.h tex2d_linear)
+        const TextureDev t{th.texels.as<uint32_t>(), th.width, th.height};
+        NX_HIP(launch_untimed(kernels::tex2d_linear_hook(), c->wideBlocks, kWideBlockThreads, c->stream, t, dUv.as<float>(), count, dOut.as<float4>()));
+    } else if (kind == 2 && c->hdrFloat) {  // a float environment map: its own lookup (nx_texture.h tex2d_float), alpha 1
         NX_HIP(launch_untimed(kernels::tex2d_float_hook(), c->wideBlocks, kWideBlockThreads, c->stream, th.texels.as<float4>(), (int)th.width, (int)th.height, dUv.as<float>(), count,
                               dOut.as<float4>()));
     } else {
@@ -367,6 +372,46 @@ try {
     NX_HIP(hipMemcpy(ok, dOk.p, (size_t)count * 4, hipMemcpyDeviceToHost));
     return NXHIP_OK;
 } NX_CATCH("nxhip_analytic_light_sample_batch")
+
+// ---- the detail maps' hook (shading_frame_hook_kernel) ----------------------------------------------
+
+int nxhip_shading_frame_batch(nxhip_ctx* c, uint32_t instanceIdx, const uint32_t* triIdx, const float* hitUv, const float* rayDir, uint32_t count, float* normalOut,
+                              float* roughnessOut, uint32_t* fellBack)
+try {
+    NX_DEBUG_HOOK("nxhip_shading_frame_batch");  // (first: a release library refuses whatever it is handed)
+    NX_CHECK_CTX(c);
+    if ((!triIdx || !hitUv || !rayDir || !normalOut || !roughnessOut || !fellBack) && count) return fail_invalid("nxhip_shading_frame_batch: null buffer");
+    NX_HIP(hipSetDevice(c->device));
+    NX_TRY(check_scene_ready(c));
+    if (instanceIdx >= c->hostInstances.size()) return fail_invalid("nxhip_shading_frame_batch: no such instance");
+    // the triangle index is followed without a bounds test on the device, as a hit record's is: checked here
+    const nx_bvh_instance& inst = c->hostInstances[instanceIdx];
+    if (inst.bvhIdx >= c->blas.size()) return fail_invalid("nxhip_shading_frame_batch: the instance refers to a BLAS id that has not been uploaded");
+    const uint32_t triCount = c->blas[inst.bvhIdx].triCount;
+    for (uint32_t k = 0; k < count; k++)
+        if (triIdx[k] >= triCount) return fail_invalid("nxhip_shading_frame_batch: triangle index out of range");
+    if (count == 0) return NXHIP_OK;
+    NX_TRY(refresh_updated_blas(c));
+    if (c->shadeInstDirty) NX_TRY(refresh_shade_inst(c));
+    NX_TRY(upload_state(c));
+    DevBuf dTri, dUv, dDir, dN, dR, dF;
+    NX_ALLOC(dTri, (size_t)count * 4);
+    NX_ALLOC(dUv, (size_t)count * 8);
+    NX_ALLOC(dDir, (size_t)count * 12);
+    NX_ALLOC(dN, (size_t)count * 12);
+    NX_ALLOC(dR, (size_t)count * 4);
+    NX_ALLOC(dF, (size_t)count * 4);
+    NX_HIP(hipMemcpy(dTri.p, triIdx, (size_t)count * 4, hipMemcpyHostToDevice));
+    NX_HIP(hipMemcpy(dUv.p, hitUv, (size_t)count * 8, hipMemcpyHostToDevice));
+    NX_HIP(hipMemcpy(dDir.p, rayDir, (size_t)count * 12, hipMemcpyHostToDevice));
+    NX_HIP(launch_untimed(kernels::shading_frame_hook(), c->wideBlocks, kWideBlockThreads, c->stream, c->dState.as<DeviceState>(), instanceIdx, dTri.as<uint32_t>(), dUv.as<float>(),
+                          dDir.as<float>(), count, dN.as<float>(), dR.as<float>(), dF.as<uint32_t>()));
+    NX_SYNC_ALL(c);
+    NX_HIP(hipMemcpy(normalOut, dN.p, (size_t)count * 12, hipMemcpyDeviceToHost));
+    NX_HIP(hipMemcpy(roughnessOut, dR.p, (size_t)count * 4, hipMemcpyDeviceToHost));
+    NX_HIP(hipMemcpy(fellBack, dF.p, (size_t)count * 4, hipMemcpyDeviceToHost));
+    return NXHIP_OK;
+} NX_CATCH("nxhip_shading_frame_batch")
 
 int nxhip_fmath_batch(nxhip_ctx* c, int op, const double* a, const double* b, uint32_t count, double* out)
 {

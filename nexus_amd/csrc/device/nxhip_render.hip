@@ -47,6 +47,13 @@ int nxd::check_scene_ready(nxhip_ctx* c)
         if (m.diffuseMapId < -1 || (m.diffuseMapId >= 0 && (size_t)m.diffuseMapId >= c->diffuseMaps.size())) return fail_invalid("a material refers to a diffuse map that has not been uploaded");
         if (m.emissiveMapId < -1 || (m.emissiveMapId >= 0 && (size_t)m.emissiveMapId >= c->emissiveMaps.size())) return fail_invalid("a material refers to an emissive map that has not been uploaded");
     }
+    // ... and the detail table (nxhip_set_material_detail): index-parallel to the materials, its ids into the normal / roughness maps
+    if (!c->hostMaterialDetail.empty() && c->hostMaterialDetail.size() != c->hostMaterials.size())
+        return fail_invalid("the material detail table does not have one entry per material (nxhip_set_material_detail)");
+    for (const nx_material_detail& d : c->hostMaterialDetail) {
+        if (d.normalMapId < -1 || (d.normalMapId >= 0 && (size_t)d.normalMapId >= c->normalMaps.size())) return fail_invalid("a material's detail entry refers to a normal map that has not been uploaded");
+        if (d.roughnessMapId < -1 || (d.roughnessMapId >= 0 && (size_t)d.roughnessMapId >= c->roughnessMaps.size())) return fail_invalid("a material's detail entry refers to a roughness map that has not been uploaded");
+    }
     for (const nx_light& l : c->hostLights)
         if (l.type == NX_LIGHT_MESH && l.mesh.meshId >= c->hostInstances.size()) return fail_invalid("a mesh light refers to an instance that does not exist");
     if (c->lightSampling == NXHIP_LIGHTS_POWER) {  // an instance has ONE place in the light table (DeviceState::instLight)
@@ -179,6 +186,11 @@ constexpr int kFlavorAnalytic = 1024;
 // (a wave-wide search multiplies in an order of its own; frames must be reproducible), and there is no tail kernel (tail_bounce).  A
 // TRANSMIT context over an all-opaque table keeps the bit clear and launches the default kernels.
 constexpr int kFlavorTransmit = 2048;
+// kFlavorDetail: some material names a normal or a roughness map (nxhip_set_material_detail) — the material kernels and the tail kernel
+// are their DETAIL instances (nx_wavefront_detail.hip), which read the instances' detail records.  It implies the general material
+// launch (there is no map-free DETAIL instance).  Not a specialisation a test may switch off: the default instances do not know such
+// maps.  A table of all -1, or none, keeps the bit clear and the graphs are the default ones.
+constexpr int kFlavorDetail = 4096;
 int pass_flavor(const nxhip_ctx* c)
 {
     int f = 0;
@@ -209,7 +221,8 @@ int pass_flavor(const nxhip_ctx* c)
     // passes are what a viewer or a rank of a tile split renders: four frames per pass 1 223 -> 1 335 Msamples/s, one frame 602 -> 620.
     if (!c->statsEnabled && c->passesInFlight <= 1u) f |= kFlavorThin;  // (the caller's setting, not effective_slots(): a timing replay of a run with passes in flight keeps that run's kernels)
     if ((c->h.sceneFlags & kSceneAllIdentity) && !c->statsEnabled) f |= kFlavorIdentity;  // (the counting variants have no such instance)
-    if (scan_pipeline(c) && !c->materialsNameMaps && !(f & kFlavorEnvMap)) f |= kFlavorNoMaps;
+    if (c->materialsNameDetail) f |= kFlavorDetail;
+    if (scan_pipeline(c) && !c->materialsNameMaps && !(f & kFlavorEnvMap) && !(f & kFlavorDetail)) f |= kFlavorNoMaps;
     if (c->h.alightCount) f |= kFlavorAnalytic;
     if (transmit_active(c)) f |= kFlavorTransmit;
     return f & ~(c->flavorForceGeneral & kFlavorSpecialised);  // (test hook: nxhip_debug_pass_flavor)
@@ -232,6 +245,7 @@ std::vector<std::vector<Launch>> frame_levels(nxhip_ctx* c, PassSlot* q)
     const bool identity = (pass_flavor(c) & kFlavorIdentity) != 0, noMaps = (pass_flavor(c) & kFlavorNoMaps) != 0;
     const bool analytic = (pass_flavor(c) & kFlavorAnalytic) != 0;
     const bool transmit = (pass_flavor(c) & kFlavorTransmit) != 0;
+    const bool detail = (pass_flavor(c) & kFlavorDetail) != 0;
     // the any-hit launch of a bounce: the TRANSMIT instance never hands over (no kTraceThinFlag) and has no IDENTITY form
     auto shadow_launch = [&](int shadowBlocksArg, int bounceArg, int thinFlagArg) {
         return transmit ? make_launch(kernels::trace_transmit(stats), shadowBlocksArg, kTraceBlockThreads, NXHIP_K_SHADOW, S, bounceArg)
@@ -285,14 +299,14 @@ std::vector<std::vector<Launch>> frame_levels(nxhip_ctx* c, PassSlot* q)
         const int tailFrom = tail_bounce(c);
         for (int bounce = 1; bounce <= pathLength; bounce++) {
             if (bounce == tailFrom) {  // the rest of the pass in one launch
-                levels.push_back({make_launch(kernels::tail(lightPower, analytic), analytic ? c->tailBlocksAnalytic[lightPower ? 1 : 0] : (lightPower ? c->tailBlocksPower : c->tailBlocks), kTraceBlockThreads, NXHIP_K_SHADE, S, bounce | kTraceScanFlag)});
+                levels.push_back({make_launch(kernels::tail(lightPower, analytic, detail), detail ? c->tailBlocksDetail[lightPower ? 1 : 0][analytic ? 1 : 0] : analytic ? c->tailBlocksAnalytic[lightPower ? 1 : 0] : (lightPower ? c->tailBlocksPower : c->tailBlocks), kTraceBlockThreads, NXHIP_K_SHADE, S, bounce | kTraceScanFlag)});
                 break;
             }
             int mask = (int)(c->materialTypeMask & 0xfu);
             if (c->h.conductorMode != NX_CONDUCTOR_EXTENDED) mask &= ~(1 << NX_MAT_CONDUCTOR);
             if (mask == 0) mask = 1 << NX_MAT_DIFFUSE;  // (a level cannot be empty)
             if (misses) mask |= 1 << kScanMiss;
-            levels.push_back({make_launch(kernels::shade_scan(lightPower, noMaps, analytic), og, kShadeBlockThreads, NXHIP_K_SHADE, S, bounce | dropFlag, mask)});
+            levels.push_back({make_launch(kernels::shade_scan(lightPower, noMaps, analytic, detail), og, kShadeBlockThreads, NXHIP_K_SHADE, S, bounce | dropFlag, mask)});
             if (bounce == 1) aov_beside(levels.back());
             if (in_use(NX_MAT_CONDUCTOR) && c->h.conductorMode != NX_CONDUCTOR_EXTENDED) {  // (counted, not shaded: count_scan_kernel)
                 levels.push_back({make_launch(kernels::count_scan(), lg, kWideBlockThreads, NXHIP_K_LOGIC, S, bounce, NX_MAT_CONDUCTOR)});
@@ -316,11 +330,11 @@ std::vector<std::vector<Launch>> frame_levels(nxhip_ctx* c, PassSlot* q)
         // graph insertion order of the reference: Diffuse, Plastic, Dielectric, Conductor (PathTracer.cpp:116-120)
         // (only the types some material of the scene has: a queue no material feeds stays empty)
         std::vector<Launch> shade;
-        if (in_use(NX_MAT_DIFFUSE)) shade.push_back(make_launch(kernels::shade(NX_MAT_DIFFUSE, lightPower, analytic), og, ob, NXHIP_K_SHADE, S, bounce));
-        if (in_use(NX_MAT_PLASTIC)) shade.push_back(make_launch(kernels::shade(NX_MAT_PLASTIC, lightPower, analytic), og, ob, NXHIP_K_SHADE, S, bounce));
-        if (in_use(NX_MAT_DIELECTRIC)) shade.push_back(make_launch(kernels::shade(NX_MAT_DIELECTRIC, lightPower, analytic), og, ob, NXHIP_K_SHADE, S, bounce));
-        if (in_use(NX_MAT_CONDUCTOR) && c->h.conductorMode == NX_CONDUCTOR_EXTENDED) shade.push_back(make_launch(kernels::shade(NX_MAT_CONDUCTOR, lightPower, analytic), og, ob, NXHIP_K_SHADE, S, bounce));
-        if (shade.empty()) shade.push_back(make_launch(kernels::shade(NX_MAT_DIFFUSE, lightPower, analytic), og, ob, NXHIP_K_SHADE, S, bounce));  // (a level cannot be empty)
+        if (in_use(NX_MAT_DIFFUSE)) shade.push_back(make_launch(kernels::shade(NX_MAT_DIFFUSE, lightPower, analytic, detail), og, ob, NXHIP_K_SHADE, S, bounce));
+        if (in_use(NX_MAT_PLASTIC)) shade.push_back(make_launch(kernels::shade(NX_MAT_PLASTIC, lightPower, analytic, detail), og, ob, NXHIP_K_SHADE, S, bounce));
+        if (in_use(NX_MAT_DIELECTRIC)) shade.push_back(make_launch(kernels::shade(NX_MAT_DIELECTRIC, lightPower, analytic, detail), og, ob, NXHIP_K_SHADE, S, bounce));
+        if (in_use(NX_MAT_CONDUCTOR) && c->h.conductorMode == NX_CONDUCTOR_EXTENDED) shade.push_back(make_launch(kernels::shade(NX_MAT_CONDUCTOR, lightPower, analytic, detail), og, ob, NXHIP_K_SHADE, S, bounce));
+        if (shade.empty()) shade.push_back(make_launch(kernels::shade(NX_MAT_DIFFUSE, lightPower, analytic, detail), og, ob, NXHIP_K_SHADE, S, bounce));  // (a level cannot be empty)
         // serial slot order needs the kernels one after the other
         for (auto& l : shade) levels.push_back({l});
         levels.push_back({make_launch(kernels::trace(false, stats, identity), traceBlocks, kTraceBlockThreads, NXHIP_K_TRACE, S, bounce | thinFlag),

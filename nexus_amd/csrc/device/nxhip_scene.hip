@@ -82,9 +82,20 @@ void nxd::refresh_see_through(nxhip_ctx* c)
     c->shadeInstDirty = true;  // (ShadeInst::seeThrough)
 }
 
+// After anything that changes the detail table (nxhip_set_material_detail): does some material name a normal or a roughness map
+// (kFlavorDetail reads the fact at every pass), and the per-instance records follow (refresh_shade_inst).
+void nxd::refresh_detail_maps(nxhip_ctx* c)
+{
+    c->materialsNameDetail = false;
+    for (const nx_material_detail& d : c->hostMaterialDetail) c->materialsNameDetail = c->materialsNameDetail || d.normalMapId != -1 || d.roughnessMapId != -1;
+    c->shadeInstDirty = true;
+}
+
 int nxd::refresh_shade_inst(nxhip_ctx* c)
 {
     const size_t n = c->hostInstances.size();
+    if (!c->hostMaterialDetail.empty() && c->hostMaterialDetail.size() != c->hostMaterialsDev.size())
+        return fail_invalid("the material detail table does not have one entry per material (nxhip_set_material_detail)");
     std::vector<nx_bvh_instance> inst(n);
     NX_SYNC_ALL(c);
     if (n) NX_HIP(hipMemcpy(inst.data(), c->instances.p, n * sizeof(nx_bvh_instance), hipMemcpyDeviceToHost));
@@ -106,6 +117,17 @@ int nxd::refresh_shade_inst(nxhip_ctx* c)
     NX_ALLOC(c->shadeInst, rec.size() * sizeof(ShadeInst));
     NX_HIP(hipMemcpy(c->shadeInst.p, rec.data(), rec.size() * sizeof(ShadeInst), hipMemcpyHostToDevice));
     c->h.shadeInst = c->shadeInst.as<ShadeInst>();
+    // the parallel array of detail records: entry i = the detail record of instance i's material; none while there is no table
+    if (c->hostMaterialDetail.empty()) {
+        c->shadeDetail = DevBuf();
+        c->h.shadeDetail = nullptr;
+    } else {
+        std::vector<nx_material_detail> det(std::max<size_t>(1, n), nx_material_detail{-1, -1, 1.0f, 0u});
+        for (size_t i = 0; i < n; i++) det[i] = c->hostMaterialDetail[(size_t)rec[i].materialId];
+        NX_ALLOC(c->shadeDetail, det.size() * sizeof(nx_material_detail));
+        NX_HIP(hipMemcpy(c->shadeDetail.p, det.data(), det.size() * sizeof(nx_material_detail), hipMemcpyHostToDevice));
+        c->h.shadeDetail = c->shadeDetail.as<nx_material_detail>();
+    }
     c->stateDirty = true;
     c->shadeInstDirty = false;
     // the traversal records' material codes follow the shading records (nx_refit.hip inst_code_kernel)
@@ -828,6 +850,26 @@ try {
     return NXHIP_OK;
 } NX_CATCH("nxhip_set_materials")
 
+// Detail maps (include/nexus_hip.h): the table is checked on the host before anything changes — a refused call leaves the previous table
+// where it is.  Ids are checked against the uploaded textures, and the count against the material table, when a pass is about to
+// follow them (check_scene_ready): a table may be set before its textures or its materials are.
+int nxhip_set_material_detail(nxhip_ctx* c, const nx_material_detail* details, uint32_t count)
+try {
+    NX_CHECK_CTX(c);
+    if (count && !details) return fail_invalid("nxhip_set_material_detail: null array");
+    for (uint32_t i = 0; i < count; i++) {
+        const std::string who = "nxhip_set_material_detail: entry " + std::to_string(i);
+        if (details[i].normalMapId < -1 || details[i].roughnessMapId < -1) return fail_invalid(who + ": a map id below -1");
+        if (!std::isfinite(details[i].normalScale)) return fail_invalid(who + ": normalScale is not finite");
+    }
+    NX_HIP(hipSetDevice(c->device));
+    NX_SYNC_ALL(c);
+    c->hostMaterialDetail.assign(details, details + (details ? count : 0));
+    for (nx_material_detail& d : c->hostMaterialDetail) d.pad_ = 0u;
+    refresh_detail_maps(c);  // (the pass graphs follow by their flavor: kFlavorDetail)
+    return NXHIP_OK;
+} NX_CATCH("nxhip_set_material_detail")
+
 int nxhip_set_lights(nxhip_ctx* c, const nx_light* lights, uint32_t count)
 try {
     NX_CHECK_CTX(c);
@@ -918,6 +960,8 @@ static int refresh_texture_tables(nxhip_ctx* c)
     NX_SYNC_ALL(c);
     NX_TRY(build(c->diffuseMaps, c->diffuseTable, c->h.diffuseMaps));
     NX_TRY(build(c->emissiveMaps, c->emissiveTable, c->h.emissiveMaps));
+    NX_TRY(build(c->normalMaps, c->normalTable, c->h.normalMaps));
+    NX_TRY(build(c->roughnessMaps, c->roughnessTable, c->h.roughnessMaps));
     c->h.hdrMap = TextureDev{c->hdrMap.texels.as<uint32_t>(), c->hdrMap.width, c->hdrMap.height};
     c->h.envFloat = c->hdrFloat ? c->hdrMap.texels.as<float4>() : nullptr;  // (a float map: hdrMap's pointer is tested, this one read)
     c->stateDirty = true;
@@ -1077,7 +1121,7 @@ try {
 int nxhip_upload_texture(nxhip_ctx* c, int kind, const uint8_t* rgba8, uint32_t width, uint32_t height, int32_t* texId)
 try {
     NX_CHECK_CTX(c);
-    if (!rgba8 || width == 0 || height == 0 || kind < 0 || kind > 2) return fail_invalid("nxhip_upload_texture: bad arguments");
+    if (!rgba8 || width == 0 || height == 0 || kind < 0 || kind > 4) return fail_invalid("nxhip_upload_texture: bad arguments");
     NX_HIP(hipSetDevice(c->device));
     TextureHost t;
     t.width = width;
@@ -1092,6 +1136,8 @@ try {
         refresh_see_through(c);  // (a material may have named this id before its texture existed)
     }
     else if (kind == 1) { c->emissiveMaps.push_back(std::move(t)); id = (int32_t)c->emissiveMaps.size() - 1; c->lightTableDirty = true; }
+    else if (kind == 3) { c->normalMaps.push_back(std::move(t)); id = (int32_t)c->normalMaps.size() - 1; }
+    else if (kind == 4) { c->roughnessMaps.push_back(std::move(t)); id = (int32_t)c->roughnessMaps.size() - 1; }
     else {
         NX_SYNC_ALL(c);
         c->hdrMap = std::move(t);
@@ -1138,6 +1184,8 @@ try {
     NX_SYNC_ALL(c);
     c->diffuseMaps.clear();
     c->emissiveMaps.clear();
+    c->normalMaps.clear();
+    c->roughnessMaps.clear();
     refresh_see_through(c);
     c->lightMapMeans = 0;
     c->lightTableDirty = true;

@@ -13,6 +13,10 @@ void AssetManager::Reset()
     m_InvalidMaterials.clear();
     m_DiffuseMaps.clear();
     m_EmissiveMaps.clear();
+    m_NormalMaps.clear();
+    m_RoughnessMaps.clear();
+    if (!m_MaterialDetails.empty()) detailsDirty = true;  // (the device must hear that the table is gone)
+    m_MaterialDetails.clear();
     m_Meshes.clear();
     m_Bvhs.clear();
     m_DeformedBvhs.clear();
@@ -94,7 +98,36 @@ int AssetManager::AddTexture(const Texture& texture)
         m_EmissiveMaps.push_back(texture);
         return static_cast<int>(m_EmissiveMaps.size()) - 1;
     }
+    if (texture.type == Texture::Type::NORMAL) {
+        m_NormalMaps.push_back(texture);
+        return static_cast<int>(m_NormalMaps.size()) - 1;
+    }
+    if (texture.type == Texture::Type::ROUGHNESS) {
+        m_RoughnessMaps.push_back(texture);
+        return static_cast<int>(m_RoughnessMaps.size()) - 1;
+    }
     return -1;
+}
+
+void AssetManager::SetMaterialDetail(int materialId, const MaterialDetail& detail)
+{
+    if (materialId < 0 || static_cast<size_t>(materialId) >= m_Materials.size()) throw std::runtime_error("AssetManager::SetMaterialDetail: no such material");
+    if (m_MaterialDetails.size() <= static_cast<size_t>(materialId)) m_MaterialDetails.resize(static_cast<size_t>(materialId) + 1);
+    m_MaterialDetails[static_cast<size_t>(materialId)] = detail;
+    detailsDirty = true;
+}
+
+void AssetManager::ClearMaterialDetails()
+{
+    m_MaterialDetails.clear();
+    detailsDirty = true;
+}
+
+std::vector<MaterialDetail> AssetManager::GetMaterialDetails() const
+{
+    std::vector<MaterialDetail> out = m_MaterialDetails;
+    if (!out.empty()) out.resize(m_Materials.size());  // (materials added since carry no maps)
+    return out;
 }
 
 void AssetManager::ApplyTextureToMaterial(int materialId, int diffuseMapId)

@@ -383,7 +383,9 @@ LoadedScene parse_glb(const std::string& file)
     std::map<std::pair<size_t, int>, int> decoded;  // (glTF texture, kind) -> index into out.textures
     auto load_texture = [&](const Json& texRef, Texture::Type kind) -> int {
         const size_t ti = static_cast<size_t>(texRef.at("index").num);
-        const auto key = std::make_pair(ti, kind == Texture::Type::DIFFUSE ? 0 : 1);
+        const bool detail = kind == Texture::Type::NORMAL || kind == Texture::Type::ROUGHNESS;
+        std::vector<Texture>& store = detail ? out.detailTextures : out.textures;
+        const auto key = std::make_pair(ti, kind == Texture::Type::DIFFUSE ? 0 : kind == Texture::Type::EMISSIVE ? 1 : kind == Texture::Type::NORMAL ? 2 : 3);
         const auto hit = decoded.find(key);
         if (hit != decoded.end()) return hit->second;
         int result = -1;
@@ -404,8 +406,8 @@ LoadedScene parse_glb(const std::string& file)
                 fail("glb: image without bufferView or uri");
             }
             t.type = kind;
-            result = static_cast<int>(out.textures.size());
-            out.textures.push_back(std::move(t));
+            result = static_cast<int>(store.size());
+            store.push_back(std::move(t));
         } catch (const std::exception& e) {
             out.warnings.push_back(std::string("texture ") + std::to_string(ti) + ": " + e.what());
         }
@@ -422,6 +424,21 @@ LoadedScene parse_glb(const std::string& file)
             if (const Json* t = m.find("emissiveTexture")) et = load_texture(*t, Texture::Type::EMISSIVE);
             out.materialDiffuseTexture.push_back(dt);
             out.materialEmissiveTexture.push_back(et);
+            // detail maps: set 0 and untransformed coordinates are all the triangles carry — the map is used with them, and the file's author is told
+            const Json* nt = m.find("normalTexture");
+            const Json* rt = nullptr;
+            if (const Json* pbr = m.find("pbrMetallicRoughness")) rt = pbr->find("metallicRoughnessTexture");
+            const std::pair<const Json*, const char*> refs[] = {{nt, "normalTexture"}, {rt, "metallicRoughnessTexture"}};
+            for (const auto& ref : refs) {
+                if (!ref.first) continue;
+                const int set = static_cast<int>(ref.first->number("texCoord", 0));
+                if (set != 0) out.warnings.push_back("material " + std::to_string(i) + ": " + ref.second + " uses texCoord " + std::to_string(set) + "; set 0 is used");
+                if (const Json* ext = ref.first->find("extensions"))
+                    if (ext->find("KHR_texture_transform")) out.warnings.push_back("material " + std::to_string(i) + ": " + ref.second + " carries KHR_texture_transform, which is ignored");
+            }
+            out.materialNormalTexture.push_back(nt ? load_texture(*nt, Texture::Type::NORMAL) : -1);
+            out.materialRoughnessTexture.push_back(rt ? load_texture(*rt, Texture::Type::ROUGHNESS) : -1);
+            out.materialNormalScale.push_back(nt ? static_cast<float>(nt->number("scale", 1.0)) : 1.0f);
         }
     if (out.materials.empty()) {
         Material m;  // pod.make_material() defaults
@@ -430,6 +447,9 @@ LoadedScene parse_glb(const std::string& file)
         out.materials.push_back(m);
         out.materialDiffuseTexture.push_back(-1);
         out.materialEmissiveTexture.push_back(-1);
+        out.materialNormalTexture.push_back(-1);
+        out.materialRoughnessTexture.push_back(-1);
+        out.materialNormalScale.push_back(1.0f);
     }
 
     // one mesh per primitive (what Assimp hands the reference, OBJLoader.cpp:165-181)
@@ -638,6 +658,9 @@ LoadedScene parse_obj(const std::string& file)
     out.materials.push_back(m);
     out.materialDiffuseTexture.push_back(-1);
     out.materialEmissiveTexture.push_back(-1);
+    out.materialNormalTexture.push_back(-1);
+    out.materialRoughnessTexture.push_back(-1);
+    out.materialNormalScale.push_back(1.0f);
     LoadedInstance inst;
     inst.name = file;
     out.instances.push_back(inst);
@@ -669,11 +692,21 @@ void OBJLoader::LoadOBJ(const std::string& path, const std::string& filename, Sc
     // textures first: a material carries the id its map got in the manager's diffuse / emissive list (OBJLoader.cpp:134-135, 157-158)
     std::vector<int> textureIds(ls.textures.size(), -1);
     for (size_t i = 0; i < ls.textures.size(); i++) textureIds[i] = assetManager->AddTexture(ls.textures[i]);
+    std::vector<int> detailIds(ls.detailTextures.size(), -1);
+    for (size_t i = 0; i < ls.detailTextures.size(); i++) detailIds[i] = assetManager->AddTexture(ls.detailTextures[i]);
     for (size_t i = 0; i < ls.materials.size(); i++) {
         Material m = ls.materials[i];
         if (ls.materialDiffuseTexture[i] >= 0) m.diffuseMapId = textureIds[static_cast<size_t>(ls.materialDiffuseTexture[i])];
         if (ls.materialEmissiveTexture[i] >= 0) m.emissiveMapId = textureIds[static_cast<size_t>(ls.materialEmissiveTexture[i])];
-        assetManager->AddMaterial(m);
+        const int id = assetManager->AddMaterial(m);
+        // detail maps: the ids their textures get in the manager's normal / roughness lists
+        if (ls.materialNormalTexture[i] >= 0 || ls.materialRoughnessTexture[i] >= 0) {
+            MaterialDetail d;
+            if (ls.materialNormalTexture[i] >= 0) d.normalMapId = detailIds[static_cast<size_t>(ls.materialNormalTexture[i])];
+            if (ls.materialRoughnessTexture[i] >= 0) d.roughnessMapId = detailIds[static_cast<size_t>(ls.materialRoughnessTexture[i])];
+            d.normalScale = ls.materialNormalScale[i];
+            assetManager->SetMaterialDetail(id, d);
+        }
     }
     // one BVH8 per mesh of the file (OBJLoader.cpp:213-239) — created together, so that a device builder can build them in one go
     std::vector<int32_t> meshIds;

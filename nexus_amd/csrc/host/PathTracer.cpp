@@ -163,6 +163,8 @@ void PathTracer::UpdateDeviceScene(const Scene& scene)
         Check(nxhip_clear_textures(m_Ctx), "nxhip_clear_textures");
         for (const Texture& t : assets.GetDiffuseMaps()) Check(nxhip_upload_texture(m_Ctx, 0, t.pixels.data(), t.width, t.height, nullptr), "nxhip_upload_texture");
         for (const Texture& t : assets.GetEmissiveMaps()) Check(nxhip_upload_texture(m_Ctx, 1, t.pixels.data(), t.width, t.height, nullptr), "nxhip_upload_texture");
+        for (const Texture& t : assets.GetNormalMaps()) Check(nxhip_upload_texture(m_Ctx, 3, t.pixels.data(), t.width, t.height, nullptr), "nxhip_upload_texture");
+        for (const Texture& t : assets.GetRoughnessMaps()) Check(nxhip_upload_texture(m_Ctx, 4, t.pixels.data(), t.width, t.height, nullptr), "nxhip_upload_texture");
         if (!scene.GetHDRMapFloat().pixels.empty()) Check(nxhip_upload_env_float(m_Ctx, scene.GetHDRMapFloat().pixels.data(), scene.GetHDRMapFloat().width, scene.GetHDRMapFloat().height), "nxhip_upload_env_float");
         else if (!scene.GetHDRMap().pixels.empty()) Check(nxhip_upload_texture(m_Ctx, 2, scene.GetHDRMap().pixels.data(), scene.GetHDRMap().width, scene.GetHDRMap().height, nullptr), "nxhip_upload_texture");
         mutableAssets.texturesDirty = false;
@@ -173,9 +175,16 @@ void PathTracer::UpdateDeviceScene(const Scene& scene)
         else Check(nxhip_upload_texture(m_Ctx, 2, scene.GetHDRMap().pixels.data(), scene.GetHDRMap().width, scene.GetHDRMap().height, nullptr), "nxhip_upload_texture");
         scene.hdrDirty = false;
     }
+    // the detail table runs parallel to the materials: it follows a change of either (count 0 while no material has detail maps)
+    const std::vector<MaterialDetail> details = assets.GetMaterialDetails();
+    const bool sendDetails = assets.detailsDirty || (assets.materialsDirty && !details.empty());
     if (assets.materialsDirty && !assets.GetMaterials().empty()) {
         Check(nxhip_set_materials(m_Ctx, assets.GetMaterials().data(), static_cast<uint32_t>(assets.GetMaterials().size())), "nxhip_set_materials");
         mutableAssets.materialsDirty = false;
+    }
+    if (sendDetails) {
+        Check(nxhip_set_material_detail(m_Ctx, details.data(), static_cast<uint32_t>(details.size())), "nxhip_set_material_detail");
+        mutableAssets.detailsDirty = false;
     }
     if (scene.tlasDirty && scene.UsesDeviceTlasBuild() && !scene.GetBVHInstances().empty()) {
         // the TLAS is built where it is used: instances (with the world bounds SetTransform gave them) go up, the tree never

@@ -75,6 +75,12 @@ class LoadedScene:
         self.textures = []            # list of (kind "diffuse" / "emissive", HxWx4 uint8 RGBA, row 0 = top)
         self.material_diffuse_texture = []   # per material: index into textures, -1 = none
         self.material_emissive_texture = []
+        # detail maps (glTF normalTexture and pbrMetallicRoughness.metallicRoughnessTexture, whose G channel is the roughness): linear data,
+        # a list of their own so that `textures` and its order stay what they were
+        self.detail_textures = []     # list of (kind "normal" / "roughness", HxWx4 uint8 RGBA, row 0 = top)
+        self.material_normal_texture = []      # per material: index into detail_textures, -1 = none
+        self.material_roughness_texture = []
+        self.material_normal_scale = []        # per material: normalTexture.scale (1.0 without one)
         self.analytic_lights = np.zeros(0, dtype=pod.ALIGHT_DT)  # glTF KHR_lights_punctual: one per node that carries a light, world space
         self.warnings = []
 
@@ -362,6 +368,7 @@ def load_glb(path):
         if key in decoded:
             return decoded[key]
         result = -1
+        store = out.detail_textures if kind in ("normal", "roughness") else out.textures
         try:
             img = doc["images"][doc["textures"][ref["index"]]["source"]]
             if "bufferView" in img:
@@ -372,8 +379,8 @@ def load_glb(path):
             else:
                 raise ValueError("image without bufferView or file uri")
             px, _ch = decode_image(raw)
-            result = len(out.textures)
-            out.textures.append((kind, px))
+            result = len(store)
+            store.append((kind, px))
         except Exception as e:  # the reference prints and carries on (IMGLoader.cpp:24-25)
             out.warnings.append("texture %d: %s" % (ref["index"], e))
         decoded[key] = result
@@ -384,8 +391,20 @@ def load_glb(path):
         et = m.get("emissiveTexture")
         out.material_diffuse_texture.append(load_texture(bt, "diffuse") if bt else -1)
         out.material_emissive_texture.append(load_texture(et, "emissive") if et else -1)
+        nt = m.get("normalTexture")
+        rt = m.get("pbrMetallicRoughness", {}).get("metallicRoughnessTexture")
+        for ref, what in ((nt, "normalTexture"), (rt, "metallicRoughnessTexture")):
+            # (set 0 and untransformed coordinates are all the triangles carry: the map is used with them, and the file's author is told)
+            if ref and int(ref.get("texCoord", 0)) != 0:
+                out.warnings.append("material %d: %s uses texCoord %d; set 0 is used" % (len(out.material_normal_texture), what, int(ref["texCoord"])))
+            if ref and "KHR_texture_transform" in ref.get("extensions", {}):
+                out.warnings.append("material %d: %s carries KHR_texture_transform, which is ignored" % (len(out.material_normal_texture), what))
+        out.material_normal_texture.append(load_texture(nt, "normal") if nt else -1)
+        out.material_roughness_texture.append(load_texture(rt, "roughness") if rt else -1)
+        out.material_normal_scale.append(float(nt.get("scale", 1.0)) if nt else 1.0)
     if not doc.get("materials"):
         out.material_diffuse_texture, out.material_emissive_texture = [-1], [-1]
+        out.material_normal_texture, out.material_roughness_texture, out.material_normal_scale = [-1], [-1], [1.0]
     mats = [_gltf_material(m) for m in doc.get("materials", [])]
     out.material_names = [m.get("name", "") for m in doc.get("materials", [])]
     out.materials = np.array(mats, dtype=pod.MAT_DT) if mats else np.array([pod.make_material()], dtype=pod.MAT_DT)
@@ -487,6 +506,7 @@ def load_obj(path):
     out.materials = np.array([pod.make_material(type=pod.MAT_PLASTIC, albedo=(0.6, 0.6, 0.6), roughness=1.0 - np.sqrt(20.0) / 31.62278)], dtype=pod.MAT_DT)
     out.material_names = ["default"]
     out.material_diffuse_texture, out.material_emissive_texture = [-1], [-1]
+    out.material_normal_texture, out.material_roughness_texture, out.material_normal_scale = [-1], [-1], [1.0]
     out.instances = [dict(mesh=0, material=0, position=np.zeros(3, np.float32), rotation=np.zeros(3, np.float32), scale=np.ones(3, np.float32), name=path)]
     return out
 

@@ -73,6 +73,10 @@ ALIGHT_DT = np.dtype([("position", "<f4", 3), ("radius", "<f4"), ("direction", "
                       ("innerConeAngle", "<f4"), ("outerConeAngle", "<f4"), ("type", "<u4"), ("pad_", "<u4")])
 assert ALIGHT_DT.itemsize == 64
 
+# nx_material_detail (extension, nxhip_set_material_detail): 16 bytes, index-parallel to the material table; -1 = no map
+DETAIL_DT = np.dtype([("normalMapId", "<i4"), ("roughnessMapId", "<i4"), ("normalScale", "<f4"), ("pad_", "<u4")])
+assert DETAIL_DT.itemsize == 16
+
 CAM_DT = np.dtype(
     {
         "names": ["position", "right", "up", "lensRadius", "lowerLeftCorner", "viewportX", "viewportY", "resolution"],
@@ -159,6 +163,13 @@ def make_material(type=MAT_DIFFUSE, albedo=(0.8, 0.8, 0.8), roughness=0.0, ior=1
     m["emissiveMapId"] = emissive_map
     m["type"] = type
     return m
+
+
+def make_material_detail(normal_map=-1, roughness_map=-1, normal_scale=1.0):
+    """one nx_material_detail: ids of nxhip_upload_texture kind 3 / 4 (-1: none) and glTF's normalTexture.scale"""
+    d = np.zeros((), dtype=DETAIL_DT)
+    d["normalMapId"], d["roughnessMapId"], d["normalScale"] = normal_map, roughness_map, normal_scale
+    return d
 
 
 def make_analytic_light(type=ALIGHT_POINT, position=(0, 0, 0), direction=(0, 0, -1), colour=(1, 1, 1), intensity=1.0, radius=0.0, angular_radius=0.0,

@@ -49,6 +49,10 @@ class Workload:
     light_sampling = pod.LIGHTS_UNIFORM
     # extension: pod.SHADOWS_TRANSMIT lets opacity and texture alpha attenuate shadow rays (nxhip_set_shadow_transmittance); applied by upload
     shadow_transmittance = pod.SHADOWS_OPAQUE
+    # extension: detail maps (nxhip_set_material_detail) — RGBA8 images of linear data and one pod.DETAIL_DT record per material; applied by upload
+    normal_maps = ()
+    roughness_maps = ()
+    material_detail = None
 
     def __init__(self, meshes, placements, materials=None, lights=None, camera=None, settings=None, diffuse_maps=(), emissive_maps=(),
                  hdr_map=None, build_threads=4):
@@ -114,6 +118,11 @@ class Workload:
             ctx.upload_texture("diffuse", img)
         for img in self.emissive_maps:
             ctx.upload_texture("emissive", img)
+        for img in self.normal_maps:
+            ctx.upload_texture("normal", img)
+        for img in self.roughness_maps:
+            ctx.upload_texture("roughness", img)
+        ctx.set_material_detail(self.material_detail if self.material_detail is not None else [])
         if self.hdr_map is not None:
             # a float32 H x W x 3 array is linear radiance (nxhip_upload_env_float); anything else the RGBA8 map it has always been
             if isinstance(self.hdr_map, np.ndarray) and self.hdr_map.dtype == np.float32:
