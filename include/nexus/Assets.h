@@ -47,6 +47,18 @@ struct AnalyticLight : nx_analytic_light {
 };
 static_assert(sizeof(AnalyticLight) == sizeof(nx_analytic_light), "AnalyticLight must alias nx_analytic_light");
 
+// Extension: fog — one homogeneous participating medium in a world-space box (nx_medium of nexus_pod.h; the rule: nexus_hip.h).
+// Scene::SetMedium places it.  The default is a unit box of no extinction (sigmaT 0: no medium), white albedo, isotropic.
+struct Medium : nx_medium {
+    Medium()
+    {
+        std::memset(static_cast<nx_medium*>(this), 0, sizeof(nx_medium));
+        boxMax[0] = boxMax[1] = boxMax[2] = 1.0f;
+        albedo[0] = albedo[1] = albedo[2] = 1.0f;
+    }
+};
+static_assert(sizeof(Medium) == sizeof(nx_medium), "Medium must alias nx_medium");
+
 // Extension: the detail maps of one material (nx_material_detail of nexus_pod.h; the shading rule: nexus_hip.h).  Ids are those
 // AssetManager::AddTexture returned for a NORMAL / a ROUGHNESS texture; -1: none.  AssetManager::SetMaterialDetail attaches one to a material.
 struct MaterialDetail : nx_material_detail {

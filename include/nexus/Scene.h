@@ -39,6 +39,11 @@ public:
     // Extension: lights that are no geometry (Assets.h AnalyticLight).  Sampled by the light sample only: invisible to camera and bounce rays.
     size_t AddAnalyticLight(const AnalyticLight& light);
     void RemoveAnalyticLight(size_t index);
+    // Extension: fog (Assets.h Medium) — one homogeneous medium in a world-space box, uploaded by PathTracer::UpdateDeviceScene
+    // (nxhip_set_medium, which validates it).  ClearMedium removes it: the device is then what it was without one.
+    void SetMedium(const Medium& medium) { m_Medium = medium; m_HasMedium = true; mediumDirty = true; }
+    void ClearMedium() { if (m_HasMedium) mediumDirty = true; m_HasMedium = false; }
+    const Medium* GetMedium() const { return m_HasMedium ? &m_Medium : nullptr; }  // nullptr: none
 
     // ---- editing: change a MeshInstance, then tell the scene which one --------------------------------------------
     std::vector<MeshInstance>& GetMeshInstances() { return m_MeshInstances; }
@@ -76,7 +81,7 @@ public:
     const FloatImage& GetHDRMapFloat() const { return m_HdrMapFloat; }  // pixels empty: the map is GetHDRMap()'s, or there is none
 
     // what the device has not seen yet (set here, cleared by PathTracer::UpdateDeviceScene)
-    mutable bool tlasDirty = true, lightsDirty = true, hdrDirty = false, analyticLightsDirty = false;
+    mutable bool tlasDirty = true, lightsDirty = true, hdrDirty = false, analyticLightsDirty = false, mediumDirty = false;
     // With SetTlasRefit(true): BVH-instance ids whose transform (and nothing else) changed since the device last saw the TLAS.
     // PathTracer::UpdateDeviceScene hands them to nxhip_set_instance_transforms — inverse, bounds, traversal records and the
     // TLAS refit happen in HBM — instead of uploading the tree again.
@@ -96,6 +101,8 @@ private:
     std::vector<BVHInstance> m_BVHInstances;    // what the TLAS and the device see, one per mesh instance
     std::vector<Light> m_Lights;
     std::vector<AnalyticLight> m_AnalyticLights;
+    Medium m_Medium;
+    bool m_HasMedium = false;
     std::shared_ptr<TLAS> m_Tlas;
 
     std::set<uint32_t> m_InvalidMeshInstances;

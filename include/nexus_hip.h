@@ -322,6 +322,61 @@ int nxhip_set_light_sampling(nxhip_ctx *ctx, int mode);
  * May be switched at any time, also between accumulated frames.  Another mode: NXHIP_ERR_INVALID. */
 enum { NXHIP_SHADOWS_OPAQUE = 0, NXHIP_SHADOWS_TRANSMIT = 1 };
 int nxhip_set_shadow_transmittance(nxhip_ctx *ctx, int mode);
+/* Extension — fog: ONE homogeneous participating medium per context, confined to a world-space axis-aligned box (nx_medium of nexus_pod.h:
+ * boxMin, boxMax, grey extinction sigmaT per world unit, Henyey-Greenstein asymmetry g, single-scattering albedo per channel).  Off by
+ * default.  The call replaces the medium; NULL removes it.  After NULL, or a medium with sigmaT == 0, the context is exactly what it was
+ * before the first call: the same flavor word, the same graphs, the same frames bit for bit.
+ *
+ * Validation, on the host — NXHIP_ERR_INVALID and the previous medium stays: a field that is not finite; sigmaT < 0; an albedo component
+ * outside [0, 1]; |g| > 0.99; boxMin[i] >= boxMax[i].
+ * Pipeline restriction of this first version: the medium needs the SCAN pipeline (NX_COMPACT_FAST) and pixel-keyed random numbers
+ * (NX_RNG_PIXEL_KEYED); while a medium with sigmaT > 0 is set, a render in any other mode is refused (NXHIP_ERR_INVALID, with a message
+ * that says so) — the classic pipeline and the slot-keyed stream have no stage of their own to draw from.
+ *
+ * THE RULE.  All arithmetic is binary32 without contraction; logf / expf / cosf / sinf are include/nexus_fmath.h's nxf_logf, nxf_expf,
+ * nxf_cosf, nxf_sinf.  It applies to every ray (o, d) of the closest-hit queue of bounce b >= 1 whose record says "shade this hit" (codes
+ * 1..4) or "miss" (code 7); tEnd = the record's t, or +inf for a miss.
+ *   segment    per axis i with d_i != 0: a_i = (boxMin_i - o_i) / d_i, b_i = (boxMax_i - o_i) / d_i; an axis with d_i == 0 contributes
+ *              (-inf, +inf) if boxMin_i <= o_i <= boxMax_i, otherwise the segment is empty.
+ *              t0 = max(0, max_i min(a_i, b_i)),  t1 = min(tEnd, min_i max(a_i, b_i)),  L = t1 - t0.
+ *              L <= 0 (or empty): the record is not touched and no random number is drawn.
+ *   flight     xi = the first number of the stream keyed by (global pixel, bounce b, frame, STAGE 256); stages 0 and 1 are the roulette's and
+ *              the material step's, and the key mixes bounce * 2 + stage + 1, so stage 2 of bounce b would be stage 0 of bounce b + 1: 256
+ *              lies past every value those two can form.  s = -logf(1.0f - xi) / sigmaT  (1 - xi is exact and lies in (0, 1]);  scatter iff s < L.
+ *              xi has 23 bits, so no flight exceeds -ln(2^-23) = 15.95 mean free paths: a box more than 15.95 / sigmaT deep is opaque
+ *              to the camera, where the true transmittance would be at most 1.2e-7.
+ *              No scatter: the record is not touched; the material launch shades the hit, or adds the miss, exactly as without a medium
+ *              (arriving has probability T = exp(-sigmaT L), so the throughput needs no factor).
+ *   scatter    at x = o + d * (t0 + s).  The record's code becomes 5 (kHitCodeMedium: no material type and no miss type looks at the
+ *              record again); t, u, v, the triangle and the instance bits stay (the feature buffers read them).
+ *              If the ray's roulette bit (kRaySurvives) is clear the path ends here.  Otherwise beta = tp.rgb / maxcomp(tp.rgb) as at a
+ *              surface ((1, 1, 1) at bounce 1), then beta *= albedo.  If b == pathLength the path ends.
+ *   light      taken when the surfaces' is (useMIS on, or analytic lights present), by the surfaces' own function: the same pick among
+ *   sample     nLights, the same count of random numbers per branch, in NXHIP_LIGHTS_UNIFORM and POWER, over mesh lights, analytic lights
+ *              and the sampled environment, continuing the medium's stream.  The origin is x with no offset (the offset vector is 0).  In
+ *              place of BSDF x cosine stands p(c), c = dot(d, omega) for the sampled direction omega:
+ *                p(c) = (1 - g*g) * (1 / (4 pi)) / (t * sqrtf(t)),  t = (1 + g*g) - (2 g) c;
+ *              p(c) is also the "BSDF pdf" of the power heuristic for mesh lights and the environment; analytic lights carry no weight.
+ *              (The function is handed the shading normal (0, 0, 1), whose frame rotation is the identity, and a zero geometric normal.)
+ *   continue   xi1, xi2 = the next numbers of the same stream, after the light sample's.  |g| < 1e-3: c = 1 - 2 xi1; otherwise
+ *              q = (1 - g*g) / ((1 - g) + (2 g) xi1),  c = ((1 + g*g) - q*q) / (2 g), clamped to [-1, 1].  sinT = sqrtf(max(0, 1 - c*c)),
+ *              phi = 6.28318531f * xi2; with (t0, t1) the branch-free orthonormal frame about d of Duff et al. 2017 (as for the analytic
+ *              lights), omega = normalize((t0 * (cosf(phi) sinT) + t1 * (sinf(phi) sinT)) + d * c).
+ *              The new ray starts at x (no offset) with throughput beta (phase / pdf is 1) and last pdf p(c); it is an ordinary sampled ray,
+ *              so x becomes the path's previous vertex.  Its roulette draw for bounce b + 1 is made as the material launch makes it.
+ *   shadow     every shadow request of a bounce — the material launch's and the medium vertex's alike — is attenuated before the any-hit
+ *   rays       launch reads it: Ls = the segment rule on (origin, direction, tEnd = tmax); if Ls > 0 the request's radiance is multiplied by
+ *              expf(-sigmaT * Ls); Ls <= 0: no multiplication at all, the bits of a request that does not cross the box are the default's.
+ *              Deterministic, and it composes with NXHIP_SHADOWS_TRANSMIT: the product is in the request before the crossings multiply.
+ * A medium whose box no camera ray, bounce ray or shadow ray crosses gives the frames of a context without one, bit for bit: its random
+ * numbers come from a stage nobody else reads.
+ * Out of scope: coloured extinction; more than one medium, or media bound to meshes; emission; heterogeneous density; an unbounded
+ * medium (a box larger than the scene serves: a sun's or an environment's shadow ray then has a finite Ls); the classic pipeline and the
+ * slot-keyed stream; a tail-kernel form (the tail kernel is off while a medium is set, as under NXHIP_SHADOWS_TRANSMIT); fog in the
+ * feature buffers (they keep the camera ray's surface hit).
+ * The two kernels of the medium (nx_medium.hip) are in the pass graphs only while a medium with sigmaT > 0 is set (bit 13 of
+ * nxhip_debug_pass_flavor's word); without it the graphs are launch for launch what they were. */
+int nxhip_set_medium(nxhip_ctx *ctx, const nx_medium *medium);
 /* PathTracer::UpdateDeviceScene / Scene::ToDevice — Renderer/PathTracer.cpp:305-308, Scene/Scene.cpp:115-140 */
 int nxhip_set_camera(nxhip_ctx *ctx, const nx_camera *camera);
 int nxhip_set_render_settings(nxhip_ctx *ctx, const nx_render_settings *settings);
@@ -696,6 +751,16 @@ int nxhip_env_eval_batch(nxhip_ctx *ctx, const float *direction, uint32_t count,
  * r outside [0, 1). */
 int nxhip_analytic_light_sample_batch(nxhip_ctx *ctx, uint32_t lightIndex, const float *origins3, const float *r2, uint32_t count,
                                       float *direction3, float *tmax, float *factor3, uint32_t *ok);
+/* The medium's rule on arrays — two test hooks over the device functions the medium's kernels call (a `make release` library refuses them).
+ * Both need a medium with sigmaT > 0 (NXHIP_ERR_INVALID otherwise, as for a NULL array or an input that is not finite or out of range).
+ * segment: for every k < count, origin[3k..], dir[3k..] (d as given: unit length is the caller's business), tEnd[k] > 0 (+inf allowed),
+ *          xi[k] in [0, 1): t0[k] and length[k] = the segment rule's t0 and L, both 0 where L <= 0 or the segment is empty;
+ *          transmittance[k] = expf(-sigmaT L), exactly 1 where L <= 0; scatterT[k] = t0 + s where the flight scatters (s < L), else -1.
+ * phase:   dirIn[3k..] = d (unit), xi1[k], xi2[k] in [0, 1): dirOut[3k..] = the continuation's omega, pdf[k] = p(dot(d, omega)) as the scatter
+ *          kernel stores it. */
+int nxhip_medium_segment_batch(nxhip_ctx *ctx, const float *origin, const float *dir, const float *tEnd, const float *xi, uint32_t count,
+                               float *t0, float *length, float *transmittance, float *scatterT);
+int nxhip_medium_phase_batch(nxhip_ctx *ctx, const float *dirIn, const float *xi1, const float *xi2, uint32_t count, float *dirOut, float *pdf);
 /* The three above work on an environment map of either kind (a float map's P(texel) follows nxhip_upload_env_float's weight).
  * read_env_float: the float map as it is stored, rgb = width x height x 3 floats, bit for bit what was uploaded (rgb NULL: only
  * *width / *height are written, which may be NULL too); NXHIP_ERR_INVALID while the environment map is not a float one or
@@ -782,7 +847,7 @@ static inline uint64_t nxhip_header_abi_stamp(void)
         sizeof(nx_bvh_instance), offsetof(nx_bvh_instance, transform), offsetof(nx_bvh_instance, materialId),
         sizeof(nx_material), offsetof(nx_material, emissive), offsetof(nx_material, type), sizeof(nx_light), offsetof(nx_light, type),
         sizeof(nx_analytic_light), offsetof(nx_analytic_light, direction), offsetof(nx_analytic_light, colour), offsetof(nx_analytic_light, innerConeAngle), offsetof(nx_analytic_light, type),
-        sizeof(nx_material_detail), offsetof(nx_material_detail, normalScale),
+        sizeof(nx_material_detail), offsetof(nx_material_detail, normalScale), sizeof(nx_medium),
         sizeof(nx_camera), offsetof(nx_camera, resolution), sizeof(nx_render_settings), offsetof(nx_render_settings, backgroundColor),
         sizeof(nx_ray), sizeof(nx_hit), sizeof(nx_bsdf_query), sizeof(nx_bsdf_result), offsetof(nx_bsdf_result, rngOut),
         sizeof(nxhip_queue_sizes), sizeof(nxhip_trace_stats), offsetof(nxhip_trace_stats, cycles), sizeof(nxhip_kernel_times), NXHIP_K_COUNT,

@@ -152,6 +152,11 @@ int nxs_scene_material_details(const nxs_scene *s, nx_material_detail *dst, uint
 int nxs_scene_remove_analytic_light(nxs_scene *s, uint32_t index);
 uint32_t nxs_scene_analytic_light_count(const nxs_scene *s);
 int nxs_scene_analytic_lights(const nxs_scene *s, nx_analytic_light *dst, uint32_t capacity);
+/* Extension: Scene::SetMedium / ClearMedium / GetMedium — fog, one homogeneous medium in a world-space box (nx_medium, nexus_pod.h), uploaded by
+ * the next device update (nxhip_set_medium, which validates it).  nxs_scene_medium: *has = 1 and *dst = the medium, or *has = 0 (dst may be NULL). */
+int nxs_scene_set_medium(nxs_scene *s, const nx_medium *medium);
+int nxs_scene_clear_medium(nxs_scene *s);
+int nxs_scene_medium(const nxs_scene *s, nx_medium *dst, int *has);
 uint32_t nxs_scene_instance_count(const nxs_scene *s);
 
 int nxs_pathtracer_create(uint32_t width, uint32_t height, int device, nxs_pathtracer **out);

@@ -12,6 +12,7 @@
  *   nx_light         12 B  Cuda/Scene/Light.cuh:4-33
  *   (nx_analytic_light 64 B: an extension, no reference layout)
  *   (nx_material_detail 16 B: an extension, no reference layout)
+ *   (nx_medium 48 B: an extension, no reference layout)
  *   nx_camera        88 B  Cuda/Scene/Camera.cuh:5-15
  *   nx_render_settings 20 B Cuda/Scene/Scene.cuh:10-17, Renderer/RenderSettings.h:4-10
  */
@@ -115,6 +116,15 @@ typedef struct nx_material_detail {
     uint32_t pad_;
 } nx_material_detail;
 NX_STATIC_ASSERT(sizeof(nx_material_detail) == 16, "nx_material_detail must be 16 bytes");
+
+/* Extension: one homogeneous participating medium ("fog") per context, confined to a world-space axis-aligned box (nxhip_set_medium; the
+ * rule is stated in full in include/nexus_hip.h). */
+typedef struct nx_medium {
+    float boxMin[3]; float sigmaT;   /* extinction per world unit, grey; 0 = no medium                        */
+    float boxMax[3]; float g;        /* Henyey-Greenstein asymmetry, forward > 0, |g| <= 0.99                 */
+    float albedo[3]; uint32_t pad;   /* single-scattering albedo sigma_s / sigma_t per channel, each in [0, 1] */
+} nx_medium;
+NX_STATIC_ASSERT(sizeof(nx_medium) == 48, "nx_medium must be 48 bytes");
 
 typedef struct NX_ALIGN(8) nx_camera {
     float position[3];

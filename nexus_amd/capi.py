@@ -38,6 +38,7 @@ HIP_SYMBOLS = [
     "nxhip_debug_read_primary_rays",
     "nxhip_set_shadow_transmittance", "nxhip_trace_transmittance_batch",
     "nxhip_set_material_detail", "nxhip_shading_frame_batch",
+    "nxhip_set_medium", "nxhip_medium_segment_batch", "nxhip_medium_phase_batch",
 ]
 HOST_SYMBOLS = [
     "nxh_bvh8_build", "nxh_tlas_build", "nxh_tlas_refit", "nxh_bvh8_refit", "nxh_bvh8_node_count", "nxh_bvh8_prim_count", "nxh_bvh8_nodes",
@@ -61,6 +62,7 @@ HOST_SYMBOLS = [
     "nxs_pathtracer_set_shadow_transmittance",
     "nxh_loaded_detail_texture_count", "nxh_loaded_detail_texture_info", "nxh_loaded_detail_texture_pixels", "nxh_loaded_material_detail",
     "nxs_scene_set_material_detail", "nxs_scene_clear_material_details", "nxs_scene_material_detail_count", "nxs_scene_material_details",
+    "nxs_scene_set_medium", "nxs_scene_clear_medium", "nxs_scene_medium",
 ]
 
 
@@ -102,7 +104,7 @@ def abi_words():
         pod.INST_DT.itemsize, off(pod.INST_DT, "transform"), off(pod.INST_DT, "materialId"),
         pod.MAT_DT.itemsize, off(pod.MAT_DT, "emissive"), off(pod.MAT_DT, "type"), pod.LIGHT_DT.itemsize, off(pod.LIGHT_DT, "type"),
         pod.ALIGHT_DT.itemsize, off(pod.ALIGHT_DT, "direction"), off(pod.ALIGHT_DT, "colour"), off(pod.ALIGHT_DT, "innerConeAngle"), off(pod.ALIGHT_DT, "type"),
-        pod.DETAIL_DT.itemsize, off(pod.DETAIL_DT, "normalScale"),
+        pod.DETAIL_DT.itemsize, off(pod.DETAIL_DT, "normalScale"), pod.MEDIUM_DT.itemsize,
         pod.CAM_DT.itemsize, off(pod.CAM_DT, "resolution"), pod.SETTINGS_DT.itemsize, off(pod.SETTINGS_DT, "backgroundColor"),
         pod.RAY_DT.itemsize, pod.HIT_DT.itemsize, pod.BSDF_QUERY_DT.itemsize, pod.BSDF_RESULT_DT.itemsize, off(pod.BSDF_RESULT_DT, "rngOut"),
         C.sizeof(QueueSizes), C.sizeof(TraceStats), TraceStats.cycles.offset, C.sizeof(KernelTimes), len(KERNEL_CLASSES),
@@ -563,6 +565,7 @@ FLAVOR_IDENTITY, FLAVOR_NO_MAPS = 256, 512  # Context.debug_pass_flavor: the spe
 FLAVOR_ANALYTIC = 1024  # ... and the instances of a context with analytic lights (set_analytic_lights)
 FLAVOR_DETAIL = 4096  # ... and the DETAIL instances of the material kernels: some material names a normal or a roughness map (set_material_detail)
 TEXTURE_KINDS = {"diffuse": 0, "emissive": 1, "hdr": 2, "normal": 3, "roughness": 4}  # nxhip_upload_texture / nxhip_tex2d_batch
+FLAVOR_MEDIUM = 8192  # ... and the medium's two launches per bounce: a medium with sigmaT > 0 is set (set_medium)
 FLAVOR_TRANSMIT = 2048  # ... and the any-hit TRANSMIT instance: SHADOWS_TRANSMIT over a table with a see-through material (set_shadow_transmittance)
 
 
@@ -637,6 +640,43 @@ class Context:
         details = np.ascontiguousarray(details, dtype=pod.DETAIL_DT).reshape(-1)
         self.L.nxhip_set_material_detail.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
         check(self.L.nxhip_set_material_detail(self.h, _ptr(details) if len(details) else None, len(details)), "nxhip_set_material_detail")
+
+    def set_medium(self, medium):
+        """fog: one homogeneous medium in a world-space box (a pod.MEDIUM_DT record, pod.make_medium); None removes it
+        (nxhip_set_medium: the rule is in include/nexus_hip.h)"""
+        self.L.nxhip_set_medium.argtypes = [C.c_void_p, C.c_void_p]
+        if medium is None:
+            check(self.L.nxhip_set_medium(self.h, None), "nxhip_set_medium")
+            return
+        m = np.ascontiguousarray(medium, dtype=pod.MEDIUM_DT).reshape(1)
+        check(self.L.nxhip_set_medium(self.h, _ptr(m)), "nxhip_set_medium")
+
+    def medium_segment_batch(self, origin, direction, t_end, xi):
+        """the medium's segment rule, transmittance and free flight for rays (origin[k], direction[k]) that end at t_end[k] (inf: a miss) with
+        the random number xi[k] in [0, 1) — a test hook: (t0, length, transmittance, scatter_t) float32[n] each; scatter_t is -1 where the
+        flight does not scatter"""
+        o = np.ascontiguousarray(origin, dtype=np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(direction, dtype=np.float32).reshape(-1, 3)
+        te = np.ascontiguousarray(t_end, dtype=np.float32).reshape(-1)
+        x = np.ascontiguousarray(xi, dtype=np.float32).reshape(-1)
+        assert len(o) == len(d) == len(te) == len(x)
+        out = [np.zeros(len(o), dtype=np.float32) for _ in range(4)]
+        self.L.nxhip_medium_segment_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        check(self.L.nxhip_medium_segment_batch(self.h, _ptr(o), _ptr(d), _ptr(te), _ptr(x), len(o), *[_ptr(a) for a in out]), "nxhip_medium_segment_batch")
+        return tuple(out)
+
+    def medium_phase_batch(self, dir_in, xi1, xi2):
+        """the continuation the medium's scatter kernel draws about the direction of travel dir_in[k] from (xi1[k], xi2[k]) in [0, 1)^2 — a test
+        hook: (direction float32[n, 3], pdf float32[n])"""
+        d = np.ascontiguousarray(dir_in, dtype=np.float32).reshape(-1, 3)
+        a = np.ascontiguousarray(xi1, dtype=np.float32).reshape(-1)
+        b = np.ascontiguousarray(xi2, dtype=np.float32).reshape(-1)
+        assert len(d) == len(a) == len(b)
+        out = np.zeros((len(d), 3), dtype=np.float32)
+        pdf = np.zeros(len(d), dtype=np.float32)
+        self.L.nxhip_medium_phase_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+        check(self.L.nxhip_medium_phase_batch(self.h, _ptr(d), _ptr(a), _ptr(b), len(d), _ptr(out), _ptr(pdf)), "nxhip_medium_phase_batch")
+        return out, pdf
 
     def shading_frame_batch(self, instance, tri_idx, hit_uv, ray_dir):
         """what the material kernels hand their sampling code for hits on triangles tri_idx[k] of `instance` at barycentrics hit_uv[k],
@@ -1500,6 +1540,24 @@ class Scene:
         out = np.zeros(int(self.L.nxs_scene_analytic_light_count(self.h)), dtype=pod.ALIGHT_DT)
         _scheck(self.L.nxs_scene_analytic_lights(self.h, _ptr(out) if len(out) else None, len(out)), "nxs_scene_analytic_lights")
         return out
+
+    def set_medium(self, medium):
+        """Scene::SetMedium (a pod.MEDIUM_DT record, pod.make_medium); None: Scene::ClearMedium"""
+        if medium is None:
+            self.L.nxs_scene_clear_medium.argtypes = [C.c_void_p]
+            _scheck(self.L.nxs_scene_clear_medium(self.h), "nxs_scene_clear_medium")
+            return
+        m = np.ascontiguousarray(medium, dtype=pod.MEDIUM_DT).reshape(1)
+        self.L.nxs_scene_set_medium.argtypes = [C.c_void_p, C.c_void_p]
+        _scheck(self.L.nxs_scene_set_medium(self.h, _ptr(m)), "nxs_scene_set_medium")
+
+    def medium(self):
+        """Scene::GetMedium: the record, or None"""
+        out = np.zeros(1, dtype=pod.MEDIUM_DT)
+        has = C.c_int(0)
+        self.L.nxs_scene_medium.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
+        _scheck(self.L.nxs_scene_medium(self.h, _ptr(out), C.byref(has)), "nxs_scene_medium")
+        return out[0] if has.value else None
 
     def instance_count(self):
         return int(self.L.nxs_scene_instance_count(self.h))

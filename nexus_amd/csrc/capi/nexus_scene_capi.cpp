@@ -373,6 +373,25 @@ int nxs_scene_analytic_lights(const nxs_scene* s, nx_analytic_light* dst, uint32
         for (size_t i = 0; i < al.size() && i < capacity; i++) dst[i] = al[i];
     });
 }
+int nxs_scene_set_medium(nxs_scene* s, const nx_medium* medium)
+{
+    return guarded([&] {
+        if (!medium) throw std::runtime_error("nxs_scene_set_medium: null medium (nxs_scene_clear_medium removes it)");
+        Medium m;
+        static_cast<nx_medium&>(m) = *medium;
+        s->scene.SetMedium(m);
+    });
+}
+int nxs_scene_clear_medium(nxs_scene* s) { return guarded([&] { s->scene.ClearMedium(); }); }
+int nxs_scene_medium(const nxs_scene* s, nx_medium* dst, int* has)
+{
+    return guarded([&] {
+        if (!has) throw std::runtime_error("nxs_scene_medium: null has");
+        const Medium* m = s->scene.GetMedium();
+        *has = m ? 1 : 0;
+        if (m && dst) *dst = *m;
+    });
+}
 uint32_t nxs_scene_instance_count(const nxs_scene* s) { return static_cast<uint32_t>(s->scene.GetBVHInstances().size()); }
 
 int nxs_pathtracer_create(uint32_t width, uint32_t height, int device, nxs_pathtracer** out)

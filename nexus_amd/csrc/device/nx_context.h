@@ -245,6 +245,7 @@ struct nxhip_ctx : nxd::PassSlot {
     // together change a pass (kFlavorTransmit): a TRANSMIT context over an all-opaque scene launches the default kernels.
     int shadowTransmittance = 0;  // NXHIP_SHADOWS_*
     bool materialsSeeThrough = false;
+    // nxhip_set_medium: the medium itself lives in the state block (h.medium, h.mediumOn: only a medium with sigmaT > 0 changes a pass — kFlavorMedium)
     int flavorForceGeneral = 0;  // nxhip_debug_pass_flavor: the kFlavor* bits of specialised kernel instances a pass must not use
     int lastPassFlavor = 0;      // pass_flavor() of the last pass issued (nxhip_debug_pass_flavor)
     bool thinInHooks = false;  // nxhip_debug_set_thin: the ray-batch hooks hand over and launch the thin kernel too

@@ -154,6 +154,9 @@ constexpr uint32_t kRaySurvives = 2u;     // SCAN pipeline: the Russian-roulette
 constexpr int kHitCodeShift = 29;
 constexpr uint32_t kHitInstMask = (1u << kHitCodeShift) - 1u;
 constexpr uint32_t kHitCodeMiss = 7u;
+// 5: the path scattered in the medium on its way to this hit or miss (nx_medium.hip medium_scatter_kernel, which rewrites the code between the
+// closest-hit launch and the material launch): no material type and no miss type looks at the record again
+constexpr uint32_t kHitCodeMedium = 5u;
 constexpr int kScanMiss = 4;  // the misses' place among the types of shade_scan_kernel (typeMask bit, ticket row)
 // the trace kernels' `bounce` argument: bounce | kTraceScanFlag = the SCAN pipeline's launch (ray set by bounce parity, codes in
 // the hit records); without the flag: rays[0], plain hit records (classic pipeline, ray-batch hooks)
@@ -460,6 +463,13 @@ struct DeviceState {
     const NX_G TextureDev* normalMaps;
     const NX_G TextureDev* roughnessMaps;
     const NX_G nx_material_detail* shadeDetail;  // [instanceCount]
+    // The medium (nxhip_set_medium; nx_medium.hip), all 0 while none with sigmaT > 0 is set.  Read only by the medium's two kernels, which
+    // pass graphs launch while mediumOn != 0 (kFlavorMedium), and by its hooks.  mediumG2 = g * g and mediumOneMinusG2 = 1 - g * g, formed on
+    // the host in binary32 as the rule states them.  Last in the block: nothing in front moves.
+    nx_medium medium;
+    float mediumG2, mediumOneMinusG2;
+    uint32_t mediumOn;
+    uint32_t padMedium_;
 };
 
 // Argument block of the adaptive update's kernels (nx_adaptive.hip; filled by nxhip_adaptive_update)
@@ -503,7 +513,7 @@ constexpr uint64_t layout_stamp()
     const uint64_t w[] = {
         sizeof(DeviceState), offsetof(DeviceState, camera), offsetof(DeviceState, envSampling), offsetof(DeviceState, localCount), offsetof(DeviceState, pixelMap),
         offsetof(DeviceState, radiance), offsetof(DeviceState, trace), offsetof(DeviceState, shadow), offsetof(DeviceState, material), offsetof(DeviceState, counters),
-        offsetof(DeviceState, frame), offsetof(DeviceState, traceStats), offsetof(DeviceState, scanStatus), offsetof(DeviceState, entry), offsetof(DeviceState, entryRuns), offsetof(DeviceState, debugRequeue), offsetof(DeviceState, aovAlbedo), offsetof(DeviceState, aovAccumNormalDepth), offsetof(DeviceState, basePixelMap), offsetof(DeviceState, adStats), offsetof(DeviceState, baseCount), offsetof(DeviceState, lightTable), offsetof(DeviceState, lightHeader), offsetof(DeviceState, lightGuideSize), offsetof(DeviceState, envFloat), offsetof(DeviceState, alights), offsetof(DeviceState, alightCount), offsetof(DeviceState, normalMaps), offsetof(DeviceState, shadeDetail), sizeof(nx_material_detail), sizeof(ALight), sizeof(LightEntry), sizeof(LightHeader), sizeof(LightBuild), offsetof(LightBuild, lightCount), sizeof(AdaptiveLaunch), offsetof(AdaptiveLaunch, baseCount), offsetof(DeviceState, thinStates), offsetof(DeviceState, leafOfInstance), sizeof(ThinState), offsetof(ThinState, stack), offsetof(DeviceState, thinClosest), offsetof(DeviceState, thinCapacity), offsetof(DeviceState, thinIters), offsetof(DeviceState, thinPoolLimit), offsetof(Counters, thinCount), sizeof(EntryState), offsetof(EntryState, sp), offsetof(EntryState, triP0), offsetof(EntryState, triInst), offsetof(Counters, scanTicket), offsetof(FrameState, scanEpoch),
+        offsetof(DeviceState, frame), offsetof(DeviceState, traceStats), offsetof(DeviceState, scanStatus), offsetof(DeviceState, entry), offsetof(DeviceState, entryRuns), offsetof(DeviceState, debugRequeue), offsetof(DeviceState, aovAlbedo), offsetof(DeviceState, aovAccumNormalDepth), offsetof(DeviceState, basePixelMap), offsetof(DeviceState, adStats), offsetof(DeviceState, baseCount), offsetof(DeviceState, lightTable), offsetof(DeviceState, lightHeader), offsetof(DeviceState, lightGuideSize), offsetof(DeviceState, envFloat), offsetof(DeviceState, alights), offsetof(DeviceState, alightCount), offsetof(DeviceState, normalMaps), offsetof(DeviceState, shadeDetail), offsetof(DeviceState, medium), offsetof(DeviceState, mediumG2), offsetof(DeviceState, mediumOn), sizeof(nx_medium), (uint64_t)kHitCodeMedium, sizeof(nx_material_detail), sizeof(ALight), sizeof(LightEntry), sizeof(LightHeader), sizeof(LightBuild), offsetof(LightBuild, lightCount), sizeof(AdaptiveLaunch), offsetof(AdaptiveLaunch, baseCount), offsetof(DeviceState, thinStates), offsetof(DeviceState, leafOfInstance), sizeof(ThinState), offsetof(ThinState, stack), offsetof(DeviceState, thinClosest), offsetof(DeviceState, thinCapacity), offsetof(DeviceState, thinIters), offsetof(DeviceState, thinPoolLimit), offsetof(Counters, thinCount), sizeof(EntryState), offsetof(EntryState, sp), offsetof(EntryState, triP0), offsetof(EntryState, triInst), offsetof(Counters, scanTicket), offsetof(FrameState, scanEpoch),
         (uint64_t)kScanKinds, (uint64_t)kScanWords, (uint64_t)kScanEpochLimit, (uint64_t)kShadeBlockOrderedThreads,
         sizeof(Counters), sizeof(RegionCounters), offsetof(RegionCounters, traceShadowSize), offsetof(RegionCounters, materialSize), offsetof(RegionCounters, traceHead),
         offsetof(RegionCounters, shadowHead), offsetof(RegionCounters, scanTile), offsetof(RegionCounters, endedSize), offsetof(Counters, orderedBase), offsetof(Counters, tailHead),

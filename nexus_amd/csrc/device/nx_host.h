@@ -40,6 +40,10 @@ const void* shade_scan_detail_kernel_ptr(bool lightPower, bool analytic);
 const void* tail_detail_kernel_ptr(bool lightPower, bool analytic);
 const void* shading_frame_hook_kernel_ptr();
 const void* tex2d_linear_hook_kernel_ptr();
+const void* medium_scatter_kernel_ptr(bool lightPower, bool analytic);  // nx_medium.hip: the medium's kernels (kFlavorMedium) and its hooks'
+const void* medium_shadow_kernel_ptr();
+const void* medium_segment_hook_kernel_ptr();
+const void* medium_phase_hook_kernel_ptr();
 const void* aov_kernel_ptr();  // nx_aov.hip
 const void* aov_fold_kernel_ptr();
 const void* denoise_gather_kernel_ptr();
@@ -57,6 +61,7 @@ const void* blas_refit_kernel_ptr();
 uint64_t layout_stamp_trace();
 uint64_t layout_stamp_wavefront();
 uint64_t layout_stamp_wavefront_detail();
+uint64_t layout_stamp_medium();
 uint64_t layout_stamp_refit();
 uint64_t layout_stamp_lbvh();
 uint64_t layout_stamp_multigpu();
@@ -145,6 +150,12 @@ inline Kernel<TextureDev, const float*, U32, float4*> tex2d_linear_hook() { retu
 inline Kernel<State, U32, const U32*, const float*, const float*, U32, float*, float*, U32*> shading_frame_hook() { return {shading_frame_hook_kernel_ptr()}; }
 // (S, light, origin, r, count, direction, tmax, factor, ok)
 inline Kernel<State, U32, const float*, const float*, U32, float*, float*, float*, U32*> alight_hook() { return {alight_hook_kernel_ptr()}; }
+inline BounceKernel medium_scatter(bool lightPower, bool analytic) { return {medium_scatter_kernel_ptr(lightPower, analytic)}; }  // (S, bounce | kShadeDropEnded)
+inline BounceKernel medium_shadow() { return {medium_shadow_kernel_ptr()}; }
+// (S, origin, dir, tEnd, xi, count, t0, length, transmittance, scatterT)
+inline Kernel<State, const float*, const float*, const float*, const float*, U32, float*, float*, float*, float*> medium_segment_hook() { return {medium_segment_hook_kernel_ptr()}; }
+// (S, dirIn, xi1, xi2, count, dirOut, pdf)
+inline Kernel<State, const float*, const float*, const float*, U32, float*, float*> medium_phase_hook() { return {medium_phase_hook_kernel_ptr()}; }
 inline StateKernel aov() { return {aov_kernel_ptr()}; }
 inline StateKernel aov_fold() { return {aov_fold_kernel_ptr()}; }
 inline Kernel<State, float4*, float4*, float4*, U32*> denoise_gather() { return {denoise_gather_kernel_ptr()}; }  // (S, colour, albedo, normalDepth, rgba8)

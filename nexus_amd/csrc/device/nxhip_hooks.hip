@@ -373,6 +373,78 @@ try {
     return NXHIP_OK;
 } NX_CATCH("nxhip_analytic_light_sample_batch")
 
+// ---- the medium's hooks (medium_segment_hook_kernel, medium_phase_hook_kernel) ----------------------
+
+// `n` floats of a hook's input or output, to or from the device
+static int medium_hook_in(DevBuf& d, const float* src, size_t n)
+{
+    NX_ALLOC(d, n * 4);
+    NX_HIP(hipMemcpy(d.p, src, n * 4, hipMemcpyHostToDevice));
+    return NXHIP_OK;
+}
+
+int nxhip_medium_segment_batch(nxhip_ctx* c, const float* origin, const float* dir, const float* tEnd, const float* xi, uint32_t count, float* t0, float* length,
+                               float* transmittance, float* scatterT)
+try {
+    NX_DEBUG_HOOK("nxhip_medium_segment_batch");  // (first: a release library refuses whatever it is handed)
+    NX_CHECK_CTX(c);
+    if (!c->h.mediumOn) return fail_invalid("nxhip_medium_segment_batch: no medium with sigmaT > 0 is set (nxhip_set_medium)");
+    if ((!origin || !dir || !tEnd || !xi || !t0 || !length || !transmittance || !scatterT) && count) return fail_invalid("nxhip_medium_segment_batch: null buffer");
+    for (size_t k = 0; k < (size_t)count * 3; k++)
+        if (!(origin[k] >= -3.0e38f && origin[k] <= 3.0e38f) || !(dir[k] >= -3.0e38f && dir[k] <= 3.0e38f)) return fail_invalid("nxhip_medium_segment_batch: origins and directions must be finite");
+    for (size_t k = 0; k < (size_t)count; k++) {
+        if (!(tEnd[k] > 0.0f)) return fail_invalid("nxhip_medium_segment_batch: tEnd must be positive (+inf allowed)");
+        if (!(xi[k] >= 0.0f && xi[k] < 1.0f)) return fail_invalid("nxhip_medium_segment_batch: xi must be in [0, 1)");
+    }
+    if (count == 0) return NXHIP_OK;
+    NX_HIP(hipSetDevice(c->device));
+    NX_TRY(upload_state(c));
+    DevBuf dO, dD, dT, dXi, dT0, dL, dTr, dS;
+    NX_TRY(medium_hook_in(dO, origin, (size_t)count * 3));
+    NX_TRY(medium_hook_in(dD, dir, (size_t)count * 3));
+    NX_TRY(medium_hook_in(dT, tEnd, count));
+    NX_TRY(medium_hook_in(dXi, xi, count));
+    NX_ALLOC(dT0, (size_t)count * 4);
+    NX_ALLOC(dL, (size_t)count * 4);
+    NX_ALLOC(dTr, (size_t)count * 4);
+    NX_ALLOC(dS, (size_t)count * 4);
+    NX_HIP(launch_untimed(kernels::medium_segment_hook(), c->wideBlocks, kWideBlockThreads, c->stream, c->dState.as<DeviceState>(), dO.as<float>(), dD.as<float>(), dT.as<float>(),
+                          dXi.as<float>(), count, dT0.as<float>(), dL.as<float>(), dTr.as<float>(), dS.as<float>()));
+    NX_SYNC_ALL(c);
+    NX_HIP(hipMemcpy(t0, dT0.p, (size_t)count * 4, hipMemcpyDeviceToHost));
+    NX_HIP(hipMemcpy(length, dL.p, (size_t)count * 4, hipMemcpyDeviceToHost));
+    NX_HIP(hipMemcpy(transmittance, dTr.p, (size_t)count * 4, hipMemcpyDeviceToHost));
+    NX_HIP(hipMemcpy(scatterT, dS.p, (size_t)count * 4, hipMemcpyDeviceToHost));
+    return NXHIP_OK;
+} NX_CATCH("nxhip_medium_segment_batch")
+
+int nxhip_medium_phase_batch(nxhip_ctx* c, const float* dirIn, const float* xi1, const float* xi2, uint32_t count, float* dirOut, float* pdf)
+try {
+    NX_DEBUG_HOOK("nxhip_medium_phase_batch");  // (first: a release library refuses whatever it is handed)
+    NX_CHECK_CTX(c);
+    if (!c->h.mediumOn) return fail_invalid("nxhip_medium_phase_batch: no medium with sigmaT > 0 is set (nxhip_set_medium)");
+    if ((!dirIn || !xi1 || !xi2 || !dirOut || !pdf) && count) return fail_invalid("nxhip_medium_phase_batch: null buffer");
+    for (size_t k = 0; k < (size_t)count * 3; k++)
+        if (!(dirIn[k] >= -3.0e38f && dirIn[k] <= 3.0e38f)) return fail_invalid("nxhip_medium_phase_batch: directions must be finite");
+    for (size_t k = 0; k < (size_t)count; k++)
+        if (!(xi1[k] >= 0.0f && xi1[k] < 1.0f) || !(xi2[k] >= 0.0f && xi2[k] < 1.0f)) return fail_invalid("nxhip_medium_phase_batch: xi1 and xi2 must be in [0, 1)");
+    if (count == 0) return NXHIP_OK;
+    NX_HIP(hipSetDevice(c->device));
+    NX_TRY(upload_state(c));
+    DevBuf dD, dX1, dX2, dOut, dPdf;
+    NX_TRY(medium_hook_in(dD, dirIn, (size_t)count * 3));
+    NX_TRY(medium_hook_in(dX1, xi1, count));
+    NX_TRY(medium_hook_in(dX2, xi2, count));
+    NX_ALLOC(dOut, (size_t)count * 12);
+    NX_ALLOC(dPdf, (size_t)count * 4);
+    NX_HIP(launch_untimed(kernels::medium_phase_hook(), c->wideBlocks, kWideBlockThreads, c->stream, c->dState.as<DeviceState>(), dD.as<float>(), dX1.as<float>(), dX2.as<float>(), count,
+                          dOut.as<float>(), dPdf.as<float>()));
+    NX_SYNC_ALL(c);
+    NX_HIP(hipMemcpy(dirOut, dOut.p, (size_t)count * 12, hipMemcpyDeviceToHost));
+    NX_HIP(hipMemcpy(pdf, dPdf.p, (size_t)count * 4, hipMemcpyDeviceToHost));
+    return NXHIP_OK;
+} NX_CATCH("nxhip_medium_phase_batch")
+
 // ---- the detail maps' hook (shading_frame_hook_kernel) ----------------------------------------------
 
 int nxhip_shading_frame_batch(nxhip_ctx* c, uint32_t instanceIdx, const uint32_t* triIdx, const float* hitUv, const float* rayDir, uint32_t count, float* normalOut,

@@ -144,6 +144,7 @@ int tail_bounce(const nxhip_ctx* c)
     // (the tail kernel traces its shadow rays with traverse_wave<true>, which knows no transmittance: a first version's restriction,
     //  DESIGN.md section 4 — the setting is ignored while the mode is in effect)
     if (transmit_active(c)) return 0;
+    if (c->h.mediumOn) return 0;  // (nor does the tail kernel know the medium: kFlavorMedium, below — the same restriction)
     int bounce = c->tailBounce;
     if (bounce < 0) {
         const double frames = pass_size_in_frames(c);
@@ -191,6 +192,11 @@ constexpr int kFlavorTransmit = 2048;
 // launch (there is no map-free DETAIL instance).  Not a specialisation a test may switch off: the default instances do not know such
 // maps.  A table of all -1, or none, keeps the bit clear and the graphs are the default ones.
 constexpr int kFlavorDetail = 4096;
+// kFlavorMedium: a medium with sigmaT > 0 is set (nxhip_set_medium) — every bounce gains two launches (nx_medium.hip): medium_scatter_kernel
+// in front of the material launch, medium_shadow_kernel in front of the any-hit launch; and there is no tail kernel (tail_bounce).  SCAN
+// pipeline and pixel-keyed random numbers only: render_pass refuses every other mode while the bit would be set.  Without a medium the bit
+// is clear and the graphs are the default ones, launch for launch.
+constexpr int kFlavorMedium = 8192;
 int pass_flavor(const nxhip_ctx* c)
 {
     int f = 0;
@@ -225,6 +231,7 @@ int pass_flavor(const nxhip_ctx* c)
     if (scan_pipeline(c) && !c->materialsNameMaps && !(f & kFlavorEnvMap) && !(f & kFlavorDetail)) f |= kFlavorNoMaps;
     if (c->h.alightCount) f |= kFlavorAnalytic;
     if (transmit_active(c)) f |= kFlavorTransmit;
+    if (c->h.mediumOn) f |= kFlavorMedium;
     return f & ~(c->flavorForceGeneral & kFlavorSpecialised);  // (test hook: nxhip_debug_pass_flavor)
 }
 
@@ -246,6 +253,7 @@ std::vector<std::vector<Launch>> frame_levels(nxhip_ctx* c, PassSlot* q)
     const bool analytic = (pass_flavor(c) & kFlavorAnalytic) != 0;
     const bool transmit = (pass_flavor(c) & kFlavorTransmit) != 0;
     const bool detail = (pass_flavor(c) & kFlavorDetail) != 0;
+    const bool medium = (pass_flavor(c) & kFlavorMedium) != 0;
     // the any-hit launch of a bounce: the TRANSMIT instance never hands over (no kTraceThinFlag) and has no IDENTITY form
     auto shadow_launch = [&](int shadowBlocksArg, int bounceArg, int thinFlagArg) {
         return transmit ? make_launch(kernels::trace_transmit(stats), shadowBlocksArg, kTraceBlockThreads, NXHIP_K_SHADOW, S, bounceArg)
@@ -266,10 +274,12 @@ std::vector<std::vector<Launch>> frame_levels(nxhip_ctx* c, PassSlot* q)
     auto thin_level = [&](int bounceArg) {
         if (!thinFlag) return;
         std::vector<Launch>& level = levels.back();
-        const int n = (int)level.size();  // 1: the primary level (closest-hit only); 2: closest-hit, any-hit
+        const int n = (int)level.size();  // the primary level: closest-hit only; a bounce's: closest-hit, [medium_shadow_kernel,] any-hit
         for (int k = 0; k < n; k++) {
-            if (k == 1 && transmit) continue;  // (no kThinAnyOnly launch: the TRANSMIT any-hit launch lists nothing)
-            Launch t = make_launch(kernels::thin(), thinBlocks, kTraceBlockThreads, NXHIP_K_THIN, S, bounceArg | (k == 0 ? kThinClosestOnly : kThinAnyOnly));
+            const bool closest = level[(size_t)k].klass == NXHIP_K_TRACE;
+            if (!closest && level[(size_t)k].klass != NXHIP_K_SHADOW) continue;  // (the medium's launch in front of the any-hit launch hands nothing over)
+            if (!closest && transmit) continue;  // (no kThinAnyOnly launch: the TRANSMIT any-hit launch lists nothing)
+            Launch t = make_launch(kernels::thin(), thinBlocks, kTraceBlockThreads, NXHIP_K_THIN, S, bounceArg | (closest ? kThinClosestOnly : kThinAnyOnly));
             t.after = k;
             level.push_back(t);
         }
@@ -306,13 +316,23 @@ std::vector<std::vector<Launch>> frame_levels(nxhip_ctx* c, PassSlot* q)
             if (c->h.conductorMode != NX_CONDUCTOR_EXTENDED) mask &= ~(1 << NX_MAT_CONDUCTOR);
             if (mask == 0) mask = 1 << NX_MAT_DIFFUSE;  // (a level cannot be empty)
             if (misses) mask |= 1 << kScanMiss;
+            // the medium's free-flight decision over the records the closest-hit level left, in front of the material launch that reads them
+            if (medium) levels.push_back({make_launch(kernels::medium_scatter(lightPower, analytic), whole_regions(wide), kShadeBlockThreads, NXHIP_K_SHADE, S, bounce | dropFlag)});
             levels.push_back({make_launch(kernels::shade_scan(lightPower, noMaps, analytic, detail), og, kShadeBlockThreads, NXHIP_K_SHADE, S, bounce | dropFlag, mask)});
             if (bounce == 1) aov_beside(levels.back());
             if (in_use(NX_MAT_CONDUCTOR) && c->h.conductorMode != NX_CONDUCTOR_EXTENDED) {  // (counted, not shaded: count_scan_kernel)
                 levels.push_back({make_launch(kernels::count_scan(), lg, kWideBlockThreads, NXHIP_K_LOGIC, S, bounce, NX_MAT_CONDUCTOR)});
             }
-            levels.push_back({make_launch(kernels::trace(false, stats, identity), traceBlocks, kTraceBlockThreads, NXHIP_K_TRACE, S, bounce | kTraceScanFlag | thinFlag),
-                              shadow_launch(shadowBlocks, bounce, thinFlag)});
+            if (medium) {
+                // the shadow requests' attenuation is chained to the any-hit launch alone: the closest-hit launch of the level does not wait for it
+                Launch anyHit = shadow_launch(shadowBlocks, bounce, thinFlag);
+                anyHit.after = 1;
+                levels.push_back({make_launch(kernels::trace(false, stats, identity), traceBlocks, kTraceBlockThreads, NXHIP_K_TRACE, S, bounce | kTraceScanFlag | thinFlag),
+                                  make_launch(kernels::medium_shadow(), wide, wideThreads, NXHIP_K_SHADE, S, bounce), anyHit});
+            } else {
+                levels.push_back({make_launch(kernels::trace(false, stats, identity), traceBlocks, kTraceBlockThreads, NXHIP_K_TRACE, S, bounce | kTraceScanFlag | thinFlag),
+                                  shadow_launch(shadowBlocks, bounce, thinFlag)});
+            }
             thin_level(bounce | kTraceScanFlag);
         }
         return levels;
@@ -521,6 +541,9 @@ try {
     NX_CHECK_CTX(c);
     NX_HIP(hipSetDevice(c->device));
     NX_TRY(check_scene_ready(c));
+    if (c->h.mediumOn && (!scan_pipeline(c) || c->h.rngMode != NX_RNG_PIXEL_KEYED))
+        return fail_invalid("a medium is set (nxhip_set_medium): it needs the SCAN pipeline (NX_COMPACT_FAST) and pixel-keyed random numbers (NX_RNG_PIXEL_KEYED) - "
+                            "the classic pipeline and the slot-keyed stream have no stage of their own to draw from; remove the medium or change the modes");
     if (c->adaptive && pass_pixels(c) == 0u) return NXHIP_OK;  // no active block: nothing is launched, the frame number stays
     struct PassFrames {  // what pass_size_in_frames (grids, tail rule, graph shape) sees while this pass is issued
         nxhip_ctx* c;

@@ -946,6 +946,38 @@ try {
     return NXHIP_OK;
 } NX_CATCH("nxhip_set_analytic_lights")
 
+// The medium (include/nexus_hip.h): checked on the host — a refused call leaves the previous medium where it is.  It rides in the state
+// block; a medium with sigmaT == 0 is no medium: the block is then what it was before the first call.
+int nxhip_set_medium(nxhip_ctx* c, const nx_medium* medium)
+try {
+    NX_CHECK_CTX(c);
+    nx_medium m;
+    std::memset(&m, 0, sizeof m);
+    if (medium) {
+        const float fields[] = {medium->boxMin[0], medium->boxMin[1], medium->boxMin[2], medium->sigmaT, medium->boxMax[0], medium->boxMax[1], medium->boxMax[2], medium->g,
+                                medium->albedo[0], medium->albedo[1], medium->albedo[2]};
+        for (const float f : fields)
+            if (!std::isfinite(f)) return fail_invalid("nxhip_set_medium: a field is not finite");
+        if (medium->sigmaT < 0.0f) return fail_invalid("nxhip_set_medium: sigmaT may not be negative");
+        for (int k = 0; k < 3; k++) {
+            if (medium->albedo[k] < 0.0f || medium->albedo[k] > 1.0f) return fail_invalid("nxhip_set_medium: every albedo component must lie in [0, 1]");
+            if (!(medium->boxMin[k] < medium->boxMax[k])) return fail_invalid("nxhip_set_medium: boxMin must be below boxMax on every axis");
+        }
+        if (std::fabs(medium->g) > 0.99f) return fail_invalid("nxhip_set_medium: |g| may not exceed 0.99");
+        if (medium->sigmaT > 0.0f) {
+            m = *medium;
+            m.pad = 0u;
+        }
+    }
+    c->h.medium = m;
+    c->h.mediumOn = m.sigmaT > 0.0f ? 1u : 0u;
+    c->h.mediumG2 = m.g * m.g;  // (binary32, as the rule states them)
+    c->h.mediumOneMinusG2 = c->h.mediumOn ? 1.0f - c->h.mediumG2 : 0.0f;
+    c->h.padMedium_ = 0u;
+    c->stateDirty = true;  // (the pass graphs follow by their flavor: kFlavorMedium)
+    return NXHIP_OK;
+} NX_CATCH("nxhip_set_medium")
+
 static int refresh_texture_tables(nxhip_ctx* c)
 {
     auto build = [&](std::vector<TextureHost>& v, DevBuf& table, const TextureDev*& dst) -> int {

@@ -225,6 +225,10 @@ void PathTracer::UpdateDeviceScene(const Scene& scene)
         Check(nxhip_set_analytic_lights(m_Ctx, al.data(), static_cast<uint32_t>(al.size())), "nxhip_set_analytic_lights");
         scene.analyticLightsDirty = false;
     }
+    if (scene.mediumDirty) {
+        Check(nxhip_set_medium(m_Ctx, scene.GetMedium()), "nxhip_set_medium");
+        scene.mediumDirty = false;
+    }
     const nx_camera cam = Camera::ToDevice(*scene.GetCamera());
     Check(nxhip_set_camera(m_Ctx, &cam), "nxhip_set_camera");
     Check(nxhip_set_render_settings(m_Ctx, reinterpret_cast<const nx_render_settings*>(&scene.GetRenderSettings())), "nxhip_set_render_settings");

@@ -24,6 +24,7 @@ void Scene::Reset()
     m_Lights.clear();
     if (!m_AnalyticLights.empty()) analyticLightsDirty = true;  // (the device must hear that they are gone)
     m_AnalyticLights.clear();
+    ClearMedium();
     m_AssetManager.Reset();
     m_Camera->Invalidate();
     m_TlasBuiltFor = 0;

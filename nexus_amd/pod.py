@@ -77,6 +77,10 @@ assert ALIGHT_DT.itemsize == 64
 DETAIL_DT = np.dtype([("normalMapId", "<i4"), ("roughnessMapId", "<i4"), ("normalScale", "<f4"), ("pad_", "<u4")])
 assert DETAIL_DT.itemsize == 16
 
+# nx_medium (extension, nxhip_set_medium): 48 bytes — fog, one homogeneous medium in a world-space box
+MEDIUM_DT = np.dtype([("boxMin", "<f4", 3), ("sigmaT", "<f4"), ("boxMax", "<f4", 3), ("g", "<f4"), ("albedo", "<f4", 3), ("pad", "<u4")])
+assert MEDIUM_DT.itemsize == 48
+
 CAM_DT = np.dtype(
     {
         "names": ["position", "right", "up", "lensRadius", "lowerLeftCorner", "viewportX", "viewportY", "resolution"],
@@ -187,3 +191,11 @@ def make_analytic_light(type=ALIGHT_POINT, position=(0, 0, 0), direction=(0, 0, 
     if type == ALIGHT_SPOT:
         l["innerConeAngle"], l["outerConeAngle"] = inner_cone, outer_cone
     return l
+
+
+def make_medium(box_min=(0, 0, 0), box_max=(1, 1, 1), sigma_t=0.0, g=0.0, albedo=(1, 1, 1)):
+    """one nx_medium: the world-space box, the grey extinction per world unit (0: no medium), the Henyey-Greenstein asymmetry (forward > 0)
+    and the single-scattering albedo per channel"""
+    m = np.zeros((), dtype=MEDIUM_DT)
+    m["boxMin"], m["boxMax"], m["sigmaT"], m["g"], m["albedo"] = box_min, box_max, sigma_t, g, albedo
+    return m

@@ -53,6 +53,8 @@ class Workload:
     normal_maps = ()
     roughness_maps = ()
     material_detail = None
+    # extension: fog — a pod.MEDIUM_DT record (pod.make_medium), None: no medium (nxhip_set_medium); applied by upload
+    medium = None
 
     def __init__(self, meshes, placements, materials=None, lights=None, camera=None, settings=None, diffuse_maps=(), emissive_maps=(),
                  hdr_map=None, build_threads=4):
@@ -135,6 +137,7 @@ class Workload:
         ctx.set_render_settings(self.settings)
         ctx.set_light_sampling(self.light_sampling)
         ctx.set_shadow_transmittance(self.shadow_transmittance)
+        ctx.set_medium(self.medium)
 
 
 def _look(eye, target, hfov, width, height):
