@@ -2,7 +2,7 @@
 // through the kept C++ host API: load a .glb / .obj, path-trace `frames` frames on an MI355X, write the image as a PPM.
 //
 //   nexus_render [--denoise] [--adaptive THRESHOLD [--max-frames N]] [--light-sampling uniform|power] [--transparent-shadows] [--env-float FILE.hdr] [--env-sampling]
-//                [--no-detail-maps] [--fog SIGMA [--fog-albedo R G B] [--fog-g G] [--fog-box X0 Y0 Z0 X1 Y1 Z1]]
+//                [--no-detail-maps] [--fog SIGMA [--fog-albedo R G B] [--fog-g G] [--fog-box X0 Y0 Z0 X1 Y1 Z1] [--fog-grid FILE.npy]]
 //                [--point-light X Y Z INTENSITY] [--sun DX DY DZ IRRADIANCE] <dir/> <file.glb|file.obj> <out.ppm> [width height frames pathLength]
 //                [eyeX eyeY eyeZ fwdX fwdY fwdZ hfovDeg]
 // --denoise: the feature buffers are accumulated with the colour and the image written is the a-trous filtered one (nxhip_denoise)
@@ -24,6 +24,8 @@
 // --fog SIGMA: a homogeneous medium of extinction SIGMA per world unit (Scene::SetMedium, nxhip_set_medium): light scatters in the air, so
 //   a spot light shows its cone and a sun its shafts.  --fog-albedo R G B (default 1 1 1), --fog-g G (Henyey-Greenstein asymmetry, default
 //   0), --fog-box X0 Y0 Z0 X1 Y1 Z1 (default: the scene's world bounds grown by 10 %).  Needs pixel-keyed random numbers: it switches them on.
+// --fog-grid FILE.npy: a density grid over the fog's box (Scene::SetMediumDensity, nxhip_set_medium_density) — a float32 .npy array of shape
+//   (nz, ny, nx); the extinction at a point becomes SIGMA x the trilinear lookup there: a cloud, not a haze.  Needs --fog; honours --fog-box.
 //
 // Build: make example   (links nexus_amd/lib/libnexus_amd.so)
 #include <cstdint>
@@ -33,6 +35,7 @@
 #include <string>
 #include <vector>
 
+#include "nexus/IMGLoader.h"
 #include "nexus/PathTracer.h"
 #include "nexus_hip.h"
 #include "nexus/Scene.h"
@@ -50,6 +53,7 @@ int main(int argc, char** argv)
     std::vector<nexus::AnalyticLight> extraLights;
     bool fog = false, fogBox = false;
     nexus::Medium medium;
+    std::string fogGrid;
     for (;;) {  // leading options, in any order
         const std::string opt = argc > 1 ? argv[1] : "";
         int used = 0;
@@ -87,6 +91,9 @@ int main(int argc, char** argv)
             fog = true;
             medium.sigmaT = static_cast<float>(std::atof(argv[2]));
             used = 2;
+        } else if (opt == "--fog-grid" && argc > 2) {
+            fogGrid = argv[2];
+            used = 2;
         } else if (opt == "--fog-g" && argc > 2) {
             medium.g = static_cast<float>(std::atof(argv[2]));
             used = 2;
@@ -114,8 +121,12 @@ int main(int argc, char** argv)
         argv += used;
         argc -= used;
     }
+    if (!fogGrid.empty() && !fog) {
+        std::fprintf(stderr, "nexus_render: --fog-grid needs --fog SIGMA (the grid scales the fog's extinction)\n");
+        return 2;
+    }
     if (argc < 4) {
-        std::fprintf(stderr, "usage: %s [--denoise] [--adaptive THRESHOLD [--max-frames N]] [--light-sampling uniform|power] [--transparent-shadows] [--env-float FILE.hdr] [--env-sampling] [--no-detail-maps] [--fog SIGMA [--fog-albedo R G B] [--fog-g G] [--fog-box X0 Y0 Z0 X1 Y1 Z1]] [--point-light X Y Z INTENSITY] [--sun DX DY DZ IRRADIANCE] <dir/> <file.glb|file.obj> <out.ppm> [width height frames pathLength] [eye(3) forward(3) hfov]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s [--denoise] [--adaptive THRESHOLD [--max-frames N]] [--light-sampling uniform|power] [--transparent-shadows] [--env-float FILE.hdr] [--env-sampling] [--no-detail-maps] [--fog SIGMA [--fog-albedo R G B] [--fog-g G] [--fog-box X0 Y0 Z0 X1 Y1 Z1] [--fog-grid FILE.npy]] [--point-light X Y Z INTENSITY] [--sun DX DY DZ IRRADIANCE] <dir/> <file.glb|file.obj> <out.ppm> [width height frames pathLength] [eye(3) forward(3) hfov]\n", argv[0]);
         return 2;
     }
     // a program built against these headers and run with another build of libnexus_amd.so gets an error string here, not a GPU fault
@@ -162,6 +173,10 @@ int main(int argc, char** argv)
                 }
             }
             scene.SetMedium(medium);
+            if (!fogGrid.empty()) {
+                const nexus::DensityGrid grid = nexus::IMGLoader::LoadNPYGrid(fogGrid);
+                scene.SetMediumDensity(grid.voxels.data(), grid.nx, grid.ny, grid.nz);
+            }
         }
 
         // NEXUS_DETERMINISTIC=1: pixel-keyed RNG, so the image does not depend on the order in which racing workgroups take

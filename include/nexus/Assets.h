@@ -87,6 +87,13 @@ struct FloatImage {
     std::vector<float> pixels;  // RGB, width x height x 3, row 0 first
 };
 
+// Extension: a fog density grid (Scene::SetMediumDensity, nxhip_set_medium_density; IMGLoader::LoadNPYGrid reads one from a .npy file):
+// nz x ny x nx voxels over the medium's box, x fastest.  Empty: none.
+struct DensityGrid {
+    uint32_t nx = 0, ny = 0, nz = 0;
+    std::vector<float> voxels;
+};
+
 struct Mesh {
     Mesh() = default;
     Mesh(const std::string& n, int32_t bId = -1, int32_t mId = -1, float3 p = make_float3(0.0f), float3 r = make_float3(0.0f), float3 s = make_float3(1.0f))

@@ -25,6 +25,11 @@ public:
     // The same RGBE reader (flat and run-length encoded scanlines), the same errors.
     static FloatImage LoadHDRFloat(const std::string& filepath);
     static FloatImage LoadHDRFloat(const unsigned char* data, size_t size);
+    // Extension: a fog density grid from a NumPy .npy file (format version 1.x or 2.x) that holds little-endian float32 ('<f4') in C order
+    // with the 3-D shape (nz, ny, nx) — what numpy.save writes for such an array.  Anything else (another dtype, Fortran order, another
+    // rank, a truncated file) is refused with a message.  The values are not judged here: nxhip_set_medium_density validates them.
+    static DensityGrid LoadNPYGrid(const std::string& filepath);
+    static DensityGrid LoadNPYGrid(const unsigned char* data, size_t size);
 };
 
 }  // namespace nexus

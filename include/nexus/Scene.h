@@ -44,6 +44,17 @@ public:
     void SetMedium(const Medium& medium) { m_Medium = medium; m_HasMedium = true; mediumDirty = true; }
     void ClearMedium() { if (m_HasMedium) mediumDirty = true; m_HasMedium = false; }
     const Medium* GetMedium() const { return m_HasMedium ? &m_Medium : nullptr; }  // nullptr: none
+    // Extension: the fog's density grid (Assets.h DensityGrid) — nz x ny x nx voxels over the medium's box, x fastest; the extinction at a
+    // point becomes sigmaT x the trilinear lookup there.  Copied here, uploaded by PathTracer::UpdateDeviceScene under its own dirty flag
+    // (nxhip_set_medium_density, which validates it); independent of SetMedium.  ClearMediumDensity: the medium is homogeneous again.
+    void SetMediumDensity(const float* voxels, uint32_t nx, uint32_t ny, uint32_t nz)
+    {
+        m_MediumDensity.nx = nx; m_MediumDensity.ny = ny; m_MediumDensity.nz = nz;
+        m_MediumDensity.voxels.assign(voxels, voxels + static_cast<size_t>(nx) * ny * nz);
+        mediumDensityDirty = true;
+    }
+    void ClearMediumDensity() { if (!m_MediumDensity.voxels.empty()) mediumDensityDirty = true; m_MediumDensity = DensityGrid(); }
+    const DensityGrid* GetMediumDensity() const { return m_MediumDensity.voxels.empty() ? nullptr : &m_MediumDensity; }  // nullptr: none
 
     // ---- editing: change a MeshInstance, then tell the scene which one --------------------------------------------
     std::vector<MeshInstance>& GetMeshInstances() { return m_MeshInstances; }
@@ -81,7 +92,7 @@ public:
     const FloatImage& GetHDRMapFloat() const { return m_HdrMapFloat; }  // pixels empty: the map is GetHDRMap()'s, or there is none
 
     // what the device has not seen yet (set here, cleared by PathTracer::UpdateDeviceScene)
-    mutable bool tlasDirty = true, lightsDirty = true, hdrDirty = false, analyticLightsDirty = false, mediumDirty = false;
+    mutable bool tlasDirty = true, lightsDirty = true, hdrDirty = false, analyticLightsDirty = false, mediumDirty = false, mediumDensityDirty = false;
     // With SetTlasRefit(true): BVH-instance ids whose transform (and nothing else) changed since the device last saw the TLAS.
     // PathTracer::UpdateDeviceScene hands them to nxhip_set_instance_transforms — inverse, bounds, traversal records and the
     // TLAS refit happen in HBM — instead of uploading the tree again.
@@ -103,6 +114,7 @@ private:
     std::vector<AnalyticLight> m_AnalyticLights;
     Medium m_Medium;
     bool m_HasMedium = false;
+    DensityGrid m_MediumDensity;
     std::shared_ptr<TLAS> m_Tlas;
 
     std::set<uint32_t> m_InvalidMeshInstances;

@@ -377,6 +377,53 @@ int nxhip_set_shadow_transmittance(nxhip_ctx *ctx, int mode);
  * The two kernels of the medium (nx_medium.hip) are in the pass graphs only while a medium with sigmaT > 0 is set (bit 13 of
  * nxhip_debug_pass_flavor's word); without it the graphs are launch for launch what they were. */
 int nxhip_set_medium(nxhip_ctx *ctx, const nx_medium *medium);
+/* Extension — fog density grid: a heterogeneous medium.  rho holds nz x ny x nx floats, x fastest, over the medium's box; the extinction at a
+ * point p of the box becomes sigmaT x rho(p).  The grid is copied before the call returns, belongs to the context and is independent of
+ * nxhip_set_medium, which leaves it alone: it modulates whichever medium is set, and takes effect only while a medium with sigmaT > 0 is
+ * set.  NULL removes it and releases its memory; the context is then exactly what it was before the first call: the same flavor word,
+ * graphs and frames.
+ *
+ * Validation, on the host and before anything is allocated — NXHIP_ERR_INVALID and the previous grid stays: a dimension of 0; a dimension
+ * above 512; more than 2^27 voxels; a value that is negative or not finite; a grid whose maximum is 0.
+ * A render — and the hook that walks — also refuses sigmaT x max(rho) x |boxMax - boxMin| > 512 (NXHIP_ERR_INVALID, with a message that
+ * says what to do): the walk below is bounded by 4096 iterations, and this keeps the bound out of reach.
+ *
+ * THE RULE.  All arithmetic is binary32 without contraction; logf is nxf_logf.  The segment t0, L, t1 = t0 + L of a ray (o, d) is the
+ * medium's segment rule above, unchanged; with L <= 0 nothing below happens.
+ *   lookup     n = (nx, ny, nz); vscale_i = n_i / (boxMax_i - boxMin_i), formed on the host in binary64 and rounded once.
+ *              g_i = (p_i - boxMin_i) * vscale_i - 0.5f,  i0 = floor(g_i),  f_i = g_i - floor(g_i); i0 and i0 + 1 are both clamped to
+ *              [0, n_i - 1] (clamp to edge).  rho(p) = three nested lerps a + f * (b - a): along x, then y, then z.  A constant grid
+ *              returns its constant exactly.
+ *   bricks     8 x 8 x 8 voxels each, nb_i = ceil(n_i / 8), the last one possibly partial.  M[b] = the maximum of rho over the voxels
+ *              [8 b_i - 1, 8 b_i + 8] per axis, clamped to the grid: the one-voxel apron is what the trilinear footprint of a point of the
+ *              brick can reach.  Built on the device in the call; the host keeps no copy of the voxels.
+ *              Brick space: u_i(t) = ((o_i + d_i t) - boxMin_i) * bscale_i,  bscale_i = n_i / (8 (boxMax_i - boxMin_i)), formed like vscale.
+ *   walk       start brick b_i = clamp(floor(u_i(t0)), 0, nb_i - 1).  The next boundary of an axis with d_i != 0:
+ *              tNext_i = (((b_i + [d_i > 0]) / bscale_i + boxMin_i) - o_i) / d_i — recomputed from the integer index after every step,
+ *              never accumulated; d_i == 0: tNext_i = +inf.  t = t0; tau = -logf(1.0f - xi), xi the next number of the stream (the first
+ *              tau is the stream's first number).  Per iteration:
+ *                ax = the axis of the smallest tNext (ties: the lowest axis); tExit = min(tNext_ax, t1); mu = sigmaT * M[b];
+ *                depth = mu * (tExit - t).
+ *                tau < depth: a TENTATIVE COLLISION — t += tau / mu, p = o + d * t, r = rho(p); the mode below decides; if the walk goes
+ *                  on it draws a new tau and stays in the brick.
+ *                otherwise: tau -= max(depth, 0); the walk ends if !(tNext_ax < t1); else t = tExit, b_ax moves by one (the walk ends if it
+ *                  leaves [0, nb_ax)) and tNext_ax is recomputed.
+ *              A brick with M == 0 costs one iteration and no random number.  Bound: 4096 iterations, brick steps and collisions together;
+ *              at the bound a free flight ends the path (absorbed, no continuation) and a shadow request gets T = 0.
+ *   free       the stream of the homogeneous flight, keyed (pixel, bounce, frame, stage 256).  At a tentative collision zeta = the next
+ *   flight     number; the collision is REAL iff zeta * M[b] < r, and the path then scatters at t: everything after it is the medium's
+ *              rule above, unchanged, continuing the same stream (code 5, beta, light sample, continuation, roulette).  A walk that ends
+ *              without a real collision does not touch the record.
+ *   shadow     ratio tracking, from a stream keyed (pixel, bounce, frame, STAGE 257), formed as the free flight forms its own (a path has
+ *   rays       at most one shadow request per bounce).  T = 1.0f; at every tentative collision T *= max(0.0f, 1.0f - r / M[b]) (a binary32
+ *              lerp may overshoot its corner maximum by an ulp); T == 0.0f ends the walk.  The request's radiance is multiplied by T only if
+ *              at least one tentative collision happened: a request that crosses no brick with M > 0 keeps the default's bits and draws
+ *              nothing.  It composes with NXHIP_SHADOWS_TRANSMIT as the homogeneous product does.
+ * The GRID instances of the medium's two kernels are in the pass graphs while a medium with sigmaT > 0 AND a grid are set (bit 14 of
+ * nxhip_debug_pass_flavor's word, beside bit 13); the homogeneous instances keep their code.
+ * Out of scope: coloured or per-channel density; emission; more than one grid; grids bound to meshes; animated grids beyond calling the
+ * setter again; residual or decomposition tracking; a tail-kernel form; fog in the feature buffers; file formats other than .npy. */
+int nxhip_set_medium_density(nxhip_ctx *ctx, const float *rho, uint32_t nx, uint32_t ny, uint32_t nz);
 /* PathTracer::UpdateDeviceScene / Scene::ToDevice — Renderer/PathTracer.cpp:305-308, Scene/Scene.cpp:115-140 */
 int nxhip_set_camera(nxhip_ctx *ctx, const nx_camera *camera);
 int nxhip_set_render_settings(nxhip_ctx *ctx, const nx_render_settings *settings);
@@ -761,6 +808,19 @@ int nxhip_analytic_light_sample_batch(nxhip_ctx *ctx, uint32_t lightIndex, const
 int nxhip_medium_segment_batch(nxhip_ctx *ctx, const float *origin, const float *dir, const float *tEnd, const float *xi, uint32_t count,
                                float *t0, float *length, float *transmittance, float *scatterT);
 int nxhip_medium_phase_batch(nxhip_ctx *ctx, const float *dirIn, const float *xi1, const float *xi2, uint32_t count, float *dirOut, float *pdf);
+/* The density grid's rule on arrays — three test hooks (a `make release` library refuses them).
+ * majorants: bricks[0..2] = nb; majorant (NULL: the counts alone) receives the nb[2] x nb[1] x nb[0] brick majorants as the device built
+ *          them, x fastest; capacity counts floats.  Needs a grid.
+ * density: rho[k] = the lookup at points3[3k..] (any finite point: clamp to edge), majorant[k] = M of the brick the walk's start rule gives
+ *          that point.  Needs a medium with sigmaT > 0 and a grid, as the next.
+ * track:   the walk in both modes for the ray origin[3k..], dir[3k..] that ends at tEnd[k] > 0 (+inf allowed); each mode starts from its own
+ *          copy of the xorshift32 state seed[k] != 0.  scatterT[k] = the parameter of the real collision, -1 where there is none;
+ *          transmittance[k] = the ratio tracking's T, exactly 1 where no tentative collision happened; steps2[2k] (free flight) and
+ *          steps2[2k + 1] (ratio tracking) = iterations | tentative collisions << 16, both 0 where the ray does not cross the box. */
+int nxhip_read_medium_majorants(nxhip_ctx *ctx, float *majorant, uint32_t capacity, uint32_t bricks[3]);
+int nxhip_medium_density_batch(nxhip_ctx *ctx, const float *points3, uint32_t count, float *rho, float *majorant);
+int nxhip_medium_track_batch(nxhip_ctx *ctx, const float *origin, const float *dir, const float *tEnd, const uint32_t *seed,
+                             uint32_t count, float *scatterT, float *transmittance, uint32_t *steps2);
 /* The three above work on an environment map of either kind (a float map's P(texel) follows nxhip_upload_env_float's weight).
  * read_env_float: the float map as it is stored, rgb = width x height x 3 floats, bit for bit what was uploaded (rgb NULL: only
  * *width / *height are written, which may be NULL too); NXHIP_ERR_INVALID while the environment map is not a float one or

@@ -157,6 +157,15 @@ int nxs_scene_analytic_lights(const nxs_scene *s, nx_analytic_light *dst, uint32
 int nxs_scene_set_medium(nxs_scene *s, const nx_medium *medium);
 int nxs_scene_clear_medium(nxs_scene *s);
 int nxs_scene_medium(const nxs_scene *s, nx_medium *dst, int *has);
+/* Extension: Scene::SetMediumDensity / ClearMediumDensity / GetMediumDensity — the fog's density grid, nz x ny x nx floats over the medium's
+ * box with x fastest, copied; uploaded by the next device update under its own dirty flag (nxhip_set_medium_density, which validates the
+ * values).  nxs_scene_medium_density: dims = (nx, ny, nz), all 0 while there is none; dst may be NULL (sizes only; dstCapacity in floats). */
+int nxs_scene_set_medium_density(nxs_scene *s, const float *rho, uint32_t nx, uint32_t ny, uint32_t nz);
+int nxs_scene_clear_medium_density(nxs_scene *s);
+int nxs_scene_medium_density(const nxs_scene *s, uint32_t dims[3], float *dst, size_t dstCapacity);
+/* IMGLoader::LoadNPYGrid on a file in memory: a NumPy .npy file, format 1.x or 2.x, '<f4', C order, 3-D shape (nz, ny, nx) — anything else is
+ * refused with a message (nxs_last_error).  dims = (nx, ny, nz); dst may be NULL (sizes only; dstCapacity in floats). */
+int nxh_decode_npy_grid(const uint8_t *data, size_t size, uint32_t dims[3], float *dst, size_t dstCapacity);
 uint32_t nxs_scene_instance_count(const nxs_scene *s);
 
 int nxs_pathtracer_create(uint32_t width, uint32_t height, int device, nxs_pathtracer **out);

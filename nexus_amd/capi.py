@@ -39,6 +39,7 @@ HIP_SYMBOLS = [
     "nxhip_set_shadow_transmittance", "nxhip_trace_transmittance_batch",
     "nxhip_set_material_detail", "nxhip_shading_frame_batch",
     "nxhip_set_medium", "nxhip_medium_segment_batch", "nxhip_medium_phase_batch",
+    "nxhip_set_medium_density", "nxhip_read_medium_majorants", "nxhip_medium_density_batch", "nxhip_medium_track_batch",
 ]
 HOST_SYMBOLS = [
     "nxh_bvh8_build", "nxh_tlas_build", "nxh_tlas_refit", "nxh_bvh8_refit", "nxh_bvh8_node_count", "nxh_bvh8_prim_count", "nxh_bvh8_nodes",
@@ -63,6 +64,7 @@ HOST_SYMBOLS = [
     "nxh_loaded_detail_texture_count", "nxh_loaded_detail_texture_info", "nxh_loaded_detail_texture_pixels", "nxh_loaded_material_detail",
     "nxs_scene_set_material_detail", "nxs_scene_clear_material_details", "nxs_scene_material_detail_count", "nxs_scene_material_details",
     "nxs_scene_set_medium", "nxs_scene_clear_medium", "nxs_scene_medium",
+    "nxs_scene_set_medium_density", "nxs_scene_clear_medium_density", "nxs_scene_medium_density", "nxh_decode_npy_grid",
 ]
 
 
@@ -542,6 +544,20 @@ def decode_png(data):
     return out, int(ch.value)
 
 
+def decode_npy_grid(data):
+    """IMGLoader::LoadNPYGrid on a .npy file in memory: the fog density grid it holds, float32 of shape (nz, ny, nx)."""
+    L = lib()
+    L.nxh_decode_npy_grid.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t]
+    buf = np.frombuffer(bytes(data), dtype=np.uint8)
+    dims = (C.c_uint32 * 3)()
+    if L.nxh_decode_npy_grid(_ptr(buf), len(buf), dims, None, 0) != 0:
+        raise NexusError("nxh_decode_npy_grid: " + L.nxs_last_error().decode())
+    out = np.zeros((dims[2], dims[1], dims[0]), dtype=np.float32)
+    if L.nxh_decode_npy_grid(_ptr(buf), len(buf), dims, _ptr(out), out.size) != 0:
+        raise NexusError("nxh_decode_npy_grid: " + L.nxs_last_error().decode())
+    return out
+
+
 def decode_hdr_float(data):
     """IMGLoader::LoadHDRFloat on a Radiance .hdr file in memory: HxWx3 float32 of linear radiance."""
     L = lib()
@@ -566,6 +582,7 @@ FLAVOR_ANALYTIC = 1024  # ... and the instances of a context with analytic light
 FLAVOR_DETAIL = 4096  # ... and the DETAIL instances of the material kernels: some material names a normal or a roughness map (set_material_detail)
 TEXTURE_KINDS = {"diffuse": 0, "emissive": 1, "hdr": 2, "normal": 3, "roughness": 4}  # nxhip_upload_texture / nxhip_tex2d_batch
 FLAVOR_MEDIUM = 8192  # ... and the medium's two launches per bounce: a medium with sigmaT > 0 is set (set_medium)
+FLAVOR_MEDIUM_GRID = 16384  # ... and their GRID instances: a medium with sigmaT > 0 and a density grid are set (set_medium_density)
 FLAVOR_TRANSMIT = 2048  # ... and the any-hit TRANSMIT instance: SHADOWS_TRANSMIT over a table with a see-through material (set_shadow_transmittance)
 
 
@@ -650,6 +667,51 @@ class Context:
             return
         m = np.ascontiguousarray(medium, dtype=pod.MEDIUM_DT).reshape(1)
         check(self.L.nxhip_set_medium(self.h, _ptr(m)), "nxhip_set_medium")
+
+    def set_medium_density(self, rho):
+        """fog density grid: a float32 array of shape (nz, ny, nx) over the medium's box — the extinction at p becomes sigmaT x rho(p), a
+        trilinear lookup; None removes it (nxhip_set_medium_density: the rule is in include/nexus_hip.h)"""
+        self.L.nxhip_set_medium_density.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]
+        if rho is None:
+            check(self.L.nxhip_set_medium_density(self.h, None, 0, 0, 0), "nxhip_set_medium_density")
+            return
+        r = np.ascontiguousarray(rho, dtype=np.float32)
+        assert r.ndim == 3, "a density grid has the shape (nz, ny, nx)"
+        nz, ny, nx = r.shape
+        check(self.L.nxhip_set_medium_density(self.h, _ptr(r), nx, ny, nz), "nxhip_set_medium_density")
+
+    def read_medium_majorants(self):
+        """the majorant bricks the device built from the density grid — a test hook: float32[nbz, nby, nbx]"""
+        nb = (C.c_uint32 * 3)()
+        self.L.nxhip_read_medium_majorants.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+        check(self.L.nxhip_read_medium_majorants(self.h, None, 0, nb), "nxhip_read_medium_majorants")
+        out = np.zeros((nb[2], nb[1], nb[0]), dtype=np.float32)
+        check(self.L.nxhip_read_medium_majorants(self.h, _ptr(out), out.size, nb), "nxhip_read_medium_majorants")
+        return out
+
+    def medium_density_batch(self, points):
+        """the density grid's lookup at points[k], and the majorant of the brick the walk would start in there — a test hook:
+        (rho float32[n], majorant float32[n])"""
+        p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+        rho, maj = np.zeros(len(p), dtype=np.float32), np.zeros(len(p), dtype=np.float32)
+        self.L.nxhip_medium_density_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+        check(self.L.nxhip_medium_density_batch(self.h, _ptr(p), len(p), _ptr(rho), _ptr(maj)), "nxhip_medium_density_batch")
+        return rho, maj
+
+    def medium_track_batch(self, origin, direction, t_end, seed):
+        """the walk through the density grid for rays (origin[k], direction[k]) that end at t_end[k] (inf: a miss), in both modes, each from
+        the xorshift32 state seed[k] != 0 — a test hook: (scatter_t float32[n], -1 where the free flight meets no real collision;
+        transmittance float32[n] of the ratio tracking; steps uint32[n, 2]: iterations | tentative collisions << 16 of the two walks)"""
+        o = np.ascontiguousarray(origin, dtype=np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(direction, dtype=np.float32).reshape(-1, 3)
+        te = np.ascontiguousarray(t_end, dtype=np.float32).reshape(-1)
+        sd = np.ascontiguousarray(seed, dtype=np.uint32).reshape(-1)
+        assert len(o) == len(d) == len(te) == len(sd)
+        st, tr = np.zeros(len(o), dtype=np.float32), np.zeros(len(o), dtype=np.float32)
+        steps = np.zeros((len(o), 2), dtype=np.uint32)
+        self.L.nxhip_medium_track_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        check(self.L.nxhip_medium_track_batch(self.h, _ptr(o), _ptr(d), _ptr(te), _ptr(sd), len(o), _ptr(st), _ptr(tr), _ptr(steps)), "nxhip_medium_track_batch")
+        return st, tr, steps
 
     def medium_segment_batch(self, origin, direction, t_end, xi):
         """the medium's segment rule, transmittance and free flight for rays (origin[k], direction[k]) that end at t_end[k] (inf: a miss) with
@@ -1550,6 +1612,28 @@ class Scene:
         m = np.ascontiguousarray(medium, dtype=pod.MEDIUM_DT).reshape(1)
         self.L.nxs_scene_set_medium.argtypes = [C.c_void_p, C.c_void_p]
         _scheck(self.L.nxs_scene_set_medium(self.h, _ptr(m)), "nxs_scene_set_medium")
+
+    def set_medium_density(self, rho):
+        """Scene::SetMediumDensity (float32 of shape (nz, ny, nx)); None: Scene::ClearMediumDensity"""
+        if rho is None:
+            self.L.nxs_scene_clear_medium_density.argtypes = [C.c_void_p]
+            _scheck(self.L.nxs_scene_clear_medium_density(self.h), "nxs_scene_clear_medium_density")
+            return
+        r = np.ascontiguousarray(rho, dtype=np.float32)
+        assert r.ndim == 3, "a density grid has the shape (nz, ny, nx)"
+        self.L.nxs_scene_set_medium_density.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]
+        _scheck(self.L.nxs_scene_set_medium_density(self.h, _ptr(r), r.shape[2], r.shape[1], r.shape[0]), "nxs_scene_set_medium_density")
+
+    def medium_density(self):
+        """Scene::GetMediumDensity: float32 of shape (nz, ny, nx), or None"""
+        dims = (C.c_uint32 * 3)()
+        self.L.nxs_scene_medium_density.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+        _scheck(self.L.nxs_scene_medium_density(self.h, dims, None, 0), "nxs_scene_medium_density")
+        if dims[0] == 0:
+            return None
+        out = np.zeros((dims[2], dims[1], dims[0]), dtype=np.float32)
+        _scheck(self.L.nxs_scene_medium_density(self.h, dims, _ptr(out), out.size), "nxs_scene_medium_density")
+        return out
 
     def medium(self):
         """Scene::GetMedium: the record, or None"""

@@ -392,6 +392,43 @@ int nxs_scene_medium(const nxs_scene* s, nx_medium* dst, int* has)
         if (m && dst) *dst = *m;
     });
 }
+int nxs_scene_set_medium_density(nxs_scene* s, const float* rho, uint32_t nx, uint32_t ny, uint32_t nz)
+{
+    return guarded([&] {
+        if (!rho) throw std::runtime_error("nxs_scene_set_medium_density: null grid (nxs_scene_clear_medium_density removes it)");
+        if (nx == 0 || ny == 0 || nz == 0 || nx > 512 || ny > 512 || nz > 512) throw std::runtime_error("nxs_scene_set_medium_density: every dimension must lie in 1 .. 512");
+        s->scene.SetMediumDensity(rho, nx, ny, nz);
+    });
+}
+int nxs_scene_clear_medium_density(nxs_scene* s) { return guarded([&] { s->scene.ClearMediumDensity(); }); }
+int nxs_scene_medium_density(const nxs_scene* s, uint32_t dims[3], float* dst, size_t dstCapacity)
+{
+    return guarded([&] {
+        if (!dims) throw std::runtime_error("nxs_scene_medium_density: null dims");
+        const DensityGrid* g = s->scene.GetMediumDensity();
+        dims[0] = g ? g->nx : 0u;
+        dims[1] = g ? g->ny : 0u;
+        dims[2] = g ? g->nz : 0u;
+        if (g && dst) {
+            if (dstCapacity < g->voxels.size()) throw std::runtime_error("nxs_scene_medium_density: destination too small");
+            std::memcpy(dst, g->voxels.data(), g->voxels.size() * sizeof(float));
+        }
+    });
+}
+int nxh_decode_npy_grid(const uint8_t* data, size_t size, uint32_t dims[3], float* dst, size_t dstCapacity)
+{
+    return guarded([&] {
+        if (!data || !dims) throw std::runtime_error("nxh_decode_npy_grid: null argument");
+        const DensityGrid g = IMGLoader::LoadNPYGrid(data, size);
+        dims[0] = g.nx;
+        dims[1] = g.ny;
+        dims[2] = g.nz;
+        if (dst) {
+            if (dstCapacity < g.voxels.size()) throw std::runtime_error("nxh_decode_npy_grid: destination too small");
+            std::memcpy(dst, g.voxels.data(), g.voxels.size() * sizeof(float));
+        }
+    });
+}
 uint32_t nxs_scene_instance_count(const nxs_scene* s) { return static_cast<uint32_t>(s->scene.GetBVHInstances().size()); }
 
 int nxs_pathtracer_create(uint32_t width, uint32_t height, int device, nxs_pathtracer** out)

@@ -246,6 +246,11 @@ struct nxhip_ctx : nxd::PassSlot {
     int shadowTransmittance = 0;  // NXHIP_SHADOWS_*
     bool materialsSeeThrough = false;
     // nxhip_set_medium: the medium itself lives in the state block (h.medium, h.mediumOn: only a medium with sigmaT > 0 changes a pass — kFlavorMedium)
+    // nxhip_set_medium_density: the voxels and the majorant bricks built from them (both empty: no grid; the state block's words follow by
+    // refresh_medium_grid), and the grid's maximum from the validation pass — the host's only knowledge of the voxels (render-time thickness check)
+    nxd::DevBuf mediumRho, mediumBricks;
+    uint32_t mediumGridN[3] = {0, 0, 0};
+    float mediumRhoMax = 0.0f;
     int flavorForceGeneral = 0;  // nxhip_debug_pass_flavor: the kFlavor* bits of specialised kernel instances a pass must not use
     int lastPassFlavor = 0;      // pass_flavor() of the last pass issued (nxhip_debug_pass_flavor)
     bool thinInHooks = false;  // nxhip_debug_set_thin: the ray-batch hooks hand over and launch the thin kernel too

@@ -470,6 +470,21 @@ struct DeviceState {
     float mediumG2, mediumOneMinusG2;
     uint32_t mediumOn;
     uint32_t padMedium_;
+    // The medium's density grid (nxhip_set_medium_density; nx_medium.hip), nullptr / 0 while there is none.  Read only by the GRID instances
+    // of the medium's two kernels, which pass graphs launch while a medium with sigmaT > 0 AND a grid are set (kFlavorMediumGrid), and by
+    // the grid's hooks.  mediumRho: [n.z][n.y][n.x] voxels, x fastest; mediumBricks: [nb.z][nb.y][nb.x] majorants of 8 x 8 x 8 voxels and
+    // their one-voxel apron, built on the device.  vscale_i = n_i / (boxMax_i - boxMin_i) and bscale_i = vscale_i / 8, formed on the host in
+    // binary64 from the medium's box and rounded once (refresh_medium_grid).  Last in the block: nothing in front moves.
+    const NX_G float* mediumRho;
+    const NX_G float* mediumBricks;
+    uint32_t mediumN[3];
+    uint32_t padGrid0_;
+    uint32_t mediumNb[3];
+    uint32_t padGrid1_;
+    float mediumVscale[3];
+    float padGrid2_;
+    float mediumBscale[3];
+    float padGrid3_;
 };
 
 // Argument block of the adaptive update's kernels (nx_adaptive.hip; filled by nxhip_adaptive_update)
@@ -513,7 +528,7 @@ constexpr uint64_t layout_stamp()
     const uint64_t w[] = {
         sizeof(DeviceState), offsetof(DeviceState, camera), offsetof(DeviceState, envSampling), offsetof(DeviceState, localCount), offsetof(DeviceState, pixelMap),
         offsetof(DeviceState, radiance), offsetof(DeviceState, trace), offsetof(DeviceState, shadow), offsetof(DeviceState, material), offsetof(DeviceState, counters),
-        offsetof(DeviceState, frame), offsetof(DeviceState, traceStats), offsetof(DeviceState, scanStatus), offsetof(DeviceState, entry), offsetof(DeviceState, entryRuns), offsetof(DeviceState, debugRequeue), offsetof(DeviceState, aovAlbedo), offsetof(DeviceState, aovAccumNormalDepth), offsetof(DeviceState, basePixelMap), offsetof(DeviceState, adStats), offsetof(DeviceState, baseCount), offsetof(DeviceState, lightTable), offsetof(DeviceState, lightHeader), offsetof(DeviceState, lightGuideSize), offsetof(DeviceState, envFloat), offsetof(DeviceState, alights), offsetof(DeviceState, alightCount), offsetof(DeviceState, normalMaps), offsetof(DeviceState, shadeDetail), offsetof(DeviceState, medium), offsetof(DeviceState, mediumG2), offsetof(DeviceState, mediumOn), sizeof(nx_medium), (uint64_t)kHitCodeMedium, sizeof(nx_material_detail), sizeof(ALight), sizeof(LightEntry), sizeof(LightHeader), sizeof(LightBuild), offsetof(LightBuild, lightCount), sizeof(AdaptiveLaunch), offsetof(AdaptiveLaunch, baseCount), offsetof(DeviceState, thinStates), offsetof(DeviceState, leafOfInstance), sizeof(ThinState), offsetof(ThinState, stack), offsetof(DeviceState, thinClosest), offsetof(DeviceState, thinCapacity), offsetof(DeviceState, thinIters), offsetof(DeviceState, thinPoolLimit), offsetof(Counters, thinCount), sizeof(EntryState), offsetof(EntryState, sp), offsetof(EntryState, triP0), offsetof(EntryState, triInst), offsetof(Counters, scanTicket), offsetof(FrameState, scanEpoch),
+        offsetof(DeviceState, frame), offsetof(DeviceState, traceStats), offsetof(DeviceState, scanStatus), offsetof(DeviceState, entry), offsetof(DeviceState, entryRuns), offsetof(DeviceState, debugRequeue), offsetof(DeviceState, aovAlbedo), offsetof(DeviceState, aovAccumNormalDepth), offsetof(DeviceState, basePixelMap), offsetof(DeviceState, adStats), offsetof(DeviceState, baseCount), offsetof(DeviceState, lightTable), offsetof(DeviceState, lightHeader), offsetof(DeviceState, lightGuideSize), offsetof(DeviceState, envFloat), offsetof(DeviceState, alights), offsetof(DeviceState, alightCount), offsetof(DeviceState, normalMaps), offsetof(DeviceState, shadeDetail), offsetof(DeviceState, medium), offsetof(DeviceState, mediumG2), offsetof(DeviceState, mediumOn), offsetof(DeviceState, mediumRho), offsetof(DeviceState, mediumBricks), offsetof(DeviceState, mediumN), offsetof(DeviceState, mediumNb), offsetof(DeviceState, mediumVscale), offsetof(DeviceState, mediumBscale), sizeof(nx_medium), (uint64_t)kHitCodeMedium, sizeof(nx_material_detail), sizeof(ALight), sizeof(LightEntry), sizeof(LightHeader), sizeof(LightBuild), offsetof(LightBuild, lightCount), sizeof(AdaptiveLaunch), offsetof(AdaptiveLaunch, baseCount), offsetof(DeviceState, thinStates), offsetof(DeviceState, leafOfInstance), sizeof(ThinState), offsetof(ThinState, stack), offsetof(DeviceState, thinClosest), offsetof(DeviceState, thinCapacity), offsetof(DeviceState, thinIters), offsetof(DeviceState, thinPoolLimit), offsetof(Counters, thinCount), sizeof(EntryState), offsetof(EntryState, sp), offsetof(EntryState, triP0), offsetof(EntryState, triInst), offsetof(Counters, scanTicket), offsetof(FrameState, scanEpoch),
         (uint64_t)kScanKinds, (uint64_t)kScanWords, (uint64_t)kScanEpochLimit, (uint64_t)kShadeBlockOrderedThreads,
         sizeof(Counters), sizeof(RegionCounters), offsetof(RegionCounters, traceShadowSize), offsetof(RegionCounters, materialSize), offsetof(RegionCounters, traceHead),
         offsetof(RegionCounters, shadowHead), offsetof(RegionCounters, scanTile), offsetof(RegionCounters, endedSize), offsetof(Counters, orderedBase), offsetof(Counters, tailHead),

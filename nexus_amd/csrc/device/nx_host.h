@@ -44,6 +44,11 @@ const void* medium_scatter_kernel_ptr(bool lightPower, bool analytic);  // nx_me
 const void* medium_shadow_kernel_ptr();
 const void* medium_segment_hook_kernel_ptr();
 const void* medium_phase_hook_kernel_ptr();
+const void* medium_scatter_grid_kernel_ptr(bool lightPower, bool analytic);  // ... the density grid's instances (kFlavorMediumGrid), its build and its hooks'
+const void* medium_shadow_grid_kernel_ptr();
+const void* medium_brick_kernel_ptr();
+const void* medium_density_hook_kernel_ptr();
+const void* medium_track_hook_kernel_ptr();
 const void* aov_kernel_ptr();  // nx_aov.hip
 const void* aov_fold_kernel_ptr();
 const void* denoise_gather_kernel_ptr();
@@ -156,6 +161,14 @@ inline BounceKernel medium_shadow() { return {medium_shadow_kernel_ptr()}; }
 inline Kernel<State, const float*, const float*, const float*, const float*, U32, float*, float*, float*, float*> medium_segment_hook() { return {medium_segment_hook_kernel_ptr()}; }
 // (S, dirIn, xi1, xi2, count, dirOut, pdf)
 inline Kernel<State, const float*, const float*, const float*, U32, float*, float*> medium_phase_hook() { return {medium_phase_hook_kernel_ptr()}; }
+inline BounceKernel medium_scatter_grid(bool lightPower, bool analytic) { return {medium_scatter_grid_kernel_ptr(lightPower, analytic)}; }
+inline BounceKernel medium_shadow_grid() { return {medium_shadow_grid_kernel_ptr()}; }
+// (rho, nx, ny, nz, nbx, nby, nbz, bricks)
+inline Kernel<const float*, U32, U32, U32, U32, U32, U32, float*> medium_brick() { return {medium_brick_kernel_ptr()}; }
+// (S, points, count, rho, majorant)
+inline Kernel<State, const float*, U32, float*, float*> medium_density_hook() { return {medium_density_hook_kernel_ptr()}; }
+// (S, origin, dir, tEnd, seed, count, scatterT, transmittance, steps2)
+inline Kernel<State, const float*, const float*, const float*, const U32*, U32, float*, float*, U32*> medium_track_hook() { return {medium_track_hook_kernel_ptr()}; }
 inline StateKernel aov() { return {aov_kernel_ptr()}; }
 inline StateKernel aov_fold() { return {aov_fold_kernel_ptr()}; }
 inline Kernel<State, float4*, float4*, float4*, U32*> denoise_gather() { return {denoise_gather_kernel_ptr()}; }  // (S, colour, albedo, normalDepth, rgba8)
@@ -292,6 +305,8 @@ inline void entry_inputs_changed(nxhip_ctx* c) { c->entryGeneration++; }
 // nxhip_api.hip: the context's state block, queues and pixel set
 void invalidate_graph(nxhip_ctx* c);
 int upload_state(nxhip_ctx* c);
+void refresh_medium_grid(nxhip_ctx* c);                      // nxhip_scene.hip: the density grid's words of the state block
+int check_medium_grid(const nxhip_ctx* c, const char* who);  // ... and the thickness a render or a walking hook refuses
 int alloc_queues(nxhip_ctx* c, size_t n);
 bool slot_queues_ready(const nxhip_ctx* c, const PassSlot* q);
 int ensure_slot_queues(nxhip_ctx* c, PassSlot* q);

@@ -10,6 +10,13 @@
 // No kernel of nx_wavefront.hip changes: its text is compiled here for the templates and device functions alone (NX_WAVEFRONT_INSTANCES_ONLY,
 // as nx_wavefront_detail.hip does) — the light sample is next_event_estimation itself, with the phase function as its "BSDF".
 // Also here: the two test hooks' kernels over the same device functions.
+//
+// The density grid (nxhip_set_medium_density; the rule: include/nexus_hip.h): extinction sigmaT x rho(p), rho a trilinear lookup in a voxel
+// grid over the box.  Both kernels have a GRID instance beside the homogeneous one (medium_scatter_kernel<.., GRID = true>, and the sibling
+// medium_shadow_grid_kernel; in the pass graphs under kFlavorMediumGrid): a per-lane 3-D DDA over bricks of 8 x 8 x 8 voxels with a majorant
+// each — delta tracking for the free flight, ratio tracking for the shadow requests.  The homogeneous instances keep their code, instruction
+// for instruction (profiles/medium_grid.txt).  medium_brick_kernel builds the majorants on the device; three hooks (lookup, walk, majorants)
+// for the tests.
 #define NX_WAVEFRONT_INSTANCES_ONLY 1
 #include "nx_wavefront.hip"
 
@@ -24,7 +31,10 @@ constexpr float kInfF = __builtin_huge_valf();
 // roulette's number of the continuation ray (measured: MIS and naive estimates 6 % apart).  256 is past every value the other stages can
 // form (bounces stay below NX_PATH_MAX_LENGTH = 100), so the medium's numbers come from a stream nobody else reads.
 constexpr uint32_t kMediumStage = 256u;
-static_assert(kMediumStage > 2u * NX_PATH_MAX_LENGTH + 2u, "the medium's stage may not collide with a roulette or material stage of any bounce");
+// ... and the shadow requests' ratio tracking under a density grid draws from the stage after it (a path has at most one request per bounce)
+constexpr uint32_t kMediumShadowStage = 257u;
+static_assert(kMediumStage > 2u * NX_PATH_MAX_LENGTH + 2u && kMediumShadowStage > 2u * NX_PATH_MAX_LENGTH + 2u && kMediumShadowStage != kMediumStage,
+              "the medium's stages may not collide with a roulette or material stage of any bounce, nor with each other");
 constexpr float kInv4Pi = 0.0795774715f;
 
 // one axis of the slab test: narrows [lo, hi]; an axis the ray runs along contributes (-inf, +inf) inside the slab, nothing outside it
@@ -95,6 +105,140 @@ template <> struct Bsdf<kMatPhase> {
 };
 
 // ------------------------------------------------------------------------------------------------------
+// the density grid: lookup, majorant bricks, the walk
+
+constexpr int kBrick = 8;             // voxels per brick edge
+constexpr int kGridWalkBound = 4096;  // iterations of one walk, brick steps and tentative collisions together (render_pass keeps it out of reach)
+
+// one axis of the lookup: the two voxel indices, clamped to the edge, and the weight of the second
+NXD void grid_axis(const float p, const float bmin, const float vscale, const uint32_t n, int& i0, int& i1, float& f)
+{
+    const float g = (p - bmin) * vscale - 0.5f;
+    const float fl = floorf(g);
+    f = g - fl;
+    const float top = (float)(n - 1u);
+    // (clamped as floats: a point far outside the box, or one that is no number, may not reach the conversion)
+    i0 = (int)fminf(fmaxf(fl, 0.0f), top);
+    i1 = (int)fminf(fmaxf(fl + 1.0f, 0.0f), top);
+}
+
+NXD float grid_lerp(const float a, const float b, const float f) { return a + f * (b - a); }
+
+// rho(p): three nested lerps, x, then y, then z
+NXD float grid_density(const DeviceState* S, const f3 p)
+{
+    const nx_medium& med = S->medium;
+    const uint32_t nx = S->mediumN[0], ny = S->mediumN[1], nz = S->mediumN[2];
+    int x0, x1, y0, y1, z0, z1;
+    float fx, fy, fz;
+    grid_axis(p.x, med.boxMin[0], S->mediumVscale[0], nx, x0, x1, fx);
+    grid_axis(p.y, med.boxMin[1], S->mediumVscale[1], ny, y0, y1, fy);
+    grid_axis(p.z, med.boxMin[2], S->mediumVscale[2], nz, z0, z1, fz);
+    const NX_G float* rho = S->mediumRho;
+    const size_t r00 = ((size_t)z0 * ny + (size_t)y0) * nx, r10 = ((size_t)z0 * ny + (size_t)y1) * nx;
+    const size_t r01 = ((size_t)z1 * ny + (size_t)y0) * nx, r11 = ((size_t)z1 * ny + (size_t)y1) * nx;
+    const float c00 = grid_lerp(rho[r00 + x0], rho[r00 + x1], fx), c10 = grid_lerp(rho[r10 + x0], rho[r10 + x1], fx);
+    const float c01 = grid_lerp(rho[r01 + x0], rho[r01 + x1], fx), c11 = grid_lerp(rho[r11 + x0], rho[r11 + x1], fx);
+    return grid_lerp(grid_lerp(c00, c10, fy), grid_lerp(c01, c11, fy), fz);
+}
+
+// the brick of a point in brick space, clamped to the grid (as floats first: see grid_axis)
+NXD int grid_brick_of(const float u, const uint32_t nb) { return (int)fminf(fmaxf(floorf(u), 0.0f), (float)(nb - 1u)); }
+
+// tNext of one axis, from the integer brick index: never accumulated
+NXD float grid_next(const int b, const bool forward, const float bscale, const float bmin, const float o, const float d)
+{
+    return d == 0.0f ? kInfF : ((((float)(b + (forward ? 1 : 0))) / bscale + bmin) - o) / d;
+}
+
+// The walk over [t0, t1] of the ray (o, d), by the rule of nexus_hip.h.  RATIO = false: delta tracking — returns 1 with tOut = the parameter
+// of a real collision, 0 if the segment is passed without one.  RATIO = true: ratio tracking — T is multiplied at every tentative
+// collision, the return value is 0.  Either: 2 at the iteration bound.  `iters` counts iterations, `colls` the tentative collisions among
+// them.  All state is scalars: the axis is chosen by selects, no array is indexed by a lane's value.
+template <bool RATIO>
+NXD int grid_walk(const DeviceState* S, const f3 o, const f3 d, const float t0, const float t1, uint32_t& rng, float& tOut, float& T, uint32_t& iters, uint32_t& colls)
+{
+    const float sigmaT = S->medium.sigmaT;
+    const float minX = S->medium.boxMin[0], minY = S->medium.boxMin[1], minZ = S->medium.boxMin[2];
+    const float bsX = S->mediumBscale[0], bsY = S->mediumBscale[1], bsZ = S->mediumBscale[2];
+    const int nbX = (int)S->mediumNb[0], nbY = (int)S->mediumNb[1], nbZ = (int)S->mediumNb[2];
+    const NX_G float* bricks = S->mediumBricks;
+    const f3 p0 = o + d * t0;
+    int bx = grid_brick_of((p0.x - minX) * bsX, (uint32_t)nbX), by = grid_brick_of((p0.y - minY) * bsY, (uint32_t)nbY), bz = grid_brick_of((p0.z - minZ) * bsZ, (uint32_t)nbZ);
+    const bool fwX = d.x > 0.0f, fwY = d.y > 0.0f, fwZ = d.z > 0.0f;
+    float tnX = grid_next(bx, fwX, bsX, minX, o.x, d.x), tnY = grid_next(by, fwY, bsY, minY, o.y, d.y), tnZ = grid_next(bz, fwZ, bsZ, minZ, o.z, d.z);
+    float t = t0;
+    float tau = -nxf_logf(1.0f - rng_next(rng));
+    iters = 0u;
+    colls = 0u;
+    for (int it = 0; it < kGridWalkBound; it++) {
+        iters++;
+        const int ax = tnX <= tnY ? (tnX <= tnZ ? 0 : 2) : (tnY <= tnZ ? 1 : 2);
+        const float tn = ax == 0 ? tnX : (ax == 1 ? tnY : tnZ);
+        const float tExit = fminf(tn, t1);
+        const float M = bricks[((size_t)bz * (size_t)nbY + (size_t)by) * (size_t)nbX + (size_t)bx];
+        const float mu = sigmaT * M;
+        const float depth = mu * (tExit - t);
+        if (tau < depth) {
+            t += tau / mu;
+            const float r = grid_density(S, o + d * t);
+            colls++;
+            if (RATIO) {
+                T *= fmaxf(0.0f, 1.0f - r / M);
+                if (T == 0.0f) return 0;
+            } else {
+                const float zeta = rng_next(rng);
+                if (zeta * M < r) {
+                    tOut = t;
+                    return 1;
+                }
+            }
+            tau = -nxf_logf(1.0f - rng_next(rng));
+        } else {
+            tau -= fmaxf(depth, 0.0f);
+            if (!(tn < t1)) return 0;
+            t = tExit;
+            if (ax == 0) {
+                bx += fwX ? 1 : -1;
+                if (bx < 0 || bx >= nbX) return 0;
+                tnX = grid_next(bx, fwX, bsX, minX, o.x, d.x);
+            } else if (ax == 1) {
+                by += fwY ? 1 : -1;
+                if (by < 0 || by >= nbY) return 0;
+                tnY = grid_next(by, fwY, bsY, minY, o.y, d.y);
+            } else {
+                bz += fwZ ? 1 : -1;
+                if (bz < 0 || bz >= nbZ) return 0;
+                tnZ = grid_next(bz, fwZ, bsZ, minZ, o.z, d.z);
+            }
+        }
+    }
+    if (RATIO) T = 0.0f;
+    return 2;
+}
+
+// medium_brick_kernel: M[b] = the maximum of rho over the voxels [8 b_i - 1, 8 b_i + 8] per axis, clamped to the grid — one lane per brick,
+// at most 10^3 reads each, every index clamped before it is formed.  Runs once per nxhip_set_medium_density, on the context's stream.
+__global__ void __launch_bounds__(kWideBlock) medium_brick_kernel(const float* __restrict__ rho, const uint32_t nx, const uint32_t ny, const uint32_t nz, const uint32_t nbx,
+                                                                   const uint32_t nby, const uint32_t nbz, float* __restrict__ bricks)
+{
+    const uint32_t total = nbx * nby * nbz;
+    for (uint32_t k = blockIdx.x * blockDim.x + threadIdx.x; k < total; k += gridDim.x * blockDim.x) {
+        const uint32_t bx = k % nbx, by = (k / nbx) % nby, bz = k / (nbx * nby);
+        const uint32_t x0 = bx ? bx * kBrick - 1u : 0u, x1 = min(bx * kBrick + kBrick, nx - 1u);
+        const uint32_t y0 = by ? by * kBrick - 1u : 0u, y1 = min(by * kBrick + kBrick, ny - 1u);
+        const uint32_t z0 = bz ? bz * kBrick - 1u : 0u, z1 = min(bz * kBrick + kBrick, nz - 1u);
+        float m = 0.0f;  // (the voxels are >= 0: nxhip_set_medium_density)
+        for (uint32_t z = z0; z <= z1; z++)
+            for (uint32_t y = y0; y <= y1; y++) {
+                const size_t row = ((size_t)z * ny + y) * nx;
+                for (uint32_t x = x0; x <= x1; x++) m = fmaxf(m, rho[row + x]);
+            }
+        bricks[k] = m;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------
 // medium_scatter_kernel
 //
 // Workgroup w serves region w % 8 of the trace queue of bounce - 1 (as the material launch does) in tiles of 256 consecutive slots — every
@@ -103,7 +247,9 @@ template <> struct Bsdf<kMatPhase> {
 // kernel took, so a region holds no more than it could without a medium.  The code word is read first: records nobody shades (0), and
 // every ray that does not cross the box, cost 4 + 32 bytes and leave.  No LDS beyond the allocator's, no spin, no wait; the tile loop is
 // bounded by the region's size.
-template <bool POWER, bool ANALYTIC>
+// GRID = false is the homogeneous kernel as it always was; GRID = true (kFlavorMediumGrid) finds the collision by the walk: lanes of a wave
+// walk different numbers of bricks, so a tile costs what its longest walk costs.
+template <bool POWER, bool ANALYTIC, bool GRID>
 __global__ void __launch_bounds__(kShadeBlock) medium_scatter_kernel(const DeviceState* __restrict__ S, const int bounceArg)
 {
     const int bounce = bounceArg & 0xff;
@@ -143,12 +289,22 @@ __global__ void __launch_bounds__(kShadeBlock) medium_scatter_kernel(const Devic
             const MediumSeg seg = medium_segment(med, o, d, tEnd);
             if (seg.L > 0.0f) {
                 uint32_t rng = seed_for(S, (uint32_t)at, pixelIdx, (uint32_t)bounce, kMediumStage, frame);
-                const float s = medium_flight(med.sigmaT, rng_next(rng));
-                if (s < seg.L) {
+                float tScatter = 0.0f;
+                int event;  // 0: the segment is passed, 1: the path scatters at tScatter, 2: the walk's bound — the path ends, absorbed
+                if (GRID) {
+                    float T = 1.0f;
+                    uint32_t iters, colls;
+                    event = grid_walk<false>(S, o, d, seg.t0, seg.t0 + seg.L, rng, tScatter, T, iters, colls);
+                } else {
+                    const float s = medium_flight(med.sigmaT, rng_next(rng));
+                    event = s < seg.L ? 1 : 0;
+                    tScatter = seg.t0 + s;
+                }
+                if (event != 0) {
                     // the path scatters at x: the record leaves the material launch's reach
                     S->trace.hitInst[at] = (word & kHitInstMask) | (kHitCodeMedium << kHitCodeShift);
-                    if ((__float_as_uint(ro.w) & kRaySurvives) != 0u && !lastBounce) {
-                        x = o + d * (seg.t0 + s);
+                    if (event == 1 && (__float_as_uint(ro.w) & kRaySurvives) != 0u && !lastBounce) {
+                        x = o + d * tScatter;
                         beta = mk3(1.0f);
                         if (bounce != 1) {
                             const float4 tp = in.tp[at];
@@ -221,6 +377,32 @@ __global__ void __launch_bounds__(kWideBlock) medium_shadow_kernel(const DeviceS
     }
 }
 
+// the GRID instance: ratio tracking along the crossing, from a stream of the request's own (stage 257); a request that meets no tentative
+// collision — no brick with M > 0 on its way, or tau outlasting them — keeps its bits.  The medium is read from the state block where it is
+// used (a held copy beside the walk's state spills scalar registers: profiles/medium.txt section 1).
+__global__ void __launch_bounds__(kWideBlock) medium_shadow_grid_kernel(const DeviceState* __restrict__ S, const int bounce)
+{
+    const QueueView in = queue_view(&S->counters->region[0].traceShadowSize[bounce], S->queueShardCap);
+    const uint32_t frame = S->frame->frameNumber;
+    for (int index = (int)(blockIdx.x * blockDim.x + threadIdx.x); index < in.total; index += (int)(gridDim.x * blockDim.x)) {
+        const int at = in.slot(index);
+        const float4 ro = S->shadow.rayO[at], rd = S->shadow.rayD[at];
+        const f3 o = mk3(ro.x, ro.y, ro.z), d = mk3(rd.x, rd.y, rd.z);
+        const MediumSeg seg = medium_segment(S->medium, o, d, ro.w);
+        if (seg.L > 0.0f) {
+            uint32_t rng = seed_for(S, (uint32_t)at, __float_as_uint(rd.w), (uint32_t)bounce, kMediumShadowStage, frame);
+            float T = 1.0f, tUnused;
+            uint32_t iters, colls;
+            const int event = grid_walk<true>(S, o, d, seg.t0, seg.t0 + seg.L, rng, tUnused, T, iters, colls);
+            if (colls != 0u || event == 2) {
+                float4 r = S->shadow.radiance[at];
+                r.x *= T; r.y *= T; r.z *= T;
+                S->shadow.radiance[at] = r;
+            }
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------------------
 // Test hooks: the functions above on plain arrays (nxhip_medium_segment_batch, nxhip_medium_phase_batch)
 
@@ -253,11 +435,64 @@ __global__ void __launch_bounds__(kWideBlock) medium_phase_hook_kernel(const Dev
     }
 }
 
+// The grid's hooks (nxhip_medium_density_batch, nxhip_medium_track_batch): the lookup with the majorant of the point's brick, and the walk
+// in both modes from the caller's stream state — each mode starts from its own copy of seed[k].  steps2[2k] is the free flight's walk,
+// steps2[2k + 1] the ratio tracking's: iterations | tentative collisions << 16 (the bound, 4096, fits 16 bits); both 0 where the ray does
+// not cross the box.
+__global__ void __launch_bounds__(kWideBlock) medium_density_hook_kernel(const DeviceState* __restrict__ S, const float* __restrict__ points, const uint32_t count,
+                                                                          float* __restrict__ rho, float* __restrict__ majorant)
+{
+    for (uint32_t k = blockIdx.x * blockDim.x + threadIdx.x; k < count; k += gridDim.x * blockDim.x) {
+        const f3 p = mk3(points[3 * k], points[3 * k + 1], points[3 * k + 2]);
+        rho[k] = grid_density(S, p);
+        const int bx = grid_brick_of((p.x - S->medium.boxMin[0]) * S->mediumBscale[0], S->mediumNb[0]);
+        const int by = grid_brick_of((p.y - S->medium.boxMin[1]) * S->mediumBscale[1], S->mediumNb[1]);
+        const int bz = grid_brick_of((p.z - S->medium.boxMin[2]) * S->mediumBscale[2], S->mediumNb[2]);
+        majorant[k] = S->mediumBricks[((size_t)bz * S->mediumNb[1] + (size_t)by) * S->mediumNb[0] + (size_t)bx];
+    }
+}
+
+__global__ void __launch_bounds__(kWideBlock) medium_track_hook_kernel(const DeviceState* __restrict__ S, const float* __restrict__ origin, const float* __restrict__ dir,
+                                                                        const float* __restrict__ tEnd, const uint32_t* __restrict__ seed, const uint32_t count,
+                                                                        float* __restrict__ scatterT, float* __restrict__ transmittance, uint32_t* __restrict__ steps2)
+{
+    for (uint32_t k = blockIdx.x * blockDim.x + threadIdx.x; k < count; k += gridDim.x * blockDim.x) {
+        const f3 o = mk3(origin[3 * k], origin[3 * k + 1], origin[3 * k + 2]), d = mk3(dir[3 * k], dir[3 * k + 1], dir[3 * k + 2]);
+        const MediumSeg seg = medium_segment(S->medium, o, d, tEnd[k]);
+        float st = -1.0f, T = 1.0f;
+        uint32_t w0 = 0u, w1 = 0u;
+        if (seg.L > 0.0f) {
+            uint32_t rng = seed[k], iters, colls;
+            float t = 0.0f, unusedT = 1.0f;
+            const int event = grid_walk<false>(S, o, d, seg.t0, seg.t0 + seg.L, rng, t, unusedT, iters, colls);
+            st = event == 1 ? t : -1.0f;
+            w0 = iters | (colls << 16);
+            rng = seed[k];
+            grid_walk<true>(S, o, d, seg.t0, seg.t0 + seg.L, rng, t, T, iters, colls);
+            w1 = iters | (colls << 16);
+        }
+        scatterT[k] = st;
+        transmittance[k] = T;
+        steps2[2 * k] = w0;
+        steps2[2 * k + 1] = w1;
+    }
+}
+
+const void* medium_scatter_grid_kernel_ptr(bool lightPower, bool analytic)
+{
+    if (analytic) return lightPower ? (const void*)medium_scatter_kernel<true, true, true> : (const void*)medium_scatter_kernel<false, true, true>;
+    return lightPower ? (const void*)medium_scatter_kernel<true, false, true> : (const void*)medium_scatter_kernel<false, false, true>;
+}
+const void* medium_shadow_grid_kernel_ptr() { return (const void*)medium_shadow_grid_kernel; }
+const void* medium_brick_kernel_ptr() { return (const void*)medium_brick_kernel; }
+const void* medium_density_hook_kernel_ptr() { return (const void*)medium_density_hook_kernel; }
+const void* medium_track_hook_kernel_ptr() { return (const void*)medium_track_hook_kernel; }
+
 // (the light sample's mode and analytic lights: next_event_estimation's instances, chosen as the material launch's are — nxhip_render.hip)
 const void* medium_scatter_kernel_ptr(bool lightPower, bool analytic)
 {
-    if (analytic) return lightPower ? (const void*)medium_scatter_kernel<true, true> : (const void*)medium_scatter_kernel<false, true>;
-    return lightPower ? (const void*)medium_scatter_kernel<true, false> : (const void*)medium_scatter_kernel<false, false>;
+    if (analytic) return lightPower ? (const void*)medium_scatter_kernel<true, true, false> : (const void*)medium_scatter_kernel<false, true, false>;
+    return lightPower ? (const void*)medium_scatter_kernel<true, false, false> : (const void*)medium_scatter_kernel<false, false, false>;
 }
 const void* medium_shadow_kernel_ptr() { return (const void*)medium_shadow_kernel; }
 const void* medium_segment_hook_kernel_ptr() { return (const void*)medium_segment_hook_kernel; }

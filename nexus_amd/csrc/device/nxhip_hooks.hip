@@ -445,6 +445,84 @@ try {
     return NXHIP_OK;
 } NX_CATCH("nxhip_medium_phase_batch")
 
+// ---- the density grid's hooks (medium_density_hook_kernel, medium_track_hook_kernel; the bricks as they are) -------------
+
+static bool medium_grid_on(const nxhip_ctx* c) { return c->h.mediumOn && c->h.mediumRho; }
+
+int nxhip_read_medium_majorants(nxhip_ctx* c, float* majorant, uint32_t capacity, uint32_t bricks[3])
+try {
+    NX_DEBUG_HOOK("nxhip_read_medium_majorants");  // (first: a release library refuses whatever it is handed)
+    NX_CHECK_CTX(c);
+    if (!c->mediumBricks.p) return fail_invalid("nxhip_read_medium_majorants: no density grid is set (nxhip_set_medium_density)");
+    const uint32_t nb[3] = {(c->mediumGridN[0] + 7u) / 8u, (c->mediumGridN[1] + 7u) / 8u, (c->mediumGridN[2] + 7u) / 8u};
+    if (bricks)
+        for (int k = 0; k < 3; k++) bricks[k] = nb[k];
+    if (!majorant) return NXHIP_OK;  // (the brick counts alone)
+    const uint32_t total = nb[0] * nb[1] * nb[2];
+    if (capacity < total) return fail_invalid("nxhip_read_medium_majorants: capacity is below the number of bricks");
+    NX_HIP(hipSetDevice(c->device));
+    NX_SYNC_ALL(c);
+    NX_HIP(hipMemcpy(majorant, c->mediumBricks.p, (size_t)total * 4, hipMemcpyDeviceToHost));
+    return NXHIP_OK;
+} NX_CATCH("nxhip_read_medium_majorants")
+
+int nxhip_medium_density_batch(nxhip_ctx* c, const float* points3, uint32_t count, float* rho, float* majorant)
+try {
+    NX_DEBUG_HOOK("nxhip_medium_density_batch");
+    NX_CHECK_CTX(c);
+    if (!medium_grid_on(c)) return fail_invalid("nxhip_medium_density_batch: it needs a medium with sigmaT > 0 (nxhip_set_medium) and a density grid (nxhip_set_medium_density)");
+    if ((!points3 || !rho || !majorant) && count) return fail_invalid("nxhip_medium_density_batch: null buffer");
+    for (size_t k = 0; k < (size_t)count * 3; k++)
+        if (!(points3[k] >= -3.0e38f && points3[k] <= 3.0e38f)) return fail_invalid("nxhip_medium_density_batch: points must be finite");
+    if (count == 0) return NXHIP_OK;
+    NX_HIP(hipSetDevice(c->device));
+    NX_TRY(upload_state(c));
+    DevBuf dP, dRho, dM;
+    NX_TRY(medium_hook_in(dP, points3, (size_t)count * 3));
+    NX_ALLOC(dRho, (size_t)count * 4);
+    NX_ALLOC(dM, (size_t)count * 4);
+    NX_HIP(launch_untimed(kernels::medium_density_hook(), c->wideBlocks, kWideBlockThreads, c->stream, c->dState.as<DeviceState>(), dP.as<float>(), count, dRho.as<float>(), dM.as<float>()));
+    NX_SYNC_ALL(c);
+    NX_HIP(hipMemcpy(rho, dRho.p, (size_t)count * 4, hipMemcpyDeviceToHost));
+    NX_HIP(hipMemcpy(majorant, dM.p, (size_t)count * 4, hipMemcpyDeviceToHost));
+    return NXHIP_OK;
+} NX_CATCH("nxhip_medium_density_batch")
+
+int nxhip_medium_track_batch(nxhip_ctx* c, const float* origin, const float* dir, const float* tEnd, const uint32_t* seed, uint32_t count, float* scatterT, float* transmittance,
+                             uint32_t* steps2)
+try {
+    NX_DEBUG_HOOK("nxhip_medium_track_batch");
+    NX_CHECK_CTX(c);
+    if (!medium_grid_on(c)) return fail_invalid("nxhip_medium_track_batch: it needs a medium with sigmaT > 0 (nxhip_set_medium) and a density grid (nxhip_set_medium_density)");
+    NX_TRY(check_medium_grid(c, "nxhip_medium_track_batch"));
+    if ((!origin || !dir || !tEnd || !seed || !scatterT || !transmittance || !steps2) && count) return fail_invalid("nxhip_medium_track_batch: null buffer");
+    for (size_t k = 0; k < (size_t)count * 3; k++)
+        if (!(origin[k] >= -3.0e38f && origin[k] <= 3.0e38f) || !(dir[k] >= -3.0e38f && dir[k] <= 3.0e38f)) return fail_invalid("nxhip_medium_track_batch: origins and directions must be finite");
+    for (size_t k = 0; k < (size_t)count; k++) {
+        if (!(tEnd[k] > 0.0f)) return fail_invalid("nxhip_medium_track_batch: tEnd must be positive (+inf allowed)");
+        if (seed[k] == 0u) return fail_invalid("nxhip_medium_track_batch: a seed may not be 0 (xorshift32 stays there)");
+    }
+    if (count == 0) return NXHIP_OK;
+    NX_HIP(hipSetDevice(c->device));
+    NX_TRY(upload_state(c));
+    DevBuf dO, dD, dT, dSeed, dS, dTr, dSteps;
+    NX_TRY(medium_hook_in(dO, origin, (size_t)count * 3));
+    NX_TRY(medium_hook_in(dD, dir, (size_t)count * 3));
+    NX_TRY(medium_hook_in(dT, tEnd, count));
+    NX_ALLOC(dSeed, (size_t)count * 4);
+    NX_HIP(hipMemcpy(dSeed.p, seed, (size_t)count * 4, hipMemcpyHostToDevice));
+    NX_ALLOC(dS, (size_t)count * 4);
+    NX_ALLOC(dTr, (size_t)count * 4);
+    NX_ALLOC(dSteps, (size_t)count * 8);
+    NX_HIP(launch_untimed(kernels::medium_track_hook(), c->wideBlocks, kWideBlockThreads, c->stream, c->dState.as<DeviceState>(), dO.as<float>(), dD.as<float>(), dT.as<float>(),
+                          dSeed.as<uint32_t>(), count, dS.as<float>(), dTr.as<float>(), dSteps.as<uint32_t>()));
+    NX_SYNC_ALL(c);
+    NX_HIP(hipMemcpy(scatterT, dS.p, (size_t)count * 4, hipMemcpyDeviceToHost));
+    NX_HIP(hipMemcpy(transmittance, dTr.p, (size_t)count * 4, hipMemcpyDeviceToHost));
+    NX_HIP(hipMemcpy(steps2, dSteps.p, (size_t)count * 8, hipMemcpyDeviceToHost));
+    return NXHIP_OK;
+} NX_CATCH("nxhip_medium_track_batch")
+
 // ---- the detail maps' hook (shading_frame_hook_kernel) ----------------------------------------------
 
 int nxhip_shading_frame_batch(nxhip_ctx* c, uint32_t instanceIdx, const uint32_t* triIdx, const float* hitUv, const float* rayDir, uint32_t count, float* normalOut,

@@ -197,6 +197,10 @@ constexpr int kFlavorDetail = 4096;
 // pipeline and pixel-keyed random numbers only: render_pass refuses every other mode while the bit would be set.  Without a medium the bit
 // is clear and the graphs are the default ones, launch for launch.
 constexpr int kFlavorMedium = 8192;
+// kFlavorMediumGrid: ... and a density grid (nxhip_set_medium_density) — the two launches are the GRID instances, which find their
+// collisions by a walk over majorant bricks.  Set iff a medium with sigmaT > 0 AND a grid are set (the state block names the grid only then:
+// refresh_medium_grid); never without kFlavorMedium.
+constexpr int kFlavorMediumGrid = 16384;
 int pass_flavor(const nxhip_ctx* c)
 {
     int f = 0;
@@ -232,6 +236,7 @@ int pass_flavor(const nxhip_ctx* c)
     if (c->h.alightCount) f |= kFlavorAnalytic;
     if (transmit_active(c)) f |= kFlavorTransmit;
     if (c->h.mediumOn) f |= kFlavorMedium;
+    if (c->h.mediumOn && c->h.mediumRho) f |= kFlavorMediumGrid;
     return f & ~(c->flavorForceGeneral & kFlavorSpecialised);  // (test hook: nxhip_debug_pass_flavor)
 }
 
@@ -254,6 +259,7 @@ std::vector<std::vector<Launch>> frame_levels(nxhip_ctx* c, PassSlot* q)
     const bool transmit = (pass_flavor(c) & kFlavorTransmit) != 0;
     const bool detail = (pass_flavor(c) & kFlavorDetail) != 0;
     const bool medium = (pass_flavor(c) & kFlavorMedium) != 0;
+    const bool mediumGrid = (pass_flavor(c) & kFlavorMediumGrid) != 0;
     // the any-hit launch of a bounce: the TRANSMIT instance never hands over (no kTraceThinFlag) and has no IDENTITY form
     auto shadow_launch = [&](int shadowBlocksArg, int bounceArg, int thinFlagArg) {
         return transmit ? make_launch(kernels::trace_transmit(stats), shadowBlocksArg, kTraceBlockThreads, NXHIP_K_SHADOW, S, bounceArg)
@@ -317,7 +323,7 @@ std::vector<std::vector<Launch>> frame_levels(nxhip_ctx* c, PassSlot* q)
             if (mask == 0) mask = 1 << NX_MAT_DIFFUSE;  // (a level cannot be empty)
             if (misses) mask |= 1 << kScanMiss;
             // the medium's free-flight decision over the records the closest-hit level left, in front of the material launch that reads them
-            if (medium) levels.push_back({make_launch(kernels::medium_scatter(lightPower, analytic), whole_regions(wide), kShadeBlockThreads, NXHIP_K_SHADE, S, bounce | dropFlag)});
+            if (medium) levels.push_back({make_launch(mediumGrid ? kernels::medium_scatter_grid(lightPower, analytic) : kernels::medium_scatter(lightPower, analytic), whole_regions(wide), kShadeBlockThreads, NXHIP_K_SHADE, S, bounce | dropFlag)});
             levels.push_back({make_launch(kernels::shade_scan(lightPower, noMaps, analytic, detail), og, kShadeBlockThreads, NXHIP_K_SHADE, S, bounce | dropFlag, mask)});
             if (bounce == 1) aov_beside(levels.back());
             if (in_use(NX_MAT_CONDUCTOR) && c->h.conductorMode != NX_CONDUCTOR_EXTENDED) {  // (counted, not shaded: count_scan_kernel)
@@ -328,7 +334,7 @@ std::vector<std::vector<Launch>> frame_levels(nxhip_ctx* c, PassSlot* q)
                 Launch anyHit = shadow_launch(shadowBlocks, bounce, thinFlag);
                 anyHit.after = 1;
                 levels.push_back({make_launch(kernels::trace(false, stats, identity), traceBlocks, kTraceBlockThreads, NXHIP_K_TRACE, S, bounce | kTraceScanFlag | thinFlag),
-                                  make_launch(kernels::medium_shadow(), wide, wideThreads, NXHIP_K_SHADE, S, bounce), anyHit});
+                                  make_launch(mediumGrid ? kernels::medium_shadow_grid() : kernels::medium_shadow(), wide, wideThreads, NXHIP_K_SHADE, S, bounce), anyHit});
             } else {
                 levels.push_back({make_launch(kernels::trace(false, stats, identity), traceBlocks, kTraceBlockThreads, NXHIP_K_TRACE, S, bounce | kTraceScanFlag | thinFlag),
                                   shadow_launch(shadowBlocks, bounce, thinFlag)});
@@ -544,6 +550,7 @@ try {
     if (c->h.mediumOn && (!scan_pipeline(c) || c->h.rngMode != NX_RNG_PIXEL_KEYED))
         return fail_invalid("a medium is set (nxhip_set_medium): it needs the SCAN pipeline (NX_COMPACT_FAST) and pixel-keyed random numbers (NX_RNG_PIXEL_KEYED) - "
                             "the classic pipeline and the slot-keyed stream have no stage of their own to draw from; remove the medium or change the modes");
+    NX_TRY(check_medium_grid(c, "nxhip_render"));
     if (c->adaptive && pass_pixels(c) == 0u) return NXHIP_OK;  // no active block: nothing is launched, the frame number stays
     struct PassFrames {  // what pass_size_in_frames (grids, tail rule, graph shape) sees while this pass is issued
         nxhip_ctx* c;

@@ -91,6 +91,49 @@ void nxd::refresh_detail_maps(nxhip_ctx* c)
     c->shadeInstDirty = true;
 }
 
+// The grid's words of the state block, from the context's grid and the medium's box: all 0 unless a medium with sigmaT > 0 AND a grid are
+// set, so a grid alone, or a medium alone, leaves the block what it was.  vscale and bscale in binary64, rounded once.
+void nxd::refresh_medium_grid(nxhip_ctx* c)
+{
+    DeviceState& h = c->h;
+    h.mediumRho = nullptr;
+    h.mediumBricks = nullptr;
+    for (int k = 0; k < 3; k++) {
+        h.mediumN[k] = h.mediumNb[k] = 0u;
+        h.mediumVscale[k] = h.mediumBscale[k] = 0.0f;
+    }
+    h.padGrid0_ = h.padGrid1_ = 0u;
+    h.padGrid2_ = h.padGrid3_ = 0.0f;
+    if (h.mediumOn && c->mediumRho.p) {
+        h.mediumRho = c->mediumRho.as<float>();
+        h.mediumBricks = c->mediumBricks.as<float>();
+        for (int k = 0; k < 3; k++) {
+            const double extent = (double)h.medium.boxMax[k] - (double)h.medium.boxMin[k];
+            h.mediumN[k] = c->mediumGridN[k];
+            h.mediumNb[k] = (c->mediumGridN[k] + 7u) / 8u;
+            h.mediumVscale[k] = (float)((double)c->mediumGridN[k] / extent);
+            h.mediumBscale[k] = (float)((double)c->mediumGridN[k] / (8.0 * extent));
+        }
+    }
+    c->stateDirty = true;  // (the pass graphs follow by their flavor: kFlavorMediumGrid)
+}
+
+// A render, and the hooks that walk, refuse a medium whose box is too deep for the walk's bound of 4096 iterations to stay out of reach.
+int nxd::check_medium_grid(const nxhip_ctx* c, const char* who)
+{
+    if (!c->h.mediumOn || !c->h.mediumRho) return NXHIP_OK;
+    double diag = 0.0;
+    for (int k = 0; k < 3; k++) {
+        const double e = (double)c->h.medium.boxMax[k] - (double)c->h.medium.boxMin[k];
+        diag += e * e;
+    }
+    const double thickness = (double)c->h.medium.sigmaT * (double)c->mediumRhoMax * std::sqrt(diag);
+    if (thickness > 512.0)
+        return fail_invalid(std::string(who) + ": the medium's density grid is too thick: sigmaT x max(rho) x |boxMax - boxMin| = " + std::to_string(thickness) +
+                            " exceeds 512 mean free paths (the tracking loop is bounded) - lower sigmaT, scale the grid's values down or shrink the box");
+    return NXHIP_OK;
+}
+
 int nxd::refresh_shade_inst(nxhip_ctx* c)
 {
     const size_t n = c->hostInstances.size();
@@ -975,8 +1018,53 @@ try {
     c->h.mediumOneMinusG2 = c->h.mediumOn ? 1.0f - c->h.mediumG2 : 0.0f;
     c->h.padMedium_ = 0u;
     c->stateDirty = true;  // (the pass graphs follow by their flavor: kFlavorMedium)
+    refresh_medium_grid(c);  // (the grid stays; its scales follow the new box)
     return NXHIP_OK;
 } NX_CATCH("nxhip_set_medium")
+
+// The density grid (include/nexus_hip.h): checked on the host before anything is allocated — a refused call leaves the previous grid where
+// it is.  The voxels go to the device as they are; the majorant bricks are built there (medium_brick_kernel), on the context's stream.
+int nxhip_set_medium_density(nxhip_ctx* c, const float* rho, uint32_t nx, uint32_t ny, uint32_t nz)
+try {
+    NX_CHECK_CTX(c);
+    if (!rho) {
+        NX_HIP(hipSetDevice(c->device));
+        NX_SYNC_ALL(c);
+        c->mediumRho = DevBuf();
+        c->mediumBricks = DevBuf();
+        c->mediumGridN[0] = c->mediumGridN[1] = c->mediumGridN[2] = 0u;
+        c->mediumRhoMax = 0.0f;
+        refresh_medium_grid(c);
+        return NXHIP_OK;
+    }
+    if (nx == 0u || ny == 0u || nz == 0u) return fail_invalid("nxhip_set_medium_density: a dimension is 0");
+    if (nx > 512u || ny > 512u || nz > 512u) return fail_invalid("nxhip_set_medium_density: a dimension exceeds 512");
+    const uint64_t voxels = (uint64_t)nx * ny * nz;
+    if (voxels > (1ull << 27)) return fail_invalid("nxhip_set_medium_density: more than 2^27 voxels");
+    float top = 0.0f;
+    for (uint64_t k = 0; k < voxels; k++) {
+        if (!(rho[k] >= 0.0f && rho[k] <= 3.4028234e38f)) return fail_invalid("nxhip_set_medium_density: voxel " + std::to_string(k) + " is negative or not finite");
+        top = std::max(top, rho[k]);
+    }
+    if (!(top > 0.0f)) return fail_invalid("nxhip_set_medium_density: the grid's maximum is 0 (NULL removes the grid)");
+    NX_HIP(hipSetDevice(c->device));
+    NX_SYNC_ALL(c);
+    const uint32_t nbx = (nx + 7u) / 8u, nby = (ny + 7u) / 8u, nbz = (nz + 7u) / 8u;
+    const uint32_t bricks = nbx * nby * nbz;
+    DevBuf freshRho, freshBricks;  // (the old grid goes only once the new one is there)
+    NX_ALLOC(freshRho, (size_t)voxels * 4);
+    NX_ALLOC(freshBricks, (size_t)bricks * 4);
+    NX_HIP(hipMemcpy(freshRho.p, rho, (size_t)voxels * 4, hipMemcpyHostToDevice));
+    const int blocks = (int)std::min<uint32_t>((bricks + (uint32_t)kWideBlockThreads - 1u) / (uint32_t)kWideBlockThreads, 4096u);
+    NX_HIP(launch_untimed(kernels::medium_brick(), blocks, kWideBlockThreads, c->stream, freshRho.as<float>(), nx, ny, nz, nbx, nby, nbz, freshBricks.as<float>()));
+    NX_HIP(hipStreamSynchronize(c->stream));  // (a setter, not the launch path: the other slots' streams may read the bricks next)
+    c->mediumRho = std::move(freshRho);
+    c->mediumBricks = std::move(freshBricks);
+    c->mediumGridN[0] = nx; c->mediumGridN[1] = ny; c->mediumGridN[2] = nz;
+    c->mediumRhoMax = top;
+    refresh_medium_grid(c);
+    return NXHIP_OK;
+} NX_CATCH("nxhip_set_medium_density")
 
 static int refresh_texture_tables(nxhip_ctx* c)
 {

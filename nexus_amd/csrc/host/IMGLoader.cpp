@@ -297,6 +297,86 @@ FloatImage IMGLoader::LoadHDRFloat(const std::string& filepath)
     return LoadHDRFloat(data.data(), data.size());
 }
 
+// The .npy header (NumPy Enhancement Proposal 1): "\x93NUMPY", major, minor, a little-endian header length of 2 (version 1) or 4 bytes
+// (version 2 and 3), then a Python dict literal — 'descr', 'fortran_order', 'shape' — padded with spaces up to the data.
+DensityGrid IMGLoader::LoadNPYGrid(const unsigned char* data, size_t size)
+{
+    static const unsigned char magic[6] = {0x93, 'N', 'U', 'M', 'P', 'Y'};
+    if (size < 10 || std::memcmp(data, magic, 6) != 0) fail("not a .npy file (no NUMPY magic)");
+    const int major = data[6];
+    if (major != 1 && major != 2) fail(".npy format version " + std::to_string(major) + "." + std::to_string(data[7]) + " is not supported (1.x and 2.x are)");
+    size_t headerLen = 0, at = 0;
+    if (major == 1) {
+        headerLen = static_cast<size_t>(data[8]) | (static_cast<size_t>(data[9]) << 8);
+        at = 10;
+    } else {
+        if (size < 12) fail("truncated .npy header");
+        headerLen = static_cast<size_t>(data[8]) | (static_cast<size_t>(data[9]) << 8) | (static_cast<size_t>(data[10]) << 16) | (static_cast<size_t>(data[11]) << 24);
+        at = 12;
+    }
+    if (headerLen > size - at) fail("truncated .npy header");
+    const std::string header(reinterpret_cast<const char*>(data + at), headerLen);
+    // the value that follows 'key': up to the next top-level comma (a tuple's commas sit inside its parentheses)
+    auto value_of = [&](const std::string& key) {
+        const size_t k = header.find("'" + key + "'");
+        if (k == std::string::npos) fail(".npy header has no '" + key + "'");
+        size_t p = header.find(':', k);
+        if (p == std::string::npos) fail("malformed .npy header");
+        p++;
+        std::string v;
+        int depth = 0;
+        for (; p < header.size(); p++) {
+            const char ch = header[p];
+            if (ch == '(') depth++;
+            if (ch == ')') depth--;
+            if ((ch == ',' && depth == 0) || ch == '}') break;
+            if (ch != ' ') v.push_back(ch);
+        }
+        return v;
+    };
+    const std::string descr = value_of("descr"), fortran = value_of("fortran_order"), shape = value_of("shape");
+    if (descr != "'<f4'" && descr != "\"<f4\"") fail("a density grid must hold little-endian float32 ('<f4'); the file holds " + descr);
+    if (fortran != "False") fail("a density grid must be in C order (fortran_order False)");
+    std::vector<uint64_t> dims;
+    {
+        uint64_t cur = 0;
+        bool digits = false;
+        for (const char ch : shape) {
+            if (ch >= '0' && ch <= '9') {
+                if (cur > (1ull << 40)) fail("a dimension of the .npy shape is out of range");
+                cur = cur * 10 + static_cast<uint64_t>(ch - '0');
+                digits = true;
+            } else if (ch == ',' || ch == ')') {
+                if (digits) dims.push_back(cur);
+                cur = 0;
+                digits = false;
+            } else if (ch != '(' && ch != 'L') {
+                fail("malformed .npy shape " + shape);
+            }
+        }
+    }
+    if (dims.size() != 3) fail("a density grid must be a 3-D array of shape (nz, ny, nx); the file holds " + std::to_string(dims.size()) + " dimension(s)");
+    for (const uint64_t dmn : dims)
+        if (dmn == 0 || dmn > 512) fail("a density grid's dimensions must lie in 1 .. 512; the file's shape is " + shape);
+    const size_t count = static_cast<size_t>(dims[0] * dims[1] * dims[2]);
+    if ((size - at - headerLen) / sizeof(float) < count) fail("truncated .npy data: the shape " + shape + " needs more floats than the file holds");
+    DensityGrid g;
+    g.nz = static_cast<uint32_t>(dims[0]);
+    g.ny = static_cast<uint32_t>(dims[1]);
+    g.nx = static_cast<uint32_t>(dims[2]);
+    g.voxels.resize(count);
+    std::memcpy(g.voxels.data(), data + at + headerLen, count * sizeof(float));  // (little-endian hosts only, as the rest of the readers)
+    return g;
+}
+
+DensityGrid IMGLoader::LoadNPYGrid(const std::string& filepath)
+{
+    std::ifstream f(filepath, std::ios::binary);
+    if (!f) fail("cannot open " + filepath);
+    const std::vector<unsigned char> data((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+    return LoadNPYGrid(data.data(), data.size());
+}
+
 Texture IMGLoader::LoadIMG(const std::string& filepath)
 {
     std::ifstream f(filepath, std::ios::binary);

@@ -229,6 +229,11 @@ void PathTracer::UpdateDeviceScene(const Scene& scene)
         Check(nxhip_set_medium(m_Ctx, scene.GetMedium()), "nxhip_set_medium");
         scene.mediumDirty = false;
     }
+    if (scene.mediumDensityDirty) {
+        const DensityGrid* g = scene.GetMediumDensity();
+        Check(nxhip_set_medium_density(m_Ctx, g ? g->voxels.data() : nullptr, g ? g->nx : 0u, g ? g->ny : 0u, g ? g->nz : 0u), "nxhip_set_medium_density");
+        scene.mediumDensityDirty = false;
+    }
     const nx_camera cam = Camera::ToDevice(*scene.GetCamera());
     Check(nxhip_set_camera(m_Ctx, &cam), "nxhip_set_camera");
     Check(nxhip_set_render_settings(m_Ctx, reinterpret_cast<const nx_render_settings*>(&scene.GetRenderSettings())), "nxhip_set_render_settings");

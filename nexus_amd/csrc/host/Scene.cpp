@@ -25,6 +25,7 @@ void Scene::Reset()
     if (!m_AnalyticLights.empty()) analyticLightsDirty = true;  // (the device must hear that they are gone)
     m_AnalyticLights.clear();
     ClearMedium();
+    ClearMediumDensity();
     m_AssetManager.Reset();
     m_Camera->Invalidate();
     m_TlasBuiltFor = 0;

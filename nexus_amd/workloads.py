@@ -55,6 +55,8 @@ class Workload:
     material_detail = None
     # extension: fog — a pod.MEDIUM_DT record (pod.make_medium), None: no medium (nxhip_set_medium); applied by upload
     medium = None
+    # ... and its density grid: a float32 array (nz, ny, nx) over the medium's box, None: none (nxhip_set_medium_density); applied by upload
+    medium_density = None
 
     def __init__(self, meshes, placements, materials=None, lights=None, camera=None, settings=None, diffuse_maps=(), emissive_maps=(),
                  hdr_map=None, build_threads=4):
@@ -138,6 +140,7 @@ class Workload:
         ctx.set_light_sampling(self.light_sampling)
         ctx.set_shadow_transmittance(self.shadow_transmittance)
         ctx.set_medium(self.medium)
+        ctx.set_medium_density(self.medium_density)
 
 
 def _look(eye, target, hfov, width, height):
