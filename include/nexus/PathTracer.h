@@ -43,6 +43,9 @@ public:
     // small-pass measures of the device layer (include/nexus_hip.h), none of which changes the image.
     void SetFramesPerPass(uint32_t frames);
     void SetPassesInFlight(uint32_t passes);
+    // Hardware queues the device layer may count on when it shapes the passes in flight (nxhip_set_queue_budget): 0 = as
+    // GPU_MAX_HW_QUEUES says (else 4), 1 .. 32 = this many.  Does not change the image.
+    void SetQueueBudget(int queues);
     void SetTailBounce(uint32_t bounce);
     // Primary rays start from the traversal state the first node steps of their run of 64 paths provably share instead of the TLAS
     // root (nxhip_set_entry_points: hit records unchanged, pinhole cameras only).  Off by default.

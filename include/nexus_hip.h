@@ -456,10 +456,32 @@ int nxhip_set_frames_per_pass(nxhip_ctx *ctx, uint32_t frames);
  * pass more than half of the pass — overlaps with the bulk of the next passes.  nxhip_accumulate folds every finished pass
  * into the one accumulation, oldest first: the image is bit-identical to R = 1.  Worth it for small passes (one frame per
  * pass: 2.2x at R = 6; 20 frames per pass: +20 % at R = 4; the persistent trace launches of the slots are sized to share the
- * CUs).  Needs enough hardware queues: export GPU_MAX_HW_QUEUES=24
- * before the process touches HIP (the runtime's default of 4 serialises the slots).  Kernel timing, the counting variant and
+ * CUs).  Fastest with enough hardware queues: export GPU_MAX_HW_QUEUES=24 before the process touches HIP; with the runtime's
+ * default of 4 the pass graphs take the shape that fits them (nxhip_set_queue_budget).  Kernel timing, the counting variant and
  * a bound radiance buffer fall back to one pass at a time. */
 int nxhip_set_passes_in_flight(nxhip_ctx *ctx, uint32_t passes);
+
+/* Queue budget: the hardware queues the library may count on when it shapes the work of R passes in flight.  Resolved at
+ * nxhip_create: GPU_MAX_HW_QUEUES if the environment sets it to a whole number in [1, 32], else 4 (the runtime's own default).  The
+ * library only READS the variable and never changes the runtime's queues.  R passes in flight need 2 R + 1 lanes (two parallel graph
+ * branches per slot — closest-hit beside any-hit — and the context's stream for the accumulates).  Where that exceeds the budget, a
+ * slot's pass graph is built as a single chain (every launch of a level behind the one in front of it), so that a slot is one lane
+ * and no branch of its graph queues behind another slot's launches (four passes in flight on four queues: +13 %).  Same kernels,
+ * arguments and grids either way: the image is bit-identical.  The accumulates stay on the context's stream.  One pass at a time and
+ * every run whose lanes fit the budget keep the parallel graphs.
+ * nxhip_set_queue_budget: queues = 0 reads the environment again, 1 .. 32 is an explicit budget, anything else NXHIP_ERR_INVALID; waits
+ * for everything issued, like nxhip_set_passes_in_flight; the next pass picks or builds the graph instance of the matching shape.
+ * nxhip_get_queue_budget (each destination may be NULL): the resolved budget; 1 if a pass issued now would replay the chain shape, else 0;
+ * the largest number of pass-graph instances any slot holds. */
+int nxhip_set_queue_budget(nxhip_ctx *ctx, int queues);
+int nxhip_get_queue_budget(nxhip_ctx *ctx, uint32_t *queues, uint32_t *chained, uint32_t *graphInstances);
+/* The budget a value of GPU_MAX_HW_QUEUES resolves to (NULL: the variable is not set): a whole number in [1, 32] is itself, anything
+ * else 4.  Needs no context and no device. */
+uint32_t nxhip_queue_budget_from_text(const char *text);
+/* Test hook: the pass graph the last pass replayed, counted from the runtime's graph object when the instance was built — kernel nodes,
+ * dependency edges, and the largest number of nodes that depend on one and the same node (1: a chain; 2: closest-hit beside any-hit).
+ * Each destination may be NULL. */
+int nxhip_debug_last_graph(nxhip_ctx *ctx, uint32_t *nodes, uint32_t *edges, uint32_t *fanOut);
 
 /* Tail kernel (no counterpart in the reference, whose graph has one node per kernel and bounce, PathTracer.cpp:114-124).
  * From bounce `bounce` on — 2 .. pathLength, 0 = off — the rest of every path is run by ONE launch after the trace of

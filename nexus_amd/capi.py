@@ -40,6 +40,7 @@ HIP_SYMBOLS = [
     "nxhip_set_material_detail", "nxhip_shading_frame_batch",
     "nxhip_set_medium", "nxhip_medium_segment_batch", "nxhip_medium_phase_batch",
     "nxhip_set_medium_density", "nxhip_read_medium_majorants", "nxhip_medium_density_batch", "nxhip_medium_track_batch",
+    "nxhip_set_queue_budget", "nxhip_get_queue_budget", "nxhip_queue_budget_from_text", "nxhip_debug_last_graph",
 ]
 HOST_SYMBOLS = [
     "nxh_bvh8_build", "nxh_tlas_build", "nxh_tlas_refit", "nxh_bvh8_refit", "nxh_bvh8_node_count", "nxh_bvh8_prim_count", "nxh_bvh8_nodes",
@@ -1161,6 +1162,27 @@ class Context:
         self.L.nxhip_set_passes_in_flight.argtypes = [C.c_void_p, C.c_uint32]
         check(self.L.nxhip_set_passes_in_flight(self.h, passes), "nxhip_set_passes_in_flight")
 
+    def set_queue_budget(self, queues):
+        """hardware queues the library may count on when it shapes R passes in flight: 0 = read GPU_MAX_HW_QUEUES again (else 4),
+        1 .. 32 = this many (include/nexus_hip.h)"""
+        self.L.nxhip_set_queue_budget.argtypes = [C.c_void_p, C.c_int]
+        check(self.L.nxhip_set_queue_budget(self.h, int(queues)), "nxhip_set_queue_budget")
+
+    def queue_budget(self):
+        """(budget, chained, graph_instances): the resolved budget, whether a pass issued now replays the chain shape, the largest
+        number of pass-graph instances a slot holds"""
+        self.L.nxhip_get_queue_budget.argtypes = [C.c_void_p] + [C.POINTER(C.c_uint32)] * 3
+        q, ch, g = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+        check(self.L.nxhip_get_queue_budget(self.h, C.byref(q), C.byref(ch), C.byref(g)), "nxhip_get_queue_budget")
+        return int(q.value), bool(ch.value), int(g.value)
+
+    def debug_last_graph(self):
+        """(nodes, edges, fan_out) of the pass graph the last pass replayed, as the runtime holds it; fan_out 1: a chain (a test hook)"""
+        self.L.nxhip_debug_last_graph.argtypes = [C.c_void_p] + [C.POINTER(C.c_uint32)] * 3
+        n, e, f = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+        check(self.L.nxhip_debug_last_graph(self.h, C.byref(n), C.byref(e), C.byref(f)), "nxhip_debug_last_graph")
+        return int(n.value), int(e.value), int(f.value)
+
     def set_frames_per_pass(self, frames):
         check(self.L.nxhip_set_frames_per_pass(self.h, frames), "nxhip_set_frames_per_pass")
         self.frames_per_pass = int(frames)
@@ -1453,6 +1475,14 @@ def mgpu_unique_id():
 
 def device_count():
     return int(lib().nxhip_device_count())
+
+
+def queue_budget_from_text(text):
+    """nxhip_queue_budget_from_text: the queue budget a value of GPU_MAX_HW_QUEUES resolves to (None: not set); no device needed"""
+    L = lib()
+    L.nxhip_queue_budget_from_text.argtypes = [C.c_char_p]
+    L.nxhip_queue_budget_from_text.restype = C.c_uint32
+    return int(L.nxhip_queue_budget_from_text(None if text is None else str(text).encode()))
 
 
 # ---- C++ Scene / PathTracer facade (include/nexus/Scene.h, PathTracer.h) -------------------------------

@@ -128,6 +128,8 @@ struct PassSlot {
         hipGraphExec_t exec = nullptr;
         int traceBlocks = 0, tailBounce = 0;
         int flavor = 0;  // pass_flavor(): pipeline, miss kernel, logic kernel variant, ..., the scene-specialised kernel instances
+        int shape = 0;   // graph_shape(): 0 = the levels' launches side by side, 1 = every level a chain (the lanes do not fit the queue budget)
+        uint32_t nodes = 0, edges = 0, fanOut = 0;  // of `graph`, as the runtime reports them (measure_graph; nxhip_debug_last_graph)
     };
     std::vector<GraphInstance> graphs;
     // pass bookkeeping (slots >= 1 and slot 0 alike)
@@ -149,6 +151,12 @@ struct nxhip_ctx : nxd::PassSlot {
     std::vector<std::unique_ptr<nxd::PassSlot>> extra;
     uint32_t passesInFlight = 1;
     uint32_t nextSlot = 0;                 // slot the next rendered pass goes to
+    // Hardware queues the process may count on (nxhip_set_queue_budget; resolved at nxhip_create from GPU_MAX_HW_QUEUES, else 4 —
+    // the runtime's own default).  Only read: it decides the SHAPE of the pass graphs (graph_shape in nxhip_render.hip), never
+    // the runtime's queues.
+    uint32_t queueBudget = 4;
+    int shapeForced = -1;          // NX_TUNING_KNOBS sweeps only (NX_GRAPH_SHAPE): -1 = by the budget, else the shape itself
+    uint32_t lastGraphNodes = 0, lastGraphEdges = 0, lastGraphFanOut = 0;  // of the graph instance the last pass replayed (nxhip_debug_last_graph)
     std::vector<nxd::PassSlot*> pending;   // rendered, not yet accumulated, oldest first
     nxd::PassSlot* lastRendered = nullptr;
 

@@ -324,6 +324,8 @@ int refresh_updated_blas(nxhip_ctx* c);
 int check_scene_ready(nxhip_ctx* c);
 int launch_now(nxhip_ctx* c, const Launch& l, hipStream_t stream = nullptr);  // (stream: the context's own unless given)
 int render_pass(nxhip_ctx* c, uint32_t framesArg);
+uint32_t queue_budget_from_text(const char* text);  // what a value of GPU_MAX_HW_QUEUES means: a whole number in [1, 32], else 4
+uint32_t queue_budget_from_environment();           // ... of the variable as it is now (nxhip_create, nxhip_set_queue_budget)
 int read_float4_as_float3(nxhip_ctx* c, const void* dev, uint32_t count, float* dst);
 // nxhip_features.hip
 int adaptive_restart(nxhip_ctx* c);

@@ -129,8 +129,8 @@ void nxd::invalidate_graph(nxhip_ctx* c)
 // may run over it; a queue buffer holds kQueueShards regions.
 static size_t queue_region_cap(size_t n) { return ((n + kQueueShards * 64 - 1) / (kQueueShards * 64)) * 64 + kQueueShardSlack; }
 static size_t queue_buffer_slots(size_t n) { return queue_region_cap(n) * kQueueShards; }
-// entries per list of rays handed to the thin kernel (nx_trace.hip): a launch hands over at most DeviceState::thinLanes (4) rays per wave, 20 480 for a
-// full grid; a list that runs over only makes the waves it has no room for finish their rays themselves
+// entries per list of rays handed to the thin kernel (nx_trace.hip): a launch hands over at most DeviceState::thinLanes (16) rays per wave, 81 920 for a
+// full grid if every wave handed over as many as it may; a list that runs over only makes the waves it has no room for finish their rays themselves
 constexpr uint32_t kThinListEntries = 1u << 15;  // (x 2 lists x (4 B + a 320-byte ThinState) = 21 MB per slot)
 static size_t scan_status_tiles(size_t n) { return n / (size_t)std::min(kLogicBlockThreads, kShadeBlockThreads) + 2; }
 
@@ -430,6 +430,7 @@ int nxhip_create(int device, uint32_t width, uint32_t height, void* stream, nxhi
     c->device = device;
     c->width = width;
     c->height = height;
+    c->queueBudget = queue_budget_from_environment();
     int rc = NXHIP_OK;
     do {
         if (stream) c->stream = (hipStream_t)stream;
@@ -527,6 +528,7 @@ int nxhip_create(int device, uint32_t width, uint32_t height, void* stream, nxhi
             }
             if (const char* e = std::getenv("NX_THIN_LANES")) { const int n = std::atoi(e); if (n >= 1 && n <= 64) c->h.thinLanes = (uint32_t)n; }   // sweeps of the hand-over rule
             if (const char* e = std::getenv("NX_THIN_ITERS")) { const int n = std::atoi(e); if (n >= 1 && n <= 4096) c->h.thinIters = (uint32_t)n; }
+            if (const char* e = std::getenv("NX_GRAPH_SHAPE")) { const int n = std::atoi(e); if (n == 0 || n == 1) c->shapeForced = n; }  // sweeps of the pass-graph shape (graph_shape)
             if (const char* e = std::getenv("NX_TRACE_BLOCKS_TOTAL")) {  // tuning experiments only
                 const int n = std::atoi(e);
                 if (n >= 1 && n <= 65536) { c->traceBlocks = c->shadowBlocks = n; c->traceGridForced = true; }

@@ -67,6 +67,17 @@ int nxd::check_scene_ready(nxhip_ctx* c)
     return NXHIP_OK;
 }
 
+// What a value of GPU_MAX_HW_QUEUES means to the runtime: a whole number in [1, 32]; anything else, or no value, is the runtime's
+// default of four.  The library only reads the variable (nxhip_create, nxhip_set_queue_budget), it never sets it.
+uint32_t nxd::queue_budget_from_text(const char* text)
+{
+    if (!text || !*text) return 4u;
+    char* end = nullptr;
+    const long n = std::strtol(text, &end, 10);
+    return (*end == '\0' && n >= 1 && n <= 32) ? (uint32_t)n : 4u;
+}
+uint32_t nxd::queue_budget_from_environment() { return queue_budget_from_text(std::getenv("GPU_MAX_HW_QUEUES")); }
+
 namespace {
 
 // Every pass starts with begin_frame_kernel, launched outside the graph because its argument (the pass size) may change from
@@ -102,6 +113,30 @@ uint32_t effective_slots(const nxhip_ctx* c)
 {
     if (c->timingEnabled || c->statsEnabled || c->radianceBoundCapacity != 0) return 1u;
     return std::min<uint32_t>(c->passesInFlight, (uint32_t)c->extra.size());
+}
+
+// The shape of a slot's pass graph.  Launches of one level that do not depend on each other are parallel graph branches, and the
+// runtime gives every branch a lane of its own: with R passes in flight that is R x 2 lanes (closest-hit beside any-hit in every
+// bounce; the feature launch beside the bounce-1 material launch) plus the context's stream.  All lanes are mapped onto the
+// process's hardware queues, which are in-order: where there are fewer queues than lanes (four by default) a level's second branch
+// lands in a queue it shares with another slot and stands behind launches it does not depend on — the kernel trace shows any-hit
+// launches ready 22-25 ms before they start, their pass waiting with them, and two slots resident only 24 % of the time.
+// kShapeChain is the frugal shape for that case: within a level every launch waits for the one in front of it (closest-hit,
+// [medium_shadow_kernel,] any-hit; the feature launch behind the bounce-1 material launch), so a slot is ONE lane.  Same kernels,
+// arguments and grids, more dependency edges: the image does not change.  One pass at a time, timing / counting runs and a bound
+// radiance buffer (effective_slots() == 1) and every run whose lanes fit the budget keep the parallel shape, node for node.
+// Four passes in flight on four queues, 64-frame passes: 2 440 -> 2 755 Msamples/s, two slots resident 56 % of the time
+// (profiles/queue_budget.txt).  The accumulates stay on the context's stream, the lane beside the slots': issued on the slots'
+// own streams, in pass order by events, the chain's gain was gone (2 449) — the accumulate of pass n + 1 then holds its slot
+// until pass n has been folded in.
+constexpr int kShapeParallel = 0, kShapeChain = 1;
+constexpr uint32_t kBranchesPerLevel = 2;
+int graph_shape(const nxhip_ctx* c)
+{
+    const uint32_t R = effective_slots(c);
+    if (R <= 1u) return kShapeParallel;
+    if (c->shapeForced >= 0) return c->shapeForced;  // (sweeps only: NX_TUNING_KNOBS)
+    return R * kBranchesPerLevel + 1u > c->queueBudget ? kShapeChain : kShapeParallel;
 }
 
 // Workgroups of a persistent trace launch.  The grid that fills the chip (6 workgroups per CU) is right for ONE large pass.
@@ -249,6 +284,18 @@ std::vector<std::vector<Launch>> frame_levels(nxhip_ctx* c, PassSlot* q)
     const int wide = c->wideBlocks;
     const int wideThreads = kWideBlockThreads;
     std::vector<std::vector<Launch>> levels;
+    // the chain shape (graph_shape): every launch of a level behind the one in front of it, in the order the level lists them
+    const bool chain = graph_shape(c) == kShapeChain;
+    auto shaped = [chain](std::vector<std::vector<Launch>>& ls) {
+        if (chain)
+            for (auto& level : ls)
+                for (size_t k = 1; k < level.size(); k++) {
+                    // (a level lists its launches in an order that is a valid serial one: whatever a launch already waits for
+                    //  inside the level stands in front of it, so the chain implies that edge)
+                    level[k].after = (int)k - 1;
+                }
+        return std::move(ls);
+    };
     levels.push_back({make_launch(kernels::generate(), wide, wideThreads, NXHIP_K_GENERATE, S)});
     // (the entry states the primary launch below installs are not a pass's work: the slot's table is walked in front of the pass
     //  that finds it stale — walk_entry_states — and read by every pass until an input of the walk changes)
@@ -341,7 +388,7 @@ std::vector<std::vector<Launch>> frame_levels(nxhip_ctx* c, PassSlot* q)
             }
             thin_level(bounce | kTraceScanFlag);
         }
-        return levels;
+        return shaped(levels);
     }
     // CLASSIC pipeline (ordered compaction; no tail kernel: tail_bounce): per bounce logic kernel -> the material kernels of the
     // types in use -> trace || shadow trace
@@ -367,7 +414,7 @@ std::vector<std::vector<Launch>> frame_levels(nxhip_ctx* c, PassSlot* q)
                           shadow_launch(shadowBlocks, bounce, thinFlag)});
         thin_level(bounce);
     }
-    return levels;
+    return shaped(levels);
 }
 
 }  // namespace
@@ -412,11 +459,28 @@ int nxd::launch_now(nxhip_ctx* c, const Launch& l, hipStream_t stream)
 // only in slot 0, and only one such instance at a time: kernel timing runs one pass at a time and the events are the context's.
 constexpr size_t kMaxGraphInstances = 8;
 
+// Nodes, edges and the widest fan-out of an instance's graph, asked of the runtime (nxhip_debug_last_graph: what a test compares a
+// shape against without asking graph_shape).
+static int measure_graph(PassSlot::GraphInstance& inst)
+{
+    size_t nodes = 0, edges = 0;
+    NX_HIP(hipGraphGetNodes(inst.graph, nullptr, &nodes));
+    NX_HIP(hipGraphGetEdges(inst.graph, nullptr, nullptr, &edges));
+    std::vector<hipGraphNode_t> from(edges), to(edges);
+    if (edges) NX_HIP(hipGraphGetEdges(inst.graph, from.data(), to.data(), &edges));
+    size_t widest = 0;
+    for (size_t i = 0; i < edges; i++) widest = std::max(widest, (size_t)std::count(from.begin(), from.begin() + (ptrdiff_t)edges, from[i]));
+    inst.nodes = (uint32_t)nodes;
+    inst.edges = (uint32_t)edges;
+    inst.fanOut = (uint32_t)widest;
+    return NXHIP_OK;
+}
+
 static int pass_graph(nxhip_ctx* c, PassSlot* q, hipGraphExec_t* execOut)
 {
-    const int blocks = trace_blocks(c, c->traceBlocks), tail = tail_bounce(c), flavor = pass_flavor(c);
+    const int blocks = trace_blocks(c, c->traceBlocks), tail = tail_bounce(c), flavor = pass_flavor(c), shape = graph_shape(c);
     for (auto& g : q->graphs)
-        if (g.traceBlocks == blocks && g.tailBounce == tail && g.flavor == flavor) {
+        if (g.traceBlocks == blocks && g.tailBounce == tail && g.flavor == flavor && g.shape == shape) {
             *execOut = g.exec;
             return NXHIP_OK;
         }
@@ -434,6 +498,7 @@ static int pass_graph(nxhip_ctx* c, PassSlot* q, hipGraphExec_t* execOut)
     inst.traceBlocks = blocks;
     inst.tailBounce = tail;
     inst.flavor = flavor;
+    inst.shape = shape;
     NX_HIP(hipGraphCreate(&inst.graph, 0));
     auto fail = [&](int rc) {
         if (inst.exec) (void)hipGraphExecDestroy(inst.exec);
@@ -482,6 +547,7 @@ static int pass_graph(nxhip_ctx* c, PassSlot* q, hipGraphExec_t* execOut)
         prev.swap(cur);
     }
     if (!hip_ok(hipGraphInstantiate(&inst.exec, inst.graph, nullptr, nullptr, 0), "hipGraphInstantiate", __FILE__, __LINE__)) return fail(NXHIP_ERR_HIP);
+    if (const int rcMeasure = measure_graph(inst)) return fail(rcMeasure);
     q->graphs.push_back(inst);
     *execOut = inst.exec;
     return NXHIP_OK;
@@ -609,6 +675,8 @@ try {
         hipGraphExec_t exec = nullptr;
         NX_TRY(pass_graph(c, q, &exec));
         NX_HIP(hipGraphLaunch(exec, q->stream));
+        for (const auto& g : q->graphs)
+            if (g.exec == exec) { c->lastGraphNodes = g.nodes; c->lastGraphEdges = g.edges; c->lastGraphFanOut = g.fanOut; }
         if (c->timingMode == 3) c->graphTimersPending = true;  // read at nxhip_read_kernel_times: the last replay only
         if (c->timingMode == 2) {
             // the graph's events are re-recorded by the next replay: read them now (timing mode is not the fast path)
@@ -869,6 +937,45 @@ try {
     c->stateDirty = true;
     return NXHIP_OK;
 } NX_CATCH("nxhip_set_passes_in_flight")
+
+// The queue budget (nx_context.h queueBudget; graph_shape above): 0 = as the environment says, 1..32 = this many.
+// A decision of the library about its own graphs and streams: the next pass picks or builds the graph instance of the shape that
+// follows (the shape is part of an instance's key), nothing of the runtime is touched.
+int nxhip_set_queue_budget(nxhip_ctx* c, int queues)
+try {
+    NX_CHECK_CTX(c);
+    if (queues < 0 || queues > 32) return fail_invalid("nxhip_set_queue_budget: queues must be 0 (read GPU_MAX_HW_QUEUES) or in [1, 32]");
+    NX_HIP(hipSetDevice(c->device));
+    NX_SYNC_ALL(c);
+    c->queueBudget = queues == 0 ? queue_budget_from_environment() : (uint32_t)queues;
+    return NXHIP_OK;
+} NX_CATCH("nxhip_set_queue_budget")
+
+int nxhip_get_queue_budget(nxhip_ctx* c, uint32_t* queues, uint32_t* chained, uint32_t* graphInstances)
+{
+    NX_CHECK_CTX(c);
+    if (queues) *queues = c->queueBudget;
+    if (chained) *chained = graph_shape(c) == kShapeChain ? 1u : 0u;
+    if (graphInstances) {
+        *graphInstances = 0u;
+        for (uint32_t k = 0; k < slot_count(c); k++) *graphInstances = std::max(*graphInstances, (uint32_t)slot_at(c, k)->graphs.size());
+    }
+    return NXHIP_OK;
+}
+
+uint32_t nxhip_queue_budget_from_text(const char* text) { return queue_budget_from_text(text); }
+
+// The graph the last pass replayed, as the runtime holds it (counted from the hipGraph itself when the instance was built:
+// measure_graph): kernel nodes, dependency edges, and the largest number of nodes that wait for one and the same node.
+int nxhip_debug_last_graph(nxhip_ctx* c, uint32_t* nodes, uint32_t* edges, uint32_t* fanOut)
+{
+    NX_DEBUG_HOOK("nxhip_debug_last_graph");  // (first: a release library refuses whatever it is handed)
+    NX_CHECK_CTX(c);
+    if (nodes) *nodes = c->lastGraphNodes;
+    if (edges) *edges = c->lastGraphEdges;
+    if (fanOut) *fanOut = c->lastGraphFanOut;
+    return NXHIP_OK;
+}
 
 int nxhip_set_frames_per_pass(nxhip_ctx* c, uint32_t frames)
 {

@@ -245,6 +245,7 @@ void PathTracer::SetFramesPerPass(uint32_t frames)
     m_FramesPerPass = frames;
 }
 void PathTracer::SetPassesInFlight(uint32_t passes) { Check(nxhip_set_passes_in_flight(m_Ctx, passes), "nxhip_set_passes_in_flight"); }
+void PathTracer::SetQueueBudget(int queues) { Check(nxhip_set_queue_budget(m_Ctx, queues), "nxhip_set_queue_budget"); }
 void PathTracer::SetTailBounce(uint32_t bounce) { Check(nxhip_set_tail_bounce(m_Ctx, bounce), "nxhip_set_tail_bounce"); }
 void PathTracer::SetEntryPoints(bool on) { Check(nxhip_set_entry_points(m_Ctx, on ? 1 : 0), "nxhip_set_entry_points"); }
 void PathTracer::SetLightSampling(int mode) { Check(nxhip_set_light_sampling(m_Ctx, mode), "nxhip_set_light_sampling"); }
