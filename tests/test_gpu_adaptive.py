@@ -12,6 +12,7 @@ import pytest
 
 from nexus_amd import capi, pod
 from tests import adaptive_reference as A
+from tests import feature_scenes as FS
 from tests import scene_helpers as SH
 
 pytestmark = pytest.mark.gpu
@@ -34,6 +35,7 @@ SCENES = {
     "cornell": (lambda: SH.cornell_scene(64, 64, path_length=4), 64, 64),  # 64 blocks
     "zoo": (_zoo, 96, 64),                                                 # 96 blocks
     "partial": (_small_cornell, 40, 30),                                   # 18 blocks and one of 48 pixels
+    "all features": (lambda: FS.all_features_scene(64, 48), 64, 48),       # 48 blocks; every shading feature on (tests/feature_scenes.py)
 }
 
 
@@ -205,7 +207,7 @@ def _adaptive_ctx(factory, rec, thr, cull=1, **how):
     return ctx
 
 
-@pytest.mark.parametrize("name", ["cornell", "zoo", "partial"])
+@pytest.mark.parametrize("name", ["cornell", "zoo", "partial", "all features"])
 def test_decisions_active_set_and_statistics_follow_the_simulator(gpu_ctx_factory, name):
     rec = _reference(gpu_ctx_factory, name)
     thr, sim, hist = _simulated(rec)
