@@ -956,7 +956,8 @@ __global__ void __launch_bounds__(kBlock) collapse_level_kernel(const Bvh2 t, co
         // quantisation frame, as nexus::collapse: e = ceil(log2(extent / 255)) per axis
         float invScale[3];
         for (int a = 0; a < 3; a++) {
-            const float ex = ceilf((float)log2((double)((nb.hi[a] - nb.lo[a]) * (1.0f / 255.0f))));
+            float ex = ceilf((float)log2((double)((nb.hi[a] - nb.lo[a]) * (1.0f / 255.0f))));
+            if (fabsf(ex) < 126.0f && 255.0f * ldexpf(1.0f, (int)ex) < nb.hi[a] - nb.lo[a]) ex += 1.0f;  // 255 * 2^e >= fl(extent), exactly
             uint32_t e = 0;
             if (ex == ex && ex > -127.0f) e = ex >= 128.0f ? 255u : (uint32_t)((int)ex + 127);
             const float pw = ex == ex ? (ex < -200.0f ? 0.0f : (ex > 200.0f ? __uint_as_float(0x7f800000u) : ldexpf(1.0f, (int)ex))) : ex;
@@ -1019,7 +1020,8 @@ __device__ void small_mesh_node(const Box3* __restrict__ triBox, const int n, nx
     node = nx_bvh8_node{};
     float invScale[3];
     for (int a = 0; a < 3; a++) {
-        const float ex = ceilf((float)log2((double)((nb.hi[a] - nb.lo[a]) * (1.0f / 255.0f))));
+        float ex = ceilf((float)log2((double)((nb.hi[a] - nb.lo[a]) * (1.0f / 255.0f))));
+        if (fabsf(ex) < 126.0f && 255.0f * ldexpf(1.0f, (int)ex) < nb.hi[a] - nb.lo[a]) ex += 1.0f;  // 255 * 2^e >= fl(extent), exactly
         uint32_t e = 0;
         if (ex == ex && ex > -127.0f) e = ex >= 128.0f ? 255u : (uint32_t)((int)ex + 127);
         const float pw = ex == ex ? (ex < -200.0f ? 0.0f : (ex > 200.0f ? __uint_as_float(0x7f800000u) : ldexpf(1.0f, (int)ex))) : ex;

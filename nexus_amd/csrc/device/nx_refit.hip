@@ -148,7 +148,8 @@ NXD void refit_node_frame(const Box& nb, const Box (&childBox)[8], const bool (&
     float invScale[3];
     ebytes = 0;
     for (int a = 0; a < 3; a++) {
-        const float ex = ceil_log2((nb.hi[a] - nb.lo[a]) * denom);
+        float ex = ceil_log2((nb.hi[a] - nb.lo[a]) * denom);
+        if (fabsf(ex) < 126.0f && 255.0f * ldexpf(1.0f, (int)ex) < nb.hi[a] - nb.lo[a]) ex += 1.0f;  // 255 * 2^e >= fl(extent), exactly
         // exponent byte of exp2f(ex): 0 below the normal range (and for -inf: a degenerate axis), 255 above it
         uint32_t e = 0;
         if (ex == ex && ex > -127.0f) e = ex >= 128.0f ? 255u : (uint32_t)((int)ex + 127);

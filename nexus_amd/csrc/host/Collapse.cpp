@@ -9,8 +9,9 @@
 // Re-design: the cost table is one flat array filled bottom-up in a single sweep (children always
 // have larger indices than their parent in the BVH2 this library builds; the TLAS tree is swept in
 // creation order), instead of a memoised recursion over vector<vector<NodeEval>>.
-// Deviation (documented in DESIGN.md): quantised bounds are clamped to [0,255]; the reference BLAS path
-// lets ceil() == 256 wrap to 0.
+// Deviations (documented in DESIGN.md): quantised bounds are clamped to [0,255]; the reference BLAS path
+// lets ceil() == 256 wrap to 0.  The frame exponent is raised by one where the rounded logarithm left
+// 255 * 2^e short of the extent (FrameExponent), so that the clamp is never what decides an upper bound.
 #include "Collapse.h"
 
 #include <cassert>
@@ -48,6 +49,18 @@ uint8_t Quantize(float v)
     if (v <= 0.0f) return 0;
     if (v >= 255.0f) return 255;
     return static_cast<uint8_t>(v);
+}
+
+// Exponent of one axis of a node's quantisation frame: e = ceil(log2(extent / 255)), raised by one where the rounded logarithm
+// (or the rounded division) came out a step short.  255 * 2^e >= fl(hi - lo) then holds exactly (the product is exact in binary32),
+// so ceil() of a child's upper offset, taken from the same rounded subtraction, never exceeds 255 and Quantize's clamp cannot
+// cut a box short of what it bounds.
+float FrameExponent(float lo, float hi)
+{
+    const float denom = 1.0f / static_cast<float>((1 << N_Q) - 1);
+    float ex = std::ceil(std::log2((hi - lo) * denom));
+    if (std::fabs(ex) < 126.0f && 255.0f * std::ldexp(1.0f, static_cast<int>(ex)) < hi - lo) ex += 1.0f;
+    return ex;
 }
 
 }  // namespace
@@ -166,10 +179,9 @@ struct Collapser {
     void CollapseNode(uint32_t n2, uint32_t n8)
     {
         const AABB nb = t.box(n2);
-        const float denom = 1.0f / static_cast<float>((1 << N_Q) - 1);
-        const float ex = std::ceil(std::log2((nb.bMax.x - nb.bMin.x) * denom));
-        const float ey = std::ceil(std::log2((nb.bMax.y - nb.bMin.y) * denom));
-        const float ez = std::ceil(std::log2((nb.bMax.z - nb.bMin.z) * denom));
+        const float ex = FrameExponent(nb.bMin.x, nb.bMax.x);
+        const float ey = FrameExponent(nb.bMin.y, nb.bMax.y);
+        const float ez = FrameExponent(nb.bMin.z, nb.bMax.z);
         const float pw[3] = {std::exp2(ex), std::exp2(ey), std::exp2(ez)};
 
         BVH8Node node;
@@ -273,10 +285,9 @@ AABB Refit(std::vector<BVH8Node>& nodes, const uint32_t* primIdx, const AABB* pr
             nb.Grow(cb);
         }
         nodeBox[k] = nb;
-        const float denom = 1.0f / static_cast<float>((1 << N_Q) - 1);
-        const float ex = std::ceil(std::log2((nb.bMax.x - nb.bMin.x) * denom));
-        const float ey = std::ceil(std::log2((nb.bMax.y - nb.bMin.y) * denom));
-        const float ez = std::ceil(std::log2((nb.bMax.z - nb.bMin.z) * denom));
+        const float ex = FrameExponent(nb.bMin.x, nb.bMax.x);
+        const float ey = FrameExponent(nb.bMin.y, nb.bMax.y);
+        const float ez = FrameExponent(nb.bMin.z, nb.bMax.z);
         const float pw[3] = {std::exp2(ex), std::exp2(ey), std::exp2(ez)};
         for (int a = 0; a < 3; a++) {
             uint32_t bits;

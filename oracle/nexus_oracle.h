@@ -53,7 +53,8 @@ void orc_bvh2_free(orc_bvh2 *b);
 
 /* BVH2 -> BVH8 collapse (Ylitie 2017 DP).  Geometry/BVH/BVH8Builder.cpp:7-393.
  * clamp_qhi = 0 mirrors the reference BLAS path (u8 cast wraps), 1 clamps ceil() to 255 like the
- * reference TLAS path (TLASBuilder.cpp:314-316). */
+ * reference TLAS path (TLASBuilder.cpp:314-316) and, as the product does, raises a frame exponent by one
+ * where 255 * 2^e is short of the extent (the clamp is then never reached); orc_tlas_build does the same. */
 int orc_bvh8_build(const nx_triangle *tris, uint32_t n, int clamp_qhi, orc_bvh8 *out);
 void orc_bvh8_free(orc_bvh8 *b);
 

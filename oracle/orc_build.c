@@ -434,14 +434,26 @@ static void ensure_nodes8(collapse_ctx *c, uint32_t n)
     }
 }
 
+/* the exponent raised by one where the rounded logarithm left 255 * 2^e short of the extent */
+static float frame_exponent_fix(float e, float lo, float hi)
+{
+    if (fabsf(e) < 126.0f && 255.0f * ldexpf(1.0f, (int)e) < hi - lo) e += 1.0f;
+    return e;
+}
+
 /* BVH8Builder.cpp:273-393 */
 static void collapse_node(collapse_ctx *c, uint32_t n2, uint32_t n8)
 {
     aabb nb = tv_box(&c->t, n2);
     const float denom = 1.0f / (float)((1 << N_Q) - 1);
-    const float ex = ceilf(log2f((nb.bMax.x - nb.bMin.x) * denom));
-    const float ey = ceilf(log2f((nb.bMax.y - nb.bMin.y) * denom));
-    const float ez = ceilf(log2f((nb.bMax.z - nb.bMin.z) * denom));
+    float ex = ceilf(log2f((nb.bMax.x - nb.bMin.x) * denom));
+    float ey = ceilf(log2f((nb.bMax.y - nb.bMin.y) * denom));
+    float ez = ceilf(log2f((nb.bMax.z - nb.bMin.z) * denom));
+    if (c->clampQhi) { /* the product's rule (not the reference's): 255 * 2^e >= fl(extent) exactly, so the clamp below never cuts a box short */
+        ex = frame_exponent_fix(ex, nb.bMin.x, nb.bMax.x);
+        ey = frame_exponent_fix(ey, nb.bMin.y, nb.bMax.y);
+        ez = frame_exponent_fix(ez, nb.bMin.z, nb.bMax.z);
+    }
     const float exe = exp2f(ex), eye = exp2f(ey), eze = exp2f(ez);
 
     nx_bvh8_node node;

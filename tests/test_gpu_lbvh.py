@@ -4,39 +4,17 @@ import numpy as np
 import pytest
 
 from nexus_amd import capi, pod, scenegen
+from tests import bvh_audit
 from tests import scene_helpers as SH
-from tests.test_builder_parity import _decode_children
 
 pytestmark = pytest.mark.gpu
 
 
 def _check_structure(nodes, idx, tris):
-    assert sorted(idx.tolist()) == list(range(len(tris))), "every triangle exactly once"
-    tmin = np.minimum(np.minimum(tris["pos0"], tris["pos1"]), tris["pos2"]).astype(np.float64)
-    tmax = np.maximum(np.maximum(tris["pos0"], tris["pos1"]), tris["pos2"]).astype(np.float64)
-    seen_nodes, seen_prims = set(), set()
-    stack = [0]
-    while stack:
-        ni = stack.pop()
-        assert ni not in seen_nodes and ni < len(nodes)
-        seen_nodes.add(ni)
-        total, inner = 0, []
-        for s, kind, lo, hi, first, count in _decode_children(nodes[ni]):
-            eps = 1e-6 * np.maximum(1.0, np.abs(hi))
-            if kind == "inner":
-                inner.append(first)
-                stack.append(first)
-            else:
-                assert 1 <= count <= 3
-                total += count
-                for k in range(first, first + count):
-                    assert k not in seen_prims
-                    seen_prims.add(k)
-                    t = idx[k]
-                    assert np.all(lo <= tmin[t] + eps) and np.all(hi >= tmax[t] - eps), (ni, s, k)
-        assert total <= 24
-        assert inner == list(range(inner[0], inner[0] + len(inner))) if inner else True, "inner children are consecutive in slot order"
-    assert len(seen_nodes) == len(nodes) and len(seen_prims) == len(tris)
+    """tests/bvh_audit.py: structure, frames, and exact containment and tightness of every slot box, inner and leaf"""
+    rep = bvh_audit.audit(nodes, idx, *bvh_audit.triangle_boxes(tris))
+    assert rep.nodes == len(nodes)
+    return rep
 
 
 MESHES = {

@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 
 from nexus_amd import capi, pod, scenegen
+from tests import bvh_audit
 from tests import scene_helpers as SH
 
 
@@ -158,37 +159,17 @@ def _geometry_bounds(scene, instances):
     return np.array(lo), np.array(hi)
 
 
-def _check_tlas_structure(nodes, idx, instances, geometry=None):
-    """every instance exactly once; children behind their parent; every leaf slot's quantised box contains its instances'
-    world boxes — the record's (BVHInstance::SetTransform's, from the BLAS root frame), or with `geometry` = (lo, hi) per instance
-    the triangles' own: the device build tightens the record's box to what the BLAS root's children hold —; inner children
-    consecutive"""
-    from tests.test_builder_parity import _decode_children
-
-    assert sorted(idx.tolist()) == list(range(len(instances)))
-    seen_nodes, seen = set(), set()
-    stack = [0]
-    while stack:
-        ni = stack.pop()
-        assert ni not in seen_nodes and ni < len(nodes)
-        seen_nodes.add(ni)
-        inner = []
-        for s, kind, lo, hi, first, count in _decode_children(nodes[ni]):
-            eps = 1e-5 * np.maximum(1.0, np.abs(hi))
-            if kind == "inner":
-                assert first > ni
-                inner.append(first)
-                stack.append(first)
-            else:
-                assert 1 <= count <= 3
-                for k in range(first, first + count):
-                    assert k not in seen
-                    seen.add(k)
-                    inst = instances[idx[k]]
-                    want_lo, want_hi = (inst["boundsMin"], inst["boundsMax"]) if geometry is None else (geometry[0][idx[k]], geometry[1][idx[k]])
-                    assert np.all(lo <= want_lo + eps) and np.all(hi >= want_hi - eps), (ni, s, k)
-        assert inner == list(range(inner[0], inner[0] + len(inner))) if inner else True
-    assert len(seen_nodes) == len(nodes) and len(seen) == len(instances)
+def _check_tlas_structure(nodes, idx, instances, geometry=None, built=True):
+    """tests/bvh_audit.py.  Every instance exactly once, children behind their parent, inner children consecutive, and every
+    slot box, inner and leaf: without `geometry`, exact containment and tightness against the instance records' world boxes
+    (BVHInstance::SetTransform's, from the BLAS root frame), exact frames; with `geometry` = (lo, hi) per instance — the device
+    build tightens the record's box to what the BLAS root's children hold, and those boxes cannot be read back — containment of
+    the triangles' own boxes, and inner slots no wider than their leaves' union plus a step.  built=False: a tree encoded by hand
+    (tests/bvh_craft.py), whose frames follow no builder's rule — structure and exact containment only"""
+    if geometry is None:
+        return bvh_audit.audit(nodes, idx, *bvh_audit.instance_boxes(instances), tlas=True, built=built)
+    assert len(idx) == len(instances)
+    return bvh_audit.audit_tlas_geometry(nodes, idx, geometry[0], geometry[1])
 
 
 @pytest.mark.gpu
