@@ -2,7 +2,7 @@
 // through the kept C++ host API: load a .glb / .obj, path-trace `frames` frames on an MI355X, write the image as a PPM.
 //
 //   nexus_render [--denoise] [--adaptive THRESHOLD [--max-frames N]] [--light-sampling uniform|power] [--transparent-shadows] [--env-float FILE.hdr] [--env-sampling]
-//                [--no-detail-maps] [--fog SIGMA [--fog-albedo R G B] [--fog-g G] [--fog-box X0 Y0 Z0 X1 Y1 Z1] [--fog-grid FILE.npy]]
+//                [--no-detail-maps] [--metal-rough] [--fog SIGMA [--fog-albedo R G B] [--fog-g G] [--fog-box X0 Y0 Z0 X1 Y1 Z1] [--fog-grid FILE.npy]]
 //                [--point-light X Y Z INTENSITY] [--sun DX DY DZ IRRADIANCE] <dir/> <file.glb|file.obj> <out.ppm> [width height frames pathLength]
 //                [eyeX eyeY eyeZ fwdX fwdY fwdZ hfovDeg]
 // --denoise: the feature buffers are accumulated with the colour and the image written is the a-trous filtered one (nxhip_denoise)
@@ -19,6 +19,8 @@
 // A .glb's KHR_lights_punctual lights (point, spot, directional) are rendered as the file places them, without a flag.
 // A .glb's normalTexture and metallicRoughnessTexture (its G channel: roughness) are used as the file's materials name them, without a flag.
 // --no-detail-maps: drop them (AssetManager::ClearMaterialDetails), for an A/B against the flat, uniformly glossy surfaces.
+// --metal-rough: a .glb's materials are read as glTF's own metallic-roughness model (Scene::SetMetalRoughMaterials: metallicFactor, the raw
+//   roughnessFactor, the B channel of the metallic-roughness texture) instead of the reference's plastic.
 // --point-light X Y Z INTENSITY: one more white point light at (X, Y, Z), radiant intensity INTENSITY per steradian (Scene::AddAnalyticLight).
 // --sun DX DY DZ IRRADIANCE: a white sun whose light travels along (DX, DY, DZ), irradiance IRRADIANCE on a surface facing it.
 // --fog SIGMA: a homogeneous medium of extinction SIGMA per world unit (Scene::SetMedium, nxhip_set_medium): light scatters in the air, so
@@ -50,6 +52,7 @@ int main(int argc, char** argv)
     std::string envFloat;
     bool envSampling = false;
     bool detailMaps = true;
+    bool metalRough = false;
     std::vector<nexus::AnalyticLight> extraLights;
     bool fog = false, fogBox = false;
     nexus::Medium medium;
@@ -86,6 +89,9 @@ int main(int argc, char** argv)
             used = 1;
         } else if (opt == "--no-detail-maps") {
             detailMaps = false;
+            used = 1;
+        } else if (opt == "--metal-rough") {
+            metalRough = true;
             used = 1;
         } else if (opt == "--fog" && argc > 2) {
             fog = true;
@@ -153,6 +159,7 @@ int main(int argc, char** argv)
             pathTracer.SetDeviceBlasBuild(scene, true);
             scene.SetDeviceTlasBuild(true);
         }
+        scene.SetMetalRoughMaterials(metalRough);
         scene.CreateMeshInstanceFromFile(dir, file);  // (a .glb's KHR_lights_punctual lights come with it)
         if (!detailMaps) scene.GetAssetManager().ClearMaterialDetails();  // (the file's normal and roughness maps: loaded, not used)
         for (const nexus::AnalyticLight& l : extraLights) scene.AddAnalyticLight(l);

@@ -15,7 +15,8 @@
 namespace nexus {
 
 struct Material : nx_material {
-    enum struct Type : int8_t { DIFFUSE = NX_MAT_DIFFUSE, DIELECTRIC = NX_MAT_DIELECTRIC, PLASTIC = NX_MAT_PLASTIC, CONDUCTOR = NX_MAT_CONDUCTOR };
+    enum struct Type : int8_t { DIFFUSE = NX_MAT_DIFFUSE, DIELECTRIC = NX_MAT_DIELECTRIC, PLASTIC = NX_MAT_PLASTIC, CONDUCTOR = NX_MAT_CONDUCTOR,
+                                 METALROUGH = NX_MAT_METALROUGH };  // (an extension: glTF's metallic-roughness model, nexus_hip.h)
     Material()
     {
         std::memset(static_cast<nx_material*>(this), 0, sizeof(nx_material));

@@ -41,13 +41,21 @@ struct LoadedScene {
     std::vector<std::string> warnings;  // images that could not be decoded (the reference prints and carries on, IMGLoader.cpp:24-25)
 };
 
+// How a file's materials are read.  metalRough (off by default: glTF's default metallicFactor is 1, so it would turn every existing
+// file into metal): a .glb material without transmission becomes an NX_MAT_METALROUGH — albedo = baseColorFactor.rgb, roughness =
+// roughnessFactor as it stands (default 1), metallic = metallicFactor (default 1), ior from KHR_materials_ior (default 1.5) —
+// instead of the reference's PLASTIC; a material with transmissionFactor > 0 stays the DIELECTRIC it is, and .obj files do not change.
+struct LoadOptions {
+    bool metalRough = false;
+};
+
 class OBJLoader {
 public:
     // Parse a file into meshes / materials / instances; throws std::runtime_error with a message on malformed input.
-    static LoadedScene Parse(const std::string& file);
+    static LoadedScene Parse(const std::string& file, const LoadOptions& options = LoadOptions());
     // Scene::CreateMeshInstanceFromFile's worker (Scene.cpp:83-91): adds the file's materials, builds one BVH8 per mesh,
     // registers the meshes and creates one mesh instance per loaded instance.
-    static void LoadOBJ(const std::string& path, const std::string& filename, Scene* scene, AssetManager* assetManager);
+    static void LoadOBJ(const std::string& path, const std::string& filename, Scene* scene, AssetManager* assetManager, const LoadOptions& options = LoadOptions());
 };
 
 }  // namespace nexus

@@ -24,6 +24,10 @@ public:
     // ---- building the scene ------------------------------------------------------------------------------------
     // Load a .glb / .obj through OBJLoader::LoadOBJ: one BVH8 per mesh, one instance per (node, primitive) — Scene.cpp:83-91
     void CreateMeshInstanceFromFile(const std::string& path, const std::string& fileName);
+    // Extension, off by default: the files loaded from here on read a .glb's materials as glTF's own metallic-roughness model
+    // (Material::Type::METALROUGH; OBJLoader.h LoadOptions::metalRough) instead of the reference's PLASTIC
+    void SetMetalRoughMaterials(bool on) { m_MetalRoughMaterials = on; }
+    bool GetMetalRoughMaterials() const { return m_MetalRoughMaterials; }
     // Place mesh `meshId` (AssetManager::AddMesh) with the mesh's own transform and material; a light is derived if its
     // material emits.  The returned reference is valid until the next instance is created.
     MeshInstance& CreateMeshInstance(uint32_t meshId);
@@ -114,6 +118,7 @@ private:
     std::vector<AnalyticLight> m_AnalyticLights;
     Medium m_Medium;
     bool m_HasMedium = false;
+    bool m_MetalRoughMaterials = false;
     DensityGrid m_MediumDensity;
     std::shared_ptr<TLAS> m_Tlas;
 

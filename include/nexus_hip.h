@@ -147,7 +147,52 @@ int nxhip_update_blas(nxhip_ctx *ctx, int32_t blasId, const nx_triangle *tris, u
 int nxhip_update_blas_device(nxhip_ctx *ctx, int32_t blasId, const void *trisDevice, uint32_t triCount);
 /* Read the device's TLAS nodes / instance table back (tests; either destination may be NULL). */
 int nxhip_read_tlas(nxhip_ctx *ctx, nx_bvh8_node *nodes, uint32_t nodeCapacity, nx_bvh_instance *instances, uint32_t instanceCapacity);
-/* AssetManager device materials — Assets/AssetManager.cpp:57-62,106-116 */
+/* AssetManager device materials — Assets/AssetManager.cpp:57-62,106-116
+ *
+ * Extension — NX_MAT_METALROUGH (type 4): glTF's metallic-roughness material as ONE BSDF.  The wavefront sorts hits by material type
+ * before any texture lookup, so per-texel metalness needs a single type whose BSDF blends inside.  View `metalrough` of the union:
+ * albedo[3], roughness, ior (plastic's fields) and metallic at byte 20.
+ *
+ * THE SHADING RULE.  Inputs at the hit, in this order:
+ *   c   albedo, or the diffuse map's texel if the material names one (the existing rule, the stochastic alpha pass-through in front of it);
+ *   r   roughness x the G channel of the detail table's roughnessMapId lookup (the existing rule: nxhip_set_material_detail);
+ *   m   metallic x the B channel of THAT lookup (this type only: one lookup for both channels); then m = clamp(m, 0, 1), NaN -> 0;
+ *   a   = clamp(r^2, 1e-3, 1) — glTF's mapping, not the reference's rough_alpha, which stays with the four reference types.
+ * Local frame, z the shading normal: ci = |wi.z|, co = |wo.z|, h = normalize(wi + wo) (on wi's side), u = wi.h.
+ *   f0d   = ((ior - 1) / (ior + 1))^2                     F0 = f0d + (c - f0d) m  (= lerp(f0d, c, m), per channel)
+ *   F     = F0 + (1 - F0)(1 - u)^5                        Fd(x) = f0d + (1 - f0d)(1 - x)^5
+ *   D     = a^2 / (pi (a^2 h.z^2 + h.x^2 + h.y^2)^2)      (this denominator, not h.z^2 (a^2 - 1) + 1, which cancels in binary32 near the clamp)
+ *   L(x)  = sqrt(a^2 + (1 - a^2) x^2)                     G1(x) = 2x / (x + L(x))
+ *   G2    = 2 ci co / (co L(ci) + ci L(co))               (height-correlated: the form glTF's Appendix B names)
+ *   f cos = [ F D G2 / (4 ci co) + (1 - m) c / pi (1 - Fd(ci)) (1 - Fd(co)) ] co            — what eval returns as the throughput
+ * The diffuse weight is the PRODUCT (1 - Fd(ci))(1 - Fd(co)), a departure from the appendix's 1 - Fd(u): the appendix (non-normative)
+ * reflects up to 1.39 of the incoming energy at grazing incidence (binary64 quadrature, white base colour), the product stays <= 1.000
+ * over r in {0.05 .. 1}, m in {0, 0.5, 1}, ci in [0.05, 0.95], and is reciprocal.
+ *   lobe  ws = mean(F0 + (1 - F0)(1 - ci)^5),  wd = mean((1 - m) c) (1 - Fd(ci)),  ps = ws / (ws + wd);  ws + wd == 0: invalid sample
+ *   pdf   = ps G1(ci) D / (4 ci) + (1 - ps) co / pi
+ * Validity: wi.z wo.z > 0, then the project's pdf_valid(pdf) (finite and > 1e-4).
+ * sample draws exactly THREE numbers on both branches: u0 — the specular lobe when u0 < ps — then (u1, u2):
+ *   specular  visible normals of GGX (Heitz 2018), V = wi on the upper side:  Vh = normalize(a V.x, a V.y, V.z);
+ *             T1 = (-Vh.y, Vh.x, 0) / |.| ((1, 0, 0) when Vh.x^2 + Vh.y^2 == 0), T2 = Vh x T1;  rr = sqrt(u1), phi = 2 pi u2,
+ *             t1 = rr cos phi, t2 = rr sin phi;  s = (1 + Vh.z) / 2,  t2 := (1 - s) sqrt(1 - t1^2) + s t2;
+ *             Nh = t1 T1 + t2 T2 + sqrt(max(0, 1 - t1^2 - t2^2)) Vh;  h = normalize(a Nh.x, a Nh.y, max(0, Nh.z)), on wi's side;
+ *             wo = reflect(-wi, h), rejected when wo.z wi.z <= 0;
+ *   diffuse   the existing cosine_hemisphere (u1, u2), on wi's side.
+ * It returns the mixture estimator: pdf is the full mixture pdf above and the throughput is f cos / pdf with the full f, so
+ * sample.throughput x sample.pdf == eval.throughput at the sampled direction (the weight stays below about 1.7).  Unlike the
+ * reference's plastic, eval and sample are the same model.
+ * The back-face flip applies as for every type but the DIELECTRIC; light sampling, MIS, transparent shadows, analytic lights, the power
+ * light table, fog and normal maps work through eval / sample as for the other types; the AOV albedo of the type is c.
+ * Out of scope: multiple-scattering energy compensation (a white metal at r = 1 reflects 0.33 at ci = 0.9); clearcoat, sheen and specular
+ * extensions; transmission inside this type; a CPU-oracle restatement.
+ * Both pipelines shade the type.  SCAN: one more case of the material launch.  CLASSIC (NX_COMPACT_ORDERED): the reference's logic kernel
+ * and its four queues stay as they are; a kernel behind it queues the surviving hits of the type into a fifth queue (the same roulette
+ * number, so the same decision), and the type's material kernel runs after the reference's four.  Under pixel-keyed numbers both give
+ * the same frames bit for bit.  A SCAN pass with the type hands no closest-hit ray to the thin kernel (its replay names the reference
+ * types' codes only); its any-hit rays are handed over as ever.
+ * The kernels that know the type are compile-time instances launched only while some material has it (bit 15 of
+ * nxhip_debug_pass_flavor's word); they are DETAIL instances too and imply the general material launch.  A context without such a
+ * material launches what it always did and has the same flavor word. */
 int nxhip_set_materials(nxhip_ctx *ctx, const nx_material *materials, uint32_t count);
 /* Scene::m_DeviceLights — Scene/Scene.cpp:142-176.  Only NX_LIGHT_MESH entries are sampled: an NX_LIGHT_POINT or NX_LIGHT_AREA entry yields
  * no light sample (the 12-byte record has no position).  Lights that are not geometry go through nxhip_set_analytic_lights below. */
@@ -231,8 +276,8 @@ int nxhip_clear_textures(nxhip_ctx *ctx);
  *   fallback   ns := N when: !(|det| > 0); the projected tangent is not finite or has length 0; ns is not finite or has length 0; or, with
  *              v = -rayDirection, (ns . v)(N . v) <= 0 — the view is below the mapped horizon.  One rule for all four material types.
  * Tangents are per triangle, from positions and UVs: the 96-byte triangle has no room for glTF's TANGENT attribute.
- * Out of scope: vertex TANGENT attributes; per-texel metalness (the material type picks the queue before any lookup — metallicFactor and
- * the B channel stay unused); the AOV normal and the denoiser's normal term keep the interpolated normal; .mtl bump maps; mip-mapping;
+ * Out of scope: vertex TANGENT attributes; per-texel metalness for the four reference types (the material type picks the queue before any
+ * lookup; NX_MAT_METALROUGH reads metallic and the B channel: nxhip_set_materials); the AOV normal and the denoiser's normal term keep the interpolated normal; .mtl bump maps; mip-mapping;
  * texCoord sets other than 0 and KHR_texture_transform (the loaders warn).  The closest-hit and any-hit kernels and the feature buffers do
  * not change.
  * The kernels that know these maps are compile-time instances launched only while some material names one (bit 12 of
@@ -731,6 +776,9 @@ typedef struct nxhip_queue_sizes {
     int32_t conductorSize[NX_PATH_MAX_LENGTH];
 } nxhip_queue_sizes;
 int nxhip_read_queue_sizes(nxhip_ctx *ctx, nxhip_queue_sizes *out);
+/* One material type's row of the same table, for ANY type (NX_MAT_METALROUGH has no field above: the struct keeps the reference's
+ * layout): out[b] = items the material step shaded as `type` at bounce slot b, NX_PATH_MAX_LENGTH ints. */
+int nxhip_read_material_queue_sizes(nxhip_ctx *ctx, int type, int32_t *out);
 
 /* PathTracer::SetPixelQuery / GetSelectedInstance — PathTracer.cpp:310-317, PathTracer.h:25 */
 int nxhip_set_pixel_query(nxhip_ctx *ctx, uint32_t x, uint32_t y);
@@ -783,6 +831,15 @@ int nxhip_tex2d_batch(nxhip_ctx *ctx, int kind, int textureId, const float *uv, 
  * a render would refuse. */
 int nxhip_shading_frame_batch(nxhip_ctx *ctx, uint32_t instanceIdx, const uint32_t *triIdx, const float *hitUv, const float *rayDir, uint32_t count,
                               float *normalOut, float *roughnessOut, uint32_t *fellBack);
+
+/* The inputs of an NX_MAT_METALROUGH material at a hit — a test hook (a `make release` library refuses it).  An exception to the hooks'
+ * habit of calling ONE device function the kernels call: shade_path has no such function to call without changing the text of the kernels
+ * every context launches, so the hook's kernel restates its sequence — bary2, the diffuse map's tex2d, detail_shading_frame (the G and B
+ * channels of one lookup), the clamp of m that the BSDF applies (metal_clamp01) — from the same device functions, in the same order: for every k < count, the hit on triangle triIdx[k] of instance `instanceIdx` at barycentrics
+ * hitUv[2k..]: out[5k..] = c.r, c.g, c.b, r, m as the rule of nxhip_set_materials states them (m after the clamp).  NXHIP_ERR_INVALID: a
+ * NULL array, no such instance, an instance whose material is of another type, a triangle index out of range, a scene a render would
+ * refuse. */
+int nxhip_material_inputs_batch(nxhip_ctx *ctx, uint32_t instanceIdx, const uint32_t *triIdx, const float *hitUv, uint32_t count, float *out);
 
 /* Test hooks of the light table (NXHIP_LIGHTS_POWER only, else NXHIP_ERR_INVALID; both bring the table up to date first).
  * read: cdf / entryLight (either may be NULL) hold `capacity` entries, lightBase (may be NULL) lightCount + 1 words; *entries = N.

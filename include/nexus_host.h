@@ -66,6 +66,11 @@ typedef struct nx_loaded_instance {
     float position[3], rotation[3] /* Euler XYZ, degrees */, scale[3];
 } nx_loaded_instance;
 int nxh_load_scene_file(const char *file, nxh_loaded_scene **out);
+/* ... with options (flags 0: exactly nxh_load_scene_file).  NXH_LOAD_METAL_ROUGH: a .glb material without transmission is read as glTF's own
+ * metallic-roughness model — an NX_MAT_METALROUGH with albedo = baseColorFactor.rgb, roughness = roughnessFactor, metallic =
+ * metallicFactor (defaults 1, 1), ior from KHR_materials_ior (default 1.5) — instead of the reference's PLASTIC; everything else stays. */
+#define NXH_LOAD_METAL_ROUGH 1u
+int nxh_load_scene_file_ex(const char *file, uint32_t flags, nxh_loaded_scene **out);
 void nxh_loaded_scene_free(nxh_loaded_scene *s);
 uint32_t nxh_loaded_mesh_count(const nxh_loaded_scene *s);
 uint32_t nxh_loaded_mesh_triangle_count(const nxh_loaded_scene *s, uint32_t mesh);
@@ -134,6 +139,8 @@ int nxs_scene_set_tlas_refit(nxs_scene *s, int enable);
 int nxs_scene_set_device_tlas(nxs_scene *s, int enable);
 /* Scene::CreateMeshInstanceFromFile — Scene.cpp:83-91: adds the file's materials, meshes (one BVH8 each) and instances. */
 int nxs_scene_load_file(nxs_scene *s, const char *path, const char *fileName);
+/* Extension, off by default: files loaded from here on read their materials as NXH_LOAD_METAL_ROUGH does (Scene::SetMetalRoughMaterials). */
+int nxs_scene_set_metal_rough(nxs_scene *s, int on);
 int nxs_scene_set_camera(nxs_scene *s, const float pos[3], const float forward[3], float horizontalFovDeg, float focusDist,
                          float defocusAngleDeg);
 int nxs_scene_set_render_settings(nxs_scene *s, const nx_render_settings *settings);

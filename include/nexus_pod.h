@@ -19,6 +19,7 @@
 #ifndef NEXUS_POD_H
 #define NEXUS_POD_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -62,7 +63,9 @@ typedef struct nx_bvh_instance {
 } nx_bvh_instance;
 NX_STATIC_ASSERT(sizeof(nx_bvh_instance) == 160, "nx_bvh_instance must be 160 bytes");
 
-enum { NX_MAT_DIFFUSE = 0, NX_MAT_DIELECTRIC = 1, NX_MAT_PLASTIC = 2, NX_MAT_CONDUCTOR = 3 };
+/* NX_MAT_METALROUGH: an extension — glTF's metallic-roughness model in one BSDF (the rule is stated in full in include/nexus_hip.h,
+ * nxhip_set_materials).  The four types in front of it are the reference's. */
+enum { NX_MAT_DIFFUSE = 0, NX_MAT_DIELECTRIC = 1, NX_MAT_PLASTIC = 2, NX_MAT_CONDUCTOR = 3, NX_MAT_METALROUGH = 4 };
 
 typedef struct nx_material {
     union {
@@ -70,6 +73,7 @@ typedef struct nx_material {
         struct { float albedo[3]; float roughness; float ior; } dielectric;
         struct { float albedo[3]; float roughness; float ior; } plastic;
         struct { float ior[3]; float k[3]; float roughness; } conductor;
+        struct { float albedo[3]; float roughness; float ior; float metallic; } metalrough; /* = plastic's fields + metallic at byte 20 */
     };
     float emissive[3];
     float intensity;
@@ -79,6 +83,7 @@ typedef struct nx_material {
     int8_t type;
 } nx_material;
 NX_STATIC_ASSERT(sizeof(nx_material) == 60, "nx_material must be 60 bytes");
+NX_STATIC_ASSERT(offsetof(nx_material, metalrough.metallic) == 20 && offsetof(nx_material, emissive) == 28, "the metalrough view fits the 28-byte union");
 
 enum { NX_LIGHT_POINT = 0, NX_LIGHT_AREA = 1, NX_LIGHT_MESH = 2 };
 

@@ -41,6 +41,7 @@ HIP_SYMBOLS = [
     "nxhip_set_medium", "nxhip_medium_segment_batch", "nxhip_medium_phase_batch",
     "nxhip_set_medium_density", "nxhip_read_medium_majorants", "nxhip_medium_density_batch", "nxhip_medium_track_batch",
     "nxhip_set_queue_budget", "nxhip_get_queue_budget", "nxhip_queue_budget_from_text", "nxhip_debug_last_graph",
+    "nxhip_read_material_queue_sizes", "nxhip_material_inputs_batch",
 ]
 HOST_SYMBOLS = [
     "nxh_bvh8_build", "nxh_tlas_build", "nxh_tlas_refit", "nxh_bvh8_refit", "nxh_bvh8_node_count", "nxh_bvh8_prim_count", "nxh_bvh8_nodes",
@@ -66,6 +67,7 @@ HOST_SYMBOLS = [
     "nxs_scene_set_material_detail", "nxs_scene_clear_material_details", "nxs_scene_material_detail_count", "nxs_scene_material_details",
     "nxs_scene_set_medium", "nxs_scene_clear_medium", "nxs_scene_medium",
     "nxs_scene_set_medium_density", "nxs_scene_clear_medium_density", "nxs_scene_medium_density", "nxh_decode_npy_grid",
+    "nxh_load_scene_file_ex", "nxs_scene_set_metal_rough",
 ]
 
 
@@ -190,6 +192,8 @@ def lib():
     L.nxhip_read_full_accumulation.argtypes = [vp, vp]
     L.nxhip_read_full_rgba8.argtypes = [vp, vp]
     L.nxhip_read_queue_sizes.argtypes = [vp, C.POINTER(QueueSizes)]
+    L.nxhip_read_material_queue_sizes.argtypes = [vp, C.c_int, vp]
+    L.nxhip_material_inputs_batch.argtypes = [vp, u32, vp, vp, u32, vp]
     L.nxhip_set_pixel_query.argtypes = [vp, u32, u32]
     L.nxhip_get_selected_instance.argtypes = [vp, C.POINTER(i32)]
     L.nxhip_trace_batch.argtypes = [vp, vp, u32, vp]
@@ -253,6 +257,7 @@ def lib():
     L.nxh_instance_init.argtypes = [vp, u32, i32, vp, vp]
     L.nxh_camera_init.argtypes = [vp, vp, vp, f32, u32, u32, f32, f32]
     L.nxh_load_scene_file.argtypes = [C.c_char_p, C.POINTER(vp)]
+    L.nxh_load_scene_file_ex.argtypes = [C.c_char_p, u32, C.POINTER(vp)]
     L.nxh_loaded_scene_free.argtypes = [vp]
     L.nxh_loaded_scene_free.restype = None
     for f in ("nxh_loaded_mesh_count", "nxh_loaded_material_count", "nxh_loaded_instance_count"):
@@ -264,6 +269,7 @@ def lib():
     L.nxh_loaded_materials.argtypes = [vp, vp]
     L.nxh_loaded_instances.argtypes = [vp, vp]
     L.nxs_scene_load_file.argtypes = [vp, C.c_char_p, C.c_char_p]
+    L.nxs_scene_set_metal_rough.argtypes = [vp, C.c_int]
     L.nxs_scene_set_instance_transform.argtypes = [vp, u32, vp, vp, vp]
     L.nxs_scene_set_tlas_refit.argtypes = [vp, C.c_int]
     L.nxs_scene_update_mesh.argtypes = [vp, u32, vp, u32]
@@ -420,11 +426,19 @@ def bvh8_refit(nodes, tri_idx, tris):
     return nodes
 
 
-def load_scene_file(path):
-    """nexus::OBJLoader::Parse through the C-ABI: (meshes [TRI_DT arrays], materials MAT_DT array, instances LOADED_INST_DT array)."""
+LOAD_METAL_ROUGH = 1  # nxh_load_scene_file_ex: NXH_LOAD_METAL_ROUGH
+
+
+def load_scene_file(path, metal_rough=False):
+    """nexus::OBJLoader::Parse through the C-ABI: (meshes [TRI_DT arrays], materials MAT_DT array, instances LOADED_INST_DT array).
+    metal_rough: LoadOptions::metalRough — a .glb's materials as MAT_METALROUGH (off: the reference's PLASTIC)"""
     L = lib()
     h = C.c_void_p()
-    if L.nxh_load_scene_file(str(path).encode(), C.byref(h)) != 0:
+    if metal_rough:
+        rc = L.nxh_load_scene_file_ex(str(path).encode(), LOAD_METAL_ROUGH, C.byref(h))
+    else:
+        rc = L.nxh_load_scene_file(str(path).encode(), C.byref(h))
+    if rc != 0:
         raise NexusError("nxh_load_scene_file: " + L.nxs_last_error().decode())
     try:
         meshes = []
@@ -584,6 +598,7 @@ FLAVOR_DETAIL = 4096  # ... and the DETAIL instances of the material kernels: so
 TEXTURE_KINDS = {"diffuse": 0, "emissive": 1, "hdr": 2, "normal": 3, "roughness": 4}  # nxhip_upload_texture / nxhip_tex2d_batch
 FLAVOR_MEDIUM = 8192  # ... and the medium's two launches per bounce: a medium with sigmaT > 0 is set (set_medium)
 FLAVOR_MEDIUM_GRID = 16384  # ... and their GRID instances: a medium with sigmaT > 0 and a density grid are set (set_medium_density)
+FLAVOR_METAL = 32768  # ... and the METAL instances of the material launch and the tail kernel: some material is a MAT_METALROUGH (set_materials)
 FLAVOR_TRANSMIT = 2048  # ... and the any-hit TRANSMIT instance: SHADOWS_TRANSMIT over a table with a see-through material (set_shadow_transmittance)
 
 
@@ -755,6 +770,16 @@ class Context:
         check(self.L.nxhip_shading_frame_batch(self.h, int(instance), _ptr(t), _ptr(uv), _ptr(d), len(t), _ptr(normal), _ptr(roughness), _ptr(fell)),
               "nxhip_shading_frame_batch")
         return normal, roughness, fell != 0
+
+    def material_inputs_batch(self, instance, tri_idx, hit_uv):
+        """base colour, roughness and metalness the BSDF of an NX_MAT_METALROUGH material receives for hits on triangles tri_idx[k] of
+        `instance` at barycentrics hit_uv[k] — a test hook: (c float32[n, 3], r float32[n], m float32[n])"""
+        t = np.ascontiguousarray(tri_idx, dtype=np.uint32).reshape(-1)
+        uv = np.ascontiguousarray(hit_uv, dtype=np.float32).reshape(-1, 2)
+        assert len(t) == len(uv)
+        out = np.zeros((len(t), 5), dtype=np.float32)
+        check(self.L.nxhip_material_inputs_batch(self.h, int(instance), _ptr(t), _ptr(uv), len(t), _ptr(out)), "nxhip_material_inputs_batch")
+        return out[:, :3].copy(), out[:, 3].copy(), out[:, 4].copy()
 
     def analytic_light_sample_batch(self, light_index, origins, r):
         """the light sample's draw for analytic light `light_index` from every origin[k] with the random pair r[k] in [0, 1)^2 — a test hook:
@@ -1353,6 +1378,12 @@ class Context:
         check(self.L.nxhip_read_queue_sizes(self.h, C.byref(q)), "nxhip_read_queue_sizes")
         return {n: np.array(getattr(q, n)[:], dtype=np.int32) for n, _ in QueueSizes._fields_}
 
+    def read_material_queue_sizes(self, material_type):
+        """items the material step shaded as `material_type` (pod.MAT_*, MAT_METALROUGH included) per bounce slot: int32[PATH_MAX_LENGTH]"""
+        out = np.zeros(pod.PATH_MAX_LENGTH, dtype=np.int32)
+        check(self.L.nxhip_read_material_queue_sizes(self.h, int(material_type), _ptr(out)), "nxhip_read_material_queue_sizes")
+        return out
+
     def set_pixel_query(self, x, y):
         check(self.L.nxhip_set_pixel_query(self.h, x, y), "nxhip_set_pixel_query")
 
@@ -1571,6 +1602,10 @@ class Scene:
     def load_file(self, path, file_name):
         """Scene::CreateMeshInstanceFromFile: materials, meshes (one BVH8 each) and instances of a .glb / .obj"""
         _scheck(self.L.nxs_scene_load_file(self.h, str(path).encode(), str(file_name).encode()), "nxs_scene_load_file")
+
+    def set_metal_rough(self, on=True):
+        """Scene::SetMetalRoughMaterials: the files loaded from here on read a .glb's materials as MAT_METALROUGH (off by default)"""
+        _scheck(self.L.nxs_scene_set_metal_rough(self.h, 1 if on else 0), "nxs_scene_set_metal_rough")
 
     def create_instance(self, mesh_id, material_id, position=(0, 0, 0), rotation_deg=(0, 0, 0), scale=(1, 1, 1)):
         p, r, s = (np.asarray(x, np.float32) for x in (position, rotation_deg, scale))

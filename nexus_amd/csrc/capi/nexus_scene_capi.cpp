@@ -133,6 +133,18 @@ int nxh_load_scene_file(const char* file, nxh_loaded_scene** out)
         *out = p.release();
     });
 }
+int nxh_load_scene_file_ex(const char* file, uint32_t flags, nxh_loaded_scene** out)
+{
+    return guarded([&] {
+        if (!file || !out) throw std::runtime_error("nxh_load_scene_file_ex: null argument");
+        if (flags & ~(uint32_t)NXH_LOAD_METAL_ROUGH) throw std::runtime_error("nxh_load_scene_file_ex: unknown flag");
+        std::unique_ptr<nxh_loaded_scene> p(new nxh_loaded_scene);
+        LoadOptions options;
+        options.metalRough = (flags & NXH_LOAD_METAL_ROUGH) != 0;
+        p->ls = OBJLoader::Parse(file, options);
+        *out = p.release();
+    });
+}
 void nxh_loaded_scene_free(nxh_loaded_scene* s) { delete s; }
 uint32_t nxh_loaded_mesh_count(const nxh_loaded_scene* s) { return static_cast<uint32_t>(s->ls.meshes.size()); }
 uint32_t nxh_loaded_mesh_triangle_count(const nxh_loaded_scene* s, uint32_t mesh)
@@ -307,6 +319,11 @@ int nxs_scene_load_file(nxs_scene* s, const char* path, const char* fileName)
         if (!path || !fileName) throw std::runtime_error("nxs_scene_load_file: null argument");
         s->scene.CreateMeshInstanceFromFile(path, fileName);
     });
+}
+
+int nxs_scene_set_metal_rough(nxs_scene* s, int on)
+{
+    return guarded([&] { s->scene.SetMetalRoughMaterials(on != 0); });
 }
 
 int nxs_scene_set_camera(nxs_scene* s, const float pos[3], const float forward[3], float hfov, float focusDist, float defocusAngle)

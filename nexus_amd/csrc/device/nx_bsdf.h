@@ -83,6 +83,7 @@ struct MatParams {
     float roughness; // dielectric / plastic / conductor
     float ior;       // dielectric / plastic
     f3 cIor, cK;     // conductor
+    float metallic;  // metalrough (the same four bytes as the conductor view's k[2]: only Bsdf<NX_MAT_METALROUGH> reads it)
 };
 
 template <int TYPE> struct Bsdf;
@@ -230,6 +231,103 @@ template <> struct Bsdf<NX_MAT_CONDUCTOR> {
         thr = F * weight;
         pdf = walter_reflection_pdf(alpha, m.z, fabsf(wiDotM));
         return true;
+    }
+};
+
+// glTF's metallic-roughness model (an extension: the reference has no such BSDF).  The rule is stated in full in include/nexus_hip.h
+// (nxhip_set_materials, NX_MAT_METALROUGH); this is its one device text.  GGX with the height-correlated Smith term, Schlick's
+// Fresnel from F0 = lerp(f0d, c, m), a Lambert base weighted by the product (1 - Fd(ci))(1 - Fd(co)), visible-normal sampling
+// (Heitz 2018) mixed with the cosine lobe.  eval and sample are the same model: sample.thr x sample.pdf == eval.thr.
+NXD float metal_clamp01(float m) { return m > 0.0f ? fminf(m, 1.0f) : 0.0f; }  // (NaN -> 0)
+NXD float pow5f(float x) { const float x2 = x * x; return (x2 * x2) * x; }
+struct MetalRoughTerms {
+    float alpha2, f0d, m, ps;
+    f3 F0, base;  // base = (1 - m) c
+    bool ok;      // ws + wd > 0
+};
+NXD float mr_lambda(float alpha2, float x) { return sqrtf(alpha2 + (1.0f - alpha2) * (x * x)); }
+NXD float mr_fd(float f0d, float x) { return f0d + (1.0f - f0d) * pow5f(1.0f - x); }
+NXD MetalRoughTerms mr_terms(const MatParams& mat, float ci)
+{
+    MetalRoughTerms t;
+    const float alpha = clampf(mat.roughness * mat.roughness, 1.0e-3f, 1.0f);
+    t.alpha2 = alpha * alpha;
+    const float q = (mat.ior - 1.0f) / (mat.ior + 1.0f);
+    t.f0d = q * q;
+    t.m = metal_clamp01(mat.metallic);
+    t.F0 = mk3(t.f0d) + (mat.albedo - mk3(t.f0d)) * t.m;
+    t.base = mat.albedo * (1.0f - t.m);
+    const float w5 = pow5f(1.0f - ci);
+    const f3 Fi = t.F0 + (mk3(1.0f) - t.F0) * w5;
+    const float ws = ((Fi.x + Fi.y) + Fi.z) * (1.0f / 3.0f);
+    const float wd = (((t.base.x + t.base.y) + t.base.z) * (1.0f / 3.0f)) * (1.0f - mr_fd(t.f0d, ci));
+    const float sum = ws + wd;
+    t.ok = sum > 0.0f;
+    t.ps = t.ok ? ws / sum : 0.0f;
+    return t;
+}
+// f.cos and the mixture pdf for a pair on one side of the surface (the caller has checked that)
+NXD void mr_eval(const MetalRoughTerms& t, f3 wi, f3 wo, f3& thr, float& pdf)
+{
+    const float ci = fabsf(wi.z), co = fabsf(wo.z);
+    const f3 h = normalize3(wi + wo);
+    const float u = dot3(wi, h);
+    const f3 F = t.F0 + (mk3(1.0f) - t.F0) * pow5f(1.0f - u);
+    const float den = t.alpha2 * (h.z * h.z) + (h.x * h.x + h.y * h.y);
+    const float D = t.alpha2 / ((3.14159265f * den) * den);
+    const float li = mr_lambda(t.alpha2, ci), lo = mr_lambda(t.alpha2, co);
+    const float G2 = ((2.0f * ci) * co) / (co * li + ci * lo);
+    const float G1 = (2.0f * ci) / (ci + li);
+    const float kd = (1.0f - mr_fd(t.f0d, ci)) * (1.0f - mr_fd(t.f0d, co));
+    const f3 f = F * ((D * G2) / ((4.0f * ci) * co)) + t.base * (kInvPi * kd);
+    thr = f * co;
+    pdf = t.ps * ((G1 * D) / (4.0f * ci)) + (1.0f - t.ps) * (co * kInvPi);
+}
+
+template <> struct Bsdf<NX_MAT_METALROUGH> {
+    static NXD bool eval(const MatParams& mat, f3 wi, f3 wo, f3& thr, float& pdf)
+    {
+        if (!(wi.z * wo.z > 0.0f)) return false;
+        const MetalRoughTerms t = mr_terms(mat, fabsf(wi.z));
+        if (!t.ok) return false;
+        mr_eval(t, wi, wo, thr, pdf);
+        return pdf_valid(pdf);
+    }
+    // exactly three numbers on both branches: u0 picks the lobe, (u1, u2) the direction
+    static NXD bool sample(const MatParams& mat, f3 wi, uint32_t& rng, f3& wo, f3& thr, float& pdf)
+    {
+        const MetalRoughTerms t = mr_terms(mat, fabsf(wi.z));
+        const float u0 = rng_next(rng);
+        const float side = sgnE(wi.z);
+        if (u0 < t.ps) {
+            const float u1 = rng_next(rng), u2 = rng_next(rng);
+            // Heitz 2018: stretch the view, build the basis, sample the disc, warp t2, back to the ellipsoid, unstretch
+            const float alpha = sqrtf(t.alpha2);
+            const f3 V = wi * side;
+            const f3 Vh = normalize3(mk3(alpha * V.x, alpha * V.y, V.z));
+            const float lensq = Vh.x * Vh.x + Vh.y * Vh.y;
+            const f3 T1 = lensq > 0.0f ? mk3(-Vh.y, Vh.x, 0.0f) * (1.0f / sqrtf(lensq)) : mk3(1.0f, 0.0f, 0.0f);
+            const f3 T2 = cross3(Vh, T1);
+            const float r = sqrtf(u1);
+            const double phi = 2 * kPiD * u2;
+            double sinPhi, cosPhi;
+            nxf_sincos(phi, &sinPhi, &cosPhi);
+            const float t1 = (float)(cosPhi * r);
+            float t2 = (float)(sinPhi * r);
+            const float s = 0.5f * (1.0f + Vh.z);
+            t2 = (1.0f - s) * sqrtf(fmaxf(0.0f, 1.0f - t1 * t1)) + s * t2;
+            const f3 Nh = (T1 * t1 + T2 * t2) + Vh * sqrtf(fmaxf(0.0f, (1.0f - t1 * t1) - t2 * t2));
+            const f3 h = normalize3(mk3(alpha * Nh.x, alpha * Nh.y, fmaxf(0.0f, Nh.z))) * side;
+            wo = reflect3(-wi, h);
+        } else {
+            wo = cosine_hemisphere(rng);
+            wo.z = wo.z * side;
+        }
+        if (!t.ok || !(wo.z * wi.z > 0.0f)) return false;
+        f3 fcos;
+        mr_eval(t, wi, wo, fcos, pdf);
+        thr = fcos / pdf;
+        return pdf_valid(pdf);
     }
 };
 

@@ -100,6 +100,7 @@ struct PassSlot {
     bool queuesScan = false;         // which pipeline the buffers above were allocated for (scan: no material queues; classic: no second ray set)
     DevBuf shRayO, shRayD, shRadiance;
     DevBuf mqHit[4], mqDirInst[4], mqTp[4];
+    DevBuf mqMetal[3];  // hit, dirInst, tp of the fifth queue (NX_MAT_METALROUGH, classic pipeline): allocated by the first pass that needs it
     DevBuf counters, frame, dState;
     DevBuf scanStatus;        // ordered compaction: tile status words (allocated with the queues)
     DevBuf thinStates;        // 2 x kThinListEntries ThinState: the traversal state of every listed ray
@@ -238,6 +239,7 @@ struct nxhip_ctx : nxd::PassSlot {
     int tailBlocks = 0;
     int tailBlocksPower = 0;  // grid of tail_kernel<true> (NXHIP_LIGHTS_POWER), from that instance's own occupancy
     int tailBlocksAnalytic[2] = {0, 0};  // grids of tail_kernel<POWER, true> (analytic lights: kFlavorAnalytic), [0] uniform, [1] POWER
+    int tailBlocksMetal[2][2] = {{0, 0}, {0, 0}};   // grids of tail_kernel<POWER, ANALYTIC, true, true> (an NX_MAT_METALROUGH material: kFlavorMetal), [power][analytic]
     int tailBlocksDetail[2][2] = {{0, 0}, {0, 0}};  // grids of tail_kernel<POWER, ANALYTIC, true> (detail maps: kFlavorDetail), [power][analytic]
     int tailBounce = -1;  // first bounce of the tail kernel, 0 = off, -1 = automatic (see tail_bounce in nxhip_render.hip)
     bool traceGridForced = false;                            // NX_TRACE_BLOCKS_*: use them as they are

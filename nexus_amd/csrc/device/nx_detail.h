@@ -23,9 +23,18 @@ NXD bool usable_length2(float l2) { return l2 > 0.0f && l2 < __builtin_huge_valf
 // (the caller has them in registers); texUv: the hit's texture coordinates.
 template <int TYPE, class Tri, class Mat>
 NXD f3 detail_shading_frame(const DeviceState* S, const nx_material_detail d, Tri tri, Mat T, const f3 tp0, const f3 tp1, const f3 tp2, const f2 texUv, const f3 rayDirection,
-                            f3& N, f3& gNormal, float& roughness, bool& fellBack)
+                            f3& N, f3& gNormal, float& roughness, bool& fellBack, float* const metallic = nullptr)
 {
-    if (d.roughnessMapId != -1) roughness = roughness * tex2d_linear(S->roughnessMaps[d.roughnessMapId], texUv.x, texUv.y).y;
+    if constexpr (TYPE == NX_MAT_METALROUGH) {
+        // metallic (NX_MAT_METALROUGH only, which always passes it): multiplied by the B channel of the SAME lookup
+        if (d.roughnessMapId != -1) {
+            const float4 mr = tex2d_linear(S->roughnessMaps[d.roughnessMapId], texUv.x, texUv.y);
+            roughness = roughness * mr.y;
+            *metallic = *metallic * mr.z;
+        }
+    } else {
+        if (d.roughnessMapId != -1) roughness = roughness * tex2d_linear(S->roughnessMaps[d.roughnessMapId], texUv.x, texUv.y).y;
+    }
     f3 ns = N;
     fellBack = false;
     if (d.normalMapId != -1) {

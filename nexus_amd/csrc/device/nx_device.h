@@ -150,7 +150,8 @@ constexpr uint32_t kRaySurvives = 2u;     // SCAN pipeline: the Russian-roulette
                                           // and frame, all known when the ray is made, and only counts if the ray hits
 // hitInst word: the instance in the low bits, a code above them.  InstTrav::instIdx carries the instance's material type + 1 there
 // (inst_code_kernel), so the closest-hit kernel has "which material kernel shades this hit" in the register that holds the hit's
-// instance anyway.  0: nothing to shade (Russian roulette ended the path, or no kernel for the type); 1 .. 4: NX_MAT_* + 1; 7: a miss.
+// instance anyway.  0: nothing to shade (Russian roulette ended the path, or no kernel for the type); 1 .. 4: NX_MAT_* + 1 of the reference's
+// four types; 6: NX_MAT_METALROUGH (below); 7: a miss.
 constexpr int kHitCodeShift = 29;
 constexpr uint32_t kHitInstMask = (1u << kHitCodeShift) - 1u;
 constexpr uint32_t kHitCodeMiss = 7u;
@@ -158,6 +159,18 @@ constexpr uint32_t kHitCodeMiss = 7u;
 // closest-hit launch and the material launch): no material type and no miss type looks at the record again
 constexpr uint32_t kHitCodeMedium = 5u;
 constexpr int kScanMiss = 4;  // the misses' place among the types of shade_scan_kernel (typeMask bit, ticket row)
+// NX_MAT_METALROUGH (the fifth material type, an extension): its type + 1 would be 5, the medium's code, so it takes the one free
+// code, 6.  The mapping type -> code for all five types is hit_code_of_type below: inst_code_metal_kernel (nx_refit.hip) writes it into the
+// traversal records of a table with the type, shade_scan_type compares against it.  inst_code_kernel and the thin kernel's one-lane replay
+// (nx_trace.hip) keep the reference types' `type + 1` as they had it — the text of kernels every context launches does not change; a pass
+// with the fifth type therefore runs no closest-hit hand-over to the thin kernel (nxhip_render.hip).  In shade_scan_kernel's typeMask the type's own bit 4 is the misses', so it takes bit 5
+// (kScanMetalBit); its ticket row and its queue-size row are the words appended to RegionCounters (scanTileMetal, materialSizeMetal).
+constexpr uint32_t kHitCodeMetalRough = 6u;
+constexpr int kScanMetalBit = 5;
+inline __host__ __device__ constexpr uint32_t hit_code_of_type(int type)
+{
+    return (type >= NX_MAT_DIFFUSE && type <= NX_MAT_CONDUCTOR) ? (uint32_t)(type + 1) : type == NX_MAT_METALROUGH ? kHitCodeMetalRough : 0u;
+}
 // the trace kernels' `bounce` argument: bounce | kTraceScanFlag = the SCAN pipeline's launch (ray set by bounce parity, codes in
 // the hit records); without the flag: rays[0], plain hit records (classic pipeline, ray-batch hooks)
 constexpr int kTraceScanFlag = 0x100;
@@ -265,7 +278,13 @@ struct RegionCounters {
     // continuation rays of this region the material launch of a bounce did NOT queue because their roulette draw was lost already
     // (kShadeDropEnded); the reference queues them, so the trace-queue size the library reports is traceSize + endedSize
     int32_t endedSize[kMaxBounceSlots];
-    int32_t pad_[2048 - 14 * kMaxBounceSlots];
+    // NX_MAT_METALROUGH's rows of materialSize and scanTile, taken from the padding so that no word in front of them moves
+    int32_t materialSizeMetal[kMaxBounceSlots];
+    int32_t scanTileMetal[kMaxBounceSlots];
+    // ... and, ordered compaction (region 0's words only), the tile tickets of its two classic launches: [0] logic_metal_kernel, [1] its
+    // shade_kernel (Counters::scanTicket has a row per reference kind and stays where it is)
+    int32_t scanTicketMetal[2][kMaxBounceSlots];
+    int32_t pad_[2048 - 18 * kMaxBounceSlots];
 };
 static_assert(sizeof(RegionCounters) == 8192, "one region's counters per 8 KiB");
 constexpr int kRegionStride = (int)(sizeof(RegionCounters) / sizeof(int32_t));  // distance between the same word of two regions
@@ -485,6 +504,10 @@ struct DeviceState {
     float padGrid2_;
     float mediumBscale[3];
     float padGrid3_;
+    // The fifth material queue of the CLASSIC pipeline (NX_MAT_METALROUGH), nullptr unless a material has the type under the ordered
+    // compaction: filled by logic_metal_kernel, read by shade_kernel<NX_MAT_METALROUGH> (nx_wavefront_metal.hip).  material[4] above keeps
+    // the reference's four.  Last in the block: nothing in front moves.
+    MaterialQueue materialMetal;
 };
 
 // Argument block of the adaptive update's kernels (nx_adaptive.hip; filled by nxhip_adaptive_update)
@@ -536,6 +559,7 @@ constexpr uint64_t layout_stamp()
         sizeof(DenoiseLaunch), offsetof(DenoiseLaunch, width), sizeof(TextureDev), sizeof(TraceQueue), sizeof(ShadowQueue), sizeof(MaterialQueue), sizeof(FrameState), sizeof(TraceStatsDev),
         (uint64_t)kNodeStride, (uint64_t)kTriStride, (uint64_t)kShadeTriStride, (uint64_t)kQueueShards, (uint64_t)kQueueShardSlack, (uint64_t)kRegionStride, (uint64_t)kMaxBounceSlots,
         (uint64_t)kEnvGuide, (uint64_t)kHitCodeShift, sizeof(TraceRays), offsetof(TraceQueue, hit), (uint64_t)kMaterialTypeOffset, sizeof(nx_material), sizeof(nx_bvh_instance), sizeof(nx_triangle), sizeof(nx_light), sizeof(nx_camera),
+        offsetof(RegionCounters, materialSizeMetal), offsetof(RegionCounters, scanTileMetal), offsetof(RegionCounters, scanTicketMetal), offsetof(DeviceState, materialMetal), (uint64_t)kHitCodeMetalRough, (uint64_t)kScanMetalBit,
     };
     for (uint64_t v : w) h = layout_mix(h, v);
     return h;

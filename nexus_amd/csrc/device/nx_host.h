@@ -39,12 +39,18 @@ const void* shade_detail_kernel_ptr(int type, bool lightPower, bool analytic);  
 const void* shade_scan_detail_kernel_ptr(bool lightPower, bool analytic);
 const void* tail_detail_kernel_ptr(bool lightPower, bool analytic);
 const void* shading_frame_hook_kernel_ptr();
+const void* shade_scan_metal_kernel_ptr(bool lightPower, bool analytic);  // nx_wavefront_metal.hip: the METAL instances (kFlavorMetal)
+const void* tail_metal_kernel_ptr(bool lightPower, bool analytic);
+const void* bsdf_hook_metal_kernel_ptr();
+const void* logic_metal_kernel_ptr();  // (the classic pipeline's fifth queue and its material kernel)
+const void* shade_metal_kernel_ptr(bool lightPower, bool analytic);
+const void* material_inputs_hook_kernel_ptr();
 const void* tex2d_linear_hook_kernel_ptr();
-const void* medium_scatter_kernel_ptr(bool lightPower, bool analytic);  // nx_medium.hip: the medium's kernels (kFlavorMedium) and its hooks'
+const void* medium_scatter_kernel_ptr(bool lightPower, bool analytic, bool metal = false);  // nx_medium.hip: the medium's kernels (kFlavorMedium) and its hooks'
 const void* medium_shadow_kernel_ptr();
 const void* medium_segment_hook_kernel_ptr();
 const void* medium_phase_hook_kernel_ptr();
-const void* medium_scatter_grid_kernel_ptr(bool lightPower, bool analytic);  // ... the density grid's instances (kFlavorMediumGrid), its build and its hooks'
+const void* medium_scatter_grid_kernel_ptr(bool lightPower, bool analytic, bool metal = false);  // ... the density grid's instances (kFlavorMediumGrid), its build and its hooks'
 const void* medium_shadow_grid_kernel_ptr();
 const void* medium_brick_kernel_ptr();
 const void* medium_density_hook_kernel_ptr();
@@ -60,12 +66,14 @@ const void* adaptive_scan_kernel_ptr();
 const void* adaptive_fill_kernel_ptr();
 const void* light_pick_kernel_ptr();  // nx_lights.hip
 const void* inst_code_kernel_ptr();  // nx_refit.hip
+const void* inst_code_metal_kernel_ptr();  // (... of a material table with an NX_MAT_METALROUGH)
 const void* instance_transform_kernel_ptr();
 const void* tlas_refit_kernel_ptr();
 const void* blas_refit_kernel_ptr();
 uint64_t layout_stamp_trace();
 uint64_t layout_stamp_wavefront();
 uint64_t layout_stamp_wavefront_detail();
+uint64_t layout_stamp_wavefront_metal();
 uint64_t layout_stamp_medium();
 uint64_t layout_stamp_refit();
 uint64_t layout_stamp_lbvh();
@@ -131,12 +139,18 @@ inline BounceKernel trace_entry(bool identity = false) { return {trace_entry_ker
 inline BounceKernel thin() { return {thin_kernel_ptr()}; }
 inline StateKernel entry_state() { return {entry_state_kernel_ptr()}; }
 // (detail: the DETAIL instances of a context whose materials name normal or roughness maps — nx_wavefront_detail.hip)
-inline BounceKernel tail(bool lightPower, bool analytic = false, bool detail = false) { return {detail ? tail_detail_kernel_ptr(lightPower, analytic) : tail_kernel_ptr(lightPower, analytic)}; }
+// (metal: the METAL instances of a context with an NX_MAT_METALROUGH material — nx_wavefront_metal.hip; they are DETAIL instances too)
+inline BounceKernel tail(bool lightPower, bool analytic = false, bool detail = false, bool metal = false)
+{
+    return {metal ? tail_metal_kernel_ptr(lightPower, analytic) : detail ? tail_detail_kernel_ptr(lightPower, analytic) : tail_kernel_ptr(lightPower, analytic)};
+}
+inline BounceKernel logic_metal() { return {logic_metal_kernel_ptr()}; }
+inline BounceKernel shade_metal(bool lightPower, bool analytic) { return {shade_metal_kernel_ptr(lightPower, analytic)}; }
 inline BounceKernel logic(int items, bool analytic = false) { return {logic_kernel_ptr(items, analytic)}; }
 inline BounceKernel shade(int type, bool lightPower, bool analytic = false, bool detail = false) { return {detail ? shade_detail_kernel_ptr(type, lightPower, analytic) : shade_kernel_ptr(type, lightPower, analytic)}; }
-inline TypeKernel shade_scan(bool lightPower, bool noMaps = false, bool analytic = false, bool detail = false)
+inline TypeKernel shade_scan(bool lightPower, bool noMaps = false, bool analytic = false, bool detail = false, bool metal = false)
 {
-    return {detail ? shade_scan_detail_kernel_ptr(lightPower, analytic) : shade_scan_kernel_ptr(lightPower, noMaps, analytic)};
+    return {metal ? shade_scan_metal_kernel_ptr(lightPower, analytic) : detail ? shade_scan_detail_kernel_ptr(lightPower, analytic) : shade_scan_kernel_ptr(lightPower, noMaps, analytic)};
 }
 inline TypeKernel count_scan() { return {count_scan_kernel_ptr()}; }
 inline Kernel<DeviceState*, U32, U32, U32> begin_frame() { return {begin_frame_kernel_ptr()}; }  // (S, frames, frameLast, scanEpoch)
@@ -146,6 +160,8 @@ inline StateKernel generate() { return {generate_kernel_ptr()}; }
 inline Kernel<State, const float4*, U32, U32, U32, U32, const U32*> accumulate() { return {accumulate_kernel_ptr()}; }
 inline Kernel<const float4*, U32, const U32*, float4*, U32*> compose() { return {compose_kernel_ptr()}; }  // (src, count, dstMap, dstAccum, dstRgba8)
 inline Kernel<const nx_material*, const nx_bsdf_query*, U32, int, nx_bsdf_result*> bsdf_hook() { return {bsdf_hook_kernel_ptr()}; }  // (material, q, count, sample, out)
+inline Kernel<const nx_material*, const nx_bsdf_query*, U32, int, nx_bsdf_result*> bsdf_hook_metal() { return {bsdf_hook_metal_kernel_ptr()}; }  // (the same list; NX_MAT_METALROUGH)
+inline Kernel<State, U32, const U32*, const float*, U32, float*> material_inputs_hook() { return {material_inputs_hook_kernel_ptr()}; }  // (S, instance, triIdx, hitUv, count, out)
 inline Kernel<int, const double*, const double*, U32, double*> fmath_hook() { return {fmath_hook_kernel_ptr()}; }                   // (op, a, b, count, out)
 inline Kernel<TextureDev, const float*, const float*, U32, float4*> tex2d_hook() { return {tex2d_hook_kernel_ptr()}; }              // (t, srgbLut, uv, count, out)
 inline Kernel<const float4*, int, int, const float*, U32, float4*> tex2d_float_hook() { return {tex2d_float_hook_kernel_ptr()}; }       // (texels, W, H, uv, count, out)
@@ -155,13 +171,13 @@ inline Kernel<TextureDev, const float*, U32, float4*> tex2d_linear_hook() { retu
 inline Kernel<State, U32, const U32*, const float*, const float*, U32, float*, float*, U32*> shading_frame_hook() { return {shading_frame_hook_kernel_ptr()}; }
 // (S, light, origin, r, count, direction, tmax, factor, ok)
 inline Kernel<State, U32, const float*, const float*, U32, float*, float*, float*, U32*> alight_hook() { return {alight_hook_kernel_ptr()}; }
-inline BounceKernel medium_scatter(bool lightPower, bool analytic) { return {medium_scatter_kernel_ptr(lightPower, analytic)}; }  // (S, bounce | kShadeDropEnded)
+inline BounceKernel medium_scatter(bool lightPower, bool analytic, bool metal = false) { return {medium_scatter_kernel_ptr(lightPower, analytic, metal)}; }  // (S, bounce | kShadeDropEnded)
 inline BounceKernel medium_shadow() { return {medium_shadow_kernel_ptr()}; }
 // (S, origin, dir, tEnd, xi, count, t0, length, transmittance, scatterT)
 inline Kernel<State, const float*, const float*, const float*, const float*, U32, float*, float*, float*, float*> medium_segment_hook() { return {medium_segment_hook_kernel_ptr()}; }
 // (S, dirIn, xi1, xi2, count, dirOut, pdf)
 inline Kernel<State, const float*, const float*, const float*, U32, float*, float*> medium_phase_hook() { return {medium_phase_hook_kernel_ptr()}; }
-inline BounceKernel medium_scatter_grid(bool lightPower, bool analytic) { return {medium_scatter_grid_kernel_ptr(lightPower, analytic)}; }
+inline BounceKernel medium_scatter_grid(bool lightPower, bool analytic, bool metal = false) { return {medium_scatter_grid_kernel_ptr(lightPower, analytic, metal)}; }
 inline BounceKernel medium_shadow_grid() { return {medium_shadow_grid_kernel_ptr()}; }
 // (rho, nx, ny, nz, nbx, nby, nbz, bricks)
 inline Kernel<const float*, U32, U32, U32, U32, U32, U32, float*> medium_brick() { return {medium_brick_kernel_ptr()}; }
@@ -180,7 +196,7 @@ inline Kernel<AdaptiveLaunch> adaptive_scan() { return {adaptive_scan_kernel_ptr
 inline Kernel<AdaptiveLaunch> adaptive_fill() { return {adaptive_fill_kernel_ptr()}; }
 // (table, guide, guideSize, entries, u, count, entry, prob)
 inline Kernel<const LightEntry*, const U32*, U32, U32, const float*, U32, U32*, float*> light_pick() { return {light_pick_kernel_ptr()}; }
-inline Kernel<State, InstTrav*, const ShadeInst*, U32> inst_code() { return {inst_code_kernel_ptr()}; }  // (S, trav, shadeInst, count)
+inline Kernel<State, InstTrav*, const ShadeInst*, U32> inst_code(bool metal = false) { return {metal ? inst_code_metal_kernel_ptr() : inst_code_kernel_ptr()}; }  // (S, trav, shadeInst, count)
 // (S, instances, trav, leafOfInstance, ids, transforms, count, tightBoxes, shadeInst, blasRefresh)
 inline Kernel<State, nx_bvh_instance*, InstTrav*, const U32*, const U32*, const float*, U32, void*, ShadeInst*, U32> instance_transform() { return {instance_transform_kernel_ptr()}; }
 // (nodes, primIdx, instances, order, levelStart, levels, nodeBox, tightBoxes)
@@ -310,6 +326,7 @@ int check_medium_grid(const nxhip_ctx* c, const char* who);  // ... and the thic
 int alloc_queues(nxhip_ctx* c, size_t n);
 bool slot_queues_ready(const nxhip_ctx* c, const PassSlot* q);
 int ensure_slot_queues(nxhip_ctx* c, PassSlot* q);
+int ensure_metal_queue(nxhip_ctx* c, PassSlot* q);  // the classic pipeline's fifth material queue, while a material is an NX_MAT_METALROUGH
 void release_slot_queues(nxhip_ctx* c, PassSlot* q);
 void release_denoise_planes(nxhip_ctx* c);
 void publish_pixel_set(nxhip_ctx* c);

@@ -249,7 +249,9 @@ __global__ void __launch_bounds__(kWideBlock) medium_brick_kernel(const float* _
 // bounded by the region's size.
 // GRID = false is the homogeneous kernel as it always was; GRID = true (kFlavorMediumGrid) finds the collision by the walk: lanes of a wave
 // walk different numbers of bricks, so a tile costs what its longest walk costs.
-template <bool POWER, bool ANALYTIC, bool GRID>
+// METAL (a context with an NX_MAT_METALROUGH material: kFlavorMetal): the fifth material type's code is a hit like the other four's; the
+// instances with METAL = false are the code of a context without such a material.
+template <bool POWER, bool ANALYTIC, bool GRID, bool METAL = false>
 __global__ void __launch_bounds__(kShadeBlock) medium_scatter_kernel(const DeviceState* __restrict__ S, const int bounceArg)
 {
     const int bounce = bounceArg & 0xff;
@@ -281,7 +283,7 @@ __global__ void __launch_bounds__(kShadeBlock) medium_scatter_kernel(const Devic
         uint32_t word = 0u;
         if (r < inRegion) word = S->trace.hitInst[at];
         const uint32_t code = word >> kHitCodeShift;
-        if (code != 0u && code != kHitCodeMedium && (code <= 4u || code == kHitCodeMiss)) {
+        if (code != 0u && code != kHitCodeMedium && (code <= 4u || (METAL && code == kHitCodeMetalRough) || code == kHitCodeMiss)) {
             const float4 ro = in.rayO[at], rd = in.rayD[at];
             const f3 o = mk3(ro.x, ro.y, ro.z), d = mk3(rd.x, rd.y, rd.z);
             pixelIdx = __float_as_uint(rd.w);
@@ -478,8 +480,12 @@ __global__ void __launch_bounds__(kWideBlock) medium_track_hook_kernel(const Dev
     }
 }
 
-const void* medium_scatter_grid_kernel_ptr(bool lightPower, bool analytic)
+const void* medium_scatter_grid_kernel_ptr(bool lightPower, bool analytic, bool metal)
 {
+    if (metal) {
+        if (analytic) return lightPower ? (const void*)medium_scatter_kernel<true, true, true, true> : (const void*)medium_scatter_kernel<false, true, true, true>;
+        return lightPower ? (const void*)medium_scatter_kernel<true, false, true, true> : (const void*)medium_scatter_kernel<false, false, true, true>;
+    }
     if (analytic) return lightPower ? (const void*)medium_scatter_kernel<true, true, true> : (const void*)medium_scatter_kernel<false, true, true>;
     return lightPower ? (const void*)medium_scatter_kernel<true, false, true> : (const void*)medium_scatter_kernel<false, false, true>;
 }
@@ -489,8 +495,12 @@ const void* medium_density_hook_kernel_ptr() { return (const void*)medium_densit
 const void* medium_track_hook_kernel_ptr() { return (const void*)medium_track_hook_kernel; }
 
 // (the light sample's mode and analytic lights: next_event_estimation's instances, chosen as the material launch's are — nxhip_render.hip)
-const void* medium_scatter_kernel_ptr(bool lightPower, bool analytic)
+const void* medium_scatter_kernel_ptr(bool lightPower, bool analytic, bool metal)
 {
+    if (metal) {
+        if (analytic) return lightPower ? (const void*)medium_scatter_kernel<true, true, false, true> : (const void*)medium_scatter_kernel<false, true, false, true>;
+        return lightPower ? (const void*)medium_scatter_kernel<true, false, false, true> : (const void*)medium_scatter_kernel<false, false, false, true>;
+    }
     if (analytic) return lightPower ? (const void*)medium_scatter_kernel<true, true, false> : (const void*)medium_scatter_kernel<false, true, false>;
     return lightPower ? (const void*)medium_scatter_kernel<true, false, false> : (const void*)medium_scatter_kernel<false, false, false>;
 }

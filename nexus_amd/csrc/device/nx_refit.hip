@@ -334,8 +334,20 @@ __global__ void __launch_bounds__(256) inst_code_kernel(const DeviceState* __res
         trav[k].instIdx = inst | ((type >= 0 && type <= 3) ? (uint32_t)(type + 1) << kHitCodeShift : 0u);
     }
 }
+// ... of a material table that holds an NX_MAT_METALROUGH, whose code is not type + 1 (nx_device.h hit_code_of_type); the kernel above stays
+// the code of every other table
+__global__ void __launch_bounds__(256) inst_code_metal_kernel(const DeviceState* __restrict__ S, InstTrav* travArg, const ShadeInst* shadeInstArg, const uint32_t count)
+{
+    NX_G InstTrav* trav = (NX_G InstTrav*)travArg;
+    const NX_G ShadeInst* shadeInst = (const NX_G ShadeInst*)shadeInstArg;
+    for (uint32_t k = blockIdx.x * blockDim.x + threadIdx.x; k < count; k += gridDim.x * blockDim.x) {
+        const uint32_t inst = trav[k].instIdx & kHitInstMask;
+        trav[k].instIdx = inst | (hit_code_of_type((int)shadeInst[inst].material.type) << kHitCodeShift);
+    }
+}
 
 const void* inst_code_kernel_ptr() { return (const void*)inst_code_kernel; }
+const void* inst_code_metal_kernel_ptr() { return (const void*)inst_code_metal_kernel; }
 const void* instance_transform_kernel_ptr() { return (const void*)instance_transform_kernel; }
 const void* tlas_refit_kernel_ptr() { return (const void*)tlas_refit_kernel; }
 const void* blas_refit_kernel_ptr() { return (const void*)blas_refit_kernel; }

@@ -135,7 +135,8 @@ struct SlotAllocator {
     int size, lastTile;
 
     // `kind`: 0 logic, 1 + NX_MAT_* material kernel; `items`: size of the launch's input queue
-    NXD void init(const DeviceState* S, int* const first, const int step, const int kind, const int bounce, const int items)
+    // (ticketWord: the tile ticket of a kind that has no row in Counters::scanTicket — NX_MAT_METALROUGH's launches; nullptr: the kind's row)
+    NXD void init(const DeviceState* S, int* const first, const int step, const int kind, const int bounce, const int items, NX_G int* const ticketWord = nullptr)
     {
         __shared__ int wave[K * kMaxWavesPerBlock];
         __shared__ int base[K];
@@ -149,7 +150,7 @@ struct SlotAllocator {
         lastTile = (items + (int)blockDim.x - 1) / (int)blockDim.x - 1;
         if (ORDERED) {
             status = S->scanStatus;
-            ticket = &S->counters->scanTicket[kind][bounce];
+            ticket = ticketWord ? ticketWord : &S->counters->scanTicket[kind][bounce];
             frame = S->frame;
             serial = S->frame->scanEpoch * 1024u + (uint32_t)bounce * 8u + (uint32_t)kind;
         }
@@ -233,7 +234,7 @@ struct TileAllocator {
     int size, lastTile, tileItems;
 
     // `kind`: 0 logic, 1 + NX_MAT_* material kernel; `items`: size of the launch's input queue
-    NXD void init(const DeviceState* S, int* const first, const int step, const int kind, const int bounce, const int items)
+    NXD void init(const DeviceState* S, int* const first, const int step, const int kind, const int bounce, const int items, NX_G int* const ticketWord = nullptr)
     {
         __shared__ int wave[U * K * kMaxWavesPerBlock];
         __shared__ int base[U * K];
@@ -248,7 +249,7 @@ struct TileAllocator {
         lastTile = (items + tileItems - 1) / tileItems - 1;
         if (ORDERED) {
             status = S->scanStatus;
-            ticket = &S->counters->scanTicket[kind][bounce];
+            ticket = ticketWord ? ticketWord : &S->counters->scanTicket[kind][bounce];
             frame = S->frame;
             serial = S->frame->scanEpoch * 1024u + (uint32_t)bounce * 8u + (uint32_t)kind;
         }
@@ -553,7 +554,8 @@ NXD uint32_t nee_light_count(const DeviceState* S)
 // LogicKernel's decision for one path (PathTracer.cu:136-210), without the queue traffic: a miss ends the path and adds the
 // (MIS-weighted) environment `bg`; a hit survives Russian roulette with probability max(throughput) — `survived`, the
 // throughput divided by it in `throughputOut` — and is shaded as the returned material type, or ends (-1).
-template <bool kEnvFloat = true, bool ANALYTIC = false, class HitInst>
+// METAL: the instances of a context with an NX_MAT_METALROUGH material (kFlavorMetal) — the fifth type is one a path may be shaded as
+template <bool kEnvFloat = true, bool ANALYTIC = false, bool METAL = false, class HitInst>
 NXD int logic_path(const DeviceState* S, const int bounce, const uint32_t frame, const uint32_t seedSlot, const uint32_t pixelIdx, const float hitT, const f3 dir,
                    const float4 tp, HitInst hitInst, bool& miss, f3& bg, bool& survived, f3& throughputOut, uint32_t& inst, bool& needsPrevVertex)
 {
@@ -589,7 +591,7 @@ NXD int logic_path(const DeviceState* S, const int bounce, const uint32_t frame,
             // record (one dependent load; the reference's instance -> material is two)
             const uint32_t typeAndFlag = *(const NX_G uint32_t*)((const NX_G char*)&S->shadeInst[inst].material + kMaterialTypeOffset);
             type = (int)(int8_t)(typeAndFlag & 0xffu);
-            if (type < 0 || type > 3) type = -1;
+            if (type < 0 || type > (METAL ? NX_MAT_METALROUGH : NX_MAT_CONDUCTOR)) type = -1;
             needsPrevVertex = ((typeAndFlag >> 8) & 1u) != 0u;
         }
     }
@@ -702,6 +704,7 @@ NXD MatParams load_params(const nx_material& m)
     p.ior = m.plastic.ior;
     p.cIor = ld3(m.conductor.ior);
     p.cK = ld3(m.conductor.k);
+    p.metallic = m.metalrough.metallic;
     return p;
 }
 
@@ -925,7 +928,8 @@ NXD void shade_path(const DeviceState* S, const int bounce, const uint32_t frame
         if constexpr (DETAIL) {
             // (from here on `normal` IS the shading normal: the interpolated one is not read again, so only three registers cross the sampling code)
             bool fellBack;
-            normal = detail_shading_frame<TYPE>(S, S->shadeDetail[instanceIdx], tri, T, tp0, tp1, tp2, texUv, rayDirection, normal, gNormal, mp.roughness, fellBack);
+            normal = detail_shading_frame<TYPE>(S, S->shadeDetail[instanceIdx], tri, T, tp0, tp1, tp2, texUv, rayDirection, normal, gNormal, mp.roughness, fellBack,
+                                                TYPE == NX_MAT_METALROUGH ? &mp.metallic : nullptr);
         } else {
             if (dot3(gNormal, rayDirection) > 0.0f && TYPE != NX_MAT_DIELECTRIC) { normal = -normal; gNormal = -gNormal; }
         }
@@ -973,14 +977,16 @@ template <int TYPE, bool ORDERED, bool POWER, bool ANALYTIC = false, bool DETAIL
 __global__ void __launch_bounds__(ORDERED ? kShadeBlockOrderedThreads : kShadeBlock, ORDERED ? NX_SHADE_WAVES_ORDERED : NX_SHADE_WAVES) shade_kernel(const DeviceState* __restrict__ S, const int bounce)
 {
     Counters* C = S->counters;
-    const QueueView in = queue_view(&C->region[0].materialSize[TYPE][bounce], S->queueShardCap);
+    // (NX_MAT_METALROUGH: the fifth queue, its size row and its ticket row are words of their own — nx_device.h)
+    constexpr bool kMetal = TYPE == NX_MAT_METALROUGH;
+    const QueueView in = queue_view(kMetal ? &C->region[0].materialSizeMetal[bounce] : &C->region[0].materialSize[kMetal ? 0 : TYPE][bounce], S->queueShardCap);
     const int size = in.total;
     if ((int)(blockIdx.x * blockDim.x) >= size) return;  // no tile for this workgroup (see logic_kernel)
     const uint32_t frame = S->frame->frameNumber;
-    const MaterialQueue mq = S->material[TYPE];
+    const MaterialQueue mq = kMetal ? S->materialMetal : S->material[kMetal ? 0 : TYPE];
     SlotAllocator<ORDERED, 2> slots;  // 0: shadow requests, 1: continuation rays
     static_assert(offsetof(RegionCounters, traceSize) + kMaxBounceSlots * sizeof(int32_t) == offsetof(RegionCounters, traceShadowSize), "traceShadowSize follows traceSize");
-    slots.init(S, &C->region[0].traceShadowSize[bounce], -kMaxBounceSlots, 1 + TYPE, bounce, size);
+    slots.init(S, &C->region[0].traceShadowSize[bounce], -kMaxBounceSlots, 1 + TYPE, bounce, size, kMetal ? &S->counters->region[0].scanTicketMetal[1][bounce] : nullptr);
     const ProducerRegions out = producer_regions(S, size, (int)blockDim.x);
     for (int tile = slots.first_tile(); tile < size; tile = slots.next_tile(tile)) {
         const int requestIdx = tile + (int)threadIdx.x;
@@ -1067,11 +1073,14 @@ NXD void shade_scan_type(const DeviceState* __restrict__ S, const int bounce, co
     // TYPE == kScanMiss: the rays that missed (code kHitCodeMiss) — what is left of the logic step when a miss can contribute: the
     // environment (flat colour or map, MIS-weighted against the environment sampler) added to the path's radiance, PathTracer.cu:152-164
     constexpr bool kMiss = TYPE == kScanMiss;
-    constexpr uint32_t kCode = kMiss ? kHitCodeMiss : (uint32_t)(TYPE + 1);
+    // TYPE == kScanMetalBit: NX_MAT_METALROUGH, whose own number is the misses' place here (its code, ticket row and size row: nx_device.h)
+    constexpr bool kMetal = TYPE == kScanMetalBit;
+    constexpr int kMat = kMetal ? NX_MAT_METALROUGH : TYPE;  // the material type shaded (kMiss: none)
+    constexpr uint32_t kCode = kMiss ? kHitCodeMiss : hit_code_of_type(kMat);
     Counters* C = S->counters;
     const int tileRays = per * kShadeBlock;
     const int tiles = (inRegion + tileRays - 1) / tileRays;
-    int* const ticket = &C->region[region].scanTile[TYPE][bounce];
+    int* const ticket = kMetal ? &C->region[region].scanTileMetal[bounce] : &C->region[region].scanTile[kMetal ? 0 : TYPE][bounce];
     int t = firstTile;
     if (t < 0 && tiles <= staticTiles) return;  // every tile has a workgroup of this type's own
     __syncthreads();  // the previous type is done with the ticket word and the ring
@@ -1090,7 +1099,7 @@ NXD void shade_scan_type(const DeviceState* __restrict__ S, const int bounce, co
     const NX_G uint32_t* const codes = S->trace.hitInst + regionBase;
     SlotAllocator<false, 2> slots;  // 0: shadow requests, 1: continuation rays
     static_assert(offsetof(RegionCounters, traceSize) + kMaxBounceSlots * sizeof(int32_t) == offsetof(RegionCounters, traceShadowSize), "traceShadowSize follows traceSize");
-    slots.init(S, &C->region[0].traceShadowSize[bounce], -kMaxBounceSlots, 1 + (kMiss ? 0 : TYPE), bounce, inRegion);
+    slots.init(S, &C->region[0].traceShadowSize[bounce], -kMaxBounceSlots, 1 + ((kMiss || kMetal) ? 0 : TYPE), bounce, inRegion);  // (the kind names a ticket word of the ORDERED allocator: unused here)
     const int lane = threadIdx.x & (kWave - 1);
     const unsigned long long laneLt = (1ull << lane) - 1ull;
     int tail = 0, head = 0;  // ring positions [tail, head) hold found slots not shaded yet (uniform)
@@ -1142,7 +1151,7 @@ NXD void shade_scan_type(const DeviceState* __restrict__ S, const int bounce, co
             // ... and the path's previous vertex, for hits that can need it (keep_previous_vertex)
             const uint32_t typeAndFlag = *(const NX_G uint32_t*)((const NX_G char*)&S->shadeInst[instanceIdx].material + kMaterialTypeOffset);
             if ((typeAndFlag >> 8) & 1u) keep_previous_vertex(S, pixelIdx, in.rayO[at]);
-            shade_path<TYPE, POWER, NO_MAPS, ANALYTIC, DETAIL>(S, bounce, frame, (uint32_t)at, pixelIdx, hit.y, hit.z, __float_as_uint(hit.w), instanceIdx, mk3(dirPix.x, dirPix.y, dirPix.z), tpdf,
+            shade_path<kMat, POWER, NO_MAPS, ANALYTIC, DETAIL>(S, bounce, frame, (uint32_t)at, pixelIdx, hit.y, hit.z, __float_as_uint(hit.w), instanceIdx, mk3(dirPix.x, dirPix.y, dirPix.z), tpdf,
                              [&]() { return S->rayOrigin[pixelIdx]; },
                              [&](f3 emitted, uint32_t instIdx) {
                                  if (bounce == 1 && bounce != (int)S->settings.pathLength && pixelIdx < S->localCount && S->frame->pixelQueryPixel == (int)global_pixel(S, pixelIdx))
@@ -1239,7 +1248,7 @@ NXD void shade_scan_type(const DeviceState* __restrict__ S, const int bounce, co
     }
     if (head - tail > 0) shade_batch(head - tail);
     // the items this workgroup shaded, for nxhip_read_queue_sizes (the reference's per-type queue sizes, D_QueueSize)
-    if (!kMiss && threadIdx.x == 0 && head) atomicAdd(&C->region[region].materialSize[kMiss ? 0 : TYPE][bounce], head);
+    if (!kMiss && threadIdx.x == 0 && head) atomicAdd(kMetal ? &C->region[region].materialSizeMetal[bounce] : &C->region[region].materialSize[(kMiss || kMetal) ? 0 : TYPE][bounce], head);
     // ... and the continuation rays it did not queue: the waves' counts meet in the ring's head word, one add per workgroup
     if (!kMiss && dropEnded) {
         __syncthreads();  // everybody has read the head
@@ -1256,7 +1265,9 @@ NXD void shade_scan_type(const DeviceState* __restrict__ S, const int bounce, co
 // workgroups start on different types (rank modulo the number of types) and move on to the next type when theirs has no tile
 // left, so the types run side by side, the launch ends when the last tile of the last type does, and a bounce costs one material
 // launch instead of one per type (the reference: four, PathTracer.cpp:116-120).  A single-bit mask is a per-type launch.
-template <bool POWER, bool NO_MAPS = false, bool ANALYTIC = false, bool DETAIL = false>  // (the light sample's mode, a map-free context, analytic lights: next_event_estimation; detail maps: shade_path)
+// METAL (a context with an NX_MAT_METALROUGH material: kFlavorMetal): the fifth material type as a sixth case, typeMask bit kScanMetalBit.  The
+// kernel's register count is the maximum over its cases, so the case is compiled into these instances alone (nx_wavefront_metal.hip).
+template <bool POWER, bool NO_MAPS = false, bool ANALYTIC = false, bool DETAIL = false, bool METAL = false>  // (the light sample's mode, a map-free context, analytic lights: next_event_estimation; detail maps: shade_path)
 __global__ void __launch_bounds__(kShadeBlock, NX_SHADE_WAVES) shade_scan_kernel(const DeviceState* __restrict__ S, const int bounceArg, const int typeMask)
 {
     const int bounce = bounceArg & 0xff;
@@ -1266,7 +1277,7 @@ __global__ void __launch_bounds__(kShadeBlock, NX_SHADE_WAVES) shade_scan_kernel
     const int region = (int)(blockIdx.x & (kQueueShards - 1));
     const int inRegion = S->counters->region[region].traceSize[bounce - 1];  // rays of this region after trace(bounce - 1)
     const int rank = (int)(blockIdx.x >> 3), ranks = max(1, (int)(gridDim.x >> 3));
-    const int nTypes = __popc((uint32_t)typeMask & 0x1fu);
+    const int nTypes = __popc((uint32_t)typeMask & (METAL ? 0x3fu : 0x1fu));
     if (inRegion <= 0 || nTypes == 0) return;
     // this workgroup's place among those that start on the same type, and how many of them there are
     const int myStart = rank % nTypes, myIndex = rank / nTypes;
@@ -1281,12 +1292,13 @@ __global__ void __launch_bounds__(kShadeBlock, NX_SHADE_WAVES) shade_scan_kernel
     if (myIndex >= tiles) return;  // more workgroups than tiles (late bounces): the surplus leaves before any barrier or atomic
     // the types in graph order of the reference (Diffuse, Plastic, Dielectric, Conductor: PathTracer.cpp:116-120), rotated so that
     // this workgroup begins with its own
-    constexpr int kOrder[5] = {NX_MAT_DIFFUSE, NX_MAT_PLASTIC, NX_MAT_DIELECTRIC, NX_MAT_CONDUCTOR, kScanMiss};
+    // (METAL: the new type goes last, so the five in front of it keep their places)
+    constexpr int kOrder[6] = {NX_MAT_DIFFUSE, NX_MAT_PLASTIC, NX_MAT_DIELECTRIC, NX_MAT_CONDUCTOR, kScanMiss, kScanMetalBit};
     for (int step = 0; step < nTypes; step++) {
         const int want = (myStart + step) % nTypes;  // index among the types present
         int type = -1, seen = 0;
 #pragma unroll
-        for (int k = 0; k < 5; k++)
+        for (int k = 0; k < (METAL ? 6 : 5); k++)
             if ((typeMask >> kOrder[k]) & 1) { if (seen == want) type = kOrder[k]; seen++; }
         const int starters = (ranks - want + nTypes - 1) / nTypes;  // workgroups whose first type this is: each takes the tile of its index
         const int first = step == 0 ? myIndex : -1;
@@ -1296,6 +1308,9 @@ __global__ void __launch_bounds__(kShadeBlock, NX_SHADE_WAVES) shade_scan_kernel
         case NX_MAT_DIELECTRIC: shade_scan_type<NX_MAT_DIELECTRIC, POWER, NO_MAPS, ANALYTIC, DETAIL>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket); break;
         case NX_MAT_CONDUCTOR: shade_scan_type<NX_MAT_CONDUCTOR, POWER, NO_MAPS, ANALYTIC, DETAIL>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket); break;
         case kScanMiss: shade_scan_type<kScanMiss, POWER, NO_MAPS, ANALYTIC, DETAIL>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket); break;
+        case kScanMetalBit:
+            if constexpr (METAL) shade_scan_type<kScanMetalBit, POWER, NO_MAPS, ANALYTIC, DETAIL>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket);
+            break;
         default: break;
         }
     }
@@ -1329,7 +1344,7 @@ __global__ void __launch_bounds__(kWideBlock) count_scan_kernel(const DeviceStat
 #ifndef NX_TAIL_REFILL_BELOW
 #define NX_TAIL_REFILL_BELOW 40
 #endif
-template <bool POWER, bool ANALYTIC = false, bool DETAIL = false>  // (the light sample's mode, analytic lights: next_event_estimation; detail maps: shade_path)
+template <bool POWER, bool ANALYTIC = false, bool DETAIL = false, bool METAL = false>  // (the light sample's mode, analytic lights: next_event_estimation; detail maps: shade_path; METAL: the fifth material type)
 __global__ void __launch_bounds__(kTraceBlock) tail_kernel(const DeviceState* __restrict__ S, const int firstBounceArg)
 {
     // firstBounce | kTraceScanFlag: the pass ran the SCAN pipeline so far — the rays of trace(firstBounce - 1) are in the set of
@@ -1395,7 +1410,7 @@ __global__ void __launch_bounds__(kTraceBlock) tail_kernel(const DeviceState* __
         if (alive) {
             bool miss, survived, needsPrevVertex;
             f3 bg = mk3(0.0f), t = mk3(0.0f);
-            type = logic_path<true, ANALYTIC>(S, bounce, frame, (uint32_t)index, pixelIdx, hitT, dir, tp, [&]() { return inst; }, miss, bg, survived, t, inst, needsPrevVertex);
+            type = logic_path<true, ANALYTIC, METAL>(S, bounce, frame, (uint32_t)index, pixelIdx, hitT, dir, tp, [&]() { return inst; }, miss, bg, survived, t, inst, needsPrevVertex);
             if (miss) { rad.x += bg.x; rad.y += bg.y; rad.z += bg.z; dirty = true; }
             if (survived) { tp.x = t.x; tp.y = t.y; tp.z = t.z; }
             if (type < 0) alive = false;
@@ -1429,6 +1444,12 @@ __global__ void __launch_bounds__(kTraceBlock) tail_kernel(const DeviceState* __
                 if (S->conductorMode == NX_CONDUCTOR_EXTENDED)
                     shade_path<NX_MAT_CONDUCTOR, POWER, false, ANALYTIC, DETAIL>(S, bounce, frame, (uint32_t)index, pixelIdx, hu, hv, tri, inst, dir, tp, prevOrigin, emit, wantShadowRay, sh, wantTrace, updatePath, nextOrigin, nextDir, nextThroughput, nextPdf);
                 else alive = false;  // (the reference's graph has no conductor kernel: such a path ends unshaded)
+            }
+        }
+        if constexpr (METAL) {
+            if (__ballot(alive && type == NX_MAT_METALROUGH) != 0ull) {
+                if (alive && type == NX_MAT_METALROUGH)
+                    shade_path<NX_MAT_METALROUGH, POWER, false, ANALYTIC, DETAIL>(S, bounce, frame, (uint32_t)index, pixelIdx, hu, hv, tri, inst, dir, tp, prevOrigin, emit, wantShadowRay, sh, wantTrace, updatePath, nextOrigin, nextDir, nextThroughput, nextPdf);
             }
         }
         // ---- the light sample's shadow ray: traced now, added when unoccluded (the shadow launch of this bounce, BVH8Traversal.cuh:515)

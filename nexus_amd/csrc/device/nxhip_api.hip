@@ -62,7 +62,7 @@ int nxd::fail_invalid(const std::string& msg) { return fail_invalid(msg.c_str())
 static int check_layouts()
 {
     const struct { const char* unit; uint64_t stamp; } units[] = {
-        {"nx_trace.hip", layout_stamp_trace()}, {"nx_wavefront.hip", layout_stamp_wavefront()}, {"nx_wavefront_detail.hip", layout_stamp_wavefront_detail()}, {"nx_medium.hip", layout_stamp_medium()}, {"nx_refit.hip", layout_stamp_refit()},
+        {"nx_trace.hip", layout_stamp_trace()}, {"nx_wavefront.hip", layout_stamp_wavefront()}, {"nx_wavefront_detail.hip", layout_stamp_wavefront_detail()}, {"nx_wavefront_metal.hip", layout_stamp_wavefront_metal()}, {"nx_medium.hip", layout_stamp_medium()}, {"nx_refit.hip", layout_stamp_refit()},
         {"nx_lbvh.hip", layout_stamp_lbvh()}, {"nxhip_multigpu.hip", layout_stamp_multigpu()}, {"nx_entry.hip", layout_stamp_entry()}, {"nx_aov.hip", layout_stamp_aov()},
         {"nx_adaptive.hip", layout_stamp_adaptive()}, {"nx_lights.hip", layout_stamp_lights()}, {"nx_envmap.hip", layout_stamp_envmap()}, {"nxhip_scene.hip", layout_stamp_scene()},
         {"nxhip_render.hip", layout_stamp_render()}, {"nxhip_features.hip", layout_stamp_features()}, {"nxhip_hooks.hip", layout_stamp_hooks()},
@@ -163,6 +163,7 @@ static void compose_view(nxhip_ctx* c, PassSlot* s)
     v.counters = s->counters.as<Counters>();
     v.frame = s->frame.as<FrameState>();
     v.scanStatus = s->scanStatus.as<unsigned long long>();
+    v.materialMetal = MaterialQueue{s->mqMetal[0].as<float4>(), s->mqMetal[1].as<float4>(), s->mqMetal[2].as<float4>()};
     v.thinClosest = s->thinLists.as<uint32_t>();
     v.thinAny = s->thinLists.p ? s->thinLists.as<uint32_t>() + kThinListEntries : nullptr;
     v.thinCapacity = (s->thinLists.p && s->thinStates.p) ? kThinListEntries : 0u;
@@ -260,6 +261,7 @@ void nxd::release_slot_queues(nxhip_ctx* c, PassSlot* q)
 {
     for (const QueueBuf& b : slot_queue_buffers(q)) b.buf->release();
     q->scanStatus.release();
+    for (DevBuf& b : q->mqMetal) b.release();
     q->thinLists.release();
     q->thinStates.release();
     q->aovAlbedo.release();
@@ -284,6 +286,18 @@ int nxd::alloc_queues(nxhip_ctx* c, size_t n)
 
 // Before a slot is used: its queues exist at the nominal capacity.
 bool nxd::slot_queues_ready(const nxhip_ctx* c, const PassSlot* q) { return q->pathCapacity >= c->queueCapacity && q->pathCapacity > 0 && q->queuesScan == scan_pipeline(c); }
+
+// The fifth material queue: three buffers as large as the other queues', for a slot whose next pass runs the classic pipeline over a table
+// with an NX_MAT_METALROUGH.  A context that never does allocates nothing.
+int nxd::ensure_metal_queue(nxhip_ctx* c, PassSlot* q)
+{
+    const size_t bytes = queue_buffer_slots(q->pathCapacity) * 16;
+    if (q->mqMetal[0].p && q->mqMetal[0].bytes >= bytes) return NXHIP_OK;
+    NX_SYNC_ALL(c);
+    for (DevBuf& b : q->mqMetal) NX_ALLOC(b, bytes);
+    c->stateDirty = true;
+    return NXHIP_OK;
+}
 
 int nxd::ensure_slot_queues(nxhip_ctx* c, PassSlot* q)
 {
@@ -498,6 +512,11 @@ int nxhip_create(int device, uint32_t width, uint32_t height, void* stream, nxhi
             for (int analytic = 0; analytic < 2; analytic++) {
                 if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, tail_detail_kernel_ptr(power != 0, analytic != 0), kTraceBlockThreads, 0) != hipSuccess || perCU < 1) perCU = 2;
                 c->tailBlocksDetail[power][analytic] = std::max(1, perCU) * c->numCUs;
+            }
+        for (int power = 0; power < 2; power++)  // (... and the METAL instances of a context with an NX_MAT_METALROUGH material)
+            for (int analytic = 0; analytic < 2; analytic++) {
+                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, tail_metal_kernel_ptr(power != 0, analytic != 0), kTraceBlockThreads, 0) != hipSuccess || perCU < 1) perCU = 2;
+                c->tailBlocksMetal[power][analytic] = std::max(1, perCU) * c->numCUs;
             }
         // Launch-geometry knobs of the measurement sweeps.  They are read only when NX_TUNING_KNOBS=1 says
         // that a sweep is running: a stray variable in a user's environment does not reconfigure the product.

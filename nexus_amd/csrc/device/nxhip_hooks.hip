@@ -179,7 +179,7 @@ static int bsdf_hook(nxhip_ctx* c, const nx_material* material, const nx_bsdf_qu
 {
     NX_CHECK_CTX(c);
     if (!material || (!queries && count) || (!results && count)) return fail_invalid("nxhip_bsdf_*_batch: null buffer");
-    if (material->type < NX_MAT_DIFFUSE || material->type > NX_MAT_CONDUCTOR) return fail_invalid("nxhip_bsdf_*_batch: unknown material type");
+    if (material->type < NX_MAT_DIFFUSE || material->type > NX_MAT_METALROUGH) return fail_invalid("nxhip_bsdf_*_batch: unknown material type");
     if (count == 0) return NXHIP_OK;
     NX_HIP(hipSetDevice(c->device));
     DevBuf dMat, dQ, dR;
@@ -188,7 +188,8 @@ static int bsdf_hook(nxhip_ctx* c, const nx_material* material, const nx_bsdf_qu
     NX_ALLOC(dR, (size_t)count * sizeof(nx_bsdf_result));
     NX_HIP(hipMemcpy(dMat.p, material, sizeof(nx_material), hipMemcpyHostToDevice));
     NX_HIP(hipMemcpy(dQ.p, queries, (size_t)count * sizeof(nx_bsdf_query), hipMemcpyHostToDevice));
-    NX_HIP(launch_untimed(kernels::bsdf_hook(), c->wideBlocks, kWideBlockThreads, c->stream, dMat.as<nx_material>(), dQ.as<nx_bsdf_query>(), count, sample, dR.as<nx_bsdf_result>()));
+    // (NX_MAT_METALROUGH has a kernel of its own: nx_wavefront_metal.hip — the four reference types keep theirs)
+    NX_HIP(launch_untimed(material->type == NX_MAT_METALROUGH ? kernels::bsdf_hook_metal() : kernels::bsdf_hook(), c->wideBlocks, kWideBlockThreads, c->stream, dMat.as<nx_material>(), dQ.as<nx_bsdf_query>(), count, sample, dR.as<nx_bsdf_result>()));
     NX_SYNC_ALL(c);
     NX_HIP(hipMemcpy(results, dR.p, (size_t)count * sizeof(nx_bsdf_result), hipMemcpyDeviceToHost));
     return NXHIP_OK;
@@ -562,6 +563,38 @@ try {
     NX_HIP(hipMemcpy(fellBack, dF.p, (size_t)count * 4, hipMemcpyDeviceToHost));
     return NXHIP_OK;
 } NX_CATCH("nxhip_shading_frame_batch")
+
+int nxhip_material_inputs_batch(nxhip_ctx* c, uint32_t instanceIdx, const uint32_t* triIdx, const float* hitUv, uint32_t count, float* out)
+try {
+    NX_DEBUG_HOOK("nxhip_material_inputs_batch");  // (first: a release library refuses whatever it is handed)
+    NX_CHECK_CTX(c);
+    if ((!triIdx || !hitUv || !out) && count) return fail_invalid("nxhip_material_inputs_batch: null buffer");
+    NX_HIP(hipSetDevice(c->device));
+    NX_TRY(check_scene_ready(c));
+    if (instanceIdx >= c->hostInstances.size()) return fail_invalid("nxhip_material_inputs_batch: no such instance");
+    // the triangle index is followed without a bounds test on the device, as a hit record's is: checked here
+    const nx_bvh_instance& inst = c->hostInstances[instanceIdx];
+    if (inst.bvhIdx >= c->blas.size()) return fail_invalid("nxhip_material_inputs_batch: the instance refers to a BLAS id that has not been uploaded");
+    if (c->hostMaterials[(size_t)inst.materialId].type != NX_MAT_METALROUGH) return fail_invalid("nxhip_material_inputs_batch: the instance's material is not an NX_MAT_METALROUGH");
+    const uint32_t triCount = c->blas[inst.bvhIdx].triCount;
+    for (uint32_t k = 0; k < count; k++)
+        if (triIdx[k] >= triCount) return fail_invalid("nxhip_material_inputs_batch: triangle index out of range");
+    if (count == 0) return NXHIP_OK;
+    NX_TRY(refresh_updated_blas(c));
+    if (c->shadeInstDirty) NX_TRY(refresh_shade_inst(c));
+    NX_TRY(upload_state(c));
+    DevBuf dTri, dUv, dOut;
+    NX_ALLOC(dTri, (size_t)count * 4);
+    NX_ALLOC(dUv, (size_t)count * 8);
+    NX_ALLOC(dOut, (size_t)count * 20);
+    NX_HIP(hipMemcpy(dTri.p, triIdx, (size_t)count * 4, hipMemcpyHostToDevice));
+    NX_HIP(hipMemcpy(dUv.p, hitUv, (size_t)count * 8, hipMemcpyHostToDevice));
+    NX_HIP(launch_untimed(kernels::material_inputs_hook(), c->wideBlocks, kWideBlockThreads, c->stream, c->dState.as<DeviceState>(), instanceIdx, dTri.as<uint32_t>(), dUv.as<float>(), count,
+                          dOut.as<float>()));
+    NX_SYNC_ALL(c);
+    NX_HIP(hipMemcpy(out, dOut.p, (size_t)count * 20, hipMemcpyDeviceToHost));
+    return NXHIP_OK;
+} NX_CATCH("nxhip_material_inputs_batch")
 
 int nxhip_fmath_batch(nxhip_ctx* c, int op, const double* a, const double* b, uint32_t count, double* out)
 {

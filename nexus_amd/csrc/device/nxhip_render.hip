@@ -236,6 +236,12 @@ constexpr int kFlavorMedium = 8192;
 // collisions by a walk over majorant bricks.  Set iff a medium with sigmaT > 0 AND a grid are set (the state block names the grid only then:
 // refresh_medium_grid); never without kFlavorMedium.
 constexpr int kFlavorMediumGrid = 16384;
+// kFlavorMetal: some material of the table is an NX_MAT_METALROUGH (nxhip_set_materials) — the SCAN pipeline's material launch and the tail
+// kernel are their METAL instances (nx_wavefront_metal.hip), the only ones that hold the fifth type's case; they are DETAIL instances too
+// (the type's metalness comes with the roughness map's lookup), so the bit implies the general material launch.  Without such a
+// material the bit is clear and the graphs are what they were, launch for launch.
+constexpr int kFlavorMetal = 32768;
+inline bool materials_metal(const nxhip_ctx* c) { return ((c->materialTypeMask >> NX_MAT_METALROUGH) & 1u) != 0u; }
 int pass_flavor(const nxhip_ctx* c)
 {
     int f = 0;
@@ -267,7 +273,8 @@ int pass_flavor(const nxhip_ctx* c)
     if (!c->statsEnabled && c->passesInFlight <= 1u) f |= kFlavorThin;  // (the caller's setting, not effective_slots(): a timing replay of a run with passes in flight keeps that run's kernels)
     if ((c->h.sceneFlags & kSceneAllIdentity) && !c->statsEnabled) f |= kFlavorIdentity;  // (the counting variants have no such instance)
     if (c->materialsNameDetail) f |= kFlavorDetail;
-    if (scan_pipeline(c) && !c->materialsNameMaps && !(f & kFlavorEnvMap) && !(f & kFlavorDetail)) f |= kFlavorNoMaps;
+    if (materials_metal(c)) f |= kFlavorMetal;
+    if (scan_pipeline(c) && !c->materialsNameMaps && !(f & kFlavorEnvMap) && !(f & kFlavorDetail) && !(f & kFlavorMetal)) f |= kFlavorNoMaps;
     if (c->h.alightCount) f |= kFlavorAnalytic;
     if (transmit_active(c)) f |= kFlavorTransmit;
     if (c->h.mediumOn) f |= kFlavorMedium;
@@ -304,6 +311,7 @@ std::vector<std::vector<Launch>> frame_levels(nxhip_ctx* c, PassSlot* q)
     const bool identity = (pass_flavor(c) & kFlavorIdentity) != 0, noMaps = (pass_flavor(c) & kFlavorNoMaps) != 0;
     const bool analytic = (pass_flavor(c) & kFlavorAnalytic) != 0;
     const bool transmit = (pass_flavor(c) & kFlavorTransmit) != 0;
+    const bool metal = (pass_flavor(c) & kFlavorMetal) != 0;
     const bool detail = (pass_flavor(c) & kFlavorDetail) != 0;
     const bool medium = (pass_flavor(c) & kFlavorMedium) != 0;
     const bool mediumGrid = (pass_flavor(c) & kFlavorMediumGrid) != 0;
@@ -315,9 +323,12 @@ std::vector<std::vector<Launch>> frame_levels(nxhip_ctx* c, PassSlot* q)
     const int traceBlocks = trace_blocks(c, c->traceBlocks), shadowBlocks = trace_blocks(c, c->shadowBlocks);
     // (the dry waves of a pass's trace launches may hand their last long rays to the thin kernel: nx_trace.hip)
     const int thinFlag = (pass_flavor(c) & kFlavorThin) ? kTraceThinFlag : 0;
+    // (the thin kernel's one-lane replay of a closest-hit ray names the hit's SCAN code itself, for the four reference types: the closest-hit
+    //  launches of a SCAN pass with the fifth type hand nothing over; its any-hit launches do, and so does the classic pipeline, which has no codes)
+    const int thinFlagClosest = (metal && scan_pipeline(c)) ? 0 : thinFlag;
     // (with entry points the primary launch is its own kernel instance: the only one that carries the install code)
     levels.push_back({make_launch((entry && !stats) ? kernels::trace_entry(identity) : kernels::trace(false, stats, identity), traceBlocks, kTraceBlockThreads, NXHIP_K_TRACE, S,
-                                  (entry ? kTraceEntryFlag : 0) | thinFlag | (scan_pipeline(c) ? kTraceScanFlag : 0))});
+                                  (entry ? kTraceEntryFlag : 0) | thinFlagClosest | (scan_pipeline(c) ? kTraceScanFlag : 0))});
     // behind the trace launch(es) of a level: the rays their dry waves handed over, a wave each (thin_kernel)
     // — each trace launch of the level gets its own, chained to it alone, so that the closest-hit rays' searches run beside whatever
     // the any-hit launch still has to do (it is the longer one of the early levels) and the other way round in the late ones
@@ -331,6 +342,7 @@ std::vector<std::vector<Launch>> frame_levels(nxhip_ctx* c, PassSlot* q)
         for (int k = 0; k < n; k++) {
             const bool closest = level[(size_t)k].klass == NXHIP_K_TRACE;
             if (!closest && level[(size_t)k].klass != NXHIP_K_SHADOW) continue;  // (the medium's launch in front of the any-hit launch hands nothing over)
+            if (closest && !thinFlagClosest) continue;  // (nothing was handed over)
             if (!closest && transmit) continue;  // (no kThinAnyOnly launch: the TRANSMIT any-hit launch lists nothing)
             Launch t = make_launch(kernels::thin(), thinBlocks, kTraceBlockThreads, NXHIP_K_THIN, S, bounceArg | (closest ? kThinClosestOnly : kThinAnyOnly));
             t.after = k;
@@ -362,16 +374,17 @@ std::vector<std::vector<Launch>> frame_levels(nxhip_ctx* c, PassSlot* q)
         const int tailFrom = tail_bounce(c);
         for (int bounce = 1; bounce <= pathLength; bounce++) {
             if (bounce == tailFrom) {  // the rest of the pass in one launch
-                levels.push_back({make_launch(kernels::tail(lightPower, analytic, detail), detail ? c->tailBlocksDetail[lightPower ? 1 : 0][analytic ? 1 : 0] : analytic ? c->tailBlocksAnalytic[lightPower ? 1 : 0] : (lightPower ? c->tailBlocksPower : c->tailBlocks), kTraceBlockThreads, NXHIP_K_SHADE, S, bounce | kTraceScanFlag)});
+                levels.push_back({make_launch(kernels::tail(lightPower, analytic, detail, metal), metal ? c->tailBlocksMetal[lightPower ? 1 : 0][analytic ? 1 : 0] : detail ? c->tailBlocksDetail[lightPower ? 1 : 0][analytic ? 1 : 0] : analytic ? c->tailBlocksAnalytic[lightPower ? 1 : 0] : (lightPower ? c->tailBlocksPower : c->tailBlocks), kTraceBlockThreads, NXHIP_K_SHADE, S, bounce | kTraceScanFlag)});
                 break;
             }
             int mask = (int)(c->materialTypeMask & 0xfu);
             if (c->h.conductorMode != NX_CONDUCTOR_EXTENDED) mask &= ~(1 << NX_MAT_CONDUCTOR);
             if (mask == 0) mask = 1 << NX_MAT_DIFFUSE;  // (a level cannot be empty)
             if (misses) mask |= 1 << kScanMiss;
+            if (metal) mask |= 1 << kScanMetalBit;  // (the type's own number is the misses' bit: nx_device.h)
             // the medium's free-flight decision over the records the closest-hit level left, in front of the material launch that reads them
-            if (medium) levels.push_back({make_launch(mediumGrid ? kernels::medium_scatter_grid(lightPower, analytic) : kernels::medium_scatter(lightPower, analytic), whole_regions(wide), kShadeBlockThreads, NXHIP_K_SHADE, S, bounce | dropFlag)});
-            levels.push_back({make_launch(kernels::shade_scan(lightPower, noMaps, analytic, detail), og, kShadeBlockThreads, NXHIP_K_SHADE, S, bounce | dropFlag, mask)});
+            if (medium) levels.push_back({make_launch(mediumGrid ? kernels::medium_scatter_grid(lightPower, analytic, metal) : kernels::medium_scatter(lightPower, analytic, metal), whole_regions(wide), kShadeBlockThreads, NXHIP_K_SHADE, S, bounce | dropFlag)});
+            levels.push_back({make_launch(kernels::shade_scan(lightPower, noMaps, analytic, detail, metal), og, kShadeBlockThreads, NXHIP_K_SHADE, S, bounce | dropFlag, mask)});
             if (bounce == 1) aov_beside(levels.back());
             if (in_use(NX_MAT_CONDUCTOR) && c->h.conductorMode != NX_CONDUCTOR_EXTENDED) {  // (counted, not shaded: count_scan_kernel)
                 levels.push_back({make_launch(kernels::count_scan(), lg, kWideBlockThreads, NXHIP_K_LOGIC, S, bounce, NX_MAT_CONDUCTOR)});
@@ -380,10 +393,10 @@ std::vector<std::vector<Launch>> frame_levels(nxhip_ctx* c, PassSlot* q)
                 // the shadow requests' attenuation is chained to the any-hit launch alone: the closest-hit launch of the level does not wait for it
                 Launch anyHit = shadow_launch(shadowBlocks, bounce, thinFlag);
                 anyHit.after = 1;
-                levels.push_back({make_launch(kernels::trace(false, stats, identity), traceBlocks, kTraceBlockThreads, NXHIP_K_TRACE, S, bounce | kTraceScanFlag | thinFlag),
+                levels.push_back({make_launch(kernels::trace(false, stats, identity), traceBlocks, kTraceBlockThreads, NXHIP_K_TRACE, S, bounce | kTraceScanFlag | thinFlagClosest),
                                   make_launch(mediumGrid ? kernels::medium_shadow_grid() : kernels::medium_shadow(), wide, wideThreads, NXHIP_K_SHADE, S, bounce), anyHit});
             } else {
-                levels.push_back({make_launch(kernels::trace(false, stats, identity), traceBlocks, kTraceBlockThreads, NXHIP_K_TRACE, S, bounce | kTraceScanFlag | thinFlag),
+                levels.push_back({make_launch(kernels::trace(false, stats, identity), traceBlocks, kTraceBlockThreads, NXHIP_K_TRACE, S, bounce | kTraceScanFlag | thinFlagClosest),
                                   shadow_launch(shadowBlocks, bounce, thinFlag)});
             }
             thin_level(bounce | kTraceScanFlag);
@@ -400,6 +413,8 @@ std::vector<std::vector<Launch>> frame_levels(nxhip_ctx* c, PassSlot* q)
         // the same test as pass_flavor's kFlavorEnvMap (hdrMap.texels is set for both kinds: nxhip_scene.hip).
         levels.push_back({make_launch(kernels::logic(c->hdrMap.texels.p ? 1 : 2, analytic), lg, lb, NXHIP_K_LOGIC, S, bounce)});
         if (bounce == 1) aov_beside(levels.back());
+        // (the fifth type's queue is filled by a kernel of its own behind the reference's logic kernel: nx_wavefront_metal.hip)
+        if (metal) levels.push_back({make_launch(kernels::logic_metal(), lg, lb, NXHIP_K_LOGIC, S, bounce)});
         // graph insertion order of the reference: Diffuse, Plastic, Dielectric, Conductor (PathTracer.cpp:116-120)
         // (only the types some material of the scene has: a queue no material feeds stays empty)
         std::vector<Launch> shade;
@@ -407,6 +422,7 @@ std::vector<std::vector<Launch>> frame_levels(nxhip_ctx* c, PassSlot* q)
         if (in_use(NX_MAT_PLASTIC)) shade.push_back(make_launch(kernels::shade(NX_MAT_PLASTIC, lightPower, analytic, detail), og, ob, NXHIP_K_SHADE, S, bounce));
         if (in_use(NX_MAT_DIELECTRIC)) shade.push_back(make_launch(kernels::shade(NX_MAT_DIELECTRIC, lightPower, analytic, detail), og, ob, NXHIP_K_SHADE, S, bounce));
         if (in_use(NX_MAT_CONDUCTOR) && c->h.conductorMode == NX_CONDUCTOR_EXTENDED) shade.push_back(make_launch(kernels::shade(NX_MAT_CONDUCTOR, lightPower, analytic, detail), og, ob, NXHIP_K_SHADE, S, bounce));
+        if (metal) shade.push_back(make_launch(kernels::shade_metal(lightPower, analytic), og, ob, NXHIP_K_SHADE, S, bounce));  // (after the reference's four)
         if (shade.empty()) shade.push_back(make_launch(kernels::shade(NX_MAT_DIFFUSE, lightPower, analytic, detail), og, ob, NXHIP_K_SHADE, S, bounce));  // (a level cannot be empty)
         // serial slot order needs the kernels one after the other
         for (auto& l : shade) levels.push_back({l});
@@ -636,6 +652,10 @@ try {
     NX_TRY(refresh_light_table(c));   // (NXHIP_LIGHTS_POWER: lights, materials, instances or meshes changed)
     if (!slot_queues_ready(c, q)) {
         NX_TRY(ensure_slot_queues(c, q));
+        NX_TRY(upload_state(c));
+    }
+    if (materials_metal(c) && !scan_pipeline(c)) {  // the classic pipeline's fifth material queue
+        NX_TRY(ensure_metal_queue(c, q));
         NX_TRY(upload_state(c));
     }
     if (c->aov) {  // the slot's feature buffers, as large as its queues
@@ -1179,6 +1199,23 @@ int nxhip_read_queue_sizes(nxhip_ctx* c, nxhip_queue_sizes* out)
             out->dielectricSize[b] += r.materialSize[NX_MAT_DIELECTRIC][b];
             out->conductorSize[b] += r.materialSize[NX_MAT_CONDUCTOR][b];
         }
+    return NXHIP_OK;
+}
+
+int nxhip_read_material_queue_sizes(nxhip_ctx* c, int type, int32_t* out)
+{
+    NX_CHECK_CTX(c);
+    if (!out) return fail_invalid("nxhip_read_material_queue_sizes: null destination");
+    if (type < NX_MAT_DIFFUSE || type > NX_MAT_METALROUGH) return fail_invalid("nxhip_read_material_queue_sizes: unknown material type");
+    NX_HIP(hipSetDevice(c->device));
+    NX_SYNC_ALL(c);
+    Counters h;
+    NX_HIP(hipMemcpy(&h, (c->lastRendered ? c->lastRendered : static_cast<PassSlot*>(c))->counters.p, sizeof h, hipMemcpyDeviceToHost));
+    for (int b = 0; b < kMaxBounceSlots; b++) {
+        out[b] = 0;
+        for (int k = 0; k < kQueueShards; k++)  // a queue's size = the sum over its regions
+            out[b] += type == NX_MAT_METALROUGH ? h.region[k].materialSizeMetal[b] : h.region[k].materialSize[type][b];
+    }
     return NXHIP_OK;
 }
 

@@ -161,12 +161,15 @@ int nxd::refresh_shade_inst(nxhip_ctx* c)
     NX_HIP(hipMemcpy(c->shadeInst.p, rec.data(), rec.size() * sizeof(ShadeInst), hipMemcpyHostToDevice));
     c->h.shadeInst = c->shadeInst.as<ShadeInst>();
     // the parallel array of detail records: entry i = the detail record of instance i's material; none while there is no table
-    if (c->hostMaterialDetail.empty()) {
+    // (... unless a material is an NX_MAT_METALROUGH: its kernels are DETAIL instances and read the array, which then names no map)
+    const bool metal = ((c->materialTypeMask >> NX_MAT_METALROUGH) & 1u) != 0u;
+    if (c->hostMaterialDetail.empty() && !metal) {
         c->shadeDetail = DevBuf();
         c->h.shadeDetail = nullptr;
     } else {
         std::vector<nx_material_detail> det(std::max<size_t>(1, n), nx_material_detail{-1, -1, 1.0f, 0u});
-        for (size_t i = 0; i < n; i++) det[i] = c->hostMaterialDetail[(size_t)rec[i].materialId];
+        if (!c->hostMaterialDetail.empty())
+            for (size_t i = 0; i < n; i++) det[i] = c->hostMaterialDetail[(size_t)rec[i].materialId];
         NX_ALLOC(c->shadeDetail, det.size() * sizeof(nx_material_detail));
         NX_HIP(hipMemcpy(c->shadeDetail.p, det.data(), det.size() * sizeof(nx_material_detail), hipMemcpyHostToDevice));
         c->h.shadeDetail = c->shadeDetail.as<nx_material_detail>();
@@ -177,7 +180,7 @@ int nxd::refresh_shade_inst(nxhip_ctx* c)
     if (c->instTrav.p && !c->hostInstIdx.empty()) {
         entry_inputs_changed(c);  // (an entry state carries its instance's index + material code: InstTrav::instIdx)
         const uint32_t count = (uint32_t)c->hostInstIdx.size();
-        NX_HIP(launch_untimed(kernels::inst_code(), (count + 255u) / 256u, 256, c->stream, c->dState.as<DeviceState>(), c->instTrav.as<InstTrav>(), c->shadeInst.as<ShadeInst>(), count));
+        NX_HIP(launch_untimed(kernels::inst_code(metal), (count + 255u) / 256u, 256, c->stream, c->dState.as<DeviceState>(), c->instTrav.as<InstTrav>(), c->shadeInst.as<ShadeInst>(), count));
         NX_HIP(hipStreamSynchronize(c->stream));
     }
     return NXHIP_OK;
@@ -885,7 +888,7 @@ try {
     c->lightTableDirty = true;
     uint32_t mask = 0u;
     for (const nx_material& m : dev)
-        if (m.type >= 0 && m.type <= 3) mask |= 1u << m.type;
+        if (m.type >= NX_MAT_DIFFUSE && m.type <= NX_MAT_METALROUGH) mask |= 1u << m.type;
     if (mask != c->materialTypeMask) {  // the pass graphs hold one material kernel per type in use
         c->materialTypeMask = mask;
         invalidate_graph(c);

@@ -283,7 +283,7 @@ void set_albedo_like(Material& m, const double rgb[3], double roughness, double 
 }
 
 // OBJLoader.cpp:71-163 through Assimp's glTF importer
-Material gltf_material(const Json& m)
+Material gltf_material(const Json& m, const LoadOptions& options)
 {
     static const Json empty;
     const Json* pbr = m.find("pbrMetallicRoughness");
@@ -306,6 +306,12 @@ Material gltf_material(const Json& m)
     Material out;
     out.type = transmission > 0.0 ? NX_MAT_DIELECTRIC : NX_MAT_PLASTIC;
     set_albedo_like(out, base, roughness, ior);
+    if (options.metalRough && !(transmission > 0.0)) {
+        // glTF's own model (LoadOptions::metalRough): the raw factors, the spec's defaults
+        out.type = NX_MAT_METALROUGH;
+        set_albedo_like(out, base, rough, ext_number("KHR_materials_ior", "ior", 1.5));
+        out.metalrough.metallic = static_cast<float>(pbr ? pbr->number("metallicFactor", 1.0) : 1.0);
+    }
     if (const Json* e = m.find("emissiveFactor"))
         for (size_t k = 0; k < 3 && k < e->size(); k++) out.emissive[k] = static_cast<float>(e->at(k).num);
     out.intensity = static_cast<float>(ext_number("KHR_materials_emissive_strength", "emissiveStrength", 1.0));
@@ -341,7 +347,7 @@ struct Accessor {
     }
 };
 
-LoadedScene parse_glb(const std::string& file)
+LoadedScene parse_glb(const std::string& file, const LoadOptions& options)
 {
     const std::vector<unsigned char> data = read_file(file);
     if (data.size() < 20 || rd32(data, 0) != 0x46546C67u || rd32(data, 4) != 2u) fail(file + " is not a glTF 2.0 binary file");
@@ -417,7 +423,7 @@ LoadedScene parse_glb(const std::string& file)
     if (const Json* mats = doc.find("materials"))
         for (size_t i = 0; i < mats->size(); i++) {
             const Json& m = mats->at(i);
-            out.materials.push_back(gltf_material(m));
+            out.materials.push_back(gltf_material(m, options));
             int dt = -1, et = -1;
             if (const Json* pbr = m.find("pbrMetallicRoughness"))
                 if (const Json* t = pbr->find("baseColorTexture")) dt = load_texture(*t, Texture::Type::DIFFUSE);
@@ -678,16 +684,16 @@ bool ends_with(const std::string& s, const char* suffix)
 
 }  // namespace
 
-LoadedScene OBJLoader::Parse(const std::string& file)
+LoadedScene OBJLoader::Parse(const std::string& file, const LoadOptions& options)
 {
-    if (ends_with(file, ".glb")) return parse_glb(file);
+    if (ends_with(file, ".glb")) return parse_glb(file, options);
     if (ends_with(file, ".obj")) return parse_obj(file);
     fail("unsupported file type (only .glb and .obj): " + file);
 }
 
-void OBJLoader::LoadOBJ(const std::string& path, const std::string& filename, Scene* scene, AssetManager* assetManager)
+void OBJLoader::LoadOBJ(const std::string& path, const std::string& filename, Scene* scene, AssetManager* assetManager, const LoadOptions& options)
 {
-    const LoadedScene ls = Parse(path + filename);
+    const LoadedScene ls = Parse(path + filename, options);
     const int materialBase = static_cast<int>(assetManager->GetMaterials().size());
     // textures first: a material carries the id its map got in the manager's diffuse / emissive list (OBJLoader.cpp:134-135, 157-158)
     std::vector<int> textureIds(ls.textures.size(), -1);

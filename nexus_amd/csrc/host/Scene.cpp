@@ -120,7 +120,9 @@ MeshInstance& Scene::CreateMeshInstance(uint32_t meshId)
 
 void Scene::CreateMeshInstanceFromFile(const std::string& path, const std::string& fileName)
 {
-    OBJLoader::LoadOBJ(path, fileName, this, &m_AssetManager);
+    LoadOptions options;
+    options.metalRough = m_MetalRoughMaterials;
+    OBJLoader::LoadOBJ(path, fileName, this, &m_AssetManager, options);
     Invalidate();  // the TLAS is rebuilt by the next Update()
 }
 

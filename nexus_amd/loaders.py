@@ -312,7 +312,7 @@ def decode_png(data):
     return out, channels
 
 
-def _gltf_material(m):
+def _gltf_material(m, metal_rough=False):
     pbr = m.get("pbrMetallicRoughness", {})
     ext = m.get("extensions", {})
     base = pbr.get("baseColorFactor", [1, 1, 1, 1])
@@ -324,11 +324,17 @@ def _gltf_material(m):
     mtype = pod.MAT_DIELECTRIC if transmission > 0.0 else pod.MAT_PLASTIC
     emissive = m.get("emissiveFactor", [0, 0, 0])
     intensity = float(ext.get("KHR_materials_emissive_strength", {}).get("emissiveStrength", 1.0))
+    if metal_rough and not transmission > 0.0:
+        # glTF's own model: the raw factors, the spec's defaults (nexus/OBJLoader.h LoadOptions::metalRough)
+        return pod.make_material(type=pod.MAT_METALROUGH, albedo=base[:3], roughness=rough, ior=float(ext.get("KHR_materials_ior", {}).get("ior", 1.5)),
+                                 metallic=float(pbr.get("metallicFactor", 1.0)), emissive=emissive, intensity=intensity, opacity=float(base[3]) if len(base) > 3 else 1.0)
     return pod.make_material(type=mtype, albedo=base[:3], roughness=roughness, ior=ior, emissive=emissive, intensity=intensity,
                              opacity=float(base[3]) if len(base) > 3 else 1.0)
 
 
-def load_glb(path):
+def load_glb(path, metal_rough=False):
+    """metal_rough (off by default: glTF's default metallicFactor is 1): materials without transmission become MAT_METALROUGH with the
+    file's raw factors instead of the reference's PLASTIC"""
     data = open(path, "rb").read()
     magic, version, _length = struct.unpack_from("<III", data, 0)
     if magic != 0x46546C67 or version != 2:
@@ -405,7 +411,7 @@ def load_glb(path):
     if not doc.get("materials"):
         out.material_diffuse_texture, out.material_emissive_texture = [-1], [-1]
         out.material_normal_texture, out.material_roughness_texture, out.material_normal_scale = [-1], [-1], [1.0]
-    mats = [_gltf_material(m) for m in doc.get("materials", [])]
+    mats = [_gltf_material(m, metal_rough) for m in doc.get("materials", [])]
     out.material_names = [m.get("name", "") for m in doc.get("materials", [])]
     out.materials = np.array(mats, dtype=pod.MAT_DT) if mats else np.array([pod.make_material()], dtype=pod.MAT_DT)
 

@@ -115,6 +115,7 @@ ADAPTIVE_DT = np.dtype([("threshold", "<f4"), ("lumFloor", "<f4"), ("minSamples"
 assert ADAPTIVE_DT.itemsize == 16
 
 MAT_DIFFUSE, MAT_DIELECTRIC, MAT_PLASTIC, MAT_CONDUCTOR = 0, 1, 2, 3
+MAT_METALROUGH = 4  # an extension: glTF's metallic-roughness model (include/nexus_hip.h)
 LIGHT_POINT, LIGHT_AREA, LIGHT_MESH = 0, 1, 2
 ALIGHT_POINT, ALIGHT_SPOT, ALIGHT_DIRECTIONAL = 0, 1, 2  # nx_analytic_light.type
 RNG_REFERENCE_SLOT, RNG_PIXEL_KEYED = 0, 1
@@ -150,7 +151,8 @@ def make_triangles(pos, normals=None, uvs=None):
 
 
 def make_material(type=MAT_DIFFUSE, albedo=(0.8, 0.8, 0.8), roughness=0.0, ior=1.45, emissive=(0, 0, 0), intensity=0.0,
-                  opacity=1.0, conductor_ior=None, conductor_k=None, diffuse_map=-1, emissive_map=-1):
+                  opacity=1.0, conductor_ior=None, conductor_k=None, diffuse_map=-1, emissive_map=-1, metallic=None):
+    """metallic: NX_MAT_METALROUGH only (byte 20 of the union; default 1, glTF's)"""
     m = np.zeros((), dtype=MAT_DT)
     if type == MAT_CONDUCTOR:
         m["u"][0:3] = conductor_ior if conductor_ior is not None else (0.2, 0.9, 1.1)
@@ -160,6 +162,8 @@ def make_material(type=MAT_DIFFUSE, albedo=(0.8, 0.8, 0.8), roughness=0.0, ior=1
         m["u"][0:3] = albedo
         m["u"][3] = roughness
         m["u"][4] = ior
+        if type == MAT_METALROUGH:
+            m["u"][5] = 1.0 if metallic is None else metallic
     m["emissive"] = emissive
     m["intensity"] = intensity
     m["opacity"] = opacity
