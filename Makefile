@@ -55,6 +55,8 @@ $(OBJDIR)/%.o: %.hip $(HDRS)
 $(OBJDIR)/nexus_amd/csrc/device/nx_wavefront_detail.o: nexus_amd/csrc/device/nx_wavefront.hip
 # (... and the METAL instances: nx_wavefront_metal.hip)
 $(OBJDIR)/nexus_amd/csrc/device/nx_wavefront_metal.o: nexus_amd/csrc/device/nx_wavefront.hip
+# (... and the SOLID instances: nx_wavefront_solid.hip)
+$(OBJDIR)/nexus_amd/csrc/device/nx_wavefront_solid.o: nexus_amd/csrc/device/nx_wavefront.hip
 # (... and so are the medium's kernels, which call its device functions)
 $(OBJDIR)/nexus_amd/csrc/device/nx_medium.o: nexus_amd/csrc/device/nx_wavefront.hip
 

@@ -2,7 +2,7 @@
 // through the kept C++ host API: load a .glb / .obj, path-trace `frames` frames on an MI355X, write the image as a PPM.
 //
 //   nexus_render [--denoise] [--adaptive THRESHOLD [--max-frames N]] [--light-sampling uniform|power] [--transparent-shadows] [--env-float FILE.hdr] [--env-sampling]
-//                [--no-detail-maps] [--metal-rough] [--fog SIGMA [--fog-albedo R G B] [--fog-g G] [--fog-box X0 Y0 Z0 X1 Y1 Z1] [--fog-grid FILE.npy]]
+//                [--no-detail-maps] [--metal-rough] [--alpha-modes] [--fog SIGMA [--fog-albedo R G B] [--fog-g G] [--fog-box X0 Y0 Z0 X1 Y1 Z1] [--fog-grid FILE.npy]]
 //                [--point-light X Y Z INTENSITY] [--sun DX DY DZ IRRADIANCE] <dir/> <file.glb|file.obj> <out.ppm> [width height frames pathLength]
 //                [eyeX eyeY eyeZ fwdX fwdY fwdZ hfovDeg]
 // --denoise: the feature buffers are accumulated with the colour and the image written is the a-trous filtered one (nxhip_denoise)
@@ -19,6 +19,8 @@
 // A .glb's KHR_lights_punctual lights (point, spot, directional) are rendered as the file places them, without a flag.
 // A .glb's normalTexture and metallicRoughnessTexture (its G channel: roughness) are used as the file's materials name them, without a flag.
 // --no-detail-maps: drop them (AssetManager::ClearMaterialDetails), for an A/B against the flat, uniformly glossy surfaces.
+// --alpha-modes: a .glb's alphaMode / alphaCutoff are honoured (Scene::SetMaterialAlphaModes): MASK cutouts are holes for camera, bounce and
+// shadow rays and for the feature buffers, OPAQUE ignores an unused alpha channel; without it alpha is a stochastic blend, as before.
 // --metal-rough: a .glb's materials are read as glTF's own metallic-roughness model (Scene::SetMetalRoughMaterials: metallicFactor, the raw
 //   roughnessFactor, the B channel of the metallic-roughness texture) instead of the reference's plastic.
 // --point-light X Y Z INTENSITY: one more white point light at (X, Y, Z), radiant intensity INTENSITY per steradian (Scene::AddAnalyticLight).
@@ -53,6 +55,7 @@ int main(int argc, char** argv)
     bool envSampling = false;
     bool detailMaps = true;
     bool metalRough = false;
+    bool alphaModes = false;
     std::vector<nexus::AnalyticLight> extraLights;
     bool fog = false, fogBox = false;
     nexus::Medium medium;
@@ -93,6 +96,9 @@ int main(int argc, char** argv)
         } else if (opt == "--metal-rough") {
             metalRough = true;
             used = 1;
+        } else if (opt == "--alpha-modes") {
+            alphaModes = true;
+            used = 1;
         } else if (opt == "--fog" && argc > 2) {
             fog = true;
             medium.sigmaT = static_cast<float>(std::atof(argv[2]));
@@ -132,7 +138,7 @@ int main(int argc, char** argv)
         return 2;
     }
     if (argc < 4) {
-        std::fprintf(stderr, "usage: %s [--denoise] [--adaptive THRESHOLD [--max-frames N]] [--light-sampling uniform|power] [--transparent-shadows] [--env-float FILE.hdr] [--env-sampling] [--no-detail-maps] [--fog SIGMA [--fog-albedo R G B] [--fog-g G] [--fog-box X0 Y0 Z0 X1 Y1 Z1] [--fog-grid FILE.npy]] [--point-light X Y Z INTENSITY] [--sun DX DY DZ IRRADIANCE] <dir/> <file.glb|file.obj> <out.ppm> [width height frames pathLength] [eye(3) forward(3) hfov]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s [--denoise] [--adaptive THRESHOLD [--max-frames N]] [--light-sampling uniform|power] [--transparent-shadows] [--env-float FILE.hdr] [--env-sampling] [--no-detail-maps] [--metal-rough] [--alpha-modes] [--fog SIGMA [--fog-albedo R G B] [--fog-g G] [--fog-box X0 Y0 Z0 X1 Y1 Z1] [--fog-grid FILE.npy]] [--point-light X Y Z INTENSITY] [--sun DX DY DZ IRRADIANCE] <dir/> <file.glb|file.obj> <out.ppm> [width height frames pathLength] [eye(3) forward(3) hfov]\n", argv[0]);
         return 2;
     }
     // a program built against these headers and run with another build of libnexus_amd.so gets an error string here, not a GPU fault
@@ -160,6 +166,7 @@ int main(int argc, char** argv)
             scene.SetDeviceTlasBuild(true);
         }
         scene.SetMetalRoughMaterials(metalRough);
+        scene.SetMaterialAlphaModes(alphaModes);
         scene.CreateMeshInstanceFromFile(dir, file);  // (a .glb's KHR_lights_punctual lights come with it)
         if (!detailMaps) scene.GetAssetManager().ClearMaterialDetails();  // (the file's normal and roughness maps: loaded, not used)
         for (const nexus::AnalyticLight& l : extraLights) scene.AddAnalyticLight(l);

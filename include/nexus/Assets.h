@@ -164,6 +164,12 @@ public:
     void SetMaterialDetail(int materialId, const MaterialDetail& detail);
     void ClearMaterialDetails();
     std::vector<MaterialDetail> GetMaterialDetails() const;
+    // Extension: how the alpha of material `materialId` is read (nx_material_alpha: NX_ALPHA_BLEND / MASK + cutoff / OPAQUE; the rule:
+    // nexus_hip.h, nxhip_set_material_alpha; throws on an id that does not exist).  GetMaterialAlphas: one record per material — materials
+    // never given one are BLEND — or empty while no material was ever given one, or after ClearMaterialAlphas (count 0 on the device).
+    void SetMaterialAlpha(int materialId, const nx_material_alpha& alpha);
+    void ClearMaterialAlphas();
+    std::vector<nx_material_alpha> GetMaterialAlphas() const;
     const std::vector<Texture>& GetNormalMaps() const { return m_NormalMaps; }
     const std::vector<Texture>& GetRoughnessMaps() const { return m_RoughnessMaps; }
     void ApplyTextureToMaterial(int materialId, int diffuseMapId);
@@ -173,7 +179,7 @@ public:
     bool IsInvalid() const { return !m_InvalidMaterials.empty() || !m_DeformedBvhs.empty(); }
 
     // what the device still has to receive (consumed by PathTracer::UpdateDeviceScene)
-    bool materialsDirty = true, texturesDirty = true, detailsDirty = false;
+    bool materialsDirty = true, texturesDirty = true, detailsDirty = false, alphasDirty = false;
     size_t uploadedBvhs = 0;
     std::set<int32_t> deformedBvhs;  // changed by UpdateMeshTriangles and not yet sent through nxhip_update_blas
 
@@ -184,6 +190,7 @@ private:
     std::vector<Texture> m_DiffuseMaps, m_EmissiveMaps;
     std::vector<Texture> m_NormalMaps, m_RoughnessMaps;
     std::vector<MaterialDetail> m_MaterialDetails;  // sparse: shorter than m_Materials while later materials have none
+    std::vector<nx_material_alpha> m_MaterialAlphas;  // likewise
     std::vector<BVH8> m_Bvhs;
     std::vector<Mesh> m_Meshes;
     BlasBuilder m_BlasBuilder;

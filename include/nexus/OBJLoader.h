@@ -37,6 +37,9 @@ struct LoadedScene {
     std::vector<Texture> detailTextures;
     std::vector<int> materialNormalTexture, materialRoughnessTexture;
     std::vector<float> materialNormalScale;
+    // glTF alphaMode / alphaCutoff per material (nx_material_alpha of nexus_pod.h; the rule: nexus_hip.h) — filled only when asked for
+    // (LoadOptions::alphaModes), else empty: every material's alpha is a stochastic blend, as it has always been
+    std::vector<nx_material_alpha> materialAlpha;
     std::vector<AnalyticLight> analyticLights;  // glTF KHR_lights_punctual: one per node that carries a light, in world space
     std::vector<std::string> warnings;  // images that could not be decoded (the reference prints and carries on, IMGLoader.cpp:24-25)
 };
@@ -45,8 +48,13 @@ struct LoadedScene {
 // file into metal): a .glb material without transmission becomes an NX_MAT_METALROUGH — albedo = baseColorFactor.rgb, roughness =
 // roughnessFactor as it stands (default 1), metallic = metallicFactor (default 1), ior from KHR_materials_ior (default 1.5) —
 // instead of the reference's PLASTIC; a material with transmissionFactor > 0 stays the DIELECTRIC it is, and .obj files do not change.
+// alphaModes (off by default, so every existing scene renders as before): a .glb material's alphaMode — OPAQUE when the file says nothing,
+// glTF's default — and alphaCutoff (default 0.5) are read into LoadedScene::materialAlpha, and LoadOBJ hands them to the AssetManager
+// (SetMaterialAlpha).  A MASK material whose alphaCutoff lies outside [0, 1] is refused by the reader, with the material's number.  .obj files
+// carry no such mode: their materials stay blends.
 struct LoadOptions {
     bool metalRough = false;
+    bool alphaModes = false;
 };
 
 class OBJLoader {

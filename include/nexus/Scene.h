@@ -28,6 +28,11 @@ public:
     // (Material::Type::METALROUGH; OBJLoader.h LoadOptions::metalRough) instead of the reference's PLASTIC
     void SetMetalRoughMaterials(bool on) { m_MetalRoughMaterials = on; }
     bool GetMetalRoughMaterials() const { return m_MetalRoughMaterials; }
+    // Extension, off by default: the files loaded from here on hand their materials' glTF alphaMode / alphaCutoff to the AssetManager
+    // (OBJLoader.h LoadOptions::alphaModes; AssetManager::SetMaterialAlpha), and PathTracer::UpdateDeviceScene sends the table
+    // (nxhip_set_material_alpha): MASK cutouts are holes for every ray, OPAQUE ignores an unused alpha channel.  Off: alpha blends.
+    void SetMaterialAlphaModes(bool on) { m_MaterialAlphaModes = on; }
+    bool GetMaterialAlphaModes() const { return m_MaterialAlphaModes; }
     // Place mesh `meshId` (AssetManager::AddMesh) with the mesh's own transform and material; a light is derived if its
     // material emits.  The returned reference is valid until the next instance is created.
     MeshInstance& CreateMeshInstance(uint32_t meshId);
@@ -119,6 +124,7 @@ private:
     Medium m_Medium;
     bool m_HasMedium = false;
     bool m_MetalRoughMaterials = false;
+    bool m_MaterialAlphaModes = false;
     DensityGrid m_MediumDensity;
     std::shared_ptr<TLAS> m_Tlas;
 

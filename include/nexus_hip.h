@@ -360,13 +360,52 @@ int nxhip_set_light_sampling(nxhip_ctx *ctx, int mode);
  * In expectation this is the stochastic pass-through of the material kernels (pass probability 1 - o a, up to the 2^-23 granularity of
  * rng_next).  Deterministic: no random number is drawn, no random stream moves.  Limits: dielectrics block shadow rays as before (only
  * opacity and alpha count); a pass-through on the path side spends a bounce, a crossing of a shadow ray does not, so at the pathLength
- * cut-off the two strategies see one segment more or less; glTF alphaMode / alphaCutoff stay ignored.
+ * cut-off the two strategies see one segment more or less; glTF alphaMode MASK / alphaCutoff: nxhip_set_material_alpha, below.
  * The mode changes a pass only while some material of the table is see-through (opacity < 1, or a diffuse map with a texel of alpha <
  * 255): otherwise the default kernels run.  While it does, the any-hit launches do not hand rays to the thin kernel and the tail kernel
  * is off (nxhip_set_tail_bounce is ignored): restrictions of a first version.  Results do not depend on nxhip_enable_trace_stats.
  * May be switched at any time, also between accumulated frames.  Another mode: NXHIP_ERR_INVALID. */
 enum { NXHIP_SHADOWS_OPAQUE = 0, NXHIP_SHADOWS_TRANSMIT = 1 };
 int nxhip_set_shadow_transmittance(nxhip_ctx *ctx, int mode);
+/* Extension: alpha-tested geometry (glTF alphaMode MASK).  Without a table every material is read as a stochastic blend (above): the
+ * traversal accepts every carrier triangle, and the material step decides.  `alphas` runs index-parallel to the material table
+ * (nx_material_alpha of nexus_pod.h: mode, cutoff), like nx_material_detail; count 0 / NULL clears it.  Entries default to NX_ALPHA_BLEND,
+ * which is the behaviour without a table, bit for bit: an all-BLEND table and a cleared one launch the default kernels.
+ *   NX_ALPHA_MASK   every traversal test — closest hit and any hit — that accepts a triangle of an instance with such a material (the test
+ *                   of today: 0 < t < tmax, u, v inside) computes s = o x a, the o and a of NXHIP_SHADOWS_TRANSMIT exactly:
+ *                     o = the material's opacity clamped to [0, 1]; `!(opacity < 1)` counts as 1, a NaN included;
+ *                     a = 1 without a diffuse map, else the .w of the bilinear lookup of diffuseMaps[diffuseMapId] at the texture
+ *                         coordinates of the ORIGINAL triangle interpolated with the u, v of this very test.
+ *                   s < cutoff: the triangle is rejected as if the ray had missed it — the closest-hit search goes on with its hit
+ *                   distance unchanged, an any-hit ray is not occluded.  s >= cutoff: the triangle is accepted as solid.  Under
+ *                   NXHIP_SHADOWS_TRANSMIT a surviving crossing of a MASK material ends the shadow ray (T = 0), a rejected one leaves T
+ *                   untouched.  The first-hit feature buffers (nxhip_set_aov) and the pixel query (nxhip_get_selected_instance) follow
+ *                   the closest hit, so they see through the holes; a hole costs a path no bounce and no material launch.
+ *   NX_ALPHA_OPAQUE (glTF's default: alpha is ignored) traversal is unchanged: every crossing counts, no fetch.  Under
+ *                   NXHIP_SHADOWS_TRANSMIT a crossing ends the shadow ray.
+ * The material step under MASK and OPAQUE: the path never passes through.  The random numbers of the pass-through test (shade_path:
+ * rng_next > opacity || (map && rng_next > alpha)) are still drawn, exactly those of a BLEND material and in the same order; only their
+ * outcome is ignored, so every later draw of the path is the one it was.  Colour still comes from the map's rgb.  The rule has one
+ * device text (shade_path's SOLID form) which both pipelines' material launches reach; the medium's scatter step shades no surface.
+ * Validation, on the host — NXHIP_ERR_INVALID and the previous table stays in place: alphas NULL with count > 0; a mode outside the
+ * enum; a MASK cutoff that is not finite or lies outside [0, 1].  At render time (and in the ray-batch hooks, which follow the table
+ * too): a count that differs from the material count; a MASK material on an instance that is a mesh light (NX_LIGHT_MESH) — the light
+ * sampler would pick points inside the holes.  Out of scope: holes in emitters, an order for BLEND (it stays stochastic), doubleSided,
+ * mip-mapping.
+ * Restrictions of a first version.  While some material of the table is MASK or OPAQUE (host-known, as the see-through fact of
+ * NXHIP_SHADOWS_TRANSMIT is): the material launches are their SOLID instances — general ones, no map-free form — and the tail kernel is
+ * off (nxhip_set_tail_bounce is ignored).  Said outright: ONE such entry — and OPAQUE is glTF's default, so any .glb read with its alpha
+ * modes has one — moves EVERY material launch of the context onto those instances, which are also the ones that read detail records and
+ * know all five material types.  They compute the same shading rule, but they are other kernels: frames of such a context are not
+ * promised to be bit-identical to frames of the same scene without the table, on any surface, and its passes are somewhat slower (no
+ * map-free launch, no tail kernel).  Equal bits hold within the family: both pipelines, every pass shape.  While some material is MASK (the pass flavor's alpha-test bit):
+ *   - the trace launches are the ALPHA_TEST instances (nx_trace.hip): no hand-over to the thin kernel, no IDENTITY instance, no ENTRY
+ *     instance;
+ *   - nxhip_set_entry_points is ignored by the pass: an entry state "walks past the first triangles" of a run of rays on the assumption
+ *     that those tests are final, which they are not when one of them may be rejected.
+ * nxhip_trace_batch, nxhip_trace_shadow_batch and nxhip_trace_transmittance_batch use the ALPHA_TEST instances whenever the table has a
+ * MASK material.  Results do not depend on nxhip_enable_trace_stats.  May be set at any time, also between accumulated frames. */
+int nxhip_set_material_alpha(nxhip_ctx *ctx, const nx_material_alpha *alphas, uint32_t count);
 /* Extension — fog: ONE homogeneous participating medium per context, confined to a world-space axis-aligned box (nx_medium of nexus_pod.h:
  * boxMin, boxMax, grey extinction sigmaT per world unit, Henyey-Greenstein asymmetry g, single-scattering albedo per channel).  Off by
  * default.  The call replaces the medium; NULL removes it.  After NULL, or a medium with sigmaT == 0, the context is exactly what it was
@@ -986,7 +1025,7 @@ static inline uint64_t nxhip_header_abi_stamp(void)
         sizeof(nx_bvh_instance), offsetof(nx_bvh_instance, transform), offsetof(nx_bvh_instance, materialId),
         sizeof(nx_material), offsetof(nx_material, emissive), offsetof(nx_material, type), sizeof(nx_light), offsetof(nx_light, type),
         sizeof(nx_analytic_light), offsetof(nx_analytic_light, direction), offsetof(nx_analytic_light, colour), offsetof(nx_analytic_light, innerConeAngle), offsetof(nx_analytic_light, type),
-        sizeof(nx_material_detail), offsetof(nx_material_detail, normalScale), sizeof(nx_medium),
+        sizeof(nx_material_detail), offsetof(nx_material_detail, normalScale), sizeof(nx_medium), sizeof(nx_material_alpha), offsetof(nx_material_alpha, cutoff),
         sizeof(nx_camera), offsetof(nx_camera, resolution), sizeof(nx_render_settings), offsetof(nx_render_settings, backgroundColor),
         sizeof(nx_ray), sizeof(nx_hit), sizeof(nx_bsdf_query), sizeof(nx_bsdf_result), offsetof(nx_bsdf_result, rngOut),
         sizeof(nxhip_queue_sizes), sizeof(nxhip_trace_stats), offsetof(nxhip_trace_stats, cycles), sizeof(nxhip_kernel_times), NXHIP_K_COUNT,

@@ -70,6 +70,9 @@ int nxh_load_scene_file(const char *file, nxh_loaded_scene **out);
  * metallic-roughness model — an NX_MAT_METALROUGH with albedo = baseColorFactor.rgb, roughness = roughnessFactor, metallic =
  * metallicFactor (defaults 1, 1), ior from KHR_materials_ior (default 1.5) — instead of the reference's PLASTIC; everything else stays. */
 #define NXH_LOAD_METAL_ROUGH 1u
+/* NXH_LOAD_ALPHA_MODES: a .glb material's alphaMode (glTF's default: OPAQUE) and alphaCutoff (default 0.5) are read as well and come back
+ * from nxh_loaded_material_alpha; without the flag that call reports no table (every material blends, as it always has). */
+#define NXH_LOAD_ALPHA_MODES 2u
 int nxh_load_scene_file_ex(const char *file, uint32_t flags, nxh_loaded_scene **out);
 void nxh_loaded_scene_free(nxh_loaded_scene *s);
 uint32_t nxh_loaded_mesh_count(const nxh_loaded_scene *s);
@@ -99,6 +102,9 @@ uint32_t nxh_loaded_detail_texture_count(const nxh_loaded_scene *s);
 int nxh_loaded_detail_texture_info(const nxh_loaded_scene *s, uint32_t index, uint32_t *width, uint32_t *height, int32_t *kind);
 int nxh_loaded_detail_texture_pixels(const nxh_loaded_scene *s, uint32_t index, uint8_t *dstRgba8);
 int nxh_loaded_material_detail(const nxh_loaded_scene *s, int32_t *normalTexture, int32_t *roughnessTexture, float *normalScale);
+/* The materials' alpha modes (nx_material_alpha, nexus_pod.h): *count = the material count when the file was read with NXH_LOAD_ALPHA_MODES,
+ * else 0; dst (may be NULL) receives up to `capacity` records. */
+int nxh_loaded_material_alpha(const nxh_loaded_scene *s, nx_material_alpha *dst, uint32_t capacity, uint32_t *count);
 uint32_t nxh_loaded_warning_count(const nxh_loaded_scene *s);
 const char *nxh_loaded_warning(const nxh_loaded_scene *s, uint32_t index);
 /* IMGLoader::LoadIMG (Assets/IMGLoader.cpp:17-41: stbi_load with 4 channels) for PNG data: RGBA8, row 0 first.
@@ -141,6 +147,11 @@ int nxs_scene_set_device_tlas(nxs_scene *s, int enable);
 int nxs_scene_load_file(nxs_scene *s, const char *path, const char *fileName);
 /* Extension, off by default: files loaded from here on read their materials as NXH_LOAD_METAL_ROUGH does (Scene::SetMetalRoughMaterials). */
 int nxs_scene_set_metal_rough(nxs_scene *s, int on);
+/* Extension, off by default: files loaded from here on carry their materials' alpha modes as NXH_LOAD_ALPHA_MODES reads them
+ * (Scene::SetMaterialAlphaModes); the next device update sends the table (nxhip_set_material_alpha).  nxs_scene_material_alphas: the
+ * AssetManager's table — *count records, 0 while no material has a mode; dst (may be NULL) receives up to `capacity` of them. */
+int nxs_scene_set_material_alpha_modes(nxs_scene *s, int on);
+int nxs_scene_material_alphas(const nxs_scene *s, nx_material_alpha *dst, uint32_t capacity, uint32_t *count);
 int nxs_scene_set_camera(nxs_scene *s, const float pos[3], const float forward[3], float horizontalFovDeg, float focusDist,
                          float defocusAngleDeg);
 int nxs_scene_set_render_settings(nxs_scene *s, const nx_render_settings *settings);

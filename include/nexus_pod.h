@@ -122,6 +122,15 @@ typedef struct nx_material_detail {
 } nx_material_detail;
 NX_STATIC_ASSERT(sizeof(nx_material_detail) == 16, "nx_material_detail must be 16 bytes");
 
+/* Extension: how the alpha of one material is read (nxhip_set_material_alpha; the rule is stated in full in include/nexus_hip.h).  A table
+ * of these runs index-parallel to the material table, like nx_material_detail: the 60-byte nx_material keeps the reference's layout. */
+enum { NX_ALPHA_BLEND = 0, NX_ALPHA_MASK = 1, NX_ALPHA_OPAQUE = 2 };
+typedef struct nx_material_alpha {
+    uint32_t mode;  /* NX_ALPHA_* */
+    float cutoff;   /* NX_ALPHA_MASK: a crossing with opacity x alpha below it does not exist (glTF alphaCutoff, default 0.5) */
+} nx_material_alpha;
+NX_STATIC_ASSERT(sizeof(nx_material_alpha) == 8, "nx_material_alpha must be 8 bytes");
+
 /* Extension: one homogeneous participating medium ("fog") per context, confined to a world-space axis-aligned box (nxhip_set_medium; the
  * rule is stated in full in include/nexus_hip.h). */
 typedef struct nx_medium {

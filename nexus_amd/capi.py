@@ -42,6 +42,7 @@ HIP_SYMBOLS = [
     "nxhip_set_medium_density", "nxhip_read_medium_majorants", "nxhip_medium_density_batch", "nxhip_medium_track_batch",
     "nxhip_set_queue_budget", "nxhip_get_queue_budget", "nxhip_queue_budget_from_text", "nxhip_debug_last_graph",
     "nxhip_read_material_queue_sizes", "nxhip_material_inputs_batch",
+    "nxhip_set_material_alpha",
 ]
 HOST_SYMBOLS = [
     "nxh_bvh8_build", "nxh_tlas_build", "nxh_tlas_refit", "nxh_bvh8_refit", "nxh_bvh8_node_count", "nxh_bvh8_prim_count", "nxh_bvh8_nodes",
@@ -68,6 +69,7 @@ HOST_SYMBOLS = [
     "nxs_scene_set_medium", "nxs_scene_clear_medium", "nxs_scene_medium",
     "nxs_scene_set_medium_density", "nxs_scene_clear_medium_density", "nxs_scene_medium_density", "nxh_decode_npy_grid",
     "nxh_load_scene_file_ex", "nxs_scene_set_metal_rough",
+    "nxh_loaded_material_alpha", "nxs_scene_set_material_alpha_modes", "nxs_scene_material_alphas",
 ]
 
 
@@ -109,7 +111,7 @@ def abi_words():
         pod.INST_DT.itemsize, off(pod.INST_DT, "transform"), off(pod.INST_DT, "materialId"),
         pod.MAT_DT.itemsize, off(pod.MAT_DT, "emissive"), off(pod.MAT_DT, "type"), pod.LIGHT_DT.itemsize, off(pod.LIGHT_DT, "type"),
         pod.ALIGHT_DT.itemsize, off(pod.ALIGHT_DT, "direction"), off(pod.ALIGHT_DT, "colour"), off(pod.ALIGHT_DT, "innerConeAngle"), off(pod.ALIGHT_DT, "type"),
-        pod.DETAIL_DT.itemsize, off(pod.DETAIL_DT, "normalScale"), pod.MEDIUM_DT.itemsize,
+        pod.DETAIL_DT.itemsize, off(pod.DETAIL_DT, "normalScale"), pod.MEDIUM_DT.itemsize, pod.ALPHA_DT.itemsize, off(pod.ALPHA_DT, "cutoff"),
         pod.CAM_DT.itemsize, off(pod.CAM_DT, "resolution"), pod.SETTINGS_DT.itemsize, off(pod.SETTINGS_DT, "backgroundColor"),
         pod.RAY_DT.itemsize, pod.HIT_DT.itemsize, pod.BSDF_QUERY_DT.itemsize, pod.BSDF_RESULT_DT.itemsize, off(pod.BSDF_RESULT_DT, "rngOut"),
         C.sizeof(QueueSizes), C.sizeof(TraceStats), TraceStats.cycles.offset, C.sizeof(KernelTimes), len(KERNEL_CLASSES),
@@ -458,6 +460,29 @@ def load_scene_file(path, metal_rough=False):
     return meshes, mats, insts
 
 
+LOAD_ALPHA_MODES = 2  # nxh_load_scene_file_ex: NXH_LOAD_ALPHA_MODES
+
+
+def load_scene_material_alpha(path, alpha_modes=True):
+    """the alpha modes of a .glb's materials as the C++ reader makes them (LoadOptions::alphaModes): pod.ALPHA_DT records, one per material;
+    none when the reader is not asked (alpha_modes=False)"""
+    L = lib()
+    h = C.c_void_p()
+    if L.nxh_load_scene_file_ex(str(path).encode(), LOAD_ALPHA_MODES if alpha_modes else 0, C.byref(h)) != 0:
+        raise NexusError("nxh_load_scene_file_ex: " + L.nxs_last_error().decode())
+    try:
+        L.nxh_loaded_material_alpha.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
+        n = C.c_uint32(0)
+        if L.nxh_loaded_material_alpha(h, None, 0, C.byref(n)) != 0:
+            raise NexusError(L.nxs_last_error().decode())
+        out = np.zeros(n.value, dtype=pod.ALPHA_DT)
+        if n.value and L.nxh_loaded_material_alpha(h, _ptr(out), n.value, C.byref(n)) != 0:
+            raise NexusError(L.nxs_last_error().decode())
+    finally:
+        L.nxh_loaded_scene_free(h)
+    return out
+
+
 def load_scene_analytic_lights(path):
     """the KHR_lights_punctual lights of a .glb as the C++ reader makes them: pod.ALIGHT_DT records, one per node that carries a light"""
     L = lib()
@@ -599,6 +624,8 @@ TEXTURE_KINDS = {"diffuse": 0, "emissive": 1, "hdr": 2, "normal": 3, "roughness"
 FLAVOR_MEDIUM = 8192  # ... and the medium's two launches per bounce: a medium with sigmaT > 0 is set (set_medium)
 FLAVOR_MEDIUM_GRID = 16384  # ... and their GRID instances: a medium with sigmaT > 0 and a density grid are set (set_medium_density)
 FLAVOR_METAL = 32768  # ... and the METAL instances of the material launch and the tail kernel: some material is a MAT_METALROUGH (set_materials)
+FLAVOR_ALPHA_TEST = 65536  # ... and the ALPHA_TEST instances of the trace kernels: some material of the alpha table is pod.ALPHA_MASK (set_material_alpha)
+FLAVOR_SOLID = 131072  # ... and the SOLID instances of the material launches: some material is pod.ALPHA_MASK or pod.ALPHA_OPAQUE (set_material_alpha)
 FLAVOR_TRANSMIT = 2048  # ... and the any-hit TRANSMIT instance: SHADOWS_TRANSMIT over a table with a see-through material (set_shadow_transmittance)
 
 
@@ -666,6 +693,13 @@ class Context:
         lights = np.ascontiguousarray(lights, dtype=pod.ALIGHT_DT).reshape(-1)
         self.L.nxhip_set_analytic_lights.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
         check(self.L.nxhip_set_analytic_lights(self.h, _ptr(lights) if len(lights) else None, len(lights)), "nxhip_set_analytic_lights")
+
+    def set_material_alpha(self, alphas):
+        """how the materials' alpha is read: pod.ALPHA_DT records (pod.make_material_alpha), one per material of the table; an empty
+        list removes the table: every material is a stochastic blend again (nxhip_set_material_alpha: the rule is in include/nexus_hip.h)"""
+        alphas = np.ascontiguousarray(alphas, dtype=pod.ALPHA_DT)
+        self.L.nxhip_set_material_alpha.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+        check(self.L.nxhip_set_material_alpha(self.h, _ptr(alphas) if len(alphas) else None, len(alphas)), "nxhip_set_material_alpha")
 
     def set_material_detail(self, details):
         """the materials' detail maps: pod.DETAIL_DT records (pod.make_material_detail), one per material of the table; an empty list
@@ -1606,6 +1640,21 @@ class Scene:
     def set_metal_rough(self, on=True):
         """Scene::SetMetalRoughMaterials: the files loaded from here on read a .glb's materials as MAT_METALROUGH (off by default)"""
         _scheck(self.L.nxs_scene_set_metal_rough(self.h, 1 if on else 0), "nxs_scene_set_metal_rough")
+
+    def set_material_alpha_modes(self, on=True):
+        """Scene::SetMaterialAlphaModes: the files loaded from here on carry their materials' glTF alphaMode / alphaCutoff to the device (off by default)"""
+        self.L.nxs_scene_set_material_alpha_modes.argtypes = [C.c_void_p, C.c_int]
+        _scheck(self.L.nxs_scene_set_material_alpha_modes(self.h, 1 if on else 0), "nxs_scene_set_material_alpha_modes")
+
+    def material_alphas(self):
+        """AssetManager::GetMaterialAlphas: pod.ALPHA_DT records, one per material (empty: no material has a mode)"""
+        self.L.nxs_scene_material_alphas.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
+        n = C.c_uint32(0)
+        _scheck(self.L.nxs_scene_material_alphas(self.h, None, 0, C.byref(n)), "nxs_scene_material_alphas")
+        out = np.zeros(n.value, dtype=pod.ALPHA_DT)
+        if n.value:
+            _scheck(self.L.nxs_scene_material_alphas(self.h, _ptr(out), n.value, C.byref(n)), "nxs_scene_material_alphas")
+        return out
 
     def create_instance(self, mesh_id, material_id, position=(0, 0, 0), rotation_deg=(0, 0, 0), scale=(1, 1, 1)):
         p, r, s = (np.asarray(x, np.float32) for x in (position, rotation_deg, scale))

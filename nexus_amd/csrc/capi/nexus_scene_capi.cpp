@@ -137,10 +137,11 @@ int nxh_load_scene_file_ex(const char* file, uint32_t flags, nxh_loaded_scene** 
 {
     return guarded([&] {
         if (!file || !out) throw std::runtime_error("nxh_load_scene_file_ex: null argument");
-        if (flags & ~(uint32_t)NXH_LOAD_METAL_ROUGH) throw std::runtime_error("nxh_load_scene_file_ex: unknown flag");
+        if (flags & ~(uint32_t)(NXH_LOAD_METAL_ROUGH | NXH_LOAD_ALPHA_MODES)) throw std::runtime_error("nxh_load_scene_file_ex: unknown flag");
         std::unique_ptr<nxh_loaded_scene> p(new nxh_loaded_scene);
         LoadOptions options;
         options.metalRough = (flags & NXH_LOAD_METAL_ROUGH) != 0;
+        options.alphaModes = (flags & NXH_LOAD_ALPHA_MODES) != 0;
         p->ls = OBJLoader::Parse(file, options);
         *out = p.release();
     });
@@ -241,6 +242,14 @@ int nxh_loaded_material_detail(const nxh_loaded_scene* s, int32_t* normalTexture
         }
     });
 }
+int nxh_loaded_material_alpha(const nxh_loaded_scene* s, nx_material_alpha* dst, uint32_t capacity, uint32_t* count)
+{
+    return guarded([&] {
+        if (!s || !count) throw std::runtime_error("nxh_loaded_material_alpha: null argument");
+        *count = static_cast<uint32_t>(s->ls.materialAlpha.size());
+        for (size_t i = 0; dst && i < s->ls.materialAlpha.size() && i < capacity; i++) dst[i] = s->ls.materialAlpha[i];
+    });
+}
 uint32_t nxh_loaded_analytic_light_count(const nxh_loaded_scene* s) { return static_cast<uint32_t>(s->ls.analyticLights.size()); }
 int nxh_loaded_analytic_lights(const nxh_loaded_scene* s, nx_analytic_light* dst)
 {
@@ -324,6 +333,20 @@ int nxs_scene_load_file(nxs_scene* s, const char* path, const char* fileName)
 int nxs_scene_set_metal_rough(nxs_scene* s, int on)
 {
     return guarded([&] { s->scene.SetMetalRoughMaterials(on != 0); });
+}
+
+int nxs_scene_set_material_alpha_modes(nxs_scene* s, int on)
+{
+    return guarded([&] { s->scene.SetMaterialAlphaModes(on != 0); });
+}
+int nxs_scene_material_alphas(const nxs_scene* s, nx_material_alpha* dst, uint32_t capacity, uint32_t* count)
+{
+    return guarded([&] {
+        if (!s || !count) throw std::runtime_error("nxs_scene_material_alphas: null argument");
+        const std::vector<nx_material_alpha> a = s->scene.GetAssetManager().GetMaterialAlphas();
+        *count = static_cast<uint32_t>(a.size());
+        for (size_t i = 0; dst && i < a.size() && i < capacity; i++) dst[i] = a[i];
+    });
 }
 
 int nxs_scene_set_camera(nxs_scene* s, const float pos[3], const float forward[3], float hfov, float focusDist, float defocusAngle)

@@ -187,6 +187,11 @@ struct nxhip_ctx : nxd::PassSlot {
     std::vector<nx_material_detail> hostMaterialDetail;
     nxd::DevBuf shadeDetail;
     bool materialsNameDetail = false;
+    // alpha modes (nxhip_set_material_alpha): the table, index-parallel to hostMaterials (empty: every material is NX_ALPHA_BLEND); whether
+    // some entry is NX_ALPHA_MASK — only then do the trace launches of a pass, or of a ray-batch hook, change (kFlavorAlphaTest); whether
+    // some entry is MASK or OPAQUE — only then do the material launches (kFlavorSolid)
+    std::vector<nx_material_alpha> hostMaterialAlpha;
+    bool materialsAlphaMask = false, materialsAlphaSolid = false;
     std::vector<nx_light> hostLights;
     nxd::DevBuf alights;  // [h.alightCount] ALight: the analytic lights' device table (nxhip_set_analytic_lights)
     std::vector<uint32_t> hostInstIdx;  // TLAS leaf order

@@ -120,8 +120,11 @@ struct __attribute__((aligned(16))) ShadeInst {
     nx_material material;    // the device copy (derived flag byte behind `type` included: kMaterialFlagOffset)
     uint32_t seeThrough;     // derived (refresh_shade_inst): 1 = a shadow ray of NXHIP_SHADOWS_TRANSMIT may pass — opacity < 1, or the diffuse
                              // map has a texel with alpha < 255; 0 = every crossing ends the ray (the any-hit TRANSMIT instance, nx_trace.hip)
+    uint32_t alphaMode;      // derived (refresh_shade_inst): NX_ALPHA_* of the instance's material (nxhip_set_material_alpha; no table: NX_ALPHA_BLEND)
+    float alphaCutoff;       // ... and its cutoff; read only behind alphaMode == NX_ALPHA_MASK (the ALPHA_TEST instances, nx_trace.hip)
+    uint32_t padAlpha_[2];
 };
-static_assert(sizeof(ShadeInst) == 176 && offsetof(ShadeInst, material) == 112, "ShadeInst layout");
+static_assert(sizeof(ShadeInst) == 192 && offsetof(ShadeInst, material) == 112 && offsetof(ShadeInst, alphaMode) == 176, "ShadeInst layout");
 
 struct TextureDev {
     const NX_G uint32_t* texels;  // RGBA8, row 0 first

@@ -16,6 +16,7 @@ namespace nxd {
 // and nx_wavefront.hip cannot include it: their text is pinned by bench.py's source hash).
 const void* trace_kernel_ptr(bool anyHit, bool stats, bool identity = false);  // nx_trace.hip
 const void* trace_transmit_kernel_ptr(bool stats);  // the any-hit TRANSMIT instance (nxhip_set_shadow_transmittance)
+const void* trace_alpha_kernel_ptr(bool anyHit, bool stats, bool transmit);  // the ALPHA_TEST instances (nxhip_set_material_alpha with a MASK material)
 const void* trace_entry_kernel_ptr(bool identity = false);
 const void* thin_kernel_ptr();
 const void* entry_state_kernel_ptr();  // nx_entry.hip
@@ -45,6 +46,8 @@ const void* bsdf_hook_metal_kernel_ptr();
 const void* logic_metal_kernel_ptr();  // (the classic pipeline's fifth queue and its material kernel)
 const void* shade_metal_kernel_ptr(bool lightPower, bool analytic);
 const void* material_inputs_hook_kernel_ptr();
+const void* shade_scan_solid_kernel_ptr(bool lightPower, bool analytic);  // nx_wavefront_solid.hip: the SOLID instances (kFlavorSolid); METAL and DETAIL instances too
+const void* shade_solid_kernel_ptr(int type, bool lightPower, bool analytic);
 const void* tex2d_linear_hook_kernel_ptr();
 const void* medium_scatter_kernel_ptr(bool lightPower, bool analytic, bool metal = false);  // nx_medium.hip: the medium's kernels (kFlavorMedium) and its hooks'
 const void* medium_shadow_kernel_ptr();
@@ -73,6 +76,7 @@ const void* blas_refit_kernel_ptr();
 uint64_t layout_stamp_trace();
 uint64_t layout_stamp_wavefront();
 uint64_t layout_stamp_wavefront_detail();
+uint64_t layout_stamp_wavefront_solid();
 uint64_t layout_stamp_wavefront_metal();
 uint64_t layout_stamp_medium();
 uint64_t layout_stamp_refit();
@@ -135,6 +139,7 @@ using BounceKernel = Kernel<State, int>;      // (S, bounce | flags)
 using TypeKernel = Kernel<State, int, int>;   // (S, bounce | flags, type or type mask)
 inline BounceKernel trace(bool anyHit, bool stats, bool identity = false) { return {trace_kernel_ptr(anyHit, stats, identity)}; }  // (identity: pass graphs only)
 inline BounceKernel trace_transmit(bool stats) { return {trace_transmit_kernel_ptr(stats)}; }  // (any hit; pass graphs of kFlavorTransmit and nxhip_trace_transmittance_batch)
+inline BounceKernel trace_alpha(bool anyHit, bool stats, bool transmit = false) { return {trace_alpha_kernel_ptr(anyHit, stats, transmit)}; }  // (pass graphs of kFlavorAlphaTest and the ray-batch hooks over such a table)
 inline BounceKernel trace_entry(bool identity = false) { return {trace_entry_kernel_ptr(identity)}; }
 inline BounceKernel thin() { return {thin_kernel_ptr()}; }
 inline StateKernel entry_state() { return {entry_state_kernel_ptr()}; }
@@ -152,6 +157,9 @@ inline TypeKernel shade_scan(bool lightPower, bool noMaps = false, bool analytic
 {
     return {metal ? shade_scan_metal_kernel_ptr(lightPower, analytic) : detail ? shade_scan_detail_kernel_ptr(lightPower, analytic) : shade_scan_kernel_ptr(lightPower, noMaps, analytic)};
 }
+// (solid: the SOLID instances of a context with an NX_ALPHA_MASK or NX_ALPHA_OPAQUE material — nx_wavefront_solid.hip; all five types, detail records)
+inline BounceKernel shade_solid(int type, bool lightPower, bool analytic) { return {shade_solid_kernel_ptr(type, lightPower, analytic)}; }
+inline TypeKernel shade_scan_solid(bool lightPower, bool analytic) { return {shade_scan_solid_kernel_ptr(lightPower, analytic)}; }
 inline TypeKernel count_scan() { return {count_scan_kernel_ptr()}; }
 inline Kernel<DeviceState*, U32, U32, U32> begin_frame() { return {begin_frame_kernel_ptr()}; }  // (S, frames, frameLast, scanEpoch)
 inline Kernel<DeviceState*, U32, int, int> hook_sizes() { return {hook_sizes_kernel_ptr()}; }    // (S, n, anyHit, slot)
@@ -334,6 +342,8 @@ int set_frame_number_device(nxhip_ctx* c, uint32_t f);
 // nxhip_scene.hip: what a pass or a hook brings up to date before it reads the scene
 int refresh_shade_inst(nxhip_ctx* c);
 bool material_see_through(const nxhip_ctx* c, const nx_material& m);  // a shadow ray of NXHIP_SHADOWS_TRANSMIT may pass it
+void refresh_alpha_modes(nxhip_ctx* c);  // nxhip_ctx::materialsAlphaMask / materialsAlphaSolid, after the alpha table has changed
+int check_alpha_table(const nxhip_ctx* c);  // the table's count and the MASK-on-a-mesh-light refusal (check_scene_ready and the ray-batch hooks)
 void refresh_detail_maps(nxhip_ctx* c);  // nxhip_ctx::materialsNameDetail, after the detail table has changed
 void refresh_see_through(nxhip_ctx* c);  // nxhip_ctx::materialsSeeThrough, and the shading records' copy of the fact
 int refresh_updated_blas(nxhip_ctx* c);

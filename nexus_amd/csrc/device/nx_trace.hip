@@ -412,7 +412,13 @@ NXD ThinResult thin_wave_search(const DeviceState* __restrict__ S, lds_u64* cons
 // ends the ray; the flush adds T x radiance.  No random number is drawn.  The pass graph launches this instance without the hand-over
 // (a wave-wide search would multiply in an order of its own); check_scene_ready and refresh_shade_inst have run before any launch:
 // instance -> material -> texture -> triangle are followed without bounds tests, as in the material kernels.
-template <bool ANY_HIT, bool STATS, bool ENTRY = false, bool IDENTITY = false, bool TRANSMIT = false>
+// ALPHA_TEST (nxhip_set_material_alpha, kFlavorAlphaTest: some material of the table is NX_ALPHA_MASK): a triangle the test accepts is looked
+// at once more before it counts.  The lane fetches its instance's shading record (one dependent load) and compares the mode: BLEND and
+// OPAQUE go on as in the instance without the parameter, with no triangle or texture fetch; MASK computes s = o x a as TRANSMIT does (the
+// same clamp, the same lookup at this test's own u, v) and, if s < cutoff, drops the triangle as if the ray had missed it — hitT stays
+// (closest hit), the ray is not occluded and its T not touched (any hit).  A surviving MASK crossing is solid: it ends an any-hit ray, with
+// or without TRANSMIT.  The general instances and their counting variants only; never hands over (the thin kernel's search knows no alpha).
+template <bool ANY_HIT, bool STATS, bool ENTRY = false, bool IDENTITY = false, bool TRANSMIT = false, bool ALPHA_TEST = false>
 // 5 waves per SIMD for both variants (96 VGPRs, no spills in the loop).  Before an instance entry also carried its BLAS
 // root (17 more live registers in the fetch), 6 waves at 80 VGPRs was the best point (5: -3 %, 7: -0.3 %, 8: -1.5 %); with it,
 // 6 waves spill 23 VGPRs inside the loop (-10 %), 5 and 4 measure +4.5 % and +1 % over the old kernel at 6.
@@ -427,10 +433,11 @@ __global__ void __launch_bounds__(kTraceBlock) trace_kernel(const DeviceState* _
     const int bounce = bounceArg & 0xff;
     const bool scan = !ANY_HIT && (bounceArg & kTraceScanFlag) != 0;
     // ... | kTraceEntryFlag: the rays name the entry state of their run (rayO.w): installed at refill instead of the root's
-    const bool entryLaunch = !ANY_HIT && (ENTRY || STATS) && (bounceArg & kTraceEntryFlag) != 0 && S->entry != nullptr;
+    const bool entryLaunch = !ANY_HIT && !ALPHA_TEST && (ENTRY || STATS) && (bounceArg & kTraceEntryFlag) != 0 && S->entry != nullptr;
     // ... | kTraceThinFlag: the last long rays of a dry wave may be handed to the thin kernel (below)
     static_assert(!TRANSMIT || (ANY_HIT && !ENTRY && !IDENTITY), "TRANSMIT: the general any-hit instance and its counting variant only");
-    bool thinAllowed = !STATS && !TRANSMIT && (bounceArg & kTraceThinFlag) != 0;
+    static_assert(!ALPHA_TEST || (!ENTRY && !IDENTITY), "ALPHA_TEST: the general instances and their counting variants only");
+    bool thinAllowed = !STATS && !TRANSMIT && !ALPHA_TEST && (bounceArg & kTraceThinFlag) != 0;
     const int thinLanes = (int)(S->thinLanes & 0xffu);
     // (test hook, nxhip_debug_set_thin inHooks bit 1: hand over after thinIters iterations of EVERY stretch between two refill points, dry
     //  queue or not — rays then arrive at the thin kernel with the state of exactly that many steps)
@@ -692,7 +699,7 @@ __global__ void __launch_bounds__(kTraceBlock) trace_kernel(const DeviceState* _
                     xformed = false;
                     nodes = tlasNodes;
                     if (STATS) nRays++;
-                    if (!ANY_HIT && (ENTRY || STATS) && entryLaunch) {
+                    if (!ANY_HIT && !ALPHA_TEST && (ENTRY || STATS) && entryLaunch) {
                         // the state the first node steps of this ray's run provably lead to (nx_entry.hip), instead of the root's: 16-byte
                         // loads from the one address the run's rays share, none of them behind another
                         const uint32_t en = __float_as_uint(o.w) >> kRayEntryShift;
@@ -869,10 +876,32 @@ __global__ void __launch_bounds__(kTraceBlock) trace_kernel(const DeviceState* _
                 const f3 sCrossEdge0 = cross3(s, edge0);
                 const float v = invDet * dot3(dir, sCrossEdge0);
                 const float t = invDet * dot3(edge1, sCrossEdge0);
-                const bool hit = !(u < 0.0f || u > 1.0f) && !(v < 0.0f || u + v > 1.0f) && (t > 0.0f && t < hitT);
+                bool hit = !(u < 0.0f || u > 1.0f) && !(v < 0.0f || u + v > 1.0f) && (t > 0.0f && t < hitT);
                 if (STATS) nTris++;
+                bool solid = false;  // (ALPHA_TEST: a MASK crossing that survived: it ends an any-hit ray whatever TRANSMIT would multiply in)
+                if constexpr (ALPHA_TEST) {
+                    if (hit) {
+                        // s = o x a against the cutoff (include/nexus_hip.h, nxhip_set_material_alpha): o and a as in the TRANSMIT branch below
+                        const NX_G ShadeInst* si = &S->shadeInst[instIdx & kHitInstMask];
+                        if (si->alphaMode == (uint32_t)NX_ALPHA_MASK) {
+                            float o = si->material.opacity;
+                            o = !(o < 1.0f) ? 1.0f : fmaxf(o, 0.0f);
+                            float a = 1.0f;
+                            const int32_t map = si->material.diffuseMapId;
+                            if (map != -1) {
+                                const NX_G nx_triangle* tri = shade_tri(si->tris, rc[0].w);  // the ORIGINAL triangle: p0.w of the leaf stream
+                                const f2 texUv = bary2(tri->texCoord0, tri->texCoord1, tri->texCoord2, u, v);
+                                a = tex2d_alpha(S->diffuseMaps[map], texUv.x, texUv.y);
+                            }
+                            if (o * a < si->alphaCutoff) hit = false;  // as if the ray had missed the triangle
+                            else solid = true;
+                        }
+                    }
+                }
                 if (hit) {
-                    if (ANY_HIT && TRANSMIT) {
+                    if (ANY_HIT && ALPHA_TEST && solid) {
+                        active = false;  // occluded: nothing to add (TRANSMIT: T = 0)
+                    } else if (ANY_HIT && TRANSMIT) {
                         // a crossing: T *= 1 - o * a (include/nexus_hip.h, nxhip_set_shadow_transmittance)
                         const NX_G ShadeInst* si = &S->shadeInst[instIdx & kHitInstMask];
                         if (si->seeThrough == 0u) {
@@ -988,6 +1017,12 @@ template __global__ void trace_kernel<false, false, true, true>(const DeviceStat
 template __global__ void trace_kernel<true, false, false, true>(const DeviceState*, int);
 template __global__ void trace_kernel<true, false, false, false, true>(const DeviceState*, int);
 template __global__ void trace_kernel<true, true, false, false, true>(const DeviceState*, int);
+template __global__ void trace_kernel<false, false, false, false, false, true>(const DeviceState*, int);
+template __global__ void trace_kernel<false, true, false, false, false, true>(const DeviceState*, int);
+template __global__ void trace_kernel<true, false, false, false, false, true>(const DeviceState*, int);
+template __global__ void trace_kernel<true, true, false, false, false, true>(const DeviceState*, int);
+template __global__ void trace_kernel<true, false, false, false, true, true>(const DeviceState*, int);
+template __global__ void trace_kernel<true, true, false, false, true, true>(const DeviceState*, int);
 
 // The listed rays of one level (closest-hit first, then any-hit; kThinClosestOnly / kThinAnyOnly: one list), one wave per ray,
 // grid-stride.  `bounceArg` as the trace launches got it: the ray set and the meaning of the closest-hit record follow kTraceScanFlag.
@@ -1102,6 +1137,14 @@ const void* trace_kernel_ptr(bool anyHit, bool stats, bool identity)
 
 // the any-hit TRANSMIT instance (reads sceneFlags: no IDENTITY form) and its counting variant
 const void* trace_transmit_kernel_ptr(bool stats) { return stats ? (const void*)trace_kernel<true, true, false, false, true> : (const void*)trace_kernel<true, false, false, false, true>; }
+
+// the ALPHA_TEST instances (nxhip_set_material_alpha with a MASK material): closest hit, any hit, any hit + TRANSMIT, and their counting variants
+const void* trace_alpha_kernel_ptr(bool anyHit, bool stats, bool transmit)
+{
+    if (!anyHit) return stats ? (const void*)trace_kernel<false, true, false, false, false, true> : (const void*)trace_kernel<false, false, false, false, false, true>;
+    if (transmit) return stats ? (const void*)trace_kernel<true, true, false, false, true, true> : (const void*)trace_kernel<true, false, false, false, true, true>;
+    return stats ? (const void*)trace_kernel<true, true, false, false, false, true> : (const void*)trace_kernel<true, false, false, false, false, true>;
+}
 
 // the device-side layouts this translation unit was compiled with (nx_device.h layout_stamp; compared by nxhip_create)
 uint64_t layout_stamp_trace() { return layout_stamp(); }

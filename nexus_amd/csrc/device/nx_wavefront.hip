@@ -855,7 +855,10 @@ NXD bool next_event_estimation(const DeviceState* S, f3 wi, const MatParams& mp,
 // BSDF's roughness and the normal map's shading normal ns (nx_detail.h: the rule is stated in include/nexus_hip.h) takes the place of the
 // interpolated normal in the frame, in the light sample and in the offset signs; the emissive hit's MIS weight keeps the interpolated
 // normal.  The instances with DETAIL = false are the code of a context without such maps.
-template <int TYPE, bool POWER, bool NO_MAPS = false, bool ANALYTIC = false, bool DETAIL = false, class PrevOrigin, class Emit>
+// SOLID (nxhip_set_material_alpha with a material that is NX_ALPHA_MASK or NX_ALPHA_OPAQUE): a hit on an instance whose alphaMode is not
+// NX_ALPHA_BLEND never passes through.  The random numbers of the pass-through test are drawn as ever, in the same order — only the outcome
+// is ignored — and the colour still comes from the map's rgb.  The one text of the rule: every SOLID instance (nx_wavefront_solid.hip) gets here.
+template <int TYPE, bool POWER, bool NO_MAPS = false, bool ANALYTIC = false, bool DETAIL = false, bool SOLID = false, class PrevOrigin, class Emit>
 NXD void shade_path(const DeviceState* S, const int bounce, const uint32_t frame, const uint32_t seedSlot, const uint32_t pixelIdx, const float hu, const float hv,
                     const uint32_t triIdx, const uint32_t instanceIdx, const f3 rayDirection, const float4 tpdf, PrevOrigin prevOrigin, Emit emit,
                     bool& wantShadow, ShadowPayload& sh, bool& wantTrace, bool& updatePath, f3& nextOrigin, f3& nextDir, f3& nextThroughput, float& nextPdf)
@@ -937,7 +940,11 @@ NXD void shade_path(const DeviceState* S, const int bounce, const uint32_t frame
         const float4 q = rotation_to_z(normal);
         const f3 wi = rotate_point(q, -rayDirection);
         f3 wo;
-        if (rng_next(rng) > material.opacity || (!NO_MAPS && material.diffuseMapId != -1 && rng_next(rng) > color.w)) {
+        bool passThrough = rng_next(rng) > material.opacity || (!NO_MAPS && material.diffuseMapId != -1 && rng_next(rng) > color.w);
+        if constexpr (SOLID) {
+            if (inst->alphaMode != (uint32_t)NX_ALPHA_BLEND) passThrough = false;  // (the draws above stand)
+        }
+        if (passThrough) {
             // texture / opacity pass-through: continue straight, path state untouched
             wo = normalize3(rotate_point(invert_rotation(q), -wi));
             const float od = sgnE(dot3(wo, normal));
@@ -966,7 +973,7 @@ NXD void shade_path(const DeviceState* S, const int bounce, const uint32_t frame
 // at 4 waves (126 VGPRs) for one large pass, +4.5 % for one-frame passes in flight, where a smaller register footprint lets
 // the material kernels of one slot share SIMDs with the trace waves of another.  6 and 8 waves per SIMD spill 30-87 VGPRs and
 // double the kernel's time: it is sensitive to memory traffic, not short of waves.
-template <int TYPE, bool ORDERED, bool POWER, bool ANALYTIC = false, bool DETAIL = false>
+template <int TYPE, bool ORDERED, bool POWER, bool ANALYTIC = false, bool DETAIL = false, bool SOLID = false>
 #ifndef NX_SHADE_WAVES
 #define NX_SHADE_WAVES 5
 #endif
@@ -1004,7 +1011,7 @@ __global__ void __launch_bounds__(ORDERED ? kShadeBlockOrderedThreads : kShadeBl
             pixelIdx = __float_as_uint(hit.x);
             const uint32_t instanceIdx = __float_as_uint(dirInst.w);
             tpdf = bounce == 1 ? make_float4(1.0f, 1.0f, 1.0f, 1.0e10f) : mq.tp[at];
-            shade_path<TYPE, POWER, false, ANALYTIC, DETAIL>(S, bounce, frame, (uint32_t)requestIdx, pixelIdx, hit.y, hit.z, __float_as_uint(hit.w), instanceIdx, mk3(dirInst.x, dirInst.y, dirInst.z), tpdf,
+            shade_path<TYPE, POWER, false, ANALYTIC, DETAIL, SOLID>(S, bounce, frame, (uint32_t)requestIdx, pixelIdx, hit.y, hit.z, __float_as_uint(hit.w), instanceIdx, mk3(dirInst.x, dirInst.y, dirInst.z), tpdf,
                              [&]() { return S->rayOrigin[pixelIdx]; },
                              [&](f3 emitted, uint32_t instIdx) {
                                  if (bounce == 1 && bounce != (int)S->settings.pathLength && pixelIdx < S->localCount && S->frame->pixelQueryPixel == (int)global_pixel(S, pixelIdx))
@@ -1066,7 +1073,7 @@ static_assert(kScanRing >= kShadeBlock + 4 * kShadeBlock && (kScanRing & (kScanR
 // from `staticTiles` on are handed out by ticket — one returning atomic per tile on the region's own word.  The share of a tile
 // that is this type's to shade varies from none to all with what the camera sees there, so a static split leaves most workgroups
 // waiting for the few whose tiles were full (measured: +40 % on the kernels).
-template <int TYPE, bool POWER, bool NO_MAPS = false, bool ANALYTIC = false, bool DETAIL = false>
+template <int TYPE, bool POWER, bool NO_MAPS = false, bool ANALYTIC = false, bool DETAIL = false, bool SOLID = false>
 NXD void shade_scan_type(const DeviceState* __restrict__ S, const int bounce, const bool dropEnded, const int region, const int inRegion, const int per, const int firstTile,
                          const int staticTiles, int* const sRing, int* const sHead, int* const sTicket)
 {
@@ -1151,7 +1158,7 @@ NXD void shade_scan_type(const DeviceState* __restrict__ S, const int bounce, co
             // ... and the path's previous vertex, for hits that can need it (keep_previous_vertex)
             const uint32_t typeAndFlag = *(const NX_G uint32_t*)((const NX_G char*)&S->shadeInst[instanceIdx].material + kMaterialTypeOffset);
             if ((typeAndFlag >> 8) & 1u) keep_previous_vertex(S, pixelIdx, in.rayO[at]);
-            shade_path<kMat, POWER, NO_MAPS, ANALYTIC, DETAIL>(S, bounce, frame, (uint32_t)at, pixelIdx, hit.y, hit.z, __float_as_uint(hit.w), instanceIdx, mk3(dirPix.x, dirPix.y, dirPix.z), tpdf,
+            shade_path<kMat, POWER, NO_MAPS, ANALYTIC, DETAIL, SOLID>(S, bounce, frame, (uint32_t)at, pixelIdx, hit.y, hit.z, __float_as_uint(hit.w), instanceIdx, mk3(dirPix.x, dirPix.y, dirPix.z), tpdf,
                              [&]() { return S->rayOrigin[pixelIdx]; },
                              [&](f3 emitted, uint32_t instIdx) {
                                  if (bounce == 1 && bounce != (int)S->settings.pathLength && pixelIdx < S->localCount && S->frame->pixelQueryPixel == (int)global_pixel(S, pixelIdx))
@@ -1267,7 +1274,7 @@ NXD void shade_scan_type(const DeviceState* __restrict__ S, const int bounce, co
 // launch instead of one per type (the reference: four, PathTracer.cpp:116-120).  A single-bit mask is a per-type launch.
 // METAL (a context with an NX_MAT_METALROUGH material: kFlavorMetal): the fifth material type as a sixth case, typeMask bit kScanMetalBit.  The
 // kernel's register count is the maximum over its cases, so the case is compiled into these instances alone (nx_wavefront_metal.hip).
-template <bool POWER, bool NO_MAPS = false, bool ANALYTIC = false, bool DETAIL = false, bool METAL = false>  // (the light sample's mode, a map-free context, analytic lights: next_event_estimation; detail maps: shade_path)
+template <bool POWER, bool NO_MAPS = false, bool ANALYTIC = false, bool DETAIL = false, bool METAL = false, bool SOLID = false>  // (the light sample's mode, a map-free context, analytic lights: next_event_estimation; detail maps: shade_path)
 __global__ void __launch_bounds__(kShadeBlock, NX_SHADE_WAVES) shade_scan_kernel(const DeviceState* __restrict__ S, const int bounceArg, const int typeMask)
 {
     const int bounce = bounceArg & 0xff;
@@ -1303,13 +1310,13 @@ __global__ void __launch_bounds__(kShadeBlock, NX_SHADE_WAVES) shade_scan_kernel
         const int starters = (ranks - want + nTypes - 1) / nTypes;  // workgroups whose first type this is: each takes the tile of its index
         const int first = step == 0 ? myIndex : -1;
         switch (type) {
-        case NX_MAT_DIFFUSE: shade_scan_type<NX_MAT_DIFFUSE, POWER, NO_MAPS, ANALYTIC, DETAIL>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket); break;
-        case NX_MAT_PLASTIC: shade_scan_type<NX_MAT_PLASTIC, POWER, NO_MAPS, ANALYTIC, DETAIL>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket); break;
-        case NX_MAT_DIELECTRIC: shade_scan_type<NX_MAT_DIELECTRIC, POWER, NO_MAPS, ANALYTIC, DETAIL>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket); break;
-        case NX_MAT_CONDUCTOR: shade_scan_type<NX_MAT_CONDUCTOR, POWER, NO_MAPS, ANALYTIC, DETAIL>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket); break;
-        case kScanMiss: shade_scan_type<kScanMiss, POWER, NO_MAPS, ANALYTIC, DETAIL>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket); break;
+        case NX_MAT_DIFFUSE: shade_scan_type<NX_MAT_DIFFUSE, POWER, NO_MAPS, ANALYTIC, DETAIL, SOLID>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket); break;
+        case NX_MAT_PLASTIC: shade_scan_type<NX_MAT_PLASTIC, POWER, NO_MAPS, ANALYTIC, DETAIL, SOLID>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket); break;
+        case NX_MAT_DIELECTRIC: shade_scan_type<NX_MAT_DIELECTRIC, POWER, NO_MAPS, ANALYTIC, DETAIL, SOLID>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket); break;
+        case NX_MAT_CONDUCTOR: shade_scan_type<NX_MAT_CONDUCTOR, POWER, NO_MAPS, ANALYTIC, DETAIL, SOLID>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket); break;
+        case kScanMiss: shade_scan_type<kScanMiss, POWER, NO_MAPS, ANALYTIC, DETAIL, SOLID>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket); break;
         case kScanMetalBit:
-            if constexpr (METAL) shade_scan_type<kScanMetalBit, POWER, NO_MAPS, ANALYTIC, DETAIL>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket);
+            if constexpr (METAL) shade_scan_type<kScanMetalBit, POWER, NO_MAPS, ANALYTIC, DETAIL, SOLID>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket);
             break;
         default: break;
         }

@@ -47,8 +47,10 @@ static int run_trace_chunk(nxhip_ctx* c, bool anyHit, uint32_t n, bool transmit 
     // from a stack-local of this function is left in flight when it returns
     NX_HIP(launch_untimed(kernels::hook_sizes(), 1, 64, c->stream, c->dState.as<DeviceState>(), n, anyHit ? 1 : 0, kHookBounceSlot));
     c->errorFresh = false;  // (this launch may set the error word after the last pass's copy of it)
-    const bool thin = c->thinInHooks && !c->statsEnabled && !transmit;  // (the TRANSMIT instance never hands over)
-    Launch l = make_launch(transmit ? kernels::trace_transmit(c->statsEnabled) : kernels::trace(anyHit, c->statsEnabled), anyHit ? c->shadowBlocks : c->traceBlocks, kTraceBlockThreads,
+    // (a table with a MASK material: the ALPHA_TEST instances, whatever the hook — nxhip_set_material_alpha)
+    const bool alphaTest = c->materialsAlphaMask;
+    const bool thin = c->thinInHooks && !c->statsEnabled && !transmit && !alphaTest;  // (the TRANSMIT and ALPHA_TEST instances never hand over)
+    Launch l = make_launch(alphaTest ? kernels::trace_alpha(anyHit, c->statsEnabled, transmit) : transmit ? kernels::trace_transmit(c->statsEnabled) : kernels::trace(anyHit, c->statsEnabled), anyHit ? c->shadowBlocks : c->traceBlocks, kTraceBlockThreads,
                            anyHit ? NXHIP_K_SHADOW : NXHIP_K_TRACE, c->dState.as<DeviceState>(), kHookBounceSlot | (thin ? kTraceThinFlag : 0));
     int rc = launch_now(c, l);
     if (rc == NXHIP_OK && thin) {  // (nxhip_debug_set_thin: what the dry waves handed over, a wave each)
@@ -65,6 +67,10 @@ try {
     if (!rays || !hits) return fail_invalid("nxhip_trace_batch: null buffer");
     NX_HIP(hipSetDevice(c->device));
     if (!c->h.tlasNodes) return fail_invalid("no TLAS has been set");
+    if (c->materialsAlphaMask) {  // what a render does before its pass: the ALPHA_TEST instance reads the shading records, the maps and the triangles
+        NX_TRY(check_scene_ready(c));
+        if (c->shadeInstDirty) NX_TRY(refresh_shade_inst(c));
+    }
     NX_TRY(ensure_slot_queues(c, c));
     NX_TRY(upload_state(c));
     NX_TRY(refresh_updated_blas(c));
@@ -107,7 +113,7 @@ static int shadow_batch(nxhip_ctx* c, const char* who, const nx_ray* rays, const
     if (!rays || !tmax || (!occluded && !transmittance)) return fail_invalid(std::string(who) + ": null buffer");
     NX_HIP(hipSetDevice(c->device));
     if (!c->h.tlasNodes) return fail_invalid("no TLAS has been set");
-    if (transmittance) {  // what a render does before its pass: the instance reads the shading records, the maps and the triangles
+    if (transmittance || c->materialsAlphaMask) {  // what a render does before its pass: the instance reads the shading records, the maps and the triangles
         NX_TRY(check_scene_ready(c));
         if (c->shadeInstDirty) NX_TRY(refresh_shade_inst(c));
     }

@@ -56,6 +56,8 @@ int nxd::check_scene_ready(nxhip_ctx* c)
     }
     for (const nx_light& l : c->hostLights)
         if (l.type == NX_LIGHT_MESH && l.mesh.meshId >= c->hostInstances.size()) return fail_invalid("a mesh light refers to an instance that does not exist");
+    // ... and the alpha table (nxhip_set_material_alpha): index-parallel to the materials too; no MASK material on a mesh light
+    NX_TRY(check_alpha_table(c));
     if (c->lightSampling == NXHIP_LIGHTS_POWER) {  // an instance has ONE place in the light table (DeviceState::instLight)
         std::vector<bool> seen(c->hostInstances.size(), false);
         for (const nx_light& l : c->hostLights) {
@@ -179,6 +181,7 @@ int tail_bounce(const nxhip_ctx* c)
     // (the tail kernel traces its shadow rays with traverse_wave<true>, which knows no transmittance: a first version's restriction,
     //  DESIGN.md section 4 — the setting is ignored while the mode is in effect)
     if (transmit_active(c)) return 0;
+    if (c->materialsAlphaSolid) return 0;  // (... nor alpha modes: kFlavorAlphaTest / kFlavorSolid, below — the same restriction)
     if (c->h.mediumOn) return 0;  // (nor does the tail kernel know the medium: kFlavorMedium, below — the same restriction)
     int bounce = c->tailBounce;
     if (bounce < 0) {
@@ -241,6 +244,18 @@ constexpr int kFlavorMediumGrid = 16384;
 // (the type's metalness comes with the roughness map's lookup), so the bit implies the general material launch.  Without such a
 // material the bit is clear and the graphs are what they were, launch for launch.
 constexpr int kFlavorMetal = 32768;
+// kFlavorAlphaTest: some material of the alpha table is NX_ALPHA_MASK (nxhip_set_material_alpha; host-known, as materialsSeeThrough is) — the
+// closest-hit and any-hit launches are the ALPHA_TEST instances (nx_trace.hip), which look a MASK crossing's alpha up before they accept
+// it.  A first version's restrictions while the bit is set: no hand-over to the thin kernel and no thin launches (its search knows no
+// alpha), no IDENTITY and no ENTRY instance — nxhip_set_entry_points is ignored by the pass: an entry state walks past the first
+// triangles of a run of rays on the assumption that their tests are final — and no tail kernel (tail_bounce).  An all-BLEND table, or
+// none, keeps the bit clear and the graphs are the default ones, launch for launch.
+constexpr int kFlavorAlphaTest = 65536;
+// kFlavorSolid: some material of the alpha table is NX_ALPHA_MASK or NX_ALPHA_OPAQUE — the material launches of both pipelines are their SOLID
+// instances (nx_wavefront_solid.hip), in which a hit on such a material never passes through.  They are METAL and DETAIL instances as
+// well, so the bit implies the general material launch (no NO_MAPS form); and there is no tail kernel (tail_bounce).  kFlavorAlphaTest
+// is never set without it.
+constexpr int kFlavorSolid = 131072;
 inline bool materials_metal(const nxhip_ctx* c) { return ((c->materialTypeMask >> NX_MAT_METALROUGH) & 1u) != 0u; }
 int pass_flavor(const nxhip_ctx* c)
 {
@@ -279,6 +294,8 @@ int pass_flavor(const nxhip_ctx* c)
     if (transmit_active(c)) f |= kFlavorTransmit;
     if (c->h.mediumOn) f |= kFlavorMedium;
     if (c->h.mediumOn && c->h.mediumRho) f |= kFlavorMediumGrid;
+    if (c->materialsAlphaSolid) f = (f | kFlavorSolid) & ~kFlavorNoMaps;
+    if (c->materialsAlphaMask) f = (f | kFlavorAlphaTest) & ~(kFlavorEntry | kFlavorThin | kFlavorIdentity);
     return f & ~(c->flavorForceGeneral & kFlavorSpecialised);  // (test hook: nxhip_debug_pass_flavor)
 }
 
@@ -311,12 +328,15 @@ std::vector<std::vector<Launch>> frame_levels(nxhip_ctx* c, PassSlot* q)
     const bool identity = (pass_flavor(c) & kFlavorIdentity) != 0, noMaps = (pass_flavor(c) & kFlavorNoMaps) != 0;
     const bool analytic = (pass_flavor(c) & kFlavorAnalytic) != 0;
     const bool transmit = (pass_flavor(c) & kFlavorTransmit) != 0;
+    const bool solid = (pass_flavor(c) & kFlavorSolid) != 0;  // (then noMaps is off and tail_bounce is 0)
+    const bool alphaTest = (pass_flavor(c) & kFlavorAlphaTest) != 0;  // (then entry, identity and the thin flags below are all off: pass_flavor)
     const bool metal = (pass_flavor(c) & kFlavorMetal) != 0;
     const bool detail = (pass_flavor(c) & kFlavorDetail) != 0;
     const bool medium = (pass_flavor(c) & kFlavorMedium) != 0;
     const bool mediumGrid = (pass_flavor(c) & kFlavorMediumGrid) != 0;
     // the any-hit launch of a bounce: the TRANSMIT instance never hands over (no kTraceThinFlag) and has no IDENTITY form
     auto shadow_launch = [&](int shadowBlocksArg, int bounceArg, int thinFlagArg) {
+        if (alphaTest) return make_launch(kernels::trace_alpha(true, stats, transmit), shadowBlocksArg, kTraceBlockThreads, NXHIP_K_SHADOW, S, bounceArg);
         return transmit ? make_launch(kernels::trace_transmit(stats), shadowBlocksArg, kTraceBlockThreads, NXHIP_K_SHADOW, S, bounceArg)
                         : make_launch(kernels::trace(true, stats, identity), shadowBlocksArg, kTraceBlockThreads, NXHIP_K_SHADOW, S, bounceArg | thinFlagArg);
     };
@@ -327,7 +347,9 @@ std::vector<std::vector<Launch>> frame_levels(nxhip_ctx* c, PassSlot* q)
     //  launches of a SCAN pass with the fifth type hand nothing over; its any-hit launches do, and so does the classic pipeline, which has no codes)
     const int thinFlagClosest = (metal && scan_pipeline(c)) ? 0 : thinFlag;
     // (with entry points the primary launch is its own kernel instance: the only one that carries the install code)
-    levels.push_back({make_launch((entry && !stats) ? kernels::trace_entry(identity) : kernels::trace(false, stats, identity), traceBlocks, kTraceBlockThreads, NXHIP_K_TRACE, S,
+    // the closest-hit launch of a bounce (not the primary one with entry points, below)
+    auto closest_kernel = [&]() { return alphaTest ? kernels::trace_alpha(false, stats) : kernels::trace(false, stats, identity); };
+    levels.push_back({make_launch((entry && !stats) ? kernels::trace_entry(identity) : closest_kernel(), traceBlocks, kTraceBlockThreads, NXHIP_K_TRACE, S,
                                   (entry ? kTraceEntryFlag : 0) | thinFlagClosest | (scan_pipeline(c) ? kTraceScanFlag : 0))});
     // behind the trace launch(es) of a level: the rays their dry waves handed over, a wave each (thin_kernel)
     // — each trace launch of the level gets its own, chained to it alone, so that the closest-hit rays' searches run beside whatever
@@ -384,7 +406,7 @@ std::vector<std::vector<Launch>> frame_levels(nxhip_ctx* c, PassSlot* q)
             if (metal) mask |= 1 << kScanMetalBit;  // (the type's own number is the misses' bit: nx_device.h)
             // the medium's free-flight decision over the records the closest-hit level left, in front of the material launch that reads them
             if (medium) levels.push_back({make_launch(mediumGrid ? kernels::medium_scatter_grid(lightPower, analytic, metal) : kernels::medium_scatter(lightPower, analytic, metal), whole_regions(wide), kShadeBlockThreads, NXHIP_K_SHADE, S, bounce | dropFlag)});
-            levels.push_back({make_launch(kernels::shade_scan(lightPower, noMaps, analytic, detail, metal), og, kShadeBlockThreads, NXHIP_K_SHADE, S, bounce | dropFlag, mask)});
+            levels.push_back({make_launch(solid ? kernels::shade_scan_solid(lightPower, analytic) : kernels::shade_scan(lightPower, noMaps, analytic, detail, metal), og, kShadeBlockThreads, NXHIP_K_SHADE, S, bounce | dropFlag, mask)});
             if (bounce == 1) aov_beside(levels.back());
             if (in_use(NX_MAT_CONDUCTOR) && c->h.conductorMode != NX_CONDUCTOR_EXTENDED) {  // (counted, not shaded: count_scan_kernel)
                 levels.push_back({make_launch(kernels::count_scan(), lg, kWideBlockThreads, NXHIP_K_LOGIC, S, bounce, NX_MAT_CONDUCTOR)});
@@ -393,10 +415,10 @@ std::vector<std::vector<Launch>> frame_levels(nxhip_ctx* c, PassSlot* q)
                 // the shadow requests' attenuation is chained to the any-hit launch alone: the closest-hit launch of the level does not wait for it
                 Launch anyHit = shadow_launch(shadowBlocks, bounce, thinFlag);
                 anyHit.after = 1;
-                levels.push_back({make_launch(kernels::trace(false, stats, identity), traceBlocks, kTraceBlockThreads, NXHIP_K_TRACE, S, bounce | kTraceScanFlag | thinFlagClosest),
+                levels.push_back({make_launch(closest_kernel(), traceBlocks, kTraceBlockThreads, NXHIP_K_TRACE, S, bounce | kTraceScanFlag | thinFlagClosest),
                                   make_launch(mediumGrid ? kernels::medium_shadow_grid() : kernels::medium_shadow(), wide, wideThreads, NXHIP_K_SHADE, S, bounce), anyHit});
             } else {
-                levels.push_back({make_launch(kernels::trace(false, stats, identity), traceBlocks, kTraceBlockThreads, NXHIP_K_TRACE, S, bounce | kTraceScanFlag | thinFlagClosest),
+                levels.push_back({make_launch(closest_kernel(), traceBlocks, kTraceBlockThreads, NXHIP_K_TRACE, S, bounce | kTraceScanFlag | thinFlagClosest),
                                   shadow_launch(shadowBlocks, bounce, thinFlag)});
             }
             thin_level(bounce | kTraceScanFlag);
@@ -418,15 +440,17 @@ std::vector<std::vector<Launch>> frame_levels(nxhip_ctx* c, PassSlot* q)
         // graph insertion order of the reference: Diffuse, Plastic, Dielectric, Conductor (PathTracer.cpp:116-120)
         // (only the types some material of the scene has: a queue no material feeds stays empty)
         std::vector<Launch> shade;
-        if (in_use(NX_MAT_DIFFUSE)) shade.push_back(make_launch(kernels::shade(NX_MAT_DIFFUSE, lightPower, analytic, detail), og, ob, NXHIP_K_SHADE, S, bounce));
-        if (in_use(NX_MAT_PLASTIC)) shade.push_back(make_launch(kernels::shade(NX_MAT_PLASTIC, lightPower, analytic, detail), og, ob, NXHIP_K_SHADE, S, bounce));
-        if (in_use(NX_MAT_DIELECTRIC)) shade.push_back(make_launch(kernels::shade(NX_MAT_DIELECTRIC, lightPower, analytic, detail), og, ob, NXHIP_K_SHADE, S, bounce));
-        if (in_use(NX_MAT_CONDUCTOR) && c->h.conductorMode == NX_CONDUCTOR_EXTENDED) shade.push_back(make_launch(kernels::shade(NX_MAT_CONDUCTOR, lightPower, analytic, detail), og, ob, NXHIP_K_SHADE, S, bounce));
-        if (metal) shade.push_back(make_launch(kernels::shade_metal(lightPower, analytic), og, ob, NXHIP_K_SHADE, S, bounce));  // (after the reference's four)
-        if (shade.empty()) shade.push_back(make_launch(kernels::shade(NX_MAT_DIFFUSE, lightPower, analytic, detail), og, ob, NXHIP_K_SHADE, S, bounce));  // (a level cannot be empty)
+        // (a context with a MASK or an OPAQUE material: the SOLID instance of every type)
+        auto shade_kernel_of = [&](int type) { return solid ? kernels::shade_solid(type, lightPower, analytic) : type == NX_MAT_METALROUGH ? kernels::shade_metal(lightPower, analytic) : kernels::shade(type, lightPower, analytic, detail); };
+        if (in_use(NX_MAT_DIFFUSE)) shade.push_back(make_launch(shade_kernel_of(NX_MAT_DIFFUSE), og, ob, NXHIP_K_SHADE, S, bounce));
+        if (in_use(NX_MAT_PLASTIC)) shade.push_back(make_launch(shade_kernel_of(NX_MAT_PLASTIC), og, ob, NXHIP_K_SHADE, S, bounce));
+        if (in_use(NX_MAT_DIELECTRIC)) shade.push_back(make_launch(shade_kernel_of(NX_MAT_DIELECTRIC), og, ob, NXHIP_K_SHADE, S, bounce));
+        if (in_use(NX_MAT_CONDUCTOR) && c->h.conductorMode == NX_CONDUCTOR_EXTENDED) shade.push_back(make_launch(shade_kernel_of(NX_MAT_CONDUCTOR), og, ob, NXHIP_K_SHADE, S, bounce));
+        if (metal) shade.push_back(make_launch(shade_kernel_of(NX_MAT_METALROUGH), og, ob, NXHIP_K_SHADE, S, bounce));  // (after the reference's four)
+        if (shade.empty()) shade.push_back(make_launch(shade_kernel_of(NX_MAT_DIFFUSE), og, ob, NXHIP_K_SHADE, S, bounce));  // (a level cannot be empty)
         // serial slot order needs the kernels one after the other
         for (auto& l : shade) levels.push_back({l});
-        levels.push_back({make_launch(kernels::trace(false, stats, identity), traceBlocks, kTraceBlockThreads, NXHIP_K_TRACE, S, bounce | thinFlag),
+        levels.push_back({make_launch(closest_kernel(), traceBlocks, kTraceBlockThreads, NXHIP_K_TRACE, S, bounce | thinFlag),
                           shadow_launch(shadowBlocks, bounce, thinFlag)});
         thin_level(bounce);
     }

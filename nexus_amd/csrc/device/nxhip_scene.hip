@@ -91,6 +91,34 @@ void nxd::refresh_detail_maps(nxhip_ctx* c)
     c->shadeInstDirty = true;
 }
 
+// After anything that changes the alpha table (nxhip_set_material_alpha): is some material NX_ALPHA_MASK (kFlavorAlphaTest and the ray-batch
+// hooks read the fact), is some material not NX_ALPHA_BLEND (kFlavorSolid), and the per-instance records follow (refresh_shade_inst: ShadeInst::alphaMode / alphaCutoff).
+void nxd::refresh_alpha_modes(nxhip_ctx* c)
+{
+    c->materialsAlphaMask = c->materialsAlphaSolid = false;
+    for (const nx_material_alpha& a : c->hostMaterialAlpha) {
+        c->materialsAlphaMask = c->materialsAlphaMask || a.mode == (uint32_t)NX_ALPHA_MASK;
+        c->materialsAlphaSolid = c->materialsAlphaSolid || a.mode != (uint32_t)NX_ALPHA_BLEND;
+    }
+    c->shadeInstDirty = true;
+}
+
+// What a render and the ray-batch hooks refuse about the alpha table: a count that is not the material count, and a MASK material on an
+// instance that is a mesh light (the light sampler would pick points inside the holes).  Instance and material ids have been checked.
+int nxd::check_alpha_table(const nxhip_ctx* c)
+{
+    if (c->hostMaterialAlpha.empty()) return NXHIP_OK;
+    if (c->hostMaterialAlpha.size() != c->hostMaterials.size())
+        return fail_invalid("the material alpha table does not have one entry per material (nxhip_set_material_alpha)");
+    for (const nx_light& l : c->hostLights) {
+        if (l.type != NX_LIGHT_MESH || l.mesh.meshId >= c->hostInstances.size()) continue;
+        const int32_t m = c->hostInstances[l.mesh.meshId].materialId;
+        if (m >= 0 && (size_t)m < c->hostMaterialAlpha.size() && c->hostMaterialAlpha[(size_t)m].mode == (uint32_t)NX_ALPHA_MASK)
+            return fail_invalid("a mesh light's material is NX_ALPHA_MASK: holes in emitters are not supported (nxhip_set_material_alpha)");
+    }
+    return NXHIP_OK;
+}
+
 // The grid's words of the state block, from the context's grid and the medium's box: all 0 unless a medium with sigmaT > 0 AND a grid are
 // set, so a grid alone, or a medium alone, leaves the block what it was.  vscale and bscale in binary64, rounded once.
 void nxd::refresh_medium_grid(nxhip_ctx* c)
@@ -139,6 +167,8 @@ int nxd::refresh_shade_inst(nxhip_ctx* c)
     const size_t n = c->hostInstances.size();
     if (!c->hostMaterialDetail.empty() && c->hostMaterialDetail.size() != c->hostMaterialsDev.size())
         return fail_invalid("the material detail table does not have one entry per material (nxhip_set_material_detail)");
+    if (!c->hostMaterialAlpha.empty() && c->hostMaterialAlpha.size() != c->hostMaterialsDev.size())
+        return fail_invalid("the material alpha table does not have one entry per material (nxhip_set_material_alpha)");
     std::vector<nx_bvh_instance> inst(n);
     NX_SYNC_ALL(c);
     if (n) NX_HIP(hipMemcpy(inst.data(), c->instances.p, n * sizeof(nx_bvh_instance), hipMemcpyDeviceToHost));
@@ -156,14 +186,22 @@ int nxd::refresh_shade_inst(nxhip_ctx* c)
         rec[i].materialId = in.materialId;
         rec[i].material = c->hostMaterialsDev[(size_t)in.materialId];
         rec[i].seeThrough = material_see_through(c, rec[i].material) ? 1u : 0u;
+        if (!c->hostMaterialAlpha.empty()) {  // (none: NX_ALPHA_BLEND, cutoff 0 — the memset above)
+            rec[i].alphaMode = c->hostMaterialAlpha[(size_t)in.materialId].mode;
+            rec[i].alphaCutoff = c->hostMaterialAlpha[(size_t)in.materialId].cutoff;
+            // (an OPAQUE material's crossing ends a TRANSMIT shadow ray with no fetch: the instance's existing test; a MASK material's
+            //  is decided by the ALPHA_TEST instance before it looks here)
+            if (rec[i].alphaMode == (uint32_t)NX_ALPHA_OPAQUE) rec[i].seeThrough = 0u;
+        }
     }
     NX_ALLOC(c->shadeInst, rec.size() * sizeof(ShadeInst));
     NX_HIP(hipMemcpy(c->shadeInst.p, rec.data(), rec.size() * sizeof(ShadeInst), hipMemcpyHostToDevice));
     c->h.shadeInst = c->shadeInst.as<ShadeInst>();
     // the parallel array of detail records: entry i = the detail record of instance i's material; none while there is no table
     // (... unless a material is an NX_MAT_METALROUGH: its kernels are DETAIL instances and read the array, which then names no map)
+    // (... or the SOLID instances are in use, which are DETAIL instances as well: materialsAlphaSolid)
     const bool metal = ((c->materialTypeMask >> NX_MAT_METALROUGH) & 1u) != 0u;
-    if (c->hostMaterialDetail.empty() && !metal) {
+    if (c->hostMaterialDetail.empty() && !metal && !c->materialsAlphaSolid) {
         c->shadeDetail = DevBuf();
         c->h.shadeDetail = nullptr;
     } else {
@@ -915,6 +953,26 @@ try {
     refresh_detail_maps(c);  // (the pass graphs follow by their flavor: kFlavorDetail)
     return NXHIP_OK;
 } NX_CATCH("nxhip_set_material_detail")
+
+// Alpha modes (include/nexus_hip.h): checked on the host before anything changes, as the detail table is; the count against the material
+// table and the mesh-light refusal when a pass or a hook is about to follow the table (check_alpha_table).
+int nxhip_set_material_alpha(nxhip_ctx* c, const nx_material_alpha* alphas, uint32_t count)
+try {
+    NX_CHECK_CTX(c);
+    if (count && !alphas) return fail_invalid("nxhip_set_material_alpha: null array");
+    for (uint32_t i = 0; i < count; i++) {
+        const std::string who = "nxhip_set_material_alpha: entry " + std::to_string(i);
+        if (alphas[i].mode != (uint32_t)NX_ALPHA_BLEND && alphas[i].mode != (uint32_t)NX_ALPHA_MASK && alphas[i].mode != (uint32_t)NX_ALPHA_OPAQUE)
+            return fail_invalid(who + ": unknown mode");
+        if (alphas[i].mode == (uint32_t)NX_ALPHA_MASK && !(std::isfinite(alphas[i].cutoff) && alphas[i].cutoff >= 0.0f && alphas[i].cutoff <= 1.0f))
+            return fail_invalid(who + ": a MASK cutoff must be finite and lie in [0, 1]");
+    }
+    NX_HIP(hipSetDevice(c->device));
+    NX_SYNC_ALL(c);
+    c->hostMaterialAlpha.assign(alphas, alphas + (alphas ? count : 0));
+    refresh_alpha_modes(c);  // (the pass graphs follow by their flavor: kFlavorAlphaTest)
+    return NXHIP_OK;
+} NX_CATCH("nxhip_set_material_alpha")
 
 int nxhip_set_lights(nxhip_ctx* c, const nx_light* lights, uint32_t count)
 try {

@@ -17,6 +17,8 @@ void AssetManager::Reset()
     m_RoughnessMaps.clear();
     if (!m_MaterialDetails.empty()) detailsDirty = true;  // (the device must hear that the table is gone)
     m_MaterialDetails.clear();
+    if (!m_MaterialAlphas.empty()) alphasDirty = true;
+    m_MaterialAlphas.clear();
     m_Meshes.clear();
     m_Bvhs.clear();
     m_DeformedBvhs.clear();
@@ -127,6 +129,27 @@ std::vector<MaterialDetail> AssetManager::GetMaterialDetails() const
 {
     std::vector<MaterialDetail> out = m_MaterialDetails;
     if (!out.empty()) out.resize(m_Materials.size());  // (materials added since carry no maps)
+    return out;
+}
+
+void AssetManager::SetMaterialAlpha(int materialId, const nx_material_alpha& alpha)
+{
+    if (materialId < 0 || static_cast<size_t>(materialId) >= m_Materials.size()) throw std::runtime_error("AssetManager::SetMaterialAlpha: no such material");
+    if (m_MaterialAlphas.size() <= static_cast<size_t>(materialId)) m_MaterialAlphas.resize(static_cast<size_t>(materialId) + 1, nx_material_alpha{NX_ALPHA_BLEND, 0.5f});
+    m_MaterialAlphas[static_cast<size_t>(materialId)] = alpha;
+    alphasDirty = true;
+}
+
+void AssetManager::ClearMaterialAlphas()
+{
+    m_MaterialAlphas.clear();
+    alphasDirty = true;
+}
+
+std::vector<nx_material_alpha> AssetManager::GetMaterialAlphas() const
+{
+    std::vector<nx_material_alpha> out = m_MaterialAlphas;
+    if (!out.empty()) out.resize(m_Materials.size(), nx_material_alpha{NX_ALPHA_BLEND, 0.5f});  // (materials added since blend)
     return out;
 }
 

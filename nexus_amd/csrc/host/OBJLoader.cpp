@@ -445,6 +445,20 @@ LoadedScene parse_glb(const std::string& file, const LoadOptions& options)
             out.materialNormalTexture.push_back(nt ? load_texture(*nt, Texture::Type::NORMAL) : -1);
             out.materialRoughnessTexture.push_back(rt ? load_texture(*rt, Texture::Type::ROUGHNESS) : -1);
             out.materialNormalScale.push_back(nt ? static_cast<float>(nt->number("scale", 1.0)) : 1.0f);
+            if (options.alphaModes) {
+                nx_material_alpha a;
+                a.mode = NX_ALPHA_OPAQUE;  // glTF's default
+                if (const Json* mode = m.find("alphaMode")) {
+                    if (mode->kind != Json::String || (mode->str != "OPAQUE" && mode->str != "MASK" && mode->str != "BLEND")) fail("glb: material " + std::to_string(i) + " has an unknown alphaMode");
+                    a.mode = mode->str == "MASK" ? NX_ALPHA_MASK : mode->str == "BLEND" ? NX_ALPHA_BLEND : NX_ALPHA_OPAQUE;
+                }
+                a.cutoff = static_cast<float>(m.number("alphaCutoff", 0.5));
+                // (glTF asks for >= 0 only; above 1 nothing would pass, which the device's table — cutoff in [0, 1] — cannot say: refused here,
+                //  by the material's number, not at the device update)
+                if (a.mode == NX_ALPHA_MASK && !(a.cutoff >= 0.0f && a.cutoff <= 1.0f))
+                    fail("glb: material " + std::to_string(i) + " has alphaMode MASK with an alphaCutoff outside [0, 1]");
+                out.materialAlpha.push_back(a);
+            }
         }
     if (out.materials.empty()) {
         Material m;  // pod.make_material() defaults
@@ -456,6 +470,7 @@ LoadedScene parse_glb(const std::string& file, const LoadOptions& options)
         out.materialNormalTexture.push_back(-1);
         out.materialRoughnessTexture.push_back(-1);
         out.materialNormalScale.push_back(1.0f);
+        if (options.alphaModes) out.materialAlpha.push_back(nx_material_alpha{NX_ALPHA_OPAQUE, 0.5f});  // (no map: the same thing as a blend)
     }
 
     // one mesh per primitive (what Assimp hands the reference, OBJLoader.cpp:165-181)
@@ -713,6 +728,7 @@ void OBJLoader::LoadOBJ(const std::string& path, const std::string& filename, Sc
             d.normalScale = ls.materialNormalScale[i];
             assetManager->SetMaterialDetail(id, d);
         }
+        if (i < ls.materialAlpha.size()) assetManager->SetMaterialAlpha(id, ls.materialAlpha[i]);
     }
     // one BVH8 per mesh of the file (OBJLoader.cpp:213-239) — created together, so that a device builder can build them in one go
     std::vector<int32_t> meshIds;

@@ -178,6 +178,9 @@ void PathTracer::UpdateDeviceScene(const Scene& scene)
     // the detail table runs parallel to the materials: it follows a change of either (count 0 while no material has detail maps)
     const std::vector<MaterialDetail> details = assets.GetMaterialDetails();
     const bool sendDetails = assets.detailsDirty || (assets.materialsDirty && !details.empty());
+    // ... and so does the alpha table (count 0 while no material has a mode)
+    const std::vector<nx_material_alpha> alphas = assets.GetMaterialAlphas();
+    const bool sendAlphas = assets.alphasDirty || (assets.materialsDirty && !alphas.empty());
     if (assets.materialsDirty && !assets.GetMaterials().empty()) {
         Check(nxhip_set_materials(m_Ctx, assets.GetMaterials().data(), static_cast<uint32_t>(assets.GetMaterials().size())), "nxhip_set_materials");
         mutableAssets.materialsDirty = false;
@@ -185,6 +188,10 @@ void PathTracer::UpdateDeviceScene(const Scene& scene)
     if (sendDetails) {
         Check(nxhip_set_material_detail(m_Ctx, details.data(), static_cast<uint32_t>(details.size())), "nxhip_set_material_detail");
         mutableAssets.detailsDirty = false;
+    }
+    if (sendAlphas) {
+        Check(nxhip_set_material_alpha(m_Ctx, alphas.data(), static_cast<uint32_t>(alphas.size())), "nxhip_set_material_alpha");
+        mutableAssets.alphasDirty = false;
     }
     if (scene.tlasDirty && scene.UsesDeviceTlasBuild() && !scene.GetBVHInstances().empty()) {
         // the TLAS is built where it is used: instances (with the world bounds SetTransform gave them) go up, the tree never

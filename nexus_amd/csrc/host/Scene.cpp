@@ -122,6 +122,7 @@ void Scene::CreateMeshInstanceFromFile(const std::string& path, const std::strin
 {
     LoadOptions options;
     options.metalRough = m_MetalRoughMaterials;
+    options.alphaModes = m_MaterialAlphaModes;
     OBJLoader::LoadOBJ(path, fileName, this, &m_AssetManager, options);
     Invalidate();  // the TLAS is rebuilt by the next Update()
 }

@@ -81,6 +81,9 @@ class LoadedScene:
         self.material_normal_texture = []      # per material: index into detail_textures, -1 = none
         self.material_roughness_texture = []
         self.material_normal_scale = []        # per material: normalTexture.scale (1.0 without one)
+        # glTF alphaMode / alphaCutoff, one pod.ALPHA_DT record per material (nxhip_set_material_alpha); None unless the reader was asked
+        # (load_glb(alpha_modes=True)): every existing scene keeps rendering its alpha as a stochastic blend
+        self.material_alpha = None
         self.analytic_lights = np.zeros(0, dtype=pod.ALIGHT_DT)  # glTF KHR_lights_punctual: one per node that carries a light, world space
         self.warnings = []
 
@@ -332,9 +335,14 @@ def _gltf_material(m, metal_rough=False):
                              opacity=float(base[3]) if len(base) > 3 else 1.0)
 
 
-def load_glb(path, metal_rough=False):
+_GLTF_ALPHA = {"OPAQUE": pod.ALPHA_OPAQUE, "MASK": pod.ALPHA_MASK, "BLEND": pod.ALPHA_BLEND}
+
+
+def load_glb(path, metal_rough=False, alpha_modes=False):
     """metal_rough (off by default: glTF's default metallicFactor is 1): materials without transmission become MAT_METALROUGH with the
-    file's raw factors instead of the reference's PLASTIC"""
+    file's raw factors instead of the reference's PLASTIC
+    alpha_modes (off by default: every existing scene renders as before): the materials' alphaMode (glTF's default: OPAQUE) and
+    alphaCutoff (default 0.5) fill LoadedScene.material_alpha"""
     data = open(path, "rb").read()
     magic, version, _length = struct.unpack_from("<III", data, 0)
     if magic != 0x46546C67 or version != 2:
@@ -413,6 +421,19 @@ def load_glb(path, metal_rough=False):
         out.material_normal_texture, out.material_roughness_texture, out.material_normal_scale = [-1], [-1], [1.0]
     mats = [_gltf_material(m, metal_rough) for m in doc.get("materials", [])]
     out.material_names = [m.get("name", "") for m in doc.get("materials", [])]
+    if alpha_modes:
+        alphas = []
+        for k, m in enumerate(doc.get("materials", [])):
+            mode = m.get("alphaMode", "OPAQUE")
+            if mode not in _GLTF_ALPHA:
+                raise ValueError("glb: material %d has the unknown alphaMode %r" % (k, mode))
+            cutoff = float(m.get("alphaCutoff", 0.5))
+            # (glTF asks for >= 0 only; above 1 nothing would pass, which the device's table — cutoff in [0, 1] — cannot say: refused here)
+            if mode == "MASK" and not (0.0 <= cutoff <= 1.0):
+                raise ValueError("glb: material %d has alphaMode MASK with an alphaCutoff outside [0, 1]" % k)
+            alphas.append(pod.make_material_alpha(_GLTF_ALPHA[mode], cutoff))
+        # (a file without materials gets the default material, which has no map: OPAQUE and BLEND are the same thing there)
+        out.material_alpha = np.array(alphas if alphas else [pod.make_material_alpha(pod.ALPHA_OPAQUE)], dtype=pod.ALPHA_DT)
     out.materials = np.array(mats, dtype=pod.MAT_DT) if mats else np.array([pod.make_material()], dtype=pod.MAT_DT)
 
     # one mesh per primitive (what Assimp hands the reference)

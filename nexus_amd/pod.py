@@ -76,6 +76,10 @@ assert ALIGHT_DT.itemsize == 64
 # nx_material_detail (extension, nxhip_set_material_detail): 16 bytes, index-parallel to the material table; -1 = no map
 DETAIL_DT = np.dtype([("normalMapId", "<i4"), ("roughnessMapId", "<i4"), ("normalScale", "<f4"), ("pad_", "<u4")])
 assert DETAIL_DT.itemsize == 16
+# nx_material_alpha (extension, nxhip_set_material_alpha): 8 bytes, index-parallel to the material table
+ALPHA_BLEND, ALPHA_MASK, ALPHA_OPAQUE = 0, 1, 2
+ALPHA_DT = np.dtype([("mode", "<u4"), ("cutoff", "<f4")])
+assert ALPHA_DT.itemsize == 8
 
 # nx_medium (extension, nxhip_set_medium): 48 bytes — fog, one homogeneous medium in a world-space box
 MEDIUM_DT = np.dtype([("boxMin", "<f4", 3), ("sigmaT", "<f4"), ("boxMax", "<f4", 3), ("g", "<f4"), ("albedo", "<f4", 3), ("pad", "<u4")])
@@ -171,6 +175,14 @@ def make_material(type=MAT_DIFFUSE, albedo=(0.8, 0.8, 0.8), roughness=0.0, ior=1
     m["emissiveMapId"] = emissive_map
     m["type"] = type
     return m
+
+
+def make_material_alpha(mode=ALPHA_BLEND, cutoff=0.5):
+    """one nx_material_alpha record: ALPHA_BLEND (the default: a stochastic blend) or ALPHA_MASK with glTF's alphaCutoff"""
+    a = np.zeros((), dtype=ALPHA_DT)
+    a["mode"] = mode
+    a["cutoff"] = cutoff
+    return a
 
 
 def make_material_detail(normal_map=-1, roughness_map=-1, normal_scale=1.0):

@@ -53,6 +53,8 @@ class Workload:
     normal_maps = ()
     roughness_maps = ()
     material_detail = None
+    # extension: how the materials' alpha is read — one pod.ALPHA_DT record per material, None: every material blends (nxhip_set_material_alpha); applied by upload
+    material_alpha = None
     # extension: fog — a pod.MEDIUM_DT record (pod.make_medium), None: no medium (nxhip_set_medium); applied by upload
     medium = None
     # ... and its density grid: a float32 array (nz, ny, nx) over the medium's box, None: none (nxhip_set_medium_density); applied by upload
@@ -127,6 +129,7 @@ class Workload:
         for img in self.roughness_maps:
             ctx.upload_texture("roughness", img)
         ctx.set_material_detail(self.material_detail if self.material_detail is not None else [])
+        ctx.set_material_alpha(self.material_alpha if self.material_alpha is not None else [])
         if self.hdr_map is not None:
             # a float32 H x W x 3 array is linear radiance (nxhip_upload_env_float); anything else the RGBA8 map it has always been
             if isinstance(self.hdr_map, np.ndarray) and self.hdr_map.dtype == np.float32:
