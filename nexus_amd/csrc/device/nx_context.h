@@ -241,11 +241,9 @@ struct nxhip_ctx : nxd::PassSlot {
     nxd::DevBuf mgpuGathered, mgpuMaps, mgpuFullAccum, mgpuFullRgba8;
 
     int traceBlocks = 0, shadowBlocks = 0, wideBlocks = 0;  // full-chip persistent grids (see trace_blocks)
-    int tailBlocks = 0;
-    int tailBlocksPower = 0;  // grid of tail_kernel<true> (NXHIP_LIGHTS_POWER), from that instance's own occupancy
-    int tailBlocksAnalytic[2] = {0, 0};  // grids of tail_kernel<POWER, true> (analytic lights: kFlavorAnalytic), [0] uniform, [1] POWER
-    int tailBlocksMetal[2][2] = {{0, 0}, {0, 0}};   // grids of tail_kernel<POWER, ANALYTIC, true, true> (an NX_MAT_METALROUGH material: kFlavorMetal), [power][analytic]
-    int tailBlocksDetail[2][2] = {{0, 0}, {0, 0}};  // grids of tail_kernel<POWER, ANALYTIC, true> (detail maps: kFlavorDetail), [power][analytic]
+    // grids of the tail kernel's instances, each from its OWN occupancy (the default mode's grid does not depend on another instance's),
+    // indexed by the instance's feature set (nx_variants.h kMf*; 0: no tail instance of that set — nxhip_create fills it)
+    int tailBlocks[64] = {};
     int tailBounce = -1;  // first bounce of the tail kernel, 0 = off, -1 = automatic (see tail_bounce in nxhip_render.hip)
     bool traceGridForced = false;                            // NX_TRACE_BLOCKS_*: use them as they are
     int shadeBlocksPerCU = 10, logicBlocksPerCU = 2;  // grid-stride kernels: workgroups per CU

@@ -7,24 +7,25 @@
 #include <vector>
 
 #include "nx_context.h"
+#include "nx_variants.h"
 
 namespace nxd {
 
 // ---- what the kernel units export ---------------------------------------------------------------------
 // nx_lbvh.hip, nx_lights.hip and nxhip_multigpu.hip include this header, so the compiler checks their declarations against the
 // definitions.  The getters of the other kernel units are declared here as they are defined there (nx_trace.hip, nx_entry.hip
-// and nx_wavefront.hip cannot include it: their text is pinned by bench.py's source hash).
-const void* trace_kernel_ptr(bool anyHit, bool stats, bool identity = false);  // nx_trace.hip
-const void* trace_transmit_kernel_ptr(bool stats);  // the any-hit TRANSMIT instance (nxhip_set_shadow_transmittance)
-const void* trace_alpha_kernel_ptr(bool anyHit, bool stats, bool transmit);  // the ALPHA_TEST instances (nxhip_set_material_alpha with a MASK material)
-const void* trace_entry_kernel_ptr(bool identity = false);
-const void* thin_kernel_ptr();
+// and nx_wavefront.hip do not include it).
+// The kernel families with compile-time instances: one lookup per family and unit, keyed by the feature set (nx_variants.h: kTf* for
+// the trace kernel, kMf* for the rest) and the material type where there is one; nullptr for a set the unit does not hold.
+const void* trace_kernel_of(unsigned set);  // nx_trace.hip
+namespace wavefront { const void* logic(int items, unsigned set); const void* shade(int type, unsigned set); const void* shade_scan(unsigned set); const void* tail(unsigned set); }  // nx_wavefront.hip
+namespace wavefront_detail { const void* shade(int type, unsigned set); const void* shade_scan(unsigned set); const void* tail(unsigned set); }  // the DETAIL instances (kFlavorDetail)
+namespace wavefront_metal { const void* shade(int type, unsigned set); const void* shade_scan(unsigned set); const void* tail(unsigned set); }  // the METAL instances (kFlavorMetal); shade: the fifth type's
+namespace wavefront_solid { const void* shade(int type, unsigned set); const void* shade_scan(unsigned set); }  // the SOLID instances (kFlavorSolid): METAL and DETAIL ones too; no tail kernel
+const void* medium_scatter_kernel_of(bool grid, unsigned set);  // nx_medium.hip: the medium's kernels (kFlavorMedium; grid: kFlavorMediumGrid) and its hooks'
+const void* thin_kernel_ptr();  // nx_trace.hip
 const void* entry_state_kernel_ptr();  // nx_entry.hip
-const void* tail_kernel_ptr(bool lightPower, bool analytic = false);  // nx_wavefront.hip
-const void* logic_kernel_ptr(int items, bool analytic = false);
-const void* shade_kernel_ptr(int type, bool lightPower, bool analytic = false);
-const void* shade_scan_kernel_ptr(bool lightPower, bool noMaps = false, bool analytic = false);
-const void* count_scan_kernel_ptr();
+const void* count_scan_kernel_ptr();  // nx_wavefront.hip
 const void* begin_frame_kernel_ptr();
 const void* hook_sizes_kernel_ptr();
 const void* generate_kernel_ptr();
@@ -36,25 +37,15 @@ const void* tex2d_hook_kernel_ptr();
 const void* env_hook_kernel_ptr();
 const void* alight_hook_kernel_ptr();
 const void* tex2d_float_hook_kernel_ptr();
-const void* shade_detail_kernel_ptr(int type, bool lightPower, bool analytic);  // nx_wavefront_detail.hip: the DETAIL instances (kFlavorDetail)
-const void* shade_scan_detail_kernel_ptr(bool lightPower, bool analytic);
-const void* tail_detail_kernel_ptr(bool lightPower, bool analytic);
-const void* shading_frame_hook_kernel_ptr();
-const void* shade_scan_metal_kernel_ptr(bool lightPower, bool analytic);  // nx_wavefront_metal.hip: the METAL instances (kFlavorMetal)
-const void* tail_metal_kernel_ptr(bool lightPower, bool analytic);
-const void* bsdf_hook_metal_kernel_ptr();
-const void* logic_metal_kernel_ptr();  // (the classic pipeline's fifth queue and its material kernel)
-const void* shade_metal_kernel_ptr(bool lightPower, bool analytic);
-const void* material_inputs_hook_kernel_ptr();
-const void* shade_scan_solid_kernel_ptr(bool lightPower, bool analytic);  // nx_wavefront_solid.hip: the SOLID instances (kFlavorSolid); METAL and DETAIL instances too
-const void* shade_solid_kernel_ptr(int type, bool lightPower, bool analytic);
+const void* shading_frame_hook_kernel_ptr();  // nx_wavefront_detail.hip
 const void* tex2d_linear_hook_kernel_ptr();
-const void* medium_scatter_kernel_ptr(bool lightPower, bool analytic, bool metal = false);  // nx_medium.hip: the medium's kernels (kFlavorMedium) and its hooks'
-const void* medium_shadow_kernel_ptr();
+const void* bsdf_hook_metal_kernel_ptr();  // nx_wavefront_metal.hip
+const void* logic_metal_kernel_ptr();  // (the classic pipeline's fifth queue)
+const void* material_inputs_hook_kernel_ptr();
+const void* medium_shadow_kernel_ptr();  // nx_medium.hip
 const void* medium_segment_hook_kernel_ptr();
 const void* medium_phase_hook_kernel_ptr();
-const void* medium_scatter_grid_kernel_ptr(bool lightPower, bool analytic, bool metal = false);  // ... the density grid's instances (kFlavorMediumGrid), its build and its hooks'
-const void* medium_shadow_grid_kernel_ptr();
+const void* medium_shadow_grid_kernel_ptr();  // ... the density grid's (kFlavorMediumGrid), its build and its hooks'
 const void* medium_brick_kernel_ptr();
 const void* medium_density_hook_kernel_ptr();
 const void* medium_track_hook_kernel_ptr();
@@ -137,29 +128,24 @@ using U32 = uint32_t;
 using StateKernel = Kernel<State>;            // (S)
 using BounceKernel = Kernel<State, int>;      // (S, bounce | flags)
 using TypeKernel = Kernel<State, int, int>;   // (S, bounce | flags, type or type mask)
-inline BounceKernel trace(bool anyHit, bool stats, bool identity = false) { return {trace_kernel_ptr(anyHit, stats, identity)}; }  // (identity: pass graphs only)
-inline BounceKernel trace_transmit(bool stats) { return {trace_transmit_kernel_ptr(stats)}; }  // (any hit; pass graphs of kFlavorTransmit and nxhip_trace_transmittance_batch)
-inline BounceKernel trace_alpha(bool anyHit, bool stats, bool transmit = false) { return {trace_alpha_kernel_ptr(anyHit, stats, transmit)}; }  // (pass graphs of kFlavorAlphaTest and the ray-batch hooks over such a table)
-inline BounceKernel trace_entry(bool identity = false) { return {trace_entry_kernel_ptr(identity)}; }
+// The families with compile-time instances, one getter each: the owning unit is asked for the set's instance.  The caller has made the
+// set canonical (nxhip_render.hip material_features / trace_features): nothing is dropped here, and a set nobody compiled gives
+// fn == nullptr, which no launch is made of (frame_levels and the ray-batch hooks refuse: NXHIP_ERR_INVALID).
+inline BounceKernel trace(unsigned set) { return {trace_kernel_of(set)}; }
 inline BounceKernel thin() { return {thin_kernel_ptr()}; }
 inline StateKernel entry_state() { return {entry_state_kernel_ptr()}; }
-// (detail: the DETAIL instances of a context whose materials name normal or roughness maps — nx_wavefront_detail.hip)
-// (metal: the METAL instances of a context with an NX_MAT_METALROUGH material — nx_wavefront_metal.hip; they are DETAIL instances too)
-inline BounceKernel tail(bool lightPower, bool analytic = false, bool detail = false, bool metal = false)
-{
-    return {metal ? tail_metal_kernel_ptr(lightPower, analytic) : detail ? tail_detail_kernel_ptr(lightPower, analytic) : tail_kernel_ptr(lightPower, analytic)};
-}
+inline BounceKernel logic(int items, unsigned set) { return {wavefront::logic(items, set)}; }
 inline BounceKernel logic_metal() { return {logic_metal_kernel_ptr()}; }
-inline BounceKernel shade_metal(bool lightPower, bool analytic) { return {shade_metal_kernel_ptr(lightPower, analytic)}; }
-inline BounceKernel logic(int items, bool analytic = false) { return {logic_kernel_ptr(items, analytic)}; }
-inline BounceKernel shade(int type, bool lightPower, bool analytic = false, bool detail = false) { return {detail ? shade_detail_kernel_ptr(type, lightPower, analytic) : shade_kernel_ptr(type, lightPower, analytic)}; }
-inline TypeKernel shade_scan(bool lightPower, bool noMaps = false, bool analytic = false, bool detail = false, bool metal = false)
+// (the units split the material kernels' instances by their newest feature: nx_wavefront_detail.hip says why the split exists)
+inline BounceKernel tail(unsigned set) { return {(set & kMfMetal) ? wavefront_metal::tail(set) : (set & kMfDetail) ? wavefront_detail::tail(set) : wavefront::tail(set)}; }
+inline TypeKernel shade_scan(unsigned set)
 {
-    return {metal ? shade_scan_metal_kernel_ptr(lightPower, analytic) : detail ? shade_scan_detail_kernel_ptr(lightPower, analytic) : shade_scan_kernel_ptr(lightPower, noMaps, analytic)};
+    return {(set & kMfSolid) ? wavefront_solid::shade_scan(set) : (set & kMfMetal) ? wavefront_metal::shade_scan(set) : (set & kMfDetail) ? wavefront_detail::shade_scan(set) : wavefront::shade_scan(set)};
 }
-// (solid: the SOLID instances of a context with an NX_ALPHA_MASK or NX_ALPHA_OPAQUE material — nx_wavefront_solid.hip; all five types, detail records)
-inline BounceKernel shade_solid(int type, bool lightPower, bool analytic) { return {shade_solid_kernel_ptr(type, lightPower, analytic)}; }
-inline TypeKernel shade_scan_solid(bool lightPower, bool analytic) { return {shade_scan_solid_kernel_ptr(lightPower, analytic)}; }
+inline BounceKernel shade(int type, unsigned set)  // (classic pipeline: the set names no METAL, the type does)
+{
+    return {(set & kMfSolid) ? wavefront_solid::shade(type, set) : type == NX_MAT_METALROUGH ? wavefront_metal::shade(type, set) : (set & kMfDetail) ? wavefront_detail::shade(type, set) : wavefront::shade(type, set)};
+}
 inline TypeKernel count_scan() { return {count_scan_kernel_ptr()}; }
 inline Kernel<DeviceState*, U32, U32, U32> begin_frame() { return {begin_frame_kernel_ptr()}; }  // (S, frames, frameLast, scanEpoch)
 inline Kernel<DeviceState*, U32, int, int> hook_sizes() { return {hook_sizes_kernel_ptr()}; }    // (S, n, anyHit, slot)
@@ -179,13 +165,12 @@ inline Kernel<TextureDev, const float*, U32, float4*> tex2d_linear_hook() { retu
 inline Kernel<State, U32, const U32*, const float*, const float*, U32, float*, float*, U32*> shading_frame_hook() { return {shading_frame_hook_kernel_ptr()}; }
 // (S, light, origin, r, count, direction, tmax, factor, ok)
 inline Kernel<State, U32, const float*, const float*, U32, float*, float*, float*, U32*> alight_hook() { return {alight_hook_kernel_ptr()}; }
-inline BounceKernel medium_scatter(bool lightPower, bool analytic, bool metal = false) { return {medium_scatter_kernel_ptr(lightPower, analytic, metal)}; }  // (S, bounce | kShadeDropEnded)
+inline BounceKernel medium_scatter(bool grid, unsigned set) { return {medium_scatter_kernel_of(grid, set)}; }  // (S, bounce | kShadeDropEnded)
 inline BounceKernel medium_shadow() { return {medium_shadow_kernel_ptr()}; }
 // (S, origin, dir, tEnd, xi, count, t0, length, transmittance, scatterT)
 inline Kernel<State, const float*, const float*, const float*, const float*, U32, float*, float*, float*, float*> medium_segment_hook() { return {medium_segment_hook_kernel_ptr()}; }
 // (S, dirIn, xi1, xi2, count, dirOut, pdf)
 inline Kernel<State, const float*, const float*, const float*, U32, float*, float*> medium_phase_hook() { return {medium_phase_hook_kernel_ptr()}; }
-inline BounceKernel medium_scatter_grid(bool lightPower, bool analytic, bool metal = false) { return {medium_scatter_grid_kernel_ptr(lightPower, analytic, metal)}; }
 inline BounceKernel medium_shadow_grid() { return {medium_shadow_grid_kernel_ptr()}; }
 // (rho, nx, ny, nz, nbx, nby, nbz, bricks)
 inline Kernel<const float*, U32, U32, U32, U32, U32, U32, float*> medium_brick() { return {medium_brick_kernel_ptr()}; }
@@ -351,6 +336,7 @@ int refresh_updated_blas(nxhip_ctx* c);
 int check_scene_ready(nxhip_ctx* c);
 int launch_now(nxhip_ctx* c, const Launch& l, hipStream_t stream = nullptr);  // (stream: the context's own unless given)
 int render_pass(nxhip_ctx* c, uint32_t framesArg);
+unsigned hook_trace_features(const nxhip_ctx* c, bool anyHit, bool transmit);  // the ray-batch hooks' trace launch, by the passes' own rule (trace_features)
 uint32_t queue_budget_from_text(const char* text);  // what a value of GPU_MAX_HW_QUEUES means: a whole number in [1, 32], else 4
 uint32_t queue_budget_from_environment();           // ... of the variable as it is now (nxhip_create, nxhip_set_queue_budget)
 int read_float4_as_float3(nxhip_ctx* c, const void* dev, uint32_t count, float* dst);

@@ -12,7 +12,7 @@
 // Also here: the two test hooks' kernels over the same device functions.
 //
 // The density grid (nxhip_set_medium_density; the rule: include/nexus_hip.h): extinction sigmaT x rho(p), rho a trilinear lookup in a voxel
-// grid over the box.  Both kernels have a GRID instance beside the homogeneous one (medium_scatter_kernel<.., GRID = true>, and the sibling
+// grid over the box.  Both kernels have a GRID instance beside the homogeneous one (medium_scatter_kernel<GRID = true, ..>, and the sibling
 // medium_shadow_grid_kernel; in the pass graphs under kFlavorMediumGrid): a per-lane 3-D DDA over bricks of 8 x 8 x 8 voxels with a majorant
 // each — delta tracking for the free flight, ratio tracking for the shadow requests.  The homogeneous instances keep their code, instruction
 // for instruction (profiles/medium_grid.txt).  medium_brick_kernel builds the majorants on the device; three hooks (lookup, walk, majorants)
@@ -251,9 +251,11 @@ __global__ void __launch_bounds__(kWideBlock) medium_brick_kernel(const float* _
 // walk different numbers of bricks, so a tile costs what its longest walk costs.
 // METAL (a context with an NX_MAT_METALROUGH material: kFlavorMetal): the fifth material type's code is a hit like the other four's; the
 // instances with METAL = false are the code of a context without such a material.
-template <bool POWER, bool ANALYTIC, bool GRID, bool METAL = false>
+template <bool GRID, unsigned F>  // (F: POWER, ANALYTIC — next_event_estimation — and METAL)
 __global__ void __launch_bounds__(kShadeBlock) medium_scatter_kernel(const DeviceState* __restrict__ S, const int bounceArg)
 {
+    constexpr bool ANALYTIC = (F & kMfAnalytic) != 0u, METAL = (F & kMfMetal) != 0u;
+    static_assert(medium_set_ok(F), "medium_scatter_kernel reads POWER, ANALYTIC and METAL alone (nx_variants.h)");
     const int bounce = bounceArg & 0xff;
     const bool dropEnded = (bounceArg & kShadeDropEnded) != 0;
     const int region = (int)(blockIdx.x & (kQueueShards - 1));
@@ -322,7 +324,7 @@ __global__ void __launch_bounds__(kShadeBlock) medium_scatter_kernel(const Devic
                             mp.ior = g2;
                             mp.cIor = d;
                             mp.cK = mk3(oneMinusG2, 0.0f, 0.0f);
-                            wantShadow = next_event_estimation<kMatPhase, POWER, false, ANALYTIC>(S, mk3(0.0f, 0.0f, 1.0f), mp, x, mk3(0.0f, 0.0f, 1.0f), mk3(0.0f), beta, rng, sh);
+                            wantShadow = next_event_estimation<kMatPhase, F>(S, mk3(0.0f, 0.0f, 1.0f), mp, x, mk3(0.0f, 0.0f, 1.0f), mk3(0.0f), beta, rng, sh);
                         }
                         const float xi1 = rng_next(rng), xi2 = rng_next(rng);
                         nextDir = phase_sample(g, g2, oneMinusG2, d, xi1, xi2, nextPdf);
@@ -480,30 +482,18 @@ __global__ void __launch_bounds__(kWideBlock) medium_track_hook_kernel(const Dev
     }
 }
 
-const void* medium_scatter_grid_kernel_ptr(bool lightPower, bool analytic, bool metal)
+// (POWER and ANALYTIC: next_event_estimation's instances, chosen as the material launch's are — nxhip_render.hip; METAL: the fifth type's hit code)
+using MediumSets = Instances<kMfPower | kMfAnalytic | kMfMetal, kMfAnalytic | kMfMetal, kMfPower | kMfMetal, kMfMetal, kMfPower | kMfAnalytic, kMfAnalytic, kMfPower, 0u>;
+template <bool GRID> const void* medium_scatter_instance(unsigned set)
 {
-    if (metal) {
-        if (analytic) return lightPower ? (const void*)medium_scatter_kernel<true, true, true, true> : (const void*)medium_scatter_kernel<false, true, true, true>;
-        return lightPower ? (const void*)medium_scatter_kernel<true, false, true, true> : (const void*)medium_scatter_kernel<false, false, true, true>;
-    }
-    if (analytic) return lightPower ? (const void*)medium_scatter_kernel<true, true, true> : (const void*)medium_scatter_kernel<false, true, true>;
-    return lightPower ? (const void*)medium_scatter_kernel<true, false, true> : (const void*)medium_scatter_kernel<false, false, true>;
+    return MediumSets::find(set, [](auto f) { return (const void*)medium_scatter_kernel<GRID, decltype(f)::value>; });
 }
+const void* medium_scatter_kernel_of(bool grid, unsigned set) { return grid ? medium_scatter_instance<true>(set) : medium_scatter_instance<false>(set); }
 const void* medium_shadow_grid_kernel_ptr() { return (const void*)medium_shadow_grid_kernel; }
 const void* medium_brick_kernel_ptr() { return (const void*)medium_brick_kernel; }
 const void* medium_density_hook_kernel_ptr() { return (const void*)medium_density_hook_kernel; }
 const void* medium_track_hook_kernel_ptr() { return (const void*)medium_track_hook_kernel; }
 
-// (the light sample's mode and analytic lights: next_event_estimation's instances, chosen as the material launch's are — nxhip_render.hip)
-const void* medium_scatter_kernel_ptr(bool lightPower, bool analytic, bool metal)
-{
-    if (metal) {
-        if (analytic) return lightPower ? (const void*)medium_scatter_kernel<true, true, false, true> : (const void*)medium_scatter_kernel<false, true, false, true>;
-        return lightPower ? (const void*)medium_scatter_kernel<true, false, false, true> : (const void*)medium_scatter_kernel<false, false, false, true>;
-    }
-    if (analytic) return lightPower ? (const void*)medium_scatter_kernel<true, true, false> : (const void*)medium_scatter_kernel<false, true, false>;
-    return lightPower ? (const void*)medium_scatter_kernel<true, false, false> : (const void*)medium_scatter_kernel<false, false, false>;
-}
 const void* medium_shadow_kernel_ptr() { return (const void*)medium_shadow_kernel; }
 const void* medium_segment_hook_kernel_ptr() { return (const void*)medium_segment_hook_kernel; }
 const void* medium_phase_hook_kernel_ptr() { return (const void*)medium_phase_hook_kernel; }

@@ -32,6 +32,7 @@
 #include "nx_queue.h"
 #include "nx_traverse.h"
 #include "nx_texture.h"
+#include "nx_variants.h"
 
 namespace nxd {
 
@@ -418,7 +419,7 @@ NXD ThinResult thin_wave_search(const DeviceState* __restrict__ S, lds_u64* cons
 // same clamp, the same lookup at this test's own u, v) and, if s < cutoff, drops the triangle as if the ray had missed it — hitT stays
 // (closest hit), the ray is not occluded and its T not touched (any hit).  A surviving MASK crossing is solid: it ends an any-hit ray, with
 // or without TRANSMIT.  The general instances and their counting variants only; never hands over (the thin kernel's search knows no alpha).
-template <bool ANY_HIT, bool STATS, bool ENTRY = false, bool IDENTITY = false, bool TRANSMIT = false, bool ALPHA_TEST = false>
+template <unsigned F>  // (a set of kTf* bits: nx_variants.h)
 // 5 waves per SIMD for both variants (96 VGPRs, no spills in the loop).  Before an instance entry also carried its BLAS
 // root (17 more live registers in the fetch), 6 waves at 80 VGPRs was the best point (5: -3 %, 7: -0.3 %, 8: -1.5 %); with it,
 // 6 waves spill 23 VGPRs inside the loop (-10 %), 5 and 4 measure +4.5 % and +1 % over the old kernel at 6.
@@ -428,6 +429,8 @@ template <bool ANY_HIT, bool STATS, bool ENTRY = false, bool IDENTITY = false, b
 __attribute__((amdgpu_waves_per_eu(NX_WAVES_PER_EU, NX_WAVES_PER_EU)))
 __global__ void __launch_bounds__(kTraceBlock) trace_kernel(const DeviceState* __restrict__ S, const int bounceArg)
 {
+    constexpr bool ANY_HIT = (F & kTfAnyHit) != 0u, STATS = (F & kTfCounting) != 0u, ENTRY = (F & kTfEntry) != 0u, IDENTITY = (F & kTfIdentity) != 0u;
+    constexpr bool TRANSMIT = (F & kTfTransmit) != 0u, ALPHA_TEST = (F & kTfAlphaTest) != 0u;
     // bounce | kTraceScanFlag: a launch of the SCAN pipeline — its rays are the set of the bounce's parity, and the closest-hit
     // record says what the path does next (see the flush below); without the flag: rays[0] and plain hit records
     const int bounce = bounceArg & 0xff;
@@ -435,8 +438,9 @@ __global__ void __launch_bounds__(kTraceBlock) trace_kernel(const DeviceState* _
     // ... | kTraceEntryFlag: the rays name the entry state of their run (rayO.w): installed at refill instead of the root's
     const bool entryLaunch = !ANY_HIT && !ALPHA_TEST && (ENTRY || STATS) && (bounceArg & kTraceEntryFlag) != 0 && S->entry != nullptr;
     // ... | kTraceThinFlag: the last long rays of a dry wave may be handed to the thin kernel (below)
-    static_assert(!TRANSMIT || (ANY_HIT && !ENTRY && !IDENTITY), "TRANSMIT: the general any-hit instance and its counting variant only");
-    static_assert(!ALPHA_TEST || (!ENTRY && !IDENTITY), "ALPHA_TEST: the general instances and their counting variants only");
+    static_assert(trace_transmit_ok(F), "TRANSMIT: the general any-hit instance and its counting variant only");
+    static_assert(trace_alpha_test_ok(F), "ALPHA_TEST: the general instances and their counting variants only");
+    static_assert(trace_set_ok(F), "IDENTITY and ENTRY have no counting form, ENTRY is the closest-hit primary launch's");
     bool thinAllowed = !STATS && !TRANSMIT && !ALPHA_TEST && (bounceArg & kTraceThinFlag) != 0;
     const int thinLanes = (int)(S->thinLanes & 0xffu);
     // (test hook, nxhip_debug_set_thin inHooks bit 1: hand over after thinIters iterations of EVERY stretch between two refill points, dry
@@ -1007,22 +1011,13 @@ __global__ void __launch_bounds__(kTraceBlock) trace_kernel(const DeviceState* _
     }
 }
 
-template __global__ void trace_kernel<false, false>(const DeviceState*, int);
-template __global__ void trace_kernel<false, false, true>(const DeviceState*, int);
-template __global__ void trace_kernel<false, true>(const DeviceState*, int);
-template __global__ void trace_kernel<true, false>(const DeviceState*, int);
-template __global__ void trace_kernel<true, true>(const DeviceState*, int);
-template __global__ void trace_kernel<false, false, false, true>(const DeviceState*, int);
-template __global__ void trace_kernel<false, false, true, true>(const DeviceState*, int);
-template __global__ void trace_kernel<true, false, false, true>(const DeviceState*, int);
-template __global__ void trace_kernel<true, false, false, false, true>(const DeviceState*, int);
-template __global__ void trace_kernel<true, true, false, false, true>(const DeviceState*, int);
-template __global__ void trace_kernel<false, false, false, false, false, true>(const DeviceState*, int);
-template __global__ void trace_kernel<false, true, false, false, false, true>(const DeviceState*, int);
-template __global__ void trace_kernel<true, false, false, false, false, true>(const DeviceState*, int);
-template __global__ void trace_kernel<true, true, false, false, false, true>(const DeviceState*, int);
-template __global__ void trace_kernel<true, false, false, false, true, true>(const DeviceState*, int);
-template __global__ void trace_kernel<true, true, false, false, true, true>(const DeviceState*, int);
+// The instances, in the order they are instantiated: the general ones and their counting variants, the primary launch's with entry
+// points, the identity-only scene's, the TRANSMIT any-hit instance's, the ALPHA_TEST ones.
+using TraceInstances = Instances<0u, kTfEntry, kTfCounting, kTfAnyHit, kTfAnyHit | kTfCounting,
+                                 kTfIdentity, kTfEntry | kTfIdentity, kTfAnyHit | kTfIdentity,
+                                 kTfAnyHit | kTfTransmit, kTfAnyHit | kTfCounting | kTfTransmit,
+                                 kTfAlphaTest, kTfCounting | kTfAlphaTest, kTfAnyHit | kTfAlphaTest, kTfAnyHit | kTfCounting | kTfAlphaTest,
+                                 kTfAnyHit | kTfTransmit | kTfAlphaTest, kTfAnyHit | kTfCounting | kTfTransmit | kTfAlphaTest>;
 
 // The listed rays of one level (closest-hit first, then any-hit; kThinClosestOnly / kThinAnyOnly: one list), one wave per ray,
 // grid-stride.  `bounceArg` as the trace launches got it: the ray set and the meaning of the closest-hit record follow kTraceScanFlag.
@@ -1124,26 +1119,10 @@ __global__ void __launch_bounds__(kTraceBlock) thin_kernel(const DeviceState* __
 }
 
 const void* thin_kernel_ptr() { return (const void*)thin_kernel; }
-// the primary launch with entry points
-const void* trace_entry_kernel_ptr(bool identity) { return identity ? (const void*)trace_kernel<false, false, true, true> : (const void*)trace_kernel<false, false, true>; }
-
-// identity: the instances of an identity-only scene's pass graphs (the counting variants have none)
-const void* trace_kernel_ptr(bool anyHit, bool stats, bool identity)
+// the instance of a set of trace features (nullptr: not compiled — the host canonicalises first: nxhip_render.hip trace_features)
+const void* trace_kernel_of(unsigned set)
 {
-    if (identity && !stats) return anyHit ? (const void*)trace_kernel<true, false, false, true> : (const void*)trace_kernel<false, false, false, true>;
-    if (anyHit) return stats ? (const void*)trace_kernel<true, true> : (const void*)trace_kernel<true, false>;
-    return stats ? (const void*)trace_kernel<false, true> : (const void*)trace_kernel<false, false>;
-}
-
-// the any-hit TRANSMIT instance (reads sceneFlags: no IDENTITY form) and its counting variant
-const void* trace_transmit_kernel_ptr(bool stats) { return stats ? (const void*)trace_kernel<true, true, false, false, true> : (const void*)trace_kernel<true, false, false, false, true>; }
-
-// the ALPHA_TEST instances (nxhip_set_material_alpha with a MASK material): closest hit, any hit, any hit + TRANSMIT, and their counting variants
-const void* trace_alpha_kernel_ptr(bool anyHit, bool stats, bool transmit)
-{
-    if (!anyHit) return stats ? (const void*)trace_kernel<false, true, false, false, false, true> : (const void*)trace_kernel<false, false, false, false, false, true>;
-    if (transmit) return stats ? (const void*)trace_kernel<true, true, false, false, true, true> : (const void*)trace_kernel<true, false, false, false, true, true>;
-    return stats ? (const void*)trace_kernel<true, true, false, false, false, true> : (const void*)trace_kernel<true, false, false, false, false, true>;
+    return TraceInstances::find(set, [](auto f) { return (const void*)trace_kernel<decltype(f)::value>; });
 }
 
 // the device-side layouts this translation unit was compiled with (nx_device.h layout_stamp; compared by nxhip_create)

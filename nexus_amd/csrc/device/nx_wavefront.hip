@@ -28,6 +28,7 @@
 #include "nx_texture.h"
 #include "nx_tonemap.h"
 #include "nx_traverse.h"
+#include "nx_variants.h"
 
 namespace nxd {
 
@@ -541,9 +542,10 @@ NXD f3 env_sample(const DeviceState* S, float r1, float r2)
 
 // lights the NEE chooses among: the mesh lights, plus the environment when it is importance sampled
 // (ANALYTIC: ... and the analytic lights between the two — only the instances of contexts that have some read their count)
-template <bool ANALYTIC = false>
+template <unsigned F = 0u>  // (a set of kMf* bits: nx_variants.h)
 NXD uint32_t nee_light_count(const DeviceState* S)
 {
+    constexpr bool ANALYTIC = (F & kMfAnalytic) != 0u;
     if constexpr (ANALYTIC) return S->lightCount + S->alightCount + ((S->envSampling && S->hdrMap.texels) ? 1u : 0u);
     else return S->lightCount + ((S->envSampling && S->hdrMap.texels) ? 1u : 0u);
 }
@@ -555,10 +557,11 @@ NXD uint32_t nee_light_count(const DeviceState* S)
 // (MIS-weighted) environment `bg`; a hit survives Russian roulette with probability max(throughput) — `survived`, the
 // throughput divided by it in `throughputOut` — and is shaded as the returned material type, or ends (-1).
 // METAL: the instances of a context with an NX_MAT_METALROUGH material (kFlavorMetal) — the fifth type is one a path may be shaded as
-template <bool kEnvFloat = true, bool ANALYTIC = false, bool METAL = false, class HitInst>
+template <bool kEnvFloat = true, unsigned F = 0u, class HitInst>
 NXD int logic_path(const DeviceState* S, const int bounce, const uint32_t frame, const uint32_t seedSlot, const uint32_t pixelIdx, const float hitT, const f3 dir,
                    const float4 tp, HitInst hitInst, bool& miss, f3& bg, bool& survived, f3& throughputOut, uint32_t& inst, bool& needsPrevVertex)
 {
+    constexpr bool METAL = (F & kMfMetal) != 0u;  // (ANALYTIC: nee_light_count reads it)
     needsPrevVertex = false;
     const f3 throughput = mk3(tp.x, tp.y, tp.z);
     int type = -1;
@@ -575,7 +578,7 @@ NXD int logic_path(const DeviceState* S, const int bounce, const uint32_t frame,
         }
         if (S->envSampling && S->hdrMap.texels && bounce > 1 && S->settings.useMIS) {
             // the NEE samples the environment too: weight the BSDF-sampled miss against it (extension)
-            const float envPdf = env_pdf(S, dir, uv) / (float)nee_light_count<ANALYTIC>(S);
+            const float envPdf = env_pdf(S, dir, uv) / (float)nee_light_count<F>(S);
             if (pdf_valid(envPdf)) bg = bg * power_heuristic(tp.w, envPdf);
         }
     } else {
@@ -608,7 +611,7 @@ NXD void keep_previous_vertex(const DeviceState* S, const uint32_t pixelIdx, con
     if ((__float_as_uint(rayOrigin.w) & kRayPassThrough) == 0u) S->rayOrigin[pixelIdx] = make_float4(rayOrigin.x, rayOrigin.y, rayOrigin.z, 0.0f);
 }
 
-template <bool ORDERED, int U, bool ANALYTIC = false>  // (ANALYTIC: the weighted miss counts the analytic lights — nee_light_count)
+template <bool ORDERED, int U, unsigned F = 0u>  // (F: ANALYTIC alone — the weighted miss counts the analytic lights: nee_light_count)
 // 8 waves per SIMD (60 VGPRs, no spills): two of the 1024-thread workgroups fit a CU instead of one, so the barriers of the
 // slot allocation in one overlap with the streaming of the other (logic kernel -16 %, bench +1 %)
 #ifndef NX_LOGIC_WAVES
@@ -616,6 +619,7 @@ template <bool ORDERED, int U, bool ANALYTIC = false>  // (ANALYTIC: the weighte
 #endif
 __global__ void __launch_bounds__(kLogicBlock, NX_LOGIC_WAVES) logic_kernel(const DeviceState* __restrict__ S, const int bounce)
 {
+    static_assert((F & ~kMfLogicReads) == 0u, "logic_kernel reads ANALYTIC alone");
     // U items per thread: a tile is U * 1 024 items behind ONE round of slot allocation
     Counters* C = S->counters;
     const QueueView in = queue_view(&C->region[0].traceSize[bounce - 1], S->queueShardCap);
@@ -651,8 +655,8 @@ __global__ void __launch_bounds__(kLogicBlock, NX_LOGIC_WAVES) logic_kernel(cons
                 const uint32_t hitInstance = S->trace.hitInst[at];
                 bool miss, survived, needsPrevVertex;
                 f3 bg = mk3(0.0f), t = mk3(0.0f);
-                // (U > 1: the instance of scenes without an environment map — logic_kernel_ptr — whose misses never reach a map lookup)
-                type[u] = logic_path<U == 1, ANALYTIC>(S, bounce, frame, (uint32_t)index, pixelIdx[u], hit[u].x, mk3(dirPix[u].x, dirPix[u].y, dirPix[u].z), tp, [&]() { return hitInstance; }, miss, bg, survived, t,
+                // (U > 1: the instance of scenes without an environment map — wavefront::logic — whose misses never reach a map lookup)
+                type[u] = logic_path<U == 1, F>(S, bounce, frame, (uint32_t)index, pixelIdx[u], hit[u].x, mk3(dirPix[u].x, dirPix[u].y, dirPix[u].z), tp, [&]() { return hitInstance; }, miss, bg, survived, t,
                                      inst[u], needsPrevVertex);
                 if (needsPrevVertex) keep_previous_vertex(S, pixelIdx[u], S->trace.rays[0].rayO[at]);
                 if (miss) {
@@ -725,13 +729,14 @@ struct ShadowPayload {
 // environment; an analytic pick draws its direction from the cone the light subtends (nx_alights.h alight_sample) and carries no MIS
 // weight — no other ray can find such a light.  With useMIS off the sample is taken among the analytic lights alone.  The instances
 // with ANALYTIC = false are the code of a context without such lights.
-template <int TYPE, bool POWER, bool NO_MAPS = false, bool ANALYTIC = false>
+template <int TYPE, unsigned F>
 NXD bool next_event_estimation(const DeviceState* S, f3 wi, const MatParams& mp, f3 hitPoint, f3 normal, f3 hitGNormal, f3 throughput,
                                uint32_t& rng, ShadowPayload& out)
 {
+    constexpr bool POWER = (F & kMfPower) != 0u, NO_MAPS = (F & kMfNoMaps) != 0u, ANALYTIC = (F & kMfAnalytic) != 0u;
     // no lights: the reference indexes an empty array here (undefined); defined as "no light sample, no random numbers
     // drawn", identically in the CPU restatement used by the tests
-    uint32_t nLights = nee_light_count<ANALYTIC>(S);
+    uint32_t nLights = nee_light_count<F>(S);
     uint32_t firstPick = 0u;
     if constexpr (ANALYTIC) {
         if (S->settings.useMIS == 0) { nLights = S->alightCount; firstPick = S->lightCount; }  // (nothing else can find them)
@@ -858,11 +863,12 @@ NXD bool next_event_estimation(const DeviceState* S, f3 wi, const MatParams& mp,
 // SOLID (nxhip_set_material_alpha with a material that is NX_ALPHA_MASK or NX_ALPHA_OPAQUE): a hit on an instance whose alphaMode is not
 // NX_ALPHA_BLEND never passes through.  The random numbers of the pass-through test are drawn as ever, in the same order — only the outcome
 // is ignored — and the colour still comes from the map's rgb.  The one text of the rule: every SOLID instance (nx_wavefront_solid.hip) gets here.
-template <int TYPE, bool POWER, bool NO_MAPS = false, bool ANALYTIC = false, bool DETAIL = false, bool SOLID = false, class PrevOrigin, class Emit>
+template <int TYPE, unsigned F, class PrevOrigin, class Emit>
 NXD void shade_path(const DeviceState* S, const int bounce, const uint32_t frame, const uint32_t seedSlot, const uint32_t pixelIdx, const float hu, const float hv,
                     const uint32_t triIdx, const uint32_t instanceIdx, const f3 rayDirection, const float4 tpdf, PrevOrigin prevOrigin, Emit emit,
                     bool& wantShadow, ShadowPayload& sh, bool& wantTrace, bool& updatePath, f3& nextOrigin, f3& nextDir, f3& nextThroughput, float& nextPdf)
 {
+    constexpr bool POWER = (F & kMfPower) != 0u, NO_MAPS = (F & kMfNoMaps) != 0u, ANALYTIC = (F & kMfAnalytic) != 0u, DETAIL = (F & kMfDetail) != 0u, SOLID = (F & kMfSolid) != 0u;
     wantShadow = false; wantTrace = false; updatePath = false;
     nextOrigin = mk3(0.0f); nextDir = mk3(0.0f); nextThroughput = mk3(0.0f);
     nextPdf = 0.0f;
@@ -906,13 +912,13 @@ NXD void shade_path(const DeviceState* S, const int bounce, const uint32_t frame
                 const uint32_t l = S->instLight[instanceIdx];
                 if (l != kNotALight && S->lightHeader->valid != 0u) P = light_entry_prob(S->lightTable, S->lightBase[l] + triIdx);
                 if (P > 0.0f) {
-                    float lightPdf = (P * ((float)S->lightCount / (float)nee_light_count<ANALYTIC>(S))) / area;
+                    float lightPdf = (P * ((float)S->lightCount / (float)nee_light_count<F>(S))) / area;
                     lightPdf *= dSquared / cosThetaO;
                     if (!pdf_valid(lightPdf)) weight = 0.0f;
                     else weight = power_heuristic(lastPdf, lightPdf);
                 }
             } else {
-                float lightPdf = 1.0f / ((float)(nee_light_count<ANALYTIC>(S) * inst->triCount) * area);
+                float lightPdf = 1.0f / ((float)(nee_light_count<F>(S) * inst->triCount) * area);
                 lightPdf *= dSquared / cosThetaO;
                 if (!pdf_valid(lightPdf)) weight = 0.0f;
                 else weight = power_heuristic(lastPdf, lightPdf);
@@ -952,7 +958,7 @@ NXD void shade_path(const DeviceState* S, const int bounce, const uint32_t frame
             nextDir = wo;
             wantTrace = true;
         } else {
-            if (useMIS || ANALYTIC) wantShadow = next_event_estimation<TYPE, POWER, NO_MAPS, ANALYTIC>(S, wi, mp, p, normal, gNormal, throughput, rng, sh);
+            if (useMIS || ANALYTIC) wantShadow = next_event_estimation<TYPE, F>(S, wi, mp, p, normal, gNormal, throughput, rng, sh);
             float pdf;
             f3 sampleThroughput;
             if (Bsdf<TYPE>::sample(mp, wi, rng, wo, sampleThroughput, pdf)) {
@@ -973,7 +979,7 @@ NXD void shade_path(const DeviceState* S, const int bounce, const uint32_t frame
 // at 4 waves (126 VGPRs) for one large pass, +4.5 % for one-frame passes in flight, where a smaller register footprint lets
 // the material kernels of one slot share SIMDs with the trace waves of another.  6 and 8 waves per SIMD spill 30-87 VGPRs and
 // double the kernel's time: it is sensitive to memory traffic, not short of waves.
-template <int TYPE, bool ORDERED, bool POWER, bool ANALYTIC = false, bool DETAIL = false, bool SOLID = false>
+template <int TYPE, bool ORDERED, unsigned F>  // (F: POWER, ANALYTIC, DETAIL, SOLID — TYPE says what METAL would, and the pipeline has no NO_MAPS form)
 #ifndef NX_SHADE_WAVES
 #define NX_SHADE_WAVES 5
 #endif
@@ -983,6 +989,7 @@ template <int TYPE, bool ORDERED, bool POWER, bool ANALYTIC = false, bool DETAIL
 // (ordered: one 1 024-thread workgroup per CU is 4 waves per SIMD whatever the register budget says, so it may as well be 128)
 __global__ void __launch_bounds__(ORDERED ? kShadeBlockOrderedThreads : kShadeBlock, ORDERED ? NX_SHADE_WAVES_ORDERED : NX_SHADE_WAVES) shade_kernel(const DeviceState* __restrict__ S, const int bounce)
 {
+    static_assert(shade_set_ok(F, TYPE == NX_MAT_METALROUGH), "a set of material features shade_kernel has no instance for (nx_variants.h)");
     Counters* C = S->counters;
     // (NX_MAT_METALROUGH: the fifth queue, its size row and its ticket row are words of their own — nx_device.h)
     constexpr bool kMetal = TYPE == NX_MAT_METALROUGH;
@@ -1011,7 +1018,7 @@ __global__ void __launch_bounds__(ORDERED ? kShadeBlockOrderedThreads : kShadeBl
             pixelIdx = __float_as_uint(hit.x);
             const uint32_t instanceIdx = __float_as_uint(dirInst.w);
             tpdf = bounce == 1 ? make_float4(1.0f, 1.0f, 1.0f, 1.0e10f) : mq.tp[at];
-            shade_path<TYPE, POWER, false, ANALYTIC, DETAIL, SOLID>(S, bounce, frame, (uint32_t)requestIdx, pixelIdx, hit.y, hit.z, __float_as_uint(hit.w), instanceIdx, mk3(dirInst.x, dirInst.y, dirInst.z), tpdf,
+            shade_path<TYPE, F>(S, bounce, frame, (uint32_t)requestIdx, pixelIdx, hit.y, hit.z, __float_as_uint(hit.w), instanceIdx, mk3(dirInst.x, dirInst.y, dirInst.z), tpdf,
                              [&]() { return S->rayOrigin[pixelIdx]; },
                              [&](f3 emitted, uint32_t instIdx) {
                                  if (bounce == 1 && bounce != (int)S->settings.pathLength && pixelIdx < S->localCount && S->frame->pixelQueryPixel == (int)global_pixel(S, pixelIdx))
@@ -1073,10 +1080,11 @@ static_assert(kScanRing >= kShadeBlock + 4 * kShadeBlock && (kScanRing & (kScanR
 // from `staticTiles` on are handed out by ticket — one returning atomic per tile on the region's own word.  The share of a tile
 // that is this type's to shade varies from none to all with what the camera sees there, so a static split leaves most workgroups
 // waiting for the few whose tiles were full (measured: +40 % on the kernels).
-template <int TYPE, bool POWER, bool NO_MAPS = false, bool ANALYTIC = false, bool DETAIL = false, bool SOLID = false>
+template <int TYPE, unsigned F>
 NXD void shade_scan_type(const DeviceState* __restrict__ S, const int bounce, const bool dropEnded, const int region, const int inRegion, const int per, const int firstTile,
                          const int staticTiles, int* const sRing, int* const sHead, int* const sTicket)
 {
+    constexpr bool NO_MAPS = (F & kMfNoMaps) != 0u;  // (the rest: shade_path reads it)
     // TYPE == kScanMiss: the rays that missed (code kHitCodeMiss) — what is left of the logic step when a miss can contribute: the
     // environment (flat colour or map, MIS-weighted against the environment sampler) added to the path's radiance, PathTracer.cu:152-164
     constexpr bool kMiss = TYPE == kScanMiss;
@@ -1125,7 +1133,7 @@ NXD void shade_scan_type(const DeviceState* __restrict__ S, const int bounce, co
                 bool miss, survived, needsPrevVertex;
                 f3 bg = mk3(0.0f), t = mk3(0.0f);
                 uint32_t inst = 0;
-                logic_path<!NO_MAPS, ANALYTIC>(S, bounce, frame, (uint32_t)at, pixelIdx, 1e30f, mk3(dirPix.x, dirPix.y, dirPix.z), tp, [&]() { return 0u; }, miss, bg, survived, t, inst, needsPrevVertex);
+                logic_path<!NO_MAPS, F & kMfAnalytic>(S, bounce, frame, (uint32_t)at, pixelIdx, 1e30f, mk3(dirPix.x, dirPix.y, dirPix.z), tp, [&]() { return 0u; }, miss, bg, survived, t, inst, needsPrevVertex);
                 if ((__float_as_uint(bg.x) | __float_as_uint(bg.y) | __float_as_uint(bg.z)) != 0u) {  // (as the logic kernel: +0 changes nothing)
                     float4 r = bounce == 1 ? make_float4(0, 0, 0, 0) : S->radiance[pixelIdx];
                     r.x += bg.x; r.y += bg.y; r.z += bg.z;
@@ -1158,7 +1166,7 @@ NXD void shade_scan_type(const DeviceState* __restrict__ S, const int bounce, co
             // ... and the path's previous vertex, for hits that can need it (keep_previous_vertex)
             const uint32_t typeAndFlag = *(const NX_G uint32_t*)((const NX_G char*)&S->shadeInst[instanceIdx].material + kMaterialTypeOffset);
             if ((typeAndFlag >> 8) & 1u) keep_previous_vertex(S, pixelIdx, in.rayO[at]);
-            shade_path<kMat, POWER, NO_MAPS, ANALYTIC, DETAIL, SOLID>(S, bounce, frame, (uint32_t)at, pixelIdx, hit.y, hit.z, __float_as_uint(hit.w), instanceIdx, mk3(dirPix.x, dirPix.y, dirPix.z), tpdf,
+            shade_path<kMat, F>(S, bounce, frame, (uint32_t)at, pixelIdx, hit.y, hit.z, __float_as_uint(hit.w), instanceIdx, mk3(dirPix.x, dirPix.y, dirPix.z), tpdf,
                              [&]() { return S->rayOrigin[pixelIdx]; },
                              [&](f3 emitted, uint32_t instIdx) {
                                  if (bounce == 1 && bounce != (int)S->settings.pathLength && pixelIdx < S->localCount && S->frame->pixelQueryPixel == (int)global_pixel(S, pixelIdx))
@@ -1274,9 +1282,11 @@ NXD void shade_scan_type(const DeviceState* __restrict__ S, const int bounce, co
 // launch instead of one per type (the reference: four, PathTracer.cpp:116-120).  A single-bit mask is a per-type launch.
 // METAL (a context with an NX_MAT_METALROUGH material: kFlavorMetal): the fifth material type as a sixth case, typeMask bit kScanMetalBit.  The
 // kernel's register count is the maximum over its cases, so the case is compiled into these instances alone (nx_wavefront_metal.hip).
-template <bool POWER, bool NO_MAPS = false, bool ANALYTIC = false, bool DETAIL = false, bool METAL = false, bool SOLID = false>  // (the light sample's mode, a map-free context, analytic lights: next_event_estimation; detail maps: shade_path)
+template <unsigned F>  // (POWER, NO_MAPS, ANALYTIC: next_event_estimation; DETAIL, SOLID: shade_path; METAL: here)
 __global__ void __launch_bounds__(kShadeBlock, NX_SHADE_WAVES) shade_scan_kernel(const DeviceState* __restrict__ S, const int bounceArg, const int typeMask)
 {
+    constexpr bool METAL = (F & kMfMetal) != 0u;
+    static_assert(material_set_ok(F), "SOLID => METAL => DETAIL => not NO_MAPS (nx_variants.h)");
     const int bounce = bounceArg & 0xff;
     const bool dropEnded = (bounceArg & kShadeDropEnded) != 0;  // (a property of the pass's shape: nxhip_api.hip pass_flavor)
     __shared__ int sRing[kScanRing];
@@ -1310,13 +1320,13 @@ __global__ void __launch_bounds__(kShadeBlock, NX_SHADE_WAVES) shade_scan_kernel
         const int starters = (ranks - want + nTypes - 1) / nTypes;  // workgroups whose first type this is: each takes the tile of its index
         const int first = step == 0 ? myIndex : -1;
         switch (type) {
-        case NX_MAT_DIFFUSE: shade_scan_type<NX_MAT_DIFFUSE, POWER, NO_MAPS, ANALYTIC, DETAIL, SOLID>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket); break;
-        case NX_MAT_PLASTIC: shade_scan_type<NX_MAT_PLASTIC, POWER, NO_MAPS, ANALYTIC, DETAIL, SOLID>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket); break;
-        case NX_MAT_DIELECTRIC: shade_scan_type<NX_MAT_DIELECTRIC, POWER, NO_MAPS, ANALYTIC, DETAIL, SOLID>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket); break;
-        case NX_MAT_CONDUCTOR: shade_scan_type<NX_MAT_CONDUCTOR, POWER, NO_MAPS, ANALYTIC, DETAIL, SOLID>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket); break;
-        case kScanMiss: shade_scan_type<kScanMiss, POWER, NO_MAPS, ANALYTIC, DETAIL, SOLID>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket); break;
+        case NX_MAT_DIFFUSE: shade_scan_type<NX_MAT_DIFFUSE, F>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket); break;
+        case NX_MAT_PLASTIC: shade_scan_type<NX_MAT_PLASTIC, F>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket); break;
+        case NX_MAT_DIELECTRIC: shade_scan_type<NX_MAT_DIELECTRIC, F>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket); break;
+        case NX_MAT_CONDUCTOR: shade_scan_type<NX_MAT_CONDUCTOR, F>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket); break;
+        case kScanMiss: shade_scan_type<kScanMiss, F>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket); break;
         case kScanMetalBit:
-            if constexpr (METAL) shade_scan_type<kScanMetalBit, POWER, NO_MAPS, ANALYTIC, DETAIL, SOLID>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket);
+            if constexpr (METAL) shade_scan_type<kScanMetalBit, F>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket);
             break;
         default: break;
         }
@@ -1351,9 +1361,11 @@ __global__ void __launch_bounds__(kWideBlock) count_scan_kernel(const DeviceStat
 #ifndef NX_TAIL_REFILL_BELOW
 #define NX_TAIL_REFILL_BELOW 40
 #endif
-template <bool POWER, bool ANALYTIC = false, bool DETAIL = false, bool METAL = false>  // (the light sample's mode, analytic lights: next_event_estimation; detail maps: shade_path; METAL: the fifth material type)
+template <unsigned F>  // (POWER, ANALYTIC: next_event_estimation; DETAIL: shade_path; METAL, the fifth material type: here and logic_path)
 __global__ void __launch_bounds__(kTraceBlock) tail_kernel(const DeviceState* __restrict__ S, const int firstBounceArg)
 {
+    constexpr bool METAL = (F & kMfMetal) != 0u;
+    static_assert(tail_set_ok(F), "a set of material features tail_kernel has no instance for (nx_variants.h)");
     // firstBounce | kTraceScanFlag: the pass ran the SCAN pipeline so far — the rays of trace(firstBounce - 1) are in the set of
     // that bounce's parity and the hit records carry codes (which this kernel does not need: it makes the logic step's decisions
     // itself, with the same random numbers)
@@ -1417,7 +1429,7 @@ __global__ void __launch_bounds__(kTraceBlock) tail_kernel(const DeviceState* __
         if (alive) {
             bool miss, survived, needsPrevVertex;
             f3 bg = mk3(0.0f), t = mk3(0.0f);
-            type = logic_path<true, ANALYTIC, METAL>(S, bounce, frame, (uint32_t)index, pixelIdx, hitT, dir, tp, [&]() { return inst; }, miss, bg, survived, t, inst, needsPrevVertex);
+            type = logic_path<true, F>(S, bounce, frame, (uint32_t)index, pixelIdx, hitT, dir, tp, [&]() { return inst; }, miss, bg, survived, t, inst, needsPrevVertex);
             if (miss) { rad.x += bg.x; rad.y += bg.y; rad.z += bg.z; dirty = true; }
             if (survived) { tp.x = t.x; tp.y = t.y; tp.z = t.z; }
             if (type < 0) alive = false;
@@ -1436,27 +1448,27 @@ __global__ void __launch_bounds__(kTraceBlock) tail_kernel(const DeviceState* __
         };
         if (__ballot(alive && type == NX_MAT_DIFFUSE) != 0ull) {
             if (alive && type == NX_MAT_DIFFUSE)
-                shade_path<NX_MAT_DIFFUSE, POWER, false, ANALYTIC, DETAIL>(S, bounce, frame, (uint32_t)index, pixelIdx, hu, hv, tri, inst, dir, tp, prevOrigin, emit, wantShadowRay, sh, wantTrace, updatePath, nextOrigin, nextDir, nextThroughput, nextPdf);
+                shade_path<NX_MAT_DIFFUSE, F>(S, bounce, frame, (uint32_t)index, pixelIdx, hu, hv, tri, inst, dir, tp, prevOrigin, emit, wantShadowRay, sh, wantTrace, updatePath, nextOrigin, nextDir, nextThroughput, nextPdf);
         }
         if (__ballot(alive && type == NX_MAT_PLASTIC) != 0ull) {
             if (alive && type == NX_MAT_PLASTIC)
-                shade_path<NX_MAT_PLASTIC, POWER, false, ANALYTIC, DETAIL>(S, bounce, frame, (uint32_t)index, pixelIdx, hu, hv, tri, inst, dir, tp, prevOrigin, emit, wantShadowRay, sh, wantTrace, updatePath, nextOrigin, nextDir, nextThroughput, nextPdf);
+                shade_path<NX_MAT_PLASTIC, F>(S, bounce, frame, (uint32_t)index, pixelIdx, hu, hv, tri, inst, dir, tp, prevOrigin, emit, wantShadowRay, sh, wantTrace, updatePath, nextOrigin, nextDir, nextThroughput, nextPdf);
         }
         if (__ballot(alive && type == NX_MAT_DIELECTRIC) != 0ull) {
             if (alive && type == NX_MAT_DIELECTRIC)
-                shade_path<NX_MAT_DIELECTRIC, POWER, false, ANALYTIC, DETAIL>(S, bounce, frame, (uint32_t)index, pixelIdx, hu, hv, tri, inst, dir, tp, prevOrigin, emit, wantShadowRay, sh, wantTrace, updatePath, nextOrigin, nextDir, nextThroughput, nextPdf);
+                shade_path<NX_MAT_DIELECTRIC, F>(S, bounce, frame, (uint32_t)index, pixelIdx, hu, hv, tri, inst, dir, tp, prevOrigin, emit, wantShadowRay, sh, wantTrace, updatePath, nextOrigin, nextDir, nextThroughput, nextPdf);
         }
         if (__ballot(alive && type == NX_MAT_CONDUCTOR) != 0ull) {
             if (alive && type == NX_MAT_CONDUCTOR) {
                 if (S->conductorMode == NX_CONDUCTOR_EXTENDED)
-                    shade_path<NX_MAT_CONDUCTOR, POWER, false, ANALYTIC, DETAIL>(S, bounce, frame, (uint32_t)index, pixelIdx, hu, hv, tri, inst, dir, tp, prevOrigin, emit, wantShadowRay, sh, wantTrace, updatePath, nextOrigin, nextDir, nextThroughput, nextPdf);
+                    shade_path<NX_MAT_CONDUCTOR, F>(S, bounce, frame, (uint32_t)index, pixelIdx, hu, hv, tri, inst, dir, tp, prevOrigin, emit, wantShadowRay, sh, wantTrace, updatePath, nextOrigin, nextDir, nextThroughput, nextPdf);
                 else alive = false;  // (the reference's graph has no conductor kernel: such a path ends unshaded)
             }
         }
         if constexpr (METAL) {
             if (__ballot(alive && type == NX_MAT_METALROUGH) != 0ull) {
                 if (alive && type == NX_MAT_METALROUGH)
-                    shade_path<NX_MAT_METALROUGH, POWER, false, ANALYTIC, DETAIL>(S, bounce, frame, (uint32_t)index, pixelIdx, hu, hv, tri, inst, dir, tp, prevOrigin, emit, wantShadowRay, sh, wantTrace, updatePath, nextOrigin, nextDir, nextThroughput, nextPdf);
+                    shade_path<NX_MAT_METALROUGH, F>(S, bounce, frame, (uint32_t)index, pixelIdx, hu, hv, tri, inst, dir, tp, prevOrigin, emit, wantShadowRay, sh, wantTrace, updatePath, nextOrigin, nextDir, nextThroughput, nextPdf);
             }
         }
         // ---- the light sample's shadow ray: traced now, added when unoccluded (the shadow launch of this bounce, BVH8Traversal.cuh:515)
@@ -1485,6 +1497,27 @@ __global__ void __launch_bounds__(kTraceBlock) tail_kernel(const DeviceState* __
         }
     }
     if (dirty) S->radiance[pixelIdx] = rad;
+}
+
+// ------------------------------------------------------------------------------------------------------
+// The instances of the three families above are compiled in four units (this one and nx_wavefront_detail / _metal / _solid.hip, which
+// say why).  Each unit lists the sets it holds (Instances: nx_variants.h) and answers for them through these lookups: naming a set in a
+// list is what compiles its instance, and a set no list names yields nullptr.  (TYPES: the material types the unit's shade_kernel
+// instances exist for, in the order they are instantiated.)
+constexpr bool kOrdered = true;  // (the classic pipeline's kernels are instantiated for the ordered compaction alone: frame_levels)
+template <class Sets> const void* shade_scan_instance(unsigned set)
+{
+    return Sets::find(set, [](auto f) { return (const void*)shade_scan_kernel<decltype(f)::value>; });
+}
+template <class Sets> const void* tail_instance(unsigned set)
+{
+    return Sets::find(set, [](auto f) { return (const void*)tail_kernel<decltype(f)::value>; });
+}
+template <class Sets, int... TYPES> const void* shade_instance(int type, unsigned set)
+{
+    const void* fn = nullptr;
+    ((TYPES == type ? (void)(fn = Sets::find(set, [](auto f) { return (const void*)shade_kernel<TYPES, kOrdered, decltype(f)::value>; })) : (void)0), ...);
+    return fn;
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -1640,51 +1673,27 @@ __global__ void __launch_bounds__(kWideBlock) alight_hook_kernel(const DeviceSta
 
 // ------------------------------------------------------------------------------------------------------
 
+// This unit's instances: the contexts without detail maps, a fifth material type or alpha modes.
+// (the classic pipeline — logic kernel and per-type material kernels — runs under the ordered compaction only: see frame_levels)
+using ShadeSets = Instances<kMfPower | kMfAnalytic, kMfAnalytic, kMfPower, 0u>;
+using ShadeScanSets = Instances<kMfPower | kMfNoMaps | kMfAnalytic, kMfNoMaps | kMfAnalytic, kMfPower | kMfAnalytic, kMfAnalytic,
+                                kMfPower | kMfNoMaps, kMfNoMaps, kMfPower, 0u>;
+using TailSets = Instances<kMfPower | kMfAnalytic, kMfAnalytic, kMfPower, 0u>;
+namespace wavefront {
 // `items` per thread: kLogicItems (2) unless the caller asks for 1 — what a scene with an environment map gets, whose misses run the
 // map lookups (binary64 arc functions) in this kernel: with a second item's state live beside them the 64-register budget spills
 // into that path (configs[3]: logic kernel +8 % with two items, -6 % on configs[1])
-const void* logic_kernel_ptr(int items, bool analytic)
+// (ANALYTIC: only the one-item instance has the form — the count enters the weighted miss, which needs an environment map)
+const void* logic(int items, unsigned set)
 {
-    // (analytic: only the one-item instance differs — the count enters the weighted miss, which needs an environment map)
-    if (analytic && (items == 1 || kLogicItems == 1)) return (const void*)logic_kernel<true, 1, true>;
-    if (items == 1 || kLogicItems == 1) return (const void*)logic_kernel<true, 1>;
-    return (const void*)logic_kernel<true, kLogicItems>;
+    if (items == 1 || kLogicItems == 1) return Instances<kMfAnalytic, 0u>::find(set, [](auto f) { return (const void*)logic_kernel<kOrdered, 1, decltype(f)::value>; });
+    return set == 0u ? (const void*)logic_kernel<kOrdered, kLogicItems> : nullptr;
 }
-
-// (the classic pipeline — logic kernel and per-type material kernels — runs under the ordered compaction only: see frame_levels)
-// (lightPower: the variants only the pass graphs of NXHIP_LIGHTS_POWER launch — nxhip_api.hip pass_flavor)
-const void* shade_kernel_ptr(int type, bool lightPower, bool analytic)
-{
-    if (analytic) {  // (the variants only the pass graphs of a context with analytic lights launch)
-        switch (type) {
-        case NX_MAT_DIFFUSE: return lightPower ? (const void*)shade_kernel<NX_MAT_DIFFUSE, true, true, true> : (const void*)shade_kernel<NX_MAT_DIFFUSE, true, false, true>;
-        case NX_MAT_DIELECTRIC: return lightPower ? (const void*)shade_kernel<NX_MAT_DIELECTRIC, true, true, true> : (const void*)shade_kernel<NX_MAT_DIELECTRIC, true, false, true>;
-        case NX_MAT_PLASTIC: return lightPower ? (const void*)shade_kernel<NX_MAT_PLASTIC, true, true, true> : (const void*)shade_kernel<NX_MAT_PLASTIC, true, false, true>;
-        default: return lightPower ? (const void*)shade_kernel<NX_MAT_CONDUCTOR, true, true, true> : (const void*)shade_kernel<NX_MAT_CONDUCTOR, true, false, true>;
-        }
-    }
-    switch (type) {
-    case NX_MAT_DIFFUSE: return lightPower ? (const void*)shade_kernel<NX_MAT_DIFFUSE, true, true> : (const void*)shade_kernel<NX_MAT_DIFFUSE, true, false>;
-    case NX_MAT_DIELECTRIC: return lightPower ? (const void*)shade_kernel<NX_MAT_DIELECTRIC, true, true> : (const void*)shade_kernel<NX_MAT_DIELECTRIC, true, false>;
-    case NX_MAT_PLASTIC: return lightPower ? (const void*)shade_kernel<NX_MAT_PLASTIC, true, true> : (const void*)shade_kernel<NX_MAT_PLASTIC, true, false>;
-    default: return lightPower ? (const void*)shade_kernel<NX_MAT_CONDUCTOR, true, true> : (const void*)shade_kernel<NX_MAT_CONDUCTOR, true, false>;
-    }
-}
-const void* shade_scan_kernel_ptr(bool lightPower, bool noMaps, bool analytic)
-{
-    if (analytic) {
-        if (noMaps) return lightPower ? (const void*)shade_scan_kernel<true, true, true> : (const void*)shade_scan_kernel<false, true, true>;
-        return lightPower ? (const void*)shade_scan_kernel<true, false, true> : (const void*)shade_scan_kernel<false, false, true>;
-    }
-    if (noMaps) return lightPower ? (const void*)shade_scan_kernel<true, true> : (const void*)shade_scan_kernel<false, true>;
-    return lightPower ? (const void*)shade_scan_kernel<true> : (const void*)shade_scan_kernel<false>;
-}
+const void* shade(int type, unsigned set) { return shade_instance<ShadeSets, NX_MAT_DIFFUSE, NX_MAT_DIELECTRIC, NX_MAT_PLASTIC, NX_MAT_CONDUCTOR>(type, set); }
+const void* shade_scan(unsigned set) { return shade_scan_instance<ShadeScanSets>(set); }
+const void* tail(unsigned set) { return tail_instance<TailSets>(set); }
+}  // namespace wavefront
 const void* count_scan_kernel_ptr() { return (const void*)count_scan_kernel; }
-const void* tail_kernel_ptr(bool lightPower, bool analytic)
-{
-    if (analytic) return lightPower ? (const void*)tail_kernel<true, true> : (const void*)tail_kernel<false, true>;
-    return lightPower ? (const void*)tail_kernel<true> : (const void*)tail_kernel<false>;
-}
 const void* begin_frame_kernel_ptr() { return (const void*)begin_frame_kernel; }
 const void* hook_sizes_kernel_ptr() { return (const void*)hook_sizes_kernel; }
 const void* generate_kernel_ptr() { return (const void*)generate_kernel; }

@@ -63,34 +63,13 @@ __global__ void __launch_bounds__(kWideBlock) tex2d_linear_hook_kernel(const Tex
     for (uint32_t k = blockIdx.x * blockDim.x + threadIdx.x; k < count; k += gridDim.x * blockDim.x) out[k] = tex2d_linear(t, uv[2 * k], uv[2 * k + 1]);
 }
 
-// (the variants only the pass graphs of a context with detail maps launch — nxhip_render.hip pass_flavor, kFlavorDetail)
-const void* shade_detail_kernel_ptr(int type, bool lightPower, bool analytic)
-{
-    if (analytic) {
-        switch (type) {
-        case NX_MAT_DIFFUSE: return lightPower ? (const void*)shade_kernel<NX_MAT_DIFFUSE, true, true, true, true> : (const void*)shade_kernel<NX_MAT_DIFFUSE, true, false, true, true>;
-        case NX_MAT_DIELECTRIC: return lightPower ? (const void*)shade_kernel<NX_MAT_DIELECTRIC, true, true, true, true> : (const void*)shade_kernel<NX_MAT_DIELECTRIC, true, false, true, true>;
-        case NX_MAT_PLASTIC: return lightPower ? (const void*)shade_kernel<NX_MAT_PLASTIC, true, true, true, true> : (const void*)shade_kernel<NX_MAT_PLASTIC, true, false, true, true>;
-        default: return lightPower ? (const void*)shade_kernel<NX_MAT_CONDUCTOR, true, true, true, true> : (const void*)shade_kernel<NX_MAT_CONDUCTOR, true, false, true, true>;
-        }
-    }
-    switch (type) {
-    case NX_MAT_DIFFUSE: return lightPower ? (const void*)shade_kernel<NX_MAT_DIFFUSE, true, true, false, true> : (const void*)shade_kernel<NX_MAT_DIFFUSE, true, false, false, true>;
-    case NX_MAT_DIELECTRIC: return lightPower ? (const void*)shade_kernel<NX_MAT_DIELECTRIC, true, true, false, true> : (const void*)shade_kernel<NX_MAT_DIELECTRIC, true, false, false, true>;
-    case NX_MAT_PLASTIC: return lightPower ? (const void*)shade_kernel<NX_MAT_PLASTIC, true, true, false, true> : (const void*)shade_kernel<NX_MAT_PLASTIC, true, false, false, true>;
-    default: return lightPower ? (const void*)shade_kernel<NX_MAT_CONDUCTOR, true, true, false, true> : (const void*)shade_kernel<NX_MAT_CONDUCTOR, true, false, false, true>;
-    }
-}
-const void* shade_scan_detail_kernel_ptr(bool lightPower, bool analytic)
-{
-    if (analytic) return lightPower ? (const void*)shade_scan_kernel<true, false, true, true> : (const void*)shade_scan_kernel<false, false, true, true>;
-    return lightPower ? (const void*)shade_scan_kernel<true, false, false, true> : (const void*)shade_scan_kernel<false, false, false, true>;
-}
-const void* tail_detail_kernel_ptr(bool lightPower, bool analytic)
-{
-    if (analytic) return lightPower ? (const void*)tail_kernel<true, true, true> : (const void*)tail_kernel<false, true, true>;
-    return lightPower ? (const void*)tail_kernel<true, false, true> : (const void*)tail_kernel<false, false, true>;
-}
+// (the instances only the pass graphs of a context with detail maps launch — nxhip_render.hip pass_flavor, kFlavorDetail)
+using DetailSets = Instances<kMfPower | kMfAnalytic | kMfDetail, kMfAnalytic | kMfDetail, kMfPower | kMfDetail, kMfDetail>;
+namespace wavefront_detail {
+const void* shade(int type, unsigned set) { return shade_instance<DetailSets, NX_MAT_DIFFUSE, NX_MAT_DIELECTRIC, NX_MAT_PLASTIC, NX_MAT_CONDUCTOR>(type, set); }
+const void* shade_scan(unsigned set) { return shade_scan_instance<DetailSets>(set); }
+const void* tail(unsigned set) { return tail_instance<DetailSets>(set); }
+}  // namespace wavefront_detail
 const void* shading_frame_hook_kernel_ptr() { return (const void*)shading_frame_hook_kernel; }
 const void* tex2d_linear_hook_kernel_ptr() { return (const void*)tex2d_linear_hook_kernel; }
 

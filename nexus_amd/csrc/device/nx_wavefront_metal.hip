@@ -97,7 +97,7 @@ __global__ void __launch_bounds__(kLogicBlock, NX_LOGIC_WAVES) logic_metal_kerne
                 const uint32_t hitInstance = S->trace.hitInst[at];
                 bool miss, survived, needsPrevVertex;
                 f3 bg = mk3(0.0f), t = mk3(0.0f);
-                const int type = logic_path<false, false, true>(S, bounce, frame, (uint32_t)index, pixelIdx, hit.x, mk3(dirPix.x, dirPix.y, dirPix.z), tp, [&]() { return hitInstance; }, miss, bg,
+                const int type = logic_path<false, kMfMetal>(S, bounce, frame, (uint32_t)index, pixelIdx, hit.x, mk3(dirPix.x, dirPix.y, dirPix.z), tp, [&]() { return hitInstance; }, miss, bg,
                                                                 survived, t, inst, needsPrevVertex);
                 want[0][0] = type == NX_MAT_METALROUGH;
                 tpOut = make_float4(t.x, t.y, t.z, tp.w);
@@ -114,23 +114,16 @@ __global__ void __launch_bounds__(kLogicBlock, NX_LOGIC_WAVES) logic_metal_kerne
     }
 }
 
-// (the variants only the pass graphs of a context with an NX_MAT_METALROUGH material launch — nxhip_render.hip pass_flavor, kFlavorMetal)
-const void* shade_scan_metal_kernel_ptr(bool lightPower, bool analytic)
-{
-    if (analytic) return lightPower ? (const void*)shade_scan_kernel<true, false, true, true, true> : (const void*)shade_scan_kernel<false, false, true, true, true>;
-    return lightPower ? (const void*)shade_scan_kernel<true, false, false, true, true> : (const void*)shade_scan_kernel<false, false, false, true, true>;
-}
-const void* tail_metal_kernel_ptr(bool lightPower, bool analytic)
-{
-    if (analytic) return lightPower ? (const void*)tail_kernel<true, true, true, true> : (const void*)tail_kernel<false, true, true, true>;
-    return lightPower ? (const void*)tail_kernel<true, false, true, true> : (const void*)tail_kernel<false, false, true, true>;
-}
+// (the instances only the pass graphs of a context with an NX_MAT_METALROUGH material launch — nxhip_render.hip pass_flavor, kFlavorMetal)
+using MetalSets = Instances<kMfPower | kMfAnalytic | kMfDetail | kMfMetal, kMfAnalytic | kMfDetail | kMfMetal, kMfPower | kMfDetail | kMfMetal, kMfDetail | kMfMetal>;
+// (the classic pipeline's material kernel of the fifth type: TYPE says METAL, the set does not — shade_kernel, nx_variants.h)
+using MetalShadeSets = Instances<kMfPower | kMfAnalytic | kMfDetail, kMfAnalytic | kMfDetail, kMfPower | kMfDetail, kMfDetail>;
+namespace wavefront_metal {
+const void* shade_scan(unsigned set) { return shade_scan_instance<MetalSets>(set); }
+const void* tail(unsigned set) { return tail_instance<MetalSets>(set); }
+const void* shade(int type, unsigned set) { return shade_instance<MetalShadeSets, NX_MAT_METALROUGH>(type, set); }
+}  // namespace wavefront_metal
 const void* logic_metal_kernel_ptr() { return (const void*)logic_metal_kernel; }
-const void* shade_metal_kernel_ptr(bool lightPower, bool analytic)
-{
-    if (analytic) return lightPower ? (const void*)shade_kernel<NX_MAT_METALROUGH, true, true, true, true> : (const void*)shade_kernel<NX_MAT_METALROUGH, true, false, true, true>;
-    return lightPower ? (const void*)shade_kernel<NX_MAT_METALROUGH, true, true, false, true> : (const void*)shade_kernel<NX_MAT_METALROUGH, true, false, false, true>;
-}
 const void* bsdf_hook_metal_kernel_ptr() { return (const void*)bsdf_hook_metal_kernel; }
 const void* material_inputs_hook_kernel_ptr() { return (const void*)material_inputs_hook_kernel; }
 

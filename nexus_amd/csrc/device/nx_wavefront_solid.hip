@@ -11,29 +11,18 @@
 
 namespace nxd {
 
-// (the variants only the pass graphs of a context with a MASK or an OPAQUE material launch — nxhip_render.hip frame_levels, materials_solid)
-const void* shade_scan_solid_kernel_ptr(bool lightPower, bool analytic)
+// (the instances only the pass graphs of a context with a MASK or an OPAQUE material launch — nxhip_render.hip pass_flavor, kFlavorSolid)
+using SolidSets = Instances<kMfPower | kMfAnalytic | kMfDetail | kMfMetal | kMfSolid, kMfAnalytic | kMfDetail | kMfMetal | kMfSolid, kMfPower | kMfDetail | kMfMetal | kMfSolid,
+                            kMfDetail | kMfMetal | kMfSolid>;
+// (the classic pipeline's material kernels, all five types: TYPE says METAL, the set does not — shade_kernel, nx_variants.h)
+using SolidShadeSets = Instances<kMfPower | kMfAnalytic | kMfDetail | kMfSolid, kMfAnalytic | kMfDetail | kMfSolid, kMfPower | kMfDetail | kMfSolid, kMfDetail | kMfSolid>;
+namespace wavefront_solid {
+const void* shade_scan(unsigned set) { return shade_scan_instance<SolidSets>(set); }
+const void* shade(int type, unsigned set)
 {
-    if (analytic) return lightPower ? (const void*)shade_scan_kernel<true, false, true, true, true, true> : (const void*)shade_scan_kernel<false, false, true, true, true, true>;
-    return lightPower ? (const void*)shade_scan_kernel<true, false, false, true, true, true> : (const void*)shade_scan_kernel<false, false, false, true, true, true>;
+    return shade_instance<SolidShadeSets, NX_MAT_DIFFUSE, NX_MAT_DIELECTRIC, NX_MAT_PLASTIC, NX_MAT_METALROUGH, NX_MAT_CONDUCTOR>(type, set);
 }
-
-template <int TYPE>
-static const void* shade_solid_of(bool lightPower, bool analytic)
-{
-    if (analytic) return lightPower ? (const void*)shade_kernel<TYPE, true, true, true, true, true> : (const void*)shade_kernel<TYPE, true, false, true, true, true>;
-    return lightPower ? (const void*)shade_kernel<TYPE, true, true, false, true, true> : (const void*)shade_kernel<TYPE, true, false, false, true, true>;
-}
-const void* shade_solid_kernel_ptr(int type, bool lightPower, bool analytic)
-{
-    switch (type) {
-    case NX_MAT_DIFFUSE: return shade_solid_of<NX_MAT_DIFFUSE>(lightPower, analytic);
-    case NX_MAT_DIELECTRIC: return shade_solid_of<NX_MAT_DIELECTRIC>(lightPower, analytic);
-    case NX_MAT_PLASTIC: return shade_solid_of<NX_MAT_PLASTIC>(lightPower, analytic);
-    case NX_MAT_METALROUGH: return shade_solid_of<NX_MAT_METALROUGH>(lightPower, analytic);
-    default: return shade_solid_of<NX_MAT_CONDUCTOR>(lightPower, analytic);
-    }
-}
+}  // namespace wavefront_solid
 
 // the device-side layouts this translation unit was compiled with (nx_device.h layout_stamp; compared by nxhip_create)
 uint64_t layout_stamp_wavefront_solid() { return layout_stamp(); }

@@ -494,30 +494,20 @@ int nxhip_create(int device, uint32_t width, uint32_t height, void* stream, nxhi
 
         // persistent launch geometry from the occupancy the kernels actually get
         int perCU = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, trace_kernel_ptr(false, false), kTraceBlockThreads, 0) != hipSuccess || perCU < 1) perCU = 4;
+        const void* const closest = kernels::trace(0u).fn, * const anyHit = kernels::trace(kTfAnyHit).fn;
+        if (!closest || !anyHit) { rc = fail_invalid("nxhip_create: no trace_kernel instance of set 0 or of set kTfAnyHit is compiled"); break; }
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, closest, kTraceBlockThreads, 0) != hipSuccess || perCU < 1) perCU = 4;
         c->traceBlocks = std::max(1, perCU) * c->numCUs;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, trace_kernel_ptr(true, false), kTraceBlockThreads, 0) != hipSuccess || perCU < 1) perCU = 4;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, anyHit, kTraceBlockThreads, 0) != hipSuccess || perCU < 1) perCU = 4;
         c->shadowBlocks = std::max(1, perCU) * c->numCUs;
         c->wideBlocks = 8 * c->numCUs;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, tail_kernel_ptr(false), kTraceBlockThreads, 0) != hipSuccess || perCU < 1) perCU = 2;
-        c->tailBlocks = std::max(1, perCU) * c->numCUs;
-        // (the POWER instance of the tail kernel fills the chip by its OWN occupancy: the default mode's grid does not depend on it)
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, tail_kernel_ptr(true), kTraceBlockThreads, 0) != hipSuccess || perCU < 1) perCU = 2;
-        c->tailBlocksPower = std::max(1, perCU) * c->numCUs;
-        for (int power = 0; power < 2; power++) {  // (... and so do the instances of a context with analytic lights)
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, tail_kernel_ptr(power != 0, true), kTraceBlockThreads, 0) != hipSuccess || perCU < 1) perCU = 2;
-            c->tailBlocksAnalytic[power] = std::max(1, perCU) * c->numCUs;
+        static_assert(sizeof c->tailBlocks / sizeof c->tailBlocks[0] == kMfAll + 1u, "one entry per set of material features");
+        for (unsigned set = 0; set <= kMfAll; set++) {  // (every tail instance some unit compiled: a set without one keeps 0)
+            const void* const tail = kernels::tail(set).fn;
+            if (!tail) continue;
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, tail, kTraceBlockThreads, 0) != hipSuccess || perCU < 1) perCU = 2;
+            c->tailBlocks[set] = std::max(1, perCU) * c->numCUs;
         }
-        for (int power = 0; power < 2; power++)  // (... and the DETAIL instances of a context with normal or roughness maps)
-            for (int analytic = 0; analytic < 2; analytic++) {
-                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, tail_detail_kernel_ptr(power != 0, analytic != 0), kTraceBlockThreads, 0) != hipSuccess || perCU < 1) perCU = 2;
-                c->tailBlocksDetail[power][analytic] = std::max(1, perCU) * c->numCUs;
-            }
-        for (int power = 0; power < 2; power++)  // (... and the METAL instances of a context with an NX_MAT_METALROUGH material)
-            for (int analytic = 0; analytic < 2; analytic++) {
-                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, tail_metal_kernel_ptr(power != 0, analytic != 0), kTraceBlockThreads, 0) != hipSuccess || perCU < 1) perCU = 2;
-                c->tailBlocksMetal[power][analytic] = std::max(1, perCU) * c->numCUs;
-            }
         // Launch-geometry knobs of the measurement sweeps.  They are read only when NX_TUNING_KNOBS=1 says
         // that a sweep is running: a stray variable in a user's environment does not reconfigure the product.
         if (const char* on = std::getenv("NX_TUNING_KNOBS"); on && std::atoi(on) == 1) {

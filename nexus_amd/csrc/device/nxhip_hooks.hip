@@ -50,7 +50,10 @@ static int run_trace_chunk(nxhip_ctx* c, bool anyHit, uint32_t n, bool transmit 
     // (a table with a MASK material: the ALPHA_TEST instances, whatever the hook — nxhip_set_material_alpha)
     const bool alphaTest = c->materialsAlphaMask;
     const bool thin = c->thinInHooks && !c->statsEnabled && !transmit && !alphaTest;  // (the TRANSMIT and ALPHA_TEST instances never hand over)
-    Launch l = make_launch(alphaTest ? kernels::trace_alpha(anyHit, c->statsEnabled, transmit) : transmit ? kernels::trace_transmit(c->statsEnabled) : kernels::trace(anyHit, c->statsEnabled), anyHit ? c->shadowBlocks : c->traceBlocks, kTraceBlockThreads,
+    const unsigned set = hook_trace_features(c, anyHit, transmit);
+    const kernels::BounceKernel trace = kernels::trace(set);
+    if (!trace.fn) return fail_invalid("ray batch: trace_kernel has no instance of feature set " + std::to_string(set));
+    Launch l = make_launch(trace, anyHit ? c->shadowBlocks : c->traceBlocks, kTraceBlockThreads,
                            anyHit ? NXHIP_K_SHADOW : NXHIP_K_TRACE, c->dState.as<DeviceState>(), kHookBounceSlot | (thin ? kTraceThinFlag : 0));
     int rc = launch_now(c, l);
     if (rc == NXHIP_OK && thin) {  // (nxhip_debug_set_thin: what the dry waves handed over, a wave each)

@@ -299,6 +299,70 @@ int pass_flavor(const nxhip_ctx* c)
     return f & ~(c->flavorForceGeneral & kFlavorSpecialised);  // (test hook: nxhip_debug_pass_flavor)
 }
 
+// Which compile-time instances (nx_variants.h) a flavor's launches are: the ONE place that decides it.  Every set that leaves here
+// is one some unit compiled; what a family has no form of is dropped here, in the open, and nowhere else.
+// The material features of a flavor: what the SCAN pipeline's material launch and the tail kernel are instances of.
+constexpr unsigned material_features(int flavor)
+{
+    unsigned f = 0u;
+    if (flavor & kFlavorLightPower) f |= kMfPower;
+    if (flavor & kFlavorAnalytic) f |= kMfAnalytic;
+    if (flavor & kFlavorDetail) f |= kMfDetail;
+    if (flavor & kFlavorMetal) f |= kMfMetal;
+    if (flavor & kFlavorSolid) f |= kMfSolid;
+    if ((flavor & kFlavorNoMaps) && (flavor & kFlavorScan)) f |= kMfNoMaps;  // (the classic pipeline never asks for the map-free form)
+    return material_closure(f);  // SOLID => METAL => DETAIL, and any of them drops NO_MAPS
+}
+// ... of the classic pipeline's material kernel of one type.  Its TYPE says what METAL would, so the bit goes — and with it the
+// DETAIL it implied, unless the scene has detail maps or alpha modes itself: the four reference types of a table with the fifth keep the
+// kernels they had, the fifth type's kernel is a DETAIL instance always.
+constexpr unsigned shade_features(int flavor, int type)
+{
+    return material_features(type == NX_MAT_METALROUGH ? flavor : (flavor & ~kFlavorMetal)) & kMfShadeReads;
+}
+// ... of the tail kernel: it has no map-free form (and no SOLID one: tail_bounce is 0 then, and a set with the bit finds no instance)
+constexpr unsigned tail_features(int flavor) { return material_features(flavor) & ~kMfNoMaps; }
+// ... of the medium's scatter kernel and of the logic kernel: they shade no surface, so each knows the facts it reads and no closure
+constexpr unsigned medium_features(int flavor) { return material_features(flavor & (kFlavorLightPower | kFlavorAnalytic | kFlavorMetal)) & kMfMediumReads; }
+// (logic_kernel: the analytic lights' count enters the weighted miss, which needs an environment map — the two-item instance of
+//  scenes without one has no ANALYTIC form)
+constexpr unsigned logic_features(int flavor, int items) { return items == 1 ? material_features(flavor) & kMfLogicReads : 0u; }
+
+// The trace features of one launch of a flavor's pass: any-hit or closest-hit, the primary launch or a bounce's, counting or not.
+constexpr unsigned trace_features(int flavor, bool anyHit, bool primary, bool counting)
+{
+    unsigned f = (anyHit ? kTfAnyHit : 0u) | (counting ? kTfCounting : 0u);
+    if (flavor & kFlavorIdentity) f |= kTfIdentity;
+    if ((flavor & kFlavorEntry) && primary && !anyHit) f |= kTfEntry;  // (the only launch that installs entry states)
+    if ((flavor & kFlavorTransmit) && anyHit) f |= kTfTransmit;
+    if (flavor & kFlavorAlphaTest) f |= kTfAlphaTest;
+    if (f & kTfCounting) f &= ~(kTfIdentity | kTfEntry);   // the counting variants read the scene's flag and keep the install either way
+    if (f & kTfAlphaTest) f &= ~(kTfIdentity | kTfEntry);  // the general instances and their counting variants only
+    if (f & kTfTransmit) f &= ~kTfIdentity;                // (reads sceneFlags: no IDENTITY form)
+    return f;
+}
+// (build-time tests of the selection, for the flavors that matter)
+static_assert(material_features(kFlavorScan) == 0u && trace_features(kFlavorScan, false, true, false) == 0u && trace_features(kFlavorScan, true, false, false) == kTfAnyHit,
+              "the default scan flavor: no feature");
+static_assert(material_features(kFlavorScan | kFlavorIdentity | kFlavorNoMaps) == kMfNoMaps && trace_features(kFlavorScan | kFlavorIdentity | kFlavorNoMaps, false, false, false) == kTfIdentity &&
+                  trace_features(kFlavorScan | kFlavorIdentity | kFlavorEntry, false, true, false) == (kTfIdentity | kTfEntry) && tail_features(kFlavorScan | kFlavorNoMaps) == 0u,
+              "an identity-only, map-free scene: the specialised instances, and the general tail kernel");
+static_assert(material_features(kFlavorScan | kFlavorAnalytic | kFlavorLightPower) == (kMfAnalytic | kMfPower) && logic_features(kFlavorAnalytic, 1) == kMfAnalytic && logic_features(kFlavorAnalytic, 2) == 0u,
+              "analytic lights with power sampling");
+static_assert(material_features(kFlavorScan | kFlavorSolid | kFlavorNoMaps) == (kMfSolid | kMfMetal | kMfDetail) && material_features(kFlavorScan | kFlavorMetal) == (kMfMetal | kMfDetail) &&
+                  material_features(kFlavorNoMaps) == 0u,
+              "SOLID implies METAL implies DETAIL, each drops NO_MAPS, and the classic pipeline never asks for it");
+static_assert(shade_features(kFlavorMetal, NX_MAT_DIFFUSE) == 0u && shade_features(kFlavorMetal, NX_MAT_METALROUGH) == kMfDetail &&
+                  shade_features(kFlavorSolid, NX_MAT_DIFFUSE) == (kMfSolid | kMfDetail) && medium_features(kFlavorSolid | kFlavorDetail | kFlavorMetal) == kMfMetal,
+              "the classic material kernels and the medium: METAL by the type, or by the table alone");
+static_assert(trace_features(kFlavorAlphaTest | kFlavorTransmit, true, false, false) == (kTfAnyHit | kTfAlphaTest | kTfTransmit) &&
+                  trace_features(kFlavorAlphaTest | kFlavorTransmit, false, false, false) == kTfAlphaTest &&
+                  trace_features(kFlavorAlphaTest | kFlavorEntry | kFlavorIdentity, false, true, false) == kTfAlphaTest &&
+                  trace_features(kFlavorTransmit | kFlavorIdentity, true, false, false) == (kTfAnyHit | kTfTransmit),
+              "alpha-test any-hit with transmit; alpha-test drops entry and identity, transmit drops identity");
+static_assert(trace_features(kFlavorIdentity, false, false, true) == kTfCounting && trace_features(kFlavorEntry, false, true, true) == kTfCounting,
+              "counting with identity or entry: counting alone");
+
 // The per-frame kernel sequence, in dependency "levels": launches of one level may run concurrently, a level
 // starts after the previous one has finished.  Reference DAG: Renderer/PathTracer.cpp:114-124, :259-278.
 std::vector<std::vector<Launch>> frame_levels(nxhip_ctx* c, PassSlot* q)
@@ -308,9 +372,21 @@ std::vector<std::vector<Launch>> frame_levels(nxhip_ctx* c, PassSlot* q)
     const int wide = c->wideBlocks;
     const int wideThreads = kWideBlockThreads;
     std::vector<std::vector<Launch>> levels;
+    // the kernel instances of this flavor (nx_variants.h): the material launches', and the three trace launches' of a pass
+    const int flavor = pass_flavor(c);
+    const unsigned mat = material_features(flavor), mediumSet = medium_features(flavor);
+    const unsigned primaryTrace = trace_features(flavor, false, true, stats), closestTrace = trace_features(flavor, false, false, stats), anyHitTrace = trace_features(flavor, true, false, stats);
     // the chain shape (graph_shape): every launch of a level behind the one in front of it, in the order the level lists them
     const bool chain = graph_shape(c) == kShapeChain;
-    auto shaped = [chain](std::vector<std::vector<Launch>>& ls) {
+    auto shaped = [=](std::vector<std::vector<Launch>>& ls) {
+        // (a set no unit compiled — unreachable while the units' lists cover the feature functions: the pass is refused, nothing launched)
+        for (auto& level : ls)
+            for (auto& l : level)
+                if (!l.fn) {
+                    (void)fail_invalid("render: no kernel instance for a launch of class " + std::to_string(l.klass) + ": material features " + std::to_string(mat) + " (medium " + std::to_string(mediumSet) +
+                                       "), trace features " + std::to_string(primaryTrace) + " / " + std::to_string(closestTrace) + " / " + std::to_string(anyHitTrace) + " (nx_variants.h)");
+                    return std::vector<std::vector<Launch>>{};
+                }
         if (chain)
             for (auto& level : ls)
                 for (size_t k = 1; k < level.size(); k++) {
@@ -323,33 +399,22 @@ std::vector<std::vector<Launch>> frame_levels(nxhip_ctx* c, PassSlot* q)
     levels.push_back({make_launch(kernels::generate(), wide, wideThreads, NXHIP_K_GENERATE, S)});
     // (the entry states the primary launch below installs are not a pass's work: the slot's table is walked in front of the pass
     //  that finds it stale — walk_entry_states — and read by every pass until an input of the walk changes)
-    const bool entry = (pass_flavor(c) & kFlavorEntry) != 0;
-    const bool lightPower = (pass_flavor(c) & kFlavorLightPower) != 0;
-    const bool identity = (pass_flavor(c) & kFlavorIdentity) != 0, noMaps = (pass_flavor(c) & kFlavorNoMaps) != 0;
-    const bool analytic = (pass_flavor(c) & kFlavorAnalytic) != 0;
-    const bool transmit = (pass_flavor(c) & kFlavorTransmit) != 0;
-    const bool solid = (pass_flavor(c) & kFlavorSolid) != 0;  // (then noMaps is off and tail_bounce is 0)
-    const bool alphaTest = (pass_flavor(c) & kFlavorAlphaTest) != 0;  // (then entry, identity and the thin flags below are all off: pass_flavor)
-    const bool metal = (pass_flavor(c) & kFlavorMetal) != 0;
-    const bool detail = (pass_flavor(c) & kFlavorDetail) != 0;
-    const bool medium = (pass_flavor(c) & kFlavorMedium) != 0;
-    const bool mediumGrid = (pass_flavor(c) & kFlavorMediumGrid) != 0;
-    // the any-hit launch of a bounce: the TRANSMIT instance never hands over (no kTraceThinFlag) and has no IDENTITY form
+    const bool entry = (flavor & kFlavorEntry) != 0, metal = (flavor & kFlavorMetal) != 0, medium = (flavor & kFlavorMedium) != 0, mediumGrid = (flavor & kFlavorMediumGrid) != 0;
+    const bool transmit = (flavor & kFlavorTransmit) != 0, alphaTest = (flavor & kFlavorAlphaTest) != 0;  // (alphaTest: entry, identity and the thin flags below are all off — pass_flavor)
+    // the any-hit launch of a bounce: the TRANSMIT and the ALPHA_TEST instances never hand over (no kTraceThinFlag)
     auto shadow_launch = [&](int shadowBlocksArg, int bounceArg, int thinFlagArg) {
-        if (alphaTest) return make_launch(kernels::trace_alpha(true, stats, transmit), shadowBlocksArg, kTraceBlockThreads, NXHIP_K_SHADOW, S, bounceArg);
-        return transmit ? make_launch(kernels::trace_transmit(stats), shadowBlocksArg, kTraceBlockThreads, NXHIP_K_SHADOW, S, bounceArg)
-                        : make_launch(kernels::trace(true, stats, identity), shadowBlocksArg, kTraceBlockThreads, NXHIP_K_SHADOW, S, bounceArg | thinFlagArg);
+        return make_launch(kernels::trace(anyHitTrace), shadowBlocksArg, kTraceBlockThreads, NXHIP_K_SHADOW, S, bounceArg | ((transmit || alphaTest) ? 0 : thinFlagArg));
     };
     const int traceBlocks = trace_blocks(c, c->traceBlocks), shadowBlocks = trace_blocks(c, c->shadowBlocks);
     // (the dry waves of a pass's trace launches may hand their last long rays to the thin kernel: nx_trace.hip)
-    const int thinFlag = (pass_flavor(c) & kFlavorThin) ? kTraceThinFlag : 0;
+    const int thinFlag = (flavor & kFlavorThin) ? kTraceThinFlag : 0;
     // (the thin kernel's one-lane replay of a closest-hit ray names the hit's SCAN code itself, for the four reference types: the closest-hit
     //  launches of a SCAN pass with the fifth type hand nothing over; its any-hit launches do, and so does the classic pipeline, which has no codes)
     const int thinFlagClosest = (metal && scan_pipeline(c)) ? 0 : thinFlag;
     // (with entry points the primary launch is its own kernel instance: the only one that carries the install code)
     // the closest-hit launch of a bounce (not the primary one with entry points, below)
-    auto closest_kernel = [&]() { return alphaTest ? kernels::trace_alpha(false, stats) : kernels::trace(false, stats, identity); };
-    levels.push_back({make_launch((entry && !stats) ? kernels::trace_entry(identity) : closest_kernel(), traceBlocks, kTraceBlockThreads, NXHIP_K_TRACE, S,
+    auto closest_kernel = [&]() { return kernels::trace(closestTrace); };
+    levels.push_back({make_launch(kernels::trace(primaryTrace), traceBlocks, kTraceBlockThreads, NXHIP_K_TRACE, S,
                                   (entry ? kTraceEntryFlag : 0) | thinFlagClosest | (scan_pipeline(c) ? kTraceScanFlag : 0))});
     // behind the trace launch(es) of a level: the rays their dry waves handed over, a wave each (thin_kernel)
     // — each trace launch of the level gets its own, chained to it alone, so that the closest-hit rays' searches run beside whatever
@@ -383,7 +448,7 @@ std::vector<std::vector<Launch>> frame_levels(nxhip_ctx* c, PassSlot* q)
     // the bounce-1 material step only reads too, and that nothing writes before the trace launches of bounce 1 — so it runs BESIDE that
     // step, as one more launch of its level
     auto aov_beside = [&](std::vector<Launch>& level) {
-        if (pass_flavor(c) & kFlavorAov) level.push_back(make_launch(kernels::aov(), wide, wideThreads, NXHIP_K_SHADE, S));
+        if (flavor & kFlavorAov) level.push_back(make_launch(kernels::aov(), wide, wideThreads, NXHIP_K_SHADE, S));
     };
     if (scan_pipeline(c)) {
         // SCAN pipeline (nx_wavefront.hip): the closest-hit launch leaves the logic step's decision in its hit records, the material
@@ -391,12 +456,13 @@ std::vector<std::vector<Launch>> frame_levels(nxhip_ctx* c, PassSlot* q)
         // fifth type, only when a miss can contribute) -> [count_scan_kernel] -> trace || shadow trace.  One launch less per bounce than
         // the reference's DAG.
         thin_level(0 | kTraceScanFlag);
-        const bool misses = pass_flavor(c) & kFlavorMissKernel;
-        const int dropFlag = (pass_flavor(c) & kFlavorDropEnded) ? kShadeDropEnded : 0;
+        const bool misses = flavor & kFlavorMissKernel;
+        const int dropFlag = (flavor & kFlavorDropEnded) ? kShadeDropEnded : 0;
         const int tailFrom = tail_bounce(c);
         for (int bounce = 1; bounce <= pathLength; bounce++) {
             if (bounce == tailFrom) {  // the rest of the pass in one launch
-                levels.push_back({make_launch(kernels::tail(lightPower, analytic, detail, metal), metal ? c->tailBlocksMetal[lightPower ? 1 : 0][analytic ? 1 : 0] : detail ? c->tailBlocksDetail[lightPower ? 1 : 0][analytic ? 1 : 0] : analytic ? c->tailBlocksAnalytic[lightPower ? 1 : 0] : (lightPower ? c->tailBlocksPower : c->tailBlocks), kTraceBlockThreads, NXHIP_K_SHADE, S, bounce | kTraceScanFlag)});
+                const unsigned tail = tail_features(flavor);  // (its grid: the instance's own, nxhip_create)
+                levels.push_back({make_launch(kernels::tail(tail), c->tailBlocks[tail], kTraceBlockThreads, NXHIP_K_SHADE, S, bounce | kTraceScanFlag)});
                 break;
             }
             int mask = (int)(c->materialTypeMask & 0xfu);
@@ -405,8 +471,8 @@ std::vector<std::vector<Launch>> frame_levels(nxhip_ctx* c, PassSlot* q)
             if (misses) mask |= 1 << kScanMiss;
             if (metal) mask |= 1 << kScanMetalBit;  // (the type's own number is the misses' bit: nx_device.h)
             // the medium's free-flight decision over the records the closest-hit level left, in front of the material launch that reads them
-            if (medium) levels.push_back({make_launch(mediumGrid ? kernels::medium_scatter_grid(lightPower, analytic, metal) : kernels::medium_scatter(lightPower, analytic, metal), whole_regions(wide), kShadeBlockThreads, NXHIP_K_SHADE, S, bounce | dropFlag)});
-            levels.push_back({make_launch(solid ? kernels::shade_scan_solid(lightPower, analytic) : kernels::shade_scan(lightPower, noMaps, analytic, detail, metal), og, kShadeBlockThreads, NXHIP_K_SHADE, S, bounce | dropFlag, mask)});
+            if (medium) levels.push_back({make_launch(kernels::medium_scatter(mediumGrid, mediumSet), whole_regions(wide), kShadeBlockThreads, NXHIP_K_SHADE, S, bounce | dropFlag)});
+            levels.push_back({make_launch(kernels::shade_scan(mat), og, kShadeBlockThreads, NXHIP_K_SHADE, S, bounce | dropFlag, mask)});
             if (bounce == 1) aov_beside(levels.back());
             if (in_use(NX_MAT_CONDUCTOR) && c->h.conductorMode != NX_CONDUCTOR_EXTENDED) {  // (counted, not shaded: count_scan_kernel)
                 levels.push_back({make_launch(kernels::count_scan(), lg, kWideBlockThreads, NXHIP_K_LOGIC, S, bounce, NX_MAT_CONDUCTOR)});
@@ -430,18 +496,18 @@ std::vector<std::vector<Launch>> frame_levels(nxhip_ctx* c, PassSlot* q)
     thin_level(0);
     const int ob = kShadeBlockOrderedThreads;
     for (int bounce = 1; bounce <= pathLength; bounce++) {
-        // Not only a tuning choice: logic_kernel<true, 2> is compiled WITHOUT the float lookup (nx_wavefront.hip logic_kernel), so under a
+        // Not only a tuning choice: the two-item logic_kernel is compiled WITHOUT the float lookup (nx_wavefront.hip logic_kernel), so under a
         // float map it would read float4 texels as RGBA8.  The two-item instance is for scenes with no environment map of either kind;
         // the same test as pass_flavor's kFlavorEnvMap (hdrMap.texels is set for both kinds: nxhip_scene.hip).
-        levels.push_back({make_launch(kernels::logic(c->hdrMap.texels.p ? 1 : 2, analytic), lg, lb, NXHIP_K_LOGIC, S, bounce)});
+        const int items = c->hdrMap.texels.p ? 1 : 2;
+        levels.push_back({make_launch(kernels::logic(items, logic_features(flavor, items)), lg, lb, NXHIP_K_LOGIC, S, bounce)});
         if (bounce == 1) aov_beside(levels.back());
         // (the fifth type's queue is filled by a kernel of its own behind the reference's logic kernel: nx_wavefront_metal.hip)
         if (metal) levels.push_back({make_launch(kernels::logic_metal(), lg, lb, NXHIP_K_LOGIC, S, bounce)});
         // graph insertion order of the reference: Diffuse, Plastic, Dielectric, Conductor (PathTracer.cpp:116-120)
         // (only the types some material of the scene has: a queue no material feeds stays empty)
         std::vector<Launch> shade;
-        // (a context with a MASK or an OPAQUE material: the SOLID instance of every type)
-        auto shade_kernel_of = [&](int type) { return solid ? kernels::shade_solid(type, lightPower, analytic) : type == NX_MAT_METALROUGH ? kernels::shade_metal(lightPower, analytic) : kernels::shade(type, lightPower, analytic, detail); };
+        auto shade_kernel_of = [&](int type) { return kernels::shade(type, shade_features(flavor, type)); };
         if (in_use(NX_MAT_DIFFUSE)) shade.push_back(make_launch(shade_kernel_of(NX_MAT_DIFFUSE), og, ob, NXHIP_K_SHADE, S, bounce));
         if (in_use(NX_MAT_PLASTIC)) shade.push_back(make_launch(shade_kernel_of(NX_MAT_PLASTIC), og, ob, NXHIP_K_SHADE, S, bounce));
         if (in_use(NX_MAT_DIELECTRIC)) shade.push_back(make_launch(shade_kernel_of(NX_MAT_DIELECTRIC), og, ob, NXHIP_K_SHADE, S, bounce));
@@ -458,6 +524,13 @@ std::vector<std::vector<Launch>> frame_levels(nxhip_ctx* c, PassSlot* q)
 }
 
 }  // namespace
+
+// The trace launch of a ray-batch hook (nxhip_hooks.hip): a bounce's launch of a pass that knows the table's MASK materials and, where
+// the hook asks for it, the transmittance — and no identity or entry instance (the counting variants and the hooks keep the scene's flag).
+unsigned nxd::hook_trace_features(const nxhip_ctx* c, bool anyHit, bool transmit)
+{
+    return trace_features((c->materialsAlphaMask ? kFlavorAlphaTest : 0) | (transmit ? kFlavorTransmit : 0), anyHit, false, c->statsEnabled);
+}
 
 // Issue one launch on the context's stream (or the slot's, when given); with kernel timing on, between an event pair of its own that joins the pool only once
 // everything has been issued (a failure leaves no entry behind for nxhip_read_kernel_times to trip over).
@@ -546,6 +619,7 @@ static int pass_graph(nxhip_ctx* c, PassSlot* q, hipGraphExec_t* execOut)
         return rc;
     };
     auto levels = frame_levels(c, q);
+    if (levels.empty()) return fail(NXHIP_ERR_INVALID);  // (a kernel instance nobody compiled: frame_levels has said which)
     std::vector<hipGraphNode_t> prev;
     for (auto& level : levels) {
         std::vector<hipGraphNode_t> cur;
@@ -711,6 +785,7 @@ try {
     if (c->timingEnabled && c->timingMode == 1) {
         // eager path: one event pair per launch, launches strictly in level order on one stream
         auto levels = frame_levels(c, q);
+        if (levels.empty()) return NXHIP_ERR_INVALID;  // (a kernel instance nobody compiled: frame_levels has said which)
         for (auto& level : levels)
             for (auto& l : level) NX_TRY(launch_now(c, l));
     } else {

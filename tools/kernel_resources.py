@@ -18,6 +18,22 @@ def demangle(names):
     return [re.sub(r"\((?:[^()]|\([^()]*\))*\)\s*$", "", o).replace("void ", "").replace("nxd::", "").replace("(anonymous namespace)::", "") for o in out]
 
 
+# The instances of the kernel families carry a set of features as an unsigned template argument (nexus_amd/csrc/device/nx_variants.h:
+# kTf* for trace_kernel, kMf* for the rest): printed by name, from the header's own constants, e.g. trace_kernel<anyhit+transmit>.
+BITS = {"Tf": [], "Mf": []}
+for kind, name, bit in re.findall(r"constexpr unsigned k(Tf|Mf)(\w+) = (\d+)u;", open(os.path.join(ROOT, "nexus_amd/csrc/device/nx_variants.h")).read()):
+    if name != "All":
+        BITS[kind].append((int(bit), name.lower()))
+
+
+def named(n):
+    m = re.match(r"(\w+)<(.*?)(\d+)u>$", n)
+    if not m:
+        return n
+    bits = BITS["Tf" if m.group(1) == "trace_kernel" else "Mf"]
+    return "%s<%s%s>" % (m.group(1), m.group(2), "+".join(name for bit, name in bits if int(m.group(3)) & bit) or "none")
+
+
 print("%-58s %5s %5s %5s %7s %8s %6s %5s" % ("kernel", "VGPR", "AGPR", "SGPR", "spilled", "scratch", "LDS", "occ"))
 for src in sorted(glob.glob(os.path.join(ROOT, "nexus_amd/csrc/device/*.hip"))):
     with tempfile.NamedTemporaryFile(suffix=".s") as tmp:
@@ -39,4 +55,4 @@ for src in sorted(glob.glob(os.path.join(ROOT, "nexus_amd/csrc/device/*.hip"))):
     for (raw, v, a, s, sp, scr, lds), n in zip(rows, names):
         if "rocprim" in n and "--all" not in sys.argv:
             continue  # the sort library's kernels (device LBVH build)
-        print("%-58s %5s %5s %5s %7s %8s %6s %5s" % (n[:58], v, a, s, sp, scr, lds, occ_by_kernel.get(raw, "?")))
+        print("%-58s %5s %5s %5s %7s %8s %6s %5s" % (named(n)[:58], v, a, s, sp, scr, lds, occ_by_kernel.get(raw, "?")))

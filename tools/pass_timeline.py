@@ -10,9 +10,10 @@ line = []
 for r in rows[s:e]:
     n = re.sub(r"\(.*", "", r["Kernel_Name"]).replace("void nxd::", "").replace("nxd::", "")
     d = (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e6
-    if n.startswith("trace_kernel<false"):
+    m = re.match(r"trace_kernel<(\d+)u>", n)  # (a set of trace features, nx_variants.h: bit 0 is any hit)
+    if m and not int(m.group(1)) & 1:
         line.append("T%.2f" % d)
-    elif n.startswith("trace_kernel<true"):
+    elif m:
         line.append("S%.2f" % d)
     elif n.startswith("logic"):
         line.append("L%.2f" % d)

@@ -24,6 +24,18 @@ a = ap.parse_args()
 #  waves handed over)
 KERNELS = {"trace_closest": ("trace_kernel<false, false",), "trace_shadow": ("trace_kernel<true, false",), "logic": ("logic_kernel<", "miss_scan_kernel"),
            "shade": ("shade_kernel<", "shade_scan_kernel"), "thin": ("thin_kernel",)}
+
+
+def in_class(k, name):
+    """trace_kernel<Nu> carries a set of trace features (nx_variants.h: bit 0 any hit, bit 1 the counting variant, which no class
+    takes); the profiles of earlier rounds spell the two as leading bools — KERNELS' patterns."""
+    m = re.search(r"trace_kernel<(\d+)u>", name)
+    if m:
+        n = int(m.group(1))
+        return not n & 2 and k == ("trace_shadow" if n & 1 else "trace_closest")
+    return any(pat in name for pat in KERNELS[k])
+
+
 bench = json.load(open(a.bench))
 rf = bench["roofline"]
 rays = {"trace_closest": rf["rays_per_frame"] * a.frames, "trace_shadow": rf["shadow"]["rays_per_frame"] * a.frames,
@@ -55,8 +67,8 @@ for d in a.passes:
     names = set()
     for f in glob.glob(d + "/**/*counter_collection.csv", recursive=True):
         for r in csv.DictReader(open(f)):
-            for k, pats in KERNELS.items():
-                if any(pat in r["Kernel_Name"] for pat in pats):
+            for k in KERNELS:
+                if in_class(k, r["Kernel_Name"]):
                     sums[k][r["Counter_Name"]] += float(r["Counter_Value"])
                     names.add(r["Counter_Name"])
                     if r["Dispatch_Id"] not in seen[k]:

@@ -34,7 +34,8 @@ print("hardware queue -> streams: " + ", ".join("%s -> %s" % (q, sorted({r["Stre
 def kind(r):
     if r["n"].startswith("shade_scan"):
         return "material"
-    if r["n"].startswith("trace_kernel") and not re.match(r"trace_kernel<\w+, \w+, true", r["n"]):  # (third argument: the primary launch's entry instance)
+    m = re.match(r"trace_kernel<(\d+)u>", r["n"])
+    if m and not int(m.group(1)) & 4:  # (a set of trace features, nx_variants.h — bit 2: the primary launch's entry instance)
         return "trace"
     return None
 
