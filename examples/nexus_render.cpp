@@ -3,7 +3,7 @@
 //
 //   nexus_render [--denoise] [--adaptive THRESHOLD [--max-frames N]] [--light-sampling uniform|power] [--transparent-shadows] [--env-float FILE.hdr] [--env-sampling]
 //                [--no-detail-maps] [--metal-rough] [--alpha-modes] [--fog SIGMA [--fog-albedo R G B] [--fog-g G] [--fog-box X0 Y0 Z0 X1 Y1 Z1] [--fog-grid FILE.npy]]
-//                [--point-light X Y Z INTENSITY] [--sun DX DY DZ IRRADIANCE] <dir/> <file.glb|file.obj> <out.ppm> [width height frames pathLength]
+//                [--point-light X Y Z INTENSITY] [--sun DX DY DZ IRRADIANCE] [--time T [--animation K]] <dir/> <file.glb|file.obj> <out.ppm> [width height frames pathLength]
 //                [eyeX eyeY eyeZ fwdX fwdY fwdZ hfovDeg]
 // --denoise: the feature buffers are accumulated with the colour and the image written is the a-trous filtered one (nxhip_denoise)
 // --adaptive THRESHOLD: render to a noise target instead of a frame count (nxhip_render_adaptive: blocks of 64 pixels stop when the
@@ -30,6 +30,9 @@
 //   0), --fog-box X0 Y0 Z0 X1 Y1 Z1 (default: the scene's world bounds grown by 10 %).  Needs pixel-keyed random numbers: it switches them on.
 // --fog-grid FILE.npy: a density grid over the fog's box (Scene::SetMediumDensity, nxhip_set_medium_density) — a float32 .npy array of shape
 //   (nz, ny, nx); the extinction at a point becomes SIGMA x the trilinear lookup there: a cloud, not a haze.  Needs --fog; honours --fog-box.
+// --time T [--animation K]: a .glb's skins are kept (Scene::SetSkins) and every skinned mesh of the file is posed at T seconds of animation K
+//   (default 0; a file without animations: the rest pose) before rendering — the pose is evaluated on the host (Scene::JointPalette), the
+//   vertices are blended and the mesh's BVH refitted on the device (PathTracer::PoseMesh, nxhip_pose_blas).  One pose holds for the image.
 //
 // Build: make example   (links nexus_amd/lib/libnexus_amd.so)
 #include <cstdint>
@@ -60,6 +63,9 @@ int main(int argc, char** argv)
     bool fog = false, fogBox = false;
     nexus::Medium medium;
     std::string fogGrid;
+    bool posed = false;
+    double poseTime = 0.0;
+    int poseAnimation = 0;
     for (;;) {  // leading options, in any order
         const std::string opt = argc > 1 ? argv[1] : "";
         int used = 0;
@@ -99,6 +105,13 @@ int main(int argc, char** argv)
         } else if (opt == "--alpha-modes") {
             alphaModes = true;
             used = 1;
+        } else if (opt == "--time" && argc > 2) {
+            posed = true;
+            poseTime = std::atof(argv[2]);
+            used = 2;
+        } else if (opt == "--animation" && argc > 2) {
+            poseAnimation = std::atoi(argv[2]);
+            used = 2;
         } else if (opt == "--fog" && argc > 2) {
             fog = true;
             medium.sigmaT = static_cast<float>(std::atof(argv[2]));
@@ -138,7 +151,7 @@ int main(int argc, char** argv)
         return 2;
     }
     if (argc < 4) {
-        std::fprintf(stderr, "usage: %s [--denoise] [--adaptive THRESHOLD [--max-frames N]] [--light-sampling uniform|power] [--transparent-shadows] [--env-float FILE.hdr] [--env-sampling] [--no-detail-maps] [--metal-rough] [--alpha-modes] [--fog SIGMA [--fog-albedo R G B] [--fog-g G] [--fog-box X0 Y0 Z0 X1 Y1 Z1] [--fog-grid FILE.npy]] [--point-light X Y Z INTENSITY] [--sun DX DY DZ IRRADIANCE] <dir/> <file.glb|file.obj> <out.ppm> [width height frames pathLength] [eye(3) forward(3) hfov]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s [--denoise] [--adaptive THRESHOLD [--max-frames N]] [--light-sampling uniform|power] [--transparent-shadows] [--env-float FILE.hdr] [--env-sampling] [--no-detail-maps] [--metal-rough] [--alpha-modes] [--fog SIGMA [--fog-albedo R G B] [--fog-g G] [--fog-box X0 Y0 Z0 X1 Y1 Z1] [--fog-grid FILE.npy]] [--point-light X Y Z INTENSITY] [--sun DX DY DZ IRRADIANCE] [--time T [--animation K]] <dir/> <file.glb|file.obj> <out.ppm> [width height frames pathLength] [eye(3) forward(3) hfov]\n", argv[0]);
         return 2;
     }
     // a program built against these headers and run with another build of libnexus_amd.so gets an error string here, not a GPU fault
@@ -167,7 +180,19 @@ int main(int argc, char** argv)
         }
         scene.SetMetalRoughMaterials(metalRough);
         scene.SetMaterialAlphaModes(alphaModes);
+        scene.SetSkins(posed);
         scene.CreateMeshInstanceFromFile(dir, file);  // (a .glb's KHR_lights_punctual lights come with it)
+        size_t posedMeshes = 0;
+        if (posed) {  // before the first Update: the instances are then placed around the posed boxes
+            const int animation = scene.GetAnimations().empty() ? -1 : poseAnimation;
+            const std::vector<nexus::Mesh>& meshes = scene.GetAssetManager().GetMeshes();
+            for (size_t m = 0; m < meshes.size(); m++) {
+                if (!meshes[m].skin) continue;
+                pathTracer.PoseMesh(scene, meshes[m].bvhId, scene.JointPalette(static_cast<uint32_t>(m), animation, poseTime));
+                posedMeshes++;
+            }
+            if (posedMeshes == 0) std::fprintf(stderr, "nexus_render: --time: %s has no skinned mesh; rendered as it is\n", file.c_str());
+        }
         if (!detailMaps) scene.GetAssetManager().ClearMaterialDetails();  // (the file's normal and roughness maps: loaded, not used)
         for (const nexus::AnalyticLight& l : extraLights) scene.AddAnalyticLight(l);
         scene.GetCamera()->LookAt(nexus::make_float3(cam[0], cam[1], cam[2]), nexus::make_float3(cam[3], cam[4], cam[5]));
@@ -240,6 +265,7 @@ int main(int argc, char** argv)
         std::fclose(fp);
         std::printf("%s: %u x %u, %d frames, %zu instances, %zu lights%s%s\n", out.c_str(), width, height, frames, scene.GetBVHInstances().size(), scene.GetLights().size(),
                     deviceBuilders ? ", BVHs built on the device" : "", denoise ? ", denoised" : "");
+        if (posedMeshes) std::printf("posed %zu skinned mesh(es) at t = %g s of animation %d\n", posedMeshes, poseTime, poseAnimation);
         if (adaptive) {
             std::vector<uint32_t> counts;
             pathTracer.ReadSampleCounts(counts);

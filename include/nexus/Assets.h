@@ -5,6 +5,7 @@
 #pragma once
 
 #include <functional>
+#include <memory>
 #include <set>
 #include <string>
 #include <vector>
@@ -95,6 +96,39 @@ struct DensityGrid {
     std::vector<float> voxels;
 };
 
+// Extension (skinned meshes; the blending rule: nexus_hip.h, nxhip_pose_blas): the skin of one mesh as the .glb reader finds it
+// (LoadOptions::skins) — per triangle corner four joints and weights, de-indexed like the positions; the skin's joints as indices into
+// Scene::GetNodes(); their inverse bind matrices (row major, binary64); the node that carries the mesh.  Scene::JointPalette evaluates a
+// pose from it, PathTracer::PoseMesh sends it to the device on first use.
+struct Skin {
+    std::vector<nx_skin_corner> corners;  // 3 per triangle: corner 3 i + v is vertex v of triangle i
+    std::vector<int> joints;
+    std::vector<double> inverseBind;      // 16 per joint
+    int meshNode = -1;
+    bool onDevice = false;                // nxhip_set_blas_skin has been called for the mesh's BLAS
+};
+
+// ... a node of a loaded file's tree (parent and rest TRS), and a joint animation as channels
+struct SceneNode {
+    std::string name;
+    int parent = -1;  // index into Scene::GetNodes(); -1: a root
+    double translation[3] = {0, 0, 0}, rotation[4] = {0, 0, 0, 1}, scale[3] = {1, 1, 1};
+    bool hasMatrix = false;  // the file gave a matrix instead of a TRS: used as it is unless a channel animates the node
+    double matrix[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};  // row major
+};
+struct AnimationChannel {
+    enum Path { TRANSLATION = 0, ROTATION = 1, SCALE = 2 };
+    int node = -1;
+    Path path = TRANSLATION;
+    bool step = false;            // STEP; else LINEAR (rotations: shortest-arc slerp).  CUBICSPLINE is read as LINEAR over the keys' values
+    std::vector<double> times;    // ascending
+    std::vector<double> values;   // 3 (4 for rotations) per key
+};
+struct Animation {
+    std::string name;
+    std::vector<AnimationChannel> channels;
+};
+
 struct Mesh {
     Mesh() = default;
     Mesh(const std::string& n, int32_t bId = -1, int32_t mId = -1, float3 p = make_float3(0.0f), float3 r = make_float3(0.0f), float3 s = make_float3(1.0f))
@@ -105,6 +139,7 @@ struct Mesh {
     float3 position = make_float3(0.0f), rotation = make_float3(0.0f), scale = make_float3(1.0f);
     int32_t materialId = -1;
     std::string name;
+    std::shared_ptr<Skin> skin;  // empty: the mesh is not skinned
 };
 
 struct MeshInstance {
@@ -147,7 +182,11 @@ public:
     // re-derives the world bounds of the mesh's instances and brings the TLAS up to date, and PathTracer::UpdateDeviceScene
     // sends the mesh through nxhip_update_blas — no new BLAS id, no new instances.  Throws on another triangle count.
     void UpdateMeshTriangles(int32_t bvhId, const std::vector<Triangle>& triangles);
-    // BVH ids changed by UpdateMeshTriangles since Scene::Update last asked (it re-places their instances)
+    // Extension (skinned meshes): BVH `bvhId` was posed on the device (PathTracer::PoseMesh) and its root now encodes [lo, hi].
+    // BVHInstance::SetTransform uses that box for the mesh's instances from here on, and the mesh joins the set Scene::Update consumes —
+    // but NOT `deformedBvhs`: the host's triangles are the bind pose, and sending them would overwrite the pose.
+    void SetPosedBounds(int32_t bvhId, const float lo[3], const float hi[3]);
+    // BVH ids changed by UpdateMeshTriangles or SetPosedBounds since Scene::Update last asked (it re-places their instances)
     std::set<int32_t> TakeDeformedBvhs();
     void AddMaterial();
     int AddMaterial(const Material& material);

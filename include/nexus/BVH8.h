@@ -31,6 +31,12 @@ struct BVH8 {
 
     // Device handle once uploaded through the C-ABI device layer (nxhip_upload_blas); -1 before.
     int32_t deviceBlasId = -1;
+
+    // Extension (skinned meshes): the mesh was posed ON THE DEVICE (PathTracer::PoseMesh), so `nodes` and `triangles` above still hold
+    // the bind pose; this is the box the device's root node encodes (nxhip_read_blas_bounds), which BVHInstance::SetTransform then
+    // derives the world bounds from in place of nodes[0]'s frame.  AssetManager::SetPosedBounds sets it, UpdateMeshTriangles clears it.
+    bool posed = false;
+    float posedMin[3] = {0.0f, 0.0f, 0.0f}, posedMax[3] = {0.0f, 0.0f, 0.0f};
 };
 
 }  // namespace nexus

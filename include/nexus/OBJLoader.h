@@ -5,6 +5,7 @@
 // OBJLoader.cpp:71-163, aiProcess_FlipUVs.  Reads binary glTF 2.0 (.glb) and triangulated / polygonal Wavefront .obj.
 #pragma once
 
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -41,6 +42,11 @@ struct LoadedScene {
     // (LoadOptions::alphaModes), else empty: every material's alpha is a stochastic blend, as it has always been
     std::vector<nx_material_alpha> materialAlpha;
     std::vector<AnalyticLight> analyticLights;  // glTF KHR_lights_punctual: one per node that carries a light, in world space
+    // glTF skins, joint animations and the node tree — filled only when asked for (LoadOptions::skins), else empty.  skins[i] belongs to
+    // meshes[i] (empty pointer: not skinned); node indices are the file's.
+    std::vector<std::shared_ptr<Skin>> skins;
+    std::vector<SceneNode> nodes;
+    std::vector<Animation> animations;
     std::vector<std::string> warnings;  // images that could not be decoded (the reference prints and carries on, IMGLoader.cpp:24-25)
 };
 
@@ -52,9 +58,13 @@ struct LoadedScene {
 // glTF's default — and alphaCutoff (default 0.5) are read into LoadedScene::materialAlpha, and LoadOBJ hands them to the AssetManager
 // (SetMaterialAlpha).  A MASK material whose alphaCutoff lies outside [0, 1] is refused by the reader, with the material's number.  .obj files
 // carry no such mode: their materials stay blends.
+// skins (off by default, so every existing scene loads as before): a .glb's skins, JOINTS_0 / WEIGHTS_0, joint animations and node tree are
+// read into LoadedScene::skins / animations / nodes, and LoadOBJ hands them to the meshes and the scene.  Morph targets and JOINTS_1 are
+// ignored with a warning; a CUBICSPLINE sampler is read as its keys' values and interpolated linearly, with a warning.
 struct LoadOptions {
     bool metalRough = false;
     bool alphaModes = false;
+    bool skins = false;
 };
 
 class OBJLoader {

@@ -31,6 +31,12 @@ public:
     // AssetManager::CreateBVH's host build; the nodes come back once, so BVH8::nodes / triangleIdx hold the tree as they do for
     // a host-built one.  The scene must not outlive this PathTracer while the switch is on.
     void SetDeviceBlasBuild(Scene& scene, bool enable);
+    // Extension (skinned meshes): pose the mesh whose BVH is `bvhId` with a joint palette (Scene::JointPalette: joints x 12 floats).  An
+    // immediate call, made BEFORE Scene::Update: the mesh's skin goes to the device on first use (nxhip_set_blas_skin), the device blends
+    // the vertices and refits the BLAS (nxhip_pose_blas), and the box its root then encodes comes back (nxhip_read_blas_bounds: one small
+    // read per posed mesh) for AssetManager::SetPosedBounds — from there Scene::Update and UpdateDeviceScene proceed as for a deformed
+    // mesh, in all three TLAS modes.  The host's copy of the triangles stays the bind pose.  Throws for a mesh without a skin.
+    void PoseMesh(Scene& scene, int32_t bvhId, const std::vector<float>& palette);
     void SetPixelQuery(uint32_t x, uint32_t y);
     int32_t GetSelectedInstance();
     uint32_t GetFrameNumber() const { return m_FrameNumber; }

@@ -33,6 +33,22 @@ public:
     // (nxhip_set_material_alpha): MASK cutouts are holes for every ray, OPAQUE ignores an unused alpha channel.  Off: alpha blends.
     void SetMaterialAlphaModes(bool on) { m_MaterialAlphaModes = on; }
     bool GetMaterialAlphaModes() const { return m_MaterialAlphaModes; }
+    // Extension, off by default: the files loaded from here on keep their glTF skins, joint animations and node tree (OBJLoader.h
+    // LoadOptions::skins): Mesh::skin, GetAnimations(), GetNodes().  JointPalette evaluates a pose on the host in binary64 — it costs joints,
+    // not vertices — and PathTracer::PoseMesh has the device blend the vertices and refit the mesh's BVH (nxhip_pose_blas).
+    void SetSkins(bool on) { m_Skins = on; }
+    bool GetSkins() const { return m_Skins; }
+    const std::vector<SceneNode>& GetNodes() const { return m_Nodes; }
+    const std::vector<Animation>& GetAnimations() const { return m_Animations; }
+    // (used by OBJLoader::LoadOBJ: a file's nodes and animations, their node indices already those of GetNodes())
+    void AddNodes(const std::vector<SceneNode>& nodes) { m_Nodes.insert(m_Nodes.end(), nodes.begin(), nodes.end()); }
+    void AddAnimation(const Animation& animation) { m_Animations.push_back(animation); }
+    // The joint palette of skinned mesh `meshId` with animation `animationIdx` (-1: the rest pose) sampled at time t, clamped to each
+    // channel's first and last key: jointCount x 12 floats, row j the row-major 3 x 4 matrix
+    // inverse(meshNodeWorld) x jointWorld[j] x inverseBind[j] (glTF's formula; the instance's own matrix puts meshNodeWorld back), rounded
+    // once to binary32.  STEP and LINEAR channels; rotations by shortest-arc slerp, normalised lerp when 1 - |q0 . q1| < 1e-9.  The twin of
+    // nexus_amd/animation.py joint_palette.  Throws for a mesh without a skin or an animation that does not exist.
+    std::vector<float> JointPalette(uint32_t meshId, int animationIdx, double t) const;
     // Place mesh `meshId` (AssetManager::AddMesh) with the mesh's own transform and material; a light is derived if its
     // material emits.  The returned reference is valid until the next instance is created.
     MeshInstance& CreateMeshInstance(uint32_t meshId);
@@ -125,6 +141,9 @@ private:
     bool m_HasMedium = false;
     bool m_MetalRoughMaterials = false;
     bool m_MaterialAlphaModes = false;
+    bool m_Skins = false;
+    std::vector<SceneNode> m_Nodes;
+    std::vector<Animation> m_Animations;
     DensityGrid m_MediumDensity;
     std::shared_ptr<TLAS> m_Tlas;
 

@@ -145,6 +145,48 @@ int nxhip_set_instance_transforms(nxhip_ctx *ctx, const uint32_t *instanceIds, c
  * stream order; it does not wait for the device.  A bad id, NULL or another count: NXHIP_ERR_INVALID, nothing changed. */
 int nxhip_update_blas(nxhip_ctx *ctx, int32_t blasId, const nx_triangle *tris, uint32_t triCount);
 int nxhip_update_blas_device(nxhip_ctx *ctx, int32_t blasId, const void *trisDevice, uint32_t triCount);
+/* Extension — skinned meshes: the step in front of the refit above.  A BLAS is given a skin once (four joints and weights per triangle
+ * corner, glTF's JOINTS_0 / WEIGHTS_0 de-indexed like the positions); after that a pose is `jointCount` matrices, and ONE kernel turns
+ * the bind-pose triangles and the joint palette into the BLAS's 96-byte triangles, its shading copy and its intersection stream (the
+ * stream bit-identical to what nxhip_update_blas makes of those triangles); the level-by-level node refit of nxhip_update_blas runs
+ * behind it.  The reference has nothing of the kind (its loader drops skins: Assets/OBJLoader.cpp).
+ *
+ * nxhip_set_blas_skin: cornerCount must be 3 x the BLAS's triangle count; corner 3 i + v belongs to vertex v of triangle i.  The call
+ * copies the BLAS's CURRENT triangles device to device into a bind copy and stores the corners; every later pose starts from that bind
+ * copy — poses never accumulate.  Weights are re-normalised on the host in binary64 to sum 1 and rounded once; a joint whose weight is 0
+ * is rewritten to index 0.  Refused with NXHIP_ERR_INVALID before anything is allocated, the previous state left in place: a bad id,
+ * another count, jointCount 0 or above 65536, a joint index >= jointCount on a corner whose weight for it is not 0, a weight that is
+ * negative or not finite, a corner whose weights sum to 0.  corners == NULL removes the skin and frees both buffers: the BLAS is then
+ * exactly what it was (triangles and nodes stay as last posed; nothing a pass is built from changes).  Works on any BLAS id: uploaded,
+ * device-built or one of a batch.  nxhip_update_blas(_device) on a skinned BLAS still works and does not touch the bind copy.
+ *
+ * nxhip_pose_blas: jointMatrices = jointCount x 12 floats, the row-major 3 x 4 object-space matrices (rotation-scale | translation) —
+ * for glTF, inverse(meshNodeWorld) x jointWorld[j] x inverseBind[j].  Copied to the BLAS's device palette in stream order, then the pose
+ * kernel and the refit; ordering and side effects are exactly nxhip_update_blas's (behind every pass already issued on any slot, before
+ * every later one; instances, traversal records and the TLAS follow at the next render, ray-batch hook or nxhip_read_tlas), and the call
+ * waits for the device only as nxhip_update_blas's host form does, for the pageable array.  A BLAS without a skin, another joint count,
+ * NULL or a matrix entry that is not finite: NXHIP_ERR_INVALID, nothing changed.
+ *
+ * THE BLENDING RULE, all of it in binary32; per corner, with its joints j_k and weights w_k, k = 0..3:
+ *   M  = sum_k w_k J[j_k]                     a 3 x 4 matrix
+ *   p' = M (p, 1)
+ *   N  = cof(M3), the cofactor matrix of M's upper 3 x 3 (= det(M3) M3^-T: correct under non-uniform scale)
+ *   n' = N n, negated when det(M3) < 0 (a mirroring pose), then normalised
+ * A bind normal of exactly (0, 0, 0) stays (0, 0, 0) (the loaders write one for meshes without NORMAL); a result whose length is 0 or
+ * not finite becomes (0, 0, 0) too.  Texture coordinates are copied.  Evaluation order and fma contraction are the compiler's: the tests
+ * bound the result (positions: gamma_8 x sum_k w_k sum_c |J_k[r][c]| |(p, 1)_c|), not its bits.  The palette is read from the LDS up to
+ * 1024 joints (48 KiB) and from global memory above.
+ * Not covered: morph targets and more than four influences (JOINTS_1) — the loaders warn and ignore them —; CUBICSPLINE samplers — the
+ * loaders warn, read the value component of each key and interpolate it linearly —; dual-quaternion blending; motion blur (one pose holds
+ * for a frame; nothing in traversal or shading changes); a restatement in the CPU oracle (the tests compare with float64 arithmetic and
+ * with nxhip_update_blas of the read-back triangles). */
+int nxhip_set_blas_skin(nxhip_ctx *ctx, int32_t blasId, const nx_skin_corner *corners, uint32_t cornerCount, uint32_t jointCount);
+int nxhip_pose_blas(nxhip_ctx *ctx, int32_t blasId, const float *jointMatrices, uint32_t jointCount);
+/* The BLAS's current 96-byte triangles (as uploaded, last updated or last posed); capacity >= its triangle count. */
+int nxhip_read_blas_triangles(nxhip_ctx *ctx, int32_t blasId, nx_triangle *out, uint32_t capacity);
+/* The box the BLAS's root node encodes after the last build, refit or pose: its quantisation frame [p, p + 255 x 2^(e - 127)], decoded as
+ * BVHInstance::SetTransform decodes it.  One 80-byte read behind the context's stream. */
+int nxhip_read_blas_bounds(nxhip_ctx *ctx, int32_t blasId, float lo[3], float hi[3]);
 /* Read the device's TLAS nodes / instance table back (tests; either destination may be NULL). */
 int nxhip_read_tlas(nxhip_ctx *ctx, nx_bvh8_node *nodes, uint32_t nodeCapacity, nx_bvh_instance *instances, uint32_t instanceCapacity);
 /* AssetManager device materials — Assets/AssetManager.cpp:57-62,106-116
@@ -1026,6 +1068,7 @@ static inline uint64_t nxhip_header_abi_stamp(void)
         sizeof(nx_material), offsetof(nx_material, emissive), offsetof(nx_material, type), sizeof(nx_light), offsetof(nx_light, type),
         sizeof(nx_analytic_light), offsetof(nx_analytic_light, direction), offsetof(nx_analytic_light, colour), offsetof(nx_analytic_light, innerConeAngle), offsetof(nx_analytic_light, type),
         sizeof(nx_material_detail), offsetof(nx_material_detail, normalScale), sizeof(nx_medium), sizeof(nx_material_alpha), offsetof(nx_material_alpha, cutoff),
+        sizeof(nx_skin_corner), offsetof(nx_skin_corner, weight),
         sizeof(nx_camera), offsetof(nx_camera, resolution), sizeof(nx_render_settings), offsetof(nx_render_settings, backgroundColor),
         sizeof(nx_ray), sizeof(nx_hit), sizeof(nx_bsdf_query), sizeof(nx_bsdf_result), offsetof(nx_bsdf_result, rngOut),
         sizeof(nxhip_queue_sizes), sizeof(nxhip_trace_stats), offsetof(nxhip_trace_stats, cycles), sizeof(nxhip_kernel_times), NXHIP_K_COUNT,

@@ -73,6 +73,10 @@ int nxh_load_scene_file(const char *file, nxh_loaded_scene **out);
 /* NXH_LOAD_ALPHA_MODES: a .glb material's alphaMode (glTF's default: OPAQUE) and alphaCutoff (default 0.5) are read as well and come back
  * from nxh_loaded_material_alpha; without the flag that call reports no table (every material blends, as it always has). */
 #define NXH_LOAD_ALPHA_MODES 2u
+/* NXH_LOAD_SKINS: a .glb's skins (JOINTS_0 / WEIGHTS_0 de-indexed like the positions), joint animations and node tree are read as well;
+ * nxh_loaded_skin reports a mesh's.  Morph targets and JOINTS_1 are ignored with a warning, a CUBICSPLINE sampler is read as its keys'
+ * values and interpolated linearly, with a warning.  Without the flag every mesh is unskinned, as it always has been. */
+#define NXH_LOAD_SKINS 4u
 int nxh_load_scene_file_ex(const char *file, uint32_t flags, nxh_loaded_scene **out);
 void nxh_loaded_scene_free(nxh_loaded_scene *s);
 uint32_t nxh_loaded_mesh_count(const nxh_loaded_scene *s);
@@ -105,6 +109,10 @@ int nxh_loaded_material_detail(const nxh_loaded_scene *s, int32_t *normalTexture
 /* The materials' alpha modes (nx_material_alpha, nexus_pod.h): *count = the material count when the file was read with NXH_LOAD_ALPHA_MODES,
  * else 0; dst (may be NULL) receives up to `capacity` records. */
 int nxh_loaded_material_alpha(const nxh_loaded_scene *s, nx_material_alpha *dst, uint32_t capacity, uint32_t *count);
+/* The skin of loaded mesh `mesh` (NXH_LOAD_SKINS): *cornerCount = 3 x its triangles — 0 for a mesh without one — and *jointCount; dst (may
+ * be NULL) receives up to `capacity` nx_skin_corner records (nexus_pod.h), corner 3 i + v = vertex v of triangle i. */
+int nxh_loaded_skin(const nxh_loaded_scene *s, uint32_t mesh, nx_skin_corner *dst, uint32_t capacity, uint32_t *cornerCount, uint32_t *jointCount);
+uint32_t nxh_loaded_animation_count(const nxh_loaded_scene *s);
 uint32_t nxh_loaded_warning_count(const nxh_loaded_scene *s);
 const char *nxh_loaded_warning(const nxh_loaded_scene *s, uint32_t index);
 /* IMGLoader::LoadIMG (Assets/IMGLoader.cpp:17-41: stbi_load with 4 channels) for PNG data: RGBA8, row 0 first.
@@ -152,6 +160,16 @@ int nxs_scene_set_metal_rough(nxs_scene *s, int on);
  * AssetManager's table — *count records, 0 while no material has a mode; dst (may be NULL) receives up to `capacity` of them. */
 int nxs_scene_set_material_alpha_modes(nxs_scene *s, int on);
 int nxs_scene_material_alphas(const nxs_scene *s, nx_material_alpha *dst, uint32_t capacity, uint32_t *count);
+/* Extension (skinned meshes), off by default: files loaded from here on keep their skins, joint animations and node tree as
+ * NXH_LOAD_SKINS reads them (Scene::SetSkins).  nxs_scene_mesh_joint_count: joints of mesh `meshId`'s skin, 0 for a mesh without one.
+ * nxs_scene_joint_palette — Scene::JointPalette: the pose of animation `animationIdx` (-1: the rest pose) at time t, evaluated on the host
+ * in binary64 and rounded once: *jointCount x 12 floats into dst (capacity in joints), row j the row-major 3 x 4 matrix
+ * inverse(meshNodeWorld) x jointWorld[j] x inverseBind[j] — what nxhip_pose_blas and nxs_pathtracer_pose_mesh take. */
+int nxs_scene_set_skins(nxs_scene *s, int on);
+uint32_t nxs_scene_mesh_count(const nxs_scene *s);
+uint32_t nxs_scene_animation_count(const nxs_scene *s);
+uint32_t nxs_scene_mesh_joint_count(const nxs_scene *s, uint32_t meshId);
+int nxs_scene_joint_palette(const nxs_scene *s, uint32_t meshId, int32_t animationIdx, double t, float *dst, uint32_t capacity, uint32_t *jointCount);
 int nxs_scene_set_camera(nxs_scene *s, const float pos[3], const float forward[3], float horizontalFovDeg, float focusDist,
                          float defocusAngleDeg);
 int nxs_scene_set_render_settings(nxs_scene *s, const nx_render_settings *settings);
@@ -205,6 +223,10 @@ int nxs_pathtracer_set_feature_buffers(nxs_pathtracer *p, int on);
 /* PathTracer::SetDeviceBlasBuild (extension, off by default): meshes added to `s` from now on get their BVH8 from the device
  * builder (nxhip_build_blas) instead of the host's; switch it off, or destroy the scene, before `p` goes away. */
 int nxs_pathtracer_set_device_blas_build(nxs_pathtracer *p, nxs_scene *s, int enable);
+/* Extension (skinned meshes) — PathTracer::PoseMesh for mesh `meshId`: an immediate call, made before nxs_scene_update.  The skin goes to
+ * the device on first use, the device blends the vertices and refits the mesh's BLAS (nxhip_pose_blas), the posed root box comes back
+ * for the instances' bounds; nxs_scene_update and nxs_pathtracer_update_device_scene then proceed as for a deformed mesh. */
+int nxs_pathtracer_pose_mesh(nxs_pathtracer *p, nxs_scene *s, uint32_t meshId, const float *palette, uint32_t jointCount);
 int nxs_pathtracer_update_device_scene(nxs_pathtracer *p, nxs_scene *s);
 int nxs_pathtracer_render(nxs_pathtracer *p, nxs_scene *s);
 int nxs_pathtracer_reset_frame_number(nxs_pathtracer *p);

@@ -131,6 +131,14 @@ typedef struct nx_material_alpha {
 } nx_material_alpha;
 NX_STATIC_ASSERT(sizeof(nx_material_alpha) == 8, "nx_material_alpha must be 8 bytes");
 
+/* Extension: the skin of one triangle corner (nxhip_set_blas_skin; the blending rule is stated in full in include/nexus_hip.h): up to four
+ * joints and their weights, as glTF's JOINTS_0 / WEIGHTS_0 of the corner's vertex.  Corner 3 i + v is vertex v of triangle i. */
+typedef struct nx_skin_corner {
+    uint16_t joint[4];
+    float weight[4];
+} nx_skin_corner;
+NX_STATIC_ASSERT(sizeof(nx_skin_corner) == 24 && offsetof(nx_skin_corner, weight) == 8, "nx_skin_corner must be 24 bytes");
+
 /* Extension: one homogeneous participating medium ("fog") per context, confined to a world-space axis-aligned box (nxhip_set_medium; the
  * rule is stated in full in include/nexus_hip.h). */
 typedef struct nx_medium {

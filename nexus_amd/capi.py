@@ -43,6 +43,7 @@ HIP_SYMBOLS = [
     "nxhip_set_queue_budget", "nxhip_get_queue_budget", "nxhip_queue_budget_from_text", "nxhip_debug_last_graph",
     "nxhip_read_material_queue_sizes", "nxhip_material_inputs_batch",
     "nxhip_set_material_alpha",
+    "nxhip_set_blas_skin", "nxhip_pose_blas", "nxhip_read_blas_triangles", "nxhip_read_blas_bounds",
 ]
 HOST_SYMBOLS = [
     "nxh_bvh8_build", "nxh_tlas_build", "nxh_tlas_refit", "nxh_bvh8_refit", "nxh_bvh8_node_count", "nxh_bvh8_prim_count", "nxh_bvh8_nodes",
@@ -70,6 +71,8 @@ HOST_SYMBOLS = [
     "nxs_scene_set_medium_density", "nxs_scene_clear_medium_density", "nxs_scene_medium_density", "nxh_decode_npy_grid",
     "nxh_load_scene_file_ex", "nxs_scene_set_metal_rough",
     "nxh_loaded_material_alpha", "nxs_scene_set_material_alpha_modes", "nxs_scene_material_alphas",
+    "nxh_loaded_skin", "nxh_loaded_animation_count", "nxs_scene_set_skins", "nxs_scene_mesh_count", "nxs_scene_animation_count",
+    "nxs_scene_mesh_joint_count", "nxs_scene_joint_palette", "nxs_pathtracer_pose_mesh",
 ]
 
 
@@ -112,6 +115,7 @@ def abi_words():
         pod.MAT_DT.itemsize, off(pod.MAT_DT, "emissive"), off(pod.MAT_DT, "type"), pod.LIGHT_DT.itemsize, off(pod.LIGHT_DT, "type"),
         pod.ALIGHT_DT.itemsize, off(pod.ALIGHT_DT, "direction"), off(pod.ALIGHT_DT, "colour"), off(pod.ALIGHT_DT, "innerConeAngle"), off(pod.ALIGHT_DT, "type"),
         pod.DETAIL_DT.itemsize, off(pod.DETAIL_DT, "normalScale"), pod.MEDIUM_DT.itemsize, pod.ALPHA_DT.itemsize, off(pod.ALPHA_DT, "cutoff"),
+        pod.SKIN_CORNER_DT.itemsize, off(pod.SKIN_CORNER_DT, "weight"),
         pod.CAM_DT.itemsize, off(pod.CAM_DT, "resolution"), pod.SETTINGS_DT.itemsize, off(pod.SETTINGS_DT, "backgroundColor"),
         pod.RAY_DT.itemsize, pod.HIT_DT.itemsize, pod.BSDF_QUERY_DT.itemsize, pod.BSDF_RESULT_DT.itemsize, off(pod.BSDF_RESULT_DT, "rngOut"),
         C.sizeof(QueueSizes), C.sizeof(TraceStats), TraceStats.cycles.offset, C.sizeof(KernelTimes), len(KERNEL_CLASSES),
@@ -213,6 +217,10 @@ def lib():
     L.nxhip_read_tlas.argtypes = [vp, vp, u32, vp, u32]
     L.nxhip_update_blas.argtypes = [vp, i32, vp, u32]
     L.nxhip_update_blas_device.argtypes = [vp, i32, vp, u32]
+    L.nxhip_set_blas_skin.argtypes = [vp, i32, vp, u32, u32]
+    L.nxhip_pose_blas.argtypes = [vp, i32, vp, u32]
+    L.nxhip_read_blas_triangles.argtypes = [vp, i32, vp, u32]
+    L.nxhip_read_blas_bounds.argtypes = [vp, i32, vp, vp]
     L.nxhip_tile_pixel_map.argtypes = [u32, u32, C.c_int, C.c_int, u32, C.c_int, vp, C.POINTER(u32)]
     L.nxhip_mgpu_unique_id.argtypes = [vp]
     L.nxhip_mgpu_init.argtypes = [vp, C.c_int, C.c_int, vp, u32]
@@ -481,6 +489,41 @@ def load_scene_material_alpha(path, alpha_modes=True):
     finally:
         L.nxh_loaded_scene_free(h)
     return out
+
+
+LOAD_SKINS = 4  # nxh_load_scene_file_ex: NXH_LOAD_SKINS
+
+
+def load_scene_skins(path, skins=True):
+    """the skins of a .glb as the C++ reader makes them (LoadOptions::skins): per loaded mesh its pod.SKIN_CORNER_DT records (None: not
+    skinned) and joint count, then the animation count and the reader's warnings -> (corner arrays, joint counts, animations, warnings)"""
+    L = lib()
+    h = C.c_void_p()
+    if L.nxh_load_scene_file_ex(str(path).encode(), LOAD_SKINS if skins else 0, C.byref(h)) != 0:
+        raise NexusError("nxh_load_scene_file_ex: " + L.nxs_last_error().decode())
+    try:
+        L.nxh_loaded_skin.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        L.nxh_loaded_animation_count.argtypes = [C.c_void_p]
+        L.nxh_loaded_animation_count.restype = C.c_uint32
+        corners, joints = [], []
+        for m in range(L.nxh_loaded_mesh_count(h)):
+            n, j = C.c_uint32(0), C.c_uint32(0)
+            if L.nxh_loaded_skin(h, m, None, 0, C.byref(n), C.byref(j)) != 0:
+                raise NexusError(L.nxs_last_error().decode())
+            out = np.zeros(n.value, dtype=pod.SKIN_CORNER_DT) if n.value else None
+            if n.value and L.nxh_loaded_skin(h, m, _ptr(out), n.value, C.byref(n), C.byref(j)) != 0:
+                raise NexusError(L.nxs_last_error().decode())
+            corners.append(out)
+            joints.append(int(j.value))
+        L.nxh_loaded_warning_count.argtypes = [C.c_void_p]
+        L.nxh_loaded_warning_count.restype = C.c_uint32
+        L.nxh_loaded_warning.argtypes = [C.c_void_p, C.c_uint32]
+        L.nxh_loaded_warning.restype = C.c_char_p
+        warnings = [L.nxh_loaded_warning(h, i).decode() for i in range(L.nxh_loaded_warning_count(h))]
+        animations = int(L.nxh_loaded_animation_count(h))
+    finally:
+        L.nxh_loaded_scene_free(h)
+    return corners, joints, animations, warnings
 
 
 def load_scene_analytic_lights(path):
@@ -983,6 +1026,34 @@ class Context:
     def update_blas_device(self, blas_id, ptr, count):
         """update_blas from `count` 96-byte triangle records in device memory (e.g. a torch tensor's data_ptr()); asynchronous"""
         check(self.L.nxhip_update_blas_device(self.h, int(blas_id), C.c_void_p(int(ptr)) if ptr else None, int(count)), "nxhip_update_blas_device")
+
+    def set_blas_skin(self, blas_id, corners, joint_count):
+        """the skin of a BLAS (3 nx_skin_corner records per triangle; None removes it): its current triangles become the bind pose
+        every pose_blas starts from"""
+        if corners is None:
+            check(self.L.nxhip_set_blas_skin(self.h, int(blas_id), None, 0, 0), "nxhip_set_blas_skin")
+            return
+        s = np.ascontiguousarray(corners, dtype=pod.SKIN_CORNER_DT)
+        check(self.L.nxhip_set_blas_skin(self.h, int(blas_id), _ptr(s), len(s), int(joint_count)), "nxhip_set_blas_skin")
+
+    def pose_blas(self, blas_id, joint_matrices):
+        """pose a skinned BLAS: (jointCount, 12) row-major 3 x 4 object-space matrices; triangles, intersection stream and nodes are
+        redone on the device, instances and the TLAS follow as after update_blas"""
+        m = np.ascontiguousarray(joint_matrices, dtype=np.float32)
+        m = m.reshape(-1, 12)
+        check(self.L.nxhip_pose_blas(self.h, int(blas_id), _ptr(m), len(m)), "nxhip_pose_blas")
+
+    def read_blas_triangles(self, blas_id, tri_count):
+        """the BLAS's current 96-byte triangles"""
+        t = np.zeros(int(tri_count), dtype=pod.TRI_DT)
+        check(self.L.nxhip_read_blas_triangles(self.h, int(blas_id), _ptr(t), len(t)), "nxhip_read_blas_triangles")
+        return t
+
+    def read_blas_bounds(self, blas_id):
+        """(lo, hi) of the box the BLAS's root node encodes after the last build, refit or pose"""
+        lo, hi = np.zeros(3, np.float32), np.zeros(3, np.float32)
+        check(self.L.nxhip_read_blas_bounds(self.h, int(blas_id), _ptr(lo), _ptr(hi)), "nxhip_read_blas_bounds")
+        return lo, hi
 
     def read_tlas(self, node_count, instance_count):
         nodes = np.zeros(node_count, dtype=pod.NODE_DT)
@@ -1646,6 +1717,38 @@ class Scene:
         self.L.nxs_scene_set_material_alpha_modes.argtypes = [C.c_void_p, C.c_int]
         _scheck(self.L.nxs_scene_set_material_alpha_modes(self.h, 1 if on else 0), "nxs_scene_set_material_alpha_modes")
 
+    def set_skins(self, on=True):
+        """Scene::SetSkins: the files loaded from here on keep their glTF skins, joint animations and node tree (off by default)"""
+        self.L.nxs_scene_set_skins.argtypes = [C.c_void_p, C.c_int]
+        _scheck(self.L.nxs_scene_set_skins(self.h, 1 if on else 0), "nxs_scene_set_skins")
+
+    def mesh_count(self):
+        self.L.nxs_scene_mesh_count.argtypes = [C.c_void_p]
+        self.L.nxs_scene_mesh_count.restype = C.c_uint32
+        return int(self.L.nxs_scene_mesh_count(self.h))
+
+    def animation_count(self):
+        self.L.nxs_scene_animation_count.argtypes = [C.c_void_p]
+        self.L.nxs_scene_animation_count.restype = C.c_uint32
+        return int(self.L.nxs_scene_animation_count(self.h))
+
+    def mesh_joint_count(self, mesh_id):
+        """joints of the mesh's skin; 0: the mesh is not skinned"""
+        self.L.nxs_scene_mesh_joint_count.argtypes = [C.c_void_p, C.c_uint32]
+        self.L.nxs_scene_mesh_joint_count.restype = C.c_uint32
+        return int(self.L.nxs_scene_mesh_joint_count(self.h, int(mesh_id)))
+
+    def joint_palette(self, mesh_id, animation=None, t=0.0):
+        """Scene::JointPalette: (joints, 12) float32 — the pose of animation `animation` (None: the rest pose) at time t, evaluated in binary64
+        on the host; the twin of nexus_amd.animation.joint_palette"""
+        self.L.nxs_scene_joint_palette.argtypes = [C.c_void_p, C.c_uint32, C.c_int32, C.c_double, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
+        n = C.c_uint32(0)
+        a = -1 if animation is None else int(animation)
+        _scheck(self.L.nxs_scene_joint_palette(self.h, int(mesh_id), a, float(t), None, 0, C.byref(n)), "nxs_scene_joint_palette")
+        out = np.zeros((n.value, 12), np.float32)
+        _scheck(self.L.nxs_scene_joint_palette(self.h, int(mesh_id), a, float(t), _ptr(out), n.value, C.byref(n)), "nxs_scene_joint_palette")
+        return out
+
     def material_alphas(self):
         """AssetManager::GetMaterialAlphas: pod.ALPHA_DT records, one per material (empty: no material has a mode)"""
         self.L.nxs_scene_material_alphas.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
@@ -1955,6 +2058,12 @@ class PathTracer:
         """PathTracer::SetDeviceBlasBuild: meshes added to `scene` from now on are built into BVH8s on the GPU"""
         self.L.nxs_pathtracer_set_device_blas_build.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         _scheck(self.L.nxs_pathtracer_set_device_blas_build(self.h, scene.h, 1 if enable else 0), "nxs_pathtracer_set_device_blas_build")
+
+    def pose_mesh(self, scene, mesh_id, palette):
+        """PathTracer::PoseMesh: pose a skinned mesh on the device with a (joints, 12) palette — before scene.update()"""
+        m = np.ascontiguousarray(palette, dtype=np.float32).reshape(-1, 12)
+        self.L.nxs_pathtracer_pose_mesh.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
+        _scheck(self.L.nxs_pathtracer_pose_mesh(self.h, scene.h, int(mesh_id), _ptr(m), len(m)), "nxs_pathtracer_pose_mesh")
 
     def update_device_scene(self, scene):
         _scheck(self.L.nxs_pathtracer_update_device_scene(self.h, scene.h), "nxs_pathtracer_update_device_scene")

@@ -137,11 +137,12 @@ int nxh_load_scene_file_ex(const char* file, uint32_t flags, nxh_loaded_scene** 
 {
     return guarded([&] {
         if (!file || !out) throw std::runtime_error("nxh_load_scene_file_ex: null argument");
-        if (flags & ~(uint32_t)(NXH_LOAD_METAL_ROUGH | NXH_LOAD_ALPHA_MODES)) throw std::runtime_error("nxh_load_scene_file_ex: unknown flag");
+        if (flags & ~(uint32_t)(NXH_LOAD_METAL_ROUGH | NXH_LOAD_ALPHA_MODES | NXH_LOAD_SKINS)) throw std::runtime_error("nxh_load_scene_file_ex: unknown flag");
         std::unique_ptr<nxh_loaded_scene> p(new nxh_loaded_scene);
         LoadOptions options;
         options.metalRough = (flags & NXH_LOAD_METAL_ROUGH) != 0;
         options.alphaModes = (flags & NXH_LOAD_ALPHA_MODES) != 0;
+        options.skins = (flags & NXH_LOAD_SKINS) != 0;
         p->ls = OBJLoader::Parse(file, options);
         *out = p.release();
     });
@@ -258,6 +259,17 @@ int nxh_loaded_analytic_lights(const nxh_loaded_scene* s, nx_analytic_light* dst
         for (size_t i = 0; i < s->ls.analyticLights.size(); i++) dst[i] = s->ls.analyticLights[i];
     });
 }
+int nxh_loaded_skin(const nxh_loaded_scene* s, uint32_t mesh, nx_skin_corner* dst, uint32_t capacity, uint32_t* cornerCount, uint32_t* jointCount)
+{
+    return guarded([&] {
+        if (!s || !cornerCount || !jointCount || mesh >= s->ls.meshes.size()) throw std::runtime_error("nxh_loaded_skin: null argument, or no such mesh");
+        const Skin* skin = mesh < s->ls.skins.size() ? s->ls.skins[mesh].get() : nullptr;
+        *cornerCount = skin ? static_cast<uint32_t>(skin->corners.size()) : 0u;
+        *jointCount = skin ? static_cast<uint32_t>(skin->joints.size()) : 0u;
+        for (size_t i = 0; skin && dst && i < skin->corners.size() && i < capacity; i++) dst[i] = skin->corners[i];
+    });
+}
+uint32_t nxh_loaded_animation_count(const nxh_loaded_scene* s) { return static_cast<uint32_t>(s->ls.animations.size()); }
 uint32_t nxh_loaded_warning_count(const nxh_loaded_scene* s) { return static_cast<uint32_t>(s->ls.warnings.size()); }
 const char* nxh_loaded_warning(const nxh_loaded_scene* s, uint32_t index) { return index < s->ls.warnings.size() ? s->ls.warnings[index].c_str() : ""; }
 
@@ -346,6 +358,30 @@ int nxs_scene_material_alphas(const nxs_scene* s, nx_material_alpha* dst, uint32
         const std::vector<nx_material_alpha> a = s->scene.GetAssetManager().GetMaterialAlphas();
         *count = static_cast<uint32_t>(a.size());
         for (size_t i = 0; dst && i < a.size() && i < capacity; i++) dst[i] = a[i];
+    });
+}
+
+int nxs_scene_set_skins(nxs_scene* s, int on)
+{
+    return guarded([&] { s->scene.SetSkins(on != 0); });
+}
+uint32_t nxs_scene_mesh_count(const nxs_scene* s) { return static_cast<uint32_t>(const_cast<nxs_scene*>(s)->scene.GetAssetManager().GetMeshes().size()); }
+uint32_t nxs_scene_animation_count(const nxs_scene* s) { return static_cast<uint32_t>(s->scene.GetAnimations().size()); }
+uint32_t nxs_scene_mesh_joint_count(const nxs_scene* s, uint32_t meshId)
+{
+    const std::vector<Mesh>& meshes = const_cast<nxs_scene*>(s)->scene.GetAssetManager().GetMeshes();
+    return meshId < meshes.size() && meshes[meshId].skin ? static_cast<uint32_t>(meshes[meshId].skin->joints.size()) : 0u;
+}
+int nxs_scene_joint_palette(const nxs_scene* s, uint32_t meshId, int32_t animationIdx, double t, float* dst, uint32_t capacity, uint32_t* jointCount)
+{
+    return guarded([&] {
+        if (!s || !jointCount) throw std::runtime_error("nxs_scene_joint_palette: null argument");
+        const std::vector<float> p = s->scene.JointPalette(meshId, animationIdx, t);
+        *jointCount = static_cast<uint32_t>(p.size() / 12);
+        if (dst) {
+            if (capacity < *jointCount) throw std::runtime_error("nxs_scene_joint_palette: destination too small");
+            std::memcpy(dst, p.data(), p.size() * sizeof(float));
+        }
     });
 }
 
@@ -490,6 +526,15 @@ int nxs_pathtracer_set_feature_buffers(nxs_pathtracer* p, int on) { return guard
 int nxs_pathtracer_set_device_blas_build(nxs_pathtracer* p, nxs_scene* s, int enable)
 {
     return guarded([&] { p->pt.SetDeviceBlasBuild(s->scene, enable != 0); });
+}
+int nxs_pathtracer_pose_mesh(nxs_pathtracer* p, nxs_scene* s, uint32_t meshId, const float* palette, uint32_t jointCount)
+{
+    return guarded([&] {
+        if (!p || !s || !palette) throw std::runtime_error("nxs_pathtracer_pose_mesh: null argument");
+        const std::vector<Mesh>& meshes = s->scene.GetAssetManager().GetMeshes();
+        if (meshId >= meshes.size()) throw std::runtime_error("nxs_pathtracer_pose_mesh: no such mesh");
+        p->pt.PoseMesh(s->scene, meshes[meshId].bvhId, std::vector<float>(palette, palette + static_cast<size_t>(jointCount) * 12));
+    });
 }
 int nxs_pathtracer_update_device_scene(nxs_pathtracer* p, nxs_scene* s)
 {

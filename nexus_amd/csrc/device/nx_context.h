@@ -70,6 +70,10 @@ struct BlasHost {
     DevBuf refitOrder, refitLevelStart, refitBoxes;
     std::vector<uint32_t> refitLevels;  // host copy of refitLevelStart; empty: no plan yet
     bool refreshPending = false;        // updated since the last refresh_updated_blas: its instances and the TLAS still hold the old root
+    // the skin of nxhip_set_blas_skin (nx_skin.hip pose_kernel): the triangles as they were when the skin was set, one SkinTri per
+    // triangle, and the palette of the last nxhip_pose_blas (48 bytes per joint); skinJoints == 0: no skin
+    DevBuf bindTris, skinTris, palette;
+    uint32_t skinJoints = 0;
 };
 
 struct TextureHost {

@@ -76,6 +76,16 @@ struct BlasDev {
     uint32_t pad_[2];
 };
 static_assert(sizeof(BlasDev) == 48, "BlasDev layout");
+// The skin of one triangle as the pose kernel reads it (nx_skin.hip): the three nx_skin_corner records of nxhip_set_blas_skin repacked
+// by the host into five 16-byte chunks — the weights of corner v in chunk v, the twelve joint indices behind them — so that every
+// load is aligned whatever the triangle's index (three 24-byte corners are 72 bytes: every other triangle would start mid-chunk).
+struct __attribute__((aligned(16))) SkinTri {
+    float weight[3][4];
+    uint16_t joint[3][4];
+    uint32_t pad_[2];
+};
+static_assert(sizeof(SkinTri) == 80 && offsetof(SkinTri, joint) == 48, "SkinTri layout");
+constexpr uint32_t kSkinLdsJoints = 1024;  // palettes up to this many joints (48 KiB) are staged in the LDS
 inline __device__ const NX_G nx_triangle* shade_tri(const NX_G nx_triangle* tris, uint32_t k) { return (const NX_G nx_triangle*)((const NX_G char*)tris + (size_t)k * (size_t)kShadeTriStride); }
 
 // Traversal record of one TLAS leaf, stored in TLAS *leaf order* (entry k belongs to tlasInstIdx[k]) so that entering an
@@ -563,6 +573,7 @@ constexpr uint64_t layout_stamp()
         (uint64_t)kNodeStride, (uint64_t)kTriStride, (uint64_t)kShadeTriStride, (uint64_t)kQueueShards, (uint64_t)kQueueShardSlack, (uint64_t)kRegionStride, (uint64_t)kMaxBounceSlots,
         (uint64_t)kEnvGuide, (uint64_t)kHitCodeShift, sizeof(TraceRays), offsetof(TraceQueue, hit), (uint64_t)kMaterialTypeOffset, sizeof(nx_material), sizeof(nx_bvh_instance), sizeof(nx_triangle), sizeof(nx_light), sizeof(nx_camera),
         offsetof(RegionCounters, materialSizeMetal), offsetof(RegionCounters, scanTileMetal), offsetof(RegionCounters, scanTicketMetal), offsetof(DeviceState, materialMetal), (uint64_t)kHitCodeMetalRough, (uint64_t)kScanMetalBit,
+        sizeof(SkinTri), offsetof(SkinTri, joint), (uint64_t)kSkinLdsJoints,
     };
     for (uint64_t v : w) h = layout_mix(h, v);
     return h;

@@ -64,6 +64,7 @@ const void* inst_code_metal_kernel_ptr();  // (... of a material table with an N
 const void* instance_transform_kernel_ptr();
 const void* tlas_refit_kernel_ptr();
 const void* blas_refit_kernel_ptr();
+const void* pose_kernel_ptr(bool lds);  // nx_skin.hip: the palette from the LDS, or from global memory
 uint64_t layout_stamp_trace();
 uint64_t layout_stamp_wavefront();
 uint64_t layout_stamp_wavefront_detail();
@@ -71,6 +72,7 @@ uint64_t layout_stamp_wavefront_solid();
 uint64_t layout_stamp_wavefront_metal();
 uint64_t layout_stamp_medium();
 uint64_t layout_stamp_refit();
+uint64_t layout_stamp_skin();
 uint64_t layout_stamp_lbvh();
 uint64_t layout_stamp_multigpu();
 uint64_t layout_stamp_entry();
@@ -196,6 +198,8 @@ inline Kernel<State, nx_bvh_instance*, InstTrav*, const U32*, const U32*, const 
 inline Kernel<nx_bvh8_node*, const U32*, const nx_bvh_instance*, const U32*, const U32*, U32, void*, const void*> tlas_refit() { return {tlas_refit_kernel_ptr()}; }
 // (nodes, triIdx, tris, order, levelStart, firstLevel, levelCount, nodeBox)
 inline Kernel<uint4*, const U32*, const nx_triangle*, const U32*, const U32*, U32, U32, void*> blas_refit() { return {blas_refit_kernel_ptr()}; }
+// (bind, skin, palette, jointCount, primIdx, n, tris, shadeTris, isect); lds: launched with 48 B of dynamic LDS per joint
+inline Kernel<const uint4*, const uint4*, const float4*, U32, const U32*, U32, uint4*, uint4*, float4*> pose(bool lds) { return {pose_kernel_ptr(lds)}; }
 }  // namespace kernels
 
 constexpr size_t arg_end(size_t at, size_t size, size_t align) { return (at + align - 1) / align * align + size; }
@@ -242,6 +246,12 @@ template <class... A> hipError_t launch_untimed(Kernel<A...> k, dim3 grid, dim3 
 {
     void* params[] = {(void*)&args...};
     return hipLaunchKernel(k.fn, grid, block, params, 0, stream);
+}
+// ... of a kernel that sizes an `extern __shared__` array by the launch (ldsBytes <= 64 KiB: no attribute needed)
+template <class... A> hipError_t launch_untimed_lds(Kernel<A...> k, dim3 grid, dim3 block, size_t ldsBytes, hipStream_t stream, std::common_type_t<A>... args)
+{
+    void* params[] = {(void*)&args...};
+    return hipLaunchKernel(k.fn, grid, block, params, ldsBytes, stream);
 }
 
 // ---- what the host units share ---------------------------------------------------------------------------

@@ -829,6 +829,32 @@ static int ensure_blas_refit_plan(nxhip_ctx* c, BlasHost& b)
 // in at most four strides, and a launch (~5 us of latency between dependent kernels) costs more than the stride it would save.
 constexpr uint32_t kBlasRefitWide = 1024, kBlasRefitBlock = 256;
 
+// What follows new triangles in b.tris and b.isect, whoever wrote them (update_blas: a copy and isect_kernel; nxhip_pose_blas: the
+// pose kernel): the nodes refitted level by level on the context's stream, and everything that embeds the BLAS marked stale.
+static int refit_blas_nodes(nxhip_ctx* c, BlasHost& b)
+{
+    const uint32_t levels = (uint32_t)b.refitLevels.size() - 1u;
+    auto width = [&](uint32_t l) { return b.refitLevels[l + 1] - b.refitLevels[l]; };
+    for (uint32_t first = 0; first < levels;) {
+        uint32_t count = 1;
+        unsigned grid = 1;
+        if (width(first) > kBlasRefitWide) {
+            grid = std::min<unsigned>((width(first) + kBlasRefitBlock - 1u) / kBlasRefitBlock, (unsigned)(8 * std::max(1, c->numCUs)));
+        } else {
+            while (first + count < levels && width(first + count) <= kBlasRefitWide) count++;  // the run of narrow levels: one workgroup
+        }
+        NX_HIP(launch_untimed(kernels::blas_refit(), grid, kBlasRefitBlock, c->stream, b.nodes.as<uint4>(), b.triIdx.as<uint32_t>(), b.tris.as<nx_triangle>(),
+                              b.refitOrder.as<uint32_t>(), b.refitLevelStart.as<uint32_t>(), first, count, b.refitBoxes.p));
+        first += count;
+    }
+    b.rootKnown = false;  // (read again by whoever next needs the host copy: refresh_inst_trav)
+    b.refreshPending = true;
+    entry_inputs_changed(c);  // (the BLAS's nodes and triangle records; the deferred refresh bumps again for what follows its root)
+    c->blasRefreshPending = true;
+    c->lightTableDirty = true;
+    return NXHIP_OK;
+}
+
 static int update_blas(nxhip_ctx* c, int32_t blasId, const void* tris, uint32_t triCount, bool fromDevice, const char* who)
 {
     NX_CHECK_CTX(c);
@@ -845,27 +871,7 @@ static int update_blas(nxhip_ctx* c, int32_t blasId, const void* tris, uint32_t 
     if (kShadeTriStride != (int)sizeof(nx_triangle))
         NX_HIP(hipMemcpy2DAsync(b.shadeTris.p, kShadeTriStride, b.tris.p, sizeof(nx_triangle), sizeof(nx_triangle), triCount, hipMemcpyDeviceToDevice, c->stream));
     NX_TRY(lbvh_write_isect(c, b.tris.as<nx_triangle>(), b.triIdx.as<uint32_t>(), triCount, b.isect.as<float4>()));
-    {
-        const uint32_t levels = (uint32_t)b.refitLevels.size() - 1u;
-        auto width = [&](uint32_t l) { return b.refitLevels[l + 1] - b.refitLevels[l]; };
-        for (uint32_t first = 0; first < levels;) {
-            uint32_t count = 1;
-            unsigned grid = 1;
-            if (width(first) > kBlasRefitWide) {
-                grid = std::min<unsigned>((width(first) + kBlasRefitBlock - 1u) / kBlasRefitBlock, (unsigned)(8 * std::max(1, c->numCUs)));
-            } else {
-                while (first + count < levels && width(first + count) <= kBlasRefitWide) count++;  // the run of narrow levels: one workgroup
-            }
-            NX_HIP(launch_untimed(kernels::blas_refit(), grid, kBlasRefitBlock, c->stream, b.nodes.as<uint4>(), b.triIdx.as<uint32_t>(), b.tris.as<nx_triangle>(),
-                                  b.refitOrder.as<uint32_t>(), b.refitLevelStart.as<uint32_t>(), first, count, b.refitBoxes.p));
-            first += count;
-        }
-    }
-    b.rootKnown = false;  // (read again by whoever next needs the host copy: refresh_inst_trav)
-    b.refreshPending = true;
-    entry_inputs_changed(c);  // (the BLAS's nodes and triangle records; the deferred refresh bumps again for what follows its root)
-    c->blasRefreshPending = true;
-    c->lightTableDirty = true;
+    NX_TRY(refit_blas_nodes(c, b));
     // a pageable host array: see nxhip_set_instance_transforms
     if (!fromDevice) NX_HIP(hipStreamSynchronize(c->stream));
     return NXHIP_OK;
@@ -880,6 +886,113 @@ int nxhip_update_blas_device(nxhip_ctx* c, int32_t blasId, const void* trisDevic
 try {
     return update_blas(c, blasId, trisDevice, triCount, true, "nxhip_update_blas_device");
 } NX_CATCH("nxhip_update_blas_device")
+
+// ---- skinned meshes (nx_skin.hip) ------------------------------------------------------------------------
+
+int nxhip_set_blas_skin(nxhip_ctx* c, int32_t blasId, const nx_skin_corner* corners, uint32_t cornerCount, uint32_t jointCount)
+try {
+    NX_CHECK_CTX(c);
+    if (blasId < 0 || (size_t)blasId >= c->blas.size()) return fail_invalid("nxhip_set_blas_skin: no such BLAS");
+    BlasHost& b = c->blas[(size_t)blasId];
+    NX_HIP(hipSetDevice(c->device));
+    if (!corners) {  // the skin goes; triangles and nodes stay as they are
+        NX_SYNC_ALL(c);  // (a pose in flight still reads the buffers)
+        b.bindTris.release();
+        b.skinTris.release();
+        b.palette.release();
+        b.skinJoints = 0;
+        return NXHIP_OK;
+    }
+    if ((uint64_t)cornerCount != 3ull * b.triCount) return fail_invalid("nxhip_set_blas_skin: the corner count is not 3 x the BLAS's triangle count");
+    if (jointCount == 0 || jointCount > 65536u) return fail_invalid("nxhip_set_blas_skin: the joint count must be 1 .. 65536");
+    // everything the kernel will index with, and the weights it will use, before anything is allocated
+    std::vector<SkinTri> packed(b.triCount);
+    std::memset(packed.data(), 0, packed.size() * sizeof(SkinTri));
+    for (uint32_t i = 0; i < cornerCount; i++) {
+        const nx_skin_corner& s = corners[i];
+        double sum = 0.0;
+        for (int k = 0; k < 4; k++) {
+            if (!std::isfinite(s.weight[k]) || s.weight[k] < 0.0f) return fail_invalid("nxhip_set_blas_skin: corner " + std::to_string(i) + " has a weight that is negative or not finite");
+            if (s.weight[k] != 0.0f && s.joint[k] >= jointCount) return fail_invalid("nxhip_set_blas_skin: corner " + std::to_string(i) + " names joint " + std::to_string(s.joint[k]) + " of " + std::to_string(jointCount));
+            sum += (double)s.weight[k];
+        }
+        if (!(sum > 0.0)) return fail_invalid("nxhip_set_blas_skin: the weights of corner " + std::to_string(i) + " sum to 0");
+        SkinTri& t = packed[i / 3];
+        for (int k = 0; k < 4; k++) {
+            t.weight[i % 3][k] = (float)((double)s.weight[k] / sum);  // sum 1 in binary64, rounded once
+            t.joint[i % 3][k] = s.weight[k] != 0.0f ? s.joint[k] : (uint16_t)0;  // (read unconditionally by the kernel)
+        }
+    }
+    DevBuf bind, skin, palette;
+    const size_t triBytes = (size_t)b.triCount * sizeof(nx_triangle), skinBytes = packed.size() * sizeof(SkinTri);
+    if (!bind.alloc(triBytes) || !skin.alloc(skinBytes) || !palette.alloc((size_t)jointCount * 48)) return NXHIP_ERR_HIP;
+    // the bind copy: the triangles as they are behind everything issued so far (an update or a pose on the stream included)
+    NX_HIP(hipMemcpyAsync(bind.p, b.tris.p, triBytes, hipMemcpyDeviceToDevice, c->stream));
+    NX_HIP(hipMemcpyAsync(skin.p, packed.data(), skinBytes, hipMemcpyHostToDevice, c->stream));
+    NX_HIP(hipStreamSynchronize(c->stream));  // (`packed` is pageable; and a previous skin's buffers are read by this stream only)
+    b.bindTris = std::move(bind);
+    b.skinTris = std::move(skin);
+    b.palette = std::move(palette);
+    b.skinJoints = jointCount;
+    return NXHIP_OK;
+} NX_CATCH("nxhip_set_blas_skin")
+
+int nxhip_pose_blas(nxhip_ctx* c, int32_t blasId, const float* jointMatrices, uint32_t jointCount)
+try {
+    NX_CHECK_CTX(c);
+    if (blasId < 0 || (size_t)blasId >= c->blas.size()) return fail_invalid("nxhip_pose_blas: no such BLAS");
+    BlasHost& b = c->blas[(size_t)blasId];
+    if (b.skinJoints == 0) return fail_invalid("nxhip_pose_blas: the BLAS has no skin (nxhip_set_blas_skin)");
+    if (!jointMatrices) return fail_invalid("nxhip_pose_blas: null matrices");
+    if (jointCount != b.skinJoints) return fail_invalid("nxhip_pose_blas: the joint count differs from the skin's");
+    for (size_t i = 0; i < (size_t)jointCount * 12; i++)
+        if (!std::isfinite(jointMatrices[i])) return fail_invalid("nxhip_pose_blas: a matrix entry is not finite");
+    NX_HIP(hipSetDevice(c->device));
+    NX_TRY(ensure_blas_refit_plan(c, b));
+    if (slot_count(c) > 1) NX_SYNC_ALL(c);  // passes on the other slots' streams still traverse the old shape
+    // stream order does the rest, as in update_blas: the palette, the pose, the refit
+    NX_HIP(hipMemcpyAsync(b.palette.p, jointMatrices, (size_t)jointCount * 48, hipMemcpyHostToDevice, c->stream));
+    const bool lds = jointCount <= kSkinLdsJoints;
+    constexpr unsigned kPoseBlock = 256;
+    const unsigned grid = std::min<unsigned>((b.triCount + kPoseBlock - 1u) / kPoseBlock, (unsigned)(8 * std::max(1, c->numCUs)));
+    uint4* const shade = kShadeTriStride == (int)sizeof(nx_triangle) ? nullptr : b.shadeTris.as<uint4>();
+    NX_HIP(launch_untimed_lds(kernels::pose(lds), grid, kPoseBlock, lds ? (size_t)jointCount * 48 : 0, c->stream, b.bindTris.as<uint4>(), b.skinTris.as<uint4>(),
+                              b.palette.as<float4>(), jointCount, b.triIdx.as<uint32_t>(), b.triCount, b.tris.as<uint4>(), shade, b.isect.as<float4>()));
+    NX_TRY(refit_blas_nodes(c, b));
+    NX_HIP(hipStreamSynchronize(c->stream));  // a pageable host array: see nxhip_set_instance_transforms
+    return NXHIP_OK;
+} NX_CATCH("nxhip_pose_blas")
+
+int nxhip_read_blas_triangles(nxhip_ctx* c, int32_t blasId, nx_triangle* out, uint32_t capacity)
+{
+    NX_CHECK_CTX(c);
+    if (blasId < 0 || (size_t)blasId >= c->blas.size()) return fail_invalid("nxhip_read_blas_triangles: no such BLAS");
+    const BlasHost& b = c->blas[(size_t)blasId];
+    if (!out || capacity < b.triCount) return fail_invalid("nxhip_read_blas_triangles: destination too small");
+    NX_HIP(hipSetDevice(c->device));
+    NX_SYNC_ALL(c);
+    NX_HIP(hipMemcpy(out, b.tris.p, (size_t)b.triCount * sizeof(nx_triangle), hipMemcpyDeviceToHost));
+    return NXHIP_OK;
+}
+
+int nxhip_read_blas_bounds(nxhip_ctx* c, int32_t blasId, float lo[3], float hi[3])
+{
+    NX_CHECK_CTX(c);
+    if (blasId < 0 || (size_t)blasId >= c->blas.size()) return fail_invalid("nxhip_read_blas_bounds: no such BLAS");
+    if (!lo || !hi) return fail_invalid("nxhip_read_blas_bounds: null destination");
+    const BlasHost& b = c->blas[(size_t)blasId];
+    NX_HIP(hipSetDevice(c->device));
+    nx_bvh8_node root;
+    NX_HIP(hipMemcpyAsync(&root, b.nodes.p, sizeof root, hipMemcpyDeviceToHost, c->stream));  // behind the refit, if one is on its way
+    NX_HIP(hipStreamSynchronize(c->stream));
+    // the root's quantisation frame, as nexus::BVHInstance::SetTransform decodes it (host/BVHInstance.cpp root_frame)
+    const float steps = std::exp2(8.0f) - 1.0f;
+    for (int a = 0; a < 3; a++) {
+        lo[a] = root.p[a];
+        hi[a] = root.p[a] + std::exp2(static_cast<float>(root.e[a] - 127)) * steps;
+    }
+    return NXHIP_OK;
+}
 
 int nxhip_read_tlas(nxhip_ctx* c, nx_bvh8_node* nodes, uint32_t nodeCapacity, nx_bvh_instance* instances, uint32_t instanceCapacity)
 {

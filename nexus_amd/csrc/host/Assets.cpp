@@ -63,8 +63,18 @@ void AssetManager::UpdateMeshTriangles(int32_t bvhId, const std::vector<Triangle
     BVH8& bvh = m_Bvhs[static_cast<size_t>(bvhId)];
     if (triangles.size() != bvh.triangleIdx.size()) throw std::runtime_error("AssetManager::UpdateMeshTriangles: the triangle count differs from the mesh's (a refit keeps the topology)");
     bvh.Refit(triangles);  // (nodes and the tree's copy of the triangles)
+    bvh.posed = false;     // (the host's shape is the mesh's shape again)
     m_DeformedBvhs.insert(bvhId);
     deformedBvhs.insert(bvhId);
+}
+
+void AssetManager::SetPosedBounds(int32_t bvhId, const float lo[3], const float hi[3])
+{
+    if (bvhId < 0 || static_cast<size_t>(bvhId) >= m_Bvhs.size()) throw std::runtime_error("AssetManager::SetPosedBounds: no such BVH");
+    BVH8& bvh = m_Bvhs[static_cast<size_t>(bvhId)];
+    bvh.posed = true;
+    for (int a = 0; a < 3; a++) { bvh.posedMin[a] = lo[a]; bvh.posedMax[a] = hi[a]; }
+    m_DeformedBvhs.insert(bvhId);  // (Scene::Update re-places the instances; the triangles stay where they are: on the device)
 }
 
 std::set<int32_t> AssetManager::TakeDeformedBvhs()

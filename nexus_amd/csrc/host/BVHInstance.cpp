@@ -11,6 +11,11 @@ namespace {
 // the root node's decode frame of a BLAS: lower corner and per-axis extent 2^(e-127) * (2^8 - 1)
 void root_frame(const BVH8& blas, float3& lo, float3& hi)
 {
+    if (blas.posed) {  // posed on the device: the box its root encodes there (AssetManager::SetPosedBounds)
+        lo = make_float3(blas.posedMin);
+        hi = make_float3(blas.posedMax);
+        return;
+    }
     const BVH8Node& root = blas.nodes[0];
     const float steps = std::exp2(8.0f) - 1.0f;
     lo = make_float3(root.p);

@@ -347,6 +347,116 @@ struct Accessor {
     }
 };
 
+// LoadOptions::skins: the node tree (parents and rest TRS), the skin of every skinned primitive (the corner records are there already:
+// the primitive loop of parse_glb) and the joint animations as channels.  The twin of nexus_amd/loaders.py _read_skins.
+template <class AccessorOf>
+void read_skins(const Json& doc, const AccessorOf& accessor, const std::map<std::pair<size_t, size_t>, std::pair<int, int>>& primMesh, LoadedScene& out)
+{
+    const Json& nodes = doc.at("nodes");
+    out.nodes.resize(nodes.size());
+    for (size_t ni = 0; ni < nodes.size(); ni++) {
+        const Json& node = nodes.at(ni);
+        SceneNode& n = out.nodes[ni];
+        if (const Json* name = node.find("name")) n.name = name->str;
+        if (const Json* j = node.find("translation"))
+            for (size_t k = 0; k < 3 && k < j->size(); k++) n.translation[k] = j->at(k).num;
+        if (const Json* j = node.find("rotation"))
+            for (size_t k = 0; k < 4 && k < j->size(); k++) n.rotation[k] = j->at(k).num;
+        if (const Json* j = node.find("scale"))
+            for (size_t k = 0; k < 3 && k < j->size(); k++) n.scale[k] = j->at(k).num;
+        if (node.find("matrix")) {
+            n.hasMatrix = true;
+            const M4 m = node_local_matrix(node);
+            for (int i = 0; i < 4; i++)
+                for (int j = 0; j < 4; j++) n.matrix[4 * i + j] = m.m[i][j];
+        }
+        if (const Json* ch = node.find("children"))
+            for (size_t k = 0; k < ch->size(); k++) {
+                const size_t c = static_cast<size_t>(ch->at(k).num);
+                if (c >= nodes.size()) fail("glb: a node names a child that does not exist");
+                out.nodes[c].parent = static_cast<int>(ni);
+            }
+    }
+    for (size_t ni = 0; ni < nodes.size(); ni++) {
+        const Json& node = nodes.at(ni);
+        const Json* meshRef = node.find("mesh");
+        const Json* skinRef = node.find("skin");
+        if (!meshRef || !skinRef) continue;
+        const Json& skin = doc.at("skins").at(static_cast<size_t>(skinRef->num));
+        const Json& joints = skin.at("joints");
+        std::vector<int> jointNodes;
+        for (size_t k = 0; k < joints.size(); k++) {
+            if (joints.at(k).num < 0 || joints.at(k).num >= static_cast<double>(nodes.size())) fail("glb: a skin names a joint node that does not exist");
+            jointNodes.push_back(static_cast<int>(joints.at(k).num));
+        }
+        std::vector<double> inverseBind(jointNodes.size() * 16, 0.0);
+        for (size_t k = 0; k < jointNodes.size(); k++)
+            for (int d = 0; d < 4; d++) inverseBind[16 * k + 5 * static_cast<size_t>(d)] = 1.0;
+        if (const Json* ibm = skin.find("inverseBindMatrices")) {
+            const Accessor a = accessor(static_cast<size_t>(ibm->num));
+            if (a.ncomp != 16 || a.count != jointNodes.size()) fail("glb: a skin's inverse bind matrices do not fit its joints");
+            for (size_t k = 0; k < a.count; k++)
+                for (int i = 0; i < 4; i++)
+                    for (int j = 0; j < 4; j++) inverseBind[16 * k + 4 * static_cast<size_t>(i) + static_cast<size_t>(j)] = a.get(k, j * 4 + i);  // glTF stores column major
+        }
+        for (const auto& kv : primMesh) {
+            if (kv.first.first != static_cast<size_t>(meshRef->num)) continue;
+            Skin* s = out.skins[static_cast<size_t>(kv.second.first)].get();
+            if (!s || s->meshNode >= 0) continue;  // (no JOINTS_0 / WEIGHTS_0; or placed by an earlier node: that one's skin holds)
+            for (const nx_skin_corner& c : s->corners)
+                for (int k = 0; k < 4; k++)
+                    if (c.weight[k] != 0.0f && c.joint[k] >= jointNodes.size()) fail("glb: a primitive names a joint its skin does not have");
+            s->joints = jointNodes;
+            s->inverseBind = inverseBind;
+            s->meshNode = static_cast<int>(ni);
+        }
+    }
+    for (std::shared_ptr<Skin>& s : out.skins)
+        if (s && s->meshNode < 0) s.reset();  // (joints and weights on a mesh no skinned node places: nothing to pose it with)
+    const Json* anims = doc.find("animations");
+    for (size_t ai = 0; anims && ai < anims->size(); ai++) {
+        const Json& anim = anims->at(ai);
+        Animation A;
+        if (const Json* name = anim.find("name")) A.name = name->str;
+        const Json* channels = anim.find("channels");
+        for (size_t ci = 0; channels && ci < channels->size(); ci++) {
+            const Json& ch = channels->at(ci);
+            const Json* target = ch.find("target");
+            if (!target || !target->find("node") || !target->find("path")) continue;
+            const std::string& path = target->at("path").str;
+            if (path != "translation" && path != "rotation" && path != "scale") continue;  // (weights: morph targets, ignored with the primitive's warning)
+            AnimationChannel c;
+            c.node = static_cast<int>(target->at("node").num);
+            if (c.node < 0 || static_cast<size_t>(c.node) >= nodes.size()) fail("glb: an animation channel names a node that does not exist");
+            c.path = path == "translation" ? AnimationChannel::TRANSLATION : path == "rotation" ? AnimationChannel::ROTATION : AnimationChannel::SCALE;
+            const Json& sampler = anim.at("samplers").at(static_cast<size_t>(ch.at("sampler").num));
+            const Accessor in = accessor(static_cast<size_t>(sampler.at("input").num)), val = accessor(static_cast<size_t>(sampler.at("output").num));
+            const Json* ip = sampler.find("interpolation");
+            const std::string interpolation = ip ? ip->str : "LINEAR";
+            size_t perKey = 1, valueAt = 0;
+            if (interpolation == "CUBICSPLINE") {
+                out.warnings.push_back("animation " + std::to_string(ai) + ": a CUBICSPLINE sampler is read as its keys' values and interpolated linearly");
+                perKey = 3;  // (in-tangent, value, out-tangent) per key
+                valueAt = 1;
+            } else if (interpolation == "STEP") {
+                c.step = true;
+            } else if (interpolation != "LINEAR") {
+                fail("glb: animation " + std::to_string(ai) + " has an unknown interpolation");
+            }
+            const int width = c.path == AnimationChannel::ROTATION ? 4 : 3;
+            if (in.count == 0 || val.count != in.count * perKey || val.ncomp != width) fail("glb: animation " + std::to_string(ai) + " has a sampler whose keys and values differ in number");
+            // (normalised integers: glTF allows them for rotations)
+            const double unit = val.componentType == 5120 ? 127.0 : val.componentType == 5121 ? 255.0 : val.componentType == 5122 ? 32767.0 : val.componentType == 5123 ? 65535.0 : 1.0;
+            for (size_t k = 0; k < in.count; k++) {
+                c.times.push_back(in.get(k, 0));
+                for (int d = 0; d < width; d++) c.values.push_back(unit == 1.0 ? val.get(perKey * k + valueAt, d) : std::max(val.get(perKey * k + valueAt, d) / unit, -1.0));
+            }
+            A.channels.push_back(std::move(c));
+        }
+        out.animations.push_back(std::move(A));
+    }
+}
+
 LoadedScene parse_glb(const std::string& file, const LoadOptions& options)
 {
     const std::vector<unsigned char> data = read_file(file);
@@ -510,6 +620,31 @@ LoadedScene parse_glb(const std::string& file, const LoadOptions& options)
                 tris.emplace_back(p[0], p[1], p[2], n[0], n[1], n[2], tc[0], tc[1], tc[2]);
             }
             primMesh[{mi, pi}] = {static_cast<int>(out.meshes.size()), static_cast<int>(prim.number("material", 0))};
+            if (options.skins) {
+                const std::string what = "mesh " + std::to_string(mi) + " primitive " + std::to_string(pi);
+                if (const Json* targets = prim.find("targets"))
+                    if (targets->size() > 0) out.warnings.push_back(what + ": morph targets are ignored");
+                if (attrs.find("JOINTS_1")) out.warnings.push_back(what + ": more than four influences per vertex (JOINTS_1) are ignored; JOINTS_0 / WEIGHTS_0 are used");
+                std::shared_ptr<Skin> skin;
+                if (attrs.find("JOINTS_0") && attrs.find("WEIGHTS_0")) {
+                    const Accessor jt = accessor(static_cast<size_t>(attrs.at("JOINTS_0").num)), wt = accessor(static_cast<size_t>(attrs.at("WEIGHTS_0").num));
+                    if (jt.ncomp != 4 || wt.ncomp != 4 || jt.count != pos.count || wt.count != pos.count) fail("glb: " + what + " has JOINTS_0 / WEIGHTS_0 that do not fit its vertices");
+                    // (normalised integers: glTF's UNSIGNED_BYTE / UNSIGNED_SHORT weights)
+                    const double unit = wt.componentType == 5121 ? 255.0 : wt.componentType == 5123 ? 65535.0 : 1.0;
+                    skin = std::make_shared<Skin>();
+                    skin->corners.resize(corners / 3 * 3);
+                    for (size_t c = 0; c < skin->corners.size(); c++) {  // corner 3 i + v = vertex v of triangle i, de-indexed like the positions
+                        const size_t v = indexed ? static_cast<size_t>(idx.get(c, 0)) : c;
+                        for (int k = 0; k < 4; k++) {
+                            const double j = jt.get(v, k);
+                            if (j < 0 || j > 65535) fail("glb: " + what + " names a joint that does not fit 16 bits");
+                            skin->corners[c].joint[k] = static_cast<uint16_t>(j);
+                            skin->corners[c].weight[k] = unit == 1.0 ? static_cast<float>(wt.get(v, k)) : static_cast<float>(wt.get(v, k) / unit);
+                        }
+                    }
+                }
+                out.skins.push_back(std::move(skin));
+            }
             out.meshes.push_back(std::move(tris));
             const Json* name = mesh.find("name");
             out.meshNames.push_back(name ? name->str : "mesh" + std::to_string(mi));
@@ -590,6 +725,7 @@ LoadedScene parse_glb(const std::string& file, const LoadOptions& options)
     for (size_t k = 0; k < roots.size(); k++) walker.walk(static_cast<size_t>(roots.at(k).num), M4::identity());
     for (const LoadedInstance& inst : out.instances)
         if (inst.material < 0 || static_cast<size_t>(inst.material) >= out.materials.size()) fail("glb: primitive refers to a material that does not exist");
+    if (options.skins) read_skins(doc, accessor, primMesh, out);
     return out;
 }
 
@@ -733,7 +869,27 @@ void OBJLoader::LoadOBJ(const std::string& path, const std::string& filename, Sc
     // one BVH8 per mesh of the file (OBJLoader.cpp:213-239) — created together, so that a device builder can build them in one go
     std::vector<int32_t> meshIds;
     const int32_t firstBvh = assetManager->CreateBVHs(ls.meshes);
-    for (size_t i = 0; i < ls.meshes.size(); i++) meshIds.push_back(assetManager->AddMesh(Mesh(ls.meshNames[i], firstBvh + static_cast<int32_t>(i), -1)));
+    // skins, nodes and animations (LoadOptions::skins): the file's node indices become the scene's, behind the nodes of the files before it
+    const int nodeBase = static_cast<int>(scene->GetNodes().size());
+    if (!ls.nodes.empty()) {
+        std::vector<SceneNode> nodes = ls.nodes;
+        for (SceneNode& n : nodes)
+            if (n.parent >= 0) n.parent += nodeBase;
+        scene->AddNodes(nodes);
+        for (Animation a : ls.animations) {
+            for (AnimationChannel& c : a.channels) c.node += nodeBase;
+            scene->AddAnimation(a);
+        }
+    }
+    for (size_t i = 0; i < ls.meshes.size(); i++) {
+        Mesh mesh(ls.meshNames[i], firstBvh + static_cast<int32_t>(i), -1);
+        if (i < ls.skins.size() && ls.skins[i]) {
+            mesh.skin = std::make_shared<Skin>(*ls.skins[i]);
+            for (int& j : mesh.skin->joints) j += nodeBase;
+            mesh.skin->meshNode += nodeBase;
+        }
+        meshIds.push_back(assetManager->AddMesh(std::move(mesh)));
+    }
     for (const LoadedInstance& inst : ls.instances) {
         MeshInstance& mi = scene->CreateMeshInstance(static_cast<uint32_t>(meshIds[static_cast<size_t>(inst.mesh)]));
         mi.name = inst.name.empty() ? ls.meshNames[static_cast<size_t>(inst.mesh)] : inst.name;

@@ -142,6 +142,26 @@ void PathTracer::SetDeviceBlasBuild(Scene& scene, bool enable)
     });
 }
 
+void PathTracer::PoseMesh(Scene& scene, int32_t bvhId, const std::vector<float>& palette)
+{
+    AssetManager& assets = scene.GetAssetManager();
+    Skin* skin = nullptr;
+    for (Mesh& m : assets.GetMeshes())
+        if (m.bvhId == bvhId && m.skin) skin = m.skin.get();
+    if (bvhId < 0 || static_cast<size_t>(bvhId) >= assets.GetBVHs().size() || !skin) throw std::runtime_error("PathTracer::PoseMesh: no skinned mesh has that BVH");
+    if (palette.size() != skin->joints.size() * 12) throw std::runtime_error("PathTracer::PoseMesh: the palette does not have 12 floats per joint of the skin");
+    UploadPendingBlas(assets);  // (a mesh posed before its first frame)
+    const int32_t blas = assets.GetBVHs()[static_cast<size_t>(bvhId)].deviceBlasId;
+    if (!skin->onDevice) {
+        Check(nxhip_set_blas_skin(m_Ctx, blas, skin->corners.data(), static_cast<uint32_t>(skin->corners.size()), static_cast<uint32_t>(skin->joints.size())), "nxhip_set_blas_skin");
+        skin->onDevice = true;
+    }
+    Check(nxhip_pose_blas(m_Ctx, blas, palette.data(), static_cast<uint32_t>(skin->joints.size())), "nxhip_pose_blas");
+    float lo[3], hi[3];
+    Check(nxhip_read_blas_bounds(m_Ctx, blas, lo, hi), "nxhip_read_blas_bounds");
+    assets.SetPosedBounds(bvhId, lo, hi);
+}
+
 void PathTracer::UpdateDeviceScene(const Scene& scene)
 {
     const AssetManager& assets = scene.GetAssetManager();

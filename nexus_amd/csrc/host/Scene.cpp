@@ -3,6 +3,8 @@
 // emissive map or intensity * max(emissive) > 0; the TLAS is rebuilt whenever an instance changed.
 #include "nexus/Scene.h"
 
+#include <algorithm>
+#include <cmath>
 #include <stdexcept>
 
 #include "nexus/IMGLoader.h"
@@ -27,6 +29,8 @@ void Scene::Reset()
     ClearMedium();
     ClearMediumDensity();
     m_AssetManager.Reset();
+    m_Nodes.clear();
+    m_Animations.clear();
     m_Camera->Invalidate();
     m_TlasBuiltFor = 0;
     tlasDirty = lightsDirty = true;
@@ -123,8 +127,186 @@ void Scene::CreateMeshInstanceFromFile(const std::string& path, const std::strin
     LoadOptions options;
     options.metalRough = m_MetalRoughMaterials;
     options.alphaModes = m_MaterialAlphaModes;
+    options.skins = m_Skins;
     OBJLoader::LoadOBJ(path, fileName, this, &m_AssetManager, options);
     Invalidate();  // the TLAS is rebuilt by the next Update()
+}
+
+// ---- pose evaluation (skinned meshes): binary64 throughout, one rounding at the end ---------------------------------------------
+namespace {
+
+struct D4 {
+    double m[4][4];
+};
+
+D4 d4_identity()
+{
+    D4 r;
+    for (int i = 0; i < 4; i++)
+        for (int j = 0; j < 4; j++) r.m[i][j] = i == j ? 1.0 : 0.0;
+    return r;
+}
+
+D4 d4_mul(const D4& a, const D4& b)
+{
+    D4 r;
+    for (int i = 0; i < 4; i++)
+        for (int j = 0; j < 4; j++) {
+            double s = 0.0;
+            for (int k = 0; k < 4; k++) s += a.m[i][k] * b.m[k][j];
+            r.m[i][j] = s;
+        }
+    return r;
+}
+
+// Gauss-Jordan with partial pivoting; throws on a singular matrix (a mesh node scaled to nothing cannot carry a skin)
+D4 d4_inverse(const D4& a)
+{
+    double w[4][8];
+    for (int i = 0; i < 4; i++)
+        for (int j = 0; j < 4; j++) {
+            w[i][j] = a.m[i][j];
+            w[i][4 + j] = i == j ? 1.0 : 0.0;
+        }
+    for (int c = 0; c < 4; c++) {
+        int p = c;
+        for (int r = c + 1; r < 4; r++)
+            if (std::fabs(w[r][c]) > std::fabs(w[p][c])) p = r;
+        if (w[p][c] == 0.0) throw std::runtime_error("Scene::JointPalette: the mesh node's world matrix is singular");
+        if (p != c)
+            for (int j = 0; j < 8; j++) std::swap(w[p][j], w[c][j]);
+        const double d = w[c][c];
+        for (int j = 0; j < 8; j++) w[c][j] /= d;
+        for (int r = 0; r < 4; r++) {
+            if (r == c) continue;
+            const double f = w[r][c];
+            if (f == 0.0) continue;
+            for (int j = 0; j < 8; j++) w[r][j] -= f * w[c][j];
+        }
+    }
+    D4 out;
+    for (int i = 0; i < 4; i++)
+        for (int j = 0; j < 4; j++) out.m[i][j] = w[i][4 + j];
+    return out;
+}
+
+void quat_normalise(double q[4])
+{
+    const double n = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+    for (int k = 0; k < 4; k++) q[k] /= n;
+}
+
+// a channel's value at time t, clamped to its first and last key
+void sample_channel(const AnimationChannel& c, double t, double out[4])
+{
+    const int width = c.path == AnimationChannel::ROTATION ? 4 : 3;
+    const size_t keys = c.times.size();
+    auto key = [&](size_t k, double v[4]) {
+        for (int d = 0; d < width; d++) v[d] = c.values[static_cast<size_t>(width) * k + static_cast<size_t>(d)];
+    };
+    if (t <= c.times.front()) return key(0, out);
+    if (t >= c.times.back()) return key(keys - 1, out);
+    const size_t i = static_cast<size_t>(std::upper_bound(c.times.begin(), c.times.end(), t) - c.times.begin()) - 1;  // times[i] <= t < times[i + 1]
+    if (c.step) return key(i, out);
+    const double u = (t - c.times[i]) / (c.times[i + 1] - c.times[i]);
+    double a[4], b[4];
+    key(i, a);
+    key(i + 1, b);
+    if (c.path != AnimationChannel::ROTATION) {
+        for (int d = 0; d < 3; d++) out[d] = (1.0 - u) * a[d] + u * b[d];
+        return;
+    }
+    // shortest-arc slerp; a normalised lerp where the arc is too short to divide by its sine
+    double dot = a[0] * b[0] + a[1] * b[1] + a[2] * b[2] + a[3] * b[3];
+    if (dot < 0.0) {
+        dot = -dot;
+        for (int d = 0; d < 4; d++) b[d] = -b[d];
+    }
+    if (1.0 - dot < 1e-9) {
+        for (int d = 0; d < 4; d++) out[d] = (1.0 - u) * a[d] + u * b[d];
+    } else {
+        const double theta = std::acos(std::min(dot, 1.0));
+        const double sa = std::sin((1.0 - u) * theta), sb = std::sin(u * theta), s = std::sin(theta);
+        for (int d = 0; d < 4; d++) out[d] = (sa * a[d] + sb * b[d]) / s;
+    }
+    quat_normalise(out);
+}
+
+}  // namespace
+
+std::vector<float> Scene::JointPalette(uint32_t meshId, int animationIdx, double t) const
+{
+    const std::vector<Mesh>& meshes = const_cast<AssetManager&>(m_AssetManager).GetMeshes();
+    if (meshId >= meshes.size() || !meshes[meshId].skin) throw std::runtime_error("Scene::JointPalette: no such mesh, or the mesh has no skin");
+    if (animationIdx < -1 || animationIdx >= static_cast<int>(m_Animations.size())) throw std::runtime_error("Scene::JointPalette: no such animation");
+    const Skin& skin = *meshes[meshId].skin;
+    // local TRS of every node: the rest pose, then what the animation's channels say at t
+    struct Trs {
+        double t[3], r[4], s[3];
+        bool animated = false;
+    };
+    std::vector<Trs> trs(m_Nodes.size());
+    for (size_t i = 0; i < m_Nodes.size(); i++) {
+        std::copy(m_Nodes[i].translation, m_Nodes[i].translation + 3, trs[i].t);
+        std::copy(m_Nodes[i].rotation, m_Nodes[i].rotation + 4, trs[i].r);
+        std::copy(m_Nodes[i].scale, m_Nodes[i].scale + 3, trs[i].s);
+    }
+    if (animationIdx >= 0)
+        for (const AnimationChannel& c : m_Animations[static_cast<size_t>(animationIdx)].channels) {
+            Trs& n = trs[static_cast<size_t>(c.node)];
+            double v[4] = {0, 0, 0, 0};
+            sample_channel(c, t, v);
+            std::copy(v, v + (c.path == AnimationChannel::ROTATION ? 4 : 3), c.path == AnimationChannel::TRANSLATION ? n.t : c.path == AnimationChannel::ROTATION ? n.r : n.s);
+            n.animated = true;
+        }
+    auto local = [&](size_t i) {
+        D4 m = d4_identity();
+        if (m_Nodes[i].hasMatrix && !trs[i].animated) {
+            for (int a = 0; a < 4; a++)
+                for (int b = 0; b < 4; b++) m.m[a][b] = m_Nodes[i].matrix[4 * a + b];
+            return m;
+        }
+        double q[4] = {trs[i].r[0], trs[i].r[1], trs[i].r[2], trs[i].r[3]};
+        quat_normalise(q);
+        const double x = q[0], y = q[1], z = q[2], w = q[3];
+        const double R[3][3] = {{1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)},
+                                {2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)},
+                                {2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)}};
+        for (int a = 0; a < 3; a++) {
+            for (int b = 0; b < 3; b++) m.m[a][b] = R[a][b] * trs[i].s[b];
+            m.m[a][3] = trs[i].t[a];
+        }
+        return m;
+    };
+    std::vector<D4> world(m_Nodes.size());
+    std::vector<char> done(m_Nodes.size(), 0);
+    auto resolve = [&](size_t i) {
+        // (iterative: up to the first resolved ancestor, then back down)
+        std::vector<size_t> chain;
+        for (size_t at = i; !done[at]; at = static_cast<size_t>(m_Nodes[at].parent)) {
+            chain.push_back(at);
+            if (m_Nodes[at].parent < 0) break;
+            if (chain.size() > m_Nodes.size()) throw std::runtime_error("Scene::JointPalette: the node tree has a cycle");
+        }
+        for (size_t k = chain.size(); k-- > 0;) {
+            const size_t at = chain[k];
+            world[at] = m_Nodes[at].parent < 0 ? local(at) : d4_mul(world[static_cast<size_t>(m_Nodes[at].parent)], local(at));
+            done[at] = 1;
+        }
+    };
+    resolve(static_cast<size_t>(skin.meshNode));
+    const D4 toMesh = d4_inverse(world[static_cast<size_t>(skin.meshNode)]);
+    std::vector<float> palette(skin.joints.size() * 12);
+    for (size_t k = 0; k < skin.joints.size(); k++) {
+        resolve(static_cast<size_t>(skin.joints[k]));
+        D4 ibm;
+        for (int a = 0; a < 4; a++)
+            for (int b = 0; b < 4; b++) ibm.m[a][b] = skin.inverseBind[16 * k + 4 * static_cast<size_t>(a) + static_cast<size_t>(b)];
+        const D4 m = d4_mul(d4_mul(toMesh, world[static_cast<size_t>(skin.joints[k])]), ibm);
+        for (int a = 0; a < 3; a++)
+            for (int b = 0; b < 4; b++) palette[12 * k + 4 * static_cast<size_t>(a) + static_cast<size_t>(b)] = static_cast<float>(m.m[a][b]);
+    }
+    return palette;
 }
 
 void Scene::AddHDRMap(const Texture& texture)

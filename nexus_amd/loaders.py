@@ -85,6 +85,15 @@ class LoadedScene:
         # (load_glb(alpha_modes=True)): every existing scene keeps rendering its alpha as a stochastic blend
         self.material_alpha = None
         self.analytic_lights = np.zeros(0, dtype=pod.ALIGHT_DT)  # glTF KHR_lights_punctual: one per node that carries a light, world space
+        # glTF skins and joint animations; empty unless the reader was asked (load_glb(skins=True)).  Posed by nexus_amd.animation.joint_palette.
+        # skins: per (node with a skin, skinned primitive of its mesh) a dict(mesh: index into meshes, corners: pod.SKIN_CORNER_DT array of
+        #   3 x triangles records de-indexed like the positions, joints: node indices, inverse_bind: (joints, 4, 4) float64, mesh_node)
+        # animations: dict(name, channels: [dict(node, path "translation" / "rotation" / "scale", times float64, values float64 (keys, 3 or 4),
+        #   interpolation "STEP" / "LINEAR")])
+        # nodes: per glTF node a dict(name, parent (-1: a root), translation, rotation (x, y, z, w), scale, matrix (4 x 4 or None: the TRS holds))
+        self.skins = []
+        self.animations = []
+        self.nodes = []
         self.warnings = []
 
 
@@ -338,11 +347,14 @@ def _gltf_material(m, metal_rough=False):
 _GLTF_ALPHA = {"OPAQUE": pod.ALPHA_OPAQUE, "MASK": pod.ALPHA_MASK, "BLEND": pod.ALPHA_BLEND}
 
 
-def load_glb(path, metal_rough=False, alpha_modes=False):
+def load_glb(path, metal_rough=False, alpha_modes=False, skins=False):
     """metal_rough (off by default: glTF's default metallicFactor is 1): materials without transmission become MAT_METALROUGH with the
     file's raw factors instead of the reference's PLASTIC
     alpha_modes (off by default: every existing scene renders as before): the materials' alphaMode (glTF's default: OPAQUE) and
-    alphaCutoff (default 0.5) fill LoadedScene.material_alpha"""
+    alphaCutoff (default 0.5) fill LoadedScene.material_alpha
+    skins (off by default: every existing scene loads as before): JOINTS_0 / WEIGHTS_0, the skins, the joint animations and the node tree
+    fill LoadedScene.skins / animations / nodes.  Morph targets and JOINTS_1 are ignored with a warning; a CUBICSPLINE sampler is read
+    as its keys' values, interpolated linearly, with a warning."""
     data = open(path, "rb").read()
     magic, version, _length = struct.unpack_from("<III", data, 0)
     if magic != 0x46546C67 or version != 2:
@@ -438,6 +450,7 @@ def load_glb(path, metal_rough=False, alpha_modes=False):
 
     # one mesh per primitive (what Assimp hands the reference)
     prim_mesh = {}
+    prim_corners = {}  # skins=True: (mesh, primitive) -> its de-indexed nx_skin_corner records
     for mi, mesh in enumerate(doc.get("meshes", [])):
         for pi, prim in enumerate(mesh["primitives"]):
             if prim.get("mode", 4) != 4:
@@ -453,6 +466,19 @@ def load_glb(path, metal_rough=False, alpha_modes=False):
                 uv[:, 1] = 1.0 - uv[:, 1]  # aiProcess_FlipUVs, OBJLoader.cpp:219-220
             t = pod.make_triangles(pos[tri], normals=normals, uvs=uv[tri] if uv is not None else None)
             prim_mesh[(mi, pi)] = (len(out.meshes), prim.get("material", 0))
+            if skins:
+                what = "mesh %d primitive %d" % (mi, pi)
+                if prim.get("targets"):
+                    out.warnings.append("%s: morph targets are ignored" % what)
+                if "JOINTS_1" in prim["attributes"]:
+                    out.warnings.append("%s: more than four influences per vertex (JOINTS_1) are ignored; JOINTS_0 / WEIGHTS_0 are used" % what)
+                if "JOINTS_0" in prim["attributes"] and "WEIGHTS_0" in prim["attributes"]:
+                    wa = doc["accessors"][prim["attributes"]["WEIGHTS_0"]]
+                    w = accessor(prim["attributes"]["WEIGHTS_0"])
+                    # (normalised integers: glTF's UNSIGNED_BYTE / UNSIGNED_SHORT weights)
+                    w = w.astype(np.float32) if wa["componentType"] == 5126 else (w.astype(np.float64) / np.iinfo(w.dtype).max).astype(np.float32)
+                    j = accessor(prim["attributes"]["JOINTS_0"]).astype(np.int64)
+                    prim_corners[(mi, pi)] = pod.make_skin_corners(j[idx], w[idx])  # corner 3 i + v = vertex v of triangle i
             out.meshes.append(t)
             out.mesh_names.append(mesh.get("name", "mesh%d" % mi))
 
@@ -485,7 +511,64 @@ def load_glb(path, metal_rough=False, alpha_modes=False):
     for ni in scene["nodes"]:
         walk(ni, np.eye(4))
     out.analytic_lights = np.array(lights, dtype=pod.ALIGHT_DT) if lights else np.zeros(0, dtype=pod.ALIGHT_DT)
+    if skins:
+        _read_skins(doc, accessor, prim_mesh, prim_corners, out)
     return out
+
+
+def _read_skins(doc, accessor, prim_mesh, prim_corners, out):
+    """LoadedScene.nodes, skins and animations of a glTF document (load_glb(skins=True))"""
+    nodes = doc.get("nodes", [])
+    parent = [-1] * len(nodes)
+    for ni, node in enumerate(nodes):
+        for c in node.get("children", []):
+            parent[c] = ni
+    for ni, node in enumerate(nodes):
+        out.nodes.append(dict(name=node.get("name", ""), parent=parent[ni],
+                              translation=np.array(node.get("translation", [0, 0, 0]), np.float64), rotation=np.array(node.get("rotation", [0, 0, 0, 1]), np.float64),
+                              scale=np.array(node.get("scale", [1, 1, 1]), np.float64),
+                              matrix=np.array(node["matrix"], np.float64).reshape(4, 4).T if "matrix" in node else None))
+    for ni, node in enumerate(nodes):
+        if "mesh" not in node or "skin" not in node:
+            continue
+        skin = doc["skins"][node["skin"]]
+        joints = [int(j) for j in skin["joints"]]
+        if "inverseBindMatrices" in skin:
+            ibm = accessor(skin["inverseBindMatrices"]).astype(np.float64).reshape(-1, 4, 4).transpose(0, 2, 1)  # glTF stores column major
+        else:
+            ibm = np.tile(np.eye(4), (len(joints), 1, 1))
+        if len(ibm) != len(joints):
+            raise ValueError("glb: skin %d has %d joints and %d inverse bind matrices" % (node["skin"], len(joints), len(ibm)))
+        for (mi, pi), (mesh_id, _mat) in prim_mesh.items():
+            if mi != node["mesh"] or (mi, pi) not in prim_corners:
+                continue
+            corners = prim_corners[(mi, pi)]
+            if np.any(corners["joint"][corners["weight"] != 0] >= len(joints)):
+                raise ValueError("glb: mesh %d primitive %d names a joint its skin does not have" % (mi, pi))
+            out.skins.append(dict(mesh=mesh_id, corners=corners, joints=joints, inverse_bind=ibm, mesh_node=ni))
+    for ai, anim in enumerate(doc.get("animations", [])):
+        channels = []
+        for ch in anim.get("channels", []):
+            target = ch.get("target", {})
+            if "node" not in target or target.get("path") not in ("translation", "rotation", "scale"):
+                continue  # (weights: morph targets, ignored with the primitive's warning)
+            s = anim["samplers"][ch["sampler"]]
+            times = accessor(s["input"]).reshape(-1).astype(np.float64)
+            oa = doc["accessors"][s["output"]]
+            values = accessor(s["output"])
+            # (normalised integers: glTF allows them for rotations)
+            values = values.astype(np.float64) if oa["componentType"] == 5126 else np.maximum(values.astype(np.float64) / np.iinfo(values.dtype).max, -1.0)
+            interpolation = s.get("interpolation", "LINEAR")
+            if interpolation == "CUBICSPLINE":
+                out.warnings.append("animation %d: a CUBICSPLINE sampler is read as its keys' values and interpolated linearly" % ai)
+                values = values.reshape(len(times), 3, -1)[:, 1]  # (in-tangent, value, out-tangent) per key
+                interpolation = "LINEAR"
+            elif interpolation not in ("STEP", "LINEAR"):
+                raise ValueError("glb: animation %d has the unknown interpolation %r" % (ai, interpolation))
+            if len(times) == 0 or len(values) != len(times):
+                raise ValueError("glb: animation %d has a sampler whose keys and values differ in number" % ai)
+            channels.append(dict(node=int(target["node"]), path=target["path"], times=times, values=values, interpolation=interpolation))
+        out.animations.append(dict(name=anim.get("name", ""), channels=channels))
 
 
 def load_obj(path):

@@ -80,6 +80,10 @@ assert DETAIL_DT.itemsize == 16
 ALPHA_BLEND, ALPHA_MASK, ALPHA_OPAQUE = 0, 1, 2
 ALPHA_DT = np.dtype([("mode", "<u4"), ("cutoff", "<f4")])
 assert ALPHA_DT.itemsize == 8
+# nx_skin_corner (extension, nxhip_set_blas_skin): 24 bytes — the four joints and weights of one triangle corner
+SKIN_CORNER_DT = np.dtype([("joint", "<u2", 4), ("weight", "<f4", 4)])
+assert SKIN_CORNER_DT.itemsize == 24
+SKIN_MAX_JOINTS = 65536
 
 # nx_medium (extension, nxhip_set_medium): 48 bytes — fog, one homogeneous medium in a world-space box
 MEDIUM_DT = np.dtype([("boxMin", "<f4", 3), ("sigmaT", "<f4"), ("boxMax", "<f4", 3), ("g", "<f4"), ("albedo", "<f4", 3), ("pad", "<u4")])
@@ -183,6 +187,39 @@ def make_material_alpha(mode=ALPHA_BLEND, cutoff=0.5):
     a["mode"] = mode
     a["cutoff"] = cutoff
     return a
+
+
+def make_skin_corners(joints, weights):
+    """nx_skin_corner records from (n, 4) joint indices and (n, 4) weights: corner 3 i + v is vertex v of triangle i"""
+    joints, weights = np.asarray(joints), np.asarray(weights, dtype=np.float32)
+    if joints.ndim != 2 or joints.shape[1] != 4 or weights.shape != joints.shape:
+        raise ValueError("joints and weights must both be (n, 4)")
+    if joints.size and (joints.min() < 0 or joints.max() >= SKIN_MAX_JOINTS):
+        raise ValueError("a joint index does not fit 16 bits")
+    c = np.zeros(len(joints), dtype=SKIN_CORNER_DT)
+    c["joint"], c["weight"] = joints, weights
+    return c
+
+
+def normalise_skin_corners(corners, joint_count):
+    """the records as nxhip_set_blas_skin stores them, by its rules: weights divided by their binary64 sum and rounded once, the joint
+    of a zero weight rewritten to 0.  ValueError for what the call refuses: a joint count outside 1 .. 65536, a weight that is negative
+    or not finite, a joint index >= joint_count under a non-zero weight, a corner whose weights sum to 0."""
+    c = np.ascontiguousarray(corners, dtype=SKIN_CORNER_DT).copy()
+    if not 1 <= int(joint_count) <= SKIN_MAX_JOINTS:
+        raise ValueError("the joint count must be 1 .. %d" % SKIN_MAX_JOINTS)
+    w = c["weight"].astype(np.float64)
+    if not np.all(np.isfinite(w)) or np.any(w < 0):
+        raise ValueError("a weight is negative or not finite")
+    used = w != 0
+    if np.any(c["joint"][used] >= joint_count):
+        raise ValueError("a joint index is not below the joint count")
+    total = w.sum(axis=1)
+    if np.any(total <= 0):
+        raise ValueError("the weights of corner %d sum to 0" % int(np.flatnonzero(total <= 0)[0]))
+    c["weight"] = (w / total[:, None]).astype(np.float32)
+    c["joint"][~used] = 0
+    return c
 
 
 def make_material_detail(normal_map=-1, roughness_map=-1, normal_scale=1.0):
