@@ -1,6 +1,9 @@
 """ctypes binding of ``nexus_amd/lib/libnexus_amd.so`` — the C-ABI declared in ``include/nexus_hip.h`` (device
 layer) and ``include/nexus_host.h`` (host builders).
 
+The headers are the only place where a function's signature is written down: ``cabi`` reads their prototypes, and ``lib()`` sets
+``restype`` and ``argtypes`` of every declared function once, when it loads the library.  Every pointer is a ``c_void_p``.
+
 There is no Python / CPU fallback: if the library is missing or a device call fails, an exception is raised.
 """
 import ctypes as C
@@ -8,76 +11,18 @@ import os
 
 import numpy as np
 
-from . import pod
+from . import cabi, pod
+from .cabi import NexusError  # noqa: F401  (the one exception type of the binding)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # NEXUS_AMD_LIB: another build of the same library (tools/ab_bench.sh compares kernel variants); still no fallback
 LIB_PATH = os.environ.get("NEXUS_AMD_LIB") or os.path.join(_HERE, "lib", "libnexus_amd.so")
 
-# every symbol include/nexus_hip.h and include/nexus_host.h declare
-HIP_SYMBOLS = [
-    "nxhip_last_error", "nxhip_device_count", "nxhip_create", "nxhip_destroy", "nxhip_resize", "nxhip_sync",
-    "nxhip_upload_blas", "nxhip_clear_blas", "nxhip_set_tlas", "nxhip_set_materials", "nxhip_set_lights",
-    "nxhip_upload_texture", "nxhip_clear_textures", "nxhip_set_camera", "nxhip_set_render_settings", "nxhip_set_modes",
-    "nxhip_set_pixel_map", "nxhip_set_frames_per_pass", "nxhip_reset_frame_number", "nxhip_set_frame_number", "nxhip_frame_number",
-    "nxhip_render_frame", "nxhip_accumulate", "nxhip_render", "nxhip_read_radiance", "nxhip_read_accumulation",
-    "nxhip_read_rgba8", "nxhip_write_accumulation", "nxhip_bind_radiance", "nxhip_read_full_accumulation", "nxhip_read_full_rgba8", "nxhip_radiance_device_ptr", "nxhip_accumulation_device_ptr", "nxhip_accumulate_external", "nxhip_compose_tiles",
-    "nxhip_read_queue_sizes", "nxhip_set_pixel_query", "nxhip_get_selected_instance", "nxhip_trace_batch",
-    "nxhip_trace_shadow_batch", "nxhip_bsdf_sample_batch", "nxhip_bsdf_eval_batch", "nxhip_tex2d_batch", "nxhip_enable_trace_stats", "nxhip_read_trace_stats", "nxhip_enable_kernel_timing",
-    "nxhip_read_kernel_times", "nxhip_read_graph_timeline", "nxhip_has_gfx950_code", "nxhip_build_info", "nxhip_set_pixel_order", "nxhip_sync_timeout", "nxhip_debug_set_requeue", "nxhip_debug_thin_counts_of_pass", "nxhip_debug_write_blas_node", "nxhip_rebuild_tlas", "nxhip_read_tlas_index", "nxhip_release_queues", "nxhip_set_device_builder",
-    "nxhip_set_instance_transforms", "nxhip_read_tlas", "nxhip_set_passes_in_flight", "nxhip_set_tail_bounce", "nxhip_set_entry_points", "nxhip_read_entry_states", "nxhip_debug_set_thin", "nxhip_debug_set_thin_pool", "nxhip_debug_thin_counts", "nxhip_build_blas", "nxhip_read_blas", "nxhip_set_env_sampling",
-    "nxhip_tile_pixel_map", "nxhip_mgpu_unique_id", "nxhip_mgpu_init", "nxhip_mgpu_attach", "nxhip_mgpu_gather", "nxhip_mgpu_read_rgba8",
-    "nxhip_mgpu_read_accumulation", "nxhip_mgpu_shutdown", "nxhip_fmath_batch", "nxhip_abi_stamp", "nxhip_check_library", "nxhip_build_blas_batch", "nxhip_read_blas_batch", "nxhip_debug_set_scan_epoch", "nxhip_debug_ended_rays_of_pass", "nxhip_debug_entry_walks", "nxhip_debug_pass_flavor",
-    "nxhip_set_aov", "nxhip_read_aov", "nxhip_read_aov_frame", "nxhip_write_aov", "nxhip_denoise", "nxhip_denoise_defaults", "nxhip_read_denoised", "nxhip_read_denoised_rgba8",
-    "nxhip_adaptive_defaults", "nxhip_set_adaptive", "nxhip_adaptive_update", "nxhip_render_adaptive", "nxhip_read_sample_counts", "nxhip_read_noise_stats",
-    "nxhip_read_block_noise", "nxhip_read_active_map", "nxhip_update_blas", "nxhip_update_blas_device",
-    "nxhip_set_light_sampling", "nxhip_read_light_table", "nxhip_light_pick_batch",
-    "nxhip_read_env_tables", "nxhip_env_sample_batch", "nxhip_env_eval_batch",
-    "nxhip_upload_env_float", "nxhip_read_env_float", "nxhip_read_env_guides",
-    "nxhip_set_analytic_lights", "nxhip_analytic_light_sample_batch",
-    "nxhip_debug_read_primary_rays",
-    "nxhip_set_shadow_transmittance", "nxhip_trace_transmittance_batch",
-    "nxhip_set_material_detail", "nxhip_shading_frame_batch",
-    "nxhip_set_medium", "nxhip_medium_segment_batch", "nxhip_medium_phase_batch",
-    "nxhip_set_medium_density", "nxhip_read_medium_majorants", "nxhip_medium_density_batch", "nxhip_medium_track_batch",
-    "nxhip_set_queue_budget", "nxhip_get_queue_budget", "nxhip_queue_budget_from_text", "nxhip_debug_last_graph",
-    "nxhip_read_material_queue_sizes", "nxhip_material_inputs_batch",
-    "nxhip_set_material_alpha",
-    "nxhip_set_blas_skin", "nxhip_pose_blas", "nxhip_read_blas_triangles", "nxhip_read_blas_bounds",
-]
-HOST_SYMBOLS = [
-    "nxh_bvh8_build", "nxh_tlas_build", "nxh_tlas_refit", "nxh_bvh8_refit", "nxh_bvh8_node_count", "nxh_bvh8_prim_count", "nxh_bvh8_nodes",
-    "nxh_bvh8_prim_indices", "nxh_bvh8_free", "nxh_bvh2_build", "nxh_mat4_from_trs", "nxh_mat4_invert",
-    "nxh_instance_init", "nxh_camera_init", "nxh_loaded_texture_count", "nxh_loaded_texture_info", "nxh_loaded_texture_pixels",
-    "nxh_loaded_material_textures", "nxh_loaded_warning_count", "nxh_loaded_warning", "nxh_decode_png", "nxh_write_png", "nxh_write_exr",
-    "nxs_scene_add_hdr_map_file", "nxs_renderer_create", "nxs_renderer_destroy", "nxs_renderer_render", "nxs_renderer_reset", "nxs_renderer_on_resize",
-    "nxs_renderer_save_screenshot", "nxs_renderer_save_exr", "nxs_renderer_frame_number", "nxs_renderer_megasamples_per_second", "nxs_renderer_device_context",
-    "nxs_renderer_set_modes", "nxs_renderer_set_denoise", "nxs_renderer_save_denoised_exr", "nxs_renderer_save_feature_exr", "nxs_pathtracer_set_feature_buffers",
-    "nxs_renderer_set_adaptive", "nxs_renderer_render_adaptive", "nxs_renderer_save_sample_count_exr", "nxs_pathtracer_set_adaptive",
-    "nxh_load_scene_file", "nxh_loaded_scene_free", "nxh_loaded_mesh_count", "nxh_loaded_mesh_triangle_count", "nxh_loaded_mesh_triangles",
-    "nxh_loaded_material_count", "nxh_loaded_materials", "nxh_loaded_instance_count", "nxh_loaded_instances", "nxs_scene_load_file", "nxs_scene_set_instance_transform", "nxs_scene_assign_material", "nxs_scene_set_tlas_refit", "nxs_scene_set_device_tlas", "nxs_scene_update_mesh", "nxs_pathtracer_set_device_blas_build",
-    "nxs_last_error", "nxs_scene_create", "nxs_scene_destroy", "nxs_scene_add_material", "nxs_scene_add_texture", "nxs_scene_set_hdr_map",
-    "nxs_scene_add_mesh", "nxs_scene_create_instance", "nxs_scene_set_camera", "nxs_scene_set_render_settings", "nxs_scene_update",
-    "nxs_scene_light_count", "nxs_scene_instance_count", "nxs_pathtracer_create", "nxs_pathtracer_destroy", "nxs_pathtracer_set_modes", "nxs_pathtracer_set_frames_per_pass", "nxs_pathtracer_set_passes_in_flight", "nxs_pathtracer_set_pixel_order", "nxs_pathtracer_set_entry_points", "nxs_pathtracer_set_light_sampling",
-    "nxs_pathtracer_update_device_scene", "nxs_pathtracer_render", "nxs_pathtracer_reset_frame_number", "nxs_pathtracer_frame_number",
-    "nxs_pathtracer_read_pixels", "nxs_pathtracer_device_context",
-    "nxs_scene_set_hdr_map_float", "nxs_scene_add_hdr_map_file_float", "nxh_decode_hdr_float",
-    "nxh_loaded_analytic_light_count", "nxh_loaded_analytic_lights",
-    "nxs_scene_add_analytic_light", "nxs_scene_remove_analytic_light", "nxs_scene_analytic_light_count", "nxs_scene_analytic_lights",
-    "nxs_pathtracer_set_shadow_transmittance",
-    "nxh_loaded_detail_texture_count", "nxh_loaded_detail_texture_info", "nxh_loaded_detail_texture_pixels", "nxh_loaded_material_detail",
-    "nxs_scene_set_material_detail", "nxs_scene_clear_material_details", "nxs_scene_material_detail_count", "nxs_scene_material_details",
-    "nxs_scene_set_medium", "nxs_scene_clear_medium", "nxs_scene_medium",
-    "nxs_scene_set_medium_density", "nxs_scene_clear_medium_density", "nxs_scene_medium_density", "nxh_decode_npy_grid",
-    "nxh_load_scene_file_ex", "nxs_scene_set_metal_rough",
-    "nxh_loaded_material_alpha", "nxs_scene_set_material_alpha_modes", "nxs_scene_material_alphas",
-    "nxh_loaded_skin", "nxh_loaded_animation_count", "nxs_scene_set_skins", "nxs_scene_mesh_count", "nxs_scene_animation_count",
-    "nxs_scene_mesh_joint_count", "nxs_scene_joint_palette", "nxs_pathtracer_pose_mesh",
-]
-
-
-class NexusError(RuntimeError):
-    pass
+# every function include/nexus_hip.h and include/nexus_host.h declare, in their order, and {name: (restype, [argtypes])} of them all
+_TABLES = cabi.signatures()
+HIP_SYMBOLS = list(_TABLES["nexus_hip.h"])
+HOST_SYMBOLS = list(_TABLES["nexus_host.h"])
+SIGNATURES = {**_TABLES["nexus_hip.h"], **_TABLES["nexus_host.h"]}
 
 
 class QueueSizes(C.Structure):
@@ -134,17 +79,26 @@ def abi_stamp(words=None):
     return h
 
 
+def _declare(L, names):
+    """Give the functions `names` of the library the signatures their prototypes declare."""
+    for name in names:
+        try:
+            fn = getattr(L, name)
+        except AttributeError:
+            raise NexusError(f"{LIB_PATH} does not export {name}, which the headers declare: rebuild it with `make`") from None
+        fn.restype, fn.argtypes = SIGNATURES[name]
+
+
 def check_library(L, stamp=None):
     """Refuse a library that does not match these bindings — a stale build reached through NEXUS_AMD_LIB, a library linked
     from objects of different source states — with an error instead of a GPU fault in the first launch."""
     if not hasattr(L, "nxhip_check_library"):
         raise NexusError(f"{LIB_PATH} predates the ABI stamp (no nxhip_check_library): rebuild it with `make`")
-    L.nxhip_check_library.argtypes = [C.c_uint64]
-    L.nxhip_abi_stamp.restype = C.c_uint64
-    L.nxhip_last_error.restype = C.c_char_p
+    _declare(L, ("nxhip_check_library", "nxhip_abi_stamp", "nxhip_last_error"))
     rc = L.nxhip_check_library(abi_stamp() if stamp is None else stamp)
     if rc != 0:
         raise NexusError("%s: %s" % (LIB_PATH, (L.nxhip_last_error() or b"").decode()))
+
 
 _lib = None
 
@@ -158,162 +112,7 @@ def lib():
         raise NexusError(f"{LIB_PATH} is missing: build it with `make` (or __graft_entry__.build()); there is no fallback path")
     L = C.CDLL(LIB_PATH)
     check_library(L)
-    vp, u32, i32, f32 = C.c_void_p, C.c_uint32, C.c_int32, C.c_float
-    L.nxhip_last_error.restype = C.c_char_p
-    L.nxhip_create.argtypes = [C.c_int, u32, u32, vp, C.POINTER(vp)]
-    L.nxhip_destroy.argtypes = [vp]
-    L.nxhip_destroy.restype = None
-    L.nxhip_resize.argtypes = [vp, u32, u32]
-    L.nxhip_sync.argtypes = [vp]
-    L.nxhip_upload_blas.argtypes = [vp, vp, u32, vp, u32, vp, C.POINTER(i32)]
-    L.nxhip_clear_blas.argtypes = [vp]
-    L.nxhip_set_tlas.argtypes = [vp, vp, u32, vp, vp, u32]
-    L.nxhip_set_materials.argtypes = [vp, vp, u32]
-    L.nxhip_set_lights.argtypes = [vp, vp, u32]
-    L.nxhip_upload_texture.argtypes = [vp, C.c_int, vp, u32, u32, C.POINTER(i32)]
-    L.nxhip_clear_textures.argtypes = [vp]
-    L.nxhip_set_camera.argtypes = [vp, vp]
-    L.nxhip_set_render_settings.argtypes = [vp, vp]
-    L.nxhip_set_modes.argtypes = [vp, C.c_int, C.c_int, C.c_int]
-    L.nxhip_set_pixel_map.argtypes = [vp, vp, u32]
-    L.nxhip_reset_frame_number.argtypes = [vp]
-    L.nxhip_set_frame_number.argtypes = [vp, u32]
-    L.nxhip_frame_number.argtypes = [vp]
-    L.nxhip_frame_number.restype = u32
-    L.nxhip_render_frame.argtypes = [vp]
-    L.nxhip_accumulate.argtypes = [vp]
-    L.nxhip_render.argtypes = [vp, u32]
-    L.nxhip_read_radiance.argtypes = [vp, vp]
-    L.nxhip_read_accumulation.argtypes = [vp, vp]
-    L.nxhip_read_rgba8.argtypes = [vp, vp]
-    L.nxhip_write_accumulation.argtypes = [vp, vp, u32]
-    L.nxhip_radiance_device_ptr.argtypes = [vp]
-    L.nxhip_radiance_device_ptr.restype = vp
-    L.nxhip_accumulation_device_ptr.argtypes = [vp]
-    L.nxhip_accumulation_device_ptr.restype = vp
-    L.nxhip_accumulate_external.argtypes = [vp, vp, u32, u32, u32, u32, vp]
-    L.nxhip_compose_tiles.argtypes = [vp, vp, u32, vp, vp, vp]
-    L.nxhip_set_frames_per_pass.argtypes = [vp, u32]
-    L.nxhip_bind_radiance.argtypes = [vp, vp, u32]
-    L.nxhip_read_full_accumulation.argtypes = [vp, vp]
-    L.nxhip_read_full_rgba8.argtypes = [vp, vp]
-    L.nxhip_read_queue_sizes.argtypes = [vp, C.POINTER(QueueSizes)]
-    L.nxhip_read_material_queue_sizes.argtypes = [vp, C.c_int, vp]
-    L.nxhip_material_inputs_batch.argtypes = [vp, u32, vp, vp, u32, vp]
-    L.nxhip_set_pixel_query.argtypes = [vp, u32, u32]
-    L.nxhip_get_selected_instance.argtypes = [vp, C.POINTER(i32)]
-    L.nxhip_trace_batch.argtypes = [vp, vp, u32, vp]
-    L.nxhip_trace_shadow_batch.argtypes = [vp, vp, vp, u32, vp]
-    L.nxhip_bsdf_sample_batch.argtypes = [vp, vp, vp, u32, vp]
-    L.nxhip_bsdf_eval_batch.argtypes = [vp, vp, vp, u32, vp]
-    L.nxhip_tex2d_batch.argtypes = [vp, C.c_int, C.c_int, vp, u32, vp]
-    L.nxhip_fmath_batch.argtypes = [vp, C.c_int, vp, vp, u32, vp]
-    L.nxhip_enable_trace_stats.argtypes = [vp, C.c_int]
-    L.nxhip_read_trace_stats.argtypes = [vp, C.POINTER(TraceStats), C.POINTER(TraceStats), C.c_int]
-    L.nxhip_enable_kernel_timing.argtypes = [vp, C.c_int]
-    L.nxhip_read_kernel_times.argtypes = [vp, C.POINTER(KernelTimes), C.c_int]
-    L.nxhip_read_graph_timeline.argtypes = [vp, vp, vp, vp, u32, C.POINTER(u32)]
-    L.nxhip_set_instance_transforms.argtypes = [vp, vp, vp, u32]
-    L.nxhip_read_tlas.argtypes = [vp, vp, u32, vp, u32]
-    L.nxhip_update_blas.argtypes = [vp, i32, vp, u32]
-    L.nxhip_update_blas_device.argtypes = [vp, i32, vp, u32]
-    L.nxhip_set_blas_skin.argtypes = [vp, i32, vp, u32, u32]
-    L.nxhip_pose_blas.argtypes = [vp, i32, vp, u32]
-    L.nxhip_read_blas_triangles.argtypes = [vp, i32, vp, u32]
-    L.nxhip_read_blas_bounds.argtypes = [vp, i32, vp, vp]
-    L.nxhip_tile_pixel_map.argtypes = [u32, u32, C.c_int, C.c_int, u32, C.c_int, vp, C.POINTER(u32)]
-    L.nxhip_mgpu_unique_id.argtypes = [vp]
-    L.nxhip_mgpu_init.argtypes = [vp, C.c_int, C.c_int, vp, u32]
-    L.nxhip_mgpu_attach.argtypes = [vp, vp, C.c_int, C.c_int, u32]
-    L.nxhip_mgpu_gather.argtypes = [vp]
-    L.nxhip_mgpu_read_rgba8.argtypes = [vp, vp]
-    L.nxhip_mgpu_read_accumulation.argtypes = [vp, vp]
-    L.nxhip_mgpu_shutdown.argtypes = [vp]
-    L.nxhip_set_aov.argtypes = [vp, C.c_int]
-    for f in ("nxhip_read_aov", "nxhip_read_aov_frame", "nxhip_write_aov"):
-        getattr(L, f).argtypes = [vp, vp, vp]
-    L.nxhip_denoise.argtypes = [vp, vp]
-    L.nxhip_denoise_defaults.argtypes = [vp]
-    L.nxhip_read_denoised.argtypes = [vp, vp]
-    L.nxhip_read_denoised_rgba8.argtypes = [vp, vp]
-    L.nxhip_adaptive_defaults.argtypes = [vp]
-    L.nxhip_set_adaptive.argtypes = [vp, vp]
-    L.nxhip_adaptive_update.argtypes = [vp, C.POINTER(u32), C.POINTER(u32)]
-    L.nxhip_render_adaptive.argtypes = [vp, u32, u32, C.POINTER(u32), C.POINTER(u32)]
-    L.nxhip_read_sample_counts.argtypes = [vp, vp]
-    L.nxhip_read_noise_stats.argtypes = [vp, vp]
-    L.nxhip_read_block_noise.argtypes = [vp, vp, vp, u32, C.POINTER(u32)]
-    L.nxhip_read_active_map.argtypes = [vp, vp, u32, C.POINTER(u32)]
-    # host builders
-    L.nxh_bvh8_build.argtypes = [vp, u32, u32, C.POINTER(vp)]
-    L.nxh_tlas_build.argtypes = [vp, u32, C.POINTER(vp)]
-    L.nxh_tlas_refit.argtypes = [vp, u32, vp, vp, u32]
-    L.nxh_bvh8_refit.argtypes = [vp, u32, vp, vp, u32]
-    L.nxh_bvh8_node_count.argtypes = [vp]
-    L.nxh_bvh8_node_count.restype = u32
-    L.nxh_bvh8_prim_count.argtypes = [vp]
-    L.nxh_bvh8_prim_count.restype = u32
-    L.nxh_bvh8_nodes.argtypes = [vp]
-    L.nxh_bvh8_nodes.restype = vp
-    L.nxh_bvh8_prim_indices.argtypes = [vp]
-    L.nxh_bvh8_prim_indices.restype = vp
-    L.nxh_bvh8_free.argtypes = [vp]
-    L.nxh_bvh8_free.restype = None
-    L.nxh_bvh2_build.argtypes = [vp, u32, u32, vp, vp]
-    L.nxh_mat4_from_trs.argtypes = [vp, vp, vp, vp]
-    L.nxh_mat4_from_trs.restype = None
-    L.nxh_mat4_invert.argtypes = [vp, vp]
-    L.nxh_mat4_invert.restype = None
-    L.nxh_instance_init.argtypes = [vp, u32, i32, vp, vp]
-    L.nxh_camera_init.argtypes = [vp, vp, vp, f32, u32, u32, f32, f32]
-    L.nxh_load_scene_file.argtypes = [C.c_char_p, C.POINTER(vp)]
-    L.nxh_load_scene_file_ex.argtypes = [C.c_char_p, u32, C.POINTER(vp)]
-    L.nxh_loaded_scene_free.argtypes = [vp]
-    L.nxh_loaded_scene_free.restype = None
-    for f in ("nxh_loaded_mesh_count", "nxh_loaded_material_count", "nxh_loaded_instance_count"):
-        getattr(L, f).argtypes = [vp]
-        getattr(L, f).restype = u32
-    L.nxh_loaded_mesh_triangle_count.argtypes = [vp, u32]
-    L.nxh_loaded_mesh_triangle_count.restype = u32
-    L.nxh_loaded_mesh_triangles.argtypes = [vp, u32, vp]
-    L.nxh_loaded_materials.argtypes = [vp, vp]
-    L.nxh_loaded_instances.argtypes = [vp, vp]
-    L.nxs_scene_load_file.argtypes = [vp, C.c_char_p, C.c_char_p]
-    L.nxs_scene_set_metal_rough.argtypes = [vp, C.c_int]
-    L.nxs_scene_set_instance_transform.argtypes = [vp, u32, vp, vp, vp]
-    L.nxs_scene_set_tlas_refit.argtypes = [vp, C.c_int]
-    L.nxs_scene_update_mesh.argtypes = [vp, u32, vp, u32]
-    # Scene / PathTracer facade
-    L.nxs_last_error.restype = C.c_char_p
-    L.nxs_scene_create.argtypes = [u32, u32, C.POINTER(vp)]
-    L.nxs_scene_destroy.argtypes = [vp]
-    L.nxs_scene_destroy.restype = None
-    L.nxs_scene_add_material.argtypes = [vp, vp, C.POINTER(i32)]
-    L.nxs_scene_add_texture.argtypes = [vp, C.c_int, vp, u32, u32, C.POINTER(i32)]
-    L.nxs_scene_set_hdr_map.argtypes = [vp, vp, u32, u32]
-    L.nxs_scene_add_mesh.argtypes = [vp, vp, u32, i32, C.POINTER(i32)]
-    L.nxs_scene_create_instance.argtypes = [vp, u32, i32, vp, vp, vp, C.POINTER(i32)]
-    L.nxs_scene_set_camera.argtypes = [vp, vp, vp, f32, f32, f32]
-    L.nxs_scene_set_render_settings.argtypes = [vp, vp]
-    L.nxs_scene_update.argtypes = [vp]
-    L.nxs_scene_light_count.argtypes = [vp]
-    L.nxs_scene_light_count.restype = u32
-    L.nxs_scene_instance_count.argtypes = [vp]
-    L.nxs_scene_instance_count.restype = u32
-    L.nxs_pathtracer_create.argtypes = [u32, u32, C.c_int, C.POINTER(vp)]
-    L.nxs_pathtracer_destroy.argtypes = [vp]
-    L.nxs_pathtracer_destroy.restype = None
-    L.nxs_pathtracer_set_modes.argtypes = [vp, C.c_int, C.c_int, C.c_int]
-    L.nxs_pathtracer_set_frames_per_pass.argtypes = [vp, C.c_uint32]
-    L.nxs_pathtracer_set_passes_in_flight.argtypes = [vp, C.c_uint32]
-    L.nxs_pathtracer_update_device_scene.argtypes = [vp, vp]
-    L.nxs_pathtracer_render.argtypes = [vp, vp]
-    L.nxs_pathtracer_reset_frame_number.argtypes = [vp]
-    L.nxs_pathtracer_frame_number.argtypes = [vp]
-    L.nxs_pathtracer_frame_number.restype = u32
-    L.nxs_pathtracer_read_pixels.argtypes = [vp, vp]
-    L.nxs_pathtracer_device_context.argtypes = [vp]
-    L.nxs_pathtracer_device_context.restype = vp
+    _declare(L, SIGNATURES)
     _lib = L
     return L
 
@@ -479,7 +278,6 @@ def load_scene_material_alpha(path, alpha_modes=True):
     if L.nxh_load_scene_file_ex(str(path).encode(), LOAD_ALPHA_MODES if alpha_modes else 0, C.byref(h)) != 0:
         raise NexusError("nxh_load_scene_file_ex: " + L.nxs_last_error().decode())
     try:
-        L.nxh_loaded_material_alpha.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
         n = C.c_uint32(0)
         if L.nxh_loaded_material_alpha(h, None, 0, C.byref(n)) != 0:
             raise NexusError(L.nxs_last_error().decode())
@@ -502,9 +300,6 @@ def load_scene_skins(path, skins=True):
     if L.nxh_load_scene_file_ex(str(path).encode(), LOAD_SKINS if skins else 0, C.byref(h)) != 0:
         raise NexusError("nxh_load_scene_file_ex: " + L.nxs_last_error().decode())
     try:
-        L.nxh_loaded_skin.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
-        L.nxh_loaded_animation_count.argtypes = [C.c_void_p]
-        L.nxh_loaded_animation_count.restype = C.c_uint32
         corners, joints = [], []
         for m in range(L.nxh_loaded_mesh_count(h)):
             n, j = C.c_uint32(0), C.c_uint32(0)
@@ -515,10 +310,6 @@ def load_scene_skins(path, skins=True):
                 raise NexusError(L.nxs_last_error().decode())
             corners.append(out)
             joints.append(int(j.value))
-        L.nxh_loaded_warning_count.argtypes = [C.c_void_p]
-        L.nxh_loaded_warning_count.restype = C.c_uint32
-        L.nxh_loaded_warning.argtypes = [C.c_void_p, C.c_uint32]
-        L.nxh_loaded_warning.restype = C.c_char_p
         warnings = [L.nxh_loaded_warning(h, i).decode() for i in range(L.nxh_loaded_warning_count(h))]
         animations = int(L.nxh_loaded_animation_count(h))
     finally:
@@ -533,9 +324,6 @@ def load_scene_analytic_lights(path):
     if L.nxh_load_scene_file(str(path).encode(), C.byref(h)) != 0:
         raise NexusError("nxh_load_scene_file: " + L.nxs_last_error().decode())
     try:
-        L.nxh_loaded_analytic_light_count.argtypes = [C.c_void_p]
-        L.nxh_loaded_analytic_light_count.restype = C.c_uint32
-        L.nxh_loaded_analytic_lights.argtypes = [C.c_void_p, C.c_void_p]
         lights = np.zeros(L.nxh_loaded_analytic_light_count(h), dtype=pod.ALIGHT_DT)
         if len(lights) and L.nxh_loaded_analytic_lights(h, _ptr(lights)) != 0:
             raise NexusError(L.nxs_last_error().decode())
@@ -552,14 +340,6 @@ def load_scene_detail(path):
     if L.nxh_load_scene_file(str(path).encode(), C.byref(h)) != 0:
         raise NexusError("nxh_load_scene_file: " + L.nxs_last_error().decode())
     try:
-        L.nxh_loaded_detail_texture_count.argtypes = [C.c_void_p]
-        L.nxh_loaded_detail_texture_info.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_int32)]
-        L.nxh_loaded_detail_texture_pixels.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
-        L.nxh_loaded_material_detail.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.nxh_loaded_material_count.argtypes = [C.c_void_p]
-        L.nxh_loaded_warning_count.argtypes = [C.c_void_p]
-        L.nxh_loaded_warning.argtypes = [C.c_void_p, C.c_uint32]
-        L.nxh_loaded_warning.restype = C.c_char_p
         textures = []
         for i in range(L.nxh_loaded_detail_texture_count(h)):
             w, hh, kind = C.c_uint32(), C.c_uint32(), C.c_int32()
@@ -587,13 +367,6 @@ def load_scene_textures(path):
     if L.nxh_load_scene_file(str(path).encode(), C.byref(h)) != 0:
         raise NexusError("nxh_load_scene_file: " + L.nxs_last_error().decode())
     try:
-        L.nxh_loaded_texture_count.argtypes = [C.c_void_p]
-        L.nxh_loaded_texture_info.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_int32)]
-        L.nxh_loaded_texture_pixels.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
-        L.nxh_loaded_material_textures.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-        L.nxh_loaded_warning_count.argtypes = [C.c_void_p]
-        L.nxh_loaded_warning.argtypes = [C.c_void_p, C.c_uint32]
-        L.nxh_loaded_warning.restype = C.c_char_p
         texs = []
         for i in range(L.nxh_loaded_texture_count(h)):
             w, hh, k = C.c_uint32(0), C.c_uint32(0), C.c_int32(0)
@@ -616,7 +389,6 @@ def load_scene_textures(path):
 def decode_png(data):
     """nexus::IMGLoader::LoadIMG through the C-ABI: (HxWx4 uint8, channels of the file)"""
     L = lib()
-    L.nxh_decode_png.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_void_p, C.c_size_t]
     buf = np.frombuffer(bytes(data), dtype=np.uint8).copy()
     w, h, ch = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
     if L.nxh_decode_png(_ptr(buf), len(buf), C.byref(w), C.byref(h), C.byref(ch), None, 0) != 0:
@@ -630,7 +402,6 @@ def decode_png(data):
 def decode_npy_grid(data):
     """IMGLoader::LoadNPYGrid on a .npy file in memory: the fog density grid it holds, float32 of shape (nz, ny, nx)."""
     L = lib()
-    L.nxh_decode_npy_grid.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t]
     buf = np.frombuffer(bytes(data), dtype=np.uint8)
     dims = (C.c_uint32 * 3)()
     if L.nxh_decode_npy_grid(_ptr(buf), len(buf), dims, None, 0) != 0:
@@ -644,7 +415,6 @@ def decode_npy_grid(data):
 def decode_hdr_float(data):
     """IMGLoader::LoadHDRFloat on a Radiance .hdr file in memory: HxWx3 float32 of linear radiance."""
     L = lib()
-    L.nxh_decode_hdr_float.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_void_p, C.c_size_t]
     buf = np.frombuffer(bytes(data), dtype=np.uint8).copy()
     w, h = C.c_uint32(0), C.c_uint32(0)
     if L.nxh_decode_hdr_float(_ptr(buf), len(buf), C.byref(w), C.byref(h), None, 0) != 0:
@@ -734,27 +504,23 @@ class Context:
         """point, sphere, spot and sun lights (pod.ALIGHT_DT records, pod.make_analytic_light); an empty list removes them
         (nxhip_set_analytic_lights: the sampling rule is in include/nexus_hip.h)"""
         lights = np.ascontiguousarray(lights, dtype=pod.ALIGHT_DT).reshape(-1)
-        self.L.nxhip_set_analytic_lights.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
         check(self.L.nxhip_set_analytic_lights(self.h, _ptr(lights) if len(lights) else None, len(lights)), "nxhip_set_analytic_lights")
 
     def set_material_alpha(self, alphas):
         """how the materials' alpha is read: pod.ALPHA_DT records (pod.make_material_alpha), one per material of the table; an empty
         list removes the table: every material is a stochastic blend again (nxhip_set_material_alpha: the rule is in include/nexus_hip.h)"""
         alphas = np.ascontiguousarray(alphas, dtype=pod.ALPHA_DT)
-        self.L.nxhip_set_material_alpha.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
         check(self.L.nxhip_set_material_alpha(self.h, _ptr(alphas) if len(alphas) else None, len(alphas)), "nxhip_set_material_alpha")
 
     def set_material_detail(self, details):
         """the materials' detail maps: pod.DETAIL_DT records (pod.make_material_detail), one per material of the table; an empty list
         removes the table (nxhip_set_material_detail: the shading rule is in include/nexus_hip.h)"""
         details = np.ascontiguousarray(details, dtype=pod.DETAIL_DT).reshape(-1)
-        self.L.nxhip_set_material_detail.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
         check(self.L.nxhip_set_material_detail(self.h, _ptr(details) if len(details) else None, len(details)), "nxhip_set_material_detail")
 
     def set_medium(self, medium):
         """fog: one homogeneous medium in a world-space box (a pod.MEDIUM_DT record, pod.make_medium); None removes it
         (nxhip_set_medium: the rule is in include/nexus_hip.h)"""
-        self.L.nxhip_set_medium.argtypes = [C.c_void_p, C.c_void_p]
         if medium is None:
             check(self.L.nxhip_set_medium(self.h, None), "nxhip_set_medium")
             return
@@ -764,7 +530,6 @@ class Context:
     def set_medium_density(self, rho):
         """fog density grid: a float32 array of shape (nz, ny, nx) over the medium's box — the extinction at p becomes sigmaT x rho(p), a
         trilinear lookup; None removes it (nxhip_set_medium_density: the rule is in include/nexus_hip.h)"""
-        self.L.nxhip_set_medium_density.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]
         if rho is None:
             check(self.L.nxhip_set_medium_density(self.h, None, 0, 0, 0), "nxhip_set_medium_density")
             return
@@ -776,7 +541,6 @@ class Context:
     def read_medium_majorants(self):
         """the majorant bricks the device built from the density grid — a test hook: float32[nbz, nby, nbx]"""
         nb = (C.c_uint32 * 3)()
-        self.L.nxhip_read_medium_majorants.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
         check(self.L.nxhip_read_medium_majorants(self.h, None, 0, nb), "nxhip_read_medium_majorants")
         out = np.zeros((nb[2], nb[1], nb[0]), dtype=np.float32)
         check(self.L.nxhip_read_medium_majorants(self.h, _ptr(out), out.size, nb), "nxhip_read_medium_majorants")
@@ -787,7 +551,6 @@ class Context:
         (rho float32[n], majorant float32[n])"""
         p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
         rho, maj = np.zeros(len(p), dtype=np.float32), np.zeros(len(p), dtype=np.float32)
-        self.L.nxhip_medium_density_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
         check(self.L.nxhip_medium_density_batch(self.h, _ptr(p), len(p), _ptr(rho), _ptr(maj)), "nxhip_medium_density_batch")
         return rho, maj
 
@@ -802,7 +565,6 @@ class Context:
         assert len(o) == len(d) == len(te) == len(sd)
         st, tr = np.zeros(len(o), dtype=np.float32), np.zeros(len(o), dtype=np.float32)
         steps = np.zeros((len(o), 2), dtype=np.uint32)
-        self.L.nxhip_medium_track_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         check(self.L.nxhip_medium_track_batch(self.h, _ptr(o), _ptr(d), _ptr(te), _ptr(sd), len(o), _ptr(st), _ptr(tr), _ptr(steps)), "nxhip_medium_track_batch")
         return st, tr, steps
 
@@ -816,7 +578,6 @@ class Context:
         x = np.ascontiguousarray(xi, dtype=np.float32).reshape(-1)
         assert len(o) == len(d) == len(te) == len(x)
         out = [np.zeros(len(o), dtype=np.float32) for _ in range(4)]
-        self.L.nxhip_medium_segment_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         check(self.L.nxhip_medium_segment_batch(self.h, _ptr(o), _ptr(d), _ptr(te), _ptr(x), len(o), *[_ptr(a) for a in out]), "nxhip_medium_segment_batch")
         return tuple(out)
 
@@ -829,7 +590,6 @@ class Context:
         assert len(d) == len(a) == len(b)
         out = np.zeros((len(d), 3), dtype=np.float32)
         pdf = np.zeros(len(d), dtype=np.float32)
-        self.L.nxhip_medium_phase_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
         check(self.L.nxhip_medium_phase_batch(self.h, _ptr(d), _ptr(a), _ptr(b), len(d), _ptr(out), _ptr(pdf)), "nxhip_medium_phase_batch")
         return out, pdf
 
@@ -843,7 +603,6 @@ class Context:
         normal = np.zeros((len(t), 3), dtype=np.float32)
         roughness = np.zeros(len(t), dtype=np.float32)
         fell = np.zeros(len(t), dtype=np.uint32)
-        self.L.nxhip_shading_frame_batch.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         check(self.L.nxhip_shading_frame_batch(self.h, int(instance), _ptr(t), _ptr(uv), _ptr(d), len(t), _ptr(normal), _ptr(roughness), _ptr(fell)),
               "nxhip_shading_frame_batch")
         return normal, roughness, fell != 0
@@ -868,7 +627,6 @@ class Context:
         tmax = np.zeros(len(o), dtype=np.float32)
         factor = np.zeros((len(o), 3), dtype=np.float32)
         ok = np.zeros(len(o), dtype=np.uint32)
-        self.L.nxhip_analytic_light_sample_batch.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         check(self.L.nxhip_analytic_light_sample_batch(self.h, int(light_index), _ptr(o), _ptr(r), len(o), _ptr(direction), _ptr(tmax), _ptr(factor), _ptr(ok)),
               "nxhip_analytic_light_sample_batch")
         return direction, tmax, factor, ok != 0
@@ -885,12 +643,10 @@ class Context:
         """the environment map as linear float radiance: H x W x 3 float32, row 0 the top row (nxhip_upload_env_float)"""
         img = np.ascontiguousarray(rgb, dtype=np.float32)
         assert img.ndim == 3 and img.shape[2] == 3
-        self.L.nxhip_upload_env_float.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
         check(self.L.nxhip_upload_env_float(self.h, _ptr(img), img.shape[1], img.shape[0]), "nxhip_upload_env_float")
 
     def read_env_float(self):
         """the float environment map as it is stored: H x W x 3 float32"""
-        self.L.nxhip_read_env_float.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         w, h = C.c_uint32(0), C.c_uint32(0)
         check(self.L.nxhip_read_env_float(self.h, None, 0, C.byref(w), C.byref(h)), "nxhip_read_env_float")
         out = np.zeros((h.value, w.value, 3), dtype=np.float32)
@@ -899,11 +655,9 @@ class Context:
 
     def read_env_guides(self):
         """the cut points of the environment sampler's cdf inversion: (marginal uint32[65], rows uint32[H, 65])"""
-        self.L.nxhip_read_env_tables.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         w, h = C.c_uint32(0), C.c_uint32(0)
         check(self.L.nxhip_read_env_tables(self.h, None, None, None, 0, C.byref(w), C.byref(h)), "nxhip_read_env_tables")
         marginal, rows = np.zeros(65, np.uint32), np.zeros((h.value, 65), np.uint32)
-        self.L.nxhip_read_env_guides.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
         check(self.L.nxhip_read_env_guides(self.h, _ptr(marginal), _ptr(rows), h.value), "nxhip_read_env_guides")
         return marginal, rows
 
@@ -932,7 +686,6 @@ class Context:
 
     def set_pixel_order(self, order):
         """nxhip_set_pixel_order: ORDER_ROWS (0, the reference's) or ORDER_TILES (1: 8 x 8 pixel tiles) over the full frame"""
-        self.L.nxhip_set_pixel_order.argtypes = [C.c_void_p, C.c_int]
         check(self.L.nxhip_set_pixel_order(self.h, int(order)), "nxhip_set_pixel_order")
         self.local_count = self.width * self.height
 
@@ -940,7 +693,6 @@ class Context:
         """BLAS built on the device (binned SAH + SAH-DP collapse by default, see set_device_builder); returns the BLAS id"""
         t = np.ascontiguousarray(tris, dtype=pod.TRI_DT)
         bid = C.c_int32(-1)
-        self.L.nxhip_build_blas.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_int32)]
         check(self.L.nxhip_build_blas(self.h, _ptr(t), len(t), C.byref(bid)), "nxhip_build_blas")
         return int(bid.value)
 
@@ -950,14 +702,12 @@ class Context:
         ptrs = (C.c_void_p * len(arrays))(*[a.ctypes.data for a in arrays])
         counts = np.array([len(a) for a in arrays], dtype=np.uint32)
         ids = np.full(len(arrays), -1, dtype=np.int32)
-        self.L.nxhip_build_blas_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
         check(self.L.nxhip_build_blas_batch(self.h, ptrs, _ptr(counts), len(arrays), _ptr(ids)), "nxhip_build_blas_batch")
         return [int(i) for i in ids]
 
     def read_blas_batch(self, first_id, tri_counts):
         """nodes and primitive index lists of consecutive BLAS ids: [(nodes, idx), ...]"""
         count = len(tri_counts)
-        self.L.nxhip_read_blas_batch.argtypes = [C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32]
         node_counts = np.zeros(count, dtype=np.uint32)
         check(self.L.nxhip_read_blas_batch(self.h, first_id, count, None, 0, _ptr(node_counts), None, 0), "nxhip_read_blas_batch")
         nodes = np.zeros(int(node_counts.sum()), dtype=pod.NODE_DT)
@@ -971,7 +721,6 @@ class Context:
         return out
 
     def read_blas(self, blas_id, tri_count):
-        self.L.nxhip_read_blas.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
         n = C.c_uint32(0)
         check(self.L.nxhip_read_blas(self.h, blas_id, None, 0, None, 0, C.byref(n)), "nxhip_read_blas")
         nodes = np.zeros(n.value, dtype=pod.NODE_DT)
@@ -991,9 +740,7 @@ class Context:
     def rebuild_tlas(self, instances):
         """build the TLAS on the device (the BLAS builder over the instances' boxes) and install it; returns (nodes, instance index list)"""
         instances = np.ascontiguousarray(instances, dtype=pod.INST_DT)
-        self.L.nxhip_rebuild_tlas.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
         check(self.L.nxhip_rebuild_tlas(self.h, _ptr(instances), len(instances)), "nxhip_rebuild_tlas")
-        self.L.nxhip_read_tlas_index.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
         n = C.c_uint32(0)
         idx = np.zeros(len(instances), dtype=np.uint32)
         check(self.L.nxhip_read_tlas_index(self.h, _ptr(idx), len(idx), C.byref(n)), "nxhip_read_tlas_index")
@@ -1003,12 +750,10 @@ class Context:
     def debug_write_blas_node(self, blas_id, node_idx, node):
         """test hook: overwrite one node of an uploaded BLAS without the upload checks"""
         node = np.ascontiguousarray(node, dtype=pod.NODE_DT).reshape(1)
-        self.L.nxhip_debug_write_blas_node.argtypes = [C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p]
         check(self.L.nxhip_debug_write_blas_node(self.h, blas_id, node_idx, _ptr(node)), "nxhip_debug_write_blas_node")
 
     def debug_set_scan_epoch(self, epoch):
         """test hook: passes begun since the ordered compaction's status words were last cleared (wraps at 2^20)"""
-        self.L.nxhip_debug_set_scan_epoch.argtypes = [C.c_void_p, C.c_uint32]
         check(self.L.nxhip_debug_set_scan_epoch(self.h, int(epoch)), "nxhip_debug_set_scan_epoch")
 
     def set_instance_transforms(self, instance_ids, transforms16):
@@ -1120,12 +865,10 @@ class Context:
                                          C.c_void_p(dst_accum_dev_ptr), C.c_void_p(dst_rgba8_dev_ptr) if dst_rgba8_dev_ptr else None), "nxhip_compose_tiles")
 
     def set_env_sampling(self, on=True):
-        self.L.nxhip_set_env_sampling.argtypes = [C.c_void_p, C.c_int]
         check(self.L.nxhip_set_env_sampling(self.h, 1 if on else 0), "nxhip_set_env_sampling")
 
     def read_env_tables(self):
         """the environment sampler's tables as uploaded: (marginalCdf float32[H], rowCdf float32[H, W], density float32[H, W])"""
-        self.L.nxhip_read_env_tables.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         w, h = C.c_uint32(0), C.c_uint32(0)
         check(self.L.nxhip_read_env_tables(self.h, None, None, None, 0, C.byref(w), C.byref(h)), "nxhip_read_env_tables")
         n = w.value * h.value
@@ -1140,7 +883,6 @@ class Context:
         direction = np.zeros((len(r), 3), dtype=np.float32)
         pdf = np.zeros(len(r), dtype=np.float32)
         texel = np.zeros(len(r), dtype=np.uint32)
-        self.L.nxhip_env_sample_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         check(self.L.nxhip_env_sample_batch(self.h, _ptr(r), len(r), _ptr(direction), _ptr(pdf), _ptr(texel)), "nxhip_env_sample_batch")
         return direction, pdf, texel
 
@@ -1151,26 +893,22 @@ class Context:
         rgb = np.zeros((len(d), 3), dtype=np.float32)
         pdf = np.zeros(len(d), dtype=np.float32) if with_pdf else None
         texel = np.zeros(len(d), dtype=np.uint32) if with_pdf else None
-        self.L.nxhip_env_eval_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         check(self.L.nxhip_env_eval_batch(self.h, _ptr(d), len(d), _ptr(rgb), _ptr(pdf) if with_pdf else None, _ptr(texel) if with_pdf else None), "nxhip_env_eval_batch")
         return rgb, pdf, texel
 
     def set_light_sampling(self, mode):
         """LIGHTS_UNIFORM (0, the reference's rule) or LIGHTS_POWER (1): the light sample picks among the mesh lights' triangles in
         proportion to area x emitted luminance, from a table built on the device (include/nexus_hip.h)"""
-        self.L.nxhip_set_light_sampling.argtypes = [C.c_void_p, C.c_int]
         check(self.L.nxhip_set_light_sampling(self.h, int(mode)), "nxhip_set_light_sampling")
 
     def set_shadow_transmittance(self, mode):
         """SHADOWS_OPAQUE (0, the reference's rule: a shadow ray ends at the first triangle) or SHADOWS_TRANSMIT (1): every crossing
         multiplies the ray's transmittance by 1 - opacity x alpha(uv) (nxhip_set_shadow_transmittance; deterministic, same expectation as
         the paths' own pass-through)"""
-        self.L.nxhip_set_shadow_transmittance.argtypes = [C.c_void_p, C.c_int]
         check(self.L.nxhip_set_shadow_transmittance(self.h, int(mode)), "nxhip_set_shadow_transmittance")
 
     def read_light_table(self, light_count):
         """the light table of LIGHTS_POWER (brought up to date first): (cdf float32[N], entryLight uint32[N], lightBase uint32[light_count + 1])"""
-        self.L.nxhip_read_light_table.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32)]
         n = C.c_uint32(0)
         base = np.zeros(int(light_count) + 1, dtype=np.uint32)
         check(self.L.nxhip_read_light_table(self.h, None, None, 0, _ptr(base), C.byref(n)), "nxhip_read_light_table")
@@ -1185,61 +923,51 @@ class Context:
         u = np.ascontiguousarray(u, dtype=np.float32)
         entry = np.zeros(len(u), dtype=np.uint32)
         prob = np.zeros(len(u), dtype=np.float32)
-        self.L.nxhip_light_pick_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
         check(self.L.nxhip_light_pick_batch(self.h, _ptr(u), len(u), _ptr(entry), _ptr(prob)), "nxhip_light_pick_batch")
         return entry, prob
 
     def set_entry_points(self, on=True):
         """primary rays start from the state their run's first node steps provably share (include/nexus_hip.h)"""
-        self.L.nxhip_set_entry_points.argtypes = [C.c_void_p, C.c_int]
         check(self.L.nxhip_set_entry_points(self.h, 1 if on else 0), "nxhip_set_entry_points")
 
     def debug_thin_counts_of_pass(self, bounce):
         """rays the trace launches of level `bounce` of the last pass handed to the thin kernel: (closest-hit, any-hit)"""
         c = (C.c_int32 * 2)()
-        self.L.nxhip_debug_thin_counts_of_pass.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
         check(self.L.nxhip_debug_thin_counts_of_pass(self.h, bounce, c), "nxhip_debug_thin_counts_of_pass")
         return int(c[0]), int(c[1])
 
     def debug_ended_rays_of_pass(self, bounce):
         """continuation rays the material launch of `bounce` of the last pass did not queue: their roulette draw was lost already (include/nexus_hip.h)"""
         n = C.c_int32(0)
-        self.L.nxhip_debug_ended_rays_of_pass.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_int32)]
         check(self.L.nxhip_debug_ended_rays_of_pass(self.h, bounce, C.byref(n)), "nxhip_debug_ended_rays_of_pass")
         return int(n.value)
 
     def debug_set_requeue(self, on=True):
         """test hook: the trace kernels hand the same rays out again and again (include/nexus_hip.h)"""
-        self.L.nxhip_debug_set_requeue.argtypes = [C.c_void_p, C.c_int]
         check(self.L.nxhip_debug_set_requeue(self.h, 1 if on else 0), "nxhip_debug_set_requeue")
 
     def sync_timeout(self, timeout_ms):
         """nxhip_sync with a wall-clock limit; raises NexusError (code NXHIP_ERR_TIMEOUT = 6, the context is dead afterwards) when it expires"""
-        self.L.nxhip_sync_timeout.argtypes = [C.c_void_p, C.c_uint32]
         check(self.L.nxhip_sync_timeout(self.h, int(timeout_ms)), "nxhip_sync_timeout")
 
     def debug_set_thin(self, lanes=16, iters=16, in_hooks=False, any_time=False):
         """the thin kernel's hand-over rule, and whether the ray-batch hooks use it too (a test hook: include/nexus_hip.h);
         any_time: hand over after `iters` iterations of every stretch between two refill points, dry queue or not"""
-        self.L.nxhip_debug_set_thin.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int]
         check(self.L.nxhip_debug_set_thin(self.h, lanes, iters, (1 if in_hooks else 0) | (2 if any_time else 0)), "nxhip_debug_set_thin")
 
     def debug_set_thin_pool(self, slots=0):
         """how many items a thin wave's pool may hold before a round puts items back (0: the product's limit; a test hook)"""
-        self.L.nxhip_debug_set_thin_pool.argtypes = [C.c_void_p, C.c_uint32]
         check(self.L.nxhip_debug_set_thin_pool(self.h, int(slots)), "nxhip_debug_set_thin_pool")
 
     def debug_thin_counts(self):
         """rays the last ray-batch hook call handed to the thin kernel: (closest-hit, any-hit)"""
         out = (C.c_int32 * 2)()
-        self.L.nxhip_debug_thin_counts.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
         check(self.L.nxhip_debug_thin_counts(self.h, out), "nxhip_debug_thin_counts")
         return int(out[0]), int(out[1])
 
     def debug_entry_walks(self):
         """entry-state walks the context has launched since it was created (include/nexus_hip.h): a table is reused until an input changes"""
         n = C.c_uint64(0)
-        self.L.nxhip_debug_entry_walks.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
         check(self.L.nxhip_debug_entry_walks(self.h, C.byref(n)), "nxhip_debug_entry_walks")
         return int(n.value)
 
@@ -1247,7 +975,6 @@ class Context:
         """the primary rays of the last pass as the generate kernel left them, in path order (path k = slice x local_count + local pixel):
         (origin float32[n, 3], direction float32[n, 3], path_index uint32[n]) — a test hook: include/nexus_hip.h.  Needs pathLength 1 and one
         pass in flight; `capacity`: the size of the arrays handed over (None: the pass's own path count)."""
-        self.L.nxhip_debug_read_primary_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
         n = C.c_uint32(0)
         if capacity is None:
             rc = self.L.nxhip_debug_read_primary_rays(self.h, None, None, None, 0, C.byref(n))
@@ -1265,7 +992,6 @@ class Context:
         map-free material launch); force_general: the bits whose specialised instances later passes must not use (None: unchanged) —
         a test hook: include/nexus_hip.h"""
         f = C.c_uint32(0)
-        self.L.nxhip_debug_pass_flavor.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
         check(self.L.nxhip_debug_pass_flavor(self.h, 0xffffffff if force_general is None else int(force_general), C.byref(f)), "nxhip_debug_pass_flavor")
         return int(f.value)
 
@@ -1273,7 +999,6 @@ class Context:
         """(runs, 40) int32: the entry states of the last pass; column 19 = node steps saved, 16 = stack entries, 18 = instance record,
         31 = instance record of the triangle the walk consumed (-1: none), 35 = triangles it skipped, 38 / 39 = the run's hit-distance
         bounds after the consumed triangle (float32 bits)"""
-        self.L.nxhip_read_entry_states.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
         n = C.c_uint32(0)
         check(self.L.nxhip_read_entry_states(self.h, None, 0, C.byref(n)), "nxhip_read_entry_states")
         out = np.zeros((n.value, 40), np.int32)
@@ -1285,30 +1010,25 @@ class Context:
 
     def set_tail_bounce(self, bounce):
         """0 = off, 2 .. pathLength = from that bounce on, Context.TAIL_AUTO = the default rule (include/nexus_hip.h)"""
-        self.L.nxhip_set_tail_bounce.argtypes = [C.c_void_p, C.c_uint32]
         check(self.L.nxhip_set_tail_bounce(self.h, bounce), "nxhip_set_tail_bounce")
 
     def set_passes_in_flight(self, passes):
-        self.L.nxhip_set_passes_in_flight.argtypes = [C.c_void_p, C.c_uint32]
         check(self.L.nxhip_set_passes_in_flight(self.h, passes), "nxhip_set_passes_in_flight")
 
     def set_queue_budget(self, queues):
         """hardware queues the library may count on when it shapes R passes in flight: 0 = read GPU_MAX_HW_QUEUES again (else 4),
         1 .. 32 = this many (include/nexus_hip.h)"""
-        self.L.nxhip_set_queue_budget.argtypes = [C.c_void_p, C.c_int]
         check(self.L.nxhip_set_queue_budget(self.h, int(queues)), "nxhip_set_queue_budget")
 
     def queue_budget(self):
         """(budget, chained, graph_instances): the resolved budget, whether a pass issued now replays the chain shape, the largest
         number of pass-graph instances a slot holds"""
-        self.L.nxhip_get_queue_budget.argtypes = [C.c_void_p] + [C.POINTER(C.c_uint32)] * 3
         q, ch, g = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
         check(self.L.nxhip_get_queue_budget(self.h, C.byref(q), C.byref(ch), C.byref(g)), "nxhip_get_queue_budget")
         return int(q.value), bool(ch.value), int(g.value)
 
     def debug_last_graph(self):
         """(nodes, edges, fan_out) of the pass graph the last pass replayed, as the runtime holds it; fan_out 1: a chain (a test hook)"""
-        self.L.nxhip_debug_last_graph.argtypes = [C.c_void_p] + [C.POINTER(C.c_uint32)] * 3
         n, e, f = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
         check(self.L.nxhip_debug_last_graph(self.h, C.byref(n), C.byref(e), C.byref(f)), "nxhip_debug_last_graph")
         return int(n.value), int(e.value), int(f.value)
@@ -1516,7 +1236,6 @@ class Context:
         rays = np.ascontiguousarray(rays, dtype=pod.RAY_DT)
         tmax = np.ascontiguousarray(tmax, dtype=np.float32)
         out = np.zeros(len(rays), dtype=np.float32)
-        self.L.nxhip_trace_transmittance_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
         check(self.L.nxhip_trace_transmittance_batch(self.h, _ptr(rays), _ptr(tmax), len(rays), _ptr(out)), "nxhip_trace_transmittance_batch")
         return out
 
@@ -1616,8 +1335,6 @@ def device_count():
 def queue_budget_from_text(text):
     """nxhip_queue_budget_from_text: the queue budget a value of GPU_MAX_HW_QUEUES resolves to (None: not set); no device needed"""
     L = lib()
-    L.nxhip_queue_budget_from_text.argtypes = [C.c_char_p]
-    L.nxhip_queue_budget_from_text.restype = C.c_uint32
     return int(L.nxhip_queue_budget_from_text(None if text is None else str(text).encode()))
 
 
@@ -1669,12 +1386,10 @@ class Scene:
     def set_hdr_map_float(self, rgb):
         """Scene::AddHDRMapFloat: H x W x 3 float32 of linear radiance"""
         img = np.ascontiguousarray(rgb, dtype=np.float32)
-        self.L.nxs_scene_set_hdr_map_float.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
         _scheck(self.L.nxs_scene_set_hdr_map_float(self.h, _ptr(img), img.shape[1], img.shape[0]), "nxs_scene_set_hdr_map_float")
 
     def add_hdr_map_file_float(self, path, file_name):
         """Scene::AddHDRMapFloat(filePath, fileName): a Radiance .hdr file as linear float radiance"""
-        self.L.nxs_scene_add_hdr_map_file_float.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p]
         _scheck(self.L.nxs_scene_add_hdr_map_file_float(self.h, path.encode(), file_name.encode()), "nxs_scene_add_hdr_map_file_float")
 
     def add_mesh(self, tris, material_id=-1):
@@ -1693,7 +1408,6 @@ class Scene:
         _scheck(self.L.nxs_scene_set_instance_transform(self.h, instance_id, _ptr(p), _ptr(r), _ptr(sc)), "nxs_scene_set_instance_transform")
 
     def assign_material(self, instance_id, material_id):
-        self.L.nxs_scene_assign_material.argtypes = [C.c_void_p, C.c_uint32, C.c_int32]
         _scheck(self.L.nxs_scene_assign_material(self.h, instance_id, material_id), "nxs_scene_assign_material")
 
     def set_tlas_refit(self, enable=True):
@@ -1701,7 +1415,6 @@ class Scene:
 
     def set_device_tlas(self, enable=True):
         """the TLAS is built (nxhip_rebuild_tlas) and refitted on the device; update() runs no host TLAS builder"""
-        self.L.nxs_scene_set_device_tlas.argtypes = [C.c_void_p, C.c_int]
         _scheck(self.L.nxs_scene_set_device_tlas(self.h, 1 if enable else 0), "nxs_scene_set_device_tlas")
 
     def load_file(self, path, file_name):
@@ -1714,34 +1427,25 @@ class Scene:
 
     def set_material_alpha_modes(self, on=True):
         """Scene::SetMaterialAlphaModes: the files loaded from here on carry their materials' glTF alphaMode / alphaCutoff to the device (off by default)"""
-        self.L.nxs_scene_set_material_alpha_modes.argtypes = [C.c_void_p, C.c_int]
         _scheck(self.L.nxs_scene_set_material_alpha_modes(self.h, 1 if on else 0), "nxs_scene_set_material_alpha_modes")
 
     def set_skins(self, on=True):
         """Scene::SetSkins: the files loaded from here on keep their glTF skins, joint animations and node tree (off by default)"""
-        self.L.nxs_scene_set_skins.argtypes = [C.c_void_p, C.c_int]
         _scheck(self.L.nxs_scene_set_skins(self.h, 1 if on else 0), "nxs_scene_set_skins")
 
     def mesh_count(self):
-        self.L.nxs_scene_mesh_count.argtypes = [C.c_void_p]
-        self.L.nxs_scene_mesh_count.restype = C.c_uint32
         return int(self.L.nxs_scene_mesh_count(self.h))
 
     def animation_count(self):
-        self.L.nxs_scene_animation_count.argtypes = [C.c_void_p]
-        self.L.nxs_scene_animation_count.restype = C.c_uint32
         return int(self.L.nxs_scene_animation_count(self.h))
 
     def mesh_joint_count(self, mesh_id):
         """joints of the mesh's skin; 0: the mesh is not skinned"""
-        self.L.nxs_scene_mesh_joint_count.argtypes = [C.c_void_p, C.c_uint32]
-        self.L.nxs_scene_mesh_joint_count.restype = C.c_uint32
         return int(self.L.nxs_scene_mesh_joint_count(self.h, int(mesh_id)))
 
     def joint_palette(self, mesh_id, animation=None, t=0.0):
         """Scene::JointPalette: (joints, 12) float32 — the pose of animation `animation` (None: the rest pose) at time t, evaluated in binary64
         on the host; the twin of nexus_amd.animation.joint_palette"""
-        self.L.nxs_scene_joint_palette.argtypes = [C.c_void_p, C.c_uint32, C.c_int32, C.c_double, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
         n = C.c_uint32(0)
         a = -1 if animation is None else int(animation)
         _scheck(self.L.nxs_scene_joint_palette(self.h, int(mesh_id), a, float(t), None, 0, C.byref(n)), "nxs_scene_joint_palette")
@@ -1751,7 +1455,6 @@ class Scene:
 
     def material_alphas(self):
         """AssetManager::GetMaterialAlphas: pod.ALPHA_DT records, one per material (empty: no material has a mode)"""
-        self.L.nxs_scene_material_alphas.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
         n = C.c_uint32(0)
         _scheck(self.L.nxs_scene_material_alphas(self.h, None, 0, C.byref(n)), "nxs_scene_material_alphas")
         out = np.zeros(n.value, dtype=pod.ALPHA_DT)
@@ -1783,39 +1486,29 @@ class Scene:
         """Scene::AddAnalyticLight: a pod.ALIGHT_DT record (pod.make_analytic_light); returns its index"""
         l = np.ascontiguousarray(light, dtype=pod.ALIGHT_DT).reshape(1)
         i = C.c_uint32(0)
-        self.L.nxs_scene_add_analytic_light.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]
         _scheck(self.L.nxs_scene_add_analytic_light(self.h, _ptr(l), C.byref(i)), "nxs_scene_add_analytic_light")
         return int(i.value)
 
     def set_material_detail(self, material_id, detail):
         """AssetManager::SetMaterialDetail: a pod.DETAIL_DT record (pod.make_material_detail) with ids of add_texture("normal" / "roughness", ...)"""
         d = np.ascontiguousarray(detail, dtype=pod.DETAIL_DT).reshape(1)
-        self.L.nxs_scene_set_material_detail.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
         _scheck(self.L.nxs_scene_set_material_detail(self.h, int(material_id), _ptr(d)), "nxs_scene_set_material_detail")
 
     def clear_material_details(self):
         """AssetManager::ClearMaterialDetails: no material has detail maps any more (what nexus_render --no-detail-maps does)"""
-        self.L.nxs_scene_clear_material_details.argtypes = [C.c_void_p]
         _scheck(self.L.nxs_scene_clear_material_details(self.h), "nxs_scene_clear_material_details")
 
     def material_details(self):
         """AssetManager::GetMaterialDetails: pod.DETAIL_DT records, one per material, or none at all"""
-        self.L.nxs_scene_material_detail_count.argtypes = [C.c_void_p]
-        self.L.nxs_scene_material_detail_count.restype = C.c_uint32
-        self.L.nxs_scene_material_details.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
         out = np.zeros(int(self.L.nxs_scene_material_detail_count(self.h)), dtype=pod.DETAIL_DT)
         _scheck(self.L.nxs_scene_material_details(self.h, _ptr(out) if len(out) else None, len(out)), "nxs_scene_material_details")
         return out
 
     def remove_analytic_light(self, index):
-        self.L.nxs_scene_remove_analytic_light.argtypes = [C.c_void_p, C.c_uint32]
         _scheck(self.L.nxs_scene_remove_analytic_light(self.h, int(index)), "nxs_scene_remove_analytic_light")
 
     def analytic_lights(self):
         """Scene::GetAnalyticLights: the records as the scene holds them (added by hand or read from a .glb's KHR_lights_punctual)"""
-        self.L.nxs_scene_analytic_light_count.argtypes = [C.c_void_p]
-        self.L.nxs_scene_analytic_light_count.restype = C.c_uint32
-        self.L.nxs_scene_analytic_lights.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
         out = np.zeros(int(self.L.nxs_scene_analytic_light_count(self.h)), dtype=pod.ALIGHT_DT)
         _scheck(self.L.nxs_scene_analytic_lights(self.h, _ptr(out) if len(out) else None, len(out)), "nxs_scene_analytic_lights")
         return out
@@ -1823,28 +1516,23 @@ class Scene:
     def set_medium(self, medium):
         """Scene::SetMedium (a pod.MEDIUM_DT record, pod.make_medium); None: Scene::ClearMedium"""
         if medium is None:
-            self.L.nxs_scene_clear_medium.argtypes = [C.c_void_p]
             _scheck(self.L.nxs_scene_clear_medium(self.h), "nxs_scene_clear_medium")
             return
         m = np.ascontiguousarray(medium, dtype=pod.MEDIUM_DT).reshape(1)
-        self.L.nxs_scene_set_medium.argtypes = [C.c_void_p, C.c_void_p]
         _scheck(self.L.nxs_scene_set_medium(self.h, _ptr(m)), "nxs_scene_set_medium")
 
     def set_medium_density(self, rho):
         """Scene::SetMediumDensity (float32 of shape (nz, ny, nx)); None: Scene::ClearMediumDensity"""
         if rho is None:
-            self.L.nxs_scene_clear_medium_density.argtypes = [C.c_void_p]
             _scheck(self.L.nxs_scene_clear_medium_density(self.h), "nxs_scene_clear_medium_density")
             return
         r = np.ascontiguousarray(rho, dtype=np.float32)
         assert r.ndim == 3, "a density grid has the shape (nz, ny, nx)"
-        self.L.nxs_scene_set_medium_density.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]
         _scheck(self.L.nxs_scene_set_medium_density(self.h, _ptr(r), r.shape[2], r.shape[1], r.shape[0]), "nxs_scene_set_medium_density")
 
     def medium_density(self):
         """Scene::GetMediumDensity: float32 of shape (nz, ny, nx), or None"""
         dims = (C.c_uint32 * 3)()
-        self.L.nxs_scene_medium_density.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
         _scheck(self.L.nxs_scene_medium_density(self.h, dims, None, 0), "nxs_scene_medium_density")
         if dims[0] == 0:
             return None
@@ -1856,7 +1544,6 @@ class Scene:
         """Scene::GetMedium: the record, or None"""
         out = np.zeros(1, dtype=pod.MEDIUM_DT)
         has = C.c_int(0)
-        self.L.nxs_scene_medium.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
         _scheck(self.L.nxs_scene_medium(self.h, _ptr(out), C.byref(has)), "nxs_scene_medium")
         return out[0] if has.value else None
 
@@ -1867,14 +1554,12 @@ class Scene:
 def write_png(path, rgba8, width, height, flip=True):
     px = np.ascontiguousarray(rgba8, dtype=np.uint32)
     L = lib()
-    L.nxh_write_png.argtypes = [C.c_char_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int]
     _scheck(L.nxh_write_png(str(path).encode(), _ptr(px), width, height, 1 if flip else 0), "nxh_write_png")
 
 
 def write_exr(path, rgb, width, height, flip=True):
     px = np.ascontiguousarray(rgb, dtype=np.float32)
     L = lib()
-    L.nxh_write_exr.argtypes = [C.c_char_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int]
     _scheck(L.nxh_write_exr(str(path).encode(), _ptr(px), width, height, 1 if flip else 0), "nxh_write_exr")
 
 
@@ -1884,26 +1569,6 @@ class Renderer:
     def __init__(self, width, height, scene, device=0):
         self.L = lib()
         L = self.L
-        L.nxs_renderer_create.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
-        L.nxs_renderer_destroy.argtypes = [C.c_void_p]
-        L.nxs_renderer_render.argtypes = [C.c_void_p, C.c_void_p, C.c_float]
-        L.nxs_renderer_reset.argtypes = [C.c_void_p]
-        L.nxs_renderer_on_resize.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
-        L.nxs_renderer_save_screenshot.argtypes = [C.c_void_p, C.c_char_p]
-        L.nxs_renderer_save_exr.argtypes = [C.c_void_p, C.c_char_p]
-        L.nxs_renderer_frame_number.argtypes = [C.c_void_p]
-        L.nxs_renderer_frame_number.restype = C.c_uint32
-        L.nxs_renderer_megasamples_per_second.argtypes = [C.c_void_p]
-        L.nxs_renderer_megasamples_per_second.restype = C.c_double
-        L.nxs_renderer_device_context.argtypes = [C.c_void_p]
-        L.nxs_renderer_device_context.restype = C.c_void_p
-        L.nxs_renderer_set_modes.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
-        L.nxs_renderer_set_denoise.argtypes = [C.c_void_p, C.c_int]
-        L.nxs_renderer_save_denoised_exr.argtypes = [C.c_void_p, C.c_char_p]
-        L.nxs_renderer_save_feature_exr.argtypes = [C.c_void_p, C.c_char_p]
-        L.nxs_renderer_set_adaptive.argtypes = [C.c_void_p, C.c_void_p]
-        L.nxs_renderer_render_adaptive.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]
-        L.nxs_renderer_save_sample_count_exr.argtypes = [C.c_void_p, C.c_char_p]
         h = C.c_void_p()
         _scheck(L.nxs_renderer_create(width, height, scene.h, device, C.byref(h)), "nxs_renderer_create")
         self.h = h
@@ -1979,7 +1644,6 @@ class Renderer:
 
     def read_accumulation(self):
         out = np.zeros((self.width * self.height, 3), dtype=np.float32)
-        lib().nxhip_read_accumulation.argtypes = [C.c_void_p, C.c_void_p]
         check(lib().nxhip_read_accumulation(C.c_void_p(self.L.nxs_renderer_device_context(self.h)), _ptr(out)), "nxhip_read_accumulation")
         return out
 
@@ -2020,21 +1684,17 @@ class PathTracer:
         _scheck(self.L.nxs_pathtracer_set_passes_in_flight(self.h, passes), "nxs_pathtracer_set_passes_in_flight")
 
     def set_pixel_order(self, order):
-        self.L.nxs_pathtracer_set_pixel_order.argtypes = [C.c_void_p, C.c_int]
         _scheck(self.L.nxs_pathtracer_set_pixel_order(self.h, int(order)), "nxs_pathtracer_set_pixel_order")
 
     def set_entry_points(self, on=True):
-        self.L.nxs_pathtracer_set_entry_points.argtypes = [C.c_void_p, C.c_int]
         _scheck(self.L.nxs_pathtracer_set_entry_points(self.h, 1 if on else 0), "nxs_pathtracer_set_entry_points")
 
     def set_shadow_transmittance(self, mode):
         """PathTracer::SetShadowTransmittance: pod.SHADOWS_OPAQUE (the reference's rule) or pod.SHADOWS_TRANSMIT (opacity and texture alpha attenuate shadow rays)"""
-        self.L.nxs_pathtracer_set_shadow_transmittance.argtypes = [C.c_void_p, C.c_int]
         _scheck(self.L.nxs_pathtracer_set_shadow_transmittance(self.h, int(mode)), "nxs_pathtracer_set_shadow_transmittance")
 
     def set_light_sampling(self, mode):
         """PathTracer::SetLightSampling: pod.LIGHTS_UNIFORM (the reference's rule) or pod.LIGHTS_POWER (area x emitted luminance)"""
-        self.L.nxs_pathtracer_set_light_sampling.argtypes = [C.c_void_p, C.c_int]
         _scheck(self.L.nxs_pathtracer_set_light_sampling(self.h, int(mode)), "nxs_pathtracer_set_light_sampling")
 
     def read_accumulation(self):
@@ -2045,24 +1705,20 @@ class PathTracer:
 
     def set_feature_buffers(self, on=True):
         """PathTracer::SetFeatureBuffers: albedo / normal / depth of the camera ray's hit, accumulated like the colour"""
-        self.L.nxs_pathtracer_set_feature_buffers.argtypes = [C.c_void_p, C.c_int]
         _scheck(self.L.nxs_pathtracer_set_feature_buffers(self.h, 1 if on else 0), "nxs_pathtracer_set_feature_buffers")
 
     def set_adaptive(self, params=None):
         """PathTracer::SetAdaptive: a pod.ADAPTIVE_DT record (adaptive_defaults()), None = off"""
-        self.L.nxs_pathtracer_set_adaptive.argtypes = [C.c_void_p, C.c_void_p]
         p = None if params is None else np.ascontiguousarray(params, dtype=pod.ADAPTIVE_DT).reshape(1)
         _scheck(self.L.nxs_pathtracer_set_adaptive(self.h, _ptr(p) if p is not None else None), "nxs_pathtracer_set_adaptive")
 
     def set_device_blas_build(self, scene, enable=True):
         """PathTracer::SetDeviceBlasBuild: meshes added to `scene` from now on are built into BVH8s on the GPU"""
-        self.L.nxs_pathtracer_set_device_blas_build.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         _scheck(self.L.nxs_pathtracer_set_device_blas_build(self.h, scene.h, 1 if enable else 0), "nxs_pathtracer_set_device_blas_build")
 
     def pose_mesh(self, scene, mesh_id, palette):
         """PathTracer::PoseMesh: pose a skinned mesh on the device with a (joints, 12) palette — before scene.update()"""
         m = np.ascontiguousarray(palette, dtype=np.float32).reshape(-1, 12)
-        self.L.nxs_pathtracer_pose_mesh.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
         _scheck(self.L.nxs_pathtracer_pose_mesh(self.h, scene.h, int(mesh_id), _ptr(m), len(m)), "nxs_pathtracer_pose_mesh")
 
     def update_device_scene(self, scene):
@@ -2090,7 +1746,6 @@ class PathTracer:
     def read_blas(self, blas_id, tri_count):
         """nodes and primitive index list of BLAS `blas_id` of this path tracer's device context"""
         ctx = self.L.nxs_pathtracer_device_context(self.h)
-        self.L.nxhip_read_blas.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
         n = C.c_uint32(0)
         check(self.L.nxhip_read_blas(ctx, blas_id, None, 0, None, 0, C.byref(n)), "nxhip_read_blas")
         nodes = np.zeros(n.value, dtype=pod.NODE_DT)

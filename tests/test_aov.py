@@ -1,6 +1,5 @@
 """Feature buffers and denoiser, the part that needs no GPU: the tests' own references are pinned (the primary-ray restatement against
 the oracle's wavefront, the numpy filter against the invariants of its definition) and the binding declares what the library exports."""
-import ctypes as C
 import re
 import os
 
@@ -71,7 +70,6 @@ def test_denoise_params_layout_and_defaults():
     # the stamp the library computes from the header = the stamp of the binding's mirrors (nx_denoise_params included)
     words = capi.abi_words()
     assert words[-3:] == [20, 4, 16]
-    capi.lib().nxhip_abi_stamp.restype = C.c_uint64
     assert capi.lib().nxhip_abi_stamp() == capi.abi_stamp()
     d = capi.denoise_defaults()[0]
     assert {k: float(d[n]) for k, n in zip(("iterations", "sigma_color", "sigma_normal", "sigma_albedo", "sigma_depth"), dt.names)} == \

@@ -28,6 +28,45 @@ def test_library_exports_every_declared_symbol():
     assert lib.nxhip_has_gfx950_code() == 1
 
 
+def _prototypes(header):
+    """{name: (return type, parameter count)} by this file's own reading of a header: text up to the name, commas between the parentheses"""
+    text = open(os.path.join(ROOT, "include", header)).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    text = re.sub(r"^static inline .*?^}", "", text, flags=re.S | re.M)
+    found = re.findall(r"^((?:const |struct )?\w+ \*?)((?:nxhip|nxh|nxs)_[a-z0-9_]+)\(([^()]*)\);", text, flags=re.M)
+    return {name: (ret.strip(), 0 if params.strip() == "void" else params.count(",") + 1) for ret, name, params in found}
+
+
+def test_every_declared_function_has_the_signature_of_its_prototype():
+    """lib() gives each function its argtypes and restype from the headers (nexus_amd/cabi.py); counted again here, with another parser"""
+    import ctypes as C
+
+    lib = capi.lib()
+    protos = {**_prototypes("nexus_hip.h"), **_prototypes("nexus_host.h")}
+    assert sorted(protos) == sorted(capi.HIP_SYMBOLS + capi.HOST_SYMBOLS)
+    for name, (ret, count) in protos.items():
+        fn = getattr(lib, name)
+        assert fn.argtypes is not None and len(fn.argtypes) == count, "%s: argtypes %r for %d parameters" % (name, fn.argtypes, count)
+        if ret != "int":
+            assert fn.restype is not C.c_int, "%s returns '%s' but has the ctypes default restype" % (name, ret)
+        else:
+            assert fn.restype is C.c_int, name
+    assert lib.nxhip_destroy.restype is None and lib.nxhip_last_error.restype is C.c_char_p
+    assert lib.nxhip_abi_stamp.restype is C.c_uint64 and lib.nxs_renderer_megasamples_per_second.restype is C.c_double
+    assert lib.nxs_pathtracer_device_context.restype is C.c_void_p and lib.nxh_loaded_texture_count.restype is C.c_uint32
+    assert lib.nxs_scene_load_file.argtypes == [C.c_void_p, C.c_char_p, C.c_char_p]
+    assert lib.nxs_scene_joint_palette.argtypes == [C.c_void_p, C.c_uint32, C.c_int32, C.c_double, C.c_void_p, C.c_uint32, C.c_void_p]
+
+
+def test_a_symbol_the_library_lacks_is_a_nexus_error_that_names_it():
+    class Partial:
+        nxhip_last_error = type("Fn", (), {})()
+
+    with pytest.raises(capi.NexusError, match="does not export nxhip_abi_stamp"):
+        capi._declare(Partial(), ("nxhip_last_error", "nxhip_abi_stamp"))
+    assert Partial.nxhip_last_error.argtypes == []
+
+
 def test_no_device_fails_loudly_not_silently():
     """Without a GPU the product must refuse, never fall back to a CPU path."""
     import pytest

@@ -43,7 +43,6 @@ def test_bad_tables_are_refused_and_the_previous_one_stays(gpu_ctx_factory):
     assert SH.hit_records_equal(before, ctx.trace_batch(rays[:512])), "a refused table changes nothing"
     # a null array with a count, and a null context
     L = capi.lib()
-    L.nxhip_set_material_alpha.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
     assert L.nxhip_set_material_alpha(ctx.h, None, 3) == INVALID and "null array" in _err()
     assert L.nxhip_set_material_alpha(None, None, 0) == INVALID
     assert L.nxhip_set_material_alpha(ctx.h, None, 0) == 0  # (clears)

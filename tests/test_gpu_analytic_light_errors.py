@@ -71,7 +71,6 @@ def test_every_refused_input_leaves_the_previous_table(ctx):
     want = _frame(ctx)
     assert not np.array_equal(want, without)
     L = ctx.L
-    L.nxhip_set_analytic_lights.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
     for what, lights in REFUSED.items():
         assert L.nxhip_set_analytic_lights(ctx.h, lights.ctypes.data_as(C.c_void_p), len(lights)) == 1, what  # NXHIP_ERR_INVALID
         with pytest.raises(capi.NexusError):

@@ -152,10 +152,6 @@ def test_environment_hooks_refuse_what_they_cannot_answer(gpu_ctx_factory):
     assert [len(a) for a in ctx.env_sample_batch(np.zeros((0, 2), np.float32))] == [0, 0, 0]
     assert len(ctx.env_eval_batch(np.zeros((0, 3), np.float32))[0]) == 0
     # null arrays with count > 0, a destination too small, a null context
-    vp, u32 = C.c_void_p, C.c_uint32
-    L.nxhip_env_sample_batch.argtypes = [vp, vp, u32, vp, vp, vp]
-    L.nxhip_env_eval_batch.argtypes = [vp, vp, u32, vp, vp, vp]
-    L.nxhip_read_env_tables.argtypes = [vp, vp, vp, vp, u32, vp, vp]
     out3, out1, outi = np.zeros(3, np.float32), np.zeros(1, np.float32), np.zeros(1, np.uint32)
     p = capi._ptr
     assert L.nxhip_env_sample_batch(ctx.h, None, 1, p(out3), p(out1), p(outi)) == 1
@@ -425,7 +421,6 @@ def test_batched_blas_build_refuses_bad_input_and_falls_back_for_other_builders(
 
     ctx = gpu_ctx_factory(32, 32)
     L = ctx.L  # (status 1 = NXHIP_ERR_INVALID, include/nexus_hip.h)
-    L.nxhip_build_blas_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
     a = np.ascontiguousarray(scenegen.random_soup(20, seed=1), dtype=pod.TRI_DT)
     ptrs = (C.c_void_p * 2)(a.ctypes.data, None)
     counts = np.array([20, 5], dtype=np.uint32)

@@ -158,7 +158,6 @@ def test_through_the_facade(gpu_ctx_factory):
         assert pt.frame_number() == 1
         ctx = capi.Context.__new__(capi.Context)  # (the path tracer's own context, not owned: as Renderer.device_context wraps its one)
         ctx.L = capi.lib()
-        ctx.L.nxs_pathtracer_device_context.restype = C.c_void_p
         ctx.h = C.c_void_p(ctx.L.nxs_pathtracer_device_context(pt.h))
         ctx.close = lambda: None
         o, d, idx = ctx.debug_read_primary_rays()

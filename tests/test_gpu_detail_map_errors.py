@@ -43,7 +43,6 @@ def test_every_refused_table_leaves_the_previous_one(ctx_scene):
     good = scene.material_detail
     want = _frame(ctx)
     L = ctx.L
-    L.nxhip_set_material_detail.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
     refused = {
         "a normal map id below -1": _with(good, 0, normalMapId=-2),
         "a roughness map id below -1": _with(good, 1, roughnessMapId=-7),
@@ -72,7 +71,6 @@ def test_a_render_refuses_a_table_that_does_not_fit(ctx_scene):
     ctx.set_material_detail(good)
     want = _frame(ctx)
     L = ctx.L
-    L.nxhip_render_frame.argtypes = [C.c_void_p]
     unfit = {
         "one entry too few": good[:3],
         "one entry too many": np.concatenate([good, good[:1]]),
@@ -107,7 +105,6 @@ def test_the_hooks_refuse_bad_arguments(ctx_scene):
     with pytest.raises(capi.NexusError):
         ctx.shading_frame_batch(0, [0, len(scene.meshes[0])], uv, d)
     L = ctx.L
-    L.nxhip_shading_frame_batch.argtypes = [C.c_void_p, C.c_uint32] + [C.c_void_p] * 3 + [C.c_uint32] + [C.c_void_p] * 3
     assert L.nxhip_shading_frame_batch(ctx.h, 0, None, None, None, 2, None, None, None) == INVALID
     assert L.nxhip_shading_frame_batch(ctx.h, 0, None, None, None, 0, None, None, None) == 0
     for kind in ("normal", "roughness"):
@@ -115,6 +112,5 @@ def test_the_hooks_refuse_bad_arguments(ctx_scene):
             ctx.tex2d_batch(kind, 1, uv)
         with pytest.raises(capi.NexusError):
             ctx.tex2d_batch(kind, -1, uv)
-    L.nxhip_upload_texture.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
     img = np.zeros((2, 2, 4), np.uint8)
     assert L.nxhip_upload_texture(ctx.h, 5, img.ctypes.data_as(C.c_void_p), 2, 2, None) == INVALID

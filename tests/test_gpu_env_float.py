@@ -446,7 +446,6 @@ def test_bad_maps_are_refused_and_change_nothing(gpu_ctx_factory):
     tables = ctx.read_env_tables()
     good = _map("seam")
     L = ctx.L
-    L.nxhip_upload_env_float.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
     for what, value in (("NaN", np.nan), ("a negative component", -1.0), ("inf", np.inf), ("-inf", -np.inf), ("-0.0 is fine, -1e-30 is not", -1e-30)):
         img = good.copy()
         img[7, 13, 1] = value

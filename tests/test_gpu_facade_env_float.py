@@ -27,7 +27,6 @@ def _sun():
 
 def _sampling_on(pt):
     L = capi.lib()
-    L.nxhip_set_env_sampling.argtypes = [C.c_void_p, C.c_int]
     capi.check(L.nxhip_set_env_sampling(C.c_void_p(L.nxs_pathtracer_device_context(pt.h)), 1), "nxhip_set_env_sampling")
 
 
@@ -35,7 +34,6 @@ def _stored(pt):
     """the float map the path tracer's context holds (nxhip_read_env_float on the handle itself: a capi.Context wrapped round it would
     destroy the path tracer's context when it is collected)"""
     L = capi.lib()
-    L.nxhip_read_env_float.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     h = C.c_void_p(L.nxs_pathtracer_device_context(pt.h))
     width, height = C.c_uint32(0), C.c_uint32(0)
     capi.check(L.nxhip_read_env_float(h, None, 0, C.byref(width), C.byref(height)), "nxhip_read_env_float")

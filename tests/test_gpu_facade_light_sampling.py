@@ -49,7 +49,6 @@ def test_set_light_sampling_through_the_facade_equals_the_capi_path(gpu_ctx_fact
     assert np.array_equal(pt.read_accumulation().view(np.uint32), acc.view(np.uint32))
     # the façade's context is in the mode: it has a light table (the default mode refuses the hook), with the light's two triangles
     L = capi.lib()
-    L.nxhip_read_light_table.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32)]
     n = C.c_uint32(0)
     assert L.nxhip_read_light_table(L.nxs_pathtracer_device_context(pt.h), None, None, 0, None, C.byref(n)) == 0 and n.value == 2
     pt.set_light_sampling(pod.LIGHTS_UNIFORM)

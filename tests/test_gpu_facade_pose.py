@@ -42,7 +42,6 @@ def _device_context(pt):
     """the path tracer's own context, not owned (as Renderer.device_context wraps its one)"""
     ctx = capi.Context.__new__(capi.Context)
     ctx.L = capi.lib()
-    ctx.L.nxs_pathtracer_device_context.restype = C.c_void_p
     ctx.h = C.c_void_p(ctx.L.nxs_pathtracer_device_context(pt.h))
     ctx.width, ctx.height, ctx.local_count, ctx.frames_per_pass = W, H, W * H, 1
     ctx.close = lambda: None

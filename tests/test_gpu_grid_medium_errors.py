@@ -42,7 +42,6 @@ def test_refusals_leave_the_previous_grid_in_effect(gpu_ctx_factory):
         return g
 
     L = ctx.L
-    L.nxhip_set_medium_density.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]
     raw = good.ctypes.data_as(C.c_void_p)
     # (more than 2^27 voxels cannot be reached with dimensions of at most 512: 512^3 is 2^27 — the dimension check answers first)
     for dims, message in (((0, 4, 3), "a dimension is 0"), ((5, 0, 3), "a dimension is 0"), ((5, 4, 0), "a dimension is 0"), ((513, 1, 1), "exceeds 512"),

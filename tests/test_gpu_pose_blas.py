@@ -321,7 +321,6 @@ def test_every_refusal_leaves_triangles_and_nodes_as_they_were(gpu_ctx_factory):
     ctx = gpu_ctx_factory(32, 32)
     bid, _nodes, _idx = _install(ctx, tris, how)
     L = ctx.L
-    L.nxhip_last_error.restype = __import__("ctypes").c_char_p
     pal = K.palette("ordinary", 2, 1.0, 1)
     good = np.ascontiguousarray(corners)
 

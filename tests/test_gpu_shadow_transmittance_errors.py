@@ -20,7 +20,6 @@ def _err():
 
 def _hook(ctx, rays, tmax, count, out):
     L = capi.lib()
-    L.nxhip_trace_transmittance_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
     ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
     return L.nxhip_trace_transmittance_batch(ctx.h, ptr(rays), ptr(tmax), count, ptr(out))
 
@@ -33,7 +32,6 @@ def test_an_unknown_mode_is_refused(gpu_ctx_factory):
     ctx.set_shadow_transmittance(pod.SHADOWS_TRANSMIT)
     ctx.set_shadow_transmittance(pod.SHADOWS_OPAQUE)
     L = capi.lib()
-    L.nxhip_set_shadow_transmittance.argtypes = [C.c_void_p, C.c_int]
     assert L.nxhip_set_shadow_transmittance(None, 1) == INVALID
 
 

@@ -262,5 +262,4 @@ def test_exported_symbols():
     from nexus_amd import workloads
     assert workloads.Workload.medium_density is None
     # the setter validates before it looks at the device: no context, no GPU
-    L.nxhip_set_medium_density.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]
     assert L.nxhip_set_medium_density(None, None, 0, 0, 0) != 0

@@ -83,9 +83,7 @@ def test_radiance_hdr_reader_cpp_equals_python(rle, tmp_path):
     p = tmp_path / "sky.hdr"
     p.write_bytes(data)
     sc = capi.Scene(16, 16)
-    import ctypes
 
-    sc.L.nxs_scene_add_hdr_map_file.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p]
     assert sc.L.nxs_scene_add_hdr_map_file(sc.h, (str(tmp_path) + os.sep).encode(), b"sky.hdr") == 0
     assert sc.L.nxs_scene_add_hdr_map_file(sc.h, (str(tmp_path) + os.sep).encode(), b"missing.hdr") != 0
 

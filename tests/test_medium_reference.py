@@ -194,6 +194,4 @@ def test_hook_bars_and_the_decision_cap():
 def test_record_size_agrees_on_both_sides():
     assert pod.MEDIUM_DT.itemsize == 48 and [pod.MEDIUM_DT.fields[n][1] for n in pod.MEDIUM_DT.names] == [0, 12, 16, 28, 32, 44]
     assert pod.MEDIUM_DT.itemsize in capi.abi_words()
-    import ctypes as C
-    capi.lib().nxhip_abi_stamp.restype = C.c_uint64
     assert capi.lib().nxhip_abi_stamp() == capi.abi_stamp()

@@ -55,7 +55,6 @@ def main():
 
     torch.cuda.set_device(0)
     med = statistics.median
-    capi.lib().nxhip_read_light_table.argtypes = [capi.C.c_void_p] * 3 + [capi.C.c_uint32] + [capi.C.c_void_p] * 2
     if not args.skip_config:
         W, H = args.width, args.height
         sc = workloads.config5(W, H, args.path_length)
