@@ -583,7 +583,9 @@ int nxhip_set_frames_per_pass(nxhip_ctx *ctx, uint32_t frames);
  * into the one accumulation, oldest first: the image is bit-identical to R = 1.  Worth it for small passes (one frame per
  * pass: 2.2x at R = 6; 20 frames per pass: +20 % at R = 4; the persistent trace launches of the slots are sized to share the
  * CUs).  Fastest with enough hardware queues: export GPU_MAX_HW_QUEUES=24 before the process touches HIP; with the runtime's
- * default of 4 the pass graphs take the shape that fits them (nxhip_set_queue_budget).  Kernel timing, the counting variant and
+ * default of 4 the pass graphs take the shape that fits them (nxhip_set_queue_budget), and the trace launches the size that fits
+ * the slots the queues keep resident (nxhip_resident_slots_for): R is the number of passes that may await nxhip_accumulate, how many
+ * of them are on the chip at once is the library's choice.  Kernel timing, the counting variant and
  * a bound radiance buffer fall back to one pass at a time. */
 int nxhip_set_passes_in_flight(nxhip_ctx *ctx, uint32_t passes);
 
@@ -604,6 +606,15 @@ int nxhip_get_queue_budget(nxhip_ctx *ctx, uint32_t *queues, uint32_t *chained, 
 /* The budget a value of GPU_MAX_HW_QUEUES resolves to (NULL: the variable is not set): a whole number in [1, 32] is itself, anything
  * else 4.  Needs no context and no device. */
 uint32_t nxhip_queue_budget_from_text(const char *text);
+/* Of `passes` in flight, the slots the library keeps resident under a budget: all of them where 2 passes + 1 lanes fit, else as many
+ * as the budget's queues serve side by side (budget - 1: one queue carries the context's stream), at least 1 and at most `passes`.  The persistent trace launches are sized to share the chip among that many slots (four passes in
+ * flight on four queues: the shares of three, +6 %); nothing else follows it: nxhip_render_frame still goes round robin over all `passes`
+ * slots, and `passes` remains the number of passes that may await nxhip_accumulate.  Same kernels and arguments, other grids: the
+ * image is bit-identical.  Needs no context and no device. */
+uint32_t nxhip_resident_slots_for(uint32_t passes, uint32_t budget);
+/* Test hook: the resident slots of a pass issued now, the workgroups of its closest-hit launches, and which of the slots
+ * (0 .. passes - 1) the last pass rendered in.  Each destination may be NULL. */
+int nxhip_debug_resident_slots(nxhip_ctx *ctx, uint32_t *resident, uint32_t *traceBlocks, uint32_t *slotOfLastPass);
 /* Test hook: the pass graph the last pass replayed, counted from the runtime's graph object when the instance was built — kernel nodes,
  * dependency edges, and the largest number of nodes that depend on one and the same node (1: a chain; 2: closest-hit beside any-hit).
  * Each destination may be NULL. */

@@ -1033,6 +1033,13 @@ class Context:
         check(self.L.nxhip_debug_last_graph(self.h, C.byref(n), C.byref(e), C.byref(f)), "nxhip_debug_last_graph")
         return int(n.value), int(e.value), int(f.value)
 
+    def debug_resident_slots(self):
+        """(resident, trace_blocks, slot_of_last_pass): the slots a pass issued now shares the chip among, the workgroups of its
+        closest-hit launches, and which of the slots the last pass rendered in (a test hook)"""
+        r, b, s = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+        check(self.L.nxhip_debug_resident_slots(self.h, C.byref(r), C.byref(b), C.byref(s)), "nxhip_debug_resident_slots")
+        return int(r.value), int(b.value), int(s.value)
+
     def set_frames_per_pass(self, frames):
         check(self.L.nxhip_set_frames_per_pass(self.h, frames), "nxhip_set_frames_per_pass")
         self.frames_per_pass = int(frames)
@@ -1336,6 +1343,11 @@ def queue_budget_from_text(text):
     """nxhip_queue_budget_from_text: the queue budget a value of GPU_MAX_HW_QUEUES resolves to (None: not set); no device needed"""
     L = lib()
     return int(L.nxhip_queue_budget_from_text(None if text is None else str(text).encode()))
+
+
+def resident_slots_for(passes, budget):
+    """nxhip_resident_slots_for: of `passes` in flight, the slots the library keeps resident under a queue budget; no device needed"""
+    return int(lib().nxhip_resident_slots_for(int(passes), int(budget)))
 
 
 # ---- C++ Scene / PathTracer facade (include/nexus/Scene.h, PathTracer.h) -------------------------------

@@ -161,6 +161,8 @@ struct nxhip_ctx : nxd::PassSlot {
     // the runtime's queues.
     uint32_t queueBudget = 4;
     int shapeForced = -1;          // NX_TUNING_KNOBS sweeps only (NX_GRAPH_SHAPE): -1 = by the budget, else the shape itself
+    int residentForced = 0;        // NX_TUNING_KNOBS sweeps only (NX_RESIDENT_SLOTS): 0 = by the budget (resident_slots_for), else the count itself
+    uint32_t lastSlotIndex = 0;    // which of the R slots the last pass rendered in (nxhip_debug_resident_slots)
     uint32_t lastGraphNodes = 0, lastGraphEdges = 0, lastGraphFanOut = 0;  // of the graph instance the last pass replayed (nxhip_debug_last_graph)
     std::vector<nxd::PassSlot*> pending;   // rendered, not yet accumulated, oldest first
     nxd::PassSlot* lastRendered = nullptr;

@@ -349,6 +349,7 @@ int render_pass(nxhip_ctx* c, uint32_t framesArg);
 unsigned hook_trace_features(const nxhip_ctx* c, bool anyHit, bool transmit);  // the ray-batch hooks' trace launch, by the passes' own rule (trace_features)
 uint32_t queue_budget_from_text(const char* text);  // what a value of GPU_MAX_HW_QUEUES means: a whole number in [1, 32], else 4
 uint32_t queue_budget_from_environment();           // ... of the variable as it is now (nxhip_create, nxhip_set_queue_budget)
+uint32_t resident_slots_for(uint32_t passes, uint32_t budget);  // of `passes` in flight, the slots whose launches a budget keeps on the chip at once
 int read_float4_as_float3(nxhip_ctx* c, const void* dev, uint32_t count, float* dst);
 // nxhip_features.hip
 int adaptive_restart(nxhip_ctx* c);

@@ -538,6 +538,7 @@ int nxhip_create(int device, uint32_t width, uint32_t height, void* stream, nxhi
             if (const char* e = std::getenv("NX_THIN_LANES")) { const int n = std::atoi(e); if (n >= 1 && n <= 64) c->h.thinLanes = (uint32_t)n; }   // sweeps of the hand-over rule
             if (const char* e = std::getenv("NX_THIN_ITERS")) { const int n = std::atoi(e); if (n >= 1 && n <= 4096) c->h.thinIters = (uint32_t)n; }
             if (const char* e = std::getenv("NX_GRAPH_SHAPE")) { const int n = std::atoi(e); if (n == 0 || n == 1) c->shapeForced = n; }  // sweeps of the pass-graph shape (graph_shape)
+            if (const char* e = std::getenv("NX_RESIDENT_SLOTS")) { const int n = std::atoi(e); if (n >= 1 && n <= 8) c->residentForced = n; }  // sweeps of the resident-slot rule (resident_slots)
             if (const char* e = std::getenv("NX_TRACE_BLOCKS_TOTAL")) {  // tuning experiments only
                 const int n = std::atoi(e);
                 if (n >= 1 && n <= 65536) { c->traceBlocks = c->shadowBlocks = n; c->traceGridForced = true; }

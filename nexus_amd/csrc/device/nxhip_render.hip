@@ -141,6 +141,35 @@ int graph_shape(const nxhip_ctx* c)
     return R * kBranchesPerLevel + 1u > c->queueBudget ? kShapeChain : kShapeParallel;
 }
 
+}  // namespace
+
+// Of R passes in flight, the slots that share the chip at once: what trace_blocks divides the chip by.  Where the parallel shape fits
+// the budget (graph_shape) that is every slot.  Where it does not, the slots are one lane each, the context's stream takes one hardware
+// queue and the R slot streams share the others (on four queues the runtime serves them with two and leaves one idle: never more than two
+// slots resident, profiles/queue_budget.txt section 4) - with the shares of R the slots that are resident leave wave slots empty.  The count
+// is budget - 1, the largest that loses nowhere: 64-frame passes, R = 4, four queues, forced counts 1 / 2 / 3 / 4: 2 973 / 2 943 / 2 934 /
+// 2 779 Msamples/s (4 = the shares of R, as before); one-frame passes through the facade, R = 3: 1 846 with the shares of three, 1 798 with
+// those of two; R = 6: 2 019 -> 2 147 with three, 2 073 with two (profiles/resident_slots.txt).  Only the grids follow this count: the
+// round robin, the graph shape, the tail rule and the flavor keep the caller's R (small passes want all R streams to issue ahead:
+// four-frame passes, R = 6, 2 164 with the round robin over six slots against 1 945 over two).  A pure function of (R, budget); never
+// above R, never below 1, never falling as the budget grows.
+uint32_t nxd::resident_slots_for(uint32_t passes, uint32_t budget)
+{
+    if (passes <= 1u) return 1u;
+    if (passes * kBranchesPerLevel + 1u <= budget) return passes;
+    return std::min(passes, budget > 2u ? budget - 1u : 1u);
+}
+
+namespace {
+
+uint32_t resident_slots(const nxhip_ctx* c)
+{
+    const uint32_t R = std::max(1u, effective_slots(c));
+    if (R <= 1u) return 1u;
+    if (c->residentForced > 0) return std::min(R, (uint32_t)c->residentForced);  // (sweeps only: NX_TUNING_KNOBS)
+    return resident_slots_for(R, c->queueBudget);
+}
+
 // Workgroups of a persistent trace launch.  The grid that fills the chip (6 workgroups per CU) is right for ONE large pass.
 // With several passes in flight every slot's closest-hit and any-hit launches would each claim the whole chip and the short
 // logic / shade kernels of the other slots queue behind their drains (one frame per pass, 6 in flight: 580 Msamples/s with
@@ -151,7 +180,7 @@ int trace_blocks(const nxhip_ctx* c, int fullGrid)
 {
     if (c->traceGridForced) return fullGrid;
     const int maxPerCU = std::max(1, fullGrid / std::max(1, c->numCUs));
-    const int R = (int)std::max(1u, effective_slots(c));
+    const int R = (int)resident_slots(c);  // (the slots that share the chip, not the passes that may await their accumulate)
     const bool small = pass_size_in_frames(c) <= 8.0;
     int perCU;
     // (round 5, with the thin level taking the drains: 4 per CU for a small single pass — 1 / 2 / 4 / 8 frames per pass 648 / 914 / 1 347 /
@@ -742,7 +771,8 @@ try {
     // exactly the single-pass behaviour)
     const uint32_t R = std::max(1u, effective_slots(c));
     if (c->nextSlot >= R) c->nextSlot = 0;
-    PassSlot* q = render_slot(c, R, c->nextSlot);
+    const uint32_t slot = c->nextSlot;
+    PassSlot* q = render_slot(c, R, slot);
     c->nextSlot = (c->nextSlot + 1) % R;
     if (c->entryPoints) NX_TRY(ensure_entry_table(c, q));  // the slot's entry-state table follows the pixel set (one state per run of 64 local pixels)
     NX_TRY(upload_state(c));
@@ -820,6 +850,7 @@ try {
     q->awaitingAccumulate = true;
     c->pending.push_back(q);
     c->lastRendered = q;
+    c->lastSlotIndex = slot;
     c->frameNumber = frameLast;
     return NXHIP_OK;
 } NX_CATCH("nxhip_render_frame")
@@ -1083,6 +1114,20 @@ int nxhip_get_queue_budget(nxhip_ctx* c, uint32_t* queues, uint32_t* chained, ui
 }
 
 uint32_t nxhip_queue_budget_from_text(const char* text) { return queue_budget_from_text(text); }
+
+uint32_t nxhip_resident_slots_for(uint32_t passes, uint32_t budget) { return resident_slots_for(passes, budget); }
+
+// What a pass issued now would be sized and placed by: the resident slots, the closest-hit launches' grid (trace_blocks), and which of
+// the R slots the last pass rendered in.
+int nxhip_debug_resident_slots(nxhip_ctx* c, uint32_t* resident, uint32_t* traceBlocks, uint32_t* slotOfLastPass)
+{
+    NX_DEBUG_HOOK("nxhip_debug_resident_slots");  // (first: a release library refuses whatever it is handed)
+    NX_CHECK_CTX(c);
+    if (resident) *resident = resident_slots(c);
+    if (traceBlocks) *traceBlocks = (uint32_t)trace_blocks(c, c->traceBlocks);
+    if (slotOfLastPass) *slotOfLastPass = c->lastSlotIndex;
+    return NXHIP_OK;
+}
 
 // The graph the last pass replayed, as the runtime holds it (counted from the hipGraph itself when the instance was built:
 // measure_graph): kernel nodes, dependency edges, and the largest number of nodes that wait for one and the same node.
