@@ -117,8 +117,24 @@ def lib():
     return L
 
 
+_F32, _U32 = np.float32, np.uint32  # (the batch hooks' column types)
+
+
 def _ptr(a):
     return a.ctypes.data_as(C.c_void_p)
+
+
+def _cols(*specs):
+    """the inputs of a batch hook, one (values, dtype, k) each, as contiguous arrays of `dtype`: (n, k), or (n,) for k == 1 — all of one n.
+    (values None: an optional input that is left out, None back)"""
+    cols = [None if a is None else np.ascontiguousarray(a, dtype=dt).reshape(-1, *((k,) if k != 1 else ())) for a, dt, k in specs]
+    assert len({len(a) for a in cols if a is not None}) <= 1, "the inputs of a batch hook must have equal lengths"
+    return cols
+
+
+def _outs(n, *specs):
+    """the outputs of a batch hook for n items, one (dtype, k) each, zeroed: (n, k), or (n,) for k == 1 (a spec of None: None back)"""
+    return [None if s is None else np.zeros((n, s[1]) if s[1] != 1 else n, dtype=s[0]) for s in specs]
 
 
 def check(rc, what=""):
@@ -549,86 +565,59 @@ class Context:
     def medium_density_batch(self, points):
         """the density grid's lookup at points[k], and the majorant of the brick the walk would start in there — a test hook:
         (rho float32[n], majorant float32[n])"""
-        p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
-        rho, maj = np.zeros(len(p), dtype=np.float32), np.zeros(len(p), dtype=np.float32)
-        check(self.L.nxhip_medium_density_batch(self.h, _ptr(p), len(p), _ptr(rho), _ptr(maj)), "nxhip_medium_density_batch")
+        p, = _cols((points, _F32, 3))
+        rho, maj = _outs(len(p), (_F32, 1), (_F32, 1))
+        self._hook("nxhip_medium_density_batch", p, len(p), rho, maj)
         return rho, maj
 
     def medium_track_batch(self, origin, direction, t_end, seed):
         """the walk through the density grid for rays (origin[k], direction[k]) that end at t_end[k] (inf: a miss), in both modes, each from
         the xorshift32 state seed[k] != 0 — a test hook: (scatter_t float32[n], -1 where the free flight meets no real collision;
         transmittance float32[n] of the ratio tracking; steps uint32[n, 2]: iterations | tentative collisions << 16 of the two walks)"""
-        o = np.ascontiguousarray(origin, dtype=np.float32).reshape(-1, 3)
-        d = np.ascontiguousarray(direction, dtype=np.float32).reshape(-1, 3)
-        te = np.ascontiguousarray(t_end, dtype=np.float32).reshape(-1)
-        sd = np.ascontiguousarray(seed, dtype=np.uint32).reshape(-1)
-        assert len(o) == len(d) == len(te) == len(sd)
-        st, tr = np.zeros(len(o), dtype=np.float32), np.zeros(len(o), dtype=np.float32)
-        steps = np.zeros((len(o), 2), dtype=np.uint32)
-        check(self.L.nxhip_medium_track_batch(self.h, _ptr(o), _ptr(d), _ptr(te), _ptr(sd), len(o), _ptr(st), _ptr(tr), _ptr(steps)), "nxhip_medium_track_batch")
+        o, d, te, sd = _cols((origin, _F32, 3), (direction, _F32, 3), (t_end, _F32, 1), (seed, _U32, 1))
+        st, tr, steps = _outs(len(o), (_F32, 1), (_F32, 1), (_U32, 2))
+        self._hook("nxhip_medium_track_batch", o, d, te, sd, len(o), st, tr, steps)
         return st, tr, steps
 
     def medium_segment_batch(self, origin, direction, t_end, xi):
         """the medium's segment rule, transmittance and free flight for rays (origin[k], direction[k]) that end at t_end[k] (inf: a miss) with
         the random number xi[k] in [0, 1) — a test hook: (t0, length, transmittance, scatter_t) float32[n] each; scatter_t is -1 where the
         flight does not scatter"""
-        o = np.ascontiguousarray(origin, dtype=np.float32).reshape(-1, 3)
-        d = np.ascontiguousarray(direction, dtype=np.float32).reshape(-1, 3)
-        te = np.ascontiguousarray(t_end, dtype=np.float32).reshape(-1)
-        x = np.ascontiguousarray(xi, dtype=np.float32).reshape(-1)
-        assert len(o) == len(d) == len(te) == len(x)
-        out = [np.zeros(len(o), dtype=np.float32) for _ in range(4)]
-        check(self.L.nxhip_medium_segment_batch(self.h, _ptr(o), _ptr(d), _ptr(te), _ptr(x), len(o), *[_ptr(a) for a in out]), "nxhip_medium_segment_batch")
+        o, d, te, x = _cols((origin, _F32, 3), (direction, _F32, 3), (t_end, _F32, 1), (xi, _F32, 1))
+        out = _outs(len(o), *[(_F32, 1)] * 4)
+        self._hook("nxhip_medium_segment_batch", o, d, te, x, len(o), *out)
         return tuple(out)
 
     def medium_phase_batch(self, dir_in, xi1, xi2):
         """the continuation the medium's scatter kernel draws about the direction of travel dir_in[k] from (xi1[k], xi2[k]) in [0, 1)^2 — a test
         hook: (direction float32[n, 3], pdf float32[n])"""
-        d = np.ascontiguousarray(dir_in, dtype=np.float32).reshape(-1, 3)
-        a = np.ascontiguousarray(xi1, dtype=np.float32).reshape(-1)
-        b = np.ascontiguousarray(xi2, dtype=np.float32).reshape(-1)
-        assert len(d) == len(a) == len(b)
-        out = np.zeros((len(d), 3), dtype=np.float32)
-        pdf = np.zeros(len(d), dtype=np.float32)
-        check(self.L.nxhip_medium_phase_batch(self.h, _ptr(d), _ptr(a), _ptr(b), len(d), _ptr(out), _ptr(pdf)), "nxhip_medium_phase_batch")
+        d, a, b = _cols((dir_in, _F32, 3), (xi1, _F32, 1), (xi2, _F32, 1))
+        out, pdf = _outs(len(d), (_F32, 3), (_F32, 1))
+        self._hook("nxhip_medium_phase_batch", d, a, b, len(d), out, pdf)
         return out, pdf
 
     def shading_frame_batch(self, instance, tri_idx, hit_uv, ray_dir):
         """what the material kernels hand their sampling code for hits on triangles tri_idx[k] of `instance` at barycentrics hit_uv[k],
         reached along ray_dir[k] — a test hook: (shading normal float32[n, 3], roughness float32[n], fell_back bool[n])"""
-        t = np.ascontiguousarray(tri_idx, dtype=np.uint32).reshape(-1)
-        uv = np.ascontiguousarray(hit_uv, dtype=np.float32).reshape(-1, 2)
-        d = np.ascontiguousarray(ray_dir, dtype=np.float32).reshape(-1, 3)
-        assert len(t) == len(uv) == len(d)
-        normal = np.zeros((len(t), 3), dtype=np.float32)
-        roughness = np.zeros(len(t), dtype=np.float32)
-        fell = np.zeros(len(t), dtype=np.uint32)
-        check(self.L.nxhip_shading_frame_batch(self.h, int(instance), _ptr(t), _ptr(uv), _ptr(d), len(t), _ptr(normal), _ptr(roughness), _ptr(fell)),
-              "nxhip_shading_frame_batch")
+        t, uv, d = _cols((tri_idx, _U32, 1), (hit_uv, _F32, 2), (ray_dir, _F32, 3))
+        normal, roughness, fell = _outs(len(t), (_F32, 3), (_F32, 1), (_U32, 1))
+        self._hook("nxhip_shading_frame_batch", int(instance), t, uv, d, len(t), normal, roughness, fell)
         return normal, roughness, fell != 0
 
     def material_inputs_batch(self, instance, tri_idx, hit_uv):
         """base colour, roughness and metalness the BSDF of an NX_MAT_METALROUGH material receives for hits on triangles tri_idx[k] of
         `instance` at barycentrics hit_uv[k] — a test hook: (c float32[n, 3], r float32[n], m float32[n])"""
-        t = np.ascontiguousarray(tri_idx, dtype=np.uint32).reshape(-1)
-        uv = np.ascontiguousarray(hit_uv, dtype=np.float32).reshape(-1, 2)
-        assert len(t) == len(uv)
-        out = np.zeros((len(t), 5), dtype=np.float32)
-        check(self.L.nxhip_material_inputs_batch(self.h, int(instance), _ptr(t), _ptr(uv), len(t), _ptr(out)), "nxhip_material_inputs_batch")
+        t, uv = _cols((tri_idx, _U32, 1), (hit_uv, _F32, 2))
+        out, = _outs(len(t), (_F32, 5))
+        self._hook("nxhip_material_inputs_batch", int(instance), t, uv, len(t), out)
         return out[:, :3].copy(), out[:, 3].copy(), out[:, 4].copy()
 
     def analytic_light_sample_batch(self, light_index, origins, r):
         """the light sample's draw for analytic light `light_index` from every origin[k] with the random pair r[k] in [0, 1)^2 — a test hook:
         (direction float32[n, 3], tmax float32[n], factor float32[n, 3], ok bool[n])"""
-        o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
-        r = np.ascontiguousarray(r, dtype=np.float32).reshape(-1, 2)
-        assert len(o) == len(r)
-        direction = np.zeros((len(o), 3), dtype=np.float32)
-        tmax = np.zeros(len(o), dtype=np.float32)
-        factor = np.zeros((len(o), 3), dtype=np.float32)
-        ok = np.zeros(len(o), dtype=np.uint32)
-        check(self.L.nxhip_analytic_light_sample_batch(self.h, int(light_index), _ptr(o), _ptr(r), len(o), _ptr(direction), _ptr(tmax), _ptr(factor), _ptr(ok)),
-              "nxhip_analytic_light_sample_batch")
+        o, r = _cols((origins, _F32, 3), (r, _F32, 2))
+        direction, tmax, factor, ok = _outs(len(o), (_F32, 3), (_F32, 1), (_F32, 3), (_U32, 1))
+        self._hook("nxhip_analytic_light_sample_batch", int(light_index), o, r, len(o), direction, tmax, factor, ok)
         return direction, tmax, factor, ok != 0
 
     def upload_texture(self, kind, rgba8):
@@ -879,21 +868,17 @@ class Context:
     def env_sample_batch(self, r):
         """the environment sampler's draw for every pair r[k] in [0, 1)^2: (direction float32[n, 3], pdf float32[n], texel uint32[n] —
         y * W + x that the cdf inversion picked)"""
-        r = np.ascontiguousarray(r, dtype=np.float32).reshape(-1, 2)
-        direction = np.zeros((len(r), 3), dtype=np.float32)
-        pdf = np.zeros(len(r), dtype=np.float32)
-        texel = np.zeros(len(r), dtype=np.uint32)
-        check(self.L.nxhip_env_sample_batch(self.h, _ptr(r), len(r), _ptr(direction), _ptr(pdf), _ptr(texel)), "nxhip_env_sample_batch")
+        r, = _cols((r, _F32, 2))
+        direction, pdf, texel = _outs(len(r), (_F32, 3), (_F32, 1), (_U32, 1))
+        self._hook("nxhip_env_sample_batch", r, len(r), direction, pdf, texel)
         return direction, pdf, texel
 
     def env_eval_batch(self, directions, with_pdf=True):
         """the background for every direction, and (with_pdf, sampler on) the sampler's pdf there and the texel the direction's map
         coordinates fall in: (rgb float32[n, 3], pdf float32[n] or None, texel uint32[n] or None)"""
-        d = np.ascontiguousarray(directions, dtype=np.float32).reshape(-1, 3)
-        rgb = np.zeros((len(d), 3), dtype=np.float32)
-        pdf = np.zeros(len(d), dtype=np.float32) if with_pdf else None
-        texel = np.zeros(len(d), dtype=np.uint32) if with_pdf else None
-        check(self.L.nxhip_env_eval_batch(self.h, _ptr(d), len(d), _ptr(rgb), _ptr(pdf) if with_pdf else None, _ptr(texel) if with_pdf else None), "nxhip_env_eval_batch")
+        d, = _cols((directions, _F32, 3))
+        rgb, pdf, texel = _outs(len(d), (_F32, 3), (_F32, 1) if with_pdf else None, (_U32, 1) if with_pdf else None)
+        self._hook("nxhip_env_eval_batch", d, len(d), rgb, pdf, texel)
         return rgb, pdf, texel
 
     def set_light_sampling(self, mode):
@@ -920,10 +905,9 @@ class Context:
 
     def light_pick_batch(self, u):
         """the device's pick for every u in [0, 1): (entry uint32[], prob float32[]) — the table's walk and its P(entry)"""
-        u = np.ascontiguousarray(u, dtype=np.float32)
-        entry = np.zeros(len(u), dtype=np.uint32)
-        prob = np.zeros(len(u), dtype=np.float32)
-        check(self.L.nxhip_light_pick_batch(self.h, _ptr(u), len(u), _ptr(entry), _ptr(prob)), "nxhip_light_pick_batch")
+        u, = _cols((u, _F32, 1))
+        entry, prob = _outs(len(u), (_U32, 1), (_F32, 1))
+        self._hook("nxhip_light_pick_batch", u, len(u), entry, prob)
         return entry, prob
 
     def set_entry_points(self, on=True):
@@ -1246,31 +1230,34 @@ class Context:
         check(self.L.nxhip_trace_transmittance_batch(self.h, _ptr(rays), _ptr(tmax), len(rays), _ptr(out)), "nxhip_trace_transmittance_batch")
         return out
 
-    def _bsdf_batch(self, fn, name, material, queries):
+    def _hook(self, name, *args):
+        """the library's `name` on this context; arrays go as their addresses, None as a null pointer"""
+        check(getattr(self.L, name)(self.h, *[_ptr(a) if isinstance(a, np.ndarray) else a for a in args]), name)
+
+    def _bsdf_batch(self, name, material, queries):
         mat = np.ascontiguousarray(material, dtype=pod.MAT_DT).reshape(1)
-        q = np.ascontiguousarray(queries, dtype=pod.BSDF_QUERY_DT)
-        out = np.zeros(len(q), dtype=pod.BSDF_RESULT_DT)
-        check(fn(self.h, _ptr(mat), _ptr(q), len(q), _ptr(out)), name)
+        q, = _cols((queries, pod.BSDF_QUERY_DT, 1))
+        out, = _outs(len(q), (pod.BSDF_RESULT_DT, 1))
+        self._hook(name, mat, q, len(q), out)
         return out
 
     def bsdf_sample_batch(self, material, queries):
-        return self._bsdf_batch(self.L.nxhip_bsdf_sample_batch, "nxhip_bsdf_sample_batch", material, queries)
+        return self._bsdf_batch("nxhip_bsdf_sample_batch", material, queries)
 
     def bsdf_eval_batch(self, material, queries):
-        return self._bsdf_batch(self.L.nxhip_bsdf_eval_batch, "nxhip_bsdf_eval_batch", material, queries)
+        return self._bsdf_batch("nxhip_bsdf_eval_batch", material, queries)
 
     def tex2d_batch(self, kind, texture_id, uv):
-        uv = np.ascontiguousarray(uv, dtype=np.float32).reshape(-1, 2)
-        out = np.zeros((len(uv), 4), dtype=np.float32)
-        check(self.L.nxhip_tex2d_batch(self.h, TEXTURE_KINDS[kind], int(texture_id), _ptr(uv), len(uv), _ptr(out)), "nxhip_tex2d_batch")
+        uv, = _cols((uv, _F32, 2))
+        out, = _outs(len(uv), (_F32, 4))
+        self._hook("nxhip_tex2d_batch", TEXTURE_KINDS[kind], int(texture_id), uv, len(uv), out)
         return out
 
     def fmath_batch(self, op, a, b=None):
         """include/nexus_fmath.h on the device: out[i] = nxf_apply(op, a[i], b[i]) (op: pod.NXF_OP_*)"""
-        a = np.ascontiguousarray(a, dtype=np.float64)
-        bb = None if b is None else np.ascontiguousarray(b, dtype=np.float64)
-        out = np.zeros(len(a), dtype=np.float64)
-        check(self.L.nxhip_fmath_batch(self.h, int(op), _ptr(a), None if bb is None else _ptr(bb), len(a), _ptr(out)), "nxhip_fmath_batch")
+        a, b = _cols((a, np.float64, 1), (b, np.float64, 1))
+        out, = _outs(len(a), (np.float64, 1))
+        self._hook("nxhip_fmath_batch", int(op), a, b, len(a), out)
         return out
 
     def enable_trace_stats(self, on=True):

@@ -7,7 +7,7 @@
 #include <string>
 #include <vector>
 
-#include "nx_host.h"
+#include "nx_hookbatch.h"
 
 using namespace nxd;
 
@@ -557,33 +557,32 @@ try {
     return NXHIP_OK;
 } NX_CATCH("nxhip_read_light_table")
 
+// ... and for a pick: the table (brought up to date) has an entry, and weights that sum to something
+static int light_table_pickable(nxhip_ctx* c)
+{
+    if (c->lightEntries == 0u) return fail_invalid("nxhip_light_pick_batch: the light table is empty (no mesh light has a triangle)");
+    // a table whose weights sum to nothing is never sampled by the renderer (its cdf is a filler of ones): the hook refuses it too
+    LightHeader header{};
+    NX_SYNC_ALL(c);
+    NX_HIP(hipMemcpy(&header, c->lightHeader.p, sizeof header, hipMemcpyDeviceToHost));
+    if (header.valid == 0u) return fail_invalid("nxhip_light_pick_batch: the light table is invalid (the lights' weights sum to nothing): nothing can be picked");
+    return NXHIP_OK;
+}
+
 int nxhip_light_pick_batch(nxhip_ctx* c, const float* u, uint32_t count, uint32_t* entry, float* prob)
 try {
     NX_CHECK_CTX(c);
     if ((!u || !entry || !prob) && count) return fail_invalid("nxhip_light_pick_batch: null buffer");
     // before anything is launched: floor(u G) of a u outside [0, 1) — or of a NaN — is no index of the guide table
-    for (uint32_t k = 0; k < count; k++)
-        if (!(u[k] >= 0.0f && u[k] < 1.0f)) return fail_invalid("nxhip_light_pick_batch: u must be in [0, 1)");
+    if (!all_unit(u, count)) return fail_invalid("nxhip_light_pick_batch: u must be in [0, 1)");
     NX_TRY(light_table_ready(c, "nxhip_light_pick_batch"));
     if (count == 0) return NXHIP_OK;
-    if (c->lightEntries == 0u) return fail_invalid("nxhip_light_pick_batch: the light table is empty (no mesh light has a triangle)");
-    {   // a table whose weights sum to nothing is never sampled by the renderer (its cdf is a filler of ones): the hook refuses it too
-        LightHeader header{};
-        NX_SYNC_ALL(c);
-        NX_HIP(hipMemcpy(&header, c->lightHeader.p, sizeof header, hipMemcpyDeviceToHost));
-        if (header.valid == 0u) return fail_invalid("nxhip_light_pick_batch: the light table is invalid (the lights' weights sum to nothing): nothing can be picked");
-    }
-    DevBuf dU, dEntry, dProb;
-    NX_ALLOC(dU, (size_t)count * 4);
-    NX_ALLOC(dEntry, (size_t)count * 4);
-    NX_ALLOC(dProb, (size_t)count * 4);
-    NX_HIP(hipMemcpy(dU.p, u, (size_t)count * 4, hipMemcpyHostToDevice));
-    NX_HIP(launch_untimed(kernels::light_pick(), c->wideBlocks, kWideBlockThreads, c->stream, c->lightTable.as<LightEntry>(), c->lightGuide.as<uint32_t>(), c->lightGuideSize,
-                          c->lightEntries, dU.as<float>(), count, dEntry.as<uint32_t>(), dProb.as<float>()));
-    NX_SYNC_ALL(c);
-    NX_HIP(hipMemcpy(entry, dEntry.p, (size_t)count * 4, hipMemcpyDeviceToHost));
-    NX_HIP(hipMemcpy(prob, dProb.p, (size_t)count * 4, hipMemcpyDeviceToHost));
-    return NXHIP_OK;
+    NX_TRY(light_table_pickable(c));
+    HookBatch b(c, count);
+    const float* dU = b.in(u, 1);
+    uint32_t* dEntry = b.out(entry, 1);
+    float* dProb = b.out(prob, 1);
+    return b.run(kernels::light_pick(), c->lightTable.as<LightEntry>(), c->lightGuide.as<uint32_t>(), c->lightGuideSize, c->lightEntries, dU, count, dEntry, dProb);
 } NX_CATCH("nxhip_light_pick_batch")
 
 }  // extern "C"

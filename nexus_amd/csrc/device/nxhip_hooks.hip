@@ -1,11 +1,14 @@
 // nxhip_hooks.hip — kernel-level test hooks (ray batches, BSDF, texture, binary64 functions), trace statistics, kernel times.
 // (the C-ABI device layer declared in include/nexus_hip.h; helpers shared with the other nxhip_*.hip units: nx_host.h)
+// A columnar hook (`count` items as flat arrays in and out, one wide kernel) checks its arguments, then states its columns on a
+// HookBatch (nx_hookbatch.h) and calls run with the kernel of kernels:: — no allocation, copy or byte count of its own.  The
+// ray-batch hooks copy into queue regions instead (HookLayout).
 #include <algorithm>
 #include <cstring>
 #include <string>
 #include <vector>
 
-#include "nx_host.h"
+#include "nx_hookbatch.h"
 
 using namespace nxd;
 
@@ -63,20 +66,27 @@ static int run_trace_chunk(nxhip_ctx* c, bool anyHit, uint32_t n, bool transmit 
     return rc;
 }
 
+// What the ray-batch hooks bring up to date before they launch.  readsScene: the trace instance reads the shading records, the maps and
+// the triangles, so what a render does before its pass is done here too.
+static int ray_batch_ready(nxhip_ctx* c, bool readsScene)
+{
+    if (!c->h.tlasNodes) return fail_invalid("no TLAS has been set");
+    if (readsScene) {
+        NX_TRY(check_scene_ready(c));
+        if (c->shadeInstDirty) NX_TRY(refresh_shade_inst(c));
+    }
+    NX_TRY(ensure_slot_queues(c, c));
+    NX_TRY(upload_state(c));
+    return refresh_updated_blas(c);
+}
+
 int nxhip_trace_batch(nxhip_ctx* c, const nx_ray* rays, uint32_t count, nx_hit* hits)
 try {
     NX_CHECK_CTX(c);
     if (count == 0) return NXHIP_OK;
     if (!rays || !hits) return fail_invalid("nxhip_trace_batch: null buffer");
     NX_HIP(hipSetDevice(c->device));
-    if (!c->h.tlasNodes) return fail_invalid("no TLAS has been set");
-    if (c->materialsAlphaMask) {  // what a render does before its pass: the ALPHA_TEST instance reads the shading records, the maps and the triangles
-        NX_TRY(check_scene_ready(c));
-        if (c->shadeInstDirty) NX_TRY(refresh_shade_inst(c));
-    }
-    NX_TRY(ensure_slot_queues(c, c));
-    NX_TRY(upload_state(c));
-    NX_TRY(refresh_updated_blas(c));
+    NX_TRY(ray_batch_ready(c, c->materialsAlphaMask));  // (the ALPHA_TEST instance reads the scene)
     const uint32_t cap = c->pathCount;
     std::vector<float4> o(std::min(cap, count)), d(std::min(cap, count)), h(std::min(cap, count));
     std::vector<uint32_t> hi(std::min(cap, count));
@@ -115,14 +125,7 @@ static int shadow_batch(nxhip_ctx* c, const char* who, const nx_ray* rays, const
     if (count == 0) return NXHIP_OK;
     if (!rays || !tmax || (!occluded && !transmittance)) return fail_invalid(std::string(who) + ": null buffer");
     NX_HIP(hipSetDevice(c->device));
-    if (!c->h.tlasNodes) return fail_invalid("no TLAS has been set");
-    if (transmittance || c->materialsAlphaMask) {  // what a render does before its pass: the instance reads the shading records, the maps and the triangles
-        NX_TRY(check_scene_ready(c));
-        if (c->shadeInstDirty) NX_TRY(refresh_shade_inst(c));
-    }
-    NX_TRY(ensure_slot_queues(c, c));
-    NX_TRY(upload_state(c));
-    NX_TRY(refresh_updated_blas(c));
+    NX_TRY(ray_batch_ready(c, transmittance || c->materialsAlphaMask));  // (the TRANSMIT and ALPHA_TEST instances read the scene)
     const uint32_t cap = c->pathCount;
     const uint32_t m = std::min(cap, count);
     std::vector<float4> o(m), d(m), rad(m, make_float4(1.0f, 0.0f, 0.0f, 0.0f)), res(m);
@@ -191,17 +194,13 @@ static int bsdf_hook(nxhip_ctx* c, const nx_material* material, const nx_bsdf_qu
     if (material->type < NX_MAT_DIFFUSE || material->type > NX_MAT_METALROUGH) return fail_invalid("nxhip_bsdf_*_batch: unknown material type");
     if (count == 0) return NXHIP_OK;
     NX_HIP(hipSetDevice(c->device));
-    DevBuf dMat, dQ, dR;
-    NX_ALLOC(dMat, sizeof(nx_material));
-    NX_ALLOC(dQ, (size_t)count * sizeof(nx_bsdf_query));
-    NX_ALLOC(dR, (size_t)count * sizeof(nx_bsdf_result));
-    NX_HIP(hipMemcpy(dMat.p, material, sizeof(nx_material), hipMemcpyHostToDevice));
-    NX_HIP(hipMemcpy(dQ.p, queries, (size_t)count * sizeof(nx_bsdf_query), hipMemcpyHostToDevice));
+    HookBatch one(c, 1), b(c, count);  // (the material: a column of one item)
+    const nx_material* dMat = one.in(material, 1);
+    NX_TRY(one.rc);
+    const nx_bsdf_query* dQ = b.in(queries, 1);
+    nx_bsdf_result* dR = b.out(results, 1);
     // (NX_MAT_METALROUGH has a kernel of its own: nx_wavefront_metal.hip — the four reference types keep theirs)
-    NX_HIP(launch_untimed(material->type == NX_MAT_METALROUGH ? kernels::bsdf_hook_metal() : kernels::bsdf_hook(), c->wideBlocks, kWideBlockThreads, c->stream, dMat.as<nx_material>(), dQ.as<nx_bsdf_query>(), count, sample, dR.as<nx_bsdf_result>()));
-    NX_SYNC_ALL(c);
-    NX_HIP(hipMemcpy(results, dR.p, (size_t)count * sizeof(nx_bsdf_result), hipMemcpyDeviceToHost));
-    return NXHIP_OK;
+    return b.run(material->type == NX_MAT_METALROUGH ? kernels::bsdf_hook_metal() : kernels::bsdf_hook(), dMat, dQ, count, sample, dR);
 }
 
 int nxhip_bsdf_sample_batch(nxhip_ctx* c, const nx_material* material, const nx_bsdf_query* queries, uint32_t count, nx_bsdf_result* results)
@@ -219,31 +218,23 @@ int nxhip_tex2d_batch(nxhip_ctx* c, int kind, int textureId, const float* uv, ui
     NX_CHECK_CTX(c);
     if ((!uv || !rgba) && count) return fail_invalid("nxhip_tex2d_batch: null buffer");
     if (kind < 0 || kind > 4) return fail_invalid("nxhip_tex2d_batch: kind must be 0 .. 4");
-    if (kind == 3 && (textureId < 0 || (size_t)textureId >= c->normalMaps.size())) return fail_invalid("nxhip_tex2d_batch: no such normal map");
-    if (kind == 4 && (textureId < 0 || (size_t)textureId >= c->roughnessMaps.size())) return fail_invalid("nxhip_tex2d_batch: no such roughness map");
-    if (kind == 0 && (textureId < 0 || (size_t)textureId >= c->diffuseMaps.size())) return fail_invalid("nxhip_tex2d_batch: no such diffuse map");
-    if (kind == 1 && (textureId < 0 || (size_t)textureId >= c->emissiveMaps.size())) return fail_invalid("nxhip_tex2d_batch: no such emissive map");
+    // kind -> the table textureId indexes and what its maps are called (2: the environment map, which has no table)
+    const std::vector<TextureHost>* const tables[5] = {&c->diffuseMaps, &c->emissiveMaps, nullptr, &c->normalMaps, &c->roughnessMaps};
+    static const char* const names[5] = {"diffuse", "emissive", "environment", "normal", "roughness"};
+    if (kind != 2 && (textureId < 0 || (size_t)textureId >= tables[kind]->size())) return fail_invalid(std::string("nxhip_tex2d_batch: no such ") + names[kind] + " map");
     if (kind == 2 && !c->hdrMap.texels.p) return fail_invalid("nxhip_tex2d_batch: no environment map has been uploaded");
     if (count == 0) return NXHIP_OK;
     NX_HIP(hipSetDevice(c->device));
-    const TextureHost& th = kind == 0 ? c->diffuseMaps[textureId] : kind == 1 ? c->emissiveMaps[textureId] : kind == 3 ? c->normalMaps[textureId] : kind == 4 ? c->roughnessMaps[textureId] : c->hdrMap;
-    DevBuf dUv, dOut;
-    NX_ALLOC(dUv, (size_t)count * 8);
-    NX_ALLOC(dOut, (size_t)count * 16);
-    NX_HIP(hipMemcpy(dUv.p, uv, (size_t)count * 8, hipMemcpyHostToDevice));
-    if (kind >= 3) {  // a detail map: linear data, its own lookup (nx_texture.h tex2d_linear)
-        const TextureDev t{th.texels.as<uint32_t>(), th.width, th.height};
-        NX_HIP(launch_untimed(kernels::tex2d_linear_hook(), c->wideBlocks, kWideBlockThreads, c->stream, t, dUv.as<float>(), count, dOut.as<float4>()));
-    } else if (kind == 2 && c->hdrFloat) {  // a float environment map: its own lookup (nx_texture.h tex2d_float), alpha 1
-        NX_HIP(launch_untimed(kernels::tex2d_float_hook(), c->wideBlocks, kWideBlockThreads, c->stream, th.texels.as<float4>(), (int)th.width, (int)th.height, dUv.as<float>(), count,
-                              dOut.as<float4>()));
-    } else {
-        const TextureDev t{th.texels.as<uint32_t>(), th.width, th.height};
-        NX_HIP(launch_untimed(kernels::tex2d_hook(), c->wideBlocks, kWideBlockThreads, c->stream, t, c->srgbLut.as<float>(), dUv.as<float>(), count, dOut.as<float4>()));
-    }
-    NX_SYNC_ALL(c);
-    NX_HIP(hipMemcpy(rgba, dOut.p, (size_t)count * 16, hipMemcpyDeviceToHost));
-    return NXHIP_OK;
+    const TextureHost& th = kind == 2 ? c->hdrMap : (*tables[kind])[textureId];
+    HookBatch b(c, count);
+    const float* dUv = b.in(uv, 2);
+    float4* dOut = b.out(reinterpret_cast<float4*>(rgba), 1);
+    const TextureDev t{th.texels.as<uint32_t>(), th.width, th.height};
+    // a detail map: linear data, its own lookup (nx_texture.h tex2d_linear)
+    if (kind >= 3) return b.run(kernels::tex2d_linear_hook(), t, dUv, count, dOut);
+    // a float environment map: its own lookup (nx_texture.h tex2d_float), alpha 1
+    if (kind == 2 && c->hdrFloat) return b.run(kernels::tex2d_float_hook(), th.texels.as<float4>(), (int)th.width, (int)th.height, dUv, count, dOut);
+    return b.run(kernels::tex2d_hook(), t, c->srgbLut.as<float>(), dUv, count, dOut);
 }
 
 // ---- the environment sampler's hooks (env_hook_kernel) ----------------------------------------------
@@ -310,19 +301,12 @@ static int env_hook(nxhip_ctx* c, int sample, const float* in, uint32_t inWidth,
 {
     NX_HIP(hipSetDevice(c->device));
     NX_TRY(upload_state(c));
-    DevBuf dIn, dVec, dPdf, dTexel;
-    NX_ALLOC(dIn, (size_t)count * inWidth * 4);
-    NX_ALLOC(dVec, (size_t)count * 12);
-    if (pdf) NX_ALLOC(dPdf, (size_t)count * 4);
-    if (texel) NX_ALLOC(dTexel, (size_t)count * 4);
-    NX_HIP(hipMemcpy(dIn.p, in, (size_t)count * inWidth * 4, hipMemcpyHostToDevice));
-    NX_HIP(launch_untimed(kernels::env_hook(), c->wideBlocks, kWideBlockThreads, c->stream, c->dState.as<DeviceState>(), sample, dIn.as<float>(), count, dVec.as<float>(),
-                          pdf ? dPdf.as<float>() : nullptr, texel ? dTexel.as<uint32_t>() : nullptr));
-    NX_SYNC_ALL(c);
-    NX_HIP(hipMemcpy(vec, dVec.p, (size_t)count * 12, hipMemcpyDeviceToHost));
-    if (pdf) NX_HIP(hipMemcpy(pdf, dPdf.p, (size_t)count * 4, hipMemcpyDeviceToHost));
-    if (texel) NX_HIP(hipMemcpy(texel, dTexel.p, (size_t)count * 4, hipMemcpyDeviceToHost));
-    return NXHIP_OK;
+    HookBatch b(c, count);
+    const float* dIn = b.in(in, inWidth);
+    float* dVec = b.out(vec, 3);
+    float* dPdf = b.out(pdf, 1);
+    uint32_t* dTexel = b.out(texel, 1);
+    return b.run(kernels::env_hook(), c->dState.as<DeviceState>(), sample, dIn, count, dVec, dPdf, dTexel);
 }
 
 int nxhip_env_sample_batch(nxhip_ctx* c, const float* r, uint32_t count, float* direction, float* pdf, uint32_t* texel)
@@ -330,8 +314,7 @@ try {
     NX_CHECK_CTX(c);
     if ((!r || !direction || !pdf || !texel) && count) return fail_invalid("nxhip_env_sample_batch: null buffer");
     // before anything is launched: floor(r G) of an r outside [0, 1) — or of a NaN — is no bucket of the guide tables
-    for (size_t k = 0; k < (size_t)count * 2; k++)
-        if (!(r[k] >= 0.0f && r[k] < 1.0f)) return fail_invalid("nxhip_env_sample_batch: r must be in [0, 1)");
+    if (!all_unit(r, (size_t)count * 2)) return fail_invalid("nxhip_env_sample_batch: r must be in [0, 1)");
     NX_TRY(env_hook_ready(c, "nxhip_env_sample_batch", true));
     if (count == 0) return NXHIP_OK;
     return env_hook(c, 1, r, 2, count, direction, pdf, texel);
@@ -341,8 +324,7 @@ int nxhip_env_eval_batch(nxhip_ctx* c, const float* direction, uint32_t count, f
 try {
     NX_CHECK_CTX(c);
     if ((!direction || !rgb) && count) return fail_invalid("nxhip_env_eval_batch: null buffer");
-    for (size_t k = 0; k < (size_t)count * 3; k++)
-        if (!(direction[k] >= -3.0e38f && direction[k] <= 3.0e38f)) return fail_invalid("nxhip_env_eval_batch: directions must be finite");
+    if (!all_finite(direction, (size_t)count * 3)) return fail_invalid("nxhip_env_eval_batch: directions must be finite");
     NX_TRY(env_hook_ready(c, "nxhip_env_eval_batch", pdf || texel));  // (the colours alone need no sampler)
     if (count == 0) return NXHIP_OK;
     return env_hook(c, 0, direction, 3, count, rgb, pdf, texel);
@@ -357,41 +339,19 @@ try {
     NX_CHECK_CTX(c);
     if (lightIndex >= c->h.alightCount) return fail_invalid("nxhip_analytic_light_sample_batch: no such analytic light (nxhip_set_analytic_lights)");
     if ((!origins3 || !r2 || !direction3 || !tmax || !factor3 || !ok) && count) return fail_invalid("nxhip_analytic_light_sample_batch: null buffer");
-    for (size_t k = 0; k < (size_t)count * 3; k++)
-        if (!(origins3[k] >= -3.0e38f && origins3[k] <= 3.0e38f)) return fail_invalid("nxhip_analytic_light_sample_batch: origins must be finite");
-    for (size_t k = 0; k < (size_t)count * 2; k++)
-        if (!(r2[k] >= 0.0f && r2[k] < 1.0f)) return fail_invalid("nxhip_analytic_light_sample_batch: r must be in [0, 1)");
+    if (!all_finite(origins3, (size_t)count * 3)) return fail_invalid("nxhip_analytic_light_sample_batch: origins must be finite");
+    if (!all_unit(r2, (size_t)count * 2)) return fail_invalid("nxhip_analytic_light_sample_batch: r must be in [0, 1)");
     if (count == 0) return NXHIP_OK;
     NX_HIP(hipSetDevice(c->device));
     NX_TRY(upload_state(c));
-    DevBuf dO, dR, dDir, dT, dF, dOk;
-    NX_ALLOC(dO, (size_t)count * 12);
-    NX_ALLOC(dR, (size_t)count * 8);
-    NX_ALLOC(dDir, (size_t)count * 12);
-    NX_ALLOC(dT, (size_t)count * 4);
-    NX_ALLOC(dF, (size_t)count * 12);
-    NX_ALLOC(dOk, (size_t)count * 4);
-    NX_HIP(hipMemcpy(dO.p, origins3, (size_t)count * 12, hipMemcpyHostToDevice));
-    NX_HIP(hipMemcpy(dR.p, r2, (size_t)count * 8, hipMemcpyHostToDevice));
-    NX_HIP(launch_untimed(kernels::alight_hook(), c->wideBlocks, kWideBlockThreads, c->stream, c->dState.as<DeviceState>(), lightIndex, dO.as<float>(), dR.as<float>(), count,
-                          dDir.as<float>(), dT.as<float>(), dF.as<float>(), dOk.as<uint32_t>()));
-    NX_SYNC_ALL(c);
-    NX_HIP(hipMemcpy(direction3, dDir.p, (size_t)count * 12, hipMemcpyDeviceToHost));
-    NX_HIP(hipMemcpy(tmax, dT.p, (size_t)count * 4, hipMemcpyDeviceToHost));
-    NX_HIP(hipMemcpy(factor3, dF.p, (size_t)count * 12, hipMemcpyDeviceToHost));
-    NX_HIP(hipMemcpy(ok, dOk.p, (size_t)count * 4, hipMemcpyDeviceToHost));
-    return NXHIP_OK;
+    HookBatch b(c, count);
+    const float *dO = b.in(origins3, 3), *dR = b.in(r2, 2);
+    float *dDir = b.out(direction3, 3), *dT = b.out(tmax, 1), *dF = b.out(factor3, 3);
+    uint32_t* dOk = b.out(ok, 1);
+    return b.run(kernels::alight_hook(), c->dState.as<DeviceState>(), lightIndex, dO, dR, count, dDir, dT, dF, dOk);
 } NX_CATCH("nxhip_analytic_light_sample_batch")
 
 // ---- the medium's hooks (medium_segment_hook_kernel, medium_phase_hook_kernel) ----------------------
-
-// `n` floats of a hook's input or output, to or from the device
-static int medium_hook_in(DevBuf& d, const float* src, size_t n)
-{
-    NX_ALLOC(d, n * 4);
-    NX_HIP(hipMemcpy(d.p, src, n * 4, hipMemcpyHostToDevice));
-    return NXHIP_OK;
-}
 
 int nxhip_medium_segment_batch(nxhip_ctx* c, const float* origin, const float* dir, const float* tEnd, const float* xi, uint32_t count, float* t0, float* length,
                                float* transmittance, float* scatterT)
@@ -400,32 +360,18 @@ try {
     NX_CHECK_CTX(c);
     if (!c->h.mediumOn) return fail_invalid("nxhip_medium_segment_batch: no medium with sigmaT > 0 is set (nxhip_set_medium)");
     if ((!origin || !dir || !tEnd || !xi || !t0 || !length || !transmittance || !scatterT) && count) return fail_invalid("nxhip_medium_segment_batch: null buffer");
-    for (size_t k = 0; k < (size_t)count * 3; k++)
-        if (!(origin[k] >= -3.0e38f && origin[k] <= 3.0e38f) || !(dir[k] >= -3.0e38f && dir[k] <= 3.0e38f)) return fail_invalid("nxhip_medium_segment_batch: origins and directions must be finite");
-    for (size_t k = 0; k < (size_t)count; k++) {
+    if (!all_finite(origin, (size_t)count * 3) || !all_finite(dir, (size_t)count * 3)) return fail_invalid("nxhip_medium_segment_batch: origins and directions must be finite");
+    for (size_t k = 0; k < (size_t)count; k++) {  // (item by item: the first bad item decides the message)
         if (!(tEnd[k] > 0.0f)) return fail_invalid("nxhip_medium_segment_batch: tEnd must be positive (+inf allowed)");
-        if (!(xi[k] >= 0.0f && xi[k] < 1.0f)) return fail_invalid("nxhip_medium_segment_batch: xi must be in [0, 1)");
+        if (!all_unit(xi + k, 1)) return fail_invalid("nxhip_medium_segment_batch: xi must be in [0, 1)");
     }
     if (count == 0) return NXHIP_OK;
     NX_HIP(hipSetDevice(c->device));
     NX_TRY(upload_state(c));
-    DevBuf dO, dD, dT, dXi, dT0, dL, dTr, dS;
-    NX_TRY(medium_hook_in(dO, origin, (size_t)count * 3));
-    NX_TRY(medium_hook_in(dD, dir, (size_t)count * 3));
-    NX_TRY(medium_hook_in(dT, tEnd, count));
-    NX_TRY(medium_hook_in(dXi, xi, count));
-    NX_ALLOC(dT0, (size_t)count * 4);
-    NX_ALLOC(dL, (size_t)count * 4);
-    NX_ALLOC(dTr, (size_t)count * 4);
-    NX_ALLOC(dS, (size_t)count * 4);
-    NX_HIP(launch_untimed(kernels::medium_segment_hook(), c->wideBlocks, kWideBlockThreads, c->stream, c->dState.as<DeviceState>(), dO.as<float>(), dD.as<float>(), dT.as<float>(),
-                          dXi.as<float>(), count, dT0.as<float>(), dL.as<float>(), dTr.as<float>(), dS.as<float>()));
-    NX_SYNC_ALL(c);
-    NX_HIP(hipMemcpy(t0, dT0.p, (size_t)count * 4, hipMemcpyDeviceToHost));
-    NX_HIP(hipMemcpy(length, dL.p, (size_t)count * 4, hipMemcpyDeviceToHost));
-    NX_HIP(hipMemcpy(transmittance, dTr.p, (size_t)count * 4, hipMemcpyDeviceToHost));
-    NX_HIP(hipMemcpy(scatterT, dS.p, (size_t)count * 4, hipMemcpyDeviceToHost));
-    return NXHIP_OK;
+    HookBatch b(c, count);
+    const float *dO = b.in(origin, 3), *dD = b.in(dir, 3), *dT = b.in(tEnd, 1), *dXi = b.in(xi, 1);
+    float *dT0 = b.out(t0, 1), *dL = b.out(length, 1), *dTr = b.out(transmittance, 1), *dS = b.out(scatterT, 1);
+    return b.run(kernels::medium_segment_hook(), c->dState.as<DeviceState>(), dO, dD, dT, dXi, count, dT0, dL, dTr, dS);
 } NX_CATCH("nxhip_medium_segment_batch")
 
 int nxhip_medium_phase_batch(nxhip_ctx* c, const float* dirIn, const float* xi1, const float* xi2, uint32_t count, float* dirOut, float* pdf)
@@ -434,25 +380,15 @@ try {
     NX_CHECK_CTX(c);
     if (!c->h.mediumOn) return fail_invalid("nxhip_medium_phase_batch: no medium with sigmaT > 0 is set (nxhip_set_medium)");
     if ((!dirIn || !xi1 || !xi2 || !dirOut || !pdf) && count) return fail_invalid("nxhip_medium_phase_batch: null buffer");
-    for (size_t k = 0; k < (size_t)count * 3; k++)
-        if (!(dirIn[k] >= -3.0e38f && dirIn[k] <= 3.0e38f)) return fail_invalid("nxhip_medium_phase_batch: directions must be finite");
-    for (size_t k = 0; k < (size_t)count; k++)
-        if (!(xi1[k] >= 0.0f && xi1[k] < 1.0f) || !(xi2[k] >= 0.0f && xi2[k] < 1.0f)) return fail_invalid("nxhip_medium_phase_batch: xi1 and xi2 must be in [0, 1)");
+    if (!all_finite(dirIn, (size_t)count * 3)) return fail_invalid("nxhip_medium_phase_batch: directions must be finite");
+    if (!all_unit(xi1, count) || !all_unit(xi2, count)) return fail_invalid("nxhip_medium_phase_batch: xi1 and xi2 must be in [0, 1)");
     if (count == 0) return NXHIP_OK;
     NX_HIP(hipSetDevice(c->device));
     NX_TRY(upload_state(c));
-    DevBuf dD, dX1, dX2, dOut, dPdf;
-    NX_TRY(medium_hook_in(dD, dirIn, (size_t)count * 3));
-    NX_TRY(medium_hook_in(dX1, xi1, count));
-    NX_TRY(medium_hook_in(dX2, xi2, count));
-    NX_ALLOC(dOut, (size_t)count * 12);
-    NX_ALLOC(dPdf, (size_t)count * 4);
-    NX_HIP(launch_untimed(kernels::medium_phase_hook(), c->wideBlocks, kWideBlockThreads, c->stream, c->dState.as<DeviceState>(), dD.as<float>(), dX1.as<float>(), dX2.as<float>(), count,
-                          dOut.as<float>(), dPdf.as<float>()));
-    NX_SYNC_ALL(c);
-    NX_HIP(hipMemcpy(dirOut, dOut.p, (size_t)count * 12, hipMemcpyDeviceToHost));
-    NX_HIP(hipMemcpy(pdf, dPdf.p, (size_t)count * 4, hipMemcpyDeviceToHost));
-    return NXHIP_OK;
+    HookBatch b(c, count);
+    const float *dD = b.in(dirIn, 3), *dX1 = b.in(xi1, 1), *dX2 = b.in(xi2, 1);
+    float *dOut = b.out(dirOut, 3), *dPdf = b.out(pdf, 1);
+    return b.run(kernels::medium_phase_hook(), c->dState.as<DeviceState>(), dD, dX1, dX2, count, dOut, dPdf);
 } NX_CATCH("nxhip_medium_phase_batch")
 
 // ---- the density grid's hooks (medium_density_hook_kernel, medium_track_hook_kernel; the bricks as they are) -------------
@@ -482,20 +418,14 @@ try {
     NX_CHECK_CTX(c);
     if (!medium_grid_on(c)) return fail_invalid("nxhip_medium_density_batch: it needs a medium with sigmaT > 0 (nxhip_set_medium) and a density grid (nxhip_set_medium_density)");
     if ((!points3 || !rho || !majorant) && count) return fail_invalid("nxhip_medium_density_batch: null buffer");
-    for (size_t k = 0; k < (size_t)count * 3; k++)
-        if (!(points3[k] >= -3.0e38f && points3[k] <= 3.0e38f)) return fail_invalid("nxhip_medium_density_batch: points must be finite");
+    if (!all_finite(points3, (size_t)count * 3)) return fail_invalid("nxhip_medium_density_batch: points must be finite");
     if (count == 0) return NXHIP_OK;
     NX_HIP(hipSetDevice(c->device));
     NX_TRY(upload_state(c));
-    DevBuf dP, dRho, dM;
-    NX_TRY(medium_hook_in(dP, points3, (size_t)count * 3));
-    NX_ALLOC(dRho, (size_t)count * 4);
-    NX_ALLOC(dM, (size_t)count * 4);
-    NX_HIP(launch_untimed(kernels::medium_density_hook(), c->wideBlocks, kWideBlockThreads, c->stream, c->dState.as<DeviceState>(), dP.as<float>(), count, dRho.as<float>(), dM.as<float>()));
-    NX_SYNC_ALL(c);
-    NX_HIP(hipMemcpy(rho, dRho.p, (size_t)count * 4, hipMemcpyDeviceToHost));
-    NX_HIP(hipMemcpy(majorant, dM.p, (size_t)count * 4, hipMemcpyDeviceToHost));
-    return NXHIP_OK;
+    HookBatch b(c, count);
+    const float* dP = b.in(points3, 3);
+    float *dRho = b.out(rho, 1), *dM = b.out(majorant, 1);
+    return b.run(kernels::medium_density_hook(), c->dState.as<DeviceState>(), dP, count, dRho, dM);
 } NX_CATCH("nxhip_medium_density_batch")
 
 int nxhip_medium_track_batch(nxhip_ctx* c, const float* origin, const float* dir, const float* tEnd, const uint32_t* seed, uint32_t count, float* scatterT, float* transmittance,
@@ -506,8 +436,7 @@ try {
     if (!medium_grid_on(c)) return fail_invalid("nxhip_medium_track_batch: it needs a medium with sigmaT > 0 (nxhip_set_medium) and a density grid (nxhip_set_medium_density)");
     NX_TRY(check_medium_grid(c, "nxhip_medium_track_batch"));
     if ((!origin || !dir || !tEnd || !seed || !scatterT || !transmittance || !steps2) && count) return fail_invalid("nxhip_medium_track_batch: null buffer");
-    for (size_t k = 0; k < (size_t)count * 3; k++)
-        if (!(origin[k] >= -3.0e38f && origin[k] <= 3.0e38f) || !(dir[k] >= -3.0e38f && dir[k] <= 3.0e38f)) return fail_invalid("nxhip_medium_track_batch: origins and directions must be finite");
+    if (!all_finite(origin, (size_t)count * 3) || !all_finite(dir, (size_t)count * 3)) return fail_invalid("nxhip_medium_track_batch: origins and directions must be finite");
     for (size_t k = 0; k < (size_t)count; k++) {
         if (!(tEnd[k] > 0.0f)) return fail_invalid("nxhip_medium_track_batch: tEnd must be positive (+inf allowed)");
         if (seed[k] == 0u) return fail_invalid("nxhip_medium_track_batch: a seed may not be 0 (xorshift32 stays there)");
@@ -515,25 +444,30 @@ try {
     if (count == 0) return NXHIP_OK;
     NX_HIP(hipSetDevice(c->device));
     NX_TRY(upload_state(c));
-    DevBuf dO, dD, dT, dSeed, dS, dTr, dSteps;
-    NX_TRY(medium_hook_in(dO, origin, (size_t)count * 3));
-    NX_TRY(medium_hook_in(dD, dir, (size_t)count * 3));
-    NX_TRY(medium_hook_in(dT, tEnd, count));
-    NX_ALLOC(dSeed, (size_t)count * 4);
-    NX_HIP(hipMemcpy(dSeed.p, seed, (size_t)count * 4, hipMemcpyHostToDevice));
-    NX_ALLOC(dS, (size_t)count * 4);
-    NX_ALLOC(dTr, (size_t)count * 4);
-    NX_ALLOC(dSteps, (size_t)count * 8);
-    NX_HIP(launch_untimed(kernels::medium_track_hook(), c->wideBlocks, kWideBlockThreads, c->stream, c->dState.as<DeviceState>(), dO.as<float>(), dD.as<float>(), dT.as<float>(),
-                          dSeed.as<uint32_t>(), count, dS.as<float>(), dTr.as<float>(), dSteps.as<uint32_t>()));
-    NX_SYNC_ALL(c);
-    NX_HIP(hipMemcpy(scatterT, dS.p, (size_t)count * 4, hipMemcpyDeviceToHost));
-    NX_HIP(hipMemcpy(transmittance, dTr.p, (size_t)count * 4, hipMemcpyDeviceToHost));
-    NX_HIP(hipMemcpy(steps2, dSteps.p, (size_t)count * 8, hipMemcpyDeviceToHost));
-    return NXHIP_OK;
+    HookBatch b(c, count);
+    const float *dO = b.in(origin, 3), *dD = b.in(dir, 3), *dT = b.in(tEnd, 1);
+    const uint32_t* dSeed = b.in(seed, 1);
+    float *dS = b.out(scatterT, 1), *dTr = b.out(transmittance, 1);
+    uint32_t* dSteps = b.out(steps2, 2);
+    return b.run(kernels::medium_track_hook(), c->dState.as<DeviceState>(), dO, dD, dT, dSeed, count, dS, dTr, dSteps);
 } NX_CATCH("nxhip_medium_track_batch")
 
 // ---- the detail maps' hook (shading_frame_hook_kernel) ----------------------------------------------
+
+// The instance and the triangle indices of the two hooks that shade given hits (after check_scene_ready).  The triangle index is followed
+// without a bounds test on the device, as a hit record's is: checked here.  metalRough: the instance's material must be of that type.
+static int check_hit_columns(const nxhip_ctx* c, const char* name, uint32_t instanceIdx, const uint32_t* triIdx, uint32_t count, bool metalRough)
+{
+    const std::string who(name);
+    if (instanceIdx >= c->hostInstances.size()) return fail_invalid(who + ": no such instance");
+    const nx_bvh_instance& inst = c->hostInstances[instanceIdx];
+    if (inst.bvhIdx >= c->blas.size()) return fail_invalid(who + ": the instance refers to a BLAS id that has not been uploaded");
+    if (metalRough && c->hostMaterials[(size_t)inst.materialId].type != NX_MAT_METALROUGH) return fail_invalid(who + ": the instance's material is not an NX_MAT_METALROUGH");
+    const uint32_t triCount = c->blas[inst.bvhIdx].triCount;
+    for (uint32_t k = 0; k < count; k++)
+        if (triIdx[k] >= triCount) return fail_invalid(who + ": triangle index out of range");
+    return NXHIP_OK;
+}
 
 int nxhip_shading_frame_batch(nxhip_ctx* c, uint32_t instanceIdx, const uint32_t* triIdx, const float* hitUv, const float* rayDir, uint32_t count, float* normalOut,
                               float* roughnessOut, uint32_t* fellBack)
@@ -543,34 +477,17 @@ try {
     if ((!triIdx || !hitUv || !rayDir || !normalOut || !roughnessOut || !fellBack) && count) return fail_invalid("nxhip_shading_frame_batch: null buffer");
     NX_HIP(hipSetDevice(c->device));
     NX_TRY(check_scene_ready(c));
-    if (instanceIdx >= c->hostInstances.size()) return fail_invalid("nxhip_shading_frame_batch: no such instance");
-    // the triangle index is followed without a bounds test on the device, as a hit record's is: checked here
-    const nx_bvh_instance& inst = c->hostInstances[instanceIdx];
-    if (inst.bvhIdx >= c->blas.size()) return fail_invalid("nxhip_shading_frame_batch: the instance refers to a BLAS id that has not been uploaded");
-    const uint32_t triCount = c->blas[inst.bvhIdx].triCount;
-    for (uint32_t k = 0; k < count; k++)
-        if (triIdx[k] >= triCount) return fail_invalid("nxhip_shading_frame_batch: triangle index out of range");
+    NX_TRY(check_hit_columns(c, "nxhip_shading_frame_batch", instanceIdx, triIdx, count, false));
     if (count == 0) return NXHIP_OK;
     NX_TRY(refresh_updated_blas(c));
     if (c->shadeInstDirty) NX_TRY(refresh_shade_inst(c));
     NX_TRY(upload_state(c));
-    DevBuf dTri, dUv, dDir, dN, dR, dF;
-    NX_ALLOC(dTri, (size_t)count * 4);
-    NX_ALLOC(dUv, (size_t)count * 8);
-    NX_ALLOC(dDir, (size_t)count * 12);
-    NX_ALLOC(dN, (size_t)count * 12);
-    NX_ALLOC(dR, (size_t)count * 4);
-    NX_ALLOC(dF, (size_t)count * 4);
-    NX_HIP(hipMemcpy(dTri.p, triIdx, (size_t)count * 4, hipMemcpyHostToDevice));
-    NX_HIP(hipMemcpy(dUv.p, hitUv, (size_t)count * 8, hipMemcpyHostToDevice));
-    NX_HIP(hipMemcpy(dDir.p, rayDir, (size_t)count * 12, hipMemcpyHostToDevice));
-    NX_HIP(launch_untimed(kernels::shading_frame_hook(), c->wideBlocks, kWideBlockThreads, c->stream, c->dState.as<DeviceState>(), instanceIdx, dTri.as<uint32_t>(), dUv.as<float>(),
-                          dDir.as<float>(), count, dN.as<float>(), dR.as<float>(), dF.as<uint32_t>()));
-    NX_SYNC_ALL(c);
-    NX_HIP(hipMemcpy(normalOut, dN.p, (size_t)count * 12, hipMemcpyDeviceToHost));
-    NX_HIP(hipMemcpy(roughnessOut, dR.p, (size_t)count * 4, hipMemcpyDeviceToHost));
-    NX_HIP(hipMemcpy(fellBack, dF.p, (size_t)count * 4, hipMemcpyDeviceToHost));
-    return NXHIP_OK;
+    HookBatch b(c, count);
+    const uint32_t* dTri = b.in(triIdx, 1);
+    const float *dUv = b.in(hitUv, 2), *dDir = b.in(rayDir, 3);
+    float *dN = b.out(normalOut, 3), *dR = b.out(roughnessOut, 1);
+    uint32_t* dF = b.out(fellBack, 1);
+    return b.run(kernels::shading_frame_hook(), c->dState.as<DeviceState>(), instanceIdx, dTri, dUv, dDir, count, dN, dR, dF);
 } NX_CATCH("nxhip_shading_frame_batch")
 
 int nxhip_material_inputs_batch(nxhip_ctx* c, uint32_t instanceIdx, const uint32_t* triIdx, const float* hitUv, uint32_t count, float* out)
@@ -580,29 +497,16 @@ try {
     if ((!triIdx || !hitUv || !out) && count) return fail_invalid("nxhip_material_inputs_batch: null buffer");
     NX_HIP(hipSetDevice(c->device));
     NX_TRY(check_scene_ready(c));
-    if (instanceIdx >= c->hostInstances.size()) return fail_invalid("nxhip_material_inputs_batch: no such instance");
-    // the triangle index is followed without a bounds test on the device, as a hit record's is: checked here
-    const nx_bvh_instance& inst = c->hostInstances[instanceIdx];
-    if (inst.bvhIdx >= c->blas.size()) return fail_invalid("nxhip_material_inputs_batch: the instance refers to a BLAS id that has not been uploaded");
-    if (c->hostMaterials[(size_t)inst.materialId].type != NX_MAT_METALROUGH) return fail_invalid("nxhip_material_inputs_batch: the instance's material is not an NX_MAT_METALROUGH");
-    const uint32_t triCount = c->blas[inst.bvhIdx].triCount;
-    for (uint32_t k = 0; k < count; k++)
-        if (triIdx[k] >= triCount) return fail_invalid("nxhip_material_inputs_batch: triangle index out of range");
+    NX_TRY(check_hit_columns(c, "nxhip_material_inputs_batch", instanceIdx, triIdx, count, true));
     if (count == 0) return NXHIP_OK;
     NX_TRY(refresh_updated_blas(c));
     if (c->shadeInstDirty) NX_TRY(refresh_shade_inst(c));
     NX_TRY(upload_state(c));
-    DevBuf dTri, dUv, dOut;
-    NX_ALLOC(dTri, (size_t)count * 4);
-    NX_ALLOC(dUv, (size_t)count * 8);
-    NX_ALLOC(dOut, (size_t)count * 20);
-    NX_HIP(hipMemcpy(dTri.p, triIdx, (size_t)count * 4, hipMemcpyHostToDevice));
-    NX_HIP(hipMemcpy(dUv.p, hitUv, (size_t)count * 8, hipMemcpyHostToDevice));
-    NX_HIP(launch_untimed(kernels::material_inputs_hook(), c->wideBlocks, kWideBlockThreads, c->stream, c->dState.as<DeviceState>(), instanceIdx, dTri.as<uint32_t>(), dUv.as<float>(), count,
-                          dOut.as<float>()));
-    NX_SYNC_ALL(c);
-    NX_HIP(hipMemcpy(out, dOut.p, (size_t)count * 20, hipMemcpyDeviceToHost));
-    return NXHIP_OK;
+    HookBatch b(c, count);
+    const uint32_t* dTri = b.in(triIdx, 1);
+    const float* dUv = b.in(hitUv, 2);
+    float* dOut = b.out(out, 5);  // (c, r, m)
+    return b.run(kernels::material_inputs_hook(), c->dState.as<DeviceState>(), instanceIdx, dTri, dUv, count, dOut);
 } NX_CATCH("nxhip_material_inputs_batch")
 
 int nxhip_fmath_batch(nxhip_ctx* c, int op, const double* a, const double* b, uint32_t count, double* out)
@@ -612,18 +516,10 @@ int nxhip_fmath_batch(nxhip_ctx* c, int op, const double* a, const double* b, ui
     if ((!a || !out) && count) return fail_invalid("nxhip_fmath_batch: null buffer");
     if (count == 0) return NXHIP_OK;
     NX_HIP(hipSetDevice(c->device));
-    DevBuf dA, dB, dOut;
-    NX_ALLOC(dA, (size_t)count * 8);
-    NX_ALLOC(dOut, (size_t)count * 8);
-    NX_HIP(hipMemcpy(dA.p, a, (size_t)count * 8, hipMemcpyHostToDevice));
-    if (b) {
-        NX_ALLOC(dB, (size_t)count * 8);
-        NX_HIP(hipMemcpy(dB.p, b, (size_t)count * 8, hipMemcpyHostToDevice));
-    }
-    NX_HIP(launch_untimed(kernels::fmath_hook(), c->wideBlocks, kWideBlockThreads, c->stream, op, dA.as<double>(), b ? dB.as<double>() : nullptr, count, dOut.as<double>()));
-    NX_SYNC_ALL(c);
-    NX_HIP(hipMemcpy(out, dOut.p, (size_t)count * 8, hipMemcpyDeviceToHost));
-    return NXHIP_OK;
+    HookBatch hb(c, count);
+    const double *dA = hb.in(a, 1), *dB = hb.in(b, 1);  // (b == nullptr: a one-operand op, and the kernel is handed a null pointer)
+    double* dOut = hb.out(out, 1);
+    return hb.run(kernels::fmath_hook(), op, dA, dB, count, dOut);
 }
 
 int nxhip_enable_kernel_timing(nxhip_ctx* c, int enable)

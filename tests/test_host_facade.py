@@ -66,7 +66,7 @@ def test_the_benched_configuration_through_the_facade_equals_the_ctypes_path(gpu
     built on the device, pixel-keyed random numbers, extended conductor, 8 x 8 pixel tiles (nxhip_set_pixel_order: the order comes from
     the LIBRARY now, not from Python), entry points, several frames per Render() call — rendered through nexus::Scene / PathTracer
     give the RGBA8 image the ctypes path gives for workloads.config2 built in memory.  (examples/nexus_bench.cpp is this call
-    sequence in C++; bench.py --through-facade times it.)"""
+    sequence in C++; tools/facade_bench.py times it.)"""
     from nexus_amd import multigpu, workloads
 
     W, H, nu, nv, frames = 256, 144, 96, 48, 4
