@@ -1,7 +1,7 @@
 // nexus_render — the reference's render loop (Renderer.cpp:41-77: scene.Update, UpdateDeviceScene, Render) driven headless
 // through the kept C++ host API: load a .glb / .obj, path-trace `frames` frames on an MI355X, write the image as a PPM.
 //
-//   nexus_render [--denoise] [--adaptive THRESHOLD [--max-frames N]] [--light-sampling uniform|power] [--transparent-shadows] [--env-float FILE.hdr] [--env-sampling]
+//   nexus_render [--denoise] [--adaptive THRESHOLD [--max-frames N]] [--light-sampling uniform|power|position] [--transparent-shadows] [--env-float FILE.hdr] [--env-sampling]
 //                [--no-detail-maps] [--metal-rough] [--alpha-modes] [--fog SIGMA [--fog-albedo R G B] [--fog-g G] [--fog-box X0 Y0 Z0 X1 Y1 Z1] [--fog-grid FILE.npy]]
 //                [--point-light X Y Z INTENSITY] [--sun DX DY DZ IRRADIANCE] [--time T [--animation K]] <dir/> <file.glb|file.obj> <out.ppm> [width height frames pathLength]
 //                [eyeX eyeY eyeZ fwdX fwdY fwdZ hfovDeg]
@@ -11,6 +11,8 @@
 //   at most N frames, default 1024; `frames` is ignored).  Combines with --denoise.  The image is not an unbiased estimate.
 // --light-sampling power: the light sample picks among the mesh lights' triangles in proportion to area x emitted luminance
 //   (nxhip_set_light_sampling; default uniform: the reference's rule).  Same expectation, less noise under small or dim emitters.
+// --light-sampling position: power mode with the shading point's position in the probability, from a light tree built on the device
+//   (nxhip_set_light_importance): less noise where many lights are far from most of what they could light.
 // --transparent-shadows: opacity (glTF baseColorFactor[3]) and the alpha of the base colour texture attenuate shadow rays instead of
 //   blocking them (nxhip_set_shadow_transmittance; default off: the reference's rule, under which a see-through surface casts a solid shadow).
 // --env-float FILE.hdr: a Radiance .hdr file as the environment, as the linear float radiance it holds (Scene::AddHDRMapFloat,
@@ -53,6 +55,7 @@ int main(int argc, char** argv)
     float threshold = 0.0f;
     uint32_t maxFrames = 1024;
     int lightSampling = NXHIP_LIGHTS_UNIFORM;
+    int lightImportance = NXHIP_LIGHT_IMPORTANCE_POWER;
     bool transparentShadows = false;
     std::string envFloat;
     bool envSampling = false;
@@ -81,11 +84,12 @@ int main(int argc, char** argv)
             used = 2;
         } else if (opt == "--light-sampling" && argc > 2) {
             const std::string mode = argv[2];
-            if (mode != "uniform" && mode != "power") {
-                std::fprintf(stderr, "--light-sampling: uniform or power\n");
+            if (mode != "uniform" && mode != "power" && mode != "position") {
+                std::fprintf(stderr, "--light-sampling: uniform, power or position\n");
                 return 2;
             }
-            lightSampling = mode == "power" ? NXHIP_LIGHTS_POWER : NXHIP_LIGHTS_UNIFORM;
+            lightSampling = mode == "uniform" ? NXHIP_LIGHTS_UNIFORM : NXHIP_LIGHTS_POWER;
+            lightImportance = mode == "position" ? NXHIP_LIGHT_IMPORTANCE_POSITION : NXHIP_LIGHT_IMPORTANCE_POWER;
             used = 2;
         } else if (opt == "--transparent-shadows") {
             transparentShadows = true;
@@ -151,7 +155,7 @@ int main(int argc, char** argv)
         return 2;
     }
     if (argc < 4) {
-        std::fprintf(stderr, "usage: %s [--denoise] [--adaptive THRESHOLD [--max-frames N]] [--light-sampling uniform|power] [--transparent-shadows] [--env-float FILE.hdr] [--env-sampling] [--no-detail-maps] [--metal-rough] [--alpha-modes] [--fog SIGMA [--fog-albedo R G B] [--fog-g G] [--fog-box X0 Y0 Z0 X1 Y1 Z1] [--fog-grid FILE.npy]] [--point-light X Y Z INTENSITY] [--sun DX DY DZ IRRADIANCE] [--time T [--animation K]] <dir/> <file.glb|file.obj> <out.ppm> [width height frames pathLength] [eye(3) forward(3) hfov]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s [--denoise] [--adaptive THRESHOLD [--max-frames N]] [--light-sampling uniform|power|position] [--transparent-shadows] [--env-float FILE.hdr] [--env-sampling] [--no-detail-maps] [--metal-rough] [--alpha-modes] [--fog SIGMA [--fog-albedo R G B] [--fog-g G] [--fog-box X0 Y0 Z0 X1 Y1 Z1] [--fog-grid FILE.npy]] [--point-light X Y Z INTENSITY] [--sun DX DY DZ IRRADIANCE] [--time T [--animation K]] <dir/> <file.glb|file.obj> <out.ppm> [width height frames pathLength] [eye(3) forward(3) hfov]\n", argv[0]);
         return 2;
     }
     // a program built against these headers and run with another build of libnexus_amd.so gets an error string here, not a GPU fault
@@ -229,6 +233,7 @@ int main(int argc, char** argv)
         }
         if (denoise) pathTracer.SetFeatureBuffers(true);
         pathTracer.SetLightSampling(lightSampling);
+        pathTracer.SetLightImportance(lightImportance);
         pathTracer.SetShadowTransmittance(transparentShadows ? NXHIP_SHADOWS_TRANSMIT : NXHIP_SHADOWS_OPAQUE);
         uint32_t activePixels = 0;
         if (adaptive) {

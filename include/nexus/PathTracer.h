@@ -60,6 +60,10 @@ public:
     // rule and the default) or NXHIP_LIGHTS_POWER (1: in proportion to area x emitted luminance, from a table built on the device).
     // Same expectation either way: may be switched between frames.
     void SetLightSampling(int mode);
+    // What an entry's probability depends on in NXHIP_LIGHTS_POWER (nxhip_set_light_importance): NXHIP_LIGHT_IMPORTANCE_POWER (0, the
+    // default) or NXHIP_LIGHT_IMPORTANCE_POSITION (1: the shading point's position too, from a light tree built on the device).
+    // Remembered in every mode; same expectation either way.
+    void SetLightImportance(int importance);
     // Transparent shadows (nxhip_set_shadow_transmittance): NXHIP_SHADOWS_OPAQUE (0, the reference's rule and the default: a shadow ray ends
     // at the first triangle) or NXHIP_SHADOWS_TRANSMIT (1: every crossing multiplies the ray's transmittance by 1 - opacity x alpha(uv)).
     void SetShadowTransmittance(int mode);

@@ -383,6 +383,66 @@ int nxhip_set_env_sampling(nxhip_ctx *ctx, int enable);
  * In POWER mode a light list that names one instance twice is refused by the render (NXHIP_ERR_INVALID).  Another mode: NXHIP_ERR_INVALID. */
 enum { NXHIP_LIGHTS_UNIFORM = 0, NXHIP_LIGHTS_POWER = 1 };
 int nxhip_set_light_sampling(nxhip_ctx *ctx, int mode);
+/* Extension, a refinement of NXHIP_LIGHTS_POWER: what the probability of a table entry depends on.
+ *   NXHIP_LIGHT_IMPORTANCE_POWER (default)  the table's P(i), the same at every shading point.
+ *   NXHIP_LIGHT_IMPORTANCE_POSITION         ... and the shading point's position p: a bounding hierarchy over the table's entries (the
+ *                                           light BVH of Conty & Kulla 2018 and of pbrt-v4), descended per light sample with a
+ *                                           probability proportional to a bound on each subtree's contribution at p.  The emitters
+ *                                           here are two-sided, so the method's orientation half is not needed: the importance
+ *                                           depends on p alone, which serves surfaces and the medium's scatter points alike.
+ * The setting is remembered in every light-sampling mode and has an effect only while the mode is NXHIP_LIGHTS_POWER: in
+ * NXHIP_LIGHTS_UNIFORM nothing is allocated, built or launched and frames are what they were, bit for bit.  Unbiased either way; the
+ * expectation of a frame does not change, so the setting may be switched at any time, also between accumulated frames.
+ *
+ * The tree.  Its entries are the light table's, in the table's order; N entries.  An entry's weight w is the table's formula — world-space
+ * area x Y — evaluated in binary64 throughout: the binary32 corners, matrix, emissive factor (or the map's mean before its rounding) and
+ * intensity as given, every operation in binary64, the same clamp (negative or not finite: 0).  The table's own w takes the binary32
+ * area of the light sample's density; the tree does not need to agree with it to the last bit — sampler and MIS weight both read the
+ * tree — and binary32 loses up to 1e-5 of the area of a small triangle far from the origin.  G =
+ * nxhip_light_tree_leaves_for(N) is the power of two >= N (N above 2^23: the render refuses, NXHIP_ERR_INVALID).  The tree is implicit
+ * and complete, a 1-based heap: node 1 is the root, the children of node k are 2k and 2k + 1, the leaves are nodes G .. 2G - 1; no child
+ * pointers.  Leaf slot j < N holds entry order[j]; `order` lists the entries sorted by (m, entry index), m = the 30-bit Morton code
+ * (x the most significant of each bit triple, then y, then z) of the triangle's world-space centroid ((a + b) + c) * (1 / 3) in
+ * cells of extent / 1024 from the minimum of all centroids, `extent` the largest of the three extents of all centroids (ONE scale: a flat
+ * arrangement stays flat in the code), each cell index clamped to 0 .. 1023.  The sort key is m << 23 | entry — no two alike — sorted by
+ * rocPRIM's radix sort: two contexts with the same scene hold the same tree bit for bit.  Slots j >= N are empty: weight 0, box +inf / -inf.
+ * A node is 32 bytes, { float lo[3]; float w; float hi[3]; uint32_t entry; }, so the two children of a node are one aligned 64-byte load.
+ * A leaf's box is the min / max of its triangle's three corners transformed in binary64 (((m0 x + m1 y) + m2 z) + m3 per row), rounded to
+ * binary32 once — the mat_point values the light sample itself computes differ from them by binary32's rounding of that sum, which the
+ * importance, continuous in the box, does not tell apart —, an inner node's the min / max of its children's; the binary64 weight W of an inner node is left + right; the stored w is
+ * binary32(W_node / W_root).  `entry` is the table entry in a leaf (0xffffffff in an empty slot) and 0 in an inner node.  slotOf[entry] is
+ * the inverse of `order`.  A root weight that is 0 or not finite clears the table header's `valid` and sets every w to 0: no mesh-light
+ * samples, the table's rule.  Built on the device with no read-back — min / max and the fixed shape make every value independent of the
+ * order threads run in — by the event that rebuilds the table (above) and with its ordering against passes in flight; a change of this
+ * setting is such an event.
+ *
+ * The importance I of a node at p.  Every operation is one binary32 rounding, in this order; no fused multiply-add:
+ *   w == 0: I = 0, and the box is not looked at.  Otherwise
+ *   c = (lo + hi) * 0.5f;  h = (hi - lo) * 0.5f;  r2 = (h.x*h.x + h.y*h.y) + h.z*h.z;
+ *   d = p - c;  d2 = (d.x*d.x + d.y*d.y) + d.z*d.z;  I = w / max(max(d2, r2), FLT_MIN).
+ * I is continuous in p, and positive for every node of positive weight unless d2 overflows.
+ *
+ * The pick uses ONE random number u, the one that replaces the uniform triangle index, so a path draws as many numbers as in both other
+ * modes.  P = 1.0f, k = 1; while k < G:  a = I(2k), b = I(2k + 1); both 0: no light sample, and no further number is drawn;
+ * s = a + b, qa = a / s, qb = b / s;  if b == 0 or (a != 0 and u < qa):  P *= qa, u = min(u / qa, 1 - 2^-24), k = 2k;  otherwise
+ * P *= qb, u = max(min((u - qa) / qb, 1 - 2^-24), 0), k = 2k + 1.  The entry is leaf k's.  N = 1: G = 1, the root is the leaf, P = 1.
+ * The probability of a given entry at p — the MIS weight of an emissive hit — walks the ancestors of slotOf[entry] root to leaf with the
+ * same a, b, s and the same factor: the pick's P bit for bit.  P = 0: the sampler cannot reach the entry from p and the MIS weight is 1,
+ * POWER mode's rule, which also covers an instance that is no light.
+ * The density is POWER mode's with this P in place of the table's: (P * (lightCount / nLights)) / area * dSquared / cosThetaO.
+ *
+ * Where p comes from: the light sample passes the hit point (the medium: the scatter point); the emissive hit passes the previous
+ * ray's origin, which the ray offset has moved off the surface by a few ulp of the position.  The two points differ by that offset, so the
+ * two MIS weights of one light path sum to one only up to (offset / distance to the nearest box) — I is continuous.  The path state
+ * carries no field to remove this.
+ *
+ * First-version restrictions: while the setting is in effect nxhip_set_tail_bounce is ignored (the tail kernel has no such instance);
+ * under the classic pipeline (NX_COMPACT_ORDERED) the setting is ignored and frames are POWER mode's bit for bit; there is no map-free
+ * instance.  Another value: NXHIP_ERR_INVALID. */
+enum { NXHIP_LIGHT_IMPORTANCE_POWER = 0, NXHIP_LIGHT_IMPORTANCE_POSITION = 1 };
+int nxhip_set_light_importance(nxhip_ctx *ctx, int importance);
+/* G of a light tree over `entries` entries: the power of two >= entries; 0 for 0 entries or for more than 2^23.  Pure host code. */
+uint32_t nxhip_light_tree_leaves_for(uint32_t entries);
 /* Extension: transparent shadows.  A material's `opacity` and the alpha of its diffuse map let a PATH pass a surface with probability
  * 1 - opacity x alpha(uv) (the material kernels, the reference's rule); the reference's shadow rays end at the first triangle whatever its
  * material, so a delta light behind a see-through surface contributes 0 and, with useMIS, the light-sample share of every emitter
@@ -940,6 +1000,17 @@ int nxhip_material_inputs_batch(nxhip_ctx *ctx, uint32_t instanceIdx, const uint
  * nothing (`valid` = 0: the renderer never samples it; the hook reads the flag back). */
 int nxhip_read_light_table(nxhip_ctx *ctx, float *cdf, uint32_t *entryLight, uint32_t capacity, uint32_t *lightBase, uint32_t *entries);
 int nxhip_light_pick_batch(nxhip_ctx *ctx, const float *u, uint32_t count, uint32_t *entry, float *prob);
+/* Test hooks of the light tree (a `make release` library refuses them; NXHIP_LIGHTS_POWER with NXHIP_LIGHT_IMPORTANCE_POSITION only, else
+ * NXHIP_ERR_INVALID; all three bring the tree up to date first).
+ * read: nodes8 (may be NULL) receives 2G nodes of eight words each — lo xyz, w, hi xyz, entry; node 0 is unused — and holds
+ *       `capacityNodes` nodes; order (may be NULL) receives N words; *leaves = G, *entries = N (either may be NULL).
+ * pick: entry[k], prob[k] = the device's descent from points3[3k..] with u[k]; entry 0xffffffff and prob 0: no light sample.
+ * prob: prob[k] = the probability the descent from points3[3k..] has of entry[k].
+ * Refused on the host before anything is launched: a point that is not finite, a u outside [0, 1), an entry >= N, an empty tree, a tree
+ * whose weights sum to nothing. */
+int nxhip_read_light_tree(nxhip_ctx *ctx, float *nodes8, uint32_t *order, uint32_t capacityNodes, uint32_t *leaves, uint32_t *entries);
+int nxhip_light_tree_pick_batch(nxhip_ctx *ctx, const float *points3, const float *u, uint32_t count, uint32_t *entry, float *prob);
+int nxhip_light_tree_prob_batch(nxhip_ctx *ctx, const float *points3, const uint32_t *entry, uint32_t count, float *prob);
 
 /* Test hooks of the environment lookup and of its importance sampler (nxhip_set_env_sampling).  All three refuse with
  * NXHIP_ERR_INVALID while no environment map is uploaded; read and sample — and eval when it is asked for a pdf or a texel —

@@ -216,6 +216,8 @@ int nxs_pathtracer_set_pixel_order(nxs_pathtracer *p, int order);
 int nxs_pathtracer_set_entry_points(nxs_pathtracer *p, int on);
 /* PathTracer::SetLightSampling (extension): NXHIP_LIGHTS_* — how the light sample chooses among the mesh lights' triangles */
 int nxs_pathtracer_set_light_sampling(nxs_pathtracer *p, int mode);
+/* PathTracer::SetLightImportance (extension): NXHIP_LIGHT_IMPORTANCE_* — in NXHIP_LIGHTS_POWER, whether the pick depends on the shading point */
+int nxs_pathtracer_set_light_importance(nxs_pathtracer *p, int importance);
 /* PathTracer::SetShadowTransmittance (extension): NXHIP_SHADOWS_* — whether opacity and texture alpha attenuate shadow rays */
 int nxs_pathtracer_set_shadow_transmittance(nxs_pathtracer *p, int mode);
 /* PathTracer::SetFeatureBuffers (extension): albedo / normal / depth of the camera ray's hit, accumulated like the colour (nxhip_set_aov) */

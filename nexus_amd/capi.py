@@ -455,6 +455,7 @@ FLAVOR_MEDIUM_GRID = 16384  # ... and their GRID instances: a medium with sigmaT
 FLAVOR_METAL = 32768  # ... and the METAL instances of the material launch and the tail kernel: some material is a MAT_METALROUGH (set_materials)
 FLAVOR_ALPHA_TEST = 65536  # ... and the ALPHA_TEST instances of the trace kernels: some material of the alpha table is pod.ALPHA_MASK (set_material_alpha)
 FLAVOR_SOLID = 131072  # ... and the SOLID instances of the material launches: some material is pod.ALPHA_MASK or pod.ALPHA_OPAQUE (set_material_alpha)
+FLAVOR_LIGHT_TREE = 262144  # ... and the TREE instances of the material launch and the medium's scatter kernel: LIGHTS_POWER with LIGHT_IMPORTANCE_POSITION under the SCAN pipeline
 FLAVOR_TRANSMIT = 2048  # ... and the any-hit TRANSMIT instance: SHADOWS_TRANSMIT over a table with a see-through material (set_shadow_transmittance)
 
 
@@ -886,6 +887,12 @@ class Context:
         proportion to area x emitted luminance, from a table built on the device (include/nexus_hip.h)"""
         check(self.L.nxhip_set_light_sampling(self.h, int(mode)), "nxhip_set_light_sampling")
 
+    def set_light_importance(self, importance):
+        """LIGHT_IMPORTANCE_POWER (0, the default) or LIGHT_IMPORTANCE_POSITION (1): in LIGHTS_POWER mode the light sample descends a
+        bounding hierarchy over the table's entries with probabilities that depend on the shading point (nxhip_set_light_importance);
+        remembered, and without effect, in LIGHTS_UNIFORM"""
+        check(self.L.nxhip_set_light_importance(self.h, int(importance)), "nxhip_set_light_importance")
+
     def set_shadow_transmittance(self, mode):
         """SHADOWS_OPAQUE (0, the reference's rule: a shadow ray ends at the first triangle) or SHADOWS_TRANSMIT (1): every crossing
         multiplies the ray's transmittance by 1 - opacity x alpha(uv) (nxhip_set_shadow_transmittance; deterministic, same expectation as
@@ -909,6 +916,30 @@ class Context:
         entry, prob = _outs(len(u), (_U32, 1), (_F32, 1))
         self._hook("nxhip_light_pick_batch", u, len(u), entry, prob)
         return entry, prob
+
+    def read_light_tree(self):
+        """the light tree of LIGHTS_POWER with LIGHT_IMPORTANCE_POSITION (brought up to date first): (nodes float32[2G, 8] — lo xyz, w,
+        hi xyz, entry bits; node 0 unused —, order uint32[N]); G = len(nodes) // 2"""
+        g, n = C.c_uint32(0), C.c_uint32(0)
+        check(self.L.nxhip_read_light_tree(self.h, None, None, 0, C.byref(g), C.byref(n)), "nxhip_read_light_tree")
+        nodes = np.zeros((2 * g.value, 8), dtype=np.float32)
+        order = np.zeros(n.value, dtype=np.uint32)
+        check(self.L.nxhip_read_light_tree(self.h, _ptr(nodes), _ptr(order), 2 * g.value, C.byref(g), C.byref(n)), "nxhip_read_light_tree")
+        return nodes, order
+
+    def light_tree_pick_batch(self, points, u):
+        """the device's descent from every point with its u in [0, 1): (entry uint32[] — 0xffffffff: no sample —, prob float32[])"""
+        p, u = _cols((points, _F32, 3), (u, _F32, 1))
+        entry, prob = _outs(len(u), (_U32, 1), (_F32, 1))
+        self._hook("nxhip_light_tree_pick_batch", p, u, len(u), entry, prob)
+        return entry, prob
+
+    def light_tree_prob_batch(self, points, entry):
+        """the probability the descent from every point has of its entry: float32[]"""
+        p, e = _cols((points, _F32, 3), (entry, _U32, 1))
+        prob, = _outs(len(e), (_F32, 1))
+        self._hook("nxhip_light_tree_prob_batch", p, e, len(e), prob)
+        return prob
 
     def set_entry_points(self, on=True):
         """primary rays start from the state their run's first node steps provably share (include/nexus_hip.h)"""
@@ -1695,6 +1726,10 @@ class PathTracer:
     def set_light_sampling(self, mode):
         """PathTracer::SetLightSampling: pod.LIGHTS_UNIFORM (the reference's rule) or pod.LIGHTS_POWER (area x emitted luminance)"""
         _scheck(self.L.nxs_pathtracer_set_light_sampling(self.h, int(mode)), "nxs_pathtracer_set_light_sampling")
+
+    def set_light_importance(self, importance):
+        """PathTracer::SetLightImportance: pod.LIGHT_IMPORTANCE_POWER (the default) or pod.LIGHT_IMPORTANCE_POSITION (the light tree)"""
+        _scheck(self.L.nxs_pathtracer_set_light_importance(self.h, int(importance)), "nxs_pathtracer_set_light_importance")
 
     def read_accumulation(self):
         """the running mean over the frames rendered so far, (pixels, 3) float32, from this path tracer's device context"""

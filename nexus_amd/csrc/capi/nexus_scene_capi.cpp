@@ -521,6 +521,7 @@ int nxs_pathtracer_set_passes_in_flight(nxs_pathtracer* p, uint32_t passes) { re
 int nxs_pathtracer_set_pixel_order(nxs_pathtracer* p, int order) { return guarded([&] { p->pt.SetPixelOrder(order); }); }
 int nxs_pathtracer_set_entry_points(nxs_pathtracer* p, int on) { return guarded([&] { p->pt.SetEntryPoints(on != 0); }); }
 int nxs_pathtracer_set_light_sampling(nxs_pathtracer* p, int mode) { return guarded([&] { p->pt.SetLightSampling(mode); }); }
+int nxs_pathtracer_set_light_importance(nxs_pathtracer* p, int importance) { return guarded([&] { p->pt.SetLightImportance(importance); }); }
 int nxs_pathtracer_set_shadow_transmittance(nxs_pathtracer* p, int mode) { return guarded([&] { p->pt.SetShadowTransmittance(mode); }); }
 int nxs_pathtracer_set_feature_buffers(nxs_pathtracer* p, int on) { return guarded([&] { p->pt.SetFeatureBuffers(on != 0); }); }
 int nxs_pathtracer_set_device_blas_build(nxs_pathtracer* p, nxs_scene* s, int enable)

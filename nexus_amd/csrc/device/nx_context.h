@@ -249,7 +249,7 @@ struct nxhip_ctx : nxd::PassSlot {
     int traceBlocks = 0, shadowBlocks = 0, wideBlocks = 0;  // full-chip persistent grids (see trace_blocks)
     // grids of the tail kernel's instances, each from its OWN occupancy (the default mode's grid does not depend on another instance's),
     // indexed by the instance's feature set (nx_variants.h kMf*; 0: no tail instance of that set — nxhip_create fills it)
-    int tailBlocks[64] = {};
+    int tailBlocks[128] = {};
     int tailBounce = -1;  // first bounce of the tail kernel, 0 = off, -1 = automatic (see tail_bounce in nxhip_render.hip)
     bool traceGridForced = false;                            // NX_TRACE_BLOCKS_*: use them as they are
     int shadeBlocksPerCU = 10, logicBlocksPerCU = 2;  // grid-stride kernels: workgroups per CU
@@ -313,5 +313,13 @@ struct nxhip_ctx : nxd::PassSlot {
     size_t lightScanBytes = 0;
     uint32_t lightEntries = 0, lightGuideSize = 0;
     nxd::DevBuf lightMapMean;       // [capacity] x 4 floats: mean sRGB-decoded texel of the emissive maps, computed once per uploaded map
+    nxd::DevBuf lightMapMean64;     // [capacity] x 4 doubles: the same means before their rounding (the light tree's weights)
     size_t lightMapMeanCapacity = 0, lightMapMeans = 0;  // maps the buffer holds / maps whose mean is in it
+    // ... and by position (nxhip_set_light_importance): the light tree over the table's entries.  Empty unless the mode is POWER and the
+    // importance POSITION; built by refresh_light_table behind the table, over the table's entries.
+    int lightImportance = 0;        // NXHIP_LIGHT_IMPORTANCE_*: remembered in every mode
+    uint32_t lightTreeLeaves = 0;   // G of the tree the buffers hold (0: none)
+    nxd::DevBuf lightTreeNodes, lightTreeWeight, lightTreeSlotOf, lightTreeBounds;  // [2G] nodes, [2G] binary64 weights, [N], the centroids' bounds
+    nxd::DevBuf lightTreeKeys, lightTreeSorted, lightTreeOrder, lightTreeSortTemp;  // [N] each: the Morton sort
+    size_t lightTreeSortBytes = 0;
 };

@@ -381,6 +381,36 @@ struct LightBuild {
     uint32_t lightCount, entries, guideSize, pad_;
 };
 
+// One node of the light tree (nxhip_set_light_importance; the rule is stated in include/nexus_hip.h): an implicit complete binary tree as a
+// 1-based heap over `leaves` slots — the children of node k are 2k and 2k + 1, ONE aligned 64-byte load.  w = binary32(W_node / W_root);
+// an empty slot has w = 0 and the box +inf / -inf.  `entry`: a leaf's table entry (kNotALight in an empty slot), 0 in an inner node.
+struct alignas(32) LightNode {
+    float lo[3];
+    float w;
+    float hi[3];
+    uint32_t entry;
+};
+static_assert(sizeof(LightNode) == 32, "two children are one 64-byte load");
+constexpr uint32_t kLightTreeLeavesMax = 1u << 23;
+
+// Argument block of the light tree's build kernels (nx_lights.hip; filled by refresh_light_table)
+struct LightTreeBuild {
+    const ShadeInst* shadeInst;
+    const nx_light* lights;
+    const uint32_t* lightBase;   // [lightCount + 1]
+    const LightEntry* table;     // the entries' lights (light_weight_kernel)
+    const double* mapMean64;     // [emissive maps] x 4: the maps' means in binary64 (light_map_mean_kernel)
+    uint32_t* bounds;            // [6] min xyz, max xyz of the centroids, as ordered integers
+    uint64_t* keys;              // [entries] Morton code << 23 | entry: no two alike, so ties go by entry whatever the sort does with equal keys
+    const uint64_t* sorted;      // [entries] the keys in ascending order
+    uint32_t* order;             // [entries] the entry of slot j
+    uint32_t* slotOf;            // [entries] the slot of entry e
+    LightNode* nodes;            // [2 x leaves]
+    double* nodeWeight;          // [2 x leaves]
+    LightHeader* header;
+    uint32_t entries, leaves;
+};
+
 // One analytic light as the kernels read it (nxhip_set_analytic_lights; sampled by nx_alights.h alight_sample): four 16-byte loads.
 // Derived on the host in binary64 from the caller's nx_analytic_light and rounded once (nxhip_scene.hip):
 //   v0  centre xyz, radius                            (DIRECTIONAL: 0)
@@ -521,6 +551,13 @@ struct DeviceState {
     // compaction: filled by logic_metal_kernel, read by shade_kernel<NX_MAT_METALROUGH> (nx_wavefront_metal.hip).  material[4] above keeps
     // the reference's four.  Last in the block: nothing in front moves.
     MaterialQueue materialMetal;
+    // The light tree (nxhip_set_light_importance; nx_lights.h), nullptr / 0 unless the mode is POWER and the importance POSITION.  Read only
+    // by the TREE instances of the material launch and of the medium's scatter kernel (kFlavorLightTree), and by its hooks.  Last in the
+    // block: nothing in front moves.
+    const NX_G LightNode* lightTree;     // [2 x lightTreeLeaves], node 0 unused
+    const NX_G uint32_t* lightSlotOf;    // [lightEntries]: the leaf slot of an entry
+    uint32_t lightTreeLeaves;            // G: a power of two >= lightEntries
+    uint32_t padLightTree_;
 };
 
 // Argument block of the adaptive update's kernels (nx_adaptive.hip; filled by nxhip_adaptive_update)
@@ -574,6 +611,8 @@ constexpr uint64_t layout_stamp()
         (uint64_t)kEnvGuide, (uint64_t)kHitCodeShift, sizeof(TraceRays), offsetof(TraceQueue, hit), (uint64_t)kMaterialTypeOffset, sizeof(nx_material), sizeof(nx_bvh_instance), sizeof(nx_triangle), sizeof(nx_light), sizeof(nx_camera),
         offsetof(RegionCounters, materialSizeMetal), offsetof(RegionCounters, scanTileMetal), offsetof(RegionCounters, scanTicketMetal), offsetof(DeviceState, materialMetal), (uint64_t)kHitCodeMetalRough, (uint64_t)kScanMetalBit,
         sizeof(SkinTri), offsetof(SkinTri, joint), (uint64_t)kSkinLdsJoints,
+        offsetof(DeviceState, lightTree), offsetof(DeviceState, lightSlotOf), offsetof(DeviceState, lightTreeLeaves), sizeof(LightNode), offsetof(LightNode, hi), sizeof(LightTreeBuild),
+        offsetof(LightTreeBuild, entries),
     };
     for (uint64_t v : w) h = layout_mix(h, v);
     return h;

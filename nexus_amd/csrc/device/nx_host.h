@@ -59,6 +59,8 @@ const void* adaptive_decide_kernel_ptr();
 const void* adaptive_scan_kernel_ptr();
 const void* adaptive_fill_kernel_ptr();
 const void* light_pick_kernel_ptr();  // nx_lights.hip
+const void* light_tree_pick_kernel_ptr();
+const void* light_tree_prob_kernel_ptr();
 const void* inst_code_kernel_ptr();  // nx_refit.hip
 const void* inst_code_metal_kernel_ptr();  // (... of a material table with an NX_MAT_METALROUGH)
 const void* instance_transform_kernel_ptr();
@@ -85,8 +87,10 @@ uint64_t layout_stamp_render();
 uint64_t layout_stamp_features();
 uint64_t layout_stamp_hooks();
 int light_scan_bytes(size_t entries, size_t* bytes);
-int light_map_mean(hipStream_t st, const TextureDev& t, const float* srgbLut, float* mean4);
+int light_map_mean(hipStream_t st, const TextureDev& t, const float* srgbLut, float* mean4, double* mean64);
 int light_table_build(hipStream_t st, const LightBuild& b, void* scanTemp, size_t scanBytes);
+int light_tree_sort_bytes(size_t entries, size_t* bytes);
+int light_tree_build(hipStream_t st, const LightTreeBuild& b, void* sortTemp, size_t sortBytes);
 // nx_envmap.hip: the float environment map's sampler tables, built on the device in stream order (temp: 2 x height doubles)
 int env_float_tables_build(hipStream_t st, const float4* texels, uint32_t width, uint32_t height, double* temp, float* marginalCdf, float* rowCdf, float* density,
                            uint32_t* marginalGuide, uint32_t* rowGuide);
@@ -191,6 +195,10 @@ inline Kernel<AdaptiveLaunch> adaptive_scan() { return {adaptive_scan_kernel_ptr
 inline Kernel<AdaptiveLaunch> adaptive_fill() { return {adaptive_fill_kernel_ptr()}; }
 // (table, guide, guideSize, entries, u, count, entry, prob)
 inline Kernel<const LightEntry*, const U32*, U32, U32, const float*, U32, U32*, float*> light_pick() { return {light_pick_kernel_ptr()}; }
+// (nodes, leaves, points, u, count, entry, prob)
+inline Kernel<const LightNode*, U32, const float*, const float*, U32, U32*, float*> light_tree_pick() { return {light_tree_pick_kernel_ptr()}; }
+// (nodes, leaves, slotOf, points, entry, count, prob)
+inline Kernel<const LightNode*, U32, const U32*, const float*, const U32*, U32, float*> light_tree_prob() { return {light_tree_prob_kernel_ptr()}; }
 inline Kernel<State, InstTrav*, const ShadeInst*, U32> inst_code(bool metal = false) { return {metal ? inst_code_metal_kernel_ptr() : inst_code_kernel_ptr()}; }  // (S, trav, shadeInst, count)
 // (S, instances, trav, leafOfInstance, ids, transforms, count, tightBoxes, shadeInst, blasRefresh)
 inline Kernel<State, nx_bvh_instance*, InstTrav*, const U32*, const U32*, const float*, U32, void*, ShadeInst*, U32> instance_transform() { return {instance_transform_kernel_ptr()}; }

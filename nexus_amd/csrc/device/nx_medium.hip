@@ -255,7 +255,7 @@ template <bool GRID, unsigned F>  // (F: POWER, ANALYTIC — next_event_estimati
 __global__ void __launch_bounds__(kShadeBlock) medium_scatter_kernel(const DeviceState* __restrict__ S, const int bounceArg)
 {
     constexpr bool ANALYTIC = (F & kMfAnalytic) != 0u, METAL = (F & kMfMetal) != 0u;
-    static_assert(medium_set_ok(F), "medium_scatter_kernel reads POWER, ANALYTIC and METAL alone (nx_variants.h)");
+    static_assert(medium_set_ok(F), "medium_scatter_kernel reads POWER, TREE, ANALYTIC and METAL alone (nx_variants.h)");
     const int bounce = bounceArg & 0xff;
     const bool dropEnded = (bounceArg & kShadeDropEnded) != 0;
     const int region = (int)(blockIdx.x & (kQueueShards - 1));
@@ -483,7 +483,8 @@ __global__ void __launch_bounds__(kWideBlock) medium_track_hook_kernel(const Dev
 }
 
 // (POWER and ANALYTIC: next_event_estimation's instances, chosen as the material launch's are — nxhip_render.hip; METAL: the fifth type's hit code)
-using MediumSets = Instances<kMfPower | kMfAnalytic | kMfMetal, kMfAnalytic | kMfMetal, kMfPower | kMfMetal, kMfMetal, kMfPower | kMfAnalytic, kMfAnalytic, kMfPower, 0u>;
+using MediumSets = Instances<kMfTree | kMfPower | kMfAnalytic | kMfMetal, kMfPower | kMfAnalytic | kMfMetal, kMfAnalytic | kMfMetal, kMfTree | kMfPower | kMfMetal, kMfPower | kMfMetal, kMfMetal,
+                             kMfTree | kMfPower | kMfAnalytic, kMfPower | kMfAnalytic, kMfAnalytic, kMfTree | kMfPower, kMfPower, 0u>;
 template <bool GRID> const void* medium_scatter_instance(unsigned set)
 {
     return MediumSets::find(set, [](auto f) { return (const void*)medium_scatter_kernel<GRID, decltype(f)::value>; });

@@ -18,13 +18,16 @@ constexpr unsigned kMfAnalytic = 4u;   // ANALYTIC: the context has analytic lig
 constexpr unsigned kMfDetail = 8u;     // DETAIL: some material names a normal or a roughness map
 constexpr unsigned kMfMetal = 16u;     // METAL: some material is an NX_MAT_METALROUGH
 constexpr unsigned kMfSolid = 32u;     // SOLID: some material is NX_ALPHA_MASK or NX_ALPHA_OPAQUE
-constexpr unsigned kMfAll = 63u;
+constexpr unsigned kMfTree = 64u;      // TREE: ... and by the shading point's position, from the light tree (NXHIP_LIGHT_IMPORTANCE_POSITION)
+constexpr unsigned kMfAll = 127u;
 
 // SOLID => METAL => DETAIL => not NO_MAPS: the later families were built on the earlier ones' records (a SOLID instance knows all five
 // material types and reads a detail record; METAL's metalness comes with the roughness map's lookup; DETAIL has no map-free form).
+// TREE => POWER and not NO_MAPS: the tree refines the table's mode (its leaves are the table's entries), and it has no map-free form.
 constexpr bool material_set_ok(unsigned f)
 {
-    return (f & ~kMfAll) == 0u && (!(f & kMfSolid) || (f & kMfMetal)) && (!(f & kMfMetal) || (f & kMfDetail)) && (!(f & kMfDetail) || !(f & kMfNoMaps));
+    return (f & ~kMfAll) == 0u && (!(f & kMfSolid) || (f & kMfMetal)) && (!(f & kMfMetal) || (f & kMfDetail)) && (!(f & kMfDetail) || !(f & kMfNoMaps)) &&
+           (!(f & kMfTree) || ((f & kMfPower) && !(f & kMfNoMaps)));
 }
 // ... and the smallest such set over `f`: what a scene with the features `f` launches
 constexpr unsigned material_closure(unsigned f)
@@ -32,22 +35,23 @@ constexpr unsigned material_closure(unsigned f)
     if (f & kMfSolid) f |= kMfMetal;
     if (f & kMfMetal) f |= kMfDetail;
     if (f & kMfDetail) f &= ~kMfNoMaps;
+    if (f & kMfTree) f = (f | kMfPower) & ~kMfNoMaps;
     return f;
 }
 
 // What a kernel family leaves out of the rule, because something else says it or because it never gets there:
 //   shade_kernel (classic pipeline): its TYPE says what METAL would — an instance of NX_MAT_METALROUGH is a DETAIL instance, the four
-//     reference types know nothing of the fifth — and the pipeline has no map-free form;
-//   tail_kernel: no map-free form and no SOLID one (no tail kernel under alpha modes: nxhip_render.hip tail_bounce);
-//   medium_scatter_kernel: shades no surface — it knows the light sample's two features and the fifth type's hit code;
+//     reference types know nothing of the fifth — and the pipeline has no map-free form and no TREE one (the setting is ignored there);
+//   tail_kernel: no map-free form, no SOLID one and no TREE one (no tail kernel under alpha modes or the light tree: nxhip_render.hip tail_bounce);
+//   medium_scatter_kernel: shades no surface — it knows the light sample's three features and the fifth type's hit code;
 //   logic_kernel: the analytic lights' count in the weighted miss, nothing else.
 constexpr unsigned kMfShadeReads = kMfPower | kMfAnalytic | kMfDetail | kMfSolid;
 constexpr unsigned kMfTailReads = kMfPower | kMfAnalytic | kMfDetail | kMfMetal;
-constexpr unsigned kMfMediumReads = kMfPower | kMfAnalytic | kMfMetal;
+constexpr unsigned kMfMediumReads = kMfPower | kMfAnalytic | kMfMetal | kMfTree;
 constexpr unsigned kMfLogicReads = kMfAnalytic;
 constexpr bool shade_set_ok(unsigned f, bool metalType) { return (f & ~kMfShadeReads) == 0u && material_set_ok(f | ((metalType || (f & kMfSolid)) ? kMfMetal : 0u)); }
 constexpr bool tail_set_ok(unsigned f) { return (f & ~kMfTailReads) == 0u && material_set_ok(f); }
-constexpr bool medium_set_ok(unsigned f) { return (f & ~kMfMediumReads) == 0u; }
+constexpr bool medium_set_ok(unsigned f) { return (f & ~kMfMediumReads) == 0u && (!(f & kMfTree) || (f & kMfPower)); }
 
 // ---- trace features: trace_kernel ------------------------------------------------------------------------------------------------
 constexpr unsigned kTfAnyHit = 1u;     // ANY_HIT: shadow rays (else closest hit)

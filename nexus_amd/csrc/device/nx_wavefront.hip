@@ -729,11 +729,14 @@ struct ShadowPayload {
 // environment; an analytic pick draws its direction from the cone the light subtends (nx_alights.h alight_sample) and carries no MIS
 // weight — no other ray can find such a light.  With useMIS off the sample is taken among the analytic lights alone.  The instances
 // with ANALYTIC = false are the code of a context without such lights.
+// TREE (nxhip_set_light_importance, NXHIP_LIGHT_IMPORTANCE_POSITION, in POWER mode: kFlavorLightTree): the entry comes from the light tree's
+// descent at hitPoint (nx_lights.h light_tree_pick) with the same ONE random number, and its probability stands where the table's
+// did.  The POWER instances without it keep their text.
 template <int TYPE, unsigned F>
 NXD bool next_event_estimation(const DeviceState* S, f3 wi, const MatParams& mp, f3 hitPoint, f3 normal, f3 hitGNormal, f3 throughput,
                                uint32_t& rng, ShadowPayload& out)
 {
-    constexpr bool POWER = (F & kMfPower) != 0u, NO_MAPS = (F & kMfNoMaps) != 0u, ANALYTIC = (F & kMfAnalytic) != 0u;
+    constexpr bool POWER = (F & kMfPower) != 0u, NO_MAPS = (F & kMfNoMaps) != 0u, ANALYTIC = (F & kMfAnalytic) != 0u, TREE = (F & kMfTree) != 0u;
     // no lights: the reference indexes an empty array here (undefined); defined as "no light sample, no random numbers
     // drawn", identically in the CPU restatement used by the tests
     uint32_t nLights = nee_light_count<F>(S);
@@ -787,10 +790,18 @@ NXD bool next_event_estimation(const DeviceState* S, f3 wi, const MatParams& mp,
     if constexpr (POWER) {
         // (the uniform pick above only decided "a mesh light": which one, and which triangle, is the table's choice)
         if (S->lightHeader->valid == 0u) return false;  // nothing emits: no light sample, no number drawn
-        const LightPick lp = light_pick(S->lightTable, S->lightGuide, S->lightGuideSize, S->lightEntries, rng_next(rng));
-        meshId = S->lights[lp.light].mesh.meshId;
-        triangleIdx = lp.entry - S->lightBase[lp.light];
-        pickProb = lp.prob;
+        if constexpr (TREE) {
+            uint32_t entry;
+            if (!light_tree_pick(S->lightTree, S->lightTreeLeaves, hitPoint, rng_next(rng), entry, pickProb)) return false;  // (no further number is drawn)
+            const uint32_t light = light_entry(S->lightTable, entry).light;
+            meshId = S->lights[light].mesh.meshId;
+            triangleIdx = entry - S->lightBase[light];
+        } else {
+            const LightPick lp = light_pick(S->lightTable, S->lightGuide, S->lightGuideSize, S->lightEntries, rng_next(rng));
+            meshId = S->lights[lp.light].mesh.meshId;
+            triangleIdx = lp.entry - S->lightBase[lp.light];
+            pickProb = lp.prob;
+        }
     } else {
         const nx_light light = S->lights[pick];
         if (light.type != NX_LIGHT_MESH) return false;
@@ -869,6 +880,7 @@ NXD void shade_path(const DeviceState* S, const int bounce, const uint32_t frame
                     bool& wantShadow, ShadowPayload& sh, bool& wantTrace, bool& updatePath, f3& nextOrigin, f3& nextDir, f3& nextThroughput, float& nextPdf)
 {
     constexpr bool POWER = (F & kMfPower) != 0u, NO_MAPS = (F & kMfNoMaps) != 0u, ANALYTIC = (F & kMfAnalytic) != 0u, DETAIL = (F & kMfDetail) != 0u, SOLID = (F & kMfSolid) != 0u;
+    constexpr bool TREE = (F & kMfTree) != 0u;
     wantShadow = false; wantTrace = false; updatePath = false;
     nextOrigin = mk3(0.0f); nextDir = mk3(0.0f); nextThroughput = mk3(0.0f);
     nextPdf = 0.0f;
@@ -910,7 +922,14 @@ NXD void shade_path(const DeviceState* S, const int bounce, const uint32_t frame
                 // is no light, or an entry of probability 0: the sampler cannot reach it, BSDF sampling carries all of it (weight 1)
                 float P = 0.0f;
                 const uint32_t l = S->instLight[instanceIdx];
-                if (l != kNotALight && S->lightHeader->valid != 0u) P = light_entry_prob(S->lightTable, S->lightBase[l] + triIdx);
+                if constexpr (TREE) {
+                    // (... the tree's probability of this triangle as seen from the previous vertex — the ray's origin, which offset_ray has
+                    //  moved off the surface the light sample stood on: include/nexus_hip.h states what that costs)
+                    if (l != kNotALight && S->lightHeader->valid != 0u)
+                        P = light_tree_prob(S->lightTree, S->lightTreeLeaves, mk3(ro.x, ro.y, ro.z), S->lightSlotOf[S->lightBase[l] + triIdx]);
+                } else {
+                    if (l != kNotALight && S->lightHeader->valid != 0u) P = light_entry_prob(S->lightTable, S->lightBase[l] + triIdx);
+                }
                 if (P > 0.0f) {
                     float lightPdf = (P * ((float)S->lightCount / (float)nee_light_count<F>(S))) / area;
                     lightPdf *= dSquared / cosThetaO;
@@ -1676,8 +1695,8 @@ __global__ void __launch_bounds__(kWideBlock) alight_hook_kernel(const DeviceSta
 // This unit's instances: the contexts without detail maps, a fifth material type or alpha modes.
 // (the classic pipeline — logic kernel and per-type material kernels — runs under the ordered compaction only: see frame_levels)
 using ShadeSets = Instances<kMfPower | kMfAnalytic, kMfAnalytic, kMfPower, 0u>;
-using ShadeScanSets = Instances<kMfPower | kMfNoMaps | kMfAnalytic, kMfNoMaps | kMfAnalytic, kMfPower | kMfAnalytic, kMfAnalytic,
-                                kMfPower | kMfNoMaps, kMfNoMaps, kMfPower, 0u>;
+using ShadeScanSets = Instances<kMfPower | kMfNoMaps | kMfAnalytic, kMfNoMaps | kMfAnalytic, kMfTree | kMfPower | kMfAnalytic, kMfPower | kMfAnalytic, kMfAnalytic,
+                                kMfPower | kMfNoMaps, kMfNoMaps, kMfTree | kMfPower, kMfPower, 0u>;
 using TailSets = Instances<kMfPower | kMfAnalytic, kMfAnalytic, kMfPower, 0u>;
 namespace wavefront {
 // `items` per thread: kLogicItems (2) unless the caller asks for 1 — what a scene with an environment map gets, whose misses run the

@@ -67,7 +67,9 @@ __global__ void __launch_bounds__(kWideBlock) tex2d_linear_hook_kernel(const Tex
 using DetailSets = Instances<kMfPower | kMfAnalytic | kMfDetail, kMfAnalytic | kMfDetail, kMfPower | kMfDetail, kMfDetail>;
 namespace wavefront_detail {
 const void* shade(int type, unsigned set) { return shade_instance<DetailSets, NX_MAT_DIFFUSE, NX_MAT_DIELECTRIC, NX_MAT_PLASTIC, NX_MAT_CONDUCTOR>(type, set); }
-const void* shade_scan(unsigned set) { return shade_scan_instance<DetailSets>(set); }
+// (the SCAN material launch alone has TREE forms: nx_variants.h)
+using DetailScanSets = Instances<kMfTree | kMfPower | kMfAnalytic | kMfDetail, kMfPower | kMfAnalytic | kMfDetail, kMfAnalytic | kMfDetail, kMfTree | kMfPower | kMfDetail, kMfPower | kMfDetail, kMfDetail>;
+const void* shade_scan(unsigned set) { return shade_scan_instance<DetailScanSets>(set); }
 const void* tail(unsigned set) { return tail_instance<DetailSets>(set); }
 }  // namespace wavefront_detail
 const void* shading_frame_hook_kernel_ptr() { return (const void*)shading_frame_hook_kernel; }

@@ -119,7 +119,10 @@ using MetalSets = Instances<kMfPower | kMfAnalytic | kMfDetail | kMfMetal, kMfAn
 // (the classic pipeline's material kernel of the fifth type: TYPE says METAL, the set does not — shade_kernel, nx_variants.h)
 using MetalShadeSets = Instances<kMfPower | kMfAnalytic | kMfDetail, kMfAnalytic | kMfDetail, kMfPower | kMfDetail, kMfDetail>;
 namespace wavefront_metal {
-const void* shade_scan(unsigned set) { return shade_scan_instance<MetalSets>(set); }
+// (the SCAN material launch alone has TREE forms: nx_variants.h)
+using MetalScanSets = Instances<kMfTree | kMfPower | kMfAnalytic | kMfDetail | kMfMetal, kMfPower | kMfAnalytic | kMfDetail | kMfMetal, kMfAnalytic | kMfDetail | kMfMetal,
+                                kMfTree | kMfPower | kMfDetail | kMfMetal, kMfPower | kMfDetail | kMfMetal, kMfDetail | kMfMetal>;
+const void* shade_scan(unsigned set) { return shade_scan_instance<MetalScanSets>(set); }
 const void* tail(unsigned set) { return tail_instance<MetalSets>(set); }
 const void* shade(int type, unsigned set) { return shade_instance<MetalShadeSets, NX_MAT_METALROUGH>(type, set); }
 }  // namespace wavefront_metal

@@ -12,7 +12,8 @@
 namespace nxd {
 
 // (the instances only the pass graphs of a context with a MASK or an OPAQUE material launch — nxhip_render.hip pass_flavor, kFlavorSolid)
-using SolidSets = Instances<kMfPower | kMfAnalytic | kMfDetail | kMfMetal | kMfSolid, kMfAnalytic | kMfDetail | kMfMetal | kMfSolid, kMfPower | kMfDetail | kMfMetal | kMfSolid,
+using SolidSets = Instances<kMfTree | kMfPower | kMfAnalytic | kMfDetail | kMfMetal | kMfSolid, kMfPower | kMfAnalytic | kMfDetail | kMfMetal | kMfSolid,
+                            kMfAnalytic | kMfDetail | kMfMetal | kMfSolid, kMfTree | kMfPower | kMfDetail | kMfMetal | kMfSolid, kMfPower | kMfDetail | kMfMetal | kMfSolid,
                             kMfDetail | kMfMetal | kMfSolid>;
 // (the classic pipeline's material kernels, all five types: TYPE says METAL, the set does not — shade_kernel, nx_variants.h)
 using SolidShadeSets = Instances<kMfPower | kMfAnalytic | kMfDetail | kMfSolid, kMfAnalytic | kMfDetail | kMfSolid, kMfPower | kMfDetail | kMfSolid, kMfDetail | kMfSolid>;

@@ -88,6 +88,60 @@ int nxd::adaptive_restart(nxhip_ctx* c)
     return NXHIP_OK;
 }
 
+// NXHIP_LIGHT_IMPORTANCE_POSITION (in POWER mode): the light tree (nx_lights.hip) over the entries of the table that refresh_light_table has
+// just laid out and queued the build of.  The buffers follow G = nxhip_light_tree_leaves_for(entries); with another importance they are
+// dropped and the state block names no tree.  The caller has waited for the passes in flight where there is more than one slot.
+static int refresh_light_tree(nxhip_ctx* c)
+{
+    const bool wanted = c->lightImportance == NXHIP_LIGHT_IMPORTANCE_POSITION;
+    const uint32_t n = c->lightEntries, leaves = wanted ? nxhip_light_tree_leaves_for(n) : 0u;
+    if (wanted && n > kLightTreeLeavesMax) return fail_invalid("NXHIP_LIGHT_IMPORTANCE_POSITION: the mesh lights have more than 2^23 triangles");
+    if (leaves != c->lightTreeLeaves || (leaves != 0u && c->lightTreeOrder.bytes != std::max<size_t>((size_t)n * 4, 16))) {
+        NX_SYNC_ALL(c);
+        if (leaves == 0u) {
+            for (DevBuf* b : {&c->lightTreeNodes, &c->lightTreeWeight, &c->lightTreeSlotOf, &c->lightTreeBounds, &c->lightTreeKeys, &c->lightTreeSorted, &c->lightTreeOrder,
+                              &c->lightTreeSortTemp})
+                b->release();
+        } else {
+            size_t sortBytes = 0;
+            NX_TRY(light_tree_sort_bytes(n, &sortBytes));
+            NX_ALLOC(c->lightTreeNodes, 2 * (size_t)leaves * sizeof(LightNode));
+            NX_ALLOC(c->lightTreeWeight, 2 * (size_t)leaves * sizeof(double));
+            NX_ALLOC(c->lightTreeSlotOf, (size_t)n * 4);
+            NX_ALLOC(c->lightTreeOrder, (size_t)n * 4);
+            NX_ALLOC(c->lightTreeKeys, (size_t)n * 8);
+            NX_ALLOC(c->lightTreeSorted, (size_t)n * 8);
+            NX_ALLOC(c->lightTreeBounds, 6 * 4);
+            NX_ALLOC(c->lightTreeSortTemp, std::max<size_t>(sortBytes, 16));
+            c->lightTreeSortBytes = sortBytes;
+        }
+        c->lightTreeLeaves = leaves;
+        c->h.lightTree = leaves ? c->lightTreeNodes.as<LightNode>() : nullptr;
+        c->h.lightSlotOf = leaves ? c->lightTreeSlotOf.as<uint32_t>() : nullptr;
+        c->h.lightTreeLeaves = leaves;
+        c->stateDirty = true;
+        NX_TRY(upload_state(c));
+    }
+    if (leaves == 0u) return NXHIP_OK;
+    LightTreeBuild b{};
+    b.shadeInst = c->shadeInst.as<ShadeInst>();
+    b.lights = c->lights.as<nx_light>();
+    b.lightBase = c->lightBase.as<uint32_t>();
+    b.table = c->lightTable.as<LightEntry>();
+    b.mapMean64 = c->lightMapMean64.as<double>();
+    b.bounds = c->lightTreeBounds.as<uint32_t>();
+    b.keys = c->lightTreeKeys.as<uint64_t>();
+    b.sorted = c->lightTreeSorted.as<uint64_t>();
+    b.order = c->lightTreeOrder.as<uint32_t>();
+    b.slotOf = c->lightTreeSlotOf.as<uint32_t>();
+    b.nodes = c->lightTreeNodes.as<LightNode>();
+    b.nodeWeight = c->lightTreeWeight.as<double>();
+    b.header = c->lightHeader.as<LightHeader>();
+    b.entries = n;
+    b.leaves = leaves;
+    return light_tree_build(c->stream, b, c->lightTreeSortTemp.p, c->lightTreeSortBytes);
+}
+
 // The context's base pixel set (count or map) has just changed.
 // NXHIP_LIGHTS_POWER: the light table (nx_lights.hip) brought up to date, once, before the next pass or hook call that reads it —
 // in the manner of refresh_updated_blas.  The shading records and the triangles it reads are current by then (the caller has run
@@ -153,13 +207,14 @@ int nxd::refresh_light_table(nxhip_ctx* c)
             if (c->lightMapMeanCapacity < maps) {
                 NX_SYNC_ALL(c);
                 NX_ALLOC(c->lightMapMean, 2 * maps * 16);
+                NX_ALLOC(c->lightMapMean64, 2 * maps * 32);
                 c->lightMapMeanCapacity = 2 * maps;
                 c->lightMapMeans = 0;
             }
             for (size_t m = c->lightMapMeans; m < maps; m++) {
                 const TextureHost& th = c->emissiveMaps[m];
                 const TextureDev t{th.texels.as<uint32_t>(), th.width, th.height};
-                NX_TRY(light_map_mean(c->stream, t, c->srgbLut.as<float>(), c->lightMapMean.as<float>() + 4 * m));
+                NX_TRY(light_map_mean(c->stream, t, c->srgbLut.as<float>(), c->lightMapMean.as<float>() + 4 * m, c->lightMapMean64.as<double>() + 4 * m));
             }
             c->lightMapMeans = maps;
         }
@@ -178,6 +233,7 @@ int nxd::refresh_light_table(nxhip_ctx* c)
         b.guideSize = c->lightGuideSize;
         NX_TRY(light_table_build(c->stream, b, c->lightScanTemp.p, c->lightScanBytes));
     }
+    NX_TRY(refresh_light_tree(c));  // (NXHIP_LIGHT_IMPORTANCE_POSITION: the tree over the table just built, behind it in stream order)
     // passes on the other slots' streams must not start on a table half built
     if (slot_count(c) > 1) NX_HIP(hipStreamSynchronize(c->stream));
     c->lightTableDirty = false;
@@ -526,6 +582,26 @@ int nxhip_set_light_sampling(nxhip_ctx* c, int mode)
     return NXHIP_OK;
 }
 
+int nxhip_set_light_importance(nxhip_ctx* c, int importance)
+{
+    NX_CHECK_CTX(c);
+    if (importance != NXHIP_LIGHT_IMPORTANCE_POWER && importance != NXHIP_LIGHT_IMPORTANCE_POSITION) return fail_invalid("nxhip_set_light_importance: unknown importance");
+    if (importance == c->lightImportance) return NXHIP_OK;
+    // (frames accumulated so far stay: the expectation is the same.  The pass graphs are keyed by it: pass_flavor.  Remembered in
+    //  every mode; the tree is built or dropped by the next refresh_light_table in POWER mode)
+    c->lightImportance = importance;
+    c->lightTableDirty = true;
+    return NXHIP_OK;
+}
+
+uint32_t nxhip_light_tree_leaves_for(uint32_t entries)
+{
+    if (entries == 0u || entries > kLightTreeLeavesMax) return 0u;
+    uint32_t g = 1u;
+    while (g < entries) g <<= 1;
+    return g;
+}
+
 // What a render does before its pass, for the hooks that read the light table
 static int light_table_ready(nxhip_ctx* c, const char* who)
 {
@@ -584,6 +660,81 @@ try {
     float* dProb = b.out(prob, 1);
     return b.run(kernels::light_pick(), c->lightTable.as<LightEntry>(), c->lightGuide.as<uint32_t>(), c->lightGuideSize, c->lightEntries, dU, count, dEntry, dProb);
 } NX_CATCH("nxhip_light_pick_batch")
+
+// ---- the light tree's hooks --------------------------------------------------------------------------------
+
+static int light_tree_ready(nxhip_ctx* c, const char* who)
+{
+    NX_CHECK_CTX(c);
+    if (c->lightSampling != NXHIP_LIGHTS_POWER || c->lightImportance != NXHIP_LIGHT_IMPORTANCE_POSITION)
+        return fail_invalid(std::string(who) + ": the context is not in NXHIP_LIGHTS_POWER with NXHIP_LIGHT_IMPORTANCE_POSITION");
+    return light_table_ready(c, who);
+}
+
+// ... and for a pick or a probability: the tree (brought up to date) has a leaf, and weights that sum to something
+static int light_tree_pickable(nxhip_ctx* c, const char* who)
+{
+    if (c->lightEntries == 0u || c->lightTreeLeaves == 0u) return fail_invalid(std::string(who) + ": the light tree is empty (no mesh light has a triangle)");
+    LightHeader header{};
+    NX_SYNC_ALL(c);
+    NX_HIP(hipMemcpy(&header, c->lightHeader.p, sizeof header, hipMemcpyDeviceToHost));
+    if (header.valid == 0u) return fail_invalid(std::string(who) + ": the light tree is invalid (the lights' weights sum to nothing): nothing can be picked");
+    return NXHIP_OK;
+}
+
+int nxhip_read_light_tree(nxhip_ctx* c, float* nodes8, uint32_t* order, uint32_t capacityNodes, uint32_t* leaves, uint32_t* entries)
+try {
+    NX_DEBUG_HOOK("nxhip_read_light_tree");  // (first: a release library refuses whatever it is handed)
+    NX_TRY(light_tree_ready(c, "nxhip_read_light_tree"));
+    const uint32_t n = c->lightEntries, g = c->lightTreeLeaves;
+    if (leaves) *leaves = g;
+    if (entries) *entries = n;
+    if (!nodes8 && !order) return NXHIP_OK;
+    if (g == 0u) return fail_invalid("nxhip_read_light_tree: the light tree is empty (no mesh light has a triangle)");
+    if (capacityNodes < 2u * g) return fail_invalid("nxhip_read_light_tree: destination too small");
+    static_assert(sizeof(LightNode) == 8 * sizeof(float), "a node is read back as eight words");
+    NX_SYNC_ALL(c);
+    if (nodes8) NX_HIP(hipMemcpy(nodes8, c->lightTreeNodes.p, 2 * (size_t)g * sizeof(LightNode), hipMemcpyDeviceToHost));
+    if (order) NX_HIP(hipMemcpy(order, c->lightTreeOrder.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+    return NXHIP_OK;
+} NX_CATCH("nxhip_read_light_tree")
+
+int nxhip_light_tree_pick_batch(nxhip_ctx* c, const float* points3, const float* u, uint32_t count, uint32_t* entry, float* prob)
+try {
+    NX_DEBUG_HOOK("nxhip_light_tree_pick_batch");  // (first: a release library refuses whatever it is handed)
+    NX_CHECK_CTX(c);
+    if ((!points3 || !u || !entry || !prob) && count) return fail_invalid("nxhip_light_tree_pick_batch: null buffer");
+    if (!all_finite(points3, 3 * (size_t)count)) return fail_invalid("nxhip_light_tree_pick_batch: a point is not finite");
+    if (!all_unit(u, count)) return fail_invalid("nxhip_light_tree_pick_batch: u must be in [0, 1)");
+    NX_TRY(light_tree_ready(c, "nxhip_light_tree_pick_batch"));
+    if (count == 0) return NXHIP_OK;
+    NX_TRY(light_tree_pickable(c, "nxhip_light_tree_pick_batch"));
+    HookBatch b(c, count);
+    const float* dP = b.in(points3, 3);
+    const float* dU = b.in(u, 1);
+    uint32_t* dEntry = b.out(entry, 1);
+    float* dProb = b.out(prob, 1);
+    return b.run(kernels::light_tree_pick(), c->lightTreeNodes.as<LightNode>(), c->lightTreeLeaves, dP, dU, count, dEntry, dProb);
+} NX_CATCH("nxhip_light_tree_pick_batch")
+
+int nxhip_light_tree_prob_batch(nxhip_ctx* c, const float* points3, const uint32_t* entry, uint32_t count, float* prob)
+try {
+    NX_DEBUG_HOOK("nxhip_light_tree_prob_batch");  // (first: a release library refuses whatever it is handed)
+    NX_CHECK_CTX(c);
+    if ((!points3 || !entry || !prob) && count) return fail_invalid("nxhip_light_tree_prob_batch: null buffer");
+    if (!all_finite(points3, 3 * (size_t)count)) return fail_invalid("nxhip_light_tree_prob_batch: a point is not finite");
+    NX_TRY(light_tree_ready(c, "nxhip_light_tree_prob_batch"));
+    // (before anything is launched: an entry past the table would index slotOf wildly)
+    for (uint32_t k = 0; k < count; k++)
+        if (entry[k] >= c->lightEntries) return fail_invalid("nxhip_light_tree_prob_batch: no such entry");
+    if (count == 0) return NXHIP_OK;
+    NX_TRY(light_tree_pickable(c, "nxhip_light_tree_prob_batch"));
+    HookBatch b(c, count);
+    const float* dP = b.in(points3, 3);
+    const uint32_t* dEntry = b.in(entry, 1);
+    float* dProb = b.out(prob, 1);
+    return b.run(kernels::light_tree_prob(), c->lightTreeNodes.as<LightNode>(), c->lightTreeLeaves, c->lightTreeSlotOf.as<uint32_t>(), dP, dEntry, count, dProb);
+} NX_CATCH("nxhip_light_tree_prob_batch")
 
 }  // extern "C"
 

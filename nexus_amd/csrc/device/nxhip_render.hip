@@ -205,6 +205,9 @@ int trace_blocks(const nxhip_ctx* c, int fullGrid)
 // NXHIP_SHADOWS_TRANSMIT takes effect in a pass (kFlavorTransmit, below): the mode is on AND some material of the table is see-through.
 bool transmit_active(const nxhip_ctx* c) { return c->shadowTransmittance == NXHIP_SHADOWS_TRANSMIT && c->materialsSeeThrough; }
 
+// NXHIP_LIGHT_IMPORTANCE_POSITION takes effect in a pass (kFlavorLightTree, below): POWER mode, the setting, and the SCAN pipeline.
+bool light_tree_active(const nxhip_ctx* c) { return c->lightSampling == NXHIP_LIGHTS_POWER && c->lightImportance == NXHIP_LIGHT_IMPORTANCE_POSITION && scan_pipeline(c); }
+
 int tail_bounce(const nxhip_ctx* c)
 {
     // (the tail kernel traces its shadow rays with traverse_wave<true>, which knows no transmittance: a first version's restriction,
@@ -212,6 +215,7 @@ int tail_bounce(const nxhip_ctx* c)
     if (transmit_active(c)) return 0;
     if (c->materialsAlphaSolid) return 0;  // (... nor alpha modes: kFlavorAlphaTest / kFlavorSolid, below — the same restriction)
     if (c->h.mediumOn) return 0;  // (nor does the tail kernel know the medium: kFlavorMedium, below — the same restriction)
+    if (light_tree_active(c)) return 0;  // (nor the light tree: kFlavorLightTree, below — the same restriction)
     int bounce = c->tailBounce;
     if (bounce < 0) {
         const double frames = pass_size_in_frames(c);
@@ -285,6 +289,11 @@ constexpr int kFlavorAlphaTest = 65536;
 // well, so the bit implies the general material launch (no NO_MAPS form); and there is no tail kernel (tail_bounce).  kFlavorAlphaTest
 // is never set without it.
 constexpr int kFlavorSolid = 131072;
+// kFlavorLightTree: POWER mode with nxhip_set_light_importance(NXHIP_LIGHT_IMPORTANCE_POSITION) under the SCAN pipeline — the material
+// launch and the medium's scatter kernel are their TREE instances, whose mesh-light sample descends the light tree (nx_lights.h).  Never
+// without kFlavorLightPower.  A first version's restrictions: no map-free instance, no tail kernel (tail_bounce), and the classic
+// pipeline ignores the setting (its kernels have no TREE form).  Without the setting the bit is clear and the graphs are what they were.
+constexpr int kFlavorLightTree = 262144;
 inline bool materials_metal(const nxhip_ctx* c) { return ((c->materialTypeMask >> NX_MAT_METALROUGH) & 1u) != 0u; }
 int pass_flavor(const nxhip_ctx* c)
 {
@@ -305,6 +314,7 @@ int pass_flavor(const nxhip_ctx* c)
     // (kShadeDropEnded).  Pixel-keyed random numbers only: a slot-keyed draw needs the slot the ray goes to.
     if (scan_pipeline(c) && !(f & kFlavorMissKernel) && c->h.rngMode == NX_RNG_PIXEL_KEYED) f |= kFlavorDropEnded;
     if (c->lightSampling == NXHIP_LIGHTS_POWER) f |= kFlavorLightPower;  // (the material kernels' POWER variants: a graph of one mode is never replayed in the other)
+    if (light_tree_active(c)) f |= kFlavorLightTree;
     if (c->aov) f |= kFlavorAov;  // (one more branch beside the bounce-1 material step: frame_levels)
     if (c->entryPoints) f |= kFlavorEntry;  // (the slot's table exists before its graph is asked for: ensure_entry_table)
     // The thin kernel (nx_trace.hip) pays when ONE pass runs at a time: the lanes a dry wave leaves idle are then idle SIMD time, and
@@ -335,6 +345,7 @@ constexpr unsigned material_features(int flavor)
 {
     unsigned f = 0u;
     if (flavor & kFlavorLightPower) f |= kMfPower;
+    if ((flavor & kFlavorLightTree) && (flavor & kFlavorLightPower) && (flavor & kFlavorScan)) f |= kMfTree;
     if (flavor & kFlavorAnalytic) f |= kMfAnalytic;
     if (flavor & kFlavorDetail) f |= kMfDetail;
     if (flavor & kFlavorMetal) f |= kMfMetal;
@@ -350,9 +361,12 @@ constexpr unsigned shade_features(int flavor, int type)
     return material_features(type == NX_MAT_METALROUGH ? flavor : (flavor & ~kFlavorMetal)) & kMfShadeReads;
 }
 // ... of the tail kernel: it has no map-free form (and no SOLID one: tail_bounce is 0 then, and a set with the bit finds no instance)
-constexpr unsigned tail_features(int flavor) { return material_features(flavor) & ~kMfNoMaps; }
+constexpr unsigned tail_features(int flavor) { return material_features(flavor) & ~kMfNoMaps; }  // (a TREE set finds no instance: tail_bounce is 0 then)
 // ... of the medium's scatter kernel and of the logic kernel: they shade no surface, so each knows the facts it reads and no closure
-constexpr unsigned medium_features(int flavor) { return material_features(flavor & (kFlavorLightPower | kFlavorAnalytic | kFlavorMetal)) & kMfMediumReads; }
+constexpr unsigned medium_features(int flavor)
+{
+    return material_features(flavor & (kFlavorScan | kFlavorLightPower | kFlavorLightTree | kFlavorAnalytic | kFlavorMetal)) & kMfMediumReads;
+}
 // (logic_kernel: the analytic lights' count enters the weighted miss, which needs an environment map — the two-item instance of
 //  scenes without one has no ANALYTIC form)
 constexpr unsigned logic_features(int flavor, int items) { return items == 1 ? material_features(flavor) & kMfLogicReads : 0u; }
@@ -378,6 +392,10 @@ static_assert(material_features(kFlavorScan | kFlavorIdentity | kFlavorNoMaps) =
               "an identity-only, map-free scene: the specialised instances, and the general tail kernel");
 static_assert(material_features(kFlavorScan | kFlavorAnalytic | kFlavorLightPower) == (kMfAnalytic | kMfPower) && logic_features(kFlavorAnalytic, 1) == kMfAnalytic && logic_features(kFlavorAnalytic, 2) == 0u,
               "analytic lights with power sampling");
+static_assert(material_features(kFlavorScan | kFlavorNoMaps | kFlavorLightPower | kFlavorLightTree) == (kMfPower | kMfTree) && material_features(kFlavorLightPower | kFlavorLightTree) == kMfPower &&
+                  material_features(kFlavorScan | kFlavorLightTree) == 0u && medium_features(kFlavorScan | kFlavorLightPower | kFlavorLightTree | kFlavorDetail) == (kMfPower | kMfTree) &&
+                  shade_features(kFlavorLightPower | kFlavorLightTree, NX_MAT_DIFFUSE) == kMfPower,
+              "the light tree: the SCAN material launch and the medium in POWER mode, no map-free form, nothing under the classic pipeline");
 static_assert(material_features(kFlavorScan | kFlavorSolid | kFlavorNoMaps) == (kMfSolid | kMfMetal | kMfDetail) && material_features(kFlavorScan | kFlavorMetal) == (kMfMetal | kMfDetail) &&
                   material_features(kFlavorNoMaps) == 0u,
               "SOLID implies METAL implies DETAIL, each drops NO_MAPS, and the classic pipeline never asks for it");

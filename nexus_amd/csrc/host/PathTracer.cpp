@@ -276,6 +276,7 @@ void PathTracer::SetQueueBudget(int queues) { Check(nxhip_set_queue_budget(m_Ctx
 void PathTracer::SetTailBounce(uint32_t bounce) { Check(nxhip_set_tail_bounce(m_Ctx, bounce), "nxhip_set_tail_bounce"); }
 void PathTracer::SetEntryPoints(bool on) { Check(nxhip_set_entry_points(m_Ctx, on ? 1 : 0), "nxhip_set_entry_points"); }
 void PathTracer::SetLightSampling(int mode) { Check(nxhip_set_light_sampling(m_Ctx, mode), "nxhip_set_light_sampling"); }
+void PathTracer::SetLightImportance(int importance) { Check(nxhip_set_light_importance(m_Ctx, importance), "nxhip_set_light_importance"); }
 void PathTracer::SetShadowTransmittance(int mode) { Check(nxhip_set_shadow_transmittance(m_Ctx, mode), "nxhip_set_shadow_transmittance"); }
 void PathTracer::SetPixelOrder(int order)
 {

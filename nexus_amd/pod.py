@@ -131,6 +131,7 @@ COMPACT_FAST, COMPACT_ORDERED = 0, 1
 CONDUCTOR_REFERENCE, CONDUCTOR_EXTENDED = 0, 1
 ORDER_ROWS, ORDER_TILES = 0, 1  # nxhip_set_pixel_order
 LIGHTS_UNIFORM, LIGHTS_POWER = 0, 1  # nxhip_set_light_sampling
+LIGHT_IMPORTANCE_POWER, LIGHT_IMPORTANCE_POSITION = 0, 1  # nxhip_set_light_importance
 SHADOWS_OPAQUE, SHADOWS_TRANSMIT = 0, 1  # nxhip_set_shadow_transmittance
 PATH_MAX_LENGTH = 100
 # include/nexus_fmath.h NXF_OP_*: the shared transcendental functions, by number (double: 0-6; float, carried in doubles: 7-12)

@@ -47,6 +47,8 @@ def checker_texture(w=64, h=32, seed=0, alpha=False):
 class Workload:
     # extension: pod.LIGHTS_POWER picks the mesh lights' triangles by area x emitted luminance (nxhip_set_light_sampling); applied by upload
     light_sampling = pod.LIGHTS_UNIFORM
+    # extension: pod.LIGHT_IMPORTANCE_POSITION lets the POWER-mode pick depend on the shading point (nxhip_set_light_importance); applied by upload
+    light_importance = pod.LIGHT_IMPORTANCE_POWER
     # extension: pod.SHADOWS_TRANSMIT lets opacity and texture alpha attenuate shadow rays (nxhip_set_shadow_transmittance); applied by upload
     shadow_transmittance = pod.SHADOWS_OPAQUE
     # extension: detail maps (nxhip_set_material_detail) — RGBA8 images of linear data and one pod.DETAIL_DT record per material; applied by upload
@@ -141,6 +143,7 @@ class Workload:
             ctx.set_camera(self.camera)
         ctx.set_render_settings(self.settings)
         ctx.set_light_sampling(self.light_sampling)
+        ctx.set_light_importance(self.light_importance)
         ctx.set_shadow_transmittance(self.shadow_transmittance)
         ctx.set_medium(self.medium)
         ctx.set_medium_density(self.medium_density)
