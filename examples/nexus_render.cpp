@@ -3,7 +3,7 @@
 //
 //   nexus_render [--denoise] [--adaptive THRESHOLD [--max-frames N]] [--light-sampling uniform|power|position] [--transparent-shadows] [--env-float FILE.hdr] [--env-sampling]
 //                [--no-detail-maps] [--metal-rough] [--alpha-modes] [--fog SIGMA [--fog-albedo R G B] [--fog-g G] [--fog-box X0 Y0 Z0 X1 Y1 Z1] [--fog-grid FILE.npy]]
-//                [--point-light X Y Z INTENSITY] [--sun DX DY DZ IRRADIANCE] [--time T [--animation K]] <dir/> <file.glb|file.obj> <out.ppm> [width height frames pathLength]
+//                [--point-light X Y Z INTENSITY] [--sun DX DY DZ IRRADIANCE] [--time T [--animation K]] [--morph-targets] <dir/> <file.glb|file.obj> <out.ppm> [width height frames pathLength]
 //                [eyeX eyeY eyeZ fwdX fwdY fwdZ hfovDeg]
 // --denoise: the feature buffers are accumulated with the colour and the image written is the a-trous filtered one (nxhip_denoise)
 // --adaptive THRESHOLD: render to a noise target instead of a frame count (nxhip_render_adaptive: blocks of 64 pixels stop when the
@@ -35,6 +35,9 @@
 // --time T [--animation K]: a .glb's skins are kept (Scene::SetSkins) and every skinned mesh of the file is posed at T seconds of animation K
 //   (default 0; a file without animations: the rest pose) before rendering — the pose is evaluated on the host (Scene::JointPalette), the
 //   vertices are blended and the mesh's BVH refitted on the device (PathTracer::PoseMesh, nxhip_pose_blas).  One pose holds for the image.
+// --morph-targets: a .glb's morph targets are kept (Scene::SetMorphs) and every mesh that has some is posed with the file's default weights —
+//   with --time T [--animation K], with the weights that animation gives at T (Scene::MorphWeights) — combined with the joint palette where
+//   the mesh is skinned: deltas, then joints, in one pass on the device (nxhip_pose_blas_morph).  Without it targets are ignored, as before.
 //
 // Build: make example   (links nexus_amd/lib/libnexus_amd.so)
 #include <cstdint>
@@ -66,7 +69,7 @@ int main(int argc, char** argv)
     bool fog = false, fogBox = false;
     nexus::Medium medium;
     std::string fogGrid;
-    bool posed = false;
+    bool posed = false, morphTargets = false;
     double poseTime = 0.0;
     int poseAnimation = 0;
     for (;;) {  // leading options, in any order
@@ -113,6 +116,9 @@ int main(int argc, char** argv)
             posed = true;
             poseTime = std::atof(argv[2]);
             used = 2;
+        } else if (opt == "--morph-targets") {
+            morphTargets = true;
+            used = 1;
         } else if (opt == "--animation" && argc > 2) {
             poseAnimation = std::atoi(argv[2]);
             used = 2;
@@ -155,7 +161,7 @@ int main(int argc, char** argv)
         return 2;
     }
     if (argc < 4) {
-        std::fprintf(stderr, "usage: %s [--denoise] [--adaptive THRESHOLD [--max-frames N]] [--light-sampling uniform|power|position] [--transparent-shadows] [--env-float FILE.hdr] [--env-sampling] [--no-detail-maps] [--metal-rough] [--alpha-modes] [--fog SIGMA [--fog-albedo R G B] [--fog-g G] [--fog-box X0 Y0 Z0 X1 Y1 Z1] [--fog-grid FILE.npy]] [--point-light X Y Z INTENSITY] [--sun DX DY DZ IRRADIANCE] [--time T [--animation K]] <dir/> <file.glb|file.obj> <out.ppm> [width height frames pathLength] [eye(3) forward(3) hfov]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s [--denoise] [--adaptive THRESHOLD [--max-frames N]] [--light-sampling uniform|power|position] [--transparent-shadows] [--env-float FILE.hdr] [--env-sampling] [--no-detail-maps] [--metal-rough] [--alpha-modes] [--fog SIGMA [--fog-albedo R G B] [--fog-g G] [--fog-box X0 Y0 Z0 X1 Y1 Z1] [--fog-grid FILE.npy]] [--point-light X Y Z INTENSITY] [--sun DX DY DZ IRRADIANCE] [--time T [--animation K]] [--morph-targets] <dir/> <file.glb|file.obj> <out.ppm> [width height frames pathLength] [eye(3) forward(3) hfov]\n", argv[0]);
         return 2;
     }
     // a program built against these headers and run with another build of libnexus_amd.so gets an error string here, not a GPU fault
@@ -184,18 +190,26 @@ int main(int argc, char** argv)
         }
         scene.SetMetalRoughMaterials(metalRough);
         scene.SetMaterialAlphaModes(alphaModes);
-        scene.SetSkins(posed);
+        scene.SetSkins(posed || morphTargets);
+        scene.SetMorphs(morphTargets);
         scene.CreateMeshInstanceFromFile(dir, file);  // (a .glb's KHR_lights_punctual lights come with it)
-        size_t posedMeshes = 0;
-        if (posed) {  // before the first Update: the instances are then placed around the posed boxes
-            const int animation = scene.GetAnimations().empty() ? -1 : poseAnimation;
+        size_t posedMeshes = 0, morphedMeshes = 0;
+        if (posed || morphTargets) {  // before the first Update: the instances are then placed around the posed boxes
+            const int animation = !posed || scene.GetAnimations().empty() ? -1 : poseAnimation;
             const std::vector<nexus::Mesh>& meshes = scene.GetAssetManager().GetMeshes();
             for (size_t m = 0; m < meshes.size(); m++) {
-                if (!meshes[m].skin) continue;
+                if (morphTargets && meshes[m].morph) {  // deltas first, then the joints where the mesh has a skin
+                    const std::vector<float> palette = meshes[m].skin ? scene.JointPalette(static_cast<uint32_t>(m), animation, poseTime) : std::vector<float>();
+                    pathTracer.PoseMesh(scene, meshes[m].bvhId, scene.MorphWeights(static_cast<uint32_t>(m), animation, poseTime), palette);
+                    morphedMeshes++;
+                    continue;
+                }
+                if (!posed || !meshes[m].skin) continue;
                 pathTracer.PoseMesh(scene, meshes[m].bvhId, scene.JointPalette(static_cast<uint32_t>(m), animation, poseTime));
                 posedMeshes++;
             }
-            if (posedMeshes == 0) std::fprintf(stderr, "nexus_render: --time: %s has no skinned mesh; rendered as it is\n", file.c_str());
+            if (posed && posedMeshes + morphedMeshes == 0) std::fprintf(stderr, "nexus_render: --time: %s has no skinned mesh; rendered as it is\n", file.c_str());
+            if (morphTargets && morphedMeshes == 0) std::fprintf(stderr, "nexus_render: --morph-targets: %s has no mesh with morph targets; rendered as it is\n", file.c_str());
         }
         if (!detailMaps) scene.GetAssetManager().ClearMaterialDetails();  // (the file's normal and roughness maps: loaded, not used)
         for (const nexus::AnalyticLight& l : extraLights) scene.AddAnalyticLight(l);
@@ -271,6 +285,8 @@ int main(int argc, char** argv)
         std::printf("%s: %u x %u, %d frames, %zu instances, %zu lights%s%s\n", out.c_str(), width, height, frames, scene.GetBVHInstances().size(), scene.GetLights().size(),
                     deviceBuilders ? ", BVHs built on the device" : "", denoise ? ", denoised" : "");
         if (posedMeshes) std::printf("posed %zu skinned mesh(es) at t = %g s of animation %d\n", posedMeshes, poseTime, poseAnimation);
+        if (morphedMeshes && posed) std::printf("morphed %zu mesh(es) with the weights at t = %g s of animation %d\n", morphedMeshes, poseTime, poseAnimation);
+        if (morphedMeshes && !posed) std::printf("morphed %zu mesh(es) with the file's default weights\n", morphedMeshes);
         if (adaptive) {
             std::vector<uint32_t> counts;
             pathTracer.ReadSampleCounts(counts);

@@ -108,6 +108,19 @@ struct Skin {
     bool onDevice = false;                // nxhip_set_blas_skin has been called for the mesh's BLAS
 };
 
+// Extension (morph targets; the rule: nexus_hip.h, nxhip_pose_blas_morph): the blend shapes of one mesh as the .glb reader finds them
+// (LoadOptions::morphs) — per target and triangle corner a position and a normal delta, de-indexed like the positions, target-major; the
+// default weights (the placing node's, else the mesh's, else zeros); extras.targetNames; the node that carries the mesh.
+// Scene::MorphWeights samples an animation's weights from it, PathTracer::PoseMesh sends it to the device on first use.
+struct Morph {
+    std::vector<nx_morph_corner> deltas;  // targets x (3 per triangle): record t x corners + 3 i + v is vertex v of triangle i under target t
+    uint32_t targets = 0;
+    std::vector<float> weights;           // one per target: the file's defaults
+    std::vector<std::string> names;       // extras.targetNames, or empty
+    int meshNode = -1;
+    bool onDevice = false;                // nxhip_set_blas_morph has been called for the mesh's BLAS
+};
+
 // ... a node of a loaded file's tree (parent and rest TRS), and a joint animation as channels
 struct SceneNode {
     std::string name;
@@ -117,12 +130,12 @@ struct SceneNode {
     double matrix[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};  // row major
 };
 struct AnimationChannel {
-    enum Path { TRANSLATION = 0, ROTATION = 1, SCALE = 2 };
+    enum Path { TRANSLATION = 0, ROTATION = 1, SCALE = 2, WEIGHTS = 3 };  // WEIGHTS: morph targets (LoadOptions::morphs only)
     int node = -1;
     Path path = TRANSLATION;
     bool step = false;            // STEP; else LINEAR (rotations: shortest-arc slerp).  CUBICSPLINE is read as LINEAR over the keys' values
     std::vector<double> times;    // ascending
-    std::vector<double> values;   // 3 (4 for rotations) per key
+    std::vector<double> values;   // 3 (4 for rotations; the target count for weights) per key
 };
 struct Animation {
     std::string name;
@@ -140,6 +153,7 @@ struct Mesh {
     int32_t materialId = -1;
     std::string name;
     std::shared_ptr<Skin> skin;  // empty: the mesh is not skinned
+    std::shared_ptr<Morph> morph;  // empty: the mesh has no morph targets
 };
 
 struct MeshInstance {

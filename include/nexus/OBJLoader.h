@@ -45,6 +45,9 @@ struct LoadedScene {
     // glTF skins, joint animations and the node tree — filled only when asked for (LoadOptions::skins), else empty.  skins[i] belongs to
     // meshes[i] (empty pointer: not skinned); node indices are the file's.
     std::vector<std::shared_ptr<Skin>> skins;
+    // glTF morph targets — filled only when asked for (LoadOptions::morphs, which fills nodes and animations too and keeps the animations'
+    // weights channels), else empty.  morphs[i] belongs to meshes[i] (empty pointer: no targets).
+    std::vector<std::shared_ptr<Morph>> morphs;
     std::vector<SceneNode> nodes;
     std::vector<Animation> animations;
     std::vector<std::string> warnings;  // images that could not be decoded (the reference prints and carries on, IMGLoader.cpp:24-25)
@@ -59,12 +62,17 @@ struct LoadedScene {
 // (SetMaterialAlpha).  A MASK material whose alphaCutoff lies outside [0, 1] is refused by the reader, with the material's number.  .obj files
 // carry no such mode: their materials stay blends.
 // skins (off by default, so every existing scene loads as before): a .glb's skins, JOINTS_0 / WEIGHTS_0, joint animations and node tree are
-// read into LoadedScene::skins / animations / nodes, and LoadOBJ hands them to the meshes and the scene.  Morph targets and JOINTS_1 are
-// ignored with a warning; a CUBICSPLINE sampler is read as its keys' values and interpolated linearly, with a warning.
+// read into LoadedScene::skins / animations / nodes, and LoadOBJ hands them to the meshes and the scene.  JOINTS_1 is ignored with a
+// warning, and so are morph targets unless `morphs` is on; a CUBICSPLINE sampler is read as its keys' values and interpolated linearly,
+// with a warning.
+// morphs (off by default): a .glb's morph targets — POSITION and NORMAL, float VEC3, sparse accessors included; all primitives of a mesh
+// with the same number of them — are read into LoadedScene::morphs, the node tree and the animations as under `skins`, and the animations'
+// `weights` channels are kept.  TANGENT deltas are not read: the 96-byte triangle has no tangents.
 struct LoadOptions {
     bool metalRough = false;
     bool alphaModes = false;
     bool skins = false;
+    bool morphs = false;
 };
 
 class OBJLoader {

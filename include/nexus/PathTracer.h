@@ -37,6 +37,11 @@ public:
     // read per posed mesh) for AssetManager::SetPosedBounds — from there Scene::Update and UpdateDeviceScene proceed as for a deformed
     // mesh, in all three TLAS modes.  The host's copy of the triangles stays the bind pose.  Throws for a mesh without a skin.
     void PoseMesh(Scene& scene, int32_t bvhId, const std::vector<float>& palette);
+    // Extension (morph targets): the same for a mesh with morph targets — one weight per target (Scene::MorphWeights) and, where the mesh is
+    // skinned too, its palette; an empty palette for an unskinned mesh.  Morph and skin go to the device on first use
+    // (nxhip_set_blas_morph, nxhip_set_blas_skin), the device adds the active targets' deltas, blends the joints and refits the BLAS in one
+    // pass (nxhip_pose_blas_morph).  Weights do not persist: the next pose names them again.  Throws for a mesh without a morph.
+    void PoseMesh(Scene& scene, int32_t bvhId, const std::vector<float>& weights, const std::vector<float>& palette);
     void SetPixelQuery(uint32_t x, uint32_t y);
     int32_t GetSelectedInstance();
     uint32_t GetFrameNumber() const { return m_FrameNumber; }

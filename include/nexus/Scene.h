@@ -38,6 +38,15 @@ public:
     // not vertices — and PathTracer::PoseMesh has the device blend the vertices and refit the mesh's BVH (nxhip_pose_blas).
     void SetSkins(bool on) { m_Skins = on; }
     bool GetSkins() const { return m_Skins; }
+    // Extension, off by default: the files loaded from here on keep their glTF morph targets, the node tree and the animations with their
+    // weights channels (OBJLoader.h LoadOptions::morphs): Mesh::morph.  MorphWeights evaluates the weights on the host, and the PoseMesh
+    // overload that takes weights has the device blend the deltas — and the joints, on a skinned mesh — into the mesh's BVH.
+    void SetMorphs(bool on) { m_Morphs = on; }
+    bool GetMorphs() const { return m_Morphs; }
+    // The weights of morphed mesh `meshId`: the file's defaults, or — where animation `animationIdx` (-1: none) has a weights channel on the
+    // node that places the mesh — that channel sampled at time t by JointPalette's rule for STEP and LINEAR channels, in binary64, rounded
+    // once.  The twin of nexus_amd/animation.py morph_weights.  Throws for a mesh without a morph or an animation that does not exist.
+    std::vector<float> MorphWeights(uint32_t meshId, int animationIdx, double t) const;
     const std::vector<SceneNode>& GetNodes() const { return m_Nodes; }
     const std::vector<Animation>& GetAnimations() const { return m_Animations; }
     // (used by OBJLoader::LoadOBJ: a file's nodes and animations, their node indices already those of GetNodes())
@@ -142,6 +151,7 @@ private:
     bool m_MetalRoughMaterials = false;
     bool m_MaterialAlphaModes = false;
     bool m_Skins = false;
+    bool m_Morphs = false;
     std::vector<SceneNode> m_Nodes;
     std::vector<Animation> m_Animations;
     DensityGrid m_MediumDensity;

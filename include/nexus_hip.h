@@ -176,12 +176,56 @@ int nxhip_update_blas_device(nxhip_ctx *ctx, int32_t blasId, const void *trisDev
  * not finite becomes (0, 0, 0) too.  Texture coordinates are copied.  Evaluation order and fma contraction are the compiler's: the tests
  * bound the result (positions: gamma_8 x sum_k w_k sum_c |J_k[r][c]| |(p, 1)_c|), not its bits.  The palette is read from the LDS up to
  * 1024 joints (48 KiB) and from global memory above.
- * Not covered: morph targets and more than four influences (JOINTS_1) — the loaders warn and ignore them —; CUBICSPLINE samplers — the
+ * Not covered: more than four influences (JOINTS_1) — the loaders warn and ignore them —; CUBICSPLINE samplers — the
  * loaders warn, read the value component of each key and interpolate it linearly —; dual-quaternion blending; motion blur (one pose holds
  * for a frame; nothing in traversal or shading changes); a restatement in the CPU oracle (the tests compare with float64 arithmetic and
  * with nxhip_update_blas of the read-back triangles). */
 int nxhip_set_blas_skin(nxhip_ctx *ctx, int32_t blasId, const nx_skin_corner *corners, uint32_t cornerCount, uint32_t jointCount);
 int nxhip_pose_blas(nxhip_ctx *ctx, int32_t blasId, const float *jointMatrices, uint32_t jointCount);
+/* Extension — morph targets (glTF blend shapes): the stage in front of the joint blend, in the same single pass.  A BLAS is given its
+ * targets once — per target and triangle corner a position and a normal delta, glTF's target POSITION / NORMAL de-indexed like the
+ * positions —; after that a pose is `targetCount` weights, plus the joint palette where the BLAS is skinned.  The deltas live in device
+ * memory (80 bytes per target and triangle); a pose costs what its ACTIVE targets cost — those whose weight is not 0 —, not what the BLAS
+ * has.  The reference has nothing of the kind.
+ *
+ * nxhip_set_blas_morph: `deltas` is target-major: record t x cornerCount + 3 i + v belongs to vertex v of triangle i under target t (the
+ * corner numbering of nxhip_set_blas_skin).  Refused with NXHIP_ERR_INVALID before anything is allocated, the previous state left in
+ * place: a bad id, a cornerCount that is not 3 x the BLAS's triangle count, targetCount 0 or above 1024, a delta component that is not
+ * finite.  deltas == NULL removes the morph (the device is waited for first, as for the skin); triangles and nodes stay as last posed.
+ * Works on any BLAS id: uploaded, device-built or one of a batch.
+ *
+ * THE BIND COPY is one, shared by the skin and the morph of a BLAS:
+ *   - whichever of nxhip_set_blas_skin and nxhip_set_blas_morph finds the BLAS with NEITHER takes the copy from the BLAS's current triangles;
+ *   - the one that finds the OTHER already present keeps that copy: deltas and skin then describe the same shape, in either order of setting;
+ *   - a skin set again on a BLAS that has only a skin re-takes the copy, and so does a morph set again on a BLAS that has only a morph;
+ *   - removing one of the two leaves the copy to the other; removing the last frees it;
+ *   - nxhip_update_blas(_device) never touches it.
+ *
+ * nxhip_pose_blas_morph: the BLAS must have a morph and targetCount must equal its own; weights must be finite — negative weights and
+ * weights above 1 are allowed, as glTF allows them.  On a skinned BLAS jointMatrices / jointCount are required and validated as by
+ * nxhip_pose_blas; on an unskinned BLAS they must be NULL and 0.  Anything else: NXHIP_ERR_INVALID, nothing changed.  The host compacts
+ * the weights into the list of active targets — (index, weight) pairs, ascending index — and uploads it in stream order; the kernel loops
+ * over that list only.  Ordering, side effects and the final wait are exactly nxhip_pose_blas's.  Weights do not persist and poses do not
+ * accumulate: every pose starts from the bind copy, and nxhip_pose_blas on a BLAS that also has a morph does what it always did — it is
+ * the pose with all weights 0.
+ *
+ * THE RULE, all of it in binary32; per corner, A = the active targets in ascending order:
+ *   p' = p + sum_{t in A} w_t dPosition_t          n' = n + sum_{t in A} w_t dNormal_t, then normalised
+ * summed left to right starting from the bind value.  A bind normal of exactly (0, 0, 0) stays (0, 0, 0) and its deltas are not applied;
+ * an n' whose length is 0 or not finite becomes (0, 0, 0).  On a skinned BLAS the rule of nxhip_pose_blas is then applied to (p', n'),
+ * unchanged: glTF's order, morph first, then skin.  Texture coordinates are copied.  With NO active target the stage is absent, not a sum
+ * of zeros: an unskinned BLAS gets its bind copy back bit for bit (normals not renormalised), a skinned one nxhip_pose_blas's triangles.
+ * Contraction is the compiler's, so the tests bound the result, not its bits:
+ *   positions  |err_c| <= gamma_{A+1} (|p_c| + sum_t |w_t| |dP_t,c|)        (A products and A additions; gamma_k = k u / (1 - k u), u = 2^-24)
+ *   normals    with v the exact unnormalised sum and t_c = |n_c| + sum_t |w_t| |dN_t,c|: the computed sum is v + e, |e_c| <= gamma_{A+1} t_c;
+ *              normalising v + e instead of v moves the unit vector by at most 2 ||e|| / ||v||, and the squares, their sum, the root and
+ *              the division stay within 4 u per component:  ||n' - v / ||v|| ||_inf <= 2 gamma_{A+1} ||t|| / ||v|| + 4 u
+ *              (as nxhip_pose_blas's normal bound is derived, with the sum's gamma in place of the cofactor product's).
+ *   skinned    the bound of nxhip_pose_blas evaluated at |p'|, plus the position bound above carried through sum_c |M[r][c]|.
+ * Not covered: TANGENT deltas (the 96-byte triangle has no tangents), more than 1024 targets per BLAS, motion blur, and a restatement in
+ * the CPU oracle (the tests compare with float64 arithmetic and with nxhip_update_blas of the read-back triangles). */
+int nxhip_set_blas_morph(nxhip_ctx *ctx, int32_t blasId, const nx_morph_corner *deltas, uint32_t cornerCount, uint32_t targetCount);
+int nxhip_pose_blas_morph(nxhip_ctx *ctx, int32_t blasId, const float *weights, uint32_t targetCount, const float *jointMatrices, uint32_t jointCount);
 /* The BLAS's current 96-byte triangles (as uploaded, last updated or last posed); capacity >= its triangle count. */
 int nxhip_read_blas_triangles(nxhip_ctx *ctx, int32_t blasId, nx_triangle *out, uint32_t capacity);
 /* The box the BLAS's root node encodes after the last build, refit or pose: its quantisation frame [p, p + 255 x 2^(e - 127)], decoded as
@@ -1150,7 +1194,7 @@ static inline uint64_t nxhip_header_abi_stamp(void)
         sizeof(nx_material), offsetof(nx_material, emissive), offsetof(nx_material, type), sizeof(nx_light), offsetof(nx_light, type),
         sizeof(nx_analytic_light), offsetof(nx_analytic_light, direction), offsetof(nx_analytic_light, colour), offsetof(nx_analytic_light, innerConeAngle), offsetof(nx_analytic_light, type),
         sizeof(nx_material_detail), offsetof(nx_material_detail, normalScale), sizeof(nx_medium), sizeof(nx_material_alpha), offsetof(nx_material_alpha, cutoff),
-        sizeof(nx_skin_corner), offsetof(nx_skin_corner, weight),
+        sizeof(nx_skin_corner), offsetof(nx_skin_corner, weight), sizeof(nx_morph_corner), offsetof(nx_morph_corner, dNormal),
         sizeof(nx_camera), offsetof(nx_camera, resolution), sizeof(nx_render_settings), offsetof(nx_render_settings, backgroundColor),
         sizeof(nx_ray), sizeof(nx_hit), sizeof(nx_bsdf_query), sizeof(nx_bsdf_result), offsetof(nx_bsdf_result, rngOut),
         sizeof(nxhip_queue_sizes), sizeof(nxhip_trace_stats), offsetof(nxhip_trace_stats, cycles), sizeof(nxhip_kernel_times), NXHIP_K_COUNT,

@@ -74,9 +74,14 @@ int nxh_load_scene_file(const char *file, nxh_loaded_scene **out);
  * from nxh_loaded_material_alpha; without the flag that call reports no table (every material blends, as it always has). */
 #define NXH_LOAD_ALPHA_MODES 2u
 /* NXH_LOAD_SKINS: a .glb's skins (JOINTS_0 / WEIGHTS_0 de-indexed like the positions), joint animations and node tree are read as well;
- * nxh_loaded_skin reports a mesh's.  Morph targets and JOINTS_1 are ignored with a warning, a CUBICSPLINE sampler is read as its keys'
- * values and interpolated linearly, with a warning.  Without the flag every mesh is unskinned, as it always has been. */
+ * nxh_loaded_skin reports a mesh's.  JOINTS_1 is ignored with a warning, and so are morph targets unless NXH_LOAD_MORPHS is given too; a
+ * CUBICSPLINE sampler is read as its keys' values and interpolated linearly, with a warning.  Without the flag every mesh is unskinned,
+ * as it always has been. */
 #define NXH_LOAD_SKINS 4u
+/* NXH_LOAD_MORPHS: a .glb's morph targets (POSITION and NORMAL, float VEC3, sparse accessors included, de-indexed like the positions) are
+ * read as well, with the node tree and the animations — their `weights` channels kept —; nxh_loaded_morph reports a mesh's.  All primitives
+ * of a mesh must have the same number of targets.  Without the flag no mesh has targets, as it always has been. */
+#define NXH_LOAD_MORPHS 8u
 int nxh_load_scene_file_ex(const char *file, uint32_t flags, nxh_loaded_scene **out);
 void nxh_loaded_scene_free(nxh_loaded_scene *s);
 uint32_t nxh_loaded_mesh_count(const nxh_loaded_scene *s);
@@ -112,6 +117,10 @@ int nxh_loaded_material_alpha(const nxh_loaded_scene *s, nx_material_alpha *dst,
 /* The skin of loaded mesh `mesh` (NXH_LOAD_SKINS): *cornerCount = 3 x its triangles — 0 for a mesh without one — and *jointCount; dst (may
  * be NULL) receives up to `capacity` nx_skin_corner records (nexus_pod.h), corner 3 i + v = vertex v of triangle i. */
 int nxh_loaded_skin(const nxh_loaded_scene *s, uint32_t mesh, nx_skin_corner *dst, uint32_t capacity, uint32_t *cornerCount, uint32_t *jointCount);
+/* The morph targets of loaded mesh `mesh` (NXH_LOAD_MORPHS): *targetCount — 0 for a mesh without any — and *cornerCount = 3 x its triangles;
+ * dst (may be NULL) receives up to `capacity` nx_morph_corner records (nexus_pod.h), target-major: record t x cornerCount + 3 i + v = vertex v
+ * of triangle i under target t; defaultWeights (may be NULL) receives *targetCount floats: the placing node's weights, else the mesh's, else 0. */
+int nxh_loaded_morph(const nxh_loaded_scene *s, uint32_t mesh, nx_morph_corner *dst, uint32_t capacity, uint32_t *cornerCount, uint32_t *targetCount, float *defaultWeights);
 uint32_t nxh_loaded_animation_count(const nxh_loaded_scene *s);
 uint32_t nxh_loaded_warning_count(const nxh_loaded_scene *s);
 const char *nxh_loaded_warning(const nxh_loaded_scene *s, uint32_t index);
@@ -170,6 +179,14 @@ uint32_t nxs_scene_mesh_count(const nxs_scene *s);
 uint32_t nxs_scene_animation_count(const nxs_scene *s);
 uint32_t nxs_scene_mesh_joint_count(const nxs_scene *s, uint32_t meshId);
 int nxs_scene_joint_palette(const nxs_scene *s, uint32_t meshId, int32_t animationIdx, double t, float *dst, uint32_t capacity, uint32_t *jointCount);
+/* Extension (morph targets), off by default: files loaded from here on keep their morph targets, node tree and animations as
+ * NXH_LOAD_MORPHS reads them (Scene::SetMorphs).  nxs_scene_mesh_target_count: targets of mesh `meshId`, 0 for a mesh without any.
+ * nxs_scene_morph_weights — Scene::MorphWeights: the file's default weights, or the weights channel of animation `animationIdx` (-1: the
+ * defaults) on the mesh's node at time t, evaluated in binary64 and rounded once: *targetCount floats into dst (capacity in floats) — what
+ * nxhip_pose_blas_morph and nxs_pathtracer_pose_mesh_morph take. */
+int nxs_scene_set_morphs(nxs_scene *s, int on);
+uint32_t nxs_scene_mesh_target_count(const nxs_scene *s, uint32_t meshId);
+int nxs_scene_morph_weights(const nxs_scene *s, uint32_t meshId, int32_t animationIdx, double t, float *dst, uint32_t capacity, uint32_t *targetCount);
 int nxs_scene_set_camera(nxs_scene *s, const float pos[3], const float forward[3], float horizontalFovDeg, float focusDist,
                          float defocusAngleDeg);
 int nxs_scene_set_render_settings(nxs_scene *s, const nx_render_settings *settings);
@@ -229,6 +246,10 @@ int nxs_pathtracer_set_device_blas_build(nxs_pathtracer *p, nxs_scene *s, int en
  * the device on first use, the device blends the vertices and refits the mesh's BLAS (nxhip_pose_blas), the posed root box comes back
  * for the instances' bounds; nxs_scene_update and nxs_pathtracer_update_device_scene then proceed as for a deformed mesh. */
 int nxs_pathtracer_pose_mesh(nxs_pathtracer *p, nxs_scene *s, uint32_t meshId, const float *palette, uint32_t jointCount);
+/* Extension (morph targets) — the PathTracer::PoseMesh overload that takes weights, for mesh `meshId`: one weight per target and, where
+ * the mesh is skinned too, its palette (NULL and 0 for an unskinned mesh).  Morph and skin go to the device on first use; the device adds
+ * the active targets' deltas, blends the joints and refits the BLAS in one pass (nxhip_pose_blas_morph).  Made before nxs_scene_update. */
+int nxs_pathtracer_pose_mesh_morph(nxs_pathtracer *p, nxs_scene *s, uint32_t meshId, const float *weights, uint32_t targetCount, const float *palette, uint32_t jointCount);
 int nxs_pathtracer_update_device_scene(nxs_pathtracer *p, nxs_scene *s);
 int nxs_pathtracer_render(nxs_pathtracer *p, nxs_scene *s);
 int nxs_pathtracer_reset_frame_number(nxs_pathtracer *p);

@@ -139,6 +139,14 @@ typedef struct nx_skin_corner {
 } nx_skin_corner;
 NX_STATIC_ASSERT(sizeof(nx_skin_corner) == 24 && offsetof(nx_skin_corner, weight) == 8, "nx_skin_corner must be 24 bytes");
 
+/* Extension: the deltas of one triangle corner under one morph target (nxhip_set_blas_morph; the rule is stated in full in include/nexus_hip.h):
+ * glTF's target POSITION and NORMAL of the corner's vertex (a target without NORMAL: zeros).  Corner 3 i + v is vertex v of triangle i. */
+typedef struct nx_morph_corner {
+    float dPosition[3];
+    float dNormal[3];
+} nx_morph_corner;
+NX_STATIC_ASSERT(sizeof(nx_morph_corner) == 24 && offsetof(nx_morph_corner, dNormal) == 12, "nx_morph_corner must be 24 bytes");
+
 /* Extension: one homogeneous participating medium ("fog") per context, confined to a world-space axis-aligned box (nxhip_set_medium; the
  * rule is stated in full in include/nexus_hip.h). */
 typedef struct nx_medium {

@@ -53,6 +53,8 @@ def node_world_matrices(scene, animation=None, t=0.0):
     trs = [dict(translation=n["translation"], rotation=n["rotation"], scale=n["scale"]) for n in scene.nodes]
     animated = set()
     for ch in (animation["channels"] if animation is not None else []):
+        if ch["path"] == "weights":
+            continue  # (morph_weights)
         trs[ch["node"]][ch["path"]] = sample_channel(ch, float(t))
         animated.add(ch["node"])
     world = [None] * len(scene.nodes)
@@ -87,3 +89,20 @@ def joint_palette(scene, skin, animation=None, t=0.0):
     to_mesh = np.linalg.inv(world[skin["mesh_node"]])
     rows = [(to_mesh @ world[j] @ skin["inverse_bind"][k])[:3, :].reshape(12) for k, j in enumerate(skin["joints"])]
     return np.array(rows, np.float64).astype(np.float32)
+
+
+def morph_weights(scene, morph, animation=None, t=0.0):
+    """(targets,) float32 for Context.pose_blas_morph: the morph's default weights, or — where `animation` has a `weights` channel on the node
+    that places the mesh — that channel at t by sample_channel's rule, evaluated in binary64 and rounded once.  morph: an index into
+    scene.morphs or one of its entries; animation: an index into scene.animations, one of its entries, or None = the defaults."""
+    if not isinstance(morph, dict):
+        morph = scene.morphs[int(morph)]
+    if animation is not None and not isinstance(animation, dict):
+        animation = scene.animations[int(animation)]
+    for ch in (animation["channels"] if animation is not None else []):
+        if ch["path"] == "weights" and ch["node"] == morph["mesh_node"]:
+            w = sample_channel(ch, float(t))
+            if len(w) != len(morph["weights"]):
+                raise ValueError("the weights channel has %d values per key and the mesh %d targets" % (len(w), len(morph["weights"])))
+            return np.asarray(w, np.float64).astype(np.float32)
+    return np.array(morph["weights"], np.float32)

@@ -60,7 +60,7 @@ def abi_words():
         pod.MAT_DT.itemsize, off(pod.MAT_DT, "emissive"), off(pod.MAT_DT, "type"), pod.LIGHT_DT.itemsize, off(pod.LIGHT_DT, "type"),
         pod.ALIGHT_DT.itemsize, off(pod.ALIGHT_DT, "direction"), off(pod.ALIGHT_DT, "colour"), off(pod.ALIGHT_DT, "innerConeAngle"), off(pod.ALIGHT_DT, "type"),
         pod.DETAIL_DT.itemsize, off(pod.DETAIL_DT, "normalScale"), pod.MEDIUM_DT.itemsize, pod.ALPHA_DT.itemsize, off(pod.ALPHA_DT, "cutoff"),
-        pod.SKIN_CORNER_DT.itemsize, off(pod.SKIN_CORNER_DT, "weight"),
+        pod.SKIN_CORNER_DT.itemsize, off(pod.SKIN_CORNER_DT, "weight"), pod.MORPH_CORNER_DT.itemsize, off(pod.MORPH_CORNER_DT, "dNormal"),
         pod.CAM_DT.itemsize, off(pod.CAM_DT, "resolution"), pod.SETTINGS_DT.itemsize, off(pod.SETTINGS_DT, "backgroundColor"),
         pod.RAY_DT.itemsize, pod.HIT_DT.itemsize, pod.BSDF_QUERY_DT.itemsize, pod.BSDF_RESULT_DT.itemsize, off(pod.BSDF_RESULT_DT, "rngOut"),
         C.sizeof(QueueSizes), C.sizeof(TraceStats), TraceStats.cycles.offset, C.sizeof(KernelTimes), len(KERNEL_CLASSES),
@@ -331,6 +331,36 @@ def load_scene_skins(path, skins=True):
     finally:
         L.nxh_loaded_scene_free(h)
     return corners, joints, animations, warnings
+
+
+LOAD_MORPHS = 8  # nxh_load_scene_file_ex: NXH_LOAD_MORPHS
+
+
+def load_scene_morphs(path, skins=False, morphs=True):
+    """the morph targets of a .glb as the C++ reader makes them (LoadOptions::morphs, with LoadOptions::skins beside it if asked): per loaded
+    mesh its (targets, 3 n) pod.MORPH_CORNER_DT records (None: no targets) and default weights, then the animation count and the reader's
+    warnings -> (delta arrays, weight arrays, animations, warnings)"""
+    L = lib()
+    h = C.c_void_p()
+    if L.nxh_load_scene_file_ex(str(path).encode(), (LOAD_MORPHS if morphs else 0) | (LOAD_SKINS if skins else 0), C.byref(h)) != 0:
+        raise NexusError("nxh_load_scene_file_ex: " + L.nxs_last_error().decode())
+    try:
+        deltas, weights = [], []
+        for m in range(L.nxh_loaded_mesh_count(h)):
+            n, t = C.c_uint32(0), C.c_uint32(0)
+            if L.nxh_loaded_morph(h, m, None, 0, C.byref(n), C.byref(t), None) != 0:
+                raise NexusError(L.nxs_last_error().decode())
+            out = np.zeros((t.value, n.value), dtype=pod.MORPH_CORNER_DT) if t.value else None
+            w = np.zeros(t.value, np.float32) if t.value else None
+            if t.value and L.nxh_loaded_morph(h, m, _ptr(out), out.size, C.byref(n), C.byref(t), _ptr(w)) != 0:
+                raise NexusError(L.nxs_last_error().decode())
+            deltas.append(out)
+            weights.append(w)
+        warnings = [L.nxh_loaded_warning(h, i).decode() for i in range(L.nxh_loaded_warning_count(h))]
+        animations = int(L.nxh_loaded_animation_count(h))
+    finally:
+        L.nxh_loaded_scene_free(h)
+    return deltas, weights, animations, warnings
 
 
 def load_scene_analytic_lights(path):
@@ -770,6 +800,27 @@ class Context:
             return
         s = np.ascontiguousarray(corners, dtype=pod.SKIN_CORNER_DT)
         check(self.L.nxhip_set_blas_skin(self.h, int(blas_id), _ptr(s), len(s), int(joint_count)), "nxhip_set_blas_skin")
+
+    def set_blas_morph(self, blas_id, deltas):
+        """the morph targets of a BLAS: (T, 3 n) nx_morph_corner records (pod.make_morph_corners), target-major; None removes them.  The
+        bind copy is shared with the skin (include/nexus_hip.h: whichever is set first takes it)"""
+        if deltas is None:
+            check(self.L.nxhip_set_blas_morph(self.h, int(blas_id), None, 0, 0), "nxhip_set_blas_morph")
+            return
+        d = np.ascontiguousarray(deltas, dtype=pod.MORPH_CORNER_DT)
+        if d.ndim != 2:
+            raise ValueError("morph deltas must be (targets, 3 x triangles) records")
+        check(self.L.nxhip_set_blas_morph(self.h, int(blas_id), _ptr(d), d.shape[1], d.shape[0]), "nxhip_set_blas_morph")
+
+    def pose_blas_morph(self, blas_id, weights, palette=None):
+        """pose a morphed BLAS: one weight per target, and on a skinned BLAS the (jointCount, 12) palette of pose_blas; deltas first, then
+        joints, in one pass, and the refit behind it.  Weights do not persist."""
+        w = np.ascontiguousarray(weights, dtype=np.float32).reshape(-1)
+        if palette is None:
+            check(self.L.nxhip_pose_blas_morph(self.h, int(blas_id), _ptr(w), len(w), None, 0), "nxhip_pose_blas_morph")
+            return
+        m = np.ascontiguousarray(palette, dtype=np.float32).reshape(-1, 12)
+        check(self.L.nxhip_pose_blas_morph(self.h, int(blas_id), _ptr(w), len(w), _ptr(m), len(m)), "nxhip_pose_blas_morph")
 
     def pose_blas(self, blas_id, joint_matrices):
         """pose a skinned BLAS: (jointCount, 12) row-major 3 x 4 object-space matrices; triangles, intersection stream and nodes are
@@ -1463,6 +1514,24 @@ class Scene:
         """Scene::SetSkins: the files loaded from here on keep their glTF skins, joint animations and node tree (off by default)"""
         _scheck(self.L.nxs_scene_set_skins(self.h, 1 if on else 0), "nxs_scene_set_skins")
 
+    def set_morphs(self, on=True):
+        """Scene::SetMorphs: the files loaded from here on keep their glTF morph targets and weights animations (off by default)"""
+        _scheck(self.L.nxs_scene_set_morphs(self.h, 1 if on else 0), "nxs_scene_set_morphs")
+
+    def mesh_target_count(self, mesh_id):
+        """morph targets of the mesh; 0: it has none"""
+        return int(self.L.nxs_scene_mesh_target_count(self.h, int(mesh_id)))
+
+    def morph_weights(self, mesh_id, animation=None, t=0.0):
+        """Scene::MorphWeights: (targets,) float32 — the file's defaults, or the weights channel of animation `animation` at time t; the twin of
+        nexus_amd.animation.morph_weights"""
+        n = C.c_uint32(0)
+        a = -1 if animation is None else int(animation)
+        _scheck(self.L.nxs_scene_morph_weights(self.h, int(mesh_id), a, float(t), None, 0, C.byref(n)), "nxs_scene_morph_weights")
+        out = np.zeros(n.value, np.float32)
+        _scheck(self.L.nxs_scene_morph_weights(self.h, int(mesh_id), a, float(t), _ptr(out), n.value, C.byref(n)), "nxs_scene_morph_weights")
+        return out
+
     def mesh_count(self):
         return int(self.L.nxs_scene_mesh_count(self.h))
 
@@ -1754,6 +1823,14 @@ class PathTracer:
         """PathTracer::PoseMesh: pose a skinned mesh on the device with a (joints, 12) palette — before scene.update()"""
         m = np.ascontiguousarray(palette, dtype=np.float32).reshape(-1, 12)
         _scheck(self.L.nxs_pathtracer_pose_mesh(self.h, scene.h, int(mesh_id), _ptr(m), len(m)), "nxs_pathtracer_pose_mesh")
+
+    def pose_mesh_morph(self, scene, mesh_id, weights, palette=None):
+        """the PathTracer::PoseMesh overload that takes weights: one per morph target, and the (joints, 12) palette where the mesh is skinned —
+        before scene.update()"""
+        w = np.ascontiguousarray(weights, dtype=np.float32).reshape(-1)
+        m = None if palette is None else np.ascontiguousarray(palette, dtype=np.float32).reshape(-1, 12)
+        _scheck(self.L.nxs_pathtracer_pose_mesh_morph(self.h, scene.h, int(mesh_id), _ptr(w), len(w), None if m is None else _ptr(m), 0 if m is None else len(m)),
+                "nxs_pathtracer_pose_mesh_morph")
 
     def update_device_scene(self, scene):
         _scheck(self.L.nxs_pathtracer_update_device_scene(self.h, scene.h), "nxs_pathtracer_update_device_scene")

@@ -137,12 +137,13 @@ int nxh_load_scene_file_ex(const char* file, uint32_t flags, nxh_loaded_scene** 
 {
     return guarded([&] {
         if (!file || !out) throw std::runtime_error("nxh_load_scene_file_ex: null argument");
-        if (flags & ~(uint32_t)(NXH_LOAD_METAL_ROUGH | NXH_LOAD_ALPHA_MODES | NXH_LOAD_SKINS)) throw std::runtime_error("nxh_load_scene_file_ex: unknown flag");
+        if (flags & ~(uint32_t)(NXH_LOAD_METAL_ROUGH | NXH_LOAD_ALPHA_MODES | NXH_LOAD_SKINS | NXH_LOAD_MORPHS)) throw std::runtime_error("nxh_load_scene_file_ex: unknown flag");
         std::unique_ptr<nxh_loaded_scene> p(new nxh_loaded_scene);
         LoadOptions options;
         options.metalRough = (flags & NXH_LOAD_METAL_ROUGH) != 0;
         options.alphaModes = (flags & NXH_LOAD_ALPHA_MODES) != 0;
         options.skins = (flags & NXH_LOAD_SKINS) != 0;
+        options.morphs = (flags & NXH_LOAD_MORPHS) != 0;
         p->ls = OBJLoader::Parse(file, options);
         *out = p.release();
     });
@@ -269,6 +270,17 @@ int nxh_loaded_skin(const nxh_loaded_scene* s, uint32_t mesh, nx_skin_corner* ds
         for (size_t i = 0; skin && dst && i < skin->corners.size() && i < capacity; i++) dst[i] = skin->corners[i];
     });
 }
+int nxh_loaded_morph(const nxh_loaded_scene* s, uint32_t mesh, nx_morph_corner* dst, uint32_t capacity, uint32_t* cornerCount, uint32_t* targetCount, float* defaultWeights)
+{
+    return guarded([&] {
+        if (!s || !cornerCount || !targetCount || mesh >= s->ls.meshes.size()) throw std::runtime_error("nxh_loaded_morph: null argument, or no such mesh");
+        const Morph* morph = mesh < s->ls.morphs.size() ? s->ls.morphs[mesh].get() : nullptr;
+        *targetCount = morph ? morph->targets : 0u;
+        *cornerCount = morph ? static_cast<uint32_t>(morph->deltas.size() / morph->targets) : 0u;
+        for (size_t i = 0; morph && dst && i < morph->deltas.size() && i < capacity; i++) dst[i] = morph->deltas[i];
+        for (size_t i = 0; morph && defaultWeights && i < morph->weights.size(); i++) defaultWeights[i] = morph->weights[i];
+    });
+}
 uint32_t nxh_loaded_animation_count(const nxh_loaded_scene* s) { return static_cast<uint32_t>(s->ls.animations.size()); }
 uint32_t nxh_loaded_warning_count(const nxh_loaded_scene* s) { return static_cast<uint32_t>(s->ls.warnings.size()); }
 const char* nxh_loaded_warning(const nxh_loaded_scene* s, uint32_t index) { return index < s->ls.warnings.size() ? s->ls.warnings[index].c_str() : ""; }
@@ -381,6 +393,28 @@ int nxs_scene_joint_palette(const nxs_scene* s, uint32_t meshId, int32_t animati
         if (dst) {
             if (capacity < *jointCount) throw std::runtime_error("nxs_scene_joint_palette: destination too small");
             std::memcpy(dst, p.data(), p.size() * sizeof(float));
+        }
+    });
+}
+
+int nxs_scene_set_morphs(nxs_scene* s, int on)
+{
+    return guarded([&] { s->scene.SetMorphs(on != 0); });
+}
+uint32_t nxs_scene_mesh_target_count(const nxs_scene* s, uint32_t meshId)
+{
+    const std::vector<Mesh>& meshes = const_cast<nxs_scene*>(s)->scene.GetAssetManager().GetMeshes();
+    return meshId < meshes.size() && meshes[meshId].morph ? meshes[meshId].morph->targets : 0u;
+}
+int nxs_scene_morph_weights(const nxs_scene* s, uint32_t meshId, int32_t animationIdx, double t, float* dst, uint32_t capacity, uint32_t* targetCount)
+{
+    return guarded([&] {
+        if (!s || !targetCount) throw std::runtime_error("nxs_scene_morph_weights: null argument");
+        const std::vector<float> w = s->scene.MorphWeights(meshId, animationIdx, t);
+        *targetCount = static_cast<uint32_t>(w.size());
+        if (dst) {
+            if (capacity < w.size()) throw std::runtime_error("nxs_scene_morph_weights: destination too small");
+            std::memcpy(dst, w.data(), w.size() * sizeof(float));
         }
     });
 }
@@ -535,6 +569,16 @@ int nxs_pathtracer_pose_mesh(nxs_pathtracer* p, nxs_scene* s, uint32_t meshId, c
         const std::vector<Mesh>& meshes = s->scene.GetAssetManager().GetMeshes();
         if (meshId >= meshes.size()) throw std::runtime_error("nxs_pathtracer_pose_mesh: no such mesh");
         p->pt.PoseMesh(s->scene, meshes[meshId].bvhId, std::vector<float>(palette, palette + static_cast<size_t>(jointCount) * 12));
+    });
+}
+int nxs_pathtracer_pose_mesh_morph(nxs_pathtracer* p, nxs_scene* s, uint32_t meshId, const float* weights, uint32_t targetCount, const float* palette, uint32_t jointCount)
+{
+    return guarded([&] {
+        if (!p || !s || !weights || (!palette && jointCount)) throw std::runtime_error("nxs_pathtracer_pose_mesh_morph: null argument");
+        const std::vector<Mesh>& meshes = s->scene.GetAssetManager().GetMeshes();
+        if (meshId >= meshes.size()) throw std::runtime_error("nxs_pathtracer_pose_mesh_morph: no such mesh");
+        p->pt.PoseMesh(s->scene, meshes[meshId].bvhId, std::vector<float>(weights, weights + targetCount),
+                       palette ? std::vector<float>(palette, palette + static_cast<size_t>(jointCount) * 12) : std::vector<float>());
     });
 }
 int nxs_pathtracer_update_device_scene(nxs_pathtracer* p, nxs_scene* s)

@@ -72,8 +72,13 @@ struct BlasHost {
     bool refreshPending = false;        // updated since the last refresh_updated_blas: its instances and the TLAS still hold the old root
     // the skin of nxhip_set_blas_skin (nx_skin.hip pose_kernel): the triangles as they were when the skin was set, one SkinTri per
     // triangle, and the palette of the last nxhip_pose_blas (48 bytes per joint); skinJoints == 0: no skin
+    // bindTris is shared with the morph below: whichever of the two is set on a BLAS that has neither takes the copy, the last to go frees it
     DevBuf bindTris, skinTris, palette;
     uint32_t skinJoints = 0;
+    // the morph of nxhip_set_blas_morph: one MorphTri per (target, triangle), target-major, and the active (index, weight) pairs of the
+    // last nxhip_pose_blas_morph (8 bytes per target); morphTargets == 0: no morph
+    DevBuf morphTris, morphActive;
+    uint32_t morphTargets = 0;
 };
 
 struct TextureHost {

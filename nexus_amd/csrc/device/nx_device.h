@@ -86,6 +86,16 @@ struct __attribute__((aligned(16))) SkinTri {
 };
 static_assert(sizeof(SkinTri) == 80 && offsetof(SkinTri, joint) == 48, "SkinTri layout");
 constexpr uint32_t kSkinLdsJoints = 1024;  // palettes up to this many joints (48 KiB) are staged in the LDS
+// The deltas of one triangle under one morph target as the pose kernel reads them (nx_skin.hip): the three nx_morph_corner records of
+// nxhip_set_blas_morph repacked by the host in the order of nx_triangle's first 18 words — the three position deltas, then the three normal
+// deltas — and padded to five 16-byte chunks, for the reason SkinTri has them.  Record t * triCount + i: triangle i under target t.
+struct __attribute__((aligned(16))) MorphTri {
+    float dPosition[3][3];
+    float dNormal[3][3];
+    uint32_t pad_[2];
+};
+static_assert(sizeof(MorphTri) == 80 && offsetof(MorphTri, dNormal) == 36, "MorphTri layout");
+constexpr uint32_t kMorphMaxTargets = 1024;  // targets of one BLAS at the most: the active list (8 bytes per target) stays within 8 KiB
 inline __device__ const NX_G nx_triangle* shade_tri(const NX_G nx_triangle* tris, uint32_t k) { return (const NX_G nx_triangle*)((const NX_G char*)tris + (size_t)k * (size_t)kShadeTriStride); }
 
 // Traversal record of one TLAS leaf, stored in TLAS *leaf order* (entry k belongs to tlasInstIdx[k]) so that entering an
@@ -611,6 +621,7 @@ constexpr uint64_t layout_stamp()
         (uint64_t)kEnvGuide, (uint64_t)kHitCodeShift, sizeof(TraceRays), offsetof(TraceQueue, hit), (uint64_t)kMaterialTypeOffset, sizeof(nx_material), sizeof(nx_bvh_instance), sizeof(nx_triangle), sizeof(nx_light), sizeof(nx_camera),
         offsetof(RegionCounters, materialSizeMetal), offsetof(RegionCounters, scanTileMetal), offsetof(RegionCounters, scanTicketMetal), offsetof(DeviceState, materialMetal), (uint64_t)kHitCodeMetalRough, (uint64_t)kScanMetalBit,
         sizeof(SkinTri), offsetof(SkinTri, joint), (uint64_t)kSkinLdsJoints,
+        sizeof(MorphTri), offsetof(MorphTri, dNormal), (uint64_t)kMorphMaxTargets,
         offsetof(DeviceState, lightTree), offsetof(DeviceState, lightSlotOf), offsetof(DeviceState, lightTreeLeaves), sizeof(LightNode), offsetof(LightNode, hi), sizeof(LightTreeBuild),
         offsetof(LightTreeBuild, entries),
     };

@@ -67,6 +67,7 @@ const void* instance_transform_kernel_ptr();
 const void* tlas_refit_kernel_ptr();
 const void* blas_refit_kernel_ptr();
 const void* pose_kernel_ptr(bool lds);  // nx_skin.hip: the palette from the LDS, or from global memory
+const void* pose_morph_kernel_ptr(bool skin, bool lds);  // ... with the morph stage in front; skin off: morph only
 uint64_t layout_stamp_trace();
 uint64_t layout_stamp_wavefront();
 uint64_t layout_stamp_wavefront_detail();
@@ -208,6 +209,11 @@ inline Kernel<nx_bvh8_node*, const U32*, const nx_bvh_instance*, const U32*, con
 inline Kernel<uint4*, const U32*, const nx_triangle*, const U32*, const U32*, U32, U32, void*> blas_refit() { return {blas_refit_kernel_ptr()}; }
 // (bind, skin, palette, jointCount, primIdx, n, tris, shadeTris, isect); lds: launched with 48 B of dynamic LDS per joint
 inline Kernel<const uint4*, const uint4*, const float4*, U32, const U32*, U32, uint4*, uint4*, float4*> pose(bool lds) { return {pose_kernel_ptr(lds)}; }
+// (the list of pose, then: morph, active, activeCount); skin off: skin and palette are not read
+inline Kernel<const uint4*, const uint4*, const float4*, U32, const U32*, U32, uint4*, uint4*, float4*, const uint4*, const uint2*, U32> pose_morph(bool skin, bool lds)
+{
+    return {pose_morph_kernel_ptr(skin, lds)};
+}
 }  // namespace kernels
 
 constexpr size_t arg_end(size_t at, size_t size, size_t align) { return (at + align - 1) / align * align + size; }

@@ -887,7 +887,10 @@ try {
     return update_blas(c, blasId, trisDevice, triCount, true, "nxhip_update_blas_device");
 } NX_CATCH("nxhip_update_blas_device")
 
-// ---- skinned meshes (nx_skin.hip) ------------------------------------------------------------------------
+// ---- skinned meshes and morph targets (nx_skin.hip) ------------------------------------------------------
+// The bind copy (BlasHost::bindTris) belongs to the skin and the morph together: the one that is set on a BLAS with neither takes it from
+// the current triangles (and so does a skin set again on a BLAS that has only a skin, a morph on one that has only a morph); the one that
+// finds the other present keeps it, so that both describe one shape; the last of the two to go frees it.
 
 int nxhip_set_blas_skin(nxhip_ctx* c, int32_t blasId, const nx_skin_corner* corners, uint32_t cornerCount, uint32_t jointCount)
 try {
@@ -897,7 +900,7 @@ try {
     NX_HIP(hipSetDevice(c->device));
     if (!corners) {  // the skin goes; triangles and nodes stay as they are
         NX_SYNC_ALL(c);  // (a pose in flight still reads the buffers)
-        b.bindTris.release();
+        if (b.morphTargets == 0) b.bindTris.release();
         b.skinTris.release();
         b.palette.release();
         b.skinJoints = 0;
@@ -924,18 +927,59 @@ try {
         }
     }
     DevBuf bind, skin, palette;
+    const bool takeBind = b.morphTargets == 0;  // (a morph is there: its deltas are relative to the copy it holds)
     const size_t triBytes = (size_t)b.triCount * sizeof(nx_triangle), skinBytes = packed.size() * sizeof(SkinTri);
-    if (!bind.alloc(triBytes) || !skin.alloc(skinBytes) || !palette.alloc((size_t)jointCount * 48)) return NXHIP_ERR_HIP;
+    if ((takeBind && !bind.alloc(triBytes)) || !skin.alloc(skinBytes) || !palette.alloc((size_t)jointCount * 48)) return NXHIP_ERR_HIP;
     // the bind copy: the triangles as they are behind everything issued so far (an update or a pose on the stream included)
-    NX_HIP(hipMemcpyAsync(bind.p, b.tris.p, triBytes, hipMemcpyDeviceToDevice, c->stream));
+    if (takeBind) NX_HIP(hipMemcpyAsync(bind.p, b.tris.p, triBytes, hipMemcpyDeviceToDevice, c->stream));
     NX_HIP(hipMemcpyAsync(skin.p, packed.data(), skinBytes, hipMemcpyHostToDevice, c->stream));
     NX_HIP(hipStreamSynchronize(c->stream));  // (`packed` is pageable; and a previous skin's buffers are read by this stream only)
-    b.bindTris = std::move(bind);
+    if (takeBind) b.bindTris = std::move(bind);
     b.skinTris = std::move(skin);
     b.palette = std::move(palette);
     b.skinJoints = jointCount;
     return NXHIP_OK;
 } NX_CATCH("nxhip_set_blas_skin")
+
+// What both pose calls issue behind their checks, in stream order as in update_blas: the palette (skinned: jointMatrices) and the active
+// targets (morph: `active`, (index, weight) pairs), ONE pose kernel, the refit, and the wait for the pageable arrays.  A skinned pose with no
+// active target is nxhip_pose_blas's kernel whoever asks: "the pose with all weights 0" has its bits by construction.
+static int issue_pose(nxhip_ctx* c, BlasHost& b, const float* jointMatrices, const std::vector<uint2>* active)
+{
+    NX_HIP(hipSetDevice(c->device));
+    NX_TRY(ensure_blas_refit_plan(c, b));
+    if (slot_count(c) > 1) NX_SYNC_ALL(c);  // passes on the other slots' streams still traverse the old shape
+    const bool skinned = jointMatrices != nullptr;
+    const uint32_t jointCount = skinned ? b.skinJoints : 0u, activeCount = active ? (uint32_t)active->size() : 0u;
+    if (skinned) NX_HIP(hipMemcpyAsync(b.palette.p, jointMatrices, (size_t)jointCount * 48, hipMemcpyHostToDevice, c->stream));
+    if (activeCount) NX_HIP(hipMemcpyAsync(b.morphActive.p, active->data(), (size_t)activeCount * 8, hipMemcpyHostToDevice, c->stream));
+    const bool lds = skinned && jointCount <= kSkinLdsJoints;
+    constexpr unsigned kPoseBlock = 256;
+    const unsigned grid = std::min<unsigned>((b.triCount + kPoseBlock - 1u) / kPoseBlock, (unsigned)(8 * std::max(1, c->numCUs)));
+    uint4* const shade = kShadeTriStride == (int)sizeof(nx_triangle) ? nullptr : b.shadeTris.as<uint4>();
+    const size_t ldsBytes = lds ? (size_t)jointCount * 48 : 0;
+    if (skinned && activeCount == 0) {
+        NX_HIP(launch_untimed_lds(kernels::pose(lds), grid, kPoseBlock, ldsBytes, c->stream, b.bindTris.as<uint4>(), b.skinTris.as<uint4>(), b.palette.as<float4>(), jointCount,
+                                  b.triIdx.as<uint32_t>(), b.triCount, b.tris.as<uint4>(), shade, b.isect.as<float4>()));
+    } else {  // (unskinned with no active target: the morph-only instance skips its stage and writes the bind copy back)
+        NX_HIP(launch_untimed_lds(kernels::pose_morph(skinned, lds), grid, kPoseBlock, ldsBytes, c->stream, b.bindTris.as<uint4>(), b.skinTris.as<uint4>(), b.palette.as<float4>(),
+                                  jointCount, b.triIdx.as<uint32_t>(), b.triCount, b.tris.as<uint4>(), shade, b.isect.as<float4>(), b.morphTris.as<uint4>(),
+                                  b.morphActive.as<uint2>(), activeCount));
+    }
+    NX_TRY(refit_blas_nodes(c, b));
+    NX_HIP(hipStreamSynchronize(c->stream));  // pageable host arrays: see nxhip_set_instance_transforms
+    return NXHIP_OK;
+}
+
+// the joint matrices of a pose of skinned BLAS b, as both pose calls check them
+static int check_palette(const BlasHost& b, const float* jointMatrices, uint32_t jointCount, const std::string& who)
+{
+    if (!jointMatrices) return fail_invalid(who + ": null matrices");
+    if (jointCount != b.skinJoints) return fail_invalid(who + ": the joint count differs from the skin's");
+    for (size_t i = 0; i < (size_t)jointCount * 12; i++)
+        if (!std::isfinite(jointMatrices[i])) return fail_invalid(who + ": a matrix entry is not finite");
+    return NXHIP_OK;
+}
 
 int nxhip_pose_blas(nxhip_ctx* c, int32_t blasId, const float* jointMatrices, uint32_t jointCount)
 try {
@@ -943,25 +987,76 @@ try {
     if (blasId < 0 || (size_t)blasId >= c->blas.size()) return fail_invalid("nxhip_pose_blas: no such BLAS");
     BlasHost& b = c->blas[(size_t)blasId];
     if (b.skinJoints == 0) return fail_invalid("nxhip_pose_blas: the BLAS has no skin (nxhip_set_blas_skin)");
-    if (!jointMatrices) return fail_invalid("nxhip_pose_blas: null matrices");
-    if (jointCount != b.skinJoints) return fail_invalid("nxhip_pose_blas: the joint count differs from the skin's");
-    for (size_t i = 0; i < (size_t)jointCount * 12; i++)
-        if (!std::isfinite(jointMatrices[i])) return fail_invalid("nxhip_pose_blas: a matrix entry is not finite");
-    NX_HIP(hipSetDevice(c->device));
-    NX_TRY(ensure_blas_refit_plan(c, b));
-    if (slot_count(c) > 1) NX_SYNC_ALL(c);  // passes on the other slots' streams still traverse the old shape
-    // stream order does the rest, as in update_blas: the palette, the pose, the refit
-    NX_HIP(hipMemcpyAsync(b.palette.p, jointMatrices, (size_t)jointCount * 48, hipMemcpyHostToDevice, c->stream));
-    const bool lds = jointCount <= kSkinLdsJoints;
-    constexpr unsigned kPoseBlock = 256;
-    const unsigned grid = std::min<unsigned>((b.triCount + kPoseBlock - 1u) / kPoseBlock, (unsigned)(8 * std::max(1, c->numCUs)));
-    uint4* const shade = kShadeTriStride == (int)sizeof(nx_triangle) ? nullptr : b.shadeTris.as<uint4>();
-    NX_HIP(launch_untimed_lds(kernels::pose(lds), grid, kPoseBlock, lds ? (size_t)jointCount * 48 : 0, c->stream, b.bindTris.as<uint4>(), b.skinTris.as<uint4>(),
-                              b.palette.as<float4>(), jointCount, b.triIdx.as<uint32_t>(), b.triCount, b.tris.as<uint4>(), shade, b.isect.as<float4>()));
-    NX_TRY(refit_blas_nodes(c, b));
-    NX_HIP(hipStreamSynchronize(c->stream));  // a pageable host array: see nxhip_set_instance_transforms
-    return NXHIP_OK;
+    NX_TRY(check_palette(b, jointMatrices, jointCount, "nxhip_pose_blas"));
+    return issue_pose(c, b, jointMatrices, nullptr);
 } NX_CATCH("nxhip_pose_blas")
+
+int nxhip_set_blas_morph(nxhip_ctx* c, int32_t blasId, const nx_morph_corner* deltas, uint32_t cornerCount, uint32_t targetCount)
+try {
+    NX_CHECK_CTX(c);
+    if (blasId < 0 || (size_t)blasId >= c->blas.size()) return fail_invalid("nxhip_set_blas_morph: no such BLAS");
+    BlasHost& b = c->blas[(size_t)blasId];
+    NX_HIP(hipSetDevice(c->device));
+    if (!deltas) {  // the morph goes; triangles and nodes stay as they are
+        NX_SYNC_ALL(c);  // (a pose in flight still reads the buffers)
+        if (b.skinJoints == 0) b.bindTris.release();
+        b.morphTris.release();
+        b.morphActive.release();
+        b.morphTargets = 0;
+        return NXHIP_OK;
+    }
+    if ((uint64_t)cornerCount != 3ull * b.triCount) return fail_invalid("nxhip_set_blas_morph: the corner count is not 3 x the BLAS's triangle count");
+    if (targetCount == 0 || targetCount > kMorphMaxTargets) return fail_invalid("nxhip_set_blas_morph: the target count must be 1 .. " + std::to_string(kMorphMaxTargets));
+    // every delta the kernel will add, before anything is allocated
+    const size_t records = (size_t)targetCount * b.triCount;
+    std::vector<MorphTri> packed(records);
+    std::memset(packed.data(), 0, packed.size() * sizeof(MorphTri));
+    for (size_t i = 0; i < (size_t)targetCount * cornerCount; i++) {
+        const nx_morph_corner& d = deltas[i];
+        for (int a = 0; a < 3; a++)
+            if (!std::isfinite(d.dPosition[a]) || !std::isfinite(d.dNormal[a]))
+                return fail_invalid("nxhip_set_blas_morph: corner " + std::to_string(i % cornerCount) + " of target " + std::to_string(i / cornerCount) + " has a delta that is not finite");
+        MorphTri& t = packed[i / 3];  // (cornerCount = 3 x triCount: record t * triCount + triangle)
+        std::memcpy(t.dPosition[i % 3], d.dPosition, 12);
+        std::memcpy(t.dNormal[i % 3], d.dNormal, 12);
+    }
+    DevBuf bind, morph, active;
+    const bool takeBind = b.skinJoints == 0;  // (a skin is there: it is relative to the copy it holds)
+    const size_t triBytes = (size_t)b.triCount * sizeof(nx_triangle), morphBytes = records * sizeof(MorphTri);
+    if ((takeBind && !bind.alloc(triBytes)) || !morph.alloc(morphBytes) || !active.alloc((size_t)targetCount * 8)) return NXHIP_ERR_HIP;
+    if (takeBind) NX_HIP(hipMemcpyAsync(bind.p, b.tris.p, triBytes, hipMemcpyDeviceToDevice, c->stream));
+    NX_HIP(hipMemcpyAsync(morph.p, packed.data(), morphBytes, hipMemcpyHostToDevice, c->stream));
+    NX_HIP(hipStreamSynchronize(c->stream));  // (`packed` is pageable; and a previous morph's buffers are read by this stream only)
+    if (takeBind) b.bindTris = std::move(bind);
+    b.morphTris = std::move(morph);
+    b.morphActive = std::move(active);
+    b.morphTargets = targetCount;
+    return NXHIP_OK;
+} NX_CATCH("nxhip_set_blas_morph")
+
+int nxhip_pose_blas_morph(nxhip_ctx* c, int32_t blasId, const float* weights, uint32_t targetCount, const float* jointMatrices, uint32_t jointCount)
+try {
+    NX_CHECK_CTX(c);
+    if (blasId < 0 || (size_t)blasId >= c->blas.size()) return fail_invalid("nxhip_pose_blas_morph: no such BLAS");
+    BlasHost& b = c->blas[(size_t)blasId];
+    if (b.morphTargets == 0) return fail_invalid("nxhip_pose_blas_morph: the BLAS has no morph (nxhip_set_blas_morph)");
+    if (!weights) return fail_invalid("nxhip_pose_blas_morph: null weights");
+    if (targetCount != b.morphTargets) return fail_invalid("nxhip_pose_blas_morph: the target count differs from the morph's");
+    const bool skinned = b.skinJoints != 0;
+    if (skinned) NX_TRY(check_palette(b, jointMatrices, jointCount, "nxhip_pose_blas_morph (the BLAS is skinned)"));
+    else if (jointMatrices || jointCount != 0) return fail_invalid("nxhip_pose_blas_morph: the BLAS has no skin: the matrices must be NULL and their count 0");
+    // the active targets: weight not 0, ascending index — the only ones the kernel visits
+    std::vector<uint2> active;
+    for (uint32_t t = 0; t < targetCount; t++) {
+        if (!std::isfinite(weights[t])) return fail_invalid("nxhip_pose_blas_morph: weight " + std::to_string(t) + " is not finite");
+        if (weights[t] != 0.0f) {
+            uint32_t bits;
+            std::memcpy(&bits, &weights[t], 4);
+            active.push_back(make_uint2(t, bits));
+        }
+    }
+    return issue_pose(c, b, skinned ? jointMatrices : nullptr, &active);
+} NX_CATCH("nxhip_pose_blas_morph")
 
 int nxhip_read_blas_triangles(nxhip_ctx* c, int32_t blasId, nx_triangle* out, uint32_t capacity)
 {

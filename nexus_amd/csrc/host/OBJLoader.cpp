@@ -350,7 +350,7 @@ struct Accessor {
 // LoadOptions::skins: the node tree (parents and rest TRS), the skin of every skinned primitive (the corner records are there already:
 // the primitive loop of parse_glb) and the joint animations as channels.  The twin of nexus_amd/loaders.py _read_skins.
 template <class AccessorOf>
-void read_skins(const Json& doc, const AccessorOf& accessor, const std::map<std::pair<size_t, size_t>, std::pair<int, int>>& primMesh, LoadedScene& out)
+void read_skins(const Json& doc, const AccessorOf& accessor, const std::map<std::pair<size_t, size_t>, std::pair<int, int>>& primMesh, LoadedScene& out, const LoadOptions& options)
 {
     const Json& nodes = doc.at("nodes");
     out.nodes.resize(nodes.size());
@@ -381,7 +381,7 @@ void read_skins(const Json& doc, const AccessorOf& accessor, const std::map<std:
         const Json& node = nodes.at(ni);
         const Json* meshRef = node.find("mesh");
         const Json* skinRef = node.find("skin");
-        if (!meshRef || !skinRef) continue;
+        if (!options.skins || !meshRef || !skinRef) continue;
         const Json& skin = doc.at("skins").at(static_cast<size_t>(skinRef->num));
         const Json& joints = skin.at("joints");
         std::vector<int> jointNodes;
@@ -424,11 +424,12 @@ void read_skins(const Json& doc, const AccessorOf& accessor, const std::map<std:
             const Json* target = ch.find("target");
             if (!target || !target->find("node") || !target->find("path")) continue;
             const std::string& path = target->at("path").str;
-            if (path != "translation" && path != "rotation" && path != "scale") continue;  // (weights: morph targets, ignored with the primitive's warning)
+            const bool weights = options.morphs && path == "weights";
+            if (path != "translation" && path != "rotation" && path != "scale" && !weights) continue;  // (weights without LoadOptions::morphs: ignored with the primitive's warning)
             AnimationChannel c;
             c.node = static_cast<int>(target->at("node").num);
             if (c.node < 0 || static_cast<size_t>(c.node) >= nodes.size()) fail("glb: an animation channel names a node that does not exist");
-            c.path = path == "translation" ? AnimationChannel::TRANSLATION : path == "rotation" ? AnimationChannel::ROTATION : AnimationChannel::SCALE;
+            c.path = weights ? AnimationChannel::WEIGHTS : path == "translation" ? AnimationChannel::TRANSLATION : path == "rotation" ? AnimationChannel::ROTATION : AnimationChannel::SCALE;
             const Json& sampler = anim.at("samplers").at(static_cast<size_t>(ch.at("sampler").num));
             const Accessor in = accessor(static_cast<size_t>(sampler.at("input").num)), val = accessor(static_cast<size_t>(sampler.at("output").num));
             const Json* ip = sampler.find("interpolation");
@@ -443,6 +444,21 @@ void read_skins(const Json& doc, const AccessorOf& accessor, const std::map<std:
             } else if (interpolation != "LINEAR") {
                 fail("glb: animation " + std::to_string(ai) + " has an unknown interpolation");
             }
+            if (weights) {  // scalars, (keys, targets) row by row: a CUBICSPLINE key is its three rows of targets
+                const size_t rows = in.count * perKey;
+                if (in.count == 0 || val.ncomp != 1 || val.count == 0 || val.count % rows != 0) fail("glb: animation " + std::to_string(ai) + " has a sampler whose keys and values differ in number");
+                const size_t targets = val.count / rows;
+                const double unit = val.componentType == 5120 ? 127.0 : val.componentType == 5121 ? 255.0 : val.componentType == 5122 ? 32767.0 : val.componentType == 5123 ? 65535.0 : 1.0;
+                for (size_t k = 0; k < in.count; k++) {
+                    c.times.push_back(in.get(k, 0));
+                    for (size_t d = 0; d < targets; d++) {
+                        const double v = val.get((perKey * k + valueAt) * targets + d, 0);
+                        c.values.push_back(unit == 1.0 ? v : std::max(v / unit, -1.0));
+                    }
+                }
+                A.channels.push_back(std::move(c));
+                continue;
+            }
             const int width = c.path == AnimationChannel::ROTATION ? 4 : 3;
             if (in.count == 0 || val.count != in.count * perKey || val.ncomp != width) fail("glb: animation " + std::to_string(ai) + " has a sampler whose keys and values differ in number");
             // (normalised integers: glTF allows them for rotations)
@@ -455,6 +471,37 @@ void read_skins(const Json& doc, const AccessorOf& accessor, const std::map<std:
         }
         out.animations.push_back(std::move(A));
     }
+}
+
+// LoadOptions::morphs: which node places each morphed mesh, and the default weights — the node's, else the mesh's, else zeros.  The twin of
+// nexus_amd/loaders.py _read_morphs.
+void read_morphs(const Json& doc, const std::map<std::pair<size_t, size_t>, std::pair<int, int>>& primMesh, LoadedScene& out)
+{
+    const Json& nodes = doc.at("nodes");
+    for (size_t ni = 0; ni < nodes.size(); ni++) {
+        const Json& node = nodes.at(ni);
+        const Json* meshRef = node.find("mesh");
+        if (!meshRef) continue;
+        const Json& mesh = doc.at("meshes").at(static_cast<size_t>(meshRef->num));
+        for (const auto& kv : primMesh) {
+            if (kv.first.first != static_cast<size_t>(meshRef->num)) continue;
+            Morph* m = out.morphs[static_cast<size_t>(kv.second.first)].get();
+            if (!m || m->meshNode >= 0) continue;  // (no targets; or placed by an earlier node: that one holds)
+            m->meshNode = static_cast<int>(ni);
+            const Json* w = node.find("weights");
+            if (!w) w = mesh.find("weights");
+            if (w) {
+                if (w->size() != m->targets) fail("glb: mesh " + std::to_string(kv.first.first) + " has " + std::to_string(m->targets) + " morph targets and " + std::to_string(w->size()) + " default weights");
+                for (size_t k = 0; k < w->size(); k++) m->weights[k] = static_cast<float>(w->at(k).num);
+            }
+            if (const Json* extras = mesh.find("extras"))
+                if (extras->kind == Json::Object)
+                    if (const Json* names = extras->find("targetNames"))
+                        for (size_t k = 0; k < names->size(); k++) m->names.push_back(names->at(k).str);
+        }
+    }
+    for (std::shared_ptr<Morph>& m : out.morphs)
+        if (m && m->meshNode < 0) m.reset();  // (a mesh no node places: the Python reader lists none either)
 }
 
 LoadedScene parse_glb(const std::string& file, const LoadOptions& options)
@@ -494,7 +541,44 @@ LoadedScene parse_glb(const std::string& file, const LoadOptions& options)
         return acc;
     };
 
+    // a morph target's attribute, 3 floats per vertex: the accessor's bufferView (zeros without one) with its sparse part written over it
+    auto target_values = [&](size_t index, const std::string& what) {
+        const Json& a = doc.at("accessors").at(index);
+        if (static_cast<int>(a.at("componentType").num) != 5126 || a.at("type").str != "VEC3") fail("glb: " + what + ": a morph target attribute must be a float VEC3 accessor");
+        const size_t count = static_cast<size_t>(a.at("count").num);
+        std::vector<float> v(count * 3, 0.0f);
+        if (a.find("bufferView")) {
+            const Accessor acc = accessor(index);
+            for (size_t i = 0; i < count; i++)
+                for (int c = 0; c < 3; c++) v[3 * i + static_cast<size_t>(c)] = static_cast<float>(acc.get(i, c));
+        }
+        if (const Json* sparse = a.find("sparse")) {
+            const size_t n = static_cast<size_t>(sparse->at("count").num);
+            auto part = [&](const Json& ref, int componentType, int ncomp) {
+                const Json& bv = doc.at("bufferViews").at(static_cast<size_t>(ref.at("bufferView").num));
+                Accessor acc;
+                acc.componentType = componentType;
+                acc.ncomp = ncomp;
+                const size_t csize = (componentType == 5120 || componentType == 5121) ? 1 : (componentType == 5122 || componentType == 5123) ? 2 : 4;
+                const size_t start = static_cast<size_t>(bv.number("byteOffset", 0)) + static_cast<size_t>(ref.number("byteOffset", 0));
+                acc.stride = csize * static_cast<size_t>(ncomp);
+                acc.count = n;
+                if (!blob || (n && start + n * acc.stride > blobLen)) fail("glb: a sparse accessor runs past the binary chunk");
+                acc.base = blob + start;
+                return acc;
+            };
+            const Accessor ind = part(sparse->at("indices"), static_cast<int>(sparse->at("indices").at("componentType").num), 1), val = part(sparse->at("values"), 5126, 3);
+            for (size_t k = 0; k < n; k++) {
+                const size_t at = static_cast<size_t>(ind.get(k, 0));
+                if (at >= count) fail("glb: a sparse accessor names an element it does not have");
+                for (int c = 0; c < 3; c++) v[3 * at + static_cast<size_t>(c)] = static_cast<float>(val.get(k, c));
+            }
+        }
+        return v;
+    };
+
     LoadedScene out;
+    std::map<size_t, size_t> meshTargets;  // LoadOptions::morphs: mesh -> the target count of its primitives (all equal)
     // texture index -> decoded image, decoded once however many materials share it
     std::map<std::pair<size_t, int>, int> decoded;  // (glTF texture, kind) -> index into out.textures
     auto load_texture = [&](const Json& texRef, Texture::Type kind) -> int {
@@ -623,7 +707,7 @@ LoadedScene parse_glb(const std::string& file, const LoadOptions& options)
             if (options.skins) {
                 const std::string what = "mesh " + std::to_string(mi) + " primitive " + std::to_string(pi);
                 if (const Json* targets = prim.find("targets"))
-                    if (targets->size() > 0) out.warnings.push_back(what + ": morph targets are ignored");
+                    if (targets->size() > 0 && !options.morphs) out.warnings.push_back(what + ": morph targets are ignored");
                 if (attrs.find("JOINTS_1")) out.warnings.push_back(what + ": more than four influences per vertex (JOINTS_1) are ignored; JOINTS_0 / WEIGHTS_0 are used");
                 std::shared_ptr<Skin> skin;
                 if (attrs.find("JOINTS_0") && attrs.find("WEIGHTS_0")) {
@@ -644,6 +728,37 @@ LoadedScene parse_glb(const std::string& file, const LoadOptions& options)
                     }
                 }
                 out.skins.push_back(std::move(skin));
+            }
+            if (options.morphs) {
+                const std::string what = "mesh " + std::to_string(mi) + " primitive " + std::to_string(pi);
+                const Json* targets = prim.find("targets");
+                const size_t count = targets ? targets->size() : 0;
+                if (!meshTargets.count(mi)) meshTargets[mi] = count;
+                if (meshTargets[mi] != count) fail("glb: mesh " + std::to_string(mi) + " has primitives with different numbers of morph targets");
+                std::shared_ptr<Morph> morph;
+                if (count) {
+                    morph = std::make_shared<Morph>();
+                    morph->targets = static_cast<uint32_t>(count);
+                    morph->weights.assign(count, 0.0f);
+                    const size_t used = corners / 3 * 3;
+                    morph->deltas.assign(count * used, nx_morph_corner{{0, 0, 0}, {0, 0, 0}});
+                    for (size_t t = 0; t < count; t++) {
+                        const Json& tg = targets->at(t);
+                        const std::pair<const char*, int> attrsOf[] = {{"POSITION", 0}, {"NORMAL", 1}};
+                        for (const auto& at : attrsOf) {
+                            const Json* ref = tg.find(at.first);
+                            if (!ref) continue;
+                            const std::vector<float> v = target_values(static_cast<size_t>(ref->num), what);
+                            if (v.size() != pos.count * 3) fail("glb: " + what + " has a morph target that does not fit its vertices");
+                            for (size_t c = 0; c < used; c++) {  // corner 3 i + v = vertex v of triangle i, de-indexed like the positions
+                                const size_t vi = indexed ? static_cast<size_t>(idx.get(c, 0)) : c;
+                                nx_morph_corner& d = morph->deltas[t * used + c];
+                                std::memcpy(at.second == 0 ? d.dPosition : d.dNormal, v.data() + 3 * vi, 12);
+                            }
+                        }
+                    }
+                }
+                out.morphs.push_back(std::move(morph));
             }
             out.meshes.push_back(std::move(tris));
             const Json* name = mesh.find("name");
@@ -725,7 +840,8 @@ LoadedScene parse_glb(const std::string& file, const LoadOptions& options)
     for (size_t k = 0; k < roots.size(); k++) walker.walk(static_cast<size_t>(roots.at(k).num), M4::identity());
     for (const LoadedInstance& inst : out.instances)
         if (inst.material < 0 || static_cast<size_t>(inst.material) >= out.materials.size()) fail("glb: primitive refers to a material that does not exist");
-    if (options.skins) read_skins(doc, accessor, primMesh, out);
+    if (options.skins || options.morphs) read_skins(doc, accessor, primMesh, out, options);
+    if (options.morphs) read_morphs(doc, primMesh, out);
     return out;
 }
 
@@ -887,6 +1003,10 @@ void OBJLoader::LoadOBJ(const std::string& path, const std::string& filename, Sc
             mesh.skin = std::make_shared<Skin>(*ls.skins[i]);
             for (int& j : mesh.skin->joints) j += nodeBase;
             mesh.skin->meshNode += nodeBase;
+        }
+        if (i < ls.morphs.size() && ls.morphs[i]) {
+            mesh.morph = std::make_shared<Morph>(*ls.morphs[i]);
+            mesh.morph->meshNode += nodeBase;
         }
         meshIds.push_back(assetManager->AddMesh(std::move(mesh)));
     }

@@ -162,6 +162,36 @@ void PathTracer::PoseMesh(Scene& scene, int32_t bvhId, const std::vector<float>&
     assets.SetPosedBounds(bvhId, lo, hi);
 }
 
+void PathTracer::PoseMesh(Scene& scene, int32_t bvhId, const std::vector<float>& weights, const std::vector<float>& palette)
+{
+    AssetManager& assets = scene.GetAssetManager();
+    Morph* morph = nullptr;
+    Skin* skin = nullptr;
+    for (Mesh& m : assets.GetMeshes())
+        if (m.bvhId == bvhId && m.morph) {
+            morph = m.morph.get();
+            skin = m.skin.get();
+        }
+    if (bvhId < 0 || static_cast<size_t>(bvhId) >= assets.GetBVHs().size() || !morph) throw std::runtime_error("PathTracer::PoseMesh: no morphed mesh has that BVH");
+    if (weights.size() != morph->targets) throw std::runtime_error("PathTracer::PoseMesh: there is not one weight per morph target");
+    const size_t joints = skin ? skin->joints.size() : 0;
+    if (palette.size() != joints * 12) throw std::runtime_error(skin ? "PathTracer::PoseMesh: the palette does not have 12 floats per joint of the skin" : "PathTracer::PoseMesh: the mesh is not skinned: the palette must be empty");
+    UploadPendingBlas(assets);  // (a mesh posed before its first frame)
+    const int32_t blas = assets.GetBVHs()[static_cast<size_t>(bvhId)].deviceBlasId;
+    if (skin && !skin->onDevice) {
+        Check(nxhip_set_blas_skin(m_Ctx, blas, skin->corners.data(), static_cast<uint32_t>(skin->corners.size()), static_cast<uint32_t>(joints)), "nxhip_set_blas_skin");
+        skin->onDevice = true;
+    }
+    if (!morph->onDevice) {
+        Check(nxhip_set_blas_morph(m_Ctx, blas, morph->deltas.data(), static_cast<uint32_t>(morph->deltas.size() / morph->targets), morph->targets), "nxhip_set_blas_morph");
+        morph->onDevice = true;
+    }
+    Check(nxhip_pose_blas_morph(m_Ctx, blas, weights.data(), morph->targets, skin ? palette.data() : nullptr, static_cast<uint32_t>(joints)), "nxhip_pose_blas_morph");
+    float lo[3], hi[3];
+    Check(nxhip_read_blas_bounds(m_Ctx, blas, lo, hi), "nxhip_read_blas_bounds");
+    assets.SetPosedBounds(bvhId, lo, hi);
+}
+
 void PathTracer::UpdateDeviceScene(const Scene& scene)
 {
     const AssetManager& assets = scene.GetAssetManager();

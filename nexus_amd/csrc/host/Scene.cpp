@@ -128,6 +128,7 @@ void Scene::CreateMeshInstanceFromFile(const std::string& path, const std::strin
     options.metalRough = m_MetalRoughMaterials;
     options.alphaModes = m_MaterialAlphaModes;
     options.skins = m_Skins;
+    options.morphs = m_Morphs;
     OBJLoader::LoadOBJ(path, fileName, this, &m_AssetManager, options);
     Invalidate();  // the TLAS is rebuilt by the next Update()
 }
@@ -196,12 +197,12 @@ void quat_normalise(double q[4])
     for (int k = 0; k < 4; k++) q[k] /= n;
 }
 
-// a channel's value at time t, clamped to its first and last key
-void sample_channel(const AnimationChannel& c, double t, double out[4])
+// a channel's value at time t, clamped to its first and last key (out: 4 doubles; a weights channel: one per target)
+void sample_channel(const AnimationChannel& c, double t, double* out)
 {
-    const int width = c.path == AnimationChannel::ROTATION ? 4 : 3;
     const size_t keys = c.times.size();
-    auto key = [&](size_t k, double v[4]) {
+    const int width = c.path == AnimationChannel::ROTATION ? 4 : c.path == AnimationChannel::WEIGHTS ? static_cast<int>(c.values.size() / keys) : 3;
+    auto key = [&](size_t k, double* v) {
         for (int d = 0; d < width; d++) v[d] = c.values[static_cast<size_t>(width) * k + static_cast<size_t>(d)];
     };
     if (t <= c.times.front()) return key(0, out);
@@ -209,13 +210,15 @@ void sample_channel(const AnimationChannel& c, double t, double out[4])
     const size_t i = static_cast<size_t>(std::upper_bound(c.times.begin(), c.times.end(), t) - c.times.begin()) - 1;  // times[i] <= t < times[i + 1]
     if (c.step) return key(i, out);
     const double u = (t - c.times[i]) / (c.times[i + 1] - c.times[i]);
+    if (c.path != AnimationChannel::ROTATION) {
+        const double* a = c.values.data() + static_cast<size_t>(width) * i;
+        const double* b = a + width;
+        for (int d = 0; d < width; d++) out[d] = (1.0 - u) * a[d] + u * b[d];
+        return;
+    }
     double a[4], b[4];
     key(i, a);
     key(i + 1, b);
-    if (c.path != AnimationChannel::ROTATION) {
-        for (int d = 0; d < 3; d++) out[d] = (1.0 - u) * a[d] + u * b[d];
-        return;
-    }
     // shortest-arc slerp; a normalised lerp where the arc is too short to divide by its sine
     double dot = a[0] * b[0] + a[1] * b[1] + a[2] * b[2] + a[3] * b[3];
     if (dot < 0.0) {
@@ -253,6 +256,7 @@ std::vector<float> Scene::JointPalette(uint32_t meshId, int animationIdx, double
     }
     if (animationIdx >= 0)
         for (const AnimationChannel& c : m_Animations[static_cast<size_t>(animationIdx)].channels) {
+            if (c.path == AnimationChannel::WEIGHTS) continue;  // (MorphWeights)
             Trs& n = trs[static_cast<size_t>(c.node)];
             double v[4] = {0, 0, 0, 0};
             sample_channel(c, t, v);
@@ -307,6 +311,25 @@ std::vector<float> Scene::JointPalette(uint32_t meshId, int animationIdx, double
             for (int b = 0; b < 4; b++) palette[12 * k + 4 * static_cast<size_t>(a) + static_cast<size_t>(b)] = static_cast<float>(m.m[a][b]);
     }
     return palette;
+}
+
+std::vector<float> Scene::MorphWeights(uint32_t meshId, int animationIdx, double t) const
+{
+    const std::vector<Mesh>& meshes = const_cast<AssetManager&>(m_AssetManager).GetMeshes();
+    if (meshId >= meshes.size() || !meshes[meshId].morph) throw std::runtime_error("Scene::MorphWeights: no such mesh, or the mesh has no morph targets");
+    if (animationIdx < -1 || animationIdx >= static_cast<int>(m_Animations.size())) throw std::runtime_error("Scene::MorphWeights: no such animation");
+    const Morph& morph = *meshes[meshId].morph;
+    if (animationIdx >= 0)
+        for (const AnimationChannel& c : m_Animations[static_cast<size_t>(animationIdx)].channels) {
+            if (c.path != AnimationChannel::WEIGHTS || c.node != morph.meshNode) continue;
+            if (c.values.size() != c.times.size() * morph.targets) throw std::runtime_error("Scene::MorphWeights: the weights channel does not have one value per target and key");
+            std::vector<double> w(std::max<size_t>(morph.targets, 4));
+            sample_channel(c, t, w.data());
+            std::vector<float> out(morph.targets);
+            for (size_t k = 0; k < out.size(); k++) out[k] = static_cast<float>(w[k]);
+            return out;
+        }
+    return morph.weights;
 }
 
 void Scene::AddHDRMap(const Texture& texture)

@@ -94,6 +94,11 @@ class LoadedScene:
         self.skins = []
         self.animations = []
         self.nodes = []
+        # glTF morph targets; empty unless the reader was asked (load_glb(morphs=True), which fills nodes and animations too and keeps the
+        # animations' "weights" channels: values float64 (keys, targets)).  Weights by nexus_amd.animation.morph_weights.
+        # morphs: per morphed primitive a dict(mesh: index into meshes, deltas: (targets, 3 x triangles) pod.MORPH_CORNER_DT de-indexed like the
+        #   positions, weights: float32 (targets,) the defaults, mesh_node: the first node that places the mesh, names: extras.targetNames or [])
+        self.morphs = []
         self.warnings = []
 
 
@@ -347,14 +352,17 @@ def _gltf_material(m, metal_rough=False):
 _GLTF_ALPHA = {"OPAQUE": pod.ALPHA_OPAQUE, "MASK": pod.ALPHA_MASK, "BLEND": pod.ALPHA_BLEND}
 
 
-def load_glb(path, metal_rough=False, alpha_modes=False, skins=False):
+def load_glb(path, metal_rough=False, alpha_modes=False, skins=False, morphs=False):
     """metal_rough (off by default: glTF's default metallicFactor is 1): materials without transmission become MAT_METALROUGH with the
     file's raw factors instead of the reference's PLASTIC
     alpha_modes (off by default: every existing scene renders as before): the materials' alphaMode (glTF's default: OPAQUE) and
     alphaCutoff (default 0.5) fill LoadedScene.material_alpha
     skins (off by default: every existing scene loads as before): JOINTS_0 / WEIGHTS_0, the skins, the joint animations and the node tree
-    fill LoadedScene.skins / animations / nodes.  Morph targets and JOINTS_1 are ignored with a warning; a CUBICSPLINE sampler is read
-    as its keys' values, interpolated linearly, with a warning."""
+    fill LoadedScene.skins / animations / nodes.  JOINTS_1 is ignored with a warning, and so are morph targets unless `morphs` is on; a
+    CUBICSPLINE sampler is read as its keys' values, interpolated linearly, with a warning.
+    morphs (off by default): the primitives' morph targets (POSITION and NORMAL, float VEC3, sparse accessors included) fill
+    LoadedScene.morphs, nodes and animations are filled as under skins, the animations' `weights` channels are kept, and the "morph targets
+    are ignored" warning is not given.  TANGENT deltas are not read: the 96-byte triangle has no tangents."""
     data = open(path, "rb").read()
     magic, version, _length = struct.unpack_from("<III", data, 0)
     if magic != 0x46546C67 or version != 2:
@@ -385,6 +393,23 @@ def load_glb(path, metal_rough=False, alpha_modes=False, skins=False):
         else:
             arr = np.stack([np.frombuffer(blob, dtype=dt, count=nc, offset=start + k * stride) for k in range(count)])
         return arr
+
+    def target_accessor(i, what):
+        """a morph target's attribute, (count, 3) float32: the accessor's bufferView (or zeros without one) with its sparse part written over it"""
+        a = doc["accessors"][i]
+        if a["componentType"] != 5126 or a["type"] != "VEC3":
+            raise ValueError("glb: %s: a morph target attribute must be a float VEC3 accessor" % what)
+        base = accessor(i).astype(np.float32) if "bufferView" in a else np.zeros((a["count"], 3), np.float32)
+        if "sparse" in a:
+            s = a["sparse"]
+
+            def part(ref, dt, nc):
+                bv = doc["bufferViews"][ref["bufferView"]]
+                return np.frombuffer(blob, dtype=dt, count=s["count"] * nc, offset=bv.get("byteOffset", 0) + ref.get("byteOffset", 0))
+
+            base = base.copy()
+            base[part(s["indices"], np.dtype(_COMPONENT[s["indices"]["componentType"]]), 1).astype(np.int64)] = part(s["values"], np.dtype("<f4"), 3).reshape(-1, 3)
+        return base
 
     out = LoadedScene()
     decoded = {}
@@ -450,7 +475,9 @@ def load_glb(path, metal_rough=False, alpha_modes=False, skins=False):
 
     # one mesh per primitive (what Assimp hands the reference)
     prim_mesh = {}
+    mesh_targets = {}  # morphs=True: mesh -> the target count of its primitives (all equal)
     prim_corners = {}  # skins=True: (mesh, primitive) -> its de-indexed nx_skin_corner records
+    prim_targets = {}  # morphs=True: (mesh, primitive) -> its de-indexed (targets, 3 x triangles) nx_morph_corner records
     for mi, mesh in enumerate(doc.get("meshes", [])):
         for pi, prim in enumerate(mesh["primitives"]):
             if prim.get("mode", 4) != 4:
@@ -468,7 +495,7 @@ def load_glb(path, metal_rough=False, alpha_modes=False, skins=False):
             prim_mesh[(mi, pi)] = (len(out.meshes), prim.get("material", 0))
             if skins:
                 what = "mesh %d primitive %d" % (mi, pi)
-                if prim.get("targets"):
+                if prim.get("targets") and not morphs:
                     out.warnings.append("%s: morph targets are ignored" % what)
                 if "JOINTS_1" in prim["attributes"]:
                     out.warnings.append("%s: more than four influences per vertex (JOINTS_1) are ignored; JOINTS_0 / WEIGHTS_0 are used" % what)
@@ -479,6 +506,15 @@ def load_glb(path, metal_rough=False, alpha_modes=False, skins=False):
                     w = w.astype(np.float32) if wa["componentType"] == 5126 else (w.astype(np.float64) / np.iinfo(w.dtype).max).astype(np.float32)
                     j = accessor(prim["attributes"]["JOINTS_0"]).astype(np.int64)
                     prim_corners[(mi, pi)] = pod.make_skin_corners(j[idx], w[idx])  # corner 3 i + v = vertex v of triangle i
+            if morphs:
+                what = "mesh %d primitive %d" % (mi, pi)
+                count = len(prim.get("targets", []))
+                if mesh_targets.setdefault(mi, count) != count:
+                    raise ValueError("glb: mesh %d has primitives with different numbers of morph targets" % mi)
+                if count:
+                    dp = np.stack([target_accessor(tg["POSITION"], what)[idx] if "POSITION" in tg else np.zeros((len(idx), 3), np.float32) for tg in prim["targets"]])
+                    dn = np.stack([target_accessor(tg["NORMAL"], what)[idx] if "NORMAL" in tg else np.zeros((len(idx), 3), np.float32) for tg in prim["targets"]])
+                    prim_targets[(mi, pi)] = pod.make_morph_corners(dp, dn)  # corner 3 i + v = vertex v of triangle i
             out.meshes.append(t)
             out.mesh_names.append(mesh.get("name", "mesh%d" % mi))
 
@@ -511,13 +547,35 @@ def load_glb(path, metal_rough=False, alpha_modes=False, skins=False):
     for ni in scene["nodes"]:
         walk(ni, np.eye(4))
     out.analytic_lights = np.array(lights, dtype=pod.ALIGHT_DT) if lights else np.zeros(0, dtype=pod.ALIGHT_DT)
-    if skins:
-        _read_skins(doc, accessor, prim_mesh, prim_corners, out)
+    if skins or morphs:
+        _read_skins(doc, accessor, prim_mesh, prim_corners, out, skins, morphs)
+    if morphs:
+        _read_morphs(doc, prim_mesh, prim_targets, out)
     return out
 
 
-def _read_skins(doc, accessor, prim_mesh, prim_corners, out):
-    """LoadedScene.nodes, skins and animations of a glTF document (load_glb(skins=True))"""
+def _read_morphs(doc, prim_mesh, prim_targets, out):
+    """LoadedScene.morphs of a glTF document (load_glb(morphs=True)): the first node that places a mesh gives its default weights"""
+    seen = set()
+    for ni, node in enumerate(doc.get("nodes", [])):
+        if "mesh" not in node or node["mesh"] in seen:
+            continue
+        seen.add(node["mesh"])
+        mesh = doc["meshes"][node["mesh"]]
+        for (mi, pi), (mesh_id, _mat) in prim_mesh.items():
+            if mi != node["mesh"] or (mi, pi) not in prim_targets:
+                continue
+            deltas = prim_targets[(mi, pi)]
+            weights = node.get("weights", mesh.get("weights", [0.0] * len(deltas)))
+            if len(weights) != len(deltas):
+                raise ValueError("glb: mesh %d has %d morph targets and %d default weights" % (mi, len(deltas), len(weights)))
+            names = [str(n) for n in (mesh.get("extras") or {}).get("targetNames", [])]
+            out.morphs.append(dict(mesh=mesh_id, deltas=deltas, weights=np.array(weights, np.float32), mesh_node=ni, names=names))
+
+
+def _read_skins(doc, accessor, prim_mesh, prim_corners, out, skins=True, morphs=False):
+    """LoadedScene.nodes, skins and animations of a glTF document (load_glb(skins=True) or (morphs=True): the skins for the first, the
+    `weights` channels for the second)"""
     nodes = doc.get("nodes", [])
     parent = [-1] * len(nodes)
     for ni, node in enumerate(nodes):
@@ -529,7 +587,7 @@ def _read_skins(doc, accessor, prim_mesh, prim_corners, out):
                               scale=np.array(node.get("scale", [1, 1, 1]), np.float64),
                               matrix=np.array(node["matrix"], np.float64).reshape(4, 4).T if "matrix" in node else None))
     for ni, node in enumerate(nodes):
-        if "mesh" not in node or "skin" not in node:
+        if not skins or "mesh" not in node or "skin" not in node:
             continue
         skin = doc["skins"][node["skin"]]
         joints = [int(j) for j in skin["joints"]]
@@ -550,8 +608,8 @@ def _read_skins(doc, accessor, prim_mesh, prim_corners, out):
         channels = []
         for ch in anim.get("channels", []):
             target = ch.get("target", {})
-            if "node" not in target or target.get("path") not in ("translation", "rotation", "scale"):
-                continue  # (weights: morph targets, ignored with the primitive's warning)
+            if "node" not in target or target.get("path") not in (("translation", "rotation", "scale", "weights") if morphs else ("translation", "rotation", "scale")):
+                continue  # (weights without morphs=True: morph targets, ignored with the primitive's warning)
             s = anim["samplers"][ch["sampler"]]
             times = accessor(s["input"]).reshape(-1).astype(np.float64)
             oa = doc["accessors"][s["output"]]
@@ -565,6 +623,8 @@ def _read_skins(doc, accessor, prim_mesh, prim_corners, out):
                 interpolation = "LINEAR"
             elif interpolation not in ("STEP", "LINEAR"):
                 raise ValueError("glb: animation %d has the unknown interpolation %r" % (ai, interpolation))
+            if target["path"] == "weights" and len(times) and values.size % len(times) == 0:
+                values = values.reshape(len(times), -1)  # (keys, targets)
             if len(times) == 0 or len(values) != len(times):
                 raise ValueError("glb: animation %d has a sampler whose keys and values differ in number" % ai)
             channels.append(dict(node=int(target["node"]), path=target["path"], times=times, values=values, interpolation=interpolation))

@@ -84,6 +84,10 @@ assert ALPHA_DT.itemsize == 8
 SKIN_CORNER_DT = np.dtype([("joint", "<u2", 4), ("weight", "<f4", 4)])
 assert SKIN_CORNER_DT.itemsize == 24
 SKIN_MAX_JOINTS = 65536
+# nx_morph_corner (extension, nxhip_set_blas_morph): 24 bytes — the position and normal deltas of one triangle corner under one morph target
+MORPH_CORNER_DT = np.dtype([("dPosition", "<f4", 3), ("dNormal", "<f4", 3)])
+assert MORPH_CORNER_DT.itemsize == 24
+MORPH_MAX_TARGETS = 1024
 
 # nx_medium (extension, nxhip_set_medium): 48 bytes — fog, one homogeneous medium in a world-space box
 MEDIUM_DT = np.dtype([("boxMin", "<f4", 3), ("sigmaT", "<f4"), ("boxMax", "<f4", 3), ("g", "<f4"), ("albedo", "<f4", 3), ("pad", "<u4")])
@@ -199,6 +203,20 @@ def make_skin_corners(joints, weights):
         raise ValueError("a joint index does not fit 16 bits")
     c = np.zeros(len(joints), dtype=SKIN_CORNER_DT)
     c["joint"], c["weight"] = joints, weights
+    return c
+
+
+def make_morph_corners(d_positions, d_normals=None):
+    """nx_morph_corner records, (T, 3 n): d_positions (T, 3 n, 3) position deltas of T targets — or (3 n, 3) for one —, d_normals the
+    normal deltas of the same shape (None: zeros, a target without NORMAL).  Corner 3 i + v is vertex v of triangle i."""
+    dp = np.asarray(d_positions, dtype=np.float32)
+    if dp.ndim == 2:
+        dp = dp[None]
+    if dp.ndim != 3 or dp.shape[2] != 3 or dp.shape[1] % 3 != 0:
+        raise ValueError("position deltas must be (targets, 3 n, 3)")
+    dn = np.zeros_like(dp) if d_normals is None else np.asarray(d_normals, dtype=np.float32).reshape(dp.shape)
+    c = np.zeros(dp.shape[:2], dtype=MORPH_CORNER_DT)
+    c["dPosition"], c["dNormal"] = dp, dn
     return c
 
 
