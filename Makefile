@@ -51,14 +51,14 @@ $(OBJDIR)/%.o: %.hip $(HDRS)
 	@mkdir -p $(dir $@)
 	$(HIPCC) $(DEVFLAGS) -c $< -o $@
 
-# (the DETAIL instances are compiled from the kernel templates of nx_wavefront.hip, which that unit includes)
-$(OBJDIR)/nexus_amd/csrc/device/nx_wavefront_detail.o: nexus_amd/csrc/device/nx_wavefront.hip
-# (... and the METAL instances: nx_wavefront_metal.hip)
-$(OBJDIR)/nexus_amd/csrc/device/nx_wavefront_metal.o: nexus_amd/csrc/device/nx_wavefront.hip
-# (... and the SOLID instances: nx_wavefront_solid.hip)
-$(OBJDIR)/nexus_amd/csrc/device/nx_wavefront_solid.o: nexus_amd/csrc/device/nx_wavefront.hip
-# (... and so are the medium's kernels, which call its device functions)
-$(OBJDIR)/nexus_amd/csrc/device/nx_medium.o: nexus_amd/csrc/device/nx_wavefront.hip
+# `make asm`: every device unit's gfx950 assembly, from the same flags as its object (build/asm/<unit>.s). tools/kernel_resources.py
+# reads the registers and spills out of these; tools/kernel_isa_diff.py compares two such directories kernel by kernel.
+ASMDIR    := build/asm
+$(ASMDIR)/%.s: nexus_amd/csrc/device/%.hip $(HDRS)
+	@mkdir -p $(dir $@)
+	$(HIPCC) $(DEVFLAGS) -S --cuda-device-only $< -o $@
+
+asm: $(patsubst nexus_amd/csrc/device/%.hip,$(ASMDIR)/%.s,$(DEV_SRCS))
 
 $(OBJDIR)/%.o: %.cpp $(HDRS)
 	@mkdir -p $(dir $@)
@@ -78,7 +78,7 @@ release:
 clean:
 	rm -rf build $(OUT)
 
-.PHONY: all oracle clean release
+.PHONY: all oracle clean release asm
 
 # Host-side AddressSanitizer + UBSan build (device code is compiled as usual; GPU ASan is not available on this pool).
 # Used by tools/run_sanitized_cpu_tests.sh; output goes to build/asan/ and never replaces the product library.

@@ -6,7 +6,7 @@
  * (Cuda/BSDF/Microfacet.cuh:18, 75), atan2f / asinf in SampleBackground (Cuda/PathTracer/PathTracer.cu:65-83) and a double pow in
  * LinearToGamma (Utils/Utils.h:51-54).  On the device those come from ROCm's ocml, in the CPU oracle from glibc; the two agree to
  * an ulp or two, one flipped Russian-roulette / lobe decision changes a pixel, and frames could only be compared as "x % of the
- * pixels within 1e-3".  The functions below are used by BOTH the HIP kernels (nx_rng.h, nx_bsdf.h, nx_wavefront.hip) and the CPU
+ * pixels within 1e-3".  The functions below are used by BOTH the HIP kernels (nx_rng.h, nx_bsdf.h, nx_wavefront.h) and the CPU
  * oracle (orc_shade.c, orc_wavefront.c): the same sequence of IEEE-754 operations on either side, so a frame of the device
  * equals the oracle's bit for bit.
  *

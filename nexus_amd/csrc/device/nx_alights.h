@@ -1,6 +1,6 @@
 // nx_alights.h — analytic lights (nxhip_set_analytic_lights): the light sample's draw for one of them (the record: nx_device.h ALight).
 // The contract is the header's (include/nexus_hip.h, "Analytic lights"); this file is its one implementation on the device: the
-// ANALYTIC instances of the material kernels (nx_wavefront.hip next_event_estimation) and the test hook (alight_hook_kernel) both
+// ANALYTIC instances of the material kernels (nx_wavefront.h next_event_estimation) and the test hook (alight_hook_kernel) both
 // call alight_sample.
 #pragma once
 

@@ -1,7 +1,7 @@
 // nx_detail.h — detail maps in the material step: the roughness map's factor and the normal map's shading normal.
 //
 // The rule is stated in full in include/nexus_hip.h (nxhip_set_material_detail); this is its one device text, called by the DETAIL
-// instances of the material kernels (nx_wavefront.hip shade_path) and by the test hook (nxhip_shading_frame_batch).
+// instances of the material kernels (nx_wavefront.h shade_path) and by the test hook (nxhip_shading_frame_batch).
 // Tangents come from the triangle's positions and texture coordinates (set 0), per triangle: the 96-byte nx_triangle has no room for
 // glTF's TANGENT attribute.
 #pragma once

@@ -31,11 +31,11 @@ struct HookBatch {
         if (d) outs.push_back({host, d, count * width * sizeof(T)});
         return d;
     }
-    // the kernel over c->wideBlocks x kWideBlockThreads on the context's stream, the wait, the outputs (typed as launch_untimed is)
+    // the kernel over c->wideBlocks x kWideBlock on the context's stream, the wait, the outputs (typed as launch_untimed is)
     template <class... A> int run(Kernel<A...> k, std::common_type_t<A>... args)
     {
         NX_TRY(rc);
-        NX_HIP(launch_untimed(k, c->wideBlocks, kWideBlockThreads, c->stream, args...));
+        NX_HIP(launch_untimed(k, c->wideBlocks, kWideBlock, c->stream, args...));
         NX_SYNC_ALL(c);
         for (const Out& o : outs) NX_HIP(hipMemcpy(o.host, o.dev, o.bytes, hipMemcpyDeviceToHost));
         return NXHIP_OK;

@@ -13,8 +13,8 @@ namespace nxd {
 
 // ---- what the kernel units export ---------------------------------------------------------------------
 // nx_lbvh.hip, nx_lights.hip and nxhip_multigpu.hip include this header, so the compiler checks their declarations against the
-// definitions.  The getters of the other kernel units are declared here as they are defined there (nx_trace.hip, nx_entry.hip
-// and nx_wavefront.hip do not include it).
+// definitions.  The getters of the other kernel units are declared here as they are defined there (nx_trace.hip, nx_entry.hip,
+// nx_hook_kernels.hip and the nx_wavefront*.hip units do not include it).
 // The kernel families with compile-time instances: one lookup per family and unit, keyed by the feature set (nx_variants.h: kTf* for
 // the trace kernel, kMf* for the rest) and the material type where there is one; nullptr for a set the unit does not hold.
 const void* trace_kernel_of(unsigned set);  // nx_trace.hip
@@ -31,16 +31,16 @@ const void* hook_sizes_kernel_ptr();
 const void* generate_kernel_ptr();
 const void* accumulate_kernel_ptr();
 const void* compose_kernel_ptr();
-const void* bsdf_hook_kernel_ptr();
+const void* logic_metal_kernel_ptr();  // nx_wavefront_metal.hip (the classic pipeline's fifth queue)
+const void* bsdf_hook_kernel_ptr();  // nx_hook_kernels.hip: the array test hooks
+const void* bsdf_hook_metal_kernel_ptr();
 const void* fmath_hook_kernel_ptr();
 const void* tex2d_hook_kernel_ptr();
+const void* tex2d_float_hook_kernel_ptr();
+const void* tex2d_linear_hook_kernel_ptr();
 const void* env_hook_kernel_ptr();
 const void* alight_hook_kernel_ptr();
-const void* tex2d_float_hook_kernel_ptr();
-const void* shading_frame_hook_kernel_ptr();  // nx_wavefront_detail.hip
-const void* tex2d_linear_hook_kernel_ptr();
-const void* bsdf_hook_metal_kernel_ptr();  // nx_wavefront_metal.hip
-const void* logic_metal_kernel_ptr();  // (the classic pipeline's fifth queue)
+const void* shading_frame_hook_kernel_ptr();
 const void* material_inputs_hook_kernel_ptr();
 const void* medium_shadow_kernel_ptr();  // nx_medium.hip
 const void* medium_segment_hook_kernel_ptr();
@@ -73,6 +73,7 @@ uint64_t layout_stamp_wavefront();
 uint64_t layout_stamp_wavefront_detail();
 uint64_t layout_stamp_wavefront_solid();
 uint64_t layout_stamp_wavefront_metal();
+uint64_t layout_stamp_hook_kernels();
 uint64_t layout_stamp_medium();
 uint64_t layout_stamp_refit();
 uint64_t layout_stamp_skin();
@@ -101,25 +102,7 @@ int lbvh_build_batch(nxhip_ctx* c, const nx_triangle* dTris, const std::vector<u
 int lbvh_write_isect(nxhip_ctx* c, const nx_triangle* dTris, const uint32_t* dPrimIdx, uint32_t n, float4* dIsect);
 int lbvh_build_tlas(nxhip_ctx* c, const nx_bvh_instance* dInstances, uint32_t n, int plocRadius, DevBuf& nodes, DevBuf& primIdx, DevBuf& box, bool* boxesAreTight, uint32_t* nodeCount);
 
-// Threads per workgroup of the kernels the host sizes grids for.  NX_TRACE_BLOCK / NX_SHADE_BLOCK / NX_LOGIC_BLOCK are build knobs
-// given on the command line of the WHOLE library (nx_traverse.h, nx_wavefront.hip hold their defaults and define the macros; this
-// header defines none, only repeats the defaults).
-#ifdef NX_TRACE_BLOCK
-constexpr int kTraceBlockThreads = NX_TRACE_BLOCK;
-#else
-constexpr int kTraceBlockThreads = 256;
-#endif
-#ifdef NX_SHADE_BLOCK
-constexpr int kShadeBlockThreads = NX_SHADE_BLOCK;
-#else
-constexpr int kShadeBlockThreads = 256;
-#endif
-#ifdef NX_LOGIC_BLOCK
-constexpr int kLogicBlockThreads = NX_LOGIC_BLOCK;
-#else
-constexpr int kLogicBlockThreads = 1024;
-#endif
-constexpr int kWideBlockThreads = 256;
+// (threads per workgroup of the kernels the host sizes grids for: kTraceBlock / kShadeBlock / kLogicBlock / kWideBlock, nx_device.h)
 constexpr int kHookBounceSlot = NX_PATH_MAX_LENGTH - 1;  // queue-size slot used by the batch test hooks
 
 // ---- typed launches ------------------------------------------------------------------------------------
@@ -323,7 +306,7 @@ int sync_all(nxhip_ctx* c);
 #define NX_DEBUG_HOOK(name) do { } while (0)
 #endif
 
-// Which pipeline a pass runs (nx_wavefront.hip): SCAN — the logic step's decision rides in the hit records and the material kernels
+// Which pipeline a pass runs (nx_wavefront.h): SCAN — the logic step's decision rides in the hit records and the material kernels
 // pick their items out of the trace queue — whenever slots are handed out by racing atomics; the CLASSIC logic kernel + material
 // queues for the ordered compaction, whose serial slot order IS the reference's copy order (PathTracer.cu:183-206).
 inline bool scan_pipeline(const nxhip_ctx* c) { return c->h.compactMode == NX_COMPACT_FAST; }

@@ -1,5 +1,5 @@
 // nx_lights.h — reading the light table (nx_device.h LightEntry; built by nx_lights.hip): the pick of the light sample and the
-// probability lookup of the MIS weight.  Shared by the POWER-mode material kernels (nx_wavefront.hip) and the pick hook.
+// probability lookup of the MIS weight.  Shared by the POWER-mode material kernels (nx_wavefront.h) and the pick hook.
 // Below them the same two for the light tree (LightNode; the TREE instances of the material launch and of the medium's scatter kernel).
 #pragma once
 

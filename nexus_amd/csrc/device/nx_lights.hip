@@ -71,7 +71,7 @@ __global__ void __launch_bounds__(kLightBlock) light_weight_kernel(const LightBu
     const ShadeInst* inst = &b.shadeInst[b.lights[lo].mesh.meshId];
     const nx_triangle* t = shade_tri(inst->tris, tri);
     const float* T = inst->transform;
-    // the very expression of the light sample's density (nx_wavefront.hip next_event_estimation)
+    // the very expression of the light sample's density (nx_wavefront.h next_event_estimation)
     const float area = tri_area(mat_point(T, ld3(t->pos0)), mat_point(T, ld3(t->pos1)), mat_point(T, ld3(t->pos2)));
     const nx_material* m = &inst->material;
     f3 e = ld3(m->emissive);

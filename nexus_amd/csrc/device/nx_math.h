@@ -69,7 +69,7 @@ NXD f3 mat_vec_transposed(P c, f3 v)
     return f3{fmaf(c[8], v.z, fmaf(c[4], v.y, c[0] * v.x)), fmaf(c[9], v.z, fmaf(c[5], v.y, c[1] * v.x)), fmaf(c[10], v.z, fmaf(c[6], v.y, c[2] * v.x))};
 }
 
-// (the light sample's density and the light table's weights — nx_wavefront.hip, nx_lights.hip — share this expression)
+// (the light sample's density and the light table's weights — nx_wavefront.h, nx_lights.hip — share this expression)
 NXD float tri_area(f3 p0, f3 p1, f3 p2) { return 0.5f * length3(cross3(p1 - p0, p2 - p0)); }
 
 // quaternion helpers — cuda_math.h:1514-1535

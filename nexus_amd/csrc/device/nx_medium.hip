@@ -7,9 +7,10 @@
 //                          the vertex's light sample and continuation ray itself, into the queues the material launch appends to;
 //   medium_shadow_kernel   between the material launch of bounce b and its any-hit launch: multiplies the radiance of every shadow request
 //                          that crosses the box by the transmittance of the crossing.
-// No kernel of nx_wavefront.hip changes: its text is compiled here for the templates and device functions alone (NX_WAVEFRONT_INSTANCES_ONLY,
-// as nx_wavefront_detail.hip does) — the light sample is next_event_estimation itself, with the phase function as its "BSDF".
-// Also here: the two test hooks' kernels over the same device functions.
+// No material kernel changes: this unit includes their shared text (nx_wavefront.h) for its device functions and instantiates none of its
+// kernels — the light sample is next_event_estimation itself, with the phase function as its "BSDF", the slots come from SlotAllocator.
+// A unit of its own: contexts without a medium launch nothing of it, and it compiles beside the material families, not behind them.
+// Also here: the two test hooks' kernels over the device functions this unit defines.
 //
 // The density grid (nxhip_set_medium_density; the rule: include/nexus_hip.h): extinction sigmaT x rho(p), rho a trilinear lookup in a voxel
 // grid over the box.  Both kernels have a GRID instance beside the homogeneous one (medium_scatter_kernel<GRID = true, ..>, and the sibling
@@ -17,8 +18,8 @@
 // each — delta tracking for the free flight, ratio tracking for the shadow requests.  The homogeneous instances keep their code, instruction
 // for instruction (profiles/medium_grid.txt).  medium_brick_kernel builds the majorants on the device; three hooks (lookup, walk, majorants)
 // for the tests.
-#define NX_WAVEFRONT_INSTANCES_ONLY 1
-#include "nx_wavefront.hip"
+#define NX_KERNEL_TU 1
+#include "nx_wavefront.h"
 
 namespace nxd {
 

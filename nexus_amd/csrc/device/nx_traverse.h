@@ -1,5 +1,5 @@
 // nx_traverse.h — the pieces of the BVH8 traversal shared by the persistent trace kernels (nx_trace.hip) and the tail kernel
-// (nx_wavefront.hip): record fetch, the LDS / scratch stack, ChildTrace, and traverse_wave, the same traversal step run for
+// (nx_wavefront.h): record fetch, the LDS / scratch stack, ChildTrace, and traverse_wave, the same traversal step run for
 // the 64 rays of one wave without refill.
 #pragma once
 #include "nx_device.h"
@@ -7,10 +7,7 @@
 
 namespace nxd {
 
-#ifndef NX_TRACE_BLOCK
-#define NX_TRACE_BLOCK 256
-#endif
-constexpr int kTraceBlock = NX_TRACE_BLOCK;  // 4 waves (NX_TRACE_BLOCK: measurement knob, 64 / 128: DESIGN.md section 7)
+// (kTraceBlock, the trace kernels' workgroup: nx_device.h)
 #ifndef NX_LDS_DEPTH
 #define NX_LDS_DEPTH 8
 #endif

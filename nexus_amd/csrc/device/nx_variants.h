@@ -1,10 +1,11 @@
 // nx_variants.h — the names of the compile-time kernel instances: which features of a scene a kernel was compiled for.
 //
 // A feature is a template instance, not a run-time branch: a context without the feature launches the kernels it always did.  A kernel
-// template takes ONE set of these bits; the kernel units list the sets they compile and look an instance up by its set (a set nobody
-// compiled yields no kernel), the host derives the set of a launch from the pass flavor (nxhip_render.hip material_features,
+// template takes ONE set of these bits; the templates of the material kernels stand in a header (nx_wavefront.h), the kernel units that
+// include it (nx_wavefront.hip, nx_wavefront_detail / _metal / _solid.hip) list the sets they compile and look an instance up by its set
+// (a set nobody compiled yields no kernel), the host derives the set of a launch from the pass flavor (nxhip_render.hip material_features,
 // trace_features).  Plain constexpr: kernel units and host units both include this.  What each feature means, and what it measured,
-// stands at the code that reads it (nx_trace.hip trace_kernel; nx_wavefront.hip next_event_estimation, shade_path, shade_scan_kernel).
+// stands at the code that reads it (nx_trace.hip trace_kernel; nx_wavefront.h next_event_estimation, shade_path, shade_scan_kernel).
 // Not to be confused with the run-time launch flags of nx_device.h (kTraceScanFlag, kTraceEntryFlag, kTraceThinFlag: bits of a launch's
 // bounce argument).
 #pragma once

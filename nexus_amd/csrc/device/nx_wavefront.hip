@@ -1,362 +1,17 @@
-// nx_wavefront.hip — the wide wavefront kernels: begin-frame, generate, logic, shade (+NEE), accumulate.
+// nx_wavefront.hip — the plain kernels of a pass (begin-frame, generate, count-scan, accumulate, compose; the ray-batch hooks' queue
+// sizes) and the BASE instances of the material kernel families: the contexts without detail maps, a fifth material type or alpha modes.
 //
-// What they compute is the reference's GenerateKernel, LogicKernel, Shade<BSDF> + NextEventEstimation<BSDF> and
-// AccumulateKernel (/root/reference/Nexus/src/Cuda/PathTracer/PathTracer.cu:85-122, 136-210, 213-458, 480-496).
-// How they run is MI355X-first:
-//   * persistent grid-stride launches (<= 2048 workgroups of 256) instead of N/64+1 blocks that mostly exit:
-//     late bounces with few live paths cost a launch, not tens of thousands of empty workgroups;
-//   * float4-packed SoA queues: every lane moves 16 B per access, fully coalesced;
-//   * queue slots are handed out once per workgroup (ballots + popcount ranks + one atomic) — NX_COMPACT_FAST — or by a
-//     grid-wide ordered scan (tiles by ticket, decoupled look-back) — NX_COMPACT_ORDERED, which reproduces the
-//     reference's serial slot order exactly (ascending thread index, material kernels in graph order) on all CUs and
-//     is what the parity tests use; the shading math is the same code in both modes;
-//   * a path's shadow-ray and continuation-ray payloads are built in registers and written after the slot
-//     allocation, outside divergent control flow;
-//   * the frame number lives on the device and is advanced by begin_frame_kernel, so a frame is one
-//     hipGraph replay with no host-side writes in between.
-// NX_WAVEFRONT_INSTANCES_ONLY: nx_wavefront_detail.hip compiles this text for the kernel TEMPLATES alone and instantiates their DETAIL
-// family there (a translation unit of its own: profiles/analytic_lights.txt section 3); everything that is not a template — the plain
-// kernels, the getters, the layout stamp — is then left out, so nothing is defined twice.
+// The families' text is nx_wavefront.h, which says how the kernels run; the instances with a newer feature are units of their own
+// (nx_wavefront_detail.hip / _metal.hip / _solid.hip), and the array test hooks are nx_hook_kernels.hip.  The four family units are
+// the build's longest compiles, about a minute and a half each (profiles/analytic_lights.txt section 3, profiles/kernel_units.txt: the
+// build's wall time is theirs), so only what a pass graph launches lives in them.
+// What the plain kernels compute is the reference's GenerateKernel and AccumulateKernel
+// (Nexus/src/Cuda/PathTracer/PathTracer.cu:85-122, 480-496).
 #define NX_KERNEL_TU 1
-#include "nx_bsdf.h"
-#include "nx_device.h"
-#include "nx_math.h"
-#include "nx_lights.h"
-#include "nx_alights.h"
-#include "nx_detail.h"
-#include "nx_queue.h"
-#include "nx_texture.h"
+#include "nx_wavefront.h"
 #include "nx_tonemap.h"
-#include "nx_traverse.h"
-#include "nx_variants.h"
 
 namespace nxd {
-
-constexpr int kWideBlock = 256;     // generate / accumulate
-#ifndef NX_SHADE_BLOCK
-#define NX_SHADE_BLOCK 256
-#endif
-#ifndef NX_LOGIC_BLOCK
-#define NX_LOGIC_BLOCK 1024
-#endif
-constexpr int kLogicBlock = NX_LOGIC_BLOCK;   // one slot atomic per tile of kLogicItems x this many items
-// Items per logic thread.  Two: a tile of 2 048 items pays ONE round of slot allocation (barriers, the returning atomic per queue
-// or, ordered, the ticket and four look-backs) where 1 024-item tiles paid two — logic kernel -4.5 % racing, ordered mode +2.7 % on
-// the driver command — at 64 VGPRs with 20 spilled (two workgroups per CU as before; with a 4-wave register budget and no spills
-// only one workgroup fits a CU: +18 % on the kernel).
-#ifndef NX_LOGIC_ITEMS
-#define NX_LOGIC_ITEMS 2
-#endif
-constexpr int kLogicItems = NX_LOGIC_ITEMS;
-constexpr int kShadeBlock = NX_SHADE_BLOCK;
-
-// ------------------------------------------------------------------------------------------------------
-// slot allocation: K queues at once, one round of workgroup-wide cooperation per tile.
-//   FAST    : per-wave ballots -> per-workgroup totals in LDS -> ONE atomicAdd per workgroup and counter (a single
-//             global counter sustains only ~88 returning atomics per microsecond on MI355X, so per-wave atomics
-//             serialise a 2M-item pass; per-workgroup ones do not).  Slot order = order of the atomics: racy, like the
-//             reference's per-thread atomicAdd (PathTracer.cu:143, 326).
-//   ORDERED : the reference's SERIAL slot order — ascending item index within a kernel, the material kernels of a bounce
-//             continuing each other's queues in graph order (PathTracer.cpp:114-124) — on the whole chip.  Tiles are handed
-//             out by ticket (so a tile's predecessors are always held by running workgroups), and a tile's base slot is the
-//             sum of its predecessors' counts, found by decoupled look-back: every tile publishes its count, then reads
-//             the status words of the tiles before it 64 at a time until it meets one that already knows its inclusive
-//             prefix, and publishes its own.  Tile 0 starts from the counter word (what the previous kernel of the chain
-//             left there), the last tile stores the new total.  Round 1-3 did this in ONE 1024-thread workgroup.
-// Must be called by every thread of the workgroup (uniform control flow).
-
-constexpr int kMaxWavesPerBlock = 1024 / kWave;
-
-NXD unsigned long long scan_word(uint32_t serial, uint32_t state, int value) { return ((unsigned long long)((serial << 2) | state) << 32) | (unsigned long long)(uint32_t)value; }
-NXD int wave_sum(int v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-// Decoupled look-back of the ordered compaction, ONE text for both allocators below (one wave per queue calls it): the slots taken
-// by all tiles before tile t of this launch (and by the kernels before it in the chain: tile 0 starts from the counter word), and
-// this tile's count published for its successors.  `st`: the queue's status words ([tile * kScanWords]), `counter`: the queue's
-// counter word, `serial`: the launch's tag (words of other launches read as "not there yet").
-NXD int scan_look_back(NX_G unsigned long long* const st, const int* const counter, NX_G FrameState* const frame, const uint32_t serial, const int t, const int total)
-{
-    const int lane = threadIdx.x & (kWave - 1);
-    if (t == 0) {
-        const int base = *counter;
-        if (lane == 0) __hip_atomic_store(&st[0], scan_word(serial, kScanPrefix, base + total), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return base;
-    }
-    if (lane == 0) __hip_atomic_store(&st[(size_t)t * kScanWords], scan_word(serial, kScanAggregate, total), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    int excl = 0, nearest = t - 1;
-    uint32_t spins = 0u;
-    for (;;) {
-        const int j = nearest - lane;  // lane 0 looks at the nearest predecessor not summed yet
-        uint32_t tag = (serial << 2) | kScanPrefix;  // (tiles "before tile 0" never decide: tile 0 itself is a prefix)
-        int value = 0;
-        if (j >= 0) {
-            const unsigned long long w = __hip_atomic_load(&st[(size_t)j * kScanWords], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            tag = (uint32_t)(w >> 32);
-            value = (int)(uint32_t)w;
-        }
-        const bool ready = (tag >> 2) == serial && (tag & 3u) != 0u;
-        const unsigned long long notReady = __ballot(!ready), prefixes = __ballot(ready && (tag & 3u) == kScanPrefix);
-        const int firstNot = notReady ? __ffsll((long long)notReady) - 1 : kWave;
-        const int firstPrefix = prefixes ? __ffsll((long long)prefixes) - 1 : kWave;
-        if (firstPrefix < firstNot) {  // every tile between here and a known prefix has published its count
-            excl += wave_sum(lane <= firstPrefix ? value : 0);
-            break;
-        }
-        // counts in front of the first tile that has not published yet are final: take them, then look again from there
-        excl += wave_sum(lane < firstNot ? value : 0);
-        nearest -= firstNot;
-        if (firstNot < kWave) {
-            __builtin_amdgcn_s_sleep(2);
-            if (++spins > (1u << 20)) {  // (about a second; see kErrScanStalled)
-                if (lane == 0) atomicOr(&frame->errorWord, kErrScanStalled);
-                break;
-            }
-        }
-    }
-    if (lane == 0) __hip_atomic_store(&st[(size_t)t * kScanWords], scan_word(serial, kScanPrefix, excl + total), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return excl;
-}
-
-template <bool ORDERED, int K>
-struct SlotAllocator {
-    int* sWave;  // [K][kMaxWavesPerBlock] per-wave counts of the current tile
-    int* sBase;  // [K] base slot of the current tile
-    int* sTile;  // ORDERED: the ticket of the current tile
-    int* counter0;  // the K counter words are counter0 + k * counterStep (an address computation, not an array of pointers: an
-    int counterStep;  // array indexed by anything but a constant makes the allocator a private-memory object in LDS or scratch)
-    NX_G unsigned long long* status;  // ORDERED: tile status words, [tile][kScanWords]
-    NX_G int* ticket;
-    NX_G FrameState* frame;
-    uint32_t serial;
-    int size, lastTile;
-
-    // `kind`: 0 logic, 1 + NX_MAT_* material kernel; `items`: size of the launch's input queue
-    // (ticketWord: the tile ticket of a kind that has no row in Counters::scanTicket — NX_MAT_METALROUGH's launches; nullptr: the kind's row)
-    NXD void init(const DeviceState* S, int* const first, const int step, const int kind, const int bounce, const int items, NX_G int* const ticketWord = nullptr)
-    {
-        __shared__ int wave[K * kMaxWavesPerBlock];
-        __shared__ int base[K];
-        __shared__ int tile;
-        sWave = wave;
-        sBase = base;
-        sTile = &tile;
-        counter0 = first;
-        counterStep = step;
-        size = items;
-        lastTile = (items + (int)blockDim.x - 1) / (int)blockDim.x - 1;
-        if (ORDERED) {
-            status = S->scanStatus;
-            ticket = ticketWord ? ticketWord : &S->counters->scanTicket[kind][bounce];
-            frame = S->frame;
-            serial = S->frame->scanEpoch * 1024u + (uint32_t)bounce * 8u + (uint32_t)kind;
-        }
-    }
-    NXD int* counter_of(const int k) const
-    {
-        return counter0 + k * counterStep;
-    }
-    // first item of the workgroup's first / next tile (>= size: none left)
-    NXD int first_tile() { return ORDERED ? take() : (int)(blockIdx.x * blockDim.x); }
-    NXD int next_tile(const int tile) { return ORDERED ? take() : tile + (int)(gridDim.x * blockDim.x); }
-    NXD int take()
-    {
-        __syncthreads();  // the previous tile's readers are done with sTile
-        if (threadIdx.x == 0) *sTile = atomicAdd(ticket, 1);
-        __syncthreads();
-        const int t = *sTile;
-        return t > lastTile ? size : t * (int)blockDim.x;
-    }
-
-    NXD int look_back(const int k, const int t, const int total) { return scan_look_back(status + k, counter_of(k), frame, serial, t, total); }
-
-    // `tile`: first item of the tile (what first_tile / next_tile returned); `region`: the queue region this tile appends to
-    // (uniform over the workgroup; ORDERED keeps one region); counters[] point at region 0's words
-    NXD void alloc(const bool (&want)[K], int (&slot)[K], const int tile, const int region = 0)
-    {
-        const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-        const int nWaves = blockDim.x / kWave;
-        unsigned long long mask[K];
-        __syncthreads();  // the previous tile's readers are done with sWave / sBase
-#pragma unroll
-        for (int k = 0; k < K; k++) {
-            mask[k] = __ballot(want[k]);
-            if (lane == 0) sWave[k * kMaxWavesPerBlock + wave] = __popcll(mask[k]);
-        }
-        __syncthreads();
-        if (ORDERED) {
-            if (wave < K) {  // (a workgroup has at least K waves: 256 threads, K <= 4)
-                const int total = wave_sum(lane < nWaves ? sWave[wave * kMaxWavesPerBlock + lane] : 0);
-                const int t = tile / (int)blockDim.x;
-                const int excl = look_back(wave, t, total);
-                if (lane == 0) {
-                    sBase[wave] = excl;
-                    if (t == lastTile) *counter_of(wave) = excl + total;
-                }
-            }
-        } else if (threadIdx.x < K) {
-            int total = 0;
-            for (int w = 0; w < nWaves; w++) total += sWave[threadIdx.x * kMaxWavesPerBlock + w];
-            int* const word = counter_of((int)threadIdx.x) + region * kRegionStride;
-            sBase[threadIdx.x] = total ? atomicAdd(word, total) : 0;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < K; k++) {
-            slot[k] = -1;
-            if (want[k]) {
-                int prefix = 0;
-                for (int w = 0; w < wave; w++) prefix += sWave[k * kMaxWavesPerBlock + w];
-                slot[k] = sBase[k] + prefix + __popcll(mask[k] & ((1ull << lane) - 1ull));
-            }
-        }
-    }
-};
-
-// The same allocator for tiles of U sub-tiles (the logic kernel: two items per thread; the material kernels keep SlotAllocator above,
-// whose register allocation the generalised text disturbed: 18-21 -> 19-35 spilled VGPRs).  U: sub-tiles per tile.  A tile is U * blockDim.x consecutive items, thread t handles items t, t + blockDim.x, ... of it; the
-// slots of sub-tile u lie in front of those of sub-tile u + 1 (ascending item index, as ORDERED needs).  One ticket, one look-back
-// and one atomic per queue cover the whole tile: what a tile costs beside its items is paid once per U * blockDim.x of them.
-template <bool ORDERED, int K, int U>
-struct TileAllocator {
-    int* sWave;  // [U * K][kMaxWavesPerBlock] per-wave counts of the current tile
-    int* sBase;  // [U * K] base slot of the current tile's sub-tile u in queue k
-    int* sTile;  // ORDERED: the ticket of the current tile
-    int* counter0;  // the K counter words are counter0 + k * counterStep (an address computation, not an array of pointers: an
-    int counterStep;  // array indexed by anything but a constant makes the allocator a private-memory object in LDS or scratch)
-    NX_G unsigned long long* status;  // ORDERED: tile status words, [tile][kScanWords]
-    NX_G int* ticket;
-    NX_G FrameState* frame;
-    uint32_t serial;
-    int size, lastTile, tileItems;
-
-    // `kind`: 0 logic, 1 + NX_MAT_* material kernel; `items`: size of the launch's input queue
-    NXD void init(const DeviceState* S, int* const first, const int step, const int kind, const int bounce, const int items, NX_G int* const ticketWord = nullptr)
-    {
-        __shared__ int wave[U * K * kMaxWavesPerBlock];
-        __shared__ int base[U * K];
-        __shared__ int tile;
-        sWave = wave;
-        sBase = base;
-        sTile = &tile;
-        counter0 = first;
-        counterStep = step;
-        size = items;
-        tileItems = U * (int)blockDim.x;
-        lastTile = (items + tileItems - 1) / tileItems - 1;
-        if (ORDERED) {
-            status = S->scanStatus;
-            ticket = ticketWord ? ticketWord : &S->counters->scanTicket[kind][bounce];
-            frame = S->frame;
-            serial = S->frame->scanEpoch * 1024u + (uint32_t)bounce * 8u + (uint32_t)kind;
-        }
-    }
-    NXD int* counter_of(const int k) const
-    {
-        return counter0 + k * counterStep;
-    }
-    // first item of the workgroup's first / next tile (>= size: none left)
-    NXD int first_tile() { return ORDERED ? take() : (int)blockIdx.x * tileItems; }
-    NXD int next_tile(const int tile) { return ORDERED ? take() : tile + (int)gridDim.x * tileItems; }
-    NXD int take()
-    {
-        __syncthreads();  // the previous tile's readers are done with sTile
-        if (threadIdx.x == 0) *sTile = atomicAdd(ticket, 1);
-        __syncthreads();
-        const int t = *sTile;
-        return t > lastTile ? size : t * tileItems;
-    }
-
-    NXD int look_back(const int k, const int t, const int total) { return scan_look_back(status + k, counter_of(k), frame, serial, t, total); }
-
-    // `tile`: first item of the tile (what first_tile / next_tile returned); `region`: the queue region this tile appends to
-    // (uniform over the workgroup; ORDERED keeps one region); counters[] point at region 0's words.  want[u][k]: this thread's
-    // item of sub-tile u goes to queue k.
-    NXD void alloc(const bool (&want)[U][K], int (&slot)[U][K], const int tile, const int region = 0)
-    {
-        const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-        const int nWaves = blockDim.x / kWave;
-        unsigned long long mask[U][K];
-        __syncthreads();  // the previous tile's readers are done with sWave / sBase
-#pragma unroll
-        for (int u = 0; u < U; u++)
-#pragma unroll
-            for (int k = 0; k < K; k++) {
-                mask[u][k] = __ballot(want[u][k]);
-                if (lane == 0) sWave[(u * K + k) * kMaxWavesPerBlock + wave] = __popcll(mask[u][k]);
-            }
-        __syncthreads();
-        if (ORDERED) {
-            if (wave < K) {  // (a workgroup has at least K waves: 256 threads, K <= 4)
-                int subTotal[U], total = 0;
-#pragma unroll
-                for (int u = 0; u < U; u++) {
-                    subTotal[u] = wave_sum(lane < nWaves ? sWave[(u * K + wave) * kMaxWavesPerBlock + lane] : 0);
-                    total += subTotal[u];
-                }
-                const int t = tile / tileItems;
-                const int excl = look_back(wave, t, total);
-                if (lane == 0) {
-                    int run = excl;
-#pragma unroll
-                    for (int u = 0; u < U; u++) {
-                        sBase[u * K + wave] = run;
-                        run += subTotal[u];
-                    }
-                    if (t == lastTile) *counter_of(wave) = excl + total;
-                }
-            }
-        } else if (threadIdx.x < K) {
-            int subTotal[U], total = 0;
-#pragma unroll
-            for (int u = 0; u < U; u++) {
-                subTotal[u] = 0;
-                for (int w = 0; w < nWaves; w++) subTotal[u] += sWave[(u * K + (int)threadIdx.x) * kMaxWavesPerBlock + w];
-                total += subTotal[u];
-            }
-            int* const word = counter_of((int)threadIdx.x) + region * kRegionStride;
-            int run = total ? atomicAdd(word, total) : 0;
-#pragma unroll
-            for (int u = 0; u < U; u++) {
-                sBase[u * K + (int)threadIdx.x] = run;
-                run += subTotal[u];
-            }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int u = 0; u < U; u++)
-#pragma unroll
-            for (int k = 0; k < K; k++) {
-                slot[u][k] = -1;
-                if (want[u][k]) {
-                    int prefix = 0;
-                    for (int w = 0; w < wave; w++) prefix += sWave[(u * K + k) * kMaxWavesPerBlock + w];
-                    slot[u][k] = sBase[u * K + k] + prefix + __popcll(mask[u][k] & ((1ull << lane) - 1ull));
-                }
-            }
-    }
-};
-
-NXD uint32_t global_pixel(const DeviceState* S, uint32_t local) { return S->pixelMap ? S->pixelMap[local] : local; }
-
-// frame number and local pixel of a path; frameLast = number of the last frame of the current pass
-struct PathId { uint32_t frame, pixel; };
-NXD PathId path_id(const DeviceState* S, uint32_t pathIdx, uint32_t frameLast)
-{
-    const uint32_t slice = S->framesPerPass > 1u ? pathIdx / S->localCount : 0u;
-    return PathId{frameLast - (S->framesPerPass - 1u) + slice, pathIdx - slice * S->localCount};
-}
-
-NXD uint32_t seed_for(const DeviceState* S, uint32_t slot, uint32_t pathIdx, uint32_t bounce, uint32_t stage, uint32_t frameLast)
-{
-    const PathId id = path_id(S, pathIdx, frameLast);
-    if (S->rngMode == NX_RNG_PIXEL_KEYED) return rng_init_keyed(global_pixel(S, id.pixel), bounce, id.frame, stage);
-    return rng_init_index(slot, S->camera.resolution[0], id.frame);
-}
 
 // ------------------------------------------------------------------------------------------------------
 // begin pass: the pass size (frames batched into this pass) and the number of its last frame arrive as kernel arguments and
@@ -365,7 +20,6 @@ NXD uint32_t seed_for(const DeviceState* S, uint32_t slot, uint32_t pathIdx, uin
 // every counter, traceSize[0] = localCount * frames (GenerateKernel's thread 0 in the reference, PathTracer.cu:112-113; the
 // memset of PathTracer.cpp:263; the frame counter of PathTracer.cpp:250).
 
-#ifndef NX_WAVEFRONT_INSTANCES_ONLY
 __global__ void __launch_bounds__(kWideBlock) begin_frame_kernel(DeviceState* __restrict__ S, const uint32_t frames, const uint32_t frameLast, const uint32_t scanEpoch)
 {
     int* c = reinterpret_cast<int*>(S->counters);
@@ -443,919 +97,9 @@ __global__ void __launch_bounds__(kWideBlock) generate_kernel(const DeviceState*
     }
 }
 
-#endif  // NX_WAVEFRONT_INSTANCES_ONLY
-
-// ------------------------------------------------------------------------------------------------------
-// SampleBackground — PathTracer.cu:65-83
-
-// (u, v) of a direction on the latitude / longitude map — PathTracer.cu:65-83.  Computed ONCE per direction and handed to the
-// colour lookup and to the sampler's density lookup alike: the arc functions are the expensive part (include/nexus_fmath.h
-// evaluates them in binary64), and a miss under environment sampling needs both lookups for the same direction.
-struct EnvUv { float u, v; };
-NXD EnvUv env_uv(f3 d)
-{
-    const float theta = nxf_atan2f(d.z, d.x);
-    const float phi = nxf_asinf(d.y);
-    return EnvUv{(float)((theta + kPiD) * kInvPi * 0.5), (float)(1.0f - (phi + kPiD * 0.5f) * kInvPi)};
-}
-// kFloat = false: an instance that never runs under a map (the two-item logic kernel) leaves the float lookup out and keeps its code
-template <bool kFloat = true>
-NXD f3 env_colour(const DeviceState* S, EnvUv uv)
-{
-    if (kFloat && S->envFloat) {  // (wave-uniform: a float map, linear radiance — nx_texture.h tex2d_float)
-        const float4 c = tex2d_float(S->envFloat, (int)S->hdrMap.width, (int)S->hdrMap.height, uv.u, uv.v);
-        return mk3(c.x, c.y, c.z);
-    }
-    const float4 c = tex2d(S->hdrMap, S->srgbLut, uv.u, uv.v);
-    return mk3(c.x, c.y, c.z);
-}
-template <bool kFloat = true>
-NXD f3 sample_background(const DeviceState* S, f3 d)
-{
-    if (S->hdrMap.texels) return env_colour<kFloat>(S, env_uv(d));
-    return ld3(S->settings.backgroundColor) * S->settings.backgroundIntensity;
-}
-
-// ------------------------------------------------------------------------------------------------------
-// Environment importance sampling — an extension (the reference adds the environment on a miss only, PathTracer.cu:152-164,
-// so an HDR map with a small bright sun converges very slowly): the NEE may pick the environment as one more light and
-// draws its direction from the map's luminance distribution; a BSDF-sampled ray that misses is MIS-weighted against it.
-
-// the texel (u, v) falls in
-NXD uint32_t env_texel(const DeviceState* S, EnvUv uv)
-{
-    const int W = (int)S->hdrMap.width, H = (int)S->hdrMap.height;
-    const int x = min(max((int)(uv.u * (float)W), 0), W - 1), y = min(max((int)(uv.v * (float)H), 0), H - 1);
-    return (uint32_t)y * (uint32_t)W + (uint32_t)x;
-}
-
-// pdf per solid angle of the environment sampler for the unit direction d whose map coordinates are uv (light-selection
-// probability excluded)
-NXD float env_pdf(const DeviceState* S, f3 d, EnvUv uv)
-{
-    const float cosLat = sqrtf(fmaxf(1.0f - d.y * d.y, 1.0e-12f));
-    return S->envDensity[env_texel(S, uv)] / cosLat;
-}
-
-// first index whose cdf exceeds r (n - 1 when none does).  `guide` brackets the answer: entry b is the first index whose cdf
-// exceeds b / kEnvGuide, r lies in bucket floor(r * kEnvGuide), so the search starts from [guide[b], guide[b + 1]] instead
-// of [0, n - 1] — the same index after 2-5 dependent loads instead of 10-11.
-NXD int cdf_find(const NX_G float* cdf, const NX_G uint32_t* guide, int n, float r)
-{
-    const int b = min(kEnvGuide - 1, max(0, (int)(r * (float)kEnvGuide)));
-    int lo = (int)guide[b], hi = min(n - 1, (int)guide[b + 1]);
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (cdf[mid] > r) hi = mid;
-        else lo = mid + 1;
-    }
-    return lo;
-}
-
-// The sampler in two steps, so that the test hook (env_hook_kernel) can say which texel the inversion PICKED: the inversion of
-// the two cdfs — row y from r1, column x of that row from r2, and the map coordinates (u, v) inside that texel — ...
-struct EnvPick { int x, y; float u, v; };
-NXD EnvPick env_invert(const DeviceState* S, float r1, float r2)
-{
-    const int W = (int)S->hdrMap.width, H = (int)S->hdrMap.height;
-    const int y = cdf_find(S->envMarginalCdf, S->envMarginalGuide, H, r1);
-    const float ylo = y ? S->envMarginalCdf[y - 1] : 0.0f;
-    const float fy = (r1 - ylo) / (S->envMarginalCdf[y] - ylo);
-    const NX_G float* row = S->envRowCdf + (size_t)y * (size_t)W;
-    const int x = cdf_find(row, S->envRowGuide + (size_t)y * (size_t)(kEnvGuide + 1), W, r2);
-    const float xlo = x ? row[x - 1] : 0.0f;
-    const float fx = (r2 - xlo) / (row[x] - xlo);
-    return EnvPick{x, y, ((float)x + fx) / (float)W, ((float)y + fy) / (float)H};
-}
-// ... and the direction of map coordinates (u, v)
-NXD f3 env_direction(float u, float v)
-{
-    const float phi = (1.0f - v) * 3.14159265f - 1.57079633f, theta = u * 6.28318531f - 3.14159265f;
-    const float c = nxf_cosf(phi);
-    return mk3(c * nxf_cosf(theta), nxf_sinf(phi), c * nxf_sinf(theta));
-}
-NXD f3 env_sample(const DeviceState* S, float r1, float r2)
-{
-    const EnvPick p = env_invert(S, r1, r2);
-    return env_direction(p.u, p.v);
-}
-
-// lights the NEE chooses among: the mesh lights, plus the environment when it is importance sampled
-// (ANALYTIC: ... and the analytic lights between the two — only the instances of contexts that have some read their count)
-template <unsigned F = 0u>  // (a set of kMf* bits: nx_variants.h)
-NXD uint32_t nee_light_count(const DeviceState* S)
-{
-    constexpr bool ANALYTIC = (F & kMfAnalytic) != 0u;
-    if constexpr (ANALYTIC) return S->lightCount + S->alightCount + ((S->envSampling && S->hdrMap.texels) ? 1u : 0u);
-    else return S->lightCount + ((S->envSampling && S->hdrMap.texels) ? 1u : 0u);
-}
-
-// ------------------------------------------------------------------------------------------------------
-// LogicKernel — PathTracer.cu:136-210
-
-// LogicKernel's decision for one path (PathTracer.cu:136-210), without the queue traffic: a miss ends the path and adds the
-// (MIS-weighted) environment `bg`; a hit survives Russian roulette with probability max(throughput) — `survived`, the
-// throughput divided by it in `throughputOut` — and is shaded as the returned material type, or ends (-1).
-// METAL: the instances of a context with an NX_MAT_METALROUGH material (kFlavorMetal) — the fifth type is one a path may be shaded as
-template <bool kEnvFloat = true, unsigned F = 0u, class HitInst>
-NXD int logic_path(const DeviceState* S, const int bounce, const uint32_t frame, const uint32_t seedSlot, const uint32_t pixelIdx, const float hitT, const f3 dir,
-                   const float4 tp, HitInst hitInst, bool& miss, f3& bg, bool& survived, f3& throughputOut, uint32_t& inst, bool& needsPrevVertex)
-{
-    constexpr bool METAL = (F & kMfMetal) != 0u;  // (ANALYTIC: nee_light_count reads it)
-    needsPrevVertex = false;
-    const f3 throughput = mk3(tp.x, tp.y, tp.z);
-    int type = -1;
-    miss = false;
-    survived = false;
-    if (hitT == 1e30f) {
-        miss = true;
-        EnvUv uv{0.0f, 0.0f};
-        if (S->hdrMap.texels) {
-            uv = env_uv(dir);
-            bg = throughput * env_colour<kEnvFloat>(S, uv);
-        } else {
-            bg = throughput * sample_background<kEnvFloat>(S, dir);
-        }
-        if (S->envSampling && S->hdrMap.texels && bounce > 1 && S->settings.useMIS) {
-            // the NEE samples the environment too: weight the BSDF-sampled miss against it (extension)
-            const float envPdf = env_pdf(S, dir, uv) / (float)nee_light_count<F>(S);
-            if (pdf_valid(envPdf)) bg = bg * power_heuristic(tp.w, envPdf);
-        }
-    } else {
-        uint32_t rng = seed_for(S, seedSlot, pixelIdx, (uint32_t)bounce, 0u, frame);
-        const float probability = maxcomp3(throughput);
-        if (rng_next(rng) < probability) {
-            survived = true;
-            throughputOut = throughput / probability;
-            inst = hitInst();
-            // type and, behind it, the flag nxhip_set_materials derived: the material can emit (an emissive hit weighs itself
-            // against the light sampler by the distance from the path's previous vertex) or let a path pass through (which
-            // keeps the path state, PathTracer.cu:372-386) — see keep_previous_vertex below.  Read from the instance's shading
-            // record (one dependent load; the reference's instance -> material is two)
-            const uint32_t typeAndFlag = *(const NX_G uint32_t*)((const NX_G char*)&S->shadeInst[inst].material + kMaterialTypeOffset);
-            type = (int)(int8_t)(typeAndFlag & 0xffu);
-            if (type < 0 || type > (METAL ? NX_MAT_METALROUGH : NX_MAT_CONDUCTOR)) type = -1;
-            needsPrevVertex = ((typeAndFlag >> 8) & 1u) != 0u;
-        }
-    }
-    return type;
-}
-
-// The previous vertex of a path (D_PathStateSOA::rayOrigin, PathTracer.cuh:19-30) is the origin of its last SAMPLED ray.  The
-// material kernels used to store it per path and bounce (a scattered 16-byte store each: 7 % of their time) although it is
-// read only by the rare emissive hit under MIS.  Now the logic step stores it, and only for hits that can need it: the
-// origin of the ray that produced the hit — unless that ray was a pass-through continuation (flagged in the ray's w), whose
-// predecessor hit a pass-through-capable material and therefore stored the right vertex itself.  Same values as before.
-NXD void keep_previous_vertex(const DeviceState* S, const uint32_t pixelIdx, const float4 rayOrigin)
-{
-    if ((__float_as_uint(rayOrigin.w) & kRayPassThrough) == 0u) S->rayOrigin[pixelIdx] = make_float4(rayOrigin.x, rayOrigin.y, rayOrigin.z, 0.0f);
-}
-
-template <bool ORDERED, int U, unsigned F = 0u>  // (F: ANALYTIC alone — the weighted miss counts the analytic lights: nee_light_count)
-// 8 waves per SIMD (60 VGPRs, no spills): two of the 1024-thread workgroups fit a CU instead of one, so the barriers of the
-// slot allocation in one overlap with the streaming of the other (logic kernel -16 %, bench +1 %)
-#ifndef NX_LOGIC_WAVES
-#define NX_LOGIC_WAVES 8
-#endif
-__global__ void __launch_bounds__(kLogicBlock, NX_LOGIC_WAVES) logic_kernel(const DeviceState* __restrict__ S, const int bounce)
-{
-    static_assert((F & ~kMfLogicReads) == 0u, "logic_kernel reads ANALYTIC alone");
-    // U items per thread: a tile is U * 1 024 items behind ONE round of slot allocation
-    Counters* C = S->counters;
-    const QueueView in = queue_view(&C->region[0].traceSize[bounce - 1], S->queueShardCap);
-    const int size = in.total;
-    // the grid is sized for the largest queue: a workgroup with no tile to process leaves before the allocator's
-    // barriers (late bounces carry a few thousand items; an all-empty launch used to cost 30 us)
-    if ((int)(blockIdx.x * blockDim.x) * U >= size) return;
-    const uint32_t frame = S->frame->frameNumber;
-    TileAllocator<ORDERED, 4, U> slots;
-    // queue k of this kernel: the material queue of type k
-    slots.init(S, &C->region[0].materialSize[0][bounce], kMaxBounceSlots, 0, bounce, size);
-    const ProducerRegions out = producer_regions(S, size, U * (int)blockDim.x);
-    for (int tile = slots.first_tile(); tile < size; tile = slots.next_tile(tile)) {
-        int type[U];
-        float4 hit[U], dirPix[U], tpOut[U];
-        uint32_t inst[U], pixelIdx[U];
-        bool want[U][4];
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            const int index = tile + u * (int)blockDim.x + (int)threadIdx.x;
-            type[u] = -1;
-            hit[u] = make_float4(0, 0, 0, 0); dirPix[u] = make_float4(0, 0, 0, 0); tpOut[u] = make_float4(0, 0, 0, 0);
-            inst[u] = 0; pixelIdx[u] = 0;
-            if (index < size) {
-                const int at = in.slot(index);  // where item `index` of the trace queue lives
-                hit[u] = S->trace.hit[at];
-                dirPix[u] = S->trace.rays[0].rayD[at];
-                pixelIdx[u] = __float_as_uint(dirPix[u].w);
-                const float4 tp = bounce == 1 ? make_float4(1.0f, 1.0f, 1.0f, 1.0e10f) : S->trace.rays[0].tp[at];
-                // the hit's instance is loaded with the rest of the entry, not behind the roulette decision that first needs it: a
-                // load inside the branch is one more dependent round trip per tile for the paths that survive (4 B per item more for
-                // those that do not; logic kernel -4 %)
-                const uint32_t hitInstance = S->trace.hitInst[at];
-                bool miss, survived, needsPrevVertex;
-                f3 bg = mk3(0.0f), t = mk3(0.0f);
-                // (U > 1: the instance of scenes without an environment map — wavefront::logic — whose misses never reach a map lookup)
-                type[u] = logic_path<U == 1, F>(S, bounce, frame, (uint32_t)index, pixelIdx[u], hit[u].x, mk3(dirPix[u].x, dirPix[u].y, dirPix[u].z), tp, [&]() { return hitInstance; }, miss, bg, survived, t,
-                                     inst[u], needsPrevVertex);
-                if (needsPrevVertex) keep_previous_vertex(S, pixelIdx[u], S->trace.rays[0].rayO[at]);
-                if (miss) {
-                    // A background contribution of exactly +0 in all three components (a black environment: the reference's default
-                    // backgroundIntensity 0) leaves the pixel's radiance as it is — generate_kernel zeroed it, later additions never
-                    // produce a negative zero from non-negative emission — so the scattered 16-byte read-modify-write is skipped:
-                    // it was a third of this kernel's memory traffic on such scenes.  (Anything else, -0 included, is added.)
-                    if ((__float_as_uint(bg.x) | __float_as_uint(bg.y) | __float_as_uint(bg.z)) != 0u) {
-                        float4 r = bounce == 1 ? make_float4(0, 0, 0, 0) : S->radiance[pixelIdx[u]];
-                        r.x += bg.x; r.y += bg.y; r.z += bg.z;
-                        if (bounce == 1) r = make_float4(bg.x, bg.y, bg.z, 0.0f);
-                        S->radiance[pixelIdx[u]] = r;
-                    }
-                    if (bounce == 1 && pixelIdx[u] < S->localCount && S->frame->pixelQueryPixel == (int)global_pixel(S, pixelIdx[u])) S->frame->pixelQueryInstance = -1;
-                }
-                // (at bounce 1 every hit survives with throughput 1 and the material kernels use that constant instead of reading
-                //  it back)
-                if (survived) tpOut[u] = make_float4(t.x, t.y, t.z, tp.w);
-            }
-#pragma unroll
-            for (int k = 0; k < 4; k++) want[u][k] = type[u] == k;
-        }
-        int slot[U][4];
-        const int region = out.of_tile(tile), regionBase = region * (int)S->queueShardCap;
-        slots.alloc(want, slot, tile, region);
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            if (type[u] >= 0) {
-                const MaterialQueue mq = S->material[type[u]];
-                const int sl = regionBase + (type[u] == 0 ? slot[u][0] : (type[u] == 1 ? slot[u][1] : (type[u] == 2 ? slot[u][2] : slot[u][3])));
-                // the hit distance is of no use to the material kernels (they work from u, v): its slot carries the path index,
-                // which saves a third array (4 B written and read per path, one load and one store instruction each)
-                mq.hit[sl] = make_float4(__uint_as_float(pixelIdx[u]), hit[u].y, hit[u].z, hit[u].w);
-                mq.dirInst[sl] = make_float4(dirPix[u].x, dirPix[u].y, dirPix[u].z, __uint_as_float(inst[u]));
-                if (bounce != 1) mq.tp[sl] = tpOut[u];  // the path's throughput after Russian roulette and its last pdf go with it
-            }
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------------------------
-// Shade<BSDF> + NextEventEstimation<BSDF> — PathTracer.cu:311-458, 213-308
-
-NXD MatParams load_params(const nx_material& m)
-{
-    MatParams p;
-    p.albedo = ld3(m.diffuse.albedo);
-    p.roughness = (m.type == NX_MAT_CONDUCTOR) ? m.conductor.roughness : m.plastic.roughness;
-    p.ior = m.plastic.ior;
-    p.cIor = ld3(m.conductor.ior);
-    p.cK = ld3(m.conductor.k);
-    p.metallic = m.metalrough.metallic;
-    return p;
-}
-
-struct ShadowPayload {
-    f3 origin, direction, radiance;
-    float distance;
-};
-
-// POWER (nxhip_set_light_sampling, NXHIP_LIGHTS_POWER): the triangle of the mesh-light sample comes from the light table (nx_lights.h) —
-// every emissive triangle of every mesh light in proportion to area x emitted luminance — with ONE random number in place of
-// the uniform triangle index, so a path draws as many numbers as in the default mode.  A template parameter, not a run-time
-// branch: the default mode's kernels are the instances with POWER = false, whose code does not change.
-// NO_MAPS (the SCAN pipeline's material launch only: shade_scan_kernel): no material of the context names a diffuse or an emissive
-// map (the host knows: kFlavorNoMaps, pass_flavor in nxhip_render.hip), so the lookups, the texture coordinates they need and the alpha
-// pass-through draw — made only behind `diffuseMapId != -1` — are not compiled in.  No arithmetic of an executed path changes.
-// Such a context has no environment map either (pass_flavor), so the instance leaves the float map's lookup out as well.
-// ANALYTIC (nxhip_set_analytic_lights with count > 0: kFlavorAnalytic): the pick is among mesh lights, then analytic lights, then the
-// environment; an analytic pick draws its direction from the cone the light subtends (nx_alights.h alight_sample) and carries no MIS
-// weight — no other ray can find such a light.  With useMIS off the sample is taken among the analytic lights alone.  The instances
-// with ANALYTIC = false are the code of a context without such lights.
-// TREE (nxhip_set_light_importance, NXHIP_LIGHT_IMPORTANCE_POSITION, in POWER mode: kFlavorLightTree): the entry comes from the light tree's
-// descent at hitPoint (nx_lights.h light_tree_pick) with the same ONE random number, and its probability stands where the table's
-// did.  The POWER instances without it keep their text.
-template <int TYPE, unsigned F>
-NXD bool next_event_estimation(const DeviceState* S, f3 wi, const MatParams& mp, f3 hitPoint, f3 normal, f3 hitGNormal, f3 throughput,
-                               uint32_t& rng, ShadowPayload& out)
-{
-    constexpr bool POWER = (F & kMfPower) != 0u, NO_MAPS = (F & kMfNoMaps) != 0u, ANALYTIC = (F & kMfAnalytic) != 0u, TREE = (F & kMfTree) != 0u;
-    // no lights: the reference indexes an empty array here (undefined); defined as "no light sample, no random numbers
-    // drawn", identically in the CPU restatement used by the tests
-    uint32_t nLights = nee_light_count<F>(S);
-    uint32_t firstPick = 0u;
-    if constexpr (ANALYTIC) {
-        if (S->settings.useMIS == 0) { nLights = S->alightCount; firstPick = S->lightCount; }  // (nothing else can find them)
-    }
-    if (nLights == 0u) return false;
-    const uint32_t pick = firstPick + uniform_index(nLights, rng);
-    if constexpr (ANALYTIC) {
-        if (pick >= S->lightCount && pick - S->lightCount < S->alightCount) {
-            const NX_G ALight* L = &S->alights[pick - S->lightCount];
-            const float r1 = rng_next(rng), r2 = rng_next(rng);  // (two numbers whatever the kind)
-            // the origin goes to the light's side of the surface, as the environment branch's does: by the direction to the centre
-            const float4 l0 = L->v0, l1 = L->v1, l2 = L->v2;
-            const f3 toLight = l2.w != 0.0f ? -mk3(l1.x, l1.y, l1.z) : mk3(l0.x, l0.y, l0.z) - hitPoint;
-            out.origin = offset_ray(hitPoint, hitGNormal * sgnE(dot3(toLight, normal)));
-            f3 factor;
-            if (!alight_sample(L, out.origin, r1, r2, out.direction, out.distance, factor)) return false;
-            const float4 q = rotation_to_z(normal);
-            const f3 wo = rotate_point(q, out.direction);
-            f3 sampleThroughput;
-            float bsdfPdf;
-            if (!Bsdf<TYPE>::eval(mp, wi, wo, sampleThroughput, bsdfPdf)) return false;
-            out.radiance = ((throughput * sampleThroughput) * factor) * (float)nLights;
-            return true;
-        }
-    }
-    if (pick >= S->lightCount) {
-        // the environment (extension): direction from the map's luminance distribution, shadow ray to infinity
-        const float r1 = rng_next(rng), r2 = rng_next(rng);
-        const f3 shDir = env_sample(S, r1, r2);
-        // (the BSDF first: a direction it rejects — most of them on a near-specular surface — needs no density lookup)
-        const float4 q = rotation_to_z(normal);
-        const f3 wo = rotate_point(q, shDir);
-        f3 sampleThroughput;
-        float bsdfPdf;
-        if (!Bsdf<TYPE>::eval(mp, wi, wo, sampleThroughput, bsdfPdf)) return false;
-        const EnvUv uv = env_uv(shDir);
-        const float lightPdf = env_pdf(S, shDir, uv) / (float)nLights;
-        if (!pdf_valid(lightPdf)) return false;
-        const float weight = power_heuristic(lightPdf, bsdfPdf);
-        out.radiance = (((throughput * weight) * sampleThroughput) * env_colour<!NO_MAPS>(S, uv)) / lightPdf;
-        out.origin = offset_ray(hitPoint, hitGNormal * sgnE(dot3(shDir, normal)));
-        out.direction = shDir;
-        out.distance = 1e30f;
-        return true;
-    }
-    uint32_t meshId, triangleIdx, lightTriCount = 0u;
-    float pickProb = 0.0f;  // POWER: the table's probability of the entry
-    if constexpr (POWER) {
-        // (the uniform pick above only decided "a mesh light": which one, and which triangle, is the table's choice)
-        if (S->lightHeader->valid == 0u) return false;  // nothing emits: no light sample, no number drawn
-        if constexpr (TREE) {
-            uint32_t entry;
-            if (!light_tree_pick(S->lightTree, S->lightTreeLeaves, hitPoint, rng_next(rng), entry, pickProb)) return false;  // (no further number is drawn)
-            const uint32_t light = light_entry(S->lightTable, entry).light;
-            meshId = S->lights[light].mesh.meshId;
-            triangleIdx = entry - S->lightBase[light];
-        } else {
-            const LightPick lp = light_pick(S->lightTable, S->lightGuide, S->lightGuideSize, S->lightEntries, rng_next(rng));
-            meshId = S->lights[lp.light].mesh.meshId;
-            triangleIdx = lp.entry - S->lightBase[lp.light];
-            pickProb = lp.prob;
-        }
-    } else {
-        const nx_light light = S->lights[pick];
-        if (light.type != NX_LIGHT_MESH) return false;
-        meshId = light.mesh.meshId;
-    }
-    // the light's instance: its shading record (transform, triangles, material behind one load)
-    const NX_G ShadeInst* inst = &S->shadeInst[meshId];
-    if constexpr (!POWER) {
-        lightTriCount = inst->triCount;
-        triangleIdx = uniform_index(lightTriCount, rng);
-    }
-    const f2 uv = uniform_triangle(rng);
-    const NX_G nx_triangle* tri = shade_tri(inst->tris, triangleIdx);
-    const f3 tp0 = ld3(tri->pos0), tp1 = ld3(tri->pos1), tp2 = ld3(tri->pos2);
-    const NX_G float* T = inst->transform;
-    const NX_G float* IT = inst->invTransform;
-
-    f3 p = mat_point(T, bary3(tp0, tp1, tp2, uv.x, uv.y));
-    const f3 lightGNormal = normalize3(mat_vec_transposed(IT, cross3(tp1 - tp0, tp2 - tp0)));
-    const f3 lightNormal = normalize3(mat_vec_transposed(IT, bary3(ld3(tri->normal0), ld3(tri->normal1), ld3(tri->normal2), uv.x, uv.y)));
-
-    f3 toLight = p - hitPoint;
-    float offsetDirection = sgnE(dot3(toLight, normal));
-    out.origin = offset_ray(hitPoint, hitGNormal * offsetDirection);
-    offsetDirection = sgnE(dot3(-toLight, lightNormal));
-    p = offset_ray(p, lightGNormal * offsetDirection);
-
-    toLight = p - out.origin;
-    out.distance = length3(toLight);
-    out.direction = toLight / out.distance;
-
-    const float4 q = rotation_to_z(normal);
-    const f3 wo = rotate_point(q, out.direction);
-    const float cosThetaO = fabsf(dot3(lightNormal, out.direction));
-    const float dSquared = dot3(toLight, toLight);
-    const float area = tri_area(mat_point(T, tp0), mat_point(T, tp1), mat_point(T, tp2));
-    float lightPdf;
-    if constexpr (POWER) lightPdf = (pickProb * ((float)S->lightCount / (float)nLights)) / area;  // (lightCount / nLights: the pick fell on a mesh light)
-    else lightPdf = 1.0f / ((float)(nLights * lightTriCount) * area);
-    lightPdf *= dSquared / cosThetaO;
-    if (!pdf_valid(lightPdf)) return false;
-
-    const NX_G nx_material* lightMaterial = &inst->material;
-    f3 sampleThroughput;
-    float bsdfPdf;
-    if (!Bsdf<TYPE>::eval(mp, wi, wo, sampleThroughput, bsdfPdf)) return false;
-    const float weight = power_heuristic(lightPdf, bsdfPdf);
-
-    f3 emissive;
-    if (!NO_MAPS && lightMaterial->emissiveMapId != -1) {
-        const f2 t = bary2(tri->texCoord0, tri->texCoord1, tri->texCoord2, uv.x, uv.y);
-        const float4 c = tex2d(S->emissiveMaps[lightMaterial->emissiveMapId], S->srgbLut, t.x, t.y);
-        emissive = mk3(c.x, c.y, c.z);
-    } else {
-        emissive = ld3(lightMaterial->emissive);
-    }
-    out.radiance = ((((throughput * weight) * sampleThroughput) * emissive) * lightMaterial->intensity) / lightPdf;
-    return true;
-}
-
-// Shade<BSDF> for one path (PathTracer.cu:311-458), without the queue traffic: shade_kernel wraps it with the material-queue
-// loads and the slot allocation, tail_kernel calls it in its per-path loop.  prevOrigin() returns the path's previous vertex
-// (only read for an emissive hit under MIS).  emit(radiance, instance) receives what the hit emits towards the path; what comes out: the shadow ray of its
-// light sample, the continuation ray and the path state that goes with it.  (Separate references, not a struct: the
-// compiler kept a struct of these in scratch memory, +30 % on the material kernels.)
-// DETAIL (nxhip_set_material_detail with a material that names a normal or a roughness map: kFlavorDetail): the roughness map scales the
-// BSDF's roughness and the normal map's shading normal ns (nx_detail.h: the rule is stated in include/nexus_hip.h) takes the place of the
-// interpolated normal in the frame, in the light sample and in the offset signs; the emissive hit's MIS weight keeps the interpolated
-// normal.  The instances with DETAIL = false are the code of a context without such maps.
-// SOLID (nxhip_set_material_alpha with a material that is NX_ALPHA_MASK or NX_ALPHA_OPAQUE): a hit on an instance whose alphaMode is not
-// NX_ALPHA_BLEND never passes through.  The random numbers of the pass-through test are drawn as ever, in the same order — only the outcome
-// is ignored — and the colour still comes from the map's rgb.  The one text of the rule: every SOLID instance (nx_wavefront_solid.hip) gets here.
-template <int TYPE, unsigned F, class PrevOrigin, class Emit>
-NXD void shade_path(const DeviceState* S, const int bounce, const uint32_t frame, const uint32_t seedSlot, const uint32_t pixelIdx, const float hu, const float hv,
-                    const uint32_t triIdx, const uint32_t instanceIdx, const f3 rayDirection, const float4 tpdf, PrevOrigin prevOrigin, Emit emit,
-                    bool& wantShadow, ShadowPayload& sh, bool& wantTrace, bool& updatePath, f3& nextOrigin, f3& nextDir, f3& nextThroughput, float& nextPdf)
-{
-    constexpr bool POWER = (F & kMfPower) != 0u, NO_MAPS = (F & kMfNoMaps) != 0u, ANALYTIC = (F & kMfAnalytic) != 0u, DETAIL = (F & kMfDetail) != 0u, SOLID = (F & kMfSolid) != 0u;
-    constexpr bool TREE = (F & kMfTree) != 0u;
-    wantShadow = false; wantTrace = false; updatePath = false;
-    nextOrigin = mk3(0.0f); nextDir = mk3(0.0f); nextThroughput = mk3(0.0f);
-    nextPdf = 0.0f;
-    f3 throughput = mk3(tpdf.x, tpdf.y, tpdf.z);
-    uint32_t rng = seed_for(S, seedSlot, pixelIdx, (uint32_t)bounce, 1u, frame);
-
-    const NX_G ShadeInst* inst = &S->shadeInst[instanceIdx];
-    const NX_G nx_triangle* tri = shade_tri(inst->tris, triIdx);
-    const nx_material material = inst->material;
-    MatParams mp = load_params(material);
-    const NX_G float* T = inst->transform;
-    const NX_G float* IT = inst->invTransform;
-    const f3 tp0 = ld3(tri->pos0), tp1 = ld3(tri->pos1), tp2 = ld3(tri->pos2);
-
-    const f3 p = mat_point(T, bary3(tp0, tp1, tp2, hu, hv));
-    f3 normal = bary3(ld3(tri->normal0), ld3(tri->normal1), ld3(tri->normal2), hu, hv);
-    const f2 texUv = bary2(tri->texCoord0, tri->texCoord1, tri->texCoord2, hu, hv);
-    normal = normalize3(mat_vec_transposed(IT, normal));
-    f3 gNormal = normalize3(mat_vec_transposed(IT, cross3(tp1 - tp0, tp2 - tp0)));
-
-    f3 emissive = ld3(material.emissive);
-    if (!NO_MAPS && material.emissiveMapId != -1) {
-        const float4 c = tex2d(S->emissiveMaps[material.emissiveMapId], S->srgbLut, texUv.x, texUv.y);
-        emissive = mk3(c.x, c.y, c.z);
-    }
-    const bool useMIS = S->settings.useMIS != 0;
-    const bool allowMIS = bounce > 1 && useMIS;
-    f3 radiance = mk3(0.0f);
-    if (maxcomp3(emissive * material.intensity) > 0.0f) {
-        float weight = 1.0f;
-        if (allowMIS) {
-            const float lastPdf = tpdf.w;
-            const float cosThetaO = fabsf(dot3(normal, rayDirection));
-            const float4 ro = prevOrigin();
-            const float dSquared = squaref(length3(p - mk3(ro.x, ro.y, ro.z)));
-            const float area = tri_area(mat_point(T, tp0), mat_point(T, tp1), mat_point(T, tp2));
-            if constexpr (POWER) {
-                // the density the light sample has for this point: the table's probability of this very triangle.  An instance that
-                // is no light, or an entry of probability 0: the sampler cannot reach it, BSDF sampling carries all of it (weight 1)
-                float P = 0.0f;
-                const uint32_t l = S->instLight[instanceIdx];
-                if constexpr (TREE) {
-                    // (... the tree's probability of this triangle as seen from the previous vertex — the ray's origin, which offset_ray has
-                    //  moved off the surface the light sample stood on: include/nexus_hip.h states what that costs)
-                    if (l != kNotALight && S->lightHeader->valid != 0u)
-                        P = light_tree_prob(S->lightTree, S->lightTreeLeaves, mk3(ro.x, ro.y, ro.z), S->lightSlotOf[S->lightBase[l] + triIdx]);
-                } else {
-                    if (l != kNotALight && S->lightHeader->valid != 0u) P = light_entry_prob(S->lightTable, S->lightBase[l] + triIdx);
-                }
-                if (P > 0.0f) {
-                    float lightPdf = (P * ((float)S->lightCount / (float)nee_light_count<F>(S))) / area;
-                    lightPdf *= dSquared / cosThetaO;
-                    if (!pdf_valid(lightPdf)) weight = 0.0f;
-                    else weight = power_heuristic(lastPdf, lightPdf);
-                }
-            } else {
-                float lightPdf = 1.0f / ((float)(nee_light_count<F>(S) * inst->triCount) * area);
-                lightPdf *= dSquared / cosThetaO;
-                if (!pdf_valid(lightPdf)) weight = 0.0f;
-                else weight = power_heuristic(lastPdf, lightPdf);
-            }
-        }
-        radiance = ((emissive * weight) * material.intensity) * throughput;
-    }
-    emit(radiance, instanceIdx);  // (here, before the sampling code: the three values need not live across it)
-
-    if (bounce != (int)S->settings.pathLength) {
-        float4 color = make_float4(1.0f, 1.0f, 1.0f, 1.0f);
-        if (!NO_MAPS && material.diffuseMapId != -1) {
-            color = tex2d(S->diffuseMaps[material.diffuseMapId], S->srgbLut, texUv.x, texUv.y);
-            mp.albedo = mk3(color.x, color.y, color.z);
-        }
-        if constexpr (DETAIL) {
-            // (from here on `normal` IS the shading normal: the interpolated one is not read again, so only three registers cross the sampling code)
-            bool fellBack;
-            normal = detail_shading_frame<TYPE>(S, S->shadeDetail[instanceIdx], tri, T, tp0, tp1, tp2, texUv, rayDirection, normal, gNormal, mp.roughness, fellBack,
-                                                TYPE == NX_MAT_METALROUGH ? &mp.metallic : nullptr);
-        } else {
-            if (dot3(gNormal, rayDirection) > 0.0f && TYPE != NX_MAT_DIELECTRIC) { normal = -normal; gNormal = -gNormal; }
-        }
-
-        const float4 q = rotation_to_z(normal);
-        const f3 wi = rotate_point(q, -rayDirection);
-        f3 wo;
-        bool passThrough = rng_next(rng) > material.opacity || (!NO_MAPS && material.diffuseMapId != -1 && rng_next(rng) > color.w);
-        if constexpr (SOLID) {
-            if (inst->alphaMode != (uint32_t)NX_ALPHA_BLEND) passThrough = false;  // (the draws above stand)
-        }
-        if (passThrough) {
-            // texture / opacity pass-through: continue straight, path state untouched
-            wo = normalize3(rotate_point(invert_rotation(q), -wi));
-            const float od = sgnE(dot3(wo, normal));
-            nextOrigin = offset_ray(p, gNormal * od);
-            nextDir = wo;
-            wantTrace = true;
-        } else {
-            if (useMIS || ANALYTIC) wantShadow = next_event_estimation<TYPE, F>(S, wi, mp, p, normal, gNormal, throughput, rng, sh);
-            float pdf;
-            f3 sampleThroughput;
-            if (Bsdf<TYPE>::sample(mp, wi, rng, wo, sampleThroughput, pdf)) {
-                wo = normalize3(rotate_point(invert_rotation(q), wo));
-                const float od = sgnE(dot3(wo, normal));
-                nextOrigin = offset_ray(p, gNormal * od);
-                nextDir = wo;
-                nextThroughput = throughput * sampleThroughput;
-                nextPdf = pdf;
-                wantTrace = true;
-                updatePath = true;
-            }
-        }
-    }
-}
-
-// Workgroups of 256 at 5 waves per SIMD (96 VGPRs, 5-11 spilled once per path), 10 workgroups per CU: equal to 512 threads
-// at 4 waves (126 VGPRs) for one large pass, +4.5 % for one-frame passes in flight, where a smaller register footprint lets
-// the material kernels of one slot share SIMDs with the trace waves of another.  6 and 8 waves per SIMD spill 30-87 VGPRs and
-// double the kernel's time: it is sensitive to memory traffic, not short of waves.
-template <int TYPE, bool ORDERED, unsigned F>  // (F: POWER, ANALYTIC, DETAIL, SOLID — TYPE says what METAL would, and the pipeline has no NO_MAPS form)
-#ifndef NX_SHADE_WAVES
-#define NX_SHADE_WAVES 5
-#endif
-#ifndef NX_SHADE_WAVES_ORDERED
-#define NX_SHADE_WAVES_ORDERED 4
-#endif
-// (ordered: one 1 024-thread workgroup per CU is 4 waves per SIMD whatever the register budget says, so it may as well be 128)
-__global__ void __launch_bounds__(ORDERED ? kShadeBlockOrderedThreads : kShadeBlock, ORDERED ? NX_SHADE_WAVES_ORDERED : NX_SHADE_WAVES) shade_kernel(const DeviceState* __restrict__ S, const int bounce)
-{
-    static_assert(shade_set_ok(F, TYPE == NX_MAT_METALROUGH), "a set of material features shade_kernel has no instance for (nx_variants.h)");
-    Counters* C = S->counters;
-    // (NX_MAT_METALROUGH: the fifth queue, its size row and its ticket row are words of their own — nx_device.h)
-    constexpr bool kMetal = TYPE == NX_MAT_METALROUGH;
-    const QueueView in = queue_view(kMetal ? &C->region[0].materialSizeMetal[bounce] : &C->region[0].materialSize[kMetal ? 0 : TYPE][bounce], S->queueShardCap);
-    const int size = in.total;
-    if ((int)(blockIdx.x * blockDim.x) >= size) return;  // no tile for this workgroup (see logic_kernel)
-    const uint32_t frame = S->frame->frameNumber;
-    const MaterialQueue mq = kMetal ? S->materialMetal : S->material[kMetal ? 0 : TYPE];
-    SlotAllocator<ORDERED, 2> slots;  // 0: shadow requests, 1: continuation rays
-    static_assert(offsetof(RegionCounters, traceSize) + kMaxBounceSlots * sizeof(int32_t) == offsetof(RegionCounters, traceShadowSize), "traceShadowSize follows traceSize");
-    slots.init(S, &C->region[0].traceShadowSize[bounce], -kMaxBounceSlots, 1 + TYPE, bounce, size, kMetal ? &S->counters->region[0].scanTicketMetal[1][bounce] : nullptr);
-    const ProducerRegions out = producer_regions(S, size, (int)blockDim.x);
-    for (int tile = slots.first_tile(); tile < size; tile = slots.next_tile(tile)) {
-        const int requestIdx = tile + (int)threadIdx.x;
-        bool wantShadow = false, wantTrace = false, updatePath = false;
-        ShadowPayload sh;
-        f3 nextOrigin = mk3(0.0f), nextDir = mk3(0.0f), nextThroughput = mk3(0.0f);
-        float nextPdf = 0.0f;
-        uint32_t pixelIdx = 0;
-        float4 tpdf = make_float4(0, 0, 0, 0);
-
-        if (requestIdx < size) {
-            const int at = in.slot(requestIdx);
-            const float4 hit = mq.hit[at];
-            const float4 dirInst = mq.dirInst[at];
-            pixelIdx = __float_as_uint(hit.x);
-            const uint32_t instanceIdx = __float_as_uint(dirInst.w);
-            tpdf = bounce == 1 ? make_float4(1.0f, 1.0f, 1.0f, 1.0e10f) : mq.tp[at];
-            shade_path<TYPE, F>(S, bounce, frame, (uint32_t)requestIdx, pixelIdx, hit.y, hit.z, __float_as_uint(hit.w), instanceIdx, mk3(dirInst.x, dirInst.y, dirInst.z), tpdf,
-                             [&]() { return S->rayOrigin[pixelIdx]; },
-                             [&](f3 emitted, uint32_t instIdx) {
-                                 if (bounce == 1 && bounce != (int)S->settings.pathLength && pixelIdx < S->localCount && S->frame->pixelQueryPixel == (int)global_pixel(S, pixelIdx))
-                                     S->frame->pixelQueryInstance = (int)instIdx;
-                                 if (emitted.x != 0.0f || emitted.y != 0.0f || emitted.z != 0.0f) {
-                                     // (most hits emit nothing: adding zeros would cost a 16-byte read and write per path and bounce)
-                                     float4 r = S->radiance[pixelIdx];
-                                     r.x += emitted.x; r.y += emitted.y; r.z += emitted.z;
-                                     S->radiance[pixelIdx] = r;
-                                 }
-                             },
-                             wantShadow, sh, wantTrace, updatePath, nextOrigin, nextDir, nextThroughput, nextPdf);
-        }
-        const bool want[2] = {wantShadow, wantTrace};
-        int slot[2];
-        const int region = out.of_tile(tile), regionBase = region * (int)S->queueShardCap;
-        slots.alloc(want, slot, tile, region);
-        const int shadowSlot = regionBase + slot[0], traceSlot = regionBase + slot[1];
-        if (wantShadow) {
-            S->shadow.rayO[shadowSlot] = make_float4(sh.origin.x, sh.origin.y, sh.origin.z, sh.distance);
-            S->shadow.rayD[shadowSlot] = make_float4(sh.direction.x, sh.direction.y, sh.direction.z, __uint_as_float(pixelIdx));
-            S->shadow.radiance[shadowSlot] = make_float4(sh.radiance.x, sh.radiance.y, sh.radiance.z, 0.0f);
-        }
-        if (wantTrace) {
-            // w: kRayPassThrough for a pass-through continuation (the path's previous vertex stays what it was: keep_previous_vertex)
-            S->trace.rays[0].rayO[traceSlot] = make_float4(nextOrigin.x, nextOrigin.y, nextOrigin.z, __uint_as_float(updatePath ? 0u : kRayPassThrough));
-            S->trace.rays[0].rayD[traceSlot] = make_float4(nextDir.x, nextDir.y, nextDir.z, __uint_as_float(pixelIdx));
-            // the path state that goes with the ray: the new one, or — a pass-through — the one the path arrived with
-            S->trace.rays[0].tp[traceSlot] = updatePath ? make_float4(nextThroughput.x, nextThroughput.y, nextThroughput.z, nextPdf) : tpdf;
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------------------------
-// The SCAN pipeline's material kernels: Shade<BSDF> straight from the trace queue, no logic kernel, no material queues.
-//
-// The reference's logic kernel (PathTracer.cu:136-210) reads every trace result, decides miss / Russian roulette / material
-// type and COPIES the survivors into one of four material queues (48 B per path and bounce, :183-206) for the Shade kernels to
-// read back.  Here the decision is already in the hit record when the closest-hit launch ends — the roulette draw is made by the
-// ray's producer and rides in the ray (kRaySurvives), the material type rides in the instance record (InstTrav::instIdx), the
-// trace kernel's flush combines the two into a code beside the hit's instance (nx_trace.hip) — so a material kernel only has to
-// FIND its items: a workgroup walks its share of the trace queue 1 024 rays at a time (one 16-byte load of four instance words
-// per thread), collects the slots whose code is its type in an LDS ring (ballots + one LDS atomic per wave), and shades them
-// 256 at a time with every lane busy, reading hit, direction and path state at the ray's own slot (ascending within a batch).
-// Per path and bounce that is 4 B scanned per material kernel in the graph + 52 B gathered, against the 52 B in / 48 B out of
-// the logic kernel + 48 B in of the material kernel; and one launch less per bounce.  The rays alternate between two sets by
-// bounce parity (TraceQueue), because a kernel of bounce b reads the rays of b - 1 while it writes those of b.
-//
-// Regions: workgroup w serves region w % 8 of the input queue (its blockIdx % 8 is its XCD: the XCD whose trace waves call that
-// region home) and appends to the same region of the output queues, so a region never holds more than it did the bounce before
-// (the primary pieces are even), and no batch mixes regions.  Fast compaction only (slot order = order of the atomics); the
-// ordered mode keeps the classic pipeline, which is the reference's serial-slot semantics.
-constexpr int kScanRing = 2048;  // LDS ring of found slots: fewer than 256 left over + 1 024 new ones at most
-static_assert(kScanRing >= kShadeBlock + 4 * kShadeBlock && (kScanRing & (kScanRing - 1)) == 0, "scan geometry");
-
-// One material type's share of a workgroup's work.  Tiles of `tileRays` rays (1 024: four instance words per thread in one 16-byte
-// load; 256 when the region holds too few rays to give every workgroup a large tile — late bounces, whose launches are as long as
-// their longest workgroup): tile `firstTile` is this workgroup's by its rank (-1: none, it comes over from another type), tiles
-// from `staticTiles` on are handed out by ticket — one returning atomic per tile on the region's own word.  The share of a tile
-// that is this type's to shade varies from none to all with what the camera sees there, so a static split leaves most workgroups
-// waiting for the few whose tiles were full (measured: +40 % on the kernels).
-template <int TYPE, unsigned F>
-NXD void shade_scan_type(const DeviceState* __restrict__ S, const int bounce, const bool dropEnded, const int region, const int inRegion, const int per, const int firstTile,
-                         const int staticTiles, int* const sRing, int* const sHead, int* const sTicket)
-{
-    constexpr bool NO_MAPS = (F & kMfNoMaps) != 0u;  // (the rest: shade_path reads it)
-    // TYPE == kScanMiss: the rays that missed (code kHitCodeMiss) — what is left of the logic step when a miss can contribute: the
-    // environment (flat colour or map, MIS-weighted against the environment sampler) added to the path's radiance, PathTracer.cu:152-164
-    constexpr bool kMiss = TYPE == kScanMiss;
-    // TYPE == kScanMetalBit: NX_MAT_METALROUGH, whose own number is the misses' place here (its code, ticket row and size row: nx_device.h)
-    constexpr bool kMetal = TYPE == kScanMetalBit;
-    constexpr int kMat = kMetal ? NX_MAT_METALROUGH : TYPE;  // the material type shaded (kMiss: none)
-    constexpr uint32_t kCode = kMiss ? kHitCodeMiss : hit_code_of_type(kMat);
-    Counters* C = S->counters;
-    const int tileRays = per * kShadeBlock;
-    const int tiles = (inRegion + tileRays - 1) / tileRays;
-    int* const ticket = kMetal ? &C->region[region].scanTileMetal[bounce] : &C->region[region].scanTile[kMetal ? 0 : TYPE][bounce];
-    int t = firstTile;
-    if (t < 0 && tiles <= staticTiles) return;  // every tile has a workgroup of this type's own
-    __syncthreads();  // the previous type is done with the ticket word and the ring
-    if (threadIdx.x == 0) {
-        *sHead = 0;
-        if (t < 0) *sTicket = staticTiles + atomicAdd(ticket, 1);
-    }
-    __syncthreads();
-    if (t < 0) {
-        t = *sTicket;
-        if (t >= tiles) return;
-    }
-    const uint32_t frame = S->frame->frameNumber;
-    const int regionBase = region * (int)S->queueShardCap;
-    const TraceRays in = S->trace.rays[(bounce - 1) & 1], out = S->trace.rays[bounce & 1];
-    const NX_G uint32_t* const codes = S->trace.hitInst + regionBase;
-    SlotAllocator<false, 2> slots;  // 0: shadow requests, 1: continuation rays
-    static_assert(offsetof(RegionCounters, traceSize) + kMaxBounceSlots * sizeof(int32_t) == offsetof(RegionCounters, traceShadowSize), "traceShadowSize follows traceSize");
-    slots.init(S, &C->region[0].traceShadowSize[bounce], -kMaxBounceSlots, 1 + ((kMiss || kMetal) ? 0 : TYPE), bounce, inRegion);  // (the kind names a ticket word of the ORDERED allocator: unused here)
-    const int lane = threadIdx.x & (kWave - 1);
-    const unsigned long long laneLt = (1ull << lane) - 1ull;
-    int tail = 0, head = 0;  // ring positions [tail, head) hold found slots not shaded yet (uniform)
-    int ended = 0;           // continuation rays of this wave that were not queued (dropEnded; uniform over the wave)
-
-    // shades `take` <= 256 slots from the ring's tail
-    const auto shade_batch = [&](const int take) {
-        const bool have = (int)threadIdx.x < take;
-        const int at = regionBase + (have ? sRing[(tail + (int)threadIdx.x) & (kScanRing - 1)] : 0);
-        tail += take;
-        if constexpr (kMiss) {
-            if (have) {
-                const float4 dirPix = in.rayD[at];
-                const uint32_t pixelIdx = __float_as_uint(dirPix.w);
-                const float4 tp = bounce == 1 ? make_float4(1.0f, 1.0f, 1.0f, 1.0e10f) : in.tp[at];
-                bool miss, survived, needsPrevVertex;
-                f3 bg = mk3(0.0f), t = mk3(0.0f);
-                uint32_t inst = 0;
-                logic_path<!NO_MAPS, F & kMfAnalytic>(S, bounce, frame, (uint32_t)at, pixelIdx, 1e30f, mk3(dirPix.x, dirPix.y, dirPix.z), tp, [&]() { return 0u; }, miss, bg, survived, t, inst, needsPrevVertex);
-                if ((__float_as_uint(bg.x) | __float_as_uint(bg.y) | __float_as_uint(bg.z)) != 0u) {  // (as the logic kernel: +0 changes nothing)
-                    float4 r = bounce == 1 ? make_float4(0, 0, 0, 0) : S->radiance[pixelIdx];
-                    r.x += bg.x; r.y += bg.y; r.z += bg.z;
-                    if (bounce == 1) r = make_float4(bg.x, bg.y, bg.z, 0.0f);
-                    S->radiance[pixelIdx] = r;
-                }
-            }
-            return;
-        } else {
-        bool wantShadow = false, wantTrace = false, updatePath = false;
-        ShadowPayload sh;
-        f3 nextOrigin = mk3(0.0f), nextDir = mk3(0.0f), nextThroughput = mk3(0.0f);
-        float nextPdf = 0.0f;
-        uint32_t pixelIdx = 0;
-        float4 tpdf = make_float4(0, 0, 0, 0);
-        if (have) {
-            const uint32_t instanceIdx = S->trace.hitInst[at] & kHitInstMask;
-            const float4 hit = S->trace.hit[at];
-            const float4 dirPix = in.rayD[at];
-            pixelIdx = __float_as_uint(dirPix.w);
-            // the rest of the logic step (PathTracer.cu:167-175): the survivor's throughput is divided by the roulette's
-            // probability (at bounce 1 both are 1)
-            tpdf = make_float4(1.0f, 1.0f, 1.0f, 1.0e10f);
-            if (bounce != 1) {
-                const float4 tp = in.tp[at];
-                const f3 throughput = mk3(tp.x, tp.y, tp.z);
-                const f3 tq = throughput / maxcomp3(throughput);
-                tpdf = make_float4(tq.x, tq.y, tq.z, tp.w);
-            }
-            // ... and the path's previous vertex, for hits that can need it (keep_previous_vertex)
-            const uint32_t typeAndFlag = *(const NX_G uint32_t*)((const NX_G char*)&S->shadeInst[instanceIdx].material + kMaterialTypeOffset);
-            if ((typeAndFlag >> 8) & 1u) keep_previous_vertex(S, pixelIdx, in.rayO[at]);
-            shade_path<kMat, F>(S, bounce, frame, (uint32_t)at, pixelIdx, hit.y, hit.z, __float_as_uint(hit.w), instanceIdx, mk3(dirPix.x, dirPix.y, dirPix.z), tpdf,
-                             [&]() { return S->rayOrigin[pixelIdx]; },
-                             [&](f3 emitted, uint32_t instIdx) {
-                                 if (bounce == 1 && bounce != (int)S->settings.pathLength && pixelIdx < S->localCount && S->frame->pixelQueryPixel == (int)global_pixel(S, pixelIdx))
-                                     S->frame->pixelQueryInstance = (int)instIdx;
-                                 if (emitted.x != 0.0f || emitted.y != 0.0f || emitted.z != 0.0f) {
-                                     float4 r = S->radiance[pixelIdx];
-                                     r.x += emitted.x; r.y += emitted.y; r.z += emitted.z;
-                                     S->radiance[pixelIdx] = r;
-                                 }
-                             },
-                             wantShadow, sh, wantTrace, updatePath, nextOrigin, nextDir, nextThroughput, nextPdf);
-        }
-        // the path state that goes with the ray: the new one, or — a pass-through — the one the path arrived with
-        const float4 tpNext = updatePath ? make_float4(nextThroughput.x, nextThroughput.y, nextThroughput.z, nextPdf) : tpdf;
-        // the next logic step's Russian roulette, drawn here (kRaySurvives): its random number is keyed by the pixel — or, with
-        // slot-keyed numbers, by the slot the ray goes to — the next bounce and the frame, its probability is the throughput
-        // just computed.  dropEnded (pixel-keyed numbers, no miss type in the pass): the draw comes before the slot, and a ray that
-        // lost it gets none — whatever it hit, nobody would read the record (see kShadeDropEnded).  The shadow request stays.
-        bool survives = true;
-        if (dropEnded) {
-            if (wantTrace) {
-                uint32_t rng = seed_for(S, 0u, pixelIdx, (uint32_t)bounce + 1u, 0u, frame);
-                survives = rng_next(rng) < maxcomp3(mk3(tpNext.x, tpNext.y, tpNext.z));
-            }
-            ended += __popcll(__ballot(wantTrace && !survives));
-            wantTrace = wantTrace && survives;
-        }
-        const bool want[2] = {wantShadow, wantTrace};
-        int slot[2];
-        slots.alloc(want, slot, 0, region);
-        const int shadowSlot = regionBase + slot[0], traceSlot = regionBase + slot[1];
-        if (wantShadow) {
-            S->shadow.rayO[shadowSlot] = make_float4(sh.origin.x, sh.origin.y, sh.origin.z, sh.distance);
-            S->shadow.rayD[shadowSlot] = make_float4(sh.direction.x, sh.direction.y, sh.direction.z, __uint_as_float(pixelIdx));
-            S->shadow.radiance[shadowSlot] = make_float4(sh.radiance.x, sh.radiance.y, sh.radiance.z, 0.0f);
-        }
-        if (wantTrace) {
-            if (!dropEnded) {
-                uint32_t rng = seed_for(S, (uint32_t)traceSlot, pixelIdx, (uint32_t)bounce + 1u, 0u, frame);
-                survives = rng_next(rng) < maxcomp3(mk3(tpNext.x, tpNext.y, tpNext.z));
-            }
-            out.rayO[traceSlot] = make_float4(nextOrigin.x, nextOrigin.y, nextOrigin.z, __uint_as_float((updatePath ? 0u : kRayPassThrough) | (survives ? kRaySurvives : 0u)));
-            out.rayD[traceSlot] = make_float4(nextDir.x, nextDir.y, nextDir.z, __uint_as_float(pixelIdx));
-            out.tp[traceSlot] = tpNext;
-        }
-        }
-    };
-
-    for (;;) {
-        // ---- find: which of this tile's rays does this kernel shade
-        if (per == 4) {
-            const int r0 = t * tileRays + 4 * (int)threadIdx.x;
-            uint4 w = make_uint4(0u, 0u, 0u, 0u);
-            if (r0 + 3 < inRegion) w = *(const NX_G uint4*)(codes + r0);
-            else {
-                if (r0 < inRegion) w.x = codes[r0];
-                if (r0 + 1 < inRegion) w.y = codes[r0 + 1];
-                if (r0 + 2 < inRegion) w.z = codes[r0 + 2];
-            }
-            const bool m0 = (w.x >> kHitCodeShift) == kCode, m1 = (w.y >> kHitCodeShift) == kCode;
-            const bool m2 = (w.z >> kHitCodeShift) == kCode, m3 = (w.w >> kHitCodeShift) == kCode;
-            const unsigned long long b0 = __ballot(m0), b1 = __ballot(m1), b2 = __ballot(m2), b3 = __ballot(m3);
-            const int n0 = __popcll(b0), n1 = __popcll(b1), n2 = __popcll(b2), n3 = __popcll(b3);
-            const int total = n0 + n1 + n2 + n3;
-            if (total) {
-                int base = 0;
-                if (lane == 0) base = atomicAdd(sHead, total);  // (an LDS atomic: the ring's head)
-                base = __builtin_amdgcn_readfirstlane(base);
-                if (m0) sRing[(base + __popcll(b0 & laneLt)) & (kScanRing - 1)] = r0;
-                if (m1) sRing[(base + n0 + __popcll(b1 & laneLt)) & (kScanRing - 1)] = r0 + 1;
-                if (m2) sRing[(base + n0 + n1 + __popcll(b2 & laneLt)) & (kScanRing - 1)] = r0 + 2;
-                if (m3) sRing[(base + n0 + n1 + n2 + __popcll(b3 & laneLt)) & (kScanRing - 1)] = r0 + 3;
-            }
-        } else {
-            const int r0 = t * tileRays + (int)threadIdx.x;
-            const bool m0 = r0 < inRegion && (codes[r0] >> kHitCodeShift) == kCode;
-            const unsigned long long b0 = __ballot(m0);
-            if (b0) {
-                int base = 0;
-                if (lane == 0) base = atomicAdd(sHead, __popcll(b0));
-                base = __builtin_amdgcn_readfirstlane(base);
-                if (m0) sRing[(base + __popcll(b0 & laneLt)) & (kScanRing - 1)] = r0;
-            }
-        }
-        __syncthreads();
-        head = *sHead;
-        // the next tile: by ticket (issued here, needed only after this tile's batches)
-        if (threadIdx.x == 0) *sTicket = tiles > staticTiles ? staticTiles + atomicAdd(ticket, 1) : tiles;
-        // ---- shade: full batches; what is left over waits for the next tile's finds, or goes last
-        while (head - tail >= kShadeBlock) shade_batch(kShadeBlock);
-        __syncthreads();  // the ticket is there; and nobody appends to the ring before everybody has read its head
-        t = *sTicket;
-        if (t >= tiles) break;
-    }
-    if (head - tail > 0) shade_batch(head - tail);
-    // the items this workgroup shaded, for nxhip_read_queue_sizes (the reference's per-type queue sizes, D_QueueSize)
-    if (!kMiss && threadIdx.x == 0 && head) atomicAdd(kMetal ? &C->region[region].materialSizeMetal[bounce] : &C->region[region].materialSize[(kMiss || kMetal) ? 0 : TYPE][bounce], head);
-    // ... and the continuation rays it did not queue: the waves' counts meet in the ring's head word, one add per workgroup
-    if (!kMiss && dropEnded) {
-        __syncthreads();  // everybody has read the head
-        if (threadIdx.x == 0) *sHead = 0;
-        __syncthreads();
-        if (lane == 0 && ended) atomicAdd(sHead, ended);
-        __syncthreads();
-        if (threadIdx.x == 0 && *sHead) atomicAdd(&C->region[region].endedSize[bounce], *sHead);
-    }
-}
-
-// All material types of a bounce in ONE launch (`typeMask`: bit NX_MAT_* = that type has a kernel in this pass; bit kScanMiss = the
-// misses contribute — an environment map or a background that is not black — and are handled here as a fifth type).  The region's
-// workgroups start on different types (rank modulo the number of types) and move on to the next type when theirs has no tile
-// left, so the types run side by side, the launch ends when the last tile of the last type does, and a bounce costs one material
-// launch instead of one per type (the reference: four, PathTracer.cpp:116-120).  A single-bit mask is a per-type launch.
-// METAL (a context with an NX_MAT_METALROUGH material: kFlavorMetal): the fifth material type as a sixth case, typeMask bit kScanMetalBit.  The
-// kernel's register count is the maximum over its cases, so the case is compiled into these instances alone (nx_wavefront_metal.hip).
-template <unsigned F>  // (POWER, NO_MAPS, ANALYTIC: next_event_estimation; DETAIL, SOLID: shade_path; METAL: here)
-__global__ void __launch_bounds__(kShadeBlock, NX_SHADE_WAVES) shade_scan_kernel(const DeviceState* __restrict__ S, const int bounceArg, const int typeMask)
-{
-    constexpr bool METAL = (F & kMfMetal) != 0u;
-    static_assert(material_set_ok(F), "SOLID => METAL => DETAIL => not NO_MAPS (nx_variants.h)");
-    const int bounce = bounceArg & 0xff;
-    const bool dropEnded = (bounceArg & kShadeDropEnded) != 0;  // (a property of the pass's shape: nxhip_api.hip pass_flavor)
-    __shared__ int sRing[kScanRing];
-    __shared__ int sHead, sTicket;
-    const int region = (int)(blockIdx.x & (kQueueShards - 1));
-    const int inRegion = S->counters->region[region].traceSize[bounce - 1];  // rays of this region after trace(bounce - 1)
-    const int rank = (int)(blockIdx.x >> 3), ranks = max(1, (int)(gridDim.x >> 3));
-    const int nTypes = __popc((uint32_t)typeMask & (METAL ? 0x3fu : 0x1fu));
-    if (inRegion <= 0 || nTypes == 0) return;
-    // this workgroup's place among those that start on the same type, and how many of them there are
-    const int myStart = rank % nTypes, myIndex = rank / nTypes;
-    // four rays per thread while that still gives every starter a tile, else one (see shade_scan_type)
-    // (... while that gives every starter FOUR tiles: with fewer the launch is as long as its unluckiest workgroup — one frame per pass:
-    //  material step 0.50 -> 0.45 ms per frame; the driver's 20-frame pass =)
-#ifndef NX_SCAN_TILE_FACTOR
-#define NX_SCAN_TILE_FACTOR 4
-#endif
-    const int per = inRegion >= NX_SCAN_TILE_FACTOR * 4 * kShadeBlock * ((ranks + nTypes - 1) / nTypes) ? 4 : 1;
-    const int tiles = (inRegion + per * kShadeBlock - 1) / (per * kShadeBlock);
-    if (myIndex >= tiles) return;  // more workgroups than tiles (late bounces): the surplus leaves before any barrier or atomic
-    // the types in graph order of the reference (Diffuse, Plastic, Dielectric, Conductor: PathTracer.cpp:116-120), rotated so that
-    // this workgroup begins with its own
-    // (METAL: the new type goes last, so the five in front of it keep their places)
-    constexpr int kOrder[6] = {NX_MAT_DIFFUSE, NX_MAT_PLASTIC, NX_MAT_DIELECTRIC, NX_MAT_CONDUCTOR, kScanMiss, kScanMetalBit};
-    for (int step = 0; step < nTypes; step++) {
-        const int want = (myStart + step) % nTypes;  // index among the types present
-        int type = -1, seen = 0;
-#pragma unroll
-        for (int k = 0; k < (METAL ? 6 : 5); k++)
-            if ((typeMask >> kOrder[k]) & 1) { if (seen == want) type = kOrder[k]; seen++; }
-        const int starters = (ranks - want + nTypes - 1) / nTypes;  // workgroups whose first type this is: each takes the tile of its index
-        const int first = step == 0 ? myIndex : -1;
-        switch (type) {
-        case NX_MAT_DIFFUSE: shade_scan_type<NX_MAT_DIFFUSE, F>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket); break;
-        case NX_MAT_PLASTIC: shade_scan_type<NX_MAT_PLASTIC, F>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket); break;
-        case NX_MAT_DIELECTRIC: shade_scan_type<NX_MAT_DIELECTRIC, F>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket); break;
-        case NX_MAT_CONDUCTOR: shade_scan_type<NX_MAT_CONDUCTOR, F>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket); break;
-        case kScanMiss: shade_scan_type<kScanMiss, F>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket); break;
-        case kScanMetalBit:
-            if constexpr (METAL) shade_scan_type<kScanMetalBit, F>(S, bounce, dropEnded, region, inRegion, per, first, min(starters, tiles), sRing, &sHead, &sTicket);
-            break;
-        default: break;
-        }
-    }
-}
-
 // The reference's queue sizes count the hits of a material type whether or not a kernel shades them (its conductor kernel's body is
 // commented out, PathTracer.cu:475-478, but the logic kernel still fills that queue): with NX_CONDUCTOR_REFERENCE the SCAN
 // pipeline has no conductor kernel to count its items, so this one does (4 B per ray; in the graph only in that mode).
-#ifndef NX_WAVEFRONT_INSTANCES_ONLY
 __global__ void __launch_bounds__(kWideBlock) count_scan_kernel(const DeviceState* __restrict__ S, const int bounce, const int type)
 {
     Counters* C = S->counters;
@@ -1367,183 +111,10 @@ __global__ void __launch_bounds__(kWideBlock) count_scan_kernel(const DeviceStat
     if ((threadIdx.x & (kWave - 1)) == 0 && n) atomicAdd(&C->region[0].materialSize[type][bounce], n);
 }
 
-#endif  // NX_WAVEFRONT_INSTANCES_ONLY
-
-// ------------------------------------------------------------------------------------------------------
-// Tail kernel: the late bounces of a pass without the graph.  From bounce `firstBounce` on a pass carries a few per cent of
-// its rays, yet every bounce still costs a trace level as long as its slowest ray plus a logic and four material launches.
-// Here a wave takes 64 paths of the trace queue after trace(firstBounce - 1) and runs each lane's path to its end —
-// logic, shade (the material kinds present in the wave, one after the other), the shadow ray of the light sample, the
-// continuation ray — with traverse_wave for the rays.  Same functions, same order of radiance additions per pixel, and the
-// random numbers are keyed by pixel, bounce and stage: the image is bit-identical to the level-by-level pipeline
-// (tests/test_gpu_tail.py).  Pixel-keyed random numbers and the workgroup-aggregated compaction only.
-#ifndef NX_TAIL_REFILL_BELOW
-#define NX_TAIL_REFILL_BELOW 40
-#endif
-template <unsigned F>  // (POWER, ANALYTIC: next_event_estimation; DETAIL: shade_path; METAL, the fifth material type: here and logic_path)
-__global__ void __launch_bounds__(kTraceBlock) tail_kernel(const DeviceState* __restrict__ S, const int firstBounceArg)
-{
-    constexpr bool METAL = (F & kMfMetal) != 0u;
-    static_assert(tail_set_ok(F), "a set of material features tail_kernel has no instance for (nx_variants.h)");
-    // firstBounce | kTraceScanFlag: the pass ran the SCAN pipeline so far — the rays of trace(firstBounce - 1) are in the set of
-    // that bounce's parity and the hit records carry codes (which this kernel does not need: it makes the logic step's decisions
-    // itself, with the same random numbers)
-    const int firstBounce = firstBounceArg & 0xff;
-    const TraceRays rays = S->trace.rays[(firstBounceArg & kTraceScanFlag) ? ((firstBounce - 1) & 1) : 0];
-    __shared__ unsigned long long ldsStack[kLdsDepth * kTraceBlock];
-    Counters* C = S->counters;
-    const QueueView in = queue_view(&C->region[0].traceSize[firstBounce - 1], S->queueShardCap);
-    const int size = in.total;
-    if (size <= 0) return;
-    const int lane = threadIdx.x & (kWave - 1);
-    const unsigned long long laneLt = (1ull << lane) - 1ull;
-    lds_u64* const stackLds = (lds_u64*)&ldsStack[threadIdx.x];
-    const uint32_t frame = S->frame->frameNumber;
-
-    // per-lane path state; a lane whose path has ended takes the next path of the queue when the wave refills
-    bool alive = false, dirty = false;
-    int bounce = firstBounce, index = 0;
-    uint32_t pixelIdx = 0, inst = 0, tri = 0;
-    float hitT = 1e30f, hu = 0.0f, hv = 0.0f;
-    f3 dir = mk3(0.0f);
-    float4 tp = make_float4(0, 0, 0, 0), ro = make_float4(0, 0, 0, 0), rad = make_float4(0, 0, 0, 0);
-    bool exhausted = false;
-
-    for (;;) {
-        // ---- refill: paths are handed out one by one (the head counts paths), 64 - alive at a time
-        unsigned long long aliveMask = __ballot(alive);
-        if (!exhausted && __popcll(aliveMask) < NX_TAIL_REFILL_BELOW) {
-            if (!alive && dirty) { S->radiance[pixelIdx] = rad; dirty = false; }
-            const unsigned long long needMask = ~aliveMask;
-            const int need = (int)__popcll(needMask);
-            int base = 0;
-            if (lane == 0) base = atomicAdd(&C->tailHead, need);
-            base = __builtin_amdgcn_readfirstlane(base);
-            if (base + need >= size) exhausted = true;
-            const int mine = base + (int)__popcll(needMask & laneLt);
-            if (!alive && mine < size) {
-                index = mine;
-                const int at = in.slot(mine);
-                const float4 hit = S->trace.hit[at];
-                const float4 dirPix = rays.rayD[at];
-                inst = S->trace.hitInst[at] & kHitInstMask;
-                pixelIdx = __float_as_uint(dirPix.w);
-                dir = mk3(dirPix.x, dirPix.y, dirPix.z);
-                hitT = hit.x; hu = hit.y; hv = hit.z; tri = __float_as_uint(hit.w);
-                tp = rays.tp[at];
-                // the path's previous vertex: the origin of the ray that produced this hit, or, after a pass-through, what
-                // the logic step of the pass-through surface kept
-                ro = rays.rayO[at];
-                if (__float_as_uint(ro.w) & kRayPassThrough) ro = S->rayOrigin[pixelIdx];
-                rad = S->radiance[pixelIdx];
-                bounce = firstBounce;
-                alive = true;
-            }
-            aliveMask = __ballot(alive);
-        }
-        if (aliveMask == 0ull) break;
-
-        // ---- logic and shade of every live path at its own bounce
-        int type = -1;
-        if (alive) {
-            bool miss, survived, needsPrevVertex;
-            f3 bg = mk3(0.0f), t = mk3(0.0f);
-            type = logic_path<true, F>(S, bounce, frame, (uint32_t)index, pixelIdx, hitT, dir, tp, [&]() { return inst; }, miss, bg, survived, t, inst, needsPrevVertex);
-            if (miss) { rad.x += bg.x; rad.y += bg.y; rad.z += bg.z; dirty = true; }
-            if (survived) { tp.x = t.x; tp.y = t.y; tp.z = t.z; }
-            if (type < 0) alive = false;
-        }
-        bool wantShadowRay = false, wantTrace = false, updatePath = false;
-        ShadowPayload sh;
-        sh.origin = mk3(0.0f); sh.direction = mk3(0.0f); sh.radiance = mk3(0.0f); sh.distance = 0.0f;
-        f3 nextOrigin = mk3(0.0f), nextDir = mk3(0.0f), nextThroughput = mk3(0.0f);
-        float nextPdf = 0.0f;
-        const auto prevOrigin = [&]() { return ro; };
-        const auto emit = [&](f3 emitted, uint32_t) {
-            if (emitted.x != 0.0f || emitted.y != 0.0f || emitted.z != 0.0f) {
-                rad.x += emitted.x; rad.y += emitted.y; rad.z += emitted.z;
-                dirty = true;
-            }
-        };
-        if (__ballot(alive && type == NX_MAT_DIFFUSE) != 0ull) {
-            if (alive && type == NX_MAT_DIFFUSE)
-                shade_path<NX_MAT_DIFFUSE, F>(S, bounce, frame, (uint32_t)index, pixelIdx, hu, hv, tri, inst, dir, tp, prevOrigin, emit, wantShadowRay, sh, wantTrace, updatePath, nextOrigin, nextDir, nextThroughput, nextPdf);
-        }
-        if (__ballot(alive && type == NX_MAT_PLASTIC) != 0ull) {
-            if (alive && type == NX_MAT_PLASTIC)
-                shade_path<NX_MAT_PLASTIC, F>(S, bounce, frame, (uint32_t)index, pixelIdx, hu, hv, tri, inst, dir, tp, prevOrigin, emit, wantShadowRay, sh, wantTrace, updatePath, nextOrigin, nextDir, nextThroughput, nextPdf);
-        }
-        if (__ballot(alive && type == NX_MAT_DIELECTRIC) != 0ull) {
-            if (alive && type == NX_MAT_DIELECTRIC)
-                shade_path<NX_MAT_DIELECTRIC, F>(S, bounce, frame, (uint32_t)index, pixelIdx, hu, hv, tri, inst, dir, tp, prevOrigin, emit, wantShadowRay, sh, wantTrace, updatePath, nextOrigin, nextDir, nextThroughput, nextPdf);
-        }
-        if (__ballot(alive && type == NX_MAT_CONDUCTOR) != 0ull) {
-            if (alive && type == NX_MAT_CONDUCTOR) {
-                if (S->conductorMode == NX_CONDUCTOR_EXTENDED)
-                    shade_path<NX_MAT_CONDUCTOR, F>(S, bounce, frame, (uint32_t)index, pixelIdx, hu, hv, tri, inst, dir, tp, prevOrigin, emit, wantShadowRay, sh, wantTrace, updatePath, nextOrigin, nextDir, nextThroughput, nextPdf);
-                else alive = false;  // (the reference's graph has no conductor kernel: such a path ends unshaded)
-            }
-        }
-        if constexpr (METAL) {
-            if (__ballot(alive && type == NX_MAT_METALROUGH) != 0ull) {
-                if (alive && type == NX_MAT_METALROUGH)
-                    shade_path<NX_MAT_METALROUGH, F>(S, bounce, frame, (uint32_t)index, pixelIdx, hu, hv, tri, inst, dir, tp, prevOrigin, emit, wantShadowRay, sh, wantTrace, updatePath, nextOrigin, nextDir, nextThroughput, nextPdf);
-            }
-        }
-        // ---- the light sample's shadow ray: traced now, added when unoccluded (the shadow launch of this bounce, BVH8Traversal.cuh:515)
-        const bool wantShadow = alive && wantShadowRay;
-        if (__ballot(wantShadow) != 0ull) {
-            float t = wantShadow ? sh.distance : 0.0f, su, sv;
-            uint32_t st, si;
-            const bool occluded = traverse_wave<true>(S, stackLds, wantShadow, sh.origin, sh.direction, t, su, sv, st, si);
-            if (wantShadow && !occluded) {
-                rad.x += sh.radiance.x; rad.y += sh.radiance.y; rad.z += sh.radiance.z;
-                dirty = true;
-            }
-        }
-        // ---- the continuation ray (a path shaded at bounce == pathLength never asks for one)
-        alive = alive && wantTrace;
-        if (alive && updatePath) {
-            ro = make_float4(nextOrigin.x, nextOrigin.y, nextOrigin.z, 0.0f);
-            tp = make_float4(nextThroughput.x, nextThroughput.y, nextThroughput.z, nextPdf);
-        }
-        if (__ballot(alive) != 0ull) {
-            if (alive) dir = nextDir;
-            float nt = 1e30f, nu = 0.0f, nv = 0.0f;
-            uint32_t ntri = 0xffffffffu, ninst = 0xffffffffu;
-            traverse_wave<false>(S, stackLds, alive, nextOrigin, nextDir, nt, nu, nv, ntri, ninst);
-            if (alive) { hitT = nt; hu = nu; hv = nv; tri = ntri; inst = ninst; bounce++; }
-        }
-    }
-    if (dirty) S->radiance[pixelIdx] = rad;
-}
-
-// ------------------------------------------------------------------------------------------------------
-// The instances of the three families above are compiled in four units (this one and nx_wavefront_detail / _metal / _solid.hip, which
-// say why).  Each unit lists the sets it holds (Instances: nx_variants.h) and answers for them through these lookups: naming a set in a
-// list is what compiles its instance, and a set no list names yields nullptr.  (TYPES: the material types the unit's shade_kernel
-// instances exist for, in the order they are instantiated.)
-constexpr bool kOrdered = true;  // (the classic pipeline's kernels are instantiated for the ordered compaction alone: frame_levels)
-template <class Sets> const void* shade_scan_instance(unsigned set)
-{
-    return Sets::find(set, [](auto f) { return (const void*)shade_scan_kernel<decltype(f)::value>; });
-}
-template <class Sets> const void* tail_instance(unsigned set)
-{
-    return Sets::find(set, [](auto f) { return (const void*)tail_kernel<decltype(f)::value>; });
-}
-template <class Sets, int... TYPES> const void* shade_instance(int type, unsigned set)
-{
-    const void* fn = nullptr;
-    ((TYPES == type ? (void)(fn = Sets::find(set, [](auto f) { return (const void*)shade_kernel<TYPES, kOrdered, decltype(f)::value>; })) : (void)0), ...);
-    return fn;
-}
-
 // ------------------------------------------------------------------------------------------------------
 // AccumulateKernel, Tonemap, LinearToGamma, ToColorUInt — PathTracer.cu:37-62, 480-496; Utils/Utils.h:51-54
 
 // (tonemap_rgba8: nx_tonemap.h — the denoiser's kernels write their RGBA8 image through the same text)
-#ifndef NX_WAVEFRONT_INSTANCES_ONLY
 
 // Running mean over `slices` consecutive frames per pixel, then tonemap.  src == nullptr: this context's own radiance
 // (slices = framesPerPass, the pass's frame numbers); otherwise externally gathered radiance laid out
@@ -1589,108 +160,6 @@ __global__ void __launch_bounds__(kWideBlock) compose_kernel(const float4* __res
 }
 
 // ------------------------------------------------------------------------------------------------------
-// Test hooks: the shading functions on plain arrays (nxhip_bsdf_*_batch, nxhip_tex2d_batch)
-
-template <int TYPE>
-NXD void bsdf_hook_one(const MatParams& mp, bool sample, const nx_bsdf_query& q, nx_bsdf_result& r)
-{
-    f3 wo = ld3(q.wo), thr = mk3(0.0f);
-    float pdf = 0.0f;
-    uint32_t rng = q.rng;
-    const bool ok = sample ? Bsdf<TYPE>::sample(mp, ld3(q.wi), rng, wo, thr, pdf) : Bsdf<TYPE>::eval(mp, ld3(q.wi), wo, thr, pdf);
-    r.wo[0] = wo.x; r.wo[1] = wo.y; r.wo[2] = wo.z;
-    r.pdf = pdf;
-    r.throughput[0] = thr.x; r.throughput[1] = thr.y; r.throughput[2] = thr.z;
-    r.ok = ok ? 1u : 0u;
-    r.rngOut = rng;
-    r.pad_[0] = r.pad_[1] = r.pad_[2] = 0u;
-}
-
-__global__ void __launch_bounds__(kWideBlock) bsdf_hook_kernel(const nx_material* __restrict__ material, const nx_bsdf_query* __restrict__ q, const uint32_t count,
-                                                                const int sample, nx_bsdf_result* __restrict__ out)
-{
-    const nx_material m = *material;
-    const MatParams mp = load_params(m);
-    for (uint32_t k = blockIdx.x * blockDim.x + threadIdx.x; k < count; k += gridDim.x * blockDim.x) {
-        nx_bsdf_result r;
-        switch (m.type) {
-        case NX_MAT_DIFFUSE: bsdf_hook_one<NX_MAT_DIFFUSE>(mp, sample != 0, q[k], r); break;
-        case NX_MAT_DIELECTRIC: bsdf_hook_one<NX_MAT_DIELECTRIC>(mp, sample != 0, q[k], r); break;
-        case NX_MAT_PLASTIC: bsdf_hook_one<NX_MAT_PLASTIC>(mp, sample != 0, q[k], r); break;
-        default: bsdf_hook_one<NX_MAT_CONDUCTOR>(mp, sample != 0, q[k], r); break;
-        }
-        out[k] = r;
-    }
-}
-
-// include/nexus_fmath.h on arrays (nxhip_fmath_batch, a test hook like the two above)
-__global__ void __launch_bounds__(kWideBlock) fmath_hook_kernel(const int op, const double* __restrict__ a, const double* __restrict__ b, const uint32_t count,
-                                                                 double* __restrict__ out)
-{
-    for (uint32_t k = blockIdx.x * blockDim.x + threadIdx.x; k < count; k += gridDim.x * blockDim.x) out[k] = nxf_apply(op, a[k], b ? b[k] : 0.0);
-}
-
-// (the texture descriptor comes by value: selecting one of S->diffuseMaps[i] / S->emissiveMaps[i] / S->hdrMap with a
-//  uniform three-way branch here was miscompiled by hipcc 7.2 — the third arm left the descriptor pointer unset)
-__global__ void __launch_bounds__(kWideBlock) tex2d_hook_kernel(const TextureDev t, const float* __restrict__ srgbLut, const float* __restrict__ uv,
-                                                                 const uint32_t count, float4* __restrict__ out)
-{
-    for (uint32_t k = blockIdx.x * blockDim.x + threadIdx.x; k < count; k += gridDim.x * blockDim.x)
-        out[k] = tex2d(t, srgbLut, uv[2 * k], uv[2 * k + 1]);
-}
-
-// ... and the float environment map's lookup (nxhip_tex2d_batch kind 2 on a float map)
-__global__ void __launch_bounds__(kWideBlock) tex2d_float_hook_kernel(const float4* __restrict__ texels, const int W, const int H, const float* __restrict__ uv,
-                                                                       const uint32_t count, float4* __restrict__ out)
-{
-    for (uint32_t k = blockIdx.x * blockDim.x + threadIdx.x; k < count; k += gridDim.x * blockDim.x)
-        out[k] = tex2d_float(texels, W, H, uv[2 * k], uv[2 * k + 1]);
-}
-
-// The environment lookup and its sampler on arrays (nxhip_env_sample_batch / nxhip_env_eval_batch): the product's own env_invert,
-// env_direction, env_uv, env_pdf, env_texel and sample_background.  sample != 0: in = count x 2 random numbers; the direction
-// drawn, its pdf formed as the NEE forms it (from env_uv of the direction) and the texel the inversion picked.  sample == 0: in =
-// count x 3 directions; the background colour and — pdf / texel may be null: the host passes them only with the sampler on —
-// the sampler's pdf and the texel of the direction's map coordinates.
-__global__ void __launch_bounds__(kWideBlock) env_hook_kernel(const DeviceState* __restrict__ S, const int sample, const float* __restrict__ in, const uint32_t count,
-                                                               float* __restrict__ vec, float* __restrict__ pdf, uint32_t* __restrict__ texel)
-{
-    for (uint32_t k = blockIdx.x * blockDim.x + threadIdx.x; k < count; k += gridDim.x * blockDim.x) {
-        if (sample) {
-            const EnvPick p = env_invert(S, in[2 * k], in[2 * k + 1]);
-            const f3 d = env_direction(p.u, p.v);
-            vec[3 * k] = d.x; vec[3 * k + 1] = d.y; vec[3 * k + 2] = d.z;
-            pdf[k] = env_pdf(S, d, env_uv(d));
-            texel[k] = (uint32_t)p.y * S->hdrMap.width + (uint32_t)p.x;
-        } else {
-            const f3 d = mk3(in[3 * k], in[3 * k + 1], in[3 * k + 2]);
-            const f3 c = sample_background(S, d);
-            vec[3 * k] = c.x; vec[3 * k + 1] = c.y; vec[3 * k + 2] = c.z;
-            const EnvUv uv = env_uv(d);
-            if (pdf) pdf[k] = env_pdf(S, d, uv);
-            if (texel) texel[k] = env_texel(S, uv);
-        }
-    }
-}
-
-// The analytic lights' draw on arrays (nxhip_analytic_light_sample_batch): the product's own alight_sample for light `index`, from the
-// origins as given (the caller's business to offset them) with r = count x 2 random numbers.
-__global__ void __launch_bounds__(kWideBlock) alight_hook_kernel(const DeviceState* __restrict__ S, const uint32_t index, const float* __restrict__ origin,
-                                                                  const float* __restrict__ r, const uint32_t count, float* __restrict__ direction,
-                                                                  float* __restrict__ tmax, float* __restrict__ factor, uint32_t* __restrict__ ok)
-{
-    for (uint32_t k = blockIdx.x * blockDim.x + threadIdx.x; k < count; k += gridDim.x * blockDim.x) {
-        f3 d, f;
-        float t;
-        const bool good = alight_sample(&S->alights[index], mk3(origin[3 * k], origin[3 * k + 1], origin[3 * k + 2]), r[2 * k], r[2 * k + 1], d, t, f);
-        direction[3 * k] = d.x; direction[3 * k + 1] = d.y; direction[3 * k + 2] = d.z;
-        tmax[k] = t;
-        factor[3 * k] = f.x; factor[3 * k + 1] = f.y; factor[3 * k + 2] = f.z;
-        ok[k] = good ? 1u : 0u;
-    }
-}
-
-// ------------------------------------------------------------------------------------------------------
 
 // This unit's instances: the contexts without detail maps, a fifth material type or alpha modes.
 // (the classic pipeline — logic kernel and per-type material kernels — runs under the ordered compaction only: see frame_levels)
@@ -1718,15 +187,8 @@ const void* hook_sizes_kernel_ptr() { return (const void*)hook_sizes_kernel; }
 const void* generate_kernel_ptr() { return (const void*)generate_kernel; }
 const void* accumulate_kernel_ptr() { return (const void*)accumulate_kernel; }
 const void* compose_kernel_ptr() { return (const void*)compose_kernel; }
-const void* bsdf_hook_kernel_ptr() { return (const void*)bsdf_hook_kernel; }
-const void* tex2d_hook_kernel_ptr() { return (const void*)tex2d_hook_kernel; }
-const void* env_hook_kernel_ptr() { return (const void*)env_hook_kernel; }
-const void* alight_hook_kernel_ptr() { return (const void*)alight_hook_kernel; }
-const void* tex2d_float_hook_kernel_ptr() { return (const void*)tex2d_float_hook_kernel; }
-const void* fmath_hook_kernel_ptr() { return (const void*)fmath_hook_kernel; }
 
 // the device-side layouts this translation unit was compiled with (nx_device.h layout_stamp; compared by nxhip_create)
 uint64_t layout_stamp_wavefront() { return layout_stamp(); }
-#endif  // NX_WAVEFRONT_INSTANCES_ONLY
 
 }  // namespace nxd

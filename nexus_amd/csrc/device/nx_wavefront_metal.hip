@@ -1,72 +1,16 @@
 // nx_wavefront_metal.hip — the METAL instances of the material kernels (NX_MAT_METALROUGH, the fifth material type: nxhip_set_materials).
 //
-// The kernels are the templates of nx_wavefront.hip, compiled here for METAL = true and for nothing else, as nx_wavefront_detail.hip does
-// for DETAIL: shade_scan_kernel is one kernel with a switch over the types and its register count is the maximum over its cases, so the
+// The kernels are the templates of nx_wavefront.h, compiled here for METAL = true and for nothing else, as nx_wavefront_detail.hip does
+// for DETAIL (a unit of its own for the same reasons: the other families keep their neighbours, and the build compiles it beside them):
+// shade_scan_kernel is one kernel with a switch over the types and its register count is the maximum over its cases, so the
 // fifth case exists only in the instances a pass graph picks while some material has the type (kFlavorMetal) — every other context
 // launches the kernels it always did.  METAL implies DETAIL (the type's metalness comes from the roughness map's B channel, read in the
 // same lookup as the roughness: nx_detail.h) and with it the general material launch: there is no NO_MAPS form.
-// Also here: the type's instance of the BSDF hook, and the test hook over the type's inputs at a hit.
-#define NX_WAVEFRONT_INSTANCES_ONLY 1
-#include "nx_wavefront.hip"
+// Also here: logic_metal_kernel, the classic pipeline's fifth queue (a pass-graph kernel; the type's test hooks: nx_hook_kernels.hip).
+#define NX_KERNEL_TU 1
+#include "nx_wavefront.h"
 
 namespace nxd {
-
-// nxhip_bsdf_*_batch for a material of type NX_MAT_METALROUGH (the four reference types keep bsdf_hook_kernel of nx_wavefront.hip)
-__global__ void __launch_bounds__(kWideBlock) bsdf_hook_metal_kernel(const nx_material* __restrict__ material, const nx_bsdf_query* __restrict__ q, const uint32_t count,
-                                                                      const int sample, nx_bsdf_result* __restrict__ out)
-{
-    const nx_material m = *material;
-    const MatParams mp = load_params(m);
-    for (uint32_t k = blockIdx.x * blockDim.x + threadIdx.x; k < count; k += gridDim.x * blockDim.x) {
-        const nx_bsdf_query qk = q[k];
-        f3 wo = ld3(qk.wo), thr = mk3(0.0f);
-        float pdf = 0.0f;
-        uint32_t rng = qk.rng;
-        const bool ok = sample ? Bsdf<NX_MAT_METALROUGH>::sample(mp, ld3(qk.wi), rng, wo, thr, pdf) : Bsdf<NX_MAT_METALROUGH>::eval(mp, ld3(qk.wi), wo, thr, pdf);
-        nx_bsdf_result r;
-        r.wo[0] = wo.x; r.wo[1] = wo.y; r.wo[2] = wo.z;
-        r.pdf = pdf;
-        r.throughput[0] = thr.x; r.throughput[1] = thr.y; r.throughput[2] = thr.z;
-        r.ok = ok ? 1u : 0u;
-        r.rngOut = rng;
-        r.pad_[0] = r.pad_[1] = r.pad_[2] = 0u;
-        out[k] = r;
-    }
-}
-
-// nxhip_material_inputs_batch: for hit k — triangle triIdx[k] of instance `instanceIdx` at barycentrics hitUv[2k..] — the base colour c, the
-// roughness r and the metalness m the BSDF of an NX_MAT_METALROUGH material receives there, formed by the device functions shade_path
-// calls and in its order: the diffuse map's texel (tex2d), the roughness map's G and B channels (detail_shading_frame, one lookup),
-// the clamp of m (metal_clamp01).  out[5k..] = c.r, c.g, c.b, r, m.
-__global__ void __launch_bounds__(kWideBlock) material_inputs_hook_kernel(const DeviceState* __restrict__ S, const uint32_t instanceIdx, const uint32_t* __restrict__ triIdx,
-                                                                           const float* __restrict__ hitUv, const uint32_t count, float* __restrict__ out)
-{
-    const NX_G ShadeInst* inst = &S->shadeInst[instanceIdx];
-    nx_material_detail d{-1, -1, 1.0f, 0u};
-    if (S->shadeDetail) d = S->shadeDetail[instanceIdx];
-    const nx_material material = inst->material;
-    const NX_G float* T = inst->transform;
-    const NX_G float* IT = inst->invTransform;
-    for (uint32_t k = blockIdx.x * blockDim.x + threadIdx.x; k < count; k += gridDim.x * blockDim.x) {
-        const float hu = hitUv[2 * k], hv = hitUv[2 * k + 1];
-        const NX_G nx_triangle* tri = shade_tri(inst->tris, triIdx[k]);
-        MatParams mp = load_params(material);
-        const f3 tp0 = ld3(tri->pos0), tp1 = ld3(tri->pos1), tp2 = ld3(tri->pos2);
-        f3 normal = bary3(ld3(tri->normal0), ld3(tri->normal1), ld3(tri->normal2), hu, hv);
-        const f2 texUv = bary2(tri->texCoord0, tri->texCoord1, tri->texCoord2, hu, hv);
-        normal = normalize3(mat_vec_transposed(IT, normal));
-        f3 gNormal = normalize3(mat_vec_transposed(IT, cross3(tp1 - tp0, tp2 - tp0)));
-        if (material.diffuseMapId != -1) {
-            const float4 color = tex2d(S->diffuseMaps[material.diffuseMapId], S->srgbLut, texUv.x, texUv.y);
-            mp.albedo = mk3(color.x, color.y, color.z);
-        }
-        bool fellBack;
-        detail_shading_frame<NX_MAT_METALROUGH>(S, d, tri, T, tp0, tp1, tp2, texUv, -gNormal, normal, gNormal, mp.roughness, fellBack, &mp.metallic);
-        out[5 * k] = mp.albedo.x; out[5 * k + 1] = mp.albedo.y; out[5 * k + 2] = mp.albedo.z;
-        out[5 * k + 3] = mp.roughness;
-        out[5 * k + 4] = metal_clamp01(mp.metallic);
-    }
-}
 
 // The CLASSIC pipeline's fifth material queue (ordered compaction).  logic_kernel stays the reference's: four queues, and a hit of the fifth
 // type leaves it as "no kernel" (the path's roulette draw, previous vertex and miss are its business and done there).  This kernel
@@ -127,8 +71,6 @@ const void* tail(unsigned set) { return tail_instance<MetalSets>(set); }
 const void* shade(int type, unsigned set) { return shade_instance<MetalShadeSets, NX_MAT_METALROUGH>(type, set); }
 }  // namespace wavefront_metal
 const void* logic_metal_kernel_ptr() { return (const void*)logic_metal_kernel; }
-const void* bsdf_hook_metal_kernel_ptr() { return (const void*)bsdf_hook_metal_kernel; }
-const void* material_inputs_hook_kernel_ptr() { return (const void*)material_inputs_hook_kernel; }
 
 // the device-side layouts this translation unit was compiled with (nx_device.h layout_stamp; compared by nxhip_create)
 uint64_t layout_stamp_wavefront_metal() { return layout_stamp(); }

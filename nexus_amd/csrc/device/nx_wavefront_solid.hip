@@ -1,13 +1,14 @@
 // nx_wavefront_solid.hip — the SOLID instances of the material kernels (nxhip_set_material_alpha with a material that is NX_ALPHA_MASK or
-// NX_ALPHA_OPAQUE: a hit on such a material never passes through; the rule's one text is shade_path's, nx_wavefront.hip).
+// NX_ALPHA_OPAQUE: a hit on such a material never passes through; the rule's one text is shade_path's, nx_wavefront.h).
 //
-// The kernels are the templates of nx_wavefront.hip, compiled here for SOLID = true and for nothing else, as nx_wavefront_detail.hip and
-// nx_wavefront_metal.hip do for their parameters: every context without such a material launches the kernels it always did.  SOLID
+// The kernels are the templates of nx_wavefront.h, compiled here for SOLID = true and for nothing else, as nx_wavefront_detail.hip and
+// nx_wavefront_metal.hip do for their parameters (and a unit of its own for their reasons: the other families keep their neighbours, the
+// build compiles this one beside them): every context without such a material launches the kernels it always did.  SOLID
 // instances are METAL instances (and with that DETAIL ones: the general material launch, no NO_MAPS form) — those know all five material
 // types and read a detail record that may name no map, so one family serves every table; refresh_shade_inst provides the detail records
 // while the family is in use.  No tail kernel: tail_bounce is 0 while the family is.
-#define NX_WAVEFRONT_INSTANCES_ONLY 1
-#include "nx_wavefront.hip"
+#define NX_KERNEL_TU 1
+#include "nx_wavefront.h"
 
 namespace nxd {
 

@@ -62,7 +62,7 @@ int nxd::fail_invalid(const std::string& msg) { return fail_invalid(msg.c_str())
 static int check_layouts()
 {
     const struct { const char* unit; uint64_t stamp; } units[] = {
-        {"nx_trace.hip", layout_stamp_trace()}, {"nx_wavefront.hip", layout_stamp_wavefront()}, {"nx_wavefront_detail.hip", layout_stamp_wavefront_detail()}, {"nx_wavefront_solid.hip", layout_stamp_wavefront_solid()}, {"nx_wavefront_metal.hip", layout_stamp_wavefront_metal()}, {"nx_medium.hip", layout_stamp_medium()}, {"nx_refit.hip", layout_stamp_refit()}, {"nx_skin.hip", layout_stamp_skin()},
+        {"nx_trace.hip", layout_stamp_trace()}, {"nx_wavefront.hip", layout_stamp_wavefront()}, {"nx_wavefront_detail.hip", layout_stamp_wavefront_detail()}, {"nx_wavefront_solid.hip", layout_stamp_wavefront_solid()}, {"nx_wavefront_metal.hip", layout_stamp_wavefront_metal()}, {"nx_hook_kernels.hip", layout_stamp_hook_kernels()}, {"nx_medium.hip", layout_stamp_medium()}, {"nx_refit.hip", layout_stamp_refit()}, {"nx_skin.hip", layout_stamp_skin()},
         {"nx_lbvh.hip", layout_stamp_lbvh()}, {"nxhip_multigpu.hip", layout_stamp_multigpu()}, {"nx_entry.hip", layout_stamp_entry()}, {"nx_aov.hip", layout_stamp_aov()},
         {"nx_adaptive.hip", layout_stamp_adaptive()}, {"nx_lights.hip", layout_stamp_lights()}, {"nx_envmap.hip", layout_stamp_envmap()}, {"nxhip_scene.hip", layout_stamp_scene()},
         {"nxhip_render.hip", layout_stamp_render()}, {"nxhip_features.hip", layout_stamp_features()}, {"nxhip_hooks.hip", layout_stamp_hooks()},
@@ -132,7 +132,7 @@ static size_t queue_buffer_slots(size_t n) { return queue_region_cap(n) * kQueue
 // entries per list of rays handed to the thin kernel (nx_trace.hip): a launch hands over at most DeviceState::thinLanes (16) rays per wave, 81 920 for a
 // full grid if every wave handed over as many as it may; a list that runs over only makes the waves it has no room for finish their rays themselves
 constexpr uint32_t kThinListEntries = 1u << 15;  // (x 2 lists x (4 B + a 320-byte ThinState) = 21 MB per slot)
-static size_t scan_status_tiles(size_t n) { return n / (size_t)std::min(kLogicBlockThreads, kShadeBlockThreads) + 2; }
+static size_t scan_status_tiles(size_t n) { return n / (size_t)std::min(kLogicBlock, kShadeBlock) + 2; }
 
 static TraceQueue trace_queue_of(const PassSlot* s)
 {
@@ -496,16 +496,16 @@ int nxhip_create(int device, uint32_t width, uint32_t height, void* stream, nxhi
         int perCU = 0;
         const void* const closest = kernels::trace(0u).fn, * const anyHit = kernels::trace(kTfAnyHit).fn;
         if (!closest || !anyHit) { rc = fail_invalid("nxhip_create: no trace_kernel instance of set 0 or of set kTfAnyHit is compiled"); break; }
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, closest, kTraceBlockThreads, 0) != hipSuccess || perCU < 1) perCU = 4;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, closest, kTraceBlock, 0) != hipSuccess || perCU < 1) perCU = 4;
         c->traceBlocks = std::max(1, perCU) * c->numCUs;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, anyHit, kTraceBlockThreads, 0) != hipSuccess || perCU < 1) perCU = 4;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, anyHit, kTraceBlock, 0) != hipSuccess || perCU < 1) perCU = 4;
         c->shadowBlocks = std::max(1, perCU) * c->numCUs;
         c->wideBlocks = 8 * c->numCUs;
         static_assert(sizeof c->tailBlocks / sizeof c->tailBlocks[0] == kMfAll + 1u, "one entry per set of material features");
         for (unsigned set = 0; set <= kMfAll; set++) {  // (every tail instance some unit compiled: a set without one keeps 0)
             const void* const tail = kernels::tail(set).fn;
             if (!tail) continue;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, tail, kTraceBlockThreads, 0) != hipSuccess || perCU < 1) perCU = 2;
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, tail, kTraceBlock, 0) != hipSuccess || perCU < 1) perCU = 2;
             c->tailBlocks[set] = std::max(1, perCU) * c->numCUs;
         }
         // Launch-geometry knobs of the measurement sweeps.  They are read only when NX_TUNING_KNOBS=1 says

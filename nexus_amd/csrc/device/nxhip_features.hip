@@ -524,7 +524,7 @@ int nxhip_denoise(nxhip_ctx* c, const nx_denoise_params* params)
         c->dnRgba8 = std::move(rgba);
     }
     // on the context's stream: behind the accumulates already issued
-    NX_TRY(launch_now(c, make_launch(kernels::denoise_gather(), c->wideBlocks, kWideBlockThreads, NXHIP_K_ACCUMULATE, c->dState.as<DeviceState>(), c->dnColour.as<float4>(),
+    NX_TRY(launch_now(c, make_launch(kernels::denoise_gather(), c->wideBlocks, kWideBlock, NXHIP_K_ACCUMULATE, c->dState.as<DeviceState>(), c->dnColour.as<float4>(),
                                    c->dnAlbedo.as<float4>(), c->dnNormalDepth.as<float4>(), p.iterations == 0u ? c->dnRgba8.as<uint32_t>() : nullptr)));
     bool forceDirect = false;  // (sweeps only: the plane variant for steps 1 and 2 too)
     if (const char* on = std::getenv("NX_TUNING_KNOBS"); on && std::atoi(on) == 1)

@@ -56,11 +56,11 @@ static int run_trace_chunk(nxhip_ctx* c, bool anyHit, uint32_t n, bool transmit 
     const unsigned set = hook_trace_features(c, anyHit, transmit);
     const kernels::BounceKernel trace = kernels::trace(set);
     if (!trace.fn) return fail_invalid("ray batch: trace_kernel has no instance of feature set " + std::to_string(set));
-    Launch l = make_launch(trace, anyHit ? c->shadowBlocks : c->traceBlocks, kTraceBlockThreads,
+    Launch l = make_launch(trace, anyHit ? c->shadowBlocks : c->traceBlocks, kTraceBlock,
                            anyHit ? NXHIP_K_SHADOW : NXHIP_K_TRACE, c->dState.as<DeviceState>(), kHookBounceSlot | (thin ? kTraceThinFlag : 0));
     int rc = launch_now(c, l);
     if (rc == NXHIP_OK && thin) {  // (nxhip_debug_set_thin: what the dry waves handed over, a wave each)
-        Launch t = make_launch(kernels::thin(), 3 * c->numCUs, kTraceBlockThreads, NXHIP_K_THIN, c->dState.as<DeviceState>(), kHookBounceSlot);
+        Launch t = make_launch(kernels::thin(), 3 * c->numCUs, kTraceBlock, NXHIP_K_THIN, c->dState.as<DeviceState>(), kHookBounceSlot);
         rc = launch_now(c, t);
     }
     return rc;
@@ -199,7 +199,7 @@ static int bsdf_hook(nxhip_ctx* c, const nx_material* material, const nx_bsdf_qu
     NX_TRY(one.rc);
     const nx_bsdf_query* dQ = b.in(queries, 1);
     nx_bsdf_result* dR = b.out(results, 1);
-    // (NX_MAT_METALROUGH has a kernel of its own: nx_wavefront_metal.hip — the four reference types keep theirs)
+    // (NX_MAT_METALROUGH has a kernel of its own: bsdf_hook_metal_kernel, nx_hook_kernels.hip — the four reference types keep theirs)
     return b.run(material->type == NX_MAT_METALROUGH ? kernels::bsdf_hook_metal() : kernels::bsdf_hook(), dMat, dQ, count, sample, dR);
 }
 

@@ -231,7 +231,7 @@ int nxhip_mgpu_gather(nxhip_ctx* c)
     if (rc != NXHIP_OK) return rc;
     if (c->mgpuRank == 0) {
         for (int k = 0; k < c->mgpuWorld; k++) {
-            NX_HIP(launch_untimed(kernels::compose(), c->wideBlocks, kWideBlockThreads, c->stream, c->mgpuGathered.as<float4>() + (size_t)k * n, n,
+            NX_HIP(launch_untimed(kernels::compose(), c->wideBlocks, kWideBlock, c->stream, c->mgpuGathered.as<float4>() + (size_t)k * n, n,
                                   c->mgpuMaps.as<uint32_t>() + (size_t)k * n, c->mgpuFullAccum.as<float4>(), c->mgpuFullRgba8.as<uint32_t>()));
         }
     }

@@ -1115,7 +1115,7 @@ try {
     c->hostMaterials.assign(materials, materials + count);
     // The device copy carries one derived flag in the padding byte behind `type` (offset 57 of the 60-byte record): the
     // material can emit or let a path pass through, i.e. its shading may look at / must keep the path's previous vertex
-    // (nx_wavefront.hip keep_previous_vertex).  The logic kernel reads type and flag with the one load it already does.
+    // (nx_wavefront.h keep_previous_vertex).  The logic kernel reads type and flag with the one load it already does.
     std::vector<nx_material> dev(materials, materials + count);
     for (nx_material& m : dev) {
         // "can emit" exactly as shade_path tests it: maxcomp3(emissive * intensity) > 0 (a negative intensity with a negative
@@ -1324,8 +1324,8 @@ try {
     NX_ALLOC(freshRho, (size_t)voxels * 4);
     NX_ALLOC(freshBricks, (size_t)bricks * 4);
     NX_HIP(hipMemcpy(freshRho.p, rho, (size_t)voxels * 4, hipMemcpyHostToDevice));
-    const int blocks = (int)std::min<uint32_t>((bricks + (uint32_t)kWideBlockThreads - 1u) / (uint32_t)kWideBlockThreads, 4096u);
-    NX_HIP(launch_untimed(kernels::medium_brick(), blocks, kWideBlockThreads, c->stream, freshRho.as<float>(), nx, ny, nz, nbx, nby, nbz, freshBricks.as<float>()));
+    const int blocks = (int)std::min<uint32_t>((bricks + (uint32_t)kWideBlock - 1u) / (uint32_t)kWideBlock, 4096u);
+    NX_HIP(launch_untimed(kernels::medium_brick(), blocks, kWideBlock, c->stream, freshRho.as<float>(), nx, ny, nz, nbx, nby, nbz, freshBricks.as<float>()));
     NX_HIP(hipStreamSynchronize(c->stream));  // (a setter, not the launch path: the other slots' streams may read the bricks next)
     c->mediumRho = std::move(freshRho);
     c->mediumBricks = std::move(freshBricks);
@@ -1366,7 +1366,7 @@ static bool env_timing()
 
 static int build_env_tables_float(nxhip_ctx* c);
 
-// Sampling distribution of the environment map (see nx_wavefront.hip, "Environment importance sampling"): texel weight =
+// Sampling distribution of the environment map (see nx_wavefront.h, "Environment importance sampling"): texel weight =
 // luminance of the sRGB-decoded texel x sin(polar angle of its row) + 1e-6, accumulated in double; cdfs as float ending in
 // exactly 1; density = weight / total x width x height / (2 pi^2) = pdf per solid angle x cos(latitude).  (An 8-bit map; a float
 // map's tables have the same layout and meaning and are built by build_env_tables_float below.)
@@ -1415,7 +1415,7 @@ static int build_env_tables(nxhip_ctx* c)
         run += rowSum[y];
         marginal[y] = y == H - 1 ? 1.0f : (float)(run / total);
     }
-    // guides for the device's cdf inversion (nx_wavefront.hip cdf_find): bracket per bucket of the random number
+    // guides for the device's cdf inversion (nx_wavefront.h cdf_find): bracket per bucket of the random number
     auto make_guide = [](const float* cdf, uint32_t n, uint32_t* guide) {
         uint32_t idx = 0;
         for (int b = 0; b <= kEnvGuide; b++) {

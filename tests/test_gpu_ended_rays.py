@@ -1,4 +1,4 @@
-"""Continuation rays the Russian roulette has already ended (nx_wavefront.hip shade_scan_type, kShadeDropEnded): under the SCAN
+"""Continuation rays the Russian roulette has already ended (nx_wavefront.h shade_scan_type, kShadeDropEnded): under the SCAN
 pipeline with pixel-keyed random numbers and no miss type in the pass (no environment map, black background) the material launch
 does not queue a continuation ray whose roulette draw it has just lost — nothing could read what such a ray hits.  The bar: every
 frame, accumulation, RGBA8 image and queue size stays the oracle's (which queues and traces those rays), the drop is off wherever a

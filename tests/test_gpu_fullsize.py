@@ -87,7 +87,7 @@ def test_config2_one_million_triangles_1080p(gpu_ctx_factory):
 def test_config2_reference_semantics_on_the_whole_chip(gpu_ctx_factory):
     """configs[1] with the reference's own semantics — random numbers keyed by queue slot, slots in serial order, no conductor
     kernel (PathTracer.cu:143, 326, 475-478; Random.cuh:79-82) — at full size: 2 M paths are some 8 000 tiles of the
-    grid-wide ordered compaction (tickets + decoupled look-back, nx_wavefront.hip), every one of whose slots decides which
+    grid-wide ordered compaction (tickets + decoupled look-back, nx_wavefront.h), every one of whose slots decides which
     random numbers a path draws next.  The oracle renders the whole frame serially; radiance and every queue size of every
     bounce must be equal."""
     W, H = 1920, 1080

@@ -1,16 +1,14 @@
-"""Register / scratch / LDS footprint of every device kernel, from the compiler's own metadata (hipcc -S of the device files
-with the Makefile's flags): VGPRs, AGPRs, SGPRs, spilled VGPRs, scratch bytes per lane, LDS bytes, occupancy (waves per SIMD).
+"""Register / scratch / LDS footprint of every device kernel, from the compiler's own metadata (the assembly `make asm` writes to
+build/asm/, one file per device unit, with the Makefile's flags): VGPRs, AGPRs, SGPRs, spilled VGPRs, scratch bytes per lane, LDS
+bytes, occupancy (waves per SIMD).  `make asm` runs first, so a missing or stale file is rebuilt.  --all: the sort library's kernels too.
     python tools/kernel_resources.py > profiles/r03_kernel_resources.txt"""
 import glob
 import os
 import re
 import subprocess
 import sys
-import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FLAGS = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Iinclude", "-Inexus_amd/csrc/device", "-Inexus_amd/csrc/host", "-fno-slp-vectorize", "-mllvm", "-amdgpu-use-amdgpu-trackers=1", "-mllvm", "-amdgpu-sched-strategy=max-memory-clause",
-         "--offload-arch=gfx950", "-DNX_BUILT_FOR_GFX950=1", "-S", "--cuda-device-only"] + [a for a in sys.argv[1:] if a != "--all"]
 
 
 def demangle(names):
@@ -35,13 +33,11 @@ def named(n):
 
 
 print("%-58s %5s %5s %5s %7s %8s %6s %5s" % ("kernel", "VGPR", "AGPR", "SGPR", "spilled", "scratch", "LDS", "occ"))
+made = subprocess.run(["make", "-j16", "asm"], cwd=ROOT, capture_output=True, text=True)
+if made.returncode != 0:
+    sys.exit("make asm failed:\n" + made.stderr[-2000:])
 for src in sorted(glob.glob(os.path.join(ROOT, "nexus_amd/csrc/device/*.hip"))):
-    with tempfile.NamedTemporaryFile(suffix=".s") as tmp:
-        r = subprocess.run(["/opt/rocm/bin/hipcc"] + FLAGS + ["-o", tmp.name, src], cwd=ROOT, capture_output=True, text=True)
-        if r.returncode != 0:
-            print("# %s: %s" % (os.path.basename(src), r.stderr.strip().split("\n")[-1]))
-            continue
-        text = open(tmp.name).read()
+    text = open(os.path.join(ROOT, "build/asm", os.path.basename(src)[:-4] + ".s")).read()
     rows = []
     for m in re.finditer(r"- \.agpr_count:\s+(\d+)(.*?)\.wavefront_size", text, re.S):
         blk = m.group(0)
