@@ -764,6 +764,13 @@ int nxhip_debug_read_primary_rays(nxhip_ctx *ctx, float *origin3, float *directi
  * bits of the graph the last pass replayed; 256 = trace instances without the transform path, 512 = map-free material launch.
  * forceGeneral: those of the two bits whose specialised instances later passes must not use (0xffffffff: unchanged). */
 int nxhip_debug_pass_flavor(nxhip_ctx *ctx, uint32_t forceGeneral, uint32_t *flavor);
+/* Test hook: the compile-time instance sets (nx_variants.h: kMf* material features, kTf* trace features) the launches of the last pass
+ * were looked up by, as recorded when the graph the pass replayed was built — beside its flavor word, not recomputed from the context
+ * at the call.  sets[0] the SCAN pipeline's material launch; sets[1] the tail kernel and sets[2] the bounce it takes over from;
+ * sets[3] the medium's scatter kernel, bit 16 set for the GRID form; sets[4] the classic pipeline's logic kernel; sets[5], sets[6],
+ * sets[7] the primary, the closest-hit and the any-hit trace launches.  A family the pass does not launch reads 0xffffffff (so do
+ * sets[1] and sets[2] without a tail kernel).  NXHIP_ERR_INVALID with a message: no pass has been rendered, or a NULL array. */
+int nxhip_debug_pass_instances(nxhip_ctx *ctx, uint32_t sets[8]);
 /* Test hook for the thin kernel (nx_trace.hip): the hand-over rule — at most `lanes` busy lanes of a dry wave for at least `iters`
  * iterations (product: 16 / 16; 64 / 0 makes every wave hand over the first rays it takes, after one iteration) — and whether the ray-batch
  * hooks (nxhip_trace_batch, nxhip_trace_shadow_batch) use the hand-over + thin launch too, so that a test can put arbitrary rays

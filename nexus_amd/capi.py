@@ -1061,6 +1061,22 @@ class Context:
         check(self.L.nxhip_debug_pass_flavor(self.h, 0xffffffff if force_general is None else int(force_general), C.byref(f)), "nxhip_debug_pass_flavor")
         return int(f.value)
 
+    PASS_INSTANCE_WORDS = ("scan", "tail", "tail_bounce", "medium", "logic", "primary", "closest", "any_hit")
+    NO_INSTANCE = 0xFFFFFFFF
+    MEDIUM_GRID_FORM = 0x10000
+
+    def debug_pass_instances(self):
+        """the instance sets (nx_variants.h) the last pass's launches were looked up by, as recorded when its graph was built: a dict over
+        PASS_INSTANCE_WORDS plus "medium_grid" (bool, None without a medium); None for a family the pass did not launch — a test hook:
+        include/nexus_hip.h"""
+        out = (C.c_uint32 * 8)()
+        check(self.L.nxhip_debug_pass_instances(self.h, out), "nxhip_debug_pass_instances")
+        got = {k: (None if int(v) == self.NO_INSTANCE else int(v)) for k, v in zip(self.PASS_INSTANCE_WORDS, out)}
+        got["medium_grid"] = None if got["medium"] is None else bool(got["medium"] & self.MEDIUM_GRID_FORM)
+        if got["medium"] is not None:
+            got["medium"] &= ~self.MEDIUM_GRID_FORM
+        return got
+
     def read_entry_states(self):
         """(runs, 40) int32: the entry states of the last pass; column 19 = node steps saved, 16 = stack entries, 18 = instance record,
         31 = instance record of the triangle the walk consumed (-1: none), 35 = triangles it skipped, 38 / 39 = the run's hit-distance

@@ -140,6 +140,9 @@ struct PassSlot {
         int flavor = 0;  // pass_flavor(): pipeline, miss kernel, logic kernel variant, ..., the scene-specialised kernel instances
         int shape = 0;   // graph_shape(): 0 = the levels' launches side by side, 1 = every level a chain (the lanes do not fit the queue budget)
         uint32_t nodes = 0, edges = 0, fanOut = 0;  // of `graph`, as the runtime reports them (measure_graph; nxhip_debug_last_graph)
+        // the instance sets (nx_variants.h) frame_levels looked the graph's kernels up by, recorded when the graph was built
+        // (nxhip_debug_pass_instances; 0xffffffff: a family the graph does not launch)
+        uint32_t sets[8] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu};
     };
     std::vector<GraphInstance> graphs;
     // pass bookkeeping (slots >= 1 and slot 0 alike)
@@ -277,6 +280,7 @@ struct nxhip_ctx : nxd::PassSlot {
     float mediumRhoMax = 0.0f;
     int flavorForceGeneral = 0;  // nxhip_debug_pass_flavor: the kFlavor* bits of specialised kernel instances a pass must not use
     int lastPassFlavor = 0;      // pass_flavor() of the last pass issued (nxhip_debug_pass_flavor)
+    uint32_t lastPassSets[8] = {};  // GraphInstance::sets of the graph the last pass replayed (nxhip_debug_pass_instances)
     bool thinInHooks = false;  // nxhip_debug_set_thin: the ray-batch hooks hand over and launch the thin kernel too
     bool dead = false;          // nxhip_sync_timeout gave up: no further device work is issued or waited for
     int pixelOrder = 0;         // nxhip_set_pixel_order: NXHIP_ORDER_* of the full frame, re-applied by nxhip_resize (a caller's own map is not)

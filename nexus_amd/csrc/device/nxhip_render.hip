@@ -384,6 +384,11 @@ constexpr unsigned trace_features(int flavor, bool anyHit, bool primary, bool co
     if (f & kTfTransmit) f &= ~kTfIdentity;                // (reads sceneFlags: no IDENTITY form)
     return f;
 }
+// The words of nxhip_debug_pass_instances (include/nexus_hip.h), and what a family the pass does not launch reads
+constexpr int kSetScanMaterial = 0, kSetTail = 1, kSetTailBounce = 2, kSetMedium = 3, kSetLogic = 4, kSetPrimaryTrace = 5, kSetClosestTrace = 6, kSetAnyHitTrace = 7;
+constexpr int kPassInstanceWords = 8;
+constexpr uint32_t kSetMediumGridBit = 0x10000u, kNoInstanceSet = 0xffffffffu;  // (bit 16 of the medium's word: the GRID form of the set)
+static_assert(kPassInstanceWords == (int)(sizeof(PassSlot::GraphInstance::sets) / sizeof(uint32_t)) && (kMfAll & kSetMediumGridBit) == 0u, "the report's words");
 // (build-time tests of the selection, for the flavors that matter)
 static_assert(material_features(kFlavorScan) == 0u && trace_features(kFlavorScan, false, true, false) == 0u && trace_features(kFlavorScan, true, false, false) == kTfAnyHit,
               "the default scan flavor: no feature");
@@ -412,7 +417,9 @@ static_assert(trace_features(kFlavorIdentity, false, false, true) == kTfCounting
 
 // The per-frame kernel sequence, in dependency "levels": launches of one level may run concurrently, a level
 // starts after the previous one has finished.  Reference DAG: Renderer/PathTracer.cpp:114-124, :259-278.
-std::vector<std::vector<Launch>> frame_levels(nxhip_ctx* c, PassSlot* q)
+// `sets` (may be null): the instance sets the launches were looked up by, a family the pass does not launch as kNoInstanceSet
+// (nxhip_debug_pass_instances: kept beside the flavor of the graph instance built from these levels).
+std::vector<std::vector<Launch>> frame_levels(nxhip_ctx* c, PassSlot* q, uint32_t* sets = nullptr)
 {
     const DeviceState* S = q->dState.as<DeviceState>();
     const bool stats = c->statsEnabled;
@@ -425,6 +432,11 @@ std::vector<std::vector<Launch>> frame_levels(nxhip_ctx* c, PassSlot* q)
     const unsigned primaryTrace = trace_features(flavor, false, true, stats), closestTrace = trace_features(flavor, false, false, stats), anyHitTrace = trace_features(flavor, true, false, stats);
     // the chain shape (graph_shape): every launch of a level behind the one in front of it, in the order the level lists them
     const bool chain = graph_shape(c) == kShapeChain;
+    uint32_t looked[kPassInstanceWords];  // what nxhip_debug_pass_instances reports: written where a launch is made, nowhere else
+    for (uint32_t& w : looked) w = kNoInstanceSet;
+    auto report = [&]() {
+        if (sets) std::memcpy(sets, looked, sizeof looked);
+    };
     auto shaped = [=](std::vector<std::vector<Launch>>& ls) {
         // (a set no unit compiled — unreachable while the units' lists cover the feature functions: the pass is refused, nothing launched)
         for (auto& level : ls)
@@ -450,6 +462,7 @@ std::vector<std::vector<Launch>> frame_levels(nxhip_ctx* c, PassSlot* q)
     const bool transmit = (flavor & kFlavorTransmit) != 0, alphaTest = (flavor & kFlavorAlphaTest) != 0;  // (alphaTest: entry, identity and the thin flags below are all off — pass_flavor)
     // the any-hit launch of a bounce: the TRANSMIT and the ALPHA_TEST instances never hand over (no kTraceThinFlag)
     auto shadow_launch = [&](int shadowBlocksArg, int bounceArg, int thinFlagArg) {
+        looked[kSetAnyHitTrace] = anyHitTrace;
         return make_launch(kernels::trace(anyHitTrace), shadowBlocksArg, kTraceBlock, NXHIP_K_SHADOW, S, bounceArg | ((transmit || alphaTest) ? 0 : thinFlagArg));
     };
     const int traceBlocks = trace_blocks(c, c->traceBlocks), shadowBlocks = trace_blocks(c, c->shadowBlocks);
@@ -460,7 +473,11 @@ std::vector<std::vector<Launch>> frame_levels(nxhip_ctx* c, PassSlot* q)
     const int thinFlagClosest = (metal && scan_pipeline(c)) ? 0 : thinFlag;
     // (with entry points the primary launch is its own kernel instance: the only one that carries the install code)
     // the closest-hit launch of a bounce (not the primary one with entry points, below)
-    auto closest_kernel = [&]() { return kernels::trace(closestTrace); };
+    auto closest_kernel = [&]() {
+        looked[kSetClosestTrace] = closestTrace;
+        return kernels::trace(closestTrace);
+    };
+    looked[kSetPrimaryTrace] = primaryTrace;
     levels.push_back({make_launch(kernels::trace(primaryTrace), traceBlocks, kTraceBlock, NXHIP_K_TRACE, S,
                                   (entry ? kTraceEntryFlag : 0) | thinFlagClosest | (scan_pipeline(c) ? kTraceScanFlag : 0))});
     // behind the trace launch(es) of a level: the rays their dry waves handed over, a wave each (thin_kernel)
@@ -509,6 +526,8 @@ std::vector<std::vector<Launch>> frame_levels(nxhip_ctx* c, PassSlot* q)
         for (int bounce = 1; bounce <= pathLength; bounce++) {
             if (bounce == tailFrom) {  // the rest of the pass in one launch
                 const unsigned tail = tail_features(flavor);  // (its grid: the instance's own, nxhip_create)
+                looked[kSetTail] = tail;
+                looked[kSetTailBounce] = (uint32_t)bounce;
                 levels.push_back({make_launch(kernels::tail(tail), c->tailBlocks[tail], kTraceBlock, NXHIP_K_SHADE, S, bounce | kTraceScanFlag)});
                 break;
             }
@@ -518,7 +537,9 @@ std::vector<std::vector<Launch>> frame_levels(nxhip_ctx* c, PassSlot* q)
             if (misses) mask |= 1 << kScanMiss;
             if (metal) mask |= 1 << kScanMetalBit;  // (the type's own number is the misses' bit: nx_device.h)
             // the medium's free-flight decision over the records the closest-hit level left, in front of the material launch that reads them
+            if (medium) looked[kSetMedium] = mediumSet | (mediumGrid ? kSetMediumGridBit : 0u);
             if (medium) levels.push_back({make_launch(kernels::medium_scatter(mediumGrid, mediumSet), whole_regions(wide), kShadeBlock, NXHIP_K_SHADE, S, bounce | dropFlag)});
+            looked[kSetScanMaterial] = mat;
             levels.push_back({make_launch(kernels::shade_scan(mat), og, kShadeBlock, NXHIP_K_SHADE, S, bounce | dropFlag, mask)});
             if (bounce == 1) aov_beside(levels.back());
             if (in_use(NX_MAT_CONDUCTOR) && c->h.conductorMode != NX_CONDUCTOR_EXTENDED) {  // (counted, not shaded: count_scan_kernel)
@@ -536,6 +557,7 @@ std::vector<std::vector<Launch>> frame_levels(nxhip_ctx* c, PassSlot* q)
             }
             thin_level(bounce | kTraceScanFlag);
         }
+        report();
         return shaped(levels);
     }
     // CLASSIC pipeline (ordered compaction; no tail kernel: tail_bounce): per bounce logic kernel -> the material kernels of the
@@ -547,6 +569,7 @@ std::vector<std::vector<Launch>> frame_levels(nxhip_ctx* c, PassSlot* q)
         // float map it would read float4 texels as RGBA8.  The two-item instance is for scenes with no environment map of either kind;
         // the same test as pass_flavor's kFlavorEnvMap (hdrMap.texels is set for both kinds: nxhip_scene.hip).
         const int items = c->hdrMap.texels.p ? 1 : 2;
+        looked[kSetLogic] = logic_features(flavor, items);
         levels.push_back({make_launch(kernels::logic(items, logic_features(flavor, items)), lg, lb, NXHIP_K_LOGIC, S, bounce)});
         if (bounce == 1) aov_beside(levels.back());
         // (the fifth type's queue is filled by a kernel of its own behind the reference's logic kernel: nx_wavefront_metal.hip)
@@ -567,6 +590,7 @@ std::vector<std::vector<Launch>> frame_levels(nxhip_ctx* c, PassSlot* q)
                           shadow_launch(shadowBlocks, bounce, thinFlag)});
         thin_level(bounce);
     }
+    report();
     return shaped(levels);
 }
 
@@ -665,7 +689,7 @@ static int pass_graph(nxhip_ctx* c, PassSlot* q, hipGraphExec_t* execOut)
         if (inst.graph) (void)hipGraphDestroy(inst.graph);
         return rc;
     };
-    auto levels = frame_levels(c, q);
+    auto levels = frame_levels(c, q, inst.sets);
     if (levels.empty()) return fail(NXHIP_ERR_INVALID);  // (a kernel instance nobody compiled: frame_levels has said which)
     std::vector<hipGraphNode_t> prev;
     for (auto& level : levels) {
@@ -832,7 +856,7 @@ try {
     c->lastPassFlavor = pass_flavor(c);  // (what the eager path's launches and the graph below are chosen by)
     if (c->timingEnabled && c->timingMode == 1) {
         // eager path: one event pair per launch, launches strictly in level order on one stream
-        auto levels = frame_levels(c, q);
+        auto levels = frame_levels(c, q, c->lastPassSets);
         if (levels.empty()) return NXHIP_ERR_INVALID;  // (a kernel instance nobody compiled: frame_levels has said which)
         for (auto& level : levels)
             for (auto& l : level) NX_TRY(launch_now(c, l));
@@ -843,7 +867,10 @@ try {
         NX_TRY(pass_graph(c, q, &exec));
         NX_HIP(hipGraphLaunch(exec, q->stream));
         for (const auto& g : q->graphs)
-            if (g.exec == exec) { c->lastGraphNodes = g.nodes; c->lastGraphEdges = g.edges; c->lastGraphFanOut = g.fanOut; }
+            if (g.exec == exec) {
+                c->lastGraphNodes = g.nodes; c->lastGraphEdges = g.edges; c->lastGraphFanOut = g.fanOut;
+                std::memcpy(c->lastPassSets, g.sets, sizeof g.sets);  // (as recorded when the instance was built: pass_graph)
+            }
         if (c->timingMode == 3) c->graphTimersPending = true;  // read at nxhip_read_kernel_times: the last replay only
         if (c->timingMode == 2) {
             // the graph's events are re-recorded by the next replay: read them now (timing mode is not the fast path)
@@ -995,6 +1022,19 @@ int nxhip_debug_pass_flavor(nxhip_ctx* c, uint32_t forceGeneral, uint32_t* flavo
     if (forceGeneral != 0xffffffffu && (forceGeneral & ~(uint32_t)kFlavorSpecialised)) return fail_invalid("nxhip_debug_pass_flavor: forceGeneral may name bits 8 (identity) and 9 (no maps) only");
     if (flavor) *flavor = (uint32_t)c->lastPassFlavor;
     if (forceGeneral != 0xffffffffu) c->flavorForceGeneral = (int)forceGeneral;  // (read by pass_flavor at the next pass: another graph)
+    return NXHIP_OK;
+}
+
+// The instance sets of the last pass issued: what frame_levels looked its kernels up by when the graph instance the pass replayed was
+// built (PassSlot::GraphInstance::sets, beside its flavor) — or, on the eager timing path, when the pass was issued.  Nothing is
+// recomputed from the context here: a test holds the selection to the scene with this, not the selection to itself.
+int nxhip_debug_pass_instances(nxhip_ctx* c, uint32_t sets[8])
+{
+    NX_DEBUG_HOOK("nxhip_debug_pass_instances");  // (first: a release library refuses whatever it is handed)
+    NX_CHECK_CTX(c);
+    if (!sets) return fail_invalid("nxhip_debug_pass_instances: null destination");
+    if (!c->lastRendered) return fail_invalid("nxhip_debug_pass_instances: no pass has been rendered");
+    std::memcpy(sets, c->lastPassSets, sizeof c->lastPassSets);
     return NXHIP_OK;
 }
 
