@@ -679,13 +679,19 @@ void orc_wavefront_render(orc_wavefront *w, uint32_t frameNumber, int nthreads)
     }
 }
 
-/* Tonemap + LinearToGamma + ToColorUInt — PathTracer.cu:37-62, Utils/Utils.h:51-54 */
+/* Tonemap + LinearToGamma + ToColorUInt — PathTracer.cu:37-62, Utils/Utils.h:51-54.  The text of nx_tonemap.h, whose header
+ * comment states the display contract: x saturated at 1e9 before the polynomials (they overflow to inf / inf = NaN from
+ * x = 1.2e19 on, which displayed black; the comparison is false for a NaN), and the clamp of the quotient written out so that a
+ * NaN, a -0 and a negative quotient all become +0 with every compiler. */
 uint32_t orc_tonemap_rgba8(const float rgb[3])
 {
+    const float kSaturate = 1.0e9f;
     uint32_t out = 0;
     for (int c = 0; c < 3; c++) {
         float x = rgb[c] * 0.6f;
-        x = clampf((x * (2.51f * x + 0.03f)) / (x * (2.43f * x + 0.59f) + 0.14f), 0.0f, 1.0f);
+        x = x > kSaturate ? kSaturate : x;
+        const float q = (x * (2.51f * x + 0.03f)) / (x * (2.43f * x + 0.59f) + 0.14f);
+        x = q > 0.0f ? (q < 1.0f ? q : 1.0f) : 0.0f;
         x = (float)nxf_pow((double)x, 0.45454545454);
         x = clampf(x, 0.0f, 1.0f);
         out |= (uint32_t)(uint8_t)(x * 255.0f) << (8 * c);

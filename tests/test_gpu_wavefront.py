@@ -203,10 +203,9 @@ def test_frames_per_pass_equals_single_frames(gpu_ctx_factory):
 def test_short_last_pass_and_compose_tiles(gpu_ctx_factory):
     """A frame budget that is not a multiple of frames-per-pass ends with a shorter pass (no reset of the frame counter
     or the accumulation), and tiles accumulated per rank + nxhip_compose_tiles give the single-context image bit for bit."""
-    import ctypes as C
-
     W, H, frames, S = 64, 48, 7, 3
     from nexus_amd import multigpu
+    from tests.hip_buffers import DeviceBuffers
 
     scene = SH.material_zoo_scene(W, H, path_length=4)
     a = gpu_ctx_factory(W, H)
@@ -228,15 +227,10 @@ def test_short_last_pass_and_compose_tiles(gpu_ctx_factory):
     assert np.array_equal(b.read_rgba8(), rgba_ref)
 
     # two "ranks" on one GPU: interleaved tiles, per-rank accumulation, root-side composition into caller-owned buffers
-    hip = C.CDLL("libamdhip64.so.7")  # the HIP runtime libnexus_amd.so is already bound to (matched by soname)
-    hip.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-    hip.hipFree.argtypes = [C.c_void_p]
-    hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
     world = 2
     n_full = W * H
-    d_acc, d_rgba = C.c_void_p(), C.c_void_p()
-    assert hip.hipMalloc(C.byref(d_acc), n_full * 16) == 0 and hip.hipMalloc(C.byref(d_rgba), n_full * 4) == 0
-    try:
+    with DeviceBuffers() as dev:
+        d_acc, d_rgba = dev.alloc(n_full * 16), dev.alloc(n_full * 4)
         for r in range(world):
             pm = multigpu.tile_pixel_map(W, H, r, world, tile_rows=4)
             c = gpu_ctx_factory(W, H)
@@ -246,19 +240,10 @@ def test_short_last_pass_and_compose_tiles(gpu_ctx_factory):
             c.set_frames_per_pass(S)
             c.render(frames)
             c.sync()
-            d_map = C.c_void_p()
-            assert hip.hipMalloc(C.byref(d_map), len(pm) * 4) == 0
-            assert hip.hipMemcpy(d_map, pm.ctypes.data_as(C.c_void_p), len(pm) * 4, 1) == 0
-            c.compose_tiles(c.accumulation_device_ptr(), len(pm), d_map.value, d_acc.value, d_rgba.value)
+            c.compose_tiles(c.accumulation_device_ptr(), len(pm), dev.upload(np.ascontiguousarray(pm, np.uint32)), d_acc, d_rgba)
             c.sync()
-            hip.hipFree(d_map)
-        acc = np.zeros((n_full, 4), np.float32)
-        rgba = np.zeros(n_full, np.uint32)
-        assert hip.hipMemcpy(acc.ctypes.data_as(C.c_void_p), d_acc, n_full * 16, 2) == 0
-        assert hip.hipMemcpy(rgba.ctypes.data_as(C.c_void_p), d_rgba, n_full * 4, 2) == 0
-    finally:
-        hip.hipFree(d_acc)
-        hip.hipFree(d_rgba)
+        acc = dev.download(d_acc, (n_full, 4), np.float32)
+        rgba = dev.download(d_rgba, n_full, np.uint32)
     assert np.array_equal(acc[:, :3].view(np.uint32), acc_ref.reshape(-1, 3).view(np.uint32))
     assert np.array_equal(rgba, rgba_ref.reshape(-1))
 
