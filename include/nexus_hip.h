@@ -1013,6 +1013,20 @@ int nxhip_debug_set_scan_epoch(nxhip_ctx *ctx, uint32_t epoch);
  * round 5 until the host's watchdog ended the process).  The per-launch progress check must end every such launch with
  * NXHIP_ERR_TRAVERSAL from nxhip_sync within milliseconds. */
 int nxhip_debug_set_requeue(nxhip_ctx *ctx, int on);
+/* Test hook: the BINARY tree a device build collapses, which the build otherwise frees.  While `on`, every single build — nxhip_build_blas,
+ * nxhip_rebuild_tlas; not nxhip_build_blas_batch — copies its tree and the collapse's cost table to the host before it returns; the last
+ * one stays with the context (switching the hook off drops it).  Off, the default, costs a build one branch.
+ * nxhip_debug_read_binary_tree copies it out.  With n primitives: internal nodes 0 .. n-2 (the root is 0), leaf k = node n-1+k =
+ * primitive leafOrder[k].  left / right / count: n-1 entries; parent: 2n-1 (the root's is -1); box6: 2n-1 x {lo[3], hi[3]};
+ * leafOrder: n; eval: 7 (n-1) entries of 8 bytes {float cost; int8_t decision (0 leaf slot, 1 wide node, 2 distribute), leftCount,
+ * rightCount, pad}, entry i of node x at 7 x + i.  *primCost: the collapse's price of a primitive (0.75 for triangles, 4 for
+ * instances); *builder: the nxhip_set_device_builder value the build ran with.  A build of at most 8 primitives is a single node
+ * without a binary tree: *n == 0 and no array is written.  `capacity`: the primitives the arrays have room for.  *n, *primCost and
+ * *builder are filled whenever a tree is stashed; NXHIP_ERR_INVALID when none is, when capacity < *n, or when an array is null
+ * although *n > 0. */
+int nxhip_debug_keep_binary_tree(nxhip_ctx *ctx, int on);
+int nxhip_debug_read_binary_tree(nxhip_ctx *ctx, uint32_t capacity, uint32_t *n, float *primCost, int32_t *builder, int32_t *left, int32_t *right,
+                                 int32_t *parent, int32_t *count, float *box6, uint32_t *leafOrder, uint64_t *eval);
 
 /* Kernel-level test hooks for the shading functions (same role as nxhip_trace_batch for the traversal): run the device
  * BSDF sample / eval (the headers of Cuda/BSDF/ as restated in nx_bsdf.h) and the software texture fetch on host arrays.

@@ -776,6 +776,32 @@ class Context:
         """test hook: passes begun since the ordered compaction's status words were last cleared (wraps at 2^20)"""
         check(self.L.nxhip_debug_set_scan_epoch(self.h, int(epoch)), "nxhip_debug_set_scan_epoch")
 
+    def debug_keep_binary_tree(self, on=True):
+        """test hook: single device builds (build_blas, rebuild_tlas) keep their binary tree and cost table for debug_read_binary_tree"""
+        check(self.L.nxhip_debug_keep_binary_tree(self.h, 1 if on else 0), "nxhip_debug_keep_binary_tree")
+
+    def debug_read_binary_tree(self):
+        """the binary tree of the last single device build (include/nexus_hip.h): a dict of n, prim_cost, builder, left / right / count
+        int32[n - 1], parent int32[2n - 1], box float32[2n - 1, 2, 3], leaf_order uint32[n] and the cost table cost float32[n - 1, 7],
+        decision / left_count / right_count int8[n - 1, 7]; n == 0 (empty arrays) after a build of at most 8 primitives"""
+        n, cost, builder = C.c_uint32(0), C.c_float(0.0), C.c_int32(0)
+        rc = self.L.nxhip_debug_read_binary_tree(self.h, 0, C.byref(n), C.byref(cost), C.byref(builder), None, None, None, None, None, None, None)
+        if n.value == 0:
+            check(rc, "nxhip_debug_read_binary_tree")
+        m = int(n.value)
+        inner, nodes = max(m - 1, 0), max(2 * m - 1, 0)
+        left, right, count = (np.zeros(inner, np.int32) for _ in range(3))
+        parent = np.zeros(nodes, np.int32)
+        box = np.zeros((nodes, 2, 3), np.float32)
+        order = np.zeros(m, np.uint32)
+        table = np.zeros((inner, 7), dtype=np.dtype([("cost", "<f4"), ("decision", "i1"), ("leftCount", "i1"), ("rightCount", "i1"), ("pad", "i1")]))
+        if m:
+            check(self.L.nxhip_debug_read_binary_tree(self.h, m, C.byref(n), C.byref(cost), C.byref(builder), _ptr(left), _ptr(right), _ptr(parent), _ptr(count),
+                                                      _ptr(box), _ptr(order), _ptr(table)), "nxhip_debug_read_binary_tree")
+        return {"n": m, "prim_cost": float(cost.value), "builder": int(builder.value), "left": left, "right": right, "count": count, "parent": parent,
+                "box": box, "leaf_order": order, "cost": np.ascontiguousarray(table["cost"]), "decision": np.ascontiguousarray(table["decision"]),
+                "left_count": np.ascontiguousarray(table["leftCount"]), "right_count": np.ascontiguousarray(table["rightCount"])}
+
     def set_instance_transforms(self, instance_ids, transforms16):
         """move existing instances on the device (inverse, bounds, traversal records, TLAS refit): no scene re-upload"""
         ids = np.ascontiguousarray(instance_ids, dtype=np.uint32)

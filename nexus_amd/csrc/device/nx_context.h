@@ -235,6 +235,20 @@ struct nxhip_ctx : nxd::PassSlot {
     size_t hostStagingBytes = 0;
     hipEvent_t stagingDone[2] = {nullptr, nullptr};  // one per half of the staging buffer: its last transfer has completed
 
+    // nxhip_debug_keep_binary_tree: while on, a single device build (BLAS or TLAS; nx_lbvh.hip lbvh_from_boxes) copies its binary tree and
+    // the collapse's cost table here before it frees them (nxhip_debug_read_binary_tree).  n == 0: the single-node path, no tree.
+    struct BinaryTreeStash {
+        bool valid = false;
+        uint32_t n = 0;
+        float primCost = 0.0f;
+        int builder = 0;  // the deviceBuilderRadius the build ran with
+        std::vector<int32_t> left, right, count, parent;  // [n - 1] x 3, [2n - 1]
+        std::vector<float> box;                           // [2n - 1] x {lo[3], hi[3]}
+        std::vector<uint32_t> leafOrder;                  // [n]: leaf k (node n - 1 + k) = primitive leafOrder[k]
+        std::vector<uint64_t> eval;                       // [7 (n - 1)] 8-byte entries {float cost; int8 decision, leftCount, rightCount, pad}
+    };
+    bool keepBinaryTree = false;
+    BinaryTreeStash binaryTree;
     int deviceBuilderRadius = -1;  // nxhip_build_blas / nxhip_rebuild_tlas: -1 = top-down binned SAH (NXHIP_BUILDER_SAH), 0 = radix tree (LBVH), > 0 = neighbour search radius of the clustering builder
     uint32_t frameNumber = 0;  // host mirror of FrameState.frameNumber
     bool statsEnabled = false;

@@ -712,6 +712,7 @@ __global__ void __launch_bounds__(64) sah_small_kernel(const Box3* __restrict__ 
             const int first = stFirst[top], count = stCount[top], node = stNode[top];
             float bestCost = 3.0e38f;
             int bestPerm[kSahSmall], bestK = count / 2;
+            bool separable = false;  // some axis tells two centroids apart
             for (int k = 0; k < count; k++) bestPerm[k] = first + k;
             for (int a = 0; a < 3; a++) {
                 int perm[kSahSmall];
@@ -723,6 +724,7 @@ __global__ void __launch_bounds__(64) sah_small_kernel(const Box3* __restrict__ 
                     key[j] = c;
                     perm[j] = first + k;
                 }
+                separable = separable || key[0] < key[count - 1];
                 float above[kSahSmall];
                 Box3 run = empty_box();
                 for (int k = count - 1; k >= 1; k--) {
@@ -740,6 +742,11 @@ __global__ void __launch_bounds__(64) sah_small_kernel(const Box3* __restrict__ 
                     }
                 }
             }
+            // All centroids coincide on all three axes: nothing separates them, and the sweep's costs differ by their rounding alone —
+            // among copies of one triangle its first cut, 1 : count - 1, wins every time and the subtree is a chain.  Halves by
+            // position, as sah_split_kernel and the host builder do (the order is still the one the segment came in: a stable sort
+            // of equal keys).
+            if (!separable) bestK = count / 2;
             {  // the chosen order, in place
                 int nid[kSahSmall];
                 Box3 nbox[kSahSmall];
@@ -1327,6 +1334,12 @@ static int lbvh_from_boxes(nxhip_ctx* c, const DevBuf& triBox, const DevBuf& bou
         if (!nodes.alloc(sizeof(nx_bvh8_node))) return NXHIP_ERR_HIP;
         small_mesh_kernel<<<1, 64, 0, st>>>(triBox.as<Box3>(), (int)n, nodes.as<nx_bvh8_node>(), primIdx.as<uint32_t>());
         *nodeCount = 1;
+        if (c->keepBinaryTree) {  // (test hook: a single node has no binary tree)
+            c->binaryTree = nxhip_ctx::BinaryTreeStash{};
+            c->binaryTree.valid = true;
+            c->binaryTree.primCost = primCost;
+            c->binaryTree.builder = plocRadius;
+        }
         return NXHIP_OK;
     }
     DevBuf codes, codesSorted, order, orderSorted, sortTemp;
@@ -1432,6 +1445,25 @@ static int lbvh_from_boxes(nxhip_ctx* c, const DevBuf& triBox, const DevBuf& bou
         return NXHIP_ERR_INVALID;
     }
     *nodeCount = used;
+    if (c->keepBinaryTree) {
+        // test hook (nxhip_debug_keep_binary_tree): the binary tree and the cost table to the host before they are freed — the copy of
+        // `used` above has waited for the last collapse level
+        nxhip_ctx::BinaryTreeStash& s = c->binaryTree;
+        s = nxhip_ctx::BinaryTreeStash{};
+        s.left.resize(inner); s.right.resize(inner); s.count.resize(inner); s.parent.resize(all);
+        s.box.resize(all * 6); s.leafOrder.resize(n); s.eval.resize(inner * 7);
+        NX_HIP(hipMemcpy(s.left.data(), left.p, inner * 4, hipMemcpyDeviceToHost));
+        NX_HIP(hipMemcpy(s.right.data(), right.p, inner * 4, hipMemcpyDeviceToHost));
+        NX_HIP(hipMemcpy(s.count.data(), count.p, inner * 4, hipMemcpyDeviceToHost));
+        NX_HIP(hipMemcpy(s.parent.data(), parent.p, all * 4, hipMemcpyDeviceToHost));
+        NX_HIP(hipMemcpy(s.box.data(), box.p, all * sizeof(Box3), hipMemcpyDeviceToHost));
+        NX_HIP(hipMemcpy(s.leafOrder.data(), leafOrder, (size_t)n * 4, hipMemcpyDeviceToHost));
+        NX_HIP(hipMemcpy(s.eval.data(), evals.p, inner * 7 * sizeof(Eval), hipMemcpyDeviceToHost));
+        s.n = n;
+        s.primCost = primCost;
+        s.builder = plocRadius;
+        s.valid = true;
+    }
     return NXHIP_OK;
 }
 

@@ -564,6 +564,39 @@ int nxhip_debug_set_scan_epoch(nxhip_ctx* c, uint32_t epoch)
     return NXHIP_OK;
 }
 
+int nxhip_debug_keep_binary_tree(nxhip_ctx* c, int on)
+try {
+    NX_DEBUG_HOOK("nxhip_debug_keep_binary_tree");  // (first: a release library refuses whatever it is handed)
+    NX_CHECK_CTX(c);
+    c->keepBinaryTree = on != 0;
+    if (!on) c->binaryTree = nxhip_ctx::BinaryTreeStash{};
+    return NXHIP_OK;
+} NX_CATCH("nxhip_debug_keep_binary_tree")
+
+int nxhip_debug_read_binary_tree(nxhip_ctx* c, uint32_t capacity, uint32_t* n, float* primCost, int32_t* builder, int32_t* left, int32_t* right, int32_t* parent, int32_t* count,
+                                 float* box6, uint32_t* leafOrder, uint64_t* eval)
+try {
+    NX_DEBUG_HOOK("nxhip_debug_read_binary_tree");  // (first: a release library refuses whatever it is handed)
+    NX_CHECK_CTX(c);
+    if (!n) return fail_invalid("nxhip_debug_read_binary_tree: null n");
+    const nxhip_ctx::BinaryTreeStash& s = c->binaryTree;
+    if (!s.valid) return fail_invalid("nxhip_debug_read_binary_tree: no binary tree is stashed (nxhip_debug_keep_binary_tree, then a single build)");
+    *n = s.n;
+    if (primCost) *primCost = s.primCost;
+    if (builder) *builder = s.builder;
+    if (s.n == 0) return NXHIP_OK;
+    if (capacity < s.n) return fail_invalid("nxhip_debug_read_binary_tree: capacity too small (*n holds the primitives of the stashed tree)");
+    if (!left || !right || !parent || !count || !box6 || !leafOrder || !eval) return fail_invalid("nxhip_debug_read_binary_tree: null destination");
+    std::memcpy(left, s.left.data(), s.left.size() * 4);
+    std::memcpy(right, s.right.data(), s.right.size() * 4);
+    std::memcpy(parent, s.parent.data(), s.parent.size() * 4);
+    std::memcpy(count, s.count.data(), s.count.size() * 4);
+    std::memcpy(box6, s.box.data(), s.box.size() * 4);
+    std::memcpy(leafOrder, s.leafOrder.data(), s.leafOrder.size() * 4);
+    std::memcpy(eval, s.eval.data(), s.eval.size() * 8);
+    return NXHIP_OK;
+} NX_CATCH("nxhip_debug_read_binary_tree")
+
 int nxhip_clear_blas(nxhip_ctx* c)
 try {
     NX_CHECK_CTX(c);

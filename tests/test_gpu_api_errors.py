@@ -411,6 +411,44 @@ def test_released_queues_come_back_with_the_next_render(gpu_ctx_factory):
     assert np.array_equal(ctx.read_accumulation().view(np.uint32), ref.read_accumulation().view(np.uint32))
 
 
+def test_binary_tree_hook_refuses_what_it_cannot_answer(gpu_ctx_factory):
+    """nxhip_debug_keep_binary_tree / nxhip_debug_read_binary_tree: nothing stashed, a null count, a null context, a capacity too small
+    (the count still comes back), a null array — NXHIP_ERR_INVALID each, the stash and the context untouched"""
+    import ctypes as C
+
+    from nexus_amd import scenegen
+
+    ctx = gpu_ctx_factory(32, 32)
+    L = ctx.L
+    n, cost, builder = C.c_uint32(77), C.c_float(0.0), C.c_int32(5)
+    nothing = (None,) * 7
+    assert L.nxhip_debug_keep_binary_tree(None, 1) == 1
+    assert L.nxhip_debug_read_binary_tree(None, 0, C.byref(n), None, None, *nothing) == 1
+    with pytest.raises(NexusError, match="no binary tree is stashed"):
+        ctx.debug_read_binary_tree()
+    tris = np.ascontiguousarray(scenegen.random_soup(20, seed=1), dtype=pod.TRI_DT)
+    ctx.build_blas(tris)
+    assert L.nxhip_debug_read_binary_tree(ctx.h, 0, C.byref(n), None, None, *nothing) == 1 and n.value == 77, "off is the default"
+    ctx.debug_keep_binary_tree(True)
+    assert L.nxhip_debug_read_binary_tree(ctx.h, 0, C.byref(n), None, None, *nothing) == 1, "on, and no build since"
+    ctx.build_blas(tris)
+    assert L.nxhip_debug_read_binary_tree(ctx.h, 20, None, None, None, *nothing) == 1
+    assert b"null n" in capi.lib().nxhip_last_error()
+    assert L.nxhip_debug_read_binary_tree(ctx.h, 0, C.byref(n), C.byref(cost), C.byref(builder), *nothing) == 1
+    assert b"capacity too small" in capi.lib().nxhip_last_error() and (n.value, cost.value, builder.value) == (20, 0.75, -1)
+    p = capi._ptr
+    i32 = [np.full(64, -7, np.int32) for _ in range(4)]
+    box, order, table = np.zeros(39 * 6, np.float32), np.zeros(20, np.uint32), np.zeros(19 * 7, np.uint64)
+    assert L.nxhip_debug_read_binary_tree(ctx.h, 19, C.byref(n), None, None, p(i32[0]), p(i32[1]), p(i32[2]), p(i32[3]), p(box), p(order), p(table)) == 1
+    assert L.nxhip_debug_read_binary_tree(ctx.h, 20, C.byref(n), None, None, p(i32[0]), p(i32[1]), p(i32[2]), p(i32[3]), p(box), None, p(table)) == 1
+    assert b"null destination" in capi.lib().nxhip_last_error() and all(np.all(a == -7) for a in i32), "nothing was written"
+    assert L.nxhip_debug_read_binary_tree(ctx.h, 20, C.byref(n), None, None, p(i32[0]), p(i32[1]), p(i32[2]), p(i32[3]), p(box), p(order), p(table)) == 0
+    assert np.all(i32[0][19:] == -7) and np.all(i32[2][39:] == -7) and sorted(order.tolist()) == list(range(20)) and i32[2][0] == -1
+    T = ctx.debug_read_binary_tree()
+    assert T["n"] == 20 and np.array_equal(T["left"], i32[0][:19]) and np.array_equal(T["parent"], i32[2][:39])
+    assert ctx.build_blas(tris) == 2, "the context builds on"
+
+
 def test_batched_blas_build_refuses_bad_input_and_falls_back_for_other_builders(gpu_ctx_factory):
     """nxhip_build_blas_batch: an empty batch, a mesh without triangles and a null mesh pointer are NXHIP_ERR_INVALID with the
     context untouched; with another builder selected (radix tree, clustering) the meshes are built one by one and still get
