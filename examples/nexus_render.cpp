@@ -5,6 +5,7 @@
 //                [--no-detail-maps] [--metal-rough] [--alpha-modes] [--fog SIGMA [--fog-albedo R G B] [--fog-g G] [--fog-box X0 Y0 Z0 X1 Y1 Z1] [--fog-grid FILE.npy]]
 //                [--point-light X Y Z INTENSITY] [--sun DX DY DZ IRRADIANCE] [--time T [--animation K]] [--morph-targets] <dir/> <file.glb|file.obj> <out.ppm> [width height frames pathLength]
 //                [eyeX eyeY eyeZ fwdX fwdY fwdZ hfovDeg]
+//   and, among the leading options: [--sky AZIMUTH_DEG ELEVATION_DEG [--sky-size W H] [--sky-disc] [--sky-sun] [--sky-altitude M] [--sky-mie SCALE]]
 // --denoise: the feature buffers are accumulated with the colour and the image written is the a-trous filtered one (nxhip_denoise)
 // --adaptive THRESHOLD: render to a noise target instead of a frame count (nxhip_render_adaptive: blocks of 64 pixels stop when the
 //   relative standard error of every pixel's mean luminance is at most THRESHOLD; pixel-keyed random numbers; decided every 8 frames;
@@ -18,6 +19,12 @@
 // --env-float FILE.hdr: a Radiance .hdr file as the environment, as the linear float radiance it holds (Scene::AddHDRMapFloat,
 //   nxhip_upload_env_float) instead of the 8 bits "Load HDR map" reduces it to.
 // --env-sampling: the light sample may pick the environment map (nxhip_set_env_sampling): what a map with a small bright sun needs.
+// --sky AZIMUTH_DEG ELEVATION_DEG: a procedural daylight environment generated on the device (Scene::SetSky, nxhip_set_sky: single-scattering
+//   Rayleigh and Mie atmosphere) with the sun at that azimuth (0 = +x, 90 = +z) and elevation; it replaces --env-float.  --sky-size W H: the
+//   map's size (default 2048 x 1024).  --sky-disc: the sun's disc is baked into the map (seen by every ray, mirrors included; wants
+//   --env-sampling).  --sky-sun: the sun as an analytic light instead (nxhip_sky_sun_light: sampled by the light sample only) — an
+//   alternative to --sky-disc: both together make two suns.  --sky-altitude M: the observer's height in metres (default 1).
+//   --sky-mie SCALE: multiplies the haze (default 1).
 // A .glb's KHR_lights_punctual lights (point, spot, directional) are rendered as the file places them, without a flag.
 // A .glb's normalTexture and metallicRoughnessTexture (its G channel: roughness) are used as the file's materials name them, without a flag.
 // --no-detail-maps: drop them (AssetManager::ClearMaterialDetails), for an A/B against the flat, uniformly glossy surfaces.
@@ -40,6 +47,7 @@
 //   the mesh is skinned: deltas, then joints, in one pass on the device (nxhip_pose_blas_morph).  Without it targets are ignored, as before.
 //
 // Build: make example   (links nexus_amd/lib/libnexus_amd.so)
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -62,6 +70,10 @@ int main(int argc, char** argv)
     bool transparentShadows = false;
     std::string envFloat;
     bool envSampling = false;
+    bool sky = false, skySun = false;
+    double skyAzimuth = 0.0, skyElevation = 45.0;
+    nx_sky skyParams;
+    nxhip_sky_defaults(&skyParams);
     bool detailMaps = true;
     bool metalRough = false;
     bool alphaModes = false;
@@ -103,6 +115,27 @@ int main(int argc, char** argv)
         } else if (opt == "--env-sampling") {
             envSampling = true;
             used = 1;
+        } else if (opt == "--sky" && argc > 3) {
+            sky = true;
+            skyAzimuth = std::atof(argv[2]);
+            skyElevation = std::atof(argv[3]);
+            used = 3;
+        } else if (opt == "--sky-size" && argc > 3) {
+            skyParams.width = static_cast<uint32_t>(std::atoi(argv[2]));
+            skyParams.height = static_cast<uint32_t>(std::atoi(argv[3]));
+            used = 3;
+        } else if (opt == "--sky-disc") {
+            skyParams.sunDisc = 1;
+            used = 1;
+        } else if (opt == "--sky-sun") {
+            skySun = true;
+            used = 1;
+        } else if (opt == "--sky-altitude" && argc > 2) {
+            skyParams.altitude = static_cast<float>(std::atof(argv[2]));
+            used = 2;
+        } else if (opt == "--sky-mie" && argc > 2) {
+            skyParams.mieScale = static_cast<float>(std::atof(argv[2]));
+            used = 2;
         } else if (opt == "--no-detail-maps") {
             detailMaps = false;
             used = 1;
@@ -161,7 +194,7 @@ int main(int argc, char** argv)
         return 2;
     }
     if (argc < 4) {
-        std::fprintf(stderr, "usage: %s [--denoise] [--adaptive THRESHOLD [--max-frames N]] [--light-sampling uniform|power|position] [--transparent-shadows] [--env-float FILE.hdr] [--env-sampling] [--no-detail-maps] [--metal-rough] [--alpha-modes] [--fog SIGMA [--fog-albedo R G B] [--fog-g G] [--fog-box X0 Y0 Z0 X1 Y1 Z1] [--fog-grid FILE.npy]] [--point-light X Y Z INTENSITY] [--sun DX DY DZ IRRADIANCE] [--time T [--animation K]] [--morph-targets] <dir/> <file.glb|file.obj> <out.ppm> [width height frames pathLength] [eye(3) forward(3) hfov]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s [--denoise] [--adaptive THRESHOLD [--max-frames N]] [--light-sampling uniform|power|position] [--transparent-shadows] [--env-float FILE.hdr] [--env-sampling] [--sky AZIMUTH_DEG ELEVATION_DEG [--sky-size W H] [--sky-disc] [--sky-sun] [--sky-altitude M] [--sky-mie SCALE]] [--no-detail-maps] [--metal-rough] [--alpha-modes] [--fog SIGMA [--fog-albedo R G B] [--fog-g G] [--fog-box X0 Y0 Z0 X1 Y1 Z1] [--fog-grid FILE.npy]] [--point-light X Y Z INTENSITY] [--sun DX DY DZ IRRADIANCE] [--time T [--animation K]] [--morph-targets] <dir/> <file.glb|file.obj> <out.ppm> [width height frames pathLength] [eye(3) forward(3) hfov]\n", argv[0]);
         return 2;
     }
     // a program built against these headers and run with another build of libnexus_amd.so gets an error string here, not a GPU fault
@@ -217,6 +250,23 @@ int main(int argc, char** argv)
         scene.GetCamera()->SetHorizontalFOV(cam[6]);
         scene.GetRenderSettings().pathLength = static_cast<unsigned char>(pathLength);
         if (!envFloat.empty()) scene.AddHDRMapFloat("", envFloat);
+        if (sky) {
+            const double deg = 3.14159265358979323846 / 180.0, ce = std::cos(skyElevation * deg);
+            skyParams.sunDirection[0] = static_cast<float>(ce * std::cos(skyAzimuth * deg));
+            skyParams.sunDirection[1] = static_cast<float>(std::sin(skyElevation * deg));
+            skyParams.sunDirection[2] = static_cast<float>(ce * std::sin(skyAzimuth * deg));
+            scene.SetSky(skyParams);
+            if (skySun) {  // the sun as an analytic light: what the light sample sees in place of the baked disc
+                nexus::AnalyticLight sun;
+                if (nxhip_sky_sun_light(&skyParams, &sun) != NXHIP_OK) {
+                    std::fprintf(stderr, "nexus_render: %s\n", nxhip_last_error());
+                    return 1;
+                }
+                scene.AddAnalyticLight(sun);
+                std::printf("sky sun: direction %.9g %.9g %.9g, angular radius %.9g, irradiance %.9g %.9g %.9g\n", sun.direction[0], sun.direction[1], sun.direction[2],
+                            sun.angularRadius, sun.colour[0] * sun.intensity, sun.colour[1] * sun.intensity, sun.colour[2] * sun.intensity);
+            }
+        }
         scene.Update();
         if (fog) {
             if (!fogBox) {  // the scene's world bounds, grown by 10 %

@@ -68,6 +68,12 @@ public:
     // width x height x 3 floats, row 0 the top row.  Either kind of map replaces the other.
     void AddHDRMapFloat(const std::string& filePath, const std::string& fileName);
     void AddHDRMapFloat(uint32_t width, uint32_t height, const float* rgb);
+    // Extension: the environment generated on the device from the sun-and-sky model (nx_sky, include/nexus_pod.h; the model is stated in
+    // include/nexus_hip.h) by PathTracer::UpdateDeviceScene (nxhip_set_sky, which validates it).  It replaces a map of either kind and is
+    // replaced by AddHDRMap / AddHDRMapFloat.  ClearSky: no environment (the textures are sent again without one).
+    void SetSky(const nx_sky& sky);
+    void ClearSky();
+    const nx_sky* GetSky() const { return m_HasSky ? &m_Sky : nullptr; }  // nullptr: none
     size_t AddLight(const Light& light);
     void RemoveLight(size_t index);
     // Extension: lights that are no geometry (Assets.h AnalyticLight).  Sampled by the light sample only: invisible to camera and bounce rays.
@@ -141,6 +147,8 @@ private:
     std::shared_ptr<Camera> m_Camera;
     Texture m_HdrMap;
     FloatImage m_HdrMapFloat;
+    nx_sky m_Sky{};
+    bool m_HasSky = false;
 
     std::vector<MeshInstance> m_MeshInstances;  // what the user edits
     std::vector<BVHInstance> m_BVHInstances;    // what the TLAS and the device see, one per mesh instance

@@ -391,6 +391,57 @@ int nxhip_set_material_detail(nxhip_ctx *ctx, const nx_material_detail *details,
  * NXHIP_ERR_INVALID, the previous map and tables left in place: rgb NULL or a zero size; width or height above 32768 or more than
  * 2^27 texels; any component negative or not finite (checked on the host before anything is allocated). */
 int nxhip_upload_env_float(nxhip_ctx *ctx, const float *rgb, uint32_t width, uint32_t height);
+/* Extension: sun and sky — a float environment map GENERATED on the device from a physically based single-scattering atmosphere
+ * (Nishita et al. 1993: Rayleigh and Mie terms only), for outdoor scenes without a .hdr file.  nx_sky: nexus_pod.h.
+ * Geometry.  Up is +y.  The map's orientation is env_uv's: texel (x, y) has u = (x + 1/2) / W, v = (y + 1/2) / H, latitude
+ *   phi = pi/2 - pi v, longitude theta = 2 pi u - pi, direction d = (cos phi cos theta, sin phi, cos phi sin theta).
+ * Constants.  Planet radius Rg = 6 360 000 m, atmosphere top Rt = 6 420 000 m, the observer at (0, Rg + altitude, 0).
+ *   Rayleigh: betaR = (5.802e-6, 13.558e-6, 33.1e-6) m^-1 x rayleighScale, scale height 8000 m, phase PR = 3/(16 pi) (1 + mu^2).
+ *   Mie:      scattering betaM = 3.996e-6 m^-1 x mieScale (grey), extinction betaM / 0.9, scale height 1200 m, Cornette-Shanks phase
+ *             PM = 3/(8 pi) (1 - g^2)(1 + mu^2) / ((2 + g^2)(1 + g^2 - 2 g mu)^1.5), g = mieG; mu = d . s, s the unit sun direction.
+ *   rho(h) = exp(-h / scale height) with h the height above Rg.  Radiometric RGB throughout (no 683 lm/W, as for the analytic lights);
+ *   sunIrradiance is the sun's irradiance at the top of the atmosphere.
+ * View ray.  From the observer along d; tEnd = the first hit with the Rg sphere if the ray hits the planet, else the exit from the Rt
+ *   sphere.  viewSteps = Nv segments with edges t_i = tEnd (i / Nv)^2 — quadratic, because the density is near the observer — and the
+ *   midpoint rule: one sample in the middle of each segment (in t), the optical depths to it = the full earlier segments + half of its own.
+ * Light ray.  From each sample towards the sun: if it hits the Rg sphere ahead of it the sample contributes nothing; otherwise
+ *   lightSteps = Nl segments to the Rt exit, the same quadratic edges and midpoint rule, summed in full.
+ * Radiance.  L = sunIrradiance x sum_i [betaR rhoR_i PR + betaM rhoM_i PM] ds_i
+ *                x exp(-(betaR (tauR_view + tauR_light) + betaM_ext (tauM_view + tauM_light))), per channel.
+ * Ground.  A view ray that ended on the planet adds T_view x groundAlbedo / pi x sunIrradiance x T_sun(ground point) x max(0, n . s):
+ *   n the outward normal there, T_view the transmittance of the whole view ray, T_sun the light-ray rule from the ground point (Nl
+ *   segments), 0 when the sun is below that point's horizon.
+ * Quadrature.  The defaults Nv = 64, Nl = 16 are within 0.5 % of 1024 x 128 steps at altitude 1 m over the zenith, the horizon towards
+ *   the sun and oblique views, for sun elevations from 60 degrees to -4 degrees (tests/test_sky.py measures it; uniform spacing with
+ *   32 x 8 steps is 5 % off).
+ * Sun disc (sunDisc = 1).  Lsun x c x k is added to the texels: Lsun = sunIrradiance x T_sun(observer) / (pi sin^2 alpha) — the
+ *   analytic lights' disc rule, T_sun by the light-ray rule with Nl segments, 0 when the sun is below the observer's geometric horizon;
+ *   c = the share of the texel's 8 x 8 regular sub-positions ((i + 1/2) / 8, (j + 1/2) / 8) of its (u, v) cell whose direction lies within
+ *   alpha of s; k = 2 pi (1 - cos alpha) / sum(c Omega), one factor per map, computed on the host in binary64 over the disc's bounding
+ *   rows and columns, Omega = (2 pi / W)(sin phi_top - sin phi_bottom) the texel's exact solid angle — so the disc carries its full
+ *   energy at any resolution.  sum = 0 (the disc fell between sub-positions): NXHIP_ERR_INVALID — use a larger map or a larger
+ *   sunAngularRadius.  No limb darkening.
+ * Device.  The texels are computed one lane each, straight into the float4 buffer the passes read (binary32, heights in a
+ *   cancellation-free form, hardware exponentials; the disc's coverage in binary64); no host copy of the texels, no read-back.  The map
+ *   is installed exactly as nxhip_upload_env_float installs its own: it replaces a map of either kind, nxhip_upload_texture(kind 2) or
+ *   nxhip_upload_env_float replaces it, nxhip_clear_textures removes it; lookup, sampler weight and tables are the float map's, built
+ *   by this call when the sampler is on.  A context that never calls it is unchanged.
+ * NXHIP_ERR_INVALID, the previous map and tables left in place, checked on the host before anything is allocated: sky NULL; any field
+ *   not finite; a zero sunDirection; a negative irradiance, albedo or scale; an albedo above 1; |mieG| >= 1; altitude outside [1, 50000];
+ *   sunAngularRadius outside [0, pi/2); sizes outside nxhip_upload_env_float's limits; steps outside [1, 1024]; sunDisc above 1;
+ *   sunDisc = 1 with sunAngularRadius = 0.
+ * Out of scope: multiple scattering; ozone; limb darkening; a moon or stars; aerial perspective on scene geometry (the fog volume is the
+ *   medium, the sky is at infinity); photometric units.
+ * nxhip_sky_defaults: sun at 45 degrees elevation along +x, angular radius 0.004675, irradiance (1, 1, 1), altitude 1, scales 1, g 0.8,
+ *   albedo 0.3, map 2048 x 1024, steps 64 / 16, no disc.  NXHIP_ERR_INVALID for NULL.
+ * nxhip_sky_sun_light: the sky's sun as an NX_ALIGHT_DIRECTIONAL record for the caller to append to its nxhip_set_analytic_lights
+ *   table — direction = -sunDirection (unit), angularRadius = alpha, colour = sunIrradiance x T_sun(observer), intensity = 1; T_sun by the
+ *   light-ray rule with a fixed 256 segments, the colour 0 when the sun is below the observer's geometric horizon.  Needs no context;
+ *   host, binary64; validates as nxhip_set_sky does.  The baked disc and this record are ALTERNATIVES: both together make two suns.  As
+ *   for every analytic light, camera rays and BSDF-sampled rays do not see the record: mirrors show the sun only with sunDisc = 1. */
+int nxhip_sky_defaults(nx_sky *sky);
+int nxhip_set_sky(nxhip_ctx *ctx, const nx_sky *sky);
+int nxhip_sky_sun_light(const nx_sky *sky, nx_analytic_light *out);
 /* Extension (BASELINE.json configs[3] asks for "HDR envmap NEE/MIS"; the reference only adds the environment when a ray
  * misses, PathTracer.cu:152-164, and its NEE knows mesh lights only, :227): with enable != 0 the next-event estimation
  * treats the environment map as one more light — picked with probability 1 / (lightCount + 1), direction drawn from the
@@ -1137,6 +1188,11 @@ int nxhip_read_env_float(nxhip_ctx *ctx, float *rgb, uint32_t capacityTexels, ui
  * cdf exceeds b / 64, clamped to the cdf's last index.  marginalGuide receives 65 words, rowGuide height x 65 (either may be NULL);
  * capacityRows >= height when rowGuide is given, else NXHIP_ERR_INVALID. */
 int nxhip_read_env_guides(nxhip_ctx *ctx, uint32_t *marginalGuide, uint32_t *rowGuide, uint32_t capacityRows);
+/* The sky's radiance on arrays — a test hook over the device function the map kernel of nxhip_set_sky calls (a `make release` library
+ * refuses it): rgb[3k..] = the sky term alone (ground included, no disc) along the unit direction dir3[3k..], for the parameters of
+ * `sky` (validated as nxhip_set_sky validates them; width, height and sunDisc are not used).  The context's map is not touched.
+ * NXHIP_ERR_INVALID: a NULL array with count > 0, a direction that is not finite, a sky nxhip_set_sky would refuse. */
+int nxhip_sky_radiance_batch(nxhip_ctx *ctx, const nx_sky *sky, const float *dir3, uint32_t count, float *rgb);
 
 /* The transcendental functions of the shading path (include/nexus_fmath.h: the ONE text the kernels and the CPU oracle both
  * compile — sin / cos / exp / log / pow / atan2 / asin replacing the libm calls of Random.cuh:119-121, Microfacet.cuh:18,75,
@@ -1219,6 +1275,7 @@ static inline uint64_t nxhip_header_abi_stamp(void)
         sizeof(nx_camera), offsetof(nx_camera, resolution), sizeof(nx_render_settings), offsetof(nx_render_settings, backgroundColor),
         sizeof(nx_ray), sizeof(nx_hit), sizeof(nx_bsdf_query), sizeof(nx_bsdf_result), offsetof(nx_bsdf_result, rngOut),
         sizeof(nxhip_queue_sizes), sizeof(nxhip_trace_stats), offsetof(nxhip_trace_stats, cycles), sizeof(nxhip_kernel_times), NXHIP_K_COUNT,
+        sizeof(nx_sky), offsetof(nx_sky, altitude), offsetof(nx_sky, groundAlbedo), offsetof(nx_sky, width), offsetof(nx_sky, sunDisc),
         sizeof(nx_adaptive_params), offsetof(nx_adaptive_params, minSamples), offsetof(nx_adaptive_params, cull),
         sizeof(nx_denoise_params), offsetof(nx_denoise_params, sigmaColor), offsetof(nx_denoise_params, sigmaDepth),
     };

@@ -141,6 +141,11 @@ int nxs_scene_set_hdr_map(nxs_scene *s, const uint8_t *rgba8, uint32_t w, uint32
 /* Extension — Scene::AddHDRMapFloat(width, height, rgb): the environment as w x h x 3 floats of linear radiance, row 0 the top row
  * (nxhip_upload_env_float at the next device update).  Either kind of map replaces the other. */
 int nxs_scene_set_hdr_map_float(nxs_scene *s, const float *rgb, uint32_t w, uint32_t h);
+/* Extension — Scene::SetSky(sky): the environment generated on the device from the sun-and-sky model (nxhip_set_sky at the next device
+ * update, which validates it; the model is stated in include/nexus_hip.h).  It replaces a map of either kind and is replaced by one.
+ * nxs_scene_clear_sky — Scene::ClearSky(): no environment. */
+int nxs_scene_set_sky(nxs_scene *s, const nx_sky *sky);
+int nxs_scene_clear_sky(nxs_scene *s);
 int nxs_scene_add_mesh(nxs_scene *s, const nx_triangle *tris, uint32_t triCount, int32_t materialId, int32_t *meshId);
 int nxs_scene_create_instance(nxs_scene *s, uint32_t meshId, int32_t materialId, const float pos[3], const float rotDeg[3],
                               const float scale[3], int32_t *instanceId);

@@ -13,6 +13,7 @@
  *   (nx_analytic_light 64 B: an extension, no reference layout)
  *   (nx_material_detail 16 B: an extension, no reference layout)
  *   (nx_medium 48 B: an extension, no reference layout)
+ *   (nx_sky 76 B: an extension, no reference layout)
  *   nx_camera        88 B  Cuda/Scene/Camera.cuh:5-15
  *   nx_render_settings 20 B Cuda/Scene/Scene.cuh:10-17, Renderer/RenderSettings.h:4-10
  */
@@ -155,6 +156,21 @@ typedef struct nx_medium {
     float albedo[3]; uint32_t pad;   /* single-scattering albedo sigma_s / sigma_t per channel, each in [0, 1] */
 } nx_medium;
 NX_STATIC_ASSERT(sizeof(nx_medium) == 48, "nx_medium must be 48 bytes");
+
+/* Extension: a procedural sun-and-sky environment (nxhip_set_sky; the model is stated in full in include/nexus_hip.h).  Up is +y;
+ * lengths in metres, angles in radians; radiometric RGB, as for the analytic lights. */
+typedef struct nx_sky {
+    float sunDirection[3];       /* TOWARDS the sun, any non-zero length (normalised on the host in binary64)  */
+    float sunAngularRadius;      /* alpha: half-angle of the sun's disc, [0, pi/2)                              */
+    float sunIrradiance[3];      /* of a surface facing the sun at the top of the atmosphere                    */
+    float altitude;              /* of the observer above the ground, [1, 50000]                                */
+    float rayleighScale, mieScale, mieG;  /* multipliers of betaR and betaM (>= 0); Cornette-Shanks g, |g| < 1 */
+    float groundAlbedo[3];       /* Lambertian planet below the horizon, each in [0, 1]                         */
+    uint32_t width, height;      /* of the generated latitude-longitude map (nxhip_upload_env_float's limits)   */
+    uint32_t viewSteps, lightSteps;  /* quadrature segments per view ray / per light ray, each in [1, 1024]    */
+    uint32_t sunDisc;            /* 1: the sun's disc is baked into the map; 0: sky and ground only             */
+} nx_sky;
+NX_STATIC_ASSERT(sizeof(nx_sky) == 76 && offsetof(nx_sky, width) == 56, "nx_sky must be 76 bytes");
 
 typedef struct NX_ALIGN(8) nx_camera {
     float position[3];

@@ -64,6 +64,7 @@ def abi_words():
         pod.CAM_DT.itemsize, off(pod.CAM_DT, "resolution"), pod.SETTINGS_DT.itemsize, off(pod.SETTINGS_DT, "backgroundColor"),
         pod.RAY_DT.itemsize, pod.HIT_DT.itemsize, pod.BSDF_QUERY_DT.itemsize, pod.BSDF_RESULT_DT.itemsize, off(pod.BSDF_RESULT_DT, "rngOut"),
         C.sizeof(QueueSizes), C.sizeof(TraceStats), TraceStats.cycles.offset, C.sizeof(KernelTimes), len(KERNEL_CLASSES),
+        pod.SKY_DT.itemsize, off(pod.SKY_DT, "altitude"), off(pod.SKY_DT, "groundAlbedo"), off(pod.SKY_DT, "width"), off(pod.SKY_DT, "sunDisc"),
         pod.ADAPTIVE_DT.itemsize, off(pod.ADAPTIVE_DT, "minSamples"), off(pod.ADAPTIVE_DT, "cull"),
         pod.DENOISE_DT.itemsize, off(pod.DENOISE_DT, "sigmaColor"), off(pod.DENOISE_DT, "sigmaDepth"),
     ]
@@ -148,6 +149,24 @@ def _copy_out(addr, count, dtype):
         return np.zeros(0, dtype=dtype)
     buf = (C.c_uint8 * (count * np.dtype(dtype).itemsize)).from_address(addr)
     return np.frombuffer(buf, dtype=dtype, count=count).copy()
+
+
+# ---- sun and sky (no context needed) ------------------------------------------------------------------
+
+def sky_defaults():
+    """nxhip_sky_defaults: a pod.SKY_DT record"""
+    s = np.zeros(1, dtype=pod.SKY_DT)
+    check(lib().nxhip_sky_defaults(_ptr(s)), "nxhip_sky_defaults")
+    return s[0]
+
+
+def sky_sun_light(sky):
+    """nxhip_sky_sun_light: the sky's sun as a pod.ALIGHT_DT record (NX_ALIGHT_DIRECTIONAL) for Context.set_analytic_lights — an
+    alternative to sunDisc = 1, never both"""
+    s = np.ascontiguousarray(sky, dtype=pod.SKY_DT).reshape(1)
+    out = np.zeros(1, dtype=pod.ALIGHT_DT)
+    check(lib().nxhip_sky_sun_light(_ptr(s), _ptr(out)), "nxhip_sky_sun_light")
+    return out[0]
 
 
 # ---- host builders --------------------------------------------------------------------------------
@@ -664,6 +683,21 @@ class Context:
         img = np.ascontiguousarray(rgb, dtype=np.float32)
         assert img.ndim == 3 and img.shape[2] == 3
         check(self.L.nxhip_upload_env_float(self.h, _ptr(img), img.shape[1], img.shape[0]), "nxhip_upload_env_float")
+
+    def set_sky(self, sky):
+        """the environment generated on the device from the sun-and-sky model (a pod.SKY_DT record, pod.Sky / capi.sky_defaults):
+        installed as a float map (nxhip_set_sky: the model is in include/nexus_hip.h)"""
+        s = np.ascontiguousarray(sky, dtype=pod.SKY_DT).reshape(1)
+        check(self.L.nxhip_set_sky(self.h, _ptr(s)), "nxhip_set_sky")
+
+    def sky_radiance(self, sky, dirs):
+        """the sky term alone (ground included, no disc) along every unit direction dirs[k]: float32[n, 3] — a test hook over the device
+        function the map kernel calls (nxhip_sky_radiance_batch)"""
+        s = np.ascontiguousarray(sky, dtype=pod.SKY_DT).reshape(1)
+        d, = _cols((dirs, _F32, 3))
+        rgb, = _outs(len(d), (_F32, 3))
+        self._hook("nxhip_sky_radiance_batch", s, d, len(d), rgb)
+        return rgb
 
     def read_env_float(self):
         """the float environment map as it is stored: H x W x 3 float32"""
@@ -1510,6 +1544,14 @@ class Scene:
         """Scene::AddHDRMapFloat: H x W x 3 float32 of linear radiance"""
         img = np.ascontiguousarray(rgb, dtype=np.float32)
         _scheck(self.L.nxs_scene_set_hdr_map_float(self.h, _ptr(img), img.shape[1], img.shape[0]), "nxs_scene_set_hdr_map_float")
+
+    def set_sky(self, sky):
+        """Scene::SetSky (a pod.SKY_DT record, pod.Sky); None: Scene::ClearSky"""
+        if sky is None:
+            _scheck(self.L.nxs_scene_clear_sky(self.h), "nxs_scene_clear_sky")
+            return
+        s = np.ascontiguousarray(sky, dtype=pod.SKY_DT).reshape(1)
+        _scheck(self.L.nxs_scene_set_sky(self.h, _ptr(s)), "nxs_scene_set_sky")
 
     def add_hdr_map_file_float(self, path, file_name):
         """Scene::AddHDRMapFloat(filePath, fileName): a Radiance .hdr file as linear float radiance"""

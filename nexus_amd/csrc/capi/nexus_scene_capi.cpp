@@ -314,6 +314,19 @@ int nxh_decode_hdr_float(const uint8_t* data, size_t size, uint32_t* width, uint
     });
 }
 
+int nxs_scene_set_sky(nxs_scene* s, const nx_sky* sky)
+{
+    return guarded([&] {
+        if (!sky) throw std::runtime_error("nxs_scene_set_sky: null argument");
+        s->scene.SetSky(*sky);
+    });
+}
+
+int nxs_scene_clear_sky(nxs_scene* s)
+{
+    return guarded([&] { s->scene.ClearSky(); });
+}
+
 int nxs_scene_set_hdr_map_float(nxs_scene* s, const float* rgb, uint32_t w, uint32_t h)
 {
     return guarded([&] { s->scene.AddHDRMapFloat(w, h, rgb); });

@@ -84,6 +84,7 @@ uint64_t layout_stamp_aov();
 uint64_t layout_stamp_adaptive();
 uint64_t layout_stamp_lights();
 uint64_t layout_stamp_envmap();
+uint64_t layout_stamp_sky();
 uint64_t layout_stamp_scene();  // the host units nxhip_*.hip that fill DeviceState, each its own
 uint64_t layout_stamp_render();
 uint64_t layout_stamp_features();
@@ -96,6 +97,31 @@ int light_tree_build(hipStream_t st, const LightTreeBuild& b, void* sortTemp, si
 // nx_envmap.hip: the float environment map's sampler tables, built on the device in stream order (temp: 2 x height doubles)
 int env_float_tables_build(hipStream_t st, const float4* texels, uint32_t width, uint32_t height, double* temp, float* marginalCdf, float* rowCdf, float* density,
                            uint32_t* marginalGuide, uint32_t* rowGuide);
+// nx_sky.hip: the sun-and-sky environment (nxhip_set_sky).  SkyLaunch: what the kernels take, kilometres, binary32.  SkyPlan: a validated
+// nx_sky in binary64 (sky_plan refuses what nxhip_set_sky refuses, naming `who`).  SkyDisc: the baked sun disc of one map — its bounding
+// box (wrapping in x), the cap and Lsun x k.
+struct SkyLaunch {
+    float r0, q0;  // the observer's |p| and |p|^2 - Rg^2
+    float sun[3];
+    float betaR[3], betaMs, betaMe;
+    float g;
+    float irradiance[3], albedo[3];
+    uint32_t nv, nl;
+};
+struct SkyDisc {
+    uint32_t x0, y0, w, h;
+    float add[3];  // Lsun x k per channel
+    double sun[3], chord2;  // |d - s|^2 <= chord2 = 4 sin^2(alpha / 2)
+};
+struct SkyPlan {
+    double sun[3], alpha, q0, r0, betaR[3], betaMs, betaMe;
+    SkyLaunch launch;
+};
+int sky_plan(const nx_sky* sky, const char* who, SkyPlan* out);
+void sky_sun_transmittance(const SkyPlan& p, uint32_t segments, double T[3]);  // T_sun(observer) by the light-ray rule
+int sky_disc_plan(const nx_sky* sky, const SkyPlan& p, const char* who, SkyDisc* out);
+int sky_generate(hipStream_t st, const SkyPlan& p, const SkyDisc* disc, float4* texels, uint32_t width, uint32_t height);
+const void* sky_hook_kernel_ptr();
 int lbvh_build(nxhip_ctx* c, const nx_triangle* dTris, uint32_t n, int plocRadius, DevBuf& nodes, DevBuf& primIdx, DevBuf& isect, uint32_t* nodeCount);
 int lbvh_build_batch(nxhip_ctx* c, const nx_triangle* dTris, const std::vector<uint32_t>& counts, DevBuf& nodes, DevBuf& primIdx, DevBuf& isect, std::vector<uint32_t>& nodeFirst,
                      std::vector<uint32_t>& nodeCounts);
@@ -150,6 +176,7 @@ inline Kernel<int, const double*, const double*, U32, double*> fmath_hook() { re
 inline Kernel<TextureDev, const float*, const float*, U32, float4*> tex2d_hook() { return {tex2d_hook_kernel_ptr()}; }              // (t, srgbLut, uv, count, out)
 inline Kernel<const float4*, int, int, const float*, U32, float4*> tex2d_float_hook() { return {tex2d_float_hook_kernel_ptr()}; }       // (texels, W, H, uv, count, out)
 inline Kernel<State, int, const float*, U32, float*, float*, U32*> env_hook() { return {env_hook_kernel_ptr()}; }                    // (S, sample, in, count, vec, pdf, texel)
+inline Kernel<SkyLaunch, const float*, U32, float*> sky_hook() { return {sky_hook_kernel_ptr()}; }                                    // (P, dir, count, rgb)
 inline Kernel<TextureDev, const float*, U32, float4*> tex2d_linear_hook() { return {tex2d_linear_hook_kernel_ptr()}; }                  // (t, uv, count, out)
 // (S, instance, triIdx, hitUv, rayDir, count, normal, roughness, fellBack)
 inline Kernel<State, U32, const U32*, const float*, const float*, U32, float*, float*, U32*> shading_frame_hook() { return {shading_frame_hook_kernel_ptr()}; }

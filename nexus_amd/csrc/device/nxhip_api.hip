@@ -64,7 +64,7 @@ static int check_layouts()
     const struct { const char* unit; uint64_t stamp; } units[] = {
         {"nx_trace.hip", layout_stamp_trace()}, {"nx_wavefront.hip", layout_stamp_wavefront()}, {"nx_wavefront_detail.hip", layout_stamp_wavefront_detail()}, {"nx_wavefront_solid.hip", layout_stamp_wavefront_solid()}, {"nx_wavefront_metal.hip", layout_stamp_wavefront_metal()}, {"nx_hook_kernels.hip", layout_stamp_hook_kernels()}, {"nx_medium.hip", layout_stamp_medium()}, {"nx_refit.hip", layout_stamp_refit()}, {"nx_skin.hip", layout_stamp_skin()},
         {"nx_lbvh.hip", layout_stamp_lbvh()}, {"nxhip_multigpu.hip", layout_stamp_multigpu()}, {"nx_entry.hip", layout_stamp_entry()}, {"nx_aov.hip", layout_stamp_aov()},
-        {"nx_adaptive.hip", layout_stamp_adaptive()}, {"nx_lights.hip", layout_stamp_lights()}, {"nx_envmap.hip", layout_stamp_envmap()}, {"nxhip_scene.hip", layout_stamp_scene()},
+        {"nx_adaptive.hip", layout_stamp_adaptive()}, {"nx_lights.hip", layout_stamp_lights()}, {"nx_envmap.hip", layout_stamp_envmap()}, {"nx_sky.hip", layout_stamp_sky()}, {"nxhip_scene.hip", layout_stamp_scene()},
         {"nxhip_render.hip", layout_stamp_render()}, {"nxhip_features.hip", layout_stamp_features()}, {"nxhip_hooks.hip", layout_stamp_hooks()},
     };
     for (const auto& u : units) {

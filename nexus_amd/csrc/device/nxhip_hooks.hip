@@ -351,6 +351,24 @@ try {
     return b.run(kernels::alight_hook(), c->dState.as<DeviceState>(), lightIndex, dO, dR, count, dDir, dT, dF, dOk);
 } NX_CATCH("nxhip_analytic_light_sample_batch")
 
+// ---- the sky's hook (sky_hook_kernel: the map kernel's own sky_radiance) ------------------------------
+
+int nxhip_sky_radiance_batch(nxhip_ctx* c, const nx_sky* sky, const float* dir3, uint32_t count, float* rgb)
+try {
+    NX_DEBUG_HOOK("nxhip_sky_radiance_batch");  // (first: a release library refuses whatever it is handed)
+    NX_CHECK_CTX(c);
+    SkyPlan plan;
+    NX_TRY(sky_plan(sky, "nxhip_sky_radiance_batch", &plan));
+    if ((!dir3 || !rgb) && count) return fail_invalid("nxhip_sky_radiance_batch: null buffer");
+    if (!all_finite(dir3, (size_t)count * 3)) return fail_invalid("nxhip_sky_radiance_batch: directions must be finite");
+    if (count == 0) return NXHIP_OK;
+    NX_HIP(hipSetDevice(c->device));
+    HookBatch b(c, count);
+    const float* dDir = b.in(dir3, 3);
+    float* dRgb = b.out(rgb, 3);
+    return b.run(kernels::sky_hook(), plan.launch, dDir, count, dRgb);
+} NX_CATCH("nxhip_sky_radiance_batch")
+
 // ---- the medium's hooks (medium_segment_hook_kernel, medium_phase_hook_kernel) ----------------------
 
 int nxhip_medium_segment_batch(nxhip_ctx* c, const float* origin, const float* dir, const float* tEnd, const float* xi, uint32_t count, float* t0, float* length,

@@ -1599,6 +1599,88 @@ try {
     return build_env_tables(c);  // a new map under an enabled sampler gets new tables
 } NX_CATCH("nxhip_upload_env_float")
 
+int nxhip_sky_defaults(nx_sky* sky)
+{
+    if (!sky) return fail_invalid("nxhip_sky_defaults: sky is NULL");
+    *sky = nx_sky();
+    sky->sunDirection[0] = sky->sunDirection[1] = 0.70710678118654752f;  // 45 degrees of elevation along +x
+    sky->sunAngularRadius = 0.004675f;
+    sky->altitude = 1.0f;
+    sky->rayleighScale = sky->mieScale = 1.0f;
+    sky->mieG = 0.8f;
+    for (int ch = 0; ch < 3; ch++) {
+        sky->sunIrradiance[ch] = 1.0f;
+        sky->groundAlbedo[ch] = 0.3f;
+    }
+    sky->width = 2048;
+    sky->height = 1024;
+    sky->viewSteps = 64;
+    sky->lightSteps = 16;
+    return NXHIP_OK;
+}
+
+int nxhip_sky_sun_light(const nx_sky* sky, nx_analytic_light* out)
+try {
+    SkyPlan plan;
+    NX_TRY(sky_plan(sky, "nxhip_sky_sun_light", &plan));
+    if (!out) return fail_invalid("nxhip_sky_sun_light: out is NULL");
+    double T[3];
+    sky_sun_transmittance(plan, 256, T);  // (0 when the sun is below the observer's geometric horizon)
+    *out = nx_analytic_light();
+    out->type = NX_ALIGHT_DIRECTIONAL;
+    out->angularRadius = sky->sunAngularRadius;
+    out->intensity = 1.0f;
+    for (int ch = 0; ch < 3; ch++) {
+        out->direction[ch] = (float)-plan.sun[ch];
+        out->colour[ch] = (float)((double)sky->sunIrradiance[ch] * T[ch]);
+    }
+    return NXHIP_OK;
+} NX_CATCH("nxhip_sky_sun_light")
+
+// The sky as a float map: generated on the device into a new texel buffer (nx_sky.hip), then installed as nxhip_upload_env_float installs
+// its own — the same steps in the same order, so that lookup, sampler and tables cannot tell the two apart.
+int nxhip_set_sky(nxhip_ctx* c, const nx_sky* sky)
+try {
+    NX_CHECK_CTX(c);
+    SkyPlan plan;
+    NX_TRY(sky_plan(sky, "nxhip_set_sky", &plan));  // before anything is allocated
+    SkyDisc disc;
+    if (sky->sunDisc) NX_TRY(sky_disc_plan(sky, plan, "nxhip_set_sky", &disc));
+    NX_HIP(hipSetDevice(c->device));
+    TextureHost t;
+    t.width = sky->width;
+    t.height = sky->height;
+    NX_ALLOC(t.texels, (size_t)sky->width * sky->height * sizeof(float4));
+    const bool timing = env_timing();
+    struct Events {  // (destroyed on every way out)
+        hipEvent_t t0 = nullptr, t1 = nullptr;
+        ~Events()
+        {
+            if (t0) (void)hipEventDestroy(t0);
+            if (t1) (void)hipEventDestroy(t1);
+        }
+    } ev;
+    if (timing) {
+        NX_HIP(hipEventCreate(&ev.t0));
+        NX_HIP(hipEventCreate(&ev.t1));
+        NX_HIP(hipEventRecord(ev.t0, c->stream));
+    }
+    NX_TRY(sky_generate(c->stream, plan, sky->sunDisc ? &disc : nullptr, t.texels.as<float4>(), sky->width, sky->height));
+    if (timing) NX_HIP(hipEventRecord(ev.t1, c->stream));
+    NX_SYNC_ALL(c);  // the new texels are complete and nothing reads the old map any more
+    if (timing) {
+        float ms = 0.0f;
+        NX_HIP(hipEventElapsedTime(&ms, ev.t0, ev.t1));
+        std::fprintf(stderr, "[sky] device build %u x %u, steps %u x %u%s: %.3f ms (events around the launches)\n", sky->width, sky->height, sky->viewSteps, sky->lightSteps,
+                     sky->sunDisc ? ", disc" : "", ms);
+    }
+    c->hdrMap = std::move(t);
+    c->hdrFloat = true;
+    c->hostHdr.clear();
+    NX_TRY(refresh_texture_tables(c));
+    return build_env_tables(c);  // a new map under an enabled sampler gets new tables
+} NX_CATCH("nxhip_set_sky")
+
 int nxhip_clear_textures(nxhip_ctx* c)
 try {
     NX_CHECK_CTX(c);

@@ -215,13 +215,15 @@ void PathTracer::UpdateDeviceScene(const Scene& scene)
         for (const Texture& t : assets.GetEmissiveMaps()) Check(nxhip_upload_texture(m_Ctx, 1, t.pixels.data(), t.width, t.height, nullptr), "nxhip_upload_texture");
         for (const Texture& t : assets.GetNormalMaps()) Check(nxhip_upload_texture(m_Ctx, 3, t.pixels.data(), t.width, t.height, nullptr), "nxhip_upload_texture");
         for (const Texture& t : assets.GetRoughnessMaps()) Check(nxhip_upload_texture(m_Ctx, 4, t.pixels.data(), t.width, t.height, nullptr), "nxhip_upload_texture");
-        if (!scene.GetHDRMapFloat().pixels.empty()) Check(nxhip_upload_env_float(m_Ctx, scene.GetHDRMapFloat().pixels.data(), scene.GetHDRMapFloat().width, scene.GetHDRMapFloat().height), "nxhip_upload_env_float");
+        if (scene.GetSky()) Check(nxhip_set_sky(m_Ctx, scene.GetSky()), "nxhip_set_sky");
+        else if (!scene.GetHDRMapFloat().pixels.empty()) Check(nxhip_upload_env_float(m_Ctx, scene.GetHDRMapFloat().pixels.data(), scene.GetHDRMapFloat().width, scene.GetHDRMapFloat().height), "nxhip_upload_env_float");
         else if (!scene.GetHDRMap().pixels.empty()) Check(nxhip_upload_texture(m_Ctx, 2, scene.GetHDRMap().pixels.data(), scene.GetHDRMap().width, scene.GetHDRMap().height, nullptr), "nxhip_upload_texture");
         mutableAssets.texturesDirty = false;
         scene.hdrDirty = false;
     } else if (scene.hdrDirty) {
-        // whichever kind the scene holds (Scene::AddHDRMap / AddHDRMapFloat: the one replaces the other, here and on the device)
-        if (!scene.GetHDRMapFloat().pixels.empty()) Check(nxhip_upload_env_float(m_Ctx, scene.GetHDRMapFloat().pixels.data(), scene.GetHDRMapFloat().width, scene.GetHDRMapFloat().height), "nxhip_upload_env_float");
+        // whichever kind the scene holds (Scene::SetSky / AddHDRMap / AddHDRMapFloat: the one replaces the other, here and on the device)
+        if (scene.GetSky()) Check(nxhip_set_sky(m_Ctx, scene.GetSky()), "nxhip_set_sky");
+        else if (!scene.GetHDRMapFloat().pixels.empty()) Check(nxhip_upload_env_float(m_Ctx, scene.GetHDRMapFloat().pixels.data(), scene.GetHDRMapFloat().width, scene.GetHDRMapFloat().height), "nxhip_upload_env_float");
         else Check(nxhip_upload_texture(m_Ctx, 2, scene.GetHDRMap().pixels.data(), scene.GetHDRMap().width, scene.GetHDRMap().height, nullptr), "nxhip_upload_texture");
         scene.hdrDirty = false;
     }

@@ -332,10 +332,28 @@ std::vector<float> Scene::MorphWeights(uint32_t meshId, int animationIdx, double
     return morph.weights;
 }
 
+void Scene::SetSky(const nx_sky& sky)
+{
+    m_Sky = sky;
+    m_HasSky = true;
+    m_HdrMap = Texture();
+    m_HdrMapFloat = FloatImage();
+    hdrDirty = true;
+}
+
+void Scene::ClearSky()
+{
+    if (!m_HasSky) return;
+    m_HasSky = false;
+    m_AssetManager.texturesDirty = true;  // (only nxhip_clear_textures removes an environment: the textures go up again, without one)
+    hdrDirty = true;
+}
+
 void Scene::AddHDRMap(const Texture& texture)
 {
     m_HdrMap = texture;
     m_HdrMapFloat = FloatImage();
+    m_HasSky = false;
     hdrDirty = true;
 }
 
@@ -346,6 +364,7 @@ void Scene::AddHDRMapFloat(uint32_t width, uint32_t height, const float* rgb)
     m_HdrMapFloat.height = height;
     m_HdrMapFloat.pixels.assign(rgb, rgb + static_cast<size_t>(width) * height * 3);
     m_HdrMap = Texture();
+    m_HasSky = false;
     hdrDirty = true;
 }
 

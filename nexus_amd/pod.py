@@ -93,6 +93,11 @@ MORPH_MAX_TARGETS = 1024
 MEDIUM_DT = np.dtype([("boxMin", "<f4", 3), ("sigmaT", "<f4"), ("boxMax", "<f4", 3), ("g", "<f4"), ("albedo", "<f4", 3), ("pad", "<u4")])
 assert MEDIUM_DT.itemsize == 48
 
+# nx_sky (extension, nxhip_set_sky): 76 bytes — the procedural sun-and-sky environment (the model is in include/nexus_hip.h)
+SKY_DT = np.dtype([("sunDirection", "<f4", 3), ("sunAngularRadius", "<f4"), ("sunIrradiance", "<f4", 3), ("altitude", "<f4"), ("rayleighScale", "<f4"), ("mieScale", "<f4"),
+                   ("mieG", "<f4"), ("groundAlbedo", "<f4", 3), ("width", "<u4"), ("height", "<u4"), ("viewSteps", "<u4"), ("lightSteps", "<u4"), ("sunDisc", "<u4")])
+assert SKY_DT.itemsize == 76
+
 CAM_DT = np.dtype(
     {
         "names": ["position", "right", "up", "lensRadius", "lowerLeftCorner", "viewportX", "viewportY", "resolution"],
@@ -271,3 +276,16 @@ def make_medium(box_min=(0, 0, 0), box_max=(1, 1, 1), sigma_t=0.0, g=0.0, albedo
     m = np.zeros((), dtype=MEDIUM_DT)
     m["boxMin"], m["boxMax"], m["sigmaT"], m["g"], m["albedo"] = box_min, box_max, sigma_t, g, albedo
     return m
+
+
+def Sky(**fields):
+    """one nx_sky: the values of nxhip_sky_defaults (sun at 45 degrees elevation along +x, 2048 x 1024, steps 64 / 16, no disc) with
+    `fields` (names of SKY_DT) replacing them"""
+    s = np.zeros((), dtype=SKY_DT)
+    s["sunDirection"] = (np.sqrt(0.5), np.sqrt(0.5), 0.0)
+    s["sunAngularRadius"], s["sunIrradiance"], s["altitude"] = 0.004675, 1.0, 1.0
+    s["rayleighScale"], s["mieScale"], s["mieG"], s["groundAlbedo"] = 1.0, 1.0, 0.8, 0.3
+    s["width"], s["height"], s["viewSteps"], s["lightSteps"], s["sunDisc"] = 2048, 1024, 64, 16, 0
+    for name, value in fields.items():
+        s[name] = value  # (a name SKY_DT does not have is numpy's ValueError)
+    return s
